@@ -13,6 +13,11 @@ decode have no data-path collective, ranks only meet at the timin
 child process, before anything touches the GPU, and exits with its code; with a torchrun environment whose WORLD_SIZE is
 not N it exits non-zero.  The line it prints always says how many ranks actually ran (`n_gpus`).
 
+`--dump-outputs DIR` writes what the last timed step returned (rank 0: the final fit loss and the decoded fields) as
+DIR/<name>.npy in float32, so that two builds can be compared output for output: every input of the step is seeded, so
+the same arguments give the same inputs on every run.  The outputs themselves agree between runs to the kernels' rounding,
+not bit for bit: the backward and the loss sum with float atomics.
+
 Prints ONE JSON line (rank 0).  Extra objects:
   roofline         : the kernel the step spends most of its time in, timed alone with events on its launch stream:
                      achieved = algorithmic (as-written) FLOPs of SURVEY.md 8a / 8d per launch / average launch time
@@ -226,6 +231,22 @@ def decode_step(c, m, dcoords, lat):
 def step(c, m, coords, dcoords, img):
     loss, lat = fit(m, coords, img)
     return loss, decode_step(c, m, dcoords, lat)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, recon):
+    """--dump-outputs: the arrays one step hands its caller, as DIR/loss.npy (the final fit loss) and DIR/recon.npy (the
+    decoded fields, (B * frames, N_decode, O)), float32 as the step computes them.  Every config's outputs fit the limit."""
+    import numpy as np
+    arrs = {"loss": loss.detach().float().cpu().numpy(), "recon": recon.detach().float().cpu().numpy()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def points_per_signal(c):
@@ -655,7 +676,11 @@ def main():
     ap.add_argument("--roofline-only", action="store_true",
                     help="run ONLY the per-kernel legs and print them (for rocprofv3 --kernel-trace --stats: the profile then "
                          "holds exactly the launches the legs time, so its per-kernel averages are the legs' launch_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0: loss, recon) to DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     ensure_world(args)
 
     from enf_pde_amd.fitting import init_distributed
@@ -695,6 +720,8 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize(device)
     dt = _max_over_ranks(time.perf_counter() - t0, device, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, recon)
 
     pts_per_step = world * c["B"] * points_per_signal(c)
     ms_per_step = dt / args.steps * 1e3

@@ -440,6 +440,14 @@ def test_bench_refuses_a_world_that_is_not_gpus():
         assert r.returncode == 2 and "GPU(s)" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_refuses_fewer_than_one_step():
+    """--steps is the number of timed steps that ms_per_step averages over: 0 is refused before anything runs."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+
 def test_bench_configs_cover_baseline_json():
     import json
     import bench
