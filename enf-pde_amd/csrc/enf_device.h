@@ -40,9 +40,6 @@ struct Frags {
 // (`f[j] = (__bf16)x`) hipcc keeps the packed conversion only where nothing touches the halves afterwards; in front of relu_frags'
 // 16-bit integer maximum it converted every value alone (the second operand a zero) and merged the halves with v_perm_b32: three
 // instructions per pair (K2's z loop: 64 of 1,150 vector instructions)
-#ifndef ENF_CVT_PK2
-#define ENF_CVT_PK2 1
-#endif
 typedef float f32x2_cvt __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_cvt __attribute__((ext_vector_type(2)));
 DEV unsigned bf16_pack2(float a, float b) {
@@ -53,14 +50,9 @@ DEV void make_frags(Frags<BF16, KB>& F, const f32x4 (&X)[2 * KB]) {
 #pragma unroll
   for (int blk = 0; blk < KB; ++blk) {
     if constexpr (BF16) {
-#if ENF_CVT_PK2
       const u32x4 w = {bf16_pack2(X[2 * blk][0], X[2 * blk][1]), bf16_pack2(X[2 * blk][2], X[2 * blk][3]),
                        bf16_pack2(X[2 * blk + 1][0], X[2 * blk + 1][1]), bf16_pack2(X[2 * blk + 1][2], X[2 * blk + 1][3])};
       F.f[blk] = __builtin_bit_cast(bf16x8, w);
-#else
-#pragma unroll
-      for (int j = 0; j < 8; ++j) F.f[blk][j] = (__bf16)X[2 * blk + (j >> 2)][j & 3];
-#endif
     } else {
       F.f[2 * blk] = X[2 * blk];
       F.f[2 * blk + 1] = X[2 * blk + 1];
@@ -68,19 +60,7 @@ DEV void make_frags(Frags<BF16, KB>& F, const f32x4 (&X)[2 * KB]) {
   }
 }
 
-#ifndef ENF_ASM_LITE
-#define ENF_ASM_LITE 0       // 1: asm GEMM stages keep 4 instead of 8 fragment reads in flight (register-starved kernels)
-#endif
-#ifndef ENF_GELU_PK
-#define ENF_GELU_PK 1
-#endif
-#ifndef ENF_GELU_POLY
-#define ENF_GELU_POLY 0
-#endif
 #include "enf_gemm_asm.h"
-#ifndef ENF_ASM_GEMM
-#define ENF_ASM_GEMM 1
-#endif
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // A tile array parked in half the registers between two uses (bf16 mode: the same packing as a fragment
@@ -158,9 +138,9 @@ DEV size_t relu_mask_index(int b, int Z, int z, int ntiles, int tile, int layer,
 enum { INIT_ACC = 0, INIT_ZERO = 1, INIT_BIAS = 2 };
 template <bool BF16, int KB, int MTS, int INIT = INIT_ACC>
 DEV void gemm_stage(f32x4* acc, const Frags<BF16, KB>& F, const char* lds, int lane, const float* bias = nullptr) {
-  if constexpr (BF16 && ENF_ASM_GEMM && GemmStageAsm<KB, MTS, ENF_ASM_LITE != 0>::available) {
+  if constexpr (BF16 && GemmStageAsm<KB, MTS>::available) {
     // hand-scheduled stage: NBUF fragment reads in flight, MFMAs round-robin over the accumulators
-    using G = GemmStageAsm<KB, MTS, ENF_ASM_LITE != 0>;
+    using G = GemmStageAsm<KB, MTS>;
     const unsigned a = (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<char*>(lds) + (lane << 4));
     if constexpr (INIT == INIT_ZERO) G::run_zero(acc, F.f, a);
     else if constexpr (INIT == INIT_BIAS) G::run_bias(acc, F.f, a, (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<float*>(bias) + 4 * (lane >> 4)));
@@ -224,36 +204,18 @@ DEV f32x4 rowvec(const float* vec, int tile, int quad) {
 }
 
 // sum over the four quads of a column (they hold disjoint feature rows)
-#ifndef ENF_XQ_SWAP
-#define ENF_XQ_SWAP 1
-#endif
 // sum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (the quads of a 16-column tile), result in all four.
-// ENF_XQ_SWAP: with gfx950's lane-swap instructions (pure VALU: v_permlane32_swap gives [a.lo | b.lo], [a.hi | b.hi],
+// With gfx950's lane-swap instructions (pure VALU: v_permlane32_swap gives [a.lo | b.lo], [a.hi | b.hi],
 // v_permlane16_swap exchanges the odd 16-lane rows of one operand with the even rows of the other) instead of two
 // ds_bpermute_b32 round trips through the LDS crossbar (scripts/ubench/permlane_sum.hip: 112 vs 172 ticks per dependent sum).
 // Inline asm -- the builtin loses its second result in hipcc 7.2 --, with the two wait states a VALU-written operand needs.
 DEV float xquad_sum(float v) {
-#if ENF_XQ_SWAP
   float a = v, b = v;
-#ifndef ENF_XQ_NOP_AFTER
-#define ENF_XQ_NOP_AFTER 0
-#endif
-#if ENF_XQ_NOP_AFTER
-  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  const float s = a + b;
-  float c = s, d = s;
-  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(c), "+v"(d));
-#else
   asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
   const float s = a + b;
   float c = s, d = s;
   asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-#endif
   return c + d;
-#else
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-#endif
 }
 
 // ------------------------------------------------------------------ math
@@ -277,46 +239,16 @@ DEV f32x2 gelu_f2(f32x2 x) {
   s[1] = __builtin_amdgcn_rcpf(e[1]);
   return x * s;
 }
-// Transcendental-free alternative (off: ENF_GELU_POLY=0).  gelu_tanh(x) = x (0.5 + f(x)), f = 0.5 tanh(..) is odd
-// and saturates: f(x) ~ xc Q(xc^2), xc = clamp(x, -4, 4), Q of degree 6 (Lawson/minimax fit, max |error| 2.8e-4).
-// Measured on gfx950 (scripts/ubench/valu_rates.hip, per SIMD with two waves, v_fma_f32 = 1): v_pk_fma/mul_f32
-// 1.73, v_exp/v_rcp/v_sin 2.5, v_med3 1.33 -- so 2 med3 + 9 packed ops per value pair cost what 4 transcendentals
-// + 5 packed ops do: no gain, and the exact form is kept.
-DEV f32x2 gelu_poly2(f32x2 x) {
-  f32x2 xc;
-  xc[0] = __builtin_amdgcn_fmed3f(x[0], -4.0f, 4.0f);
-  xc[1] = __builtin_amdgcn_fmed3f(x[1], -4.0f, 4.0f);
-  const f32x2 s = xc * xc;
-  f32x2 q = s * 2.394300707e-08f + -1.664713792e-06f;
-  q = q * s + 4.940474534e-05f;
-  q = q * s + -8.289572461e-04f;
-  q = q * s + 8.840011712e-03f;
-  q = q * s + -6.464239978e-02f;
-  q = q * s + 3.977454025e-01f;
-  return x * (xc * q + 0.5f);
-}
-template <int NT, bool FAST = false> DEV void gelu_tiles(f32x4 (&X)[NT]) {
+// (a transcendental-free polynomial form costs as much on gfx950: scripts/ubench/valu_rates.hip)
+template <int NT> DEV void gelu_tiles(f32x4 (&X)[NT]) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    if constexpr (FAST && ENF_GELU_POLY) {
-      const f32x2 lo = gelu_poly2(f32x2{X[t][0], X[t][1]}), hi = gelu_poly2(f32x2{X[t][2], X[t][3]});
-      X[t] = f32x4{lo[0], lo[1], hi[0], hi[1]};
-      continue;
-    }
-#if ENF_GELU_PK
     const f32x2 lo = gelu_f2(f32x2{X[t][0], X[t][1]}), hi = gelu_f2(f32x2{X[t][2], X[t][3]});
     X[t] = f32x4{lo[0], lo[1], hi[0], hi[1]};
-#else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) X[t][i] = gelu_f(X[t][i]);
-#endif
   }
 }
 DEV f32x2 lo2(const f32x4& x) { return __builtin_shufflevector(x, x, 0, 1); }
 DEV f32x2 hi2(const f32x4& x) { return __builtin_shufflevector(x, x, 2, 3); }
-#ifndef ENF_GELU_DG_FMA
-#define ENF_GELU_DG_FMA 1
-#endif
 // gelu and its derivative from ONE exp + rcp (the backward kernel needs both for the same pre-activation):
 // X <- gelu(X), G <- gelu'(X), two values per instruction where the ISA has a packed form
 DEV void gelu_fg2(f32x2 x, f32x2& g, f32x2& dg) {
@@ -332,11 +264,7 @@ DEV void gelu_fg2(f32x2 x, f32x2& g, f32x2& dg) {
   s[0] = __builtin_amdgcn_rcpf(e[0]);
   s[1] = __builtin_amdgcn_rcpf(e[1]);
   g = x * s;
-#if ENF_GELU_DG_FMA
   dg = (g - g * s) * (x2 * (6.0f * c * 0.044715f) + 2.0f * c) + s;       // (g - g s: ONE packed fma; 1 - s would be two scalar subtractions)
-#else
-  dg = g * (1.0f - s) * (x2 * (6.0f * c * 0.044715f) + 2.0f * c) + s;
-#endif
 }
 // the same one value at a time (no register-pair constraints for the allocator: the packed form spills in K3)
 DEV void gelu_fg1(float x, float& g, float& dg) {
@@ -355,17 +283,6 @@ DEV void gelu_fg_tile(f32x4& x, f32x4& g) {
   gelu_fg2(hi2(x), g1, d1);
   g = f32x4{g0[0], g0[1], g1[0], g1[1]};
   x = f32x4{d0[0], d0[1], d1[0], d1[1]};
-}
-// in place: X <- gelu(X), returns gelu'(X) in G
-template <int NT> DEV void gelu_fg_tiles(f32x4 (&X)[NT], f32x4 (&G)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    f32x2 g0, d0, g1, d1;
-    gelu_fg2(f32x2{X[t][0], X[t][1]}, g0, d0);
-    gelu_fg2(f32x2{X[t][2], X[t][3]}, g1, d1);
-    X[t] = f32x4{g0[0], g0[1], g1[0], g1[1]};
-    G[t] = f32x4{d0[0], d0[1], d1[0], d1[1]};
-  }
 }
 // d/dx of the above: s + x s (1-s) 2c(1+3*0.044715x^2),  s = sigmoid(2c(x+0.044715x^3))
 DEV float gelu_grad_f(float x) {
@@ -400,9 +317,6 @@ DEV __amdgpu_buffer_rsrc_t make_blob_rsrc(const char* blob, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(blob), 0, bytes, 0x00020000);
 }
 
-#ifndef ENF_STAGE_CONTIG
-#define ENF_STAGE_CONTIG 1
-#endif
 // pieces I .. PPW-1 of a wave's run (the offset field wants a constant: unrolled by recursion)
 template <int BYTES, bool FULL, int I, int PPW>
 DEV void stage_pieces(__amdgpu_buffer_rsrc_t rs, lds_ptr_t dst, int voff, unsigned soff, int base) {
@@ -415,7 +329,6 @@ template <int BYTES, int NW = NWAVES>
 DEV void stage_issue(__amdgpu_buffer_rsrc_t rs, unsigned src_off, char* dst, int wave, int lane) {
   static_assert(BYTES % 1024 == 0 && BYTES <= STAGE_MAX, "stage size");
   constexpr int PIECES = BYTES / 1024;                  // 1 KB per wave-instruction
-#if ENF_STAGE_CONTIG
   // a wave copies PPW CONSECUTIVE kilobytes: the piece index then fits the instruction's 12-bit offset field (which moves the source and
   // the LDS side alike), so a stage needs ONE scalar source offset and ONE M0 value per wave.  With the pieces interleaved over the waves
   // (8 KB apart) every piece had its own pair, hipcc hoisted all of them out of the tile loop and spilled them: ~60 v_readlane_b32 per
@@ -423,28 +336,16 @@ DEV void stage_issue(__amdgpu_buffer_rsrc_t rs, unsigned src_off, char* dst, int
   constexpr int PPW = (PIECES + NW - 1) / NW;
   const int base = wave * (PPW * 1024);
   stage_pieces<BYTES, PIECES % NW == 0, 0, PPW>(rs, (lds_ptr_t)(dst + base), lane * 16, src_off + base, base);
-#else
-#pragma unroll
-  for (int i = 0; i < (PIECES + NW - 1) / NW; ++i) {
-    const int piece = (i * NW + wave) * 1024;
-    if (PIECES % NW == 0 || piece < BYTES)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(dst + piece), 16, lane * 16, src_off + piece, 0, 0);
-  }
-#endif
 }
 DEV void stage_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Panel = (MTOUT out-tiles of 16 rows) x (KBIN in-blocks of 32) of A-operand fragments, streamed
 // through a 2-slot LDS ring (slot stride STAGE_MAX) in stages of MTS out-tiles.
-// `early` (wave-uniform; opt-in through first_stage<.., ANTI = true>): the upper half of the workgroup's
-// waves -- the SIMD-mates of the lower half -- take each stage's barrier BEFORE its MFMAs instead of
-// after them.  Every wave still meets every barrier and reads a ring slot only inside that slot's
-// window, but inside a window one wave of a SIMD runs [MFMA, epilogue] while its mate runs
-// [epilogue, MFMA]: the matrix pipe and the vector ALU work at the same time instead of in turns.
-// A kernel that opts in must end its stage sequence with pipe_finish().
 // Stage offsets with STAGE_RS2 set address the second buffer resource `rs2` (the per-latent panels of the
 // z-fold forward path) instead of the weight blob `rs`; a kernel without one sets rs2 = rs.
 constexpr unsigned STAGE_RS2 = 0x80000000u;
+// `early` is always false since the antiphase staging was removed.  The field and its checks in stage_open /
+// stage_close / pipe_finish stay: without them hipcc allocates the registers of the tail and K3 differently.
 struct Pipe { __amdgpu_buffer_rsrc_t rs, rs2; int cur; int wave; bool early; };
 template <int BYTES, int NW = NWAVES>
 DEV void stage_issue_p(const Pipe& P, unsigned src_off, char* dst, int lane) {
@@ -536,12 +437,12 @@ DEV void panel_gemm_flip(f32x4 (&acc)[TRANS ? MTOUT : 1], const Frags<BF16, KBIN
     else if (sp + 1 < C::SPP) stage_issue_p<C::STAGE, NW>(P, panel + (sp + 1) * C::STAGE, ring + (P.cur ^ 1) * STAGE_MAX, lane);
     else if (next != NO_STAGE) stage_issue_p<NEXT_BYTES, NW>(P, next, ring + (P.cur ^ 1) * STAGE_MAX, lane);
     const char* slot = ring + P.cur * STAGE_MAX;
-    if constexpr (TRANS && BF16 && ENF_ASM_GEMM && GemmStageAsm<KBIN, C::MTS, ENF_ASM_LITE != 0>::available) {
+    if constexpr (TRANS && BF16 && GemmStageAsm<KBIN, C::MTS>::available) {
       // one fragment read feeds both products (hand-scheduled stage, enf_gemm_asm.h)
       f32x4 af[C::MTS];
 #pragma unroll
       for (int mt = 0; mt < C::MTS; ++mt) af[mt] = flip_init(sp * C::MTS + mt);
-      using G = GemmStageAsm<KBIN, C::MTS, ENF_ASM_LITE != 0>;
+      using G = GemmStageAsm<KBIN, C::MTS>;
       const unsigned a = (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<char*>(slot) + (lane << 4));
       if constexpr (INIT == INIT_ZERO) G::run_both_zero(&acc[sp * C::MTS], af, F.f, a);
       else if constexpr (INIT == INIT_BIAS)
@@ -549,9 +450,9 @@ DEV void panel_gemm_flip(f32x4 (&acc)[TRANS ? MTOUT : 1], const Frags<BF16, KBIN
       else G::run_both(&acc[sp * C::MTS], af, F.f, a);
 #pragma unroll
       for (int mt = 0; mt < C::MTS; ++mt) flip(sp * C::MTS + mt, af[mt]);
-    } else if constexpr (!TRANS && BF16 && ENF_ASM_GEMM && GemmStageAsm<KBIN, C::MTS, ENF_ASM_LITE != 0>::available) {
+    } else if constexpr (!TRANS && BF16 && GemmStageAsm<KBIN, C::MTS>::available) {
       // flipped product only
-      using G = GemmStageAsm<KBIN, C::MTS, ENF_ASM_LITE != 0>;
+      using G = GemmStageAsm<KBIN, C::MTS>;
       const unsigned a = (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<char*>(slot) + (lane << 4));
       f32x4 af[C::MTS];
       if constexpr (INIT == INIT_ZERO) {
@@ -578,67 +479,20 @@ DEV void panel_gemm_flip(f32x4 (&acc)[TRANS ? MTOUT : 1], const Frags<BF16, KBIN
 }
 
 
-// ---- "A3": antiphase over a THREE-slot ring (single-stage panels).  The upper half of the workgroup's waves -- the SIMD-mates of
-// the lower half -- take each stage's barrier BEFORE its MFMAs, the lower half after them, so that on every SIMD one wave multiplies
-// while the other runs its vector epilogue.  Barrier b (the same instance for all waves) therefore completes when the late waves
-// have finished G_b and the early ones V_{b-1}: slot b % 3 is still being read by the early waves, panel b + 1 must be (and is:
-// issued behind barrier b - 1, waited for by every wave before it arrives) resident for the late waves' next G, and slot
-// (b + 2) % 3 -- last read for G_{b-1}, which every wave has behind it -- is free: panel b + 2 is issued into it behind the barrier.
-// Two slots cannot do this (the refill of a slot would race the early waves' reads of it); both halves meet every barrier once.
-template <int BYTES0, int BYTES1, int NW = NWAVES>
-DEV void first_stage_a3(Pipe& P, char* ring, unsigned panel0, unsigned panel1, int wave, int lane) {
-  P.cur = 0;
-  P.wave = __builtin_amdgcn_readfirstlane(wave);
-  P.early = P.wave >= NW / 2;
-  stage_issue_p<BYTES0, NW>(P, panel0, ring, lane);
-  stage_issue_p<BYTES1, NW>(P, panel1, ring + STAGE_MAX, lane);
-  stage_wait();
-  __syncthreads();
-}
-template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES, int NW = NWAVES, int INIT = INIT_ACC>
-DEV void panel_gemm_a3(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned next2, bool active, int lane,
-                       const float* bias = nullptr) {
-  using C = PanelCfg<KBIN, MTOUT, BF16>;
-  static_assert(C::SPP == 1, "A3 staging: single-stage panels");
-  char* refill = ring + ((P.cur + 2) % 3) * STAGE_MAX;
-  if (P.early) {
-    stage_wait();
-    __syncthreads();
-    if (next2 != NO_STAGE) stage_issue_p<NEXT_BYTES, NW>(P, next2, refill, lane);
-  }
-  if (active) gemm_stage<BF16, KBIN, C::MTS, INIT>(acc, F, ring + P.cur * STAGE_MAX, lane, bias);
-  else if constexpr (INIT != INIT_ACC) {
-#pragma unroll
-    for (int mt = 0; mt < C::MTS; ++mt)
-      acc[mt] = INIT == INIT_BIAS ? *reinterpret_cast<const f32x4*>(bias + 16 * mt + 4 * (lane >> 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  if (!P.early) {
-    stage_wait();
-    __syncthreads();
-    if (next2 != NO_STAGE) stage_issue_p<NEXT_BYTES, NW>(P, next2, refill, lane);
-  }
-  P.cur = (P.cur + 1) % 3;
-}
-
-template <int BYTES, int NW = NWAVES, bool ANTI = false>
+template <int BYTES, int NW = NWAVES>
 DEV void first_stage(Pipe& P, char* ring, unsigned panel, int wave, int lane) {
   P.cur = 0;
   P.wave = __builtin_amdgcn_readfirstlane(wave);
-  P.early = ANTI && P.wave >= NW / 2;
+  P.early = false;
   stage_issue_p<BYTES, NW>(P, panel, ring, lane);
-  if constexpr (ANTI) __syncthreads();      // publishes the kernel's LDS constants to the early waves
   if (!P.early) { stage_wait(); __syncthreads(); }
 }
 
 // Per-lane sums over a lane's NT x 4 values, two at a time: even / odd running sums in one register pair each, so a sum costs one
 // v_pk_add_f32 / v_pk_fma_f32 per TWO elements (plain operands: no op_sel, no neg).  Written with a single accumulator the additions are a
 // serial chain the compiler may not reassociate: 64 vector instructions per LayerNorm instead of 34 -- 6 % of K3's, 8 % of K2's.
-#ifndef ENF_PK_SUMS
-#define ENF_PK_SUMS 1
-#endif
 // s = sum x, q = sum x^2
 template <int NT> DEV void tiles_sum_sq(const f32x4 (&X)[NT], float& s, float& q) {
-#if ENF_PK_SUMS
   f32x2 s2 = {0.f, 0.f}, q2 = {0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -647,17 +501,9 @@ template <int NT> DEV void tiles_sum_sq(const f32x4 (&X)[NT], float& s, float& q
     s2 += b; q2 = __builtin_elementwise_fma(b, b, q2);
   }
   s = s2[0] + s2[1]; q = q2[0] + q2[1];
-#else
-  s = 0.f; q = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { s += X[t][i]; q = fmaf(X[t][i], X[t][i], q); }
-#endif
 }
 // s = sum a, d = sum a b      (`get(t)` yields tile t of b: a register array or parked fragments)
 template <int NT, typename GetB> DEV void tiles_sum_dot(const f32x4 (&A)[NT], GetB get, float& s, float& d) {
-#if ENF_PK_SUMS
   f32x2 s2 = {0.f, 0.f}, d2 = {0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -666,20 +512,10 @@ template <int NT, typename GetB> DEV void tiles_sum_dot(const f32x4 (&A)[NT], Ge
     s2 += hi2(A[t]); d2 = __builtin_elementwise_fma(hi2(A[t]), hi2(bt), d2);
   }
   s = s2[0] + s2[1]; d = d2[0] + d2[1];
-#else
-  s = 0.f; d = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const f32x4 bt = get(t);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { s += A[t][i]; d = fmaf(A[t][i], bt[i], d); }
-  }
-#endif
 }
 
 // d = sum a b
 template <int NT, typename GetA, typename GetB> DEV float tiles_dot(GetA geta, GetB getb) {
-#if ENF_PK_SUMS
   f32x2 d2 = {0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -688,16 +524,6 @@ template <int NT, typename GetA, typename GetB> DEV float tiles_dot(GetA geta, G
     d2 = __builtin_elementwise_fma(hi2(at), hi2(bt), d2);
   }
   return d2[0] + d2[1];
-#else
-  float d = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const f32x4 at = geta(t), bt = getb(t);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d = fmaf(at[i], bt[i], d);
-  }
-  return d;
-#endif
 }
 
 // LayerNorm statistics over the NT*16 features of this lane's column: biased variance, eps 1e-6,
@@ -717,17 +543,8 @@ template <int NT> DEV void ln_stats(const f32x4 (&X)[NT], float& mu, float& rstd
 // particular state: the long-standing "K3 run-to-run deviations" (scripts/k3_race/store_probe.py finds it in
 // seconds, 47 of 47 events with this signature, 0 in 4000 runs of a build without SLP packing).  The asm is opaque to the
 // vectoriser; the leading s_nop covers a transcendental producer (v_rsq_f32) the compiler cannot see being consumed here.
-#ifndef ENF_LN_APPLY_ASM
-#define ENF_LN_APPLY_ASM 2
-#endif
-#ifdef ENF_LN_FORM           // investigation builds: one explicit packed-operand form (scripts/k3_race/ln_forms.h)
-#include "../../scripts/k3_race/ln_forms.h"
-#endif
 template <int NT> DEV void ln_apply(f32x4 (&X)[NT], float mu, float rstd) {
-#ifdef ENF_LN_FORM
-  ln_apply_form<NT>(X, mu, rstd);
-#elif ENF_LN_APPLY_ASM == 2
-  // as below, with the wait states where the hazards are instead of one s_nop per element: ONE in front (rstd comes out of
+  // the wait states sit where the hazards are, not one s_nop per element: ONE in front (rstd comes out of
   // v_rsq_f32, and a transcendental's result needs a wait state before a VALU read the compiler cannot see), and the two of
   // VALU -> MFMA operand behind the LAST fma, tied to every tile by data dependence (an asm without operands orders only
   // against other volatile asm: a compiler-scheduled MFMA reading X -- fp32 mode, where the fragments ARE these registers --
@@ -751,26 +568,6 @@ template <int NT> DEV void ln_apply(f32x4 (&X)[NT], float mu, float rstd) {
     asm volatile("s_nop 1" : "+v"(X[0]), "+v"(X[1]), "+v"(X[2]), "+v"(X[3]), "+v"(X[4]), "+v"(X[5]), "+v"(X[6]), "+v"(X[7]),
                  "+v"(X[8]), "+v"(X[9]), "+v"(X[10]), "+v"(X[11]), "+v"(X[12]), "+v"(X[13]), "+v"(X[14]), "+v"(X[15]));
   }
-#elif ENF_LN_APPLY_ASM
-  const float nmr = -mu * rstd;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float y;
-      asm volatile("s_nop 0\n\tv_fma_f32 %0, %1, %2, %3" : "=v"(y) : "v"(X[t][i]), "v"(rstd), "v"(nmr));
-      X[t][i] = y;
-    }
-  // the results may feed a compiler-scheduled MFMA directly (fp32 mode: the fragments ARE these registers), and the compiler
-  // does not know a vector instruction wrote them: the two wait states of VALU -> MFMA operand (scripts/ubench), behind the
-  // last fma (volatile statements keep their order)
-  asm volatile("s_nop 1");
-#else
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) X[t][i] = (X[t][i] - mu) * rstd;
-#endif
 }
 
 // ------------------------------------------------------------------ invariants + window

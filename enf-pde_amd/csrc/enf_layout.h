@@ -195,8 +195,7 @@ ENF_HD inline int enf_lt_off_c(int H, int D) { return 2 * H * D + 8; }
 // sits between them), built by enf_wz_kernel into `wz` before the pair kernel runs.  It needs
 // enough 128-query workgroups to fill the chip; below that the latent-split variant runs.
 // EnfDesc.pair_fwd_variant forces the choice per call; ENF_VARIANT_AUTO is the heuristic below, a function of the shape
-// alone (only an -DENF_AB_SWITCHES build of the library lets ENF_ZFOLD=0 / 1 in the environment replace it).
-int enf_zfold_env(int backward);   // enf_api.hip: -1 (always, in the product library), 0 / 1
+// alone.
 // The z-fold kernel's work below 192 query tiles (ENF_VARIANT_ZFOLD_ZSPLIT), "stream-K" over the latents: the flattened
 // (signal, 128-query tile, latent) space -- tiles x Z latent steps -- is cut into <= 256 runs of `len` steps, one workgroup each, so a
 // single round of workgroups ends together whatever the tile count (144 tiles x 128 latents: 256 runs of 72 -- 0.56 of the unsplit time;
@@ -208,9 +207,6 @@ inline EnfStreamK enf_streamk(long long tiles, int Z, int len_min) {
   const long long total = tiles * Z;
   long long len = (total + 255) / 256;
   if (len < len_min) len = len_min;
-#ifdef ENF_SK_FORCE_LEN      // A/B builds only (scripts/build_variant.sh): e.g. 43 at config 3 = round 3's earlier three equal parts per tile
-  len = ENF_SK_FORCE_LEN;
-#endif
   EnfStreamK k{(int)len, (int)((total + len - 1) / len), 1};
   if (len >= Z) return k;
   for (long long t = 0; t < tiles; ++t) {
@@ -232,7 +228,7 @@ inline EnfStreamK enf_zfold_streamk(const EnfDims& m) {
   const long long tiles = (long long)((m.N + 127) / 128) * m.B;
   if (tiles * m.Z >= 0x7fffffffLL) return none;
   if (m.var_fwd == ENF_VARIANT_ZFOLD_ZSPLIT) return m.Z >= 2 ? enf_streamk(tiles, m.Z, (m.Z + 2) / 3) : none;   // forced: <= 4 parts
-  if (m.var_fwd != ENF_VARIANT_AUTO || enf_zfold_env(0) >= 0) return none;
+  if (m.var_fwd != ENF_VARIANT_AUTO) return none;
   if (tiles >= 192 || m.Z < ENF_SK_MIN_Z) return none;
   const EnfStreamK k = enf_streamk(tiles, m.Z, ENF_SK_MIN_RUN);
   // against the latent-split kernel: a run costs its latent steps + ~5 (fold kernel, merge), and in the time of one latent step (128
@@ -252,8 +248,6 @@ inline int enf_zfold_split(const EnfDims& m) {
   if (k.parts > 1) return k.parts;
   if (m.var_fwd == ENF_VARIANT_ZFOLD_ZSPLIT) return 1;
   if (m.var_fwd != ENF_VARIANT_AUTO) return m.var_fwd == ENF_VARIANT_ZFOLD ? 1 : 0;
-  const int mode = enf_zfold_env(0);
-  if (mode >= 0) return mode;
   return (long long)((m.N + 127) / 128) * m.B >= 192 ? 1 : 0;
 }
 inline bool enf_use_zfold(const EnfDims& m) { return enf_zfold_split(m) > 0; }
@@ -265,8 +259,6 @@ ENF_HD inline size_t enf_wzu_bytes(int H, int D) { return (size_t)(D / 32) * 4 *
 // workgroup.  Needs enough latents to fill the chip.  EnfDesc.pair_bwd_variant as for the forward.
 inline bool enf_use_zfold_bwd(const EnfDims& m) {
   if (m.var_bwd != ENF_VARIANT_AUTO) return m.var_bwd == ENF_VARIANT_ZFOLD;
-  const int mode = enf_zfold_env(1);
-  if (mode >= 0) return mode == 1;
   return (long long)m.B * m.Z >= 192;
 }
 

@@ -17,100 +17,15 @@
 // gemm_tile_flip -- same panels, MFMA operands swapped) whose rows are the queries, so they cost 4
 // FMAs per 16x16 tile and 32 accumulator registers instead of 128; +160 MFMAs per tile.
 #include <hip/hip_runtime.h>
-#ifndef ENF_K3_LITE
-#define ENF_K3_LITE 0
-#endif
-#define ENF_ASM_LITE ENF_K3_LITE
 #include "enf_layout.h"
 #include "enf_launch.h"
 #include "enf_device.h"
 #include "enf_pair_common.h"
 
-#ifndef ENF_K3_FENCE
-#define ENF_K3_FENCE 1
-#endif
-#if ENF_K3_FENCE
 #define K3_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define K3_SCHED_FENCE() do {} while (0)
-#endif
-#ifndef ENF_K3_OPAQUE
-#define ENF_K3_OPAQUE 1
-#endif
-#if ENF_K3_OPAQUE
 #define K3_OPAQUE(x) asm volatile("" : "+v"(x))
-#else
-#define K3_OPAQUE(x) do {} while (0)
-#endif
-#ifndef ENF_K3_EARLY_DY
-#define ENF_K3_EARLY_DY 0
-#endif
-#ifndef ENF_K3_PARK
-#define ENF_K3_PARK 1
-#endif
-#ifndef ENF_K3_FUSED_GELU
-#define ENF_K3_FUSED_GELU 0
-#endif
-#ifndef ENF_K3_ZF_FUSED       // z-fold heads: gelu(a5) and gelu'(a5) from one exp + rcp (a5 is overwritten by its gelu')
-#define ENF_K3_ZF_FUSED 1
-#endif
-#ifndef ENF_K3_ENTRY_BARRIER  // round 1's timing mitigation of the run-to-run deviations (a barrier as the kernel's first statement).  OFF since
-#define ENF_K3_ENTRY_BARRIER 0  // the cause is fixed (enf_device.h: ln_apply): probes and suite clean without it (scripts/k3_race/README.md)
-#endif
-#ifndef ENF_K3_ANTI           // the upper four waves (the SIMD-mates of the lower four) take each stage's barrier BEFORE its MFMAs
-#define ENF_K3_ANTI 0         // (enf_device.h: Pipe.early): one wave of a SIMD multiplies while the other runs its vector epilogue.
-#endif                        // OFF: correct (148 tests) but 9 % SLOWER on the fit (3.00 vs 2.75 ms, gpurun_out/r02/ab_anti.log), as in K2
-#ifndef ENF_K3_PREFETCH       // per-tile global reads (query coordinates, lse) issued one tile ahead.  OFF: measured 1.4 % SLOWER
-#define ENF_K3_PREFETCH 0     // on the fit (2.74 -> 2.78 ms same-box, gpurun_out/r02/ab_pf.log): the five live registers cost more
-#endif                        // than the exposed L2 latency at the top of a tile; with delta prefetched too, +25 spilled dwords
-#if ENF_K3_PREFETCH
-#define K3_LSE(h) t_lse[h]
-#else
 #define K3_LSE(h) A.lse[qrow * H + (h)]
-#endif
 #define K3_DELTA(h) A.delta[qrow * H + (h)]     // (delta is wanted late in the tile: prefetching it costs 25 spilled dwords)
-#ifndef ENF_STORE_NT          // activation store (STORE instantiation): non-temporal stores
-#define ENF_STORE_NT 0
-#endif
-#ifndef ENF_K3_A3_FUSED       // value chain: park gelu'(a3) (from the sigmoid gelu(a3) needs anyway) instead of a3
-#define ENF_K3_A3_FUSED 1
-#endif
-#ifndef ENF_K3_UF_FUSED       // unfolded heads: the same
-#define ENF_K3_UF_FUSED 1
-#endif
-#ifndef ENF_K3_LA             // z-fold bf16: look-ahead staging (enf_device.h: panel_gemm<.., LA>) -- one stage always in flight
-#define ENF_K3_LA 1
-#endif
-#ifndef ENF_K3_LDSACC
-#define ENF_K3_LDSACC 1
-#endif
-#ifndef ENF_K3_ZF_SPLIT       // z-fold at a full chip: workgroups per latent (query tiles split), co-located on one XCD (launch code below)
-#define ENF_K3_ZF_SPLIT 1
-#endif
-#ifndef ENF_K3_DN_LATE        // z-fold: the d n^ GEMMs run after both heads (their inputs parked as fragments) instead of inside them
-#define ENF_K3_DN_LATE 1
-#endif
-#ifndef ENF_K3_GELU_PK        // the fused gelu / gelu' with its polynomial parts as packed instructions (gelu_fg_tile)
-#define ENF_K3_GELU_PK 1
-#endif
-#ifndef ENF_K3_DOT_PK         // the four-term dot products of the flipped d v0 sums as packed multiplies
-#define ENF_K3_DOT_PK 1
-#endif
-#ifndef ENF_K3_ZF_EARLY_DY    // z-fold heads: d ybar / delta requested before the head's first GEMM stage
-#define ENF_K3_ZF_EARLY_DY 1
-#endif
-#ifndef ENF_K3_INV_SPECIALISED
-#define ENF_K3_INV_SPECIALISED 1
-#endif
-#ifndef ENF_K3_STORE_SPEC
-#define ENF_K3_STORE_SPEC 1
-#endif
-#ifndef ENF_K3_STATIC_PRIO
-#define ENF_K3_STATIC_PRIO 0
-#endif
-#ifndef ENF_K3_XCD_REMAP
-#define ENF_K3_XCD_REMAP 1
-#endif
 
 struct PairBwdArgs {
   const float* x; long long x_bstride;
@@ -130,18 +45,11 @@ struct PairBwdArgs {
 // The STORE instantiation's 7 + 4 H buffer pointers, fetched from the kernel-argument segment where they are used (s_load_dwordx2 +
 // lgkmcnt).  Read as `A.store[i]` hipcc loads all of them once, cannot keep 30 scalar registers across the tile loop and spills them to
 // scratch: 15 scratch reloads per tile, each with an `s_waitcnt vmcnt(0)` that also waits for the LDS-DMA stage in flight.
-#ifndef ENF_K3_STORE_SLOAD
-#define ENF_K3_STORE_SLOAD 1
-#endif
 DEV void* k3_store_ptr(const PairBwdArgs& A, int i) {
-#if ENF_K3_STORE_SLOAD
   void* p;
   const unsigned off = (unsigned)(offsetof(PairBwdArgs, store) + 8 * i);
   asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(p) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "s"(off));
   return p;
-#else
-  return A.store[i];
-#endif
 }
 
 // Debug build only (-DENF_STAMPS): s_memtime stamps of the first tiles of one workgroup (scripts/stamps_k3.py)
@@ -193,12 +101,7 @@ DEV void store_frags(void* base, size_t row, int D, const Frags<BF16, KB>& F, in
     __bf16* p = reinterpret_cast<__bf16*>(base) + row * D;
 #pragma unroll
     for (int blk = 0; blk < KB; ++blk) {
-#if ENF_STORE_NT
-      // written once, read once by enf_xtd_kernel, 2 GB per pass: streaming stores keep it out of the way of the panels in L2
-      __builtin_nontemporal_store(__builtin_bit_cast(f32x4, F.f[blk]), reinterpret_cast<f32x4*>(p + 32 * blk + 8 * quad));
-#else
       *reinterpret_cast<bf16x8*>(p + 32 * blk + 8 * quad) = F.f[blk];
-#endif
     }
   } else {
     float* p = reinterpret_cast<float*>(base) + row * D;
@@ -218,7 +121,7 @@ template <int D, int H, bool BF16> struct PairBwdSmem {
   static constexpr int LACC = ZVEC + 4 * NWAVES * 2 * H * D;               // NWAVES x (2 H D/16) x 64 lanes floats: dU | dV0 partial sums
   // ball / ball_lat: NWAVES x 11 x 16 floats, per-column partial sums of d R (9, quad-0 lanes) and of the two latent-only
   // invariants' gradients (quad-1 lanes)
-  static constexpr int EXTACC = LACC + (ENF_K3_LDSACC ? 4 * NWAVES * 2 * H * (D / 16) * 64 : 0);
+  static constexpr int EXTACC = LACC + 4 * NWAVES * 2 * H * (D / 16) * 64;
   static constexpr bool EXT_OK = D == 64;            // the 128-wide kernels have no LDS left: ball needs D = 64 (enf_check_desc)
   static constexpr int TOTAL = EXTACC + (EXT_OK ? 4 * NWAVES * 11 * 16 : 0);
   static_assert(TOTAL <= 160 * 1024, "K3 LDS budget");
@@ -246,7 +149,7 @@ DEV void gb_panel_flip(f32x4 (&v)[D / 16], f32x4 (&opgf)[D / 16], const Frags<BF
     else if (next != NO_STAGE) stage_issue<NEXT_BYTES>(P.rs, next, ring + (P.cur ^ 1) * STAGE_MAX, P.wave, lane);
     const char* slot = ring + P.cur * STAGE_MAX;
     f32x4 t[MTS];
-    constexpr bool ASM = BF16 && ENF_ASM_GEMM && GemmStageAsm<KB, MTS, ENF_ASM_LITE != 0>::available && MTS == 8;
+    constexpr bool ASM = BF16 && GemmStageAsm<KB, MTS>::available && MTS == 8;
     if constexpr (ASM) {
       // transposed product of all 8 tiles + flipped product of the 4 gamma tiles {0,1,4,5} from one fragment read
       f32x4 af[4];
@@ -255,7 +158,7 @@ DEV void gb_panel_flip(f32x4 (&v)[D / 16], f32x4 (&opgf)[D / 16], const Frags<BF
         const float bc = 1.0f + bias[16 * (sp * MTS + 4 * (j >> 1) + (j & 1)) + col];
         af[j] = f32x4{bc, bc, bc, bc};
       }
-      GemmStageAsm<KB, MTS, ENF_ASM_LITE != 0>::run_gb_bias(t, af, F.f, (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<char*>(slot) + (lane << 4)),
+      GemmStageAsm<KB, MTS>::run_gb_bias(t, af, F.f, (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<char*>(slot) + (lane << 4)),
                                                             (unsigned)(uintptr_t)(lds_ptr_t)(const_cast<float*>(bias) + 16 * sp * MTS + 4 * quad));
 #pragma unroll
       for (int j = 0; j < 4; ++j) opgf[2 * (sp * (MTS / 4) + (j >> 1)) + (j & 1)] = af[j];
@@ -423,7 +326,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   constexpr int NW = NWAVES;
   // look-ahead staging: every panel of the z-fold bf16 chain is ONE 32 KB (8 KB at D = 64) stage, so the stage after next
   // can be issued behind each stage's closing barrier; call sites pass `LA ? <stage after next> : <next stage>`
-  constexpr bool LA = ZF && BF16 && ENF_K3_LA != 0 && ENF_K3_ANTI == 0 && Cfg::DD::SPP == 1;
+  constexpr bool LA = ZF && BF16 && Cfg::DD::SPP == 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem + SM::RING;
   float* cst = reinterpret_cast<float*>(smem + SM::CONSTS);
@@ -434,22 +337,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   float* zv = reinterpret_cast<float*>(smem + SM::ZVEC) + wave * 2 * H * D;
   const char* blob = A.blob;
   auto G = [&](size_t off) { return reinterpret_cast<const float*>(blob + off); };
-  // Entry barrier: no wave touches LDS or issues a load before all eight waves of the workgroup are resident (the first four
-  // are launched up to ~1000 cycles ahead of the last two, scripts/k3_race/README.md).  Without it the unfolded 64-wide bf16
-  // two-head instantiation returned run-to-run different gradients for the latents of waves 4-7 (the first-launched, older
-  // wave of each SIMD).  Round 2 established what this is NOT -- not the LDS-DMA ring (read-back, poison and register-staging
-  // builds), not a missed barrier (phase self-check), not a stale scalar cache, not a documented MFMA / trans hazard (all
-  // measured, scripts/ubench/) -- and found and removed one real defect of the same symptom (inline-asm relu behind
-  // compiler-scheduled MFMAs, enf_device.h: relu_f).  The effect itself turned out to be elsewhere: the SLP-packed LayerNorm apply
-  // (enf_device.h: ln_apply; scripts/k3_race/README.md, "Resolution") -- this barrier had only moved the timing, and it is compiled out
-  // now: 21,000 polluted store-probe calls, 10,000 forward / 3,500 training-backward probe iterations and the GPU suite are clean without it.
+  // No entry barrier: it only moved the timing of the run-to-run deviations, whose cause was the SLP-packed LayerNorm apply
+  // (enf_device.h: ln_apply; scripts/k3_race/README.md, "Resolution").
   WSTAMP(0);
-#if ENF_K3_STATIC_PRIO      // A/B: the second-dispatched half of the workgroup loses every VALU arbitration to its SIMD-mates (T5, static form)
-  if (wave >= NWAVES / 2) __builtin_amdgcn_s_setprio(1);
-#endif
-#if ENF_K3_ENTRY_BARRIER
-  __syncthreads();
-#endif
 
   // this wave's latent: flat (b,z) index; waves past the end keep the barrier cadence only
   // ZF with xcd_remap: workgroup ids are dealt round-robin over the 8 XCDs (id % 8 labels the XCD, MI355X_MICROARCH.md
@@ -518,14 +408,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   if constexpr (ZF) P.rs2 = make_blob_rsrc(A.wzt + (size_t)bzc * H * 2 * PANEL_DD, (unsigned)(H * 2 * PANEL_DD));
   else P.rs2 = P.rs;
   const unsigned pWG = (unsigned)A.L.awg;
-  first_stage<ST_DD, NW, (ENF_K3_ANTI != 0) && ZF>(P, ring, pQ1, wave, lane);
+  first_stage<ST_DD, NW>(P, ring, pQ1, wave, lane);
   if constexpr (LA) stage_issue_p<ST_DD, NW>(P, pV1, ring + STAGE_MAX, lane);       // the second stage is in flight from here on
 
   // per-lane partial sums over this wave's queries.  dU/dV0: lane (col, quad) holds feature
   // 16 t + col, summed over the queries n = 4 quad + i of every tile (flipped products).
-  // ENF_K3_LDSACC: they live in wave-private LDS ([slot][lane], conflict-free) instead of 32 registers that are
+  // They live in wave-private LDS ([slot][lane], conflict-free) instead of 32 registers that are
   // touched once per tile (and otherwise spilled to scratch for the whole sweep).
-#if ENF_K3_LDSACC
   float* lacc = reinterpret_cast<float*>(smem + SM::LACC) + wave * (2 * H * NT * 64) + lane;
   // every lane owns its slots: plain read-modify-write (an LDS float atomic costs ~1000 cycles here)
   // flush NT partial sums of one head at once: all reads, then all adds, then all writes (one LDS round trip)
@@ -538,24 +427,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   };
   auto dU_get = [&](int h, int t) { return lacc[(h * NT + t) * 64]; };
   auto dV0_get = [&](int h, int t) { return lacc[((H + h) * NT + t) * 64]; };
-#else
-  float dU[H][NT], dV0[H][NT];
-  auto dU_add = [&](int h, int t, float v) { dU[h][t] += v; };
-  auto dV0_add = [&](int h, int t, float v) { dV0[h][t] += v; };
-  auto dU_get = [&](int h, int t) { return dU[h][t]; };
-  auto dV0_get = [&](int h, int t) { return dV0[h][t]; };
-#endif
   float dC[H], dpose[4] = {0.f, 0.f, 0.f, 0.f}, dwc = 0.f;
 #pragma unroll
   for (int h = 0; h < H; ++h) {
     dC[h] = 0.f;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-#if ENF_K3_LDSACC
       lacc[(h * NT + t) * 64] = 0.f; lacc[((H + h) * NT + t) * 64] = 0.f;
-#else
-      dU[h][t] = 0.f; dV0[h][t] = 0.f;
-#endif
     }
   }
 
@@ -564,26 +442,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   // ZF: the 8 waves share the sweep (wave w takes every 8th tile of the split); all run the same number of steps
   const int my_tiles = ZF ? (split_tiles + NW - 1) / NW : split_tiles;
   WSTAMP(1);
-#if ENF_K3_PREFETCH
-  // this lane's query of tile step `ts` (clamped to a valid row): the per-tile global reads -- coordinates, lse -- are
-  // issued one tile ahead (ENF_K3_PREFETCH), under the previous tile's last GEMM stage, instead of at the top of the tile
-  // where nothing hides their latency
-  auto tile_query = [&](int ts) {
-    const int tk_ = ZF ? ts * NW + wave : ts;
-    const int n0_ = tk_ < split_tiles ? (split + tk_ * A.nsplit) * 16 : 0;
-    return min(n0_ + col, A.N - 1);
-  };
-  float pf_x[3], pf_lse[H];
-  auto prefetch = [&](int ts) {
-    const int n_ = tile_query(ts);
-    const float* xp = A.x + (size_t)b * A.x_bstride + (size_t)n_ * A.dx;
-    pf_x[0] = xp[0]; pf_x[1] = A.dx > 1 ? xp[1] : 0.f; pf_x[2] = A.dx > 2 ? xp[2] : 0.f;
-    const size_t qr = (size_t)b * A.N + n_;
-#pragma unroll
-    for (int h = 0; h < H; ++h) pf_lse[h] = A.lse[qr * H + h];
-  };
-  if (my_tiles > 0) prefetch(0);
-#endif
   for (int ti = 0; ti < my_tiles; ++ti) {
     const int tk = ZF ? ti * NW + wave : ti;
     const bool tvalid = tk < split_tiles;
@@ -591,14 +449,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     const bool nvalid = tvalid && n0 + col < A.N;
     const int n = min(n0 + col, A.N - 1);
     const size_t qrow = (size_t)b * A.N + n;
-#if ENF_K3_PREFETCH
-    float t_lse[H];
-#pragma unroll
-    for (int h = 0; h < H; ++h) t_lse[h] = pf_lse[h];
-    const QueryPt q = make_query(pf_x[0], pf_x[1], pf_x[2], inv_id);
-#else
     const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * dx_, dx_, inv_id);
-#endif
     float inv[4], win;
     pair_invariant<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, ext);
     const size_t srow = (size_t)bzc * A.N + n;        // row of the materialised activations (STORE)
@@ -634,17 +485,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     BSTAMP(1);
     // ---------------- v-forward to the normalised f
     unsigned relu_mask = 0u;             // bit (4t + i): a2[t][i] > 0
-#if ENF_K3_PARK
     Parked<BF16, NT> A3P;                // gelu'(a3) (or a3) waits here for the backward chain in half the registers;
                                          // n^ is recovered from its own fragments F, which the heads keep alive anyway
-#else
-    f32x4 a3[NT], nh[NT];
-#endif
     float mu1, r1;
     {
-#if ENF_K3_PARK
       f32x4 a3[NT], nh[NT];
-#endif
       f32x4 acc[NT];
       rff_embed<D, BF16>(acc, inv, c_acv, lane, quad, phv);
       make_frags<BF16, KB>(F, acc);
@@ -666,64 +511,37 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       if (STORE && A.masks) relu_mask = maskv;
       make_frags<BF16, KB>(F, acc);
       if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_G1), srow, D, F, quad);
-      if constexpr (ZF) panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(a3, F, P, ring, pF, LA ? (ENF_K3_DN_LATE ? gM : STAGE_RS2 | (unsigned)PANEL_DD) : STAGE_RS2, true, lane, c_bf);
+      if constexpr (ZF) panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(a3, F, P, ring, pF, LA ? gM : STAGE_RS2, true, lane, c_bf);
       else panel_gemm<KB, NT, BF16, ST_GB, NWAVES, INIT_BIAS>(a3, F, P, ring, pF, pGB, true, lane, c_bf);
-#if ENF_K3_A3_FUSED
       // nh = gelu(a3), a3 <- gelu'(a3) from one exp + rcp per element (one tile at a time, as in the heads); the backward
       // needs nothing else of a3, so gelu'(a3) is what gets parked
       K3_SCHED_FENCE();
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-#if ENF_K3_GELU_PK
         gelu_fg_tile(a3[t], nh[t]);
-#else
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float g, d;
-          gelu_fg1(a3[t][i], g, d);
-          nh[t][i] = g;
-          a3[t][i] = d;
-        }
-#endif
         asm volatile("" : "+v"(nh[t]), "+v"(a3[t]));
         K3_SCHED_FENCE();
       }
-#elif ENF_K3_FUSED_GELU
-#pragma unroll
-      for (int t = 0; t < NT; ++t) nh[t] = a3[t];
-      gelu_fg_tiles<NT>(nh, a3);            // nh = gelu(a3); a3 <- gelu'(a3), all the backward needs of it
-#else
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) nh[t][i] = gelu_f(a3[t][i]);
-        K3_SCHED_FENCE();
-      }
-#endif
       ln_stats<NT>(nh, mu1, r1, A.inv_d);
       ln_apply<NT>(nh, mu1, r1);
       make_frags<BF16, KB>(F, nh);
       if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_NH), srow, D, F, quad);
-#if ENF_K3_PARK
       A3P.park(a3);
-#endif
     }
     BSTAMP(2);
     f32x4 dnh[NT];                       // d n^ accumulated over heads
-    constexpr bool DNL = ZF && ENF_K3_DN_LATE != 0;    // z-fold: d n^ = sum_h W_zh d a5_h is taken AFTER the heads, from their parked d a5
-    if constexpr (!DNL) {                              // fragments (16 registers per head instead of the 32 of a running sum)
+    if constexpr (!ZF) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) dnh[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
     if constexpr (ZF) {
-      Frags<BF16, KB> FAh[DNL ? H : 1];
+      Frags<BF16, KB> FAh[H];
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-        const unsigned wzf = STAGE_RS2 | (unsigned)(h * 2 * PANEL_DD), wzb = wzf + PANEL_DD;
+        const unsigned wzf = STAGE_RS2 | (unsigned)(h * 2 * PANEL_DD);
         // ---- a5 = W_zh^T n + c_zh
         f32x4 a5[NT], v[NT];
-#if ENF_K3_ZF_EARLY_DY
         // this head's d ybar row and delta are requested BEFORE the GEMM stage: the L2 round trip runs under its MFMAs and the gelu
         // instead of in front of the dot products that consume it (32 registers that are free while d n^ is taken after the heads)
         f32x4 dy[NT];
@@ -733,49 +551,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
           for (int t = 0; t < NT; ++t) dy[t] = *reinterpret_cast<const f32x4*>(dyrow + 16 * t);
         }
         const float delta_h = K3_DELTA(h);
-#endif
-        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(a5, F, P, ring, wzf, DNL ? (LA ? pWG + h * PANEL_DD : gM) : (LA ? gM : wzb), true, lane, zv + H * D + h * D);
+        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(a5, F, P, ring, wzf, LA ? pWG + h * PANEL_DD : gM, true, lane, zv + H * D + h * D);
         BSTAMP(4 + 6 * h);
         float mu2, r2;
-#if ENF_K3_ZF_FUSED
         K3_SCHED_FENCE();
         // gelu(a5) and gelu'(a5) share their sigmoid, and nothing but reductions sits between their uses in this branch:
         // one exp + rcp per element, a5 <- gelu'(a5) in place (the same 32 registers it was kept alive in anyway)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-#if ENF_K3_GELU_PK
           gelu_fg_tile(a5[t], v[t]);
-#else
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            float g, d;
-            gelu_fg1(a5[t][i], g, d);
-            v[t][i] = g;
-            a5[t][i] = d;
-          }
-#endif
           asm volatile("" : "+v"(v[t]), "+v"(a5[t]));
           K3_SCHED_FENCE();
         }
-#else
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) v[t][i] = gelu_f(a5[t][i]);
-        }
-#endif
         ln_stats<NT>(v, mu2, r2, A.inv_d);
         ln_apply<NT>(v, mu2, r2);
         float s0 = 0.f, sd = 0.f;
-#if !ENF_K3_ZF_EARLY_DY
-        f32x4 dy[NT];
-        const float delta_h = K3_DELTA(h);
-        {
-          const float* dyrow = A.dybar + qrow * (H * D) + h * D + 4 * quad;
-#pragma unroll
-          for (int t = 0; t < NT; ++t) dy[t] = *reinterpret_cast<const f32x4*>(dyrow + 16 * t);
-        }
-#endif
         tiles_sum_dot<NT>(dy, [&](int t) { return v[t]; }, sd, s0);
         const float datt = xquad_sum(s0);
         dlogit[h] = nvalid ? att[h] * (datt - delta_h) : 0.f;
@@ -790,22 +580,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
             K3_OPAQUE(a5[t]);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              dy[t][i] = fmaf(nm2r, v[t][i], fmaf(ahr, dy[t][i], -m1r)) * (ENF_K3_ZF_FUSED ? a5[t][i] : gelu_grad_f(a5[t][i]));   // d a5
+              dy[t][i] = fmaf(nm2r, v[t][i], fmaf(ahr, dy[t][i], -m1r)) * a5[t][i];   // d a5
           }
         }
         BSTAMP(5 + 6 * h);
-        Frags<BF16, KB>& FA = FAh[DNL ? h : 0];
+        Frags<BF16, KB>& FA = FAh[h];
         make_frags<BF16, KB>(FA, dy);
-        // ---- d n += W_zh d a5
-        if constexpr (!DNL) panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ACC, LA>(dnh, FA, P, ring, wzb, LA ? pWG + h * PANEL_DD : gM, true, lane);
         // ---- d v0 += sum_n dv (1 + gamma), both as flipped products (rows = queries)
         f32x4 dvf[NT];
         {
           f32x4 none[1];
           const unsigned wzb0 = STAGE_RS2 | (unsigned)PANEL_DD;               // head 0's backward-orientation panel
           // the stage after this head's last one, and the one after that
-          const unsigned nxt = DNL ? (h + 1 < H ? wzf + 2 * PANEL_DD : wzb0) : (h + 1 < H ? wzf + 2 * PANEL_DD : gF);
-          const unsigned nxt2 = DNL ? (h + 1 < H ? gM : (H > 1 ? wzb0 + 2 * PANEL_DD : gF)) : (h + 1 < H ? wzb + 2 * PANEL_DD : gV1);
+          const unsigned nxt = h + 1 < H ? wzf + 2 * PANEL_DD : wzb0;
+          const unsigned nxt2 = h + 1 < H ? gM : (H > 1 ? wzb0 + 2 * PANEL_DD : gF);
           panel_gemm_flip<KB, NT, BF16, ST_DD, NW, false, INIT_ZERO, LA>(
               none, FA, P, ring, gM, LA ? nxt : pWG + h * PANEL_DD, lane, [](int) { return f32x4{0.f, 0.f, 0.f, 0.f}; },
               [&](int mt, const f32x4& af) { dvf[mt] = af; });
@@ -814,23 +602,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
               none, F, P, ring, pWG + h * PANEL_DD, LA ? nxt2 : nxt, lane,
               [&](int mt) { const float bc = c_bgb[h * D + 16 * mt + col]; return f32x4{bc, bc, bc, bc}; },
               [&](int mt, const f32x4& af) {
-#if ENF_K3_DOT_PK
                 const f32x2 p2 = __builtin_elementwise_fma(hi2(af), hi2(dvf[mt]), lo2(af) * lo2(dvf[mt]));
                 part[mt] = p2[0] + p2[1];
-#else
-                part[mt] = af[0] * dvf[mt][0] + af[1] * dvf[mt][1] + af[2] * dvf[mt][2] + af[3] * dvf[mt][3];
-#endif
               });
-#if ENF_K3_LDSACC
           lacc_flush((H + h) * NT, part);
-#else
-#pragma unroll
-          for (int mt = 0; mt < NT; ++mt) dV0_add(h, mt, part[mt]);
-#endif
         }
         BSTAMP(6 + 6 * h);
       }
-      if constexpr (DNL) {
+      // d n^ = sum_h W_zh d a5_h is taken after the heads, from their parked d a5 fragments (16 registers per head instead of
+      // the 32 of a running sum)
+      {
 #pragma unroll
         for (int h = 0; h < H; ++h) {
           const unsigned wzb = (STAGE_RS2 | (unsigned)(h * 2 * PANEL_DD)) + PANEL_DD;
@@ -843,7 +624,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     } else
 #pragma unroll
     for (int h = 0; h < H; ++h) {
-#if ENF_K3_PARK
       f32x4 v[NT];
       Parked<BF16, NT> OPG;
       {
@@ -852,11 +632,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
                                       lane, col, quad);
         OPG.park(opgf);
       }
-#else
-      f32x4 v[NT], opgf[NT];
-      gb_panel_flip<D, BF16, ST_DD>(v, opgf, F, P, ring, pGB + h * PANEL_GB, pM, c_bgb + 2 * h * D, zv + H * D + h * D,
-                                    lane, col, quad);
-#endif
       BSTAMP(3 + 6 * h);
       f32x4 a5[NT];
       {
@@ -868,16 +643,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       BSTAMP(4 + 6 * h);
       // d ybar of this head: issued first, the gelu / LayerNorm arithmetic below hides the L2 round trip
       f32x4 dy[NT];
-#if ENF_K3_EARLY_DY
-      {
-        const float* dyrow = A.dybar + qrow * (H * D) + h * D;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) dy[t] = *reinterpret_cast<const f32x4*>(dyrow + 16 * t + 4 * quad);
-      }
-#endif
       // mixer LN stats; v <- n~ = (gelu(a5) - mu) * rstd
       float mu2, r2;
-#if ENF_K3_UF_FUSED
       // as in the z-fold heads: v = gelu(a5), a5 <- gelu'(a5) from one exp + rcp per element, one tile at a time
       K3_SCHED_FENCE();
 #pragma unroll
@@ -892,28 +659,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         asm volatile("" : "+v"(v[t]), "+v"(a5[t]));
         K3_SCHED_FENCE();
       }
-#elif ENF_K3_FUSED_GELU
-#pragma unroll
-      for (int t = 0; t < NT; ++t) v[t] = a5[t];
-      gelu_fg_tiles<NT>(v, a5);             // v = gelu(a5); a5 <- gelu'(a5)
-#else
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[t][i] = gelu_f(a5[t][i]);
-        K3_SCHED_FENCE();
-      }
-#endif
       ln_stats<NT>(v, mu2, r2, A.inv_d);
       ln_apply<NT>(v, mu2, r2);
       // d n~ = att * d ybar ;  d att = d ybar . n~ ;  softmax backward with the forward's lse / delta
-#if !ENF_K3_EARLY_DY
       {
         const float* dyrow = A.dybar + qrow * (H * D) + h * D;
 #pragma unroll
         for (int t = 0; t < NT; ++t) dy[t] = *reinterpret_cast<const f32x4*>(dyrow + 16 * t + 4 * quad);
       }
-#endif
       float s0, sd;
       tiles_sum_dot<NT>(dy, [&](int t) { return v[t]; }, sd, s0);
       const float datt = xquad_sum(s0);
@@ -929,7 +682,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         K3_OPAQUE(a5[t]);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          dy[t][i] = r2 * (fmaf(ah, dy[t][i], -m1) - v[t][i] * m2) * ((ENF_K3_FUSED_GELU || ENF_K3_UF_FUSED) ? a5[t][i] : gelu_grad_f(a5[t][i]));   // d a5
+          dy[t][i] = r2 * (fmaf(ah, dy[t][i], -m1) - v[t][i] * m2) * a5[t][i];   // d a5
         K3_SCHED_FENCE();     // one tile's transcendental chain at a time: interleaving all 32 costs ~100 live registers
       }
       BSTAMP(5 + 6 * h);
@@ -943,19 +696,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         panel_gemm_flip<KB, NT, BF16, ST_GG, NW, true, INIT_ZERO>(
             v, FA, P, ring, gM, gGB + h * PANEL_GG, lane, [](int) { return f32x4{0.f, 0.f, 0.f, 0.f}; },
             [&](int mt, const f32x4& af) {
-#if ENF_K3_PARK
               const f32x4 og = OPG.get(mt);
-#else
-              const f32x4 og = opgf[mt];
-#endif
               part[mt] = af[0] * og[0] + af[1] * og[1] + af[2] * og[2] + af[3] * og[3];
             });                                                                                               // v <- d v
-#if ENF_K3_LDSACC
         lacc_flush((H + h) * NT, part);
-#else
-#pragma unroll
-        for (int mt = 0; mt < NT; ++mt) dV0_add(h, mt, part[mt]);
-#endif
       }
       BSTAMP(6 + 6 * h);
       // FiLM backward: d gamma = d v * v0; d beta = d v.
@@ -1002,25 +746,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     float dlat[2] = {0.f, 0.f};           // ball / ball_lat: gradient rows 4, 5 of the gc panels (quad-1 lanes)
     {
       float s1, s2;
-#if ENF_K3_PARK
       tiles_sum_dot<NT>(dnh, [&](int t) { return Parked<BF16, NT>{F}.get(t); }, s1, s2);
-#else
-      tiles_sum_dot<NT>(dnh, [&](int t) { return nh[t]; }, s1, s2);
-#endif
       const float m1 = xquad_sum(s1) * A.inv_d, m2 = xquad_sum(s2) * A.inv_d;
       const float m1r = m1 * r1, nm2r = -m2 * r1;
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-#if ENF_K3_PARK
         const f32x4 nht = Parked<BF16, NT>{F}.get(t);
         f32x4 a3t = A3P.get(t);
         K3_OPAQUE(a3t);
-#else
-        const f32x4 nht = nh[t], a3t = a3[t];
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          dnh[t][i] = fmaf(nm2r, nht[i], fmaf(r1, dnh[t][i], -m1r)) * ((ENF_K3_FUSED_GELU || ENF_K3_A3_FUSED) ? a3t[i] : gelu_grad_f(a3t[i]));   // d a3
+          dnh[t][i] = fmaf(nm2r, nht[i], fmaf(r1, dnh[t][i], -m1r)) * a3t[i];   // d a3
         K3_SCHED_FENCE();
       }
       make_frags<BF16, KB>(F, dnh);
@@ -1081,22 +817,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
             } else { r0 = relu_f(af[0]); r1 = relu_f(af[1]); r2 = relu_f(af[2]); r3 = relu_f(af[3]); }
 #pragma unroll
             for (int h = 0; h < H; ++h) {
-#if ENF_K3_DOT_PK
               const f32x2 p2 = __builtin_elementwise_fma(f32x2{r2, r3}, f32x2{dl[h][2], dl[h][3]}, f32x2{r0, r1} * f32x2{dl[h][0], dl[h][1]});
               upart[h][mt] = p2[0] + p2[1];
-#else
-              upart[h][mt] = dl[h][0] * r0 + dl[h][1] * r1 + dl[h][2] * r2 + dl[h][3] * r3;
-#endif
             }
           }, c_bq1);                                                                                             // a1
 #pragma unroll
       for (int h = 0; h < H; ++h) {
-#if ENF_K3_LDSACC
         lacc_flush(h * NT, upart[h]);
-#else
-#pragma unroll
-        for (int mt = 0; mt < NT; ++mt) dU_add(h, mt, upart[h][mt]);
-#endif
       }
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -1114,9 +841,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       Frags<BF16, KB> FA;
       make_frags<BF16, KB>(FA, acc);
       if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_DA1), srow, D, FA, quad);
-#if ENF_K3_PREFETCH
-      if (more) prefetch(ti + 1);          // the next tile's coordinates / lse land under this stage
-#endif
       panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(acc, FA, P, ring, gQ1, more ? (LA ? pV1 : pQ1) : NO_STAGE, true, lane);   // d E_q
       f32x4 dT[TT];
       rff_embed_bwd<D>(dT, acc, E);
@@ -1154,7 +878,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   }
 
 #ifdef ENF_TEST_HOOKS
-  if constexpr (ENF_K3_LDSACC != 0 && 2 * H * (D / 16) <= 16) {
+  if constexpr (2 * H * (D / 16) <= 16) {
     const int wg = blockIdx.y * gridDim.x + blockIdx.x;
     if (wg < ENF_HOOK_WGS) {
       float* o = enf_hook_wave_sums + (size_t)(wg * NWAVES + wave) * ENF_HOOK_ROW;
@@ -1171,12 +895,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     }
   }
 #endif
-  pipe_finish(P);          // (antiphase staging only: the early waves take the last stage's barrier here)
+  pipe_finish(P);
   WSTAMP(2);
   // ---- fold the partial sums and add this wave's share into the latent-table gradient
   if (!active) return;   // (unfolded: a wave without a latent; no barrier follows on that path.  z-fold: all eight waves share the latent)
   float* drow = A.dlt + (size_t)bz * ltstride;
-#if ENF_K3_LDSACC
   if constexpr (ZF) {
     // the eight waves of a z-fold workgroup share one latent: their partial sums are added through LDS first -- wave w folds
     // slots w, w + 8, ... over the waves (fixed order) and the quads -- so a gradient element gets ONE atomic per workgroup
@@ -1193,7 +916,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         atomicAdd(drow + (sl < H * NT ? enf_lt_off_u(H, D) + 16 * sl : enf_lt_off_v0(H, D) + 16 * (sl - H * NT)) + col, v);
     }
   } else
-#endif
 #pragma unroll
   for (int h = 0; h < H; ++h)
 #pragma unroll
@@ -1262,16 +984,8 @@ extern "C" int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const c
   const int wgs = zf ? m.B * m.Z : (m.B * m.Z + NWAVES - 1) / NWAVES, ntiles = (m.N + 15) / 16;
   int ns = 1;
   while (wgs * ns < 256 && ns * 2 <= ntiles) ns *= 2;
-#ifdef ENF_K3_ZF_NSPLIT      // A/B builds: force the z-fold split
-  if (zf) { ns = ENF_K3_ZF_NSPLIT; while (ns > 1 && ns > ntiles) ns /= 2; }
-#else
-  // z-fold, chip already full: split each latent's sweep over ENF_K3_ZF_SPLIT workgroups placed on one XCD, so that the XCD's
-  // resident workgroups stream 32 / split latents' panels (128 KB each at D = 128, H = 2) instead of 32 -- they then stay in
-  // the 4 MB L2 across the sweep steps instead of coming from HBM every step
-  if (zf && ns == 1 && wgs % 8 == 0 && wgs >= 256) { ns = ENF_K3_ZF_SPLIT; while (ns > 1 && ns * 8 > ntiles) ns /= 2; }
-#endif
   A.nsplit = ns;
-  A.xcd_remap = zf && ns > 1 && wgs % 8 == 0 && ENF_K3_XCD_REMAP;
+  A.xcd_remap = zf && ns > 1 && wgs % 8 == 0;
   if (store)
     for (int i = 0; i < ENF_NUM_STORE(m.H); ++i) A.store[i] = store[i];
 #define ENF_CASE(DD, HH)                                                                   \
@@ -1280,7 +994,6 @@ extern "C" int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const c
     if (zf) return m.bf16 ? launch_pair_bwd<DD, HH, true, false, true>(A, st) : launch_pair_bwd<DD, HH, false, false, true>(A, st);    \
     return m.bf16 ? launch_pair_bwd<DD, HH, true, false, false>(A, st) : launch_pair_bwd<DD, HH, false, false, false>(A, st);         \
   }
-#if ENF_K3_INV_SPECIALISED
   // the z-fold bf16 kernels of the shipped configs with the invariant as a compile-time constant (configs 2, 4, 5:
   // rel_pos_periodic; config 3: latitude_periodic and the SO(3) polar_periodic; config 1: ponita at num_hidden 64)
   if (zf && m.bf16 && m.dx == 2) {
@@ -1291,12 +1004,9 @@ extern "C" int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const c
     }
     if (m.D == 64 && m.H == 2 && m.inv == ENF_INV_PONITA) return launch_pair_bwd<64, 2, true, false, true, ENF_INV_PONITA>(A, st);
   }
-#if ENF_K3_STORE_SPEC
   // the training path's kernel (activation store) of the headline configs likewise
   if (store && m.bf16 && m.dx == 2 && m.D == 128 && m.H == 2 && m.inv == ENF_INV_REL_POS_PERIODIC)
     return launch_pair_bwd<128, 2, true, true, false, ENF_INV_REL_POS_PERIODIC>(A, st);
-#endif
-#endif
   ENF_CASE(128, 2)
   ENF_CASE(64, 2)
   ENF_CASE(128, 1)

@@ -55,16 +55,10 @@ extern "C" int enf_debug_read_stamps(unsigned long long* dst) {
 #define STAMP(k) do {} while (0)
 #endif
 
-#ifndef ENF_K2_BIAS_IN_STAGE
-#define ENF_K2_BIAS_IN_STAGE 0   // measured: 1.19 vs 1.135 ms with the bias loads inside the asm stage (K2 has registers to spare)
-#endif
-#define K2_INIT (ENF_K2_BIAS_IN_STAGE ? INIT_BIAS : INIT_ACC)
-// accumulators start from the bias row vector: loaded here (INIT_ACC) or inside the asm stage (INIT_BIAS)
+// accumulators start from the bias row vector, loaded here (INIT_ACC; inside the asm stage measured 1.19 vs 1.135 ms)
 #define K2_BIAS(ACC, PTR)                                                              \
   do {                                                                                 \
-    if (K2_INIT == INIT_ACC) {                                                         \
-      _Pragma("unroll") for (int t_ = 0; t_ < NT; ++t_) ACC[t_] = rowvec(PTR, t_, quad); \
-    }                                                                                  \
+    _Pragma("unroll") for (int t_ = 0; t_ < NT; ++t_) ACC[t_] = rowvec(PTR, t_, quad);   \
   } while (0)
 // relu-mask modes live in their own instantiation (MASKS): as wave-uniform runtime branches in the one kernel they cost
 // the default path 1.3 % (measured)
@@ -72,30 +66,15 @@ extern "C" int enf_debug_read_stamps(unsigned long long* dst) {
 #ifndef ENF_ZFOLD_WAVES
 #define ENF_ZFOLD_WAVES 8
 #endif
-#ifndef ENF_K2_LA             // z-fold bf16: look-ahead staging (enf_device.h: panel_gemm<.., LA>).  OFF: measured 3 % SLOWER on this
-#define ENF_K2_LA 0           // kernel (decode shape 1.275 vs 1.238 ms same-box, gpurun_out/r02/ab_la3.log): every stage here is followed
-#endif                        // by a vector epilogue longer than the DMA, which the 2-slot order already hides; in K3 it pays (-7 %)
-#ifndef ENF_ANTIPHASE
-#define ENF_ANTIPHASE false
-#endif
-#ifndef ENF_K2_A3             // z-fold bf16: antiphase staging over a three-slot ring (enf_device.h: panel_gemm_a3).  OFF: correct (189 forward /
-#define ENF_K2_A3 0           // golden tests) but 2 % SLOWER at the decode shape (1.153 vs 1.129 ms same-box, profiles/r03_ab_k2_a3.log): an MFMA
-#endif                        // holds the SIMD's vector issue for half its duration, so the mate's epilogue does not run "under" it for free
-#ifndef ENF_K2_LN_ASM         // the LayerNorm apply as scalar asm fmas (ln_apply, enf_device.h: the form K3 needed).  K2's fmaf loop packed
-#define ENF_K2_LN_ASM 1       // differently and never deviated (scripts/k3_race/fwd_probe.py); the asm form costs nothing (same-box A/B: decode
-#endif                        // 1.238-1.241 vs 1.240-1.250 ms), so K2 avoids the instruction class too
 
 // waves per workgroup: the z-fold variant runs TWO independent 4-wave workgroups per CU (one wave of each
 // per SIMD) so that the SIMD-mates never meet at a barrier: while one computes its MFMA stage the other
 // keeps the vector ALU busy (8-wave lockstep measured 2 V + M per stage, M = the younger wave's MFMAs).
-#ifndef ENF_K2_INV_SPECIALISED
-#define ENF_K2_INV_SPECIALISED 1
-#endif
 template <bool ZFOLD> struct PairWaves { static constexpr int NW = ZFOLD && ENF_ZFOLD_WAVES == 4 ? 4 : NWAVES; };
 
-template <int D, int H, bool BF16, int NW, int NSLOT = 2> struct PairSmem {
-  static constexpr int RING = 0;                                   // 2 slots (3: A3 staging)
-  static constexpr int CONSTS = RING + NSLOT * STAGE_MAX;              // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (2D each)
+template <int D, int H, bool BF16, int NW> struct PairSmem {
+  static constexpr int RING = 0;                                   // 2 slots
+  static constexpr int CONSTS = RING + 2 * STAGE_MAX;              // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (2D each)
   static constexpr int N_CONST = 4 * D + 2 * H * D + 4 * D;
   static constexpr int ZVEC = CONSTS + 4 * N_CONST;                // NWAVES x 2*H*D floats
   static constexpr int XCH = ZVEC + 4 * NW * 2 * H * D;            // NW x H x 3 x 16 floats
@@ -115,8 +94,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   const int dx_ = INV >= 0 ? 2 : A.dx;
   using Cfg = PairCfg<D, BF16>;
   constexpr int NW = PairWaves<ZFOLD>::NW, NTH = 64 * NW;
-  constexpr bool A3 = ZFOLD && BF16 && ENF_K2_A3 != 0 && NW == 8 && PairCfg<D, BF16>::DD::SPP == 1;
-  using SM = PairSmem<D, H, BF16, NW, A3 ? 3 : 2>;
+  using SM = PairSmem<D, H, BF16, NW>;
   constexpr int KB = Cfg::KB, NT = Cfg::NT;
   constexpr int ST_DD = Cfg::DD::STAGE, ST_GB = Cfg::GB::STAGE, PANEL_GB = Cfg::GB::BYTES, PANEL_DD = Cfg::DD::BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -176,17 +154,10 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * dx_, dx_, inv_id);
   if constexpr (ZFOLD) P.rs2 = make_blob_rsrc(A.wz + (size_t)b * A.Z * H * PANEL_DD, (unsigned)(A.Z * H * PANEL_DD));
   else P.rs2 = P.rs;
-  if constexpr (A3) first_stage_a3<ST_DD, ST_DD, NW>(P, ring, pQ1, pV1, wave, lane);
-  else first_stage<ST_DD, NW, ENF_ANTIPHASE>(P, ring, pQ1, wave, lane);
-  // look-ahead staging: all five panels of a z-fold bf16 iteration are single 32 KB (8 KB) stages, so the stage after next is
-  // issued behind each stage's closing barrier and streams under the vector epilogue that follows every stage of this kernel;
-  // call sites pass `LA ? <stage after next> : <next stage>`
-  constexpr bool LA = A3 || (ZFOLD && BF16 && ENF_K2_LA != 0 && !ENF_ANTIPHASE && Cfg::DD::SPP == 1);   // (call sites name the stage AFTER next)
-  if constexpr (LA && !A3) stage_issue_p<ST_DD, NW>(P, pV1, ring + STAGE_MAX, lane);
-  // the z-fold stages of this kernel: 2-slot (optionally look-ahead) staging, or the antiphase 3-slot form
+  first_stage<ST_DD, NW>(P, ring, pQ1, wave, lane);
+  // the z-fold stages of this kernel: 2-slot staging (look-ahead and antiphase 3-slot staging measured 3 % / 2 % slower)
   auto zgemm = [&](f32x4 (&acc_)[NT], const Frags<BF16, KB>& F_, unsigned panel_, unsigned next_, bool active_, const float* bias_) {
-    if constexpr (A3) panel_gemm_a3<KB, NT, BF16, ST_DD, NW, K2_INIT>(acc_, F_, P, ring, next_, active_, lane, bias_);
-    else panel_gemm<KB, NT, BF16, ST_DD, NW, K2_INIT, LA>(acc_, F_, P, ring, panel_, next_, active_, lane, bias_);
+    panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc_, F_, P, ring, panel_, next_, active_, lane, bias_);
   };
 
 #pragma unroll
@@ -238,8 +209,8 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
       make_frags<BF16, KB>(F, acc);
       K2_BIAS(acc, c_bq1);
       STAMP(1);
-      if constexpr (ZFOLD) zgemm(acc, F, pQ1, LA ? pF : pV1, active, c_bq1);
-      else panel_gemm<KB, NT, BF16, ST_DD, NW, K2_INIT, LA>(acc, F, P, ring, pQ1, LA ? pF : pV1, active, lane, c_bq1);
+      if constexpr (ZFOLD) zgemm(acc, F, pQ1, pV1, active, c_bq1);
+      else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pQ1, pV1, active, lane, c_bq1);
       STAMP(2);
       const bool mread = K2_MASK_MODE == 2;                       // wave-uniform
       if (K2_MASK_MODE) {
@@ -282,8 +253,8 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
       make_frags<BF16, KB>(F, acc);
       K2_BIAS(acc, c_bv1);
       STAMP(4);
-      if constexpr (ZFOLD) zgemm(acc, F, pV1, LA ? STAGE_RS2 | (unsigned)(z * H * PANEL_DD) : pF, active, c_bv1);
-      else panel_gemm<KB, NT, BF16, ST_DD, NW, K2_INIT, LA>(acc, F, P, ring, pV1, pF, active, lane, c_bv1);
+      if constexpr (ZFOLD) zgemm(acc, F, pV1, pF, active, c_bv1);
+      else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pV1, pF, active, lane, c_bv1);
       STAMP(5);
       const bool mread = K2_MASK_MODE == 2;
       if (K2_MASK_MODE) {
@@ -297,23 +268,17 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
       STAMP(6);
       if constexpr (ZFOLD) {
         const unsigned wz0 = STAGE_RS2 | (unsigned)(z * H * PANEL_DD);
+        // the look-ahead staging's next stage (that staging is removed): unused, but without it hipcc numbers this kernel's SGPRs differently
         const unsigned after = H > 1 ? wz0 + PANEL_DD : (it + 1 < iters ? pQ1 : NO_STAGE);
-        zgemm(acc, F, pF, LA ? after : wz0, active, c_bf);
+        (void)after;
+        zgemm(acc, F, pF, wz0, active, c_bf);
       }
-      else panel_gemm<KB, NT, BF16, ST_GB, NW, K2_INIT>(acc, F, P, ring, pF, pGB, active, lane, c_bf);
+      else panel_gemm<KB, NT, BF16, ST_GB, NW, INIT_ACC>(acc, F, P, ring, pF, pGB, active, lane, c_bf);
       STAMP(7);
-      gelu_tiles<NT, BF16>(acc);
+      gelu_tiles<NT>(acc);
       float mu, rstd;
       ln_stats<NT>(acc, mu, rstd, A.inv_d);
-#if ENF_K2_LN_ASM
       ln_apply<NT>(acc, mu, rstd);
-#else
-      const float nmr = -mu * rstd;
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] = fmaf(acc[t][i], rstd, nmr);
-#endif
       make_frags<BF16, KB>(F, acc);   // F = normalised f, shared by all heads' gamma/beta panels
       STAMP(8);
     }
@@ -326,8 +291,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         STAMP(10 + 4 * h);
         const bool more = it + 1 < iters;
         const unsigned nx1 = h + 1 < H ? wzh + PANEL_DD : (more ? pQ1 : NO_STAGE);
-        const unsigned nx2 = h + 2 < H ? wzh + 2 * PANEL_DD : (h + 2 == H ? (more ? pQ1 : NO_STAGE) : (more ? pV1 : NO_STAGE));
-        zgemm(v, F, wzh, LA ? nx2 : nx1, active, zv + H * D + h * D);
+        zgemm(v, F, wzh, nx1, active, zv + H * D + h * D);
       } else {
         f32x4 dummy[1];
         gb_panel<D, BF16, ST_DD, false, NW>(v, dummy, F, P, ring, pGB + h * PANEL_GB, pM, active, c_bgb + 2 * h * D,
@@ -337,11 +301,11 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         make_frags<BF16, KB>(FV, v);
         K2_BIAS(v, c_bm);
         STAMP(10 + 4 * h);
-        if (h + 1 < H) panel_gemm<KB, NT, BF16, ST_GB, NW, K2_INIT>(v, FV, P, ring, pM, pGB + (h + 1) * PANEL_GB, active, lane, c_bm);
-        else panel_gemm<KB, NT, BF16, ST_DD, NW, K2_INIT>(v, FV, P, ring, pM, it + 1 < iters ? pQ1 : NO_STAGE, active, lane, c_bm);
+        if (h + 1 < H) panel_gemm<KB, NT, BF16, ST_GB, NW, INIT_ACC>(v, FV, P, ring, pM, pGB + (h + 1) * PANEL_GB, active, lane, c_bm);
+        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(v, FV, P, ring, pM, it + 1 < iters ? pQ1 : NO_STAGE, active, lane, c_bm);
       }
       STAMP(11 + 4 * h);
-      gelu_tiles<NT, BF16>(v);
+      gelu_tiles<NT>(v);
       float mu, rstd;
       ln_stats<NT>(v, mu, rstd, A.inv_d);
       if (active) {
@@ -371,8 +335,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
     }
   }
 
-  if constexpr (!A3) pipe_finish(P);       // (A3: both halves have met every barrier)
-  else __syncthreads();                    // the ring is reused below
+  pipe_finish(P);
   if constexpr (ZFOLD) {
     if (split) {               // partial weighted sums against this segment's own reference logit + (m, l, c): merged afterwards
       if (n0 + col < A.N) {
@@ -499,8 +462,7 @@ static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
     if (A.mask_mode) return launch_pair_fwd<D, H, BF16, ZFOLD, true>(A, st);       // (the masked passes keep the run-time invariant)
   }
   constexpr int NW = PairWaves<ZFOLD>::NW;
-  constexpr bool A3 = ZFOLD && BF16 && ENF_K2_A3 != 0 && NW == 8 && PairCfg<D, BF16>::DD::SPP == 1;
-  using SM = PairSmem<D, H, BF16, NW, A3 ? 3 : 2>;
+  using SM = PairSmem<D, H, BF16, NW>;
   auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV>;
   static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
   if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
@@ -551,7 +513,6 @@ extern "C" int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const c
     if (zfold) return m.bf16 ? launch_pair_fwd<DD, HH, true, true>(A, st) : launch_pair_fwd<DD, HH, false, true>(A, st); \
     return m.bf16 ? launch_pair_fwd<DD, HH, true, false>(A, st) : launch_pair_fwd<DD, HH, false, false>(A, st);         \
   }
-#if ENF_K2_INV_SPECIALISED
   if (m.bf16 && m.dx == 2 && !A.mask_mode) {       // the shipped configs' bf16 kernels with the invariant fixed at compile time
     if (m.D == 128 && m.H == 2) {
 #define ENF_SPEC(INVID)                                                                                                  \
@@ -563,7 +524,6 @@ extern "C" int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const c
     if (m.D == 64 && m.H == 2 && m.inv == ENF_INV_PONITA)
       return zfold ? launch_pair_fwd<64, 2, true, true, false, ENF_INV_PONITA>(A, st) : launch_pair_fwd<64, 2, true, false, false, ENF_INV_PONITA>(A, st);
   }
-#endif
   ENF_CASE(128, 2)
   ENF_CASE(64, 2)
   ENF_CASE(128, 1)

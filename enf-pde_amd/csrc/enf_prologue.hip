@@ -1,4 +1,4 @@
-// enf_prologue.hip -- K1 and its backward on the matrix pipe (fp32 `v_mfma_f32_16x16x4_f32`), 16 latents per workgroup.
+// enf_prologue.hip -- the backward of K1 on the matrix pipe (fp32 `v_mfma_f32_16x16x4_f32`), 16 latents per workgroup.
 //
 // The per-latent part of the decoder (NEF:220, NEF:56, ECA:93-94 and the logit fold of enf_pack.hip):
 //   s = a Ws + bs -> LayerNorm -> an;  k = an Wk + bk;  v0 = an Wv + bv;  u_h = MU_h k_h;  c_h = cvec_h . k_h
@@ -9,6 +9,7 @@
 // output features of every layer: each weight element is read once per 16 latents as an A-operand dword (coalesced: the output index
 // on the lanes), activations sit in LDS as [feature][latent] (the B operand is one conflict-free ds_read_b32), accumulator tiles go
 // back to LDS as the next layer's input.  Same arithmetic (fp32 throughout), same buffers (`an`, `kv`, latent table, `pg`).
+// K1 itself stays in enf_pack.hip: in this form it measured 21.0 us against 20.0 there.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <type_traits>
@@ -78,165 +79,6 @@ __device__ __forceinline__ void mm_tiles(pf4 (&acc)[NT], const float* const (&ap
 __device__ __forceinline__ float half_sum(float v) {          // sum over the 32 lanes of a half-wave
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-struct ProArgs {
-  const float* p; const float* a; const float* sigma;
-  const char* blob; EnfLayout L;
-  float* lt; float* an; float* kv;
-  int BZ, H, D, C, dp, inv, Dt;
-};
-
-__global__ __launch_bounds__(64 * PW) void enf_prologue_mfma_kernel(ProArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int D = A.D, H = A.H, HD = H * D, C = A.C;
-  float* s_a = sm;                          // [C][LT]
-  float* s_s = s_a + C * LT;                // [D][LT]   stem output
-  float* s_an = s_s + D * LT;               // [D][LT]   LayerNorm output (affine)
-  float* s_k = s_an + D * LT;               // [2HD][LT] k | v0
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
-  const int row0 = blockIdx.x * LT;
-  auto W = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
-  const int stride = enf_lt_stride(H, D);
-  for (int t = tid; t < LT * C; t += 64 * PW) {
-    const int zz = t / C, c = t % C, r = row0 + zz;
-    s_a[c * LT + zz] = r < A.BZ ? A.a[(size_t)r * C + c] : 0.f;
-  }
-  __syncthreads();
-  const int r_mine = row0 + j;              // this lane's latent in the accumulator layout
-  const bool rok = r_mine < A.BZ;
-  // ---- stem: s = a Ws + bs (NEF:220)
-  for (int t = wave; t < D / 16; t += PW) {
-    pf4 acc = *reinterpret_cast<const pf4*>(W(A.L.stem_b) + 16 * t + 4 * q);
-    mm_tile(acc, W(A.L.stem_w), D, 16 * t, C, s_a, lane);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s_s[(16 * t + 4 * q + e) * LT + j] = acc[e];
-  }
-  __syncthreads();
-  // ---- LayerNorm (NEF:56): biased variance, eps 1e-6, statistics over the Dt real features; one half-wave per latent
-  {
-    const int zz = 2 * wave + (lane >> 5), l32 = lane & 31, r = row0 + zz;
-    float v = 0.f;
-    for (int d = l32; d < A.Dt; d += 32) v += s_s[d * LT + zz];
-    const float mu = half_sum(v) / A.Dt;
-    float qv = 0.f;
-    for (int d = l32; d < A.Dt; d += 32) { const float t = s_s[d * LT + zz] - mu; qv += t * t; }
-    const float rstd = rsqrtf(half_sum(qv) / A.Dt + 1e-6f);
-    for (int d = l32; d < D; d += 32) {
-      const float sv = s_s[d * LT + zz], xn = (sv - mu) * rstd;
-      if (r < A.BZ) {
-        A.an[(size_t)r * (2 * D + 2) + d] = sv;
-        A.an[(size_t)r * (2 * D + 2) + D + d] = xn;
-      }
-      s_an[d * LT + zz] = xn * W(A.L.lna_g)[d] + W(A.L.lna_b)[d];
-    }
-    if (l32 == 0 && r < A.BZ) { A.an[(size_t)r * (2 * D + 2) + 2 * D] = mu; A.an[(size_t)r * (2 * D + 2) + 2 * D + 1] = rstd; }
-  }
-  __syncthreads();
-  // ---- k = an Wk + bk, v0 = an Wv + bv (ECA:93-94): 2 HD output features, a wave's tiles in one pass (shared B operand)
-  {
-    const int T = 2 * HD / 16;                       // 8, 16 or 32 tiles: 1, 2 or 4 per wave
-    auto kv_tiles = [&](auto nt_c) {
-      constexpr int NT = decltype(nt_c)::value;
-      pf4 acc[NT];
-      const float* ap[NT];
-      const float* bp[NT];
-      int f0[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        f0[t] = 16 * (wave + PW * t);
-        const bool isv = f0[t] >= HD;
-        const int c0 = isv ? f0[t] - HD : f0[t];
-        acc[t] = *reinterpret_cast<const pf4*>(W(isv ? A.L.bv : A.L.bk) + c0 + 4 * q);
-        ap[t] = W(isv ? A.L.wv : A.L.wk) + (size_t)q * HD + c0 + j;
-        bp[t] = s_an + q * LT + j;
-      }
-      mm_tiles<NT>(acc, ap, bp, HD, D);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const bool isv = f0[t] >= HD;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s_k[(f0[t] + 4 * q + e) * LT + j] = acc[t][e];
-        if (rok) {
-          *reinterpret_cast<pf4*>(A.kv + (size_t)r_mine * 2 * HD + f0[t] + 4 * q) = acc[t];
-          if (isv) *reinterpret_cast<pf4*>(A.lt + (size_t)r_mine * stride + enf_lt_off_v0(H, D) + f0[t] - HD + 4 * q) = acc[t];
-        }
-      }
-    };
-    if (T == 32) kv_tiles(std::integral_constant<int, 4>{});
-    else if (T == 16) kv_tiles(std::integral_constant<int, 2>{});
-    else kv_tiles(std::integral_constant<int, 1>{});
-  }
-  __syncthreads();
-  // ---- u_h = MU_h k_h (mut[h][d][i]: the output index i contiguous)
-  {
-    const int T = HD / 16;                           // 4, 8 or 16 tiles
-    auto u_tiles = [&](auto nt_c) {
-      constexpr int NT = decltype(nt_c)::value;
-      pf4 acc[NT];
-      const float* ap[NT];
-      const float* bp[NT];
-      int f0[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        f0[t] = 16 * (wave + PW * t);
-        const int h = f0[t] / D, i0 = f0[t] % D;
-        acc[t] = pf4{0.f, 0.f, 0.f, 0.f};
-        ap[t] = W(A.L.mut) + (size_t)h * D * D + (size_t)q * D + i0 + j;
-        bp[t] = s_k + (h * D + q) * LT + j;
-      }
-      mm_tiles<NT>(acc, ap, bp, D, D);
-      if (rok) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) *reinterpret_cast<pf4*>(A.lt + (size_t)r_mine * stride + enf_lt_off_u(H, D) + f0[t] + 4 * q) = acc[t];
-      }
-    };
-    if (T == 16) u_tiles(std::integral_constant<int, 2>{});
-    else if (T == 8 || wave < T) u_tiles(std::integral_constant<int, 1>{});
-  }
-  // ---- c_h = cvec_h . k_h: one half-wave per latent
-  {
-    const int zz = 2 * wave + (lane >> 5), l32 = lane & 31, r = row0 + zz;
-    for (int h = 0; h < H; ++h) {
-      float sacc = 0.f;
-      for (int dd = l32; dd < D; dd += 32) sacc = fmaf(W(A.L.cvec)[h * D + dd], s_k[(h * D + dd) * LT + zz], sacc);
-      sacc = half_sum(sacc);
-      if (l32 == 0 && r < A.BZ) A.lt[(size_t)r * stride + enf_lt_off_c(H, D) + h] = sacc;
-    }
-  }
-  // ---- pose embed (NEF:214-217) + window coefficient (+ ball / ball_lat: rotation matrix and RFF phases)
-  if (tid < LT) {
-    const int r = row0 + tid;
-    if (r < A.BZ) {
-      const float* pp = A.p + (size_t)r * A.dp;
-      float qv[4] = {0.f, 0.f, 0.f, 0.f};
-      const float sg = A.sigma ? A.sigma[r] : 1.f;
-      const bool sphere = A.inv == ENF_INV_LATITUDE_PERIODIC || A.inv == ENF_INV_POLAR_PERIODIC || enf_inv_has_phase(A.inv);
-      if (A.inv == ENF_INV_PONITA || A.inv == ENF_INV_PONITA_FULL) { qv[0] = pp[0]; qv[1] = pp[1]; qv[2] = cosf(pp[2]); qv[3] = sinf(pp[2]); }
-      else if (sphere) { qv[0] = pp[0]; qv[1] = pp[1]; qv[2] = sinf(pp[1]); qv[3] = cosf(pp[1]); }
-      else { for (int i = 0; i < A.dp && i < 3; ++i) qv[i] = pp[i]; }
-      const float wc = sphere ? 1.f / (2.f * sg * sg) : 1.f / (sg * sg);
-      float* o = A.lt + (size_t)r * stride;
-      for (int i = 0; i < 4; ++i) o[enf_lt_off_pose(H, D) + i] = qv[i];
-      o[enf_lt_off_wcoef(H, D)] = wc;
-      if (enf_inv_has_phase(A.inv)) {
-        float lat[2] = {0.f, 0.f};
-        if (A.inv == ENF_INV_BALL) {            // R(alpha, beta, gamma), ball.py:76-84; latent-only invariant r_p
-          const float ca = cosf(pp[0]), sa = sinf(pp[0]), cb = cosf(pp[1]), sb = sinf(pp[1]), cg = cosf(pp[2]), sg2 = sinf(pp[2]);
-          float* R = o + enf_lt_off_ext(H, D);
-          R[0] = ca * cb; R[1] = ca * sb * sg2 - sa * cg; R[2] = ca * sb * cg + sa * sg2;
-          R[3] = sa * cb; R[4] = sa * sb * sg2 + ca * cg; R[5] = sa * sb * cg - ca * sg2;
-          R[6] = -sb;     R[7] = cb * sg2;                R[8] = cb * cg;
-          lat[0] = pp[3];
-        } else { lat[0] = pp[1]; lat[1] = pp[3]; }      // ball_lat: th_p, r_p
-        const float* cq = W(A.L.cphq), *cv = W(A.L.cphv);
-        for (int jj = 0; jj < D / 2; ++jj) {            // phase in revolutions (the kernels' sin/cos take 2 pi t)
-          o[enf_lt_off_phq(H, D) + jj] = lat[0] * cq[jj] + lat[1] * cq[D / 2 + jj];
-          o[enf_lt_off_phv(H, D) + jj] = lat[0] * cv[jj] + lat[1] * cv[D / 2 + jj];
-        }
-      }
-    }
-  }
 }
 
 struct ProBwdArgs {
@@ -394,18 +236,6 @@ __global__ __launch_bounds__(64 * PW) void enf_prologue_bwd_mfma_kernel(ProBwdAr
   }
 }
 }  // namespace
-
-extern "C" int enf_launch_prologue_mfma(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* a,
-                                        const float* sigma, float* lt, float* an, float* kv, hipStream_t st) {
-  ProArgs A;
-  A.p = p; A.a = a; A.sigma = sigma; A.blob = blob; A.L = L; A.lt = lt; A.an = an; A.kv = kv;
-  A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp = m.dp; A.inv = m.inv; A.Dt = m.Dt;
-  const size_t smem = sizeof(float) * LT * (m.C + 2 * m.D + 2 * m.HD);
-  static EnfAttrBits attr{0};
-  if (!enf_lds_attr(reinterpret_cast<const void*>(enf_prologue_mfma_kernel), 160 * 1024, attr)) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(enf_prologue_mfma_kernel, dim3((A.BZ + LT - 1) / LT), dim3(64 * PW), smem, st, A);
-  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
 
 extern "C" int enf_launch_prologue_bwd_mfma(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* sigma,
                                             const float* an, const float* kv, const float* dlt, float* dp, float* da, float* dsigma,

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(64 * WZ_WAVES) void enf_wz_kernel(WzArgs A) {
       for (int a = 0; a < 2; ++a) {
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) af[a][kt] = bf[a][kt];
-        if constexpr (BF16 && ENF_ASM_GEMM && GemmStageAsm<KB, NT>::available) {
+        if constexpr (BF16 && GemmStageAsm<KB, NT>::available) {
           GemmStageAsm<KB, NT>::run_flip(af[a], FX[a].f, (unsigned)(uintptr_t)(lds_ptr_t)(smem + (lane << 4)));
         } else {
 #pragma unroll
@@ -207,13 +207,7 @@ static int launch_wz(const WzArgs& A, hipStream_t st) {
   // the backward's call (both orientations) runs on the side stream beside the tail kernels and is off the critical
   // path with half the chip (same-box A/B of the fit: 3.036 ms with 128 workgroups, 3.052 with 256); the decode's call
   // is ON the critical path and takes the whole chip
-#ifdef ENF_AB_SWITCHES       // A/B builds only: ENF_WZ_GRID=n overrides the workgroup count
-  static int envgrid = -1;
-  if (envgrid < 0) { const char* e = getenv("ENF_WZ_GRID"); envgrid = e ? atoi(e) : 0; if (envgrid == 1) envgrid = 2; }
-#else
-  constexpr int envgrid = 0;
-#endif
-  const int maxgrid = envgrid > 0 ? envgrid : (A.wzt ? ENF_WZ_BWD_GRID : ENF_WZ_MAXGRID);
+  const int maxgrid = A.wzt ? ENF_WZ_BWD_GRID : ENF_WZ_MAXGRID;
   const int max_waves = maxgrid * WZ_WAVES;
   int lanes = A.BZ;
   while (lanes * COMBOS > max_waves && lanes > 1) lanes = (lanes + 1) / 2;
