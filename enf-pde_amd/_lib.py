@@ -38,11 +38,12 @@ class EnfDesc(ctypes.Structure):
                [("h_true", ctypes.c_int32), ("d_true", ctypes.c_int32),
                 # per-call options (include/enf_hip.h): the library keeps no settings
                 ("pair_fwd_variant", ctypes.c_int32), ("pair_bwd_variant", ctypes.c_int32), ("mask_mode", ctypes.c_int32),
-                ("mask_signals", ctypes.c_int32), ("reserved", ctypes.c_int32), ("relu_masks", ctypes.c_void_p)]
+                ("mask_signals", ctypes.c_int32), ("embedding", ctypes.c_int32), ("relu_masks", ctypes.c_void_p)]
 
 
 VARIANT = {"auto": 0, "latent_split": 1, "z_fold": 2, "z_fold_zsplit": 3}       # ENF_VARIANT_*
 MASK_MODE = {"off": 0, "write": 1, "read": 2}                # ENF_MASK_*
+EMB = {"rff": 0, "ffn": 1}                                   # ENF_EMB_*
 
 
 class EnfSgdSegment(ctypes.Structure):
@@ -203,13 +204,15 @@ def launch(dev, fn, *args):
 
 
 def make_desc(B, N, Z, H, D, C, O, dx, invariant_id, use_window, precision, d_true=0, h_true=0, variants=(0, 0),
-              masks=None):
-    """``variants``: (forward, backward) ENF_VARIANT_*; ``masks``: None or (int32 device tensor, "write" | "read", signals)."""
+              masks=None, embedding=0):
+    """``variants``: (forward, backward) ENF_VARIANT_*; ``masks``: None or (int32 device tensor, "write" | "read", signals);
+    ``embedding``: ENF_EMB_*."""
     d = EnfDesc()
     d.B, d.N, d.Z, d.H, d.D, d.C, d.O, d.dx = int(B), int(N), int(Z), int(H), int(D), int(C), int(O), int(dx)
     d.invariant_id, d.use_window, d.precision = int(invariant_id), int(bool(use_window)), int(precision)
     d.d_true, d.h_true = int(d_true), int(h_true)
     d.pair_fwd_variant, d.pair_bwd_variant = int(variants[0]), int(variants[1])
+    d.embedding = int(embedding)
     if masks is not None:
         buf, mode, signals = masks
         d.relu_masks, d.mask_mode, d.mask_signals = buf.data_ptr(), MASK_MODE[mode], int(signals)

@@ -73,6 +73,8 @@ extern "C" int enf_check_desc(const EnfDesc* d) {
   if (d->pair_bwd_variant < ENF_VARIANT_AUTO || d->pair_bwd_variant > ENF_VARIANT_ZFOLD) return ENF_EINVAL;
   if (d->mask_mode < ENF_MASK_OFF || d->mask_mode > ENF_MASK_READ || d->mask_signals < 0) return ENF_EINVAL;
   if (d->mask_mode != ENF_MASK_OFF && !d->relu_masks) return ENF_EINVAL;
+  if (d->embedding != ENF_EMB_RFF && d->embedding != ENF_EMB_FFN) return ENF_EINVAL;
+  if (d->embedding == ENF_EMB_FFN && enf_inv_has_phase(d->invariant_id)) return ENF_EUNSUPPORTED;
   return ENF_OK;
 }
 
@@ -439,6 +441,7 @@ extern "C" int enf_backward_weights(const EnfDesc* d, const float* x, int64_t x_
                                     float* const* dpair, float* dx, void* scratch, size_t scratch_bytes, void* stream) {
   int rc = enf_check_desc(d);
   if (rc) return rc;
+  if (d->embedding == ENF_EMB_FFN) return ENF_EUNSUPPORTED;       // the ENF_P_* (composed) path: rff only; ffn trains through enf_backward_all
   if (!x || !lt || !packed || !lse || !dybar || !delta || !dlt || !dpair || !scratch) return ENF_EINVAL;
   for (int i = 0; i < ENF_NUM_PAIR_TENSORS; ++i)
     if (i != ENF_P_COEFQ && i != ENF_P_COEFV && !dpair[i]) return ENF_EINVAL;

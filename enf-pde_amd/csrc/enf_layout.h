@@ -35,6 +35,7 @@ struct EnfDims {
   int OB;      // ceil(O/32) output blocks of the last layer
   // per-call options (EnfDesc): requested pair-kernel variants (ENF_VARIANT_*), relu masks
   int var_fwd, var_bwd, mask_mode, mask_B;
+  int ffn;       // EnfDesc.embedding == ENF_EMB_FFN
   int mask_b0;   // signal index of b = 0 in the batch the masks were taken for (set by chunked passes; 0 otherwise)
   unsigned* masks;
 };
@@ -92,6 +93,7 @@ inline EnfDims enf_dims(const EnfDesc* d) {
   m.I = enf_inv_dim(m.inv, m.dx); m.dp = enf_inv_pose_dim(m.inv, m.dx);
   m.HD = m.H * m.D; m.KB = m.D / 32; m.KBH = m.HD / 32; m.OB = (m.O + 31) / 32;
   m.var_fwd = d->pair_fwd_variant; m.var_bwd = d->pair_bwd_variant;
+  m.ffn = d->embedding == ENF_EMB_FFN;
   m.masks = (unsigned*)d->relu_masks;
   m.mask_mode = m.masks ? d->mask_mode : ENF_MASK_OFF;
   m.mask_B = d->mask_signals > 0 ? d->mask_signals : d->B;
@@ -109,7 +111,8 @@ struct EnfLayout {
   size_t cvec;   // H x D:       c_h    = sum_d cvec[h][d] * k_h[d]
   size_t mut;    // H x (D x D): mu transposed per head ([h][d][i]) for the forward prologue's coalesced reads
   size_t wkt, wvt;   // HD x D: a_to_k / a_to_v kernels transposed, for the prologue backward
-  // ---- coefficient A-operands of t = coeff^T inv (fp32 16x16x4 MFMA), [D/32 t-tiles][64 lanes]
+  // ---- coefficient A-operands of t = coeff^T inv (fp32 16x16x4 MFMA), [D/32 t-tiles][64 lanes]; ffn: Dense_0's kernel
+  //      as 4 rows of D floats (rows >= I zero), the A operand of the pre-activation W0^T inv
   size_t acq, acv;
   size_t cphq, cphv;   // 2 x D/2: coefficient rows of the latent-only invariants (ball, ball_lat), zero otherwise
   // ---- accumulator-init vectors, fp32
@@ -120,7 +123,7 @@ struct EnfLayout {
   size_t atb, atf1, ato0, ato2, ato4;   // KBHxKBH, KBHxKBH, KBxKBH, KBxKB, OBxKB
   // ---- backward panels (A operand = W, in x out): dX = W dY
   size_t gq1, gv1, gf, ggb, gm;         // KBxKB; ggb: H panels of KB x 2KB (out = D, in = that head's [g b ..] 2D)
-  size_t gcq, gcv;                      // 1 x D/64: A[c][t] = 2 pi coeff[c][t]  (d inv = 2 pi coeff d t)
+  size_t gcq, gcv;                      // 1 x D/64: A[c][t] = 2 pi coeff[c][t]  (d inv = 2 pi coeff d t); unused with ffn
   size_t gtb, gtf1, gto0, gto2, gto4;   // KBHxKBH, KBHxKBH, KBHxKB, KBxKB, KBxOB
   // ---- plain fp32 (in,out) copies of folded matrices
   size_t p_af, p_agb, p_wb, p_wf1, p_tmp, p_o4;   // DxD, Dx2HD, HDxHD, HDxHD, HDxHD, Dx(32*OB)
@@ -147,7 +150,8 @@ inline EnfLayout enf_layout(const EnfDims& m) {
   L.wk = take(f * D * HD); L.bk = take(f * HD); L.wv = take(f * D * HD); L.bv = take(f * HD);
   L.mu = take(f * H * D * D); L.cvec = take(f * H * D);
   L.mut = take(f * H * D * D); L.wkt = take(f * HD * D); L.wvt = take(f * HD * D);
-  L.acq = take(f * (D / 32) * 64); L.acv = take(f * (D / 32) * 64);   // D/32 t-tiles x 64 lanes
+  const int EW = m.ffn ? 4 * D : 2 * D;                             // rff: D/32 t-tiles x 64 lanes; ffn: 4 rows of D
+  L.acq = take(f * EW); L.acv = take(f * EW);
   L.cphq = take(f * D); L.cphv = take(f * D);
   L.bq1 = take(f * D); L.bv1 = take(f * D); L.bf = take(f * D); L.bgb = take(f * 2 * HD); L.bm = take(f * D);
   L.bB = take(f * HD); L.bF1 = take(f * HD); L.bO0 = take(f * D); L.bO2 = take(f * D); L.bO4 = take(f * 32 * m.OB);

@@ -164,7 +164,14 @@ static int pack_pair_panels(hipStream_t st, char* blob, const EnfLayout& L, cons
                             const float* coefv) {
   const int D = m.D, H = m.H, HD = m.HD, I = m.I, bf = m.bf16;
   int rc;
-  {
+  if (m.ffn) {
+    // Dense_0 of both branches (I x D, in the R?_COEF slots) as 4 rows of D (zero rows below I): the pre-activation's A operand
+    // and the rows of d inv = W0 d P in the pair kernels.  No ball invariant (enf_check_desc): the rows are in reference order.
+    if (hipMemsetAsync(blob + L.acq, 0, sizeof(float) * 4 * D, st) != hipSuccess) return ENF_ELAUNCH;
+    if (hipMemsetAsync(blob + L.acv, 0, sizeof(float) * 4 * D, st) != hipSuccess) return ENF_ELAUNCH;
+    if (hipMemcpyAsync(blob + L.acq, coefq, sizeof(float) * I * D, hipMemcpyDeviceToDevice, st) != hipSuccess) return ENF_ELAUNCH;
+    if (hipMemcpyAsync(blob + L.acv, coefv, sizeof(float) * I * D, hipMemcpyDeviceToDevice, st) != hipSuccess) return ENF_ELAUNCH;
+  } else {
     // coefficient rows permuted to [per-pair rows | latent-only rows] (identity except for ball / ball_lat)
     float* cq = reinterpret_cast<float*>(blob + L.p_tmp);
     float* cv = cq + 8 * (D / 2);
@@ -180,13 +187,15 @@ static int pack_pair_panels(hipStream_t st, char* blob, const EnfLayout& L, cons
     if ((rc = pack_panel(st, blob, L.gcq, cq, D / 2, 16, D / 2, 1, bf, 8, D / 2, 6.283185307179586f))) return rc;
     if ((rc = pack_panel(st, blob, L.gcv, cv, D / 2, 16, D / 2, 1, bf, 8, D / 2, 6.283185307179586f))) return rc;
   }
-  if ((rc = pack_panel(st, blob, L.aq1, aq1, D, D, D, 0, bf))) return rc;
-  if ((rc = pack_panel(st, blob, L.av1, av1, D, D, D, 0, bf))) return rc;
+  if (!m.ffn) {       // the relu layers' panels (rff only)
+    if ((rc = pack_panel(st, blob, L.aq1, aq1, D, D, D, 0, bf))) return rc;
+    if ((rc = pack_panel(st, blob, L.av1, av1, D, D, D, 0, bf))) return rc;
+    if ((rc = pack_panel(st, blob, L.gq1, aq1, D, D, D, 1, bf))) return rc;
+    if ((rc = pack_panel(st, blob, L.gv1, av1, D, D, D, 1, bf))) return rc;
+  }
   if ((rc = pack_panel(st, blob, L.af, af, D, D, D, 0, bf))) return rc;
   if ((rc = pack_panel(st, blob, L.agb, agb, 2 * HD, 2 * HD, D, 0, bf))) return rc;
   if ((rc = pack_panel(st, blob, L.am, am, D, D, D, 0, bf))) return rc;
-  if ((rc = pack_panel(st, blob, L.gq1, aq1, D, D, D, 1, bf))) return rc;
-  if ((rc = pack_panel(st, blob, L.gv1, av1, D, D, D, 1, bf))) return rc;
   if ((rc = pack_panel(st, blob, L.gf, af, D, D, D, 1, bf))) return rc;
   for (int h = 0; h < H; ++h)   // one K-slice (that head's [g g b b ..] 2D columns) per head
     if ((rc = pack_panel(st, blob, L.ggb + (size_t)h * enf_panel_bytes(D, 2 * D, bf), agb + h * 2 * D, 2 * HD, D, 2 * D, 1, bf))) return rc;
@@ -210,6 +219,7 @@ extern "C" int enf_pack_pair(const EnfDesc* d, const float* const* T, void* pack
   if (!d || !T || !packed) return ENF_EINVAL;
   int rc = enf_check_desc(d);
   if (rc) return rc;
+  if (d->embedding == ENF_EMB_FFN) return ENF_EUNSUPPORTED;          // the training path's pair blob: rff only
   for (int i = 0; i < ENF_NUM_PAIR_TENSORS; ++i)
     if (!T[i]) return ENF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -244,8 +254,9 @@ extern "C" int enf_pack_weights(const EnfDesc* d, const float* const* T, void* p
   if (!d || !T || !packed) return ENF_EINVAL;
   int rc = enf_check_desc(d);
   if (rc) return rc;
+  const bool ffn = d->embedding == ENF_EMB_FFN;
   for (int i = 0; i < ENF_NUM_TENSORS; ++i)
-    if (!T[i]) return ENF_EINVAL;
+    if (!T[i] && !(ffn && (i == ENF_W_RQ_W1 || i == ENF_W_RV_W1))) return ENF_EINVAL;   // ffn: the R?_W1 slots are unused
   hipStream_t st = (hipStream_t)stream;
   const EnfDims m = enf_dims(d);
   const EnfLayout L = enf_layout(m);

@@ -110,13 +110,14 @@ DEV void store_frags(void* base, size_t row, int D, const Frags<BF16, KB>& F, in
   }
 }
 
-template <int D, int H, bool BF16> struct PairBwdSmem {
+template <int D, int H, bool BF16, bool FFN = false> struct PairBwdSmem {
   static constexpr int RING = 0;
   static constexpr int CONSTS = RING + 2 * STAGE_MAX;
-  // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (2D each)
-  static constexpr int N_CONST = 4 * D + 2 * H * D + 4 * D;
-  static constexpr int GC = CONSTS + 4 * N_CONST;                          // gcq | gcv panels
-  static constexpr int GC_BYTES = PanelCfg<D / 64, 1, BF16>::BYTES;
+  static constexpr int EW = FFN ? 4 * D : 2 * D;                           // embedding of one branch: coefficient A-operands / Dense_0 rows
+  // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (EW each)
+  static constexpr int N_CONST = 4 * D + 2 * H * D + 2 * EW;
+  static constexpr int GC = CONSTS + 4 * N_CONST;                          // gcq | gcv panels (rff only)
+  static constexpr int GC_BYTES = FFN ? 0 : PanelCfg<D / 64, 1, BF16>::BYTES;
   static constexpr int ZVEC = GC + 2 * GC_BYTES;                           // NWAVES x 2HD floats
   static constexpr int LACC = ZVEC + 4 * NWAVES * 2 * H * D;               // NWAVES x (2 H D/16) x 64 lanes floats: dU | dV0 partial sums
   // ball / ball_lat: NWAVES x 11 x 16 floats, per-column partial sums of d R (9, quad-0 lanes) and of the two latent-only
@@ -134,6 +135,22 @@ template <int D> DEV void rff_embed_bwd(f32x4 (&dT)[D / 32], const f32x4 (&dE)[D
   for (int m = 0; m < TT; ++m)
 #pragma unroll
     for (int i = 0; i < 4; ++i) dT[m][i] = dE[m][i] * E[TT + m][i] - dE[TT + m][i] * E[m][i];
+}
+
+// ffn, STORE: this lane's invariant as a D-wide activation row (features 0..3 = inv, the rest 0), the ENF_S_EQ / ENF_S_EV row
+template <bool BF16, int KB> DEV void ffn_inv_frags(Frags<BF16, KB>& F, const float (&inv)[4], int quad) {
+  f32x4 X[2 * KB];
+#pragma unroll
+  for (int t = 0; t < 2 * KB; ++t) X[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (quad == 0) X[0] = f32x4{inv[0], inv[1], inv[2], inv[3]};
+  make_frags<BF16, KB>(F, X);
+}
+
+// ffn: d inv[c] += sum_f W0[c][f] d P[f] for this lane's query (fp32, the 4 Dense_0 rows of D floats in LDS), in all four quads
+template <int NT> DEV void ffn_dinv(float (&dinv)[4], const f32x4 (&dP)[NT], const float* w0, int quad) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    dinv[c] += xquad_sum(tiles_dot<NT>([&](int t) { return dP[t]; }, [&](int t) { return rowvec(w0 + c * 16 * NT, t, quad); }));
 }
 
 // gamma/beta panel of one head: transposed product -> v = v0 (1+gamma) + beta (as gb_panel), and the
@@ -310,7 +327,14 @@ DEV void pair_invariant_bwd(int inv_id, int dx, const QueryPt& q, const f32x4& p
 // invariant chosen at run time the tile loop carries the switch of pair_invariant / pair_invariant_bwd -- ~2000 instructions of
 // wave-uniform branches whose join points cost spilled registers, and every scratch reload's s_waitcnt vmcnt(0) also waits for
 // the LDS-DMA stage in flight: 4.9 k of a tile's 66 k cycles sat between the last GEMM stage and the next tile's first one.
-template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1>
+// FFN: the ffn embedding (ENF_EMB_FFN).  A tile starts at the AF panel; the embedding's pre-activation P = W0^T inv + b0 is
+// recomputed where it is needed (NT fp32 MFMAs), d P = gelu'(P) d h, and d inv = W0 d P is taken in fp32 from the Dense_0 rows in
+// LDS (ffn_dinv), which replaces the relu layer's two transposed GEMMs, the [sin, cos] backward and the gc panels (the 128-wide
+// fp32 kernel has no LDS left for a D-input gc panel).  d u takes the FLIPPED pre-activation (the same MFMAs, operands swapped).
+// No relu: no masks.  STORE: the embedding's "input" rows ENF_S_EQ / ENF_S_EV hold the invariant in features 0..3 (zeros
+// elsewhere; ffn_inv_frags) and ENF_S_DA1 / ENF_S_DA2 hold d P, so K4's X^T delta products give d W0 in their first I rows and
+// d b0 as the column sums.
+template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1, bool FFN = false>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A) {
   static_assert(!(ZF && STORE), "the activation store needs the unfolded chain");
   static_assert(INV < 0 || INV == ENF_INV_REL_POS_PERIODIC || INV == ENF_INV_LATITUDE_PERIODIC || INV == ENF_INV_POLAR_PERIODIC ||
@@ -318,7 +342,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   const int inv_id = INV >= 0 ? INV : A.inv;
   const int dx_ = INV >= 0 ? 2 : A.dx;
   using Cfg = PairCfg<D, BF16>;
-  using SM = PairBwdSmem<D, H, BF16>;
+  using SM = PairBwdSmem<D, H, BF16, FFN>;
   constexpr int KB = Cfg::KB, NT = Cfg::NT, TT = D / 32;
   constexpr int ST_DD = Cfg::DD::STAGE, ST_GB = Cfg::GB::STAGE, PANEL_GB = Cfg::GB::BYTES;
   using GG = PanelCfg<2 * KB, NT, BF16>;              // one head's d n^ += AGB_h [dgamma; dbeta]
@@ -331,7 +355,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   char* ring = smem + SM::RING;
   float* cst = reinterpret_cast<float*>(smem + SM::CONSTS);
   float* c_bq1 = cst, *c_bv1 = cst + D, *c_bf = cst + 2 * D, *c_bm = cst + 3 * D, *c_bgb = cst + 4 * D;
-  float* c_acq = c_bgb + 2 * H * D, *c_acv = c_acq + 2 * D;
+  float* c_acq = c_bgb + 2 * H * D, *c_acv = c_acq + SM::EW;
   char* gcq = smem + SM::GC, *gcv = gcq + SM::GC_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), col = lane & 15, quad = lane >> 4;
   float* zv = reinterpret_cast<float*>(smem + SM::ZVEC) + wave * 2 * H * D;
@@ -362,7 +386,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   for (int i = tid; i < D; i += NTHREADS) { c_bq1[i] = G(A.L.bq1)[i]; c_bv1[i] = G(A.L.bv1)[i]; c_bf[i] = G(A.L.bf)[i]; c_bm[i] = G(A.L.bm)[i]; }
   if constexpr (ZF) { for (int i = tid; i < H * D; i += NTHREADS) c_bgb[i] = G(A.L.p_opbg)[i]; }     // 1 + bgamma_h
   else { for (int i = tid; i < 2 * H * D; i += NTHREADS) c_bgb[i] = G(A.L.bgb)[i]; }
-  for (int i = tid; i < 2 * D; i += NTHREADS) { c_acq[i] = G(A.L.acq)[i]; c_acv[i] = G(A.L.acv)[i]; }
+  for (int i = tid; i < SM::EW; i += NTHREADS) { c_acq[i] = G(A.L.acq)[i]; c_acv[i] = G(A.L.acv)[i]; }
   for (int i = tid; i < SM::GC_BYTES / 4; i += NTHREADS) {
     reinterpret_cast<float*>(gcq)[i] = G(A.L.gcq)[i];
     reinterpret_cast<float*>(gcv)[i] = G(A.L.gcv)[i];
@@ -408,8 +432,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   if constexpr (ZF) P.rs2 = make_blob_rsrc(A.wzt + (size_t)bzc * H * 2 * PANEL_DD, (unsigned)(H * 2 * PANEL_DD));
   else P.rs2 = P.rs;
   const unsigned pWG = (unsigned)A.L.awg;
-  first_stage<ST_DD, NW>(P, ring, pQ1, wave, lane);
-  if constexpr (LA) stage_issue_p<ST_DD, NW>(P, pV1, ring + STAGE_MAX, lane);       // the second stage is in flight from here on
+  first_stage<ST_DD, NW>(P, ring, FFN ? pF : pQ1, wave, lane);
+  if constexpr (LA) stage_issue_p<ST_DD, NW>(P, FFN ? STAGE_RS2 : pV1, ring + STAGE_MAX, lane);       // the second stage is in flight from here on
 
   // per-lane partial sums over this wave's queries.  dU/dV0: lane (col, quad) holds feature
   // 16 t + col, summed over the queries n = 4 quad + i of every tile (flipped products).
@@ -462,17 +486,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     unsigned maskq = 0u, maskv = 0u;     // STORE with A.masks: this tile's relu masks (query / value RFFNet layer)
     {
       f32x4 acc[NT];
-      rff_embed<D, BF16>(acc, inv, c_acq, lane, quad, phq);
-      make_frags<BF16, KB>(F, acc);
-      panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(acc, F, P, ring, pQ1, LA ? pF : pV1, true, lane, c_bq1);
-      if constexpr (STORE) {
+      if constexpr (FFN) {
+        ffn_pre<D>(acc, inv, c_acq, c_bq1, col, quad);
+        gelu_tiles<NT>(acc);
+      } else {
+        rff_embed<D, BF16>(acc, inv, c_acq, lane, quad, phq);
+        make_frags<BF16, KB>(F, acc);
+        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(acc, F, P, ring, pQ1, LA ? pF : pV1, true, lane, c_bq1);
+      }
+      if constexpr (STORE && !FFN) {
         if (A.masks) {        // relu linearised at the masks' point: h1 = a1 where the bit is set (not max(a1, 0))
           maskq = A.masks[relu_mask_index((b + A.mask_b0) % A.mask_B, A.Z, bzc % A.Z, (A.N + 15) / 16, n0 / 16, 0, lane)];
           maskv = A.masks[relu_mask_index((b + A.mask_b0) % A.mask_B, A.Z, bzc % A.Z, (A.N + 15) / 16, n0 / 16, 1, lane)];
           relu_apply_mask<NT>(acc, maskq);
         }
       }
-      const bool masked = STORE && A.masks != nullptr;
+      const bool masked = FFN || (STORE && A.masks != nullptr);     // (ffn: acc = gelu(P) already, no relu)
 #pragma unroll
       for (int h = 0; h < H; ++h) {
         const float s = tiles_dot<NT>(
@@ -491,26 +520,38 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     {
       f32x4 a3[NT], nh[NT];
       f32x4 acc[NT];
-      rff_embed<D, BF16>(acc, inv, c_acv, lane, quad, phv);
-      make_frags<BF16, KB>(F, acc);
-      if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_EV), srow, D, F, quad);
-      panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(acc, F, P, ring, pV1, LA ? STAGE_RS2 : pF, true, lane, c_bv1);
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (STORE && A.masks) {
-            acc[t][i] = (maskv >> (4 * t + i)) & 1u ? acc[t][i] : 0.f;
-          } else {
-            // relu as an integer maximum (relu_f), the mask bit from its bits: min(bits, 1) is 1 exactly where a2 > 0 -- three
-            // instructions per element where compare + select + or + a NaN-quieting fmaxf were five
-            if (acc[t][i] > 0.f) relu_mask |= 1u << (4 * t + i);
-            acc[t][i] = fmaxf(acc[t][i], 0.f);
-          }
+      if constexpr (FFN) {
+        ffn_pre<D>(acc, inv, c_acv, c_bv1, col, quad);
+        gelu_tiles<NT>(acc);
+        make_frags<BF16, KB>(F, acc);
+        if (swrite) {
+          store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_G1), srow, D, F, quad);
+          Frags<BF16, KB> FI;
+          ffn_inv_frags<BF16, KB>(FI, inv, quad);
+          store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_EV), srow, D, FI, quad);
         }
-      if (STORE && A.masks) relu_mask = maskv;
-      make_frags<BF16, KB>(F, acc);
-      if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_G1), srow, D, F, quad);
+      } else {
+        rff_embed<D, BF16>(acc, inv, c_acv, lane, quad, phv);
+        make_frags<BF16, KB>(F, acc);
+        if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_EV), srow, D, F, quad);
+        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(acc, F, P, ring, pV1, LA ? STAGE_RS2 : pF, true, lane, c_bv1);
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (STORE && A.masks) {
+              acc[t][i] = (maskv >> (4 * t + i)) & 1u ? acc[t][i] : 0.f;
+            } else {
+              // relu as an integer maximum (relu_f), the mask bit from its bits: min(bits, 1) is 1 exactly where a2 > 0 -- three
+              // instructions per element where compare + select + or + a NaN-quieting fmaxf were five
+              if (acc[t][i] > 0.f) relu_mask |= 1u << (4 * t + i);
+              acc[t][i] = fmaxf(acc[t][i], 0.f);
+            }
+          }
+        if (STORE && A.masks) relu_mask = maskv;
+        make_frags<BF16, KB>(F, acc);
+        if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_G1), srow, D, F, quad);
+      }
       if constexpr (ZF) panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_BIAS, LA>(a3, F, P, ring, pF, LA ? gM : STAGE_RS2, true, lane, c_bf);
       else panel_gemm<KB, NT, BF16, ST_GB, NWAVES, INIT_BIAS>(a3, F, P, ring, pF, pGB, true, lane, c_bf);
       // nh = gelu(a3), a3 <- gelu'(a3) from one exp + rcp per element (one tile at a time, as in the heads); the backward
@@ -616,7 +657,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         for (int h = 0; h < H; ++h) {
           const unsigned wzb = (STAGE_RS2 | (unsigned)(h * 2 * PANEL_DD)) + PANEL_DD;
           const unsigned after = h + 1 < H ? wzb + 2 * PANEL_DD : gF;                                   // next stage
-          const unsigned after2 = h + 2 < H ? wzb + 4 * PANEL_DD : (h + 2 == H ? gF : gV1);              // the one after that
+          const unsigned after2 = h + 2 < H ? wzb + 4 * PANEL_DD : (h + 2 == H ? gF : FFN ? (ti + 1 < my_tiles ? pF : NO_STAGE) : gV1);   // the one after that
           if (h == 0) panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(dnh, FAh[h], P, ring, wzb, LA ? after2 : after, true, lane);
           else panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ACC, LA>(dnh, FAh[h], P, ring, wzb, LA ? after2 : after, true, lane);
         }
@@ -762,27 +803,95 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       make_frags<BF16, KB>(F, dnh);
       if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_DA3), srow, D, F, quad);
       f32x4 acc[NT];
-      panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(acc, F, P, ring, gF, LA ? pQ1 : gV1, true, lane);       // d g1
+      if constexpr (FFN) {
+        // next: the next tile's first stage (pF) and, looking ahead, the one after it (its first head's W_zh panel); none after the last tile
+        const bool more = ti + 1 < my_tiles;
+        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(acc, F, P, ring, gF, more ? (LA ? STAGE_RS2 : pF) : NO_STAGE, true, lane);   // d h_v
+        f32x4 pre[NT];
+        ffn_pre<D>(pre, inv, c_acv, c_bv1, col, quad);                                                                // recomputed
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
+        for (int t = 0; t < NT; ++t) {
+          f32x4 g;
+          gelu_fg_tile(pre[t], g);                                                                                      // pre <- gelu'(P)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)       // d a2
-          acc[t][i] = ((relu_mask >> (4 * t + i)) & 1u) ? acc[t][i] : 0.f;
-      make_frags<BF16, KB>(F, acc);
-      if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_DA2), srow, D, F, quad);
-      panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(acc, F, P, ring, gV1, LA ? gQ1 : pQ1, true, lane);      // d E_v
-      f32x4 Ev[NT];
-      rff_embed<D, BF16>(Ev, inv, c_acv, lane, quad, phv);                                                           // recomputed
-      f32x4 dT[TT];
-      rff_embed_bwd<D>(dT, acc, Ev);
-      Frags<BF16, D / 64> FT;
-      make_frags<BF16, D / 64>(FT, dT);
-      f32x4 di[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      gemm_stage<BF16, D / 64, 1>(di, FT, gcv, lane);
-      if (quad == 0) { dinv[0] += di[0][0]; dinv[1] += di[0][1]; dinv[2] += di[0][2]; dinv[3] += di[0][3]; }
-      else if (quad == 1) { dlat[0] += di[0][0]; dlat[1] += di[0][1]; }
+          for (int i = 0; i < 4; ++i) acc[t][i] *= pre[t][i];                                                           // d P_v
+        }
+        if (swrite) {
+          Frags<BF16, KB> FD;
+          make_frags<BF16, KB>(FD, acc);
+          store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_DA2), srow, D, FD, quad);
+        }
+        ffn_dinv<NT>(dinv, acc, c_acv, quad);                                                                           // W0_v d P_v
+      } else {
+        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(acc, F, P, ring, gF, LA ? pQ1 : gV1, true, lane);       // d g1
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)       // d a2
+            acc[t][i] = ((relu_mask >> (4 * t + i)) & 1u) ? acc[t][i] : 0.f;
+        make_frags<BF16, KB>(F, acc);
+        if (swrite) store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_DA2), srow, D, F, quad);
+        panel_gemm<KB, NT, BF16, ST_DD, NWAVES, INIT_ZERO, LA>(acc, F, P, ring, gV1, LA ? gQ1 : pQ1, true, lane);      // d E_v
+        f32x4 Ev[NT];
+        rff_embed<D, BF16>(Ev, inv, c_acv, lane, quad, phv);                                                           // recomputed
+        f32x4 dT[TT];
+        rff_embed_bwd<D>(dT, acc, Ev);
+        Frags<BF16, D / 64> FT;
+        make_frags<BF16, D / 64>(FT, dT);
+        f32x4 di[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+        gemm_stage<BF16, D / 64, 1>(di, FT, gcv, lane);
+        if (quad == 0) { dinv[0] += di[0][0]; dinv[1] += di[0][1]; dinv[2] += di[0][2]; dinv[3] += di[0][3]; }
+        else if (quad == 1) { dlat[0] += di[0][0]; dlat[1] += di[0][1]; }
+      }
     }
     BSTAMP(16);
+    if constexpr (FFN) {
+      // ---------------- q-branch: d u[f] += sum_n dlogit[n] h[n][f] on the flipped h (rows = queries); d P_q = gelu'(P_q) d h with
+      // d h = sum_h dlogit_h u_h; d inv += W0_q d P_q
+      float dl[H][4];                     // dlogit of the 4 queries this lane's flipped rows hold
+#pragma unroll
+      for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dl[h][i] = __shfl(dlogit[h], (quad << 4) | (4 * quad + i), 64);
+      {
+        f32x4 hf[NT];
+        ffn_pre_flip<D>(hf, inv, c_acq, c_bq1, col, quad);
+        gelu_tiles<NT>(hf);
+        float upart[H][NT];
+#pragma unroll
+        for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+          for (int h = 0; h < H; ++h) {
+            const f32x2 p2 = __builtin_elementwise_fma(hi2(hf[mt]), f32x2{dl[h][2], dl[h][3]}, lo2(hf[mt]) * f32x2{dl[h][0], dl[h][1]});
+            upart[h][mt] = p2[0] + p2[1];
+          }
+#pragma unroll
+        for (int h = 0; h < H; ++h) lacc_flush(h * NT, upart[h]);
+      }
+      f32x4 pre[NT];
+      ffn_pre<D>(pre, inv, c_acq, c_bq1, col, quad);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        f32x4 g, dh = {0.f, 0.f, 0.f, 0.f};
+        gelu_fg_tile(pre[t], g);                                                                                        // pre <- gelu'(P)
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          const f32x4 u = rowvec(zv + h * D, t, quad);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) dh[i] = fmaf(dlogit[h], u[i], dh[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pre[t][i] *= dh[i];                                                                 // d P_q
+      }
+      if (swrite) {
+        Frags<BF16, KB> FS;
+        make_frags<BF16, KB>(FS, pre);
+        store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_DA1), srow, D, FS, quad);
+        ffn_inv_frags<BF16, KB>(FS, inv, quad);
+        store_frags<BF16, KB>(k3_store_ptr(A, ENF_S_EQ), srow, D, FS, quad);
+      }
+      ffn_dinv<NT>(dinv, pre, c_acq, quad);                                                                            // W0_q d P_q
+    } else
     // ---------------- q-branch: recompute a1 (transposed, for the relu mask of d h1) and its flipped
     // twin h1f (rows = queries) for d u[f] += sum_n dlogit[n] h1f[n][f]
     {
@@ -956,10 +1065,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   WSTAMP(3);
 }
 
-template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1>
+template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1, bool FFN = false>
 static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
-  using SM = PairBwdSmem<D, H, BF16>;
-  auto kern = enf_pair_bwd_kernel<D, H, BF16, STORE, ZF, INV>;
+  using SM = PairBwdSmem<D, H, BF16, FFN>;
+  auto kern = enf_pair_bwd_kernel<D, H, BF16, STORE, ZF, INV, FFN>;
   static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
   if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
   dim3 grid(ZF ? A.B * A.Z : (A.B * A.Z + NWAVES - 1) / NWAVES, A.nsplit);
@@ -988,6 +1097,22 @@ extern "C" int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const c
   A.xcd_remap = zf && ns > 1 && wgs % 8 == 0;
   if (store)
     for (int i = 0; i < ENF_NUM_STORE(m.H); ++i) A.store[i] = store[i];
+  if (m.ffn) {                 // the ffn embedding: every shape of the rff set, run-time invariant; no relu, so no masks
+    A.masks = nullptr;
+#define ENF_FFN_CASE(DD, HH)                                                                                                       \
+    if (m.D == DD && m.H == HH) {                                                                                                 \
+      if (store) return m.bf16 ? launch_pair_bwd<DD, HH, true, true, false, -1, true>(A, st) : launch_pair_bwd<DD, HH, false, true, false, -1, true>(A, st); \
+      if (zf) return m.bf16 ? launch_pair_bwd<DD, HH, true, false, true, -1, true>(A, st) : launch_pair_bwd<DD, HH, false, false, true, -1, true>(A, st); \
+      return m.bf16 ? launch_pair_bwd<DD, HH, true, false, false, -1, true>(A, st) : launch_pair_bwd<DD, HH, false, false, false, -1, true>(A, st);      \
+    }
+    ENF_FFN_CASE(128, 2)
+    ENF_FFN_CASE(64, 2)
+    ENF_FFN_CASE(128, 1)
+    ENF_FFN_CASE(64, 1)
+    ENF_FFN_CASE(64, 4)
+#undef ENF_FFN_CASE
+    return ENF_EUNSUPPORTED;
+  }
 #define ENF_CASE(DD, HH)                                                                   \
   if (m.D == DD && m.H == HH) {                                                            \
     if (store) return m.bf16 ? launch_pair_bwd<DD, HH, true, true, false>(A, st) : launch_pair_bwd<DD, HH, false, true, false>(A, st); \

@@ -61,3 +61,24 @@ DEV void rff_embed(f32x4 (&E)[D / 16], const float (&inv)[4], const float* cfrag
     for (int i = 0; i < 4; ++i) { E[tt][i] = sin_rev<BF16>(t[i]); E[TT + tt][i] = cos_rev<BF16>(t[i]); }
   }
 }
+
+// ffn embedding (embedding/linear.py, FFNEmbedding): pre-activation P = W0^T inv + b0 of this lane's pair, one fp32 MFMA per
+// 16 features (K = 4 = the invariant components), the accumulator started from Dense_0's bias as rff_embed starts it from the
+// phase; the caller applies gelu.  `w0`: Dense_0's kernel as 4 rows of D floats (rows >= I zero), `bias`: b0 (D floats).  The
+// A operand of lane (col, quad) is W0[quad][16 t + col].
+template <int D>
+DEV void ffn_pre(f32x4 (&P)[D / 16], const float (&inv)[4], const float* w0, const float* bias, int col, int quad) {
+  const float bq = quad == 0 ? inv[0] : quad == 1 ? inv[1] : quad == 2 ? inv[2] : inv[3];
+#pragma unroll
+  for (int t = 0; t < D / 16; ++t) P[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[quad * D + 16 * t + col], bq, rowvec(bias, t, quad), 0, 0, 0);
+}
+// the same product FLIPPED (operands swapped): rows = this tile's 16 queries (4 quad + i), column = feature 16 t + col
+template <int D>
+DEV void ffn_pre_flip(f32x4 (&P)[D / 16], const float (&inv)[4], const float* w0, const float* bias, int col, int quad) {
+  const float bq = quad == 0 ? inv[0] : quad == 1 ? inv[1] : quad == 2 ? inv[2] : inv[3];
+#pragma unroll
+  for (int t = 0; t < D / 16; ++t) {
+    const float bc = bias[16 * t + col];
+    P[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq, w0[quad * D + 16 * t + col], f32x4{bc, bc, bc, bc}, 0, 0, 0);
+  }
+}

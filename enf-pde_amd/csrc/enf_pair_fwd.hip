@@ -62,7 +62,7 @@ extern "C" int enf_debug_read_stamps(unsigned long long* dst) {
   } while (0)
 // relu-mask modes live in their own instantiation (MASKS): as wave-uniform runtime branches in the one kernel they cost
 // the default path 1.3 % (measured)
-#define K2_MASK_MODE (MASKS ? A.mask_mode : 0)
+#define K2_MASK_MODE (MASKS && !FFN ? A.mask_mode : 0)
 #ifndef ENF_ZFOLD_WAVES
 #define ENF_ZFOLD_WAVES 8
 #endif
@@ -72,10 +72,11 @@ extern "C" int enf_debug_read_stamps(unsigned long long* dst) {
 // keeps the vector ALU busy (8-wave lockstep measured 2 V + M per stage, M = the younger wave's MFMAs).
 template <bool ZFOLD> struct PairWaves { static constexpr int NW = ZFOLD && ENF_ZFOLD_WAVES == 4 ? 4 : NWAVES; };
 
-template <int D, int H, bool BF16, int NW> struct PairSmem {
+template <int D, int H, bool BF16, int NW, bool FFN = false> struct PairSmem {
   static constexpr int RING = 0;                                   // 2 slots
-  static constexpr int CONSTS = RING + 2 * STAGE_MAX;              // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (2D each)
-  static constexpr int N_CONST = 4 * D + 2 * H * D + 4 * D;
+  static constexpr int EW = FFN ? 4 * D : 2 * D;                   // embedding of one branch: coefficient A-operands / Dense_0 rows
+  static constexpr int CONSTS = RING + 2 * STAGE_MAX;              // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (EW each)
+  static constexpr int N_CONST = 4 * D + 2 * H * D + 2 * EW;
   static constexpr int ZVEC = CONSTS + 4 * N_CONST;                // NWAVES x 2*H*D floats
   static constexpr int XCH = ZVEC + 4 * NW * 2 * H * D;            // NW x H x 3 x 16 floats
   static constexpr int TOTAL = XCH + 4 * NW * H * 3 * 16;
@@ -88,20 +89,22 @@ template <int D, int H, bool BF16, int NW> struct PairSmem {
 //   a5_h = W_zh^T n + c_zh      (5 D x D GEMMs per pair instead of 9 D x D equivalents)
 // INV >= 0: the invariant as a compile-time constant (the shipped configs' instantiations, launch code below): the per-latent step then
 // carries no switch over the invariant (as in K3, enf_pair_bwd.hip)
-template <int D, int H, bool BF16, bool ZFOLD, bool MASKS, int INV = -1>
+// FFN: the ffn embedding (ENF_EMB_FFN) in both branches: h = gelu(W0^T inv + b0) takes the place of the relu layer's output, so
+// a latent step starts at the AF panel (the relu-layer panels aq1 / av1 and the relu masks do not exist)
+template <int D, int H, bool BF16, bool ZFOLD, bool MASKS, int INV = -1, bool FFN = false>
 __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_kernel(PairFwdArgs A) {
   const int inv_id = INV >= 0 ? INV : A.inv;
   const int dx_ = INV >= 0 ? 2 : A.dx;
   using Cfg = PairCfg<D, BF16>;
   constexpr int NW = PairWaves<ZFOLD>::NW, NTH = 64 * NW;
-  using SM = PairSmem<D, H, BF16, NW>;
+  using SM = PairSmem<D, H, BF16, NW, FFN>;
   constexpr int KB = Cfg::KB, NT = Cfg::NT;
   constexpr int ST_DD = Cfg::DD::STAGE, ST_GB = Cfg::GB::STAGE, PANEL_GB = Cfg::GB::BYTES, PANEL_DD = Cfg::DD::BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem + SM::RING;
   float* cst = reinterpret_cast<float*>(smem + SM::CONSTS);
   float* c_bq1 = cst, *c_bv1 = cst + D, *c_bf = cst + 2 * D, *c_bm = cst + 3 * D, *c_bgb = cst + 4 * D;
-  float* c_acq = c_bgb + 2 * H * D, *c_acv = c_acq + 2 * D;
+  float* c_acq = c_bgb + 2 * H * D, *c_acv = c_acq + SM::EW;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
   float* zv = reinterpret_cast<float*>(smem + SM::ZVEC) + wave * 2 * H * D;
   float* xch = reinterpret_cast<float*>(smem + SM::XCH);
@@ -129,9 +132,10 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   // ---- constants -> LDS
   for (int i = tid; i < D; i += NTH) { c_bq1[i] = G(A.L.bq1)[i]; c_bv1[i] = G(A.L.bv1)[i]; c_bf[i] = G(A.L.bf)[i]; c_bm[i] = G(A.L.bm)[i]; }
   for (int i = tid; i < 2 * H * D; i += NTH) c_bgb[i] = G(A.L.bgb)[i];
-  for (int i = tid; i < 2 * D; i += NTH) { c_acq[i] = G(A.L.acq)[i]; c_acv[i] = G(A.L.acv)[i]; }
+  for (int i = tid; i < SM::EW; i += NTH) { c_acq[i] = G(A.L.acq)[i]; c_acv[i] = G(A.L.acv)[i]; }
 
   const unsigned pQ1 = (unsigned)A.L.aq1, pV1 = (unsigned)A.L.av1, pF = (unsigned)A.L.af, pGB = (unsigned)A.L.agb, pM = (unsigned)A.L.am;
+  const unsigned pFirst = FFN ? pF : pQ1;      // the first panel of a latent step
   Pipe P;
   P.rs = make_blob_rsrc(blob, (unsigned)A.L.total);
   float sm_m[H], sm_l[H], sm_c[H];     // softmax state against a per-column reference logit (the first one seen); fp32 accumulators
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * dx_, dx_, inv_id);
   if constexpr (ZFOLD) P.rs2 = make_blob_rsrc(A.wz + (size_t)b * A.Z * H * PANEL_DD, (unsigned)(A.Z * H * PANEL_DD));
   else P.rs2 = P.rs;
-  first_stage<ST_DD, NW>(P, ring, pQ1, wave, lane);
+  first_stage<ST_DD, NW>(P, ring, pFirst, wave, lane);
   // the z-fold stages of this kernel: 2-slot staging (look-ahead and antiphase 3-slot staging measured 3 % / 2 % slower)
   auto zgemm = [&](f32x4 (&acc_)[NT], const Frags<BF16, KB>& F_, unsigned panel_, unsigned next_, bool active_, const float* bias_) {
     panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc_, F_, P, ring, panel_, next_, active_, lane, bias_);
@@ -205,14 +209,19 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
     Frags<BF16, KB> F;
     {  // ---------------- query branch
       f32x4 acc[NT];
-      rff_embed<D, BF16>(acc, inv, c_acq, lane, quad, has_ph ? ltrow + enf_lt_off_phq(H, D) : nullptr);
-      make_frags<BF16, KB>(F, acc);
-      K2_BIAS(acc, c_bq1);
-      STAMP(1);
-      if constexpr (ZFOLD) zgemm(acc, F, pQ1, pV1, active, c_bq1);
-      else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pQ1, pV1, active, lane, c_bq1);
+      if constexpr (FFN) {
+        ffn_pre<D>(acc, inv, c_acq, c_bq1, col, quad);
+        gelu_tiles<NT>(acc);
+      } else {
+        rff_embed<D, BF16>(acc, inv, c_acq, lane, quad, has_ph ? ltrow + enf_lt_off_phq(H, D) : nullptr);
+        make_frags<BF16, KB>(F, acc);
+        K2_BIAS(acc, c_bq1);
+        STAMP(1);
+        if constexpr (ZFOLD) zgemm(acc, F, pQ1, pV1, active, c_bq1);
+        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pQ1, pV1, active, lane, c_bq1);
+      }
       STAMP(2);
-      const bool mread = K2_MASK_MODE == 2;                       // wave-uniform
+      const bool mread = FFN || K2_MASK_MODE == 2;                // wave-uniform; also: no relu to apply (ffn)
       if (K2_MASK_MODE) {
         const size_t mrow = relu_mask_index(b % A.mask_B, A.Z, active ? z : A.Z - 1, (A.N + 15) / 16, n0 / 16, 0, lane);
         if (K2_MASK_MODE == 1 && active && n0 < A.N) A.masks[mrow] = relu_mask_of<NT>(acc);
@@ -247,16 +256,21 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
       }
     }
     STAMP(3);
-    {  // ---------------- value branch: RFFNet layer, folded (linear_final . Dense_0), gelu, LN
+    {  // ---------------- value branch: RFFNet layer (ffn: Dense_0 + gelu), folded (linear_final . Dense_0), gelu, LN
       f32x4 acc[NT];
-      rff_embed<D, BF16>(acc, inv, c_acv, lane, quad, has_ph ? ltrow + enf_lt_off_phv(H, D) : nullptr);
-      make_frags<BF16, KB>(F, acc);
-      K2_BIAS(acc, c_bv1);
-      STAMP(4);
-      if constexpr (ZFOLD) zgemm(acc, F, pV1, pF, active, c_bv1);
-      else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pV1, pF, active, lane, c_bv1);
+      if constexpr (FFN) {
+        ffn_pre<D>(acc, inv, c_acv, c_bv1, col, quad);
+        gelu_tiles<NT>(acc);
+      } else {
+        rff_embed<D, BF16>(acc, inv, c_acv, lane, quad, has_ph ? ltrow + enf_lt_off_phv(H, D) : nullptr);
+        make_frags<BF16, KB>(F, acc);
+        K2_BIAS(acc, c_bv1);
+        STAMP(4);
+        if constexpr (ZFOLD) zgemm(acc, F, pV1, pF, active, c_bv1);
+        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pV1, pF, active, lane, c_bv1);
+      }
       STAMP(5);
-      const bool mread = K2_MASK_MODE == 2;
+      const bool mread = FFN || K2_MASK_MODE == 2;
       if (K2_MASK_MODE) {
         const size_t mrow = relu_mask_index(b % A.mask_B, A.Z, active ? z : A.Z - 1, (A.N + 15) / 16, n0 / 16, 1, lane);
         if (K2_MASK_MODE == 1 && active && n0 < A.N) A.masks[mrow] = relu_mask_of<NT>(acc);
@@ -290,7 +304,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         K2_BIAS(v, zv + H * D + h * D);
         STAMP(10 + 4 * h);
         const bool more = it + 1 < iters;
-        const unsigned nx1 = h + 1 < H ? wzh + PANEL_DD : (more ? pQ1 : NO_STAGE);
+        const unsigned nx1 = h + 1 < H ? wzh + PANEL_DD : (more ? pFirst : NO_STAGE);
         zgemm(v, F, wzh, nx1, active, zv + H * D + h * D);
       } else {
         f32x4 dummy[1];
@@ -302,7 +316,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         K2_BIAS(v, c_bm);
         STAMP(10 + 4 * h);
         if (h + 1 < H) panel_gemm<KB, NT, BF16, ST_GB, NW, INIT_ACC>(v, FV, P, ring, pM, pGB + (h + 1) * PANEL_GB, active, lane, c_bm);
-        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(v, FV, P, ring, pM, it + 1 < iters ? pQ1 : NO_STAGE, active, lane, c_bm);
+        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(v, FV, P, ring, pM, it + 1 < iters ? pFirst : NO_STAGE, active, lane, c_bm);
       }
       STAMP(11 + 4 * h);
       gelu_tiles<NT>(v);
@@ -456,14 +470,14 @@ __global__ __launch_bounds__(256) void enf_zsplit_merge_kernel(const float* __re
   if (c % D == 0) lse[(size_t)row * H + h] = ms + __logf(L);
 }
 
-template <int D, int H, bool BF16, bool ZFOLD, bool MASKS = false, int INV = -1>
+template <int D, int H, bool BF16, bool ZFOLD, bool MASKS = false, int INV = -1, bool FFN = false>
 static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
-  if constexpr (!MASKS) {
+  if constexpr (!MASKS && !FFN) {
     if (A.mask_mode) return launch_pair_fwd<D, H, BF16, ZFOLD, true>(A, st);       // (the masked passes keep the run-time invariant)
   }
   constexpr int NW = PairWaves<ZFOLD>::NW;
-  using SM = PairSmem<D, H, BF16, NW>;
-  auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV>;
+  using SM = PairSmem<D, H, BF16, NW, FFN>;
+  auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV, FFN>;
   static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
   if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
   dim3 grid((A.N + 16 * A.qg - 1) / (16 * A.qg), A.B);
@@ -488,7 +502,7 @@ extern "C" int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const c
   PairFwdArgs A;
   A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.ybar = ybar; A.lse = lse; A.wz = wz; A.wzb = wzb; A.wzu = wzu; A.inv_d = 1.0f / (float)m.Dt;
   A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
-  A.masks = m.masks; A.mask_mode = (run_pair & 1) ? m.mask_mode : 0; A.mask_B = m.mask_B;
+  A.masks = m.masks; A.mask_mode = (run_pair & 1) && !m.ffn ? m.mask_mode : 0; A.mask_B = m.mask_B;   // (ffn: no relu, no masks)
   // as many latent splits as there are latents to split (up to 8); the rest of the 8 waves take more queries
   int zs = 1;
   while (zs < NWAVES && zs * 2 <= m.Z) zs *= 2;
@@ -508,6 +522,20 @@ extern "C" int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const c
     }
   }
   if (!(run_pair & 1)) return 0;
+  if (m.ffn) {                 // the ffn embedding: every shape of the rff set, run-time invariant
+#define ENF_FFN_CASE(DD, HH)                                                                                                      \
+    if (m.D == DD && m.H == HH) {                                                                                                \
+      if (zfold) return m.bf16 ? launch_pair_fwd<DD, HH, true, true, false, -1, true>(A, st) : launch_pair_fwd<DD, HH, false, true, false, -1, true>(A, st); \
+      return m.bf16 ? launch_pair_fwd<DD, HH, true, false, false, -1, true>(A, st) : launch_pair_fwd<DD, HH, false, false, false, -1, true>(A, st);         \
+    }
+    ENF_FFN_CASE(128, 2)
+    ENF_FFN_CASE(64, 2)
+    ENF_FFN_CASE(128, 1)
+    ENF_FFN_CASE(64, 1)
+    ENF_FFN_CASE(64, 4)
+#undef ENF_FFN_CASE
+    return ENF_EUNSUPPORTED;
+  }
 #define ENF_CASE(DD, HH)                                                                                      \
   if (m.D == DD && m.H == HH) {                                                                               \
     if (zfold) return m.bf16 ? launch_pair_fwd<DD, HH, true, true>(A, st) : launch_pair_fwd<DD, HH, false, true>(A, st); \

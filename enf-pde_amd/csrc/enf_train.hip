@@ -264,9 +264,11 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   if (rc) return rc;
   if (!x || !p || !a || !T || !packed || !ybar || !lse || !dout || !dp || !da || !dsigma || !dW || !workspace || !scratch) return ENF_EINVAL;
   if (d->use_window && !sigma) return ENF_EINVAL;
+  const bool ffn = d->embedding == ENF_EMB_FFN;
   for (int i = 0; i < ENF_NUM_TENSORS; ++i) {
-    if (!T[i]) return ENF_EINVAL;
-    if (!dW[i] && i != ENF_W_RQ_COEF && i != ENF_W_RV_COEF) return ENF_EINVAL;
+    const bool unused = ffn && (i == ENF_W_RQ_W1 || i == ENF_W_RV_W1);        // (include/enf_hip.h, ENF_EMB_FFN)
+    if (!T[i] && !unused) return ENF_EINVAL;
+    if (!dW[i] && !unused && i != ENF_W_RQ_COEF && i != ENF_W_RV_COEF) return ENF_EINVAL;
   }
   EnfDims m = enf_dims(d);
   if (m.OB != 1) return ENF_EUNSUPPORTED;
@@ -392,8 +394,16 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   X.gemm(dW[ENF_W_F1_BE], D, dBGB, 2 * HD, 0, T[ENF_W_F1_W1], 2 * HD, 1, 1, D, 2 * HD);
   X.axpy(dW[ENF_W_F1_B1], dBGB, 2 * HD);
   // 6d. direct per-pair tensors
-  X.axpy(dW[ENF_W_RQ_W1], dpair[ENF_P_AQ1], D * D); X.axpy(dW[ENF_W_RQ_B1], dpair[ENF_P_BQ1], D);
-  X.axpy(dW[ENF_W_RV_W1], dpair[ENF_P_AV1], D * D); X.axpy(dW[ENF_W_RV_B1], dpair[ENF_P_BV1], D);
+  if (m.ffn) {
+    // ffn: the store's embedding inputs are the invariant in features 0..3 (enf_pair_bwd.hip), so rows 0..I-1 of the layer's
+    // X^T delta are d Dense_0.kernel (I x D, row-major like the (D, D) product); the bias sums are d Dense_0.bias
+    if (dW[ENF_W_RQ_COEF]) X.axpy(dW[ENF_W_RQ_COEF], dpair[ENF_P_AQ1], m.I * D);
+    if (dW[ENF_W_RV_COEF]) X.axpy(dW[ENF_W_RV_COEF], dpair[ENF_P_AV1], m.I * D);
+    X.axpy(dW[ENF_W_RQ_B1], dpair[ENF_P_BQ1], D); X.axpy(dW[ENF_W_RV_B1], dpair[ENF_P_BV1], D);
+  } else {
+    X.axpy(dW[ENF_W_RQ_W1], dpair[ENF_P_AQ1], D * D); X.axpy(dW[ENF_W_RQ_B1], dpair[ENF_P_BQ1], D);
+    X.axpy(dW[ENF_W_RV_W1], dpair[ENF_P_AV1], D * D); X.axpy(dW[ENF_W_RV_B1], dpair[ENF_P_BV1], D);
+  }
   X.axpy(dW[ENF_W_MX_W0], dpair[ENF_P_AM], D * D);  X.axpy(dW[ENF_W_MX_B0], dpair[ENF_P_BM], D);
   // 6e. WB_h = mxw T_h,  T = AO_W FF_W0,  bB = AO_B FF_W0 + FF_B0 + sum_h mxb T_h;   mxw = diag(MX_G) MX_W1, mxb = MX_BE MX_W1 + MX_B1
   X.gemm(Tm, HD, T[ENF_W_AO_W], HD, 0, T[ENF_W_FF_W0], HD, 0, HD, HD, HD);
@@ -419,6 +429,11 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   X.scale_outer(dW[ENF_W_FF_W1], HD, dwf1, HD, T[ENF_W_FF_G], T[ENF_W_FF_BE], dbF1, HD, HD);
   X.gemm(dW[ENF_W_FF_BE], HD, dbF1, HD, 0, T[ENF_W_FF_W1], HD, 1, 1, HD, HD);
   X.axpy(dW[ENF_W_FF_B1], dbF1, HD);
+  if (m.ffn) {            // the unused R?_W1 slots: exact zeros where the caller gave a buffer
+    if (dW[ENF_W_RQ_W1] && hipMemsetAsync(dW[ENF_W_RQ_W1], 0, sizeof(float) * (size_t)D * D, st) != hipSuccess) return ENF_ELAUNCH;
+    if (dW[ENF_W_RV_W1] && hipMemsetAsync(dW[ENF_W_RV_W1], 0, sizeof(float) * (size_t)D * D, st) != hipSuccess) return ENF_ELAUNCH;
+    return X.rc;
+  }
   // frozen RFF coefficients (rff.py:87-90): zero gradient where the caller asked for one
   if (dW[ENF_W_RQ_COEF] && hipMemsetAsync(dW[ENF_W_RQ_COEF], 0, sizeof(float) * (size_t)m.I * (D / 2), st) != hipSuccess) return ENF_ELAUNCH;
   if (dW[ENF_W_RV_COEF] && hipMemsetAsync(dW[ENF_W_RV_COEF], 0, sizeof(float) * (size_t)m.I * (D / 2), st) != hipSuccess) return ENF_ELAUNCH;

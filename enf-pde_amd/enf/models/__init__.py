@@ -17,7 +17,7 @@ from ..steerable_attention.invariant import BaseInvariant
 from ... import _lib
 from . import _pad
 
-__all__ = ["EquivariantCrossAttentionNeF", "TENSOR_PATHS", "tensor_paths"]
+__all__ = ["EquivariantCrossAttentionNeF", "TENSOR_PATHS", "FFN_TENSOR_PATHS", "tensor_paths"]
 
 _BLK = "cross_attention_blocks_0"
 # ENF_W_* order of include/enf_hip.h -> path in the Flax parameter tree
@@ -53,6 +53,17 @@ TENSOR_PATHS = [
 ]
 assert len(TENSOR_PATHS) == _lib.ENF_NUM_TENSORS
 BLOCK_PATHS = [t[1:] for t in TENSOR_PATHS if t[0] == _BLK]       # the 38 tensors of one attention block
+
+
+def _ffn_paths(branch):
+    e = (_BLK, "attn", f"invariant_embedding_{branch}")
+    return [e + ("Dense_0", "kernel"), None, e + ("Dense_0", "bias"), e + ("Dense_1", "kernel"), e + ("Dense_1", "bias")]
+
+
+# the same list for embedding_type="ffn" (include/enf_hip.h, ENF_EMB_FFN): Dense_0 takes the R?_COEF / R?_B1 slots, Dense_1 the
+# linear_final slots R?_W2 / R?_B2; the R?_W1 slots have no tensor (None)
+FFN_TENSOR_PATHS = TENSOR_PATHS[:4] + _ffn_paths("query") + _ffn_paths("value") + TENSOR_PATHS[14:]
+assert len(FFN_TENSOR_PATHS) == _lib.ENF_NUM_TENSORS
 
 
 def tensor_paths(num_layers=0):
@@ -163,14 +174,23 @@ class EquivariantCrossAttentionNeF:
                  condition_value_transform=True, use_gaussian_window=True, precision="bf16"):
         if not isinstance(cross_attn_invariant, BaseInvariant):
             raise TypeError("cross_attn_invariant must come from enf.steerable_attention.invariant.get_ca_invariant")
-        if embedding_type != "rff":
-            if embedding_type in ("ffn", "polynomial"):
+        if embedding_type not in ("rff", "ffn"):
+            if embedding_type == "polynomial":
                 raise NotImplementedError(f"embedding type '{embedding_type}' is outside the accelerated path "
                                           "(no shipped config selects it; SURVEY.md 2, row 2)")
             raise ValueError(f"Unknown embedding type: {embedding_type}.")          # EMB:33
+        if embedding_type == "ffn":
+            if int(num_layers) > 0:
+                raise NotImplementedError("embedding type 'ffn' is built for num_layers = 0 only (no latent self-attention)")
+            if cross_attn_invariant.name in ("ball", "ball_lat"):
+                raise NotImplementedError(f"embedding type 'ffn' is not built for the '{cross_attn_invariant.name}' invariant")
         if not condition_value_transform:
             raise NotImplementedError("condition_value_transform=False is not on the accelerated path")
-        assert not num_hidden % 2, "For the Fourier Features hidden_dim should be even to calculate them correctly."  # RFF:75-77
+        if embedding_type == "rff":
+            assert not num_hidden % 2, "For the Fourier Features hidden_dim should be even to calculate them correctly."  # RFF:75-77
+        elif num_hidden % 2:
+            # (the reference takes any width for ffn; the kernels' zero-padded widths are even: EnfDesc.d_true)
+            raise NotImplementedError(f"embedding type 'ffn' is built for an even num_hidden, not {num_hidden}")
         if precision not in _lib.PREC:
             raise ValueError(f"unknown precision {precision!r}")
         self.num_hidden, self.num_heads, self.num_layers = int(num_hidden), int(num_heads), int(num_layers)
@@ -220,7 +240,7 @@ class EquivariantCrossAttentionNeF:
                               d_true=self.num_hidden if self._Dp != self.num_hidden else 0,
                               h_true=self.num_heads if self._Hp != self.num_heads else 0,
                               variants=tuple(_lib.VARIANT[v] for v in (self.pair_variants or self.default_pair_variants)),
-                              masks=masks)
+                              masks=masks, embedding=_lib.EMB[self.embedding_type])
 
     def _workspace(self, desc, device):
         # one cached scratch buffer per (shape, stream); the autograd graph never keeps it alive
@@ -287,8 +307,12 @@ class EquivariantCrossAttentionNeF:
                     "layers_0": {"linear": {"kernel": normal((D, D), math.sqrt(2.0 / D)), "bias": normal((D,), 1e-6)}},  # RFF:55-60
                     "linear_final": {"kernel": (torch.rand((D, D), generator=g) * 2 - 1) * lim, "bias": normal((D,), 1e-6)}}  # RFF:35-40
 
-        fq, fv = self.embedding_freq_multiplier
-        attn = {"invariant_embedding_query": rff(fq), "invariant_embedding_value": rff(fv),
+        def ffn_emb():      # FFNEmbedding (embedding/linear.py): Dense(I -> D) -> gelu -> Dense(D -> D), flax defaults
+            return {"Dense_0": lecun(I, D), "Dense_1": lecun(D, D)}
+
+        fq, fv = self.embedding_freq_multiplier        # (ignored by ffn, as in the reference: embedding/__init__.py:25-33)
+        emb_q, emb_v = (ffn_emb(), ffn_emb()) if self.embedding_type == "ffn" else (rff(fq), rff(fv))
+        attn = {"invariant_embedding_query": emb_q, "invariant_embedding_value": emb_v,
                 "inv_emb_to_q": lecun(D, HD), "a_to_k": lecun(D, HD), "a_to_v": lecun(D, HD),
                 "inv_emb_to_v": ffn(D, D, 2 * HD), "inv_emb_cond_mixer": ffn(D, D, D), "out_proj": lecun(HD, HD)}
         P = {"latent_stem": lecun(C, D),
@@ -311,10 +335,19 @@ class EquivariantCrossAttentionNeF:
             return {k: to_dev(v) for k, v in t.items()} if isinstance(t, dict) else t.to(device=device, dtype=torch.float32)
         return {"params": to_dev(P)}
 
+    def tensor_paths(self):
+        """This model's tensor paths in C-ABI order: ``tensor_paths(num_layers)`` for rff, FFN_TENSOR_PATHS (None in the unused
+        ENF_W_R?_W1 slots) for ffn."""
+        return FFN_TENSOR_PATHS if self.embedding_type == "ffn" else tensor_paths(self.num_layers)
+
     def param_tensors(self, params):
-        """The ENF_NUM_TENSORS weight tensors in C-ABI order (then, for num_layers > 0, 38 per self-attention block)."""
+        """The ENF_NUM_TENSORS weight tensors in C-ABI order (then, for num_layers > 0, 38 per self-attention block); ffn: an
+        empty tensor in each unused ENF_W_R?_W1 slot (so that optimiser states, all-reduces and the trainers' lists keep their
+        46 entries; its gradient is None, like the frozen rff coefficients')."""
         P = params["params"] if "params" in params else params
-        return [_get(P, path) for path in tensor_paths(self.num_layers)]
+        paths = self.tensor_paths()
+        dev = _get(P, paths[0]).device
+        return [torch.empty(0, device=dev) if path is None else _get(P, path) for path in paths]
 
     def invalidate_caches(self):
         """Forget the packed-weight blob, the packed pair panels of the training path and the latent tables held in workspaces.
@@ -335,8 +368,9 @@ class EquivariantCrossAttentionNeF:
         self.invalidate_caches()
         P = tree["params"] if "params" in tree else tree
         out = {}
-        for path in tensor_paths(self.num_layers):
-            _set(out, path, torch.as_tensor(_get(P, path)).to(device=device, dtype=torch.float32).contiguous())
+        for path in self.tensor_paths():
+            if path is not None:
+                _set(out, path, torch.as_tensor(_get(P, path)).to(device=device, dtype=torch.float32).contiguous())
         return {"params": out}
 
     def pack(self, params):
@@ -346,33 +380,43 @@ class EquivariantCrossAttentionNeF:
         dev = ts[0].device
         if dev.type != "cuda":
             raise _lib.EnfError("parameters must live on the GPU: the decoder has no CPU path")
-        key = (self.precision, tuple((t.data_ptr(), t._version) for t in ts))
+        key = (self.precision, tuple((t.data_ptr(), t._version) if t is not None else None for t in ts))
         hit = self._pack_cache.get("k")
         if hit is not None and hit[0] == key:
             return hit[1]
         desc = self._desc(1, 1, 1)
         _lib.check(lib.enf_check_desc(ctypes.byref(desc)))
-        ts = [t.detach().to(torch.float32).contiguous() for t in ts]
+        ts = [t.detach().to(torch.float32).contiguous() if t is not None else None for t in ts]
         self._check_shapes(ts)
         if self._Dp != self.num_hidden or self._Hp != self.num_heads:
-            ts = [t.contiguous() for t in _pad.pad_tensors(ts, self.num_hidden, self._Dp, self.num_heads, self._Hp)]
+            ts = [t.contiguous() if t is not None else None
+                  for t in _pad.pad_tensors(ts, self.num_hidden, self._Dp, self.num_heads, self._Hp, ffn=self.embedding_type == "ffn")]
         nbytes = lib.enf_packed_weight_bytes(ctypes.byref(desc))
         blob = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
-        arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
         st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.launch(dev, lib.enf_pack_weights, ctypes.byref(desc), arr, _ptr(blob), st)
         self._pack_cache["k"] = (key, blob, ts)   # keep the fp32 sources alive until the pack kernels ran
         return blob
 
     def _check_shapes(self, ts):
-        for t, shp, path in zip(ts, self._expected_shapes(), TENSOR_PATHS):
+        shp_done = []
+        for t, shp, path in zip(ts, self._expected_shapes(), self.tensor_paths()):
+            if shp is None:           # ffn: an unused ENF_W_R?_W1 slot
+                if t is not None and t.numel():
+                    raise ValueError(f"the ffn embedding has no tensor in ENF_W_* slot {len(shp_done)}")
+                shp_done.append(None)
+                continue
+            shp_done.append(shp)
+            if t is None:
+                raise ValueError(f"parameter {'/'.join(path)} is missing")
             if tuple(t.shape) != shp:
                 raise ValueError(f"parameter {'/'.join(path)} has shape {tuple(t.shape)}, expected {shp}")
 
     def _expected_shapes(self):
         D, H, C, O, I = self.num_hidden, self.num_heads, self.latent_dim, self.num_out, self.cross_attn_invariant.dim
         HD = H * D
-        rff = [(I, D // 2), (D, D), (D,), (D, D), (D,)]
+        rff = [(I, D), None, (D,), (D, D), (D,)] if self.embedding_type == "ffn" else [(I, D // 2), (D, D), (D,), (D, D), (D,)]
         return ([(C, D), (D,), (D,), (D,)] + rff + rff + [(D, HD), (HD,)] * 3 +
                 [(D, D), (D,), (D,), (D,), (D, 2 * HD), (2 * HD,)] + [(D, D), (D,), (D,), (D,), (D, D), (D,)] +
                 [(HD, HD), (HD,)] + [(HD, HD), (HD,), (HD,), (HD,), (HD, HD), (HD,)] +
@@ -409,7 +453,7 @@ class EquivariantCrossAttentionNeF:
             from . import _train
             self._check_shapes(ts)
             return _train.apply_layers(self, ts, x, p, a, sigma)
-        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in ts)):
+        if torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in ts)):
             # training path: gradients w.r.t. the weights (TR:255, NTR:304-339) and / or the query coordinates
             from . import _train
             self._check_shapes(ts)

@@ -84,14 +84,23 @@ def pad_block_tensors(tensors, D, Dp, H, Hp=None):
     return list(tensors) if D == Dp and H == Hp else _pad_list(tensors, BLOCK_AXES, D, Dp, H, Hp)
 
 
-def pad_tensors(tensors, D, Dp, H, Hp=None):
-    """The 46 weight tensors (ENF_W_* order) of a (width D, H heads) model as a (width Dp, Hp heads) model."""
+# the ffn embedding's slots (include/enf_hip.h, ENF_EMB_FFN): Dense_0 (I, D) | (unused) | b0 | Dense_1 (D, D) | b1.  Exact as well:
+# a padded feature of Dense_0 is gelu(0) = 0, and nothing splits the width
+_FFN_EMB = [(None, "D"), None, ("D",), ("D", "D"), ("D",)]
+FFN_AXES = AXES[:4] + _FFN_EMB + _FFN_EMB + AXES[14:]
+assert len(FFN_AXES) == 46
+
+
+def pad_tensors(tensors, D, Dp, H, Hp=None, ffn=False):
+    """The 46 weight tensors (ENF_W_* order) of a (width D, H heads) model as a (width Dp, Hp heads) model; ``ffn``: the ffn
+    embedding's slots (None stays None)."""
     Hp = H if Hp is None else Hp
     if D == Dp and H == Hp:
         return list(tensors)
     out = []
-    for t, kinds in zip(tensors, AXES):
-        for ax, kind in enumerate(kinds):
-            t = _pad_axis(t, ax, kind, D, Dp, H, Hp)
+    for t, kinds in zip(tensors, FFN_AXES if ffn else AXES):
+        if kinds is not None:       # (None: ffn's unused slots, passed through)
+            for ax, kind in enumerate(kinds):
+                t = _pad_axis(t, ax, kind, D, Dp, H, Hp)
         out.append(t)
     return out

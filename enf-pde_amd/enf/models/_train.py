@@ -367,7 +367,9 @@ class _TrainAllFunction(torch.autograd.Function):
         nscr = int(lib.enf_backward_all_scratch_bytes(ctypes.byref(desc), cb))
         scratch = torch.empty(nscr, device=dev, dtype=torch.uint8)
         f32 = dict(device=dev, dtype=torch.float32)
-        grads = [None if i in FROZEN else torch.empty(t.shape, **f32) for i, t in enumerate(ctx.ts)]
+        ffn = model.embedding_type == "ffn"
+        # no gradient: the frozen rff coefficients; ffn: its unused R?_W1 slots (empty tensors) -- its R?_COEF slots are Dense_0
+        grads = [None if (t.numel() == 0 if ffn else i in FROZEN) else torch.empty(t.shape, **f32) for i, t in enumerate(ctx.ts)]
         arrT = (ctypes.c_void_p * len(ctx.ts))(*[t.data_ptr() for t in ctx.ts])
         arrG = (ctypes.c_void_p * len(grads))(*[None if g is None else g.data_ptr() for g in grads])
         dp, da = torch.empty_like(p_), torch.empty_like(a_)
@@ -442,10 +444,11 @@ def apply_layers(model, tensors, x, p, a, sigma):
 
 def apply_train(model, tensors, x, p, a, sigma):
     """nef.apply differentiable w.r.t. every weight tensor and the latents."""
-    if NATIVE_BACKWARD:
+    ffn = model.embedding_type == "ffn"
+    if NATIVE_BACKWARD or ffn:        # (ffn trains through enf_backward_all only: the composed ENF_P_* path is rff's)
         key = (model.precision, str(p.device), tuple((t.data_ptr(), t._version) for t in tensors))
         if model._Dp != model.num_hidden or model._Hp != model.num_heads:  # run in the kernels' shape (differentiable zero padding)
-            tensors = _pad.pad_tensors(tensors, model.num_hidden, model._Dp, model.num_heads, model._Hp)
+            tensors = _pad.pad_tensors(tensors, model.num_hidden, model._Dp, model.num_heads, model._Hp, ffn=ffn)
         _lib.check(_lib.load().enf_check_desc(ctypes.byref(model._desc(p.shape[0], x.shape[1], p.shape[1]))))
         return _TrainAllFunction.apply(x, p, a, sigma, model, key, *tensors)
     if model._Dp != model.num_hidden or model._Hp != model.num_heads:      # run in the kernels' shape (differentiable zero padding)

@@ -83,7 +83,7 @@ class NonMetaPDETrainer:
         w = [t.detach().requires_grad_(True) for t in self.nef.param_tensors(state.params["nef"])]
         p, a, window = self.autodecoder.apply({"params": leaves}, traj_idx)               # :338
         xs = coords[None].expand(img.shape[0], -1, -1)
-        out = self.nef.apply(_tree_from_tensors(w), xs, p, a, window)                     # :341
+        out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
         loss = ((out - img) ** 2).mean()
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)
         gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
@@ -101,7 +101,7 @@ class NonMetaPDETrainer:
         if update_nef:
             new_w, nef_opt_state = self.nef_opt.update(clip_by_global_norm(gw, 1.0), state.nef_opt_state,
                                                        self.nef.param_tensors(state.params["nef"]))
-            nef_params = _tree_from_tensors(new_w)
+            nef_params = _tree_from_tensors(new_w, self.nef)
         P = state.params["autodecoder"]["params"]
         new_p, ad_state = self.autodecoder_opt.update([ga[k] for k in names], state.autodecoder_opt_state, [P[k] for k in names])
         return loss, NonMetaTrainState(params={"nef": nef_params, "autodecoder": {"params": dict(zip(names, new_p))}},

@@ -67,11 +67,14 @@ def _unflatten(tree, leaves):
     return build(tree)
 
 
-def _tree_from_tensors(tensors):
+def _tree_from_tensors(tensors, nef=None):
+    """The parameter tree of ``nef.param_tensors`` order; without ``nef`` the rff tree (with its self-attention blocks)."""
     out = {}
     layers = (len(tensors) - len(TENSOR_PATHS)) // len(BLOCK_PATHS)       # self-attention blocks, if any
-    for path, t in zip(tensor_paths(layers), tensors):
-        _set(out, path, t)
+    paths = nef.tensor_paths() if nef is not None else tensor_paths(layers)
+    for path, t in zip(paths, tensors):
+        if path is not None:
+            _set(out, path, t)
     return {"params": out}
 
 
@@ -94,7 +97,7 @@ def _full_grads(nef, weights, coords, img, masks, s, lat, keys):
     """(loss, grads w.r.t. the 46 weight tensors, grads w.r.t. the latents) on the training path."""
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
-    loss = _loss(nef, _tree_from_tensors(w), coords, img, masks, s, leaves)
+    loss = _loss(nef, _tree_from_tensors(w, nef), coords, img, masks, s, leaves)
     g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
     gl = {k: (torch.zeros_like(lat[k]) if gi is None else gi) for k, gi in zip(keys, g[len(w):])}
@@ -113,7 +116,7 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     ys = img[:, masks[:, s]]
     import contextlib
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
-        out = nef.apply(_tree_from_tensors(w), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
+        out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
         loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
         g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
@@ -139,7 +142,7 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     B = img.shape[0]
     S = masks.shape[1] - 1
     weights = nef.param_tensors(nef_params)
-    frozen = _tree_from_tensors([t.detach() for t in weights])           # inference path for the inner steps
+    frozen = _tree_from_tensors([t.detach() if t is not None else None for t in weights], nef)           # inference path for the inner steps
     lat = {k: v.detach().repeat_interleave(B, dim=0).clone() for k, v in latents0.items()}
     if noise_pos:
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator, device="cpu").to(lat["p_pos"].device) * noise_pos
@@ -294,7 +297,7 @@ class MetaSGDPDETrainer:
         # nef: clip_by_global_norm(1.0) -> adamw                                  (pde_trainer.py:60-63,258-259)
         weights = self.nef.param_tensors(state.params["nef"])
         new_w, nef_opt_state = self.nef_opt.update(clip_by_global_norm(grads["nef"], 1.0), state.nef_opt_state, weights)
-        nef_params = _tree_from_tensors(new_w)
+        nef_params = _tree_from_tensors(new_w, self.nef)
         # latent initialisation: adam, only when learning_rate_codes != 0         (pde_trainer.py:261-268)
         ad = state.params["autodecoder"]
         ad_state = state.autodecoder_opt_state
@@ -333,7 +336,9 @@ class MetaSGDPDETrainer:
         rel = lambda a, b: float((a - b).norm() / b.norm().clamp_min(1e-30))
         gmax = max(float(t.norm()) for t in ref["nef"])
         out = {}
-        for path, a, b in zip(tensor_paths(self.nef.num_layers), own["nef"], ref["nef"]):
+        for path, a, b in zip(self.nef.tensor_paths(), own["nef"], ref["nef"]):
+            if path is None:            # (ffn: an unused slot)
+                continue
             if float(b.norm()) > 1e-6 * gmax:
                 out["/".join(path)] = rel(a, b)
         vals = sorted(out.values())
@@ -477,7 +482,7 @@ class MetaSGDPDETrainer:
         def terminal(weights, lat, keys):
             w = [t.detach().requires_grad_(True) for t in weights]
             lv = {k: lat[k].detach().requires_grad_(True) for k in lat}
-            loss = self.ode_loss(_tree_from_tensors(w), ode_params, lv, trajectory, point_masks, graph=graph)
+            loss = self.ode_loss(_tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph)
             g = torch.autograd.grad(loss, w + [lv[k] for k in keys] + leaves, allow_unused=True)
             z = lambda t, gi: torch.zeros_like(t) if gi is None else gi
             side["ode"] = [z(t, gi) for t, gi in zip(leaves, g[len(w) + len(keys):])]
@@ -497,7 +502,7 @@ class MetaSGDPDETrainer:
         new_lrs, lr_state = self.meta_sgd_opt.update([grads["meta_sgd_lrs"][k] for k in lr_keys], state.meta_sgd_opt_state,
                                                      [lrs[k] for k in lr_keys])
         new_leaves, ode_opt_state = self.ode_opt.update(side["ode"], state.ode_opt_state, [t.detach() for t in leaves])
-        params = dict(state.params, nef=_tree_from_tensors(new_w), meta_sgd_lrs={k: v.clamp(1e-6, 10.0) for k, v in zip(lr_keys, new_lrs)},
+        params = dict(state.params, nef=_tree_from_tensors(new_w, self.nef), meta_sgd_lrs={k: v.clamp(1e-6, 10.0) for k, v in zip(lr_keys, new_lrs)},
                       ode_params=_unflatten(state.params["ode_params"], new_leaves))
         return flat[-1][0], TrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=state.autodecoder_opt_state,
                                        meta_sgd_opt_state=lr_state, ode_opt_state=ode_opt_state, step=state.step + 1, rng=state.rng)

@@ -67,6 +67,22 @@ enum {
                                     query's value depend on the call's shape (the run boundaries order the partial sums) */
 };
 
+/* invariant embedding (reference enf/steerable_attention/embedding/__init__.py:25-33), EnfDesc.embedding.
+ * ENF_EMB_FFN is Dense(I -> D) -> gelu -> Dense(D -> D) (embedding/linear.py, FFNEmbedding; flax Dense, tanh gelu).  It reuses
+ * the weight slots of the rff embedding of both branches (R? = RQ / RV):
+ *   ENF_W_R?_COEF  Dense_0.kernel (I, D)      ENF_W_R?_B1  Dense_0.bias (D)
+ *   ENF_W_R?_W2    Dense_1.kernel (D, D)      ENF_W_R?_B2  Dense_1.bias (D)   (the role of rff's linear_final)
+ *   ENF_W_R?_W1    unused: NULL is accepted; enf_backward_all writes exact zeros to its gradient if a buffer is given.
+ * ffn is built for the non-ball invariants; the relu-mask modes are accepted and do nothing (the chain has no relu).
+ * enf_backward_all gives every weight gradient (d Dense_0 in the R?_COEF slots) and the query gradient; with a store,
+ * enf_pair_backward_ex writes ENF_S_EQ / ENF_S_EV as the invariant in features 0..3 (zeros elsewhere) and ENF_S_DA1 / DA2 as
+ * d of the Dense_0 pre-activation.  The composed path of the ENF_P_* tensors (enf_pack_pair, enf_backward_weights) returns
+ * ENF_EUNSUPPORTED for ffn. */
+enum {
+  ENF_EMB_RFF = 0,
+  ENF_EMB_FFN = 1
+};
+
 /* relu masks of a call (see "Relu masks" below) */
 #define ENF_MASK_OFF 0
 #define ENF_MASK_WRITE 1
@@ -99,7 +115,7 @@ typedef struct EnfDesc {
   int32_t pair_bwd_variant; /* ENF_VARIANT_*: backward pair kernel (the weight-gradient path always runs the unfolded one) */
   int32_t mask_mode;        /* ENF_MASK_*: what the pair kernels of THIS call do with `relu_masks` */
   int32_t mask_signals;     /* signals b, b + mask_signals, ... share the masks of signal b % mask_signals (0 = B) */
-  int32_t reserved;
+  int32_t embedding;        /* ENF_EMB_*: invariant embedding of both branches (a zeroed descriptor is rff) */
   void* relu_masks;         /* enf_relu_mask_bytes(d) bytes of device memory, or NULL with ENF_MASK_OFF */
 } EnfDesc;
 
