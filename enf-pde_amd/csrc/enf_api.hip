@@ -5,27 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <unordered_map>
-#include "enf_layout.h"
-
-extern "C" {
-int enf_launch_prologue(const EnfDims&, const EnfLayout&, const char*, const float*, const float*, const float*, float*,
-                        float*, float*, hipStream_t);
-int enf_launch_prologue_bwd(const EnfDims&, const EnfLayout&, const char*, const float*, const float*, const float*,
-                            const float*, const float*, float*, float*, float*, hipStream_t);
-int enf_launch_pair_fwd(const EnfDims&, const EnfLayout&, const char*, const float*, long long, const float*, float*, float*,
-                        char*, float*, char*, float*, int, int, hipStream_t);
-int enf_launch_pair_bwd(const EnfDims&, const EnfLayout&, const char*, const float*, long long, const float*, const float*,
-                        const float*, const float*, float*, void* const*, const char*, const float*, float*, hipStream_t);
-int enf_launch_wz(const EnfDims&, const EnfLayout&, const char*, const float*, char*, float*, char*, char*, hipStream_t);
-int enf_launch_tail(const EnfDims&, const EnfLayout&, const char*, const float*, float*, const float*, float*, float*, float*,
-                    int, int, hipStream_t);
-int enf_launch_tail_loss(const EnfDims&, const EnfLayout&, const char*, const float*, const float*, float, float*, float*, float*,
-                         float*, hipStream_t);
-}
-
-size_t enf_xtd_part_bytes(const EnfDims& m, long long P);
-int enf_launch_xtd(const EnfDims& m, void* const* store, long long P, float* const* dpair, float* part, int accumulate,
-                   hipStream_t st);
+#include "enf_launch.h"
 
 extern "C" int enf_abi_version(void) { return ENF_ABI_VERSION; }
 
@@ -132,10 +112,6 @@ static SideStream* side_stream() {      // of the calling thread's current devic
   return table[dev];
 }
 
-// join the side-stream work an earlier ENF_STAGE_PREPARE_BWD left pending on THIS workspace (no matching backward
-// came) before `st` touches the regions it writes
-int enf_side_join_pending(hipStream_t st, const void* workspace);
-static int side_join_pending(hipStream_t st, const void* workspace) { return enf_side_join_pending(st, workspace); }
 int enf_side_join_pending(hipStream_t st, const void* workspace) {
   SideStream* side = side_stream();
   if (!side) return 0;
@@ -148,53 +124,56 @@ int enf_side_join_pending(hipStream_t st, const void* workspace) {
   return 0;
 }
 
+// What the z-fold backward pair kernel needs from the latent table alone -- its per-latent folded matrices (enf_wz_kernel, both
+// orientations) and, with `zero_dlt`, the zeroed gradient table -- on the side stream behind what `c.st` holds now: fork, the
+// work, the workspace's join event, pending until enf_side_join_pending.  Returns 1 if it forked, 0 (and nothing has been done)
+// where there is no side stream (`side` NULL) or no entry for the workspace, or an error (< 0): one after the fork returns at
+// once, the entry is pending only once the join event is recorded.  The three callers differ, on purpose:
+//   ENF_STAGE_PREPARE_BWD     z-fold backward only; zeroes on the side stream; not forked: nothing at all (the backward prepares
+//                             for itself later)
+//   enf_backward_latents_ex   z-fold backward only; does NOT zero here (its memset follows the tail backward on the caller's
+//                             stream); not forked: enf_launch_wz on the caller's stream
+//   enf_fit_step              zeroes on the side stream; not forked (or not the z-fold backward): enf_launch_wz (z-fold only) and
+//                             the memset on the caller's stream
+static int side_prepare_bwd(SideStream* side, const EnfCall& c, bool zero_dlt) {
+  if (!side) return 0;
+  std::lock_guard<std::mutex> lk(side->mu);
+  SidePending* e = side->entry(c.ws);
+  if (!e) return 0;
+  if (hipEventRecord(side->fork, c.st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess) return ENF_ELAUNCH;
+  if (int rc = enf_launch_wz(c.m, c.L, c.blob, c.F(c.W.lt), nullptr, c.F(c.W.wzb), nullptr, c.ws + c.W.wzt, side->s)) return rc;
+  if (zero_dlt && hipMemsetAsync(c.F(c.W.dlt), 0, enf_lt_bytes(c.m), side->s) != hipSuccess) return ENF_ELAUNCH;
+  if (hipEventRecord(e->join, side->s) != hipSuccess) return ENF_ELAUNCH;
+  e->pending = true;              // until joined: a failure in between leaves it for the next call's join
+  return 1;
+}
+
 extern "C" int enf_forward_stages(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a,
                                   const float* sigma, const void* packed, float* out, float* ybar, float* lse,
                                   void* workspace, size_t workspace_bytes, unsigned stages, void* stream) {
-  int rc = enf_check_desc(d);
+  EnfCall c;
+  int rc = enf_call(c, d, x && p && a && out, sigma, packed, workspace, workspace_bytes, stream);
   if (rc) return rc;
-  if (!x || !p || !a || !packed || !out || !workspace) return ENF_EINVAL;
-  if (d->use_window && !sigma) return ENF_EINVAL;
-  const EnfDims m = enf_dims(d);
-  const EnfLayout L = enf_layout(m);
-  const EnfWorkspace W = enf_workspace(m);
-  if (workspace_bytes < W.total) return ENF_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const char* blob = (const char*)packed;
-  float* yb = ybar ? ybar : F(W.ybar);
+  const EnfDims& m = c.m;
+  const EnfWorkspace& W = c.W;
+  float* yb = ybar ? ybar : c.F(W.ybar);
   const bool zf = enf_use_zfold(m);
-  float* ls = lse ? lse : F(W.lse);
-  // ENF_STAGE_YBAR_HALF: the hand-off to the tail as bf16 (the launchers' flag bit 1)
+  float* ls = lse ? lse : c.F(W.lse);
+  // ENF_STAGE_YBAR_HALF: the hand-off to the tail as bf16 (the launchers' flag 2)
   const bool yhalf = (stages & ENF_STAGE_YBAR_HALF) && m.bf16 && !ybar && (stages & ENF_STAGE_PAIR) && (stages & ENF_STAGE_TAIL) &&
                      !(stages & ENF_STAGE_TAIL_SAVE) && enf_zfold_split(m) <= 1;
-  if ((rc = side_join_pending(st, workspace))) return rc;
-  if ((stages & ENF_STAGE_PROLOGUE) && (rc = enf_launch_prologue(m, L, blob, p, a, sigma, F(W.lt), F(W.an), F(W.kv), st))) return rc;
+  if ((rc = enf_side_join_pending(c.st, workspace))) return rc;
+  if ((stages & ENF_STAGE_PROLOGUE) && (rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), c.st))) return rc;
   if ((stages & (ENF_STAGE_PAIR | ENF_STAGE_FOLD)) &&
-      (rc = enf_launch_pair_fwd(m, L, blob, x, x_bstride, F(W.lt), yb, ls, zf ? ws + W.wz : nullptr, zf ? F(W.wzb) : nullptr,
-                                zf ? ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? F(W.ysplit) : nullptr, (stages & ENF_STAGE_FOLD) != 0,
-                                ((stages & ENF_STAGE_PAIR) != 0 ? 1 : 0) | (yhalf ? 2 : 0), st)))
+      (rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), yb, ls, zf ? c.ws + W.wz : nullptr, zf ? c.F(W.wzb) : nullptr,
+                                zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, (stages & ENF_STAGE_FOLD) != 0,
+                                ((stages & ENF_STAGE_PAIR) != 0 ? 1 : 0) | (yhalf ? 2 : 0), c.st)))
     return rc;
-  if ((stages & ENF_STAGE_PREPARE_BWD) && enf_use_zfold_bwd(m)) {
-    // what the backward needs from the latent table alone -- its per-latent folded matrices, the zeroed gradient table --
-    // starts on the side stream behind the pair kernel, beside the tail, the caller's loss and the tail backward
-    SideStream* side = side_stream();
-    if (side) {
-      std::lock_guard<std::mutex> lk(side->mu);
-      SidePending* e = side->entry(workspace);
-      if (e) {
-        if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess) return ENF_ELAUNCH;
-        if ((rc = enf_launch_wz(m, L, blob, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, side->s))) return rc;
-        if (hipMemsetAsync(F(W.dlt), 0, sizeof(float) * (size_t)m.B * m.Z * enf_lt_stride(m.H, m.D), side->s) != hipSuccess) return ENF_ELAUNCH;
-        if (hipEventRecord(e->join, side->s) != hipSuccess) return ENF_ELAUNCH;
-        e->pending = true;
-      }
-    }
-  }
+  // starts behind the pair kernel, beside the tail, the caller's loss and the tail backward
+  if ((stages & ENF_STAGE_PREPARE_BWD) && enf_use_zfold_bwd(m) && (rc = side_prepare_bwd(side_stream(), c, true)) < 0) return rc;
   const bool tsave = (stages & ENF_STAGE_TAIL_SAVE) != 0;      // stash the tail's pre-activations for the backward that follows
   if ((stages & ENF_STAGE_TAIL) &&
-      (rc = enf_launch_tail(m, L, blob, yb, out, nullptr, nullptr, nullptr, tsave ? F(W.tail_act) : nullptr, 0, (tsave ? 1 : 0) | (yhalf ? 2 : 0), st)))
+      (rc = enf_launch_tail(m, c.L, c.blob, yb, out, nullptr, nullptr, nullptr, tsave ? c.F(W.tail_act) : nullptr, 0, (tsave ? 1 : 0) | (yhalf ? 2 : 0), c.st)))
     return rc;
   return ENF_OK;
 }
@@ -214,32 +193,32 @@ extern "C" int enf_backward_latents(const EnfDesc* d, const float* x, int64_t x_
                                  workspace_bytes, 0u, stream);
 }
 
+// the backward pair kernel on the workspace's dybar / delta / dlt, in the z-fold form where the shape resolves to it
+static int pair_bwd_on_workspace(const EnfCall& c, const float* x, int64_t x_bstride, const float* lse) {
+  const bool zb = enf_use_zfold_bwd(c.m);
+  return enf_launch_pair_bwd(c.m, c.L, c.blob, x, x_bstride, c.F(c.W.lt), lse, c.F(c.W.dybar), c.F(c.W.delta), c.F(c.W.dlt), nullptr,
+                             zb ? c.ws + c.W.wzt : nullptr, zb ? c.F(c.W.wzb) : nullptr, nullptr, c.st);
+}
+
 extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a,
                                        const float* sigma, const void* packed, const float* ybar, const float* lse,
                                        const float* dout, float* dp, float* da, float* dsigma, void* workspace,
                                        size_t workspace_bytes, unsigned flags, void* stream) {
-  int rc = enf_check_desc(d);
+  EnfCall c;
+  int rc = enf_call(c, d, x && p && a && ybar && lse && dout && dp && da && dsigma, sigma, packed, workspace, workspace_bytes, stream);
   if (rc) return rc;
-  if (!x || !p || !a || !packed || !ybar || !lse || !dout || !dp || !da || !dsigma || !workspace) return ENF_EINVAL;
-  if (d->use_window && !sigma) return ENF_EINVAL;
-  const EnfDims m = enf_dims(d);
-  const EnfLayout L = enf_layout(m);
-  const EnfWorkspace W = enf_workspace(m);
-  if (workspace_bytes < W.total) return ENF_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const char* blob = (const char*)packed;
+  const EnfDims& m = c.m;
+  const EnfWorkspace& W = c.W;
+  hipStream_t st = c.st;
   const bool zb = enf_use_zfold_bwd(m);
   if (flags & ENF_BWD_ONLY_PAIR) {      // measurement hook: the pair kernel alone, on what a complete backward left behind
-    if ((rc = side_join_pending(st, workspace))) return rc;
-    if (hipMemsetAsync(F(W.dlt), 0, sizeof(float) * (size_t)m.B * m.Z * enf_lt_stride(m.H, m.D), st) != hipSuccess) return ENF_ELAUNCH;
-    return enf_launch_pair_bwd(m, L, blob, x, x_bstride, F(W.lt), lse, F(W.dybar), F(W.delta), F(W.dlt), nullptr,
-                               zb ? ws + W.wzt : nullptr, zb ? F(W.wzb) : nullptr, nullptr, st);
+    if ((rc = enf_side_join_pending(st, workspace))) return rc;
+    if (hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+    return pair_bwd_on_workspace(c, x, x_bstride, lse);
   }
   // the latent table is recomputed (cheap) so the call does not depend on workspace contents, unless the
   // caller vouches that nothing has touched the workspace since the matching enf_forward
-  if (!(flags & ENF_BWD_REUSE_PROLOGUE) && (rc = enf_launch_prologue(m, L, blob, p, a, sigma, F(W.lt), F(W.an), F(W.kv), st)))
+  if (!(flags & ENF_BWD_REUSE_PROLOGUE) && (rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st)))
     return rc;
   // z-fold backward: the per-latent matrices depend on the latent table only, so enf_wz_kernel runs on a side stream
   // (fork / join by events) beside the tail backward instead of in front of the pair kernel
@@ -250,30 +229,17 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
     auto it = side->ws.find(workspace);
     prepared = it != side->ws.end() && it->second.pending;   // launched by the matching forward ON THIS WORKSPACE
   }
-  if (!prepared && (rc = side_join_pending(st, workspace))) return rc;
+  if (!prepared && (rc = enf_side_join_pending(st, workspace))) return rc;
   if (zb && !prepared) {
-    bool forked = false;
-    if (side) {
-      std::lock_guard<std::mutex> lk(side->mu);
-      SidePending* e = side->entry(workspace);
-      if (e) {
-        if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess) return ENF_ELAUNCH;
-        if ((rc = enf_launch_wz(m, L, blob, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, side->s))) return rc;
-        if (hipEventRecord(e->join, side->s) != hipSuccess) return ENF_ELAUNCH;
-        e->pending = true;              // until joined below: a failure in between leaves it for the next call's join
-        forked = true;
-      }
-    }
-    if (!forked && (rc = enf_launch_wz(m, L, blob, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, st))) return rc;
+    if ((rc = side_prepare_bwd(side, c, false)) < 0) return rc;
+    if (!rc && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
   }
   const bool treuse = (flags & ENF_BWD_REUSE_TAIL) && (flags & ENF_BWD_REUSE_PROLOGUE);
-  if ((rc = enf_launch_tail(m, L, blob, ybar, nullptr, dout, F(W.dybar), F(W.delta), F(W.tail_act), 1, treuse ? 1 : 0, st))) return rc;
-  if (!prepared && hipMemsetAsync(F(W.dlt), 0, sizeof(float) * (size_t)m.B * m.Z * enf_lt_stride(m.H, m.D), st) != hipSuccess) return ENF_ELAUNCH;
-  if ((rc = side_join_pending(st, workspace))) return rc;      // the per-latent matrices (and, if prepared, the zeroed table)
-  if ((rc = enf_launch_pair_bwd(m, L, blob, x, x_bstride, F(W.lt), lse, F(W.dybar), F(W.delta), F(W.dlt), nullptr,
-                                zb ? ws + W.wzt : nullptr, zb ? F(W.wzb) : nullptr, nullptr, st))) return rc;
-  if ((rc = enf_launch_prologue_bwd(m, L, blob, p, sigma, F(W.an), F(W.kv), F(W.dlt), dp, da, dsigma, st))) return rc;
-  return ENF_OK;
+  if ((rc = enf_launch_tail(m, c.L, c.blob, ybar, nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), 1, treuse ? 1 : 0, st))) return rc;
+  if (!prepared && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+  if ((rc = enf_side_join_pending(st, workspace))) return rc;      // the per-latent matrices (and, if prepared, the zeroed table)
+  if ((rc = pair_bwd_on_workspace(c, x, x_bstride, lse))) return rc;
+  return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
 }
 
 
@@ -284,49 +250,28 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
 extern "C" int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                             const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                             float* dsigma, void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = enf_check_desc(d);
+  EnfCall c;
+  int rc = enf_call(c, d, x && p && a && target && loss && dp && da && dsigma, sigma, packed, workspace, workspace_bytes, stream);
   if (rc) return rc;
-  if (!x || !p || !a || !packed || !target || !loss || !dp || !da || !dsigma || !workspace) return ENF_EINVAL;
-  if (d->use_window && !sigma) return ENF_EINVAL;
-  const EnfDims m = enf_dims(d);
-  const EnfLayout L = enf_layout(m);
-  const EnfWorkspace W = enf_workspace(m);
-  if (workspace_bytes < W.total) return ENF_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const char* blob = (const char*)packed;
+  const EnfDims& m = c.m;
+  const EnfWorkspace& W = c.W;
+  hipStream_t st = c.st;
   const bool zf = enf_use_zfold(m), zb = enf_use_zfold_bwd(m);
-  if ((rc = side_join_pending(st, workspace))) return rc;
-  if ((rc = enf_launch_prologue(m, L, blob, p, a, sigma, F(W.lt), F(W.an), F(W.kv), st))) return rc;
-  if ((rc = enf_launch_pair_fwd(m, L, blob, x, x_bstride, F(W.lt), F(W.ybar), F(W.lse), zf ? ws + W.wz : nullptr, zf ? F(W.wzb) : nullptr,
-                                zf ? ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? F(W.ysplit) : nullptr, 1, 1, st)))
+  if ((rc = enf_side_join_pending(st, workspace))) return rc;
+  if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
+  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
+                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
     return rc;
   // what the backward pair kernel needs from the latent table alone runs on the side stream beside the tail
-  const size_t dlt_bytes = sizeof(float) * (size_t)m.B * m.Z * enf_lt_stride(m.H, m.D);
-  bool forked = false;
-  SideStream* side = zb ? side_stream() : nullptr;
-  if (side) {
-    std::lock_guard<std::mutex> lk(side->mu);
-    SidePending* e = side->entry(workspace);
-    if (e) {
-      if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess) return ENF_ELAUNCH;
-      if ((rc = enf_launch_wz(m, L, blob, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, side->s))) return rc;
-      if (hipMemsetAsync(F(W.dlt), 0, dlt_bytes, side->s) != hipSuccess) return ENF_ELAUNCH;
-      if (hipEventRecord(e->join, side->s) != hipSuccess) return ENF_ELAUNCH;
-      e->pending = true;
-      forked = true;
-    }
+  if ((rc = side_prepare_bwd(zb ? side_stream() : nullptr, c, true)) < 0) return rc;
+  if (!rc) {
+    if (zb && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
+    if (hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   }
-  if (!forked) {
-    if (zb && (rc = enf_launch_wz(m, L, blob, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, st))) return rc;
-    if (hipMemsetAsync(F(W.dlt), 0, dlt_bytes, st) != hipSuccess) return ENF_ELAUNCH;
-  }
-  if ((rc = enf_launch_tail_loss(m, L, blob, F(W.ybar), target, grad_scale, loss, F(W.dybar), F(W.delta), F(W.tail_act), st))) return rc;
-  if ((rc = side_join_pending(st, workspace))) return rc;
-  if ((rc = enf_launch_pair_bwd(m, L, blob, x, x_bstride, F(W.lt), F(W.lse), F(W.dybar), F(W.delta), F(W.dlt), nullptr,
-                                zb ? ws + W.wzt : nullptr, zb ? F(W.wzb) : nullptr, nullptr, st))) return rc;
-  return enf_launch_prologue_bwd(m, L, blob, p, sigma, F(W.an), F(W.kv), F(W.dlt), dp, da, dsigma, st);
+  if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
+  if ((rc = enf_side_join_pending(st, workspace))) return rc;
+  if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse)))) return rc;
+  return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
 }
 
 extern "C" int enf_lt_layout(const EnfDesc* d, int* stride, int* off_u, int* off_v0, int* off_pose, int* off_wcoef, int* off_c) {
@@ -372,13 +317,23 @@ extern "C" int enf_pair_partition(const EnfDesc* d, int32_t* run, int32_t* workg
   return 1;
 }
 
+// the z-fold forward's scratch outside a workspace (byte offsets; total 0: the latent-split variant, no scratch)
+struct PairScratch { size_t wz, wzb, wzu, ysplit, total; };
+static PairScratch pair_scratch(const EnfDims& m) {
+  PairScratch s{0, 0, 0, 0, 0};
+  if (!enf_use_zfold(m)) return s;
+  const size_t BZ = (size_t)m.B * m.Z, BN = (size_t)m.B * m.N;
+  const int split = enf_zfold_split(m);
+  s.wzb = s.wz + enf_align(BZ * m.H * enf_panel_bytes(m.D, m.D, m.bf16));
+  s.wzu = s.wzb + enf_align(sizeof(float) * BZ * m.HD);
+  s.ysplit = s.wzu + enf_align(BZ * enf_wzu_bytes(m.H, m.D));
+  s.total = s.ysplit + (split > 1 ? sizeof(float) * split * (BN * m.HD + BN * m.H * 3) : 0);
+  return s;
+}
+
 extern "C" size_t enf_pair_scratch_bytes(const EnfDesc* d) {
   if (enf_check_desc(d)) return 0;
-  const EnfDims m = enf_dims(d);
-  if (!enf_use_zfold(m)) return 0;
-  return enf_align((size_t)m.B * m.Z * m.H * enf_panel_bytes(m.D, m.D, m.bf16)) +
-         enf_align(sizeof(float) * (size_t)m.B * m.Z * m.HD) + enf_align((size_t)m.B * m.Z * enf_wzu_bytes(m.H, m.D)) +
-         (enf_zfold_split(m) > 1 ? sizeof(float) * enf_zfold_split(m) * ((size_t)m.B * m.N * m.HD + (size_t)m.B * m.N * m.H * 3) : 0);
+  return pair_scratch(enf_dims(d)).total;
 }
 
 extern "C" int enf_pair_forward(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
@@ -387,14 +342,13 @@ extern "C" int enf_pair_forward(const EnfDesc* d, const float* x, int64_t x_bstr
   if (rc) return rc;
   if (!x || !lt || !packed || !ybar || !lse) return ENF_EINVAL;
   const EnfDims m = enf_dims(d);
-  const size_t need = enf_pair_scratch_bytes(d);
-  if (need && (!scratch || scratch_bytes < need)) return ENF_EWORKSPACE;
-  char* wz = need ? (char*)scratch : nullptr;
-  float* wzb = need ? reinterpret_cast<float*>(wz + enf_align((size_t)m.B * m.Z * m.H * enf_panel_bytes(m.D, m.D, m.bf16))) : nullptr;
-  char* wzu = need ? reinterpret_cast<char*>(wzb) + enf_align(sizeof(float) * (size_t)m.B * m.Z * m.HD) : nullptr;
-  float* ysplit = need && enf_zfold_split(m) > 1 ? reinterpret_cast<float*>(wzu + enf_align((size_t)m.B * m.Z * enf_wzu_bytes(m.H, m.D))) : nullptr;
-  return enf_launch_pair_fwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, ybar, lse, wz, wzb, wzu, ysplit, 1, 1,
-                             (hipStream_t)stream);
+  const PairScratch S = pair_scratch(m);
+  const bool zf = S.total != 0;
+  if (zf && (!scratch || scratch_bytes < S.total)) return ENF_EWORKSPACE;
+  char* sc = (char*)scratch;
+  return enf_launch_pair_fwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, ybar, lse, zf ? sc + S.wz : nullptr,
+                             zf ? reinterpret_cast<float*>(sc + S.wzb) : nullptr, zf ? sc + S.wzu : nullptr,
+                             zf && enf_zfold_split(m) > 1 ? reinterpret_cast<float*>(sc + S.ysplit) : nullptr, 1, 1, (hipStream_t)stream);
 }
 
 extern "C" size_t enf_relu_mask_bytes(const EnfDesc* d) {
@@ -420,20 +374,14 @@ extern "C" int enf_pair_backward_ex(const EnfDesc* d, const float* x, int64_t x_
     for (int i = 0; i < ENF_NUM_STORE(m.H); ++i)
       if (!store[i]) return ENF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(dlt, 0, sizeof(float) * (size_t)m.B * m.Z * enf_lt_stride(m.H, m.D), st) != hipSuccess) return ENF_ELAUNCH;
+  if (hipMemsetAsync(dlt, 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, nullptr, nullptr, dx, st);
 }
 
-// ---- weight gradients of the per-pair chain: K3 (STORE) -> K4 (enf_xtd.hip), chunked over signals
-static size_t bw_store_bytes(const EnfDims& m, int cb) {
-  return enf_align((size_t)cb * m.Z * m.N * m.D * (m.bf16 ? 2 : 4));          // one ENF_S_* buffer of a chunk
-}
-static size_t bw_scratch_bytes(const EnfDims& m, int cb) {
-  return (size_t)ENF_NUM_STORE(m.H) * bw_store_bytes(m, cb) + enf_xtd_part_bytes(m, (long long)cb * m.Z * m.N);
-}
+// ---- weight gradients of the per-pair chain: K3 (STORE) -> K4, chunked over signals (enf_xtd.hip)
 extern "C" size_t enf_backward_weights_scratch_bytes(const EnfDesc* d, int chunk_signals) {
   if (enf_check_desc(d) != ENF_OK || chunk_signals < 1 || chunk_signals > d->B) return 0;
-  return bw_scratch_bytes(enf_dims(d), chunk_signals);
+  return enf_wgrad_scratch_bytes(enf_dims(d), chunk_signals);
 }
 
 extern "C" int enf_backward_weights(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
@@ -445,32 +393,9 @@ extern "C" int enf_backward_weights(const EnfDesc* d, const float* x, int64_t x_
   if (!x || !lt || !packed || !lse || !dybar || !delta || !dlt || !dpair || !scratch) return ENF_EINVAL;
   for (int i = 0; i < ENF_NUM_PAIR_TENSORS; ++i)
     if (i != ENF_P_COEFQ && i != ENF_P_COEFV && !dpair[i]) return ENF_EINVAL;
-  EnfDims m = enf_dims(d);
-  const EnfLayout L = enf_layout(m);
-  // the largest chunk of signals whose store fits; with masks, whole groups of mask_signals (signal b replays b % mask_signals)
-  const int step = m.mask_mode == ENF_MASK_READ && m.mask_B < m.B ? m.mask_B : 1;
-  int cb = m.B;
-  while (cb > step && bw_scratch_bytes(m, cb) > scratch_bytes) cb = (cb - 1) / step * step;
-  if (cb < 1 || bw_scratch_bytes(m, cb) > scratch_bytes) return ENF_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int stride = enf_lt_stride(m.H, m.D);
-  if (hipMemsetAsync(dlt, 0, sizeof(float) * (size_t)m.B * m.Z * stride, st) != hipSuccess) return ENF_ELAUNCH;
-  char* sc = (char*)scratch;
-  void* store[ENF_NUM_STORE(4)];
-  const size_t sb = bw_store_bytes(m, cb);
-  for (int i = 0; i < ENF_NUM_STORE(m.H); ++i) store[i] = sc + (size_t)i * sb;
-  float* part = reinterpret_cast<float*>(sc + (size_t)ENF_NUM_STORE(m.H) * sb);
-  const int B = m.B;
-  for (int b0 = 0; b0 < B; b0 += cb) {
-    const int nb = b0 + cb <= B ? cb : B - b0;
-    EnfDims mc = m;
-    mc.B = nb; mc.mask_b0 = b0;
-    const size_t qo = (size_t)b0 * m.N;
-    if ((rc = enf_launch_pair_bwd(mc, L, (const char*)packed, x + (size_t)b0 * x_bstride, x_bstride, lt + (size_t)b0 * m.Z * stride,
-                                  lse + qo * m.H, dybar + qo * m.HD, delta + qo * m.H, dlt + (size_t)b0 * m.Z * stride, store,
-                                  nullptr, nullptr, dx ? dx + qo * m.dx : nullptr, st)))
-      return rc;
-    if ((rc = enf_launch_xtd(mc, store, (long long)nb * m.Z * m.N, dpair, part, b0 > 0, st))) return rc;
-  }
-  return ENF_OK;
+  const EnfDims m = enf_dims(d);
+  const int cb = enf_wgrad_chunk(m, scratch_bytes, [&](int n) { return enf_wgrad_scratch_bytes(m, n); });
+  if (!cb) return ENF_EWORKSPACE;
+  return enf_launch_wgrad_chunks(m, enf_layout(m), (const char*)packed, cb, x, x_bstride, lt, lse, dybar, delta, dlt, dx, (char*)scratch,
+                                 dpair, (hipStream_t)stream);
 }

@@ -1,7 +1,7 @@
 // enf_debug.hip -- layout self-test: Y (M x 16) = A (M x K) . X (K x 16) through the same
 // pack_panel + make_frags + gemm_stage path the production kernels use.  Test-only entry point.
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
+#include "enf_launch.h"
 #include "enf_device.h"
 
 template <int KBIN, int MTOUT, bool BF16>

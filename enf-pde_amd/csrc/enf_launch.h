@@ -1,7 +1,11 @@
-// enf_launch.h -- host-side launch helpers shared by the kernel files.
+// enf_launch.h -- everything host-side that one .hip file of the library uses from another: the kernel launchers, the call
+// context of the C-ABI entry points and the shared launch helpers (with enf_layout.h).  Every .hip file includes it, the file
+// that defines a function too, and the functions have C++ linkage: a definition that drifts from its declaration here is a
+// link error.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include "enf_layout.h"
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) holds per DEVICE: `done` keeps one bit per device ordinal of the calling
 // thread's current device (ordinals beyond 63 set the attribute on every launch).  Safe from concurrent host threads:
@@ -15,3 +19,104 @@ inline bool enf_lds_attr(const void* kern, int bytes, EnfAttrBits& done) {
   if (dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_release);
   return true;
 }
+
+// ---- what the entry points that run on a workspace (enf_forward_stages, enf_backward_latents_ex, enf_fit_step,
+// enf_backward_all) derive from their arguments
+struct EnfCall {
+  EnfDims m;
+  EnfLayout L;
+  EnfWorkspace W;
+  hipStream_t st;
+  char* ws;             // the workspace (also the key of its pending side-stream work)
+  const char* blob;     // the packed weights
+  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+};
+// Errors in their order of precedence: the descriptor's (enf_check_desc), ENF_EINVAL for a NULL pointer (`pointers_ok` is the
+// entry point's own set; `packed` and `workspace` are everybody's) or for a window without `sigma`, ENF_EWORKSPACE.
+inline int enf_call(EnfCall& c, const EnfDesc* d, bool pointers_ok, const float* sigma, const void* packed, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  const int rc = enf_check_desc(d);
+  if (rc) return rc;
+  if (!pointers_ok || !packed || !workspace) return ENF_EINVAL;
+  if (d->use_window && !sigma) return ENF_EINVAL;
+  c.m = enf_dims(d);
+  c.L = enf_layout(c.m);
+  c.W = enf_workspace(c.m);
+  if (workspace_bytes < c.W.total) return ENF_EWORKSPACE;
+  c.st = (hipStream_t)stream;
+  c.ws = (char*)workspace;
+  c.blob = (const char*)packed;
+  return ENF_OK;
+}
+
+// join the side-stream work an earlier ENF_STAGE_PREPARE_BWD left pending on THIS workspace (no matching backward
+// came) before `st` touches the regions it writes (enf_api.hip)
+int enf_side_join_pending(hipStream_t st, const void* workspace);
+
+// ---- K1, the latent prologue (enf_prologue.hip): p, a, sigma -> the latent table `lt` and what its backward reads (`an`, `kv`)
+int enf_launch_prologue(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* a, const float* sigma,
+                        float* lt, float* an, float* kv, hipStream_t st);
+// d lt -> d p, d a, d sigma; _wg: with pg != NULL also the operand rows of the prologue's weight gradients (enf_train.hip)
+int enf_launch_prologue_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* sigma,
+                            const float* an, const float* kv, const float* dlt, float* dp, float* da, float* dsigma, hipStream_t st);
+int enf_launch_prologue_bwd_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* sigma,
+                               const float* an, const float* kv, const float* dlt, float* dp, float* da, float* dsigma, float* pg,
+                               hipStream_t st);
+
+// ---- the per-latent folded matrices of the z-fold pair kernels (enf_wz.hip)
+// wzt == NULL: forward panels only, packed back to back in `wz`, and the logit rows `wzu` (the z-fold forward kernel's layout);
+// wzt != NULL: `wzt` holds [forward | backward] panel pairs per (latent, head), `wz` is ignored.  `wzb`: the bias vectors.
+int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const float* lt, char* wz, float* wzb, char* wzu,
+                  char* wzt, hipStream_t st);
+
+// ---- K2, the forward pair kernel (enf_pair_fwd.hip).  wz / wzb / wzu: scratch of the z-fold variant (EnfWorkspace), all NULL
+// for the latent-split variant; ysplit: the partial sums of ENF_VARIANT_ZFOLD_ZSPLIT, or NULL.
+//   run_fold   nonzero: the z-fold variant first builds its per-latent matrices (enf_launch_wz)
+//   run_pair   bit set: 1 = run the pair stage (without it the call is the fold alone), 2 = hand ybar to the tail as bf16
+int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride, const float* lt,
+                        float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit, int run_fold, int run_pair,
+                        hipStream_t st);
+
+// ---- K3, the backward pair kernel (enf_pair_bwd.hip): ADDS to `dlt`.  store != NULL: the activation-store form (the K4 operands
+// of ENF_NUM_STORE(H) buffers); otherwise wzt / wzb != NULL selects the z-fold form.  dxq: d x per query, or NULL.
+int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride, const float* lt,
+                        const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store, const char* wzt,
+                        const float* wzb, float* dxq, hipStream_t st);
+
+// ---- K4, X^T delta over the activation store (enf_xtd.hip)
+size_t enf_xtd_part_bytes(const EnfDims& m, long long P);       // slice partials of a pass over P rows (256-aligned)
+// store: the ENF_NUM_STORE(H) device buffers K3 wrote for P rows; dpair: ENF_NUM_PAIR_TENSORS fp32 device pointers in
+// ENF_P_* order (the two coefficient entries are not touched); accumulate = add to what dpair holds (later chunks)
+int enf_launch_xtd(const EnfDims& m, void* const* store, long long P, float* const* dpair, float* part, int accumulate,
+                   hipStream_t st);
+
+// The weight-gradient pass of the per-pair chain, chunked over signals: zero `dlt`, then per chunk of `cb` signals K3 with
+// the activation store and K4.  `scratch` holds enf_wgrad_scratch_bytes(m, cb); x .. dx are the whole batch's (dx may be NULL).
+size_t enf_wgrad_scratch_bytes(const EnfDims& m, int cb);
+int enf_launch_wgrad_chunks(const EnfDims& m, const EnfLayout& L, const char* blob, int cb, const float* x, long long x_bstride,
+                            const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt, float* dx,
+                            char* scratch, float* const* dpair, hipStream_t st);
+// the largest chunk of signals whose scratch, bytes(cb), fits in `avail` (0: none does); with relu masks, whole groups of
+// mask_signals (signal b replays b % mask_signals)
+template <class Bytes>
+inline int enf_wgrad_chunk(const EnfDims& m, size_t avail, Bytes bytes) {
+  const int step = m.mask_mode == ENF_MASK_READ && m.mask_B < m.B ? m.mask_B : 1;
+  int cb = m.B;
+  while (cb > step && bytes(cb) > avail) cb = (cb - 1) / step * step;
+  return cb >= 1 && bytes(cb) <= avail ? cb : 0;
+}
+
+// ---- the per-query tail (enf_tail.hip)
+//   bwd   0: forward (ybar -> out); nonzero: backward (dout -> dybar, delta)
+//   opt   bit set: 1 = forward: stash the pre-activations in `act`; backward: `act` holds them, skip the recompute
+//                  2 = forward only: ybar is bf16 (the pair kernel's run_pair & 2)
+// _wg: tdel != NULL (backward only) is the weight-gradient form -- it also leaves every layer's input (in `act`, in place of
+// the pre-activations) and delta (in `tdel`) for the X^T delta products of enf_train.hip
+int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, const float* dout,
+                    float* dybar, float* delta, float* act, int bwd, int opt, hipStream_t st);
+int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, const float* dout,
+                       float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
+// the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
+// backward chain -> d ybar, delta
+int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target, float gscale,
+                         float* loss, float* dybar, float* delta, float* act, hipStream_t st);

@@ -192,6 +192,8 @@ ENF_HD inline int enf_lt_off_v0(int H, int D) { return H * D; }
 ENF_HD inline int enf_lt_off_pose(int H, int D) { return 2 * H * D; }
 ENF_HD inline int enf_lt_off_wcoef(int H, int D) { return 2 * H * D + 4; }
 ENF_HD inline int enf_lt_off_c(int H, int D) { return 2 * H * D + 8; }
+// bytes of the table (and of its gradient, which the backward zeroes before the pair kernel adds to it)
+inline size_t enf_lt_bytes(const EnfDims& m) { return sizeof(float) * (size_t)m.B * m.Z * enf_lt_stride(m.H, m.D); }
 
 // Forward pair kernel variant.  "z-fold": all 8 waves of a workgroup walk the latents together (one
 // latent per step, 128 queries per workgroup), which lets FiLM and the mixer's first Dense collapse
@@ -290,7 +292,7 @@ inline EnfWorkspace enf_workspace(const EnfDims& m) {
   auto take = [&](size_t bytes) { size_t r = o; o = enf_align(o + bytes); return r; };
   const size_t f = sizeof(float);
   const size_t BZ = (size_t)m.B * m.Z, BN = (size_t)m.B * m.N;
-  W.lt = take(f * BZ * enf_lt_stride(m.H, m.D));
+  W.lt = take(enf_lt_bytes(m));
   W.an = take(f * BZ * (2 * m.D + 2));
   W.kv = take(f * BZ * 2 * m.HD);
   W.ybar = take(f * BN * m.HD);
@@ -298,7 +300,7 @@ inline EnfWorkspace enf_workspace(const EnfDims& m) {
   W.dybar = take(f * BN * m.HD);
   W.delta = take(f * BN * m.H);
   W.tail_act = take(f * BN * (2 * m.HD + 2 * m.D + 2));
-  W.dlt = take(f * BZ * enf_lt_stride(m.H, m.D));
+  W.dlt = take(enf_lt_bytes(m));
   const bool zf = enf_use_zfold(m), zb = enf_use_zfold_bwd(m);
   W.wz = take(zf || zb ? BZ * m.H * enf_panel_bytes(m.D, m.D, m.bf16) : 0);
   W.wzb = take(zf || zb ? f * BZ * m.HD : 0);

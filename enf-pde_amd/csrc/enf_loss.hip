@@ -7,7 +7,7 @@
 // enf_meta_sgd_update: the meta-SGD update of every latent component in ONE launch (pde_trainer.py:206-219):
 //   out_k = x_k - lr_k (scale g_k),   scale = the batch size (the gradient of a batch-mean loss, :206)
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
+#include "enf_launch.h"
 
 __global__ __launch_bounds__(256) void enf_mse_kernel(const float* __restrict__ out, const float* __restrict__ target, size_t n,
                                                       float inv_n, float gscale, float* __restrict__ dout, float* loss) {

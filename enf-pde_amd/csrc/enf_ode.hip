@@ -14,7 +14,7 @@
 // (First version: one wave per (b, r, channel tile) -- 8 re-reads of every basis tile and one dependent MFMA chain per
 // wave: 22.5 us per call at B=16, Z=64, J=64, C=128 = 0.31 of the fp32-MFMA peak.)
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
+#include "enf_launch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define OB_MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)

@@ -18,7 +18,6 @@
 //             order by the reduce kernel (bitwise reproducible, no atomics).
 // I <= 4 (smaller I: zero-padded components meet zero weight rows), degree 3, hidden / basis widths multiples of 16.
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
 #include "enf_launch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

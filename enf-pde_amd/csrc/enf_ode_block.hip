@@ -14,7 +14,6 @@
 // The sum over the MFMA's K index is order-free: lane quad q takes 4 CONSECUTIVE k of a 16-wide super-step, so operands that
 // are contiguous along K are one 16-byte load.
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
 #include "enf_launch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -17,7 +17,6 @@
 // gemm_tile_flip -- same panels, MFMA operands swapped) whose rows are the queries, so they cost 4
 // FMAs per 16x16 tile and 32 accumulator registers instead of 128; +160 MFMAs per tile.
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
 #include "enf_launch.h"
 #include "enf_device.h"
 #include "enf_pair_common.h"
@@ -1079,9 +1078,9 @@ static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
 
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor); read by the STORE instantiation only
 
-extern "C" int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
-                                   const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
-                                   void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st) {
+int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
+                        const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
+                        void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st) {
   PairBwdArgs A;
   A.dxq = dxq;
   A.masks = store && m.mask_mode == ENF_MASK_READ ? m.masks : nullptr; A.mask_B = m.mask_B; A.mask_b0 = m.mask_b0;

@@ -18,7 +18,6 @@
 // linear in the softmax-weighted sum and are applied once per query by the tail kernel.
 // Weight panels stream L2 -> LDS by LDS-DMA through a 2-slot ring shared by the 8 waves.
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
 #include "enf_launch.h"
 #include "enf_device.h"
 #include "enf_pair_common.h"
@@ -491,14 +490,10 @@ static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }
 
-extern "C" int enf_launch_wz(const EnfDims&, const EnfLayout&, const char*, const float*, char*, float*, char*, char*, hipStream_t);
-
-// wz / wzb: scratch for the z-fold variant (enf_workspace: W.wz, W.wzb), or NULL for the latent-split variant
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor)
-
-extern "C" int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
-                                   const float* lt, float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit,
-                                   int run_fold, int run_pair, hipStream_t st) {
+int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
+                        const float* lt, float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit,
+                        int run_fold, int run_pair, hipStream_t st) {
   PairFwdArgs A;
   A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.ybar = ybar; A.lse = lse; A.wz = wz; A.wzb = wzb; A.wzu = wzu; A.inv_d = 1.0f / (float)m.Dt;
   A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;

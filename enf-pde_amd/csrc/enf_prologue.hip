@@ -1,25 +1,380 @@
-// enf_prologue.hip -- the backward of K1 on the matrix pipe (fp32 `v_mfma_f32_16x16x4_f32`), 16 latents per workgroup.
+// enf_prologue.hip -- K1, the latent prologue: the forward kernel and its backward, on the vector ALU and on the matrix pipe.
 //
 // The per-latent part of the decoder (NEF:220, NEF:56, ECA:93-94 and the logit fold of enf_pack.hip):
 //   s = a Ws + bs -> LayerNorm -> an;  k = an Wk + bk;  v0 = an Wv + bv;  u_h = MU_h k_h;  c_h = cvec_h . k_h
-// is a chain of small dense products over the B Z latent rows.  The first version (enf_pack.hip: 4 latents per workgroup, one
-// output feature per thread, weights streamed from L2 per workgroup) was bound by the latency of that stream -- every workgroup read
-// all 392 KB of prologue weights for 4 latents: 100 MB of L2 traffic per call, 20 us forward / 35 us backward for 0.2 GFLOP, three
-// times per inner step.  Here a workgroup takes SIXTEEN latents -- the column count of an MFMA tile -- and its eight waves split the
-// output features of every layer: each weight element is read once per 16 latents as an A-operand dword (coalesced: the output index
-// on the lanes), activations sit in LDS as [feature][latent] (the B operand is one conflict-free ds_read_b32), accumulator tiles go
-// back to LDS as the next layer's input.  Same arithmetic (fp32 throughout), same buffers (`an`, `kv`, latent table, `pg`).
-// K1 itself stays in enf_pack.hip: in this form it measured 21.0 us against 20.0 there.
+// is a chain of small dense products over the B Z latent rows.  The first form (enf_prologue_kernel, enf_prologue_bwd_kernel: 4 latents
+// per workgroup, one output feature per thread, weights streamed from L2 per workgroup) is bound by the latency of that stream -- every
+// workgroup reads all 392 KB of prologue weights for 4 latents: 100 MB of L2 traffic per call, 20 us forward / 35 us backward for
+// 0.2 GFLOP, three times per inner step.  In the second (enf_prologue_bwd_mfma_kernel, fp32 `v_mfma_f32_16x16x4_f32`) a workgroup takes
+// SIXTEEN latents -- the column count of an MFMA tile -- and its eight waves split the output features of every layer: each weight
+// element is read once per 16 latents as an A-operand dword (coalesced: the output index on the lanes), activations sit in LDS as
+// [feature][latent] (the B operand is one conflict-free ds_read_b32), accumulator tiles go back to LDS as the next layer's input.  Same
+// arithmetic (fp32 throughout), same buffers (`an`, `kv`, latent table, `pg`).
+// The forward runs in the first form (20.0 us against 21.0 on the matrix pipe), the backward in the second where D % 32 == 0 (25.5 us
+// against 32.0).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <type_traits>
-#include "enf_layout.h"
 #include "enf_launch.h"
 
+typedef float pf4 __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------- K1 latent prologue
+// One block = ZT consecutive (b,z) rows, 256 threads.  Every weight matrix is read with the OUTPUT index on the
+// lanes (coalesced: stem_w, wk, wv are (in,out) row-major; the logit fold uses the transposed copy muT) and every
+// weight element is read once per ZT latents.  Activations sit in LDS as [feature][latent] so that one
+// ds_read_b128 pair broadcasts the ZT values a weight element multiplies.  LayerNorm: one wave per row.
+#ifndef ENF_PROLOGUE_ZT
+#define ENF_PROLOGUE_ZT 4
+#endif
+constexpr int ZT = ENF_PROLOGUE_ZT;   // latents per block (multiple of 4)
+#ifndef ENF_PROLOGUE_UNROLL
+#define ENF_PROLOGUE_UNROLL 16         // independent weight loads in flight per thread: these kernels are latency chains
+#endif
+#define PRO_UNROLL ENF_PROLOGUE_UNROLL
+
+static __device__ __forceinline__ float wave_sum(float v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct PrologueArgs {
+  const float* p; const float* a; const float* sigma;
+  const char* blob; EnfLayout L;
+  float* lt; float* an; float* kv;
+  int BZ, H, D, C, dp, inv;
+  int Dt;                // true num_hidden (LayerNorm statistics); D may be a zero-padded width
+};
+
+__global__ __launch_bounds__(256) void enf_prologue_kernel(PrologueArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int D = A.D, H = A.H, HD = H * D, C = A.C;
+  float* s_a = sm;                 // [C][ZT]
+  float* s_an = s_a + ZT * C;      // [D][ZT]   stem output, then the normalised + affine row
+  float* s_k = s_an + ZT * D;      // [HD][ZT]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.x * ZT;
+  auto W = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
+  const int stride = enf_lt_stride(H, D);
+  for (int i = tid; i < ZT * C; i += 256) {
+    const int zz = i / C, c = i % C, r = row0 + zz;
+    s_a[c * ZT + zz] = r < A.BZ ? A.a[(size_t)r * C + c] : 0.f;
+  }
+  __syncthreads();
+  // stem: s = a @ Ws + bs  (NEF:220)
+  for (int d = tid; d < D; d += 256) {
+    float acc[ZT];
+    const float bs = W(A.L.stem_b)[d];
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) acc[zz] = bs;
+#pragma unroll PRO_UNROLL
+    for (int c = 0; c < C; ++c) {
+      const float w = W(A.L.stem_w)[(size_t)c * D + d];
+#pragma unroll
+      for (int q = 0; q < ZT / 4; ++q) {
+        const pf4 x = *reinterpret_cast<const pf4*>(s_a + c * ZT + 4 * q);
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(x[zz], w, acc[4 * q + zz]);
+      }
+    }
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) s_an[d * ZT + zz] = acc[zz];
+  }
+  __syncthreads();
+  // LayerNorm (NEF:56): biased variance, eps 1e-6; one wave per row
+  for (int zz = wave; zz < ZT; zz += 4) {
+    const int r = row0 + zz;
+    float v = 0.f;
+    for (int d = lane; d < A.Dt; d += 64) v += s_an[d * ZT + zz];          // statistics over the real features only
+    const float mu = wave_sum(v) / A.Dt;
+    float q = 0.f;
+    for (int d = lane; d < A.Dt; d += 64) { const float t = s_an[d * ZT + zz] - mu; q += t * t; }
+    const float rstd = rsqrtf(wave_sum(q) / A.Dt + 1e-6f);
+    for (int d = lane; d < D; d += 64) {
+      const float sv = s_an[d * ZT + zz];
+      const float xn = (sv - mu) * rstd;
+      if (r < A.BZ) {
+        A.an[(size_t)r * (2 * D + 2) + d] = sv;          // stem output (pre-LN)
+        A.an[(size_t)r * (2 * D + 2) + D + d] = xn;      // normalised, before scale/bias
+      }
+      s_an[d * ZT + zz] = xn * W(A.L.lna_g)[d] + W(A.L.lna_b)[d];
+    }
+    if (lane == 0 && r < A.BZ) { A.an[(size_t)r * (2 * D + 2) + 2 * D] = mu; A.an[(size_t)r * (2 * D + 2) + 2 * D + 1] = rstd; }
+  }
+  __syncthreads();
+  // k = an @ Wk + bk, v0 = an @ Wv + bv   (ECA:93-94)
+  for (int j = tid; j < 2 * HD; j += 256) {
+    const bool isv = j >= HD;
+    const int jj = isv ? j - HD : j;
+    const float* Wm = W(isv ? A.L.wv : A.L.wk);
+    float acc[ZT];
+    const float bb = W(isv ? A.L.bv : A.L.bk)[jj];
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) acc[zz] = bb;
+#pragma unroll PRO_UNROLL
+    for (int d = 0; d < D; ++d) {
+      const float w = Wm[(size_t)d * HD + jj];
+#pragma unroll
+      for (int q = 0; q < ZT / 4; ++q) {
+        const pf4 x = *reinterpret_cast<const pf4*>(s_an + d * ZT + 4 * q);
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(x[zz], w, acc[4 * q + zz]);
+      }
+    }
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) {
+      const int r = row0 + zz;
+      if (!isv) s_k[jj * ZT + zz] = acc[zz];
+      if (r < A.BZ) {
+        A.kv[(size_t)r * 2 * HD + j] = acc[zz];
+        if (isv) A.lt[(size_t)r * stride + enf_lt_off_v0(H, D) + jj] = acc[zz];
+      }
+    }
+  }
+  __syncthreads();
+  // u_h = MU_h k_h  (muT[h][d][i]: the output index i on the lanes)
+  for (int j = tid; j < HD; j += 256) {
+    const int h = j / D, i = j % D;
+    const float* mut = W(A.L.mut) + (size_t)h * D * D + i;
+    float acc[ZT];
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) acc[zz] = 0.f;
+#pragma unroll PRO_UNROLL
+    for (int dd = 0; dd < D; ++dd) {
+      const float w = mut[(size_t)dd * D];
+      const float* kp = s_k + (h * D + dd) * ZT;
+#pragma unroll
+      for (int q = 0; q < ZT / 4; ++q) {
+        const pf4 x = *reinterpret_cast<const pf4*>(kp + 4 * q);
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(x[zz], w, acc[4 * q + zz]);
+      }
+    }
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) {
+      const int r = row0 + zz;
+      if (r < A.BZ) A.lt[(size_t)r * stride + enf_lt_off_u(H, D) + j] = acc[zz];
+    }
+  }
+  // c_h = cvec_h . k_h : one wave per (row, head)
+  for (int t = wave; t < ZT * H; t += 4) {
+    const int zz = t / H, h = t % H, r = row0 + zz;
+    float sacc = 0.f;
+    for (int dd = lane; dd < D; dd += 64) sacc = fmaf(W(A.L.cvec)[h * D + dd], s_k[(h * D + dd) * ZT + zz], sacc);
+    sacc = wave_sum(sacc);
+    if (lane == 0 && r < A.BZ) A.lt[(size_t)r * stride + enf_lt_off_c(H, D) + h] = sacc;
+  }
+  // pose embed (NEF:214-217) + window coefficient
+  if (tid < ZT) {
+    const int r = row0 + tid;
+    if (r < A.BZ) {
+      const float* pp = A.p + (size_t)r * A.dp;
+      float q[4] = {0.f, 0.f, 0.f, 0.f};
+      float wc;
+      const float sg = A.sigma ? A.sigma[r] : 1.f;
+      const bool sphere = A.inv == ENF_INV_LATITUDE_PERIODIC || A.inv == ENF_INV_POLAR_PERIODIC || enf_inv_has_phase(A.inv);
+      if (A.inv == ENF_INV_PONITA || A.inv == ENF_INV_PONITA_FULL) { q[0] = pp[0]; q[1] = pp[1]; q[2] = cosf(pp[2]); q[3] = sinf(pp[2]); }
+      else if (sphere) { q[0] = pp[0]; q[1] = pp[1]; q[2] = sinf(pp[1]); q[3] = cosf(pp[1]); }    // ball: (alpha, beta) play (phi, theta) in the window
+      else { for (int i = 0; i < A.dp && i < 3; ++i) q[i] = pp[i]; }
+      wc = sphere ? 1.f / (2.f * sg * sg) : 1.f / (sg * sg);
+      float* o = A.lt + (size_t)r * stride;
+      for (int i = 0; i < 4; ++i) o[enf_lt_off_pose(H, D) + i] = q[i];
+      o[enf_lt_off_wcoef(H, D)] = wc;
+      if (enf_inv_has_phase(A.inv)) {
+        float lat[2] = {0.f, 0.f};
+        if (A.inv == ENF_INV_BALL) {            // R(alpha, beta, gamma), ball.py:76-84; latent-only invariant r_p
+          const float ca = cosf(pp[0]), sa = sinf(pp[0]), cb = cosf(pp[1]), sb = sinf(pp[1]), cg = cosf(pp[2]), sg2 = sinf(pp[2]);
+          float* R = o + enf_lt_off_ext(H, D);
+          R[0] = ca * cb; R[1] = ca * sb * sg2 - sa * cg; R[2] = ca * sb * cg + sa * sg2;
+          R[3] = sa * cb; R[4] = sa * sb * sg2 + ca * cg; R[5] = sa * sb * cg - ca * sg2;
+          R[6] = -sb;     R[7] = cb * sg2;                R[8] = cb * cg;
+          lat[0] = pp[3];
+        } else { lat[0] = pp[1]; lat[1] = pp[3]; }      // ball_lat: th_p, r_p
+        const float* cq = W(A.L.cphq), *cv = W(A.L.cphv);
+        for (int j = 0; j < D / 2; ++j) {               // phase in revolutions (the kernels' sin/cos take 2 pi t)
+          o[enf_lt_off_phq(H, D) + j] = lat[0] * cq[j] + lat[1] * cq[D / 2 + j];
+          o[enf_lt_off_phv(H, D) + j] = lat[0] * cv[j] + lat[1] * cv[D / 2 + j];
+        }
+      }
+    }
+  }
+}
+
+int enf_launch_prologue(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* a,
+                        const float* sigma, float* lt, float* an, float* kv, hipStream_t st) {
+  PrologueArgs A;
+  A.p = p; A.a = a; A.sigma = sigma; A.blob = blob; A.L = L; A.lt = lt; A.an = an; A.kv = kv;
+  A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp = m.dp; A.inv = m.inv; A.Dt = m.Dt;
+  const size_t smem = sizeof(float) * (ZT * m.C + ZT * m.D + ZT * m.HD);
+  hipLaunchKernelGGL(enf_prologue_kernel, dim3((A.BZ + ZT - 1) / ZT), dim3(256), smem, st, A);
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+
+// ---------------------------------------------------------------- K1 backward
+// dlt (B*Z rows: du | dv0 | dc | dpose | dwcoef) -> dp, da, dsigma.  Same scheme as the forward: gradient rows
+// staged in LDS as [feature][latent], the reduction index off the lanes (mu as stored is [h][i][d], i.e. the
+// output d of the transposed product is contiguous; a_to_k / a_to_v use their transposed copies wkT / wvT).
+struct PrologueBwdArgs {
+  const float* p; const float* sigma; const char* blob; EnfLayout L;
+  const float* an; const float* kv; const float* dlt;
+  float* dp; float* da; float* dsigma;
+  int BZ, H, D, C, dp_dim, inv;
+  int Dt;
+  float* pg;     // weight-gradient backward (or NULL): per latent row [d k (HD) | d an (D) | d s (D) | an (D) | d an * xn (D) | d c_h k_h (HD)],
+                 // the operands of the prologue's X^T delta products and column sums (enf_train.hip); an = the LayerNorm's affine output
+};
+
+__global__ __launch_bounds__(256) void enf_prologue_bwd_kernel(PrologueBwdArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int D = A.D, H = A.H, HD = H * D, C = A.C;
+  float* s_du = sm;                    // [HD][ZT]  d u
+  float* s_dk = s_du + ZT * HD;        // [2HD][ZT] d k | d v0
+  float* s_dan = s_dk + ZT * 2 * HD;   // [D][ZT]
+  float* s_dc = s_dan + ZT * D;        // [H][ZT]
+  float* s_part = s_dc + ZT * H;       // [256][ZT] partial sums of the d(an) stage
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row0 = blockIdx.x * ZT;
+  const int stride = enf_lt_stride(H, D);
+  auto W = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
+  for (int t = tid; t < ZT * HD; t += 256) {
+    const int zz = t / HD, j = t % HD, r = row0 + zz;
+    const float* g = A.dlt + (size_t)(r < A.BZ ? r : 0) * stride;
+    s_du[j * ZT + zz] = r < A.BZ ? g[enf_lt_off_u(H, D) + j] : 0.f;
+    s_dk[(HD + j) * ZT + zz] = r < A.BZ ? g[enf_lt_off_v0(H, D) + j] : 0.f;
+  }
+  if (tid < ZT * H) {
+    const int zz = tid / H, h = tid % H, r = row0 + zz;
+    s_dc[h * ZT + zz] = r < A.BZ ? A.dlt[(size_t)r * stride + enf_lt_off_c(H, D) + h] : 0.f;
+  }
+  __syncthreads();
+  // dk[h*D+d] = sum_i MU_h[i][d] du_h[i] + cvec_h[d] dc_h
+  for (int j = tid; j < HD; j += 256) {
+    const int h = j / D, dd = j % D;
+    const float cv = W(A.L.cvec)[h * D + dd];
+    const float* mu = W(A.L.mu) + (size_t)h * D * D + dd;
+    float acc[ZT];
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) acc[zz] = cv * s_dc[h * ZT + zz];
+#pragma unroll PRO_UNROLL
+    for (int i = 0; i < D; ++i) {
+      const float w = mu[(size_t)i * D];
+      const float* gp = s_du + (h * D + i) * ZT;
+#pragma unroll
+      for (int q = 0; q < ZT / 4; ++q) {
+        const pf4 x = *reinterpret_cast<const pf4*>(gp + 4 * q);
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(x[zz], w, acc[4 * q + zz]);
+      }
+    }
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) {
+      s_dk[j * ZT + zz] = acc[zz];
+      if (A.pg && row0 + zz < A.BZ) {
+        float* pr = A.pg + (size_t)(row0 + zz) * (2 * HD + 4 * D);
+        pr[j] = acc[zz];
+        pr[HD + 4 * D + j] = s_dc[h * ZT + zz] * A.kv[(size_t)(row0 + zz) * 2 * HD + j];
+      }
+    }
+  }
+  __syncthreads();
+  // d(an_affine)[d] = sum_j Wk[d][j] dk[j] + Wv[d][j] dv0[j]  (wkT/wvT: [j][d]); then through scale: dxn = dy * g.
+  // D outputs only: the 256 / D thread groups each take a slice of j and the partial sums meet in LDS
+  {
+    const int nsplit = 256 / D, d = tid % D, part = tid / D, jper = HD / nsplit;
+    float acc[ZT];
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) acc[zz] = 0.f;
+    const float* wkt = W(A.L.wkt) + d;
+    const float* wvt = W(A.L.wvt) + d;
+#pragma unroll PRO_UNROLL
+    for (int j = part * jper; j < (part + 1) * jper; ++j) {
+      const float wk = wkt[(size_t)j * D], wv = wvt[(size_t)j * D];
+#pragma unroll
+      for (int q = 0; q < ZT / 4; ++q) {
+        const pf4 kq = *reinterpret_cast<const pf4*>(s_dk + j * ZT + 4 * q), vq = *reinterpret_cast<const pf4*>(s_dk + (HD + j) * ZT + 4 * q);
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(wk, kq[zz], fmaf(wv, vq[zz], acc[4 * q + zz]));
+      }
+    }
+#pragma unroll
+    for (int zz = 0; zz < ZT; ++zz) s_part[tid * ZT + zz] = acc[zz];
+    __syncthreads();
+    if (tid < D) {
+      const float g = W(A.L.lna_g)[tid];
+#pragma unroll
+      for (int zz = 0; zz < ZT; ++zz) {
+        float v = 0.f;
+        for (int q = 0; q < nsplit; ++q) v += s_part[(q * D + tid) * ZT + zz];
+        s_dan[tid * ZT + zz] = v * g;
+        if (A.pg && row0 + zz < A.BZ) {
+          float* pr = A.pg + (size_t)(row0 + zz) * (2 * HD + 4 * D) + HD;
+          const float xn = A.an[(size_t)(row0 + zz) * (2 * D + 2) + D + tid];
+          pr[tid] = v;
+          pr[2 * D + tid] = xn * g + W(A.L.lna_b)[tid];
+          pr[3 * D + tid] = v * xn;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // LayerNorm backward: ds = rstd * (dxn - mean(dxn) - xn * mean(dxn * xn)); one wave per row
+  for (int zz = wave; zz < ZT; zz += 4) {
+    const int r = row0 + zz;
+    const int rr = r < A.BZ ? r : A.BZ - 1;
+    const float* anr = A.an + (size_t)rr * (2 * D + 2);
+    float v1 = 0.f, v2 = 0.f;
+    for (int d = lane; d < D; d += 64) { const float g = s_dan[d * ZT + zz]; v1 += g; v2 += g * anr[D + d]; }
+    const float m1 = wave_sum(v1) / A.Dt, m2 = wave_sum(v2) / A.Dt;
+    const float rstd = anr[2 * D + 1];
+    for (int d = lane; d < D; d += 64) {
+      const float ds = rstd * (s_dan[d * ZT + zz] - m1 - anr[D + d] * m2);
+      s_dan[d * ZT + zz] = ds;
+      if (A.pg && r < A.BZ) A.pg[(size_t)r * (2 * HD + 4 * D) + HD + D + d] = ds;
+    }
+  }
+  __syncthreads();
+  // da[c] = sum_d Ws[c][d] ds[d]
+  for (int t = tid; t < ZT * C; t += 256) {
+    const int zz = t / C, c = t % C, r = row0 + zz;
+    float sacc = 0.f;
+#pragma unroll PRO_UNROLL
+    for (int d = 0; d < D; ++d) sacc = fmaf(W(A.L.stem_w)[(size_t)c * D + d], s_dan[d * ZT + zz], sacc);
+    if (r < A.BZ) A.da[(size_t)r * C + c] = sacc;
+  }
+  if (tid < ZT) {
+    const int r = row0 + tid;
+    if (r < A.BZ) {
+      const float* g = A.dlt + (size_t)r * stride + enf_lt_off_pose(H, D);
+      const float* pp = A.p + (size_t)r * A.dp_dim;
+      float* o = A.dp + (size_t)r * A.dp_dim;
+      const bool sph = A.inv == ENF_INV_LATITUDE_PERIODIC || A.inv == ENF_INV_POLAR_PERIODIC || enf_inv_has_phase(A.inv);
+      if (A.inv == ENF_INV_PONITA || A.inv == ENF_INV_PONITA_FULL) { o[0] = g[0]; o[1] = g[1]; o[2] = -sinf(pp[2]) * g[2] + cosf(pp[2]) * g[3]; }
+      else if (sph) { o[0] = g[0]; o[1] = g[1] + cosf(pp[1]) * g[2] - sinf(pp[1]) * g[3]; }
+      else { for (int i = 0; i < A.dp_dim && i < 3; ++i) o[i] = g[i]; }
+      if (enf_inv_has_phase(A.inv)) {
+        const float* e = A.dlt + (size_t)r * stride + enf_lt_off_ext(H, D);     // d R (9) | d(latent-only invariants) (2)
+        if (A.inv == ENF_INV_BALL) {
+          const float ca = cosf(pp[0]), sa = sinf(pp[0]), cb = cosf(pp[1]), sb = sinf(pp[1]), cg = cosf(pp[2]), sg2 = sinf(pp[2]);
+          // chain rule through R(alpha, beta, gamma)
+          o[0] += e[0] * (-sa * cb) + e[1] * (-sa * sb * sg2 - ca * cg) + e[2] * (-sa * sb * cg + ca * sg2) +
+                  e[3] * (ca * cb) + e[4] * (ca * sb * sg2 - sa * cg) + e[5] * (ca * sb * cg + sa * sg2);
+          o[1] += e[0] * (-ca * sb) + e[1] * (ca * cb * sg2) + e[2] * (ca * cb * cg) + e[3] * (-sa * sb) + e[4] * (sa * cb * sg2) +
+                  e[5] * (sa * cb * cg) + e[6] * (-cb) + e[7] * (-sb * sg2) + e[8] * (-sb * cg);
+          o[2] = e[1] * (ca * sb * cg + sa * sg2) + e[2] * (-ca * sb * sg2 + sa * cg) + e[4] * (sa * sb * cg - ca * sg2) +
+                 e[5] * (-sa * sb * sg2 - ca * cg) + e[7] * (cb * cg) + e[8] * (-cb * sg2);
+          o[3] = e[9];
+        } else { o[1] += e[9]; o[2] = 0.f; o[3] = e[10]; }
+      }
+      const float sg = A.sigma ? A.sigma[r] : 1.f;
+      const float dwc = A.dlt[(size_t)r * stride + enf_lt_off_wcoef(H, D)];
+      A.dsigma[r] = (sph ? -1.f : -2.f) / (sg * sg * sg) * dwc;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- K1 backward on the matrix pipe, 16 latents per workgroup
 namespace {
 constexpr int LT = 16;            // latents per workgroup
 constexpr int PW = 8;             // waves per workgroup
-typedef float pf4 __attribute__((ext_vector_type(4)));
 
 // acc (16 out features i0.. x 16 latents) += sum_k A[k][i0 + i] * sB[k][latent]:  A row-major with `lda` floats between k rows
 // (the OUTPUT index contiguous: coalesced), sB = LDS [K][LT].
@@ -237,9 +592,9 @@ __global__ __launch_bounds__(64 * PW) void enf_prologue_bwd_mfma_kernel(ProBwdAr
 }
 }  // namespace
 
-extern "C" int enf_launch_prologue_bwd_mfma(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* sigma,
-                                            const float* an, const float* kv, const float* dlt, float* dp, float* da, float* dsigma,
-                                            float* pg, hipStream_t st) {
+static int enf_launch_prologue_bwd_mfma(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* sigma,
+                                        const float* an, const float* kv, const float* dlt, float* dp, float* da, float* dsigma,
+                                        float* pg, hipStream_t st) {
   ProBwdArgs A;
   A.p = p; A.sigma = sigma; A.blob = blob; A.L = L; A.an = an; A.kv = kv; A.dlt = dlt;
   A.dp = dp; A.da = da; A.dsigma = dsigma; A.pg = pg;
@@ -248,5 +603,24 @@ extern "C" int enf_launch_prologue_bwd_mfma(const EnfDims& m, const EnfLayout& L
   static EnfAttrBits attr{0};
   if (!enf_lds_attr(reinterpret_cast<const void*>(enf_prologue_bwd_mfma_kernel), 160 * 1024, attr)) return ENF_ELAUNCH;
   hipLaunchKernelGGL(enf_prologue_bwd_mfma_kernel, dim3((A.BZ + LT - 1) / LT), dim3(64 * PW), smem, st, A);
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+
+int enf_launch_prologue_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p,
+                            const float* sigma, const float* an, const float* kv, const float* dlt, float* dp,
+                            float* da, float* dsigma, hipStream_t st) {
+  return enf_launch_prologue_bwd_wg(m, L, blob, p, sigma, an, kv, dlt, dp, da, dsigma, nullptr, st);
+}
+int enf_launch_prologue_bwd_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p,
+                               const float* sigma, const float* an, const float* kv, const float* dlt, float* dp,
+                               float* da, float* dsigma, float* pg, hipStream_t st) {
+  if (m.D % 32 == 0) return enf_launch_prologue_bwd_mfma(m, L, blob, p, sigma, an, kv, dlt, dp, da, dsigma, pg, st);
+  PrologueBwdArgs A;
+  A.pg = pg;
+  A.p = p; A.sigma = sigma; A.blob = blob; A.L = L; A.an = an; A.kv = kv; A.dlt = dlt;
+  A.dp = dp; A.da = da; A.dsigma = dsigma;
+  A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
+  const size_t smem = sizeof(float) * (ZT * 3 * m.HD + ZT * m.D + ZT * m.H + ZT * 256);
+  hipLaunchKernelGGL(enf_prologue_bwd_kernel, dim3((A.BZ + ZT - 1) / ZT), dim3(256), smem, st, A);
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }

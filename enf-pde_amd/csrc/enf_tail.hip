@@ -11,7 +11,6 @@
 // delta[n,h] = sum_d d(ybar)[n,h,d] * ybar[n,h,d]  (the softmax-backward row constant).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "enf_layout.h"
 #include "enf_launch.h"
 #define ENF_PIPE_ONE_RS 1      // the tail streams from the weight blob only (enf_device.h: stage_issue_p)
 #include "enf_device.h"
@@ -448,18 +447,12 @@ static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st) {
   return opt ? go(enf_tail_fwd_kernel<D, H, BF16, false, true>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false>);
 }
 
-extern "C" int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
-                                  const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
-extern "C" int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
-                               const float* dout, float* dybar, float* delta, float* act, int bwd, int opt, hipStream_t st) {
+int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
+                    const float* dout, float* dybar, float* delta, float* act, int bwd, int opt, hipStream_t st) {
   return enf_launch_tail_wg(m, L, blob, ybar, out, dout, dybar, delta, act, nullptr, bwd, opt, st);
 }
-// tdel != NULL (backward only): the weight-gradient form of the backward -- it also leaves every layer's input (in `act`, in place
-// of the pre-activations) and delta (in `tdel`) for the X^T delta products of enf_train.hip
-extern "C" int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                                    float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st);
-extern "C" int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
-                                  const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st) {
+int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
+                       const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
   A.target = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f;
@@ -479,10 +472,8 @@ extern "C" int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const ch
   return ENF_EUNSUPPORTED;
 }
 
-// the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
-// backward chain -> d ybar, delta
-extern "C" int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                                    float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st) {
+int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
+                         float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
   A.ybar = ybar; A.blob = blob; A.L = L; A.out = nullptr; A.dout = nullptr; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = nullptr;

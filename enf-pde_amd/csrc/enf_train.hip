@@ -3,7 +3,7 @@
 //
 //   d out --tail backward (enf_tail.hip, weight-gradient form)--> d ybar, delta, and per query every tail layer's input / delta
 //         --K3 (store) + K4 (enf_pair_bwd.hip, enf_xtd.hip)-----> d lt and the ten per-pair tensors' gradients (97 % of the FLOPs)
-//         --prologue backward (enf_pack.hip, with operand rows)--> d p, d a, d sigma, and per latent the prologue's inputs / deltas
+//         --prologue backward (enf_prologue.hip, operand rows)---> d p, d a, d sigma, and per latent the prologue's inputs / deltas
 //         --X^T delta products + column sums (this file)---------> gradients of the FOLDED tail / prologue matrices
 //         --fold backward (this file)-----------------------------> the 46 Flax-named tensors (exact chain rule through
 //                                                                    enf_pack_weights' folds, enf_layout.h)
@@ -11,22 +11,7 @@
 // small (rows = B N queries or B Z latents, at most 256 x 256 outputs): fp32 on the matrix pipe (v_mfma_f32_16x16x4_f32), split
 // over row slices, slices summed in a fixed order -- same inputs, same bits.
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
 #include "enf_launch.h"
-
-int enf_side_join_pending(hipStream_t st, const void* workspace);      // enf_api.hip
-extern "C" {
-int enf_launch_prologue(const EnfDims&, const EnfLayout&, const char*, const float*, const float*, const float*, float*,
-                        float*, float*, hipStream_t);
-int enf_launch_prologue_bwd_wg(const EnfDims&, const EnfLayout&, const char*, const float*, const float*, const float*,
-                               const float*, const float*, float*, float*, float*, float*, hipStream_t);
-int enf_launch_pair_bwd(const EnfDims&, const EnfLayout&, const char*, const float*, long long, const float*, const float*,
-                        const float*, const float*, float*, void* const*, const char*, const float*, float*, hipStream_t);
-int enf_launch_tail_wg(const EnfDims&, const EnfLayout&, const char*, const float*, float*, const float*, float*, float*, float*,
-                       float*, int, int, hipStream_t);
-}
-size_t enf_xtd_part_bytes(const EnfDims& m, long long P);
-int enf_launch_xtd(const EnfDims& m, void* const* store, long long P, float* const* dpair, float* part, int accumulate, hipStream_t st);
 
 typedef float tf4 __attribute__((ext_vector_type(4)));
 
@@ -219,7 +204,7 @@ struct TrainScratch {
   size_t fold;      // folded-matrix gradients and temporaries
   size_t part;      // X^T Y slice partials
   size_t total;
-  size_t part_floats, pair_bytes;
+  size_t part_floats;
 };
 inline size_t pair_grad_floats(const EnfDims& m) {
   const size_t D = m.D, HD = m.HD;
@@ -230,16 +215,11 @@ inline size_t fold_floats(const EnfDims& m) {
   // dWB HDxHD | dbB HD | dwf1 HDxHD | dbF1 HD | T HDxHD | dT HDxHD | dMU H DxD | dcvec HD | dmxw DxD | dmxb D
   return 4 * HD * HD + 3 * HD + H * D * D + D * D + D + 256;
 }
-size_t bw_store_bytes_(const EnfDims& m, int cb) { return enf_align((size_t)cb * m.Z * m.N * m.D * (m.bf16 ? 2 : 4)); }
-size_t bw_pair_bytes_(const EnfDims& m, int cb) {
-  return (size_t)ENF_NUM_STORE(m.H) * bw_store_bytes_(m, cb) + enf_align(enf_xtd_part_bytes(m, (long long)cb * m.Z * m.N));
-}
 TrainScratch train_scratch(const EnfDims& m, int cb) {
   TrainScratch s;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o = enf_align(o + bytes); return r; };
-  s.pair_bytes = bw_pair_bytes_(m, cb);
-  s.pair = take(s.pair_bytes);
+  s.pair = take(enf_wgrad_scratch_bytes(m, cb));
   s.tdel = take(sizeof(float) * (size_t)m.B * m.N * (2 * m.HD + 2 * m.D));
   s.pg = take(sizeof(float) * (size_t)m.B * m.Z * (2 * m.HD + 4 * m.D));
   s.dpair = take(sizeof(float) * pair_grad_floats(m));
@@ -260,34 +240,29 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
                                 const float* const* T, const void* packed, const float* ybar, const float* lse, const float* dout,
                                 float* dp, float* da, float* dsigma, float* const* dW, float* dx, void* workspace,
                                 size_t workspace_bytes, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
-  int rc = enf_check_desc(d);
-  if (rc) return rc;
-  if (!x || !p || !a || !T || !packed || !ybar || !lse || !dout || !dp || !da || !dsigma || !dW || !workspace || !scratch) return ENF_EINVAL;
-  if (d->use_window && !sigma) return ENF_EINVAL;
-  const bool ffn = d->embedding == ENF_EMB_FFN;
-  for (int i = 0; i < ENF_NUM_TENSORS; ++i) {
-    const bool unused = ffn && (i == ENF_W_RQ_W1 || i == ENF_W_RV_W1);        // (include/enf_hip.h, ENF_EMB_FFN)
-    if (!T[i] && !unused) return ENF_EINVAL;
-    if (!dW[i] && !unused && i != ENF_W_RQ_COEF && i != ENF_W_RV_COEF) return ENF_EINVAL;
+  // every pointer the call reads through, the tensor tables' entries included (d is looked at only if it is there: what is
+  // wrong with it is enf_call's to report, first)
+  bool ptrs = x && p && a && T && ybar && lse && dout && dp && da && dsigma && dW && scratch;
+  for (int i = 0; ptrs && d && i < ENF_NUM_TENSORS; ++i) {
+    const bool unused = d->embedding == ENF_EMB_FFN && (i == ENF_W_RQ_W1 || i == ENF_W_RV_W1);        // (include/enf_hip.h, ENF_EMB_FFN)
+    ptrs = unused || (T[i] && (dW[i] || i == ENF_W_RQ_COEF || i == ENF_W_RV_COEF));
   }
-  EnfDims m = enf_dims(d);
+  EnfCall c;
+  int rc = enf_call(c, d, ptrs, sigma, packed, workspace, workspace_bytes, stream);
+  if (rc) return rc;
+  const EnfDims& m = c.m;
   if (m.OB != 1) return ENF_EUNSUPPORTED;
-  const EnfLayout L = enf_layout(m);
-  const EnfWorkspace W = enf_workspace(m);
-  if (workspace_bytes < W.total) return ENF_EWORKSPACE;
-  // the largest chunk of signals whose activation store fits (with relu masks: whole groups of mask_signals)
-  const int step = m.mask_mode == ENF_MASK_READ && m.mask_B < m.B ? m.mask_B : 1;
-  int cb = m.B;
-  while (cb > step && train_scratch(m, cb).total > scratch_bytes) cb = (cb - 1) / step * step;
-  if (cb < 1) return ENF_EWORKSPACE;
+  const EnfLayout& L = c.L;
+  const EnfWorkspace& W = c.W;
+  // the largest chunk of signals whose activation store fits
+  const int cb = enf_wgrad_chunk(m, scratch_bytes, [&](int n) { return train_scratch(m, n).total; });
+  if (!cb) return ENF_EWORKSPACE;
   const TrainScratch S = train_scratch(m, cb);
-  if (S.total > scratch_bytes) return ENF_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
+  hipStream_t st = c.st;
   char* sc = (char*)scratch;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  auto F = [&](size_t off) { return c.F(off); };
   auto G = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
-  const char* blob = (const char*)packed;
+  const char* blob = c.blob;
   auto Bf = [&](size_t off) { return reinterpret_cast<const float*>(blob + off); };
   const int D = m.D, H = m.H, HD = m.HD, C = m.C, O = m.O;
   const long long BN = (long long)m.B * m.N, BZ = (long long)m.B * m.Z;
@@ -300,8 +275,7 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   float* tdel = G(S.tdel);
   if ((rc = enf_launch_tail_wg(m, L, blob, ybar, nullptr, dout, F(W.dybar), F(W.delta), F(W.tail_act), tdel, 1, treuse ? 1 : 0, st))) return rc;
 
-  // ---- 2. the per-pair chain: K3 with the activation store, K4 (chunked over signals like enf_backward_weights)
-  if (hipMemsetAsync(F(W.dlt), 0, sizeof(float) * (size_t)BZ * stride, st) != hipSuccess) return ENF_ELAUNCH;
+  // ---- 2. the per-pair chain: K3 with the activation store, K4, chunked over signals (enf_xtd.hip)
   float* dpair[ENF_NUM_PAIR_TENSORS];
   {
     float* q = G(S.dpair);
@@ -310,23 +284,8 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
     for (int i = 0; i < 10; ++i) { dpair[i] = q; q += sz[i]; }
     dpair[ENF_P_COEFQ] = dpair[ENF_P_COEFV] = nullptr;
   }
-  {
-    void* store[ENF_NUM_STORE(4)];
-    const size_t sb = bw_store_bytes_(m, cb);
-    for (int i = 0; i < ENF_NUM_STORE(H); ++i) store[i] = sc + S.pair + (size_t)i * sb;
-    float* part = reinterpret_cast<float*>(sc + S.pair + (size_t)ENF_NUM_STORE(H) * sb);
-    for (int b0 = 0; b0 < m.B; b0 += cb) {
-      const int nb = b0 + cb <= m.B ? cb : m.B - b0;
-      EnfDims mc = m;
-      mc.B = nb; mc.mask_b0 = b0;
-      const size_t qo = (size_t)b0 * m.N;
-      if ((rc = enf_launch_pair_bwd(mc, L, blob, x + (size_t)b0 * x_bstride, x_bstride, F(W.lt) + (size_t)b0 * m.Z * stride,
-                                    lse + qo * H, F(W.dybar) + qo * HD, F(W.delta) + qo * H, F(W.dlt) + (size_t)b0 * m.Z * stride, store,
-                                    nullptr, nullptr, dx ? dx + qo * m.dx : nullptr, st)))
-        return rc;
-      if ((rc = enf_launch_xtd(mc, store, (long long)nb * m.Z * m.N, dpair, part, b0 > 0, st))) return rc;
-    }
-  }
+  if ((rc = enf_launch_wgrad_chunks(m, L, blob, cb, x, x_bstride, F(W.lt), lse, F(W.dybar), F(W.delta), F(W.dlt), dx, sc + S.pair, dpair, st)))
+    return rc;
 
   // ---- 3. prologue backward: d p, d a, d sigma + the operand rows of its weight gradients
   float* pg = G(S.pg);

@@ -20,7 +20,6 @@
 // the result is converted and stored 16 bytes per lane, lane-linear, no transpose.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "enf_layout.h"
 #include "enf_launch.h"
 #include "enf_device.h"
 
@@ -217,10 +216,8 @@ static int launch_wz(const WzArgs& A, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }
 
-extern "C" int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const float* lt, char* wz, float* wzb,
-                             char* wzu, char* wzt, hipStream_t st) {
-  // wzt == NULL: forward panels only, packed back to back in wz (the z-fold forward kernel's layout);
-  // wzt != NULL: `wzt` holds [forward | backward] panel pairs per (latent, head) and `wz` is ignored
+int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const float* lt, char* wz, float* wzb,
+                  char* wzu, char* wzt, hipStream_t st) {
   WzArgs A;
   const size_t PB = enf_panel_bytes(m.D, m.D, m.bf16);
   A.lt = lt; A.blob = blob; A.L = L; A.wzb = wzb; A.wzu = wzu; A.BZ = m.B * m.Z;

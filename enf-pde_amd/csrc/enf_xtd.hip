@@ -19,7 +19,6 @@
 // Why not inside K3: the accumulators of the (3 + 3H) D x D products are 9 * 64 KB = 576 KB in fp32 at D = 128, H = 2 --
 // more than the 512 KB vector register file of a CU, with K3 itself needing all of it ("Training path").
 #include <hip/hip_runtime.h>
-#include "enf_layout.h"
 #include "enf_launch.h"
 #include "enf_device.h"
 
@@ -279,8 +278,6 @@ size_t enf_xtd_part_bytes(const EnfDims& m, long long P) {
   return enf_align(sizeof(float) * (size_t)xtd_slices(P, NP) * NP * (m.D + 1) * m.D);
 }
 
-// store: the ENF_NUM_STORE(H) device buffers K3 wrote for P rows; dpair: ENF_NUM_PAIR_TENSORS fp32 device pointers in
-// ENF_P_* order (the two coefficient entries are not touched); accumulate = add to what dpair holds (later chunks)
 int enf_launch_xtd(const EnfDims& m, void* const* store, long long P, float* const* dpair, float* part, int accumulate,
                    hipStream_t st) {
   const int H = m.H, D = m.D, HD = m.HD;
@@ -310,4 +307,37 @@ int enf_launch_xtd(const EnfDims& m, void* const* store, long long P, float* con
   if (D == 128) return m.bf16 ? launch_xtd<128, true>(A, R, KS, st) : launch_xtd<128, false>(A, R, KS, st);
   if (D == 64) return m.bf16 ? launch_xtd<64, true>(A, R, KS, st) : launch_xtd<64, false>(A, R, KS, st);
   return ENF_EUNSUPPORTED;
+}
+
+// ---- the chunked pass: K3 with the activation store, then K4, per chunk of signals
+static size_t wgrad_store_bytes(const EnfDims& m, int cb) {
+  return enf_align((size_t)cb * m.Z * m.N * m.D * (m.bf16 ? 2 : 4));          // one ENF_S_* buffer of a chunk
+}
+// [ENF_NUM_STORE(H) store buffers | K4 partials].  Every piece is a multiple of 256 bytes, so the sum is what
+// enf_backward_weights asks for as it stands and also where enf_backward_all's next region starts.
+size_t enf_wgrad_scratch_bytes(const EnfDims& m, int cb) {
+  return (size_t)ENF_NUM_STORE(m.H) * wgrad_store_bytes(m, cb) + enf_xtd_part_bytes(m, (long long)cb * m.Z * m.N);
+}
+
+int enf_launch_wgrad_chunks(const EnfDims& m, const EnfLayout& L, const char* blob, int cb, const float* x, long long x_bstride,
+                            const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt, float* dx,
+                            char* scratch, float* const* dpair, hipStream_t st) {
+  if (hipMemsetAsync(dlt, 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+  const int stride = enf_lt_stride(m.H, m.D);
+  void* store[ENF_NUM_STORE(4)];
+  const size_t sb = wgrad_store_bytes(m, cb);
+  for (int i = 0; i < ENF_NUM_STORE(m.H); ++i) store[i] = scratch + (size_t)i * sb;
+  float* part = reinterpret_cast<float*>(scratch + (size_t)ENF_NUM_STORE(m.H) * sb);
+  for (int b0 = 0; b0 < m.B; b0 += cb) {
+    const int nb = b0 + cb <= m.B ? cb : m.B - b0;
+    EnfDims mc = m;
+    mc.B = nb; mc.mask_b0 = b0;
+    const size_t qo = (size_t)b0 * m.N;
+    int rc = enf_launch_pair_bwd(mc, L, blob, x + (size_t)b0 * x_bstride, x_bstride, lt + (size_t)b0 * m.Z * stride, lse + qo * m.H,
+                                 dybar + qo * m.HD, delta + qo * m.H, dlt + (size_t)b0 * m.Z * stride, store, nullptr, nullptr,
+                                 dx ? dx + qo * m.dx : nullptr, st);
+    if (rc) return rc;
+    if ((rc = enf_launch_xtd(mc, store, (long long)nb * m.Z * m.N, dpair, part, b0 > 0, st))) return rc;
+  }
+  return ENF_OK;
 }
