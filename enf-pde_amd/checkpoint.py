@@ -52,7 +52,7 @@ def load_tree(path, device="cpu", dtype=torch.float32):
 # Training-state checkpoints (experiments/fitting/trainers/_base_pde_trainer.py:192-237: the reference saves the whole
 # TrainState -- params, every optimiser's count / mu / nu -- plus the config through orbax, and restores it into a freshly
 # initialised state).  One ``.npz`` per checkpoint, every array in its own dtype:
-#   params/...                         the parameter tree (nef weights, meta-init latents, inner rates, ODE weights)
+#   params/...                         the parameter tree (nef weights, meta-init latents / latent table, inner rates, ODE weights)
 #   <name>_opt_state/count (int64), <name>_opt_state/mu/<i>, <name>_opt_state/nu/<i>     for every optimiser state
 #   step, epoch (int64), rng_state (uint8: torch.Generator.get_state()), config_json (the config as JSON)
 def _to_plain(cfg):
@@ -98,7 +98,11 @@ def load_train_state(path, template, device=None):
         flat = {k: z[k] for k in z.files}
     state = copy.copy(template)
     tflat = flatten_tree(template.params, ("params",))
-    if set(tflat) != {k for k in flat if k.startswith("params/")}:
+    saved = {k for k in flat if k.startswith("params/")}
+    if set(tflat) != saved:
+        if set(tflat) - saved and all(k.startswith("params/ode_params/") for k in set(tflat) ^ saved):
+            raise ValueError("checkpoint holds no latent-ODE state (it was written by a trainer built without an ode_model), "
+                             "but this trainer has one: load it into a trainer built without ode_model")
         raise ValueError("checkpoint parameter tree does not match this trainer's: "
                          f"{sorted(set(tflat) ^ {k for k in flat if k.startswith('params/')})[:6]}")
     to = lambda a, like: torch.as_tensor(a).to(device=device or like.device, dtype=like.dtype)

@@ -7,15 +7,16 @@
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
   ode_models           ode_models/ponita_ode_g.py, mlp_ode.py  PonitaODEGen (fused SepGconv HIP kernels), MLPODE
   solve_latent_ode     trainers/trainer_utils/solvers.py:69-162 Euler / RK4 over the latent tuple
-  NonMetaPDETrainer    trainers/nonmaml_pde_trainer.py:56-171  auto-decoder training step (first-order, exact)
+  NonMetaPDETrainer    trainers/nonmaml_pde_trainer.py:56-307  auto-decoder trainer: nef steps (first-order, exact), ode step, val_step
+  draw_point_masks     nonmaml_pde_trainer.py:273-283          per-frame point subsets of the roll-out loss (shared by both trainers)
 """
 from .model import get_model_pde
 from .inner_loop import inner_loop, decode, make_masks, default_meta_sgd_lrs
 from .parallel import shard_range, allreduce_mean_, init_distributed
-from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState
+from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState, draw_point_masks
 from .trainers.trainer_utils import solve_latent_ode
 from .ode_models import PonitaODEGen, MLPODE
 
 __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "default_meta_sgd_lrs", "shard_range",
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
-           "solve_latent_ode", "PonitaODEGen", "MLPODE"]
+           "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks"]

@@ -1,6 +1,7 @@
-"""Auto-decoder (non-meta) ENF trainer -- the nef phase of experiments/fitting/trainers/nonmaml_pde_trainer.py.
+"""Auto-decoder (non-meta) ENF trainer, mirroring experiments/fitting/trainers/nonmaml_pde_trainer.py: the nef phase, the
+latent-ODE phase and the validation roll-out.
 
-Every training signal owns a row of latents in a PositionOrientationFeatureAutodecoder (:37-45); one step is
+Every training signal owns a row of latents in a PositionOrientationFeatureAutodecoder (:37-45); one nef step is
 
     recon_loss, grads = jax.value_and_grad(self.enf_loss)(params, state, autodecoder_fn, trajectory, mask, traj_idx)   (:118)
     nef:          clip_by_global_norm(1.0) -> adamw(lr_enf)                                                        (:63-66,121-122)
@@ -9,14 +10,30 @@ Every training signal owns a row of latents in a PositionOrientationFeatureAutod
 with enf_loss = mean((nef.apply(params['nef'], coords[mask], *autodecoder(params['autodecoder'], traj_idx)) - state)^2)
 (:309-341).  The gradient is first order, so it is exactly what the training path of the decoder provides (weight
 gradients through the HIP pair kernels' activation store, latent gradients through the latent table).
+
+The ODE phase (:173-199, 244-307) trains the latent ODE on the STORED latents: the rows of ``traj_idx`` are rolled out over
+the first 10 frames (t0 = 0, tf = 9, node.dt, node.method), all B x 10 signal-frames are decoded in one nef.apply at
+``max_num_sampled_points`` random grid points per frame and compared with the trajectory;
+
+    ode:          clip_by_global_norm(1.0) -> adamw(lr_enf)       (:68-69 -- learning_rate_enf, not learning_rate_ode)
+
+The reference differentiates the loss w.r.t. every parameter group and keeps the ODE's (:182-187); here only the ODE
+parameters are differentiated: nef weights and table rows enter as constants, so the decoder's backward is its latent
+backward alone (HIP pair kernels) -> solver -> ODE model.  From the latents on this is the arithmetic of the MAML trainer's
+ode_loss / rollout; both trainers take it from latent_ode.LatentODEMixin.  ``val_step`` (:201-241) rolls the same rows out
+over 20 frames, decodes the full grid in chunks of ``max_num_sampled_points`` and returns the errors of frames 0..9 and 10..19.
 """
 from dataclasses import dataclass, field
 
 import torch
 
-from ..optim import Adam, AdamW, clip_by_global_norm
+from ..optim import Adam, AdamW, clip_by_global_norm, global_norm
 from ..parallel import allreduce_mean_
+from ..inner_loop import decode
+from .latent_ode import LatentODEMixin, _leaves, _unflatten
 from .pde_trainer import _tree_from_tensors
+
+TRAIN_FRAMES, VAL_FRAMES = 10, 20            # fixed in the reference (:206,241,252), not read from the dataset config
 
 
 @dataclass
@@ -24,35 +41,49 @@ class NonMetaTrainState:
     params: dict
     nef_opt_state: dict
     autodecoder_opt_state: dict
+    ode_opt_state: dict = None
     step: int = 0
     rng: torch.Generator = field(default_factory=lambda: torch.Generator().manual_seed(0))
 
 
-class NonMetaPDETrainer:
+class NonMetaPDETrainer(LatentODEMixin):
     """``config`` fields used: optimizer.learning_rate_enf, optimizer.learning_rate_codes,
-    training.max_num_sampled_points.  ``autodecoder``: enf_pde_amd.enf.latents.autodecoder.PositionOrientationFeatureAutodecoder
-    sized for the training set.
+    training.max_num_sampled_points; with an ``ode_model`` also node.dt, node.method and, for the phase schedule,
+    training.nef / training.ode .train_from_epoch / .train_until_epoch.
+    ``autodecoder``: enf_pde_amd.enf.latents.autodecoder.PositionOrientationFeatureAutodecoder sized for the training set.
+    ``ode_model`` (keyword only): PonitaODEGen / MLPODE, the second value of get_model_pde(cfg).  Without one the train state
+    has no ODE entries and ode_train_step / val_step raise ValueError.
 
-    Scope: SURVEY.md 8f row 1 asks for the nef phase (the first-order decoder gradients this build accelerates).  The
-    reference's other two steps of this trainer -- ``_ode_train_step`` (:173-199, clip + adamw on the latent ODE over the
-    auto-decoder's latents) and ``_val_step`` (:201-241, fit validation latents from scratch, then roll out) -- are beyond
-    section 8; they exist here as methods that raise, so that a config which schedules them fails loudly instead of
-    silently training less than the reference does.  The MAML trainer (pde_trainer.py) has both phases."""
+    ``training.graph_ode_training`` is honoured as in the MAML trainer (ode_train_step replays captured derivative
+    evaluations; off by default).  Validation signals need no second shell here: a shell only indexes the table it is given,
+    so val_step takes the shell as an argument and reads ``state.params['autodecoder']`` through it (:209-210), which the
+    caller has replaced by the validation table as validate_epoch does (:437-444)."""
 
-    def __init__(self, config, nef, autodecoder, coords, seed=42):
+    def __init__(self, config, nef, autodecoder, coords, seed=42, *, ode_model=None):
         self.config, self.nef, self.autodecoder, self.coords, self.seed = config, nef, autodecoder, coords, seed
-        self.nef_opt = AdamW(config.optimizer.learning_rate_enf)
+        self.ode_model = ode_model
+        self.graph_ode_training = bool(getattr(getattr(config, "training", None), "graph_ode_training", False))
+        self.nef_opt = AdamW(config.optimizer.learning_rate_enf)                # after clip_by_global_norm(1.0)
         self.autodecoder_opt = Adam(config.optimizer.learning_rate_codes)
+        self.ode_opt = AdamW(config.optimizer.learning_rate_enf) if ode_model is not None else None    # after clip (:68-69)
 
-    def init_train_state(self, nef_params=None):
+    def init_train_state(self, nef_params=None, ode_params=None):
         dev = self.coords.device
         g = torch.Generator().manual_seed(self.seed)
         ad = self.autodecoder.init(g, device=dev)
         if nef_params is None:
             nef_params = self.nef.init(g, device=dev)
-        return NonMetaTrainState(params={"nef": nef_params, "autodecoder": ad},
+        params = {"nef": nef_params, "autodecoder": ad}
+        ode_opt_state = None
+        if self.ode_model is not None:                                           # :80-81,89: shapes from row 0 of the table
+            if ode_params is None:
+                ode_params = self.ode_model.init(self.seed + 1, self.autodecoder.apply(ad, torch.tensor([0])), device=dev)
+            params["ode_params"] = ode_params
+            ode_opt_state = self.ode_opt.init(_leaves(ode_params))
+        return NonMetaTrainState(params=params,
                                  nef_opt_state=self.nef_opt.init(self.nef.param_tensors(nef_params)),
-                                 autodecoder_opt_state=self.autodecoder_opt.init(list(ad["params"].values())), step=0, rng=g)
+                                 autodecoder_opt_state=self.autodecoder_opt.init(list(ad["params"].values())),
+                                 ode_opt_state=ode_opt_state, step=0, rng=g)
 
     def save_checkpoint(self, state, path, epoch=0):
         """_base_pde_trainer.py:192-202: the whole train state (parameters, every optimiser's count / mu / nu, step, rng)
@@ -104,9 +135,9 @@ class NonMetaPDETrainer:
             nef_params = _tree_from_tensors(new_w, self.nef)
         P = state.params["autodecoder"]["params"]
         new_p, ad_state = self.autodecoder_opt.update([ga[k] for k in names], state.autodecoder_opt_state, [P[k] for k in names])
-        return loss, NonMetaTrainState(params={"nef": nef_params, "autodecoder": {"params": dict(zip(names, new_p))}},
-                                       nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state, step=state.step + 1,
-                                       rng=state.rng)
+        params = dict(state.params, nef=nef_params, autodecoder={"params": dict(zip(names, new_p))})    # ode_params carried over
+        return loss, NonMetaTrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state,
+                                       ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
 
     def nef_train_step(self, state, batch, mask=None):
         """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137)"""
@@ -116,10 +147,97 @@ class NonMetaPDETrainer:
         """Only the latents move (:139-171)."""
         return self._step(state, batch, mask, False)
 
-    def ode_train_step(self, state, batch):
-        raise NotImplementedError("NonMetaPDETrainer: the latent-ODE phase of nonmaml_pde_trainer.py:173-199 is outside "
-                                  "SURVEY.md section 8; use MetaSGDPDETrainer.ode_train_step for the latent ODE")
+    # ------------------------------------------------------------------ latent-ODE phase (:173-307)
+    def _need_ode(self, what):
+        if self.ode_model is None:
+            raise ValueError(f"NonMetaPDETrainer.{what} needs a latent ODE: build the trainer with ode_model=... "
+                             "(the second value of get_model_pde(cfg))")
 
-    def val_step(self, state, batch):
-        raise NotImplementedError("NonMetaPDETrainer: the validation roll-out of nonmaml_pde_trainer.py:201-241 is outside "
-                                  "SURVEY.md section 8; use MetaSGDPDETrainer.val_step")
+    def ode_loss(self, params, trajectory, traj_idx, point_masks=None, generator=None, graph=False):
+        """:244-307.  The first 10 frames of ``trajectory`` (B, T, *grid, O) against the roll-out of the table rows ``traj_idx``
+        (B,) long, decoded at ``point_masks`` (frames, n_s) long -- one permutation of the grid per frame, shared by the signals of
+        the batch; drawn from ``generator`` when None and max_num_sampled_points is smaller than the grid."""
+        self._need_ode("ode_loss")
+        trajectory = trajectory[:, :TRAIN_FRAMES]                                # :252
+        z0 = self.autodecoder.apply(params["autodecoder"], traj_idx)             # :255
+        return self.rollout_loss(params["nef"], params["ode_params"], z0, trajectory, point_masks, generator, graph=graph)
+
+    def ode_train_step(self, state, batch, point_masks=None):
+        """:173-199: one clip_by_global_norm(1) + AdamW step on the ODE parameters only.  ``batch`` = (trajectory (B, T, *grid, O),
+        trajectory indices (B,) long) or the reference's (trajectory, _, traj_idx): the trajectory is ``batch[0]`` and the indices
+        are ``batch[-1]``, whatever lies between is ignored.  nef weights, the latent table and their optimiser states are handed
+        on untouched; the gradient runs decoder -> (HIP latent backward) -> solver -> ODE model.  In a multi-rank run every rank
+        passes its shard; gradients and loss are averaged by one flat all-reduce.
+        ``point_masks`` (10, n_s) long, or None to draw them from ``state.rng``.  The reference splits ``state.rng`` every step
+        (:175); here the generator advances only when masks are drawn (ten permutations), so a step with given masks, or on a grid
+        no larger than max_num_sampled_points, leaves it where it was.
+        A loss or gradient that is not finite raises FloatingPointError BEFORE anything is updated (on every rank alike: the test
+        is on the all-reduced values), so it reaches neither the parameters nor the AdamW moments.  The known way there is a
+        table still at its initial value: with features exactly 1 the ODE model sees a - 1 = 0, every LayerNorm(eps 1e-6) in it
+        normalises a constant vector with gain 1000, and the Jacobian of da/dt w.r.t. a (~1e5 for three layers) compounds over
+        the nine steps of the roll-out beyond the fp32 range."""
+        self._need_ode("ode_train_step")
+        trajectory, traj_idx = batch[0], batch[-1]
+        leaves, graph = self._ode_train_leaves(state.params["ode_params"])
+        P = state.params["autodecoder"]["params"]
+        params = {"nef": state.params["nef"], "autodecoder": {"params": {k: v.detach() for k, v in P.items()}},
+                  "ode_params": _unflatten(state.params["ode_params"], leaves)}
+        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph)
+        grads = torch.autograd.grad(loss, leaves, allow_unused=True)
+        grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
+        flat = grads + [loss.detach().reshape(1)]
+        allreduce_mean_(flat, weight=trajectory.shape[0])
+        if not bool(torch.isfinite(torch.stack([global_norm(grads), flat[-1][0]])).all()):
+            raise FloatingPointError(f"NonMetaPDETrainer.ode_train_step: loss {float(flat[-1][0])}, ODE gradient norm "
+                                     f"{float(global_norm(grads))} at step {state.step}; nothing was updated.  (A latent table still "
+                                     "at its initial value, features exactly 1, does this through the 10-frame roll-out.)")
+        new_leaves, ode_opt_state = self.ode_opt.update(clip_by_global_norm(grads, 1.0), state.ode_opt_state,
+                                                        [t.detach() for t in leaves])
+        params = dict(state.params, ode_params=_unflatten(state.params["ode_params"], new_leaves))
+        return flat[-1][0], NonMetaTrainState(params=params, nef_opt_state=state.nef_opt_state,
+                                              autodecoder_opt_state=state.autodecoder_opt_state, ode_opt_state=ode_opt_state,
+                                              step=state.step + 1, rng=state.rng)
+
+    @torch.no_grad()
+    def val_step(self, state, batch, autodecoder=None):
+        """:201-241: ``batch`` = (trajectory, traj_idx) or (trajectory, _, traj_idx), read as ``batch[0]`` and ``batch[-1]`` like
+        ode_train_step's.  The first 20 frames against the roll-out of the rows ``traj_idx`` of ``state.params['autodecoder']``, read
+        through ``autodecoder`` (a shell for validation signals; default: the trainer's own), decoded on the full grid in chunks of
+        max_num_sampled_points.  Returns (mse over frames 0..9, mse over frames 10..19); a trajectory of at most 10 frames gives
+        zero for the second.  Roll-outs of more than 4 frames replay one captured hipGraph per derivative evaluation."""
+        self._need_ode("val_step")
+        trajectory, traj_idx = batch[0], batch[-1]
+        trajectory = trajectory[:, :VAL_FRAMES]                                  # :206
+        B, T = trajectory.shape[:2]
+        z0 = (autodecoder or self.autodecoder).apply(state.params["autodecoder"], traj_idx)     # :209-210
+        sol = self.rollout(state.params["ode_params"], tuple(None if v is None else v.detach() for v in z0), T, graph=T > 4)
+        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
+        recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl,
+                       chunk=self.config.training.max_num_sampled_points).reshape(trajectory.shape)    # :228-238
+        err = (recon - trajectory) ** 2
+        return err[:, :TRAIN_FRAMES].mean(), (err[:, TRAIN_FRAMES:].mean() if T > TRAIN_FRAMES else err.new_zeros(()))
+
+    def select_train_step(self, epoch):
+        """The step of ``epoch`` by the windows of _base_pde_trainer.py:280-289: nef while training.nef.train_from_epoch < epoch
+        <= train_until_epoch, ode likewise.  Where the two windows OVERLAP the nef step runs: this trainer has no dual step, and
+        its own train_epoch in the reference tests the nef window first (nonmaml_pde_trainer.py:380-383).  An epoch in neither
+        window raises ValueError (as :298-299), and so does an ODE epoch on a trainer built without an ODE model.  Every
+        returned step takes (state, batch) with batch = (trajectory (B, T, *grid, O), traj_idx) or (trajectory, _, traj_idx);
+        the nef step fits frame 0 (:311)."""
+        t = self.config.training
+        if t.nef.train_from_epoch < epoch <= t.nef.train_until_epoch:
+            return lambda state, batch, **kw: self.nef_train_step(state, (batch[0][:, 0], batch[-1]), **kw)
+        if t.ode.train_from_epoch < epoch <= t.ode.train_until_epoch:
+            self._need_ode("select_train_step (epoch %d lies in the ode window)" % epoch)
+            return self.ode_train_step
+        raise ValueError("No training step set")
+
+    def train_epoch(self, state, loader, epoch):
+        """One pass over ``loader`` (an iterable of the batches select_train_step describes) with the step the schedule
+        selects; returns (mean loss, state)."""
+        step = self.select_train_step(epoch)
+        total, n = 0.0, 0
+        for batch in loader:
+            loss, state = step(state, batch)
+            total, n = total + float(loss), n + 1
+        return total / max(n, 1), state

@@ -43,28 +43,12 @@ from types import SimpleNamespace
 import torch
 
 from ..inner_loop import _pose, make_masks, inner_loop, decode
-from .trainer_utils.solvers import solve_latent_ode
+from .latent_ode import LatentODEMixin, draw_point_masks, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
-
-
-def _leaves(tree):
-    """Leaves of a nested parameter dict in a fixed (sorted-key) order."""
-    out = []
-    for k in sorted(tree):
-        out += _leaves(tree[k]) if isinstance(tree[k], dict) else [tree[k]]
-    return out
-
-
-def _unflatten(tree, leaves):
-    it = iter(leaves)
-
-    def build(t):
-        return {k: (build(t[k]) if isinstance(t[k], dict) else next(it)) for k in sorted(t)}
-    return build(tree)
 
 
 def _tree_from_tensors(tensors, nef=None):
@@ -208,7 +192,7 @@ class TrainState:
     rng: torch.Generator = field(default_factory=lambda: torch.Generator().manual_seed(0))
 
 
-class MetaSGDPDETrainer:
+class MetaSGDPDETrainer(LatentODEMixin):
     """nef phase of MetaSGDPDETrainer (pde_trainer.py): init_train_state / nef_train_step.
 
     ``config`` carries the reference's field names: optimizer.learning_rate_enf, optimizer.learning_rate_codes,
@@ -365,77 +349,12 @@ class MetaSGDPDETrainer:
                                generator=state.rng, device=coords.device)
         return coords, img, masks
 
-    def rollout(self, ode_params, lat, num_frames, graph=False):
-        """Latents of ``num_frames`` frames from the fitted ones: (B, T, Z, .) each (pde_trainer.py:432-441).
-        graph=True (inference): every derivative evaluation replays one captured hipGraph (PonitaODEGen.graphed)."""
-        cfg = self.config
-        n_ori = self.nef.cross_attn_invariant.num_z_ori_dims
-        z0 = (_pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
-        if graph and hasattr(self.ode_model, "graphed") and not torch.is_grad_enabled():
-            # one capture per (parameter tensors, latent shapes): validation sweeps many batches with the same parameters
-            leaves = _leaves(ode_params)
-            key = (tuple(id(t) for t in leaves), tuple(None if v is None else tuple(v.shape) for v in z0))
-            hit = getattr(self, "_ode_graph", None)
-            if hit is None or hit[0] != key:
-                hit = (key, self.ode_model.graphed(ode_params, z0), leaves)      # (leaves kept alive: ids stay unique)
-                self._ode_graph = hit
-            f = hit[1]
-            return solve_latent_ode(lambda z, t: f(z), z0, 0, num_frames - 1, cfg.node.dt, method=cfg.node.method)
-        if graph and torch.is_grad_enabled() and hasattr(self.ode_model, "graphed_train") and z0[1].is_cuda:
-            # training: one captured (forward, backward) pair per derivative evaluation of the roll-out; ``ode_params`` must
-            # be the persistent leaves of _ode_static_leaves (the graphs keep their addresses)
-            leaves = _leaves(ode_params)
-            n_eval = (num_frames - 1) * (4 if cfg.node.method == "rk4" else 1)
-            key = (tuple(id(t) for t in leaves), tuple(None if v is None else tuple(v.shape) for v in z0), n_eval)
-            cache = self.__dict__.setdefault("_ode_train_graphs", {})
-            if key not in cache:
-                if len(cache) >= 4:
-                    cache.clear()
-                cache[key] = (self.ode_model.graphed_train(ode_params, z0, n_eval), leaves)
-            calls = iter(cache[key][0])
-            return solve_latent_ode(lambda z, t: next(calls)(z), z0, 0, num_frames - 1, cfg.node.dt, method=cfg.node.method)
-        return solve_latent_ode(lambda z, t: self.ode_model.apply(ode_params, z), z0, 0, num_frames - 1, cfg.node.dt,
-                                method=cfg.node.method)
-
-    def _ode_static_leaves(self, ode_params):
-        """The ODE parameters as PERSISTENT leaf tensors that require grad, holding the current values: captured training
-        evaluations read their parameters by address, the optimiser hands out new tensors every step."""
-        cur = _leaves(ode_params)
-        st = getattr(self, "_ode_static", None)
-        if st is None or len(st) != len(cur) or any(a.shape != b.shape or a.device != b.device for a, b in zip(st, cur)):
-            st = [t.detach().clone().requires_grad_(True) for t in cur]
-            self._ode_static = st
-            self.__dict__.pop("_ode_train_graphs", None)
-        else:
-            with torch.no_grad():
-                torch._foreach_copy_(st, [t.detach() for t in cur])
-        return st
-
-    def _ode_train_leaves(self, ode_params):
-        if self.graph_ode_training and _leaves(ode_params)[0].is_cuda:
-            return self._ode_static_leaves(ode_params), True
-        return [t.detach().requires_grad_(True) for t in _leaves(ode_params)], False
-
     def ode_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False):
         """pde_trainer.py:411-481 from the fitted latents on: roll the latents out over the training frames, decode every
         frame (at ``max_num_sampled_points`` random grid points per frame when the grid is larger) and compare.
-        ``trajectory`` (B, T, *grid, O);  ``point_masks`` (T, n_s) long, or None to draw them."""
-        cfg = self.config
-        B, T = trajectory.shape[:2]
-        sol = self.rollout(ode_params, lat, T, graph=graph)
-        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
-        traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
-        N, n_s = self.coords.shape[0], cfg.training.max_num_sampled_points
-        if n_s < N:                                                               # pde_trainer.py:446-471
-            if point_masks is None:
-                point_masks = torch.stack([torch.randperm(N, generator=generator)[:n_s] for _ in range(T)]).to(self.coords.device)
-            xs = self.coords[point_masks][None].expand(B, -1, -1, -1).reshape(B * T, n_s, -1)
-            ys = torch.gather(traj, 2, point_masks[None, :, :, None].expand(B, -1, -1, traj.shape[-1])).reshape(B * T, n_s, -1)
-        else:
-            xs = self.coords[None].expand(B * T, -1, -1)
-            ys = traj.reshape(B * T, N, -1)
-        recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
-        return ((recon - ys) ** 2).mean()
+        ``trajectory`` (B, T, *grid, O);  ``point_masks`` (T, n_s) long, or None to draw them.  The arithmetic (and
+        ``rollout``) is latent_ode.LatentODEMixin's, shared with the auto-decoder trainer."""
+        return self.rollout_loss(nef_params, ode_params, lat, trajectory, point_masks, generator, graph=graph)
 
     def _fitted(self, state, trajectory, masks):
         coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks)
@@ -475,8 +394,8 @@ class MetaSGDPDETrainer:
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
         if point_masks is None and cfg.training.max_num_sampled_points < self.coords.shape[0]:
-            point_masks = torch.stack([torch.randperm(self.coords.shape[0], generator=state.rng)[:cfg.training.max_num_sampled_points]
-                                       for _ in range(trajectory.shape[1])]).to(self.coords.device)
+            point_masks = draw_point_masks(self.coords.shape[0], cfg.training.max_num_sampled_points, trajectory.shape[1],
+                                           state.rng, self.coords.device)
         side = {}
 
         def terminal(weights, lat, keys):
