@@ -19,11 +19,17 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_pair_backward", "enf_pair_backward_ex", "enf_pair_scratch_bytes", "enf_pair_variant", "enf_pair_partition", "enf_backward_weights", "enf_backward_weights_scratch_bytes",
            "enf_backward_all", "enf_backward_all_scratch_bytes", "enf_fit_step", "enf_fit_inputs",
            "enf_mse_value_grad",
+           "enf_workspace_bytes_ex", "enf_fit_step_ex", "enf_mse_value_grad_ex", "enf_mse_scratch_bytes", "enf_pair_backward_ex2",
+           "enf_pair_backward_scratch_bytes", "enf_backward_all_scratch_bytes_ex", "enf_backward_weights_ex",
+           "enf_backward_weights_scratch_bytes_ex",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
            "enf_ode_basis_backward", "enf_relu_mask_bytes", "enf_meta_sgd_update"]
 ENF_NUM_PAIR_TENSORS = 12          # ENF_P_* of include/enf_hip.h
+# deterministic mode (include/enf_hip.h, "Deterministic mode"): one bit for every entry point that takes flags
+ENF_BWD_DETERMINISTIC = ENF_FIT_DETERMINISTIC = ENF_MSE_DETERMINISTIC = 16
+ENF_BWD_QUERY_GRAD = 32            # size queries: a query gradient will be asked for
 (ENF_S_EQ, ENF_S_EV, ENF_S_G1, ENF_S_NH, ENF_S_DA1, ENF_S_DA2, ENF_S_DA3, ENF_S_HEAD0) = range(8)
 
 
@@ -166,6 +172,21 @@ def _bind(path, test_hooks):
     lib.enf_pair_forward.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
     lib.enf_pair_backward.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp]
     lib.enf_pair_backward_ex.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp]
+    cu = ctypes.c_uint
+    lib.enf_workspace_bytes_ex.restype = sz
+    lib.enf_workspace_bytes_ex.argtypes = [dp, cu]
+    lib.enf_fit_step_ex.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, sz, cu, vp]
+    lib.enf_mse_scratch_bytes.restype = sz
+    lib.enf_mse_scratch_bytes.argtypes = [sz, cu]
+    lib.enf_mse_value_grad_ex.argtypes = [vp, vp, sz, ctypes.c_float, vp, vp, vp, sz, cu, vp]
+    lib.enf_pair_backward_scratch_bytes.restype = sz
+    lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]
+    lib.enf_pair_backward_ex2.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]
+    lib.enf_backward_all_scratch_bytes_ex.restype = sz
+    lib.enf_backward_all_scratch_bytes_ex.argtypes = [dp, ci, cu]
+    lib.enf_backward_weights_scratch_bytes_ex.restype = sz
+    lib.enf_backward_weights_scratch_bytes_ex.argtypes = [dp, ci, cu]
+    lib.enf_backward_weights_ex.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]
     if test_hooks:
         for name in ("enf_debug_gemm", "enf_debug_pack", "enf_test_read_wave_sums"):
             getattr(lib, name).restype = ci

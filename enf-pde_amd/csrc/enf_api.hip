@@ -68,6 +68,15 @@ extern "C" size_t enf_workspace_bytes(const EnfDesc* d) {
   return enf_workspace(enf_dims(d)).total;
 }
 
+// the workspace of a call with these flags: ENF_BWD_DETERMINISTIC (= ENF_FIT_DETERMINISTIC) adds K3's partial rows and the fused
+// tail's loss partials behind the plain workspace (enf_launch.h: enf_det_workspace)
+extern "C" size_t enf_workspace_bytes_ex(const EnfDesc* d, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || (flags & ~(ENF_BWD_DETERMINISTIC | ENF_BWD_QUERY_GRAD))) return 0;
+  const EnfDims m = enf_dims(d);
+  const EnfWorkspace W = enf_workspace(m);
+  return (flags & ENF_BWD_DETERMINISTIC) ? enf_det_workspace(m, W).total : W.total;
+}
+
 // Side streams.  Work that can overlap the caller's stream (the z-fold backward's per-latent matrices) runs on ONE side
 // stream per device, created at the first call that needs it on that device.  Fork / join is by events, so the caller's stream order is preserved.  What a forward leaves pending for
 // its backward (ENF_STAGE_PREPARE_BWD) is recorded against the WORKSPACE it was prepared in, with an event of its own:
@@ -193,11 +202,12 @@ extern "C" int enf_backward_latents(const EnfDesc* d, const float* x, int64_t x_
                                  workspace_bytes, 0u, stream);
 }
 
-// the backward pair kernel on the workspace's dybar / delta / dlt, in the z-fold form where the shape resolves to it
-static int pair_bwd_on_workspace(const EnfCall& c, const float* x, int64_t x_bstride, const float* lse) {
+// the backward pair kernel on the workspace's dybar / delta / dlt, in the z-fold form where the shape resolves to it;
+// det: through the workspace's partial rows and the fixed-order reduction (which overwrites dlt) instead of float atomics
+static int pair_bwd_on_workspace(const EnfCall& c, const float* x, int64_t x_bstride, const float* lse, bool det = false) {
   const bool zb = enf_use_zfold_bwd(c.m);
   return enf_launch_pair_bwd(c.m, c.L, c.blob, x, x_bstride, c.F(c.W.lt), lse, c.F(c.W.dybar), c.F(c.W.delta), c.F(c.W.dlt), nullptr,
-                             zb ? c.ws + c.W.wzt : nullptr, zb ? c.F(c.W.wzb) : nullptr, nullptr, c.st);
+                             zb ? c.ws + c.W.wzt : nullptr, zb ? c.F(c.W.wzb) : nullptr, nullptr, c.st, det ? c.F(c.X.part) : nullptr);
 }
 
 extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a,
@@ -205,7 +215,10 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
                                        const float* dout, float* dp, float* da, float* dsigma, void* workspace,
                                        size_t workspace_bytes, unsigned flags, void* stream) {
   EnfCall c;
-  int rc = enf_call(c, d, x && p && a && ybar && lse && dout && dp && da && dsigma, sigma, packed, workspace, workspace_bytes, stream);
+  const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0;
+  const bool known = !(flags & ~(ENF_BWD_REUSE_PROLOGUE | ENF_BWD_REUSE_TAIL | ENF_BWD_REUSE_PREPARED | ENF_BWD_ONLY_PAIR | ENF_BWD_DETERMINISTIC));
+  int rc = enf_call(c, d, known && x && p && a && ybar && lse && dout && dp && da && dsigma, sigma, packed, workspace, workspace_bytes,
+                    stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
@@ -213,8 +226,8 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
   const bool zb = enf_use_zfold_bwd(m);
   if (flags & ENF_BWD_ONLY_PAIR) {      // measurement hook: the pair kernel alone, on what a complete backward left behind
     if ((rc = enf_side_join_pending(st, workspace))) return rc;
-    if (hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
-    return pair_bwd_on_workspace(c, x, x_bstride, lse);
+    if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+    return pair_bwd_on_workspace(c, x, x_bstride, lse, det);
   }
   // the latent table is recomputed (cheap) so the call does not depend on workspace contents, unless the
   // caller vouches that nothing has touched the workspace since the matching enf_forward
@@ -236,9 +249,10 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
   }
   const bool treuse = (flags & ENF_BWD_REUSE_TAIL) && (flags & ENF_BWD_REUSE_PROLOGUE);
   if ((rc = enf_launch_tail(m, c.L, c.blob, ybar, nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), 1, treuse ? 1 : 0, st))) return rc;
-  if (!prepared && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+  // (deterministic mode: the reduction overwrites the gradient table, nothing to zero)
+  if (!prepared && !det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;      // the per-latent matrices (and, if prepared, the zeroed table)
-  if ((rc = pair_bwd_on_workspace(c, x, x_bstride, lse))) return rc;
+  if ((rc = pair_bwd_on_workspace(c, x, x_bstride, lse, det))) return rc;
   return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
 }
 
@@ -250,8 +264,19 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
 extern "C" int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                             const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                             float* dsigma, void* workspace, size_t workspace_bytes, void* stream) {
+  return enf_fit_step_ex(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, 0u,
+                         stream);
+}
+
+// flags = ENF_FIT_DETERMINISTIC: the same kernels; the tail's loss partials and K3's gradient rows go through the workspace's
+// partial buffers and are added in a fixed order (no float atomic, no zero-fill of the gradient table)
+extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                               float* dsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
   EnfCall c;
-  int rc = enf_call(c, d, x && p && a && target && loss && dp && da && dsigma, sigma, packed, workspace, workspace_bytes, stream);
+  const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
+  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma, sigma, packed,
+                    workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
@@ -263,14 +288,16 @@ extern "C" int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride,
                                 zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
     return rc;
   // what the backward pair kernel needs from the latent table alone runs on the side stream beside the tail
-  if ((rc = side_prepare_bwd(zb ? side_stream() : nullptr, c, true)) < 0) return rc;
+  if ((rc = side_prepare_bwd(zb ? side_stream() : nullptr, c, !det)) < 0) return rc;
   if (!rc) {
     if (zb && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
-    if (hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+    if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   }
-  if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
+  if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
+                                 det ? c.F(c.X.loss) : nullptr)))
+    return rc;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
-  if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse)))) return rc;
+  if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse), det))) return rc;
   return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
 }
 
@@ -366,14 +393,37 @@ extern "C" int enf_pair_backward(const EnfDesc* d, const float* x, int64_t x_bst
 extern "C" int enf_pair_backward_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
                                     const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store,
                                     float* dx, void* stream) {
+  return enf_pair_backward_ex2(d, x, x_bstride, lt, packed, lse, dybar, delta, dlt, store, dx, nullptr, 0, 0u, stream);
+}
+
+// scratch of enf_pair_backward_ex2: [K3's partial rows | with ENF_BWD_QUERY_GRAD the per-latent shares of d x]; 0 without the
+// deterministic flag (the stand-alone entry point always runs the latent-split kernel)
+extern "C" size_t enf_pair_backward_scratch_bytes(const EnfDesc* d, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || (flags & ~(ENF_BWD_DETERMINISTIC | ENF_BWD_QUERY_GRAD))) return 0;
+  if (!(flags & ENF_BWD_DETERMINISTIC)) return 0;
+  const EnfDims m = enf_dims(d);
+  return enf_det_part_bytes(m, false) + ((flags & ENF_BWD_QUERY_GRAD) ? enf_det_dx_bytes(m) : 0);
+}
+
+extern "C" int enf_pair_backward_ex2(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
+                                     const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store,
+                                     float* dx, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
   int rc = enf_check_desc(d);
   if (rc) return rc;
-  if (!x || !lt || !packed || !lse || !dybar || !delta || !dlt) return ENF_EINVAL;
+  if ((flags & ~ENF_BWD_DETERMINISTIC) || !x || !lt || !packed || !lse || !dybar || !delta || !dlt) return ENF_EINVAL;
+  const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0;
+  if (det && !scratch) return ENF_EINVAL;
   const EnfDims m = enf_dims(d);
   if (store)
     for (int i = 0; i < ENF_NUM_STORE(m.H); ++i)
       if (!store[i]) return ENF_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  if (det) {
+    const size_t pb = enf_det_part_bytes(m, false);
+    if (scratch_bytes < pb + (dx ? enf_det_dx_bytes(m) : 0)) return ENF_EWORKSPACE;
+    return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, nullptr, nullptr, dx, st,
+                               (float*)scratch, dx ? reinterpret_cast<float*>((char*)scratch + pb) : nullptr);
+  }
   if (hipMemsetAsync(dlt, 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, nullptr, nullptr, dx, st);
 }
@@ -387,15 +437,41 @@ extern "C" size_t enf_backward_weights_scratch_bytes(const EnfDesc* d, int chunk
 extern "C" int enf_backward_weights(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
                                     const float* lse, const float* dybar, const float* delta, float* dlt,
                                     float* const* dpair, float* dx, void* scratch, size_t scratch_bytes, void* stream) {
+  return enf_backward_weights_ex(d, x, x_bstride, lt, packed, lse, dybar, delta, dlt, dpair, dx, scratch, scratch_bytes, 0u, stream);
+}
+
+// scratch with flags: [the plain scratch | K3's partial rows | with ENF_BWD_QUERY_GRAD a chunk's shares of d x]
+static size_t wgrad_scratch_ex(const EnfDims& m, int cb, unsigned flags) {
+  size_t n = enf_wgrad_scratch_bytes(m, cb);
+  if (flags & ENF_BWD_DETERMINISTIC) {
+    n += enf_wgrad_det_part_bytes(m, cb);
+    if (flags & ENF_BWD_QUERY_GRAD) n += enf_align(sizeof(float) * (size_t)cb * m.Z * m.N * m.dx);
+  }
+  return n;
+}
+extern "C" size_t enf_backward_weights_scratch_bytes_ex(const EnfDesc* d, int chunk_signals, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || chunk_signals < 1 || chunk_signals > d->B) return 0;
+  if (flags & ~(ENF_BWD_DETERMINISTIC | ENF_BWD_QUERY_GRAD)) return 0;
+  return wgrad_scratch_ex(enf_dims(d), chunk_signals, flags);
+}
+
+extern "C" int enf_backward_weights_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
+                                       const float* lse, const float* dybar, const float* delta, float* dlt,
+                                       float* const* dpair, float* dx, void* scratch, size_t scratch_bytes, unsigned flags,
+                                       void* stream) {
   int rc = enf_check_desc(d);
   if (rc) return rc;
   if (d->embedding == ENF_EMB_FFN) return ENF_EUNSUPPORTED;       // the ENF_P_* (composed) path: rff only; ffn trains through enf_backward_all
-  if (!x || !lt || !packed || !lse || !dybar || !delta || !dlt || !dpair || !scratch) return ENF_EINVAL;
+  if ((flags & ~ENF_BWD_DETERMINISTIC) || !x || !lt || !packed || !lse || !dybar || !delta || !dlt || !dpair || !scratch) return ENF_EINVAL;
   for (int i = 0; i < ENF_NUM_PAIR_TENSORS; ++i)
     if (i != ENF_P_COEFQ && i != ENF_P_COEFV && !dpair[i]) return ENF_EINVAL;
   const EnfDims m = enf_dims(d);
-  const int cb = enf_wgrad_chunk(m, scratch_bytes, [&](int n) { return enf_wgrad_scratch_bytes(m, n); });
+  const unsigned sflags = flags ? (ENF_BWD_DETERMINISTIC | (dx ? ENF_BWD_QUERY_GRAD : 0u)) : 0u;
+  const int cb = enf_wgrad_chunk(m, scratch_bytes, [&](int n) { return wgrad_scratch_ex(m, n, sflags); });
   if (!cb) return ENF_EWORKSPACE;
-  return enf_launch_wgrad_chunks(m, enf_layout(m), (const char*)packed, cb, x, x_bstride, lt, lse, dybar, delta, dlt, dx, (char*)scratch,
-                                 dpair, (hipStream_t)stream);
+  char* sc = (char*)scratch;
+  float* part = sflags ? reinterpret_cast<float*>(sc + enf_wgrad_scratch_bytes(m, cb)) : nullptr;
+  float* dxpart = sflags && dx ? reinterpret_cast<float*>(sc + enf_wgrad_scratch_bytes(m, cb) + enf_wgrad_det_part_bytes(m, cb)) : nullptr;
+  return enf_launch_wgrad_chunks(m, enf_layout(m), (const char*)packed, cb, x, x_bstride, lt, lse, dybar, delta, dlt, dx, sc, dpair,
+                                 (hipStream_t)stream, part, dxpart);
 }

@@ -20,12 +20,43 @@ inline bool enf_lds_attr(const void* kern, int bytes, EnfAttrBits& done) {
   return true;
 }
 
+// ---- deterministic mode (ENF_BWD_DETERMINISTIC / ENF_FIT_DETERMINISTIC): K3 and the loss kernels store their partial sums in
+// scratch and a fixed-order pass adds them; no result depends on the order in which workgroups finish.
+// K3's query split (grid.y): one workgroup per CU is resident (LDS), so the query tiles are split until all 256 CUs have one.
+// `zfold` = the launch runs the z-fold form (one workgroup per latent; otherwise one wave per latent, 8 per workgroup).
+inline bool enf_pair_bwd_zfold_fits(const EnfDims& m) { return (size_t)m.H * 2 * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu; }
+inline int enf_pair_bwd_nsplit(const EnfDims& m, bool zfold) {
+  const long long wgs = zfold ? (long long)m.B * m.Z : ((long long)m.B * m.Z + 7) / 8;
+  const int ntiles = (m.N + 15) / 16;
+  int ns = 1;
+  while (wgs * ns < 256 && ns * 2 <= ntiles) ns *= 2;
+  return ns;
+}
+// K3's partial rows of d lt, [nsplit][B Z][lt stride] floats, and its per-latent shares of the query gradient, (B, Z, N, dx)
+inline size_t enf_det_part_bytes(const EnfDims& m, bool zfold) {
+  return enf_align(sizeof(float) * (size_t)enf_pair_bwd_nsplit(m, zfold) * m.B * m.Z * enf_lt_stride(m.H, m.D));
+}
+inline size_t enf_det_dx_bytes(const EnfDims& m) { return enf_align(sizeof(float) * (size_t)m.B * m.Z * m.N * m.dx); }
+// the fused tail's loss partials: one per wave (enf_tail.hip)
+int enf_tail_loss_parts(const EnfDims& m);
+// *loss += part[0] + ... + part[n - 1], one workgroup, fixed order (enf_loss.hip)
+int enf_launch_loss_sum(const float* part, int n, float* loss, hipStream_t st);
+struct EnfDetWorkspace { size_t part, loss, total; };      // byte offsets in the workspace, behind EnfWorkspace::total
+inline EnfDetWorkspace enf_det_workspace(const EnfDims& m, const EnfWorkspace& W) {
+  EnfDetWorkspace X;
+  X.part = W.total;
+  X.loss = X.part + enf_det_part_bytes(m, enf_use_zfold_bwd(m) && enf_pair_bwd_zfold_fits(m));
+  X.total = X.loss + enf_align(sizeof(float) * (size_t)enf_tail_loss_parts(m));
+  return X;
+}
+
 // ---- what the entry points that run on a workspace (enf_forward_stages, enf_backward_latents_ex, enf_fit_step,
 // enf_backward_all) derive from their arguments
 struct EnfCall {
   EnfDims m;
   EnfLayout L;
   EnfWorkspace W;
+  EnfDetWorkspace X;    // what a deterministic call carves behind W.total (enf_workspace_bytes_ex)
   hipStream_t st;
   char* ws;             // the workspace (also the key of its pending side-stream work)
   const char* blob;     // the packed weights
@@ -34,7 +65,7 @@ struct EnfCall {
 // Errors in their order of precedence: the descriptor's (enf_check_desc), ENF_EINVAL for a NULL pointer (`pointers_ok` is the
 // entry point's own set; `packed` and `workspace` are everybody's) or for a window without `sigma`, ENF_EWORKSPACE.
 inline int enf_call(EnfCall& c, const EnfDesc* d, bool pointers_ok, const float* sigma, const void* packed, void* workspace,
-                    size_t workspace_bytes, void* stream) {
+                    size_t workspace_bytes, void* stream, bool deterministic = false) {
   const int rc = enf_check_desc(d);
   if (rc) return rc;
   if (!pointers_ok || !packed || !workspace) return ENF_EINVAL;
@@ -42,7 +73,8 @@ inline int enf_call(EnfCall& c, const EnfDesc* d, bool pointers_ok, const float*
   c.m = enf_dims(d);
   c.L = enf_layout(c.m);
   c.W = enf_workspace(c.m);
-  if (workspace_bytes < c.W.total) return ENF_EWORKSPACE;
+  c.X = enf_det_workspace(c.m, c.W);
+  if (workspace_bytes < (deterministic ? c.X.total : c.W.total)) return ENF_EWORKSPACE;
   c.st = (hipStream_t)stream;
   c.ws = (char*)workspace;
   c.blob = (const char*)packed;
@@ -78,10 +110,13 @@ int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, 
                         hipStream_t st);
 
 // ---- K3, the backward pair kernel (enf_pair_bwd.hip): ADDS to `dlt`.  store != NULL: the activation-store form (the K4 operands
-// of ENF_NUM_STORE(H) buffers); otherwise wzt / wzb != NULL selects the z-fold form.  dxq: d x per query, or NULL.
+// of ENF_NUM_STORE(H) buffers); otherwise wzt / wzb != NULL selects the z-fold form.  dxq: d x per query (added to), or NULL.
+// part != NULL: deterministic mode -- the kernel stores its partial rows in `part` (enf_det_part_bytes) and, with dxq, its
+// per-latent query-gradient shares in `dxpart` (enf_det_dx_bytes); two reduction kernels then OVERWRITE `dlt` (splits in
+// order) and `dxq` (latents in order): no float atomic runs, `dlt` need not be zeroed.
 int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride, const float* lt,
                         const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store, const char* wzt,
-                        const float* wzb, float* dxq, hipStream_t st);
+                        const float* wzb, float* dxq, hipStream_t st, float* part = nullptr, float* dxpart = nullptr);
 
 // ---- K4, X^T delta over the activation store (enf_xtd.hip)
 size_t enf_xtd_part_bytes(const EnfDims& m, long long P);       // slice partials of a pass over P rows (256-aligned)
@@ -92,10 +127,12 @@ int enf_launch_xtd(const EnfDims& m, void* const* store, long long P, float* con
 
 // The weight-gradient pass of the per-pair chain, chunked over signals: zero `dlt`, then per chunk of `cb` signals K3 with
 // the activation store and K4.  `scratch` holds enf_wgrad_scratch_bytes(m, cb); x .. dx are the whole batch's (dx may be NULL).
+// part / dxpart: deterministic mode as in enf_launch_pair_bwd, sized for the chunks (enf_wgrad_det_part_bytes, cb signals' dx shares).
 size_t enf_wgrad_scratch_bytes(const EnfDims& m, int cb);
+size_t enf_wgrad_det_part_bytes(const EnfDims& m, int cb);
 int enf_launch_wgrad_chunks(const EnfDims& m, const EnfLayout& L, const char* blob, int cb, const float* x, long long x_bstride,
                             const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt, float* dx,
-                            char* scratch, float* const* dpair, hipStream_t st);
+                            char* scratch, float* const* dpair, hipStream_t st, float* part = nullptr, float* dxpart = nullptr);
 // the largest chunk of signals whose scratch, bytes(cb), fits in `avail` (0: none does); with relu masks, whole groups of
 // mask_signals (signal b replays b % mask_signals)
 template <class Bytes>
@@ -118,5 +155,6 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
                        float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
 // the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
 // backward chain -> d ybar, delta
+// loss_part != NULL (enf_tail_loss_parts(m) floats): every wave stores its partial there and enf_launch_loss_sum adds them to *loss
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target, float gscale,
-                         float* loss, float* dybar, float* delta, float* act, hipStream_t st);
+                         float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part = nullptr);

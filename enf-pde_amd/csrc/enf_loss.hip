@@ -2,7 +2,9 @@
 //   loss = mean((out - target)^2)          (pde_trainer.py:185)
 //   dout = 2 (out - target) / n * grad_scale
 // so that a fit step is forward -> this kernel -> backward, without a framework autograd graph of tiny
-// elementwise kernels in between.  `loss` is accumulated with one atomic per block: the caller zeroes it.
+// elementwise kernels in between.  `loss` is accumulated with one atomic per block: the caller zeroes it.  Deterministic mode
+// (enf_mse_value_grad_ex with ENF_MSE_DETERMINISTIC; the fused tail of enf_fit_step_ex): the blocks / waves STORE their partials in
+// scratch and enf_loss_sum_kernel, one workgroup, adds them in index order -- same inputs, same bits.
 //
 // enf_meta_sgd_update: the meta-SGD update of every latent component in ONE launch (pde_trainer.py:206-219):
 //   out_k = x_k - lr_k (scale g_k),   scale = the batch size (the gradient of a batch-mean loss, :206)
@@ -10,7 +12,8 @@
 #include "enf_launch.h"
 
 __global__ __launch_bounds__(256) void enf_mse_kernel(const float* __restrict__ out, const float* __restrict__ target, size_t n,
-                                                      float inv_n, float gscale, float* __restrict__ dout, float* loss) {
+                                                      float inv_n, float gscale, float* __restrict__ dout, float* loss,
+                                                      float* __restrict__ part) {
   __shared__ float red[4];
   float s = 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -21,17 +24,60 @@ __global__ __launch_bounds__(256) void enf_mse_kernel(const float* __restrict__ 
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv_n);
+  if (threadIdx.x == 0) {
+    const float v = (red[0] + red[1] + red[2] + red[3]) * inv_n;
+    if (part) part[blockIdx.x] = v;
+    else atomicAdd(loss, v);
+  }
+}
+
+// *loss += part[0] + ... + part[n - 1]: thread t adds part[t], part[t + 256], ... in order, then a fixed tree over the 256 threads.
+// The order depends on n alone, never on which workgroup of the producing kernel finished first.
+__global__ __launch_bounds__(256) void enf_loss_sum_kernel(const float* __restrict__ part, int n, float* loss) {
+  __shared__ float red[256];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss += red[0];
+}
+
+int enf_launch_loss_sum(const float* part, int n, float* loss, hipStream_t st) {
+  hipLaunchKernelGGL(enf_loss_sum_kernel, dim3(1), dim3(256), 0, st, part, n, loss);
+  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+}
+
+static size_t mse_blocks(size_t n) {
+  const size_t blocks = (n + 255) / 256;
+  return blocks > 1024 ? 1024 : blocks;
+}
+
+extern "C" size_t enf_mse_scratch_bytes(size_t n, unsigned flags) {
+  if (n == 0 || (flags & ~ENF_MSE_DETERMINISTIC)) return 0;
+  return (flags & ENF_MSE_DETERMINISTIC) ? enf_align(sizeof(float) * mse_blocks(n)) : 0;
+}
+
+extern "C" int enf_mse_value_grad_ex(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
+                                     void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+  if (!out || !target || !loss || n == 0 || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
+  const bool det = (flags & ENF_MSE_DETERMINISTIC) != 0;
+  if (det && !scratch) return ENF_EINVAL;
+  if (det && scratch_bytes < enf_mse_scratch_bytes(n, flags)) return ENF_EWORKSPACE;
+  const size_t blocks = mse_blocks(n);
+  float* part = det ? (float*)scratch : nullptr;
+  hipLaunchKernelGGL(enf_mse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, n, 1.0f / (float)n,
+                     grad_scale, dout, loss, part);
+  if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
+  return det ? enf_launch_loss_sum(part, (int)blocks, loss, (hipStream_t)stream) : ENF_OK;
 }
 
 extern "C" int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
                                   void* stream) {
-  if (!out || !target || !loss || n == 0) return ENF_EINVAL;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(enf_mse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, n, 1.0f / (float)n,
-                     grad_scale, dout, loss);
-  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+  return enf_mse_value_grad_ex(out, target, n, grad_scale, dout, loss, nullptr, 0, 0u, stream);
 }
 
 struct SgdArgs { EnfSgdSegment seg[ENF_SGD_MAX_SEGMENTS]; int nseg; float scale; };

@@ -39,6 +39,10 @@ struct PairBwdArgs {
   int mask_b0;                          // signal index of this launch's b = 0 in the caller's batch (chunked weight-gradient passes)
   int B, N, Z, dx, inv, use_window, nsplit;
   int xcd_remap;                        // ZF: 1-D grid, the nsplit workgroups of a latent adjacent on one XCD (launch_pair_bwd)
+  // deterministic mode (nullptr: the atomics above).  part: [nsplit][B Z][lt stride] -- the epilogue STORES its share of a gradient
+  // row in row (split, b Z + z) instead of adding it to dlt; dxpart (with dxq): (B, Z, N, dx) -- a latent's wave stores its share of
+  // d x there.  Reduction kernels add splits / latents in index order (enf_launch_pair_bwd).
+  float* part; float* dxpart;
 };
 
 // The STORE instantiation's 7 + 4 H buffer pointers, fetched from the kernel-argument segment where they are used (s_load_dwordx2 +
@@ -977,10 +981,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       } else
       pair_invariant_bwd<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, dpose, dwc, nullptr, dxp);
       if (A.dxq && nvalid && active) {          // every latent's wave adds its share to the query's gradient
-        float* o = A.dxq + ((size_t)b * A.N + n) * dx_;
-        atomicAdd(o, dxv[0]);
-        if (dx_ > 1) atomicAdd(o + 1, dxv[1]);
-        if (dx_ > 2) atomicAdd(o + 2, dxv[2]);
+        if (A.dxpart) {                         // deterministic mode: the share goes to (b, z, n, :), summed over z afterwards
+          float* o = A.dxpart + ((size_t)bzc * A.N + n) * dx_;
+          o[0] = dxv[0];
+          if (dx_ > 1) o[1] = dxv[1];
+          if (dx_ > 2) o[2] = dxv[2];
+        } else {
+          float* o = A.dxq + ((size_t)b * A.N + n) * dx_;
+          atomicAdd(o, dxv[0]);
+          if (dx_ > 1) atomicAdd(o + 1, dxv[1]);
+          if (dx_ > 2) atomicAdd(o + 2, dxv[2]);
+        }
       }
     } else if (has_ph && quad == 1) { eacc[9 * 16] += dlat[0]; eacc[10 * 16] += dlat[1]; }
   }
@@ -1007,7 +1018,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   WSTAMP(2);
   // ---- fold the partial sums and add this wave's share into the latent-table gradient
   if (!active) return;   // (unfolded: a wave without a latent; no barrier follows on that path.  z-fold: all eight waves share the latent)
-  float* drow = A.dlt + (size_t)bz * ltstride;
+  // deterministic mode (wave-uniform): the share is STORED in this split's row of the partial buffer -- every (split, latent)
+  // row is written whole (a split without tiles writes zeros), enf_dlt_reduce_kernel adds the splits in order
+  const bool det = A.part != nullptr;
+  float* drow = det ? A.part + ((size_t)split * ((size_t)A.B * A.Z) + bz) * ltstride : A.dlt + (size_t)bz * ltstride;
+  auto put = [&](float* p, float v) { if (det) *p = v; else atomicAdd(p, v); };
   if constexpr (ZF) {
     // the eight waves of a z-fold workgroup share one latent: their partial sums are added through LDS first -- wave w folds
     // slots w, w + 8, ... over the waves (fixed order) and the quads -- so a gradient element gets ONE atomic per workgroup
@@ -1021,7 +1036,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       for (int w = 0; w < NW; ++w) v += lall[(w * NS + sl) * 64];
       v = xquad_sum(v);
       if (quad == 0)
-        atomicAdd(drow + (sl < H * NT ? enf_lt_off_u(H, D) + 16 * sl : enf_lt_off_v0(H, D) + 16 * (sl - H * NT)) + col, v);
+        put(drow + (sl < H * NT ? enf_lt_off_u(H, D) + 16 * sl : enf_lt_off_v0(H, D) + 16 * (sl - H * NT)) + col, v);
     }
   } else
 #pragma unroll
@@ -1030,8 +1045,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     for (int t = 0; t < NT; ++t) {
       const float a = xquad_sum(dU_get(h, t)), c = xquad_sum(dV0_get(h, t));
       if (quad == 0) {
-        atomicAdd(drow + enf_lt_off_u(H, D) + h * D + 16 * t + col, a);
-        atomicAdd(drow + enf_lt_off_v0(H, D) + h * D + 16 * t + col, c);
+        put(drow + enf_lt_off_u(H, D) + h * D + 16 * t + col, a);
+        put(drow + enf_lt_off_v0(H, D) + h * D + 16 * t + col, c);
       }
     }
   float sc[H + 5];
@@ -1045,12 +1060,48 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
     sc[i] = a;
   }
+  if constexpr (ZF) {
+    if (det) {
+      // deterministic mode, z-fold: the eight waves hold partial scalars of ONE latent.  They meet in LDS (the LACC region, free once
+      // every wave has read it above), wave 0 adds them in wave order and stores the row's scalar fields: slots 0 .. H + 4 =
+      // c | pose | wcoef, slots 16 .. 26 = the ext field.  (active is uniform over the workgroup here: the barriers are safe.)
+      __syncthreads();
+      float* fold = reinterpret_cast<float*>(smem + SM::LACC);
+      // (every lane holds the wave's sums: lane i keeps sum i and stores it -- one store per lane, not a run of stores from lane 0,
+      // which hipcc's SLP vectoriser takes as the seed to pack the dpose accumulators of the tile loop, tests/test_host.py)
+      float mine = 0.f;
+#pragma unroll
+      for (int i = 0; i < H + 5; ++i) mine = lane == i ? sc[i] : mine;
+      if (has_ph) {
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+          float a = quad == (k < 9 ? 0 : 1) ? eacc[k * 16] : 0.f;
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+          mine = lane == 16 + k ? a : mine;
+        }
+      }
+      if (lane < 32) fold[wave * 32 + lane] = mine;
+      __syncthreads();
+      if (wave == 0 && (lane < H + 5 || (has_ph && lane >= 16 && lane < 27))) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v += fold[w * 32 + lane];
+        const int off = lane < H ? enf_lt_off_c(H, D) + lane
+                        : lane < H + 4 ? enf_lt_off_pose(H, D) + lane - H
+                        : lane == H + 4 ? enf_lt_off_wcoef(H, D) : enf_lt_off_ext(H, D) + lane - 16;
+        drow[off] = v;
+      }
+      WSTAMP(3);
+      return;
+    }
+  }
   if (lane == 0) {
 #pragma unroll
-    for (int h = 0; h < H; ++h) atomicAdd(drow + enf_lt_off_c(H, D) + h, sc[h]);
+    for (int h = 0; h < H; ++h) put(drow + enf_lt_off_c(H, D) + h, sc[h]);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) atomicAdd(drow + enf_lt_off_pose(H, D) + i, sc[H + i]);
-    atomicAdd(drow + enf_lt_off_wcoef(H, D), sc[H + 4]);
+    for (int i = 0; i < 4; ++i) put(drow + enf_lt_off_pose(H, D) + i, sc[H + i]);
+    put(drow + enf_lt_off_wcoef(H, D), sc[H + 4]);
   }
   if (has_ph) {            // d R (9) | d(latent-only invariants) (2) -> the gradient row's ext field
 #pragma unroll
@@ -1058,10 +1109,39 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       float a = quad == (k < 9 ? 0 : 1) ? eacc[k * 16] : 0.f;
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-      if (lane == 0) atomicAdd(drow + enf_lt_off_ext(H, D) + k, a);
+      if (lane == 0) put(drow + enf_lt_off_ext(H, D) + k, a);
     }
   }
   WSTAMP(3);
+}
+
+// Deterministic mode, d lt: dlt[r][e] = part[0][r][e] + ... + part[nsplit - 1][r][e] in that order for the fields K3's epilogue
+// writes (u, v0, pose, wcoef, c, and with `ext` the 11 ext slots), zero elsewhere.  OVERWRITES dlt: no zero-fill is needed.
+__global__ __launch_bounds__(256) void enf_dlt_reduce_kernel(const float* __restrict__ part, int nsplit, long long rows, int H, int D,
+                                                            int ext, float* __restrict__ dlt) {
+  const int stride = enf_lt_stride(H, D);
+  const long long total = rows * stride, e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int c = (int)(e % stride), base = 2 * H * D;
+  const bool written = c < base + 5 || (c >= enf_lt_off_c(H, D) && c < enf_lt_off_c(H, D) + H) ||
+                       (ext && c >= enf_lt_off_ext(H, D) && c < enf_lt_off_ext(H, D) + 11);
+  float s = 0.f;
+  if (written) {
+    s = part[e];
+    for (int k = 1; k < nsplit; ++k) s += part[(size_t)k * total + e];
+  }
+  dlt[e] = s;
+}
+// Deterministic mode, d x: dx[b][n][:] = dxpart[b][0][n][:] + ... + dxpart[b][Z - 1][n][:] in that order.  OVERWRITES dx.
+__global__ __launch_bounds__(256) void enf_dxq_reduce_kernel(const float* __restrict__ dxpart, int B, int Z, int N, int dx,
+                                                            float* __restrict__ out) {
+  const long long per = (long long)N * dx, e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= per * B) return;
+  const long long b = e / per, r = e - b * per;
+  const float* src = dxpart + (size_t)b * Z * per + r;
+  float s = src[0];
+  for (int z = 1; z < Z; ++z) s += src[(size_t)z * per];
+  out[e] = s;
 }
 
 template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1, bool FFN = false>
@@ -1078,21 +1158,48 @@ static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
 
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor); read by the STORE instantiation only
 
+static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
+                           const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
+                           void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st, float* part,
+                           float* dxpart, int* nsplit);
+
 int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
                         const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
-                        void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st) {
+                        void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st, float* part,
+                        float* dxpart) {
+  if (part && dxq && !dxpart) return ENF_EINVAL;
+  int ns = 1;
+  if (int rc = pair_bwd_kernel(m, L, blob, x, x_bstride, lt, lse, dybar, delta, dlt, store, wzt, wzb, dxq, st, part,
+                               part ? dxpart : nullptr, &ns))
+    return rc;
+  if (!part) return 0;
+  // deterministic mode: the fixed-order passes over what the kernel stored
+  const long long rows = (long long)m.B * m.Z, nl = rows * enf_lt_stride(m.H, m.D);
+  hipLaunchKernelGGL(enf_dlt_reduce_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, part, ns, rows, m.H, m.D,
+                     (int)enf_inv_has_phase(m.inv), dlt);
+  if (dxq) {
+    const long long nx = (long long)m.B * m.N * m.dx;
+    hipLaunchKernelGGL(enf_dxq_reduce_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, dxpart, m.B, m.Z, m.N, m.dx, dxq);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+
+static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
+                           const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
+                           void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st, float* part,
+                           float* dxpart, int* nsplit) {
   PairBwdArgs A;
-  A.dxq = dxq;
+  A.dxq = dxq; A.part = part; A.dxpart = dxpart;
   A.masks = store && m.mask_mode == ENF_MASK_READ ? m.masks : nullptr; A.mask_B = m.mask_B; A.mask_b0 = m.mask_b0;
-  const bool zf = !store && wzt && wzb && (size_t)m.H * 2 * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu;
+  const bool zf = !store && wzt && wzb && enf_pair_bwd_zfold_fits(m);
   A.wzt = wzt; A.wzb = wzb; A.inv_d = 1.0f / (float)m.Dt;
   A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.lse = lse; A.dybar = dybar; A.delta = delta;
   A.dlt = dlt; A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
   // one workgroup per CU is resident (LDS): split the query tiles over grid.y until all 256 CUs have one
-  const int wgs = zf ? m.B * m.Z : (m.B * m.Z + NWAVES - 1) / NWAVES, ntiles = (m.N + 15) / 16;
-  int ns = 1;
-  while (wgs * ns < 256 && ns * 2 <= ntiles) ns *= 2;
-  A.nsplit = ns;
+  static_assert(NWAVES == 8, "enf_pair_bwd_nsplit (enf_launch.h) counts 8 latents per latent-split workgroup");
+  const int wgs = zf ? m.B * m.Z : (m.B * m.Z + NWAVES - 1) / NWAVES;
+  const int ns = enf_pair_bwd_nsplit(m, zf);
+  A.nsplit = ns; *nsplit = ns;
   A.xcd_remap = zf && ns > 1 && wgs % 8 == 0;
   if (store)
     for (int i = 0; i < ENF_NUM_STORE(m.H); ++i) A.store[i] = store[i];

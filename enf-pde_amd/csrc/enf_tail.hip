@@ -21,6 +21,7 @@ struct TailArgs {
   const float* dout;     // backward
   float* dybar; float* delta; float* act;   // backward outputs + scratch (B*N x (2HD + 2D + 2))
   const float* target; float* loss; float gscale, inv_n;     // fused loss (LOSS): d out = 2 (out - target) inv_n gscale, *loss += mean sq. error
+  float* loss_part;      // LOSS, deterministic mode: wave w of workgroup g stores its partial in loss_part[g * NWAVES + w] (nullptr: atomic)
   float* tdel;           // weight-gradient backward (WG): per query d a_B | d a_F1 | d a_O0 | d a_O2 (2HD + 2D floats); the layer INPUTS
                          // n^ | gelu(a_F1) | gelu(a_O0) | gelu(a_O2) replace the pre-activations in `act` (enf_train.hip forms X^T delta)
   int ybar_half;         // forward only (ENF_STAGE_YBAR_HALF): `ybar` holds bf16 rows
@@ -295,7 +296,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
       }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-    if (lane == 0) atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
+    if (lane == 0) {
+      if (A.loss_part) A.loss_part[blockIdx.x * NWAVES + wave] = se * A.inv_n;     // deterministic mode: summed in index order afterwards
+      else atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
+    }
   } else {
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -455,7 +459,7 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
                        const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
-  A.target = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f;
+  A.target = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr;
   A.tdel = tdel;
   A.ybar_half = (!bwd && (opt & 2) && m.bf16) ? 1 : 0;
   opt &= 1;
@@ -472,10 +476,24 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
   return ENF_EUNSUPPORTED;
 }
 
+int enf_tail_loss_parts(const EnfDims& m) {
+  return (int)(((long long)m.B * m.N + 16 * NWAVES - 1) / (16 * NWAVES)) * NWAVES;
+}
+
+static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
+                            float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part);
+
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                         float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st) {
+                         float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
+  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, gscale, loss, dybar, delta, act, st, loss_part)) return rc;
+  return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
+}
+
+static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
+                            float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
+  A.loss_part = loss_part;
   A.ybar = ybar; A.blob = blob; A.L = L; A.out = nullptr; A.dout = nullptr; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = nullptr;
   A.ybar_half = 0;
   A.target = target; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);

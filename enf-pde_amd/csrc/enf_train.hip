@@ -203,6 +203,8 @@ struct TrainScratch {
   size_t dpair;     // the ten per-pair gradients, ENF_P_* order, contiguous
   size_t fold;      // folded-matrix gradients and temporaries
   size_t part;      // X^T Y slice partials
+  size_t detpart;   // ENF_BWD_DETERMINISTIC: K3's partial rows of d lt for a chunk
+  size_t detdx;     // ... with ENF_BWD_QUERY_GRAD: a chunk's per-latent shares of d x
   size_t total;
   size_t part_floats;
 };
@@ -215,7 +217,7 @@ inline size_t fold_floats(const EnfDims& m) {
   // dWB HDxHD | dbB HD | dwf1 HDxHD | dbF1 HD | T HDxHD | dT HDxHD | dMU H DxD | dcvec HD | dmxw DxD | dmxb D
   return 4 * HD * HD + 3 * HD + H * D * D + D * D + D + 256;
 }
-TrainScratch train_scratch(const EnfDims& m, int cb) {
+TrainScratch train_scratch(const EnfDims& m, int cb, unsigned flags = 0u) {
   TrainScratch s;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o = enf_align(o + bytes); return r; };
@@ -226,6 +228,9 @@ TrainScratch train_scratch(const EnfDims& m, int cb) {
   s.fold = take(sizeof(float) * fold_floats(m));
   s.part_floats = (size_t)64 * m.HD * m.HD;
   s.part = take(sizeof(float) * s.part_floats);
+  const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0;
+  s.detpart = take(det ? enf_wgrad_det_part_bytes(m, cb) : 0);
+  s.detdx = take(det && (flags & ENF_BWD_QUERY_GRAD) ? sizeof(float) * (size_t)cb * m.Z * m.N * m.dx : 0);
   s.total = o;
   return s;
 }
@@ -236,6 +241,12 @@ extern "C" size_t enf_backward_all_scratch_bytes(const EnfDesc* d, int chunk_sig
   return train_scratch(enf_dims(d), chunk_signals).total;
 }
 
+extern "C" size_t enf_backward_all_scratch_bytes_ex(const EnfDesc* d, int chunk_signals, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || chunk_signals < 1 || chunk_signals > d->B) return 0;
+  if (flags & ~(ENF_BWD_DETERMINISTIC | ENF_BWD_QUERY_GRAD)) return 0;
+  return train_scratch(enf_dims(d), chunk_signals, flags).total;
+}
+
 extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                 const float* const* T, const void* packed, const float* ybar, const float* lse, const float* dout,
                                 float* dp, float* da, float* dsigma, float* const* dW, float* dx, void* workspace,
@@ -243,6 +254,9 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   // every pointer the call reads through, the tensor tables' entries included (d is looked at only if it is there: what is
   // wrong with it is enf_call's to report, first)
   bool ptrs = x && p && a && T && ybar && lse && dout && dp && da && dsigma && dW && scratch;
+  ptrs = ptrs && !(flags & ~(ENF_BWD_REUSE_PROLOGUE | ENF_BWD_REUSE_TAIL | ENF_BWD_REUSE_PREPARED | ENF_BWD_DETERMINISTIC));
+  // ENF_BWD_DETERMINISTIC: the partials come from `scratch` (enf_backward_all_scratch_bytes_ex); with `dx` also the query-gradient shares
+  const unsigned sflags = (flags & ENF_BWD_DETERMINISTIC) ? (ENF_BWD_DETERMINISTIC | (dx ? ENF_BWD_QUERY_GRAD : 0u)) : 0u;
   for (int i = 0; ptrs && d && i < ENF_NUM_TENSORS; ++i) {
     const bool unused = d->embedding == ENF_EMB_FFN && (i == ENF_W_RQ_W1 || i == ENF_W_RV_W1);        // (include/enf_hip.h, ENF_EMB_FFN)
     ptrs = unused || (T[i] && (dW[i] || i == ENF_W_RQ_COEF || i == ENF_W_RV_COEF));
@@ -255,9 +269,9 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   const EnfLayout& L = c.L;
   const EnfWorkspace& W = c.W;
   // the largest chunk of signals whose activation store fits
-  const int cb = enf_wgrad_chunk(m, scratch_bytes, [&](int n) { return train_scratch(m, n).total; });
+  const int cb = enf_wgrad_chunk(m, scratch_bytes, [&](int n) { return train_scratch(m, n, sflags).total; });
   if (!cb) return ENF_EWORKSPACE;
-  const TrainScratch S = train_scratch(m, cb);
+  const TrainScratch S = train_scratch(m, cb, sflags);
   hipStream_t st = c.st;
   char* sc = (char*)scratch;
   auto F = [&](size_t off) { return c.F(off); };
@@ -284,7 +298,8 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
     for (int i = 0; i < 10; ++i) { dpair[i] = q; q += sz[i]; }
     dpair[ENF_P_COEFQ] = dpair[ENF_P_COEFV] = nullptr;
   }
-  if ((rc = enf_launch_wgrad_chunks(m, L, blob, cb, x, x_bstride, F(W.lt), lse, F(W.dybar), F(W.delta), F(W.dlt), dx, sc + S.pair, dpair, st)))
+  if ((rc = enf_launch_wgrad_chunks(m, L, blob, cb, x, x_bstride, F(W.lt), lse, F(W.dybar), F(W.delta), F(W.dlt), dx, sc + S.pair, dpair, st,
+                                    sflags ? G(S.detpart) : nullptr, sflags && dx ? G(S.detdx) : nullptr)))
     return rc;
 
   // ---- 3. prologue backward: d p, d a, d sigma + the operand rows of its weight gradients

@@ -319,10 +319,25 @@ size_t enf_wgrad_scratch_bytes(const EnfDims& m, int cb) {
   return (size_t)ENF_NUM_STORE(m.H) * wgrad_store_bytes(m, cb) + enf_xtd_part_bytes(m, (long long)cb * m.Z * m.N);
 }
 
+// deterministic mode: the partial rows of the largest K3 launch of the pass (a full chunk, or the shorter last one: fewer signals
+// can mean more query splits)
+size_t enf_wgrad_det_part_bytes(const EnfDims& m, int cb) {
+  EnfDims mc = m;
+  mc.B = cb;
+  size_t n = enf_det_part_bytes(mc, false);
+  if (m.B % cb) {
+    mc.B = m.B % cb;
+    const size_t r = enf_det_part_bytes(mc, false);
+    if (r > n) n = r;
+  }
+  return n;
+}
+
 int enf_launch_wgrad_chunks(const EnfDims& m, const EnfLayout& L, const char* blob, int cb, const float* x, long long x_bstride,
                             const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt, float* dx,
-                            char* scratch, float* const* dpair, hipStream_t st) {
-  if (hipMemsetAsync(dlt, 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+                            char* scratch, float* const* dpair, hipStream_t st, float* detpart, float* dxpart) {
+  // (deterministic mode overwrites every chunk's rows of d lt: no zero-fill)
+  if (!detpart && hipMemsetAsync(dlt, 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   const int stride = enf_lt_stride(m.H, m.D);
   void* store[ENF_NUM_STORE(4)];
   const size_t sb = wgrad_store_bytes(m, cb);
@@ -335,7 +350,7 @@ int enf_launch_wgrad_chunks(const EnfDims& m, const EnfLayout& L, const char* bl
     const size_t qo = (size_t)b0 * m.N;
     int rc = enf_launch_pair_bwd(mc, L, blob, x + (size_t)b0 * x_bstride, x_bstride, lt + (size_t)b0 * m.Z * stride, lse + qo * m.H,
                                  dybar + qo * m.HD, delta + qo * m.H, dlt + (size_t)b0 * m.Z * stride, store, nullptr, nullptr,
-                                 dx ? dx + qo * m.dx : nullptr, st);
+                                 dx ? dx + qo * m.dx : nullptr, st, detpart, dxpart);
     if (rc) return rc;
     if ((rc = enf_launch_xtd(mc, store, (long long)nb * m.Z * m.N, dpair, part, b0 > 0, st))) return rc;
   }

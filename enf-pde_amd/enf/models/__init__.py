@@ -153,6 +153,7 @@ class _EnfFunction(torch.autograd.Function):
         reuse = 1 if model._ws_tag(ws) == ctx.ws_tag else 0          # ENF_BWD_REUSE_PROLOGUE
         if reuse and ctx.tail_saved:
             reuse |= 2                                               # ENF_BWD_REUSE_TAIL
+        reuse |= model._det_flag()                                   # ENF_BWD_DETERMINISTIC
         _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(p_), _ptr(a_), _ptr(sigma),
                                                _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da),
                                                _ptr(dsig), _ptr(ws), ws.numel(), reuse, st)
@@ -165,13 +166,18 @@ class EquivariantCrossAttentionNeF:
 
     Args mirror the Flax module's fields (NEF:85-96); ``precision`` ("bf16" | "f32") selects
     the MFMA arithmetic of the per-pair contractions (ENF_PREC_*).
+
+    ``deterministic``: True = every native call of this model takes its deterministic form (include/enf_hip.h, "Deterministic
+    mode": partial sums through scratch and fixed-order reductions instead of float atomics -- equal bits for equal inputs,
+    shapes and kernel variants); False = the default (atomic) path; None = follow
+    ``torch.are_deterministic_algorithms_enabled()`` at the time of each call.
     """
 
     default_pair_variants = ("auto", "auto")
 
     def __init__(self, num_hidden, num_heads, num_layers, num_out, latent_dim, cross_attn_invariant,
                  self_attn_invariant=None, embedding_type="rff", embedding_freq_multiplier=(0.05, 0.1),
-                 condition_value_transform=True, use_gaussian_window=True, precision="bf16"):
+                 condition_value_transform=True, use_gaussian_window=True, precision="bf16", deterministic=None):
         if not isinstance(cross_attn_invariant, BaseInvariant):
             raise TypeError("cross_attn_invariant must come from enf.steerable_attention.invariant.get_ca_invariant")
         if embedding_type not in ("rff", "ffn"):
@@ -193,6 +199,9 @@ class EquivariantCrossAttentionNeF:
             raise NotImplementedError(f"embedding type 'ffn' is built for an even num_hidden, not {num_hidden}")
         if precision not in _lib.PREC:
             raise ValueError(f"unknown precision {precision!r}")
+        if deterministic not in (None, True, False):
+            raise ValueError("deterministic must be True, False or None (= follow torch.use_deterministic_algorithms)")
+        self.deterministic = deterministic
         self.num_hidden, self.num_heads, self.num_layers = int(num_hidden), int(num_heads), int(num_layers)
         self._Dp = _pad.padded_width(self.num_hidden)      # width of the kernels that run it (zero-padded if wider)
         self._Hp = _pad.padded_heads(self.num_heads)       # heads of the kernels that run it (3 -> 4, one zero head)
@@ -231,6 +240,18 @@ class EquivariantCrossAttentionNeF:
         m._pack_cache, m._ws_cache, m._ws_gen, m._ws_tags, m._masks, m._lt_held = {}, {}, 0, {}, None, {}
         return m
 
+    # ------------------------------------------------------------------ deterministic mode
+    def is_deterministic(self):
+        """Whether a native call made now takes its deterministic form: the constructor's ``deterministic``, or torch's global
+        switch when that is None."""
+        if self.deterministic is None:
+            return bool(torch.are_deterministic_algorithms_enabled())
+        return bool(self.deterministic)
+
+    def _det_flag(self):
+        """ENF_BWD_DETERMINISTIC / ENF_FIT_DETERMINISTIC / ENF_MSE_DETERMINISTIC (one bit) or 0."""
+        return _lib.ENF_BWD_DETERMINISTIC if self.is_deterministic() else 0
+
     # ------------------------------------------------------------------ descriptors / buffers
     def _desc(self, B, N, Z, masks=None):
         """The call descriptor; ``masks`` = a (buffer, mode, signals) triple for calls whose pair kernels take relu masks."""
@@ -245,7 +266,9 @@ class EquivariantCrossAttentionNeF:
     def _workspace(self, desc, device):
         # one cached scratch buffer per (shape, stream); the autograd graph never keeps it alive
         lib = _lib.load()
-        nbytes = lib.enf_workspace_bytes(ctypes.byref(desc))
+        # (sized for the deterministic form while the mode is on: its partial buffers sit behind the plain workspace)
+        det = self._det_flag()
+        nbytes = lib.enf_workspace_bytes_ex(ctypes.byref(desc), det) if det else lib.enf_workspace_bytes(ctypes.byref(desc))
         if nbytes == 0:
             _lib.check(lib.enf_check_desc(ctypes.byref(desc)))
         key = (str(device), torch.cuda.current_stream(device).cuda_stream)
@@ -521,6 +544,7 @@ class EquivariantCrossAttentionNeF:
         loss = loss_out if loss_out is not None else torch.zeros(1, device=dev, dtype=torch.float32)
         dp, da = torch.empty_like(p_), torch.empty_like(a_)
         dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
+        det = self._det_flag()
         if not FUSED_FIT_STEP:       # the same step as three library calls (cross-check in the tests, A/B in scripts/)
             HD = self._Hp * self._Dp
             out = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32)
@@ -529,14 +553,18 @@ class EquivariantCrossAttentionNeF:
             _lib.launch(dev, lib.enf_forward_stages, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed),
                         _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(), 15 | 16 | 32, st)       # + TAIL_SAVE + PREPARE_BWD
             dout = torch.empty_like(out)
-            _lib.launch(dev, lib.enf_mse_value_grad, _ptr(out), _ptr(tgt), out.numel(), float(grad_scale), _ptr(dout), _ptr(loss), st)
+            nmse = int(lib.enf_mse_scratch_bytes(out.numel(), det))
+            mse_scr = torch.empty(nmse, device=dev, dtype=torch.uint8) if nmse else None
+            _lib.launch(dev, lib.enf_mse_value_grad_ex, _ptr(out), _ptr(tgt), out.numel(), float(grad_scale), _ptr(dout), _ptr(loss),
+                        _ptr(mse_scr), nmse, det, st)
             _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_),
-                        _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), 1 | 2 | 4, st)
+                        _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(),
+                        1 | 2 | 4 | det, st)
             self._ws_touch(ws)
             return loss, dp, da, (dsig if sigma is not None else None)
         # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
         # the loss and its gradient formed in registers, pair backward, prologue backward
-        _lib.launch(dev, lib.enf_fit_step, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), st)
+        _lib.launch(dev, lib.enf_fit_step_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), det, st)
         self._ws_touch(ws)
         return loss, dp, da, (dsig if sigma is not None else None)

@@ -163,14 +163,20 @@ class _PairFunction(torch.autograd.Function):
         dlt = torch.empty_like(lt)
         stride = lt.shape[1]
         # gradient w.r.t. the query coordinates (self-attention blocks: the queries are the latent poses), on request
-        dxq = torch.zeros((B, N, ctx.x_shape[-1]), device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        # deterministic mode (the model's setting at the time of the backward): partials in scratch, fixed-order sums; d x is
+        # then overwritten by the library, not accumulated into
+        det = model._det_flag()
+        dxq = (torch.empty if det else torch.zeros)((B, N, ctx.x_shape[-1]), device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        sflags = det | (_lib.ENF_BWD_QUERY_GRAD if det and dxq is not None else 0)
 
         def dx_out():
             return dxq          # (B, N, dx) also for a broadcast grid: autograd sums over the expand itself
         if not ctx.need_w:
             desc = model._desc(B, N, Z)
-            _lib.launch(dev, lib.enf_pair_backward_ex, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(lt), _ptr(blob), _ptr(lse),
-                                                _ptr(dybar), _ptr(delta), _ptr(dlt), None, _ptr(dxq), st)
+            nscr = int(lib.enf_pair_backward_scratch_bytes(ctypes.byref(desc), sflags))
+            scratch = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr else None
+            _lib.launch(dev, lib.enf_pair_backward_ex2, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(lt), _ptr(blob), _ptr(lse),
+                        _ptr(dybar), _ptr(delta), _ptr(dlt), None, _ptr(dxq), _ptr(scratch), nscr, det, st)
             return (dx_out(), dlt, None) + (None,) * _lib.ENF_NUM_PAIR_TENSORS
 
         # weight gradients: ONE library call (include/enf_hip.h: enf_backward_weights) -- K3 writes the layer inputs / deltas
@@ -178,15 +184,15 @@ class _PairFunction(torch.autograd.Function):
         desc = model._desc(B, N, Z, masks=ctx.masks) if ctx.masks is not None and ctx.masks[1] == "read" else model._desc(B, N, Z)
         group = ctx.masks[2] if ctx.masks is not None and ctx.masks[1] == "read" else 1
         cb = B
-        while cb > group and int(lib.enf_backward_weights_scratch_bytes(ctypes.byref(desc), cb)) > STORE_BUDGET_BYTES:
+        while cb > group and int(lib.enf_backward_weights_scratch_bytes_ex(ctypes.byref(desc), cb, sflags)) > STORE_BUDGET_BYTES:
             cb = max(group, (cb - 1) // group * group)
-        scratch = torch.empty(int(lib.enf_backward_weights_scratch_bytes(ctypes.byref(desc), cb)), device=dev, dtype=torch.uint8)
+        scratch = torch.empty(int(lib.enf_backward_weights_scratch_bytes_ex(ctypes.byref(desc), cb, sflags)), device=dev, dtype=torch.uint8)
         f32 = dict(device=dev, dtype=torch.float32)
         shapes = [(D, D), (D,), (D, D), (D,), (D, D), (D,), (D, 2 * HD), (2 * HD,), (D, D), (D,)]      # ENF_P_AQ1 .. ENF_P_BM
         grads = [torch.empty(sh, **f32) for sh in shapes]
         arr = (ctypes.c_void_p * _lib.ENF_NUM_PAIR_TENSORS)(*([g.data_ptr() for g in grads] + [None, None]))
-        _lib.launch(dev, lib.enf_backward_weights, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(lt), _ptr(blob), _ptr(lse),
-                    _ptr(dybar), _ptr(delta), _ptr(dlt), arr, _ptr(dxq), _ptr(scratch), scratch.numel(), st)
+        _lib.launch(dev, lib.enf_backward_weights_ex, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(lt), _ptr(blob), _ptr(lse),
+                    _ptr(dybar), _ptr(delta), _ptr(dlt), arr, _ptr(dxq), _ptr(scratch), scratch.numel(), det, st)
         assert dlt.shape[1] == stride
         # ENF_P_* order: AQ1,BQ1, AV1,BV1, AF,BF, AGB,BGB, AM,BM, COEFQ,COEFV (frozen: RFF:87-90)
         return (dx_out(), dlt, None, *grads, None, None)
@@ -362,9 +368,11 @@ class _TrainAllFunction(torch.autograd.Function):
         desc = model._desc(B, N, Z, masks=ctx.masks) if read else model._desc(B, N, Z)
         group = ctx.masks[2] if read else 1
         cb = B
-        while cb > group and int(lib.enf_backward_all_scratch_bytes(ctypes.byref(desc), cb)) > STORE_BUDGET_BYTES:
+        det = model._det_flag()              # deterministic mode: K3's partials come from the scratch, fixed-order sums
+        sflags = det | (_lib.ENF_BWD_QUERY_GRAD if det and ctx.needs_input_grad[0] else 0)
+        while cb > group and int(lib.enf_backward_all_scratch_bytes_ex(ctypes.byref(desc), cb, sflags)) > STORE_BUDGET_BYTES:
             cb = max(group, (cb - 1) // group * group)
-        nscr = int(lib.enf_backward_all_scratch_bytes(ctypes.byref(desc), cb))
+        nscr = int(lib.enf_backward_all_scratch_bytes_ex(ctypes.byref(desc), cb, sflags))
         scratch = torch.empty(nscr, device=dev, dtype=torch.uint8)
         f32 = dict(device=dev, dtype=torch.float32)
         ffn = model.embedding_type == "ffn"
@@ -374,9 +382,9 @@ class _TrainAllFunction(torch.autograd.Function):
         arrG = (ctypes.c_void_p * len(grads))(*[None if g is None else g.data_ptr() for g in grads])
         dp, da = torch.empty_like(p_), torch.empty_like(a_)
         dsig = torch.empty((B, Z, 1), **f32)
-        dxq = torch.zeros((B, N, ctx.x_shape[-1]), **f32) if ctx.needs_input_grad[0] else None
+        dxq = (torch.empty if det else torch.zeros)((B, N, ctx.x_shape[-1]), **f32) if ctx.needs_input_grad[0] else None     # (det: overwritten)
         ws = model._workspace(desc, dev)
-        flags = 3 if model._ws_tag(ws) == ctx.ws_tag else 0       # latent table + tail stash still the forward's
+        flags = (3 if model._ws_tag(ws) == ctx.ws_tag else 0) | det       # latent table + tail stash still the forward's
         _lib.launch(dev, lib.enf_backward_all, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(p_), _ptr(a_), _ptr(sigma), arrT,
                     _ptr(blob), _ptr(ybar), _ptr(lse), _ptr(dout.contiguous().float()), _ptr(dp), _ptr(da), _ptr(dsig), arrG, _ptr(dxq),
                     _ptr(ws), ws.numel(), _ptr(scratch), nscr, flags, st)
@@ -393,6 +401,7 @@ class _SelfAttnView:
         self.num_hidden, self.num_heads = model.num_hidden, model.num_heads
         self._x_arg = model._x_arg
         self.pair_variants, self.default_pair_variants = model.pair_variants, model.default_pair_variants
+        self._det_flag = model._det_flag
 
     def _desc(self, B, N, Z, masks=None):
         m, inv = self._m, self._m.self_attn_invariant

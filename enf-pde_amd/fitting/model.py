@@ -20,7 +20,9 @@ def get_model_pde(cfg, precision="bf16"):
         embedding_type=cfg.nef.embedding_type,
         embedding_freq_multiplier=[cfg.nef.embedding_freq_multiplier_invariant, cfg.nef.embedding_freq_multiplier_value],
         condition_value_transform=cfg.nef.condition_value_transform,
-        use_gaussian_window=cfg.nef.use_gaussian_window, precision=precision)
+        use_gaussian_window=cfg.nef.use_gaussian_window, precision=precision,
+        # (not a reference key) True / False / None as EquivariantCrossAttentionNeF's ``deterministic``; absent = None
+        deterministic=getattr(cfg.nef, "deterministic", None))
     node = getattr(cfg, "node", None)
     if node is None:
         return nef, None

@@ -155,6 +155,12 @@ int enf_pack_weights(const EnfDesc* d, const float* const* tensors, void* packed
 
 /* scratch the forward / backward need (latent table, per-query partials) */
 size_t enf_workspace_bytes(const EnfDesc* d);
+/* The same for a call that carries `flags`: 0 gives enf_workspace_bytes(d); ENF_BWD_DETERMINISTIC (= ENF_FIT_DETERMINISTIC, see
+ * "Deterministic mode" below) adds the partial-sum buffers of enf_backward_latents_ex / enf_fit_step_ex (equal to the plain size
+ * plus one gradient table where the backward pair kernel does not split the queries).  ENF_BWD_QUERY_GRAD is accepted so that one
+ * flag word serves every size query; it adds nothing here (the query gradient's partials come from enf_backward_all's / enf_pair_backward_ex2's
+ * scratch).  0 for a bad descriptor or an unknown flag bit. */
+size_t enf_workspace_bytes_ex(const EnfDesc* d, unsigned flags);
 
 /* Replaces nef.apply (NEF:204-235).  `ybar` (B,N,H*D) and `lse` (B,N,H) are optional
  * outputs (may be NULL): the attention-weighted value sum and the softmax log-sum-exp,
@@ -208,6 +214,21 @@ int enf_backward_latents(const EnfDesc* d, const float* x, int64_t x_bstride, co
  * backward pair kernel (preceded by the zero-fill of the 2 MB gradient table it accumulates into) on the workspace a
  * complete enf_backward_latents[_ex] call with the same arguments has just left; dp / da / dsigma are not written. */
 #define ENF_BWD_ONLY_PAIR 8u
+/* Deterministic mode.  By default the backward pair kernel adds its shares of a latent-table gradient row -- one per query split,
+ * `nsplit` = 1, 2, 4, ... of them, until every compute unit has a workgroup -- and, for the query gradient, one share per latent,
+ * with float atomics, and the loss kernels add one partial per wave / block the same way: the sums' order, and so their last
+ * bits, follow the order in which workgroups finish.  With ENF_BWD_DETERMINISTIC (enf_backward_latents_ex, enf_backward_all,
+ * enf_pair_backward_ex2), ENF_FIT_DETERMINISTIC (enf_fit_step_ex) or ENF_MSE_DETERMINISTIC (enf_mse_value_grad_ex) the same
+ * kernels STORE those shares in scratch and a second pass adds them in index order: no float atomic runs, and the results are the
+ * same bits for the same inputs, the same shape, the same resolved kernel variants and the same build of the library, whatever
+ * the workspace's address, size or previous contents.  What is NOT promised: equal bits between the deterministic and the default
+ * path (another summation order), across shapes (the split z-fold forward orders its partial sums by the call's shape; nsplit
+ * follows B, Z, N) or across library builds.  The default path is unchanged: same kernels, same workspace sizes.  Cost: one or two
+ * small kernels per call and the partial buffers, nsplit x B Z gradient rows (DESIGN.md 7 has the measured times).
+ * A deterministic call needs enf_workspace_bytes_ex(d, flags) bytes of workspace (ENF_EWORKSPACE otherwise); flag bits an entry
+ * point does not know are ENF_EINVAL. */
+#define ENF_BWD_DETERMINISTIC 16u
+#define ENF_BWD_QUERY_GRAD 32u     /* size queries only: a query gradient (`dx`) will be asked for */
 int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p,
                          const float* a, const float* sigma, const void* packed, const float* ybar,
                          const float* lse, const float* dout, float* dp, float* da, float* dsigma,
@@ -269,6 +290,13 @@ int enf_pair_backward(const EnfDesc* d, const float* x, int64_t x_bstride, const
 int enf_pair_backward_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
                          const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store,
                          float* dx, void* stream);
+/* The same with flags (0 = enf_pair_backward_ex).  ENF_BWD_DETERMINISTIC: `dlt` and `dx` are summed in a fixed order from partials
+ * in `scratch` (enf_pair_backward_scratch_bytes(d, flags); pass ENF_BWD_QUERY_GRAD to the size query when `dx` is not NULL), and
+ * `dx` is then OVERWRITTEN, not accumulated into. */
+size_t enf_pair_backward_scratch_bytes(const EnfDesc* d, unsigned flags);
+int enf_pair_backward_ex2(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
+                          const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store,
+                          float* dx, void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
 
 /* Relu masks.  Second-order terms taken as finite differences of FIRST-order gradients (the outer MAML step,
  * pde_trainer.py:255) converge to the DISTRIBUTIONAL second derivative: relu units whose sign changes between the two
@@ -289,11 +317,23 @@ size_t enf_relu_mask_bytes(const EnfDesc* d);
 int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                  const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
                  void* workspace, size_t workspace_bytes, void* stream);
+/* The same with flags (0 = enf_fit_step).  ENF_FIT_DETERMINISTIC: loss and gradients are summed in a fixed order (same inputs,
+ * same bits; "Deterministic mode" above); `workspace`: enf_workspace_bytes_ex(d, ENF_FIT_DETERMINISTIC). */
+#define ENF_FIT_DETERMINISTIC 16u
+int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                    const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                    void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
 
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
                        void* stream);
+/* The same with flags (0 = enf_mse_value_grad, no scratch).  ENF_MSE_DETERMINISTIC: the blocks' partial sums go to `scratch`
+ * (enf_mse_scratch_bytes(n, flags)) and one workgroup adds them to *loss in index order. */
+#define ENF_MSE_DETERMINISTIC 16u
+size_t enf_mse_scratch_bytes(size_t n, unsigned flags);
+int enf_mse_value_grad_ex(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
+                          void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
 
 /* The meta-SGD update of one inner step for all latent components in one launch (pde_trainer.py:206-219):
  *     out = x - lr * (scale * g)        scale = the batch size (:206); lr broadcasts over the leading dims
@@ -399,11 +439,16 @@ int enf_ode_basis_backward(int64_t P, int I, int degree, int H1, int J, const fl
  * enf_backward_latents_ex; 0 recomputes what it needs), `dx` (B,N,dx) or NULL accumulates the gradient w.r.t. the queries.
  * Kernels: the tail backward in its weight-gradient form, K3 with the activation store + K4 (enf_xtd_kernel), the prologue
  * backward, fp32 matrix-pipe X^T delta products over the query / latent rows, and the chain rule through the folds of
- * enf_pack_weights -- no library GEMM, no host framework op; slices are summed in a fixed order (same inputs, same bits,
- * up to the float atomics of d lt).  scratch_bytes >= enf_backward_all_scratch_bytes(d, c) for some chunk size c in 1..B
+ * enf_pack_weights -- no library GEMM, no host framework op; slices are summed in a fixed order.  By default d lt and `dx` are
+ * accumulated with float atomics, so the results are reproducible up to those sums' last bits; with ENF_BWD_DETERMINISTIC in
+ * `flags` the store-variant pair kernel's shares of d lt and of `dx` go through partial buffers in `scratch` and fixed-order sums
+ * -- same inputs, same bits, for every output -- and `dx` is OVERWRITTEN instead of accumulated into; size `scratch` with
+ * enf_backward_all_scratch_bytes_ex(d, c, ENF_BWD_DETERMINISTIC [| ENF_BWD_QUERY_GRAD when `dx` is given]); the workspace is the
+ * plain enf_workspace_bytes(d).  scratch_bytes >= enf_backward_all_scratch_bytes(d, c) for some chunk size c in 1..B
  * signals (the largest c that fits is used; with relu masks a multiple of mask_signals).  EnfDesc.mask_mode = ENF_MASK_READ
  * replays the relu masks in the pair kernel as enf_backward_weights does. */
 size_t enf_backward_all_scratch_bytes(const EnfDesc* d, int chunk_signals);
+size_t enf_backward_all_scratch_bytes_ex(const EnfDesc* d, int chunk_signals, unsigned flags);
 int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                      const float* const* tensors, const void* packed, const float* ybar, const float* lse, const float* dout,
                      float* dp, float* da, float* dsigma, float* const* dW, float* dx, void* workspace, size_t workspace_bytes,
@@ -424,6 +469,13 @@ size_t enf_backward_weights_scratch_bytes(const EnfDesc* d, int chunk_signals);
 int enf_backward_weights(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
                          const float* lse, const float* dybar, const float* delta, float* dlt, float* const* dpair,
                          float* dx, void* scratch, size_t scratch_bytes, void* stream);
+/* The same with flags (0 = enf_backward_weights): ENF_BWD_DETERMINISTIC sums `dlt` and `dx` in a fixed order from partials at the
+ * end of `scratch` (enf_backward_weights_scratch_bytes_ex(d, c, flags), with ENF_BWD_QUERY_GRAD when `dx` is given); `dx` is then
+ * OVERWRITTEN. */
+size_t enf_backward_weights_scratch_bytes_ex(const EnfDesc* d, int chunk_signals, unsigned flags);
+int enf_backward_weights_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* lt, const void* packed,
+                            const float* lse, const float* dybar, const float* delta, float* dlt, float* const* dpair,
+                            float* dx, void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
 
 /* The pair-kernel variant a call with this descriptor runs (ENF_VARIANT_AUTO resolved): ENF_VARIANT_LATENT_SPLIT or
  * ENF_VARIANT_ZFOLD (or, forward only, ENF_VARIANT_ZFOLD_ZSPLIT); `backward` = 0 for the forward kernel, 1 for the backward kernel.
