@@ -93,7 +93,8 @@ __global__ __launch_bounds__(256) void enf_ode_conv_fwd_kernel(OdeConvArgs A) {
 
 // One wave per (b, r) and group of JG 16-basis tiles: d kb[b, r, s, 16 jt + 4 quad + i] for 16 senders at a time; the
 // product g (.) a of a sender tile is formed once and meets JG independent accumulators.
-template <int CM, int JG>   // C = 16 CM; JG basis tiles per wave (JG * CM * 4 <= 128 registers of W)
+template <int CM, int JG>   // C = 16 CM; JG basis tiles per wave (JG * CM * 4 <= 128 registers of W; C = 256: one wave per SIMD
+                            // has 512, W (JG <= 2) and g take 192 of them and the channel sum stays one pass in one wave)
 __global__ __launch_bounds__(256) void enf_ode_conv_dkb_kernel(OdeConvArgs A) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, quad = lane >> 4;
   const int jt0 = blockIdx.x * JG, r = blockIdx.y * 4 + wave, b = blockIdx.z;
@@ -134,9 +135,9 @@ __global__ __launch_bounds__(256) void enf_ode_conv_dkb_kernel(OdeConvArgs A) {
 
 static int ode_check(int B, int Z, int J, int C) {
   if (B <= 0 || Z <= 0) return ENF_EINVAL;
-  if (J % 16 || C % 16 || J < 16 || C < 16 || J > 128 || C > 128) return ENF_EUNSUPPORTED;
+  if (J % 16 || C % 16 || J < 16 || C < 16 || J > 128 || C > 256) return ENF_EUNSUPPORTED;
   if ((J / 16) & (J / 16 - 1)) return ENF_EUNSUPPORTED;      // 16, 32, 64, 128
-  if ((C / 16) & (C / 16 - 1)) return ENF_EUNSUPPORTED;
+  if ((C / 16) & (C / 16 - 1)) return ENF_EUNSUPPORTED;      // 16, 32, 64, 128, 256
   if (Z > 65535 || B > 65535) return ENF_EUNSUPPORTED;
   return ENF_OK;
 }
@@ -148,19 +149,22 @@ extern "C" int enf_ode_conv_forward(int B, int Z, int J, int C, const float* a, 
   if (!a || !kb || !W || !out) return ENF_EINVAL;
   if (kb_stride_r % 4 || kb_stride_s % 4) return ENF_EINVAL;  // 16-byte loads along the basis axis
   OdeConvArgs A{a, kb, W, bias, nullptr, out, B, Z, J, C, (long)kb_stride_r, (long)kb_stride_s};
-  // channel tiles per wave: all of them while W fits 128 registers, fewer (more waves) when B Z alone cannot fill the chip
+  // channel tiles per wave: all of them while W fits 128 registers -- 8 at the most: C = 256 takes two waves per receiver --,
+  // fewer (more waves) when B Z alone cannot fill the chip
   const int CT = C / 16, JM = J / 16;
-  int cg = CT;
+  int cg = CT < 8 ? CT : 8;
   while (cg * JM * 4 > 128) cg /= 2;
   while (cg > 1 && (long)B * Z * (CT / cg) < 2048) cg /= 2;
   const dim3 grid(CT / cg, (Z + 3) / 4, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define ODE_FWD(JM_, CG_) if (JM == JM_ && cg == CG_) hipLaunchKernelGGL((enf_ode_conv_fwd_kernel<JM_, CG_>), grid, block, 0, st, A);
+  bool hit = false;                                          // a shape no instantiation covers is an error, not a no-op
+#define ODE_FWD(JM_, CG_) if (JM == JM_ && cg == CG_) { hit = true; hipLaunchKernelGGL((enf_ode_conv_fwd_kernel<JM_, CG_>), grid, block, 0, st, A); }
   ODE_FWD(1, 1) ODE_FWD(1, 2) ODE_FWD(1, 4) ODE_FWD(1, 8)
   ODE_FWD(2, 1) ODE_FWD(2, 2) ODE_FWD(2, 4) ODE_FWD(2, 8)
   ODE_FWD(4, 1) ODE_FWD(4, 2) ODE_FWD(4, 4) ODE_FWD(4, 8)
   ODE_FWD(8, 1) ODE_FWD(8, 2) ODE_FWD(8, 4)
 #undef ODE_FWD
+  if (!hit) return ENF_EUNSUPPORTED;
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
@@ -176,12 +180,15 @@ extern "C" int enf_ode_conv_backward_basis(int B, int Z, int J, int C, const flo
   while (jg > 1 && (long)B * Z * (JT / jg) < 2048) jg /= 2;
   const dim3 grid(JT / jg, (Z + 3) / 4, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define ODE_DKB(CM_, JG_) if (CM == CM_ && jg == JG_) hipLaunchKernelGGL((enf_ode_conv_dkb_kernel<CM_, JG_>), grid, block, 0, st, A);
+  bool hit = false;
+#define ODE_DKB(CM_, JG_) if (CM == CM_ && jg == JG_) { hit = true; hipLaunchKernelGGL((enf_ode_conv_dkb_kernel<CM_, JG_>), grid, block, 0, st, A); }
   ODE_DKB(1, 1) ODE_DKB(1, 2) ODE_DKB(1, 4) ODE_DKB(1, 8)
   ODE_DKB(2, 1) ODE_DKB(2, 2) ODE_DKB(2, 4) ODE_DKB(2, 8)
   ODE_DKB(4, 1) ODE_DKB(4, 2) ODE_DKB(4, 4) ODE_DKB(4, 8)
   ODE_DKB(8, 1) ODE_DKB(8, 2) ODE_DKB(8, 4)
+  ODE_DKB(16, 1) ODE_DKB(16, 2)
 #undef ODE_DKB
+  if (!hit) return ENF_EUNSUPPORTED;
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
@@ -191,13 +198,15 @@ extern "C" int enf_ode_conv_backward_basis(int B, int Z, int J, int C, const flo
 // senders s0 + 4 q + 0..3 of a 16-sender tile.  A workgroup walks a contiguous share of the (b, r) rows; wave w owns the
 // channel tiles w, w + 4 for every basis tile, accumulates them in registers over the whole share and writes one partial
 // (J, C) per workgroup -- followed by its share of d bias[c] = sum_{b,r} g[b,r,c], which costs the kernel one add per row --;
-// enf_ode_sum_partials_kernel adds the partials in a fixed order.
+// enf_ode_sum_partials_kernel adds the partials in a fixed order.  C = 256: 4 channel tiles per wave would be 128 accumulators
+// (512 registers) at J = 128, so the grid's y index splits the channels into groups of 4 CK tiles (two halves of 128); a group
+// writes its own columns of its row share's partial, d bias included, and the number of partials stays what it is.
 struct OdeConvDwArgs { const float* a; const float* kb; const float* g; float* part; int B, Z, J, C, rows_per_wg; };
 
-template <int JT, int CK>   // J = 16 JT; CK = channel tiles per wave (C <= 64 CK)
+template <int JT, int CK>   // J = 16 JT; CK = channel tiles per wave (C <= 64 CK gridDim.y)
 __global__ __launch_bounds__(256) void enf_ode_conv_dw_kernel(OdeConvDwArgs A) {
   const int lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + 4 * CK * blockIdx.y;   // first channel tile of this wave
   const int C = A.C, J = A.J, Z = A.Z, CT = C / 16;
   f32x4 acc[CK][JT];
 #pragma unroll
@@ -288,11 +297,13 @@ extern "C" int enf_ode_conv_backward_weight(int B, int Z, int J, int C, const fl
   if (scratch_bytes < enf_ode_conv_backward_weight_scratch_bytes(B, Z, J, C)) return ENF_EINVAL;
   const int rows = B * Z, nwg0 = ode_dw_wgs(B, Z), rpw = (rows + nwg0 - 1) / nwg0, nwg = (rows + rpw - 1) / rpw;
   OdeConvDwArgs A{a, kb, g, (float*)scratch, B, Z, J, C, rpw};
-  const int JT = J / 16, CK = C > 64 ? 2 : 1;
+  const int JT = J / 16, CK = C > 64 ? 2 : 1, groups = C > 128 ? C / 128 : 1;
   hipStream_t st = (hipStream_t)stream;
-#define ODE_DW(JT_, CK_) if (JT == JT_ && CK == CK_) hipLaunchKernelGGL((enf_ode_conv_dw_kernel<JT_, CK_>), dim3(nwg), dim3(256), 0, st, A);
+  bool hit = false;
+#define ODE_DW(JT_, CK_) if (JT == JT_ && CK == CK_) { hit = true; hipLaunchKernelGGL((enf_ode_conv_dw_kernel<JT_, CK_>), dim3(nwg, groups), dim3(256), 0, st, A); }
   ODE_DW(1, 1) ODE_DW(2, 1) ODE_DW(4, 1) ODE_DW(8, 1) ODE_DW(1, 2) ODE_DW(2, 2) ODE_DW(4, 2) ODE_DW(8, 2)
 #undef ODE_DW
+  if (!hit) return ENF_EUNSUPPORTED;
   hipLaunchKernelGGL(enf_ode_sum_partials_kernel, dim3((J * C + C + 31) / 32), dim3(256), 0, st, (const float*)scratch, nwg, J * C + C, dW);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }

@@ -65,7 +65,8 @@ class _PairDense(torch.autograd.Function):
 
 
 class _SepGconv(torch.autograd.Function):
-    """out[b,r,:] = bias + sum_s a[b,s,:] * (kb[b,r,s,:] @ W)   (SepGconv.__call__, ponita_ode_g.py:63-83)."""
+    """out[b,r,:] = bias + sum_s a[b,s,:] * (kb[b,r,s,:] @ W)   (SepGconv.__call__, ponita_ode_g.py:63-83).  Channels C in
+    {16, 32, 64, 128, 256}, basis width J in {16, 32, 64, 128} (csrc/enf_ode.hip); anything else raises NotImplementedError."""
 
     @staticmethod
     def forward(ctx, a, kb, W, bias):
@@ -234,8 +235,8 @@ def _dense(x, p):
 class _LatentMLP(torch.autograd.Function):
     """ConvBlock after the convolution (ponita_ode_g.py:44-48): LayerNorm(eps 1e-6) -> Dense -> gelu -> Dense over the B Z latent
     rows.  Widths the HIP kernels cover (csrc/enf_ode_block.hip: hidden 32 / 64 / 128, widening factor 2): ONE launch forward,
-    two backward.  Other widths: library GEMMs with the backward written out (4 launches forward, 10 backward instead of the
-    ~25 of the op-by-op autograd graph) -- the evaluation is launch-bound."""
+    two backward.  Other widths (hidden 256 of config_shallow_water.yaml's node among them): library GEMMs with the backward
+    written out (4 launches forward, 10 backward instead of the ~25 of the op-by-op autograd graph) -- the evaluation is launch-bound."""
     EPS = 1e-6
 
     @staticmethod

@@ -376,7 +376,8 @@ int enf_fit_inputs(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z
  * enf_ode_conv_backward_weight: d W (J,C) = kb^T (g (x) a) over the pair axis, the (B,Z,Z,C) product formed in registers, and
  *   d bias (C) = sum_{b,r} g: `dW` is ONE buffer of J*C + C floats, d W followed by d bias;
  *   scratch: enf_ode_conv_backward_weight_scratch_bytes(B,Z,J,C) bytes (per-workgroup partials, summed in a fixed order).
- * J, C in {16, 32, 64, 128}; all buffers fp32, contiguous, 16-byte aligned. */
+ * J in {16, 32, 64, 128}, C in {16, 32, 64, 128, 256} (256: config_shallow_water.yaml's node), anything else ENF_EUNSUPPORTED;
+ * all buffers fp32, contiguous, 16-byte aligned. */
 int enf_ode_conv_forward(int B, int Z, int J, int C, const float* a, const float* kb, int64_t kb_stride_r,
                          int64_t kb_stride_s, const float* W, const float* bias, float* out, void* stream);
 int enf_ode_conv_backward_basis(int B, int Z, int J, int C, const float* a, const float* g, const float* W, float* dkb,

@@ -1,8 +1,11 @@
 """Latent ODE at the bench shape (16 signals x 64 latents of width 16; config_navier_stokes.yaml's node: ponita, hidden 128,
 basis 64, 3 layers, degree 3): time of one derivative evaluation (forward, forward + backward), of the fused SepGconv
 kernels alone against their fp32-MFMA roofline, and of one ode_train_step (10 frames, Euler, 512 points per frame).
-Prints one JSON line.  Usage: python scripts/bench_ode.py [iters]"""
-import json, os, sys, time
+--hidden / --basis / --latents / --latent-dim choose another node, e.g. config_shallow_water.yaml's
+(--hidden 256 --basis 128 --latents 8 --latent-dim 32); the train and validation steps are timed at the bench's latent set only
+(its decoder and grid of latents), so with other --latents / --latent-dim the line stops after the convolution.
+Prints one JSON line.  Usage: python scripts/bench_ode.py [iters] [--hidden H] [--basis J] [--latents Z] [--latent-dim C]"""
+import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from types import SimpleNamespace as NS
 import torch
@@ -13,8 +16,15 @@ from enf_pde_amd.fitting.trainers import MetaSGDPDETrainer
 from enf_pde_amd.enf.latents.autodecoder_meta import PositionOrientationFeatureAutodecoderMeta
 
 dev = torch.device("cuda:0")
-iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-B, Z, C, H, J = bench.B_PER_GPU, bench.Z, bench.C, 128, 64
+ap = argparse.ArgumentParser()
+ap.add_argument("iters", nargs="?", type=int, default=20)
+ap.add_argument("--hidden", type=int, default=128)
+ap.add_argument("--basis", type=int, default=64)
+ap.add_argument("--latents", type=int, default=bench.Z)
+ap.add_argument("--latent-dim", type=int, default=bench.C)
+args = ap.parse_args()
+iters = args.iters
+B, Z, C, H, J = bench.B_PER_GPU, args.latents, args.latent_dim, args.hidden, args.basis
 cfg = NS(nef=NS(num_in=2, num_out=1, num_layers=0, num_hidden=128, num_heads=2, condition_value_transform=True, latent_dim=C,
                 num_latents=Z, use_gaussian_window=True, embedding_type="rff", embedding_freq_multiplier_invariant=0.05,
                 embedding_freq_multiplier_value=0.1, invariant_type="rel_pos_periodic"),
@@ -81,6 +91,16 @@ with torch.no_grad():
     ms_conv = timed(lambda: sep_gconv(A_, KB, W_, b_), 200)
 flops = 2.0 * B * Z * Z * J * H + 2.0 * B * Z * Z * H           # kb @ W, then * a and the sender sum
 bytes_ = 4.0 * (B * Z * Z * J + 2 * B * Z * H + J * H)
+workload = f"ponita ODE, B={B} Z={Z} C={C} hidden={H} basis={J} layers=3 degree=3 (340 features)"
+conv = {"ms": round(ms_conv, 5), "tflops": round(flops / ms_conv / 1e9, 2), "peak_tflops_fp32_mfma": 157.3,
+        "frac_mfma": round(flops / ms_conv / 1e9 / 157.3, 4), "gbps": round(bytes_ / ms_conv / 1e6, 1),
+        "frac_hbm": round(bytes_ / ms_conv / 1e6 / 8000, 4)}
+evals = {"workload": workload, "ms_ode_eval_fwd": round(ms_fwd, 4), "ms_ode_eval_fwd_bwd": round(ms_fb, 4),
+         "ms_ode_eval_fwd_bwd_graphed": round(ms_fb_graph, 4), "pair_evals_per_s_fwd": round(B * Z * Z / ms_fwd * 1e3, 1),
+         "sep_gconv": conv}
+if (Z, C) != (bench.Z, bench.C):                   # the trainer below runs on the bench's decoder and latent grid
+    print(json.dumps(evals))
+    sys.exit(0)
 # one ode_train_step: 10 frames, 512 points per frame
 conf = NS(optimizer=NS(learning_rate_enf=1e-4, learning_rate_codes=0.0, learning_rate_ode=1e-3),
           meta=NS(learning_rate_meta_sgd=1e-3, num_inner_steps=3, inner_learning_rate_p=1.0, inner_learning_rate_a=5.0,
@@ -107,11 +127,4 @@ ms_step = timed(step, max(3, iters // 4))
 tr.graph_ode_training = False
 with torch.no_grad():
     ms_val = timed(lambda: tr.val_step(state[0], traj), max(3, iters // 4))
-print(json.dumps({"workload": f"ponita ODE, B={B} Z={Z} C={C} hidden={H} basis={J} layers=3 degree=3 (340 features)",
-                  "ms_ode_eval_fwd": round(ms_fwd, 4), "ms_ode_eval_fwd_bwd": round(ms_fb, 4),
-                  "ms_ode_eval_fwd_bwd_graphed": round(ms_fb_graph, 4),
-                  "pair_evals_per_s_fwd": round(B * Z * Z / ms_fwd * 1e3, 1),
-                  "sep_gconv": {"ms": round(ms_conv, 5), "tflops": round(flops / ms_conv / 1e9, 2), "peak_tflops_fp32_mfma": 157.3,
-                                "frac_mfma": round(flops / ms_conv / 1e9 / 157.3, 4), "gbps": round(bytes_ / ms_conv / 1e6, 1),
-                                "frac_hbm": round(bytes_ / ms_conv / 1e6 / 8000, 4)},
-                  "ms_ode_train_step_10_frames": round(ms_step_eager, 3), "ms_ode_train_step_10_frames_graphed_evals": round(ms_step, 3), "ms_val_step_14_frames_full_grid": round(ms_val, 3)}))
+print(json.dumps({**evals, "ms_ode_train_step_10_frames": round(ms_step_eager, 3), "ms_ode_train_step_10_frames_graphed_evals": round(ms_step, 3), "ms_val_step_14_frames_full_grid": round(ms_val, 3)}))
