@@ -18,7 +18,12 @@ DIR/<name>.npy in float32, so that two builds can be compared output for output:
 the same arguments give the same inputs on every run.  The outputs themselves agree between runs to the kernels' rounding,
 not bit for bit: the backward and the loss sum with float atomics.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the
+dump if asked for, and the line with the metric, `value`, `ms_per_step`, the workload's description and the final fit loss.
+`--full` (off by default) adds every other measurement and check below to the same line, after the timed steps; the
+`--no-*`, `--events-steps`, `--kernel-iters` and `--graph-leg` options choose among them and mean nothing without it
+(`--graph-leg` without `--full` is refused).  `--roofline-only` is a run of its own and needs no `--full`.  Extra objects
+of a `--full` run:
   roofline         : the kernel the step spends most of its time in, timed alone with events on its launch stream:
                      achieved = algorithmic (as-written) FLOPs of SURVEY.md 8a / 8d per launch / average launch time
                      against the dense bf16 MFMA peak; `executed_frac` = the MFMA FLOPs the kernel really issues (exact
@@ -658,6 +663,12 @@ def ensure_world(args):
     sys.exit(subprocess.call(cmd, env=env))
 
 
+def _leave(world):
+    if world > 1:
+        torch.distributed.barrier()          # ranks leave together (rank 0 may have just run its extra legs)
+        torch.distributed.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -665,6 +676,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=HEADLINE, choices=sorted(CONFIGS), help="BASELINE.json config (default: 2, the metric's)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check (outer step, event timing, accuracy against "
+                         "the oracle, fit / decode split, per-kernel rooflines, latent-ODE evaluation, CPU baseline) and add them to the "
+                         "line; the options below choose among these legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-meta", action="store_true", help="skip the outer-step leg")
     ap.add_argument("--no-ode", action="store_true", help="skip the latent-ODE evaluation leg (config 2, one GPU)")
@@ -681,6 +696,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.graph_leg and not args.full:
+        ap.error("--graph-leg is one of the legs of a --full run: pass --full with it")
     ensure_world(args)
 
     from enf_pde_amd.fitting import init_distributed
@@ -742,6 +759,11 @@ def main():
         "final_fit_loss": round(float(loss), 6),
         "timing": {"value_from": "wall clock over exactly --steps steps between barrier + synchronize, max over ranks (the contract)"},
     }
+    if not args.full:                    # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        _leave(world)
+        return
     if not args.no_meta and not c.get("rollout"):
         meta = meta_leg(c, m, coords, img, device, world)          # every rank: the outer step has the collective
         result["meta_step"] = meta
@@ -772,9 +794,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_leg(c)
         print(json.dumps(result), flush=True)
-    if world > 1:
-        torch.distributed.barrier()          # ranks leave together (rank 0 has just run its extra legs)
-        torch.distributed.destroy_process_group()
+    _leave(world)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_profiled.log 2>&1 || { echo "stats pass failed"; tail -5 $OUT/bench_profiled.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_profiled.log 2>&1 || { echo "stats pass failed"; tail -5 $OUT/bench_profiled.log; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 240 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/hbm_$c -o p -- python3 $REPO/scripts/prof_fwd.py fwd > $OUT/hbm_$c.log 2>&1 || { echo "pmc $c failed"; tail -5 $OUT/hbm_$c.log; exit 1; }
 done

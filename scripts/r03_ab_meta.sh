@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_weight_grads.py tests/test_gpu
 [ $rc = 0 ] || exit 1
 for r in 1 2 3; do for v in $1 default; do
   L=variants/libenf_$v.so; [ $v = default ] && L=
-  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-ode --events-steps 0 --no-roofline --no-accuracy > $O/meta_$v.json 2>$O/meta_$v.err || { echo "bench $v failed"; tail -5 $O/meta_$v.err; exit 1; }
+  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-ode --events-steps 0 --no-roofline --no-accuracy > $O/meta_$v.json 2>$O/meta_$v.err || { echo "bench $v failed"; tail -5 $O/meta_$v.err; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$O/meta_$v.json').readline()); print('$v', 'meta', d['meta_step']['ms_per_step'])"
 done; done

@@ -6,6 +6,6 @@ ENF_HIP_LIB=variants/libenf_$1.so timeout -k 10 600 python -m pytest tests/test_
 [ $rc = 0 ] || exit 1
 for r in 1 2 3; do for v in $1 default; do
   L=variants/libenf_$v.so; [ $v = default ] && L=
-  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-meta --no-ode --no-roofline --no-accuracy --events-steps 100 2>/dev/null | python3 -c "
+  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-meta --no-ode --no-roofline --no-accuracy --events-steps 100 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.readline()); print('$v', d['ms_per_step'], d['timing']['events']['ms_median'])"
 done; done

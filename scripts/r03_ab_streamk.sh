@@ -7,7 +7,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_forward.py tests/test_gpu_gold
 [ $rc = 0 ] || exit 1
 for v in sk43 default sk43 default; do
   L=variants/libenf_$v.so; [ $v = default ] && L=
-  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --config 3 --steps 20 --warmup 5 --no-cpu-baseline --no-meta --no-ode --events-steps 0 --no-accuracy > $O/c18_$v.json 2>$O/c18_$v.err || { echo "bench $v failed"; tail -5 $O/c18_$v.err; exit 1; }
+  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --full --config 3 --steps 20 --warmup 5 --no-cpu-baseline --no-meta --no-ode --events-steps 0 --no-accuracy > $O/c18_$v.json 2>$O/c18_$v.err || { echo "bench $v failed"; tail -5 $O/c18_$v.err; exit 1; }
   python3 - $O/c18_$v.json $v <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).readline())

@@ -7,7 +7,7 @@ timeout -k 10 1000 python -m pytest tests/test_gpu_forward.py tests/test_gpu_bac
 [ $rc = 0 ] || exit 1
 for v in base default base default base default; do
   L=variants/libenf_$v.so; [ $v = default ] && L=
-  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-meta --no-ode --events-steps 0 --kernel-iters 60 > $O/pk_$v.json 2>$O/pk_$v.err || { echo "bench $v failed"; tail -5 $O/pk_$v.err; exit 1; }
+  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-meta --no-ode --events-steps 0 --kernel-iters 60 > $O/pk_$v.json 2>$O/pk_$v.err || { echo "bench $v failed"; tail -5 $O/pk_$v.err; exit 1; }
   python3 - $O/pk_$v.json $v <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).readline())

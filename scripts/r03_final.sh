@@ -9,9 +9,9 @@ if [ "$1" = "suite" ]; then
   [ $rc = 0 ] || exit 1
 fi
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && tail -2 $O/smoke.log &&
-python bench.py > $O/bench.json 2> $O/bench.err && cut -c1-400 $O/bench.json &&
+python bench.py --full > $O/bench.json 2> $O/bench.err && cut -c1-400 $O/bench.json &&
 cd /tmp && export TMPDIR=/tmp &&
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_bench -o p -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/bench_profiled.json 2> $R/$O/bench_profiled.err &&
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_bench -o p -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/bench_profiled.json 2> $R/$O/bench_profiled.err &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_roofline -o p -- python3 $R/bench.py --roofline-only > $R/$O/roofline_only.json 2> $R/$O/roofline_only.err &&
 cd $R && cp $O/prof_bench/p_kernel_stats.csv $O/bench_kernel_stats.csv && cp $O/prof_roofline/p_kernel_stats.csv $O/roofline_only_kernel_stats.csv &&
 python3 - <<'PY'

@@ -29,7 +29,7 @@ for mode in ("half", "full"):
 PY
 for v in base default base default base default; do
   L=variants/libenf_$v.so; [ $v = default ] && L=
-  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-meta --no-ode --events-steps 0 --no-roofline > $O/yh_$v.json 2>$O/yh_$v.err || { echo "bench $v failed"; tail -5 $O/yh_$v.err; exit 1; }
+  ENF_HIP_LIB=$L timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-meta --no-ode --events-steps 0 --no-roofline > $O/yh_$v.json 2>$O/yh_$v.err || { echo "bench $v failed"; tail -5 $O/yh_$v.err; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$O/yh_$v.json').readline()); print('$v', d['ms_per_step'], '%.2e' % d['accuracy']['mse_vs_oracle'])"
 done

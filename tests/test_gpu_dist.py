@@ -78,7 +78,7 @@ def test_two_ranks_share_one_outer_step(cuda):
 def test_bench_spawns_its_own_ranks(cuda, gpus, config):
     """`bench.py --gpus N` with no torchrun environment launches N ranks itself (here all on the one GPU, over gloo:
     ENF_BENCH_SHARE_GPU=1, a rehearsal switch) and the line it prints says N ranks ran, with the outer step's all-reduce
-    inside the timed meta_step leg.  (4, 4): BASELINE config 4's data-parallel workload (128 latents, 128 x 128 grid, 8 signals
+    inside the timed meta_step leg (a leg of a --full run).  (4, 4): BASELINE config 4's data-parallel workload (128 latents, 128 x 128 grid, 8 signals
     per rank) at the largest rank count one GPU box admits (its process guard allows 6 GPU processes; the 8-rank exchange
     itself is covered on CPU: tests/test_dist_gloo.py)."""
     import json
@@ -89,7 +89,7 @@ def test_bench_spawns_its_own_ranks(cuda, gpus, config):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["ENF_BENCH_SHARE_GPU"] = "1"
     steps = 2 if gpus == 2 else 1
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--config", str(config), "--steps", str(steps),
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", str(gpus), "--config", str(config), "--steps", str(steps),
                         "--warmup", "1", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -101,12 +101,12 @@ def test_bench_spawns_its_own_ranks(cuda, gpus, config):
     assert abs(d["value"] - gpus * one * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-3 * d["value"]      # the whole job's points / time
 
 
-@pytest.mark.parametrize("flags", [["--config", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
-                                   ["--config", "3", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-meta", "--no-roofline"],
+@pytest.mark.parametrize("flags", [["--config", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
+                                   ["--config", "3", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-meta", "--no-roofline"],
                                    ["--roofline-only"]])
 def test_bench_flags(cuda, flags):
-    """bench.py's other workloads and legs keep running: a BASELINE.json config other than the headline one prints the
-    contract's line with its own workload name; --roofline-only prints the three per-kernel legs."""
+    """bench.py's other workloads and the legs of a --full run keep running: a BASELINE.json config other than the headline one
+    prints the contract's line with its own workload name; --roofline-only prints the three per-kernel legs."""
     import json
     import subprocess
     import sys
@@ -128,13 +128,13 @@ def test_bench_flags(cuda, flags):
 
 
 def test_bench_default_line_carries_the_ode_leg(cuda):
-    """The headline workload's line also reports the latent-ODE derivative evaluation (`ode_eval`): measured, not an error string."""
+    """The headline workload's --full line also reports the latent-ODE derivative evaluation (`ode_eval`): measured, not an error string."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-meta",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-meta",
                         "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -149,7 +149,8 @@ def test_bench_dumps_the_last_steps_outputs(cuda, tmp_path):
     runs with the same arguments give the same outputs up to the order of the float atomics in the backward and the loss,
     which the bf16 inner steps carry into the fitted latents: measured ~4e-5 relative on the loss and a field MSE of ~1.4e-6
     between runs, the size of the bf16 kernels' error against the fp64 oracle, so the fields are held to the bench's accuracy
-    budget for that error (1e-5).  Other inputs would differ by O(0.1).  --steps sets the number of timed steps."""
+    budget for that error (1e-5).  Other inputs would differ by O(0.1).  --steps sets the number of timed steps.
+    These are plain runs (no --full): their line carries the headline's fields and none of the objects that the legs of a --full run add."""
     import json
     import subprocess
     import sys
@@ -161,12 +162,16 @@ def test_bench_dumps_the_last_steps_outputs(cuda, tmp_path):
     runs = []
     for i in range(2):
         out = tmp_path / f"run{i}"
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-meta",
-                            "--no-roofline", "--no-ode", "--no-accuracy", "--events-steps", "0", "--dump-outputs", str(out)],
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(out)],
                            env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
         assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert d["metric"].startswith("query-points/sec") and d["unit"] == "query-points/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert abs(d["value"] - c["B"] * ((c["S"] + 1) * c["N_s"] + c["grid"][0] * c["grid"][1]) / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+        assert not {"meta_step", "accuracy", "split", "roofline", "roofline_kernels", "roofline_step", "ode_eval", "cpu_baseline"} & set(d)
+        assert set(d["timing"]) == {"value_from"}
         loss, recon = np.load(out / "loss.npy"), np.load(out / "recon.npy")
         assert loss.dtype == np.float32 and loss.shape == () and abs(float(loss) - d["final_fit_loss"]) < 1e-6
         assert recon.dtype == np.float32 and recon.shape == (c["B"], c["grid"][0] * c["grid"][1], c["O"]) and np.isfinite(recon).all()

@@ -448,6 +448,18 @@ def test_bench_refuses_fewer_than_one_step():
     assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_has_a_full_option_that_owns_the_extra_legs():
+    """--full is an option of bench.py, off by default, and an option that asks for one of its legs (--graph-leg) without it
+    is refused before anything runs, so that a leg never goes missing from a line without a word."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    bench = os.path.join(ROOT, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--graph-leg"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr and not r.stdout.strip()
+    r = subprocess.run([sys.executable, bench, "--full", "--steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr and "unrecognized" not in r.stderr and not r.stdout.strip()
+
+
 def test_bench_configs_cover_baseline_json():
     import json
     import bench
