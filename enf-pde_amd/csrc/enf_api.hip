@@ -273,6 +273,15 @@ extern "C" int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride,
 extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                                float* dsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  return enf_fit_step_w(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes,
+                        nullptr, flags, stream);
+}
+
+// weight != NULL: one loss weight per signal and query (include/enf_hip.h, "Weighted loss"); the one copy of the fit-step sequence
+extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, unsigned flags,
+                              void* stream) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
   int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma, sigma, packed,
@@ -293,7 +302,7 @@ extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstri
     if (zb && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
     if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   }
-  if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
+  if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
                                  det ? c.F(c.X.loss) : nullptr)))
     return rc;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;

@@ -155,6 +155,8 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
                        float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
 // the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
 // backward chain -> d ybar, delta
+// weight: NULL, or one loss weight per query (B N floats, include/enf_hip.h "Weighted loss")
 // loss_part != NULL (enf_tail_loss_parts(m) floats): every wave stores its partial there and enf_launch_loss_sum adds them to *loss
-int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target, float gscale,
-                         float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part = nullptr);
+int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
+                         const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st,
+                         float* loss_part = nullptr);

@@ -1,6 +1,7 @@
 // enf_loss.hip -- the inner loop's reconstruction loss and its gradient in one pass.
 //   loss = mean((out - target)^2)          (pde_trainer.py:185)
 //   dout = 2 (out - target) / n * grad_scale
+// optionally with one weight per signal and point on the squared error (enf_mse_value_grad_w),
 // so that a fit step is forward -> this kernel -> backward, without a framework autograd graph of tiny
 // elementwise kernels in between.  `loss` is accumulated with one atomic per block: the caller zeroes it.  Deterministic mode
 // (enf_mse_value_grad_ex with ENF_MSE_DETERMINISTIC; the fused tail of enf_fit_step_ex): the blocks / waves STORE their partials in
@@ -11,14 +12,24 @@
 #include <hip/hip_runtime.h>
 #include "enf_launch.h"
 
-__global__ __launch_bounds__(256) void enf_mse_kernel(const float* __restrict__ out, const float* __restrict__ target, size_t n,
-                                                      float inv_n, float gscale, float* __restrict__ dout, float* loss,
-                                                      float* __restrict__ part) {
+// weight != nullptr: one loss weight per group of O consecutive elements (per signal and query point; include/enf_hip.h, "Weighted
+// loss"): s += w d^2, dout *= w; a point of weight 0 does not exist -- its target is never used in arithmetic and its dout is 0.0f.
+__global__ __launch_bounds__(256) void enf_mse_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                      const float* __restrict__ weight, size_t n, int O, float inv_n, float gscale,
+                                                      float* __restrict__ dout, float* loss, float* __restrict__ part) {
   __shared__ float red[4];
   float s = 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float d = out[i] - target[i];
-    s = fmaf(d, d, s);
+    float d;
+    if (weight) {          // (uniform over the launch; the unweighted arithmetic stays as it was)
+      const float w = weight[i / (size_t)O];
+      const float dd = w > 0.f ? out[i] - target[i] : 0.f;
+      d = w * dd;
+      s = fmaf(d, dd, s);
+    } else {
+      d = out[i] - target[i];
+      s = fmaf(d, d, s);
+    }
     if (dout) dout[i] = 2.0f * d * inv_n * gscale;
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -61,18 +72,23 @@ extern "C" size_t enf_mse_scratch_bytes(size_t n, unsigned flags) {
   return (flags & ENF_MSE_DETERMINISTIC) ? enf_align(sizeof(float) * mse_blocks(n)) : 0;
 }
 
-extern "C" int enf_mse_value_grad_ex(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
-                                     void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
-  if (!out || !target || !loss || n == 0 || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
+extern "C" int enf_mse_value_grad_w(const float* out, const float* target, const float* weight, size_t n, int32_t O, float grad_scale,
+                                    float* dout, float* loss, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+  if (!out || !target || !loss || n == 0 || O < 1 || n % (size_t)O != 0 || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
   const bool det = (flags & ENF_MSE_DETERMINISTIC) != 0;
   if (det && !scratch) return ENF_EINVAL;
   if (det && scratch_bytes < enf_mse_scratch_bytes(n, flags)) return ENF_EWORKSPACE;
   const size_t blocks = mse_blocks(n);
   float* part = det ? (float*)scratch : nullptr;
-  hipLaunchKernelGGL(enf_mse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, n, 1.0f / (float)n,
-                     grad_scale, dout, loss, part);
+  hipLaunchKernelGGL(enf_mse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, weight, n, (int)O,
+                     1.0f / (float)n, grad_scale, dout, loss, part);
   if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
   return det ? enf_launch_loss_sum(part, (int)blocks, loss, (hipStream_t)stream) : ENF_OK;
+}
+
+extern "C" int enf_mse_value_grad_ex(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
+                                     void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+  return enf_mse_value_grad_w(out, target, nullptr, n, 1, grad_scale, dout, loss, scratch, scratch_bytes, flags, stream);
 }
 
 extern "C" int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
@@ -123,6 +139,7 @@ struct FitInArgs {
   int ncomp, B, Z, N, Ns, S1, dx, O;
   const float* coords; const float* img; const int64_t* masks;
   float* xs; float* ys; float* losses;
+  const float* weight; float* ws;      // both or neither: the loss weights (B, N) and their gather (S1, B, Ns)
 };
 
 __global__ __launch_bounds__(256) void enf_fit_inputs_kernel(FitInArgs A) {
@@ -153,13 +170,29 @@ __global__ __launch_bounds__(256) void enf_fit_inputs_kernel(FitInArgs A) {
     return;
   }
   i -= ny;
+  if (A.weight) {                                 // ws[s][b][q] = weight[b][masks[q][s]]
+    const int64_t nw = (int64_t)A.S1 * A.B * A.Ns;
+    if (i < nw) {
+      const int64_t q = i % A.Ns, r = i / A.Ns, b = r % A.B, s = r / A.B;
+      A.ws[i] = A.weight[b * A.N + A.masks[q * A.S1 + s]];
+      return;
+    }
+    i -= nw;
+  }
   if (i < A.S1) A.losses[i] = 0.f;
 }
 
 extern "C" int enf_fit_inputs(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx,
                               int32_t O, const float* coords, const float* img, const int64_t* masks, float* xs, float* ys, float* losses,
                               void* stream) {
+  return enf_fit_inputs_w(ncomp, comps, B, Z, N, Ns, S1, dx, O, coords, img, masks, xs, ys, losses, nullptr, nullptr, stream);
+}
+
+extern "C" int enf_fit_inputs_w(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx,
+                                int32_t O, const float* coords, const float* img, const int64_t* masks, float* xs, float* ys,
+                                float* losses, const float* weight, float* ws, void* stream) {
   if (ncomp < 1 || ncomp > ENF_SGD_MAX_SEGMENTS || !comps || !coords || !img || !masks || !xs || !ys || !losses) return ENF_EINVAL;
+  if ((weight == nullptr) != (ws == nullptr)) return ENF_EINVAL;
   if (B < 1 || Z < 1 || N < 1 || Ns < 1 || S1 < 1 || dx < 1 || O < 1) return ENF_EDIM;
   FitInArgs A{};
   int64_t total = 0;
@@ -169,9 +202,8 @@ extern "C" int enf_fit_inputs(int ncomp, const EnfFitComponent* comps, int32_t B
     total += (int64_t)B * Z * comps[k].width;
   }
   A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = N; A.Ns = Ns; A.S1 = S1; A.dx = dx; A.O = O;
-  A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses;
-  total += (int64_t)S1 * Ns * dx + (int64_t)S1 * B * Ns * O + S1;
+  A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = weight; A.ws = ws;
+  total += (int64_t)S1 * Ns * dx + (int64_t)S1 * B * Ns * O + (weight ? (int64_t)S1 * B * Ns : 0) + S1;
   hipLaunchKernelGGL(enf_fit_inputs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
-

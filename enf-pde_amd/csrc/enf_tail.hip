@@ -21,6 +21,8 @@ struct TailArgs {
   const float* dout;     // backward
   float* dybar; float* delta; float* act;   // backward outputs + scratch (B*N x (2HD + 2D + 2))
   const float* target; float* loss; float gscale, inv_n;     // fused loss (LOSS): d out = 2 (out - target) inv_n gscale, *loss += mean sq. error
+  const float* weight;   // LOSS: nullptr, or one loss weight per query (NQ floats, >= 0): se += w (out - target)^2, d out *= w; a query of weight
+                         // 0 does not exist -- its target is never used in arithmetic (it may be NaN) and its d out is exactly 0
   float* loss_part;      // LOSS, deterministic mode: wave w of workgroup g stores its partial in loss_part[g * NWAVES + w] (nullptr: atomic)
   float* tdel;           // weight-gradient backward (WG): per query d a_B | d a_F1 | d a_O0 | d a_O2 (2HD + 2D floats); the layer INPUTS
                          // n^ | gelu(a_F1) | gelu(a_O0) | gelu(a_O2) replace the pre-activations in `act` (enf_train.hip forms X^T delta)
@@ -285,6 +287,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   if constexpr (LOSS) {
     float se = 0.f;
     const float gs = 2.0f * A.inv_n * A.gscale;
+    if (A.weight) {          // (wave-uniform; the unweighted arithmetic below stays as it was, bit for bit)
+      const float w = A.weight[qi];
+      const bool live = qvalid && w > 0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int o = 16 * t + 4 * quad + i;
+          const float dd = (o < A.O && live) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
+          const float wd = w * dd;
+          se = fmaf(wd, dd, se);
+          g0[t][i] = wd * gs;
+        }
+    } else {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -294,6 +310,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
         se = fmaf(dd, dd, se);
         g0[t][i] = dd * gs;
       }
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
     if (lane == 0) {
@@ -459,7 +476,7 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
                        const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
-  A.target = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr;
+  A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr;
   A.tdel = tdel;
   A.ybar_half = (!bwd && (opt & 2) && m.bf16) ? 1 : 0;
   opt &= 1;
@@ -481,22 +498,22 @@ int enf_tail_loss_parts(const EnfDims& m) {
 }
 
 static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                            float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part);
+                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part);
 
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                         float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
-  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, gscale, loss, dybar, delta, act, st, loss_part)) return rc;
+                         const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
+  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, gscale, loss, dybar, delta, act, st, loss_part)) return rc;
   return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
 }
 
 static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                            float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
+                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
   A.loss_part = loss_part;
   A.ybar = ybar; A.blob = blob; A.L = L; A.out = nullptr; A.dout = nullptr; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = nullptr;
   A.ybar_half = 0;
-  A.target = target; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
+  A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
 #define ENF_CASE(DD, HH)                                                                   \
   if (m.D == DD && m.H == HH) return m.bf16 ? launch_tail<DD, HH, true>(A, true, false, st) : launch_tail<DD, HH, false>(A, true, false, st);

@@ -511,12 +511,19 @@ class EquivariantCrossAttentionNeF:
         return cm()
 
     @torch.no_grad()
-    def mse_value_and_latent_grads(self, params, x, p, a, gaussian_window_size, target, grad_scale=1.0, loss_out=None):
+    def mse_value_and_latent_grads(self, params, x, p, a, gaussian_window_size, target, grad_scale=1.0, loss_out=None, weight=None):
         """loss = mean((nef.apply(params, x, p, a, window) - target)^2) and grad_scale * d loss / d(p, a, window) in one
         sequence of HIP launches (forward, loss + d out, backward), without building an autograd graph: what one
         inner step of the MAML loop computes (pde_trainer.py:175-207; grad_scale = B there).
         ``loss_out``: an already ZEROED float32 (1,) tensor to accumulate the loss into (saves the fill per call).
+        ``weight``: None, or (B, N) loss weights per signal and query point, finite and >= 0 (include/enf_hip.h, "Weighted
+        loss"): loss = sum_{b,n} weight[b,n] sum_o (out - target)^2 / (B N O), not normalised here (fitting/weights.py does
+        that); a point of weight 0 does not exist -- its target may be NaN.
         Returns (loss (1,), dp, da, dwindow or None)."""
+        if weight is not None:
+            if tuple(weight.shape) != (p.shape[0], x.shape[1]):
+                raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(p.shape[0], x.shape[1])}")
+            weight = weight.float().contiguous()
         lib = _lib.load()
         sigma = gaussian_window_size if self.use_gaussian_window else None
         if self.num_layers > 0:           # no fused sequence for the layered model: autograd through apply()
@@ -524,7 +531,12 @@ class EquivariantCrossAttentionNeF:
                 leaves = [t.detach().float().requires_grad_(True) for t in (p, a)] + \
                          ([sigma.detach().float().requires_grad_(True)] if sigma is not None else [])
                 out = self.apply(params, x, leaves[0], leaves[1], leaves[2] if sigma is not None else None)
-                loss = ((out - target) ** 2).mean()
+                if weight is None:
+                    loss = ((out - target) ** 2).mean()
+                else:
+                    wgt = weight[..., None]
+                    dd = torch.where(wgt > 0, out - target, torch.zeros_like(out))
+                    loss = (wgt * dd * dd).mean()
                 g = torch.autograd.grad(loss * grad_scale, leaves, allow_unused=True)
             g = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(leaves, g)]
             if loss_out is not None:
@@ -555,8 +567,8 @@ class EquivariantCrossAttentionNeF:
             dout = torch.empty_like(out)
             nmse = int(lib.enf_mse_scratch_bytes(out.numel(), det))
             mse_scr = torch.empty(nmse, device=dev, dtype=torch.uint8) if nmse else None
-            _lib.launch(dev, lib.enf_mse_value_grad_ex, _ptr(out), _ptr(tgt), out.numel(), float(grad_scale), _ptr(dout), _ptr(loss),
-                        _ptr(mse_scr), nmse, det, st)
+            _lib.launch(dev, lib.enf_mse_value_grad_w, _ptr(out), _ptr(tgt), _ptr(weight), out.numel(), self.num_out, float(grad_scale),
+                        _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
             _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_),
                         _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(),
                         1 | 2 | 4 | det, st)
@@ -564,7 +576,7 @@ class EquivariantCrossAttentionNeF:
             return loss, dp, da, (dsig if sigma is not None else None)
         # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
         # the loss and its gradient formed in registers, pair backward, prologue backward
-        _lib.launch(dev, lib.enf_fit_step_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), det, st)
+        _lib.launch(dev, lib.enf_fit_step_w, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(weight), det, st)
         self._ws_touch(ws)
         return loss, dp, da, (dsig if sigma is not None else None)

@@ -4,6 +4,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from .weights import gather_point_weights
 
 
 def default_meta_sgd_lrs(latent_dim, lr_p=1.0, lr_a=5.0, lr_window=0.0, with_ori=False, device="cuda"):
@@ -25,10 +26,11 @@ def make_masks(num_coords, num_sampled, num_inner_steps, generator=None, device=
 FUSED_FIT_INPUTS = __import__("os").environ.get("ENF_FIT_INPUTS") != "0"
 
 
-def _fit_inputs(latents0, coords, img, masks):
-    """enf_fit_inputs (include/enf_hip.h): (lat, xs_all, ys_all, losses) of inner_loop in one launch, or None where the arguments are not
-    what the kernel takes (fp32, contiguous, on one GPU, at most four latent components of leading dimension 1)."""
-    ts = list(latents0.values()) + [coords, img]
+def _fit_inputs(latents0, coords, img, masks, weights=None):
+    """enf_fit_inputs[_w] (include/enf_hip.h): (lat, xs_all, ys_all, losses) of inner_loop in one launch, or None where the
+    arguments are not what the kernel takes (fp32, contiguous, on one GPU, at most four latent components of leading dimension 1).
+    With ``weights`` (B, N) a fifth value, their gather ws_all (S1, B, Ns)."""
+    ts = list(latents0.values()) + [coords, img] + ([weights] if weights is not None else [])
     if not (img.is_cuda and masks.is_cuda and masks.dtype == torch.int64 and masks.dim() == 2 and masks.is_contiguous() and coords.dim() == 2
             and img.dim() == 3 and 1 <= len(latents0) <= _lib.ENF_SGD_MAX_SEGMENTS and masks.shape[0] > 0
             and all(t.dtype == torch.float32 and t.is_contiguous() and t.device == img.device for t in ts)
@@ -50,9 +52,11 @@ def _fit_inputs(latents0, coords, img, masks):
         keep.append(src)
         comps[i] = _lib.EnfFitComponent(src.data_ptr(), lat[k].data_ptr(), v.shape[2], 0)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.launch(dev, _lib.load().enf_fit_inputs, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(), img.data_ptr(),
-                masks.data_ptr(), xs.data_ptr(), ys.data_ptr(), losses.data_ptr(), st)
-    return lat, xs, ys, losses
+    ws = torch.empty((S1, B, Ns), device=dev, dtype=torch.float32) if weights is not None else None
+    _lib.launch(dev, _lib.load().enf_fit_inputs_w, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(), img.data_ptr(),
+                masks.data_ptr(), xs.data_ptr(), ys.data_ptr(), losses.data_ptr(), weights.data_ptr() if weights is not None else None,
+                ws.data_ptr() if ws is not None else None, st)
+    return (lat, xs, ys, losses) if weights is None else (lat, xs, ys, losses, ws)
 
 
 def _pose(lat, num_ori_dims):
@@ -85,7 +89,7 @@ def meta_sgd_update(lat, grads, lrs, scale):
 
 
 def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
-               noise_pos=0.0, generator=None):
+               noise_pos=0.0, generator=None, weights=None):
     """Fit per-signal latents with S steps of meta-SGD (pde_trainer.py:156-235).
 
     latents0 : {'p_pos','a','gaussian_window'[,'p_ori']} with leading dim 1 (the meta-init)
@@ -94,22 +98,31 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     Each step is one HIP forward, the fused loss/d-out kernel and one HIP backward-to-latents
     (nef.mse_value_and_latent_grads: no autograd graph); the gradient of the batch-mean loss is multiplied by B
     (pde_trainer.py:207) so signals are independent.
+    weights  : None, or (B, N) loss weights on the full grid, finite and >= 0 (fitting/weights.py; taken as they are -- the trainers
+               normalise them to mean 1 per signal first).  They are gathered with the targets and weigh every step's loss and
+               the final one; a point of weight 0 does not exist, its target may be NaN.
     Returns (loss on the last mask, fitted latents dict with leading dim B).
     """
     B = img.shape[0]
     S = masks.shape[1] - 1
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    fused = _fit_inputs(latents0, coords, img, masks) if FUSED_FIT_INPUTS else None
+    if weights is not None:
+        if tuple(weights.shape) != tuple(img.shape[:2]):
+            raise ValueError(f"weights have shape {tuple(weights.shape)}, expected {tuple(img.shape[:2])}")
+        weights = weights.to(device=img.device, dtype=torch.float32).contiguous()
+    fused = _fit_inputs(latents0, coords, img, masks, weights) if FUSED_FIT_INPUTS else None
     if fused is not None:
         # the signals' copies of the latent initialisation (pde_trainer.py:157-159), the coordinates and targets of all S+1 steps
         # gathered once (:193-197) and the zeroed loss accumulators: ONE launch (enf_fit_inputs) instead of eight framework kernels
-        lat, xs_all, ys_all, losses = fused
+        lat, xs_all, ys_all, losses = fused[:4]
+        ws_all = fused[4] if weights is not None else None
     else:
         lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}       # pde_trainer.py:157-159 (a fresh tensor)
         masks_t = masks.t().contiguous()                                     # (a gather inherits the strides of a transposed index)
         xs_all = coords[masks_t]                                             # (S+1, N_s, dx)
         ys_all = img[:, masks_t].transpose(0, 1).float().contiguous()        # (S+1, B, N_s, O)
         losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)  # one accumulator per step, zeroed in one fill
+        ws_all = gather_point_weights(weights, masks) if weights is not None else None      # (S+1, B, N_s)
     if noise_pos:                                                                             # pde_trainer.py:162-167
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
@@ -117,7 +130,8 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     for s in range(S):                                                  # pde_trainer.py:191
         xs = xs_all[s][None].expand(B, -1, -1)                          # stride-0 batch
         _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
-                                                         lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1])
+                                                         lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
+                                                         weight=None if ws_all is None else ws_all[s])
         # the gradient of the batch-mean loss times B (pde_trainer.py:206), scaled by the learned rates (:215-219);
         # sigma only moves when asked to (:209-212)
         grads = {"p_pos": dp[..., :n_pos], "a": da}
@@ -132,8 +146,12 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
         if out.shape != ys_all[S].shape:
             raise AssertionError(f"targets have shape {tuple(ys_all[S].shape)}, expected {tuple(out.shape)}")
-        _lib.launch(out.device, _lib.load().enf_mse_value_grad, out.data_ptr(), ys_all[S].data_ptr(), out.numel(), 1.0, None,
-                    losses[S:].data_ptr(), st)
+        if ws_all is None:
+            _lib.launch(out.device, _lib.load().enf_mse_value_grad, out.data_ptr(), ys_all[S].data_ptr(), out.numel(), 1.0, None,
+                        losses[S:].data_ptr(), st)
+        else:
+            _lib.launch(out.device, _lib.load().enf_mse_value_grad_w, out.data_ptr(), ys_all[S].data_ptr(), ws_all[S].data_ptr(),
+                        out.numel(), out.shape[-1], 1.0, None, losses[S:].data_ptr(), None, 0, 0, st)
     return losses[S], lat
 
 

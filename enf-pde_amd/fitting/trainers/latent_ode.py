@@ -9,6 +9,7 @@ from the inner loop, the auto-decoder trainer from its latent table; from there 
 import torch
 
 from ..inner_loop import _pose
+from ..weights import normalize_point_weights, prepare_point_weights, weighted_mse
 from .trainer_utils.solvers import solve_latent_ode
 
 
@@ -35,16 +36,34 @@ def draw_point_masks(num_points, num_sampled, num_frames, generator=None, device
     return masks if device is None else masks.to(device)
 
 
-def sample_frames(coords, traj, point_masks=None):
+def sample_frames(coords, traj, point_masks=None, weights=None):
     """Queries and targets of the B T signal-frames: ``coords`` (N, dx), ``traj`` (B, T, N, O), ``point_masks`` (T, n_s) long or
-    None for the full grid.  Returns xs (B T, n, dx) and ys (B T, n, O), signal-major like the flattened roll-out."""
+    None for the full grid.  Returns xs (B T, n, dx) and ys (B T, n, O), signal-major like the flattened roll-out; with
+    ``weights`` (B, T, N) also their gather ws (B T, n)."""
     B, T, N, O = traj.shape
     if point_masks is None:
-        return coords[None].expand(B * T, -1, -1), traj.reshape(B * T, N, O)
+        xs, ys = coords[None].expand(B * T, -1, -1), traj.reshape(B * T, N, O)
+        return (xs, ys) if weights is None else (xs, ys, weights.reshape(B * T, N))
     n_s = point_masks.shape[1]
     xs = coords[point_masks][None].expand(B, -1, -1, -1).reshape(B * T, n_s, -1)
     ys = torch.gather(traj, 2, point_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n_s, O)
-    return xs, ys
+    if weights is None:
+        return xs, ys
+    return xs, ys, torch.gather(weights, 2, point_masks[None].expand(B, -1, -1)).reshape(B * T, n_s)
+
+
+def frame_weights(weights, B, T, N, normalize=True, device=None):
+    """``weights`` (N,), (B, N) or (B, T, N) -> float32 (B, T, N), every signal-frame's weights of mean 1 over the full grid
+    unless ``normalize`` is False (fitting/weights.py); None stays None."""
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights, dtype=torch.float32)
+    if w.dim() == 3:
+        if tuple(w.shape) != (B, T, N):
+            raise ValueError(f"weights have shape {tuple(w.shape)}, expected {(B, T, N)}, {(B, N)} or {(N,)}")
+        w = normalize_point_weights(w) if normalize else w
+        return w.to(device) if device is not None else w
+    return prepare_point_weights(w, B, N, normalize, device)[:, None].expand(B, T, N)
 
 
 class LatentODEMixin:
@@ -101,10 +120,13 @@ class LatentODEMixin:
             return self._ode_static_leaves(ode_params), True
         return [t.detach().requires_grad_(True) for t in _leaves(ode_params)], False
 
-    def rollout_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False):
+    def rollout_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False, weights=None,
+                     normalize=True):
         """Roll ``lat`` out over the frames of ``trajectory`` (B, T, *grid, O), decode every frame in ONE nef.apply over the
         B T signal-frames (at ``max_num_sampled_points`` random grid points per frame when the grid is larger) and return the
-        mean squared error.  ``point_masks`` (T, n_s) long, or None to draw them from ``generator``."""
+        mean squared error.  ``point_masks`` (T, n_s) long, or None to draw them from ``generator``.
+        ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1
+        per signal-frame before the points are sampled unless ``normalize`` is False; they are gathered with the point masks."""
         B, T = trajectory.shape[:2]
         sol = self.rollout(ode_params, lat, T, graph=graph)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
@@ -115,6 +137,10 @@ class LatentODEMixin:
                 point_masks = draw_point_masks(N, n_s, T, generator, self.coords.device)
         else:
             point_masks = None
-        xs, ys = sample_frames(self.coords, traj, point_masks)
+        if weights is None:
+            xs, ys = sample_frames(self.coords, traj, point_masks)
+            recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
+            return ((recon - ys) ** 2).mean()
+        xs, ys, ws = sample_frames(self.coords, traj, point_masks, frame_weights(weights, B, T, N, normalize, traj.device))
         recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
-        return ((recon - ys) ** 2).mean()
+        return weighted_mse(recon, ys, ws)

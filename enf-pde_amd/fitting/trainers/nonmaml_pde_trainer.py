@@ -30,7 +30,8 @@ import torch
 from ..optim import Adam, AdamW, clip_by_global_norm, global_norm
 from ..parallel import allreduce_mean_
 from ..inner_loop import decode
-from .latent_ode import LatentODEMixin, _leaves, _unflatten
+from ..weights import prepare_point_weights, weighted_mse
+from .latent_ode import LatentODEMixin, frame_weights, _leaves, _unflatten
 from .pde_trainer import _tree_from_tensors
 
 TRAIN_FRAMES, VAL_FRAMES = 10, 20            # fixed in the reference (:206,241,252), not read from the dataset config
@@ -97,17 +98,22 @@ class NonMetaPDETrainer(LatentODEMixin):
         state, epoch, _ = load_train_state(path, self.init_train_state(**init_kwargs))
         return state, epoch
 
-    def loss_and_grads(self, state, initial_state, traj_idx, mask=None):
-        """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table)."""
+    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True):
+        """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
+        ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
+        before ``mask`` and the point sampling unless ``normalize`` is False."""
         cfg = self.config
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
+        pw = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
         if mask is not None:                                                              # :321-323
             img, coords = img[:, mask], coords[mask]
+            pw = None if pw is None else pw[:, mask]
         npts = cfg.training.max_num_sampled_points
         if npts < coords.shape[0]:                                                        # :326-335
             sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
             img, coords = img[:, sub], coords[sub]
+            pw = None if pw is None else pw[:, sub]
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
@@ -115,15 +121,15 @@ class NonMetaPDETrainer(LatentODEMixin):
         p, a, window = self.autodecoder.apply({"params": leaves}, traj_idx)               # :338
         xs = coords[None].expand(img.shape[0], -1, -1)
         out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
-        loss = ((out - img) ** 2).mean()
+        loss = ((out - img) ** 2).mean() if pw is None else weighted_mse(out, img, pw)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)
         gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
         ga = [torch.zeros_like(leaves[k]) if gi is None else gi for k, gi in zip(names, g[len(w):])]
         return loss.detach(), gw, dict(zip(names, ga))
 
-    def _step(self, state, batch, mask, update_nef):
+    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True):
         initial_state, traj_idx = batch
-        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask)
+        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize)
         names = list(ga.keys())
         flat = gw + [ga[k] for k in names] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=initial_state.shape[0])
@@ -139,13 +145,13 @@ class NonMetaPDETrainer(LatentODEMixin):
         return loss, NonMetaTrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state,
                                        ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def nef_train_step(self, state, batch, mask=None):
-        """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137)"""
-        return self._step(state, batch, mask, True)
+    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True):
+        """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137); ``weights`` as in loss_and_grads"""
+        return self._step(state, batch, mask, True, weights, normalize)
 
-    def nef_train_step_autodec_only(self, state, batch, mask=None):
+    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True):
         """Only the latents move (:139-171)."""
-        return self._step(state, batch, mask, False)
+        return self._step(state, batch, mask, False, weights, normalize)
 
     # ------------------------------------------------------------------ latent-ODE phase (:173-307)
     def _need_ode(self, what):
@@ -153,16 +159,19 @@ class NonMetaPDETrainer(LatentODEMixin):
             raise ValueError(f"NonMetaPDETrainer.{what} needs a latent ODE: build the trainer with ode_model=... "
                              "(the second value of get_model_pde(cfg))")
 
-    def ode_loss(self, params, trajectory, traj_idx, point_masks=None, generator=None, graph=False):
+    def ode_loss(self, params, trajectory, traj_idx, point_masks=None, generator=None, graph=False, weights=None, normalize=True):
         """:244-307.  The first 10 frames of ``trajectory`` (B, T, *grid, O) against the roll-out of the table rows ``traj_idx``
         (B,) long, decoded at ``point_masks`` (frames, n_s) long -- one permutation of the grid per frame, shared by the signals of
         the batch; drawn from ``generator`` when None and max_num_sampled_points is smaller than the grid."""
         self._need_ode("ode_loss")
         trajectory = trajectory[:, :TRAIN_FRAMES]                                # :252
+        if weights is not None and torch.as_tensor(weights).dim() == 3:          # (B, T, N): the frames the loss sees
+            weights = torch.as_tensor(weights)[:, :TRAIN_FRAMES]
         z0 = self.autodecoder.apply(params["autodecoder"], traj_idx)             # :255
-        return self.rollout_loss(params["nef"], params["ode_params"], z0, trajectory, point_masks, generator, graph=graph)
+        return self.rollout_loss(params["nef"], params["ode_params"], z0, trajectory, point_masks, generator, graph=graph,
+                                 weights=weights, normalize=normalize)
 
-    def ode_train_step(self, state, batch, point_masks=None):
+    def ode_train_step(self, state, batch, point_masks=None, weights=None, normalize=True):
         """:173-199: one clip_by_global_norm(1) + AdamW step on the ODE parameters only.  ``batch`` = (trajectory (B, T, *grid, O),
         trajectory indices (B,) long) or the reference's (trajectory, _, traj_idx): the trajectory is ``batch[0]`` and the indices
         are ``batch[-1]``, whatever lies between is ignored.  nef weights, the latent table and their optimiser states are handed
@@ -182,7 +191,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         P = state.params["autodecoder"]["params"]
         params = {"nef": state.params["nef"], "autodecoder": {"params": {k: v.detach() for k, v in P.items()}},
                   "ode_params": _unflatten(state.params["ode_params"], leaves)}
-        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph)
+        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph, weights=weights, normalize=normalize)
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
         grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
         flat = grads + [loss.detach().reshape(1)]
@@ -199,7 +208,7 @@ class NonMetaPDETrainer(LatentODEMixin):
                                               step=state.step + 1, rng=state.rng)
 
     @torch.no_grad()
-    def val_step(self, state, batch, autodecoder=None):
+    def val_step(self, state, batch, autodecoder=None, weights=None, normalize=True):
         """:201-241: ``batch`` = (trajectory, traj_idx) or (trajectory, _, traj_idx), read as ``batch[0]`` and ``batch[-1]`` like
         ode_train_step's.  The first 20 frames against the roll-out of the rows ``traj_idx`` of ``state.params['autodecoder']``, read
         through ``autodecoder`` (a shell for validation signals; default: the trainer's own), decoded on the full grid in chunks of
@@ -214,8 +223,17 @@ class NonMetaPDETrainer(LatentODEMixin):
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl,
                        chunk=self.config.training.max_num_sampled_points).reshape(trajectory.shape)    # :228-238
-        err = (recon - trajectory) ** 2
-        return err[:, :TRAIN_FRAMES].mean(), (err[:, TRAIN_FRAMES:].mean() if T > TRAIN_FRAMES else err.new_zeros(()))
+        if weights is None:
+            err = (recon - trajectory) ** 2
+            return err[:, :TRAIN_FRAMES].mean(), (err[:, TRAIN_FRAMES:].mean() if T > TRAIN_FRAMES else err.new_zeros(()))
+        # (N,) / (B, N) / (B, T, N) weights on the full grid: the pair is (weighted mse over frames 0..9, weighted mse beyond)
+        N, O = self.coords.shape[0], trajectory.shape[-1]
+        if torch.as_tensor(weights).dim() == 3:
+            weights = torch.as_tensor(weights)[:, :T]
+        fw = frame_weights(weights, B, T, N, normalize, recon.device)
+        rec, tgt, F = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O), TRAIN_FRAMES
+        return weighted_mse(rec[:, :F], tgt[:, :F], fw[:, :F]), \
+            (weighted_mse(rec[:, F:], tgt[:, F:], fw[:, F:]) if T > F else recon.new_zeros(()))
 
     def select_train_step(self, epoch):
         """The step of ``epoch`` by the windows of _base_pde_trainer.py:280-289: nef while training.nef.train_from_epoch < epoch

@@ -43,9 +43,10 @@ from types import SimpleNamespace
 import torch
 
 from ..inner_loop import _pose, make_masks, inner_loop, decode
-from .latent_ode import LatentODEMixin, draw_point_masks, _leaves, _unflatten
+from .latent_ode import LatentODEMixin, draw_point_masks, frame_weights, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
+from ..weights import prepare_point_weights, weighted_mse
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
@@ -62,33 +63,35 @@ def _tree_from_tensors(tensors, nef=None):
     return {"params": out}
 
 
-def _loss(nef, params, coords, img, masks, s, lat):
+def _loss(nef, params, coords, img, masks, s, lat, weights=None):
     B = img.shape[0]
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
     xs = coords[masks[:, s]][None].expand(B, -1, -1)                    # pde_trainer.py:193-197
     ys = img[:, masks[:, s]]
     out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
-    return ((out - ys) ** 2).mean()                                     # pde_trainer.py:185
+    if weights is None:
+        return ((out - ys) ** 2).mean()                                 # pde_trainer.py:185
+    return weighted_mse(out, ys, weights[:, masks[:, s]])               # (fitting/weights.py: the per-point weighted form)
 
 
-def _latent_grads(nef, params, coords, img, masks, s, lat, keys):
+def _latent_grads(nef, params, coords, img, masks, s, lat, keys, weights=None):
     leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
-    g = torch.autograd.grad(_loss(nef, params, coords, img, masks, s, leaves), [leaves[k] for k in keys], allow_unused=True)
+    g = torch.autograd.grad(_loss(nef, params, coords, img, masks, s, leaves, weights), [leaves[k] for k in keys], allow_unused=True)
     return {k: (torch.zeros_like(lat[k]) if gk is None else gk) for k, gk in zip(keys, g)}
 
 
-def _full_grads(nef, weights, coords, img, masks, s, lat, keys):
+def _full_grads(nef, weights, coords, img, masks, s, lat, keys, point_weights=None):
     """(loss, grads w.r.t. the 46 weight tensors, grads w.r.t. the latents) on the training path."""
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
-    loss = _loss(nef, _tree_from_tensors(w, nef), coords, img, masks, s, leaves)
+    loss = _loss(nef, _tree_from_tensors(w, nef), coords, img, masks, s, leaves, point_weights)
     g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
     gl = {k: (torch.zeros_like(lat[k]) if gi is None else gi) for k, gi in zip(keys, g[len(w):])}
     return loss.detach(), gw, gl
 
 
-def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf=None):
+def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf=None, point_weights=None):
     """grads(plus) - grads(minus) of the step-s loss, w.r.t. the weights and the latents, in ONE training-path pass: the two
     latent sets run as one batch of 2B signals whose second half enters the loss with a minus sign (the outer step is
     bound by its many small kernels, so one pass of twice the batch costs about half of two passes)."""
@@ -101,7 +104,11 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     import contextlib
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
         out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
-        loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
+        if point_weights is None:
+            loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
+        else:
+            pw = point_weights[:, masks[:, s]]
+            loss = weighted_mse(out[:B], ys, pw) - weighted_mse(out[B:], ys, pw)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
     gl = {k: (torch.zeros_like(plus[k]) if gi is None else gi[:B] + gi[B:]) for k, gi in zip(keys, g[len(w):])}
@@ -109,7 +116,8 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
 
 
 def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
-                   second_order="fd", fd_step=None, noise_pos=0.0, generator=None, terminal=None, freeze_relu=True):
+                   second_order="fd", fd_step=None, noise_pos=0.0, generator=None, terminal=None, freeze_relu=True,
+                   weights=None, normalize=True):
     """Value and gradient of the last-inner-step loss w.r.t. (nef weights, meta-init latents, inner lrs).
 
     Returns (loss, grads) with grads = {'nef': [46 tensors in ENF_W_* order], 'autodecoder': {key: (1,Z,.)},
@@ -118,6 +126,8 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     ``freeze_relu``: take the finite differences with the relu masks frozen at the unperturbed latents (module docstring).
     ``terminal(weights, lat, keys) -> (loss, d loss/d weights, {key: d loss/d lat[key]})`` replaces the objective on
     the fitted latents (default: the reconstruction loss on the last mask); dual_train_step passes the roll-out loss.
+    ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
+    unless ``normalize`` is False; they weigh every inner step's loss and the default terminal loss.
     """
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
@@ -125,6 +135,7 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
         fd_step = 2e-2 if getattr(nef, "precision", "f32") in ("bf16", "bfloat16") else 5e-3      # are 100x noisier
     B = img.shape[0]
     S = masks.shape[1] - 1
+    pw = prepare_point_weights(weights, B, img.shape[1], normalize, img.device)
     weights = nef.param_tensors(nef_params)
     frozen = _tree_from_tensors([t.detach() if t is not None else None for t in weights], nef)           # inference path for the inner steps
     lat = {k: v.detach().repeat_interleave(B, dim=0).clone() for k, v in latents0.items()}
@@ -143,14 +154,14 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
         # (the forward of this pass also records the relu masks at phi_s for the adjoint sweep's frozen-mask differences)
         relu_bufs.append(nef.relu_mask_buffer(B, masks.shape[0], lat["a"].shape[1], coords.device) if freeze else None)
         with (nef.relu_masks(relu_bufs[s], "write", B) if freeze else contextlib.nullcontext()):
-            g = _latent_grads(nef, frozen, coords, img, masks, s, lat, keys)
+            g = _latent_grads(nef, frozen, coords, img, masks, s, lat, keys, pw)
         g = {k: (torch.zeros_like(lat[k]) if (k not in g or masked(k)) else g[k] * B) for k in lat}    # pde_trainer.py:207
         phis.append(lat)
         gs.append(g)
         lat = {k: (lat[k] - lrs[k] * g[k]).detach() for k in lat}                                       # pde_trainer.py:215-219
     # ---- last step: value, d/d theta, lambda_S
     if terminal is None:
-        loss, g_theta, lam = _full_grads(nef, weights, coords, img, masks, S, lat, keys)
+        loss, g_theta, lam = _full_grads(nef, weights, coords, img, masks, S, lat, keys, pw)
     else:
         loss, g_theta, lam = terminal(weights, lat, keys)
     lam = {k: lam.get(k, torch.zeros_like(lat[k])) for k in lat}
@@ -173,7 +184,7 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
         # with the relu masks AT phi_s both perturbed passes differentiate the same piecewise-linear branch, so their
         # difference is the almost-everywhere second derivative (what jax.grad of the inner steps computes) instead of
         # also counting the units that flip between phi_s - eps w and phi_s + eps w
-        gw_d, gl_d = _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_bufs[s])
+        gw_d, gl_d = _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_bufs[s], pw)
         c = B / (2.0 * eps)                                                     # a 0-dim device tensor
         g_theta = list(torch._foreach_sub(g_theta, torch._foreach_mul(gw_d, c)))
         lam = {k: lam[k] - c * gl_d[k] if k in gl_d else lam[k] for k in lam}
@@ -259,8 +270,9 @@ class MetaSGDPDETrainer(LatentODEMixin):
         keys = [k for k in LATENT_KEYS if k in P and not (k == "p_ori" and self.outer_autodecoder.num_ori_dims == 0)]
         return {k: P[k] for k in keys}
 
-    def nef_train_step(self, state, batch, masks=None):
+    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True):
         """One outer step on ``batch`` = (B, N, O) initial states (trajectory[:, 0], pde_trainer.py:485-487).
+        ``weights``: None, or (N,) / (B, N) loss weights on the full grid (meta_gradients).
         Returns (recon_loss, new_state).  In a multi-rank run every rank passes its shard of the meta-batch;
         the outer gradients are averaged with one flat all-reduce before the (identical) optimiser updates."""
         cfg = self.config
@@ -273,7 +285,8 @@ class MetaSGDPDETrainer(LatentODEMixin):
         loss, grads = meta_gradients(self.nef, state.params["nef"], lat0, lrs, self.coords, img, masks,
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
-                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng)
+                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng,
+                                     weights=weights, normalize=normalize)
         lat_keys, lr_keys = list(lat0.keys()), list(lrs.keys())
         flat = grads["nef"] + [grads["autodecoder"][k] for k in lat_keys] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])                               # one exchange per outer step
@@ -336,43 +349,60 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return out
 
     # ------------------------------------------------------------------ latent-ODE phase (pde_trainer.py:290-500)
-    def _fit_initial_latents(self, state, initial_state, masks=None, initial_state_dp=0.0):
-        """inner_loop on the first frame of every trajectory (pde_trainer.py:424-427): fitted latents, leading dim B."""
+    def _fit_initial_latents(self, state, initial_state, masks=None, initial_state_dp=0.0, weights=None):
+        """What inner_loop takes for the first frame of every trajectory (pde_trainer.py:424-427): (coords, img, masks), and with
+        ``weights`` (B, N) a fourth value, the weights of the same point subset."""
         cfg = self.config
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
         if initial_state_dp > 0:                                                  # pde_trainer.py:139-145
             keep = torch.randperm(coords.shape[0], generator=state.rng)[:int(coords.shape[0] * initial_state_dp)].to(coords.device)
             coords, img = coords[keep], img[:, keep]
+            if weights is not None:
+                weights = weights[:, keep].contiguous()
         if masks is None:
             masks = make_masks(coords.shape[0], cfg.training.max_num_sampled_points, cfg.meta.num_inner_steps,
                                generator=state.rng, device=coords.device)
-        return coords, img, masks
+        return (coords, img, masks) if weights is None else (coords, img, masks, weights)
 
-    def ode_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False):
+    def ode_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False, weights=None,
+                 normalize=True):
         """pde_trainer.py:411-481 from the fitted latents on: roll the latents out over the training frames, decode every
         frame (at ``max_num_sampled_points`` random grid points per frame when the grid is larger) and compare.
         ``trajectory`` (B, T, *grid, O);  ``point_masks`` (T, n_s) long, or None to draw them.  The arithmetic (and
-        ``rollout``) is latent_ode.LatentODEMixin's, shared with the auto-decoder trainer."""
-        return self.rollout_loss(nef_params, ode_params, lat, trajectory, point_masks, generator, graph=graph)
+        ``rollout``) is latent_ode.LatentODEMixin's, shared with the auto-decoder trainer; ``weights`` as in rollout_loss."""
+        return self.rollout_loss(nef_params, ode_params, lat, trajectory, point_masks, generator, graph=graph, weights=weights,
+                                 normalize=normalize)
 
-    def _fitted(self, state, trajectory, masks):
+    @staticmethod
+    def _frame0_weights(weights, B, N, normalize, device):
+        """The weights of the fit on frame 0, (B, N) float32 or None, from (N,), (B, N) or (B, T, N) ``weights``."""
+        if weights is not None and torch.as_tensor(weights).dim() == 3:
+            weights = torch.as_tensor(weights)[:, 0]
+        return prepare_point_weights(weights, B, N, normalize, device)
+
+    def _fitted(self, state, trajectory, masks, weights=None):
         coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks)
         cfg = self.config
         _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
                             optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
-                            noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng)
+                            noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, weights=weights)
         return {k: v.detach() for k, v in lat.items()}
 
-    def ode_train_step(self, state, trajectory, masks=None, point_masks=None):
+    def ode_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True):
         """pde_trainer.py:290-318: one Adam step on the ODE parameters only.  The fitted latents do not depend on them, so
-        the inner loop runs without a graph; the gradient flows decoder -> (HIP latent backward) -> solver -> ODE model."""
+        the inner loop runs without a graph; the gradient flows decoder -> (HIP latent backward) -> solver -> ODE model.
+        ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid: frame 0's weigh the fit, all the roll-out loss."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]                  # pde_trainer.py:421-422
-        lat = self._fitted(state, trajectory, masks)
+        if weights is not None and torch.as_tensor(weights).dim() == 3:
+            weights = torch.as_tensor(weights)[:, :cfg.dataset.traj_len_train]
+        lat = self._fitted(state, trajectory, masks,
+                           self._frame0_weights(weights, trajectory.shape[0], self.coords.shape[0], normalize, self.coords.device))
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
-        loss = self.ode_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph)
+        loss = self.ode_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
+                             normalize=normalize)
         grads = list(torch.autograd.grad(loss, leaves, allow_unused=True))
         grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
         flat = grads + [loss.detach().reshape(1)]
@@ -383,13 +413,15 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                        autodecoder_opt_state=state.autodecoder_opt_state, meta_sgd_opt_state=state.meta_sgd_opt_state,
                                        ode_opt_state=ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def dual_train_step(self, state, trajectory, masks=None, point_masks=None):
+    def dual_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True):
         """pde_trainer.py:320-358: the roll-out loss trains the nef weights (clip + AdamW), the inner learning rates (Adam,
         clipped) and the ODE parameters (Adam); the latent initialisation is left alone.  The nef / learning-rate
         gradients include the path through the inner loop (the same adjoint recursion as nef_train_step, started from
-        d loss / d fitted latents of the roll-out)."""
+        d loss / d fitted latents of the roll-out).  ``weights`` as in ode_train_step."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]
+        if weights is not None and torch.as_tensor(weights).dim() == 3:
+            weights = torch.as_tensor(weights)[:, :cfg.dataset.traj_len_train]
         coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks)
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
@@ -397,11 +429,13 @@ class MetaSGDPDETrainer(LatentODEMixin):
             point_masks = draw_point_masks(self.coords.shape[0], cfg.training.max_num_sampled_points, trajectory.shape[1],
                                            state.rng, self.coords.device)
         side = {}
+        point_weights = weights             # (`weights` below are the network's)
 
         def terminal(weights, lat, keys):
             w = [t.detach().requires_grad_(True) for t in weights]
             lv = {k: lat[k].detach().requires_grad_(True) for k in lat}
-            loss = self.ode_loss(_tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph)
+            loss = self.ode_loss(_tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph,
+                                 weights=point_weights, normalize=normalize)
             g = torch.autograd.grad(loss, w + [lv[k] for k in keys] + leaves, allow_unused=True)
             z = lambda t, gi: torch.zeros_like(t) if gi is None else gi
             side["ode"] = [z(t, gi) for t, gi in zip(leaves, g[len(w) + len(keys):])]
@@ -412,7 +446,9 @@ class MetaSGDPDETrainer(LatentODEMixin):
         loss, grads = meta_gradients(self.nef, state.params["nef"], self._latents0(state), lrs, coords, img, masks,
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
-                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal)
+                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal,
+                                     weights=self._frame0_weights(point_weights, img.shape[0], img.shape[1], normalize, img.device),
+                                     normalize=False)
         lr_keys = list(lrs.keys())
         flat = grads["nef"] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + side["ode"] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])
@@ -463,19 +499,34 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return total / max(n, 1), state
 
     @torch.no_grad()
-    def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None):
+    def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True):
         """pde_trainer.py:360-409: fit the first frame, roll out over train + out-of-horizon frames, decode the full grid;
-        returns (mse over the training horizon, mse beyond it)."""
+        returns (mse over the training horizon, mse beyond it).  ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on
+        the full grid (fitting/weights.py; mean 1 per signal-frame unless ``normalize`` is False): frame 0's weigh the fit, and
+        the pair returned is (weighted mse over the training horizon, weighted mse beyond it)."""
         cfg = self.config
         T_in = cfg.dataset.traj_len_train
         trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
         B, T = trajectory.shape[:2]
-        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp)
+        N = self.coords.shape[0]
+        if weights is not None and torch.as_tensor(weights).dim() == 3:
+            weights = torch.as_tensor(weights)[:, :T]
+        w0 = self._frame0_weights(weights, B, N, normalize, self.coords.device)
+        if w0 is None:
+            coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp)
+        else:
+            coords, img, masks, w0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, w0)
         with torch.enable_grad():
             _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
-                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False))
+                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), weights=w0)
         sol = self.rollout(state.params["ode_params"], {k: v.detach() for k, v in lat.items()}, T, graph=T > 4)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl).reshape(trajectory.shape)
-        err = (recon - trajectory) ** 2
-        return err[:, :T_in].mean(), (err[:, T_in:].mean() if T > T_in else err.new_zeros(()))
+        if weights is None:
+            err = (recon - trajectory) ** 2
+            return err[:, :T_in].mean(), (err[:, T_in:].mean() if T > T_in else err.new_zeros(()))
+        O = trajectory.shape[-1]
+        fw = frame_weights(weights, B, T, N, normalize, recon.device)
+        rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
+        return weighted_mse(rec[:, :T_in], tgt[:, :T_in], fw[:, :T_in]), \
+            (weighted_mse(rec[:, T_in:], tgt[:, T_in:], fw[:, T_in:]) if T > T_in else recon.new_zeros(()))

@@ -324,6 +324,20 @@ int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const f
                     const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
                     void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
 
+/* Weighted loss (enf_fit_step_w, enf_mse_value_grad_w, enf_fit_inputs_w).  `weight` is fp32 of shape (B, N): one value per signal
+ * and query point, finite and >= 0, or NULL for the unweighted calls above.
+ *     loss  = 1 / (B N O) * sum_{b,n} weight[b,n] * sum_o (out[b,n,o] - target[b,n,o])^2
+ *     d out = 2 * weight[b,n] * (out - target) / (B N O) * grad_scale
+ * With weight == 1 everywhere this is the unweighted loss.  The library does NOT normalise the weights (no reduction pass over
+ * them: a call stays a pure function of its arguments); a caller who wants a weighted MEAN passes weights of mean 1.
+ * A point with weight == 0 does not exist: its `target` values are never used in arithmetic and may be NaN or Inf, and its
+ * contribution to the loss and to d out is exactly 0.0f (not 0 * NaN) -- weight = isfinite(field) is usable as it stands.
+ * A signal whose weights are all zero adds 0 to the loss and gets zero gradients; it is not an error.
+ * Flags, workspace and scratch sizes are those of the unweighted calls; with weight == NULL the arithmetic is theirs, bit for bit. */
+int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                   const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                   void* workspace, size_t workspace_bytes, const float* weight /* (B,N) or NULL */, unsigned flags, void* stream);
+
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
@@ -334,6 +348,11 @@ int enf_mse_value_grad(const float* out, const float* target, size_t n, float gr
 size_t enf_mse_scratch_bytes(size_t n, unsigned flags);
 int enf_mse_value_grad_ex(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
                           void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
+
+/* The same with the weighted loss above: `weight` holds one value per O consecutive elements (n / O of them; n % O != 0 is
+ * ENF_EINVAL), or NULL (then O only has to divide n). */
+int enf_mse_value_grad_w(const float* out, const float* target, const float* weight /* (n / O) or NULL */, size_t n, int32_t O,
+                         float grad_scale, float* dout, float* loss, void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
 
 /* The meta-SGD update of one inner step for all latent components in one launch (pde_trainer.py:206-219):
  *     out = x - lr * (scale * g)        scale = the batch size (:206); lr broadcasts over the leading dims
@@ -364,6 +383,13 @@ typedef struct EnfFitComponent {
 } EnfFitComponent;
 int enf_fit_inputs(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx, int32_t O,
                    const float* coords, const float* img, const int64_t* masks, float* xs, float* ys, float* losses, void* stream);
+/* The same, plus the loss weights of the S1 sampled sets gathered in the same launch:
+ *       ws[s, b, i] = weight[b, masks[i, s]]     (S1, B, Ns)       weight (B, N)
+ * (a plain copy: the NaN targets of zero-weight points pass through `ys` untouched).  weight and ws are given together or both
+ * NULL (= enf_fit_inputs); one without the other is ENF_EINVAL. */
+int enf_fit_inputs_w(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx, int32_t O,
+                     const float* coords, const float* img, const int64_t* masks, float* xs, float* ys, float* losses,
+                     const float* weight /* (B,N) or NULL */, float* ws /* (S1,B,Ns) */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
