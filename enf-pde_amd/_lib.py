@@ -22,7 +22,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_workspace_bytes_ex", "enf_fit_step_ex", "enf_mse_value_grad_ex", "enf_mse_scratch_bytes", "enf_pair_backward_ex2",
            "enf_pair_backward_scratch_bytes", "enf_backward_all_scratch_bytes_ex", "enf_backward_weights_ex",
            "enf_backward_weights_scratch_bytes_ex",
-           "enf_fit_step_w", "enf_mse_value_grad_w", "enf_fit_inputs_w",
+           "enf_fit_step_w", "enf_mse_value_grad_w", "enf_fit_inputs_w", "enf_fit_inputs_b",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
@@ -184,6 +184,8 @@ def _bind(path, test_hooks):
     lib.enf_fit_step_w.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, sz, vp, cu, vp]
     lib.enf_mse_value_grad_w.argtypes = [vp, vp, vp, sz, ctypes.c_int32, ctypes.c_float, vp, vp, vp, sz, cu, vp]
     lib.enf_fit_inputs_w.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 9
+    # per-signal index sets, masks (B, Ns, S1); ws may be given without weight (include/enf_hip.h: the index contract)
+    lib.enf_fit_inputs_b.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 9
     lib.enf_pair_backward_scratch_bytes.restype = sz
     lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]
     lib.enf_pair_backward_ex2.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]

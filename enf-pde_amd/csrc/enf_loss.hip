@@ -207,3 +207,61 @@ extern "C" int enf_fit_inputs_w(int ncomp, const EnfFitComponent* comps, int32_t
   hipLaunchKernelGGL(enf_fit_inputs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
+
+// enf_fit_inputs_b: the same setup for PER-SIGNAL index sets, masks (B, Ns, S1) (include/enf_hip.h).  A kernel of its own, so that the
+// shared-mask kernel above keeps its code object.  One thread per (s, b, i) row of the outputs: it reads its index once and copies the
+// dx coordinates, the O target values and the weight of that point; consecutive threads write consecutive rows of xs, ys and ws.  The
+// threads after the rows broadcast the latent components and zero the loss accumulators.  An index outside [0, N) is never used as an
+// offset: its row is coords[0], zero targets and weight 0 -- by the weighted-loss contract the point does not exist.
+__global__ __launch_bounds__(256) void enf_fit_inputs_b_kernel(FitInArgs A) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nrow = (int64_t)A.S1 * A.B * A.Ns;
+  if (i < nrow) {
+    const int64_t q = i % A.Ns, r = i / A.Ns, b = r % A.B, s = r / A.B;
+    const int64_t m = A.masks[(b * A.Ns + q) * A.S1 + s];
+    const bool ok = m >= 0 && m < (int64_t)A.N;
+    const float* __restrict__ cx = A.coords + (ok ? m : (int64_t)0) * A.dx;
+    float* __restrict__ x = A.xs + i * A.dx;
+    for (int c = 0; c < A.dx; ++c) x[c] = cx[c];
+    float* __restrict__ y = A.ys + i * A.O;
+    if (ok) {
+      const float* __restrict__ im = A.img + (b * A.N + m) * A.O;
+      for (int o = 0; o < A.O; ++o) y[o] = im[o];
+      if (A.ws) A.ws[i] = A.weight ? A.weight[b * A.N + m] : 1.0f;
+    } else {
+      for (int o = 0; o < A.O; ++o) y[o] = 0.f;
+      if (A.ws) A.ws[i] = 0.f;
+    }
+    return;
+  }
+  i -= nrow;
+#pragma unroll
+  for (int k = 0; k < ENF_SGD_MAX_SEGMENTS; ++k) {
+    if (k < A.ncomp) {
+      const int64_t per = (int64_t)A.Z * A.comp[k].width, n = per * A.B;
+      if (i < n) { A.comp[k].dst[i] = A.comp[k].src[i % per]; return; }
+      i -= n;
+    }
+  }
+  if (i < A.S1) A.losses[i] = 0.f;
+}
+
+extern "C" int enf_fit_inputs_b(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx,
+                                int32_t O, const float* coords, const float* img, const int64_t* masks, float* xs, float* ys,
+                                float* losses, const float* weight, float* ws, void* stream) {
+  if (ncomp < 1 || ncomp > ENF_SGD_MAX_SEGMENTS || !comps || !coords || !img || !masks || !xs || !ys || !losses) return ENF_EINVAL;
+  if (!ws) return ENF_EINVAL;      // ws is what says that an index outside [0, N) does not exist; without weight it is 1 / 0
+  if (B < 1 || Z < 1 || N < 1 || Ns < 1 || S1 < 1 || dx < 1 || O < 1) return ENF_EDIM;
+  FitInArgs A{};
+  int64_t total = (int64_t)S1 * B * Ns + S1;
+  for (int k = 0; k < ncomp; ++k) {
+    if (!comps[k].src || !comps[k].dst || comps[k].width < 1) return ENF_EINVAL;
+    A.comp[k] = comps[k];
+    total += (int64_t)B * Z * comps[k].width;
+  }
+  if ((total + 255) / 256 > (int64_t)0x7fffffff) return ENF_EDIM;
+  A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = N; A.Ns = Ns; A.S1 = S1; A.dx = dx; A.O = O;
+  A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = weight; A.ws = ws;
+  hipLaunchKernelGGL(enf_fit_inputs_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+}

@@ -2,6 +2,7 @@
 
   get_model_pde(cfg)   experiments/fitting/__init__.py:14-65   (nef, ode_model)
   inner_loop(...)      trainers/pde_trainer.py:122-235         MAML inner loop: per-signal latent SGD
+  make_signal_masks    (no counterpart)                        per-signal point sets drawn from each signal's observed points
   decode(...)          trainers/pde_trainer.py:389-405         full-grid decode (chunking optional)
   shard_signals / allreduce_mean_   SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
@@ -11,12 +12,12 @@
   draw_point_masks     nonmaml_pde_trainer.py:273-283          per-frame point subsets of the roll-out loss (shared by both trainers)
 """
 from .model import get_model_pde
-from .inner_loop import inner_loop, decode, make_masks, default_meta_sgd_lrs
+from .inner_loop import inner_loop, decode, make_masks, make_signal_masks, default_meta_sgd_lrs
 from .parallel import shard_range, allreduce_mean_, init_distributed
 from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState, draw_point_masks
 from .trainers.trainer_utils import solve_latent_ode
 from .ode_models import PonitaODEGen, MLPODE
 
-__all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "default_meta_sgd_lrs", "shard_range",
+__all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_masks", "default_meta_sgd_lrs", "shard_range",
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks"]

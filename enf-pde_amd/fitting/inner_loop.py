@@ -23,26 +23,79 @@ def make_masks(num_coords, num_sampled, num_inner_steps, generator=None, device=
     return torch.stack(cols, dim=1).to(device)
 
 
+def make_signal_masks(weights_or_valid, num_sampled, num_inner_steps, generator=None, device="cuda"):
+    """(B, N_s, S+1) long: for every signal and step, N_s distinct indices drawn uniformly from that signal's observed set
+    {weights_or_valid[b] > 0} -- the per-signal counterpart of make_masks for fields observed at different places (sensor drop-out,
+    land masks, cloud gaps; fitting/weights.py: valid_weights).  A signal with fewer than N_s observed points gets them all, in random
+    order, followed by -1: enf_fit_inputs_b gives such a row weight 0, so it does not exist (include/enf_hip.h).
+    A draw from the observed set meets no zero-weight point, so full-grid weights of mean 1 no longer make the sampled loss an
+    estimate of the full-grid weighted mean: fit with fitting/weights.py: observed_sampling_weights(weights, N_s) to keep its scale.
+    Random fp64 keys, the unobserved points keyed to +inf, and the N_s smallest keys of every row; the keys are drawn where the
+    generator lives (the CPU without one), so a seed fixes the masks."""
+    valid = torch.as_tensor(weights_or_valid)
+    if valid.dim() != 2:
+        raise ValueError(f"weights_or_valid must be (B, N), got {tuple(valid.shape)}")
+    gdev = generator.device if generator is not None else torch.device("cpu")
+    observed = (valid > 0).to(gdev)
+    B, N = observed.shape
+    S1 = num_inner_steps + 1
+    keys = torch.rand((S1, B, N), generator=generator, dtype=torch.float64, device=gdev)
+    keys = keys.masked_fill(~observed[None], float("inf"))
+    k = min(int(num_sampled), N)
+    vals, idx = torch.topk(keys, k, dim=-1, largest=False, sorted=True)          # ascending: the +inf keys come last
+    idx = idx.masked_fill(torch.isinf(vals), -1)
+    if k < num_sampled:
+        idx = torch.cat((idx, idx.new_full((S1, B, int(num_sampled) - k), -1)), dim=-1)
+    return idx.permute(1, 2, 0).contiguous().to(device)
+
+
+def gather_signal_points(coords, img, masks, weights=None):
+    """What enf_fit_inputs_b gathers, in torch ops: coords (N, dx), img (B, N, O), masks (B, N_s, S1) long, weights (B, N) or None
+    -> xs (S1, B, N_s, dx), ys (S1, B, N_s, O), ws (S1, B, N_s).  An index outside [0, N) gives coords[0], zero targets and weight 0;
+    without ``weights`` ws is 1 for an index in range."""
+    B, N, O = img.shape
+    S1 = masks.shape[2]
+    idx = masks.permute(2, 0, 1)
+    ok = (idx >= 0) & (idx < N)
+    ic = torch.where(ok, idx, torch.zeros_like(idx))
+    xs = coords[ic]
+    ys = torch.gather(img[None].expand(S1, -1, -1, -1), 2, ic[..., None].expand(-1, -1, -1, O))
+    ys = torch.where(ok[..., None], ys, torch.zeros_like(ys))
+    w = torch.gather(weights[None].expand(S1, -1, -1), 2, ic) if weights is not None else torch.ones(ic.shape, device=img.device)
+    ws = torch.where(ok, w.float(), torch.zeros_like(w, dtype=torch.float32))
+    return xs.contiguous(), ys.float().contiguous(), ws.contiguous()
+
+
+def normalize_sampled_weights(ws):
+    """ws (..., N_s) >= 0 -> the same with mean 1 over every signal's N_s samples; a signal whose samples sum to zero stays zero."""
+    total = ws.sum(dim=-1, keepdim=True)
+    return torch.where(total > 0, ws * (ws.shape[-1] / torch.where(total > 0, total, torch.ones_like(total))), torch.zeros_like(ws))
+
+
 FUSED_FIT_INPUTS = __import__("os").environ.get("ENF_FIT_INPUTS") != "0"
 
 
 def _fit_inputs(latents0, coords, img, masks, weights=None):
     """enf_fit_inputs[_w] (include/enf_hip.h): (lat, xs_all, ys_all, losses) of inner_loop in one launch, or None where the
     arguments are not what the kernel takes (fp32, contiguous, on one GPU, at most four latent components of leading dimension 1).
-    With ``weights`` (B, N) a fifth value, their gather ws_all (S1, B, Ns)."""
+    With ``weights`` (B, N) a fifth value, their gather ws_all (S1, B, Ns).  Per-signal ``masks`` (B, Ns, S1) go to enf_fit_inputs_b:
+    xs_all is then (S1, B, Ns, dx) and ws_all is always returned."""
     ts = list(latents0.values()) + [coords, img] + ([weights] if weights is not None else [])
-    if not (img.is_cuda and masks.is_cuda and masks.dtype == torch.int64 and masks.dim() == 2 and masks.is_contiguous() and coords.dim() == 2
+    per_signal = masks.dim() == 3          # masks (B, Ns, S1): enf_fit_inputs_b, xs (S1, B, Ns, dx) and ws always (1 / 0 without weights)
+    if not (img.is_cuda and masks.is_cuda and masks.dtype == torch.int64 and masks.dim() in (2, 3) and masks.is_contiguous() and coords.dim() == 2
             and img.dim() == 3 and 1 <= len(latents0) <= _lib.ENF_SGD_MAX_SEGMENTS and masks.shape[0] > 0
             and all(t.dtype == torch.float32 and t.is_contiguous() and t.device == img.device for t in ts)
             and all(v.dim() == 3 and v.shape[0] == 1 for v in latents0.values())
             and len({v.shape[1] for v in latents0.values()}) == 1):
         return None
     B, N, O = img.shape
-    Ns, S1 = masks.shape
+    Ns, S1 = masks.shape[-2:]
+    if per_signal and masks.shape[0] != B:
+        return None
     Z = next(iter(latents0.values())).shape[1]
     dev = img.device
     lat = {k: torch.empty((B, Z, v.shape[2]), device=dev, dtype=torch.float32) for k, v in latents0.items()}
-    xs = torch.empty((S1, Ns, coords.shape[1]), device=dev, dtype=torch.float32)
+    xs = torch.empty((S1, B, Ns, coords.shape[1]) if per_signal else (S1, Ns, coords.shape[1]), device=dev, dtype=torch.float32)
     ys = torch.empty((S1, B, Ns, O), device=dev, dtype=torch.float32)
     losses = torch.empty(S1, device=dev, dtype=torch.float32)
     comps = (_lib.EnfFitComponent * _lib.ENF_SGD_MAX_SEGMENTS)()
@@ -52,7 +105,12 @@ def _fit_inputs(latents0, coords, img, masks, weights=None):
         keep.append(src)
         comps[i] = _lib.EnfFitComponent(src.data_ptr(), lat[k].data_ptr(), v.shape[2], 0)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    ws = torch.empty((S1, B, Ns), device=dev, dtype=torch.float32) if weights is not None else None
+    ws = torch.empty((S1, B, Ns), device=dev, dtype=torch.float32) if weights is not None or per_signal else None
+    if per_signal:
+        _lib.launch(dev, _lib.load().enf_fit_inputs_b, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(),
+                    img.data_ptr(), masks.data_ptr(), xs.data_ptr(), ys.data_ptr(), losses.data_ptr(),
+                    weights.data_ptr() if weights is not None else None, ws.data_ptr(), st)
+        return lat, xs, ys, losses, ws
     _lib.launch(dev, _lib.load().enf_fit_inputs_w, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(), img.data_ptr(),
                 masks.data_ptr(), xs.data_ptr(), ys.data_ptr(), losses.data_ptr(), weights.data_ptr() if weights is not None else None,
                 ws.data_ptr() if ws is not None else None, st)
@@ -89,22 +147,32 @@ def meta_sgd_update(lat, grads, lrs, scale):
 
 
 def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
-               noise_pos=0.0, generator=None, weights=None):
+               noise_pos=0.0, generator=None, weights=None, normalize_weights=False):
     """Fit per-signal latents with S steps of meta-SGD (pde_trainer.py:156-235).
 
     latents0 : {'p_pos','a','gaussian_window'[,'p_ori']} with leading dim 1 (the meta-init)
     lrs      : inner learning rates, same keys
-    coords   : (N, dx) grid;  img: (B, N, O) targets;  masks: (N_s, S+1) long
+    coords   : (N, dx) grid;  img: (B, N, O) targets;  masks: (N_s, S+1) long, one index set per step shared by the signals, or
+               (B, N_s, S+1) long, one per signal and step (make_signal_masks; enf_fit_inputs_b): every signal is then fitted on
+               its own points, x (B, N_s, dx) with a real batch stride.  There an index outside [0, N) -- the sampler's -1 padding
+               of a signal with fewer than N_s observed points -- has weight 0 and does not exist.
     Each step is one HIP forward, the fused loss/d-out kernel and one HIP backward-to-latents
     (nef.mse_value_and_latent_grads: no autograd graph); the gradient of the batch-mean loss is multiplied by B
     (pde_trainer.py:207) so signals are independent.
     weights  : None, or (B, N) loss weights on the full grid, finite and >= 0 (fitting/weights.py; taken as they are -- the trainers
                normalise them to mean 1 per signal first).  They are gathered with the targets and weigh every step's loss and
                the final one; a point of weight 0 does not exist, its target may be NaN.
+    normalize_weights : rescale every signal's sampled weights ws[s, b, :] to mean 1 over its N_s samples before each step (a zero
+               sum stays zero), so that a signal with few valid samples takes a step as long as a fully sampled one.  Off by
+               default: the loss is the library's un-normalised 1 / (B N_s O) sum, as with ``weights`` alone.  Needs sampled
+               weights (``weights`` or per-signal masks).
     Returns (loss on the last mask, fitted latents dict with leading dim B).
     """
     B = img.shape[0]
-    S = masks.shape[1] - 1
+    per_signal = masks.dim() == 3
+    if per_signal and masks.shape[0] != B:
+        raise ValueError(f"per-signal masks have shape {tuple(masks.shape)}, expected ({B}, N_s, S + 1)")
+    S = masks.shape[-1] - 1
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
     if weights is not None:
         if tuple(weights.shape) != tuple(img.shape[:2]):
@@ -115,7 +183,11 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         # the signals' copies of the latent initialisation (pde_trainer.py:157-159), the coordinates and targets of all S+1 steps
         # gathered once (:193-197) and the zeroed loss accumulators: ONE launch (enf_fit_inputs) instead of eight framework kernels
         lat, xs_all, ys_all, losses = fused[:4]
-        ws_all = fused[4] if weights is not None else None
+        ws_all = fused[4] if weights is not None or per_signal else None
+    elif per_signal:
+        lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
+        xs_all, ys_all, ws_all = gather_signal_points(coords, img, masks, weights)       # (S+1, B, N_s, .): enf_fit_inputs_b in torch ops
+        losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)
     else:
         lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}       # pde_trainer.py:157-159 (a fresh tensor)
         masks_t = masks.t().contiguous()                                     # (a gather inherits the strides of a transposed index)
@@ -123,12 +195,16 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         ys_all = img[:, masks_t].transpose(0, 1).float().contiguous()        # (S+1, B, N_s, O)
         losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)  # one accumulator per step, zeroed in one fill
         ws_all = gather_point_weights(weights, masks) if weights is not None else None      # (S+1, B, N_s)
+    if normalize_weights:
+        if ws_all is None:
+            raise ValueError("normalize_weights needs sampled weights: pass weights= or per-signal masks")
+        ws_all = normalize_sampled_weights(ws_all)
     if noise_pos:                                                                             # pde_trainer.py:162-167
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
     n_pos = lat["p_pos"].shape[-1]
     for s in range(S):                                                  # pde_trainer.py:191
-        xs = xs_all[s][None].expand(B, -1, -1)                          # stride-0 batch
+        xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)             # every signal's own points, or a stride-0 batch
         _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
                                                          lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
                                                          weight=None if ws_all is None else ws_all[s])
@@ -141,7 +217,7 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
             grads["gaussian_window"] = dsig
         lat = meta_sgd_update(lat, grads, lrs, B)
     with torch.no_grad():                                               # pde_trainer.py:225-235
-        xs = xs_all[S][None].expand(B, -1, -1)
+        xs = xs_all[S] if per_signal else xs_all[S][None].expand(B, -1, -1)
         out = nef.apply(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window")).float().contiguous()
         st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
         if out.shape != ys_all[S].shape:

@@ -29,8 +29,8 @@ import torch
 
 from ..optim import Adam, AdamW, clip_by_global_norm, global_norm
 from ..parallel import allreduce_mean_
-from ..inner_loop import decode
-from ..weights import prepare_point_weights, weighted_mse
+from ..inner_loop import decode, make_signal_masks, gather_signal_points
+from ..weights import prepare_point_weights, weighted_mse, observed_sampling_weights
 from .latent_ode import LatentODEMixin, frame_weights, _leaves, _unflatten
 from .pde_trainer import _tree_from_tensors
 
@@ -58,9 +58,15 @@ class NonMetaPDETrainer(LatentODEMixin):
     ``training.graph_ode_training`` is honoured as in the MAML trainer (ode_train_step replays captured derivative
     evaluations; off by default).  Validation signals need no second shell here: a shell only indexes the table it is given,
     so val_step takes the shell as an argument and reads ``state.params['autodecoder']`` through it (:209-210), which the
-    caller has replaced by the validation table as validate_epoch does (:437-444)."""
+    caller has replaced by the validation table as validate_epoch does (:437-444).
 
-    def __init__(self, config, nef, autodecoder, coords, seed=42, *, ode_model=None):
+    ``sample_observed`` (keyword only): a nef step that is given ``weights`` draws its point subset per signal from that signal's
+    observed points ({weight > 0}; make_signal_masks, from the state's generator) instead of one subset shared by the batch, with
+    the weights rescaled by fitting/weights.py: observed_sampling_weights so that the loss still estimates the full-grid weighted
+    mean (without it signal b's loss would be N / n_b times the shared subset's).  Off by default.  (val_step fits nothing here -- it reads stored latents -- so it has no drop-out variant.)"""
+
+    def __init__(self, config, nef, autodecoder, coords, seed=42, *, ode_model=None, sample_observed=False):
+        self.sample_observed = bool(sample_observed)
         self.config, self.nef, self.autodecoder, self.coords, self.seed = config, nef, autodecoder, coords, seed
         self.ode_model = ode_model
         self.graph_ode_training = bool(getattr(getattr(config, "training", None), "graph_ode_training", False))
@@ -110,7 +116,12 @@ class NonMetaPDETrainer(LatentODEMixin):
             img, coords = img[:, mask], coords[mask]
             pw = None if pw is None else pw[:, mask]
         npts = cfg.training.max_num_sampled_points
-        if npts < coords.shape[0]:                                                        # :326-335
+        xs = None
+        if self.sample_observed and pw is not None:      # every signal's own min(npts, N) observed points; -1 padding has weight 0
+            m = make_signal_masks(pw, min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
+            # (the factor n_b / N of a draw from the observed points: the loss keeps the scale of the shared subset's)
+            xs, img, pw = (t[0] for t in gather_signal_points(coords, img, m, observed_sampling_weights(pw, m.shape[1])))
+        elif npts < coords.shape[0]:                                                      # :326-335
             sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
             img, coords = img[:, sub], coords[sub]
             pw = None if pw is None else pw[:, sub]
@@ -119,7 +130,8 @@ class NonMetaPDETrainer(LatentODEMixin):
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
         w = [t.detach().requires_grad_(True) for t in self.nef.param_tensors(state.params["nef"])]
         p, a, window = self.autodecoder.apply({"params": leaves}, traj_idx)               # :338
-        xs = coords[None].expand(img.shape[0], -1, -1)
+        if xs is None:
+            xs = coords[None].expand(img.shape[0], -1, -1)
         out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
         loss = ((out - img) ** 2).mean() if pw is None else weighted_mse(out, img, pw)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)

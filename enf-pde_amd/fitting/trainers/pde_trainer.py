@@ -42,11 +42,11 @@ from types import SimpleNamespace
 
 import torch
 
-from ..inner_loop import _pose, make_masks, inner_loop, decode
+from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
 from .latent_ode import LatentODEMixin, draw_point_masks, frame_weights, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
-from ..weights import prepare_point_weights, weighted_mse
+from ..weights import prepare_point_weights, weighted_mse, normalize_point_weights, observed_sampling_weights
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
@@ -63,15 +63,25 @@ def _tree_from_tensors(tensors, nef=None):
     return {"params": out}
 
 
-def _loss(nef, params, coords, img, masks, s, lat, weights=None):
+def _sampled(coords, img, masks, s, weights, copies=1):
+    """The points of step ``s``: (xs (copies * B, N_s, dx), ys (B, N_s, O), weights (B, N_s) or None).  Shared masks (N_s, S+1) give
+    the reference's gather (pde_trainer.py:193-197) with a stride-0 batch; per-signal masks (B, N_s, S+1) give every signal its own
+    points and always weights (0 where the sampler padded with -1; fitting/inner_loop.py: gather_signal_points)."""
     B = img.shape[0]
+    if masks.dim() == 2:
+        m = masks[:, s]
+        return coords[m][None].expand(copies * B, -1, -1), img[:, m], (None if weights is None else weights[:, m])
+    xs, ys, ws = gather_signal_points(coords, img, masks[:, :, s:s + 1], weights)
+    return (xs[0] if copies == 1 else xs[0].repeat(copies, 1, 1)), ys[0].to(img.dtype), ws[0]
+
+
+def _loss(nef, params, coords, img, masks, s, lat, weights=None):
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    xs = coords[masks[:, s]][None].expand(B, -1, -1)                    # pde_trainer.py:193-197
-    ys = img[:, masks[:, s]]
+    xs, ys, ws = _sampled(coords, img, masks, s, weights)               # pde_trainer.py:193-197
     out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
-    if weights is None:
+    if ws is None:
         return ((out - ys) ** 2).mean()                                 # pde_trainer.py:185
-    return weighted_mse(out, ys, weights[:, masks[:, s]])               # (fitting/weights.py: the per-point weighted form)
+    return weighted_mse(out, ys, ws)                                    # (fitting/weights.py: the per-point weighted form)
 
 
 def _latent_grads(nef, params, coords, img, masks, s, lat, keys, weights=None):
@@ -99,15 +109,13 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: torch.cat([plus[k], minus[k]], 0).detach().requires_grad_(True) for k in plus}
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    xs = coords[masks[:, s]][None].expand(2 * B, -1, -1)
-    ys = img[:, masks[:, s]]
+    xs, ys, pw = _sampled(coords, img, masks, s, point_weights, copies=2)     # (per-signal masks: signal b + B at the points of b)
     import contextlib
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
         out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
-        if point_weights is None:
+        if pw is None:
             loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
         else:
-            pw = point_weights[:, masks[:, s]]
             loss = weighted_mse(out[:B], ys, pw) - weighted_mse(out[B:], ys, pw)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
@@ -128,13 +136,15 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     the fitted latents (default: the reconstruction loss on the last mask); dual_train_step passes the roll-out loss.
     ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
     unless ``normalize`` is False; they weigh every inner step's loss and the default terminal loss.
+    ``masks``: (N_s, S+1), or per-signal (B, N_s, S+1) (make_signal_masks): the forward sweep, the terminal loss and the adjoint
+    sweep's re-evaluations all gather the same per-signal points.
     """
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
     if fd_step is None:      # truncation (~step^2) against the rounding of the first-order gradients (~1 / step): bf16 kernels
         fd_step = 2e-2 if getattr(nef, "precision", "f32") in ("bf16", "bfloat16") else 5e-3      # are 100x noisier
     B = img.shape[0]
-    S = masks.shape[1] - 1
+    S = masks.shape[-1] - 1
     pw = prepare_point_weights(weights, B, img.shape[1], normalize, img.device)
     weights = nef.param_tensors(nef_params)
     frozen = _tree_from_tensors([t.detach() if t is not None else None for t in weights], nef)           # inference path for the inner steps
@@ -152,7 +162,7 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     import contextlib
     for s in range(S):
         # (the forward of this pass also records the relu masks at phi_s for the adjoint sweep's frozen-mask differences)
-        relu_bufs.append(nef.relu_mask_buffer(B, masks.shape[0], lat["a"].shape[1], coords.device) if freeze else None)
+        relu_bufs.append(nef.relu_mask_buffer(B, masks.shape[-2], lat["a"].shape[1], coords.device) if freeze else None)
         with (nef.relu_masks(relu_bufs[s], "write", B) if freeze else contextlib.nullcontext()):
             g = _latent_grads(nef, frozen, coords, img, masks, s, lat, keys, pw)
         g = {k: (torch.zeros_like(lat[k]) if (k not in g or masked(k)) else g[k] * B) for k in lat}    # pde_trainer.py:207
@@ -210,9 +220,19 @@ class MetaSGDPDETrainer(LatentODEMixin):
     meta.learning_rate_meta_sgd, meta.num_inner_steps, meta.inner_learning_rate_{p,a,window},
     meta.noise_pos_inner_loop, nef.optimize_gaussian_window, training.max_num_sampled_points; with an ``ode_model``
     also optimizer.learning_rate_ode, node.dt, node.method, dataset.traj_len_train, dataset.traj_len_out_horizon.
+
+    ``sample_observed``: a step that is given ``weights`` and no masks draws per-signal masks from every signal's observed points
+    ({frame-0 weight > 0}; make_signal_masks, from the state's generator) instead of one set shared by the batch, so that no
+    sampled point is spent where a signal has no data.  The fit's weights are then observed_sampling_weights(weights, N_s)
+    (fitting/weights.py): a draw from the observed set meets no zero-weight point, and without the factor n_b / N every loss and
+    every inner step of signal b would be N / n_b times those of the shared-mask step; with it the sampled loss estimates the same
+    full-grid weighted mean.  Masks PASSED to a step are taken with the weights as they are.  Off by default: the masks drawn are
+    then exactly make_masks'.
     """
 
-    def __init__(self, config, nef, outer_autodecoder, coords, seed=0, second_order="fd", fd_step=None, ode_model=None):
+    def __init__(self, config, nef, outer_autodecoder, coords, seed=0, second_order="fd", fd_step=None, ode_model=None,
+                 sample_observed=False):
+        self.sample_observed = bool(sample_observed)
         self.config, self.nef, self.outer_autodecoder, self.coords, self.seed = config, nef, outer_autodecoder, coords, seed
         self.second_order, self.fd_step = second_order, fd_step
         self.ode_model = ode_model
@@ -270,6 +290,21 @@ class MetaSGDPDETrainer(LatentODEMixin):
         keys = [k for k in LATENT_KEYS if k in P and not (k == "p_ori" and self.outer_autodecoder.num_ori_dims == 0)]
         return {k: P[k] for k in keys}
 
+    def _draw_masks(self, state, num_coords, observed=None):
+        """The index sets of one fit: make_masks, or with ``sample_observed`` and ``observed`` (B, N) weights make_signal_masks."""
+        cfg = self.config
+        n = cfg.training.max_num_sampled_points
+        if self.sample_observed and observed is not None:
+            return make_signal_masks(observed, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
+        return make_masks(num_coords, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
+
+    @staticmethod
+    def _observed_weights(drew, masks, weights):
+        """The fit's weights: rescaled for masks this trainer drew per signal from the observed points, else as they are."""
+        if drew and masks.dim() == 3 and weights is not None:
+            return observed_sampling_weights(weights, masks.shape[1])
+        return weights
+
     def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True):
         """One outer step on ``batch`` = (B, N, O) initial states (trajectory[:, 0], pde_trainer.py:485-487).
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (meta_gradients).
@@ -277,9 +312,12 @@ class MetaSGDPDETrainer(LatentODEMixin):
         the outer gradients are averaged with one flat all-reduce before the (identical) optimiser updates."""
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
-        if masks is None:
-            masks = make_masks(self.coords.shape[0], cfg.training.max_num_sampled_points, cfg.meta.num_inner_steps,
-                               generator=state.rng, device=self.coords.device)
+        if masks is None and self.sample_observed and weights is not None:
+            weights = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
+            masks = self._draw_masks(state, self.coords.shape[0], weights)
+            weights, normalize = self._observed_weights(True, masks, weights), False
+        elif masks is None:
+            masks = self._draw_masks(state, self.coords.shape[0])
         lat0 = self._latents0(state)
         lrs = state.params["meta_sgd_lrs"]
         loss, grads = meta_gradients(self.nef, state.params["nef"], lat0, lrs, self.coords, img, masks,
@@ -349,9 +387,10 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return out
 
     # ------------------------------------------------------------------ latent-ODE phase (pde_trainer.py:290-500)
-    def _fit_initial_latents(self, state, initial_state, masks=None, initial_state_dp=0.0, weights=None):
+    def _fit_initial_latents(self, state, initial_state, masks=None, initial_state_dp=0.0, weights=None, observed=None):
         """What inner_loop takes for the first frame of every trajectory (pde_trainer.py:424-427): (coords, img, masks), and with
-        ``weights`` (B, N) a fourth value, the weights of the same point subset."""
+        ``weights`` (B, N) a fourth value, the weights of the same point subset.  ``observed`` (B, N): with ``sample_observed``
+        the masks are drawn per signal from {observed > 0} (default: ``weights``)."""
         cfg = self.config
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
@@ -360,9 +399,10 @@ class MetaSGDPDETrainer(LatentODEMixin):
             coords, img = coords[keep], img[:, keep]
             if weights is not None:
                 weights = weights[:, keep].contiguous()
+            if observed is not None:
+                observed = observed[:, keep]
         if masks is None:
-            masks = make_masks(coords.shape[0], cfg.training.max_num_sampled_points, cfg.meta.num_inner_steps,
-                               generator=state.rng, device=coords.device)
+            masks = self._draw_masks(state, coords.shape[0], weights if observed is None else observed)
         return (coords, img, masks) if weights is None else (coords, img, masks, weights)
 
     def ode_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False, weights=None,
@@ -382,7 +422,9 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return prepare_point_weights(weights, B, N, normalize, device)
 
     def _fitted(self, state, trajectory, masks, weights=None):
-        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks)
+        drew = masks is None
+        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=weights)
+        weights = self._observed_weights(drew, masks, weights)
         cfg = self.config
         _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
                             optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
@@ -422,7 +464,10 @@ class MetaSGDPDETrainer(LatentODEMixin):
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]
         if weights is not None and torch.as_tensor(weights).dim() == 3:
             weights = torch.as_tensor(weights)[:, :cfg.dataset.traj_len_train]
-        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks)
+        w0 = self._frame0_weights(weights, trajectory.shape[0], self.coords.shape[0], normalize, self.coords.device)
+        drew = masks is None
+        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=w0)
+        w0 = self._observed_weights(drew, masks, w0)
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
         if point_masks is None and cfg.training.max_num_sampled_points < self.coords.shape[0]:
@@ -447,8 +492,7 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal,
-                                     weights=self._frame0_weights(point_weights, img.shape[0], img.shape[1], normalize, img.device),
-                                     normalize=False)
+                                     weights=w0, normalize=False)
         lr_keys = list(lrs.keys())
         flat = grads["nef"] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + side["ode"] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])
@@ -499,11 +543,16 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return total / max(n, 1), state
 
     @torch.no_grad()
-    def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True):
+    def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True, drop_rate=None):
         """pde_trainer.py:360-409: fit the first frame, roll out over train + out-of-horizon frames, decode the full grid;
         returns (mse over the training horizon, mse beyond it).  ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on
         the full grid (fitting/weights.py; mean 1 per signal-frame unless ``normalize`` is False): frame 0's weigh the fit, and
-        the pair returned is (weighted mse over the training horizon, weighted mse beyond it)."""
+        the pair returned is (weighted mse over the training horizon, weighted mse beyond it).
+        ``drop_rate`` r in [0, 1): validation under point drop-out (the reference's val_mse_*_dpK).  Every signal keeps each of its
+        observed frame-0 points with probability 1 - r (drawn from the state's generator) and is fitted on per-signal masks of
+        min(max_num_sampled_points, int((1 - r) N)) points from what it kept (make_signal_masks), with the kept points' weights
+        renormalised and rescaled by observed_sampling_weights so that the fit's loss has the scale of a fit without drop-out; the
+        two errors are still taken over all valid points of the full grid."""
         cfg = self.config
         T_in = cfg.dataset.traj_len_train
         trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
@@ -512,10 +561,28 @@ class MetaSGDPDETrainer(LatentODEMixin):
         if weights is not None and torch.as_tensor(weights).dim() == 3:
             weights = torch.as_tensor(weights)[:, :T]
         w0 = self._frame0_weights(weights, B, N, normalize, self.coords.device)
-        if w0 is None:
+        if drop_rate is not None:
+            if not 0.0 <= drop_rate < 1.0:
+                raise ValueError(f"drop_rate must lie in [0, 1), got {drop_rate}")
+            if masks is not None or initial_state_dp > 0:
+                raise ValueError("drop_rate draws its own per-signal masks: pass neither masks nor initial_state_dp with it")
+            kept = torch.rand((B, N), generator=state.rng) >= drop_rate
+            if w0 is not None:
+                kept &= (w0 > 0).cpu()
+            coords, img = self.coords, trajectory[:, 0].reshape(B, -1, trajectory.shape[-1])
+            masks = make_signal_masks(kept, max(1, min(cfg.training.max_num_sampled_points, int((1.0 - drop_rate) * N))),
+                                      cfg.meta.num_inner_steps, generator=state.rng, device=coords.device)
+            # what the signal kept is its observed set: weights of mean 1 over the grid again (as normalize asks), then the
+            # factor of a draw from the observed points -- the fit's loss keeps the scale of a fit without drop-out
+            kept = kept.to(coords.device)
+            w0 = kept.float() if w0 is None else w0 * kept
+            w0 = observed_sampling_weights(normalize_point_weights(w0) if normalize else w0, masks.shape[1])
+        elif w0 is None:
             coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp)
         else:
+            drew = masks is None
             coords, img, masks, w0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, w0)
+            w0 = self._observed_weights(drew, masks, w0)
         with torch.enable_grad():
             _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
                                 optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), weights=w0)

@@ -5,6 +5,7 @@
 A point of weight 0 does not exist: its target may be NaN or Inf and never enters the arithmetic.  The library does not
 normalise; the trainers call ``normalize_point_weights`` once on the FULL grid, before any sampling, so that the loss on a
 random subset of points is an unbiased estimate of the full-grid weighted mean and weights of all ones change nothing.
+Where the subset is drawn per signal from its observed points only, ``observed_sampling_weights`` keeps that property.
 Pure torch, no GPU needed.
 """
 import torch
@@ -69,6 +70,26 @@ def prepare_point_weights(weights, B, N, normalize=True, device=None):
 def gather_point_weights(weights, masks):
     """weights (B, N), masks (N_s, S1) long -> (S1, B, N_s): ws[s, b, i] = weights[b, masks[i, s]] (what enf_fit_inputs_w gathers)."""
     return weights[:, masks.t()].transpose(0, 1).contiguous()
+
+
+def observed_sampling_weights(weights, num_sampled):
+    """Full-grid weights (B, N) -> the weights to fit with when every signal's points are drawn uniformly from its OWN observed set
+    {weights > 0} (inner_loop.make_signal_masks) instead of from the whole grid.  Such a draw meets only observed points, so the
+    sampled loss 1 / N_s * sum_i w_i d_i^2 estimates the mean of w d^2 over the n_b observed points, which is N / n_b times the
+    full-grid weighted mean 1 / N * sum_n w_n d_n^2 that a draw from the whole grid estimates.  Signal b's weights are therefore
+    multiplied by n_b / N, and where n_b < N_s -- the rows the sampler pads: all n_b points are met once, the divisor stays N_s
+    -- by N_s / n_b as well:
+
+        c_b = n_b / N * N_s / min(N_s, n_b)
+
+    With these weights the sampled loss is an unbiased estimate of the same full-grid weighted mean as with shared masks (exact
+    where n_b <= N_s), so loss values and step lengths keep their scale; 0/1 weights normalised to mean 1 on the grid (1 / f
+    on the observed points) come out as 1 on the observed points.  A signal that observes nothing stays zero."""
+    w = torch.as_tensor(weights)
+    N = w.shape[-1]
+    n = (w > 0).sum(dim=-1, keepdim=True).to(w.dtype)
+    c = n / N * (float(num_sampled) / n.clamp(min=1.0).clamp(max=float(num_sampled)))
+    return w * c
 
 
 def weighted_mse(out, target, weights=None):

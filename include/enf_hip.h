@@ -390,6 +390,21 @@ int enf_fit_inputs(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z
 int enf_fit_inputs_w(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx, int32_t O,
                      const float* coords, const float* img, const int64_t* masks, float* xs, float* ys, float* losses,
                      const float* weight /* (B,N) or NULL */, float* ws /* (S1,B,Ns) */, void* stream);
+/* The same for PER-SIGNAL index sets (signals observed at different places: sensor drop-out, land masks, cloud gaps), one launch:
+ *       masks (B, Ns, S1) int64: one set of Ns indices into the N grid points per signal and step
+ *       xs[s, b, i, :] = coords[masks[b, i, s], :]     (S1, B, Ns, dx)      -- the consumers take xs[s] with x_bstride = Ns * dx
+ *       ys[s, b, i, :] = img[b, masks[b, i, s], :]     (S1, B, Ns, O)
+ *       ws[s, b, i]    = weight[b, masks[b, i, s]]     (S1, B, Ns)
+ * plus the latent broadcast and the zeroed loss accumulators of enf_fit_inputs.  Row offsets are 64-bit (B N O may exceed 2^31).
+ * Index contract: an index < 0 or >= N is never dereferenced.  Its xs row is coords[0], its ys row is zeros and its ws is 0.0f, so
+ * by the weighted-loss contract above the point does not exist; a sampler pads a signal that has fewer than Ns observed points
+ * with -1.  ws is what expresses this, so it is REQUIRED (NULL is ENF_EINVAL, with or without weight); weight stays optional: without
+ * it ws is 1.0f for an index in range and 0.0f for one outside.
+ * The loss stays un-normalised, 1 / (B Ns O): a caller who wants a signal with few valid samples to take a step as long as a fully
+ * sampled one rescales ws[s, b, :] to mean 1 (inner_loop(normalize_weights=True)); the library forms no sums over weights. */
+int enf_fit_inputs_b(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx, int32_t O,
+                     const float* coords, const float* img, const int64_t* masks /* (B,Ns,S1) */, float* xs, float* ys, float* losses,
+                     const float* weight /* (B,N) or NULL */, float* ws /* (S1,B,Ns), required */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
