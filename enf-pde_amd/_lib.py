@@ -26,7 +26,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
-           "enf_ode_basis_backward", "enf_relu_mask_bytes", "enf_meta_sgd_update"]
+           "enf_ode_basis_backward", "enf_relu_mask_bytes", "enf_meta_sgd_update", "enf_table_adam_update"]
 ENF_NUM_PAIR_TENSORS = 12          # ENF_P_* of include/enf_hip.h
 # deterministic mode (include/enf_hip.h, "Deterministic mode"): one bit for every entry point that takes flags
 ENF_BWD_DETERMINISTIC = ENF_FIT_DETERMINISTIC = ENF_MSE_DETERMINISTIC = 16
@@ -60,6 +60,15 @@ class EnfSgdSegment(ctypes.Structure):
 
 
 ENF_SGD_MAX_SEGMENTS = 4
+
+
+ENF_ADAM_MAX_SEGMENTS = 4
+
+
+class EnfAdamSegment(ctypes.Structure):
+    """One component of a latent table for enf_table_adam_update (include/enf_hip.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "mu", "nu", "g", "x_out", "mu_out", "nu_out")] + \
+               [("width", ctypes.c_int32), ("g_stride", ctypes.c_int32)]
 
 
 class EnfFitComponent(ctypes.Structure):
@@ -134,6 +143,8 @@ def _bind(path, test_hooks):
     lib.enf_pack_pair.argtypes = [dp, ctypes.POINTER(vp), vp, vp]
     lib.enf_mse_value_grad.argtypes = [vp, vp, sz, ctypes.c_float, vp, vp, vp]
     lib.enf_meta_sgd_update.argtypes = [ctypes.c_int, ctypes.POINTER(EnfSgdSegment), ctypes.c_float, vp]
+    lib.enf_table_adam_update.argtypes = [ctypes.c_int, ctypes.POINTER(EnfAdamSegment), i64, ctypes.c_int32, vp, ctypes.c_int32] + \
+                                         [ctypes.c_float] * 6 + [vp]
     lib.enf_fit_inputs.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 7
     lib.enf_ode_conv_forward.argtypes = [ci, ci, ci, ci, vp, vp, i64, i64, vp, vp, vp, vp]
     lib.enf_ode_conv_backward_basis.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp]

@@ -1,5 +1,5 @@
 """Auto-decoder (non-meta) ENF trainer, mirroring experiments/fitting/trainers/nonmaml_pde_trainer.py: the nef phase, the
-latent-ODE phase and the validation roll-out.
+latent-ODE phase, the validation roll-out and the validation protocol (validate_epoch, with its latent-only fit step).
 
 Every training signal owns a row of latents in a PositionOrientationFeatureAutodecoder (:37-45); one nef step is
 
@@ -27,7 +27,7 @@ from dataclasses import dataclass, field
 
 import torch
 
-from ..optim import Adam, AdamW, clip_by_global_norm, global_norm
+from ..optim import Adam, AdamW, clip_by_global_norm, global_norm, scatter_rows, table_adam_update
 from ..parallel import allreduce_mean_
 from ..inner_loop import decode, make_signal_masks, gather_signal_points
 from ..weights import prepare_point_weights, weighted_mse, observed_sampling_weights
@@ -104,18 +104,17 @@ class NonMetaPDETrainer(LatentODEMixin):
         state, epoch, _ = load_train_state(path, self.init_train_state(**init_kwargs))
         return state, epoch
 
-    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True):
-        """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
-        ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
-        before ``mask`` and the point sampling unless ``normalize`` is False."""
-        cfg = self.config
+    def _fit_points(self, state, initial_state, mask, weights, normalize):
+        """What a nef step fits on (:311-335): (targets (B, n, O), coordinates (n, dx), loss weights (B, n) or None, per-signal
+        coordinates (B, n, dx) or None).  The one place where a nef step draws from ``state.rng``: loss_and_grads and
+        fit_latents_step both call it, so the two consume the generator alike."""
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
         pw = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
         if mask is not None:                                                              # :321-323
             img, coords = img[:, mask], coords[mask]
             pw = None if pw is None else pw[:, mask]
-        npts = cfg.training.max_num_sampled_points
+        npts = self.config.training.max_num_sampled_points
         xs = None
         if self.sample_observed and pw is not None:      # every signal's own min(npts, N) observed points; -1 padding has weight 0
             m = make_signal_masks(pw, min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
@@ -125,6 +124,13 @@ class NonMetaPDETrainer(LatentODEMixin):
             sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
             img, coords = img[:, sub], coords[sub]
             pw = None if pw is None else pw[:, sub]
+        return img, coords, pw, xs
+
+    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True):
+        """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
+        ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
+        before ``mask`` and the point sampling unless ``normalize`` is False."""
+        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
@@ -164,6 +170,43 @@ class NonMetaPDETrainer(LatentODEMixin):
     def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True):
         """Only the latents move (:139-171)."""
         return self._step(state, batch, mask, False, weights, normalize)
+
+    @torch.no_grad()
+    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True):
+        """nef_train_step_autodec_only (:139-171) on the native latent-only path: same arguments, same (loss, new_state), same draw
+        from ``state.rng`` (_fit_points), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
+        are read under no_grad, ONE nef.mse_value_and_latent_grads (enf_fit_step_w: forward, fused weighted loss, backward to the
+        latents; neither ``out`` nor an autograd graph nor a weight gradient exists) returns the loss and the gradient w.r.t.
+        those rows, and ONE enf_table_adam_update (optim.table_adam_update) applies optax adam to the whole table from them: rows
+        outside the batch move by their momentum only, as in _step.  A shared point subset is passed as a stride-0 ``x``.
+        The nef parameters, ``nef_opt_state`` and ``ode_opt_state`` are handed on untouched.  In a multi-rank run the gathered
+        gradients are scattered to dense tensors, averaged with the loss by the flat all-reduce of _step, and the kernel runs in
+        its dense form (idx = None).  This is the step validate_epoch repeats; nef_train_step_autodec_only stays as it is."""
+        initial_state, traj_idx = batch
+        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize)
+        P = state.params["autodecoder"]["params"]
+        names = list(P.keys())
+        tables = [P[k].detach() for k in names]
+        p, a, window = self.autodecoder.apply({"params": dict(zip(names, tables))}, traj_idx)
+        if xs is None:
+            xs = coords[None].expand(img.shape[0], -1, -1)
+        loss, dp, da, dwin = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, weight=pw)
+        loss = loss.reshape(())
+        n_pos = P["p_pos"].shape[-1]
+        by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dwin}
+        grads = [by_name.get(k) for k in names]
+        grads = [torch.zeros((dp.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) if g is None else g
+                 for g, t in zip(grads, tables)]                                             # e.g. a decoder without a window
+        idx = traj_idx
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            grads = scatter_rows([g.float() for g in grads], traj_idx, tables[0].shape[0])
+            flat = grads + [loss.reshape(1).clone()]
+            allreduce_mean_(flat, weight=initial_state.shape[0])
+            loss, idx = flat[-1][0], None
+        new_tables, ad_state = table_adam_update(self.autodecoder_opt, state.autodecoder_opt_state, tables, grads, idx=idx)
+        params = dict(state.params, autodecoder={"params": dict(zip(names, new_tables))})    # nef, ode_params carried over
+        return loss, NonMetaTrainState(params=params, nef_opt_state=state.nef_opt_state, autodecoder_opt_state=ad_state,
+                                       ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
 
     # ------------------------------------------------------------------ latent-ODE phase (:173-307)
     def _need_ode(self, what):
@@ -246,6 +289,63 @@ class NonMetaPDETrainer(LatentODEMixin):
         rec, tgt, F = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O), TRAIN_FRAMES
         return weighted_mse(rec[:, :F], tgt[:, :F], fw[:, :F]), \
             (weighted_mse(rec[:, F:], tgt[:, F:], fw[:, F:]) if T > F else recon.new_zeros(()))
+
+    def validate_epoch(self, state, train_loader, val_loader, val_autodecoder, *, drop_rates=(0.0, 0.05, 0.1, 0.5), epochs=None,
+                       fit_train=True):
+        """:399-548, without its logging and plots.  Validating an auto-decoder means fitting a FRESH latent table to the signals
+        with the decoder frozen, then rolling the fitted rows out.  Returns (metrics, the last validation state):
+
+            train_mse_{in,out}_t_sc                     val_step over ``train_loader`` on the STORED table of ``state`` (:419-431)
+            val_mse_{in,out}_t[_dpR]   per drop rate R  a table from ``val_autodecoder.init`` and a fresh Adam state (:436-444),
+                                                        ``epochs`` passes of fit_latents_step over ``val_loader`` on frame 0
+                                                        (:460-474), then val_step over ``val_loader``, averaged (:477-496)
+            train_mse_{in,out}_t[_dpR] (``fit_train``)  the same with ``self.autodecoder.init`` over ``train_loader`` (:501-536)
+
+        (the keys of rate 0.0 carry no suffix; the others end in ``_dp0.05`` etc., the reference's f-string.)  Loaders are
+        re-iterable and yield (trajectory (B, T, *grid, O), _, traj_idx) or (trajectory, traj_idx); ``val_autodecoder`` is the
+        shell sized for the validation set.  Tables are initialised on the device of ``self.coords`` with ``state.rng`` as key,
+        and the fits draw their point subsets from it (the reference splits the key per rate, :436; here the one generator runs
+        on).  The nef and ODE parameters and the stored table of ``state`` are only read.  Two points are the reference's verbatim:
+          - epochs: ``range(1, total_val_epochs)`` with total_val_epochs = training.nef.train_until_epoch (:447,460), so the
+            default is train_until_epoch - 1 passes;
+          - drop-out: the mask of rate R is ``permutation(N)[:int(N * R)]`` (:452-455), and nef_loss indexes WITH it
+            (``initial_state[:, mask]``, :321), so it KEEPS int(N * R) points: R = 0.05 fits on 5 % of the grid.  It is drawn once
+            per rate and shared by the validation and the training fit; rate 0 has no mask."""
+        self._need_ode("validate_epoch")
+        if epochs is None:
+            epochs = self.config.training.nef.train_until_epoch - 1
+        dev, N = self.coords.device, self.coords.shape[0]
+
+        def rollout_errors(st, loader, shell):
+            tot_in, tot_out, n = 0.0, 0.0, 0
+            for batch in loader:
+                e_in, e_out = self.val_step(st, batch, autodecoder=shell)
+                tot_in, tot_out, n = tot_in + e_in, tot_out + e_out, n + 1
+            return float(tot_in) / max(n, 1), float(tot_out) / max(n, 1)
+
+        def fit(shell, loader, dp_mask):
+            table = shell.init(state.rng, device=dev)
+            st = NonMetaTrainState(params=dict(state.params, autodecoder=table), nef_opt_state=state.nef_opt_state,
+                                   autodecoder_opt_state=self.autodecoder_opt.init(list(table["params"].values())),
+                                   ode_opt_state=state.ode_opt_state, step=state.step, rng=state.rng)
+            for _ in range(epochs):
+                for batch in loader:
+                    _, st = self.fit_latents_step(st, (batch[0][:, 0], batch[-1]), mask=dp_mask)
+            return st
+
+        metrics = {}
+        metrics["train_mse_in_t_sc"], metrics["train_mse_out_t_sc"] = rollout_errors(state, train_loader, self.autodecoder)
+        val_state = None
+        for dp in drop_rates:
+            dp_mask = torch.randperm(N, generator=state.rng)[:int(N * dp)].to(dev) if dp > 0 else None
+            suffix = f"_dp{dp}" if dp > 0 else ""
+            val_state = fit(val_autodecoder, val_loader, dp_mask)
+            metrics["val_mse_in_t" + suffix], metrics["val_mse_out_t" + suffix] = rollout_errors(val_state, val_loader, val_autodecoder)
+            if fit_train:
+                train_state = fit(self.autodecoder, train_loader, dp_mask)
+                metrics["train_mse_in_t" + suffix], metrics["train_mse_out_t" + suffix] = \
+                    rollout_errors(train_state, train_loader, self.autodecoder)
+        return metrics, val_state
 
     def select_train_step(self, epoch):
         """The step of ``epoch`` by the windows of _base_pde_trainer.py:280-289: nef while training.nef.train_from_epoch < epoch

@@ -370,6 +370,36 @@ typedef struct EnfSgdSegment {
 } EnfSgdSegment;
 int enf_meta_sgd_update(int nseg, const EnfSgdSegment* segs, float scale, void* stream);
 
+/* The Adam counterpart for an auto-decoder's latent TABLE (nonmaml_pde_trainer.py:67,125-126,159-160: optax.adam over the whole
+ * table): one optax `adam` step (scale_by_adam with bias correction, eps outside the root, no weight decay) over every component of
+ * the table in one launch, straight from the GATHERED gradient rows a fit step returns.  Per table element (s, z, c) of a segment:
+ *     g   = sum over j with idx[j] == s of g[(j, z, c)], added in increasing j; exact 0.0f when no j matches
+ *     mu' = b1 mu + (1 - b1) g            nu' = b2 nu + (1 - b2) g g
+ *     x'  = x - lr (mu' / c1) / (sqrt(nu' / c2) + eps)
+ * c1 = 1 - b1^count and c2 = 1 - b2^count are formed by the caller (in double, passed as float): the library keeps no counter.
+ * A row outside the batch moves by its momentum only, as optax's dense Adam over the whole table does -- this is no sparse update.
+ * idx == NULL: the gradient is dense, nidx must equal S and row j is table row j (what a multi-rank run holds after its all-reduce).
+ * One thread owns one element and scans the nidx indices (a batch size): no atomics, no scratch; duplicate indices are legal and
+ * summed in a fixed order (same inputs, same bits); x_out == x, mu_out == mu, nu_out == nu (in place) is safe.  The gradient
+ * buffers must not overlap an output.  An index outside [0, S) is never used as an offset: it matches no row and contributes
+ * nothing (the rule of enf_fit_inputs_b).  Element offsets are 64-bit (S Z width may exceed 2^31).
+ * ENF_EINVAL: a NULL pointer, a non-positive size (nseg outside 1..ENF_ADAM_MAX_SEGMENTS, S, Z, nidx, width), c1 <= 0 or c2 <= 0;
+ * ENF_EDIM: g_stride < width, or idx == NULL with nidx != S. */
+#define ENF_ADAM_MAX_SEGMENTS 4
+typedef struct EnfAdamSegment {      /* one component: p_pos, p_ori, a, gaussian_window */
+  const float* x;                    /* table (S, Z, width) ... */
+  const float* mu;                   /* ... and its first ... */
+  const float* nu;                   /* ... and second moment */
+  const float* g;                    /* gradient rows (nidx, Z, width); may be a column slice of a wider array (g_stride) */
+  float* x_out;                      /* (S, Z, width); each output may equal its input */
+  float* mu_out;
+  float* nu_out;
+  int32_t width, g_stride;           /* g element (j, z, c) = g[(j * Z + z) * g_stride + c] */
+} EnfAdamSegment;
+int enf_table_adam_update(int nseg, const EnfAdamSegment* segs, int64_t S, int32_t Z,
+                          const int64_t* idx /* (nidx) table rows of the gradient's signals, or NULL */, int32_t nidx,
+                          float lr, float b1, float b2, float eps, float c1, float c2, void* stream);
+
 /* What the inner loop prepares before its first step, in ONE launch (pde_trainer.py:157-159, 193-197; six framework kernels otherwise):
  *   - every latent component of the shared initialisation, (1, Z, width), repeated for the B signals -> (B, Z, width);
  *   - the coordinates and the targets of all S1 = S + 1 sampled point sets gathered once:
