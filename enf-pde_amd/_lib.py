@@ -23,6 +23,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_pair_backward_scratch_bytes", "enf_backward_all_scratch_bytes_ex", "enf_backward_weights_ex",
            "enf_backward_weights_scratch_bytes_ex",
            "enf_fit_step_w", "enf_mse_value_grad_w", "enf_fit_inputs_w", "enf_fit_inputs_b",
+           "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
@@ -197,6 +198,11 @@ def _bind(path, test_hooks):
     lib.enf_fit_inputs_w.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 9
     # per-signal index sets, masks (B, Ns, S1); ws may be given without weight (include/enf_hip.h: the index contract)
     lib.enf_fit_inputs_b.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 9
+    # per-channel loss weights (include/enf_hip.h, "Weighted loss"): cweight (B, N, O) fp32, required; the gather takes the mask
+    # layout as its last integer (0: shared (Ns, S1), 1: per-signal (B, Ns, S1))
+    lib.enf_fit_step_cw.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, sz, vp, cu, vp]
+    lib.enf_mse_value_grad_cw.argtypes = [vp, vp, vp, sz, ctypes.c_float, vp, vp, vp, sz, cu, vp]
+    lib.enf_fit_inputs_cw.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 8 + [ctypes.c_int32, vp]
     lib.enf_pair_backward_scratch_bytes.restype = sz
     lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]
     lib.enf_pair_backward_ex2.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]

@@ -277,15 +277,16 @@ extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstri
                         nullptr, flags, stream);
 }
 
-// weight != NULL: one loss weight per signal and query (include/enf_hip.h, "Weighted loss"); the one copy of the fit-step sequence
-extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
-                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, unsigned flags,
-                              void* stream) {
+// The one copy of the fit-step sequence.  weight != NULL: one loss weight per signal and query (include/enf_hip.h, "Weighted loss"),
+// or with `per_value` one per output value (B, N, O), which is then required.
+static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                             const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                             float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, bool per_value, unsigned flags,
+                             void* stream) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
-  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma, sigma, packed,
-                    workspace, workspace_bytes, stream, det);
+  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma && (!per_value || weight),
+                    sigma, packed, workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
@@ -303,11 +304,28 @@ extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstrid
     if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   }
   if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
-                                 det ? c.F(c.X.loss) : nullptr)))
+                                 det ? c.F(c.X.loss) : nullptr, per_value)))
     return rc;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse), det))) return rc;
   return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
+}
+
+extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, unsigned flags,
+                              void* stream) {
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, weight,
+                           false, flags, stream);
+}
+
+// per-channel loss weights, cweight (B, N, O), required (include/enf_hip.h, "Weighted loss")
+extern "C" int enf_fit_step_cw(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                               float* dsigma, void* workspace, size_t workspace_bytes, const float* cweight, unsigned flags,
+                               void* stream) {
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, cweight,
+                           true, flags, stream);
 }
 
 extern "C" int enf_lt_layout(const EnfDesc* d, int* stride, int* off_u, int* off_v0, int* off_pose, int* off_wcoef, int* off_c) {

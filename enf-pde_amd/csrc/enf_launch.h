@@ -155,8 +155,9 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
                        float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
 // the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
 // backward chain -> d ybar, delta
-// weight: NULL, or one loss weight per query (B N floats, include/enf_hip.h "Weighted loss")
+// weight: NULL, or one loss weight per query (B N floats, include/enf_hip.h "Weighted loss"); per_value: `weight` (not NULL) holds one
+// weight per output value instead, B N O floats (enf_fit_step_cw) -- a kernel instantiation of its own
 // loss_part != NULL (enf_tail_loss_parts(m) floats): every wave stores its partial there and enf_launch_loss_sum adds them to *loss
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st,
-                         float* loss_part = nullptr);
+                         float* loss_part = nullptr, bool per_value = false);

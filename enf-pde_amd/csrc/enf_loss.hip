@@ -42,6 +42,31 @@ __global__ __launch_bounds__(256) void enf_mse_kernel(const float* __restrict__ 
   }
 }
 
+// One weight per ELEMENT (include/enf_hip.h, "Weighted loss": per-channel weights): s += w d^2, dout = 2 w d inv_n gscale; an element
+// of weight 0 does not exist -- its target is never used in arithmetic and its dout is 0.0f.  A kernel of its own: the one above keeps
+// its code.  Same grid, same partials, same reduction.
+__global__ __launch_bounds__(256) void enf_mse_cw_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                         const float* __restrict__ cweight, size_t n, float inv_n, float gscale,
+                                                         float* __restrict__ dout, float* loss, float* __restrict__ part) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float w = cweight[i];
+    const float dd = w > 0.f ? out[i] - target[i] : 0.f;
+    const float d = w * dd;
+    s = fmaf(d, dd, s);
+    if (dout) dout[i] = 2.0f * d * inv_n * gscale;
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float v = (red[0] + red[1] + red[2] + red[3]) * inv_n;
+    if (part) part[blockIdx.x] = v;
+    else atomicAdd(loss, v);
+  }
+}
+
 // *loss += part[0] + ... + part[n - 1]: thread t adds part[t], part[t + 256], ... in order, then a fixed tree over the 256 threads.
 // The order depends on n alone, never on which workgroup of the producing kernel finished first.
 __global__ __launch_bounds__(256) void enf_loss_sum_kernel(const float* __restrict__ part, int n, float* loss) {
@@ -82,6 +107,20 @@ extern "C" int enf_mse_value_grad_w(const float* out, const float* target, const
   float* part = det ? (float*)scratch : nullptr;
   hipLaunchKernelGGL(enf_mse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, weight, n, (int)O,
                      1.0f / (float)n, grad_scale, dout, loss, part);
+  if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
+  return det ? enf_launch_loss_sum(part, (int)blocks, loss, (hipStream_t)stream) : ENF_OK;
+}
+
+extern "C" int enf_mse_value_grad_cw(const float* out, const float* target, const float* cweight, size_t n, float grad_scale, float* dout,
+                                     float* loss, void* scratch, size_t scratch_bytes, unsigned flags, void* stream) {
+  if (!out || !target || !cweight || !loss || n == 0 || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
+  const bool det = (flags & ENF_MSE_DETERMINISTIC) != 0;
+  if (det && !scratch) return ENF_EINVAL;
+  if (det && scratch_bytes < enf_mse_scratch_bytes(n, flags)) return ENF_EWORKSPACE;
+  const size_t blocks = mse_blocks(n);
+  float* part = det ? (float*)scratch : nullptr;
+  hipLaunchKernelGGL(enf_mse_cw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, target, cweight, n, 1.0f / (float)n,
+                     grad_scale, dout, loss, part);
   if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
   return det ? enf_launch_loss_sum(part, (int)blocks, loss, (hipStream_t)stream) : ENF_OK;
 }
@@ -140,6 +179,7 @@ struct FitInArgs {
   const float* coords; const float* img; const int64_t* masks;
   float* xs; float* ys; float* losses;
   const float* weight; float* ws;      // both or neither: the loss weights (B, N) and their gather (S1, B, Ns)
+                                       // (enf_fit_inputs_cw: per-channel weights (B, N, O) and their gather (S1, B, Ns, O))
 };
 
 __global__ __launch_bounds__(256) void enf_fit_inputs_kernel(FitInArgs A) {
@@ -263,5 +303,66 @@ extern "C" int enf_fit_inputs_b(int ncomp, const EnfFitComponent* comps, int32_t
   A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = N; A.Ns = Ns; A.S1 = S1; A.dx = dx; A.O = O;
   A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = weight; A.ws = ws;
   hipLaunchKernelGGL(enf_fit_inputs_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+}
+
+// enf_fit_inputs_cw: the setup with PER-CHANNEL loss weights, cweight (B, N, O) -> ws (S1, B, Ns, O), for both mask layouts
+// (include/enf_hip.h).  A kernel of its own beside the two above.  One thread per (s, b, i) row of ys / ws, as in enf_fit_inputs_b: it
+// reads its index once and copies the O targets and the O weights of that point; with per-signal masks also its row of xs, with shared
+// masks the threads of signal 0 write xs (S1, Ns, dx).  The index contract of enf_fit_inputs_b holds for both layouts: an index outside
+// [0, N) is never used as an offset, its row is coords[0], O zero targets and O zero weights.  All offsets are 64-bit.
+__global__ __launch_bounds__(256) void enf_fit_inputs_cw_kernel(FitInArgs A, int per_signal) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nrow = (int64_t)A.S1 * A.B * A.Ns;
+  if (i < nrow) {
+    const int64_t q = i % A.Ns, r = i / A.Ns, b = r % A.B, s = r / A.B;
+    const int64_t m = A.masks[per_signal ? (b * A.Ns + q) * A.S1 + s : q * A.S1 + s];
+    const bool ok = m >= 0 && m < (int64_t)A.N;
+    if (per_signal || b == 0) {
+      const float* __restrict__ cx = A.coords + (ok ? m : (int64_t)0) * A.dx;
+      float* __restrict__ x = A.xs + (per_signal ? i : s * A.Ns + q) * A.dx;
+      for (int c = 0; c < A.dx; ++c) x[c] = cx[c];
+    }
+    float* __restrict__ y = A.ys + i * A.O;
+    float* __restrict__ w = A.ws + i * A.O;
+    if (ok) {
+      const float* __restrict__ im = A.img + (b * A.N + m) * A.O;
+      const float* __restrict__ cw = A.weight + (b * A.N + m) * A.O;
+      for (int o = 0; o < A.O; ++o) { y[o] = im[o]; w[o] = cw[o]; }
+    } else {
+      for (int o = 0; o < A.O; ++o) { y[o] = 0.f; w[o] = 0.f; }
+    }
+    return;
+  }
+  i -= nrow;
+#pragma unroll
+  for (int k = 0; k < ENF_SGD_MAX_SEGMENTS; ++k) {
+    if (k < A.ncomp) {
+      const int64_t per = (int64_t)A.Z * A.comp[k].width, n = per * A.B;
+      if (i < n) { A.comp[k].dst[i] = A.comp[k].src[i % per]; return; }
+      i -= n;
+    }
+  }
+  if (i < A.S1) A.losses[i] = 0.f;
+}
+
+extern "C" int enf_fit_inputs_cw(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx,
+                                 int32_t O, const float* coords, const float* img, const int64_t* masks, float* xs, float* ys,
+                                 float* losses, const float* cweight, float* ws, int32_t per_signal_masks, void* stream) {
+  if (ncomp < 1 || ncomp > ENF_SGD_MAX_SEGMENTS || !comps || !coords || !img || !masks || !xs || !ys || !losses) return ENF_EINVAL;
+  if (!cweight || !ws) return ENF_EINVAL;
+  if (B < 1 || Z < 1 || N < 1 || Ns < 1 || S1 < 1 || dx < 1 || O < 1) return ENF_EDIM;
+  FitInArgs A{};
+  int64_t total = (int64_t)S1 * B * Ns + S1;
+  for (int k = 0; k < ncomp; ++k) {
+    if (!comps[k].src || !comps[k].dst || comps[k].width < 1) return ENF_EINVAL;
+    A.comp[k] = comps[k];
+    total += (int64_t)B * Z * comps[k].width;
+  }
+  if ((total + 255) / 256 > (int64_t)0x7fffffff) return ENF_EDIM;
+  A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = N; A.Ns = Ns; A.S1 = S1; A.dx = dx; A.O = O;
+  A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = cweight; A.ws = ws;
+  hipLaunchKernelGGL(enf_fit_inputs_cw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A,
+                     per_signal_masks != 0 ? 1 : 0);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }

@@ -23,6 +23,8 @@ struct TailArgs {
   const float* target; float* loss; float gscale, inv_n;     // fused loss (LOSS): d out = 2 (out - target) inv_n gscale, *loss += mean sq. error
   const float* weight;   // LOSS: nullptr, or one loss weight per query (NQ floats, >= 0): se += w (out - target)^2, d out *= w; a query of weight
                          // 0 does not exist -- its target is never used in arithmetic (it may be NaN) and its d out is exactly 0
+                         // LOSS + CW (the kernel's template flag): one weight per OUTPUT VALUE instead, (NQ, O) floats, never nullptr;
+                         // the same rule per value
   float* loss_part;      // LOSS, deterministic mode: wave w of workgroup g stores its partial in loss_part[g * NWAVES + w] (nullptr: atomic)
   float* tdel;           // weight-gradient backward (WG): per query d a_B | d a_F1 | d a_O0 | d a_O2 (2HD + 2D floats); the layer INPUTS
                          // n^ | gelu(a_F1) | gelu(a_O0) | gelu(a_O2) replace the pre-activations in `act` (enf_train.hip forms X^T delta)
@@ -243,9 +245,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
 // LOSS (with RECOMP): the inner step's tail in ONE kernel -- forward chain, the reconstruction loss and its gradient
 // (pde_trainer.py:185: mean squared error over all B N O outputs; enf_loss.hip's arithmetic) formed in registers from the forward's
 // outputs, backward chain: no `out` / `d out` round trip and two launches less between the pair kernels of an inner step.
-template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false>
+// CW (with LOSS): `weight` holds one value per output element (include/enf_hip.h, "Weighted loss": per-channel weights).  An
+// instantiation of its own: the per-point and the unweighted kernels keep their code.
+template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   static_assert(!LOSS || RECOMP, "the fused loss needs the forward chain's outputs");
+  static_assert(!CW || LOSS, "per-channel weights belong to the fused loss");
   using T = TailCfg<D, H, BF16>;
   constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD;
   using PG4 = Pan<1, NT, BF16>; using PG2 = Pan<KB, NT, BF16>; using PG0 = Pan<KB, NTH, BF16>; using PGH = Pan<KBH, NTH, BF16>;
@@ -287,7 +292,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   if constexpr (LOSS) {
     float se = 0.f;
     const float gs = 2.0f * A.inv_n * A.gscale;
-    if (A.weight) {          // (wave-uniform; the unweighted arithmetic below stays as it was, bit for bit)
+    if constexpr (CW) {      // the lane that holds output o of query n reads weight[n][o]; the zero test is per value: a select, never
+                             // 0 * target, so that the NaN of a missing value reaches neither the loss nor d out
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int o = 16 * t + 4 * quad + i;
+          const bool in = o < A.O && qvalid;
+          const float w = in ? A.weight[(size_t)qi * A.O + o] : 0.f;
+          const float dd = (in && w > 0.f) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
+          const float wd = w * dd;
+          se = fmaf(wd, dd, se);
+          g0[t][i] = wd * gs;
+        }
+    } else if (A.weight) {          // (wave-uniform; the unweighted arithmetic below stays as it was, bit for bit)
       const float w = A.weight[qi];
       const bool live = qvalid && w > 0.f;
 #pragma unroll
@@ -437,7 +456,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
 }
 
 template <int D, int H, bool BF16>
-static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st) {
+static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false) {
   const bool wg = bwd && A.tdel != nullptr;
   const bool fused_loss = bwd && A.target != nullptr;
   using T = TailCfg<D, H, BF16>;
@@ -445,15 +464,20 @@ static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st) {
   // few workgroups (at most one per CU): the deeper weight pipeline (LA2) instead of a second workgroup per CU
   const bool la2 = grid.x <= 256;
   // opt: forward -> stash the pre-activations (SAVE); backward -> they are stashed, skip the recompute
-  static EnfAttrBits attr_done[4][2][2];     // [fwd / bwd / bwd + WG][la2][opt] (this function is one instantiation per D, H, BF16), one bit per device
+  static EnfAttrBits attr_done[5][2][2];     // [fwd / bwd / bwd + WG / fused loss / fused loss + CW][la2][opt] (this function is one instantiation per D, H, BF16), one bit per device
   auto go = [&](void (*kern_ptr)(TailArgs)) -> int {
     const int smem = la2 ? T::SMEM3 : T::SMEM;
-    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[fused_loss ? 3 : (wg ? 2 : bwd)][la2][opt])) return ENF_ELAUNCH;
+    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd)][la2][opt])) return ENF_ELAUNCH;
     hipLaunchKernelGGL(kern_ptr, grid, dim3(NTHREADS), smem, st, A);
     return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
   };
   if (fused_loss) {
     if (wg || opt) return ENF_EINVAL;
+    if (cw) {
+      if (!A.weight) return ENF_EINVAL;
+      return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, true>)
+                 : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, true, true>);
+    }
     return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, true>) : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, true>);
   }
   if (wg) {
@@ -498,16 +522,19 @@ int enf_tail_loss_parts(const EnfDims& m) {
 }
 
 static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part);
+                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
+                            bool per_value);
 
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                         const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
-  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, gscale, loss, dybar, delta, act, st, loss_part)) return rc;
+                         const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
+                         bool per_value) {
+  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, gscale, loss, dybar, delta, act, st, loss_part, per_value)) return rc;
   return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
 }
 
 static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
+                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
+                            bool per_value) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
   A.loss_part = loss_part;
@@ -516,7 +543,7 @@ static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* bl
   A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
 #define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH) return m.bf16 ? launch_tail<DD, HH, true>(A, true, false, st) : launch_tail<DD, HH, false>(A, true, false, st);
+  if (m.D == DD && m.H == HH) return m.bf16 ? launch_tail<DD, HH, true>(A, true, false, st, per_value) : launch_tail<DD, HH, false>(A, true, false, st, per_value);
   ENF_CASE(128, 2)
   ENF_CASE(64, 2)
   ENF_CASE(128, 1)

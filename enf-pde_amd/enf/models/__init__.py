@@ -511,7 +511,8 @@ class EquivariantCrossAttentionNeF:
         return cm()
 
     @torch.no_grad()
-    def mse_value_and_latent_grads(self, params, x, p, a, gaussian_window_size, target, grad_scale=1.0, loss_out=None, weight=None):
+    def mse_value_and_latent_grads(self, params, x, p, a, gaussian_window_size, target, grad_scale=1.0, loss_out=None, weight=None,
+                                   channel_weight=None):
         """loss = mean((nef.apply(params, x, p, a, window) - target)^2) and grad_scale * d loss / d(p, a, window) in one
         sequence of HIP launches (forward, loss + d out, backward), without building an autograd graph: what one
         inner step of the MAML loop computes (pde_trainer.py:175-207; grad_scale = B there).
@@ -519,7 +520,16 @@ class EquivariantCrossAttentionNeF:
         ``weight``: None, or (B, N) loss weights per signal and query point, finite and >= 0 (include/enf_hip.h, "Weighted
         loss"): loss = sum_{b,n} weight[b,n] sum_o (out - target)^2 / (B N O), not normalised here (fitting/weights.py does
         that); a point of weight 0 does not exist -- its target may be NaN.
+        ``channel_weight``: None, or (B, N, O) loss weights per signal, query point and output channel (the same section:
+        enf_fit_step_cw): loss = sum_{b,n,o} channel_weight[b,n,o] (out - target)^2 / (B N O); the rule holds per value.  Not
+        together with ``weight`` (ValueError).
         Returns (loss (1,), dp, da, dwindow or None)."""
+        if channel_weight is not None:
+            if weight is not None:
+                raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
+            if tuple(channel_weight.shape) != (p.shape[0], x.shape[1], self.num_out):
+                raise ValueError(f"channel_weight has shape {tuple(channel_weight.shape)}, expected {(p.shape[0], x.shape[1], self.num_out)}")
+            channel_weight = channel_weight.float().contiguous()
         if weight is not None:
             if tuple(weight.shape) != (p.shape[0], x.shape[1]):
                 raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(p.shape[0], x.shape[1])}")
@@ -531,7 +541,10 @@ class EquivariantCrossAttentionNeF:
                 leaves = [t.detach().float().requires_grad_(True) for t in (p, a)] + \
                          ([sigma.detach().float().requires_grad_(True)] if sigma is not None else [])
                 out = self.apply(params, x, leaves[0], leaves[1], leaves[2] if sigma is not None else None)
-                if weight is None:
+                if channel_weight is not None:
+                    dd = torch.where(channel_weight > 0, out - target, torch.zeros_like(out))
+                    loss = (channel_weight * dd * dd).mean()
+                elif weight is None:
                     loss = ((out - target) ** 2).mean()
                 else:
                     wgt = weight[..., None]
@@ -567,8 +580,12 @@ class EquivariantCrossAttentionNeF:
             dout = torch.empty_like(out)
             nmse = int(lib.enf_mse_scratch_bytes(out.numel(), det))
             mse_scr = torch.empty(nmse, device=dev, dtype=torch.uint8) if nmse else None
-            _lib.launch(dev, lib.enf_mse_value_grad_w, _ptr(out), _ptr(tgt), _ptr(weight), out.numel(), self.num_out, float(grad_scale),
-                        _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
+            if channel_weight is not None:
+                _lib.launch(dev, lib.enf_mse_value_grad_cw, _ptr(out), _ptr(tgt), _ptr(channel_weight), out.numel(), float(grad_scale),
+                            _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
+            else:
+                _lib.launch(dev, lib.enf_mse_value_grad_w, _ptr(out), _ptr(tgt), _ptr(weight), out.numel(), self.num_out, float(grad_scale),
+                            _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
             _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_),
                         _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(),
                         1 | 2 | 4 | det, st)
@@ -576,6 +593,11 @@ class EquivariantCrossAttentionNeF:
             return loss, dp, da, (dsig if sigma is not None else None)
         # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
         # the loss and its gradient formed in registers, pair backward, prologue backward
+        if channel_weight is not None:      # the same sequence, the tail's per-channel instantiation
+            _lib.launch(dev, lib.enf_fit_step_cw, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                        float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(channel_weight), det, st)
+            self._ws_touch(ws)
+            return loss, dp, da, (dsig if sigma is not None else None)
         _lib.launch(dev, lib.enf_fit_step_w, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
                     float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(weight), det, st)
         self._ws_touch(ws)

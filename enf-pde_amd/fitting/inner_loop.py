@@ -52,7 +52,8 @@ def make_signal_masks(weights_or_valid, num_sampled, num_inner_steps, generator=
 def gather_signal_points(coords, img, masks, weights=None):
     """What enf_fit_inputs_b gathers, in torch ops: coords (N, dx), img (B, N, O), masks (B, N_s, S1) long, weights (B, N) or None
     -> xs (S1, B, N_s, dx), ys (S1, B, N_s, O), ws (S1, B, N_s).  An index outside [0, N) gives coords[0], zero targets and weight 0;
-    without ``weights`` ws is 1 for an index in range."""
+    without ``weights`` ws is 1 for an index in range.  Channel weights (B, N, O) give ws (S1, B, N_s, O), a row of O zeros for an
+    index outside (enf_fit_inputs_cw)."""
     B, N, O = img.shape
     S1 = masks.shape[2]
     idx = masks.permute(2, 0, 1)
@@ -61,13 +62,19 @@ def gather_signal_points(coords, img, masks, weights=None):
     xs = coords[ic]
     ys = torch.gather(img[None].expand(S1, -1, -1, -1), 2, ic[..., None].expand(-1, -1, -1, O))
     ys = torch.where(ok[..., None], ys, torch.zeros_like(ys))
+    if weights is not None and weights.dim() == 3:
+        w = torch.gather(weights[None].expand(S1, -1, -1, -1), 2, ic[..., None].expand(-1, -1, -1, O)).float()
+        return xs.contiguous(), ys.float().contiguous(), torch.where(ok[..., None], w, torch.zeros_like(w)).contiguous()
     w = torch.gather(weights[None].expand(S1, -1, -1), 2, ic) if weights is not None else torch.ones(ic.shape, device=img.device)
     ws = torch.where(ok, w.float(), torch.zeros_like(w, dtype=torch.float32))
     return xs.contiguous(), ys.float().contiguous(), ws.contiguous()
 
 
-def normalize_sampled_weights(ws):
-    """ws (..., N_s) >= 0 -> the same with mean 1 over every signal's N_s samples; a signal whose samples sum to zero stays zero."""
+def normalize_sampled_weights(ws, channel=False):
+    """ws (..., N_s) >= 0 -> the same with mean 1 over every signal's N_s samples; a signal whose samples sum to zero stays zero.
+    ``channel``: ws is (..., N_s, O) and the mean is over every signal's N_s * O sampled values."""
+    if channel:
+        return normalize_sampled_weights(ws.reshape(*ws.shape[:-2], -1)).reshape(ws.shape)
     total = ws.sum(dim=-1, keepdim=True)
     return torch.where(total > 0, ws * (ws.shape[-1] / torch.where(total > 0, total, torch.ones_like(total))), torch.zeros_like(ws))
 
@@ -75,11 +82,12 @@ def normalize_sampled_weights(ws):
 FUSED_FIT_INPUTS = __import__("os").environ.get("ENF_FIT_INPUTS") != "0"
 
 
-def _fit_inputs(latents0, coords, img, masks, weights=None):
+def _fit_inputs(latents0, coords, img, masks, weights=None, channel=False):
     """enf_fit_inputs[_w] (include/enf_hip.h): (lat, xs_all, ys_all, losses) of inner_loop in one launch, or None where the
     arguments are not what the kernel takes (fp32, contiguous, on one GPU, at most four latent components of leading dimension 1).
     With ``weights`` (B, N) a fifth value, their gather ws_all (S1, B, Ns).  Per-signal ``masks`` (B, Ns, S1) go to enf_fit_inputs_b:
-    xs_all is then (S1, B, Ns, dx) and ws_all is always returned."""
+    xs_all is then (S1, B, Ns, dx) and ws_all is always returned.  ``channel``: ``weights`` are per-channel, (B, N, O); both mask
+    layouts go to enf_fit_inputs_cw and ws_all is (S1, B, Ns, O)."""
     ts = list(latents0.values()) + [coords, img] + ([weights] if weights is not None else [])
     per_signal = masks.dim() == 3          # masks (B, Ns, S1): enf_fit_inputs_b, xs (S1, B, Ns, dx) and ws always (1 / 0 without weights)
     if not (img.is_cuda and masks.is_cuda and masks.dtype == torch.int64 and masks.dim() in (2, 3) and masks.is_contiguous() and coords.dim() == 2
@@ -105,6 +113,12 @@ def _fit_inputs(latents0, coords, img, masks, weights=None):
         keep.append(src)
         comps[i] = _lib.EnfFitComponent(src.data_ptr(), lat[k].data_ptr(), v.shape[2], 0)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    if channel:
+        ws = torch.empty((S1, B, Ns, O), device=dev, dtype=torch.float32)
+        _lib.launch(dev, _lib.load().enf_fit_inputs_cw, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(),
+                    img.data_ptr(), masks.data_ptr(), xs.data_ptr(), ys.data_ptr(), losses.data_ptr(), weights.data_ptr(), ws.data_ptr(),
+                    1 if per_signal else 0, st)
+        return lat, xs, ys, losses, ws
     ws = torch.empty((S1, B, Ns), device=dev, dtype=torch.float32) if weights is not None or per_signal else None
     if per_signal:
         _lib.launch(dev, _lib.load().enf_fit_inputs_b, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(),
@@ -147,7 +161,7 @@ def meta_sgd_update(lat, grads, lrs, scale):
 
 
 def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
-               noise_pos=0.0, generator=None, weights=None, normalize_weights=False):
+               noise_pos=0.0, generator=None, weights=None, normalize_weights=False, channel_weights=None):
     """Fit per-signal latents with S steps of meta-SGD (pde_trainer.py:156-235).
 
     latents0 : {'p_pos','a','gaussian_window'[,'p_ori']} with leading dim 1 (the meta-init)
@@ -165,7 +179,12 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     normalize_weights : rescale every signal's sampled weights ws[s, b, :] to mean 1 over its N_s samples before each step (a zero
                sum stays zero), so that a signal with few valid samples takes a step as long as a fully sampled one.  Off by
                default: the loss is the library's un-normalised 1 / (B N_s O) sum, as with ``weights`` alone.  Needs sampled
-               weights (``weights`` or per-signal masks).
+               weights (``weights``, ``channel_weights`` or per-signal masks).
+    channel_weights : None, or (B, N, O) loss weights per value on the full grid, finite and >= 0 (fitting/weights.py:
+               prepare_channel_weights), for fields whose variables are observed separately; not together with ``weights``.  They are
+               gathered with the targets in the same launch (enf_fit_inputs_cw, either mask layout) and every step runs
+               enf_fit_step_cw; a value of weight 0 does not exist, its target may be NaN.  ``normalize_weights`` then rescales to
+               mean 1 over every signal's N_s * O sampled values.  None takes the code path above unchanged.
     Returns (loss on the last mask, fitted latents dict with leading dim B).
     """
     B = img.shape[0]
@@ -174,6 +193,29 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         raise ValueError(f"per-signal masks have shape {tuple(masks.shape)}, expected ({B}, N_s, S + 1)")
     S = masks.shape[-1] - 1
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
+    channel = channel_weights is not None
+    if channel:
+        if weights is not None:
+            raise ValueError("pass weights= (B, N) or channel_weights= (B, N, O), not both")
+        if tuple(channel_weights.shape) != tuple(img.shape):
+            raise ValueError(f"channel_weights have shape {tuple(channel_weights.shape)}, expected {tuple(img.shape)}")
+        cw = channel_weights.to(device=img.device, dtype=torch.float32).contiguous()
+        fused = _fit_inputs(latents0, coords, img, masks, cw, channel=True) if FUSED_FIT_INPUTS else None
+        if fused is not None:
+            lat, xs_all, ys_all, losses, ws_all = fused
+        else:
+            lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
+            losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)
+            if per_signal:
+                xs_all, ys_all, ws_all = gather_signal_points(coords, img, masks, cw)
+            else:
+                masks_t = masks.t().contiguous()
+                xs_all, ys_all = coords[masks_t], img[:, masks_t].transpose(0, 1).float().contiguous()
+                ws_all = gather_point_weights(cw, masks)                             # (S+1, B, N_s, O)
+        if normalize_weights:
+            ws_all = normalize_sampled_weights(ws_all, channel=True)
+        return _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_signal, S, B, n_ori,
+                            optimize_gaussian_window, noise_pos, generator)
     if weights is not None:
         if tuple(weights.shape) != tuple(img.shape[:2]):
             raise ValueError(f"weights have shape {tuple(weights.shape)}, expected {tuple(img.shape[:2])}")
@@ -228,6 +270,36 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         else:
             _lib.launch(out.device, _lib.load().enf_mse_value_grad_w, out.data_ptr(), ys_all[S].data_ptr(), ws_all[S].data_ptr(),
                         out.numel(), out.shape[-1], 1.0, None, losses[S:].data_ptr(), None, 0, 0, st)
+    return losses[S], lat
+
+
+def _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_signal, S, B, n_ori, optimize_gaussian_window,
+                 noise_pos, generator):
+    """The S meta-SGD steps and the final loss of inner_loop for per-channel weights ws_all (S+1, B, N_s, O): the same sequence with
+    enf_fit_step_cw / enf_mse_value_grad_cw."""
+    if noise_pos:
+        lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
+                                                  device="cpu").to(lat["p_pos"].device) * noise_pos
+    n_pos = lat["p_pos"].shape[-1]
+    for s in range(S):
+        xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)
+        _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
+                                                         lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
+                                                         channel_weight=ws_all[s])
+        grads = {"p_pos": dp[..., :n_pos], "a": da}
+        if n_ori > 0:
+            grads["p_ori"] = dp[..., n_pos:]
+        if optimize_gaussian_window and dsig is not None:
+            grads["gaussian_window"] = dsig
+        lat = meta_sgd_update(lat, grads, lrs, B)
+    with torch.no_grad():
+        xs = xs_all[S] if per_signal else xs_all[S][None].expand(B, -1, -1)
+        out = nef.apply(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window")).float().contiguous()
+        st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
+        if out.shape != ys_all[S].shape:
+            raise AssertionError(f"targets have shape {tuple(ys_all[S].shape)}, expected {tuple(out.shape)}")
+        _lib.launch(out.device, _lib.load().enf_mse_value_grad_cw, out.data_ptr(), ys_all[S].data_ptr(), ws_all[S].data_ptr(),
+                    out.numel(), 1.0, None, losses[S:].data_ptr(), None, 0, 0, st)
     return losses[S], lat
 
 

@@ -9,7 +9,7 @@ from the inner loop, the auto-decoder trainer from its latent table; from there 
 import torch
 
 from ..inner_loop import _pose
-from ..weights import normalize_point_weights, prepare_point_weights, weighted_mse
+from ..weights import normalize_point_weights, prepare_point_weights, weighted_mse, normalize_channel_weights, prepare_channel_weights
 from .trainer_utils.solvers import solve_latent_ode
 
 
@@ -39,16 +39,18 @@ def draw_point_masks(num_points, num_sampled, num_frames, generator=None, device
 def sample_frames(coords, traj, point_masks=None, weights=None):
     """Queries and targets of the B T signal-frames: ``coords`` (N, dx), ``traj`` (B, T, N, O), ``point_masks`` (T, n_s) long or
     None for the full grid.  Returns xs (B T, n, dx) and ys (B T, n, O), signal-major like the flattened roll-out; with
-    ``weights`` (B, T, N) also their gather ws (B T, n)."""
+    ``weights`` (B, T, N) also their gather ws (B T, n); per-channel weights (B, T, N, O) give ws (B T, n, O)."""
     B, T, N, O = traj.shape
     if point_masks is None:
         xs, ys = coords[None].expand(B * T, -1, -1), traj.reshape(B * T, N, O)
-        return (xs, ys) if weights is None else (xs, ys, weights.reshape(B * T, N))
+        return (xs, ys) if weights is None else (xs, ys, weights.reshape(B * T, N, *weights.shape[3:]))
     n_s = point_masks.shape[1]
     xs = coords[point_masks][None].expand(B, -1, -1, -1).reshape(B * T, n_s, -1)
     ys = torch.gather(traj, 2, point_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n_s, O)
     if weights is None:
         return xs, ys
+    if weights.dim() == 4:
+        return xs, ys, torch.gather(weights, 2, point_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n_s, O)
     return xs, ys, torch.gather(weights, 2, point_masks[None].expand(B, -1, -1)).reshape(B * T, n_s)
 
 
@@ -64,6 +66,22 @@ def frame_weights(weights, B, T, N, normalize=True, device=None):
         w = normalize_point_weights(w) if normalize else w
         return w.to(device) if device is not None else w
     return prepare_point_weights(w, B, N, normalize, device)[:, None].expand(B, T, N)
+
+
+def frame_channel_weights(weights, B, T, N, O, normalize=True, device=None):
+    """Per-channel ``weights`` (N, O), (B, N, O) or (B, T, N, O) -> float32 (B, T, N, O), every signal-frame's weights of mean 1 over
+    its N * O values unless ``normalize`` is False (fitting/weights.py); None stays None."""
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights, dtype=torch.float32)
+    if w.dim() == 4:
+        if tuple(w.shape) != (B, T, N, O):
+            raise ValueError(f"channel weights have shape {tuple(w.shape)}, expected {(B, T, N, O)}, {(B, N, O)} or {(N, O)}")
+        if bool((w < 0).any()) or not bool(torch.isfinite(w).all()):
+            raise ValueError("channel weights must be finite and >= 0")
+        w = normalize_channel_weights(w) if normalize else w
+        return w.to(device) if device is not None else w
+    return prepare_channel_weights(w, B, N, O, normalize, device)[:, None].expand(B, T, N, O)
 
 
 class LatentODEMixin:
@@ -121,12 +139,15 @@ class LatentODEMixin:
         return [t.detach().requires_grad_(True) for t in _leaves(ode_params)], False
 
     def rollout_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False, weights=None,
-                     normalize=True):
+                     normalize=True, channel_weights=None):
         """Roll ``lat`` out over the frames of ``trajectory`` (B, T, *grid, O), decode every frame in ONE nef.apply over the
         B T signal-frames (at ``max_num_sampled_points`` random grid points per frame when the grid is larger) and return the
         mean squared error.  ``point_masks`` (T, n_s) long, or None to draw them from ``generator``.
         ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1
-        per signal-frame before the points are sampled unless ``normalize`` is False; they are gathered with the point masks."""
+        per signal-frame before the points are sampled unless ``normalize`` is False; they are gathered with the point masks.
+        ``channel_weights``: None, or per-channel (N, O) / (B, N, O) / (B, T, N, O) weights, treated alike; not with ``weights``."""
+        if channel_weights is not None and weights is not None:
+            raise ValueError("pass weights= or channel_weights=, not both")
         B, T = trajectory.shape[:2]
         sol = self.rollout(ode_params, lat, T, graph=graph)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
@@ -137,6 +158,10 @@ class LatentODEMixin:
                 point_masks = draw_point_masks(N, n_s, T, generator, self.coords.device)
         else:
             point_masks = None
+        if channel_weights is not None:
+            fw = frame_channel_weights(channel_weights, B, T, N, traj.shape[-1], normalize, traj.device)
+            xs, ys, ws = sample_frames(self.coords, traj, point_masks, fw)
+            return weighted_mse(self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl), ys, ws)
         if weights is None:
             xs, ys = sample_frames(self.coords, traj, point_masks)
             recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)

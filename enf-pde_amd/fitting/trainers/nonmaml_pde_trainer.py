@@ -30,8 +30,9 @@ import torch
 from ..optim import Adam, AdamW, clip_by_global_norm, global_norm, scatter_rows, table_adam_update
 from ..parallel import allreduce_mean_
 from ..inner_loop import decode, make_signal_masks, gather_signal_points
-from ..weights import prepare_point_weights, weighted_mse, observed_sampling_weights
-from .latent_ode import LatentODEMixin, frame_weights, _leaves, _unflatten
+from ..weights import prepare_point_weights, weighted_mse, observed_sampling_weights, prepare_channel_weights, \
+    observed_channel_sampling_weights, point_support
+from .latent_ode import LatentODEMixin, frame_weights, frame_channel_weights, _leaves, _unflatten
 from .pde_trainer import _tree_from_tensors
 
 TRAIN_FRAMES, VAL_FRAMES = 10, 20            # fixed in the reference (:206,241,252), not read from the dataset config
@@ -104,12 +105,27 @@ class NonMetaPDETrainer(LatentODEMixin):
         state, epoch, _ = load_train_state(path, self.init_train_state(**init_kwargs))
         return state, epoch
 
-    def _fit_points(self, state, initial_state, mask, weights, normalize):
+    def _fit_points(self, state, initial_state, mask, weights, normalize, channel_weights=None):
         """What a nef step fits on (:311-335): (targets (B, n, O), coordinates (n, dx), loss weights (B, n) or None, per-signal
         coordinates (B, n, dx) or None).  The one place where a nef step draws from ``state.rng``: loss_and_grads and
-        fit_latents_step both call it, so the two consume the generator alike."""
+        fit_latents_step both call it, so the two consume the generator alike.  With ``channel_weights`` (N, O) / (B, N, O) the
+        third value is per-channel, (B, n, O), and a point counts as observed where any of its channels is."""
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
+        if channel_weights is not None:
+            if weights is not None:
+                raise ValueError("pass weights= or channel_weights=, not both")
+            cw = prepare_channel_weights(channel_weights, *img.shape, normalize, img.device)
+            if mask is not None:
+                img, coords, cw = img[:, mask], coords[mask], cw[:, mask]
+            npts, xs = self.config.training.max_num_sampled_points, None
+            if self.sample_observed:
+                m = make_signal_masks(point_support(cw), min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
+                xs, img, cw = (t[0] for t in gather_signal_points(coords, img, m, observed_channel_sampling_weights(cw, m.shape[1])))
+            elif npts < coords.shape[0]:
+                sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
+                img, coords, cw = img[:, sub], coords[sub], cw[:, sub]
+            return img, coords, cw.contiguous(), xs
         pw = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
         if mask is not None:                                                              # :321-323
             img, coords = img[:, mask], coords[mask]
@@ -126,11 +142,13 @@ class NonMetaPDETrainer(LatentODEMixin):
             pw = None if pw is None else pw[:, sub]
         return img, coords, pw, xs
 
-    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True):
+    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None):
         """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
-        before ``mask`` and the point sampling unless ``normalize`` is False."""
-        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize)
+        before ``mask`` and the point sampling unless ``normalize`` is False.
+        ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (mean 1 over each signal's N * O values unless
+        ``normalize`` is False), for fields whose variables are observed separately; not together with ``weights``."""
+        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
@@ -145,9 +163,9 @@ class NonMetaPDETrainer(LatentODEMixin):
         ga = [torch.zeros_like(leaves[k]) if gi is None else gi for k, gi in zip(names, g[len(w):])]
         return loss.detach(), gw, dict(zip(names, ga))
 
-    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True):
+    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True, channel_weights=None):
         initial_state, traj_idx = batch
-        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize)
+        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize, channel_weights)
         names = list(ga.keys())
         flat = gw + [ga[k] for k in names] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=initial_state.shape[0])
@@ -163,16 +181,17 @@ class NonMetaPDETrainer(LatentODEMixin):
         return loss, NonMetaTrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state,
                                        ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True):
-        """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137); ``weights`` as in loss_and_grads"""
-        return self._step(state, batch, mask, True, weights, normalize)
+    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None):
+        """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137); ``weights`` / ``channel_weights`` as in
+        loss_and_grads"""
+        return self._step(state, batch, mask, True, weights, normalize, channel_weights)
 
-    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True):
+    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None):
         """Only the latents move (:139-171)."""
-        return self._step(state, batch, mask, False, weights, normalize)
+        return self._step(state, batch, mask, False, weights, normalize, channel_weights)
 
     @torch.no_grad()
-    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True):
+    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None):
         """nef_train_step_autodec_only (:139-171) on the native latent-only path: same arguments, same (loss, new_state), same draw
         from ``state.rng`` (_fit_points), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
         are read under no_grad, ONE nef.mse_value_and_latent_grads (enf_fit_step_w: forward, fused weighted loss, backward to the
@@ -181,16 +200,20 @@ class NonMetaPDETrainer(LatentODEMixin):
         outside the batch move by their momentum only, as in _step.  A shared point subset is passed as a stride-0 ``x``.
         The nef parameters, ``nef_opt_state`` and ``ode_opt_state`` are handed on untouched.  In a multi-rank run the gathered
         gradients are scattered to dense tensors, averaged with the loss by the flat all-reduce of _step, and the kernel runs in
-        its dense form (idx = None).  This is the step validate_epoch repeats; nef_train_step_autodec_only stays as it is."""
+        its dense form (idx = None).  This is the step validate_epoch repeats; nef_train_step_autodec_only stays as it is.
+        ``channel_weights`` (N, O) / (B, N, O): the one fit call is enf_fit_step_cw; still one fit call and one table update."""
         initial_state, traj_idx = batch
-        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize)
+        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         tables = [P[k].detach() for k in names]
         p, a, window = self.autodecoder.apply({"params": dict(zip(names, tables))}, traj_idx)
         if xs is None:
             xs = coords[None].expand(img.shape[0], -1, -1)
-        loss, dp, da, dwin = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, weight=pw)
+        if channel_weights is not None:
+            loss, dp, da, dwin = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, channel_weight=pw)
+        else:
+            loss, dp, da, dwin = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, weight=pw)
         loss = loss.reshape(())
         n_pos = P["p_pos"].shape[-1]
         by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dwin}
@@ -263,13 +286,17 @@ class NonMetaPDETrainer(LatentODEMixin):
                                               step=state.step + 1, rng=state.rng)
 
     @torch.no_grad()
-    def val_step(self, state, batch, autodecoder=None, weights=None, normalize=True):
+    def val_step(self, state, batch, autodecoder=None, weights=None, normalize=True, channel_weights=None):
         """:201-241: ``batch`` = (trajectory, traj_idx) or (trajectory, _, traj_idx), read as ``batch[0]`` and ``batch[-1]`` like
         ode_train_step's.  The first 20 frames against the roll-out of the rows ``traj_idx`` of ``state.params['autodecoder']``, read
         through ``autodecoder`` (a shell for validation signals; default: the trainer's own), decoded on the full grid in chunks of
         max_num_sampled_points.  Returns (mse over frames 0..9, mse over frames 10..19); a trajectory of at most 10 frames gives
-        zero for the second.  Roll-outs of more than 4 frames replay one captured hipGraph per derivative evaluation."""
+        zero for the second.  Roll-outs of more than 4 frames replay one captured hipGraph per derivative evaluation.
+        ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value; the two errors are then weighted per value
+        (a NaN under a zero weight does not count); not together with ``weights``."""
         self._need_ode("val_step")
+        if channel_weights is not None and weights is not None:
+            raise ValueError("pass weights= or channel_weights=, not both")
         trajectory, traj_idx = batch[0], batch[-1]
         trajectory = trajectory[:, :VAL_FRAMES]                                  # :206
         B, T = trajectory.shape[:2]
@@ -278,6 +305,13 @@ class NonMetaPDETrainer(LatentODEMixin):
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl,
                        chunk=self.config.training.max_num_sampled_points).reshape(trajectory.shape)    # :228-238
+        if channel_weights is not None:
+            N, O, F = self.coords.shape[0], trajectory.shape[-1], TRAIN_FRAMES
+            cw = torch.as_tensor(channel_weights)
+            fw = frame_channel_weights(cw[:, :T] if cw.dim() == 4 else cw, B, T, N, O, normalize, recon.device)
+            rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
+            return weighted_mse(rec[:, :F], tgt[:, :F], fw[:, :F]), \
+                (weighted_mse(rec[:, F:], tgt[:, F:], fw[:, F:]) if T > F else recon.new_zeros(()))
         if weights is None:
             err = (recon - trajectory) ** 2
             return err[:, :TRAIN_FRAMES].mean(), (err[:, TRAIN_FRAMES:].mean() if T > TRAIN_FRAMES else err.new_zeros(()))
@@ -291,7 +325,7 @@ class NonMetaPDETrainer(LatentODEMixin):
             (weighted_mse(rec[:, F:], tgt[:, F:], fw[:, F:]) if T > F else recon.new_zeros(()))
 
     def validate_epoch(self, state, train_loader, val_loader, val_autodecoder, *, drop_rates=(0.0, 0.05, 0.1, 0.5), epochs=None,
-                       fit_train=True):
+                       fit_train=True, channel_weights=None):
         """:399-548, without its logging and plots.  Validating an auto-decoder means fitting a FRESH latent table to the signals
         with the decoder frozen, then rolling the fitted rows out.  Returns (metrics, the last validation state):
 
@@ -310,8 +344,17 @@ class NonMetaPDETrainer(LatentODEMixin):
             default is train_until_epoch - 1 passes;
           - drop-out: the mask of rate R is ``permutation(N)[:int(N * R)]`` (:452-455), and nef_loss indexes WITH it
             (``initial_state[:, mask]``, :321), so it KEEPS int(N * R) points: R = 0.05 fits on 5 % of the grid.  It is drawn once
-            per rate and shared by the validation and the training fit; rate 0 has no mask."""
+            per rate and shared by the validation and the training fit; rate 0 has no mask.
+        ``channel_weights``: None, or a function ``batch -> (B, T, N, O) or (B, N, O) or (N, O)`` weights per value for that batch
+        (e.g. ``lambda b: valid_channel_weights(b[0].flatten(2, -2))``), or such a tensor for every batch: the fits run
+        fit_latents_step(channel_weights=) on frame 0's weights and the errors are val_step(channel_weights=)'s."""
         self._need_ode("validate_epoch")
+
+        def cw_of(batch, frame0):      # the extra keyword of the two steps; nothing without channel weights
+            if channel_weights is None:
+                return {}
+            cw = torch.as_tensor(channel_weights(batch) if callable(channel_weights) else channel_weights)
+            return {"channel_weights": cw[:, 0] if frame0 and cw.dim() == 4 else cw}
         if epochs is None:
             epochs = self.config.training.nef.train_until_epoch - 1
         dev, N = self.coords.device, self.coords.shape[0]
@@ -319,7 +362,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         def rollout_errors(st, loader, shell):
             tot_in, tot_out, n = 0.0, 0.0, 0
             for batch in loader:
-                e_in, e_out = self.val_step(st, batch, autodecoder=shell)
+                e_in, e_out = self.val_step(st, batch, autodecoder=shell, **cw_of(batch, False))
                 tot_in, tot_out, n = tot_in + e_in, tot_out + e_out, n + 1
             return float(tot_in) / max(n, 1), float(tot_out) / max(n, 1)
 
@@ -330,7 +373,7 @@ class NonMetaPDETrainer(LatentODEMixin):
                                    ode_opt_state=state.ode_opt_state, step=state.step, rng=state.rng)
             for _ in range(epochs):
                 for batch in loader:
-                    _, st = self.fit_latents_step(st, (batch[0][:, 0], batch[-1]), mask=dp_mask)
+                    _, st = self.fit_latents_step(st, (batch[0][:, 0], batch[-1]), mask=dp_mask, **cw_of(batch, True))
             return st
 
         metrics = {}

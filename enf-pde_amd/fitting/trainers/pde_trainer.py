@@ -43,10 +43,11 @@ from types import SimpleNamespace
 import torch
 
 from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
-from .latent_ode import LatentODEMixin, draw_point_masks, frame_weights, _leaves, _unflatten
+from .latent_ode import LatentODEMixin, draw_point_masks, frame_weights, frame_channel_weights, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
-from ..weights import prepare_point_weights, weighted_mse, normalize_point_weights, observed_sampling_weights
+from ..weights import prepare_point_weights, weighted_mse, normalize_point_weights, observed_sampling_weights, \
+    prepare_channel_weights, normalize_channel_weights, observed_channel_sampling_weights, point_support
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
@@ -66,7 +67,8 @@ def _tree_from_tensors(tensors, nef=None):
 def _sampled(coords, img, masks, s, weights, copies=1):
     """The points of step ``s``: (xs (copies * B, N_s, dx), ys (B, N_s, O), weights (B, N_s) or None).  Shared masks (N_s, S+1) give
     the reference's gather (pde_trainer.py:193-197) with a stride-0 batch; per-signal masks (B, N_s, S+1) give every signal its own
-    points and always weights (0 where the sampler padded with -1; fitting/inner_loop.py: gather_signal_points)."""
+    points and always weights (0 where the sampler padded with -1; fitting/inner_loop.py: gather_signal_points).  Per-channel
+    ``weights`` (B, N, O) come back as (B, N_s, O); weighted_mse tells the two apart by their rank."""
     B = img.shape[0]
     if masks.dim() == 2:
         m = masks[:, s]
@@ -125,7 +127,7 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
 
 def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
                    second_order="fd", fd_step=None, noise_pos=0.0, generator=None, terminal=None, freeze_relu=True,
-                   weights=None, normalize=True):
+                   weights=None, normalize=True, channel_weights=None):
     """Value and gradient of the last-inner-step loss w.r.t. (nef weights, meta-init latents, inner lrs).
 
     Returns (loss, grads) with grads = {'nef': [46 tensors in ENF_W_* order], 'autodecoder': {key: (1,Z,.)},
@@ -138,7 +140,12 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     unless ``normalize`` is False; they weigh every inner step's loss and the default terminal loss.
     ``masks``: (N_s, S+1), or per-signal (B, N_s, S+1) (make_signal_masks): the forward sweep, the terminal loss and the adjoint
     sweep's re-evaluations all gather the same per-signal points.
+    ``channel_weights``: None, or (N, O) / (B, N, O) loss weights per value (fitting/weights.py: prepare_channel_weights), mean 1
+    over each signal's N * O values unless ``normalize`` is False; not together with ``weights``.  Every pass that takes the
+    per-point weights -- the inner steps, the terminal loss and both perturbed passes of the finite differences -- takes these.
     """
+    if channel_weights is not None and weights is not None:
+        raise ValueError("pass weights= or channel_weights=, not both")
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
     if fd_step is None:      # truncation (~step^2) against the rounding of the first-order gradients (~1 / step): bf16 kernels
@@ -146,6 +153,8 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     B = img.shape[0]
     S = masks.shape[-1] - 1
     pw = prepare_point_weights(weights, B, img.shape[1], normalize, img.device)
+    if channel_weights is not None:
+        pw = prepare_channel_weights(channel_weights, B, img.shape[1], img.shape[2], normalize, img.device)
     weights = nef.param_tensors(nef_params)
     frozen = _tree_from_tensors([t.detach() if t is not None else None for t in weights], nef)           # inference path for the inner steps
     lat = {k: v.detach().repeat_interleave(B, dim=0).clone() for k, v in latents0.items()}
@@ -305,14 +314,25 @@ class MetaSGDPDETrainer(LatentODEMixin):
             return observed_sampling_weights(weights, masks.shape[1])
         return weights
 
-    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True):
+    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None):
         """One outer step on ``batch`` = (B, N, O) initial states (trajectory[:, 0], pde_trainer.py:485-487).
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (meta_gradients).
+        ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (meta_gradients); with ``sample_observed`` the masks are
+        drawn from the points that carry at least one observed value (point_support).
         Returns (recon_loss, new_state).  In a multi-rank run every rank passes its shard of the meta-batch;
         the outer gradients are averaged with one flat all-reduce before the (identical) optimiser updates."""
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
-        if masks is None and self.sample_observed and weights is not None:
+        if channel_weights is not None:
+            if weights is not None:
+                raise ValueError("pass weights= or channel_weights=, not both")
+            channel_weights = prepare_channel_weights(channel_weights, *img.shape, normalize, img.device)
+            normalize = False
+            if masks is None:
+                masks = self._draw_masks(state, self.coords.shape[0], point_support(channel_weights))
+                if masks.dim() == 3:
+                    channel_weights = observed_channel_sampling_weights(channel_weights, masks.shape[1])
+        elif masks is None and self.sample_observed and weights is not None:
             weights = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
             masks = self._draw_masks(state, self.coords.shape[0], weights)
             weights, normalize = self._observed_weights(True, masks, weights), False
@@ -324,7 +344,7 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng,
-                                     weights=weights, normalize=normalize)
+                                     weights=weights, normalize=normalize, channel_weights=channel_weights)
         lat_keys, lr_keys = list(lat0.keys()), list(lrs.keys())
         flat = grads["nef"] + [grads["autodecoder"][k] for k in lat_keys] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])                               # one exchange per outer step
@@ -406,13 +426,19 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return (coords, img, masks) if weights is None else (coords, img, masks, weights)
 
     def ode_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False, weights=None,
-                 normalize=True):
+                 normalize=True, channel_weights=None):
         """pde_trainer.py:411-481 from the fitted latents on: roll the latents out over the training frames, decode every
         frame (at ``max_num_sampled_points`` random grid points per frame when the grid is larger) and compare.
         ``trajectory`` (B, T, *grid, O);  ``point_masks`` (T, n_s) long, or None to draw them.  The arithmetic (and
         ``rollout``) is latent_ode.LatentODEMixin's, shared with the auto-decoder trainer; ``weights`` as in rollout_loss."""
         return self.rollout_loss(nef_params, ode_params, lat, trajectory, point_masks, generator, graph=graph, weights=weights,
-                                 normalize=normalize)
+                                 normalize=normalize, channel_weights=channel_weights)
+
+    @staticmethod
+    def _frame0_channel_weights(channel_weights, B, N, O, normalize, device):
+        """The per-channel weights of the fit on frame 0, (B, N, O) float32, from (N, O), (B, N, O) or (B, T, N, O)."""
+        cw = torch.as_tensor(channel_weights)
+        return prepare_channel_weights(cw[:, 0] if cw.dim() == 4 else cw, B, N, O, normalize, device)
 
     @staticmethod
     def _frame0_weights(weights, B, N, normalize, device):
@@ -455,18 +481,32 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                        autodecoder_opt_state=state.autodecoder_opt_state, meta_sgd_opt_state=state.meta_sgd_opt_state,
                                        ode_opt_state=ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def dual_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True):
+    def dual_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True, channel_weights=None):
         """pde_trainer.py:320-358: the roll-out loss trains the nef weights (clip + AdamW), the inner learning rates (Adam,
         clipped) and the ODE parameters (Adam); the latent initialisation is left alone.  The nef / learning-rate
         gradients include the path through the inner loop (the same adjoint recursion as nef_train_step, started from
-        d loss / d fitted latents of the roll-out).  ``weights`` as in ode_train_step."""
+        d loss / d fitted latents of the roll-out).  ``weights`` as in ode_train_step.
+        ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value: frame 0's weigh the fit, all the roll-out
+        loss; not together with ``weights``."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]
+        if channel_weights is not None and weights is not None:
+            raise ValueError("pass weights= or channel_weights=, not both")
+        if channel_weights is not None and torch.as_tensor(channel_weights).dim() == 4:
+            channel_weights = torch.as_tensor(channel_weights)[:, :cfg.dataset.traj_len_train]
         if weights is not None and torch.as_tensor(weights).dim() == 3:
             weights = torch.as_tensor(weights)[:, :cfg.dataset.traj_len_train]
         w0 = self._frame0_weights(weights, trajectory.shape[0], self.coords.shape[0], normalize, self.coords.device)
         drew = masks is None
-        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=w0)
+        c0 = None
+        if channel_weights is not None:
+            c0 = self._frame0_channel_weights(channel_weights, trajectory.shape[0], self.coords.shape[0], trajectory.shape[-1], normalize,
+                                              self.coords.device)
+            coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=point_support(c0))
+            if drew and masks.dim() == 3:
+                c0 = observed_channel_sampling_weights(c0, masks.shape[1])
+        else:
+            coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=w0)
         w0 = self._observed_weights(drew, masks, w0)
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
@@ -480,7 +520,7 @@ class MetaSGDPDETrainer(LatentODEMixin):
             w = [t.detach().requires_grad_(True) for t in weights]
             lv = {k: lat[k].detach().requires_grad_(True) for k in lat}
             loss = self.ode_loss(_tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph,
-                                 weights=point_weights, normalize=normalize)
+                                 weights=point_weights, normalize=normalize, channel_weights=channel_weights)
             g = torch.autograd.grad(loss, w + [lv[k] for k in keys] + leaves, allow_unused=True)
             z = lambda t, gi: torch.zeros_like(t) if gi is None else gi
             side["ode"] = [z(t, gi) for t, gi in zip(leaves, g[len(w) + len(keys):])]
@@ -492,7 +532,7 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal,
-                                     weights=w0, normalize=False)
+                                     weights=w0, normalize=False, channel_weights=c0)
         lr_keys = list(lrs.keys())
         flat = grads["nef"] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + side["ode"] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])
@@ -543,7 +583,8 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return total / max(n, 1), state
 
     @torch.no_grad()
-    def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True, drop_rate=None):
+    def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True, drop_rate=None,
+                 channel_weights=None):
         """pde_trainer.py:360-409: fit the first frame, roll out over train + out-of-horizon frames, decode the full grid;
         returns (mse over the training horizon, mse beyond it).  ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on
         the full grid (fitting/weights.py; mean 1 per signal-frame unless ``normalize`` is False): frame 0's weigh the fit, and
@@ -552,7 +593,14 @@ class MetaSGDPDETrainer(LatentODEMixin):
         observed frame-0 points with probability 1 - r (drawn from the state's generator) and is fitted on per-signal masks of
         min(max_num_sampled_points, int((1 - r) N)) points from what it kept (make_signal_masks), with the kept points' weights
         renormalised and rescaled by observed_sampling_weights so that the fit's loss has the scale of a fit without drop-out; the
-        two errors are still taken over all valid points of the full grid."""
+        two errors are still taken over all valid points of the full grid.
+        ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value, used like ``weights`` (not together with
+        them): frame 0's weigh the fit, a point is observed where any of its channels is, and the two errors are weighted per
+        value -- a field with NaN in one variable validates on its other variables there."""
+        if channel_weights is not None:
+            if weights is not None:
+                raise ValueError("pass weights= or channel_weights=, not both")
+            return self._val_step_channel(state, trajectory, initial_state_dp, masks, channel_weights, normalize, drop_rate)
         cfg = self.config
         T_in = cfg.dataset.traj_len_train
         trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
@@ -594,6 +642,46 @@ class MetaSGDPDETrainer(LatentODEMixin):
             return err[:, :T_in].mean(), (err[:, T_in:].mean() if T > T_in else err.new_zeros(()))
         O = trajectory.shape[-1]
         fw = frame_weights(weights, B, T, N, normalize, recon.device)
+        rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
+        return weighted_mse(rec[:, :T_in], tgt[:, :T_in], fw[:, :T_in]), \
+            (weighted_mse(rec[:, T_in:], tgt[:, T_in:], fw[:, T_in:]) if T > T_in else recon.new_zeros(()))
+
+    @torch.no_grad()
+    def _val_step_channel(self, state, trajectory, initial_state_dp, masks, channel_weights, normalize, drop_rate):
+        """val_step with per-channel weights: the same sequence, the fit through inner_loop(channel_weights=)."""
+        cfg = self.config
+        T_in = cfg.dataset.traj_len_train
+        trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
+        B, T = trajectory.shape[:2]
+        N, O = self.coords.shape[0], trajectory.shape[-1]
+        cw = torch.as_tensor(channel_weights)
+        if cw.dim() == 4:
+            cw = cw[:, :T]
+        c0 = self._frame0_channel_weights(cw, B, N, O, normalize, self.coords.device)
+        if drop_rate is not None:
+            if not 0.0 <= drop_rate < 1.0:
+                raise ValueError(f"drop_rate must lie in [0, 1), got {drop_rate}")
+            if masks is not None or initial_state_dp > 0:
+                raise ValueError("drop_rate draws its own per-signal masks: pass neither masks nor initial_state_dp with it")
+            kept = (torch.rand((B, N), generator=state.rng) >= drop_rate) & (point_support(c0) > 0).cpu()
+            coords, img = self.coords, trajectory[:, 0].reshape(B, -1, O)
+            masks = make_signal_masks(kept, max(1, min(cfg.training.max_num_sampled_points, int((1.0 - drop_rate) * N))),
+                                      cfg.meta.num_inner_steps, generator=state.rng, device=coords.device)
+            c0 = c0 * kept.to(coords.device)[..., None]
+            c0 = observed_channel_sampling_weights(normalize_channel_weights(c0) if normalize else c0, masks.shape[1])
+        else:
+            drew = masks is None
+            coords, img, masks, c0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, c0,
+                                                               observed=point_support(c0))
+            if drew and masks.dim() == 3:
+                c0 = observed_channel_sampling_weights(c0, masks.shape[1])
+        with torch.enable_grad():
+            _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
+                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), channel_weights=c0)
+        sol = self.rollout(state.params["ode_params"], {k: v.detach() for k, v in lat.items()}, T, graph=T > 4)
+        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
+        recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl).reshape(trajectory.shape)
+        fw = frame_channel_weights(cw, B, T, N, O, normalize, recon.device)
         rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
         return weighted_mse(rec[:, :T_in], tgt[:, :T_in], fw[:, :T_in]), \
             (weighted_mse(rec[:, T_in:], tgt[:, T_in:], fw[:, T_in:]) if T > T_in else recon.new_zeros(()))

@@ -6,6 +6,15 @@ A point of weight 0 does not exist: its target may be NaN or Inf and never enter
 normalise; the trainers call ``normalize_point_weights`` once on the FULL grid, before any sampling, so that the loss on a
 random subset of points is an unbiased estimate of the full-grid weighted mean and weights of all ones change nothing.
 Where the subset is drawn per signal from its observed points only, ``observed_sampling_weights`` keeps that property.
+
+Per-channel weights (the same section of the header): one value per signal, grid point AND output channel, (B, N, O), for
+variables that are observed separately,
+
+    loss = 1 / (B N O) * sum_{b,n,o} cw[b,n,o] * (out[b,n,o] - target[b,n,o])^2
+
+with the same rule per value.  ``valid_channel_weights``, ``prepare_channel_weights``, ``point_support`` and
+``observed_channel_sampling_weights`` are the counterparts of the per-point helpers; ``weighted_mse`` and
+``gather_point_weights`` take either kind.
 Pure torch, no GPU needed.
 """
 import torch
@@ -52,6 +61,48 @@ def valid_weights(field):
     return torch.isfinite(field).all(dim=-1).to(torch.float32)
 
 
+def valid_channel_weights(field):
+    """``field`` (..., N, O) -> (..., N, O) float: 1 where the value is finite, 0 where it is NaN or Inf -- per value, not per point."""
+    return torch.isfinite(field).to(torch.float32)
+
+
+def normalize_channel_weights(cw):
+    """``cw`` (..., N, O) >= 0 -> the same weights with mean 1 over every signal's N * O values.  A signal whose weights are all zero
+    stays zero; weights of all ones come back as all ones exactly."""
+    cw = torch.as_tensor(cw)
+    if not cw.is_floating_point():
+        cw = cw.float()
+    if cw.dim() < 2:
+        raise ValueError(f"channel weights must be (..., N, O), got {tuple(cw.shape)}")
+    return normalize_point_weights(cw.reshape(*cw.shape[:-2], -1)).reshape(cw.shape)
+
+
+def prepare_channel_weights(weights, B, N, O, normalize=True, device=None):
+    """What a trainer does with its ``channel_weights`` argument: None stays None; (N, O) or (B, N, O) becomes float32 (B, N, O),
+    finite and >= 0 (ValueError otherwise), with mean 1 over each signal's N * O values unless ``normalize`` is False."""
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights, dtype=torch.float32)
+    if w.dim() == 2:
+        w = w[None].expand(B, -1, -1)
+    if tuple(w.shape) != (B, N, O):
+        raise ValueError(f"channel weights have shape {tuple(w.shape)}, expected {(B, N, O)} or {(N, O)}")
+    if normalize:
+        w = normalize_channel_weights(w)
+    elif bool((w < 0).any()) or not bool(torch.isfinite(w).all()):
+        raise ValueError("channel weights must be finite and >= 0")
+    return w.to(device).contiguous() if device is not None else w.contiguous()
+
+
+def point_support(cweights):
+    """Channel weights (..., N, O) -> point weights (..., N), > 0 exactly where at least one channel of the point is observed (the
+    sum over the channels).  What make_signal_masks takes, so that per-signal sampling draws from the points that carry a value."""
+    cw = torch.as_tensor(cweights)
+    if cw.dim() < 2:
+        raise ValueError(f"channel weights must be (..., N, O), got {tuple(cw.shape)}")
+    return cw.clamp_min(0).sum(dim=-1)
+
+
 def prepare_point_weights(weights, B, N, normalize=True, device=None):
     """What a trainer does with its ``weights`` argument: None stays None; (N,) or (B, N) becomes float32 (B, N), with
     mean 1 per signal unless ``normalize`` is False."""
@@ -68,7 +119,8 @@ def prepare_point_weights(weights, B, N, normalize=True, device=None):
 
 
 def gather_point_weights(weights, masks):
-    """weights (B, N), masks (N_s, S1) long -> (S1, B, N_s): ws[s, b, i] = weights[b, masks[i, s]] (what enf_fit_inputs_w gathers)."""
+    """weights (B, N), masks (N_s, S1) long -> (S1, B, N_s): ws[s, b, i] = weights[b, masks[i, s]] (what enf_fit_inputs_w gathers).
+    Channel weights (B, N, O) give (S1, B, N_s, O) the same way (enf_fit_inputs_cw)."""
     return weights[:, masks.t()].transpose(0, 1).contiguous()
 
 
@@ -92,11 +144,27 @@ def observed_sampling_weights(weights, num_sampled):
     return w * c
 
 
+def observed_channel_sampling_weights(cweights, num_sampled):
+    """observed_sampling_weights for channel weights (B, N, O): a point is observed where any of its channels is (point_support),
+    n_b counts those points, and the same factor c_b multiplies all channels of signal b's points."""
+    cw = torch.as_tensor(cweights)
+    N = cw.shape[-2]
+    n = (point_support(cw) > 0).sum(dim=-1, keepdim=True).to(cw.dtype)
+    c = n / N * (float(num_sampled) / n.clamp(min=1.0).clamp(max=float(num_sampled)))
+    return cw * c[..., None]
+
+
 def weighted_mse(out, target, weights=None):
-    """The loss above in torch (differentiable): ``out`` / ``target`` (..., N, O), ``weights`` (..., N) or None (the plain
-    mean).  Where the weight is 0 the target is not used: NaN there reaches neither the value nor a gradient."""
+    """The loss above in torch (differentiable): ``out`` / ``target`` (..., N, O), ``weights`` (..., N), per-channel (..., N, O)
+    -- told apart by their rank -- or None (the plain mean).  Where the weight is 0 the target is not used: NaN there reaches
+    neither the value nor a gradient."""
     if weights is None:
         return ((out - target) ** 2).mean()
-    w = weights[..., None].to(out.dtype)
+    if weights.dim() == out.dim():
+        if tuple(weights.shape) != tuple(out.shape):
+            raise ValueError(f"channel weights have shape {tuple(weights.shape)}, expected {tuple(out.shape)}")
+        w = weights.to(out.dtype)
+    else:
+        w = weights[..., None].to(out.dtype)
     d = torch.where(w > 0, out - target, torch.zeros_like(out))
     return (w * d * d).mean()

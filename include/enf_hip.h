@@ -338,6 +338,24 @@ int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const fl
                    const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
                    void* workspace, size_t workspace_bytes, const float* weight /* (B,N) or NULL */, unsigned flags, void* stream);
 
+/* Per-channel weights (enf_fit_step_cw, enf_mse_value_grad_cw, enf_fit_inputs_cw): variables that are observed separately -- a buoy
+ * that gives height but no vorticity, a retrieval that fails for one variable.  `cweight` is fp32 of shape (B, N, O): one value per
+ * signal, query point and output channel, finite and >= 0.
+ *     loss  = 1 / (B N O) * sum_{b,n,o} cweight[b,n,o] * (out[b,n,o] - target[b,n,o])^2
+ *     d out = 2 * cweight[b,n,o] * (out - target) / (B N O) * grad_scale
+ * The rule above holds per VALUE: an element of weight 0 does not exist, its target is never used in arithmetic and may be NaN or Inf,
+ * and its share of the loss and of d out is exactly 0.0f (a select on the weight, not a product) -- cweight = isfinite(field) per value is
+ * usable as it stands.  The library does not normalise.  A signal or a channel whose weights are all zero contributes zeros and is not
+ * an error.  cweight[b,n,o] = weight[b,n] for every o is the per-point loss: every squared error is weighted BEFORE it is added to the
+ * sum over o, not the sum afterwards, and the two calls are promised to agree to rounding, not bit for bit (they are different kernel
+ * instantiations).
+ * x_bstride, flags (ENF_FIT_DETERMINISTIC: same inputs, same bits), workspace and scratch sizes are those of enf_fit_step_w /
+ * enf_mse_value_grad_w; both precisions and every width, head count and O <= 32 of the fit step are served.  cweight == NULL is
+ * ENF_EINVAL: a caller without channel weights uses the calls above, whose signatures and arithmetic are unchanged. */
+int enf_fit_step_cw(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                    const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                    void* workspace, size_t workspace_bytes, const float* cweight /* (B,N,O), required */, unsigned flags, void* stream);
+
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
@@ -353,6 +371,11 @@ int enf_mse_value_grad_ex(const float* out, const float* target, size_t n, float
  * ENF_EINVAL), or NULL (then O only has to divide n). */
 int enf_mse_value_grad_w(const float* out, const float* target, const float* weight /* (n / O) or NULL */, size_t n, int32_t O,
                          float grad_scale, float* dout, float* loss, void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
+
+/* The same with one weight per ELEMENT, cweight (n floats, required): the per-channel weighted loss above.  Flags and scratch are
+ * those of enf_mse_value_grad_w (enf_mse_scratch_bytes(n, flags)). */
+int enf_mse_value_grad_cw(const float* out, const float* target, const float* cweight /* (n), required */, size_t n, float grad_scale,
+                          float* dout, float* loss, void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
 
 /* The meta-SGD update of one inner step for all latent components in one launch (pde_trainer.py:206-219):
  *     out = x - lr * (scale * g)        scale = the batch size (:206); lr broadcasts over the leading dims
@@ -435,6 +458,17 @@ int enf_fit_inputs_w(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t
 int enf_fit_inputs_b(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx, int32_t O,
                      const float* coords, const float* img, const int64_t* masks /* (B,Ns,S1) */, float* xs, float* ys, float* losses,
                      const float* weight /* (B,N) or NULL */, float* ws /* (S1,B,Ns), required */, void* stream);
+
+/* The counterpart of enf_fit_inputs_w (per_signal_masks == 0: masks (Ns, S1), xs (S1, Ns, dx)) and of enf_fit_inputs_b
+ * (per_signal_masks != 0: masks (B, Ns, S1), xs (S1, B, Ns, dx)) for PER-CHANNEL weights, in the same single launch as the latent
+ * broadcast, xs, ys and the zeroed loss accumulators:
+ *       ws[s, b, i, o] = cweight[b, masks[..], o]      (S1, B, Ns, O)      cweight (B, N, O)
+ * cweight and ws are both required (NULL is ENF_EINVAL).  The index contract of enf_fit_inputs_b holds for BOTH layouts: an index
+ * < 0 or >= N is never dereferenced; its xs row is coords[0], its ys row is zeros and its ws row is O zeros.  Offsets are 64-bit. */
+int enf_fit_inputs_cw(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t N, int32_t Ns, int32_t S1, int32_t dx, int32_t O,
+                      const float* coords, const float* img, const int64_t* masks, float* xs, float* ys, float* losses,
+                      const float* cweight /* (B,N,O), required */, float* ws /* (S1,B,Ns,O), required */, int32_t per_signal_masks,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
