@@ -24,6 +24,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_backward_weights_scratch_bytes_ex",
            "enf_fit_step_w", "enf_mse_value_grad_w", "enf_fit_inputs_w", "enf_fit_inputs_b",
            "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
+           "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
@@ -203,6 +204,10 @@ def _bind(path, test_hooks):
     lib.enf_fit_step_cw.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, sz, vp, cu, vp]
     lib.enf_mse_value_grad_cw.argtypes = [vp, vp, vp, sz, ctypes.c_float, vp, vp, vp, sz, cu, vp]
     lib.enf_fit_inputs_cw.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 7 + [vp] * 8 + [ctypes.c_int32, vp]
+    # per-signal and per-point errors (include/enf_hip.h): weight (B, N) | NULL, cweight (B, N, O) | NULL, err (B, N), loss_b (B) | NULL
+    lib.enf_fit_step_e.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, cu, vp]
+    lib.enf_eval_loss.argtypes = [dp, vp, i64] + [vp] * 11 + [sz, cu, vp]
+    lib.enf_signal_sum.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, vp, vp]
     lib.enf_pair_backward_scratch_bytes.restype = sz
     lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]
     lib.enf_pair_backward_ex2.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]

@@ -279,14 +279,16 @@ extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstri
 
 // The one copy of the fit-step sequence.  weight != NULL: one loss weight per signal and query (include/enf_hip.h, "Weighted loss"),
 // or with `per_value` one per output value (B, N, O), which is then required.
+// err != NULL (enf_fit_step_e): the fused tail also stores the per-point errors (B, N), and with loss_b the per-signal sums follow at the
+// end of the sequence on the same stream; args_ok: the entry point's own argument checks (ENF_EINVAL, behind the descriptor's errors).
 static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, bool per_value, unsigned flags,
-                             void* stream) {
+                             void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
-  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma && (!per_value || weight),
-                    sigma, packed, workspace, workspace_bytes, stream, det);
+  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma && (!per_value || weight) &&
+                    args_ok, sigma, packed, workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
@@ -304,11 +306,13 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
     if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   }
   if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
-                                 det ? c.F(c.X.loss) : nullptr, per_value)))
+                                 det ? c.F(c.X.loss) : nullptr, per_value, err)))
     return rc;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse), det))) return rc;
-  return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
+  if ((rc = enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st))) return rc;
+  // (behind the gradients: nothing of the step waits for the per-signal sums)
+  return err && loss_b ? enf_launch_signal_sum(err, m.B, m.N, 1.0f / ((float)m.N * (float)m.O), loss_b, st) : ENF_OK;
 }
 
 extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
@@ -326,6 +330,42 @@ extern "C" int enf_fit_step_cw(const EnfDesc* d, const float* x, int64_t x_bstri
                                void* stream) {
   return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, cweight,
                            true, flags, stream);
+}
+
+// enf_fit_step_w / _cw plus the per-point errors and, with loss_b, the per-signal losses (include/enf_hip.h, "Per-signal and per-point
+// errors"): the same kernel instantiations with the `err` pointer set, so loss and gradients are those calls', bit for bit
+extern "C" int enf_fit_step_e(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, const float* cweight,
+                              float* err, float* loss_b, unsigned flags, void* stream) {
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes,
+                           cweight ? cweight : weight, cweight != nullptr, flags, stream, err, loss_b, err && !(weight && cweight));
+}
+
+// Evaluation without a decode: prologue, forward pair kernel (whatever variant the descriptor resolves to), the evaluation tail, the
+// per-signal sums.  loss_b without err: the per-point errors go through the workspace's (unused) d ybar region, B N HD floats.
+extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                             const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
+                             float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  EnfCall c;
+  const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
+  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && !(weight && cweight) && (loss || err || loss_b),
+                    sigma, packed, workspace, workspace_bytes, stream, det);
+  if (rc) return rc;
+  const EnfDims& m = c.m;
+  const EnfWorkspace& W = c.W;
+  hipStream_t st = c.st;
+  const bool zf = enf_use_zfold(m);
+  if ((rc = enf_side_join_pending(st, workspace))) return rc;
+  if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
+  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
+                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
+    return rc;
+  float* e = err ? err : (loss_b ? c.F(W.dybar) : nullptr);
+  if ((rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
+                                 det ? c.F(c.X.loss) : nullptr)))
+    return rc;
+  return loss_b ? enf_launch_signal_sum(e, m.B, m.N, 1.0f / ((float)m.N * (float)m.O), loss_b, st) : ENF_OK;
 }
 
 extern "C" int enf_lt_layout(const EnfDesc* d, int* stride, int* off_u, int* off_v0, int* off_pose, int* off_wcoef, int* off_c) {

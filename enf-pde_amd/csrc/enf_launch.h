@@ -158,6 +158,14 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
 // weight: NULL, or one loss weight per query (B N floats, include/enf_hip.h "Weighted loss"); per_value: `weight` (not NULL) holds one
 // weight per output value instead, B N O floats (enf_fit_step_cw) -- a kernel instantiation of its own
 // loss_part != NULL (enf_tail_loss_parts(m) floats): every wave stores its partial there and enf_launch_loss_sum adds them to *loss
+// err != NULL (B N floats): the same kernels also store every query's weighted squared error, err[b,n] = sum_o w (out - target)^2
+// (include/enf_hip.h, "Per-signal and per-point errors"); the loss, the partials and d out keep their arithmetic
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st,
-                         float* loss_part = nullptr, bool per_value = false);
+                         float* loss_part = nullptr, bool per_value = false, float* err = nullptr);
+// the evaluation tail: the forward chain whose epilogue forms err (B N floats, or NULL) and, with loss != NULL, adds the scalar loss to
+// *loss (through loss_part in deterministic mode) instead of storing `out`; weight / per_value as above.  ybar is fp32.
+int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
+                         const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part = nullptr);
+// loss_b[b] = scale * (err[b, 0] + ... + err[b, N - 1]): one workgroup per signal, fixed order, no atomics (enf_loss.hip)
+int enf_launch_signal_sum(const float* err, int B, int N, float scale, float* loss_b, hipStream_t st);

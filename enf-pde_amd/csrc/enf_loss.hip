@@ -87,6 +87,33 @@ int enf_launch_loss_sum(const float* part, int n, float* loss, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
+// loss_b[b] = scale * sum_n err[b, n] (include/enf_hip.h, "Per-signal and per-point errors"; scale = 1 / (N O)): one workgroup per signal.
+// Thread t adds err[b, t], err[b, t + 256], ... in order, then the fixed tree of enf_loss_sum_kernel over the 256 threads: the order
+// depends on N alone -- same inputs, same bits, in every mode.  No atomics, no scratch; N < 256 leaves zeros in the tree.  64-bit offsets.
+__global__ __launch_bounds__(256) void enf_signal_sum_kernel(const float* __restrict__ err, int N, float scale, float* __restrict__ loss_b) {
+  __shared__ float red[256];
+  const float* __restrict__ row = err + (size_t)blockIdx.x * (size_t)N;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < N; i += 256) s += row[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_b[blockIdx.x] = red[0] * scale;
+}
+
+int enf_launch_signal_sum(const float* err, int B, int N, float scale, float* loss_b, hipStream_t st) {
+  hipLaunchKernelGGL(enf_signal_sum_kernel, dim3((unsigned)B), dim3(256), 0, st, err, N, scale, loss_b);
+  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+}
+
+extern "C" int enf_signal_sum(const float* err, int32_t B, int32_t N, float scale, float* loss_b, void* stream) {
+  if (!err || !loss_b || B < 1 || N < 1) return ENF_EINVAL;
+  return enf_launch_signal_sum(err, B, N, scale, loss_b, (hipStream_t)stream);
+}
+
 static size_t mse_blocks(size_t n) {
   const size_t blocks = (n + 255) / 256;
   return blocks > 1024 ? 1024 : blocks;

@@ -25,6 +25,8 @@ struct TailArgs {
                          // 0 does not exist -- its target is never used in arithmetic (it may be NaN) and its d out is exactly 0
                          // LOSS + CW (the kernel's template flag): one weight per OUTPUT VALUE instead, (NQ, O) floats, never nullptr;
                          // the same rule per value
+  float* err;            // LOSS / EVAL: nullptr, or the weighted squared error of every query, err[n] = sum_o w (out - target)^2 (NQ floats,
+                         // OVERWRITTEN; include/enf_hip.h, "Per-signal and per-point errors"): lanes 0..15 of a wave store their 16 queries
   float* loss_part;      // LOSS, deterministic mode: wave w of workgroup g stores its partial in loss_part[g * NWAVES + w] (nullptr: atomic)
   float* tdel;           // weight-gradient backward (WG): per query d a_B | d a_F1 | d a_O0 | d a_O2 (2HD + 2D floats); the layer INPUTS
                          // n^ | gelu(a_F1) | gelu(a_O0) | gelu(a_O2) replace the pre-activations in `act` (enf_train.hip forms X^T delta)
@@ -207,8 +209,77 @@ DEV void tail_consts(float* cst, const char* blob, const EnfLayout& L, int tid) 
   for (int i = tid; i < 32; i += NTHREADS) cst[2 * HD + 2 * D + i] = G(L.bO4)[i];
 }
 
-template <int D, int H, bool BF16, bool LA2, bool SAVE>
+// The fused loss of one wave's 16 queries (enf_loss.hip's arithmetic on the forward chain's outputs, in registers): this lane's share of
+// sum_o w (out - target)^2 and, in g0, d out = 2 w (out - target) inv_n gscale (gs = 2 inv_n gscale).  CW: `weight` holds one value per
+// output element, else nullptr or one per query.  A weight of 0 is a select, never 0 * target: the NaN of a missing value reaches neither
+// the sum nor d out.
+template <bool CW>
+DEV float tail_sq_err(const f32x4 (&o4)[2], f32x4 (&g0)[2], const TailArgs& A, int qi, bool qvalid, int quad, float gs) {
+  float se = 0.f;
+  if constexpr (CW) {      // the lane that holds output o of query n reads weight[n][o]; the zero test is per value
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = 16 * t + 4 * quad + i;
+        const bool in = o < A.O && qvalid;
+        const float w = in ? A.weight[(size_t)qi * A.O + o] : 0.f;
+        const float dd = (in && w > 0.f) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
+        const float wd = w * dd;
+        se = fmaf(wd, dd, se);
+        g0[t][i] = wd * gs;
+      }
+  } else if (A.weight) {          // (wave-uniform; the unweighted arithmetic below stays as it was, bit for bit)
+    const float w = A.weight[qi];
+    const bool live = qvalid && w > 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = 16 * t + 4 * quad + i;
+        const float dd = (o < A.O && live) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
+        const float wd = w * dd;
+        se = fmaf(wd, dd, se);
+        g0[t][i] = wd * gs;
+      }
+  } else {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = 16 * t + 4 * quad + i;
+        const float dd = (o < A.O && qvalid) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
+        se = fmaf(dd, dd, se);
+        g0[t][i] = dd * gs;
+      }
+  }
+  return se;
+}
+// The wave's reduction of `se` in the order it always had (xor 32, 16, 8, 4, 2, 1).  After the first two steps the four quads are
+// folded: lanes 0..15 hold one weighted squared error per query, and with `err` they store it (one 64-byte store per wave; rows beyond
+// NQ -- clamped duplicate lanes -- do not).  No atomic and nothing that depends on which signals a wave straddles.  `want_sum` false:
+// the per-query values were all that was asked for.
+DEV float tail_err_reduce(float se, float* err, int q, bool qvalid, int quad, bool want_sum = true) {
+  se += __shfl_xor(se, 32, 64);
+  se += __shfl_xor(se, 16, 64);
+  if (err && quad == 0 && qvalid) err[q] = se;
+  if (want_sum) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+  }
+  return se;
+}
+DEV void tail_loss_add(float se, const TailArgs& A, int wave) {
+  if (A.loss_part) A.loss_part[blockIdx.x * NWAVES + wave] = se * A.inv_n;     // deterministic mode: summed in index order afterwards
+  else atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
+}
+
+// EVAL (1: unweighted or per-point weights, 2: per-channel weights; never with SAVE): the evaluation tail -- the epilogue forms err and,
+// with A.loss, the scalar loss from the output accumulators instead of storing `out` (enf_eval_loss): no backward chain, no stash, no
+// `out` in HBM.
+template <int D, int H, bool BF16, bool LA2, bool SAVE, int EVAL = 0>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
+  static_assert(!(SAVE && EVAL != 0), "the evaluation tail has no backward to stash for");
   using T = TailCfg<D, H, BF16>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
@@ -231,7 +302,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
                          : A.ybar + (size_t)qi * T::HD;
   tail_forward<D, H, BF16, SAVE, LA2, NoPan, NoPan>(o4, yrow, SAVE ? A.act + (size_t)qi * T::ACT : nullptr, A.L,
                                                     cst, P, ring, NO_STAGE, NO_STAGE, lane, quad, A.inv_hd, true, yh);
-  if (q0 + col < A.NQ) {
+  if constexpr (EVAL != 0) {
+    const bool qvalid = q0 + col < A.NQ;
+    f32x4 g0[2];       // (d out is not wanted: dead code)
+    float se = tail_sq_err<EVAL == 2>(o4, g0, A, qi, qvalid, quad, 0.f);
+    se = tail_err_reduce(se, A.err, q0 + col, qvalid, quad, A.loss != nullptr);
+    if (A.loss && lane == 0) tail_loss_add(se, A, wave);
+  } else if (q0 + col < A.NQ) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -290,52 +367,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   // ---- backward chain
   f32x4 g0[2];
   if constexpr (LOSS) {
-    float se = 0.f;
-    const float gs = 2.0f * A.inv_n * A.gscale;
-    if constexpr (CW) {      // the lane that holds output o of query n reads weight[n][o]; the zero test is per value: a select, never
-                             // 0 * target, so that the NaN of a missing value reaches neither the loss nor d out
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int o = 16 * t + 4 * quad + i;
-          const bool in = o < A.O && qvalid;
-          const float w = in ? A.weight[(size_t)qi * A.O + o] : 0.f;
-          const float dd = (in && w > 0.f) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
-          const float wd = w * dd;
-          se = fmaf(wd, dd, se);
-          g0[t][i] = wd * gs;
-        }
-    } else if (A.weight) {          // (wave-uniform; the unweighted arithmetic below stays as it was, bit for bit)
-      const float w = A.weight[qi];
-      const bool live = qvalid && w > 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int o = 16 * t + 4 * quad + i;
-          const float dd = (o < A.O && live) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
-          const float wd = w * dd;
-          se = fmaf(wd, dd, se);
-          g0[t][i] = wd * gs;
-        }
-    } else {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = 16 * t + 4 * quad + i;
-        const float dd = (o < A.O && qvalid) ? o4[t][i] - A.target[(size_t)qi * A.O + o] : 0.f;
-        se = fmaf(dd, dd, se);
-        g0[t][i] = dd * gs;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
-    if (lane == 0) {
-      if (A.loss_part) A.loss_part[blockIdx.x * NWAVES + wave] = se * A.inv_n;     // deterministic mode: summed in index order afterwards
-      else atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
-    }
+    float se = tail_sq_err<CW>(o4, g0, A, qi, qvalid, quad, 2.0f * A.inv_n * A.gscale);
+    se = tail_err_reduce(se, A.err, q0 + col, qvalid, quad);
+    if (lane == 0) tail_loss_add(se, A, wave);
   } else {
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -456,7 +490,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
 }
 
 template <int D, int H, bool BF16>
-static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false) {
+static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false, bool eval = false) {
   const bool wg = bwd && A.tdel != nullptr;
   const bool fused_loss = bwd && A.target != nullptr;
   using T = TailCfg<D, H, BF16>;
@@ -464,13 +498,21 @@ static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bo
   // few workgroups (at most one per CU): the deeper weight pipeline (LA2) instead of a second workgroup per CU
   const bool la2 = grid.x <= 256;
   // opt: forward -> stash the pre-activations (SAVE); backward -> they are stashed, skip the recompute
-  static EnfAttrBits attr_done[5][2][2];     // [fwd / bwd / bwd + WG / fused loss / fused loss + CW][la2][opt] (this function is one instantiation per D, H, BF16), one bit per device
+  // [fwd / bwd / bwd + WG / fused loss / fused loss + CW / evaluation / evaluation + CW][la2][opt] (this function is one instantiation per
+  // D, H, BF16), one bit per device
+  static EnfAttrBits attr_done[7][2][2];
   auto go = [&](void (*kern_ptr)(TailArgs)) -> int {
     const int smem = la2 ? T::SMEM3 : T::SMEM;
-    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd)][la2][opt])) return ENF_ELAUNCH;
+    const int which = eval ? (cw ? 6 : 5) : fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd);
+    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[which][la2][opt])) return ENF_ELAUNCH;
     hipLaunchKernelGGL(kern_ptr, grid, dim3(NTHREADS), smem, st, A);
     return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
   };
+  if (eval) {      // the evaluation tail: a forward instantiation whose epilogue forms err / the loss (same LA2 choice as the forward)
+    if (bwd || opt || !A.target || (cw && !A.weight)) return ENF_EINVAL;
+    if (cw) return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 2>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 2>);
+    return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 1>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 1>);
+  }
   if (fused_loss) {
     if (wg || opt) return ENF_EINVAL;
     if (cw) {
@@ -500,7 +542,7 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
                        const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
-  A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr;
+  A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr; A.err = nullptr;
   A.tdel = tdel;
   A.ybar_half = (!bwd && (opt & 2) && m.bf16) ? 1 : 0;
   opt &= 1;
@@ -523,27 +565,35 @@ int enf_tail_loss_parts(const EnfDims& m) {
 
 static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                             const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
-                            bool per_value);
+                            bool per_value, float* err, bool eval);
 
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
-                         bool per_value) {
-  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, gscale, loss, dybar, delta, act, st, loss_part, per_value)) return rc;
+                         bool per_value, float* err) {
+  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, gscale, loss, dybar, delta, act, st, loss_part, per_value, err, false)) return rc;
+  return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
+}
+
+int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
+                         const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part) {
+  if (!loss) loss_part = nullptr;
+  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, 0.f, loss, nullptr, nullptr, nullptr, st, loss_part, per_value, err, true)) return rc;
   return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
 }
 
 static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                             const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
-                            bool per_value) {
+                            bool per_value, float* err, bool eval) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
-  A.loss_part = loss_part;
+  A.loss_part = loss_part; A.err = err;
   A.ybar = ybar; A.blob = blob; A.L = L; A.out = nullptr; A.dout = nullptr; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = nullptr;
   A.ybar_half = 0;
   A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
 #define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH) return m.bf16 ? launch_tail<DD, HH, true>(A, true, false, st, per_value) : launch_tail<DD, HH, false>(A, true, false, st, per_value);
+  if (m.D == DD && m.H == HH)                                                              \
+    return m.bf16 ? launch_tail<DD, HH, true>(A, !eval, false, st, per_value, eval) : launch_tail<DD, HH, false>(A, !eval, false, st, per_value, eval);
   ENF_CASE(128, 2)
   ENF_CASE(64, 2)
   ENF_CASE(128, 1)

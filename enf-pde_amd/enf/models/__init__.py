@@ -512,7 +512,7 @@ class EquivariantCrossAttentionNeF:
 
     @torch.no_grad()
     def mse_value_and_latent_grads(self, params, x, p, a, gaussian_window_size, target, grad_scale=1.0, loss_out=None, weight=None,
-                                   channel_weight=None):
+                                   channel_weight=None, return_errors=False):
         """loss = mean((nef.apply(params, x, p, a, window) - target)^2) and grad_scale * d loss / d(p, a, window) in one
         sequence of HIP launches (forward, loss + d out, backward), without building an autograd graph: what one
         inner step of the MAML loop computes (pde_trainer.py:175-207; grad_scale = B there).
@@ -523,7 +523,14 @@ class EquivariantCrossAttentionNeF:
         ``channel_weight``: None, or (B, N, O) loss weights per signal, query point and output channel (the same section:
         enf_fit_step_cw): loss = sum_{b,n,o} channel_weight[b,n,o] (out - target)^2 / (B N O); the rule holds per value.  Not
         together with ``weight`` (ValueError).
-        Returns (loss (1,), dp, da, dwindow or None)."""
+        ``return_errors``: also return the per-point errors err (B, N) = sum_o w (out - target)^2 and the per-signal losses loss_b (B,)
+        = err.sum(1) / (N O) of this step (include/enf_hip.h, "Per-signal and per-point errors": enf_fit_step_e -- the same kernels
+        with one store added, so loss and gradients are the bits of the call without it).  Needs the one-call step.
+        Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err, loss_b)."""
+        if return_errors and not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda):
+            raise _lib.EnfError("mse_value_and_latent_grads(return_errors=True) needs CUDA/HIP tensors: there is no CPU path")
+        if return_errors and (self.num_layers > 0 or not FUSED_FIT_STEP):
+            raise NotImplementedError("return_errors needs the one-call inner step (enf_fit_step_e): num_layers = 0 and ENF_FIT_STEP on")
         if channel_weight is not None:
             if weight is not None:
                 raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
@@ -593,6 +600,14 @@ class EquivariantCrossAttentionNeF:
             return loss, dp, da, (dsig if sigma is not None else None)
         # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
         # the loss and its gradient formed in registers, pair backward, prologue backward
+        if return_errors:                   # the same sequence and instantiations; the tail also stores its per-query errors
+            err = torch.empty((B, N), device=dev, dtype=torch.float32)
+            loss_b = torch.empty((B,), device=dev, dtype=torch.float32)
+            _lib.launch(dev, lib.enf_fit_step_e, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                        float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(weight), _ptr(channel_weight),
+                        _ptr(err), _ptr(loss_b), det, st)
+            self._ws_touch(ws)
+            return loss, dp, da, (dsig if sigma is not None else None), err, loss_b
         if channel_weight is not None:      # the same sequence, the tail's per-channel instantiation
             _lib.launch(dev, lib.enf_fit_step_cw, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
                         float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(channel_weight), det, st)
@@ -602,3 +617,61 @@ class EquivariantCrossAttentionNeF:
                     float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(weight), det, st)
         self._ws_touch(ws)
         return loss, dp, da, (dsig if sigma is not None else None)
+
+    @torch.no_grad()
+    def eval_loss(self, params, x, p, a, gaussian_window_size, target, weight=None, channel_weight=None, loss_out=None, per_signal=True):
+        """Evaluation without a decode (include/enf_hip.h: enf_eval_loss): the per-point errors err (B, N) = sum_o w (out - target)^2
+        and the per-signal losses loss_b (B,) = err.sum(1) / (N O) of nef.apply(params, x, p, a, window) against ``target`` (B, N, O),
+        formed in the tail's registers -- no ``out``, no autograd.  ``weight`` (B, N) / ``channel_weight`` (B, N, O) as in
+        mse_value_and_latent_grads: a value of weight 0 does not exist, its target may be NaN.  Both results are the same bits for the
+        same inputs in every mode.
+        ``loss_out``: an already ZEROED float32 (1,) tensor; the scalar loss (the mean over all B N O values) is added to it.
+        ``per_signal`` False skips the per-signal sums (a caller that evaluates a grid in chunks sums once: ``signal_losses``).
+        Returns (loss_b or None, err)."""
+        if not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda):
+            raise _lib.EnfError("EquivariantCrossAttentionNeF.eval_loss needs CUDA/HIP tensors: there is no CPU path")
+        if self.num_layers > 0:
+            raise NotImplementedError("eval_loss is built for num_layers = 0 (the fused decoder)")
+        B, Z, N = p.shape[0], p.shape[1], x.shape[1]
+        if weight is not None and channel_weight is not None:
+            raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
+        if channel_weight is not None and tuple(channel_weight.shape) != (B, N, self.num_out):
+            raise ValueError(f"channel_weight has shape {tuple(channel_weight.shape)}, expected {(B, N, self.num_out)}")
+        if weight is not None and tuple(weight.shape) != (B, N):
+            raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(B, N)}")
+        tgt = target.float().contiguous()
+        if tuple(tgt.shape) != (B, N, self.num_out):
+            raise AssertionError(f"target has shape {tuple(tgt.shape)}, expected {(B, N, self.num_out)}")
+        lib = _lib.load()
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        packed = self.pack(params)
+        p_, a_ = p.float().contiguous(), a.float().contiguous()
+        s_ = sigma.float().reshape(B, Z, 1).contiguous() if sigma is not None else None
+        w_ = weight.float().contiguous() if weight is not None else None
+        cw_ = channel_weight.float().contiguous() if channel_weight is not None else None
+        dev = p_.device
+        desc = self._desc(B, N, Z, masks=self._masks)
+        xb, xstride = self._x_arg(x.float())
+        ws = self._workspace(desc, dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        err = torch.empty((B, N), device=dev, dtype=torch.float32)
+        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
+        _lib.launch(dev, lib.enf_eval_loss, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    _ptr(w_), _ptr(cw_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
+        self._ws_touch(ws)
+        return loss_b, err
+
+    @torch.no_grad()
+    def signal_losses(self, err):
+        """loss_b (B,) = err.sum(1) / (N num_out) of per-point errors err (B, N), by the fixed-order sum enf_eval_loss itself runs
+        (enf_signal_sum: one workgroup per signal, same inputs, same bits)."""
+        if not err.is_cuda:
+            raise _lib.EnfError("EquivariantCrossAttentionNeF.signal_losses needs CUDA/HIP tensors: there is no CPU path")
+        e = err.float().contiguous()
+        B, N = e.shape
+        loss_b = torch.empty((B,), device=e.device, dtype=torch.float32)
+        st = ctypes.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
+        _lib.launch(e.device, _lib.load().enf_signal_sum, _ptr(e), B, N, 1.0 / (float(N) * float(self.num_out)), _ptr(loss_b), st)
+        return loss_b

@@ -161,7 +161,7 @@ def meta_sgd_update(lat, grads, lrs, scale):
 
 
 def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
-               noise_pos=0.0, generator=None, weights=None, normalize_weights=False, channel_weights=None):
+               noise_pos=0.0, generator=None, weights=None, normalize_weights=False, channel_weights=None, per_signal_loss=False):
     """Fit per-signal latents with S steps of meta-SGD (pde_trainer.py:156-235).
 
     latents0 : {'p_pos','a','gaussian_window'[,'p_ori']} with leading dim 1 (the meta-init)
@@ -185,7 +185,12 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
                gathered with the targets in the same launch (enf_fit_inputs_cw, either mask layout) and every step runs
                enf_fit_step_cw; a value of weight 0 does not exist, its target may be NaN.  ``normalize_weights`` then rescales to
                mean 1 over every signal's N_s * O sampled values.  None takes the code path above unchanged.
-    Returns (loss on the last mask, fitted latents dict with leading dim B).
+    per_signal_loss : also return loss_b (S + 1, B), every signal's own loss at each step and on the last mask (include/enf_hip.h,
+               "Per-signal and per-point errors": loss_b[s].mean() is step s's loss up to rounding).  The steps then run enf_fit_step_e
+               -- the kernels of the plain steps with one store added, so the fitted latents are the same -- and the final loss comes
+               from enf_eval_loss, without a decode, instead of enf_forward + enf_mse_value_grad*: the same sum in another order.
+               Every weight form and both mask layouts; False takes the code path above unchanged.
+    Returns (loss on the last mask, fitted latents dict with leading dim B), with ``per_signal_loss`` followed by loss_b.
     """
     B = img.shape[0]
     per_signal = masks.dim() == 3
@@ -215,7 +220,7 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         if normalize_weights:
             ws_all = normalize_sampled_weights(ws_all, channel=True)
         return _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_signal, S, B, n_ori,
-                            optimize_gaussian_window, noise_pos, generator)
+                            optimize_gaussian_window, noise_pos, generator, per_signal_loss)
     if weights is not None:
         if tuple(weights.shape) != tuple(img.shape[:2]):
             raise ValueError(f"weights have shape {tuple(weights.shape)}, expected {tuple(img.shape[:2])}")
@@ -244,6 +249,9 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     if noise_pos:                                                                             # pde_trainer.py:162-167
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
+    if per_signal_loss:
+        return _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, "weight", losses, per_signal, S, B, n_ori,
+                              optimize_gaussian_window)
     n_pos = lat["p_pos"].shape[-1]
     for s in range(S):                                                  # pde_trainer.py:191
         xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)             # every signal's own points, or a stride-0 batch
@@ -273,13 +281,41 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     return losses[S], lat
 
 
+def _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, weight_kw, losses, per_signal, S, B, n_ori, optimize_gaussian_window):
+    """inner_loop(per_signal_loss=True) from the gathered inputs on, for every weight form (``weight_kw``: the keyword that takes
+    ws_all[s], "weight" or "channel_weight"; ws_all may be None): S steps through enf_fit_step_e, the final loss through enf_eval_loss.
+    Returns (loss, lat, loss_b (S + 1, B))."""
+    n_pos = lat["p_pos"].shape[-1]
+    rows = []
+    for s in range(S):
+        xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)
+        _, dp, da, dsig, _, lb = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"),
+                                                                ys_all[s], loss_out=losses[s:s + 1], return_errors=True,
+                                                                **{weight_kw: None if ws_all is None else ws_all[s]})
+        rows.append(lb)
+        grads = {"p_pos": dp[..., :n_pos], "a": da}
+        if n_ori > 0:
+            grads["p_ori"] = dp[..., n_pos:]
+        if optimize_gaussian_window and dsig is not None:
+            grads["gaussian_window"] = dsig
+        lat = meta_sgd_update(lat, grads, lrs, B)
+    xs = xs_all[S] if per_signal else xs_all[S][None].expand(B, -1, -1)
+    lb, _ = nef.eval_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], loss_out=losses[S:],
+                          **{weight_kw: None if ws_all is None else ws_all[S]})
+    rows.append(lb)
+    return losses[S], lat, torch.stack(rows)
+
+
 def _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_signal, S, B, n_ori, optimize_gaussian_window,
-                 noise_pos, generator):
+                 noise_pos, generator, per_signal_loss=False):
     """The S meta-SGD steps and the final loss of inner_loop for per-channel weights ws_all (S+1, B, N_s, O): the same sequence with
     enf_fit_step_cw / enf_mse_value_grad_cw."""
     if noise_pos:
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
+    if per_signal_loss:
+        return _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, "channel_weight", losses, per_signal, S, B, n_ori,
+                              optimize_gaussian_window)
     n_pos = lat["p_pos"].shape[-1]
     for s in range(S):
         xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)

@@ -191,7 +191,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         return self._step(state, batch, mask, False, weights, normalize, channel_weights)
 
     @torch.no_grad()
-    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None):
+    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, per_signal_loss=False):
         """nef_train_step_autodec_only (:139-171) on the native latent-only path: same arguments, same (loss, new_state), same draw
         from ``state.rng`` (_fit_points), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
         are read under no_grad, ONE nef.mse_value_and_latent_grads (enf_fit_step_w: forward, fused weighted loss, backward to the
@@ -201,7 +201,10 @@ class NonMetaPDETrainer(LatentODEMixin):
         The nef parameters, ``nef_opt_state`` and ``ode_opt_state`` are handed on untouched.  In a multi-rank run the gathered
         gradients are scattered to dense tensors, averaged with the loss by the flat all-reduce of _step, and the kernel runs in
         its dense form (idx = None).  This is the step validate_epoch repeats; nef_train_step_autodec_only stays as it is.
-        ``channel_weights`` (N, O) / (B, N, O): the one fit call is enf_fit_step_cw; still one fit call and one table update."""
+        ``channel_weights`` (N, O) / (B, N, O): the one fit call is enf_fit_step_cw; still one fit call and one table update.
+        ``per_signal_loss``: the one fit call is enf_fit_step_e and a third value is returned, loss_b (B,): every signal's own loss
+        (this rank's signals; loss_b.mean() is the loss before the all-reduce, up to rounding).  Same draw from ``state.rng``, same
+        new state."""
         initial_state, traj_idx = batch
         img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
@@ -210,10 +213,11 @@ class NonMetaPDETrainer(LatentODEMixin):
         p, a, window = self.autodecoder.apply({"params": dict(zip(names, tables))}, traj_idx)
         if xs is None:
             xs = coords[None].expand(img.shape[0], -1, -1)
+        more = {"return_errors": True} if per_signal_loss else {}
         if channel_weights is not None:
-            loss, dp, da, dwin = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, channel_weight=pw)
+            loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, channel_weight=pw, **more)
         else:
-            loss, dp, da, dwin = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, weight=pw)
+            loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, weight=pw, **more)
         loss = loss.reshape(())
         n_pos = P["p_pos"].shape[-1]
         by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dwin}
@@ -228,8 +232,9 @@ class NonMetaPDETrainer(LatentODEMixin):
             loss, idx = flat[-1][0], None
         new_tables, ad_state = table_adam_update(self.autodecoder_opt, state.autodecoder_opt_state, tables, grads, idx=idx)
         params = dict(state.params, autodecoder={"params": dict(zip(names, new_tables))})    # nef, ode_params carried over
-        return loss, NonMetaTrainState(params=params, nef_opt_state=state.nef_opt_state, autodecoder_opt_state=ad_state,
-                                       ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
+        new_state = NonMetaTrainState(params=params, nef_opt_state=state.nef_opt_state, autodecoder_opt_state=ad_state,
+                                      ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
+        return (loss, new_state, errs[1]) if per_signal_loss else (loss, new_state)
 
     # ------------------------------------------------------------------ latent-ODE phase (:173-307)
     def _need_ode(self, what):

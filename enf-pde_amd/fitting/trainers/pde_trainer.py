@@ -42,6 +42,7 @@ from types import SimpleNamespace
 
 import torch
 
+from ... import _lib
 from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
 from .latent_ode import LatentODEMixin, draw_point_masks, frame_weights, frame_channel_weights, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
@@ -370,6 +371,51 @@ class MetaSGDPDETrainer(LatentODEMixin):
         new_state = TrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state,
                                meta_sgd_opt_state=lr_state, ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
         return loss, new_state
+
+    @torch.no_grad()
+    def fit_errors(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None, chunk=None):
+        """Which signal did not fit, and where: fit the latents of ``batch`` = (B, N, O) initial states as nef_train_step's inner loop
+        does (same arguments, same draw of the masks from ``state.rng``), then evaluate the fit on the FULL grid without decoding it
+        (nef.eval_loss, include/enf_hip.h: enf_eval_loss).  Returns (loss_b (B,), err (B, N)):
+            err[b, n]  = sum_o w[b, n, o] (recon - batch)^2      loss_b[b] = err[b].sum() / (N O)
+        with w the prepared ``weights`` / ``channel_weights`` on the full grid (mean 1 per signal unless ``normalize`` is False; not the
+        rescaled weights a fit on per-signal masks uses), or 1; a point of weight 0 has err 0 and its target may be NaN.
+        ``chunk``: points per evaluation call, as val_step's decode takes it (None: the whole grid in one call).  Every chunk's errors
+        are written into the one (B, N) tensor and loss_b is summed from it once, in a fixed order."""
+        cfg = self.config
+        img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
+        B, N, O = img.shape
+        if not (img.is_cuda and self.coords.is_cuda):
+            raise _lib.EnfError("MetaSGDPDETrainer.fit_errors needs CUDA/HIP tensors: there is no CPU path")
+        pw = cw = None
+        if channel_weights is not None:
+            if weights is not None:
+                raise ValueError("pass weights= or channel_weights=, not both")
+            cw = prepare_channel_weights(channel_weights, B, N, O, normalize, img.device)
+        else:
+            pw = prepare_point_weights(weights, B, N, normalize, img.device)
+        fit_pw, fit_cw = pw, cw
+        if masks is None:
+            masks = self._draw_masks(state, N, point_support(cw) if cw is not None else pw)
+            fit_pw = self._observed_weights(True, masks, pw)
+            if cw is not None and masks.dim() == 3:
+                fit_cw = observed_channel_sampling_weights(cw, masks.shape[1])
+        with torch.enable_grad():
+            # (per_signal_loss: the loop's own final loss comes from enf_eval_loss too -- nothing is decoded anywhere)
+            _, lat, _ = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], self.coords, img, masks,
+                                   optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
+                                   noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, weights=fit_pw,
+                                   channel_weights=fit_cw, per_signal_loss=True)
+        pose = _pose(lat, self.nef.cross_attn_invariant.num_z_ori_dims)
+        err = torch.empty((B, N), device=img.device, dtype=torch.float32)
+        step = N if chunk is None else max(1, int(chunk))
+        for i in range(0, N, step):
+            part = slice(i, min(i + step, N))
+            _, e = self.nef.eval_loss(state.params["nef"], self.coords[part][None].expand(B, -1, -1), pose, lat["a"],
+                                      lat.get("gaussian_window"), img[:, part], weight=None if pw is None else pw[:, part],
+                                      channel_weight=None if cw is None else cw[:, part], per_signal=False)
+            err[:, part] = e
+        return self.nef.signal_losses(err), err
 
     def meta_gradient_report(self, state, batch, masks=None):
         """How far this trainer's meta-gradient (the model's own arithmetic, normally bf16) is from the same meta-gradient

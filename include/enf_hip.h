@@ -356,6 +356,45 @@ int enf_fit_step_cw(const EnfDesc* d, const float* x, int64_t x_bstride, const f
                     const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
                     void* workspace, size_t workspace_bytes, const float* cweight /* (B,N,O), required */, unsigned flags, void* stream);
 
+/* Per-signal and per-point errors (enf_fit_step_e, enf_eval_loss): which signal did not fit, and where on the grid the error is,
+ * without a decode.  With w[b,n,o] the per-channel weight, the per-point weight broadcast over o, or 1:
+ *     err[b,n]  = sum_o w[b,n,o] * (out[b,n,o] - target[b,n,o])^2        (B, N) fp32, OVERWRITTEN
+ *     loss_b[b] = 1 / (N O) * sum_n err[b,n]                              (B)    fp32, OVERWRITTEN
+ * The zero-weight rule of "Weighted loss" holds unchanged: a value of weight 0 does not exist, its target may be NaN or Inf, and its share
+ * of err is exactly 0.0f (a select, not a product); a point whose weights are all zero -- a padded index of enf_fit_inputs_b among them --
+ * has err == 0.0f, a signal whose weights are all zero has loss_b == 0.0f.  Weights are not normalised.  mean_b loss_b equals the scalar
+ * loss of the calls above up to rounding.  err and loss_b are caller-owned; nothing past [0, B N) and [0, B) is written.
+ * Both are deterministic by construction, in the default mode too: the fused tail holds 16 queries' squared errors per wave in
+ * registers, and after folding the output channels 16 lanes store one value per query (no atomic, nothing that depends on the signals a
+ * wave straddles); enf_signal_sum_kernel, one workgroup per signal, adds a row of err in an order fixed by N alone.  (Their bits follow
+ * `out`: the split z-fold forward variant orders its partial sums by the call's shape, see "Deterministic mode".)
+ *
+ * enf_fit_step_e: enf_fit_step_w (weight, or neither) / enf_fit_step_cw (cweight) on the same arguments -- the same host sequence and the
+ * same kernel instantiations with a store added, so `loss`, dp, da and dsigma are those calls', bit for bit -- plus err (required) and,
+ * with loss_b != NULL, one more small launch at the end of the sequence.  weight and cweight both non-NULL is ENF_EINVAL.  flags and
+ * workspace as enf_fit_step_w (ENF_FIT_DETERMINISTIC concerns `loss` and the gradients; other bits are ENF_EINVAL). */
+int enf_fit_step_e(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                   const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                   void* workspace, size_t workspace_bytes, const float* weight /* (B,N) or NULL */, const float* cweight /* (B,N,O) or NULL */,
+                   float* err /* (B,N), required */, float* loss_b /* (B) or NULL */, unsigned flags, void* stream);
+/* Evaluation without a decode: latent prologue, forward pair kernel (the variant the descriptor resolves to), and a tail whose epilogue
+ * forms err -- and, with loss != NULL, *loss += the scalar loss of enf_mse_value_grad[_w|_cw] (the caller zeroes it) -- from the output
+ * accumulators: no `out` in memory, no backward chain, no stash.  At least one of loss, err, loss_b must be given (all NULL is
+ * ENF_EINVAL), weight and cweight both non-NULL is ENF_EINVAL.  loss_b WITHOUT err is allowed: the per-point errors then pass through a
+ * region of the workspace this call does not otherwise use.  flags: 0 or ENF_FIT_DETERMINISTIC (the scalar loss through the workspace's
+ * partials in a fixed order; `workspace` is then enf_workspace_bytes_ex(d, flags), else enf_workspace_bytes(d)); err and loss_b are the
+ * same bits either way. */
+int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                  const void* packed, const float* target, const float* weight /* (B,N) or NULL */, const float* cweight /* (B,N,O) or NULL */,
+                  float* loss /* scalar, accumulated, or NULL */, float* err /* (B,N) or NULL */, float* loss_b /* (B) or NULL */,
+                  void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
+/* The per-signal sum on its own, for a caller that fills err (B, N) from several calls (a grid evaluated in chunks):
+ *     loss_b[b] = scale * (err[b,0] + ... + err[b,N-1])        scale = 1 / (N O) for the definition above
+ * One workgroup per signal: each of its 256 threads adds a fixed strided slice, then a fixed tree -- same inputs and N, same bits; no
+ * atomics, no scratch, any N >= 1, 64-bit offsets.  The kernel enf_fit_step_e and enf_eval_loss run.  NULL or B, N < 1: ENF_EINVAL. */
+int enf_signal_sum(const float* err, int32_t B, int32_t N, float scale, float* loss_b, void* stream);
+
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
