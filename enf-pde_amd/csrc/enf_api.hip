@@ -368,6 +368,77 @@ extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride
   return loss_b ? enf_launch_signal_sum(e, m.B, m.N, 1.0f / ((float)m.N * (float)m.O), loss_b, st) : ENF_OK;
 }
 
+// ---- derivative fields: the Jacobian of a decode w.r.t. the query coordinates (include/enf_hip.h, "Derivative fields")
+// The workspace of enf_field_grad / enf_query_vjp: the plain one; with ENF_BWD_DETERMINISTIC the deterministic one (K3's partial rows)
+// followed by the per-latent shares of the query gradient, (B, Z, N, dx) floats, reused by every channel's pass.
+extern "C" size_t enf_field_grad_workspace_bytes(const EnfDesc* d, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || d->mask_mode != ENF_MASK_OFF || (flags & ~ENF_BWD_DETERMINISTIC)) return 0;
+  const EnfDims m = enf_dims(d);
+  const EnfWorkspace W = enf_workspace(m);
+  return (flags & ENF_BWD_DETERMINISTIC) ? enf_det_workspace(m, W).total + enf_det_dx_bytes(m) : W.total;
+}
+
+// The one copy of the sequence.  dout == NULL: the Jacobian -- one seeded tail backward and one backward pair kernel per output channel,
+// channel o's query gradient into grad + o B N dx; dout != NULL: one pass of the tail backward on `dout`, the vector-Jacobian product
+// into grad (B, N, dx).  Prologue, the z-fold backward's per-latent matrices, forward pair kernel and the forward tail with its stash run
+// once.  Everything is on the caller's stream.
+static int field_grad_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* dout, float* out, float* grad, bool args_ok, void* workspace,
+                               size_t workspace_bytes, unsigned flags, void* stream) {
+  int rc = enf_check_desc(d);
+  if (rc) return rc;
+  if (d->mask_mode != ENF_MASK_OFF) return ENF_EUNSUPPORTED;      // relu masks belong to the meta-gradient, not to a decode
+  EnfCall c;
+  const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0;
+  if ((rc = enf_call(c, d, !(flags & ~ENF_BWD_DETERMINISTIC) && x && p && a && grad && args_ok, sigma, packed, workspace, workspace_bytes,
+                     stream, det)))
+    return rc;
+  const EnfDims& m = c.m;
+  const EnfWorkspace& W = c.W;
+  hipStream_t st = c.st;
+  if (det && workspace_bytes < c.X.total + enf_det_dx_bytes(m)) return ENF_EWORKSPACE;
+  float* part = det ? c.F(c.X.part) : nullptr;
+  float* dxpart = det ? c.F(c.X.total) : nullptr;
+  const bool zf = enf_use_zfold(m), zb = enf_use_zfold_bwd(m);
+  const size_t per = (size_t)m.B * m.N * m.dx;                    // one channel's query gradient
+  const int passes = dout ? 1 : m.O;
+  if ((rc = enf_side_join_pending(st, workspace))) return rc;
+  if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
+  if (zb && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
+  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
+                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
+    return rc;
+  // the forward tail with the stash; without `out` its B N O values land in the workspace's d ybar region (B N HD floats, O <= 32 <= HD),
+  // which the first backward pass overwrites
+  if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), out ? out : c.F(W.dybar), nullptr, nullptr, nullptr, c.F(W.tail_act), 0, 1, st))) return rc;
+  // default mode: K3 adds to d lt (scratch of this call, never returned: zeroed once, the passes pile up in it) and to the query gradient
+  // with float atomics; deterministic mode: the fixed-order reductions overwrite both
+  if (!det && (hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess ||
+               hipMemsetAsync(grad, 0, sizeof(float) * per * passes, st) != hipSuccess))
+    return ENF_ELAUNCH;
+  for (int o = 0; o < passes; ++o) {
+    if (dout) rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), 1, 1, st);
+    else rc = enf_launch_tail_seed(m, c.L, c.blob, c.F(W.ybar), o, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st);
+    if (rc) return rc;
+    if ((rc = enf_launch_pair_bwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), c.F(W.dlt), nullptr,
+                                  zb ? c.ws + W.wzt : nullptr, zb ? c.F(W.wzb) : nullptr, grad + (size_t)o * per, st, part, dxpart)))
+      return rc;
+  }
+  return ENF_OK;
+}
+
+extern "C" int enf_field_grad(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, float* out, float* jac, void* workspace, size_t workspace_bytes, unsigned flags,
+                              void* stream) {
+  return field_grad_sequence(d, x, x_bstride, p, a, sigma, packed, nullptr, out, jac, true, workspace, workspace_bytes, flags, stream);
+}
+
+extern "C" int enf_query_vjp(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                             const void* packed, const float* dout, float* out, float* dx, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream) {
+  return field_grad_sequence(d, x, x_bstride, p, a, sigma, packed, dout, out, dx, dout != nullptr, workspace, workspace_bytes, flags, stream);
+}
+
 extern "C" int enf_lt_layout(const EnfDesc* d, int* stride, int* off_u, int* off_v0, int* off_pose, int* off_wcoef, int* off_c) {
   int rc = enf_check_desc(d);
   if (rc) return rc;

@@ -153,6 +153,10 @@ int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, cons
                     float* dybar, float* delta, float* act, int bwd, int opt, hipStream_t st);
 int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, const float* dout,
                        float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
+// the seeded tail backward (enf_field_grad): d out = the unit vector of output channel `seed` (0 <= seed < O), formed in registers --
+// no d out in memory; `act` holds the pre-activations a forward with opt & 1 stashed; writes d ybar and delta
+int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
+                         float* act, hipStream_t st);
 // the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
 // backward chain -> d ybar, delta
 // weight: NULL, or one loss weight per query (B N floats, include/enf_hip.h "Weighted loss"); per_value: `weight` (not NULL) holds one

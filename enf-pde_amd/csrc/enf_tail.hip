@@ -30,7 +30,10 @@ struct TailArgs {
   float* loss_part;      // LOSS, deterministic mode: wave w of workgroup g stores its partial in loss_part[g * NWAVES + w] (nullptr: atomic)
   float* tdel;           // weight-gradient backward (WG): per query d a_B | d a_F1 | d a_O0 | d a_O2 (2HD + 2D floats); the layer INPUTS
                          // n^ | gelu(a_F1) | gelu(a_O0) | gelu(a_O2) replace the pre-activations in `act` (enf_train.hip forms X^T delta)
-  int ybar_half;         // forward only (ENF_STAGE_YBAR_HALF): `ybar` holds bf16 rows
+  union {
+    int ybar_half;       // forward only (ENF_STAGE_YBAR_HALF): `ybar` holds bf16 rows
+    int seed;            // backward, SEED (the kernel's template flag) only: the output channel o of the unit seed d out = e_o
+  };
   int NQ, O;             // NQ = B*N queries
   float inv_hd;          // 1 / (H * true num_hidden)
 };
@@ -324,10 +327,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
 // outputs, backward chain: no `out` / `d out` round trip and two launches less between the pair kernels of an inner step.
 // CW (with LOSS): `weight` holds one value per output element (include/enf_hip.h, "Weighted loss": per-channel weights).  An
 // instantiation of its own: the per-point and the unweighted kernels keep their code.
-template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false>
+// SEED (never with RECOMP, WG or LOSS): the seeded backward of enf_field_grad -- d out is the unit vector e_o of output channel
+// o = A.seed (a run-time argument: one instantiation serves every channel), formed in registers where LOSS forms its gradient; no
+// `d out` is read and no (B, N, O) one-hot tensor exists.  The pre-activations come from the forward's stash.
+template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false, bool SEED = false>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   static_assert(!LOSS || RECOMP, "the fused loss needs the forward chain's outputs");
   static_assert(!CW || LOSS, "per-channel weights belong to the fused loss");
+  static_assert(!SEED || (!RECOMP && !WG && !LOSS), "the seeded backward reads the stash and writes d ybar and delta only");
   using T = TailCfg<D, H, BF16>;
   constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD;
   using PG4 = Pan<1, NT, BF16>; using PG2 = Pan<KB, NT, BF16>; using PG0 = Pan<KB, NTH, BF16>; using PGH = Pan<KBH, NTH, BF16>;
@@ -370,6 +377,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
     float se = tail_sq_err<CW>(o4, g0, A, qi, qvalid, quad, 2.0f * A.inv_n * A.gscale);
     se = tail_err_reduce(se, A.err, q0 + col, qvalid, quad);
     if (lane == 0) tail_loss_add(se, A, wave);
+  } else if constexpr (SEED) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) g0[t][i] = (16 * t + 4 * quad + i == A.seed && qvalid) ? 1.f : 0.f;
   } else {
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -490,7 +502,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
 }
 
 template <int D, int H, bool BF16>
-static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false, bool eval = false) {
+static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false, bool eval = false, bool seeded = false) {
   const bool wg = bwd && A.tdel != nullptr;
   const bool fused_loss = bwd && A.target != nullptr;
   using T = TailCfg<D, H, BF16>;
@@ -498,16 +510,21 @@ static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bo
   // few workgroups (at most one per CU): the deeper weight pipeline (LA2) instead of a second workgroup per CU
   const bool la2 = grid.x <= 256;
   // opt: forward -> stash the pre-activations (SAVE); backward -> they are stashed, skip the recompute
-  // [fwd / bwd / bwd + WG / fused loss / fused loss + CW / evaluation / evaluation + CW][la2][opt] (this function is one instantiation per
-  // D, H, BF16), one bit per device
-  static EnfAttrBits attr_done[7][2][2];
+  // [fwd / bwd / bwd + WG / fused loss / fused loss + CW / evaluation / evaluation + CW / seeded bwd][la2][opt] (this function is one
+  // instantiation per D, H, BF16), one bit per device
+  static EnfAttrBits attr_done[8][2][2];
   auto go = [&](void (*kern_ptr)(TailArgs)) -> int {
     const int smem = la2 ? T::SMEM3 : T::SMEM;
-    const int which = eval ? (cw ? 6 : 5) : fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd);
+    const int which = seeded ? 7 : eval ? (cw ? 6 : 5) : fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd);
     if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[which][la2][opt])) return ENF_ELAUNCH;
     hipLaunchKernelGGL(kern_ptr, grid, dim3(NTHREADS), smem, st, A);
     return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
   };
+  if (seeded) {    // the seeded backward: the stash is its only form (opt), d out = e_seed
+    if (!bwd || !opt || wg || fused_loss || eval || A.seed < 0 || A.seed >= A.O) return ENF_EINVAL;
+    return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, false, false, false, false, true>)
+               : go(enf_tail_bwd_kernel<D, H, BF16, false, false, false, false, false, true>);
+  }
   if (eval) {      // the evaluation tail: a forward instantiation whose epilogue forms err / the loss (same LA2 choice as the forward)
     if (bwd || opt || !A.target || (cw && !A.weight)) return ENF_EINVAL;
     if (cw) return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 2>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 2>);
@@ -550,6 +567,27 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
 #define ENF_CASE(DD, HH)                                                                   \
   if (m.D == DD && m.H == HH) return m.bf16 ? launch_tail<DD, HH, true>(A, bwd != 0, opt != 0, st) : launch_tail<DD, HH, false>(A, bwd != 0, opt != 0, st);
+  ENF_CASE(128, 2)
+  ENF_CASE(64, 2)
+  ENF_CASE(128, 1)
+  ENF_CASE(64, 1)
+  ENF_CASE(64, 4)
+#undef ENF_CASE
+  return ENF_EUNSUPPORTED;
+}
+
+int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
+                         float* act, hipStream_t st) {
+  if (m.OB != 1) return ENF_EUNSUPPORTED;
+  TailArgs A;
+  A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr; A.err = nullptr;
+  A.tdel = nullptr; A.out = nullptr; A.dout = nullptr;
+  A.seed = seed;
+  A.ybar = ybar; A.blob = blob; A.L = L; A.dybar = dybar; A.delta = delta; A.act = act;
+  A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
+#define ENF_CASE(DD, HH)                                                                   \
+  if (m.D == DD && m.H == HH)                                                              \
+    return m.bf16 ? launch_tail<DD, HH, true>(A, true, true, st, false, false, true) : launch_tail<DD, HH, false>(A, true, true, st, false, false, true);
   ENF_CASE(128, 2)
   ENF_CASE(64, 2)
   ENF_CASE(128, 1)

@@ -263,12 +263,15 @@ class EquivariantCrossAttentionNeF:
                               variants=tuple(_lib.VARIANT[v] for v in (self.pair_variants or self.default_pair_variants)),
                               masks=masks, embedding=_lib.EMB[self.embedding_type])
 
-    def _workspace(self, desc, device):
+    def _workspace(self, desc, device, size_query=None):
         # one cached scratch buffer per (shape, stream); the autograd graph never keeps it alive
         lib = _lib.load()
         # (sized for the deterministic form while the mode is on: its partial buffers sit behind the plain workspace)
         det = self._det_flag()
-        nbytes = lib.enf_workspace_bytes_ex(ctypes.byref(desc), det) if det else lib.enf_workspace_bytes(ctypes.byref(desc))
+        if size_query is not None:          # an entry point with a size query of its own (desc, flags), e.g. enf_field_grad_workspace_bytes
+            nbytes = size_query(ctypes.byref(desc), det)
+        else:
+            nbytes = lib.enf_workspace_bytes_ex(ctypes.byref(desc), det) if det else lib.enf_workspace_bytes(ctypes.byref(desc))
         if nbytes == 0:
             _lib.check(lib.enf_check_desc(ctypes.byref(desc)))
         key = (str(device), torch.cuda.current_stream(device).cuda_stream)
@@ -485,6 +488,75 @@ class EquivariantCrossAttentionNeF:
         return _EnfFunction.apply(x, p, a, sigma, self, packed)
 
     __call__ = apply
+
+    # ------------------------------------------------------------------ derivative fields
+    def _field_grad_args(self, what, x, p, a, gaussian_window_size):
+        """The checks and conversions of ``apply`` for the derivative calls: (x tensor, its batch stride, p, a, sigma or None)."""
+        if self.num_layers > 0:
+            raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
+        if not (x.is_cuda and p.is_cuda and a.is_cuda):
+            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
+        inv = self.cross_attn_invariant
+        if x.dim() != 3 or x.shape[-1] != inv.num_x_pos_dims:
+            raise AssertionError(f"x has shape {tuple(x.shape)}, invariant '{inv.name}' expects (B, N, {inv.num_x_pos_dims})")
+        if p.shape[-1] != inv.num_z_pos_dims + inv.num_z_ori_dims:
+            raise AssertionError(f"p has width {p.shape[-1]}, expected {inv.num_z_pos_dims + inv.num_z_ori_dims}")
+        if a.shape[-1] != self.latent_dim:
+            raise AssertionError(f"a has width {a.shape[-1]}, expected latent_dim={self.latent_dim}")
+        if x.shape[0] != p.shape[0] or a.shape[:2] != p.shape[:2]:
+            raise AssertionError("batch / latent dimensions of x, p, a disagree")
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        B, Z = p.shape[0], p.shape[1]
+        if sigma is not None and not torch.is_tensor(sigma):
+            sigma = torch.full((B, Z, 1), float(sigma), device=p.device)
+        s_ = sigma.float().reshape(B, Z, 1).contiguous() if sigma is not None else None
+        xb, xstride = self._x_arg(x.float())
+        return xb, xstride, p.float().contiguous(), a.float().contiguous(), s_
+
+    @torch.no_grad()
+    def jacobian(self, params, x, p, a, gaussian_window_size=None, return_out=True):
+        """The decode and its Jacobian w.r.t. the query coordinates in one native call (include/enf_hip.h: enf_field_grad):
+        jac[b, n, o, i] = d out[b, n, o] / d x[b, n, i], returned as (out (B, N, O) or None, jac (B, N, O, dx)); ``jac`` is a permuted view
+        of the call's (O, B, N, dx) buffer.  No autograd graph is built and none of the inputs gets a gradient; ``deterministic``
+        selects the fixed-order sums (equal bits for equal inputs) in place of float atomics.
+        Derivatives are w.r.t. the coordinates as given -- angles for the spherical and ball invariants, no metric factors -- and per
+        signal also for a stride-0 (broadcast) ``x``: sum over the batch for the derivative w.r.t. a shared grid.
+        ``return_out`` False skips the store of the decode."""
+        xb, xstride, p_, a_, s_ = self._field_grad_args("jacobian", x, p, a, gaussian_window_size)
+        lib = _lib.load()
+        packed = self.pack(params)
+        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
+        desc = self._desc(B, N, Z)
+        ws = self._workspace(desc, dev, lib.enf_field_grad_workspace_bytes)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        out = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32) if return_out else None
+        jac = torch.empty((self.num_out, B, N, x.shape[-1]), device=dev, dtype=torch.float32)
+        _lib.launch(dev, lib.enf_field_grad, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(out),
+                    _ptr(jac), _ptr(ws), ws.numel(), self._det_flag(), st)
+        self._ws_touch(ws)
+        return out, jac.permute(1, 2, 0, 3)
+
+    @torch.no_grad()
+    def query_vjp(self, params, x, p, a, gaussian_window_size, dout):
+        """dx (B, N, dx) = sum_o dout[b, n, o] * d out[b, n, o] / d x[b, n, :] for a seed ``dout`` (B, N, O), in one native call with one
+        backward pass (include/enf_hip.h: enf_query_vjp); per signal, coordinates as given, no autograd -- see ``jacobian``."""
+        xb, xstride, p_, a_, s_ = self._field_grad_args("query_vjp", x, p, a, gaussian_window_size)
+        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
+        if tuple(dout.shape) != (B, N, self.num_out):
+            raise AssertionError(f"dout has shape {tuple(dout.shape)}, expected {(B, N, self.num_out)}")
+        lib = _lib.load()
+        packed = self.pack(params)
+        g = dout.float().contiguous()
+        desc = self._desc(B, N, Z)
+        ws = self._workspace(desc, dev, lib.enf_field_grad_workspace_bytes)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        dx = torch.empty((B, N, x.shape[-1]), device=dev, dtype=torch.float32)
+        _lib.launch(dev, lib.enf_query_vjp, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(g), None,
+                    _ptr(dx), _ptr(ws), ws.numel(), self._det_flag(), st)
+        self._ws_touch(ws)
+        return dx
 
     # ------------------------------------------------------------------ relu masks (second-order terms by differences)
     def relu_mask_buffer(self, B, N, Z, device):

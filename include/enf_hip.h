@@ -395,6 +395,40 @@ int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const flo
  * atomics, no scratch, any N >= 1, 64-bit offsets.  The kernel enf_fit_step_e and enf_eval_loss run.  NULL or B, N < 1: ENF_EINVAL. */
 int enf_signal_sum(const float* err, int32_t B, int32_t N, float scale, float* loss_b, void* stream);
 
+/* Derivative fields (enf_field_grad, enf_query_vjp): the Jacobian of a decode with respect to its query coordinates -- grad u, the
+ * vorticity or divergence of a velocity field, a PDE residual on a decoded frame -- in one call, without the weight-gradient machinery.
+ *     jac[o,b,n,i] = d out[b,n,o] / d x[b,n,i]        (O, B, N, dx) fp32, channel-major, required, OVERWRITTEN
+ * The derivatives are with respect to the coordinates AS GIVEN: for the spherical and ball invariants x holds angles (and a radius), and
+ * jac holds the plain partial derivatives w.r.t. those angles -- no metric factors (1 / sin theta, 1 / r) are applied; ponita_full's third
+ * column is d / d theta_x.  jac is per SIGNAL also when x_bstride == 0: a caller who wants the derivative w.r.t. a grid shared by the
+ * batch sums over b.  `out` (B, N, O) is the decode itself, or NULL; with out == NULL
+ * nothing outside jac and the workspace is written.
+ * Sequence: latent prologue; the z-fold backward's per-latent matrices where the descriptor resolves to that variant; the forward pair
+ * kernel; the forward tail, stashing its pre-activations; then per output channel o the SEEDED tail backward -- d out = the unit vector
+ * e_o formed in registers, no (B, N, O) seed tensor exists -- and the backward pair kernel without a store, its query gradient into
+ * jac + o B N dx.  The call picks no pair-kernel variant of its own: pair_fwd_variant / pair_bwd_variant decide, as everywhere.
+ * Default mode: jac is zeroed by the call and every latent's share of a query's gradient is ADDED with float atomics, so the last bits
+ * follow the order in which wavefronts finish.  flags = ENF_BWD_DETERMINISTIC: the shares go to the workspace and are summed over the
+ * latents in index order -- same inputs, same bits, with the promise and the limits of "Deterministic mode" above.  Other flag bits are
+ * ENF_EINVAL.  The gradient of the latent table that the backward pair kernel also forms is scratch of the call and is not returned.
+ * `workspace`: enf_field_grad_workspace_bytes(d, flags) bytes, ONE buffer for everything the call needs (flags = 0: equal to
+ * enf_workspace_bytes(d); deterministic: enf_workspace_bytes_ex(d, flags) plus B Z N dx floats of query-gradient shares); contents need
+ * not be kept.  The size query returns 0 for a bad descriptor, a mask mode or an unknown flag bit.
+ * Errors in this order: the descriptor's; EnfDesc.mask_mode != ENF_MASK_OFF is ENF_EUNSUPPORTED (relu masks belong to the
+ * meta-gradient, not to a decode); a NULL x, p, a, packed, workspace, jac / dx / dout (or sigma with a window) or an unknown flag bit is
+ * ENF_EINVAL; then ENF_EWORKSPACE.  Every invariant, both embeddings, both precisions and every width, head count and O <= 32 of the
+ * forward are served.  Cost: one forward plus O backward passes (DESIGN.md 7 has the measured times). */
+size_t enf_field_grad_workspace_bytes(const EnfDesc* d, unsigned flags);
+int enf_field_grad(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                   const void* packed, float* out /* (B,N,O) or NULL */, float* jac /* (O,B,N,dx), required */, void* workspace,
+                   size_t workspace_bytes, unsigned flags, void* stream);
+/* The vector-Jacobian product for a caller-given seed, the same sequence with ONE backward pass (the tail backward reads `dout`):
+ *     dx[b,n,:] = sum_o dout[b,n,o] * d out[b,n,o] / d x[b,n,:]        (B, N, dx) fp32, required, OVERWRITTEN
+ * per signal like jac.  dout (B, N, O) is required; out, flags, workspace (enf_field_grad_workspace_bytes) and errors as above. */
+int enf_query_vjp(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                  const void* packed, const float* dout /* (B,N,O) */, float* out /* (B,N,O) or NULL */, float* dx /* (B,N,dx) */,
+                  void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
