@@ -69,9 +69,10 @@ extern "C" size_t enf_workspace_bytes(const EnfDesc* d) {
 }
 
 // the workspace of a call with these flags: ENF_BWD_DETERMINISTIC (= ENF_FIT_DETERMINISTIC) adds K3's partial rows and the fused
-// tail's loss partials behind the plain workspace (enf_launch.h: enf_det_workspace)
+// tail's loss partials behind the plain workspace (enf_launch.h: enf_det_workspace); ENF_FIT_SHARED_LATENTS adds nothing (its parts
+// borrow the d ybar | delta region)
 extern "C" size_t enf_workspace_bytes_ex(const EnfDesc* d, unsigned flags) {
-  if (enf_check_desc(d) != ENF_OK || (flags & ~(ENF_BWD_DETERMINISTIC | ENF_BWD_QUERY_GRAD))) return 0;
+  if (enf_check_desc(d) != ENF_OK || (flags & ~(ENF_BWD_DETERMINISTIC | ENF_BWD_QUERY_GRAD | ENF_FIT_SHARED_LATENTS))) return 0;
   const EnfDims m = enf_dims(d);
   const EnfWorkspace W = enf_workspace(m);
   return (flags & ENF_BWD_DETERMINISTIC) ? enf_det_workspace(m, W).total : W.total;
@@ -161,7 +162,9 @@ extern "C" int enf_forward_stages(const EnfDesc* d, const float* x, int64_t x_bs
                                   const float* sigma, const void* packed, float* out, float* ybar, float* lse,
                                   void* workspace, size_t workspace_bytes, unsigned stages, void* stream) {
   EnfCall c;
-  int rc = enf_call(c, d, x && p && a && out, sigma, packed, workspace, workspace_bytes, stream);
+  // ENF_STAGE_SHARED_LATENTS: the caller's statement that the signals share latents and points -- a batch stride contradicts it
+  const bool shared = (stages & ENF_STAGE_SHARED_LATENTS) && d && d->B > 1;
+  int rc = enf_call(c, d, x && p && a && out && !(shared && x_bstride != 0), sigma, packed, workspace, workspace_bytes, stream);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
@@ -176,7 +179,7 @@ extern "C" int enf_forward_stages(const EnfDesc* d, const float* x, int64_t x_bs
   if ((stages & (ENF_STAGE_PAIR | ENF_STAGE_FOLD)) &&
       (rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), yb, ls, zf ? c.ws + W.wz : nullptr, zf ? c.F(W.wzb) : nullptr,
                                 zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, (stages & ENF_STAGE_FOLD) != 0,
-                                ((stages & ENF_STAGE_PAIR) != 0 ? 1 : 0) | (yhalf ? 2 : 0), c.st)))
+                                ((stages & ENF_STAGE_PAIR) != 0 ? 1 : 0) | (yhalf ? 2 : 0), c.st, shared ? c.F(W.dybar) : nullptr)))
     return rc;
   // starts behind the pair kernel, beside the tail, the caller's loss and the tail backward
   if ((stages & ENF_STAGE_PREPARE_BWD) && enf_use_zfold_bwd(m) && (rc = side_prepare_bwd(side_stream(), c, true)) < 0) return rc;
@@ -287,8 +290,10 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
                              void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
-  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && loss && dp && da && dsigma && (!per_value || weight) &&
-                    args_ok, sigma, packed, workspace, workspace_bytes, stream, det);
+  // ENF_FIT_SHARED_LATENTS (include/enf_hip.h): a permission for the forward pair kernel; with one signal it says nothing
+  const bool shared = (flags & ENF_FIT_SHARED_LATENTS) && d && d->B > 1;
+  int rc = enf_call(c, d, !(flags & ~(ENF_FIT_DETERMINISTIC | ENF_FIT_SHARED_LATENTS)) && !(shared && x_bstride != 0) && x && p && a && target &&
+                    loss && dp && da && dsigma && (!per_value || weight) && args_ok, sigma, packed, workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
@@ -296,8 +301,10 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
   const bool zf = enf_use_zfold(m), zb = enf_use_zfold_bwd(m);
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
+  // (shared: the parts of the one forward borrow d ybar | delta, which this step's tail overwrites afterwards)
   if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
-                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
+                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st,
+                                shared ? c.F(W.dybar) : nullptr)))
     return rc;
   // what the backward pair kernel needs from the latent table alone runs on the side stream beside the tail
   if ((rc = side_prepare_bwd(zb ? side_stream() : nullptr, c, !det)) < 0) return rc;
@@ -469,6 +476,18 @@ extern "C" int enf_pair_variant(const EnfDesc* d, int backward) {
   if (backward) return enf_use_zfold_bwd(m) ? ENF_VARIANT_ZFOLD : ENF_VARIANT_LATENT_SPLIT;
   const int sp = enf_zfold_split(m);
   return sp > 1 ? ENF_VARIANT_ZFOLD_ZSPLIT : (sp == 1 ? ENF_VARIANT_ZFOLD : ENF_VARIANT_LATENT_SPLIT);
+}
+
+// the shared-latent forward's parts (enf_layout.h: enf_shared_fwd_parts): 1 and *parts = P where a call with ENF_FIT_SHARED_LATENTS /
+// ENF_STAGE_SHARED_LATENTS on this descriptor runs the one shared forward, 0 (and *parts = 1) where it runs the ordinary sequence
+extern "C" int enf_shared_forward_parts(const EnfDesc* d, int32_t* parts) {
+  const int rc = enf_check_desc(d);
+  if (rc) return rc;
+  if (!parts) return ENF_EINVAL;
+  const EnfDims m = enf_dims(d);
+  const int P = enf_use_zfold(m) || (m.mask_mode != ENF_MASK_OFF && !m.ffn) ? 0 : enf_shared_fwd_parts(m);
+  *parts = P ? P : 1;
+  return P ? 1 : 0;
 }
 
 extern "C" int enf_pair_partition(const EnfDesc* d, int32_t* run, int32_t* workgroups, int32_t* parts) {

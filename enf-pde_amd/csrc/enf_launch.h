@@ -105,9 +105,13 @@ int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const 
 // for the latent-split variant; ysplit: the partial sums of ENF_VARIANT_ZFOLD_ZSPLIT, or NULL.
 //   run_fold   nonzero: the z-fold variant first builds its per-latent matrices (enf_launch_wz)
 //   run_pair   bit set: 1 = run the pair stage (without it the call is the fold alone), 2 = hand ybar to the tail as bf16
+//   spart      != NULL: the caller vouches that all B signals hold the same latent rows and query points (x_bstride == 0) and lends
+//              B N (HD + H) floats: where the call runs the latent-split kernel without relu masks and without the bf16 hand-off, and
+//              B > 1, it computes signal 0 alone, its latents in enf_shared_fwd_parts(m) parts (enf_layout.h), and a merge kernel
+//              writes every signal's rows of ybar / lse; elsewhere the argument is ignored
 int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride, const float* lt,
                         float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit, int run_fold, int run_pair,
-                        hipStream_t st);
+                        hipStream_t st, float* spart = nullptr);
 
 // ---- K3, the backward pair kernel (enf_pair_bwd.hip): ADDS to `dlt`.  store != NULL: the activation-store form (the K4 operands
 // of ENF_NUM_STORE(H) buffers); otherwise wzt / wzb != NULL selects the z-fold form.  dxq: d x per query (added to), or NULL.

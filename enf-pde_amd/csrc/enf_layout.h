@@ -258,6 +258,33 @@ inline int enf_zfold_split(const EnfDims& m) {
 }
 inline bool enf_use_zfold(const EnfDims& m) { return enf_zfold_split(m) > 0; }
 
+// The latent-split kernel's latent splits per workgroup (its 8 waves are 8 / ZS query groups x ZS splits): as many as there
+// are latents to split, up to 8.
+inline int enf_latent_splits(int Z) {
+  int zs = 1;
+  while (zs < 8 && zs * 2 <= Z) zs *= 2;
+  return zs;
+}
+
+// The shared-latent forward (ENF_FIT_SHARED_LATENTS / ENF_STAGE_SHARED_LATENTS): all B signals hold the same latents and query
+// points, so the latent-split kernel runs for signal 0 alone, its latents cut into P parts -- grid (query tiles, P), every part a
+// contiguous ceil(Z / P) latents split ZS ways over the workgroup's waves -- and a merge kernel adds the parts and writes the row
+// to all B signals.  P is the largest power of two such that
+//   every wave of every part still gets a latent      P ZS <= Z
+//   one round of workgroups                           tiles P <= 256 (the CUs of the device the shapes are tuned for)
+//   the parts fit in the borrowed d ybar | delta region of the workspace, B N (HD + H) floats:   P (HD + 3 H) <= B (HD + H)
+// (per query a part holds H D partial sums and (m, l, c) per head).  Returns 0 where the shared path does not run at all (one
+// signal: nothing is shared, and P = 1 alone does not fit the region), else P >= 1 (P = 1: signal 0 once, then the broadcast).
+inline int enf_shared_fwd_parts(const EnfDims& m) {
+  if (m.B < 2) return 0;
+  const int zs = enf_latent_splits(m.Z);
+  const long long tiles = (m.N + 16 * (8 / zs) - 1) / (16 * (8 / zs));
+  const long long slot = m.HD + 3 * m.H, room = (long long)m.B * (m.HD + m.H);
+  int P = 1;
+  while ((long long)2 * P * zs <= m.Z && tiles * 2 * P <= 256 && 2 * P * slot <= room) P *= 2;
+  return P;
+}
+
 ENF_HD inline size_t enf_wzu_bytes(int H, int D) { return (size_t)(D / 32) * 4 * H * 16; }
 
 // Backward counterpart (enf_pair_bwd_kernel<.., ZF = true>): one workgroup per latent, its 8 waves take 8 query

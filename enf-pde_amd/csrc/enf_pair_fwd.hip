@@ -36,6 +36,11 @@ struct PairFwdArgs {
                                           // flattened (signal, query tile, latent) space (enf_layout.h: enf_zfold_streamk)
   int ybar_half;                          // ENF_STAGE_YBAR_HALF: `ybar` is written as bf16 rows (H D x 2 bytes) for the tail kernel of the same call
   float* ysplit;                          // zsplit > 1: [zsplit][B N HD] partial sums | [zsplit][B N H][3] (m, l, c), merged by enf_zsplit_merge_kernel
+  // the shared-latent forward of the latent-split kernel (enf_layout.h: enf_shared_fwd_parts), NULL / 1 / 1 otherwise: the grid is
+  // (query tiles, parts) for signal 0, the partial sums go to [parts][N HD] | [parts][N H][3] (m*, L, C) in `spart` and
+  // enf_shared_merge_kernel writes ybar / lse of all `bcast` signals
+  float* spart;
+  int parts, bcast;
 };
 
 // Debug build only (-DENF_STAMPS): s_memtime stamps of the first iterations of workgroup 0, one row per
@@ -122,6 +127,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   // (signal, query tile, latent) space -- the same count for every workgroup, so one round of <= 256 workgroups ends together -- and
   // walks them as one or more SEGMENTS, each a run of latents of one query tile that leaves partial sums in that tile's slot `part`
   const bool split = ZFOLD && A.zsplit > 1;
+  const bool shared = !ZFOLD && A.spart != nullptr;    // blockIdx.y is then a part of signal 0's latents, not a signal
   const int tiles_n = (A.N + 16 * QG - 1) / (16 * QG);
   int f0 = split ? (int)blockIdx.x * A.sk_len : 0;
   const int f1 = split ? min(f0 + A.sk_len, tiles_n * A.B * A.Z) : 0;
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
     bx = tf - by * tiles_n;
     f0 += seg_iters;
   }
-  b = by;
+  b = shared ? 0 : by;
   n0 = (bx * QG + qgi) * 16;
   const int n = min(n0 + col, A.N - 1);
   const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * dx_, dx_, inv_id);
@@ -171,10 +177,17 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   }
 
   const int ltstride = enf_lt_stride(H, D);
-  const int iters = split ? seg_iters : ZFOLD ? A.Z : (A.Z + ZS - 1) / ZS;
+  // latent-split: this workgroup's latents [z_first, z_end) -- all of them, or with `shared` part `by`: a contiguous ceil(Z / parts),
+  // the last part the rest; a wave whose share of them is empty stays at m = -inf, l = c = 0, Y = 0.  The helper's P ZS <= Z keeps
+  // every wave of a FULL part busy, but the last part may be short (Z = 65, P = 8: 2 latents, six empty waves), and from P = 16 on
+  // whole trailing parts can be empty ((P - 1) ceil(Z / P) >= Z, e.g. Z = 129: part 15 starts at 135): such a workgroup walks its
+  // passes inactive and stores m* = -inf, L = C = 0, Y = 0
+  const int zpart = shared ? (A.Z + A.parts - 1) / A.parts : A.Z;
+  const int z_first = shared ? by * zpart : 0, z_end = shared ? min(z_first + zpart, A.Z) : A.Z;
+  const int iters = split ? seg_iters : ZFOLD ? A.Z : (zpart + ZS - 1) / ZS;
   for (int it = 0; it < iters; ++it) {
-    const int z = ZFOLD ? z_lo + it : it * ZS + zs;
-    const bool active = z < A.Z;
+    const int z = ZFOLD ? z_lo + it : z_first + it * ZS + zs;
+    const bool active = z < z_end;
     const float* ltrow = A.lt + ((size_t)b * A.Z + (active ? z : A.Z - 1)) * ltstride;
     STAMP(0);
     // per-latent vectors u | v0 -> wave-private LDS
@@ -390,8 +403,10 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
       L = fmaf(aw, xch[((w * H + h) * 3 + 1) * 16 + col], L);
       C = fmaf(aw, xch[((w * H + h) * 3 + 2) * 16 + col], C);
     }
+    if (shared && ms == -INFINITY) { L = 0.f; C = 0.f; }     // a part without a latent (the merge skips it)
     mstar[h] = ms; Ltot[h] = L; Ctot[h] = C;
-    const float sc = __expf(sm_m[h] - ms) / L;     // exp(-inf) = 0 for a split that saw no latent
+    float sc = __expf(sm_m[h] - ms) / L;           // exp(-inf) = 0 for a split that saw no latent
+    if (shared) sc = ms == -INFINITY ? 0.f : __expf(sm_m[h] - ms);      // un-normalised: the merge divides by the parts' L
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -420,6 +435,20 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
           for (int i = 0; i < 4; ++i) Y[h][t][i] += src[((h * NT + t) * 4 + i) * 64 + lane];
     }
     __syncthreads();
+  }
+  if (shared) {                // this part's partial sums against its reference m* and (m*, L, C): enf_shared_merge_kernel
+    if (zs == 0 && n0 + col < A.N) {
+      const size_t row = (size_t)by * A.N + n0 + col;
+      float* yo = A.spart + row * (H * D);
+      float* so = A.spart + (size_t)A.parts * A.N * (H * D) + row * (H * 3);
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4*>(yo + h * D + 16 * t + 4 * quad) = Y[h][t];
+        if (quad == 0) { so[h * 3] = mstar[h]; so[h * 3 + 1] = Ltot[h]; so[h * 3 + 2] = Ctot[h]; }
+      }
+    }
+    return;
   }
   if (zs == 0 && n0 + col < A.N) {
     float* yo = A.ybar + ((size_t)b * A.N + n0 + col) * (H * D);
@@ -469,6 +498,39 @@ __global__ __launch_bounds__(256) void enf_zsplit_merge_kernel(const float* __re
   if (c % D == 0) lse[(size_t)row * H + h] = ms + __logf(L);
 }
 
+// The shared-latent forward's merge: the parts of signal 0's row -> ybar / lse of that row in all `bcast` signals, by the formula of
+// the in-kernel combine (and of enf_zsplit_merge_kernel): ybar = (sum_r e^{m_r - m*} Y_r - C) / L, lse = m* + log L with
+// L = sum_r e^{m_r - m*} L_r (C alike); a part with m_r = -inf saw no latent and adds nothing.  One thread per (row, 4 features);
+// blockIdx.y strides over the signals.
+__global__ __launch_bounds__(256) void enf_shared_merge_kernel(const float* __restrict__ part, int P, int N, int H, int D, int bcast,
+                                                              float* __restrict__ ybar, float* __restrict__ lse) {
+  const int HD = H * D, Q = HD / 4;
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)N * Q) return;
+  const int row = (int)(e / Q), c = (int)(e % Q) * 4, h = c / D;
+  const float* st = part + (size_t)P * N * HD;
+  float ms = -INFINITY;
+  for (int r = 0; r < P; ++r) ms = fmaxf(ms, st[((size_t)r * N + row) * (H * 3) + h * 3]);
+  float L = 0.f, C = 0.f;
+  f32x4 y = {0.f, 0.f, 0.f, 0.f};
+  for (int r = 0; r < P; ++r) {
+    const float* q = st + ((size_t)r * N + row) * (H * 3) + h * 3;
+    const float aw = q[0] == -INFINITY ? 0.f : __expf(q[0] - ms);
+    const f32x4 yr = *reinterpret_cast<const f32x4*>(part + ((size_t)r * N + row) * HD + c);
+    L = fmaf(aw, q[1], L);
+    C = fmaf(aw, q[2], C);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = fmaf(aw, yr[i], y[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = (y[i] - C) / L;
+  const float ls = ms + __logf(L);
+  for (int b = blockIdx.y; b < bcast; b += gridDim.y) {
+    *reinterpret_cast<f32x4*>(ybar + ((size_t)b * N + row) * HD + c) = y;
+    if (c % D == 0) lse[((size_t)b * N + row) * H + h] = ls;
+  }
+}
+
 template <int D, int H, bool BF16, bool ZFOLD, bool MASKS = false, int INV = -1, bool FFN = false>
 static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
   if constexpr (!MASKS && !FFN) {
@@ -481,7 +543,14 @@ static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
   if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
   dim3 grid((A.N + 16 * A.qg - 1) / (16 * A.qg), A.B);
   if (ZFOLD && A.zsplit > 1) grid = dim3((unsigned)(((long long)grid.x * A.B * A.Z + A.sk_len - 1) / A.sk_len));
+  const bool shared = !ZFOLD && A.spart != nullptr;
+  if (shared) grid.y = (unsigned)A.parts;
   hipLaunchKernelGGL(kern, grid, dim3(64 * NW), SM::TOTAL, st, A);
+  if (shared) {
+    const long long tot = (long long)A.N * (H * D / 4);
+    hipLaunchKernelGGL(enf_shared_merge_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)(A.bcast < 4 ? A.bcast : 4)), dim3(256), 0, st,
+                       (const float*)A.spart, A.parts, A.N, H, D, A.bcast, A.ybar, A.lse);
+  }
   if (ZFOLD && A.zsplit > 1) {
     const long long BN = (long long)A.B * A.N, tot = BN * H * D;
     hipLaunchKernelGGL(enf_zsplit_merge_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)A.ysplit, A.zsplit, BN, H, D,
@@ -493,15 +562,14 @@ static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor)
 int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
                         const float* lt, float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit,
-                        int run_fold, int run_pair, hipStream_t st) {
+                        int run_fold, int run_pair, hipStream_t st, float* spart) {
   PairFwdArgs A;
   A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.ybar = ybar; A.lse = lse; A.wz = wz; A.wzb = wzb; A.wzu = wzu; A.inv_d = 1.0f / (float)m.Dt;
   A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
   A.masks = m.masks; A.mask_mode = (run_pair & 1) && !m.ffn ? m.mask_mode : 0; A.mask_B = m.mask_B;   // (ffn: no relu, no masks)
   // as many latent splits as there are latents to split (up to 8); the rest of the 8 waves take more queries
-  int zs = 1;
-  while (zs < NWAVES && zs * 2 <= m.Z) zs *= 2;
-  A.qg = NWAVES / zs;
+  static_assert(NWAVES == 8, "enf_latent_splits (enf_layout.h) splits 8 waves");
+  A.qg = NWAVES / enf_latent_splits(m.Z);
   const bool zfold = wz && wzb && wzu && (size_t)m.Z * m.H * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu;
   const EnfStreamK sk = enf_zfold_streamk(m);
   A.zsplit = zfold && ysplit && sk.parts > 1 ? sk.parts : 1;
@@ -509,6 +577,9 @@ int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, 
   A.ysplit = ysplit;
   A.ybar_half = (run_pair & 2) && A.zsplit == 1 && m.bf16;
   A.xcd_remap = zfold && m.B % 8 == 0 && A.zsplit == 1;
+  // the shared-latent forward is a permission: it runs on the latent-split kernel, without relu masks, with ybar in fp32
+  const int sparts = spart && !zfold && !A.mask_mode && (run_pair & 3) == 1 ? enf_shared_fwd_parts(m) : 0;
+  A.spart = sparts ? spart : nullptr; A.parts = sparts ? sparts : 1; A.bcast = sparts ? m.B : 1;
   if (zfold) {
     A.qg = PairWaves<true>::NW;
     if (run_fold) {

@@ -584,7 +584,7 @@ class EquivariantCrossAttentionNeF:
 
     @torch.no_grad()
     def mse_value_and_latent_grads(self, params, x, p, a, gaussian_window_size, target, grad_scale=1.0, loss_out=None, weight=None,
-                                   channel_weight=None, return_errors=False):
+                                   channel_weight=None, return_errors=False, shared_latents=False):
         """loss = mean((nef.apply(params, x, p, a, window) - target)^2) and grad_scale * d loss / d(p, a, window) in one
         sequence of HIP launches (forward, loss + d out, backward), without building an autograd graph: what one
         inner step of the MAML loop computes (pde_trainer.py:175-207; grad_scale = B there).
@@ -598,6 +598,9 @@ class EquivariantCrossAttentionNeF:
         ``return_errors``: also return the per-point errors err (B, N) = sum_o w (out - target)^2 and the per-signal losses loss_b (B,)
         = err.sum(1) / (N O) of this step (include/enf_hip.h, "Per-signal and per-point errors": enf_fit_step_e -- the same kernels
         with one store added, so loss and gradients are the bits of the call without it).  Needs the one-call step.
+        ``shared_latents``: the caller's statement that every signal holds the same latents (p, a, window) and that ``x`` is one point
+        set expanded over the signals with stride 0 -- the first inner step of a fit (include/enf_hip.h: ENF_FIT_SHARED_LATENTS).  The
+        one-call step may then run its forward pair kernel once for all signals; ignored on the composed fallbacks.
         Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err, loss_b)."""
         if return_errors and not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda):
             raise _lib.EnfError("mse_value_and_latent_grads(return_errors=True) needs CUDA/HIP tensors: there is no CPU path")
@@ -672,6 +675,8 @@ class EquivariantCrossAttentionNeF:
             return loss, dp, da, (dsig if sigma is not None else None)
         # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
         # the loss and its gradient formed in registers, pair backward, prologue backward
+        if shared_latents:
+            det |= _lib.ENF_FIT_SHARED_LATENTS
         if return_errors:                   # the same sequence and instantiations; the tail also stores its per-query errors
             err = torch.empty((B, N), device=dev, dtype=torch.float32)
             loss_b = torch.empty((B,), device=dev, dtype=torch.float32)

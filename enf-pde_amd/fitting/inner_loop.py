@@ -1,5 +1,7 @@
 """MAML inner loop and decode on the HIP path (trainers/pde_trainer.py:122-235, 389-405)."""
 import ctypes
+import functools
+import inspect
 
 import torch
 
@@ -160,6 +162,33 @@ def meta_sgd_update(lat, grads, lrs, scale):
     return new
 
 
+@functools.lru_cache(maxsize=64)
+def _takes_shared_hint(fn):
+    """Whether a decoder's step names the ``shared_latents`` keyword.  inner_loop is duck-typed over ``nef`` and the hint is new, so it
+    looks at its callee's signature once per function instead of breaking every decoder -- the stand-ins of the older tests among them --
+    whose step was written before the keyword existed."""
+    try:
+        params = inspect.signature(fn).parameters.values()      # (by name only: a **kwargs wrapper may record what it is given)
+    except (TypeError, ValueError):
+        return False
+    return any(q.name == "shared_latents" for q in params)
+
+
+def _shared_kw(nef, s, per_signal, noise_pos):
+    """The keyword of step ``s``'s mse_value_and_latent_grads: at step 0 every signal still holds the one latent initialisation, and with
+    shared masks the same points (a stride-0 batch) -- unless the poses were jittered per signal -- so the step may run its forward pair
+    kernel once for all signals (include/enf_hip.h: ENF_FIT_SHARED_LATENTS).  A decoder whose step does not know the hint is not given it,
+    and neither is one in deterministic mode: the one forward adds a query's partial sums in another fp32 order, and that mode keeps a
+    fit on shared masks equal, bit for bit, to the same fit on per-signal masks that repeat them."""
+    if s != 0 or per_signal or noise_pos:
+        return {}
+    det = getattr(nef, "is_deterministic", None)
+    if det is not None and det():
+        return {}
+    fn = nef.mse_value_and_latent_grads
+    return {"shared_latents": True} if _takes_shared_hint(getattr(fn, "__func__", fn)) else {}
+
+
 def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
                noise_pos=0.0, generator=None, weights=None, normalize_weights=False, channel_weights=None, per_signal_loss=False):
     """Fit per-signal latents with S steps of meta-SGD (pde_trainer.py:156-235).
@@ -251,13 +280,14 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
     if per_signal_loss:
         return _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, "weight", losses, per_signal, S, B, n_ori,
-                              optimize_gaussian_window)
+                              optimize_gaussian_window, noise_pos)
     n_pos = lat["p_pos"].shape[-1]
     for s in range(S):                                                  # pde_trainer.py:191
         xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)             # every signal's own points, or a stride-0 batch
         _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
                                                          lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
-                                                         weight=None if ws_all is None else ws_all[s])
+                                                         weight=None if ws_all is None else ws_all[s],
+                                                         **_shared_kw(nef, s, per_signal, noise_pos))
         # the gradient of the batch-mean loss times B (pde_trainer.py:206), scaled by the learned rates (:215-219);
         # sigma only moves when asked to (:209-212)
         grads = {"p_pos": dp[..., :n_pos], "a": da}
@@ -281,7 +311,8 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     return losses[S], lat
 
 
-def _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, weight_kw, losses, per_signal, S, B, n_ori, optimize_gaussian_window):
+def _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, weight_kw, losses, per_signal, S, B, n_ori, optimize_gaussian_window,
+                   noise_pos=0.0):
     """inner_loop(per_signal_loss=True) from the gathered inputs on, for every weight form (``weight_kw``: the keyword that takes
     ws_all[s], "weight" or "channel_weight"; ws_all may be None): S steps through enf_fit_step_e, the final loss through enf_eval_loss.
     Returns (loss, lat, loss_b (S + 1, B))."""
@@ -291,7 +322,8 @@ def _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, weight_kw,
         xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)
         _, dp, da, dsig, _, lb = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"),
                                                                 ys_all[s], loss_out=losses[s:s + 1], return_errors=True,
-                                                                **{weight_kw: None if ws_all is None else ws_all[s]})
+                                                                **{weight_kw: None if ws_all is None else ws_all[s]},
+                                                                **_shared_kw(nef, s, per_signal, noise_pos))
         rows.append(lb)
         grads = {"p_pos": dp[..., :n_pos], "a": da}
         if n_ori > 0:
@@ -315,13 +347,13 @@ def _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
     if per_signal_loss:
         return _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, "channel_weight", losses, per_signal, S, B, n_ori,
-                              optimize_gaussian_window)
+                              optimize_gaussian_window, noise_pos)
     n_pos = lat["p_pos"].shape[-1]
     for s in range(S):
         xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)
         _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
                                                          lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
-                                                         channel_weight=ws_all[s])
+                                                         channel_weight=ws_all[s], **_shared_kw(nef, s, per_signal, noise_pos))
         grads = {"p_pos": dp[..., :n_pos], "a": da}
         if n_ori > 0:
             grads["p_ori"] = dp[..., n_pos:]

@@ -190,6 +190,10 @@ int enf_forward(const EnfDesc* d, const float* x, int64_t x_bstride, const float
                                    workspace -- half the bytes of the largest tensor of a forward; the tail rounds `ybar` to bf16 for its
                                    first matrix product anyway, so `out` is the same bit for bit.  Ignored where it does not apply
                                    (f32 mode, ENF_STAGE_TAIL_SAVE, the split z-fold variant, a caller-owned `ybar`). */
+#define ENF_STAGE_SHARED_LATENTS 128u /* the forward's form of ENF_FIT_SHARED_LATENTS (below), same statement and same rules: with
+                                   ENF_STAGE_PAIR the pair kernel may compute signal 0 alone and write its `ybar` / `lse` rows to every
+                                   signal; B > 1 with x_bstride != 0 is ENF_EINVAL.  Where ENF_STAGE_YBAR_HALF applies in the same
+                                   call, that hand-off runs instead.  The workspace's d ybar | delta region is overwritten. */
 int enf_forward_stages(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a,
                        const float* sigma, const void* packed, float* out, float* ybar, float* lse,
                        void* workspace, size_t workspace_bytes, unsigned stages, void* stream);
@@ -320,6 +324,21 @@ int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const floa
 /* The same with flags (0 = enf_fit_step).  ENF_FIT_DETERMINISTIC: loss and gradients are summed in a fixed order (same inputs,
  * same bits; "Deterministic mode" above); `workspace`: enf_workspace_bytes_ex(d, ENF_FIT_DETERMINISTIC). */
 #define ENF_FIT_DETERMINISTIC 16u
+/* ENF_FIT_SHARED_LATENTS (enf_fit_step_ex / _w / _cw / _e): the caller's statement that rows b Z + z of `p`, `a` and `sigma` are equal
+ * for all b and that all signals share their query points -- the first inner step of a fit, which starts every signal from the one
+ * latent initialisation on one shared mask.  B > 1 with x_bstride != 0 contradicts it: ENF_EINVAL.  B == 1: no-op.  The flag is a
+ * permission, not a command: where the forward resolves to the latent-split pair kernel and relu masks are off, that kernel then
+ * runs ONCE, for signal 0, with its latents cut into P parts over all compute units (enf_shared_forward_parts), and a merge kernel
+ * writes the row to all B signals' `ybar` / `lse`; elsewhere the ordinary sequence runs unchanged.  What differs from the call without
+ * the flag is the fp32 order in which the partial sums over a query's latents are added; the B copies are the same bits.  Everything
+ * behind the forward pair kernel (tail, loss, backward) is the ordinary sequence on per-signal targets and weights.  The parts borrow
+ * the workspace's d ybar | delta region: the workspace sizes do not change (enf_workspace_bytes_ex accepts the bit and ignores it).
+ * The library does NOT check the statement: with unequal latents every signal gets signal 0's forward. */
+#define ENF_FIT_SHARED_LATENTS 128u
+/* 1 and *parts = P (a power of two; 1 = signal 0 in one pass, then the broadcast) where a call with ENF_FIT_SHARED_LATENTS /
+ * ENF_STAGE_SHARED_LATENTS on this descriptor runs the shared forward; 0 and *parts = 1 where it runs the ordinary sequence (B == 1,
+ * the z-fold forward, relu masks); negative ENF_E* on a bad descriptor. */
+int enf_shared_forward_parts(const EnfDesc* d, int32_t* parts);
 int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                     const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
                     void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
