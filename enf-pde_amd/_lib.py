@@ -31,6 +31,14 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
            "enf_ode_basis_backward", "enf_relu_mask_bytes", "enf_meta_sgd_update", "enf_table_adam_update"]
 ENF_NUM_PAIR_TENSORS = 12          # ENF_P_* of include/enf_hip.h
+# every ENF_STAGE_* / ENF_BWD_* / ENF_FIT_* / ENF_MSE_* bit of include/enf_hip.h under the header's name (tests/test_host.py
+# compares them): package code builds its stage and flag words from these, never from numbers
+ENF_STAGE_PROLOGUE, ENF_STAGE_PAIR, ENF_STAGE_TAIL, ENF_STAGE_FOLD = 1, 2, 4, 8
+ENF_STAGE_TAIL_SAVE = 16           # stash the tail's pre-activations for the backward (ENF_BWD_REUSE_TAIL)
+ENF_STAGE_PREPARE_BWD = 32         # a backward on the same inputs and workspace follows (ENF_BWD_REUSE_PREPARED)
+ENF_STAGE_YBAR_HALF = 64           # nothing reads this call's ybar: the pair kernel may hand it to the tail as bf16
+ENF_STAGES_FORWARD = ENF_STAGE_PROLOGUE | ENF_STAGE_PAIR | ENF_STAGE_TAIL | ENF_STAGE_FOLD       # (not a macro: what enf_forward runs)
+ENF_BWD_REUSE_PROLOGUE, ENF_BWD_REUSE_TAIL, ENF_BWD_REUSE_PREPARED, ENF_BWD_ONLY_PAIR = 1, 2, 4, 8
 # deterministic mode (include/enf_hip.h, "Deterministic mode"): one bit for every entry point that takes flags
 ENF_BWD_DETERMINISTIC = ENF_FIT_DETERMINISTIC = ENF_MSE_DETERMINISTIC = 16
 ENF_FIT_SHARED_LATENTS = ENF_STAGE_SHARED_LATENTS = 128      # include/enf_hip.h: the signals share latents and points (first inner step)
@@ -259,6 +267,17 @@ def launch(dev, fn, *args):
         return check(fn(*args))
     with torch.cuda.device(idx):
         return check(fn(*args))
+
+
+def ptr(t):
+    """A tensor's address as a pointer argument; None is NULL."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def stream(dev):
+    """The current torch stream of ``dev`` as the stream argument of an entry point."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def make_desc(B, N, Z, H, D, C, O, dx, invariant_id, use_window, precision, d_true=0, h_true=0, variants=(0, 0),

@@ -83,8 +83,7 @@ def _set(tree, path, value):
     tree[path[-1]] = value
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+_ptr = _lib.ptr
 
 
 FUSED_FIT_STEP = __import__("os").environ.get("ENF_FIT_STEP") != "0"      # mse_value_and_latent_grads through enf_fit_step (one call)
@@ -98,11 +97,10 @@ class _EnfFunction(torch.autograd.Function):
         lib = _lib.load()
         B, Z = p.shape[0], p.shape[1]
         N = x.shape[1]
-        desc = model._desc(B, N, Z, masks=model._masks)
-        xb, xstride = model._x_arg(x)
-        p_, a_ = p.contiguous(), a.contiguous()
-        s_ = sigma.contiguous() if sigma is not None else None
         dev = p.device
+        desc, ws, st = model._call_ctx(B, N, Z, dev, masks=model._masks)
+        xb, xstride = model._x_arg(x)
+        p_, a_, s_ = model._latent_args(p, a, sigma)
         out = torch.empty((B, N, model.num_out), device=dev, dtype=torch.float32)
         HD = model._Hp * model._Dp
         # no input needs a gradient (a decode): nothing will read this call's ybar / lse -- they stay in the workspace, and the pair
@@ -110,8 +108,6 @@ class _EnfFunction(torch.autograd.Function):
         no_grad = not any(ctx.needs_input_grad[:4])
         ybar = None if no_grad else torch.empty((B, N, HD), device=dev, dtype=torch.float32)
         lse = None if no_grad else torch.empty((B, N, model._Hp), device=dev, dtype=torch.float32)
-        ws = model._workspace(desc, dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         # a backward follows when an input needs a gradient: stash the tail's pre-activations for it (ENF_STAGE_TAIL_SAVE)
         ctx.tail_saved = any(ctx.needs_input_grad[1:4])
         # the latent table depends on (p, a, sigma, weights) only and sits at the head of the workspace whatever N is: a
@@ -120,7 +116,9 @@ class _EnfFunction(torch.autograd.Function):
         lt_key = (ws.data_ptr(), packed.data_ptr(), B, Z) + tuple((t.data_ptr(), t._version) for t in (p_, a_) + ((s_,) if s_ is not None else ()))
         held = model._lt_held.get(ws.data_ptr())
         reuse_lt = held is not None and held[0] == lt_key and held[1] == model._ws_tags.get(ws.data_ptr())
-        stages = (14 if reuse_lt else 15) | (16 if ctx.tail_saved else 0) | (64 if no_grad else 0)
+        stages = _lib.ENF_STAGES_FORWARD | (_lib.ENF_STAGE_TAIL_SAVE if ctx.tail_saved else 0) | (_lib.ENF_STAGE_YBAR_HALF if no_grad else 0)
+        if reuse_lt:
+            stages &= ~_lib.ENF_STAGE_PROLOGUE
         _lib.launch(dev, lib.enf_forward_stages, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed),
                                           _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(), stages, st)
         ctx.ws_tag = model._ws_touch(ws)      # backward may reuse the latent table if nothing else used the workspace
@@ -142,18 +140,16 @@ class _EnfFunction(torch.autograd.Function):
         sigma = s_ if ctx.has_sigma else None
         B, Z = p_.shape[0], p_.shape[1]
         N = ybar.shape[1]
-        desc = model._desc(B, N, Z)
         dev = p_.device
+        desc, ws, st = model._call_ctx(B, N, Z, dev)
         dout = dout.contiguous().float()
         dp = torch.empty_like(p_)
         da = torch.empty_like(a_)
         dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
-        ws = model._workspace(desc, dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        reuse = 1 if model._ws_tag(ws) == ctx.ws_tag else 0          # ENF_BWD_REUSE_PROLOGUE
+        reuse = _lib.ENF_BWD_REUSE_PROLOGUE if model._ws_tag(ws) == ctx.ws_tag else 0
         if reuse and ctx.tail_saved:
-            reuse |= 2                                               # ENF_BWD_REUSE_TAIL
-        reuse |= model._det_flag()                                   # ENF_BWD_DETERMINISTIC
+            reuse |= _lib.ENF_BWD_REUSE_TAIL
+        reuse |= model._det_flag()
         _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(p_), _ptr(a_), _ptr(sigma),
                                                _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da),
                                                _ptr(dsig), _ptr(ws), ws.numel(), reuse, st)
@@ -228,6 +224,7 @@ class EquivariantCrossAttentionNeF:
         self.pair_variants = None               # (forward, backward) pair-kernel variant of this model's calls (_lib.VARIANT
                                                 # keys); None = the class default below (tests flip it to cover both kernels)
         self._masks = None                      # (buffer, "write" | "read", signals) inside relu_masks(), else None
+        self._pair_key = self._pair_blob = self._train_blob = None      # the training path's packed blobs and their keys (_train.py)
 
     def with_precision(self, precision):
         """The same model (fields, invariants) running its per-pair contractions in another arithmetic ("f32" | "bf16"), with
@@ -238,6 +235,7 @@ class EquivariantCrossAttentionNeF:
         m = copy.copy(self)
         m.precision = precision
         m._pack_cache, m._ws_cache, m._ws_gen, m._ws_tags, m._masks, m._lt_held = {}, {}, 0, {}, None, {}
+        m._pair_key = m._pair_blob = m._train_blob = None
         return m
 
     # ------------------------------------------------------------------ deterministic mode
@@ -253,11 +251,12 @@ class EquivariantCrossAttentionNeF:
         return _lib.ENF_BWD_DETERMINISTIC if self.is_deterministic() else 0
 
     # ------------------------------------------------------------------ descriptors / buffers
-    def _desc(self, B, N, Z, masks=None):
-        """The call descriptor; ``masks`` = a (buffer, mode, signals) triple for calls whose pair kernels take relu masks."""
-        inv = self.cross_attn_invariant
+    def _desc(self, B, N, Z, masks=None, inv=None, dx=None):
+        """The call descriptor; ``masks`` = a (buffer, mode, signals) triple for calls whose pair kernels take relu masks.  ``inv`` and
+        ``dx``: another invariant and coordinate width than the cross-attention's (the latent self-attention blocks of _train.py)."""
+        inv = inv if inv is not None else self.cross_attn_invariant
         return _lib.make_desc(B, N, Z, self._Hp, self._Dp, self.latent_dim, self.num_out,
-                              inv.num_x_pos_dims, inv.kernel_id, self.use_gaussian_window, _lib.PREC[self.precision],
+                              inv.num_x_pos_dims if dx is None else dx, inv.kernel_id, self.use_gaussian_window, _lib.PREC[self.precision],
                               d_true=self.num_hidden if self._Dp != self.num_hidden else 0,
                               h_true=self.num_heads if self._Hp != self.num_heads else 0,
                               variants=tuple(_lib.VARIANT[v] for v in (self.pair_variants or self.default_pair_variants)),
@@ -274,12 +273,37 @@ class EquivariantCrossAttentionNeF:
             nbytes = lib.enf_workspace_bytes_ex(ctypes.byref(desc), det) if det else lib.enf_workspace_bytes(ctypes.byref(desc))
         if nbytes == 0:
             _lib.check(lib.enf_check_desc(ctypes.byref(desc)))
-        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+        key = (str(device), _lib.stream(device).value)
         ws = self._ws_cache.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(int(nbytes), device=device, dtype=torch.uint8)
             self._ws_cache[key] = ws
         return ws
+
+    def _call_ctx(self, B, N, Z, dev, masks=None, size_query=None):
+        """What every native call on this model starts from: (descriptor, workspace, stream argument) for a (B, N, Z) problem on the
+        current stream of ``dev``; ``masks`` as in _desc, ``size_query`` as in _workspace."""
+        desc = self._desc(B, N, Z, masks=masks)
+        return desc, self._workspace(desc, dev, size_query), _lib.stream(dev)
+
+    @staticmethod
+    def _latent_args(p, a, sigma):
+        """The latents as the library takes them: p, a float32 and contiguous, sigma (B, Z, 1) likewise or None."""
+        p_ = p.float().contiguous()
+        s_ = sigma.float().reshape(p_.shape[0], p_.shape[1], 1).contiguous() if sigma is not None else None
+        return p_, a.float().contiguous(), s_
+
+    def _weight_args(self, weight, channel_weight, B, N):
+        """The loss weights of a (B, N) problem, checked and as the library takes them: (weight (B, N) or None, channel_weight
+        (B, N, O) or None), float32 and contiguous; at most one of them."""
+        if weight is not None and channel_weight is not None:
+            raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
+        if channel_weight is not None and tuple(channel_weight.shape) != (B, N, self.num_out):
+            raise ValueError(f"channel_weight has shape {tuple(channel_weight.shape)}, expected {(B, N, self.num_out)}")
+        if weight is not None and tuple(weight.shape) != (B, N):
+            raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(B, N)}")
+        return (weight.float().contiguous() if weight is not None else None,
+                channel_weight.float().contiguous() if channel_weight is not None else None)
 
     def _ws_touch(self, ws):
         """Mark a use of workspace `ws`; returns the tag identifying this use."""
@@ -385,9 +409,7 @@ class EquivariantCrossAttentionNeF:
         ``_version`` unchanged: call this method after such a write (``load_params`` does, for the tree it returns is new)."""
         self._pack_cache.clear()
         self._lt_held.clear()
-        self._pair_key = None
-        self._pair_blob = None
-        self._train_blob = None
+        self._pair_key = self._pair_blob = self._train_blob = None
 
     def load_params(self, tree, device="cuda"):
         """Build a parameter tree from nested numpy / torch arrays (e.g. an exported Flax tree)."""
@@ -420,8 +442,7 @@ class EquivariantCrossAttentionNeF:
         nbytes = lib.enf_packed_weight_bytes(ctypes.byref(desc))
         blob = torch.empty(int(nbytes), device=dev, dtype=torch.uint8)
         arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.launch(dev, lib.enf_pack_weights, ctypes.byref(desc), arr, _ptr(blob), st)
+        _lib.launch(dev, lib.enf_pack_weights, ctypes.byref(desc), arr, _ptr(blob), _lib.stream(dev))
         self._pack_cache["k"] = (key, blob, ts)   # keep the fp32 sources alive until the pack kernels ran
         return blob
 
@@ -449,15 +470,13 @@ class EquivariantCrossAttentionNeF:
                 [(HD, D), (D,), (D, D), (D,), (D, O), (O,)])
 
     # ------------------------------------------------------------------ forward
-    def apply(self, params, x, p, a, gaussian_window_size=None):
-        """nef.apply(params, x, p, a, gaussian_window) -> (B, N, num_out)   (NEF:204-235).
-
-        x (B,N,dx) [stride-0 batch allowed], p (B,Z,z_pos+z_ori), a (B,Z,latent_dim),
-        gaussian_window_size (B,Z,1).  Differentiable w.r.t. p, a, gaussian_window_size, the weights and x.
-        """
-        inv = self.cross_attn_invariant
+    def _check_inputs(self, what, x, p, a, gaussian_window_size):
+        """The input checks of the entry point ``what`` (apply and the derivative calls): device, coordinate / pose / latent widths,
+        batch agreement and the presence of the window.  Returns sigma: the window as a tensor (a scalar is expanded to (B, Z, 1)), or
+        None for a model without one."""
         if not (x.is_cuda and p.is_cuda and a.is_cuda):
-            raise _lib.EnfError("EquivariantCrossAttentionNeF.apply needs CUDA/HIP tensors: there is no CPU path")
+            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
+        inv = self.cross_attn_invariant
         if x.shape[-1] != inv.num_x_pos_dims:
             raise AssertionError(f"x has coordinate width {x.shape[-1]}, invariant '{inv.name}' expects {inv.num_x_pos_dims}")
         if p.shape[-1] != inv.num_z_pos_dims + inv.num_z_ori_dims:
@@ -471,9 +490,17 @@ class EquivariantCrossAttentionNeF:
             raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
         if sigma is not None and not torch.is_tensor(sigma):
             sigma = torch.full((p.shape[0], p.shape[1], 1), float(sigma), device=p.device)
-        x, p, a = x.float(), p.float(), a.float()
-        if sigma is not None:
-            sigma = sigma.float().reshape(p.shape[0], p.shape[1], 1)
+        return sigma
+
+    def apply(self, params, x, p, a, gaussian_window_size=None):
+        """nef.apply(params, x, p, a, gaussian_window) -> (B, N, num_out)   (NEF:204-235).
+
+        x (B,N,dx) [stride-0 batch allowed], p (B,Z,z_pos+z_ori), a (B,Z,latent_dim),
+        gaussian_window_size (B,Z,1).  Differentiable w.r.t. p, a, gaussian_window_size, the weights and x.
+        """
+        sigma = self._check_inputs("apply", x, p, a, gaussian_window_size)
+        x = x.float()
+        p, a, sigma = self._latent_args(p, a, sigma)
         ts = self.param_tensors(params)
         if self.num_layers > 0:
             from . import _train
@@ -491,29 +518,15 @@ class EquivariantCrossAttentionNeF:
 
     # ------------------------------------------------------------------ derivative fields
     def _field_grad_args(self, what, x, p, a, gaussian_window_size):
-        """The checks and conversions of ``apply`` for the derivative calls: (x tensor, its batch stride, p, a, sigma or None)."""
+        """The checks of ``apply`` for the derivative calls, then (x tensor, its batch stride, p, a, sigma or None) as the library
+        takes them."""
         if self.num_layers > 0:
             raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
-        if not (x.is_cuda and p.is_cuda and a.is_cuda):
-            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
-        inv = self.cross_attn_invariant
-        if x.dim() != 3 or x.shape[-1] != inv.num_x_pos_dims:
-            raise AssertionError(f"x has shape {tuple(x.shape)}, invariant '{inv.name}' expects (B, N, {inv.num_x_pos_dims})")
-        if p.shape[-1] != inv.num_z_pos_dims + inv.num_z_ori_dims:
-            raise AssertionError(f"p has width {p.shape[-1]}, expected {inv.num_z_pos_dims + inv.num_z_ori_dims}")
-        if a.shape[-1] != self.latent_dim:
-            raise AssertionError(f"a has width {a.shape[-1]}, expected latent_dim={self.latent_dim}")
-        if x.shape[0] != p.shape[0] or a.shape[:2] != p.shape[:2]:
-            raise AssertionError("batch / latent dimensions of x, p, a disagree")
-        sigma = gaussian_window_size if self.use_gaussian_window else None
-        if self.use_gaussian_window and sigma is None:
-            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
-        B, Z = p.shape[0], p.shape[1]
-        if sigma is not None and not torch.is_tensor(sigma):
-            sigma = torch.full((B, Z, 1), float(sigma), device=p.device)
-        s_ = sigma.float().reshape(B, Z, 1).contiguous() if sigma is not None else None
-        xb, xstride = self._x_arg(x.float())
-        return xb, xstride, p.float().contiguous(), a.float().contiguous(), s_
+        sigma = self._check_inputs(what, x, p, a, gaussian_window_size)
+        if x.dim() != 3:
+            raise AssertionError(f"x has shape {tuple(x.shape)}, expected (B, N, {x.shape[-1]})")
+        p_, a_, s_ = self._latent_args(p, a, sigma)
+        return (*self._x_arg(x.float()), p_, a_, s_)
 
     @torch.no_grad()
     def jacobian(self, params, x, p, a, gaussian_window_size=None, return_out=True):
@@ -528,9 +541,7 @@ class EquivariantCrossAttentionNeF:
         lib = _lib.load()
         packed = self.pack(params)
         B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
-        desc = self._desc(B, N, Z)
-        ws = self._workspace(desc, dev, lib.enf_field_grad_workspace_bytes)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_field_grad_workspace_bytes)
         out = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32) if return_out else None
         jac = torch.empty((self.num_out, B, N, x.shape[-1]), device=dev, dtype=torch.float32)
         _lib.launch(dev, lib.enf_field_grad, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(out),
@@ -549,9 +560,7 @@ class EquivariantCrossAttentionNeF:
         lib = _lib.load()
         packed = self.pack(params)
         g = dout.float().contiguous()
-        desc = self._desc(B, N, Z)
-        ws = self._workspace(desc, dev, lib.enf_field_grad_workspace_bytes)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_field_grad_workspace_bytes)
         dx = torch.empty((B, N, x.shape[-1]), device=dev, dtype=torch.float32)
         _lib.launch(dev, lib.enf_query_vjp, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(g), None,
                     _ptr(dx), _ptr(ws), ws.numel(), self._det_flag(), st)
@@ -606,16 +615,7 @@ class EquivariantCrossAttentionNeF:
             raise _lib.EnfError("mse_value_and_latent_grads(return_errors=True) needs CUDA/HIP tensors: there is no CPU path")
         if return_errors and (self.num_layers > 0 or not FUSED_FIT_STEP):
             raise NotImplementedError("return_errors needs the one-call inner step (enf_fit_step_e): num_layers = 0 and ENF_FIT_STEP on")
-        if channel_weight is not None:
-            if weight is not None:
-                raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
-            if tuple(channel_weight.shape) != (p.shape[0], x.shape[1], self.num_out):
-                raise ValueError(f"channel_weight has shape {tuple(channel_weight.shape)}, expected {(p.shape[0], x.shape[1], self.num_out)}")
-            channel_weight = channel_weight.float().contiguous()
-        if weight is not None:
-            if tuple(weight.shape) != (p.shape[0], x.shape[1]):
-                raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(p.shape[0], x.shape[1])}")
-            weight = weight.float().contiguous()
+        weight, channel_weight = self._weight_args(weight, channel_weight, p.shape[0], x.shape[1])
         lib = _lib.load()
         sigma = gaussian_window_size if self.use_gaussian_window else None
         if self.num_layers > 0:           # no fused sequence for the layered model: autograd through apply()
@@ -638,13 +638,10 @@ class EquivariantCrossAttentionNeF:
                 loss_out.add_(loss.detach().reshape(1))
             return loss.detach().reshape(1), g[0], g[1], (g[2] if sigma is not None else None)
         packed = self.pack(params)
-        x, p_, a_ = x.float(), p.float().contiguous(), a.float().contiguous()
-        s_ = sigma.float().reshape(p_.shape[0], p_.shape[1], 1).contiguous() if sigma is not None else None
+        p_, a_, s_ = self._latent_args(p, a, sigma)
         B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
-        desc = self._desc(B, N, Z, masks=self._masks)
-        xb, xstride = self._x_arg(x)
-        ws = self._workspace(desc, dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        xb, xstride = self._x_arg(x.float())
+        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
         tgt = target.float().contiguous()
         if tuple(tgt.shape) != (B, N, self.num_out):
             raise AssertionError(f"target has shape {tuple(tgt.shape)}, expected {(B, N, self.num_out)}")
@@ -658,7 +655,8 @@ class EquivariantCrossAttentionNeF:
             ybar = torch.empty((B, N, HD), device=dev, dtype=torch.float32)
             lse = torch.empty((B, N, self._Hp), device=dev, dtype=torch.float32)
             _lib.launch(dev, lib.enf_forward_stages, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed),
-                        _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(), 15 | 16 | 32, st)       # + TAIL_SAVE + PREPARE_BWD
+                        _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(),
+                        _lib.ENF_STAGES_FORWARD | _lib.ENF_STAGE_TAIL_SAVE | _lib.ENF_STAGE_PREPARE_BWD, st)
             dout = torch.empty_like(out)
             nmse = int(lib.enf_mse_scratch_bytes(out.numel(), det))
             mse_scr = torch.empty(nmse, device=dev, dtype=torch.uint8) if nmse else None
@@ -670,7 +668,7 @@ class EquivariantCrossAttentionNeF:
                             _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
             _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_),
                         _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(),
-                        1 | 2 | 4 | det, st)
+                        _lib.ENF_BWD_REUSE_PROLOGUE | _lib.ENF_BWD_REUSE_TAIL | _lib.ENF_BWD_REUSE_PREPARED | det, st)
             self._ws_touch(ws)
             return loss, dp, da, (dsig if sigma is not None else None)
         # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
@@ -680,20 +678,16 @@ class EquivariantCrossAttentionNeF:
         if return_errors:                   # the same sequence and instantiations; the tail also stores its per-query errors
             err = torch.empty((B, N), device=dev, dtype=torch.float32)
             loss_b = torch.empty((B,), device=dev, dtype=torch.float32)
-            _lib.launch(dev, lib.enf_fit_step_e, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                        float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(weight), _ptr(channel_weight),
-                        _ptr(err), _ptr(loss_b), det, st)
-            self._ws_touch(ws)
-            return loss, dp, da, (dsig if sigma is not None else None), err, loss_b
-        if channel_weight is not None:      # the same sequence, the tail's per-channel instantiation
-            _lib.launch(dev, lib.enf_fit_step_cw, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                        float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(channel_weight), det, st)
-            self._ws_touch(ws)
-            return loss, dp, da, (dsig if sigma is not None else None)
-        _lib.launch(dev, lib.enf_fit_step_w, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), _ptr(weight), det, st)
+            fn, extra = lib.enf_fit_step_e, (_ptr(weight), _ptr(channel_weight), _ptr(err), _ptr(loss_b))
+        elif channel_weight is not None:    # the same sequence, the tail's per-channel instantiation
+            fn, extra = lib.enf_fit_step_cw, (_ptr(channel_weight),)
+        else:
+            fn, extra = lib.enf_fit_step_w, (_ptr(weight),)
+        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt), float(grad_scale),
+                    _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), *extra, det, st)
         self._ws_touch(ws)
-        return loss, dp, da, (dsig if sigma is not None else None)
+        res = (loss, dp, da, dsig if sigma is not None else None)
+        return res + (err, loss_b) if return_errors else res
 
     @torch.no_grad()
     def eval_loss(self, params, x, p, a, gaussian_window_size, target, weight=None, channel_weight=None, loss_out=None, per_signal=True):
@@ -710,12 +704,7 @@ class EquivariantCrossAttentionNeF:
         if self.num_layers > 0:
             raise NotImplementedError("eval_loss is built for num_layers = 0 (the fused decoder)")
         B, Z, N = p.shape[0], p.shape[1], x.shape[1]
-        if weight is not None and channel_weight is not None:
-            raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
-        if channel_weight is not None and tuple(channel_weight.shape) != (B, N, self.num_out):
-            raise ValueError(f"channel_weight has shape {tuple(channel_weight.shape)}, expected {(B, N, self.num_out)}")
-        if weight is not None and tuple(weight.shape) != (B, N):
-            raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(B, N)}")
+        w_, cw_ = self._weight_args(weight, channel_weight, B, N)
         tgt = target.float().contiguous()
         if tuple(tgt.shape) != (B, N, self.num_out):
             raise AssertionError(f"target has shape {tuple(tgt.shape)}, expected {(B, N, self.num_out)}")
@@ -724,15 +713,10 @@ class EquivariantCrossAttentionNeF:
         if self.use_gaussian_window and sigma is None:
             raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
         packed = self.pack(params)
-        p_, a_ = p.float().contiguous(), a.float().contiguous()
-        s_ = sigma.float().reshape(B, Z, 1).contiguous() if sigma is not None else None
-        w_ = weight.float().contiguous() if weight is not None else None
-        cw_ = channel_weight.float().contiguous() if channel_weight is not None else None
+        p_, a_, s_ = self._latent_args(p, a, sigma)
         dev = p_.device
-        desc = self._desc(B, N, Z, masks=self._masks)
         xb, xstride = self._x_arg(x.float())
-        ws = self._workspace(desc, dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
         err = torch.empty((B, N), device=dev, dtype=torch.float32)
         loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
         _lib.launch(dev, lib.enf_eval_loss, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
@@ -749,6 +733,6 @@ class EquivariantCrossAttentionNeF:
         e = err.float().contiguous()
         B, N = e.shape
         loss_b = torch.empty((B,), device=e.device, dtype=torch.float32)
-        st = ctypes.c_void_p(torch.cuda.current_stream(e.device).cuda_stream)
-        _lib.launch(e.device, _lib.load().enf_signal_sum, _ptr(e), B, N, 1.0 / (float(N) * float(self.num_out)), _ptr(loss_b), st)
+        _lib.launch(e.device, _lib.load().enf_signal_sum, _ptr(e), B, N, 1.0 / (float(N) * float(self.num_out)), _ptr(loss_b),
+                    _lib.stream(e.device))
         return loss_b

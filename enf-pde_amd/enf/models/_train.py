@@ -24,12 +24,16 @@ LN_EPS = 1e-6          # flax.linen.LayerNorm default (NEF:56, ECA:19)
 STORE_BUDGET_BYTES = 6 << 30   # bound on the materialised activations of one backward chunk
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+_ptr, _stream = _lib.ptr, _lib.stream
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+def _chunk_signals(size_query, desc, B, group, sflags):
+    """How many signals one backward chunk takes: the largest multiple of ``group`` (one group at the least, B at the most) whose
+    scratch, by ``size_query(desc, signals, flags)``, fits STORE_BUDGET_BYTES."""
+    cb = B
+    while cb > group and int(size_query(ctypes.byref(desc), cb, sflags)) > STORE_BUDGET_BYTES:
+        cb = max(group, (cb - 1) // group * group)
+    return cb
 
 
 def lt_layout(desc):
@@ -115,7 +119,7 @@ class _PairFunction(torch.autograd.Function):
         Z = lt.shape[0] // B
         H, D = model._Hp, model._Dp
         dev = lt.device
-        ctx.masks = getattr(model, "_masks", None)       # relu masks of this call (model.relu_masks); its backward replays them
+        ctx.masks = model._masks                         # relu masks of this call (model.relu_masks); its backward replays them
         desc = model._desc(B, N, Z, masks=ctx.masks) if ctx.masks is not None else model._desc(B, N, Z)
         xb, xstride = model._x_arg(x)
         lt_ = lt.detach().contiguous()
@@ -123,8 +127,8 @@ class _PairFunction(torch.autograd.Function):
         # the packed panels of the effective tensors: the outer step runs several passes on the SAME weights (new tensor
         # objects of unchanged storage), so the blob is cached on the identity + version of the leaf weights
         # (apply_train: model._pair_key) and the ~20 pack launches run once per weight update, not once per pass
-        key, leaves = getattr(model, "_pair_key", None) or (None, None)
-        hit = getattr(model, "_pair_blob", None)
+        key, leaves = model._pair_key or (None, None)
+        hit = model._pair_blob
         if key is not None and hit is not None and hit[0] == key:
             blob, effc = hit[1], hit[2]
         else:
@@ -183,9 +187,7 @@ class _PairFunction(torch.autograd.Function):
         # of a chunk of signals into the scratch, K4 (csrc/enf_xtd.hip) forms every X^T delta and bias sum from it
         desc = model._desc(B, N, Z, masks=ctx.masks) if ctx.masks is not None and ctx.masks[1] == "read" else model._desc(B, N, Z)
         group = ctx.masks[2] if ctx.masks is not None and ctx.masks[1] == "read" else 1
-        cb = B
-        while cb > group and int(lib.enf_backward_weights_scratch_bytes_ex(ctypes.byref(desc), cb, sflags)) > STORE_BUDGET_BYTES:
-            cb = max(group, (cb - 1) // group * group)
+        cb = _chunk_signals(lib.enf_backward_weights_scratch_bytes_ex, desc, B, group, sflags)
         scratch = torch.empty(int(lib.enf_backward_weights_scratch_bytes_ex(ctypes.byref(desc), cb, sflags)), device=dev, dtype=torch.uint8)
         f32 = dict(device=dev, dtype=torch.float32)
         shapes = [(D, D), (D,), (D, D), (D,), (D, D), (D,), (D, 2 * HD), (2 * HD,), (D, D), (D,)]      # ENF_P_AQ1 .. ENF_P_BM
@@ -324,14 +326,14 @@ class _TrainAllFunction(torch.autograd.Function):
     def forward(ctx, x, p, a, sigma, model, key, *tensors):
         lib = _lib.load()
         B, Z, N, dev = p.shape[0], p.shape[1], x.shape[1], p.device
-        ctx.masks = getattr(model, "_masks", None)
+        ctx.masks = model._masks
         desc = model._desc(B, N, Z, masks=ctx.masks)
         xb, xstride = model._x_arg(x)
         p_, a_ = p.detach().contiguous(), a.detach().contiguous()
         s_ = sigma.detach().contiguous() if sigma is not None else None
         st = _stream(dev)
         ts = [t.detach().to(torch.float32).contiguous() for t in tensors]
-        hit = getattr(model, "_train_blob", None)
+        hit = model._train_blob
         if key is not None and hit is not None and hit[0] == key:
             blob, ts = hit[1], hit[2]
         else:
@@ -346,7 +348,7 @@ class _TrainAllFunction(torch.autograd.Function):
         lse = torch.empty((B, N, model._Hp), device=dev, dtype=torch.float32)
         ws = model._workspace(desc, dev)
         _lib.launch(dev, lib.enf_forward_stages, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(blob),
-                    _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(), 15 | 16, st)          # prologue, fold, pair, tail + stash
+                    _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(), _lib.ENF_STAGES_FORWARD | _lib.ENF_STAGE_TAIL_SAVE, st)
         ctx.ws_tag = model._ws_touch(ws)
         ctx.model, ctx.xstride, ctx.dims, ctx.has_sigma = model, xstride, (B, N, Z), sigma is not None
         ctx.x_shape = tuple(x.shape)
@@ -367,11 +369,9 @@ class _TrainAllFunction(torch.autograd.Function):
         read = ctx.masks is not None and ctx.masks[1] == "read"
         desc = model._desc(B, N, Z, masks=ctx.masks) if read else model._desc(B, N, Z)
         group = ctx.masks[2] if read else 1
-        cb = B
         det = model._det_flag()              # deterministic mode: K3's partials come from the scratch, fixed-order sums
         sflags = det | (_lib.ENF_BWD_QUERY_GRAD if det and ctx.needs_input_grad[0] else 0)
-        while cb > group and int(lib.enf_backward_all_scratch_bytes_ex(ctypes.byref(desc), cb, sflags)) > STORE_BUDGET_BYTES:
-            cb = max(group, (cb - 1) // group * group)
+        cb = _chunk_signals(lib.enf_backward_all_scratch_bytes_ex, desc, B, group, sflags)
         nscr = int(lib.enf_backward_all_scratch_bytes_ex(ctypes.byref(desc), cb, sflags))
         scratch = torch.empty(nscr, device=dev, dtype=torch.uint8)
         f32 = dict(device=dev, dtype=torch.float32)
@@ -384,7 +384,8 @@ class _TrainAllFunction(torch.autograd.Function):
         dsig = torch.empty((B, Z, 1), **f32)
         dxq = (torch.empty if det else torch.zeros)((B, N, ctx.x_shape[-1]), **f32) if ctx.needs_input_grad[0] else None     # (det: overwritten)
         ws = model._workspace(desc, dev)
-        flags = (3 if model._ws_tag(ws) == ctx.ws_tag else 0) | det       # latent table + tail stash still the forward's
+        # (latent table + tail stash still the forward's)
+        flags = (_lib.ENF_BWD_REUSE_PROLOGUE | _lib.ENF_BWD_REUSE_TAIL if model._ws_tag(ws) == ctx.ws_tag else 0) | det
         _lib.launch(dev, lib.enf_backward_all, ctypes.byref(desc), _ptr(xb), ctx.xstride, _ptr(p_), _ptr(a_), _ptr(sigma), arrT,
                     _ptr(blob), _ptr(ybar), _ptr(lse), _ptr(dout.contiguous().float()), _ptr(dp), _ptr(da), _ptr(dsig), arrG, _ptr(dxq),
                     _ptr(ws), ws.numel(), _ptr(scratch), nscr, flags, st)
@@ -402,13 +403,11 @@ class _SelfAttnView:
         self._x_arg = model._x_arg
         self.pair_variants, self.default_pair_variants = model.pair_variants, model.default_pair_variants
         self._det_flag = model._det_flag
+        self._masks = self._pair_key = self._pair_blob = None      # what _PairFunction reads: no relu masks, no cached panels
 
     def _desc(self, B, N, Z, masks=None):
-        m, inv = self._m, self._m.self_attn_invariant
-        return _lib.make_desc(B, N, Z, m._Hp, m._Dp, m.latent_dim, m.num_out, inv.num_x_pos_dims + inv.num_x_ori_dims,
-                              inv.kernel_id, m.use_gaussian_window, _lib.PREC[m.precision],
-                              d_true=m.num_hidden if m._Dp != m.num_hidden else 0, h_true=m.num_heads if m._Hp != m.num_heads else 0,
-                              variants=tuple(_lib.VARIANT[v] for v in (m.pair_variants or m.default_pair_variants)), masks=masks)
+        inv = self._m.self_attn_invariant
+        return self._m._desc(B, N, Z, masks=masks, inv=inv, dx=inv.num_x_pos_dims + inv.num_x_ori_dims)
 
 
 def apply_layers(model, tensors, x, p, a, sigma):

@@ -1,5 +1,4 @@
 """MAML inner loop and decode on the HIP path (trainers/pde_trainer.py:122-235, 389-405)."""
-import ctypes
 import functools
 import inspect
 
@@ -114,7 +113,7 @@ def _fit_inputs(latents0, coords, img, masks, weights=None, channel=False):
         src = v.detach()
         keep.append(src)
         comps[i] = _lib.EnfFitComponent(src.data_ptr(), lat[k].data_ptr(), v.shape[2], 0)
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _lib.stream(dev)
     if channel:
         ws = torch.empty((S1, B, Ns, O), device=dev, dtype=torch.float32)
         _lib.launch(dev, _lib.load().enf_fit_inputs_cw, len(latents0), comps, B, Z, N, Ns, S1, coords.shape[1], O, coords.data_ptr(),
@@ -131,6 +130,43 @@ def _fit_inputs(latents0, coords, img, masks, weights=None, channel=False):
                 masks.data_ptr(), xs.data_ptr(), ys.data_ptr(), losses.data_ptr(), weights.data_ptr() if weights is not None else None,
                 ws.data_ptr() if ws is not None else None, st)
     return (lat, xs, ys, losses) if weights is None else (lat, xs, ys, losses, ws)
+
+
+def _full_grid_weights(img, weights, channel_weights):
+    """The loss weights of a fit on the full grid, float32 and contiguous next to ``img``: ``channel_weights`` (B, N, O), or ``weights``
+    (B, N), or None."""
+    if channel_weights is not None:
+        if weights is not None:
+            raise ValueError("pass weights= (B, N) or channel_weights= (B, N, O), not both")
+        if tuple(channel_weights.shape) != tuple(img.shape):
+            raise ValueError(f"channel_weights have shape {tuple(channel_weights.shape)}, expected {tuple(img.shape)}")
+        return channel_weights.to(device=img.device, dtype=torch.float32).contiguous()
+    if weights is None:
+        return None
+    if tuple(weights.shape) != tuple(img.shape[:2]):
+        raise ValueError(f"weights have shape {tuple(weights.shape)}, expected {tuple(img.shape[:2])}")
+    return weights.to(device=img.device, dtype=torch.float32).contiguous()
+
+
+def _gather_inputs(latents0, coords, img, masks, weights, channel):
+    """What inner_loop prepares before its first step, for every weight form and both mask layouts: the signals' copies of the latent
+    initialisation (pde_trainer.py:157-159), the coordinates and targets of all S+1 steps gathered once (:193-197), one zeroed loss
+    accumulator per step and the gathered weights -- (lat, xs_all, ys_all, losses, ws_all), ws_all None without weights on shared
+    masks.  ONE launch (_fit_inputs) instead of eight framework kernels, or the same in torch ops."""
+    fused = _fit_inputs(latents0, coords, img, masks, weights, channel=channel) if FUSED_FIT_INPUTS else None
+    if fused is not None:
+        return fused if len(fused) == 5 else (*fused, None)
+    B = img.shape[0]
+    lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}       # (a fresh tensor)
+    losses = torch.zeros(masks.shape[-1], device=img.device, dtype=torch.float32)        # zeroed in one fill
+    if masks.dim() == 3:                                                 # (S+1, B, N_s, .): enf_fit_inputs_b / _cw in torch ops
+        xs_all, ys_all, ws_all = gather_signal_points(coords, img, masks, weights)
+        return lat, xs_all, ys_all, losses, ws_all
+    masks_t = masks.t().contiguous()                                     # (a gather inherits the strides of a transposed index)
+    xs_all = coords[masks_t]                                             # (S+1, N_s, dx)
+    ys_all = img[:, masks_t].transpose(0, 1).float().contiguous()        # (S+1, B, N_s, O)
+    ws_all = gather_point_weights(weights, masks) if weights is not None else None      # (S+1, B, N_s[, O])
+    return lat, xs_all, ys_all, losses, ws_all
 
 
 def _pose(lat, num_ori_dims):
@@ -157,8 +193,7 @@ def meta_sgd_update(lat, grads, lrs, scale):
         segs[i] = _lib.EnfSgdSegment(x.data_ptr(), g.data_ptr(), lr.data_ptr(), out.data_ptr(), x.numel(), w,
                                      g.stride(-2) if g.dim() > 1 else w, lr.numel(), 0)
         new[k] = out
-    st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    _lib.launch(out.device, lib.enf_meta_sgd_update, len(grads), segs, float(scale), st)
+    _lib.launch(out.device, lib.enf_meta_sgd_update, len(grads), segs, float(scale), _lib.stream(out.device))
     return new
 
 
@@ -213,12 +248,12 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
                prepare_channel_weights), for fields whose variables are observed separately; not together with ``weights``.  They are
                gathered with the targets in the same launch (enf_fit_inputs_cw, either mask layout) and every step runs
                enf_fit_step_cw; a value of weight 0 does not exist, its target may be NaN.  ``normalize_weights`` then rescales to
-               mean 1 over every signal's N_s * O sampled values.  None takes the code path above unchanged.
+               mean 1 over every signal's N_s * O sampled values.
     per_signal_loss : also return loss_b (S + 1, B), every signal's own loss at each step and on the last mask (include/enf_hip.h,
                "Per-signal and per-point errors": loss_b[s].mean() is step s's loss up to rounding).  The steps then run enf_fit_step_e
                -- the kernels of the plain steps with one store added, so the fitted latents are the same -- and the final loss comes
                from enf_eval_loss, without a decode, instead of enf_forward + enf_mse_value_grad*: the same sum in another order.
-               Every weight form and both mask layouts; False takes the code path above unchanged.
+               Every weight form and both mask layouts.
     Returns (loss on the last mask, fitted latents dict with leading dim B), with ``per_signal_loss`` followed by loss_b.
     """
     B = img.shape[0]
@@ -228,66 +263,31 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
     S = masks.shape[-1] - 1
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
     channel = channel_weights is not None
-    if channel:
-        if weights is not None:
-            raise ValueError("pass weights= (B, N) or channel_weights= (B, N, O), not both")
-        if tuple(channel_weights.shape) != tuple(img.shape):
-            raise ValueError(f"channel_weights have shape {tuple(channel_weights.shape)}, expected {tuple(img.shape)}")
-        cw = channel_weights.to(device=img.device, dtype=torch.float32).contiguous()
-        fused = _fit_inputs(latents0, coords, img, masks, cw, channel=True) if FUSED_FIT_INPUTS else None
-        if fused is not None:
-            lat, xs_all, ys_all, losses, ws_all = fused
-        else:
-            lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
-            losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)
-            if per_signal:
-                xs_all, ys_all, ws_all = gather_signal_points(coords, img, masks, cw)
-            else:
-                masks_t = masks.t().contiguous()
-                xs_all, ys_all = coords[masks_t], img[:, masks_t].transpose(0, 1).float().contiguous()
-                ws_all = gather_point_weights(cw, masks)                             # (S+1, B, N_s, O)
-        if normalize_weights:
-            ws_all = normalize_sampled_weights(ws_all, channel=True)
-        return _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_signal, S, B, n_ori,
-                            optimize_gaussian_window, noise_pos, generator, per_signal_loss)
-    if weights is not None:
-        if tuple(weights.shape) != tuple(img.shape[:2]):
-            raise ValueError(f"weights have shape {tuple(weights.shape)}, expected {tuple(img.shape[:2])}")
-        weights = weights.to(device=img.device, dtype=torch.float32).contiguous()
-    fused = _fit_inputs(latents0, coords, img, masks, weights) if FUSED_FIT_INPUTS else None
-    if fused is not None:
-        # the signals' copies of the latent initialisation (pde_trainer.py:157-159), the coordinates and targets of all S+1 steps
-        # gathered once (:193-197) and the zeroed loss accumulators: ONE launch (enf_fit_inputs) instead of eight framework kernels
-        lat, xs_all, ys_all, losses = fused[:4]
-        ws_all = fused[4] if weights is not None or per_signal else None
-    elif per_signal:
-        lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
-        xs_all, ys_all, ws_all = gather_signal_points(coords, img, masks, weights)       # (S+1, B, N_s, .): enf_fit_inputs_b in torch ops
-        losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)
-    else:
-        lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}       # pde_trainer.py:157-159 (a fresh tensor)
-        masks_t = masks.t().contiguous()                                     # (a gather inherits the strides of a transposed index)
-        xs_all = coords[masks_t]                                             # (S+1, N_s, dx)
-        ys_all = img[:, masks_t].transpose(0, 1).float().contiguous()        # (S+1, B, N_s, O)
-        losses = torch.zeros(S + 1, device=img.device, dtype=torch.float32)  # one accumulator per step, zeroed in one fill
-        ws_all = gather_point_weights(weights, masks) if weights is not None else None      # (S+1, B, N_s)
+    full = _full_grid_weights(img, weights, channel_weights)
+    lat, xs_all, ys_all, losses, ws_all = _gather_inputs(latents0, coords, img, masks, full, channel)
     if normalize_weights:
         if ws_all is None:
             raise ValueError("normalize_weights needs sampled weights: pass weights= or per-signal masks")
-        ws_all = normalize_sampled_weights(ws_all)
+        ws_all = normalize_sampled_weights(ws_all, channel=channel)
     if noise_pos:                                                                             # pde_trainer.py:162-167
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
-    if per_signal_loss:
-        return _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, "weight", losses, per_signal, S, B, n_ori,
-                              optimize_gaussian_window, noise_pos)
     n_pos = lat["p_pos"].shape[-1]
+    weight_kw = "channel_weight" if channel else "weight"      # the keyword that takes ws_all[s]: enf_fit_step_cw, or enf_fit_step_w
+
+    def sampled(s):     # step s's points -- every signal's own, or a stride-0 batch -- and weights
+        return xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1), None if ws_all is None else ws_all[s]
+
+    rows = []                                                           # loss_b, with per_signal_loss
     for s in range(S):                                                  # pde_trainer.py:191
-        xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)             # every signal's own points, or a stride-0 batch
-        _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
-                                                         lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
-                                                         weight=None if ws_all is None else ws_all[s],
-                                                         **_shared_kw(nef, s, per_signal, noise_pos))
+        xs, ws = sampled(s)
+        res = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[s],
+                                             loss_out=losses[s:s + 1], **{weight_kw: ws},
+                                             **({"return_errors": True} if per_signal_loss else {}),
+                                             **_shared_kw(nef, s, per_signal, noise_pos))
+        _, dp, da, dsig = res[:4]
+        if per_signal_loss:
+            rows.append(res[5])
         # the gradient of the batch-mean loss times B (pde_trainer.py:206), scaled by the learned rates (:215-219);
         # sigma only moves when asked to (:209-212)
         grads = {"p_pos": dp[..., :n_pos], "a": da}
@@ -296,78 +296,24 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
         if optimize_gaussian_window and dsig is not None:
             grads["gaussian_window"] = dsig
         lat = meta_sgd_update(lat, grads, lrs, B)
-    with torch.no_grad():                                               # pde_trainer.py:225-235
-        xs = xs_all[S] if per_signal else xs_all[S][None].expand(B, -1, -1)
-        out = nef.apply(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window")).float().contiguous()
-        st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-        if out.shape != ys_all[S].shape:
-            raise AssertionError(f"targets have shape {tuple(ys_all[S].shape)}, expected {tuple(out.shape)}")
-        if ws_all is None:
-            _lib.launch(out.device, _lib.load().enf_mse_value_grad, out.data_ptr(), ys_all[S].data_ptr(), out.numel(), 1.0, None,
-                        losses[S:].data_ptr(), st)
-        else:
-            _lib.launch(out.device, _lib.load().enf_mse_value_grad_w, out.data_ptr(), ys_all[S].data_ptr(), ws_all[S].data_ptr(),
-                        out.numel(), out.shape[-1], 1.0, None, losses[S:].data_ptr(), None, 0, 0, st)
-    return losses[S], lat
-
-
-def _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, weight_kw, losses, per_signal, S, B, n_ori, optimize_gaussian_window,
-                   noise_pos=0.0):
-    """inner_loop(per_signal_loss=True) from the gathered inputs on, for every weight form (``weight_kw``: the keyword that takes
-    ws_all[s], "weight" or "channel_weight"; ws_all may be None): S steps through enf_fit_step_e, the final loss through enf_eval_loss.
-    Returns (loss, lat, loss_b (S + 1, B))."""
-    n_pos = lat["p_pos"].shape[-1]
-    rows = []
-    for s in range(S):
-        xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)
-        _, dp, da, dsig, _, lb = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"),
-                                                                ys_all[s], loss_out=losses[s:s + 1], return_errors=True,
-                                                                **{weight_kw: None if ws_all is None else ws_all[s]},
-                                                                **_shared_kw(nef, s, per_signal, noise_pos))
-        rows.append(lb)
-        grads = {"p_pos": dp[..., :n_pos], "a": da}
-        if n_ori > 0:
-            grads["p_ori"] = dp[..., n_pos:]
-        if optimize_gaussian_window and dsig is not None:
-            grads["gaussian_window"] = dsig
-        lat = meta_sgd_update(lat, grads, lrs, B)
-    xs = xs_all[S] if per_signal else xs_all[S][None].expand(B, -1, -1)
-    lb, _ = nef.eval_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], loss_out=losses[S:],
-                          **{weight_kw: None if ws_all is None else ws_all[S]})
-    rows.append(lb)
-    return losses[S], lat, torch.stack(rows)
-
-
-def _inner_steps(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, losses, per_signal, S, B, n_ori, optimize_gaussian_window,
-                 noise_pos, generator, per_signal_loss=False):
-    """The S meta-SGD steps and the final loss of inner_loop for per-channel weights ws_all (S+1, B, N_s, O): the same sequence with
-    enf_fit_step_cw / enf_mse_value_grad_cw."""
-    if noise_pos:
-        lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
-                                                  device="cpu").to(lat["p_pos"].device) * noise_pos
+    xs, ws = sampled(S)
     if per_signal_loss:
-        return _inner_steps_e(nef, nef_params, lat, lrs, xs_all, ys_all, ws_all, "channel_weight", losses, per_signal, S, B, n_ori,
-                              optimize_gaussian_window, noise_pos)
-    n_pos = lat["p_pos"].shape[-1]
-    for s in range(S):
-        xs = xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1)
-        _, dp, da, dsig = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"],
-                                                         lat.get("gaussian_window"), ys_all[s], loss_out=losses[s:s + 1],
-                                                         channel_weight=ws_all[s], **_shared_kw(nef, s, per_signal, noise_pos))
-        grads = {"p_pos": dp[..., :n_pos], "a": da}
-        if n_ori > 0:
-            grads["p_ori"] = dp[..., n_pos:]
-        if optimize_gaussian_window and dsig is not None:
-            grads["gaussian_window"] = dsig
-        lat = meta_sgd_update(lat, grads, lrs, B)
-    with torch.no_grad():
-        xs = xs_all[S] if per_signal else xs_all[S][None].expand(B, -1, -1)
+        lb, _ = nef.eval_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], loss_out=losses[S:],
+                              **{weight_kw: ws})
+        rows.append(lb)
+        return losses[S], lat, torch.stack(rows)
+    with torch.no_grad():                                               # pde_trainer.py:225-235
         out = nef.apply(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window")).float().contiguous()
-        st = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
         if out.shape != ys_all[S].shape:
             raise AssertionError(f"targets have shape {tuple(ys_all[S].shape)}, expected {tuple(out.shape)}")
-        _lib.launch(out.device, _lib.load().enf_mse_value_grad_cw, out.data_ptr(), ys_all[S].data_ptr(), ws_all[S].data_ptr(),
-                    out.numel(), 1.0, None, losses[S:].data_ptr(), None, 0, 0, st)
+        lib, n, loss = _lib.load(), out.numel(), losses[S:].data_ptr()
+        if ws is None:
+            fn, args = lib.enf_mse_value_grad, (n, 1.0, None, loss)
+        elif channel:
+            fn, args = lib.enf_mse_value_grad_cw, (ws.data_ptr(), n, 1.0, None, loss, None, 0, 0)
+        else:
+            fn, args = lib.enf_mse_value_grad_w, (ws.data_ptr(), n, out.shape[-1], 1.0, None, loss, None, 0, 0)
+        _lib.launch(out.device, fn, out.data_ptr(), ys_all[S].data_ptr(), *args, _lib.stream(out.device))
     return losses[S], lat
 
 

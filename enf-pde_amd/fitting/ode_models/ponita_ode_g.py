@@ -11,7 +11,6 @@ Work split (per ODE evaluation, B signals x Z latents):
 Everything is differentiable (d/d p, d/d a, d/d weights) so that `ode_loss` (pde_trainer.py:411-500) can be trained
 through the solver.  Parameters: the reference's flax tree ``{'params': {'ponita': {...}}}`` with device tensors.
 """
-import ctypes
 import math
 import os
 
@@ -21,12 +20,7 @@ import torch.nn.functional as Fnn
 from ... import _lib
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_ptr, _stream = _lib.ptr, _lib.stream
 
 
 SPLIT_K = 4096      # rows per slice of the pair axis in a weight-gradient GEMM X^T G: (K x P)(P x N) has only K N / tile^2

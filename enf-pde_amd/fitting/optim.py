@@ -14,7 +14,6 @@ trees are flat lists of tensors.  Pure tensor code, device-agnostic (tested on C
 ``table_adam_update`` is the one native piece: optax adam over an auto-decoder's whole latent table from the gathered gradient
 rows of a batch, one HIP launch (enf_table_adam_update, include/enf_hip.h).
 """
-import ctypes
 import struct
 
 import torch
@@ -135,7 +134,7 @@ def table_adam_update(opt, state, tables, grads, idx=None, inplace=False):
     keep, outs = [], ([], [], [])
     if idx is not None:
         idx = idx.to(device=dev, dtype=torch.int64).contiguous()
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    st = _lib.stream(dev)
     for lo in range(0, len(tables), _lib.ENF_ADAM_MAX_SEGMENTS):
         segs = (_lib.EnfAdamSegment * _lib.ENF_ADAM_MAX_SEGMENTS)()
         n = 0

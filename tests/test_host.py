@@ -68,6 +68,19 @@ def test_desc_struct_matches_header():
             assert _lib.INVARIANT_IDS[name.lower()] == int(i)
 
 
+def test_every_stage_and_flag_bit_of_the_header_is_named_in_the_binding():
+    """Package code builds its stage and flag words from the names of _lib, so each ENF_STAGE_* / ENF_BWD_* / ENF_FIT_* / ENF_MSE_*
+    macro must be there under the header's name with the header's value."""
+    from enf_pde_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "enf_hip.h")).read()
+    macros = re.findall(r"#define (ENF_(?:STAGE|BWD|FIT|MSE)_\w+) (\d+)u", hdr)
+    assert len(macros) == 17 and len({n for n, _ in macros}) == 17        # (a header that changes its spelling must not pass as "none")
+    for name, val in macros:
+        assert getattr(_lib, name, None) == int(val), name
+    stages = {n: int(v) for n, v in macros if n.startswith("ENF_STAGE_")}
+    assert _lib.ENF_STAGES_FORWARD == sum(stages[f"ENF_STAGE_{k}"] for k in ("PROLOGUE", "PAIR", "TAIL", "FOLD"))
+
+
 def test_check_desc_and_error_mapping(lib):
     from enf_pde_amd import _lib
     ok = _lib.make_desc(2, 100, 64, 2, 128, 16, 1, 2, 0, 1, 1)
