@@ -9,7 +9,7 @@ from the inner loop, the auto-decoder trainer from its latent table; from there 
 import torch
 
 from ..inner_loop import _pose
-from ..weights import normalize_point_weights, prepare_point_weights, weighted_mse, normalize_channel_weights, prepare_channel_weights
+from ..weights import LossWeights, loss_tensor, weighted_mse
 from .trainer_utils.solvers import solve_latent_ode
 
 
@@ -52,36 +52,6 @@ def sample_frames(coords, traj, point_masks=None, weights=None):
     if weights.dim() == 4:
         return xs, ys, torch.gather(weights, 2, point_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n_s, O)
     return xs, ys, torch.gather(weights, 2, point_masks[None].expand(B, -1, -1)).reshape(B * T, n_s)
-
-
-def frame_weights(weights, B, T, N, normalize=True, device=None):
-    """``weights`` (N,), (B, N) or (B, T, N) -> float32 (B, T, N), every signal-frame's weights of mean 1 over the full grid
-    unless ``normalize`` is False (fitting/weights.py); None stays None."""
-    if weights is None:
-        return None
-    w = torch.as_tensor(weights, dtype=torch.float32)
-    if w.dim() == 3:
-        if tuple(w.shape) != (B, T, N):
-            raise ValueError(f"weights have shape {tuple(w.shape)}, expected {(B, T, N)}, {(B, N)} or {(N,)}")
-        w = normalize_point_weights(w) if normalize else w
-        return w.to(device) if device is not None else w
-    return prepare_point_weights(w, B, N, normalize, device)[:, None].expand(B, T, N)
-
-
-def frame_channel_weights(weights, B, T, N, O, normalize=True, device=None):
-    """Per-channel ``weights`` (N, O), (B, N, O) or (B, T, N, O) -> float32 (B, T, N, O), every signal-frame's weights of mean 1 over
-    its N * O values unless ``normalize`` is False (fitting/weights.py); None stays None."""
-    if weights is None:
-        return None
-    w = torch.as_tensor(weights, dtype=torch.float32)
-    if w.dim() == 4:
-        if tuple(w.shape) != (B, T, N, O):
-            raise ValueError(f"channel weights have shape {tuple(w.shape)}, expected {(B, T, N, O)}, {(B, N, O)} or {(N, O)}")
-        if bool((w < 0).any()) or not bool(torch.isfinite(w).all()):
-            raise ValueError("channel weights must be finite and >= 0")
-        w = normalize_channel_weights(w) if normalize else w
-        return w.to(device) if device is not None else w
-    return prepare_channel_weights(w, B, N, O, normalize, device)[:, None].expand(B, T, N, O)
 
 
 class LatentODEMixin:
@@ -146,26 +116,28 @@ class LatentODEMixin:
         ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1
         per signal-frame before the points are sampled unless ``normalize`` is False; they are gathered with the point masks.
         ``channel_weights``: None, or per-channel (N, O) / (B, N, O) / (B, T, N, O) weights, treated alike; not with ``weights``."""
-        if channel_weights is not None and weights is not None:
-            raise ValueError("pass weights= or channel_weights=, not both")
         B, T = trajectory.shape[:2]
+        N, n_s = self.coords.shape[0], self.config.training.max_num_sampled_points
+        fw = LossWeights.build(weights, channel_weights, B, N, trajectory.shape[-1], T=T, normalize=normalize, device=trajectory.device)
         sol = self.rollout(ode_params, lat, T, graph=graph)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
-        N, n_s = self.coords.shape[0], self.config.training.max_num_sampled_points
         if n_s < N:                                                               # pde_trainer.py:446-471
             if point_masks is None:
                 point_masks = draw_point_masks(N, n_s, T, generator, self.coords.device)
         else:
             point_masks = None
-        if channel_weights is not None:
-            fw = frame_channel_weights(channel_weights, B, T, N, traj.shape[-1], normalize, traj.device)
-            xs, ys, ws = sample_frames(self.coords, traj, point_masks, fw)
-            return weighted_mse(self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl), ys, ws)
-        if weights is None:
-            xs, ys = sample_frames(self.coords, traj, point_masks)
-            recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
-            return ((recon - ys) ** 2).mean()
-        xs, ys, ws = sample_frames(self.coords, traj, point_masks, frame_weights(weights, B, T, N, normalize, traj.device))
+        xs, ys, *ws = sample_frames(self.coords, traj, point_masks, loss_tensor(fw))
         recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
-        return weighted_mse(recon, ys, ws)
+        return weighted_mse(recon, ys, ws[0]) if ws else ((recon - ys) ** 2).mean()
+
+    def _horizon_errors(self, recon, trajectory, num_in, fw=None):
+        """(mean squared error of ``recon`` over the first ``num_in`` frames of ``trajectory`` (B, T, *grid, O), the same beyond them, zero
+        where there are none); with ``fw``, a LossWeights over the (B, T, N) signal-frame points, the two weighted_mse."""
+        T = trajectory.shape[1]
+        if fw is None:
+            err = (recon - trajectory) ** 2
+            return err[:, :num_in].mean(), (err[:, num_in:].mean() if T > num_in else err.new_zeros(()))
+        rec, tgt = (v.reshape(*fw.w.shape[:3], -1) for v in (recon, trajectory))
+        return weighted_mse(rec[:, :num_in], tgt[:, :num_in], fw.frame_range(0, num_in).w), \
+            (weighted_mse(rec[:, num_in:], tgt[:, num_in:], fw.frame_range(num_in, T).w) if T > num_in else recon.new_zeros(()))

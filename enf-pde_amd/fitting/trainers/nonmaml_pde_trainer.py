@@ -30,9 +30,8 @@ import torch
 from ..optim import Adam, AdamW, clip_by_global_norm, global_norm, scatter_rows, table_adam_update
 from ..parallel import allreduce_mean_
 from ..inner_loop import decode, make_signal_masks, gather_signal_points
-from ..weights import prepare_point_weights, weighted_mse, observed_sampling_weights, prepare_channel_weights, \
-    observed_channel_sampling_weights, point_support
-from .latent_ode import LatentODEMixin, frame_weights, frame_channel_weights, _leaves, _unflatten
+from ..weights import LossWeights, cut_frames, nef_kw, weighted_mse
+from .latent_ode import LatentODEMixin, _leaves, _unflatten
 from .pde_trainer import _tree_from_tensors
 
 TRAIN_FRAMES, VAL_FRAMES = 10, 20            # fixed in the reference (:206,241,252), not read from the dataset config
@@ -106,41 +105,25 @@ class NonMetaPDETrainer(LatentODEMixin):
         return state, epoch
 
     def _fit_points(self, state, initial_state, mask, weights, normalize, channel_weights=None):
-        """What a nef step fits on (:311-335): (targets (B, n, O), coordinates (n, dx), loss weights (B, n) or None, per-signal
-        coordinates (B, n, dx) or None).  The one place where a nef step draws from ``state.rng``: loss_and_grads and
-        fit_latents_step both call it, so the two consume the generator alike.  With ``channel_weights`` (N, O) / (B, N, O) the
-        third value is per-channel, (B, n, O), and a point counts as observed where any of its channels is."""
+        """What a nef step fits on (:311-335): (targets (B, n, O), coordinates (n, dx), the LossWeights of these points or None,
+        per-signal coordinates (B, n, dx) or None).  The one place where a nef step draws from ``state.rng``: loss_and_grads and
+        fit_latents_step both call it, so the two consume the generator alike.  With ``channel_weights`` (N, O) / (B, N, O) a
+        point counts as observed where any of its channels is."""
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
-        if channel_weights is not None:
-            if weights is not None:
-                raise ValueError("pass weights= or channel_weights=, not both")
-            cw = prepare_channel_weights(channel_weights, *img.shape, normalize, img.device)
-            if mask is not None:
-                img, coords, cw = img[:, mask], coords[mask], cw[:, mask]
-            npts, xs = self.config.training.max_num_sampled_points, None
-            if self.sample_observed:
-                m = make_signal_masks(point_support(cw), min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
-                xs, img, cw = (t[0] for t in gather_signal_points(coords, img, m, observed_channel_sampling_weights(cw, m.shape[1])))
-            elif npts < coords.shape[0]:
-                sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
-                img, coords, cw = img[:, sub], coords[sub], cw[:, sub]
-            return img, coords, cw.contiguous(), xs
-        pw = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
+        lw = LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device)
         if mask is not None:                                                              # :321-323
-            img, coords = img[:, mask], coords[mask]
-            pw = None if pw is None else pw[:, mask]
-        npts = self.config.training.max_num_sampled_points
-        xs = None
-        if self.sample_observed and pw is not None:      # every signal's own min(npts, N) observed points; -1 padding has weight 0
-            m = make_signal_masks(pw, min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
+            img, coords, lw = img[:, mask], coords[mask], lw and lw.points(mask)
+        npts, xs = self.config.training.max_num_sampled_points, None
+        if self.sample_observed and lw is not None:      # every signal's own min(npts, N) observed points; -1 padding has weight 0
+            m = make_signal_masks(lw.support(), min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
             # (the factor n_b / N of a draw from the observed points: the loss keeps the scale of the shared subset's)
-            xs, img, pw = (t[0] for t in gather_signal_points(coords, img, m, observed_sampling_weights(pw, m.shape[1])))
+            xs, img, ws = (t[0] for t in gather_signal_points(coords, img, m, lw.drawn_on(m).w))
+            lw = LossWeights(ws, lw.channel)
         elif npts < coords.shape[0]:                                                      # :326-335
             sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
-            img, coords = img[:, sub], coords[sub]
-            pw = None if pw is None else pw[:, sub]
-        return img, coords, pw, xs
+            img, coords, lw = img[:, sub], coords[sub], lw and lw.points(sub)
+        return img, coords, lw, xs
 
     def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None):
         """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
@@ -148,7 +131,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         before ``mask`` and the point sampling unless ``normalize`` is False.
         ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (mean 1 over each signal's N * O values unless
         ``normalize`` is False), for fields whose variables are observed separately; not together with ``weights``."""
-        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
+        img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
@@ -157,7 +140,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         if xs is None:
             xs = coords[None].expand(img.shape[0], -1, -1)
         out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
-        loss = ((out - img) ** 2).mean() if pw is None else weighted_mse(out, img, pw)
+        loss = ((out - img) ** 2).mean() if lw is None else weighted_mse(out, img, lw.w)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)
         gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
         ga = [torch.zeros_like(leaves[k]) if gi is None else gi for k, gi in zip(names, g[len(w):])]
@@ -206,7 +189,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         (this rank's signals; loss_b.mean() is the loss before the all-reduce, up to rounding).  Same draw from ``state.rng``, same
         new state."""
         initial_state, traj_idx = batch
-        img, coords, pw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
+        img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         tables = [P[k].detach() for k in names]
@@ -214,10 +197,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         if xs is None:
             xs = coords[None].expand(img.shape[0], -1, -1)
         more = {"return_errors": True} if per_signal_loss else {}
-        if channel_weights is not None:
-            loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, channel_weight=pw, **more)
-        else:
-            loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, weight=pw, **more)
+        loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, **nef_kw(lw), **more)
         loss = loss.reshape(())
         n_pos = P["p_pos"].shape[-1]
         by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dwin}
@@ -248,8 +228,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         the batch; drawn from ``generator`` when None and max_num_sampled_points is smaller than the grid."""
         self._need_ode("ode_loss")
         trajectory = trajectory[:, :TRAIN_FRAMES]                                # :252
-        if weights is not None and torch.as_tensor(weights).dim() == 3:          # (B, T, N): the frames the loss sees
-            weights = torch.as_tensor(weights)[:, :TRAIN_FRAMES]
+        weights = cut_frames(weights, slice(TRAIN_FRAMES))                       # (B, T, N): the frames the loss sees
         z0 = self.autodecoder.apply(params["autodecoder"], traj_idx)             # :255
         return self.rollout_loss(params["nef"], params["ode_params"], z0, trajectory, point_masks, generator, graph=graph,
                                  weights=weights, normalize=normalize)
@@ -300,34 +279,18 @@ class NonMetaPDETrainer(LatentODEMixin):
         ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value; the two errors are then weighted per value
         (a NaN under a zero weight does not count); not together with ``weights``."""
         self._need_ode("val_step")
-        if channel_weights is not None and weights is not None:
-            raise ValueError("pass weights= or channel_weights=, not both")
         trajectory, traj_idx = batch[0], batch[-1]
         trajectory = trajectory[:, :VAL_FRAMES]                                  # :206
         B, T = trajectory.shape[:2]
+        # (N,) / (B, N) / (B, T, N) weights on the full grid, or per channel: the pair is then the two weighted errors
+        fw = LossWeights.build(weights, channel_weights, B, self.coords.shape[0], trajectory.shape[-1], T=T, normalize=normalize,
+                               device=self.coords.device, frames=slice(T))
         z0 = (autodecoder or self.autodecoder).apply(state.params["autodecoder"], traj_idx)     # :209-210
         sol = self.rollout(state.params["ode_params"], tuple(None if v is None else v.detach() for v in z0), T, graph=T > 4)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl,
                        chunk=self.config.training.max_num_sampled_points).reshape(trajectory.shape)    # :228-238
-        if channel_weights is not None:
-            N, O, F = self.coords.shape[0], trajectory.shape[-1], TRAIN_FRAMES
-            cw = torch.as_tensor(channel_weights)
-            fw = frame_channel_weights(cw[:, :T] if cw.dim() == 4 else cw, B, T, N, O, normalize, recon.device)
-            rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
-            return weighted_mse(rec[:, :F], tgt[:, :F], fw[:, :F]), \
-                (weighted_mse(rec[:, F:], tgt[:, F:], fw[:, F:]) if T > F else recon.new_zeros(()))
-        if weights is None:
-            err = (recon - trajectory) ** 2
-            return err[:, :TRAIN_FRAMES].mean(), (err[:, TRAIN_FRAMES:].mean() if T > TRAIN_FRAMES else err.new_zeros(()))
-        # (N,) / (B, N) / (B, T, N) weights on the full grid: the pair is (weighted mse over frames 0..9, weighted mse beyond)
-        N, O = self.coords.shape[0], trajectory.shape[-1]
-        if torch.as_tensor(weights).dim() == 3:
-            weights = torch.as_tensor(weights)[:, :T]
-        fw = frame_weights(weights, B, T, N, normalize, recon.device)
-        rec, tgt, F = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O), TRAIN_FRAMES
-        return weighted_mse(rec[:, :F], tgt[:, :F], fw[:, :F]), \
-            (weighted_mse(rec[:, F:], tgt[:, F:], fw[:, F:]) if T > F else recon.new_zeros(()))
+        return self._horizon_errors(recon, trajectory, TRAIN_FRAMES, fw)
 
     def validate_epoch(self, state, train_loader, val_loader, val_autodecoder, *, drop_rates=(0.0, 0.05, 0.1, 0.5), epochs=None,
                        fit_train=True, channel_weights=None):

@@ -36,6 +36,7 @@ and the inner learning rates then agree with exact second-order autograd to 1e-3
 f32 default) and 3-7e-5 at 1e-3.  bf16 kernels (scripts/meta_grad_err_bf16.py): best at 2e-2 (their default): median 7e-3
 per tensor, 4-8 % on the worst (the bf16 noise floor of the first-order weight gradients themselves).
 """
+import contextlib
 import math
 from dataclasses import dataclass, field
 from types import SimpleNamespace
@@ -44,11 +45,10 @@ import torch
 
 from ... import _lib
 from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
-from .latent_ode import LatentODEMixin, draw_point_masks, frame_weights, frame_channel_weights, _leaves, _unflatten
+from .latent_ode import LatentODEMixin, draw_point_masks, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
-from ..weights import prepare_point_weights, weighted_mse, normalize_point_weights, observed_sampling_weights, \
-    prepare_channel_weights, normalize_channel_weights, observed_channel_sampling_weights, point_support
+from ..weights import LossWeights, cut_frames, loop_kw, nef_kw, loss_tensor, weighted_mse
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
@@ -113,7 +113,6 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     leaves = {k: torch.cat([plus[k], minus[k]], 0).detach().requires_grad_(True) for k in plus}
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
     xs, ys, pw = _sampled(coords, img, masks, s, point_weights, copies=2)     # (per-signal masks: signal b + B at the points of b)
-    import contextlib
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
         out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
         if pw is None:
@@ -145,17 +144,13 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     over each signal's N * O values unless ``normalize`` is False; not together with ``weights``.  Every pass that takes the
     per-point weights -- the inner steps, the terminal loss and both perturbed passes of the finite differences -- takes these.
     """
-    if channel_weights is not None and weights is not None:
-        raise ValueError("pass weights= or channel_weights=, not both")
+    pw = loss_tensor(LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device))
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
     if fd_step is None:      # truncation (~step^2) against the rounding of the first-order gradients (~1 / step): bf16 kernels
         fd_step = 2e-2 if getattr(nef, "precision", "f32") in ("bf16", "bfloat16") else 5e-3      # are 100x noisier
     B = img.shape[0]
     S = masks.shape[-1] - 1
-    pw = prepare_point_weights(weights, B, img.shape[1], normalize, img.device)
-    if channel_weights is not None:
-        pw = prepare_channel_weights(channel_weights, B, img.shape[1], img.shape[2], normalize, img.device)
     weights = nef.param_tensors(nef_params)
     frozen = _tree_from_tensors([t.detach() if t is not None else None for t in weights], nef)           # inference path for the inner steps
     lat = {k: v.detach().repeat_interleave(B, dim=0).clone() for k, v in latents0.items()}
@@ -169,7 +164,6 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     # ---- forward sweep, keeping every phi_s and g_s
     phis, gs, relu_bufs = [], [], []
     freeze = second_order == "fd" and freeze_relu and hasattr(nef, "relu_masks")
-    import contextlib
     for s in range(S):
         # (the forward of this pass also records the relu masks at phi_s for the adjoint sweep's frozen-mask differences)
         relu_bufs.append(nef.relu_mask_buffer(B, masks.shape[-2], lat["a"].shape[1], coords.device) if freeze else None)
@@ -300,20 +294,15 @@ class MetaSGDPDETrainer(LatentODEMixin):
         keys = [k for k in LATENT_KEYS if k in P and not (k == "p_ori" and self.outer_autodecoder.num_ori_dims == 0)]
         return {k: P[k] for k in keys}
 
-    def _draw_masks(self, state, num_coords, observed=None):
-        """The index sets of one fit: make_masks, or with ``sample_observed`` and ``observed`` (B, N) weights make_signal_masks."""
+    def _draw_masks(self, state, num_coords, lw=None):
+        """The index sets of one fit and the weights to fit on them with: make_masks and ``lw`` as it is, or with ``sample_observed``
+        and weights make_signal_masks on their support and the weights rescaled for that draw (LossWeights.drawn_on)."""
         cfg = self.config
         n = cfg.training.max_num_sampled_points
-        if self.sample_observed and observed is not None:
-            return make_signal_masks(observed, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
-        return make_masks(num_coords, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
-
-    @staticmethod
-    def _observed_weights(drew, masks, weights):
-        """The fit's weights: rescaled for masks this trainer drew per signal from the observed points, else as they are."""
-        if drew and masks.dim() == 3 and weights is not None:
-            return observed_sampling_weights(weights, masks.shape[1])
-        return weights
+        if self.sample_observed and lw is not None:
+            masks = make_signal_masks(lw.support(), n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
+            return masks, lw.drawn_on(masks)
+        return make_masks(num_coords, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device), lw
 
     def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None):
         """One outer step on ``batch`` = (B, N, O) initial states (trajectory[:, 0], pde_trainer.py:485-487).
@@ -324,28 +313,20 @@ class MetaSGDPDETrainer(LatentODEMixin):
         the outer gradients are averaged with one flat all-reduce before the (identical) optimiser updates."""
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
-        if channel_weights is not None:
-            if weights is not None:
-                raise ValueError("pass weights= or channel_weights=, not both")
-            channel_weights = prepare_channel_weights(channel_weights, *img.shape, normalize, img.device)
-            normalize = False
-            if masks is None:
-                masks = self._draw_masks(state, self.coords.shape[0], point_support(channel_weights))
-                if masks.dim() == 3:
-                    channel_weights = observed_channel_sampling_weights(channel_weights, masks.shape[1])
-        elif masks is None and self.sample_observed and weights is not None:
-            weights = prepare_point_weights(weights, img.shape[0], img.shape[1], normalize, img.device)
-            masks = self._draw_masks(state, self.coords.shape[0], weights)
-            weights, normalize = self._observed_weights(True, masks, weights), False
-        elif masks is None:
-            masks = self._draw_masks(state, self.coords.shape[0])
+        # (point weights that this step does not draw from go on as they came: meta_gradients prepares them)
+        lw, kw = None, {"weights": weights, "normalize": normalize}
+        if channel_weights is not None or (masks is None and self.sample_observed):
+            lw = LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device)
+        if masks is None:
+            masks, lw = self._draw_masks(state, self.coords.shape[0], lw)
+        if lw is not None:
+            kw = dict(loop_kw(lw), normalize=False)
         lat0 = self._latents0(state)
         lrs = state.params["meta_sgd_lrs"]
         loss, grads = meta_gradients(self.nef, state.params["nef"], lat0, lrs, self.coords, img, masks,
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
-                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng,
-                                     weights=weights, normalize=normalize, channel_weights=channel_weights)
+                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, **kw)
         lat_keys, lr_keys = list(lat0.keys()), list(lrs.keys())
         flat = grads["nef"] + [grads["autodecoder"][k] for k in lat_keys] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])                               # SURVEY.md 8e: one exchange per outer step
@@ -387,33 +368,23 @@ class MetaSGDPDETrainer(LatentODEMixin):
         B, N, O = img.shape
         if not (img.is_cuda and self.coords.is_cuda):
             raise _lib.EnfError("MetaSGDPDETrainer.fit_errors needs CUDA/HIP tensors: there is no CPU path")
-        pw = cw = None
-        if channel_weights is not None:
-            if weights is not None:
-                raise ValueError("pass weights= or channel_weights=, not both")
-            cw = prepare_channel_weights(channel_weights, B, N, O, normalize, img.device)
-        else:
-            pw = prepare_point_weights(weights, B, N, normalize, img.device)
-        fit_pw, fit_cw = pw, cw
+        lw = fit_lw = LossWeights.build(weights, channel_weights, B, N, O, normalize=normalize, device=img.device)
         if masks is None:
-            masks = self._draw_masks(state, N, point_support(cw) if cw is not None else pw)
-            fit_pw = self._observed_weights(True, masks, pw)
-            if cw is not None and masks.dim() == 3:
-                fit_cw = observed_channel_sampling_weights(cw, masks.shape[1])
+            masks, fit_lw = self._draw_masks(state, N, lw)
         with torch.enable_grad():
             # (per_signal_loss: the loop's own final loss comes from enf_eval_loss too -- nothing is decoded anywhere)
             _, lat, _ = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], self.coords, img, masks,
                                    optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
-                                   noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, weights=fit_pw,
-                                   channel_weights=fit_cw, per_signal_loss=True)
+                                   noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, per_signal_loss=True,
+                                   **loop_kw(fit_lw))
         pose = _pose(lat, self.nef.cross_attn_invariant.num_z_ori_dims)
         err = torch.empty((B, N), device=img.device, dtype=torch.float32)
         step = N if chunk is None else max(1, int(chunk))
         for i in range(0, N, step):
             part = slice(i, min(i + step, N))
             _, e = self.nef.eval_loss(state.params["nef"], self.coords[part][None].expand(B, -1, -1), pose, lat["a"],
-                                      lat.get("gaussian_window"), img[:, part], weight=None if pw is None else pw[:, part],
-                                      channel_weight=None if cw is None else cw[:, part], per_signal=False)
+                                      lat.get("gaussian_window"), img[:, part], per_signal=False,
+                                      **nef_kw(lw and lw.points(part)))
             err[:, part] = e
         return self.nef.signal_losses(err), err
 
@@ -453,23 +424,17 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return out
 
     # ------------------------------------------------------------------ latent-ODE phase (pde_trainer.py:290-500)
-    def _fit_initial_latents(self, state, initial_state, masks=None, initial_state_dp=0.0, weights=None, observed=None):
-        """What inner_loop takes for the first frame of every trajectory (pde_trainer.py:424-427): (coords, img, masks), and with
-        ``weights`` (B, N) a fourth value, the weights of the same point subset.  ``observed`` (B, N): with ``sample_observed``
-        the masks are drawn per signal from {observed > 0} (default: ``weights``)."""
-        cfg = self.config
+    def _fit_initial_latents(self, state, initial_state, masks=None, initial_state_dp=0.0, weights=None):
+        """What inner_loop takes for the first frame of every trajectory (pde_trainer.py:424-427): (coords, img, masks, weights), the
+        last a LossWeights on the same point subset -- rescaled for masks drawn here per signal (``sample_observed``) -- or None."""
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
         coords = self.coords
         if initial_state_dp > 0:                                                  # pde_trainer.py:139-145
             keep = torch.randperm(coords.shape[0], generator=state.rng)[:int(coords.shape[0] * initial_state_dp)].to(coords.device)
-            coords, img = coords[keep], img[:, keep]
-            if weights is not None:
-                weights = weights[:, keep].contiguous()
-            if observed is not None:
-                observed = observed[:, keep]
+            coords, img, weights = coords[keep], img[:, keep], weights and weights.points(keep)
         if masks is None:
-            masks = self._draw_masks(state, coords.shape[0], weights if observed is None else observed)
-        return (coords, img, masks) if weights is None else (coords, img, masks, weights)
+            masks, weights = self._draw_masks(state, coords.shape[0], weights)
+        return coords, img, masks, weights
 
     def ode_loss(self, nef_params, ode_params, lat, trajectory, point_masks=None, generator=None, graph=False, weights=None,
                  normalize=True, channel_weights=None):
@@ -480,28 +445,18 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return self.rollout_loss(nef_params, ode_params, lat, trajectory, point_masks, generator, graph=graph, weights=weights,
                                  normalize=normalize, channel_weights=channel_weights)
 
-    @staticmethod
-    def _frame0_channel_weights(channel_weights, B, N, O, normalize, device):
-        """The per-channel weights of the fit on frame 0, (B, N, O) float32, from (N, O), (B, N, O) or (B, T, N, O)."""
-        cw = torch.as_tensor(channel_weights)
-        return prepare_channel_weights(cw[:, 0] if cw.dim() == 4 else cw, B, N, O, normalize, device)
-
-    @staticmethod
-    def _frame0_weights(weights, B, N, normalize, device):
-        """The weights of the fit on frame 0, (B, N) float32 or None, from (N,), (B, N) or (B, T, N) ``weights``."""
-        if weights is not None and torch.as_tensor(weights).dim() == 3:
-            weights = torch.as_tensor(weights)[:, 0]
-        return prepare_point_weights(weights, B, N, normalize, device)
-
     def _fitted(self, state, trajectory, masks, weights=None):
-        drew = masks is None
-        coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=weights)
-        weights = self._observed_weights(drew, masks, weights)
+        coords, img, masks, weights = self._fit_initial_latents(state, trajectory[:, 0], masks, weights=weights)
         cfg = self.config
         _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
                             optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
-                            noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, weights=weights)
+                            noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, **loop_kw(weights))
         return {k: v.detach() for k, v in lat.items()}
+
+    def _frame0(self, trajectory, weights, channel_weights, normalize):
+        """The LossWeights of the fit on frame 0 of ``trajectory`` (B, T, *grid, O), or None."""
+        return LossWeights.build(weights, channel_weights, trajectory.shape[0], self.coords.shape[0], trajectory.shape[-1],
+                                 normalize=normalize, device=self.coords.device, frames=0)
 
     def ode_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True):
         """pde_trainer.py:290-318: one Adam step on the ODE parameters only.  The fitted latents do not depend on them, so
@@ -509,10 +464,8 @@ class MetaSGDPDETrainer(LatentODEMixin):
         ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid: frame 0's weigh the fit, all the roll-out loss."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]                  # pde_trainer.py:421-422
-        if weights is not None and torch.as_tensor(weights).dim() == 3:
-            weights = torch.as_tensor(weights)[:, :cfg.dataset.traj_len_train]
-        lat = self._fitted(state, trajectory, masks,
-                           self._frame0_weights(weights, trajectory.shape[0], self.coords.shape[0], normalize, self.coords.device))
+        weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
+        lat = self._fitted(state, trajectory, masks, self._frame0(trajectory, weights, None, normalize))
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
         loss = self.ode_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
@@ -536,24 +489,10 @@ class MetaSGDPDETrainer(LatentODEMixin):
         loss; not together with ``weights``."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]
-        if channel_weights is not None and weights is not None:
-            raise ValueError("pass weights= or channel_weights=, not both")
-        if channel_weights is not None and torch.as_tensor(channel_weights).dim() == 4:
-            channel_weights = torch.as_tensor(channel_weights)[:, :cfg.dataset.traj_len_train]
-        if weights is not None and torch.as_tensor(weights).dim() == 3:
-            weights = torch.as_tensor(weights)[:, :cfg.dataset.traj_len_train]
-        w0 = self._frame0_weights(weights, trajectory.shape[0], self.coords.shape[0], normalize, self.coords.device)
-        drew = masks is None
-        c0 = None
-        if channel_weights is not None:
-            c0 = self._frame0_channel_weights(channel_weights, trajectory.shape[0], self.coords.shape[0], trajectory.shape[-1], normalize,
-                                              self.coords.device)
-            coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=point_support(c0))
-            if drew and masks.dim() == 3:
-                c0 = observed_channel_sampling_weights(c0, masks.shape[1])
-        else:
-            coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, observed=w0)
-        w0 = self._observed_weights(drew, masks, w0)
+        lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
+        weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
+        channel_weights = cut_frames(channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
+        coords, img, masks, lw0 = self._fit_initial_latents(state, trajectory[:, 0], masks, weights=lw0)
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
         if point_masks is None and cfg.training.max_num_sampled_points < self.coords.shape[0]:
@@ -578,7 +517,7 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal,
-                                     weights=w0, normalize=False, channel_weights=c0)
+                                     normalize=False, **loop_kw(lw0))
         lr_keys = list(lrs.keys())
         flat = grads["nef"] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + side["ode"] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])
@@ -643,91 +582,35 @@ class MetaSGDPDETrainer(LatentODEMixin):
         ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value, used like ``weights`` (not together with
         them): frame 0's weigh the fit, a point is observed where any of its channels is, and the two errors are weighted per
         value -- a field with NaN in one variable validates on its other variables there."""
-        if channel_weights is not None:
-            if weights is not None:
-                raise ValueError("pass weights= or channel_weights=, not both")
-            return self._val_step_channel(state, trajectory, initial_state_dp, masks, channel_weights, normalize, drop_rate)
         cfg = self.config
         T_in = cfg.dataset.traj_len_train
         trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
         B, T = trajectory.shape[:2]
-        N = self.coords.shape[0]
-        if weights is not None and torch.as_tensor(weights).dim() == 3:
-            weights = torch.as_tensor(weights)[:, :T]
-        w0 = self._frame0_weights(weights, B, N, normalize, self.coords.device)
+        N, O = self.coords.shape[0], trajectory.shape[-1]
+        lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
         if drop_rate is not None:
             if not 0.0 <= drop_rate < 1.0:
                 raise ValueError(f"drop_rate must lie in [0, 1), got {drop_rate}")
             if masks is not None or initial_state_dp > 0:
                 raise ValueError("drop_rate draws its own per-signal masks: pass neither masks nor initial_state_dp with it")
             kept = torch.rand((B, N), generator=state.rng) >= drop_rate
-            if w0 is not None:
-                kept &= (w0 > 0).cpu()
-            coords, img = self.coords, trajectory[:, 0].reshape(B, -1, trajectory.shape[-1])
+            if lw0 is not None:
+                kept &= (lw0.support() > 0).cpu()
+            coords, img = self.coords, trajectory[:, 0].reshape(B, -1, O)
             masks = make_signal_masks(kept, max(1, min(cfg.training.max_num_sampled_points, int((1.0 - drop_rate) * N))),
                                       cfg.meta.num_inner_steps, generator=state.rng, device=coords.device)
             # what the signal kept is its observed set: weights of mean 1 over the grid again (as normalize asks), then the
             # factor of a draw from the observed points -- the fit's loss keeps the scale of a fit without drop-out
             kept = kept.to(coords.device)
-            w0 = kept.float() if w0 is None else w0 * kept
-            w0 = observed_sampling_weights(normalize_point_weights(w0) if normalize else w0, masks.shape[1])
-        elif w0 is None:
-            coords, img, masks = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp)
+            lw0 = LossWeights(kept.float()) if lw0 is None else lw0.keep(kept)
+            lw0 = (lw0.renormalized() if normalize else lw0).observed_draw(masks.shape[1])
         else:
-            drew = masks is None
-            coords, img, masks, w0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, w0)
-            w0 = self._observed_weights(drew, masks, w0)
+            coords, img, masks, lw0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, lw0)
         with torch.enable_grad():
             _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
-                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), weights=w0)
+                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), **loop_kw(lw0))
         sol = self.rollout(state.params["ode_params"], {k: v.detach() for k, v in lat.items()}, T, graph=T > 4)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl).reshape(trajectory.shape)
-        if weights is None:
-            err = (recon - trajectory) ** 2
-            return err[:, :T_in].mean(), (err[:, T_in:].mean() if T > T_in else err.new_zeros(()))
-        O = trajectory.shape[-1]
-        fw = frame_weights(weights, B, T, N, normalize, recon.device)
-        rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
-        return weighted_mse(rec[:, :T_in], tgt[:, :T_in], fw[:, :T_in]), \
-            (weighted_mse(rec[:, T_in:], tgt[:, T_in:], fw[:, T_in:]) if T > T_in else recon.new_zeros(()))
-
-    @torch.no_grad()
-    def _val_step_channel(self, state, trajectory, initial_state_dp, masks, channel_weights, normalize, drop_rate):
-        """val_step with per-channel weights: the same sequence, the fit through inner_loop(channel_weights=)."""
-        cfg = self.config
-        T_in = cfg.dataset.traj_len_train
-        trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
-        B, T = trajectory.shape[:2]
-        N, O = self.coords.shape[0], trajectory.shape[-1]
-        cw = torch.as_tensor(channel_weights)
-        if cw.dim() == 4:
-            cw = cw[:, :T]
-        c0 = self._frame0_channel_weights(cw, B, N, O, normalize, self.coords.device)
-        if drop_rate is not None:
-            if not 0.0 <= drop_rate < 1.0:
-                raise ValueError(f"drop_rate must lie in [0, 1), got {drop_rate}")
-            if masks is not None or initial_state_dp > 0:
-                raise ValueError("drop_rate draws its own per-signal masks: pass neither masks nor initial_state_dp with it")
-            kept = (torch.rand((B, N), generator=state.rng) >= drop_rate) & (point_support(c0) > 0).cpu()
-            coords, img = self.coords, trajectory[:, 0].reshape(B, -1, O)
-            masks = make_signal_masks(kept, max(1, min(cfg.training.max_num_sampled_points, int((1.0 - drop_rate) * N))),
-                                      cfg.meta.num_inner_steps, generator=state.rng, device=coords.device)
-            c0 = c0 * kept.to(coords.device)[..., None]
-            c0 = observed_channel_sampling_weights(normalize_channel_weights(c0) if normalize else c0, masks.shape[1])
-        else:
-            drew = masks is None
-            coords, img, masks, c0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, c0,
-                                                               observed=point_support(c0))
-            if drew and masks.dim() == 3:
-                c0 = observed_channel_sampling_weights(c0, masks.shape[1])
-        with torch.enable_grad():
-            _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
-                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), channel_weights=c0)
-        sol = self.rollout(state.params["ode_params"], {k: v.detach() for k, v in lat.items()}, T, graph=T > 4)
-        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
-        recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl).reshape(trajectory.shape)
-        fw = frame_channel_weights(cw, B, T, N, O, normalize, recon.device)
-        rec, tgt = recon.reshape(B, T, N, O), trajectory.reshape(B, T, N, O)
-        return weighted_mse(rec[:, :T_in], tgt[:, :T_in], fw[:, :T_in]), \
-            (weighted_mse(rec[:, T_in:], tgt[:, T_in:], fw[:, T_in:]) if T > T_in else recon.new_zeros(()))
+        fw = LossWeights.build(weights, channel_weights, B, N, O, T=T, normalize=normalize, device=recon.device, frames=slice(T))
+        return self._horizon_errors(recon, trajectory, T_in, fw)

@@ -12,11 +12,14 @@ variables that are observed separately,
 
     loss = 1 / (B N O) * sum_{b,n,o} cw[b,n,o] * (out[b,n,o] - target[b,n,o])^2
 
-with the same rule per value.  ``valid_channel_weights``, ``prepare_channel_weights``, ``point_support`` and
-``observed_channel_sampling_weights`` are the counterparts of the per-point helpers; ``weighted_mse`` and
-``gather_point_weights`` take either kind.
+with the same rule per value; ``point_support`` says where a point carries any value.  ``weighted_mse`` and
+``gather_point_weights`` take either kind and tell them apart by rank.  (B, T, N) point weights and (B, N, O) channel weights have
+the same rank, so the trainers carry a ``LossWeights``: the prepared tensor and its kind, with the frames, subsets, support and
+rescaling a step needs; the prepare_* / frame_* / observed_* functions are the same code, one kind at a time.
 Pure torch, no GPU needed.
 """
+from dataclasses import dataclass
+
 import torch
 
 QUADRATURE_KINDS = ("latitude", "colatitude", "ball")
@@ -77,23 +80,6 @@ def normalize_channel_weights(cw):
     return normalize_point_weights(cw.reshape(*cw.shape[:-2], -1)).reshape(cw.shape)
 
 
-def prepare_channel_weights(weights, B, N, O, normalize=True, device=None):
-    """What a trainer does with its ``channel_weights`` argument: None stays None; (N, O) or (B, N, O) becomes float32 (B, N, O),
-    finite and >= 0 (ValueError otherwise), with mean 1 over each signal's N * O values unless ``normalize`` is False."""
-    if weights is None:
-        return None
-    w = torch.as_tensor(weights, dtype=torch.float32)
-    if w.dim() == 2:
-        w = w[None].expand(B, -1, -1)
-    if tuple(w.shape) != (B, N, O):
-        raise ValueError(f"channel weights have shape {tuple(w.shape)}, expected {(B, N, O)} or {(N, O)}")
-    if normalize:
-        w = normalize_channel_weights(w)
-    elif bool((w < 0).any()) or not bool(torch.isfinite(w).all()):
-        raise ValueError("channel weights must be finite and >= 0")
-    return w.to(device).contiguous() if device is not None else w.contiguous()
-
-
 def point_support(cweights):
     """Channel weights (..., N, O) -> point weights (..., N), > 0 exactly where at least one channel of the point is observed (the
     sum over the channels).  What make_signal_masks takes, so that per-signal sampling draws from the points that carry a value."""
@@ -103,19 +89,65 @@ def point_support(cweights):
     return cw.clamp_min(0).sum(dim=-1)
 
 
-def prepare_point_weights(weights, B, N, normalize=True, device=None):
-    """What a trainer does with its ``weights`` argument: None stays None; (N,) or (B, N) becomes float32 (B, N), with
-    mean 1 per signal unless ``normalize`` is False."""
+def cut_frames(weights, frames, channel=False):
+    """A caller's weights with a frame axis -- (B, T, N), per-channel (B, T, N, O) -- cut to ``weights[:, frames]`` (an index or a
+    slice); weights without one, and None, come back as they are."""
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights)
+    return w[:, frames] if w.dim() == (4 if channel else 3) else w
+
+
+def _prepare(weights, B, N, O, T, channel, normalize, device):
+    """The one preparation behind prepare_* (``T`` None) and frame_*: float32, broadcast over the batch (and over T frames), mean 1
+    per signal(-frame) unless ``normalize`` is False, on ``device``.  Channel weights are checked finite and >= 0 where they are not
+    normalised and wherever they come with a frame axis; point weights only by normalize_point_weights (every check is a host
+    synchronisation, so none is added)."""
     if weights is None:
         return None
     w = torch.as_tensor(weights, dtype=torch.float32)
-    if w.dim() == 1:
-        w = w[None].expand(B, -1)
-    if tuple(w.shape) != (B, N):
-        raise ValueError(f"weights have shape {tuple(w.shape)}, expected {(B, N)} or {(N,)}")
+    name, grid = ("channel weights", (N, O)) if channel else ("weights", (N,))
+    framed = T is not None and w.dim() == len(grid) + 2
+    if framed:
+        if tuple(w.shape) != (B, T) + grid:
+            raise ValueError(f"{name} have shape {tuple(w.shape)}, expected {(B, T) + grid}, {(B,) + grid} or {grid}")
+    else:
+        if w.dim() == len(grid):
+            w = w[None].expand(B, *w.shape)
+        if tuple(w.shape) != (B,) + grid:
+            raise ValueError(f"{name} have shape {tuple(w.shape)}, expected {(B,) + grid} or {grid}")
+    if channel and (framed or not normalize) and (bool((w < 0).any()) or not bool(torch.isfinite(w).all())):
+        raise ValueError("channel weights must be finite and >= 0")
     if normalize:
-        w = normalize_point_weights(w)
-    return w.to(device).contiguous() if device is not None else w.contiguous()
+        w = normalize_channel_weights(w) if channel else normalize_point_weights(w)
+    w = w.to(device) if device is not None else w
+    if framed:
+        return w
+    return w.contiguous() if T is None else w.contiguous()[:, None].expand(B, T, *grid)
+
+
+def prepare_point_weights(weights, B, N, normalize=True, device=None):
+    """What a trainer does with its ``weights`` argument: None stays None; (N,) or (B, N) becomes float32 (B, N), with
+    mean 1 per signal unless ``normalize`` is False."""
+    return _prepare(weights, B, N, None, None, False, normalize, device)
+
+
+def prepare_channel_weights(weights, B, N, O, normalize=True, device=None):
+    """What a trainer does with its ``channel_weights`` argument: None stays None; (N, O) or (B, N, O) becomes float32 (B, N, O),
+    finite and >= 0 (ValueError otherwise), with mean 1 over each signal's N * O values unless ``normalize`` is False."""
+    return _prepare(weights, B, N, O, None, True, normalize, device)
+
+
+def frame_weights(weights, B, T, N, normalize=True, device=None):
+    """``weights`` (N,), (B, N) or (B, T, N) -> float32 (B, T, N), every signal-frame's weights of mean 1 over the full grid
+    unless ``normalize`` is False; None stays None."""
+    return _prepare(weights, B, N, None, T, False, normalize, device)
+
+
+def frame_channel_weights(weights, B, T, N, O, normalize=True, device=None):
+    """Per-channel ``weights`` (N, O), (B, N, O) or (B, T, N, O) -> float32 (B, T, N, O), every signal-frame's weights of mean 1 over
+    its N * O values unless ``normalize`` is False; None stays None."""
+    return _prepare(weights, B, N, O, T, True, normalize, device)
 
 
 def gather_point_weights(weights, masks):
@@ -138,20 +170,21 @@ def observed_sampling_weights(weights, num_sampled):
     where n_b <= N_s), so loss values and step lengths keep their scale; 0/1 weights normalised to mean 1 on the grid (1 / f
     on the observed points) come out as 1 on the observed points.  A signal that observes nothing stays zero."""
     w = torch.as_tensor(weights)
-    N = w.shape[-1]
-    n = (w > 0).sum(dim=-1, keepdim=True).to(w.dtype)
-    c = n / N * (float(num_sampled) / n.clamp(min=1.0).clamp(max=float(num_sampled)))
-    return w * c
+    return w * _observed_factor(w, num_sampled)
+
+
+def _observed_factor(support, num_sampled):
+    """c_b of observed_sampling_weights, (..., 1), from point weights (..., N) that are > 0 on signal b's n_b observed points."""
+    N = support.shape[-1]
+    n = (support > 0).sum(dim=-1, keepdim=True).to(support.dtype)
+    return n / N * (float(num_sampled) / n.clamp(min=1.0).clamp(max=float(num_sampled)))
 
 
 def observed_channel_sampling_weights(cweights, num_sampled):
     """observed_sampling_weights for channel weights (B, N, O): a point is observed where any of its channels is (point_support),
     n_b counts those points, and the same factor c_b multiplies all channels of signal b's points."""
     cw = torch.as_tensor(cweights)
-    N = cw.shape[-2]
-    n = (point_support(cw) > 0).sum(dim=-1, keepdim=True).to(cw.dtype)
-    c = n / N * (float(num_sampled) / n.clamp(min=1.0).clamp(max=float(num_sampled)))
-    return cw * c[..., None]
+    return cw * _observed_factor(point_support(cw), num_sampled)[..., None]
 
 
 def weighted_mse(out, target, weights=None):
@@ -168,3 +201,86 @@ def weighted_mse(out, target, weights=None):
         w = weights[..., None].to(out.dtype)
     d = torch.where(w > 0, out - target, torch.zeros_like(out))
     return (w * d * d).mean()
+
+
+@dataclass(frozen=True, eq=False)
+class LossWeights:
+    """The loss weights of one step, prepared: ``w`` float32 and whether it is per point -- (B, N), with frames (B, T, N) -- or per
+    channel -- (B, N, O), (B, T, N, O).  Rank alone cannot tell (B, T, N) from (B, N, O); this value can, so a trainer carries one
+    variable whatever its caller passed.  "No weights" is None, never an instance: ``build`` returns None for it, and ``loop_kw`` /
+    ``nef_kw`` / ``loss_tensor`` below take None and hand on nothing, so an unweighted step runs not one operation more.
+
+    What the trainers rely on:
+      - ``build`` is the only place that tells ``weights=`` from ``channel_weights=``; it raises for both, for a wrong shape, and for
+        values that are not finite and >= 0 exactly where the prepare_* / frame_* helpers do (_prepare), and costs their host
+        synchronisations, no more.
+      - The weights of the fit (``frames=0``) and those of the errors over all frames (``T=``) are prepared from the caller's weights
+        separately: frame 0 is normalised on its own, not cut from the normalised frames.
+      - Nothing here draws random numbers.  A step draws its masks from ``support()`` and only then calls ``drawn_on(masks)``; under
+        point drop-out it draws the keep-mask first, then the masks, then ``keep`` / ``renormalized`` / ``observed_draw``.
+      - ``observed_draw`` rescales the weights a FIT on per-signal masks takes; errors on the full grid (fit_errors, val_step) take the
+        value as built."""
+    w: torch.Tensor
+    channel: bool = False
+
+    @classmethod
+    def build(cls, weights, channel_weights, B, N, O, T=None, normalize=True, device=None, frames=None):
+        """From a step's ``weights`` ((N,), (B, N), (B, T', N)) and ``channel_weights`` ((N, O), (B, N, O), (B, T', N, O)): None for
+        neither, ValueError for both.  ``frames``: an index or slice of the frame axis, where the input has one (cut_frames), taken
+        first.  ``T`` None gives (B, N[, O]); otherwise (B, T, N[, O]), input without a frame axis repeated over the T frames."""
+        if channel_weights is not None and weights is not None:
+            raise ValueError("pass weights= or channel_weights=, not both")
+        channel = channel_weights is not None
+        raw = channel_weights if channel else weights
+        if frames is not None:
+            raw = cut_frames(raw, frames, channel)
+        w = _prepare(raw, B, N, O, T, channel, normalize, device)
+        return None if w is None else cls(w, channel)
+
+    def _like(self, w):
+        return LossWeights(w, self.channel)
+
+    def _per_point(self, t):
+        """``t`` (..., N), one value per point, shaped to multiply ``w``."""
+        return t[..., None] if self.channel else t
+
+    def frame_range(self, start, stop):
+        return self._like(self.w[:, start:stop])
+
+    def support(self):
+        """(..., N), > 0 exactly where the point is observed: what make_signal_masks takes."""
+        return point_support(self.w) if self.channel else self.w
+
+    def points(self, index):
+        """The weights of a subset of the grid points, ``[:, index]`` along N."""
+        return self._like(self.w[:, index])
+
+    def keep(self, mask):
+        """Times a (B, N) keep-mask: a point that is not kept is not observed."""
+        return self._like(self.w * self._per_point(mask))
+
+    def renormalized(self):
+        return self._like(normalize_channel_weights(self.w) if self.channel else normalize_point_weights(self.w))
+
+    def observed_draw(self, num_sampled):
+        """Rescaled for a fit on ``num_sampled`` points per signal drawn from its observed set (observed_sampling_weights)."""
+        return self._like(self.w * self._per_point(_observed_factor(self.support(), num_sampled)))
+
+    def drawn_on(self, masks):
+        """The weights of a fit on ``masks`` the step drew itself: rescaled where they are per signal (B, N_s, S+1), else as they are."""
+        return self.observed_draw(masks.shape[1]) if masks.dim() == 3 else self
+
+
+def loop_kw(lw):
+    """The keyword inner_loop and meta_gradients take a LossWeights (or None) by."""
+    return {} if lw is None else {"channel_weights" if lw.channel else "weights": lw.w}
+
+
+def nef_kw(lw):
+    """The keyword nef.mse_value_and_latent_grads and nef.eval_loss take it by."""
+    return {} if lw is None else {"channel_weight" if lw.channel else "weight": lw.w}
+
+
+def loss_tensor(lw):
+    """What weighted_mse, gather_signal_points and sample_frames take: the tensor (they tell the kinds apart by its rank) or None."""
+    return None if lw is None else lw.w
