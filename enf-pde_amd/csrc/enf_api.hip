@@ -144,14 +144,17 @@ int enf_side_join_pending(hipStream_t st, const void* workspace) {
 //   enf_backward_latents_ex   z-fold backward only; does NOT zero here (its memset follows the tail backward on the caller's
 //                             stream); not forked: enf_launch_wz on the caller's stream
 //   enf_fit_step              zeroes on the side stream; not forked (or not the z-fold backward): enf_launch_wz (z-fold only) and
-//                             the memset on the caller's stream
-static int side_prepare_bwd(SideStream* side, const EnfCall& c, bool zero_dlt) {
+//                             the memset on the caller's stream; with the shared-latent backward (wz_signals = 1) the matrices
+//                             of signal 0's Z latents only -- the zero-fill stays whole
+static int side_prepare_bwd(SideStream* side, const EnfCall& c, bool zero_dlt, int wz_signals = 0) {
   if (!side) return 0;
+  EnfDims mw = c.m;
+  if (wz_signals > 0) mw.B = wz_signals;
   std::lock_guard<std::mutex> lk(side->mu);
   SidePending* e = side->entry(c.ws);
   if (!e) return 0;
   if (hipEventRecord(side->fork, c.st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess) return ENF_ELAUNCH;
-  if (int rc = enf_launch_wz(c.m, c.L, c.blob, c.F(c.W.lt), nullptr, c.F(c.W.wzb), nullptr, c.ws + c.W.wzt, side->s)) return rc;
+  if (int rc = enf_launch_wz(mw, c.L, c.blob, c.F(c.W.lt), nullptr, c.F(c.W.wzb), nullptr, c.ws + c.W.wzt, side->s)) return rc;
   if (zero_dlt && hipMemsetAsync(c.F(c.W.dlt), 0, enf_lt_bytes(c.m), side->s) != hipSuccess) return ENF_ELAUNCH;
   if (hipEventRecord(e->join, side->s) != hipSuccess) return ENF_ELAUNCH;
   e->pending = true;              // until joined: a failure in between leaves it for the next call's join
@@ -306,11 +309,30 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
                                 zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st,
                                 shared ? c.F(W.dybar) : nullptr)))
     return rc;
+  // the shared-latent backward (enf_layout.h: enf_shared_backward_rule): tail, loss and backward pair kernel run ONCE, on signal 0
+  const bool sbwd = enf_shared_backward_rule(m, flags, per_value, err != nullptr) == 1;
+  EnfDims m1 = m;
+  if (sbwd) m1.B = 1;
   // what the backward pair kernel needs from the latent table alone runs on the side stream beside the tail
-  if ((rc = side_prepare_bwd(zb ? side_stream() : nullptr, c, !det)) < 0) return rc;
+  if ((rc = side_prepare_bwd(zb ? side_stream() : nullptr, c, !det, sbwd ? 1 : 0)) < 0) return rc;
   if (!rc) {
-    if (zb && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
+    if (zb && (rc = enf_launch_wz(m1, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
     if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+  }
+  if (sbwd) {
+    // signal 0's tail forward (pre-activations stashed), the loss of that one row against all B targets and weights with d out
+    // (B, N), the unit-seeded tail backward, then the one pair pass contracted with d out.  d out and the row of outputs borrow the
+    // d ybar region behind signal 0's rows, which nothing else of this step uses: [N HD | d out: B N | out: N].
+    float* dout = c.F(W.dybar) + (size_t)m.N * m.HD;
+    float* out1 = dout + (size_t)m.B * m.N;
+    if ((rc = enf_launch_tail(m1, c.L, c.blob, c.F(W.ybar), out1, nullptr, nullptr, nullptr, c.F(W.tail_act), 0, 1, st))) return rc;
+    if ((rc = enf_launch_mse_shared(out1, target, weight, m.B, m.N, grad_scale, dout, loss, st))) return rc;
+    if ((rc = enf_launch_tail_seed(m1, c.L, c.blob, c.F(W.ybar), 0, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
+    if ((rc = enf_side_join_pending(st, workspace))) return rc;
+    if ((rc = enf_launch_pair_bwd_shared(m, c.L, c.blob, x, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), dout, c.F(W.dlt),
+                                         c.ws + W.wzt, c.F(W.wzb), st)))
+      return rc;
+    return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
   }
   if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
                                  det ? c.F(c.X.loss) : nullptr, per_value, err)))
@@ -488,6 +510,15 @@ extern "C" int enf_shared_forward_parts(const EnfDesc* d, int32_t* parts) {
   const int P = enf_use_zfold(m) || (m.mask_mode != ENF_MASK_OFF && !m.ffn) ? 0 : enf_shared_fwd_parts(m);
   *parts = P ? P : 1;
   return P ? 1 : 0;
+}
+
+// 1 where a fit step with these flags on this descriptor takes the shared-latent backward (enf_layout.h: enf_shared_backward_rule; a
+// call that carries per-channel weights or wants the per-point errors never does), 0 where it runs the ordinary sequence
+extern "C" int enf_shared_backward_applies(const EnfDesc* d, unsigned flags) {
+  const int rc = enf_check_desc(d);
+  if (rc) return rc;
+  if (flags & ~(ENF_FIT_DETERMINISTIC | ENF_FIT_SHARED_LATENTS)) return ENF_EINVAL;
+  return enf_shared_backward_rule(enf_dims(d), flags, false, false);
 }
 
 extern "C" int enf_pair_partition(const EnfDesc* d, int32_t* run, int32_t* workgroups, int32_t* parts) {

@@ -32,6 +32,15 @@ inline int enf_pair_bwd_nsplit(const EnfDims& m, bool zfold) {
   while (wgs * ns < 256 && ns * 2 <= ntiles) ns *= 2;
   return ns;
 }
+// the shared-latent backward's query split (grid.y; grid.x = the Z latents of signal 0): where Z ceil(N / 128) workgroups fit one round
+// of 256 CUs every wave gets at most one tile, so the launch is one tile step deep; larger shapes follow the sweep above on Z latents
+inline int enf_pair_bwd_shared_nsplit(const EnfDims& m) {
+  const int ntiles = (m.N + 15) / 16;
+  if ((long long)m.Z * ((m.N + 127) / 128) <= 256) return (ntiles + 7) / 8;
+  EnfDims m1 = m;
+  m1.B = 1;
+  return enf_pair_bwd_nsplit(m1, true);
+}
 // K3's partial rows of d lt, [nsplit][B Z][lt stride] floats, and its per-latent shares of the query gradient, (B, Z, N, dx)
 inline size_t enf_det_part_bytes(const EnfDims& m, bool zfold) {
   return enf_align(sizeof(float) * (size_t)enf_pair_bwd_nsplit(m, zfold) * m.B * m.Z * enf_lt_stride(m.H, m.D));
@@ -122,6 +131,12 @@ int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, 
                         const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store, const char* wzt,
                         const float* wzb, float* dxq, hipStream_t st, float* part = nullptr, float* dxpart = nullptr);
 
+// the shared-latent backward (enf_layout.h: enf_shared_backward_rule): signal 0's pairs once, on the unit-seeded dybar / delta, contracted
+// with dout (B, N) into all B Z rows of `dlt` (ADDS); ENF_EUNSUPPORTED where there is no such instantiation
+int enf_launch_pair_bwd_shared(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, const float* lt, const float* lse,
+                               const float* dybar, const float* delta, const float* dout, float* dlt, const char* wzt, const float* wzb,
+                               hipStream_t st);
+
 // ---- K4, X^T delta over the activation store (enf_xtd.hip)
 size_t enf_xtd_part_bytes(const EnfDims& m, long long P);       // slice partials of a pass over P rows (256-aligned)
 // store: the ENF_NUM_STORE(H) device buffers K3 wrote for P rows; dpair: ENF_NUM_PAIR_TENSORS fp32 device pointers in
@@ -175,5 +190,9 @@ int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob,
 // *loss (through loss_part in deterministic mode) instead of storing `out`; weight / per_value as above.  ybar is fp32.
 int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part = nullptr);
+// the shared-latent backward's loss (enf_loss.hip): ONE row out1 (N values, O = 1) against all B signals' targets and weights (B, N;
+// weight may be NULL): *loss += the mean squared error, dout (B, N) = its gradient times gscale -- enf_mse_kernel's arithmetic
+int enf_launch_mse_shared(const float* out1, const float* target, const float* weight, int B, int N, float gscale, float* dout,
+                          float* loss, hipStream_t st);
 // loss_b[b] = scale * (err[b, 0] + ... + err[b, N - 1]): one workgroup per signal, fixed order, no atomics (enf_loss.hip)
 int enf_launch_signal_sum(const float* err, int B, int N, float scale, float* loss_b, hipStream_t st);

@@ -295,6 +295,26 @@ inline bool enf_use_zfold_bwd(const EnfDims& m) {
   return (long long)m.B * m.Z >= 192;
 }
 
+// The shared-latent backward (ENF_FIT_SHARED_LATENTS, first inner step): with equal latents and points every activation the z-fold
+// backward recomputes, and the tail's Jacobian, are the same for all B signals, and the map d out -> d(latent table) is linear in
+// d out.  With one output channel
+//   dlt[b, z, f] = sum_n dout[b, n] c[n, z, f],   c = the per-pair contributions for d out = 1 at every query,
+// so ONE pass over (N queries x Z latents) on signal 0 with the unit-seeded tail backward, contracted with the (B, N) matrix d out
+// (enf_pair_bwd.hip: SHARED), replaces B passes.  THE rule (the C-ABI's enf_shared_backward_applies and the fit step both ask it):
+// 1 where a fit step with these flags takes that path.  per_value / err: the call carries per-channel weights / wants the per-point
+// errors (both keep the ordinary sequence).
+inline bool enf_pair_bwd_shared_exists(const EnfDims& m) {      // the SHARED instantiations of enf_pair_bwd_kernel (launch_shared)
+  return !m.ffn && !enf_inv_has_phase(m.inv) && ((m.D == 128 && (m.H == 2 || m.H == 1)) || (m.D == 64 && m.H == 2));
+}
+inline int enf_shared_backward_rule(const EnfDims& m, unsigned flags, bool per_value, bool err) {
+  if (!(flags & ENF_FIT_SHARED_LATENTS) || (flags & ENF_FIT_DETERMINISTIC)) return 0;
+  // the shared forward runs: more than one signal, the latent-split forward, relu masks off
+  if (m.B < 2 || enf_use_zfold(m) || m.mask_mode != ENF_MASK_OFF || enf_shared_fwd_parts(m) < 1) return 0;
+  if (m.O != 1 || per_value || err) return 0;
+  if (!enf_use_zfold_bwd(m) || (size_t)m.H * 2 * enf_panel_bytes(m.D, m.D, m.bf16) >= 0x7fffffffu) return 0;
+  return enf_pair_bwd_shared_exists(m) ? 1 : 0;
+}
+
 struct EnfWorkspace {
   size_t lt;        // B*Z*lt_stride floats: latent table
   size_t an;        // B*Z*(D + D + 2) floats: stem output, a_norm, LN mean/rstd (prologue backward)

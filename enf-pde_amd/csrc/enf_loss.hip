@@ -67,6 +67,43 @@ __global__ __launch_bounds__(256) void enf_mse_cw_kernel(const float* __restrict
   }
 }
 
+// The shared-latent backward's loss (enf_layout.h: enf_shared_backward_rule): every signal's output is the ONE row out1 (N values, one
+// channel), so element i = b N + n compares out1[n] with target[i].  The arithmetic per element, the partial sums and the one atomic
+// per block are enf_mse_kernel's; dout (B, N) is the only per-signal quantity the shared backward pair kernel reads.
+__global__ __launch_bounds__(256) void enf_mse_shared_kernel(const float* __restrict__ out1, const float* __restrict__ target,
+                                                             const float* __restrict__ weight, size_t n, int N, float inv_n, float gscale,
+                                                             float* __restrict__ dout, float* loss) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float o = out1[i % (size_t)N];
+    float d;
+    if (weight) {
+      const float w = weight[i];
+      const float dd = w > 0.f ? o - target[i] : 0.f;
+      d = w * dd;
+      s = fmaf(d, dd, s);
+    } else {
+      d = o - target[i];
+      s = fmaf(d, d, s);
+    }
+    dout[i] = 2.0f * d * inv_n * gscale;
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv_n);
+}
+
+int enf_launch_mse_shared(const float* out1, const float* target, const float* weight, int B, int N, float gscale, float* dout,
+                          float* loss, hipStream_t st) {
+  const size_t n = (size_t)B * (size_t)N;
+  const size_t blocks = (n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256;
+  hipLaunchKernelGGL(enf_mse_shared_kernel, dim3((unsigned)blocks), dim3(256), 0, st, out1, target, weight, n, N, 1.0f / (float)n, gscale,
+                     dout, loss);
+  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+}
+
 // *loss += part[0] + ... + part[n - 1]: thread t adds part[t], part[t + 256], ... in order, then a fixed tree over the 256 threads.
 // The order depends on n alone, never on which workgroup of the producing kernel finished first.
 __global__ __launch_bounds__(256) void enf_loss_sum_kernel(const float* __restrict__ part, int n, float* loss) {

@@ -43,6 +43,9 @@ struct PairBwdArgs {
   // row in row (split, b Z + z) instead of adding it to dlt; dxpart (with dxq): (B, Z, N, dx) -- a latent's wave stores its share of
   // d x there.  Reduction kernels add splits / latents in index order (enf_launch_pair_bwd).
   float* part; float* dxpart;
+  // SHARED (shared-latent backward, enf_layout.h: enf_shared_backward_rule): the kernel's own B is 1 (signal 0's x, latent rows, W_zh
+  // panels, unit-seeded dybar / delta); dout (SB, N) is d out of all SB signals, dlt their SB Z gradient rows; grid.z = groups of 16 signals
+  const float* dout; int SB;
 };
 
 // The STORE instantiation's 7 + 4 H buffer pointers, fetched from the kernel-argument segment where they are used (s_load_dwordx2 +
@@ -337,9 +340,17 @@ DEV void pair_invariant_bwd(int inv_id, int dx, const QueryPt& q, const f32x4& p
 // No relu: no masks.  STORE: the embedding's "input" rows ENF_S_EQ / ENF_S_EV hold the invariant in features 0..3 (zeros
 // elsewhere; ffn_inv_frags) and ENF_S_DA1 / ENF_S_DA2 hold d P, so K4's X^T delta products give d W0 in their first I rows and
 // d b0 as the column sums.
-template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1, bool FFN = false>
+// SHARED (z-fold, rff, no STORE): the shared-latent backward.  The tile chain is the same code on signal 0 with the unit-seeded
+// d ybar / delta; what changes is the four sums over a tile's queries.  The flipped tiles already have rows = queries (4 quad + i) and
+// columns = features (lane & 15): that is the B operand of v_mfma_f32_16x16x4_f32, one MFMA per register i, and the A operand is
+// dout[b = lane & 15][n0 + 4 quad + i] (0 for b >= SB or n >= N), so four chained MFMAs per 16-feature tile give G[b, f] with rows =
+// signals, in exact fp32.  d u folds dlogit_h[n] into the A operand.  The seven per-query scalars (d c_h, d pose, d wcoef) are moved
+// from the quad-0 columns into one more such tile.  Every G goes to dlt[b, z, :] with float atomics as it is produced: no partial sum
+// is kept across tiles, the epilogue is empty.
+template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1, bool FFN = false, bool SHARED = false>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A) {
   static_assert(!(ZF && STORE), "the activation store needs the unfolded chain");
+  static_assert(!SHARED || (ZF && !STORE && !FFN), "the shared-latent backward is a z-fold rff instantiation");
   static_assert(INV < 0 || INV == ENF_INV_REL_POS_PERIODIC || INV == ENF_INV_LATITUDE_PERIODIC || INV == ENF_INV_POLAR_PERIODIC ||
                 INV == ENF_INV_PONITA, "specialised invariants: two coordinates, no phase");
   const int inv_id = INV >= 0 ? INV : A.inv;
@@ -458,9 +469,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
 #pragma unroll
   for (int h = 0; h < H; ++h) {
     dC[h] = 0.f;
+    if constexpr (!SHARED) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      lacc[(h * NT + t) * 64] = 0.f; lacc[((H + h) * NT + t) * 64] = 0.f;
+      for (int t = 0; t < NT; ++t) {
+        lacc[(h * NT + t) * 64] = 0.f; lacc[((H + h) * NT + t) * 64] = 0.f;
+      }
     }
   }
 
@@ -481,6 +494,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     pair_invariant<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, ext);
     const size_t srow = (size_t)bzc * A.N + n;        // row of the materialised activations (STORE)
     const bool swrite = STORE && nvalid && active;
+    // SHARED: the A operand of the contraction, dout[signal 16 group + col][n0 + 4 quad + i], read again where it is used (L2 hits)
+    // instead of held over the tile; and the atomics of one 16-signal x 16-feature result tile G into field offset `off` of row z
+    auto load_dout = [&](float (&ad)[4]) {
+      const int sb = 16 * (int)blockIdx.z + col;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int nn = n0 + 4 * quad + i;
+        ad[i] = SHARED && tvalid && sb < A.SB && nn < A.N ? A.dout[(size_t)sb * A.N + nn] : 0.f;
+      }
+    };
+    auto shared_add = [&](int off, const f32x4& g, bool cols) {
+      if (!(SHARED && tvalid && active && cols)) return;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int sb = 16 * (int)blockIdx.z + 4 * quad + j;
+        if (sb < A.SB) atomicAdd(A.dlt + ((size_t)sb * A.Z + bz) * ltstride + off, g[j]);
+      }
+    };
 
     BSTAMP(0);
     // ---------------- q-forward: logits -> attention probabilities
@@ -642,14 +673,23 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
               none, FA, P, ring, gM, LA ? nxt : pWG + h * PANEL_DD, lane, [](int) { return f32x4{0.f, 0.f, 0.f, 0.f}; },
               [&](int mt, const f32x4& af) { dvf[mt] = af; });
           float part[NT];
+          float ad[4];
+          if constexpr (SHARED) load_dout(ad);
           panel_gemm_flip<KB, NT, BF16, ST_DD, NW, false, INIT_ACC, LA>(
               none, F, P, ring, pWG + h * PANEL_DD, LA ? nxt2 : nxt, lane,
               [&](int mt) { const float bc = c_bgb[h * D + 16 * mt + col]; return f32x4{bc, bc, bc, bc}; },
               [&](int mt, const f32x4& af) {
-                const f32x2 p2 = __builtin_elementwise_fma(hi2(af), hi2(dvf[mt]), lo2(af) * lo2(dvf[mt]));
-                part[mt] = p2[0] + p2[1];
+                if constexpr (SHARED) {
+                  f32x4 g = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                  for (int i = 0; i < 4; ++i) g = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[i], af[i] * dvf[mt][i], g, 0, 0, 0);
+                  shared_add(enf_lt_off_v0(H, D) + h * D + 16 * mt + col, g, true);
+                } else {
+                  const f32x2 p2 = __builtin_elementwise_fma(hi2(af), hi2(dvf[mt]), lo2(af) * lo2(dvf[mt]));
+                  part[mt] = p2[0] + p2[1];
+                }
               });
-          lacc_flush((H + h) * NT, part);
+          if constexpr (!SHARED) lacc_flush((H + h) * NT, part);
         }
         BSTAMP(6 + 6 * h);
       }
@@ -910,6 +950,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         for (int i = 0; i < 4; ++i) dl[h][i] = __shfl(dlogit[h], (quad << 4) | (4 * quad + i), 64);
       const bool more = ti + 1 < my_tiles;
       float upart[H][NT];
+      float adl[H][4];                    // SHARED: dout dlogit_h, the A operand of d u
+      if constexpr (SHARED) {
+        float ad[4];
+        load_dout(ad);
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) adl[h][i] = ad[i] * dl[h][i];
+      }
       // flipped tiles hold feature 16 mt + col of queries 4 quad + i: their mask bits sit in the words of lanes
       // (col >> 2) * 16 + 4 quad + i, bit 4 mt + (col & 3)
       unsigned mflip[4] = {0u, 0u, 0u, 0u};
@@ -929,13 +978,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
             } else { r0 = relu_f(af[0]); r1 = relu_f(af[1]); r2 = relu_f(af[2]); r3 = relu_f(af[3]); }
 #pragma unroll
             for (int h = 0; h < H; ++h) {
-              const f32x2 p2 = __builtin_elementwise_fma(f32x2{r2, r3}, f32x2{dl[h][2], dl[h][3]}, f32x2{r0, r1} * f32x2{dl[h][0], dl[h][1]});
-              upart[h][mt] = p2[0] + p2[1];
+              if constexpr (SHARED) {
+                f32x4 g = {0.f, 0.f, 0.f, 0.f};
+                g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][0], r0, g, 0, 0, 0);
+                g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][1], r1, g, 0, 0, 0);
+                g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][2], r2, g, 0, 0, 0);
+                g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][3], r3, g, 0, 0, 0);
+                shared_add(enf_lt_off_u(H, D) + h * D + 16 * mt + col, g, true);
+              } else {
+                const f32x2 p2 = __builtin_elementwise_fma(f32x2{r2, r3}, f32x2{dl[h][2], dl[h][3]}, f32x2{r0, r1} * f32x2{dl[h][0], dl[h][1]});
+                upart[h][mt] = p2[0] + p2[1];
+              }
             }
           }, c_bq1);                                                                                             // a1
+      if constexpr (!SHARED) {
 #pragma unroll
-      for (int h = 0; h < H; ++h) {
-        lacc_flush(h * NT, upart[h]);
+        for (int h = 0; h < H; ++h) {
+          lacc_flush(h * NT, upart[h]);
+        }
       }
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
@@ -965,6 +1025,36 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     }
     BSTAMP(17);
     // ---------------- per-latent scalars (each column is counted once: quad 0)
+    if constexpr (SHARED) {
+      // this tile's per-query scalars sc[j] (d c_h | d pose | d wcoef) sit in the quad-0 lane of their query.  Lane (col, quad) of the
+      // B operand wants scalar j = col of query 4 quad + i: one lane read per (i, j), kept where j == col.  G[b, j] then goes to the
+      // scalar fields of row (b, z).
+      float sc[H + 5];
+#pragma unroll
+      for (int j = 0; j < H + 5; ++j) sc[j] = 0.f;
+      if (quad == 0) {
+        float dwin = 0.f, tp[4] = {0.f, 0.f, 0.f, 0.f}, tw = 0.f;
+#pragma unroll
+        for (int h = 0; h < H; ++h) { sc[h] = dlogit[h]; dwin += dlogit[h]; }
+        pair_invariant_bwd<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, tp, tw, nullptr, nullptr);
+        sc[H] = tp[0]; sc[H + 1] = tp[1]; sc[H + 2] = tp[2]; sc[H + 3] = tp[3]; sc[H + 4] = tw;
+      }
+      float ad[4];
+      load_dout(ad);
+      f32x4 g = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float bv = 0.f;
+#pragma unroll
+        for (int j = 0; j < H + 5; ++j) {
+          const float t = __shfl(sc[j], 4 * quad + i, 64);
+          bv = col == j ? t : bv;
+        }
+        g = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[i], bv, g, 0, 0, 0);
+      }
+      const int off = col < H ? enf_lt_off_c(H, D) + col : col < H + 4 ? enf_lt_off_pose(H, D) + col - H : enf_lt_off_wcoef(H, D);
+      shared_add(off, g, col < H + 5);
+    } else
     if (quad == 0) {
       float dwin = 0.f;
 #pragma unroll
@@ -997,7 +1087,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   }
 
 #ifdef ENF_TEST_HOOKS
-  if constexpr (2 * H * (D / 16) <= 16) {
+  if constexpr (!SHARED && 2 * H * (D / 16) <= 16) {
     const int wg = blockIdx.y * gridDim.x + blockIdx.x;
     if (wg < ENF_HOOK_WGS) {
       float* o = enf_hook_wave_sums + (size_t)(wg * NWAVES + wave) * ENF_HOOK_ROW;
@@ -1016,6 +1106,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
 #endif
   pipe_finish(P);
   WSTAMP(2);
+  if constexpr (SHARED) return;     // every tile's sums have been added where they were formed
   // ---- fold the partial sums and add this wave's share into the latent-table gradient
   if (!active) return;   // (unfolded: a wave without a latent; no barrier follows on that path.  z-fold: all eight waves share the latent)
   // deterministic mode (wave-uniform): the share is STORED in this split's row of the partial buffer -- every (split, latent)
@@ -1156,6 +1247,43 @@ static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }
 
+template <int D, int H, bool BF16, int INV = -1>
+static int launch_pair_bwd_shared(const PairBwdArgs& A, hipStream_t st) {
+  using SM = PairBwdSmem<D, H, BF16, false>;
+  auto kern = enf_pair_bwd_kernel<D, H, BF16, false, true, INV, false, true>;
+  static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
+  if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
+  hipLaunchKernelGGL(kern, dim3(A.Z, A.nsplit, (A.SB + 15) / 16), dim3(NTHREADS), SM::TOTAL, st, A);
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+
+// The shared-latent backward (enf_layout.h: enf_shared_backward_rule; `m` is the whole batch's): one pass over signal 0's (N x Z) pairs
+// on the unit-seeded dybar (N, HD) / delta (N, H), contracted with dout (B, N) into all B Z rows of `dlt` (added to: the caller zeroes
+// them).  x, lt, lse, wzt, wzb: signal 0's rows.  The instantiations are those of enf_pair_bwd_shared_exists.
+int enf_launch_pair_bwd_shared(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, const float* lt, const float* lse,
+                               const float* dybar, const float* delta, const float* dout, float* dlt, const char* wzt, const float* wzb,
+                               hipStream_t st) {
+  if (!enf_pair_bwd_shared_exists(m) || !enf_pair_bwd_zfold_fits(m) || !wzt || !wzb || !dout) return ENF_EUNSUPPORTED;
+  PairBwdArgs A;
+  A.dxq = nullptr; A.part = nullptr; A.dxpart = nullptr; A.masks = nullptr; A.mask_B = 1; A.mask_b0 = 0;
+  A.wzt = wzt; A.wzb = wzb; A.inv_d = 1.0f / (float)m.Dt;
+  A.x = x; A.x_bstride = 0; A.lt = lt; A.blob = blob; A.L = L; A.lse = lse; A.dybar = dybar; A.delta = delta;
+  A.dlt = dlt; A.B = 1; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
+  A.nsplit = enf_pair_bwd_shared_nsplit(m); A.xcd_remap = 0;
+  A.dout = dout; A.SB = m.B;
+  if (m.bf16 && m.dx == 2) {      // the invariant as a compile-time constant, as for the per-signal kernels of the shipped configs
+    if (m.D == 128 && m.H == 2 && m.inv == ENF_INV_REL_POS_PERIODIC) return launch_pair_bwd_shared<128, 2, true, ENF_INV_REL_POS_PERIODIC>(A, st);
+    if (m.D == 64 && m.H == 2 && m.inv == ENF_INV_PONITA) return launch_pair_bwd_shared<64, 2, true, ENF_INV_PONITA>(A, st);
+  }
+#define ENF_CASE(DD, HH) \
+  if (m.D == DD && m.H == HH) return m.bf16 ? launch_pair_bwd_shared<DD, HH, true>(A, st) : launch_pair_bwd_shared<DD, HH, false>(A, st);
+  ENF_CASE(128, 2)
+  ENF_CASE(64, 2)
+  ENF_CASE(128, 1)
+#undef ENF_CASE
+  return ENF_EUNSUPPORTED;
+}
+
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor); read by the STORE instantiation only
 
 static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
@@ -1190,6 +1318,7 @@ static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blo
                            float* dxpart, int* nsplit) {
   PairBwdArgs A;
   A.dxq = dxq; A.part = part; A.dxpart = dxpart;
+  A.dout = nullptr; A.SB = 0;
   A.masks = store && m.mask_mode == ENF_MASK_READ ? m.masks : nullptr; A.mask_B = m.mask_B; A.mask_b0 = m.mask_b0;
   const bool zf = !store && wzt && wzb && enf_pair_bwd_zfold_fits(m);
   A.wzt = wzt; A.wzb = wzb; A.inv_d = 1.0f / (float)m.Dt;

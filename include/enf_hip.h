@@ -330,11 +330,31 @@ int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const floa
  * permission, not a command: where the forward resolves to the latent-split pair kernel and relu masks are off, that kernel then
  * runs ONCE, for signal 0, with its latents cut into P parts over all compute units (enf_shared_forward_parts), and a merge kernel
  * writes the row to all B signals' `ybar` / `lse`; elsewhere the ordinary sequence runs unchanged.  What differs from the call without
- * the flag is the fp32 order in which the partial sums over a query's latents are added; the B copies are the same bits.  Everything
- * behind the forward pair kernel (tail, loss, backward) is the ordinary sequence on per-signal targets and weights.  The parts borrow
+ * the flag is the fp32 order in which the partial sums over a query's latents are added; the B copies are the same bits.  The parts borrow
  * the workspace's d ybar | delta region: the workspace sizes do not change (enf_workspace_bytes_ex accepts the bit and ignores it).
+ * The shared backward.  With equal latents and points every activation the backward pair kernel recomputes, and the tail's Jacobian,
+ * are the same for all signals too, and d out -> d(latent table) is linear in d out.  With ONE output channel the whole backward of a
+ * fit step is dlt[b, z, f] = sum_n dout[b, n] c[n, z, f], c = the per-pair contributions for d out = 1 at every query, and
+ * dout[b, n] = 2 w[b, n] (out[n] - target[b, n]) grad_scale / (B N) is the only per-signal quantity.  Where ALL of the following hold
+ * (enf_shared_backward_applies), behind the shared forward the step therefore also runs ONCE, on signal 0: the tail forward, one loss
+ * kernel (that row of outputs against all B targets and weights, which also writes d out (B, N)), the unit-seeded tail backward, the
+ * per-latent matrices of Z latents (not B Z), and ONE backward pass of the pair kernel over (N queries x Z latents) that contracts its
+ * sums over queries with d out (fp32 matrix instructions: fp32 sums) and adds the result to all B Z gradient rows:
+ *     the shared forward runs;  O == 1;  no per-channel weights (enf_fit_step_cw);  no per-point errors asked for (enf_fit_step_e with
+ *     err);  ENF_FIT_DETERMINISTIC not set;  the backward resolves to the z-fold pair kernel;  the rff embedding, an invariant without
+ *     per-latent phases (not ball / ball_lat), and (D, H) one of (128, 2), (128, 1), (64, 2), in either precision.
+ * Elsewhere everything behind the forward pair kernel is the ordinary sequence on per-signal targets and weights, bit for bit.  Loss
+ * and gradients of the shared backward differ from the unflagged call's by rounding only: in fp32 mode by the order of the fp32 sums
+ * over queries; in bf16 mode also by WHERE d out meets a bf16 rounding (the ordinary backward rounds every signal's d out and the
+ * quantities scaled by it to bf16 operands, the shared one rounds the unit-seeded quantities and multiplies by d out in fp32).
+ * Workspace: d out and the row of outputs borrow the d ybar region behind signal 0's rows -- floats [N HD, N HD + B N) and the N
+ * after them; d ybar and delta are written for signal 0 only (floats [0, N HD) and [0, N H)): delta's floats [N H, B N H), which the
+ * ordinary backward writes, keep what they held.  The sizes do not change.
  * The library does NOT check the statement: with unequal latents every signal gets signal 0's forward. */
 #define ENF_FIT_SHARED_LATENTS 128u
+/* 1 where a fit step (enf_fit_step_ex / _w, or _e without err) with `flags` on this descriptor takes the shared backward above, 0
+ * where it runs the ordinary sequence behind the forward; negative ENF_E* on a bad descriptor, ENF_EINVAL on unknown flag bits. */
+int enf_shared_backward_applies(const EnfDesc* d, unsigned flags);
 /* 1 and *parts = P (a power of two; 1 = signal 0 in one pass, then the broadcast) where a call with ENF_FIT_SHARED_LATENTS /
  * ENF_STAGE_SHARED_LATENTS on this descriptor runs the shared forward; 0 and *parts = 1 where it runs the ordinary sequence (B == 1,
  * the z-fold forward, relu masks); negative ENF_E* on a bad descriptor. */
