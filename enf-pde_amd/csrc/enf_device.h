@@ -488,6 +488,30 @@ DEV void first_stage(Pipe& P, char* ring, unsigned panel, int wave, int lane) {
   if (!P.early) { stage_wait(); __syncthreads(); }
 }
 
+// RESIDENT panels: a weight panel that every unit of a workgroup's work multiplies by is loaded ONCE per workgroup, outside the
+// ring, and stays in LDS for the workgroup's lifetime.  resident_load issues the LDS-DMA (STAGE_MAX bytes per round, the piece
+// split of stage_issue); the caller retires it with the wait + barrier of the first_stage that follows.  resident_gemm is
+// panel_gemm on that address: the same stages, fragments and MFMA order, and no staging, wait, barrier or slot flip.
+template <int BYTES, int NW = NWAVES>
+DEV void resident_load(__amdgpu_buffer_rsrc_t rs, unsigned src_off, char* dst, int wave, int lane) {
+  constexpr int CH = BYTES < STAGE_MAX ? BYTES : STAGE_MAX;
+  static_assert(BYTES % CH == 0, "resident panel: whole staging rounds");
+#pragma unroll
+  for (int o = 0; o < BYTES; o += CH) stage_issue<CH, NW>(rs, src_off + o, dst + o, wave, lane);
+}
+template <int KBIN, int MTOUT, bool BF16, int INIT = INIT_ACC>
+DEV void resident_gemm(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, const char* panel, bool active, int lane,
+                       const float* bias = nullptr) {
+  using C = PanelCfg<KBIN, MTOUT, BF16>;
+  static_assert(INIT == INIT_ACC, "resident_gemm: the caller initialises the accumulators");
+  // the fragment address (panel + 16 lane) is formed here, at the use: left to hipcc it is loop-invariant, hoisted out of the
+  // latent loop and costs one more live register per resident panel in kernels that sit at the 256-register limit
+  asm volatile("" : "+v"(lane));
+#pragma unroll
+  for (int sp = 0; sp < C::SPP; ++sp)
+    if (active) gemm_stage<BF16, KBIN, C::MTS, INIT>(&acc[sp * C::MTS], F, panel + sp * C::STAGE, lane, bias + 16 * sp * C::MTS);
+}
+
 // Per-lane sums over a lane's NT x 4 values, two at a time: even / odd running sums in one register pair each, so a sum costs one
 // v_pk_add_f32 / v_pk_fma_f32 per TWO elements (plain operands: no op_sel, no neg).  Written with a single accumulator the additions are a
 // serial chain the compiler may not reassociate: 64 vector instructions per LayerNorm instead of 34 -- 6 % of K3's, 8 % of K2's.

@@ -16,7 +16,8 @@
 //   softmax over z of logit_h; ybar_h += softmax * (g - mu) * rstd              ECA:141-144
 // The mixer's LayerNorm affine and Dense_1, attn.out_proj and the block FFN's Dense_0 are
 // linear in the softmax-weighted sum and are applied once per query by the tail kernel.
-// Weight panels stream L2 -> LDS by LDS-DMA through a 2-slot ring shared by the 8 waves.
+// Weight panels stream L2 -> LDS by LDS-DMA through a 2-slot ring shared by the 8 waves; the shared panels that fit behind the
+// ring stay resident in LDS for the workgroup's lifetime (PairSmem).
 #include <hip/hip_runtime.h>
 #include "enf_launch.h"
 #include "enf_device.h"
@@ -76,16 +77,57 @@ extern "C" int enf_debug_read_stamps(unsigned long long* dst) {
 // keeps the vector ALU busy (8-wave lockstep measured 2 V + M per stage, M = the younger wave's MFMAs).
 template <bool ZFOLD> struct PairWaves { static constexpr int NW = ZFOLD && ENF_ZFOLD_WAVES == 4 ? 4 : NWAVES; };
 
-template <int D, int H, bool BF16, int NW, bool FFN = false> struct PairSmem {
+// The shared D x D weight panels of a latent step, in the order the step multiplies by them.  (The gamma/beta panels are one per
+// head and twice the size, the z-fold's W_zh are per latent: both always stream.)
+enum { RP_Q1 = 0, RP_V1 = 1, RP_F = 2, RP_M = 3, RP_COUNT = 4 };
+constexpr int LDS_PER_CU = 160 * 1024;
+// The resident set (a bit per RP_*): greedily the candidate that saves the most ring loads per latent step, then the smaller one,
+// then the earlier one, as long as it fits in `room` bytes.  saved[i] = 0: the step has no such panel.
+constexpr unsigned pair_resident_set(const int (&saved)[RP_COUNT], const int (&bytes)[RP_COUNT], int room) {
+  unsigned set = 0;
+  for (int n = 0; n < RP_COUNT; ++n) {
+    int best = -1;
+    for (int i = 0; i < RP_COUNT; ++i) {
+      if ((set >> i & 1u) || saved[i] <= 0 || bytes[i] > room) continue;
+      if (best < 0 || saved[i] > saved[best] || (saved[i] == saved[best] && bytes[i] < bytes[best])) best = i;
+    }
+    if (best < 0) break;
+    set |= 1u << best;
+    room -= bytes[best];
+  }
+  return set;
+}
+// where the resident panels in front of panel `p` end, the first of them at `base`
+constexpr int pair_resident_end(unsigned set, const int (&bytes)[RP_COUNT], int p, int base) {
+  for (int i = 0; i < p; ++i) base += (set >> i & 1u) ? bytes[i] : 0;
+  return base;
+}
+
+// LDS map (bytes from 0): ring, 2 slots of 32 KB | constants | per-wave latent vectors | softmax exchange | resident panels.
+// RES = false leaves the resident set empty (every panel streams through the ring): the test library's reference, not a product path.
+template <int D, int H, bool BF16, int NW, bool FFN = false, bool ZFOLD = false, bool RES = true> struct PairSmem {
   static constexpr int RING = 0;                                   // 2 slots
   static constexpr int EW = FFN ? 4 * D : 2 * D;                   // embedding of one branch: coefficient A-operands / Dense_0 rows
   static constexpr int CONSTS = RING + 2 * STAGE_MAX;              // bq1 bv1 bf bm (D each) | bgb (2HD) | acq acv (EW each)
   static constexpr int N_CONST = 4 * D + 2 * H * D + 2 * EW;
   static constexpr int ZVEC = CONSTS + 4 * N_CONST;                // NWAVES x 2*H*D floats
   static constexpr int XCH = ZVEC + 4 * NW * 2 * H * D;            // NW x H x 3 x 16 floats
-  static constexpr int TOTAL = XCH + 4 * NW * H * 3 * 16;
+  static constexpr int RESIDENT = XCH + 4 * NW * H * 3 * 16;       // the resident panels, in RP_* order
   static constexpr int YBYTES = H * (D / 16) * 4 * 64 * 4;         // one wave's Y in [reg][lane] order
-  static_assert(4 * YBYTES <= 2 * STAGE_MAX, "combine buffer must fit in the ring");
+  static_assert(4 * YBYTES <= 2 * STAGE_MAX, "combine buffer must fit in the ring");   // (so it ends below the resident panels)
+  // ring loads a resident panel saves per latent step: the relu-layer panels exist without the ffn embedding only, the mixer panel
+  // AM is multiplied once per head and only in the latent-split variant (the z-fold has it folded into W_zh).  Single-stage panels
+  // only: a two-stage one (fp32, D = 128: 64 KB) would take all the room for one panel, and unrolled over both stages without a
+  // barrier between them its GEMM spills (84-356 bytes of scratch per lane where the streamed kernel has none)
+  static constexpr int PANEL = PanelCfg<D / 32, D / 16, BF16>::BYTES, SPP = PanelCfg<D / 32, D / 16, BF16>::SPP;
+  static constexpr int ONE = SPP == 1 ? 1 : 0;
+  static constexpr int SAVED[RP_COUNT] = {FFN ? 0 : ONE, FFN ? 0 : ONE, ONE, ZFOLD ? 0 : H * ONE};
+  static constexpr int BYTES[RP_COUNT] = {PANEL, PANEL, PANEL, PANEL};
+  static constexpr unsigned SET = RES && RESIDENT <= LDS_PER_CU ? pair_resident_set(SAVED, BYTES, LDS_PER_CU - RESIDENT) : 0u;
+  static constexpr bool has(int p) { return SET >> p & 1u; }
+  static constexpr int off(int p) { return pair_resident_end(SET, BYTES, p, RESIDENT); }    // byte offset of resident panel p
+  static constexpr int TOTAL = pair_resident_end(SET, BYTES, RP_COUNT, RESIDENT);
+  static_assert(TOTAL <= LDS_PER_CU, "K2's LDS (ring + constants + resident panels) exceeds one CU's");
 };
 
 // ZFOLD: qg = 8 (every wave walks all latents, the 8 waves in step), and per head the gamma/beta GEMM, FiLM
@@ -95,13 +137,14 @@ template <int D, int H, bool BF16, int NW, bool FFN = false> struct PairSmem {
 // carries no switch over the invariant (as in K3, enf_pair_bwd.hip)
 // FFN: the ffn embedding (ENF_EMB_FFN) in both branches: h = gelu(W0^T inv + b0) takes the place of the relu layer's output, so
 // a latent step starts at the AF panel (the relu-layer panels aq1 / av1 and the relu masks do not exist)
-template <int D, int H, bool BF16, bool ZFOLD, bool MASKS, int INV = -1, bool FFN = false>
+// RES: keep the resident set of PairSmem in LDS for the workgroup's lifetime and stream only the other panels through the ring
+template <int D, int H, bool BF16, bool ZFOLD, bool MASKS, int INV = -1, bool FFN = false, bool RES = true>
 __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_kernel(PairFwdArgs A) {
   const int inv_id = INV >= 0 ? INV : A.inv;
   const int dx_ = INV >= 0 ? 2 : A.dx;
   using Cfg = PairCfg<D, BF16>;
   constexpr int NW = PairWaves<ZFOLD>::NW, NTH = 64 * NW;
-  using SM = PairSmem<D, H, BF16, NW, FFN>;
+  using SM = PairSmem<D, H, BF16, NW, FFN, ZFOLD, RES && NW == NWAVES>;
   constexpr int KB = Cfg::KB, NT = Cfg::NT;
   constexpr int ST_DD = Cfg::DD::STAGE, ST_GB = Cfg::GB::STAGE, PANEL_GB = Cfg::GB::BYTES, PANEL_DD = Cfg::DD::BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -140,9 +183,26 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   for (int i = tid; i < SM::EW; i += NTH) { c_acq[i] = G(A.L.acq)[i]; c_acv[i] = G(A.L.acv)[i]; }
 
   const unsigned pQ1 = (unsigned)A.L.aq1, pV1 = (unsigned)A.L.av1, pF = (unsigned)A.L.af, pGB = (unsigned)A.L.agb, pM = (unsigned)A.L.am;
-  const unsigned pFirst = FFN ? pF : pQ1;      // the first panel of a latent step
   Pipe P;
   P.rs = make_blob_rsrc(blob, (unsigned)A.L.total);
+  // ---- resident panels -> LDS, once per workgroup: retired by the wait + barrier of the first first_stage below
+  constexpr bool rQ1 = SM::has(RP_Q1), rV1 = SM::has(RP_V1), rF = SM::has(RP_F), rM = SM::has(RP_M);
+  constexpr int oQ1 = SM::off(RP_Q1), oV1 = SM::off(RP_V1), oF = SM::off(RP_F), oM = SM::off(RP_M);
+  {
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    if constexpr (rQ1) resident_load<PANEL_DD, NW>(P.rs, pQ1, smem + oQ1, wv, lane);
+    if constexpr (rV1) resident_load<PANEL_DD, NW>(P.rs, pV1, smem + oV1, wv, lane);
+    if constexpr (rF) resident_load<PANEL_DD, NW>(P.rs, pF, smem + oF, wv, lane);
+    if constexpr (rM) resident_load<PANEL_DD, NW>(P.rs, pM, smem + oM, wv, lane);
+  }
+  // The ring carries the streamed panels only, each stage naming the next STREAMED one.  A step multiplies in the order
+  // Q1, V1, F (positions 0, 1, 2; the ffn embedding has no Q1 / V1) and then per head W_zh (z-fold) or GB_h, M (latent-split);
+  // W_zh and GB_h always stream, so position 3 ends the search.  first_from(pos): the first streamed panel at or behind `pos`
+  // (`at3`: the one at position 3), ST_FROM<pos>: its stage size.
+  constexpr bool sQ1 = !FFN && !rQ1, sV1 = !FFN && !rV1, sF = !rF;
+  auto first_from = [&](int pos, unsigned at3) { return sQ1 && pos <= 0 ? pQ1 : sV1 && pos <= 1 ? pV1 : sF && pos <= 2 ? pF : at3; };
+  constexpr int ST_3 = ZFOLD ? ST_DD : ST_GB;
+  constexpr int ST_FROM0 = sQ1 || sV1 || sF ? ST_DD : ST_3, ST_FROM1 = sV1 || sF ? ST_DD : ST_3, ST_FROM2 = sF ? ST_DD : ST_3;
   float sm_m[H], sm_l[H], sm_c[H];     // softmax state against a per-column reference logit (the first one seen); fp32 accumulators
   f32x4 Y[H][NT];
   int b, n0;
@@ -163,10 +223,14 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * dx_, dx_, inv_id);
   if constexpr (ZFOLD) P.rs2 = make_blob_rsrc(A.wz + (size_t)b * A.Z * H * PANEL_DD, (unsigned)(A.Z * H * PANEL_DD));
   else P.rs2 = P.rs;
-  first_stage<ST_DD, NW>(P, ring, pFirst, wave, lane);
+  auto wzp = [&](int zz, int h_) { return STAGE_RS2 | (unsigned)((zz * H + h_) * PANEL_DD); };    // z-fold: W_zh of latent zz
+  first_stage<ST_FROM0, NW>(P, ring, first_from(0, ZFOLD ? wzp(z_lo, 0) : pGB), wave, lane);
   // the z-fold stages of this kernel: 2-slot staging (look-ahead and antiphase 3-slot staging measured 3 % / 2 % slower)
   auto zgemm = [&](f32x4 (&acc_)[NT], const Frags<BF16, KB>& F_, unsigned panel_, unsigned next_, bool active_, const float* bias_) {
     panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc_, F_, P, ring, panel_, next_, active_, lane, bias_);
+  };
+  auto rgemm = [&](f32x4 (&acc_)[NT], const Frags<BF16, KB>& F_, int off_, bool active_, const float* bias_) {
+    resident_gemm<KB, NT, BF16, INIT_ACC>(acc_, F_, smem + off_, active_, lane, bias_);
   };
 
 #pragma unroll
@@ -188,6 +252,8 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
   for (int it = 0; it < iters; ++it) {
     const int z = ZFOLD ? z_lo + it : z_first + it * ZS + zs;
     const bool active = z < z_end;
+    const unsigned at3 = ZFOLD ? wzp(z, 0) : pGB;                                              // this step's first per-head panel
+    const unsigned wrap = it + 1 < iters ? first_from(0, ZFOLD ? wzp(z + 1, 0) : pGB) : NO_STAGE;   // the next step's first stage
     const float* ltrow = A.lt + ((size_t)b * A.Z + (active ? z : A.Z - 1)) * ltstride;
     STAMP(0);
     // per-latent vectors u | v0 -> wave-private LDS
@@ -229,8 +295,8 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         make_frags<BF16, KB>(F, acc);
         K2_BIAS(acc, c_bq1);
         STAMP(1);
-        if constexpr (ZFOLD) zgemm(acc, F, pQ1, pV1, active, c_bq1);
-        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pQ1, pV1, active, lane, c_bq1);
+        if constexpr (rQ1) rgemm(acc, F, oQ1, active, c_bq1);
+        else panel_gemm<KB, NT, BF16, ST_FROM1, NW, INIT_ACC>(acc, F, P, ring, pQ1, first_from(1, at3), active, lane, c_bq1);
       }
       STAMP(2);
       const bool mread = FFN || K2_MASK_MODE == 2;                // wave-uniform; also: no relu to apply (ffn)
@@ -278,8 +344,8 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         make_frags<BF16, KB>(F, acc);
         K2_BIAS(acc, c_bv1);
         STAMP(4);
-        if constexpr (ZFOLD) zgemm(acc, F, pV1, pF, active, c_bv1);
-        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(acc, F, P, ring, pV1, pF, active, lane, c_bv1);
+        if constexpr (rV1) rgemm(acc, F, oV1, active, c_bv1);
+        else panel_gemm<KB, NT, BF16, ST_FROM2, NW, INIT_ACC>(acc, F, P, ring, pV1, first_from(2, at3), active, lane, c_bv1);
       }
       STAMP(5);
       const bool mread = FFN || K2_MASK_MODE == 2;
@@ -292,14 +358,8 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
       if (!mread) relu_frags<BF16, KB>(F);
       K2_BIAS(acc, c_bf);
       STAMP(6);
-      if constexpr (ZFOLD) {
-        const unsigned wz0 = STAGE_RS2 | (unsigned)(z * H * PANEL_DD);
-        // the look-ahead staging's next stage (that staging is removed): unused, but without it hipcc numbers this kernel's SGPRs differently
-        const unsigned after = H > 1 ? wz0 + PANEL_DD : (it + 1 < iters ? pQ1 : NO_STAGE);
-        (void)after;
-        zgemm(acc, F, pF, wz0, active, c_bf);
-      }
-      else panel_gemm<KB, NT, BF16, ST_GB, NW, INIT_ACC>(acc, F, P, ring, pF, pGB, active, lane, c_bf);
+      if constexpr (rF) rgemm(acc, F, oF, active, c_bf);
+      else panel_gemm<KB, NT, BF16, ST_3, NW, INIT_ACC>(acc, F, P, ring, pF, at3, active, lane, c_bf);
       STAMP(7);
       gelu_tiles<NT>(acc);
       float mu, rstd;
@@ -315,20 +375,21 @@ __global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_ker
         const unsigned wzh = STAGE_RS2 | (unsigned)((z * H + h) * PANEL_DD);
         K2_BIAS(v, zv + H * D + h * D);
         STAMP(10 + 4 * h);
-        const bool more = it + 1 < iters;
-        const unsigned nx1 = h + 1 < H ? wzh + PANEL_DD : (more ? pFirst : NO_STAGE);
-        zgemm(v, F, wzh, nx1, active, zv + H * D + h * D);
+        zgemm(v, F, wzh, h + 1 < H ? wzh + PANEL_DD : wrap, active, zv + H * D + h * D);
       } else {
         f32x4 dummy[1];
-        gb_panel<D, BF16, ST_DD, false, NW>(v, dummy, F, P, ring, pGB + h * PANEL_GB, pM, active, c_bgb + 2 * h * D,
-                                        zv + H * D + h * D, lane, quad);
+        const float* gbias = c_bgb + 2 * h * D, *v0 = zv + H * D + h * D;
+        if constexpr (!rM) gb_panel<D, BF16, ST_DD, false, NW>(v, dummy, F, P, ring, pGB + h * PANEL_GB, pM, active, gbias, v0, lane, quad);
+        else if (h + 1 < H) gb_panel<D, BF16, ST_GB, false, NW>(v, dummy, F, P, ring, pGB + h * PANEL_GB, pGB + (h + 1) * PANEL_GB, active, gbias, v0, lane, quad);
+        else gb_panel<D, BF16, ST_FROM0, false, NW>(v, dummy, F, P, ring, pGB + h * PANEL_GB, wrap, active, gbias, v0, lane, quad);
         STAMP(9 + 4 * h);
         Frags<BF16, KB> FV;
         make_frags<BF16, KB>(FV, v);
         K2_BIAS(v, c_bm);
         STAMP(10 + 4 * h);
-        if (h + 1 < H) panel_gemm<KB, NT, BF16, ST_GB, NW, INIT_ACC>(v, FV, P, ring, pM, pGB + (h + 1) * PANEL_GB, active, lane, c_bm);
-        else panel_gemm<KB, NT, BF16, ST_DD, NW, INIT_ACC>(v, FV, P, ring, pM, it + 1 < iters ? pFirst : NO_STAGE, active, lane, c_bm);
+        if constexpr (rM) rgemm(v, FV, oM, active, c_bm);
+        else if (h + 1 < H) panel_gemm<KB, NT, BF16, ST_GB, NW, INIT_ACC>(v, FV, P, ring, pM, pGB + (h + 1) * PANEL_GB, active, lane, c_bm);
+        else panel_gemm<KB, NT, BF16, ST_FROM0, NW, INIT_ACC>(v, FV, P, ring, pM, wrap, active, lane, c_bm);
       }
       STAMP(11 + 4 * h);
       gelu_tiles<NT>(v);
@@ -531,14 +592,26 @@ __global__ __launch_bounds__(256) void enf_shared_merge_kernel(const float* __re
   }
 }
 
-template <int D, int H, bool BF16, bool ZFOLD, bool MASKS = false, int INV = -1, bool FFN = false>
+#ifdef ENF_TEST_HOOKS
+// Test library only: enf_test_pair_fwd_streamed(1) makes every following pair forward run with an EMPTY resident set (all panels
+// through the ring), the reference tests/test_gpu_resident_panels.py compares the resident kernels with; (0) switches back.
+static int g_test_streamed = 0;
+extern "C" int enf_test_pair_fwd_streamed(int on) { const int was = g_test_streamed; g_test_streamed = on != 0; return was; }
+#endif
+
+template <int D, int H, bool BF16, bool ZFOLD, bool MASKS = false, int INV = -1, bool FFN = false, bool RES = true>
 static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
   if constexpr (!MASKS && !FFN) {
     if (A.mask_mode) return launch_pair_fwd<D, H, BF16, ZFOLD, true>(A, st);       // (the masked passes keep the run-time invariant)
   }
+#ifdef ENF_TEST_HOOKS
+  if constexpr (RES) {
+    if (g_test_streamed) return launch_pair_fwd<D, H, BF16, ZFOLD, MASKS, INV, FFN, false>(A, st);
+  }
+#endif
   constexpr int NW = PairWaves<ZFOLD>::NW;
-  using SM = PairSmem<D, H, BF16, NW, FFN>;
-  auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV, FFN>;
+  using SM = PairSmem<D, H, BF16, NW, FFN, ZFOLD, RES && NW == NWAVES>;
+  auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV, FFN, RES>;
   static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
   if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
   dim3 grid((A.N + 16 * A.qg - 1) / (16 * A.qg), A.B);

@@ -335,6 +335,16 @@ def _lecun(gen, n_in, n_out, device, bias=True):
     return p
 
 
+def _collect_before_capture():
+    """Run Python's cycle collector before a hipGraph capture begins.  Captured callables of an earlier trainer are cyclic garbage
+    (torch.cuda.make_graphed_callables wraps each in a class defined on the fly, and a class is only ever freed by the cycle
+    collector), so their CUDAGraph objects and pool memory are destroyed whenever a collection happens to run -- and inside a
+    capture (global error mode) that destruction is an illegal call in a destructor: the process aborts.  torch.cuda.graph
+    collected here itself up to torch 2.9; it no longer does unless torch.compiler.config.force_cudagraph_gc is set."""
+    import gc
+    gc.collect()
+
+
 def _flatten_tree(tree):
     """Leaves of a nested dict in sorted-key order, and the function that rebuilds the dict from such a list."""
     def leaves(t):
@@ -462,6 +472,7 @@ class PonitaODEGen:
         those of the sample ``latents``; ``params`` are read in place (later in-place updates are seen, new tensors are
         not).  No autograd: use ``apply`` for training."""
         static_in = tuple(None if v is None else v.detach().clone() for v in latents)
+        _collect_before_capture()
         with torch.no_grad():
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -498,6 +509,7 @@ class PonitaODEGen:
 
         fresh = lambda t: t.detach().clone().requires_grad_(True)       # own input buffers per capture: a backward may read them
         samples = tuple((fresh(p0), fresh(a0), *leaves) for _ in range(n))
+        _collect_before_capture()
         graphed = torch.cuda.make_graphed_callables((fn,) * n, samples, allow_unused_input=True)
         graphed = graphed if isinstance(graphed, tuple) else (graphed,)
 
