@@ -234,8 +234,12 @@ def _bind(path, test_hooks):
     lib.enf_backward_weights_scratch_bytes_ex.argtypes = [dp, ci, cu]
     lib.enf_backward_weights_ex.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]
     if test_hooks:
-        for name in ("enf_debug_gemm", "enf_debug_pack", "enf_test_read_wave_sums", "enf_test_pair_fwd_streamed"):
+        for name in ("enf_debug_gemm", "enf_debug_pack", "enf_test_read_wave_sums", "enf_test_pair_fwd_streamed",
+                     "enf_test_tail_active_waves", "enf_test_tail_parts", "enf_test_tail"):
             getattr(lib, name).restype = ci
+        lib.enf_test_tail_active_waves.argtypes = [ci]      # 1, 2, 4, 8: the tail launches run with that many active waves; 0: the launcher's rule; returns the previous setting
+        lib.enf_test_tail_parts.argtypes = [dp]
+        lib.enf_test_tail.argtypes = [dp, vp, ci, ci, vp, vp, vp, ci] + [vp] * 8      # one tail launch on the caller's buffers (csrc/enf_tail.hip)
         lib.enf_test_pair_fwd_streamed.argtypes = [ci]      # 1: the forward pair kernels run with an empty resident set; returns the previous setting
         lib.enf_debug_gemm.argtypes = [vp, vp, vp, ci, ci, ci, vp]
         lib.enf_debug_pack.argtypes = [vp, vp, ci, ci, ci, vp]

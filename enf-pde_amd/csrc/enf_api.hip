@@ -320,14 +320,13 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
     if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   }
   if (sbwd) {
-    // signal 0's tail forward (pre-activations stashed), the loss of that one row against all B targets and weights with d out
-    // (B, N), the unit-seeded tail backward, then the one pair pass contracted with d out.  d out and the row of outputs borrow the
-    // d ybar region behind signal 0's rows, which nothing else of this step uses: [N HD | d out: B N | out: N].
+    // signal 0's tail forward and unit-seeded tail backward in one launch (the seed does not depend on the loss), the loss of that one
+    // row against all B targets and weights with d out (B, N), then the one pair pass contracted with d out.  d out and the row of
+    // outputs borrow the d ybar region behind signal 0's rows, which nothing else of this step uses: [N HD | d out: B N | out: N].
     float* dout = c.F(W.dybar) + (size_t)m.N * m.HD;
     float* out1 = dout + (size_t)m.B * m.N;
-    if ((rc = enf_launch_tail(m1, c.L, c.blob, c.F(W.ybar), out1, nullptr, nullptr, nullptr, c.F(W.tail_act), 0, 1, st))) return rc;
+    if ((rc = enf_launch_tail_fwd_seed(m1, c.L, c.blob, c.F(W.ybar), out1, 0, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
     if ((rc = enf_launch_mse_shared(out1, target, weight, m.B, m.N, grad_scale, dout, loss, st))) return rc;
-    if ((rc = enf_launch_tail_seed(m1, c.L, c.blob, c.F(W.ybar), 0, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
     if ((rc = enf_side_join_pending(st, workspace))) return rc;
     if ((rc = enf_launch_pair_bwd_shared(m, c.L, c.blob, x, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), dout, c.F(W.dlt),
                                          c.ws + W.wzt, c.F(W.wzb), st)))

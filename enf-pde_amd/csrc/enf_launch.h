@@ -176,6 +176,10 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
 // no d out in memory; `act` holds the pre-activations a forward with opt & 1 stashed; writes d ybar and delta
 int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
                          float* act, hipStream_t st);
+// forward chain with the stash (and `out`, if given) and the seeded backward in ONE launch (the shared-latent fit step): the results of
+// enf_launch_tail(.., opt = 1) followed by enf_launch_tail_seed, bit for bit
+int enf_launch_tail_fwd_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
+                             float* delta, float* act, hipStream_t st);
 // the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->
 // backward chain -> d ybar, delta
 // weight: NULL, or one loss weight per query (B N floats, include/enf_hip.h "Weighted loss"); per_value: `weight` (not NULL) holds one

@@ -59,7 +59,7 @@ DEV void* k3_store_ptr(const PairBwdArgs& A, int i) {
 }
 
 // Debug build only (-DENF_STAMPS): s_memtime stamps of the first tiles of one workgroup (scripts/stamps_k3.py)
-#ifdef ENF_STAMPS
+#if defined(ENF_STAMPS) && !defined(ENF_PAIR_BWD_KERNEL_ONLY)
 __device__ unsigned long long enf_stamps_bwd[8 * 4 * 24];
 #define BSTAMP(k)                                                                                             \
   do {                                                                                                        \
@@ -505,11 +505,27 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       }
     };
     auto shared_add = [&](int off, const f32x4& g, bool cols) {
-      if (!(SHARED && tvalid && active && cols)) return;
+      if (!(SHARED && active && cols)) return;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int sb = 16 * (int)blockIdx.z + 4 * quad + j;
         if (sb < A.SB) atomicAdd(A.dlt + ((size_t)sb * A.Z + bz) * ltstride + off, g[j]);
+      }
+    };
+    // SHARED: the eight waves of the workgroup own the same latent, so their result tiles are added through LDS first and an element
+    // gets ONE atomic per workgroup.  A wave parks a group of at most NT tiles in its slab of the LACC region (tile s at 1 KB s + 16 lane:
+    // conflict-free b128; zeros from a wave without a tile); behind a workgroup barrier wave w adds tile w over the slabs in wave order
+    // and hands the sum to shared_add.  A barrier must pass between a group's reduce and the next group's first park.
+    auto shared_park = [&](int s, const f32x4& g) {
+      *reinterpret_cast<f32x4*>(smem + SM::LACC + (wave * NT + s) * 1024 + lane * 16) = tvalid ? g : f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    auto shared_reduce = [&](int ns, auto&& off_of, bool cols) {
+      for (int s = wave; s < ns; s += NW) {
+        const char* t0 = smem + SM::LACC + s * 1024 + lane * 16;
+        f32x4 v = *reinterpret_cast<const f32x4*>(t0);
+#pragma unroll
+        for (int w = 1; w < NW; ++w) v += *reinterpret_cast<const f32x4*>(t0 + w * NT * 1024);
+        shared_add(off_of(s), v, cols);
       }
     };
 
@@ -683,13 +699,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
                   f32x4 g = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                   for (int i = 0; i < 4; ++i) g = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[i], af[i] * dvf[mt][i], g, 0, 0, 0);
-                  shared_add(enf_lt_off_v0(H, D) + h * D + 16 * mt + col, g, true);
+                  shared_park(mt, g);
                 } else {
                   const f32x2 p2 = __builtin_elementwise_fma(hi2(af), hi2(dvf[mt]), lo2(af) * lo2(dvf[mt]));
                   part[mt] = p2[0] + p2[1];
                 }
               });
-          if constexpr (!SHARED) lacc_flush((H + h) * NT, part);
+          if constexpr (SHARED) shared_reduce(NT, [&](int s) { return enf_lt_off_v0(H, D) + h * D + 16 * s + col; }, true);   // (behind the stage's barrier)
+          else lacc_flush((H + h) * NT, part);
         }
         BSTAMP(6 + 6 * h);
       }
@@ -959,6 +976,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
 #pragma unroll
           for (int i = 0; i < 4; ++i) adl[h][i] = ad[i] * dl[h][i];
       }
+      constexpr int UCH = NT / H;           // SHARED: out-tiles per parked chunk of d u (slot h UCH + mt % UCH)
+      static_assert(!SHARED || NT % H == 0, "d u chunks");
+      auto u_off = [&](int c) { return [&, c](int s) { return enf_lt_off_u(H, D) + (s / UCH) * D + 16 * (c * UCH + s % UCH) + col; }; };
       // flipped tiles hold feature 16 mt + col of queries 4 quad + i: their mask bits sit in the words of lanes
       // (col >> 2) * 16 + 4 quad + i, bit 4 mt + (col & 3)
       unsigned mflip[4] = {0u, 0u, 0u, 0u};
@@ -984,14 +1004,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
                 g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][1], r1, g, 0, 0, 0);
                 g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][2], r2, g, 0, 0, 0);
                 g = __builtin_amdgcn_mfma_f32_16x16x4f32(adl[h][3], r3, g, 0, 0, 0);
-                shared_add(enf_lt_off_u(H, D) + h * D + 16 * mt + col, g, true);
+                // the H tiles of NT / H out-tiles fill the slab: a chunk that is not the last is reduced here, between two barriers
+                // of its own (every wave runs this epilogue); the last one behind the stage's closing barrier
+                shared_park(h * UCH + mt % UCH, g);
+                if (h == H - 1 && mt % UCH == UCH - 1 && mt != NT - 1) {
+                  __syncthreads();
+                  shared_reduce(NT, u_off(mt / UCH), true);
+                  __syncthreads();
+                }
               } else {
                 const f32x2 p2 = __builtin_elementwise_fma(f32x2{r2, r3}, f32x2{dl[h][2], dl[h][3]}, f32x2{r0, r1} * f32x2{dl[h][0], dl[h][1]});
                 upart[h][mt] = p2[0] + p2[1];
               }
             }
           }, c_bq1);                                                                                             // a1
-      if constexpr (!SHARED) {
+      if constexpr (SHARED) shared_reduce(NT, u_off(H - 1), true);
+      else {
 #pragma unroll
         for (int h = 0; h < H; ++h) {
           lacc_flush(h * NT, upart[h]);
@@ -1053,7 +1081,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         g = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[i], bv, g, 0, 0, 0);
       }
       const int off = col < H ? enf_lt_off_c(H, D) + col : col < H + 4 ? enf_lt_off_pose(H, D) + col - H : enf_lt_off_wcoef(H, D);
-      shared_add(off, g, col < H + 5);
+      // (the d E_q stage's barrier lies between the last d u reduce and this park; the next tile's first park is stages away)
+      shared_park(0, g);
+      __syncthreads();
+      shared_reduce(1, [&](int) { return off; }, col < H + 5);
     } else
     if (quad == 0) {
       float dwin = 0.f;
@@ -1206,6 +1237,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
   WSTAMP(3);
 }
 
+// (enf_pair_bwd_shared.hip includes this file for the kernel template alone: its SHARED instantiations are a translation unit of their
+// own, because hipcc allocates the registers of the instantiations below differently when they share one with them)
+#ifndef ENF_PAIR_BWD_KERNEL_ONLY
 // Deterministic mode, d lt: dlt[r][e] = part[0][r][e] + ... + part[nsplit - 1][r][e] in that order for the fields K3's epilogue
 // writes (u, v0, pose, wcoef, c, and with `ext` the 11 ext slots), zero elsewhere.  OVERWRITES dlt: no zero-fill is needed.
 __global__ __launch_bounds__(256) void enf_dlt_reduce_kernel(const float* __restrict__ part, int nsplit, long long rows, int H, int D,
@@ -1245,43 +1279,6 @@ static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
   if (ZF && A.xcd_remap) grid = dim3(A.B * A.Z * A.nsplit, 1);
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), SM::TOTAL, st, A);
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
-
-template <int D, int H, bool BF16, int INV = -1>
-static int launch_pair_bwd_shared(const PairBwdArgs& A, hipStream_t st) {
-  using SM = PairBwdSmem<D, H, BF16, false>;
-  auto kern = enf_pair_bwd_kernel<D, H, BF16, false, true, INV, false, true>;
-  static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
-  if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3(A.Z, A.nsplit, (A.SB + 15) / 16), dim3(NTHREADS), SM::TOTAL, st, A);
-  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
-
-// The shared-latent backward (enf_layout.h: enf_shared_backward_rule; `m` is the whole batch's): one pass over signal 0's (N x Z) pairs
-// on the unit-seeded dybar (N, HD) / delta (N, H), contracted with dout (B, N) into all B Z rows of `dlt` (added to: the caller zeroes
-// them).  x, lt, lse, wzt, wzb: signal 0's rows.  The instantiations are those of enf_pair_bwd_shared_exists.
-int enf_launch_pair_bwd_shared(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, const float* lt, const float* lse,
-                               const float* dybar, const float* delta, const float* dout, float* dlt, const char* wzt, const float* wzb,
-                               hipStream_t st) {
-  if (!enf_pair_bwd_shared_exists(m) || !enf_pair_bwd_zfold_fits(m) || !wzt || !wzb || !dout) return ENF_EUNSUPPORTED;
-  PairBwdArgs A;
-  A.dxq = nullptr; A.part = nullptr; A.dxpart = nullptr; A.masks = nullptr; A.mask_B = 1; A.mask_b0 = 0;
-  A.wzt = wzt; A.wzb = wzb; A.inv_d = 1.0f / (float)m.Dt;
-  A.x = x; A.x_bstride = 0; A.lt = lt; A.blob = blob; A.L = L; A.lse = lse; A.dybar = dybar; A.delta = delta;
-  A.dlt = dlt; A.B = 1; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
-  A.nsplit = enf_pair_bwd_shared_nsplit(m); A.xcd_remap = 0;
-  A.dout = dout; A.SB = m.B;
-  if (m.bf16 && m.dx == 2) {      // the invariant as a compile-time constant, as for the per-signal kernels of the shipped configs
-    if (m.D == 128 && m.H == 2 && m.inv == ENF_INV_REL_POS_PERIODIC) return launch_pair_bwd_shared<128, 2, true, ENF_INV_REL_POS_PERIODIC>(A, st);
-    if (m.D == 64 && m.H == 2 && m.inv == ENF_INV_PONITA) return launch_pair_bwd_shared<64, 2, true, ENF_INV_PONITA>(A, st);
-  }
-#define ENF_CASE(DD, HH) \
-  if (m.D == DD && m.H == HH) return m.bf16 ? launch_pair_bwd_shared<DD, HH, true>(A, st) : launch_pair_bwd_shared<DD, HH, false>(A, st);
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
 }
 
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor); read by the STORE instantiation only
@@ -1375,3 +1372,4 @@ static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blo
 #undef ENF_CASE
   return ENF_EUNSUPPORTED;
 }
+#endif  // ENF_PAIR_BWD_KERNEL_ONLY

@@ -11,6 +11,7 @@
 // delta[n,h] = sum_d d(ybar)[n,h,d] * ybar[n,h,d]  (the softmax-backward row constant).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 #include "enf_launch.h"
 #define ENF_PIPE_ONE_RS 1      // the tail streams from the weight blob only (enf_device.h: stage_issue_p)
 #include "enf_device.h"
@@ -94,7 +95,8 @@ template <int KBIN, int MTOUT, bool BF16> struct Pan {
 struct NoPan { static constexpr int SPP = 0, STAGE = 0; };
 
 // One stage step: issue the stage two ahead (own panel, else next panel N1, else the one after, N2), multiply, wait, barrier.
-template <int SP, int KBIN, int MTOUT, bool BF16, typename N1, typename N2, int INIT>
+// ACTIVE false (the code path of a wave without queries, tail_cadence): issue this wave's share of the stage, wait, meet the barrier.
+template <int SP, int KBIN, int MTOUT, bool BF16, typename N1, typename N2, int INIT, bool ACTIVE>
 DEV void la2_step(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned panel, unsigned n1, unsigned n2,
                   int lane, const float* bias) {
   using C = PanelCfg<KBIN, MTOUT, BF16>;
@@ -104,17 +106,17 @@ DEV void la2_step(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char
   if constexpr (AHEAD < 0) la2_issue<C::STAGE>(P, panel + (SP + 2) * C::STAGE, ring, slot2, lane);
   else if constexpr (AHEAD < N1::SPP) la2_issue<N1::STAGE>(P, n1 + AHEAD * N1::STAGE, ring, slot2, lane);
   else if constexpr (AHEAD == N1::SPP && N1::SPP <= 1 && N2::STAGE > 0) la2_issue<N2::STAGE>(P, n2, ring, slot2, lane);
-  gemm_stage<BF16, KBIN, C::MTS, INIT>(&acc[SP * C::MTS], F, ring + P.cur * STAGE_MAX, lane, bias + 16 * SP * C::MTS);
+  if constexpr (ACTIVE) gemm_stage<BF16, KBIN, C::MTS, INIT>(&acc[SP * C::MTS], F, ring + P.cur * STAGE_MAX, lane, bias + 16 * SP * C::MTS);
   wait_vm<La2Cnt<ISSUED>::K>();
   __syncthreads();
   P.cur = (P.cur + 1) % 3;
 }
-template <int KBIN, int MTOUT, bool BF16, typename N1, typename N2, int INIT = INIT_ACC>
+template <int KBIN, int MTOUT, bool BF16, typename N1, typename N2, bool ACTIVE = true, int INIT = INIT_ACC>
 DEV void panel_gemm_la2(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned panel, unsigned n1,
                         unsigned n2, int lane, const float* bias = nullptr) {
   using C = PanelCfg<KBIN, MTOUT, BF16>;
   static_assert(C::SPP <= 8, "unrolled by hand");
-#define LA2_STEP(SP_) if constexpr (C::SPP > SP_) la2_step<SP_, KBIN, MTOUT, BF16, N1, N2, INIT>(acc, F, P, ring, panel, n1, n2, lane, bias);
+#define LA2_STEP(SP_) if constexpr (C::SPP > SP_) la2_step<SP_, KBIN, MTOUT, BF16, N1, N2, INIT, ACTIVE>(acc, F, P, ring, panel, n1, n2, lane, bias);
   LA2_STEP(0) LA2_STEP(1) LA2_STEP(2) LA2_STEP(3) LA2_STEP(4) LA2_STEP(5) LA2_STEP(6) LA2_STEP(7)
 #undef LA2_STEP
 }
@@ -132,11 +134,11 @@ DEV void la2_first(Pipe& P, char* ring, unsigned a, unsigned b, int wave, int la
   __syncthreads();
 }
 // dispatch: LA2 or the 2-slot panel_gemm
-template <bool LA2, int KBIN, int MTOUT, bool BF16, typename N1, typename N2, int NEXT_BYTES>
+template <bool LA2, int KBIN, int MTOUT, bool BF16, typename N1, typename N2, int NEXT_BYTES, bool ACTIVE = true>
 DEV void tail_gemm(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned panel, unsigned n1, unsigned n2,
                    int lane) {
-  if constexpr (LA2) panel_gemm_la2<KBIN, MTOUT, BF16, N1, N2>(acc, F, P, ring, panel, n1, n2, lane);
-  else panel_gemm<KBIN, MTOUT, BF16, NEXT_BYTES>(acc, F, P, ring, panel, n1, true, lane);
+  if constexpr (LA2) panel_gemm_la2<KBIN, MTOUT, BF16, N1, N2, ACTIVE>(acc, F, P, ring, panel, n1, n2, lane);
+  else panel_gemm<KBIN, MTOUT, BF16, NEXT_BYTES>(acc, F, P, ring, panel, n1, ACTIVE, lane);
 }
 
 // Forward chain for this wave's 16 queries.  o4 = the (padded) 32 network outputs.
@@ -212,6 +214,47 @@ DEV void tail_consts(float* cst, const char* blob, const EnfLayout& L, int tid) 
   for (int i = tid; i < 32; i += NTHREADS) cst[2 * HD + 2 * D + i] = G(L.bO4)[i];
 }
 
+// The code path of a wave WITHOUT queries in the kernels with fewer than NWAVES active waves (LA2 only): its part of the constants, then
+// the stage cadence of the kernel's whole chain -- this wave's share of every LDS-DMA stage, the wait, the barrier -- and nothing else:
+// no load, no store, no MFMA, no epilogue.  FWD: the forward chain (tail_forward); BWD: the backward chain of enf_tail_bwd_kernel behind
+// it, or alone.  The GEMM calls below are those of the two chains, panel for panel, with the same look-ahead arguments: they must
+// change together (tests/test_gpu_tail_active_waves.py compares every form with the eight-wave kernel, whose waves all run the chain).
+// The waves with queries run the kernel's own code, which is the eight-wave kernel's, instruction for instruction.
+template <int D, int H, bool BF16, bool FWD, bool BWD>
+DEV void tail_cadence(const TailArgs& A, char* smem) {
+  using T = TailCfg<D, H, BF16>;
+  constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH;
+  using PTB = Pan<KBH, NTH, BF16>; using PO0 = Pan<KBH, NT, BF16>; using PO2 = Pan<KB, NT, BF16>; using PO4 = Pan<KB, 2, BF16>;
+  using PG4 = Pan<1, NT, BF16>; using PG2 = Pan<KB, NT, BF16>; using PG0 = Pan<KB, NTH, BF16>; using PGH = Pan<KBH, NTH, BF16>;
+  using NX1 = std::conditional_t<BWD, PG4, NoPan>; using NX2 = std::conditional_t<BWD, PG2, NoPan>;
+  char* ring = smem;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const EnfLayout& L = A.L;
+  tail_consts<D, H, BF16>(reinterpret_cast<float*>(smem + 3 * STAGE_MAX), A.blob, L, tid);
+  Pipe P;
+  P.rs = make_blob_rsrc(A.blob, (unsigned)L.total);
+  P.rs2 = P.rs;
+  __syncthreads();
+  f32x4 a[NTH], c[NT], o4[2];            // never read: ACTIVE is false in every call
+  Frags<BF16, KBH> FH; Frags<BF16, KB> FD; Frags<BF16, 1> F1;
+  const unsigned next = BWD ? (unsigned)L.gto4 : NO_STAGE, next2 = BWD ? (unsigned)L.gto2 : NO_STAGE;
+  if constexpr (FWD) {
+    la2_first<PTB, PTB>(P, ring, (unsigned)L.atb, (unsigned)L.atf1, wave, lane);
+    tail_gemm<true, KBH, NTH, BF16, PTB, PO0, T::ST_TB, false>(a, FH, P, ring, (unsigned)L.atb, (unsigned)L.atf1, (unsigned)L.ato0, lane);
+    tail_gemm<true, KBH, NTH, BF16, PO0, PO2, T::ST_O0, false>(a, FH, P, ring, (unsigned)L.atf1, (unsigned)L.ato0, (unsigned)L.ato2, lane);
+    tail_gemm<true, KBH, NT, BF16, PO2, PO4, T::ST_O2, false>(c, FH, P, ring, (unsigned)L.ato0, (unsigned)L.ato2, (unsigned)L.ato4, lane);
+    tail_gemm<true, KB, NT, BF16, PO4, NX1, T::ST_O4, false>(c, FD, P, ring, (unsigned)L.ato2, (unsigned)L.ato4, next, lane);
+    tail_gemm<true, KB, 2, BF16, NX1, NX2, 1024, false>(o4, FD, P, ring, (unsigned)L.ato4, next, next2, lane);
+  } else la2_first<PG4, PG2>(P, ring, (unsigned)L.gto4, (unsigned)L.gto2, wave, lane);
+  if constexpr (BWD) {
+    tail_gemm<true, 1, NT, BF16, PG2, PG0, T::ST_O2, false>(c, F1, P, ring, (unsigned)L.gto4, (unsigned)L.gto2, (unsigned)L.gto0, lane);
+    tail_gemm<true, KB, NT, BF16, PG0, PGH, T::ST_G0, false>(c, FD, P, ring, (unsigned)L.gto2, (unsigned)L.gto0, (unsigned)L.gtf1, lane);
+    tail_gemm<true, KB, NTH, BF16, PGH, PGH, T::ST_TB, false>(a, FD, P, ring, (unsigned)L.gto0, (unsigned)L.gtf1, (unsigned)L.gtb, lane);
+    tail_gemm<true, KBH, NTH, BF16, PGH, NoPan, T::ST_TB, false>(a, FH, P, ring, (unsigned)L.gtf1, (unsigned)L.gtb, NO_STAGE, lane);
+    tail_gemm<true, KBH, NTH, BF16, NoPan, NoPan, 1024, false>(a, FH, P, ring, (unsigned)L.gtb, NO_STAGE, NO_STAGE, lane);
+  }
+}
+
 // The fused loss of one wave's 16 queries (enf_loss.hip's arithmetic on the forward chain's outputs, in registers): this lane's share of
 // sum_o w (out - target)^2 and, in g0, d out = 2 w (out - target) inv_n gscale (gs = 2 inv_n gscale).  CW: `weight` holds one value per
 // output element, else nullptr or one per query.  A weight of 0 is a select, never 0 * target: the NaN of a missing value reaches neither
@@ -272,23 +315,35 @@ DEV float tail_err_reduce(float se, float* err, int q, bool qvalid, int quad, bo
   }
   return se;
 }
-DEV void tail_loss_add(float se, const TailArgs& A, int wave) {
-  if (A.loss_part) A.loss_part[blockIdx.x * NWAVES + wave] = se * A.inv_n;     // deterministic mode: summed in index order afterwards
+DEV void tail_loss_add(float se, const TailArgs& A, int qtile) {      // qtile: the wave's global query-tile index
+  if (A.loss_part) A.loss_part[qtile] = se * A.inv_n;     // deterministic mode: summed in index order afterwards
   else atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
 }
 
 // EVAL (1: unweighted or per-point weights, 2: per-channel weights; never with SAVE): the evaluation tail -- the epilogue forms err and,
 // with A.loss, the scalar loss from the output accumulators instead of storing `out` (enf_eval_loss): no backward chain, no stash, no
 // `out` in HBM.
-template <int D, int H, bool BF16, bool LA2, bool SAVE, int EVAL = 0>
+//
+// AW (active waves; 8, 4, 2 or 1): a launch whose grid would be far below the CU count runs workgroups in which only the first AW of
+// the eight waves carry queries (q0 = 16 AW blockIdx.x + 16 wave; tail_active_waves below picks AW).  A stage costs the same ~2.5 us
+// whether 4 or 64 workgroups run it -- the eight waves of a workgroup queue two per SIMD on one vector ALU and one LDS port between the
+// stage barriers -- so the same queries spread over 8 / AW times as many CUs finish every stage sooner.  The other waves leave for
+// tail_cadence: they keep issuing their share of every LDS-DMA stage and keep the wait / barrier cadence (stage_issue's piece split, the
+// 12-bit offsets and La2Cnt are those of eight waves) and run nothing else.  The waves with queries run the code below unchanged, so
+// their arithmetic does not depend on AW: the results are bit-equal.
+template <int D, int H, bool BF16, bool LA2, bool SAVE, int EVAL = 0, int AW = NWAVES>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
   static_assert(!(SAVE && EVAL != 0), "the evaluation tail has no backward to stash for");
+  static_assert(AW == NWAVES || (LA2 && (AW == 4 || AW == 2 || AW == 1)), "fewer active waves: small grids, the 3-slot ring");
   using T = TailCfg<D, H, BF16>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
   float* cst = reinterpret_cast<float*>(smem + (LA2 ? 3 : 2) * STAGE_MAX);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
-  const int q0 = blockIdx.x * (16 * NWAVES) + wave * 16;
+  if constexpr (AW < NWAVES) {
+    if (__builtin_amdgcn_readfirstlane(wave) >= AW) { tail_cadence<D, H, BF16, true, false>(A, smem); return; }
+  }
+  const int q0 = blockIdx.x * (16 * AW) + wave * 16;
   const int qi = min(q0 + col, A.NQ - 1);
   tail_consts<D, H, BF16>(cst, A.blob, A.L, tid);
   Pipe P;
@@ -310,7 +365,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
     f32x4 g0[2];       // (d out is not wanted: dead code)
     float se = tail_sq_err<EVAL == 2>(o4, g0, A, qi, qvalid, quad, 0.f);
     se = tail_err_reduce(se, A.err, q0 + col, qvalid, quad, A.loss != nullptr);
-    if (A.loss && lane == 0) tail_loss_add(se, A, wave);
+    if (A.loss && lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
   } else if (q0 + col < A.NQ) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -327,14 +382,19 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
 // outputs, backward chain: no `out` / `d out` round trip and two launches less between the pair kernels of an inner step.
 // CW (with LOSS): `weight` holds one value per output element (include/enf_hip.h, "Weighted loss": per-channel weights).  An
 // instantiation of its own: the per-point and the unweighted kernels keep their code.
-// SEED (never with RECOMP, WG or LOSS): the seeded backward of enf_field_grad -- d out is the unit vector e_o of output channel
+// SEED (never with WG or LOSS): the seeded backward of enf_field_grad -- d out is the unit vector e_o of output channel
 // o = A.seed (a run-time argument: one instantiation serves every channel), formed in registers where LOSS forms its gradient; no
 // `d out` is read and no (B, N, O) one-hot tensor exists.  The pre-activations come from the forward's stash.
-template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false, bool SEED = false>
+// SEED with RECOMP: the shared-latent fit step's tail in one kernel -- the unit seed does not depend on the loss, so the forward chain
+// (stash as ever, `out` stored where A.out is given) and the seeded backward chain need no launch between them.
+// AW: as in enf_tail_fwd_kernel.
+template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false, bool SEED = false,
+          int AW = NWAVES>
 __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   static_assert(!LOSS || RECOMP, "the fused loss needs the forward chain's outputs");
   static_assert(!CW || LOSS, "per-channel weights belong to the fused loss");
-  static_assert(!SEED || (!RECOMP && !WG && !LOSS), "the seeded backward reads the stash and writes d ybar and delta only");
+  static_assert(!SEED || (!WG && !LOSS), "the seeded backward writes d ybar and delta (and, with the forward chain, out) only");
+  static_assert(AW == NWAVES || (LA2 && !WG && (AW == 4 || AW == 2 || AW == 1)), "fewer active waves: small grids, the 3-slot ring");
   using T = TailCfg<D, H, BF16>;
   constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD;
   using PG4 = Pan<1, NT, BF16>; using PG2 = Pan<KB, NT, BF16>; using PG0 = Pan<KB, NTH, BF16>; using PGH = Pan<KBH, NTH, BF16>;
@@ -342,7 +402,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   char* ring = smem;
   float* cst = reinterpret_cast<float*>(smem + (LA2 ? 3 : 2) * STAGE_MAX);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
-  const int q0 = blockIdx.x * (16 * NWAVES) + wave * 16;
+  if constexpr (AW < NWAVES) {
+    if (__builtin_amdgcn_readfirstlane(wave) >= AW) { tail_cadence<D, H, BF16, RECOMP, true>(A, smem); return; }
+  }
+  const int q0 = blockIdx.x * (16 * AW) + wave * 16;
   const bool qvalid = q0 + col < A.NQ;
   const int qi = min(q0 + col, A.NQ - 1);
   // clamped (duplicate) queries write the same scratch values: benign
@@ -363,6 +426,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
     // its row with the query's own lane in another wave -- must not store: its late pre-activation would land on the finished row
     tail_forward<D, H, BF16, true, LA2, PG4, PG2>(o4, yrow, act, A.L, cst, P, ring, (unsigned)A.L.gto4, (unsigned)A.L.gto2, lane, quad,
                                                   A.inv_hd, !WG || qvalid);
+    if constexpr (SEED) {      // the forward's output row, for the loss kernel that follows
+      if (qvalid && A.out) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int o = 16 * t + 4 * quad + i;
+            if (o < A.O) A.out[(size_t)(q0 + col) * A.O + o] = o4[t][i];
+          }
+      }
+    }
   } else {      // the forward of this step stashed the pre-activations (enf_tail_fwd_kernel<.., SAVE>): start at the backward chain
     if constexpr (LA2) {
       __syncthreads();
@@ -376,7 +450,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   if constexpr (LOSS) {
     float se = tail_sq_err<CW>(o4, g0, A, qi, qvalid, quad, 2.0f * A.inv_n * A.gscale);
     se = tail_err_reduce(se, A.err, q0 + col, qvalid, quad);
-    if (lane == 0) tail_loss_add(se, A, wave);
+    if (lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
   } else if constexpr (SEED) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -501,42 +575,99 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
   if (qvalid) store_rows<NTH>(a, A.dybar + (size_t)qi * HD, quad);
 }
 
+// The active waves of a tail launch of nq queries (enf_tail_fwd_kernel): the largest AW whose grid ceil(tiles / AW) still reaches the
+// 256 CUs the shapes are tuned for, else 1.  512 queries: 32 workgroups of one active wave; 8192: 256 workgroups of two.
+static int tail_active_waves(int nq) {
+  const int tiles = (nq + 15) / 16;
+  for (int aw = NWAVES; aw > 1; aw >>= 1)
+    if ((tiles + aw - 1) / aw >= 256) return aw;
+  return 1;
+}
+// The fused-loss tail keeps eight active waves: on four (128 workgroups beside the fold kernel's 128) the step measured slower
+// (DESIGN.md section 5).  The test library has it in every AW, as one more form whose bits must not depend on AW.
+#ifdef ENF_TEST_HOOKS
+// Test library only: enf_test_tail_active_waves(aw) makes every following tail launch of a form that has the instantiation run with
+// `aw` active waves (1, 2, 4 or 8; 0: the launcher's own rule again).  Returns the previous setting.
+static int g_test_tail_aw = 0;
+extern "C" int enf_test_tail_active_waves(int aw) {
+  const int was = g_test_tail_aw;
+  g_test_tail_aw = (aw == 1 || aw == 2 || aw == 4 || aw == NWAVES) ? aw : 0;
+  return was;
+}
+constexpr bool TAIL_LOSS_AW_ALL = true;       // the fused loss in every AW (tests/test_gpu_tail_active_waves.py)
+#else
+constexpr bool TAIL_LOSS_AW_ALL = false;
+#endif
+
 template <int D, int H, bool BF16>
 static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false, bool eval = false, bool seeded = false) {
   const bool wg = bwd && A.tdel != nullptr;
   const bool fused_loss = bwd && A.target != nullptr;
   using T = TailCfg<D, H, BF16>;
-  dim3 grid((A.NQ + 16 * NWAVES - 1) / (16 * NWAVES));
+  // fewer active waves: the forward forms and the seeded backward forms.  Deterministic mode keeps eight (the partial-sum slots
+  // enf_launch_loss_sum reads are those of the 8-wave grid); so do the d out and weight-gradient backward.
+  int aw = NWAVES;
+  if ((!bwd || seeded) && !A.loss_part) aw = tail_active_waves(A.NQ);
+#ifdef ENF_TEST_HOOKS
+  if (g_test_tail_aw && !wg && !A.loss_part && (!bwd || seeded || fused_loss)) aw = g_test_tail_aw;
+#endif
+  dim3 grid((A.NQ + 16 * aw - 1) / (16 * aw));
   // few workgroups (at most one per CU): the deeper weight pipeline (LA2) instead of a second workgroup per CU
-  const bool la2 = grid.x <= 256;
+  const bool la2 = grid.x <= 256 || aw < NWAVES;
+  const int awi = aw == NWAVES ? 0 : aw == 4 ? 1 : aw == 2 ? 2 : 3;
   // opt: forward -> stash the pre-activations (SAVE); backward -> they are stashed, skip the recompute
-  // [fwd / bwd / bwd + WG / fused loss / fused loss + CW / evaluation / evaluation + CW / seeded bwd][la2][opt] (this function is one
-  // instantiation per D, H, BF16), one bit per device
-  static EnfAttrBits attr_done[8][2][2];
+  // [fwd / bwd / bwd + WG / fused loss / fused loss + CW / evaluation / evaluation + CW / seeded bwd][la2][opt][aw] (this function is
+  // one instantiation per D, H, BF16), one bit per device
+  static EnfAttrBits attr_done[8][2][2][4];
   auto go = [&](void (*kern_ptr)(TailArgs)) -> int {
     const int smem = la2 ? T::SMEM3 : T::SMEM;
     const int which = seeded ? 7 : eval ? (cw ? 6 : 5) : fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd);
-    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[which][la2][opt])) return ENF_ELAUNCH;
+    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[which][la2][opt][awi])) return ENF_ELAUNCH;
     hipLaunchKernelGGL(kern_ptr, grid, dim3(NTHREADS), smem, st, A);
     return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
   };
-  if (seeded) {    // the seeded backward: the stash is its only form (opt), d out = e_seed
-    if (!bwd || !opt || wg || fused_loss || eval || A.seed < 0 || A.seed >= A.O) return ENF_EINVAL;
-    return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, false, false, false, false, true>)
-               : go(enf_tail_bwd_kernel<D, H, BF16, false, false, false, false, false, true>);
+  // the instantiations with fewer active waves (3-slot ring only): K(AW) names the kernel
+#define ENF_TAIL_AW(K)                 \
+  if (aw == 4) return go(K(4));        \
+  if (aw == 2) return go(K(2));        \
+  if (aw == 1) return go(K(1));
+#define ENF_K_SEED_STASH(AW_) enf_tail_bwd_kernel<D, H, BF16, true, false, false, false, false, true, AW_>
+#define ENF_K_SEED_FWD(AW_) enf_tail_bwd_kernel<D, H, BF16, true, true, false, false, false, true, AW_>
+#define ENF_K_LOSS(AW_) enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, false, false, AW_>
+#define ENF_K_LOSS_CW(AW_) enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, true, false, AW_>
+#define ENF_K_EVAL(AW_) enf_tail_fwd_kernel<D, H, BF16, true, false, 1, AW_>
+#define ENF_K_EVAL_CW(AW_) enf_tail_fwd_kernel<D, H, BF16, true, false, 2, AW_>
+#define ENF_K_FWD(AW_) enf_tail_fwd_kernel<D, H, BF16, true, false, 0, AW_>
+#define ENF_K_FWD_SAVE(AW_) enf_tail_fwd_kernel<D, H, BF16, true, true, 0, AW_>
+  if (seeded) {    // the seeded backward, d out = e_seed: from the stash (opt), or behind its own forward chain, which also stores `out`
+    if (!bwd || wg || fused_loss || eval || A.seed < 0 || A.seed >= A.O) return ENF_EINVAL;
+    if (opt) {
+      ENF_TAIL_AW(ENF_K_SEED_STASH)
+      return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, false, false, false, false, true>)
+                 : go(enf_tail_bwd_kernel<D, H, BF16, false, false, false, false, false, true>);
+    }
+    ENF_TAIL_AW(ENF_K_SEED_FWD)
+    return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, false, false, true>)
+               : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, false, false, true>);
   }
   if (eval) {      // the evaluation tail: a forward instantiation whose epilogue forms err / the loss (same LA2 choice as the forward)
     if (bwd || opt || !A.target || (cw && !A.weight)) return ENF_EINVAL;
-    if (cw) return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 2>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 2>);
+    if (cw) {
+      ENF_TAIL_AW(ENF_K_EVAL_CW)
+      return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 2>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 2>);
+    }
+    ENF_TAIL_AW(ENF_K_EVAL)
     return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 1>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 1>);
   }
   if (fused_loss) {
     if (wg || opt) return ENF_EINVAL;
     if (cw) {
       if (!A.weight) return ENF_EINVAL;
+      if constexpr (TAIL_LOSS_AW_ALL) { ENF_TAIL_AW(ENF_K_LOSS_CW) }
       return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, true>)
                  : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, true, true>);
     }
+    if constexpr (TAIL_LOSS_AW_ALL) { ENF_TAIL_AW(ENF_K_LOSS) }
     return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, true>) : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, true>);
   }
   if (wg) {
@@ -547,8 +678,21 @@ static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bo
     if (la2) return opt ? go(enf_tail_bwd_kernel<D, H, BF16, true, false>) : go(enf_tail_bwd_kernel<D, H, BF16, true, true>);
     return opt ? go(enf_tail_bwd_kernel<D, H, BF16, false, false>) : go(enf_tail_bwd_kernel<D, H, BF16, false, true>);
   }
-  if (la2) return opt ? go(enf_tail_fwd_kernel<D, H, BF16, true, true>) : go(enf_tail_fwd_kernel<D, H, BF16, true, false>);
-  return opt ? go(enf_tail_fwd_kernel<D, H, BF16, false, true>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false>);
+  if (opt) {
+    ENF_TAIL_AW(ENF_K_FWD_SAVE)
+    return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, true>) : go(enf_tail_fwd_kernel<D, H, BF16, false, true>);
+  }
+  ENF_TAIL_AW(ENF_K_FWD)
+  return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false>);
+#undef ENF_TAIL_AW
+#undef ENF_K_SEED_STASH
+#undef ENF_K_SEED_FWD
+#undef ENF_K_LOSS
+#undef ENF_K_LOSS_CW
+#undef ENF_K_EVAL
+#undef ENF_K_EVAL_CW
+#undef ENF_K_FWD
+#undef ENF_K_FWD_SAVE
 }
 
 int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
@@ -576,18 +720,18 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
   return ENF_EUNSUPPORTED;
 }
 
-int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
-                         float* act, hipStream_t st) {
+static int tail_seed_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
+                            float* delta, float* act, bool stashed, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   TailArgs A;
   A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr; A.err = nullptr;
-  A.tdel = nullptr; A.out = nullptr; A.dout = nullptr;
+  A.tdel = nullptr; A.out = out; A.dout = nullptr;
   A.seed = seed;
   A.ybar = ybar; A.blob = blob; A.L = L; A.dybar = dybar; A.delta = delta; A.act = act;
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
 #define ENF_CASE(DD, HH)                                                                   \
   if (m.D == DD && m.H == HH)                                                              \
-    return m.bf16 ? launch_tail<DD, HH, true>(A, true, true, st, false, false, true) : launch_tail<DD, HH, false>(A, true, true, st, false, false, true);
+    return m.bf16 ? launch_tail<DD, HH, true>(A, true, stashed, st, false, false, true) : launch_tail<DD, HH, false>(A, true, stashed, st, false, false, true);
   ENF_CASE(128, 2)
   ENF_CASE(64, 2)
   ENF_CASE(128, 1)
@@ -595,6 +739,17 @@ int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob,
   ENF_CASE(64, 4)
 #undef ENF_CASE
   return ENF_EUNSUPPORTED;
+}
+
+int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
+                         float* act, hipStream_t st) {
+  return tail_seed_kernel(m, L, blob, ybar, nullptr, seed, dybar, delta, act, true, st);
+}
+// Forward chain (stash in `act`, `out` (B N, O) stored if given) and the seeded backward in one launch: what enf_launch_tail with the
+// stash followed by enf_launch_tail_seed compute, bit for bit.
+int enf_launch_tail_fwd_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
+                             float* delta, float* act, hipStream_t st) {
+  return tail_seed_kernel(m, L, blob, ybar, out, seed, dybar, delta, act, false, st);
 }
 
 int enf_tail_loss_parts(const EnfDims& m) {
@@ -640,3 +795,30 @@ static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* bl
 #undef ENF_CASE
   return ENF_EUNSUPPORTED;
 }
+
+#ifdef ENF_TEST_HOOKS
+// Test library only: one tail launch on the caller's buffers (tests/test_gpu_tail_active_waves.py).  ybar (B N, H D); act (B N,
+// 2 H D + 2 D + 2) is the stash.  form 0: forward -> out; 1: forward with the stash -> out, act; 2: evaluation -> err, *loss; 3: seeded
+// backward from the stash -> dybar, delta; 4: forward + seeded backward in one launch -> out, act, dybar, delta; 5: fused loss -> act,
+// dybar, delta, err, *loss.  weight: nullptr, one per query, or with per_value one per output value; loss_part: nullptr, or the
+// deterministic mode's partial sums (enf_tail_loss_parts floats); the caller zeroes *loss.
+extern "C" int enf_test_tail_parts(const EnfDesc* d) { return enf_check_desc(d) ? -1 : enf_tail_loss_parts(enf_dims(d)); }
+extern "C" int enf_test_tail(const EnfDesc* d, const void* packed, int form, int seed, const float* ybar, const float* target,
+                             const float* weight, int per_value, float* out, float* act, float* dybar, float* delta, float* err, float* loss,
+                             float* loss_part, void* stream) {
+  if (int rc = enf_check_desc(d)) return rc;
+  const EnfDims m = enf_dims(d);
+  const EnfLayout L = enf_layout(m);
+  const char* blob = (const char*)packed;
+  hipStream_t st = (hipStream_t)stream;
+  switch (form) {
+    case 0: return enf_launch_tail(m, L, blob, ybar, out, nullptr, nullptr, nullptr, nullptr, 0, 0, st);
+    case 1: return enf_launch_tail(m, L, blob, ybar, out, nullptr, nullptr, nullptr, act, 0, 1, st);
+    case 2: return enf_launch_tail_eval(m, L, blob, ybar, target, weight, per_value != 0, loss, err, st, loss_part);
+    case 3: return enf_launch_tail_seed(m, L, blob, ybar, seed, dybar, delta, act, st);
+    case 4: return enf_launch_tail_fwd_seed(m, L, blob, ybar, out, seed, dybar, delta, act, st);
+    case 5: return enf_launch_tail_loss(m, L, blob, ybar, target, weight, 1.0f, loss, dybar, delta, act, st, loss_part, per_value != 0, err);
+  }
+  return ENF_EINVAL;
+}
+#endif
