@@ -26,6 +26,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
+           "enf_field_tangent_workspace_bytes", "enf_field_tangent",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
@@ -225,6 +226,10 @@ def _bind(path, test_hooks):
     lib.enf_field_grad_workspace_bytes.argtypes = [dp, cu]
     lib.enf_field_grad.argtypes = [dp, vp, i64] + [vp] * 7 + [sz, cu, vp]
     lib.enf_query_vjp.argtypes = [dp, vp, i64] + [vp] * 8 + [sz, cu, vp]
+    # tendency fields (include/enf_hip.h, "Tendency fields"): p, a, sigma | dp, da, dsigma (each may be NULL) | blob, out | NULL, tan, workspace, stream
+    lib.enf_field_tangent_workspace_bytes.restype = sz
+    lib.enf_field_tangent_workspace_bytes.argtypes = [dp]
+    lib.enf_field_tangent.argtypes = [dp, vp, i64] + [vp] * 11
     lib.enf_pair_backward_scratch_bytes.restype = sz
     lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]
     lib.enf_pair_backward_ex2.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]

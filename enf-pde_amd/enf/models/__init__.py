@@ -567,6 +567,46 @@ class EquivariantCrossAttentionNeF:
         self._ws_touch(ws)
         return dx
 
+    # ------------------------------------------------------------------ tendency fields
+    @torch.no_grad()
+    def tangent(self, params, x, p, a, gaussian_window_size, dp=None, da=None, dwindow=None, return_out=True):
+        """The decode in forward mode along a latent direction, in one native call (include/enf_hip.h: enf_field_tangent):
+        tan[b, n, o] = sum_z d out[b, n, o] / d (p, a, window)[b, z, :] . (dp, da, dwindow)[b, z, :], returned as (out (B, N, O) or
+        None, tan (B, N, O)).  With (dp, da, dwindow) = the latent ODE's right-hand side this is d u / d t of the decoded field.
+        ``dp`` / ``da`` / ``dwindow`` have the shapes of p / a / the window (B, Z, 1) and must be float32 and contiguous on the
+        latents' device; each may be None (= zero), not all three.  ``dwindow`` of a model without a window contributes exactly zero.
+        No autograd graph is built and none of the inputs gets a gradient.  Every element is written once without atomics: equal
+        inputs give equal bits.  ``return_out`` False skips the store of the decode."""
+        if self.num_layers > 0:
+            raise NotImplementedError("tangent is built for num_layers = 0 (the fused decoder)")
+        if self.embedding_type != "rff":
+            raise NotImplementedError(f"tangent serves the rff embedding, not '{self.embedding_type}'")
+        name = self.cross_attn_invariant.name
+        if name in ("ball", "ball_lat", "ponita_full"):
+            raise NotImplementedError(f"tangent does not serve the '{name}' invariant (no tangent of the per-latent phase / rotation)")
+        if dp is None and da is None and dwindow is None:
+            raise ValueError("tangent needs at least one of dp, da, dwindow")
+        xb, xstride, p_, a_, s_ = self._field_grad_args("tangent", x, p, a, gaussian_window_size)
+        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
+        for what, t, shape in (("dp", dp, tuple(p_.shape)), ("da", da, tuple(a_.shape)), ("dwindow", dwindow, (B, Z, 1))):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape:
+                raise AssertionError(f"{what} has shape {tuple(t.shape)}, expected {shape}")
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous float32 tensor on {dev}")
+        if self._masks is not None:
+            raise NotImplementedError("tangent does not take relu masks")
+        lib = _lib.load()
+        packed = self.pack(params)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lambda d, flags: lib.enf_field_tangent_workspace_bytes(d))
+        out = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32) if return_out else None
+        tan = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32)
+        _lib.launch(dev, lib.enf_field_tangent, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(dp), _ptr(da),
+                    _ptr(dwindow), _ptr(packed), _ptr(out), _ptr(tan), _ptr(ws), st)
+        self._ws_touch(ws)
+        return out, tan
+
     # ------------------------------------------------------------------ relu masks (second-order terms by differences)
     def relu_mask_buffer(self, B, N, Z, device):
         """Device buffer for the relu masks of a (B, N, Z) problem (enf_relu_mask_bytes)."""

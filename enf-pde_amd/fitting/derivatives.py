@@ -2,6 +2,9 @@
 (EquivariantCrossAttentionNeF.jacobian, include/enf_hip.h: enf_field_grad) and the first-order operators built on it.
 
   decode_jacobian(...)   the counterpart of inner_loop.decode: (out, jac) on the full grid, chunking optional
+  decode_tangent(...)    (out, tan) on the full grid: the decode in forward mode along a latent direction
+                         (EquivariantCrossAttentionNeF.tangent, include/enf_hip.h: enf_field_tangent)
+  decode_tendency(...)   (u, du/dt) on the full grid for latents that follow dz/dt = ode_model(z)
   divergence / curl_2d / gradient_norm   operators on a Jacobian whose components are CARTESIAN
 
 The Jacobian is w.r.t. the coordinates as the model takes them.  For the planar invariants these are Cartesian and the operators
@@ -10,7 +13,7 @@ the metric factors, which are not applied here.
 """
 import torch
 
-__all__ = ["decode_jacobian", "divergence", "curl_2d", "gradient_norm"]
+__all__ = ["decode_jacobian", "decode_tangent", "decode_tendency", "divergence", "curl_2d", "gradient_norm"]
 
 
 def decode_jacobian(nef, nef_params, coords, p, a, window, chunk=None):
@@ -24,6 +27,30 @@ def decode_jacobian(nef, nef_params, coords, p, a, window, chunk=None):
         return nef.jacobian(nef_params, x, p, a, window)
     parts = [nef.jacobian(nef_params, x[:, i:i + chunk], p, a, window) for i in range(0, x.shape[1], chunk)]
     return torch.cat([o for o, _ in parts], dim=1), torch.cat([j for _, j in parts], dim=1)
+
+
+def decode_tangent(nef, nef_params, coords, p, a, window, dp, da, dwindow, chunk=None):
+    """(out (B, N, O), tan (B, N, O)) on the full grid: tan = the directional derivative of the decode along the latent direction
+    (dp, da, dwindow) -- shapes of p, a, window; ``None`` entries mean zero, not all three.  ``coords`` and ``chunk`` as in
+    decode_jacobian: the chunks are slices of the grid, every query's result is the unchunked call's, bit for bit."""
+    B = p.shape[0]
+    x = coords[None].expand(B, -1, -1) if coords.dim() == 2 else coords
+    if chunk is None:
+        return nef.tangent(nef_params, x, p, a, window, dp=dp, da=da, dwindow=dwindow)
+    parts = [nef.tangent(nef_params, x[:, i:i + chunk], p, a, window, dp=dp, da=da, dwindow=dwindow) for i in range(0, x.shape[1], chunk)]
+    return torch.cat([o for o, _ in parts], dim=1), torch.cat([t for _, t in parts], dim=1)
+
+
+def decode_tendency(nef, nef_params, ode_model, ode_params, coords, p, a, window, chunk=None):
+    """(u (B, N, O), du/dt (B, N, O)) on the full grid for latents that follow the latent ODE: dz/dt = ode_model.apply(ode_params,
+    (p, a, window)) is evaluated ONCE, without autograd, and pushed through the decoder by decode_tangent (du/dt = J_z dz/dt).
+    ``None`` entries of the ODE's output mean zero (an ODE that leaves the window alone returns None or zeros for it)."""
+    with torch.no_grad():
+        dz = ode_model.apply(ode_params, (p, a, window))
+    dp, da, dw = (None if v is None else v.detach().float().contiguous() for v in dz)
+    if dw is not None:
+        dw = dw.reshape(p.shape[0], p.shape[1], 1)
+    return decode_tangent(nef, nef_params, coords, p, a, window, dp, da, dw, chunk=chunk)
 
 
 def _check(jac, what):

@@ -468,6 +468,33 @@ int enf_query_vjp(const EnfDesc* d, const float* x, int64_t x_bstride, const flo
                   const void* packed, const float* dout /* (B,N,O) */, float* out /* (B,N,O) or NULL */, float* dx /* (B,N,dx) */,
                   void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
 
+/* Tendency fields (enf_field_tangent): the decode in FORWARD mode along a latent direction -- the Jacobian-vector product of the
+ * decoder with respect to its latents,
+ *     tan[b,n,o] = sum_z  d out[b,n,o] / d (p, a, sigma)[b,z,:]  .  (dp, da, dsigma)[b,z,:]        (B, N, O) fp32, required, OVERWRITTEN
+ * With (dp, da, dsigma) = dz/dt of a latent ODE this is the time derivative d u / d t of the decoded field (the other half of a PDE
+ * residual next to enf_field_grad); it also pushes a latent perturbation to the field (linearised uncertainty, the sensitivity to one
+ * latent, the J v of a Gauss-Newton fit whose J^T w is enf_backward_latents).
+ * dp, da, dsigma have the shapes of p, a, sigma; each may be NULL (= zero), not all three.  dsigma without a window
+ * (EnfDesc.use_window == 0) contributes exactly zero.  `out` (B, N, O) is the decode itself, or NULL.  x may have x_bstride == 0.
+ * Sequence: latent prologue and its tangent (a second latent table), the tangent pair kernel (the latent-split layout; every weight
+ * stage multiplies the primal and the tangent fragments; softmax sums T = sum e (dy + dl y), S = sum e dl beside Y, C, L), the tangent
+ * tail.  In bf16 mode the tangent fragments are rounded to bf16 exactly where the primal ones are.
+ * tan and out are written once per element, by one lane, with no atomics and a fixed order of operations: the call is bit-reproducible
+ * run to run by construction, and independent of what the workspace held.
+ * Caller-owned buffers, the caller's stream, no allocation, no host synchronisation, no settings.  `workspace`:
+ * enf_field_tangent_workspace_bytes(d) bytes -- the plain workspace's regions (latent table, an, kv, ybar) followed by the table's
+ * tangent and d ybar, so a buffer of this size also serves every plain call on the same descriptor; contents need not be kept.  The
+ * size query returns 0 for a bad or unserved descriptor.
+ * Served: embedding rff; rel_pos_periodic, latitude_periodic, polar_periodic, ponita, abs_pos, rel_pos, norm_rel_pos; every width and
+ * head count of the forward (d_true / h_true included); both precisions.  ball, ball_lat, ponita_full, ENF_EMB_FFN and
+ * mask_mode != ENF_MASK_OFF are ENF_EUNSUPPORTED.  Errors in this order: the descriptor's; ENF_EUNSUPPORTED as above; a NULL x, p, a,
+ * blob, tan, workspace (or sigma with a window), or all three tangents NULL: ENF_EINVAL.  (DESIGN.md 7 has accuracy and times.) */
+size_t enf_field_tangent_workspace_bytes(const EnfDesc* d);
+int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                      const float* dp, const float* da, const float* dsigma /* tangents: shapes of p / a / sigma, each may be NULL */,
+                      const void* blob, float* out /* (B,N,O) or NULL */, float* tan /* (B,N,O), OVERWRITTEN */, void* workspace,
+                      void* stream);
+
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
