@@ -174,9 +174,10 @@ extern "C" int enf_forward_stages(const EnfDesc* d, const float* x, int64_t x_bs
   float* yb = ybar ? ybar : c.F(W.ybar);
   const bool zf = enf_use_zfold(m);
   float* ls = lse ? lse : c.F(W.lse);
-  // ENF_STAGE_YBAR_HALF: the hand-off to the tail as bf16 (the launchers' flag 2)
+  // ENF_STAGE_YBAR_HALF: the hand-off to the tail as bf16 (the launchers' flag 2), decided HERE, once, for the pair kernel that writes
+  // the rows and the tail that reads them.  Not with relu masks: the masked pair kernels (training passes) store fp32 only
   const bool yhalf = (stages & ENF_STAGE_YBAR_HALF) && m.bf16 && !ybar && (stages & ENF_STAGE_PAIR) && (stages & ENF_STAGE_TAIL) &&
-                     !(stages & ENF_STAGE_TAIL_SAVE) && enf_zfold_split(m) <= 1;
+                     !(stages & ENF_STAGE_TAIL_SAVE) && enf_zfold_split(m) <= 1 && m.mask_mode == ENF_MASK_OFF;
   if ((rc = enf_side_join_pending(c.st, workspace))) return rc;
   if ((stages & ENF_STAGE_PROLOGUE) && (rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), c.st))) return rc;
   if ((stages & (ENF_STAGE_PAIR | ENF_STAGE_FOLD)) &&

@@ -113,7 +113,8 @@ int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const 
 // ---- K2, the forward pair kernel (enf_pair_fwd.hip).  wz / wzb / wzu: scratch of the z-fold variant (EnfWorkspace), all NULL
 // for the latent-split variant; ysplit: the partial sums of ENF_VARIANT_ZFOLD_ZSPLIT, or NULL.
 //   run_fold   nonzero: the z-fold variant first builds its per-latent matrices (enf_launch_wz)
-//   run_pair   bit set: 1 = run the pair stage (without it the call is the fold alone), 2 = hand ybar to the tail as bf16
+//   run_pair   bit set: 1 = run the pair stage (without it the call is the fold alone), 2 = hand ybar to the tail as bf16 (the caller
+//              passes the same decision to the tail's opt & 2; with relu masks on a call that runs the masked kernels: ENF_EINVAL)
 //   spart      != NULL: the caller vouches that all B signals hold the same latent rows and query points (x_bstride == 0) and lends
 //              B N (HD + H) floats: where the call runs the latent-split kernel without relu masks and without the bf16 hand-off, and
 //              B > 1, it computes signal 0 alone, its latents in enf_shared_fwd_parts(m) parts (enf_layout.h), and a merge kernel

@@ -640,6 +640,10 @@ int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, 
   A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.ybar = ybar; A.lse = lse; A.wz = wz; A.wzb = wzb; A.wzu = wzu; A.inv_d = 1.0f / (float)m.Dt;
   A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
   A.masks = m.masks; A.mask_mode = (run_pair & 1) && !m.ffn ? m.mask_mode : 0; A.mask_B = m.mask_B;   // (ffn: no relu, no masks)
+  // the bf16 hand-off is the caller's decision, made once for this launcher and the tail's (enf_api.hip: yhalf).  The masked
+  // instantiations store fp32 rows only: a caller that asks for both has decided wrongly -- refused, not answered with fp32 rows
+  // that its tail would read as bf16
+  if ((run_pair & 2) && A.mask_mode) return ENF_EINVAL;
   // as many latent splits as there are latents to split (up to 8); the rest of the 8 waves take more queries
   static_assert(NWAVES == 8, "enf_latent_splits (enf_layout.h) splits 8 waves");
   A.qg = NWAVES / enf_latent_splits(m.Z);

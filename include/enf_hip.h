@@ -189,7 +189,9 @@ int enf_forward(const EnfDesc* d, const float* x, int64_t x_bstride, const float
                                    its `ybar` (a decode: no backward follows), so the pair kernel may hand it to the tail as bf16 in the
                                    workspace -- half the bytes of the largest tensor of a forward; the tail rounds `ybar` to bf16 for its
                                    first matrix product anyway, so `out` is the same bit for bit.  Ignored where it does not apply
-                                   (f32 mode, ENF_STAGE_TAIL_SAVE, the split z-fold variant, a caller-owned `ybar`). */
+                                   (f32 mode, ENF_STAGE_TAIL_SAVE, the split z-fold variant, a caller-owned `ybar`, relu masks:
+                                   EnfDesc.mask_mode != ENF_MASK_OFF -- masked passes are training passes, their pair kernels hand
+                                   over fp32 rows only). */
 #define ENF_STAGE_SHARED_LATENTS 128u /* the forward's form of ENF_FIT_SHARED_LATENTS (below), same statement and same rules: with
                                    ENF_STAGE_PAIR the pair kernel may compute signal 0 alone and write its `ybar` / `lse` rows to every
                                    signal; B > 1 with x_bstride != 0 is ENF_EINVAL.  Where ENF_STAGE_YBAR_HALF applies in the same
