@@ -27,6 +27,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent",
+           "enf_gn_workspace_bytes", "enf_gn_product", "enf_cg_update",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
@@ -44,6 +45,7 @@ ENF_BWD_REUSE_PROLOGUE, ENF_BWD_REUSE_TAIL, ENF_BWD_REUSE_PREPARED, ENF_BWD_ONLY
 ENF_BWD_DETERMINISTIC = ENF_FIT_DETERMINISTIC = ENF_MSE_DETERMINISTIC = 16
 ENF_FIT_SHARED_LATENTS = ENF_STAGE_SHARED_LATENTS = 128      # include/enf_hip.h: the signals share latents and points (first inner step)
 ENF_BWD_QUERY_GRAD = 32            # size queries: a query gradient will be asked for
+ENF_GN_REUSE_POINT = 1             # enf_gn_product: a fit step or a product at the same point was the workspace's last user
 (ENF_S_EQ, ENF_S_EV, ENF_S_G1, ENF_S_NH, ENF_S_DA1, ENF_S_DA2, ENF_S_DA3, ENF_S_HEAD0) = range(8)
 
 
@@ -82,6 +84,15 @@ class EnfAdamSegment(ctypes.Structure):
     """One component of a latent table for enf_table_adam_update (include/enf_hip.h)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("x", "mu", "nu", "g", "x_out", "mu_out", "nu_out")] + \
                [("width", ctypes.c_int32), ("g_stride", ctypes.c_int32)]
+
+
+ENF_CG_MAX_SEGMENTS = 3
+
+
+class EnfCgSegment(ctypes.Structure):
+    """One latent component of a batched conjugate-gradient step (include/enf_hip.h: enf_cg_update)."""
+    _fields_ = [("x", ctypes.c_void_p), ("r", ctypes.c_void_p), ("d", ctypes.c_void_p), ("q", ctypes.c_void_p),
+                ("width", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class EnfFitComponent(ctypes.Structure):
@@ -230,6 +241,12 @@ def _bind(path, test_hooks):
     lib.enf_field_tangent_workspace_bytes.restype = sz
     lib.enf_field_tangent_workspace_bytes.argtypes = [dp]
     lib.enf_field_tangent.argtypes = [dp, vp, i64] + [vp] * 11
+    # Gauss-Newton product (include/enf_hip.h): p, a, sigma | vp, va, vsigma (each may be NULL) | packed, weight, cweight | grad_scale |
+    # gp, ga, gsigma | workspace, bytes, flags, stream
+    lib.enf_gn_workspace_bytes.restype = sz
+    lib.enf_gn_workspace_bytes.argtypes = [dp, cu]
+    lib.enf_gn_product.argtypes = [dp, vp, i64] + [vp] * 9 + [ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
+    lib.enf_cg_update.argtypes = [ci, ctypes.POINTER(EnfCgSegment), ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
     lib.enf_pair_backward_scratch_bytes.restype = sz
     lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]
     lib.enf_pair_backward_ex2.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]

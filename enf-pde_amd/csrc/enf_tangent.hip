@@ -10,6 +10,10 @@
 //                                 zero start and no bias); the softmax sums Y, C, L get T = sum e (dy + dl y) and S = sum e dl beside
 //                                 them and  ybar = (Y - C) / L,  d ybar = T / L - (S / L) ybar
 //   enf_tail_tangent_kernel       tail_forward's chain (enf_tail.hip) with the same doubling; writes out (optional) and tan
+// The same file holds the Gauss-Newton product (enf_gn_product, at the end): prologue tangent and pair kernel as above -- the pair
+// kernel then also stores lse for the backward pair kernel -- and
+//   enf_gn_tail_kernel            the tail's chain with tangents, d out = w tan formed in registers, the tail's backward chain
+// followed by the backward pair kernel and the prologue backward of the other files.
 // Register room: at D = 128, H = 2 the accumulators Y and T alone are 128 registers, so these kernels run ONE wave per SIMD
 // (workgroups of 4 waves, a 512-register budget) instead of K2's two.  Every output element is written once, by one lane, in a fixed
 // order of operations: no atomics, the call is bit-reproducible run to run.
@@ -336,6 +340,7 @@ struct PairTanArgs {
   const float* x; long long x_bstride;
   const float* lt; const float* ltd; const char* blob; EnfLayout L;
   float* ybar; float* ydot;               // (B, N, H D) fp32 each
+  float* lse;                             // (B, N, H) in K2's convention (m* + log L) for the backward pair kernel, or nullptr
   float inv_d;                            // 1 / (true num_hidden)
   int B, N, Z, dx, inv, use_window, qg;   // qg: query groups per workgroup (1, 2, 4); ZS = TW / qg latent splits
 };
@@ -547,6 +552,7 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A)
       S = fmaf(aw, e[48], S);
     }
     cs[h] = C / L; sb[h] = S / L;
+    if (A.lse && wave < QG && quad == 0 && n0 + col < A.N) A.lse[((size_t)b * A.N + n0 + col) * H + h] = ms + __logf(L);
     const float sc = __expf(sm_m[h] - ms) / L;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -691,7 +697,215 @@ __global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(TailTanArgs A)
   }
 }
 
+// ---------------------------------------------------------------- (d) the Gauss-Newton tail (include/enf_hip.h, "Gauss-Newton product")
+// enf_tail_tangent_kernel's chain, stashing the primal pre-activations in `act` (enf_tail.hip's layout: a_B | a_F1 | a_O0 | a_O2 | mu |
+// rstd), then d out = (w > 0 ? w tan : 0) gs formed in registers where tail_sq_err forms its gradient, then enf_tail_bwd_kernel's
+// backward chain on the stash: d ybar and delta for the backward pair kernel.  Neither tan nor d out reaches memory and the forward
+// chain runs once.  One wave per SIMD, the 2-slot ring with four waves issuing, as every kernel of this file.
+// The one-operand panel product in that cadence: acc += panel . F (the caller initialised acc); `next` / NEXT_BYTES as in panel_gemm2.
+template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES>
+DEV void panel_gemm1(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned panel, unsigned next, int lane) {
+  using C = PanelCfg<KBIN, MTOUT, BF16>;
+#pragma unroll
+  for (int sp = 0; sp < C::SPP; ++sp) {
+    if (sp + 1 < C::SPP) tan_issue<C::STAGE>(P, panel + (sp + 1) * C::STAGE, ring + (P.cur ^ 1) * STAGE_MAX, lane);
+    else if (next != NO_STAGE) tan_issue<NEXT_BYTES>(P, next, ring + (P.cur ^ 1) * STAGE_MAX, lane);
+    gemm_stage<BF16, KBIN, C::MTS, INIT_ACC>(&acc[sp * C::MTS], F, ring + P.cur * STAGE_MAX, lane);
+    stage_close(P);
+  }
+}
+template <int NT> DEV void tan_load_rows(f32x4 (&X)[NT], const float* row, int quad) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) X[t] = *reinterpret_cast<const f32x4*>(row + 16 * t + 4 * quad);
+}
+template <int NT> DEV void tan_store_rows(const f32x4 (&X)[NT], float* row, int quad) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4*>(row + 16 * t + 4 * quad) = X[t];
+}
+template <int NT> DEV void tan_zero_tiles(f32x4 (&X)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) X[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// X <- X * gelu'(pre)
+template <int NT> DEV void gelu_back(f32x4 (&X)[NT], const float* pre_row, int quad) {
+  f32x4 pre[NT];
+  tan_load_rows<NT>(pre, pre_row, quad);
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) X[t][i] *= gelu_grad_f(pre[t][i]);
+}
+
+struct GnTailArgs {
+  const float* ybar; const float* ydot; const char* blob; EnfLayout L;
+  const float* weight;   // nullptr, one weight per query (NQ), or with `cw` one per output value (NQ, O)
+  float* dybar; float* delta; float* act;      // (NQ, HD), (NQ, H), (NQ, 2 HD + 2 D + 2)
+  int NQ, O, cw;
+  float inv_hd;          // 1 / (true heads * true num_hidden)
+  float gs;              // 2 grad_scale / (B N O)
+};
+
+template <int D, int H, bool BF16>
+__global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
+  constexpr int KB = D / 32, KBH = H * D / 32, NT = D / 16, NTH = H * D / 16, HD = H * D, ACT = 2 * HD + 2 * D + 2;
+  using PTB = PanelCfg<KBH, NTH, BF16>; using PO0 = PanelCfg<KBH, NT, BF16>; using PO2 = PanelCfg<KB, NT, BF16>; using PO4 = PanelCfg<KB, 2, BF16>;
+  using PG4 = PanelCfg<1, NT, BF16>; using PG0 = PanelCfg<KB, NTH, BF16>;      // gto4: out D, in 32; gto0: out HD, in D
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* ring = smem;
+  float* cst = reinterpret_cast<float*>(smem + TailTanSmem<D, H>::CONSTS);
+  const float* c_bB = cst, *c_bF1 = cst + HD, *c_bO0 = cst + 2 * HD, *c_bO2 = cst + 2 * HD + D, *c_bO4 = cst + 2 * HD + 2 * D;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
+  const int q0 = blockIdx.x * (16 * TW) + wave * 16;
+  const bool qvalid = q0 + col < A.NQ;
+  const int qi = min(q0 + col, A.NQ - 1);      // clamped (duplicate) queries stash the same values and store nothing else
+  float* act = A.act + (size_t)qi * ACT;
+  const float* yrow = A.ybar + (size_t)qi * HD;
+  const EnfLayout& L = A.L;
+  auto G = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
+  for (int i = tid; i < HD; i += TTH) { cst[i] = G(L.bB)[i]; cst[HD + i] = G(L.bF1)[i]; }
+  for (int i = tid; i < D; i += TTH) { cst[2 * HD + i] = G(L.bO0)[i]; cst[2 * HD + D + i] = G(L.bO2)[i]; }
+  for (int i = tid; i < 32; i += TTH) cst[2 * HD + 2 * D + i] = G(L.bO4)[i];
+  Pipe P;
+  P.rs = make_blob_rsrc(A.blob, (unsigned)L.total);
+  P.rs2 = P.rs;
+  tan_first_stage<PTB::STAGE>(P, ring, (unsigned)L.atb, wave, lane);
+
+  // ---- forward chain with tangents; the pre-activations this lane stores are re-read by this lane only
+  f32x4 g0[2];
+  {
+    f32x4 a[NTH], da[NTH];
+    Frags<BF16, KBH> FH, dFH;
+    tan_load_rows<NTH>(a, yrow, quad);
+    tan_load_rows<NTH>(da, A.ydot + (size_t)qi * HD, quad);
+    make_frags<BF16, KBH>(FH, a);
+    make_frags<BF16, KBH>(dFH, da);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bB, t, quad);
+    panel_gemm2<KBH, NTH, BF16, PTB::STAGE>(a, da, FH, dFH, P, ring, (unsigned)L.atb, (unsigned)L.atf1, true, lane);
+    tan_store_rows<NTH>(a, act, quad);
+    gelu_tangent<NTH>(a, da);
+    float mu, rstd;
+    ln_stats<NTH>(a, mu, rstd, A.inv_hd);
+    if (quad == 0) { act[ACT - 2] = mu; act[ACT - 1] = rstd; }
+    ln_apply<NTH>(a, mu, rstd);
+    ln_tangent<NTH>(da, a, rstd, A.inv_hd);
+    make_frags<BF16, KBH>(FH, a);
+    make_frags<BF16, KBH>(dFH, da);
+#pragma unroll
+    for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bF1, t, quad);
+    panel_gemm2<KBH, NTH, BF16, PO0::STAGE>(a, da, FH, dFH, P, ring, (unsigned)L.atf1, (unsigned)L.ato0, true, lane);
+    tan_store_rows<NTH>(a, act + HD, quad);
+    gelu_tangent<NTH>(a, da);
+    make_frags<BF16, KBH>(FH, a);
+    make_frags<BF16, KBH>(dFH, da);
+    f32x4 c[NT], dc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO0, t, quad);
+    panel_gemm2<KBH, NT, BF16, PO2::STAGE>(c, dc, FH, dFH, P, ring, (unsigned)L.ato0, (unsigned)L.ato2, true, lane);
+    tan_store_rows<NT>(c, act + 2 * HD, quad);
+    gelu_tangent<NT>(c, dc);
+    Frags<BF16, KB> FD, dFD;
+    make_frags<BF16, KB>(FD, c);
+    make_frags<BF16, KB>(dFD, dc);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO2, t, quad);
+    panel_gemm2<KB, NT, BF16, PO4::STAGE>(c, dc, FD, dFD, P, ring, (unsigned)L.ato2, (unsigned)L.ato4, true, lane);
+    tan_store_rows<NT>(c, act + 2 * HD + D, quad);
+    gelu_tangent<NT>(c, dc);
+    make_frags<BF16, KB>(FD, c);
+    make_frags<BF16, KB>(dFD, dc);
+    f32x4 o4[2], do4[2];
+    o4[0] = rowvec(c_bO4, 0, quad);
+    o4[1] = rowvec(c_bO4, 1, quad);
+    panel_gemm2<KB, 2, BF16, PG4::STAGE>(o4, do4, FD, dFD, P, ring, (unsigned)L.ato4, (unsigned)L.gto4, true, lane);
+    // ---- d out = (w > 0 ? w tan : 0) gs: a weight of 0 is a select, as in the fused loss
+    const float wq = (A.weight && !A.cw) ? A.weight[qi] : 1.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = 16 * t + 4 * quad + i;
+        const bool in = o < A.O && qvalid;
+        const float w = (in && A.cw) ? A.weight[(size_t)qi * A.O + o] : wq;
+        g0[t][i] = (in && w > 0.f) ? w * do4[t][i] * A.gs : 0.f;
+      }
+  }
+
+  // ---- backward chain (enf_tail_bwd_kernel's) on the stash
+  Frags<BF16, 1> F1;
+  make_frags<BF16, 1>(F1, g0);
+  f32x4 c[NT];
+  tan_zero_tiles<NT>(c);
+  panel_gemm1<1, NT, BF16, PO2::STAGE>(c, F1, P, ring, (unsigned)L.gto4, (unsigned)L.gto2, lane);                 // d g4
+  gelu_back<NT>(c, act + 2 * HD + D, quad);                                                                       // d a_O2
+  Frags<BF16, KB> FD;
+  make_frags<BF16, KB>(FD, c);
+  tan_zero_tiles<NT>(c);
+  panel_gemm1<KB, NT, BF16, PG0::STAGE>(c, FD, P, ring, (unsigned)L.gto2, (unsigned)L.gto0, lane);                // d g3
+  gelu_back<NT>(c, act + 2 * HD, quad);                                                                           // d a_O0
+  make_frags<BF16, KB>(FD, c);
+  f32x4 a[NTH];
+  tan_zero_tiles<NTH>(a);
+  panel_gemm1<KB, NTH, BF16, PTB::STAGE>(a, FD, P, ring, (unsigned)L.gto0, (unsigned)L.gtf1, lane);               // d g2
+  gelu_back<NTH>(a, act + HD, quad);                                                                              // d a_F1
+  Frags<BF16, KBH> FH;
+  make_frags<BF16, KBH>(FH, a);
+  tan_zero_tiles<NTH>(a);
+  panel_gemm1<KBH, NTH, BF16, PTB::STAGE>(a, FH, P, ring, (unsigned)L.gtf1, (unsigned)L.gtb, lane);               // d n
+  {     // LayerNorm backward + gelu backward on a_B
+    f32x4 pre[NTH];
+    tan_load_rows<NTH>(pre, act, quad);
+    const float mu = act[ACT - 2], rstd = act[ACT - 1];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < NTH; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float nh = (gelu_f(pre[t][i]) - mu) * rstd;
+        s1 += a[t][i]; s2 = fmaf(a[t][i], nh, s2);
+      }
+    const float m1 = xquad_sum(s1) * A.inv_hd, m2 = xquad_sum(s2) * A.inv_hd;
+#pragma unroll
+    for (int t = 0; t < NTH; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float nh = (gelu_f(pre[t][i]) - mu) * rstd;
+        a[t][i] = rstd * (a[t][i] - m1 - nh * m2) * gelu_grad_f(pre[t][i]);                                       // d a_B
+      }
+  }
+  make_frags<BF16, KBH>(FH, a);
+  tan_zero_tiles<NTH>(a);
+  panel_gemm1<KBH, NTH, BF16, 1024>(a, FH, P, ring, (unsigned)L.gtb, NO_STAGE, lane);                             // d ybar
+  f32x4 y[NTH];
+  tan_load_rows<NTH>(y, yrow, quad);
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s = fmaf(a[h * NT + t][i], y[h * NT + t][i], s);
+    s = xquad_sum(s);
+    if (quad == 0 && qvalid) A.delta[(size_t)qi * H + h] = s;
+  }
+  if (qvalid) tan_store_rows<NTH>(a, A.dybar + (size_t)qi * HD, quad);
+}
+
 // ---------------------------------------------------------------- launchers
+template <int D, int H, bool BF16>
+int launch_pair_gn_tail(const PairTanArgs& PA, const GnTailArgs& GA, hipStream_t st) {
+  auto pk = enf_pair_tangent_kernel<D, H, BF16>;
+  auto tk = enf_gn_tail_kernel<D, H, BF16>;
+  static EnfAttrBits pair_done{0}, tail_done{0};        // one per instantiation, one bit per device
+  constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
+  if (!enf_lds_attr(reinterpret_cast<const void*>(pk), pair_lds, pair_done)) return ENF_ELAUNCH;
+  if (!enf_lds_attr(reinterpret_cast<const void*>(tk), tail_lds, tail_done)) return ENF_ELAUNCH;
+  hipLaunchKernelGGL(pk, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), pair_lds, st, PA);
+  if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
+  hipLaunchKernelGGL(tk, dim3((GA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, GA);
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+
 template <int D, int H, bool BF16>
 int launch_pair_tail_tangent(const PairTanArgs& PA, const TailTanArgs& TA, hipStream_t st) {
   auto pk = enf_pair_tangent_kernel<D, H, BF16>;
@@ -757,7 +971,7 @@ extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bst
   }
   PairTanArgs PA;
   PA.x = x; PA.x_bstride = x_bstride; PA.lt = F(T.W.lt); PA.ltd = F(T.ltd); PA.blob = pk; PA.L = L;
-  PA.ybar = F(T.W.ybar); PA.ydot = F(T.ydot); PA.inv_d = 1.0f / (float)m.Dt;
+  PA.ybar = F(T.W.ybar); PA.ydot = F(T.ydot); PA.lse = nullptr; PA.inv_d = 1.0f / (float)m.Dt;
   PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
   const int zs = enf_latent_splits(m.Z);                 // as many latent splits as there are latents to split, up to one per wave
   PA.qg = TW / (zs < TW ? zs : TW);
@@ -774,4 +988,95 @@ extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bst
   ENF_TAN_CASE(64, 4)
 #undef ENF_TAN_CASE
   return ENF_EUNSUPPORTED;
+}
+
+// ---------------------------------------------------------------- the Gauss-Newton product (include/enf_hip.h, "Gauss-Newton product")
+namespace {
+// the workspace: the plain workspace's regions at their usual offsets, with ENF_BWD_DETERMINISTIC the deterministic regions behind them
+// (enf_det_workspace: K3's partial rows), then the table's tangent and d ybar's tangent -- a fit step or an evaluation with the same
+// deterministic bit runs on the same buffer
+struct GnWorkspace { EnfWorkspace W; EnfDetWorkspace X; size_t ltd, ydot, total; };
+GnWorkspace gn_workspace(const EnfDims& m, bool det) {
+  GnWorkspace T;
+  T.W = enf_workspace(m);
+  T.X = enf_det_workspace(m, T.W);
+  T.ltd = det ? T.X.total : T.W.total;
+  T.ydot = T.ltd + enf_align(enf_lt_bytes(m));
+  T.total = T.ydot + enf_align(sizeof(float) * (size_t)m.B * m.N * m.HD);
+  return T;
+}
+constexpr unsigned GN_FLAGS = ENF_BWD_DETERMINISTIC | ENF_GN_REUSE_POINT;
+}  // namespace
+
+extern "C" size_t enf_gn_workspace_bytes(const EnfDesc* d, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || !tangent_supported(d) || (flags & ~GN_FLAGS)) return 0;
+  return gn_workspace(enf_dims(d), (flags & ENF_BWD_DETERMINISTIC) != 0).total;
+}
+
+extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
+                              const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
+                              size_t workspace_bytes, unsigned flags, void* stream) {
+  int rc = enf_check_desc(d);
+  if (rc) return rc;
+  if (!tangent_supported(d)) return ENF_EUNSUPPORTED;
+  if (!x || !p || !a || !packed || !gp || !ga || !gsigma || !workspace || !(vp || va || vsigma) || (weight && cweight) ||
+      (flags & ~GN_FLAGS) || (d->use_window && !sigma))
+    return ENF_EINVAL;
+  const EnfDims m = enf_dims(d);
+  const EnfLayout L = enf_layout(m);
+  const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0, reuse = (flags & ENF_GN_REUSE_POINT) != 0;
+  const GnWorkspace T = gn_workspace(m, det);
+  if (workspace_bytes < T.total) return ENF_EWORKSPACE;
+  const EnfWorkspace& W = T.W;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  const char* pk = (const char*)packed;
+  const bool zb = enf_use_zfold_bwd(m);
+  if ((rc = enf_side_join_pending(st, workspace))) return rc;
+  // the point: latent table, what the prologue backward reads, and the z-fold backward's per-latent matrices -- unless the caller
+  // vouches that a fit step or an earlier product at this point left them
+  if (!reuse) {
+    if ((rc = enf_launch_prologue(m, L, pk, p, a, sigma, F(W.lt), F(W.an), F(W.kv), st))) return rc;
+    if (zb && (rc = enf_launch_wz(m, L, pk, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, st))) return rc;
+  }
+  {
+    PrologueTanArgs A;
+    A.p = p; A.sigma = d->use_window ? sigma : nullptr; A.dp = vp; A.da = va; A.dsigma = vsigma; A.blob = pk; A.L = L;
+    A.an = F(W.an); A.ltd = F(T.ltd);
+    A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
+    const size_t smem = sizeof(float) * PZT * (m.C + m.D + m.HD);
+    hipLaunchKernelGGL(enf_prologue_tangent_kernel, dim3((A.BZ + PZT - 1) / PZT), dim3(256), smem, st, A);
+    if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
+  }
+  PairTanArgs PA;
+  PA.x = x; PA.x_bstride = x_bstride; PA.lt = F(W.lt); PA.ltd = F(T.ltd); PA.blob = pk; PA.L = L;
+  PA.ybar = F(W.ybar); PA.ydot = F(T.ydot); PA.lse = F(W.lse); PA.inv_d = 1.0f / (float)m.Dt;
+  PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
+  const int zs = enf_latent_splits(m.Z);
+  PA.qg = TW / (zs < TW ? zs : TW);
+  GnTailArgs GA;
+  GA.ybar = PA.ybar; GA.ydot = PA.ydot; GA.blob = pk; GA.L = L; GA.weight = cweight ? cweight : weight; GA.cw = cweight != nullptr;
+  GA.dybar = F(W.dybar); GA.delta = F(W.delta); GA.act = F(W.tail_act);
+  GA.NQ = m.B * m.N; GA.O = m.O; GA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
+  GA.gs = 2.0f * grad_scale / ((float)m.B * (float)m.N * (float)m.O);
+  rc = ENF_EUNSUPPORTED;
+#define ENF_GN_CASE(DD, HH)                                                                                                  \
+  if (m.D == DD && m.H == HH)                                                                                                \
+    rc = m.bf16 ? launch_pair_gn_tail<DD, HH, true>(PA, GA, st) : launch_pair_gn_tail<DD, HH, false>(PA, GA, st);
+  ENF_GN_CASE(128, 2)
+  ENF_GN_CASE(64, 2)
+  ENF_GN_CASE(128, 1)
+  ENF_GN_CASE(64, 1)
+  ENF_GN_CASE(64, 4)
+#undef ENF_GN_CASE
+  if (rc) return rc;
+  // the backward pair kernel without a store, in the variant the descriptor resolves to; deterministic: through the partial rows and
+  // the fixed-order reduction, which overwrites the gradient table
+  if (!det && hipMemsetAsync(F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+  if ((rc = enf_launch_pair_bwd(m, L, pk, x, x_bstride, F(W.lt), F(W.lse), F(W.dybar), F(W.delta), F(W.dlt), nullptr,
+                                zb ? ws + W.wzt : nullptr, zb ? F(W.wzb) : nullptr, nullptr, st, det ? F(T.X.part) : nullptr)))
+    return rc;
+  return enf_launch_prologue_bwd(m, L, pk, p, sigma, F(W.an), F(W.kv), F(W.dlt), gp, ga, gsigma, st);
 }

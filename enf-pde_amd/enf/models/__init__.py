@@ -568,6 +568,77 @@ class EquivariantCrossAttentionNeF:
         return dx
 
     # ------------------------------------------------------------------ tendency fields
+    def _tangent_args(self, what, x, p, a, gaussian_window_size, tangents):
+        """The refusals and argument checks of the forward-mode calls (``tangent``, ``gn_product``), then _field_grad_args' tuple.
+        ``tangents``: ((name, tensor or None) for p, a, window), shapes of p / a / (B, Z, 1)."""
+        if self.num_layers > 0:
+            raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
+        if self.embedding_type != "rff":
+            raise NotImplementedError(f"{what} serves the rff embedding, not '{self.embedding_type}'")
+        name = self.cross_attn_invariant.name
+        if name in ("ball", "ball_lat", "ponita_full"):
+            raise NotImplementedError(f"{what} does not serve the '{name}' invariant (no tangent of the per-latent phase / rotation)")
+        if all(t is None for _, t in tangents):
+            raise ValueError(f"{what} needs at least one of " + ", ".join(n for n, _ in tangents))
+        xb, xstride, p_, a_, s_ = self._field_grad_args(what, x, p, a, gaussian_window_size)
+        B, Z, dev = p_.shape[0], p_.shape[1], p_.device
+        for (label, t), shape in zip(tangents, (tuple(p_.shape), tuple(a_.shape), (B, Z, 1))):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape:
+                raise AssertionError(f"{label} has shape {tuple(t.shape)}, expected {shape}")
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{label} must be a contiguous float32 tensor on {dev}")
+        if self._masks is not None:
+            raise NotImplementedError(f"{what} does not take relu masks")
+        return xb, xstride, p_, a_, s_
+
+    # ------------------------------------------------------------------ Gauss-Newton product
+    def gn_reserve(self, B, N, Z, device):
+        """Size this stream's cached workspace for ``gn_product`` on a (B, N, Z) problem.  The cache grows by REPLACING a buffer, so a
+        fit step whose workspace a following ``gn_product(reuse=...)`` is to reuse must already run on the larger buffer: call this
+        first.  Returns the workspace's current tag (``workspace_tag``)."""
+        lib = _lib.load()
+        self._call_ctx(B, N, Z, torch.device(device), size_query=lib.enf_gn_workspace_bytes)
+        return self.workspace_tag(device)
+
+    def workspace_tag(self, device):
+        """The tag of the last native call on this stream's cached workspace of ``device`` (None before the first): what
+        ``gn_product(reuse=...)`` takes right after the fit step at the same point."""
+        device = torch.device(device)
+        ws = self._ws_cache.get((str(device), _lib.stream(device).value))
+        return None if ws is None else self._ws_tag(ws)
+
+    @torch.no_grad()
+    def gn_product(self, params, x, p, a, gaussian_window_size, vp=None, va=None, vwindow=None, weight=None, channel_weight=None,
+                   grad_scale=1.0, reuse=None):
+        """The Gauss-Newton matrix of a latent fit applied to a direction, in one native call (include/enf_hip.h: enf_gn_product):
+        (gp, ga, gwindow or None) = grad_scale * 2 / (B N O) * J^T W J (vp, va, vwindow) with J = d out / d (p, a, window) and W the
+        loss weights of ``mse_value_and_latent_grads`` (``weight`` (B, N), ``channel_weight`` (B, N, O), or 1).  With the fit step's
+        ``grad_scale`` this is the Gauss-Newton Hessian of that step's loss in the units of its gradient.  ``vp`` / ``va`` /
+        ``vwindow`` as the tangents of ``tangent``: each may be None (= zero), not all three.  The model's deterministic mode selects
+        the fixed-order sums of the backward pair kernel.
+        ``reuse``: the ``workspace_tag`` taken right after the ``mse_value_and_latent_grads`` (not ``shared_latents``) or the
+        ``gn_product`` that last ran at the SAME (x, p, a, window, params) on this stream -- the latent prologue is then not recomputed.
+        A tag that is no longer the workspace's current one silently recomputes.  Size the buffer first: ``gn_reserve``."""
+        xb, xstride, p_, a_, s_ = self._tangent_args("gn_product", x, p, a, gaussian_window_size,
+                                                     (("vp", vp), ("va", va), ("vwindow", vwindow)))
+        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
+        w_, cw_ = self._weight_args(weight, channel_weight, B, N)
+        lib = _lib.load()
+        packed = self.pack(params)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_gn_workspace_bytes)
+        flags = self._det_flag()
+        if reuse is not None and reuse == self._ws_tag(ws) and reuse[1] is not None:
+            flags |= _lib.ENF_GN_REUSE_POINT
+        gp, ga = torch.empty_like(p_), torch.empty_like(a_)
+        gs = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
+        _lib.launch(dev, lib.enf_gn_product, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(vp), _ptr(va),
+                    _ptr(vwindow), _ptr(packed), _ptr(w_), _ptr(cw_), float(grad_scale), _ptr(gp), _ptr(ga), _ptr(gs), _ptr(ws),
+                    ws.numel(), flags, st)
+        self._ws_touch(ws)
+        return gp, ga, (gs if s_ is not None else None)
+
     @torch.no_grad()
     def tangent(self, params, x, p, a, gaussian_window_size, dp=None, da=None, dwindow=None, return_out=True):
         """The decode in forward mode along a latent direction, in one native call (include/enf_hip.h: enf_field_tangent):
@@ -577,26 +648,8 @@ class EquivariantCrossAttentionNeF:
         latents' device; each may be None (= zero), not all three.  ``dwindow`` of a model without a window contributes exactly zero.
         No autograd graph is built and none of the inputs gets a gradient.  Every element is written once without atomics: equal
         inputs give equal bits.  ``return_out`` False skips the store of the decode."""
-        if self.num_layers > 0:
-            raise NotImplementedError("tangent is built for num_layers = 0 (the fused decoder)")
-        if self.embedding_type != "rff":
-            raise NotImplementedError(f"tangent serves the rff embedding, not '{self.embedding_type}'")
-        name = self.cross_attn_invariant.name
-        if name in ("ball", "ball_lat", "ponita_full"):
-            raise NotImplementedError(f"tangent does not serve the '{name}' invariant (no tangent of the per-latent phase / rotation)")
-        if dp is None and da is None and dwindow is None:
-            raise ValueError("tangent needs at least one of dp, da, dwindow")
-        xb, xstride, p_, a_, s_ = self._field_grad_args("tangent", x, p, a, gaussian_window_size)
+        xb, xstride, p_, a_, s_ = self._tangent_args("tangent", x, p, a, gaussian_window_size, (("dp", dp), ("da", da), ("dwindow", dwindow)))
         B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
-        for what, t, shape in (("dp", dp, tuple(p_.shape)), ("da", da, tuple(a_.shape)), ("dwindow", dwindow, (B, Z, 1))):
-            if t is None:
-                continue
-            if tuple(t.shape) != shape:
-                raise AssertionError(f"{what} has shape {tuple(t.shape)}, expected {shape}")
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous float32 tensor on {dev}")
-        if self._masks is not None:
-            raise NotImplementedError("tangent does not take relu masks")
         lib = _lib.load()
         packed = self.pack(params)
         desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lambda d, flags: lib.enf_field_tangent_workspace_bytes(d))

@@ -497,6 +497,58 @@ int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const
                       const void* blob, float* out /* (B,N,O) or NULL */, float* tan /* (B,N,O), OVERWRITTEN */, void* workspace,
                       void* stream);
 
+/* Gauss-Newton product (enf_gn_product): the matrix-vector product of a Gauss-Newton / Levenberg-Marquardt fit of the latents in one
+ * call,
+ *     gv = grad_scale * 2 / (B N O) * sum_{n,o} J[b,n,o,:]^T  w[b,n,o]  (J v)[b,n,o]
+ *     J = d out / d (p, a, sigma),   v = (vp, va, vsigma),   gv = (gp, ga, gsigma)        shapes of p / a / sigma, fp32, OVERWRITTEN
+ * w = `weight` (B, N) broadcast over o, `cweight` (B, N, O), or 1, with the definitions and the zero-weight select of "Weighted loss":
+ * a value of weight 0 does not exist.  With the grad_scale of a fit step gv is the Gauss-Newton Hessian of that step's loss applied to
+ * v, in the units of that step's gradient.  The call takes no target and no loss.  vp, va, vsigma: each may be NULL (= zero), not all
+ * three; vsigma without a window contributes exactly zero.  gp, ga, gsigma are all required.  x may have x_bstride == 0.
+ * Sequence: latent prologue; the prologue tangent; where pair_bwd_variant resolves to the z-fold backward, its per-latent matrices;
+ * the tangent pair kernel of enf_field_tangent, which here also stores lse in the forward pair kernel's convention; the GN tail -- ONE
+ * kernel that runs the tail's forward chain with tangents, forms d out = (w > 0 ? w tan : 0) * 2 grad_scale / (B N O) in registers and
+ * runs the tail's backward chain on the primal pre-activations (stashed in the workspace): neither tan nor d out reaches memory and the
+ * forward chain runs once; the backward pair kernel without a store; the prologue backward.
+ * flags: ENF_BWD_DETERMINISTIC -- the backward pair kernel's fixed-order route: no float atomic runs, same inputs give the same bits,
+ * independent of what the workspace held (the rest of the sequence is deterministic by construction).  ENF_GN_REUSE_POINT -- the
+ * caller's statement that the last call on this workspace was enf_fit_step_w / _cw / _e / _ex WITHOUT ENF_FIT_SHARED_LATENTS, or an
+ * earlier enf_gn_product, on the same (d, x, p, a, sigma, packed) and the same deterministic bit: the prologue and the z-fold matrices
+ * are not recomputed (a CG solve calls the product many times at one point, right behind the fit step that gave the gradient).  Any
+ * other bit: ENF_EINVAL.
+ * `workspace`: ONE buffer of enf_gn_workspace_bytes(d, flags) bytes.  It begins with the plain workspace's regions at their usual
+ * offsets (with ENF_BWD_DETERMINISTIC: those of enf_workspace_bytes_ex), so the fit steps and enf_eval_loss with the same deterministic
+ * bit run on the same buffer; contents need not be kept otherwise.  The size query returns 0 for a bad or unserved descriptor or an
+ * unknown flag bit.
+ * Served: what enf_field_tangent serves.  Errors in this order: the descriptor's; ENF_EUNSUPPORTED for ENF_EMB_FFN, ball, ball_lat,
+ * ponita_full or mask_mode != ENF_MASK_OFF; ENF_EINVAL for a NULL x, p, a, packed, gp, ga, gsigma, workspace (or sigma with a window),
+ * all three tangents NULL, weight and cweight both given, or an unknown flag bit; then ENF_EWORKSPACE. */
+#define ENF_GN_REUSE_POINT 1u
+size_t enf_gn_workspace_bytes(const EnfDesc* d, unsigned flags);
+int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                   const float* vp, const float* va, const float* vsigma /* shapes of p / a / sigma; each may be NULL, not all */,
+                   const void* packed, const float* weight /* (B,N) or NULL */, const float* cweight /* (B,N,O) or NULL */,
+                   float grad_scale, float* gp, float* ga, float* gsigma /* shapes of p / a / sigma, required, OVERWRITTEN */,
+                   void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+/* One conjugate-gradient step for B independent systems in one launch: the Gauss-Newton matrix of a fit is block diagonal over the
+ * signals, so a solve is B separate CG iterations with per-signal alpha, beta and damping.  The vectors are split over up to three
+ * segments (the latent components), each (B, Z, width) fp32 contiguous.
+ *   INIT (q == NULL in every segment):  x = 0,  d = r,  rho = r . r        (the caller has put -g in r)
+ *   step, per signal b:  q' = q + lam_b d;  kappa = d . q';  alpha = rho / kappa;  x += alpha d;  r -= alpha q';  rho' = r . r;
+ *                        d = r + (rho' / rho) d;  rho = rho'
+ * A signal whose rho or kappa is not a finite positive number is FROZEN -- it has converged, its right-hand side is zero, or the matrix
+ * is numerically indefinite (bf16): its x, r, d and rho stay exactly as they were, so one signal cannot poison the batch with a NaN.
+ * One workgroup per signal; the dot products run as a fixed strided slice per thread plus a fixed tree: same inputs, same bits, no
+ * atomics, any Z * width.  ENF_EINVAL: nseg outside 1..3, a NULL segs / rho / x / r / d, a width or B or Z < 1, q given in some
+ * segments only. */
+typedef struct EnfCgSegment {      /* one latent component: p, a or sigma */
+  float* x; float* r; float* d;    /* iterate, residual, search direction: updated in place */
+  const float* q;                  /* G d as enf_gn_product returned it (undamped), or NULL in every segment: INIT */
+  int32_t width, reserved;
+} EnfCgSegment;
+int enf_cg_update(int nseg /* 1..3 */, const EnfCgSegment* segs, int32_t B, int32_t Z, const float* lam /* (B) damping, or NULL = 0 */,
+                  float* rho /* (B) r . r, in/out */, void* stream);
+
 /* Reconstruction loss of the inner loop and its gradient in one pass (pde_trainer.py:185):
  *   *loss += mean((out - target)^2)   (the caller zeroes *loss),   dout = 2 (out - target) / n * grad_scale  (dout may be NULL) */
 int enf_mse_value_grad(const float* out, const float* target, size_t n, float grad_scale, float* dout, float* loss,
