@@ -15,6 +15,7 @@
 #include "enf_launch.h"
 #define ENF_PIPE_ONE_RS 1      // the tail streams from the weight blob only (enf_device.h: stage_issue_p)
 #include "enf_device.h"
+#include "enf_tail_common.h"     // load_rows, store_rows, zero_tiles, TailCfg, tail_consts
 
 struct TailArgs {
   const float* ybar; const char* blob; EnfLayout L;
@@ -39,12 +40,7 @@ struct TailArgs {
   float inv_hd;          // 1 / (H * true num_hidden)
 };
 
-// row-per-query global <-> acc layout (feature f = 16 t + 4 quad + i lives in tile t register i)
-template <int NT> DEV void load_rows(f32x4 (&X)[NT], const float* row, int quad) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) X[t] = *reinterpret_cast<const f32x4*>(row + 16 * t + 4 * quad);
-}
-// the same from bf16 rows (two values per word, low half first)
+// load_rows (enf_tail_common.h) from bf16 rows (two values per word, low half first)
 template <int NT> DEV void load_rows_half(f32x4 (&X)[NT], const unsigned short* row, int quad) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -53,27 +49,6 @@ template <int NT> DEV void load_rows_half(f32x4 (&X)[NT], const unsigned short* 
                  __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
   }
 }
-template <int NT> DEV void store_rows(const f32x4 (&X)[NT], float* row, int quad) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4*>(row + 16 * t + 4 * quad) = X[t];
-}
-template <int NT> DEV void zero_tiles(f32x4 (&X)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) X[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-template <int D, int H, bool BF16> struct TailCfg {
-  static constexpr int KB = D / 32, KBH = H * D / 32, NT = D / 16, NTH = H * D / 16, HD = H * D;
-  static constexpr int ACT = 2 * HD + 2 * D + 2;   // a_B | a_F1 | a_O0 | a_O2 | mu | rstd
-  static constexpr int ST_TB = PanelCfg<KBH, NTH, BF16>::STAGE;   // HD x HD
-  static constexpr int ST_O0 = PanelCfg<KBH, NT, BF16>::STAGE;    // out D, in HD
-  static constexpr int ST_O2 = PanelCfg<KB, NT, BF16>::STAGE;     // D x D
-  static constexpr int ST_O4 = PanelCfg<KB, 2, BF16>::STAGE;      // out 32 (O padded), in D
-  static constexpr int ST_G4 = PanelCfg<1, NT, BF16>::STAGE;      // gto4: out D, in 32
-  static constexpr int ST_G0 = PanelCfg<KB, NTH, BF16>::STAGE;    // gto0: out HD, in D
-  static constexpr int SMEM = 2 * STAGE_MAX + 4 * (2 * HD + 2 * D + 32);
-  static constexpr int SMEM3 = 3 * STAGE_MAX + 4 * (2 * HD + 2 * D + 32);      // LA2: three ring slots
-};
 
 // ---- LA2: a 3-slot ring with TWO stages in flight.  The tail's GEMM stages are short (0.25 us of MFMAs per 32 KB
 // stage) against ~1.1 us from LDS-DMA issue to landing, so with one stage in flight (panel_gemm) a small grid -- the fit
@@ -203,15 +178,6 @@ DEV void tail_forward(f32x4 (&o4)[2], const float* yrow, float* act, const EnfLa
   o4[0] = rowvec(c_bO4, 0, quad);
   o4[1] = rowvec(c_bO4, 1, quad);
   tail_gemm<LA2, KB, 2, BF16, NX1, NX2, NEXT_BYTES>(o4, FD, P, ring, (unsigned)L.ato4, next, next2, lane);
-}
-
-template <int D, int H, bool BF16>
-DEV void tail_consts(float* cst, const char* blob, const EnfLayout& L, int tid) {
-  constexpr int HD = H * D;
-  auto G = [&](size_t off) { return reinterpret_cast<const float*>(blob + off); };
-  for (int i = tid; i < HD; i += NTHREADS) { cst[i] = G(L.bB)[i]; cst[HD + i] = G(L.bF1)[i]; }
-  for (int i = tid; i < D; i += NTHREADS) { cst[2 * HD + i] = G(L.bO0)[i]; cst[2 * HD + D + i] = G(L.bO2)[i]; }
-  for (int i = tid; i < 32; i += NTHREADS) cst[2 * HD + 2 * D + i] = G(L.bO4)[i];
 }
 
 // The code path of a wave WITHOUT queries in the kernels with fewer than NWAVES active waves (LA2 only): its part of the constants, then

@@ -14,6 +14,11 @@
 // kernel then also stores lse for the backward pair kernel -- and
 //   enf_gn_tail_kernel            the tail's chain with tangents, d out = w tan formed in registers, the tail's backward chain
 // followed by the backward pair kernel and the prologue backward of the other files.
+// There is one copy of each thing the two entry points have in common: the doubled tail chain (tail_forward_tan, which stashes the
+// pre-activations for the Gauss-Newton tail only), the panel product (panel_gemm2, whose one-operand form serves the backward chain),
+// the launcher and its (D, H) dispatch (launch_pair_tail), and the host sequence (tan_call: refusals, dimensions, workspace;
+// tan_launch_prologue; tan_pair_args).  The row moves, the chain's shapes and the constants' load are enf_tail.hip's
+// (enf_tail_common.h).  Not shared: the Gauss-Newton tail's backward chain, a copy of enf_tail_bwd_kernel's (see there).
 // Register room: at D = 128, H = 2 the accumulators Y and T alone are 128 registers, so these kernels run ONE wave per SIMD
 // (workgroups of 4 waves, a 512-register budget) instead of K2's two.  Every output element is written once, by one lane, in a fixed
 // order of operations: no atomics, the call is bit-reproducible run to run.
@@ -22,6 +27,7 @@
 #include "enf_launch.h"
 #include "enf_device.h"
 #include "enf_pair_common.h"
+#include "enf_tail_common.h"
 
 namespace {
 
@@ -50,7 +56,8 @@ template <int BYTES> DEV void tan_first_stage(Pipe& P, char* ring, unsigned pane
 
 // The two-operand form of panel_gemm: acc += panel . F (the caller initialised acc), dacc = panel . dF (zero start, no bias), both
 // from the SAME staged panel before its slot is released.  Preconditions and `next` / NEXT_BYTES / `active` as in panel_gemm.
-template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES>
+// TAN false is the one-operand product in this cadence (four waves issuing): dacc and dF are not touched.
+template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES, bool TAN = true>
 DEV void panel_gemm2(f32x4 (&acc)[MTOUT], f32x4 (&dacc)[MTOUT], const Frags<BF16, KBIN>& F, const Frags<BF16, KBIN>& dF, Pipe& P,
                      char* ring, unsigned panel, unsigned next, bool active, int lane) {
   using C = PanelCfg<KBIN, MTOUT, BF16>;
@@ -61,13 +68,18 @@ DEV void panel_gemm2(f32x4 (&acc)[MTOUT], f32x4 (&dacc)[MTOUT], const Frags<BF16
     const char* slot = ring + P.cur * STAGE_MAX;
     if (active) {
       gemm_stage<BF16, KBIN, C::MTS, INIT_ACC>(&acc[sp * C::MTS], F, slot, lane);
-      gemm_stage<BF16, KBIN, C::MTS, INIT_ZERO>(&dacc[sp * C::MTS], dF, slot, lane);
-    } else {
+      if constexpr (TAN) gemm_stage<BF16, KBIN, C::MTS, INIT_ZERO>(&dacc[sp * C::MTS], dF, slot, lane);
+    } else if constexpr (TAN) {
 #pragma unroll
       for (int mt = 0; mt < C::MTS; ++mt) dacc[sp * C::MTS + mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     stage_close(P);
   }
+}
+// acc += panel . F alone, every wave active (the Gauss-Newton tail's backward chain)
+template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES>
+DEV void panel_gemm2(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned panel, unsigned next, int lane) {
+  panel_gemm2<KBIN, MTOUT, BF16, NEXT_BYTES, false>(acc, acc, F, F, P, ring, panel, next, true, lane);
 }
 
 // gb_panel (enf_pair_common.h) with the tangent: FiLM v = v0 (1 + gamma) + beta,  dv = dv0 (1 + gamma) + v0 dgamma + dbeta,
@@ -605,7 +617,82 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A)
   }
 }
 
-// ---------------------------------------------------------------- (c) the tail
+// ---------------------------------------------------------------- (c) the tails
+// LDS map of both tail kernels: ring (2 slots) | tail_consts' vectors (enf_tail_common.h)
+template <int D, int H> struct TailTanSmem {
+  static constexpr int CONSTS = 2 * STAGE_MAX;                     // bB bF1 (HD each) | bO0 bO2 (D each) | bO4 (32)
+  static constexpr int TOTAL = CONSTS + 4 * (2 * H * D + 2 * D + 32);
+  static_assert(TOTAL <= TAN_LDS_MAX, "the tangent tail's LDS exceeds one CU's 160 KiB");
+};
+
+// tail_forward's chain (enf_tail.hip) for this wave's 16 queries with a tangent beside every activation: o4 / do4 = the (padded) 32
+// network outputs and their tangents.  Precondition: the first stage of L.atb is resident in ring[P.cur] and visible.
+// SAVE: stash the primal pre-activations and the LayerNorm's mu, rstd in `act` (TailCfg's layout) for a backward chain.
+// next / NEXT_BYTES: the stage that streams behind the last panel (NO_STAGE: nothing follows).
+template <int D, int H, bool BF16, bool SAVE, int NEXT_BYTES>
+DEV void tail_forward_tan(f32x4 (&o4)[2], f32x4 (&do4)[2], const float* yrow, const float* ydrow, float* act, const EnfLayout& L,
+                          const float* cst, Pipe& P, char* ring, unsigned next, int lane, int quad, float inv_hd) {
+  using T = TailCfg<D, H, BF16>;
+  constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD;
+  const float* c_bB = cst, *c_bF1 = cst + HD, *c_bO0 = cst + 2 * HD, *c_bO2 = cst + 2 * HD + D, *c_bO4 = cst + 2 * HD + 2 * D;
+  f32x4 a[NTH], da[NTH];
+  Frags<BF16, KBH> FH, dFH;
+  load_rows<NTH>(a, yrow, quad);
+  load_rows<NTH>(da, ydrow, quad);
+  make_frags<BF16, KBH>(FH, a);
+  make_frags<BF16, KBH>(dFH, da);
+#pragma unroll
+  for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bB, t, quad);
+  panel_gemm2<KBH, NTH, BF16, T::ST_TB>(a, da, FH, dFH, P, ring, (unsigned)L.atb, (unsigned)L.atf1, true, lane);
+  if constexpr (SAVE) store_rows<NTH>(a, act, quad);
+  gelu_tangent<NTH>(a, da);
+  float mu, rstd;
+  ln_stats<NTH>(a, mu, rstd, inv_hd);
+  if constexpr (SAVE) {
+    if (quad == 0) { act[T::ACT - 2] = mu; act[T::ACT - 1] = rstd; }
+  }
+  ln_apply<NTH>(a, mu, rstd);
+  ln_tangent<NTH>(da, a, rstd, inv_hd);
+  make_frags<BF16, KBH>(FH, a);
+  make_frags<BF16, KBH>(dFH, da);
+#pragma unroll
+  for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bF1, t, quad);
+  panel_gemm2<KBH, NTH, BF16, T::ST_O0>(a, da, FH, dFH, P, ring, (unsigned)L.atf1, (unsigned)L.ato0, true, lane);
+  if constexpr (SAVE) store_rows<NTH>(a, act + HD, quad);
+  gelu_tangent<NTH>(a, da);
+  make_frags<BF16, KBH>(FH, a);
+  make_frags<BF16, KBH>(dFH, da);
+  f32x4 c[NT], dc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO0, t, quad);
+  panel_gemm2<KBH, NT, BF16, T::ST_O2>(c, dc, FH, dFH, P, ring, (unsigned)L.ato0, (unsigned)L.ato2, true, lane);
+  if constexpr (SAVE) store_rows<NT>(c, act + 2 * HD, quad);
+  gelu_tangent<NT>(c, dc);
+  Frags<BF16, KB> FD, dFD;
+  make_frags<BF16, KB>(FD, c);
+  make_frags<BF16, KB>(dFD, dc);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO2, t, quad);
+  panel_gemm2<KB, NT, BF16, T::ST_O4>(c, dc, FD, dFD, P, ring, (unsigned)L.ato2, (unsigned)L.ato4, true, lane);
+  if constexpr (SAVE) store_rows<NT>(c, act + 2 * HD + D, quad);
+  gelu_tangent<NT>(c, dc);
+  make_frags<BF16, KB>(FD, c);
+  make_frags<BF16, KB>(dFD, dc);
+  o4[0] = rowvec(c_bO4, 0, quad);
+  o4[1] = rowvec(c_bO4, 1, quad);
+  panel_gemm2<KB, 2, BF16, NEXT_BYTES>(o4, do4, FD, dFD, P, ring, (unsigned)L.ato4, next, true, lane);
+}
+
+// What both tail kernels do before the chain: the LDS constants, the blob's resource, the first stage of the first panel (its barrier
+// also publishes the constants).
+template <int D, int H, bool BF16>
+DEV void tail_tan_open(Pipe& P, char* smem, const char* blob, const EnfLayout& L, int tid) {
+  tail_consts<D, H, BF16, TTH>(reinterpret_cast<float*>(smem + TailTanSmem<D, H>::CONSTS), blob, L, tid);
+  P.rs = make_blob_rsrc(blob, (unsigned)L.total);
+  P.rs2 = P.rs;
+  tan_first_stage<TailCfg<D, H, BF16>::ST_TB>(P, smem, (unsigned)L.atb, tid >> 6, tid & 63);
+}
+
 struct TailTanArgs {
   const float* ybar; const float* ydot; const char* blob; EnfLayout L;
   float* out;            // (B N, O) or nullptr
@@ -613,76 +700,20 @@ struct TailTanArgs {
   int NQ, O;
   float inv_hd;          // 1 / (true heads * true num_hidden)
 };
-template <int D, int H> struct TailTanSmem {
-  static constexpr int CONSTS = 2 * STAGE_MAX;                     // bB bF1 (HD each) | bO0 bO2 (D each) | bO4 (32)
-  static constexpr int TOTAL = CONSTS + 4 * (2 * H * D + 2 * D + 32);
-  static_assert(TOTAL <= TAN_LDS_MAX, "the tangent tail's LDS exceeds one CU's 160 KiB");
-};
 
 template <int D, int H, bool BF16>
 __global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(TailTanArgs A) {
-  constexpr int KB = D / 32, KBH = H * D / 32, NT = D / 16, NTH = H * D / 16, HD = H * D;
-  using PTB = PanelCfg<KBH, NTH, BF16>; using PO0 = PanelCfg<KBH, NT, BF16>; using PO2 = PanelCfg<KB, NT, BF16>; using PO4 = PanelCfg<KB, 2, BF16>;
+  constexpr int HD = H * D;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ring = smem;
-  float* cst = reinterpret_cast<float*>(smem + TailTanSmem<D, H>::CONSTS);
-  const float* c_bB = cst, *c_bF1 = cst + HD, *c_bO0 = cst + 2 * HD, *c_bO2 = cst + 2 * HD + D, *c_bO4 = cst + 2 * HD + 2 * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
   const int q0 = blockIdx.x * (16 * TW) + wave * 16;
   const int qi = min(q0 + col, A.NQ - 1);
-  const EnfLayout& L = A.L;
-  auto G = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
-  for (int i = tid; i < HD; i += TTH) { cst[i] = G(L.bB)[i]; cst[HD + i] = G(L.bF1)[i]; }
-  for (int i = tid; i < D; i += TTH) { cst[2 * HD + i] = G(L.bO0)[i]; cst[2 * HD + D + i] = G(L.bO2)[i]; }
-  for (int i = tid; i < 32; i += TTH) cst[2 * HD + 2 * D + i] = G(L.bO4)[i];
   Pipe P;
-  P.rs = make_blob_rsrc(A.blob, (unsigned)L.total);
-  P.rs2 = P.rs;
-  tan_first_stage<PTB::STAGE>(P, ring, (unsigned)L.atb, wave, lane);
-
-  f32x4 a[NTH], da[NTH];
-  Frags<BF16, KBH> FH, dFH;
-#pragma unroll
-  for (int t = 0; t < NTH; ++t) {
-    a[t] = *reinterpret_cast<const f32x4*>(A.ybar + (size_t)qi * HD + 16 * t + 4 * quad);
-    da[t] = *reinterpret_cast<const f32x4*>(A.ydot + (size_t)qi * HD + 16 * t + 4 * quad);
-  }
-  make_frags<BF16, KBH>(FH, a);
-  make_frags<BF16, KBH>(dFH, da);
-#pragma unroll
-  for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bB, t, quad);
-  panel_gemm2<KBH, NTH, BF16, PTB::STAGE>(a, da, FH, dFH, P, ring, (unsigned)L.atb, (unsigned)L.atf1, true, lane);
-  gelu_tangent<NTH>(a, da);
-  float mu, rstd;
-  ln_stats<NTH>(a, mu, rstd, A.inv_hd);
-  ln_apply<NTH>(a, mu, rstd);
-  ln_tangent<NTH>(da, a, rstd, A.inv_hd);
-  make_frags<BF16, KBH>(FH, a);
-  make_frags<BF16, KBH>(dFH, da);
-#pragma unroll
-  for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bF1, t, quad);
-  panel_gemm2<KBH, NTH, BF16, PO0::STAGE>(a, da, FH, dFH, P, ring, (unsigned)L.atf1, (unsigned)L.ato0, true, lane);
-  gelu_tangent<NTH>(a, da);
-  make_frags<BF16, KBH>(FH, a);
-  make_frags<BF16, KBH>(dFH, da);
-  f32x4 c[NT], dc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO0, t, quad);
-  panel_gemm2<KBH, NT, BF16, PO2::STAGE>(c, dc, FH, dFH, P, ring, (unsigned)L.ato0, (unsigned)L.ato2, true, lane);
-  gelu_tangent<NT>(c, dc);
-  Frags<BF16, KB> FD, dFD;
-  make_frags<BF16, KB>(FD, c);
-  make_frags<BF16, KB>(dFD, dc);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO2, t, quad);
-  panel_gemm2<KB, NT, BF16, PO4::STAGE>(c, dc, FD, dFD, P, ring, (unsigned)L.ato2, (unsigned)L.ato4, true, lane);
-  gelu_tangent<NT>(c, dc);
-  make_frags<BF16, KB>(FD, c);
-  make_frags<BF16, KB>(dFD, dc);
+  tail_tan_open<D, H, BF16>(P, smem, A.blob, A.L, tid);
   f32x4 o4[2], do4[2];
-  o4[0] = rowvec(c_bO4, 0, quad);
-  o4[1] = rowvec(c_bO4, 1, quad);
-  panel_gemm2<KB, 2, BF16, 1024>(o4, do4, FD, dFD, P, ring, (unsigned)L.ato4, NO_STAGE, true, lane);
+  tail_forward_tan<D, H, BF16, false, 1024>(o4, do4, A.ybar + (size_t)qi * HD, A.ydot + (size_t)qi * HD, nullptr, A.L,
+                                            reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, smem, NO_STAGE, lane,
+                                            quad, A.inv_hd);
   if (q0 + col < A.NQ) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -698,38 +729,18 @@ __global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(TailTanArgs A)
 }
 
 // ---------------------------------------------------------------- (d) the Gauss-Newton tail (include/enf_hip.h, "Gauss-Newton product")
-// enf_tail_tangent_kernel's chain, stashing the primal pre-activations in `act` (enf_tail.hip's layout: a_B | a_F1 | a_O0 | a_O2 | mu |
-// rstd), then d out = (w > 0 ? w tan : 0) gs formed in registers where tail_sq_err forms its gradient, then enf_tail_bwd_kernel's
+// The chain above with the stash, then d out = (w > 0 ? w tan : 0) gs formed in registers where tail_sq_err forms its gradient, then a
 // backward chain on the stash: d ybar and delta for the backward pair kernel.  Neither tan nor d out reaches memory and the forward
 // chain runs once.  One wave per SIMD, the 2-slot ring with four waves issuing, as every kernel of this file.
-// The one-operand panel product in that cadence: acc += panel . F (the caller initialised acc); `next` / NEXT_BYTES as in panel_gemm2.
-template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES>
-DEV void panel_gemm1(f32x4 (&acc)[MTOUT], const Frags<BF16, KBIN>& F, Pipe& P, char* ring, unsigned panel, unsigned next, int lane) {
-  using C = PanelCfg<KBIN, MTOUT, BF16>;
-#pragma unroll
-  for (int sp = 0; sp < C::SPP; ++sp) {
-    if (sp + 1 < C::SPP) tan_issue<C::STAGE>(P, panel + (sp + 1) * C::STAGE, ring + (P.cur ^ 1) * STAGE_MAX, lane);
-    else if (next != NO_STAGE) tan_issue<NEXT_BYTES>(P, next, ring + (P.cur ^ 1) * STAGE_MAX, lane);
-    gemm_stage<BF16, KBIN, C::MTS, INIT_ACC>(&acc[sp * C::MTS], F, ring + P.cur * STAGE_MAX, lane);
-    stage_close(P);
-  }
-}
-template <int NT> DEV void tan_load_rows(f32x4 (&X)[NT], const float* row, int quad) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) X[t] = *reinterpret_cast<const f32x4*>(row + 16 * t + 4 * quad);
-}
-template <int NT> DEV void tan_store_rows(const f32x4 (&X)[NT], float* row, int quad) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4*>(row + 16 * t + 4 * quad) = X[t];
-}
-template <int NT> DEV void tan_zero_tiles(f32x4 (&X)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) X[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
+// The backward chain MIRRORS enf_tail_bwd_kernel's (enf_tail.hip), line for line, and is kept as a second copy on purpose: that kernel
+// runs another ring (three slots or two, eight waves issuing), and a chain shared between the two would either make the hot tail branch
+// on its caller or -- tried -- change the code generation of all 220 of its backward instantiations.  A change of the
+// arithmetic there belongs here too.
+
 // X <- X * gelu'(pre)
 template <int NT> DEV void gelu_back(f32x4 (&X)[NT], const float* pre_row, int quad) {
   f32x4 pre[NT];
-  tan_load_rows<NT>(pre, pre_row, quad);
+  load_rows<NT>(pre, pre_row, quad);
 #pragma unroll
   for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -739,7 +750,7 @@ template <int NT> DEV void gelu_back(f32x4 (&X)[NT], const float* pre_row, int q
 struct GnTailArgs {
   const float* ybar; const float* ydot; const char* blob; EnfLayout L;
   const float* weight;   // nullptr, one weight per query (NQ), or with `cw` one per output value (NQ, O)
-  float* dybar; float* delta; float* act;      // (NQ, HD), (NQ, H), (NQ, 2 HD + 2 D + 2)
+  float* dybar; float* delta; float* act;      // (NQ, HD), (NQ, H), (NQ, TailCfg::ACT)
   int NQ, O, cw;
   float inv_hd;          // 1 / (true heads * true num_hidden)
   float gs;              // 2 grad_scale / (B N O)
@@ -747,13 +758,10 @@ struct GnTailArgs {
 
 template <int D, int H, bool BF16>
 __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
-  constexpr int KB = D / 32, KBH = H * D / 32, NT = D / 16, NTH = H * D / 16, HD = H * D, ACT = 2 * HD + 2 * D + 2;
-  using PTB = PanelCfg<KBH, NTH, BF16>; using PO0 = PanelCfg<KBH, NT, BF16>; using PO2 = PanelCfg<KB, NT, BF16>; using PO4 = PanelCfg<KB, 2, BF16>;
-  using PG4 = PanelCfg<1, NT, BF16>; using PG0 = PanelCfg<KB, NTH, BF16>;      // gto4: out D, in 32; gto0: out HD, in D
+  using T = TailCfg<D, H, BF16>;
+  constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD, ACT = T::ACT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
-  float* cst = reinterpret_cast<float*>(smem + TailTanSmem<D, H>::CONSTS);
-  const float* c_bB = cst, *c_bF1 = cst + HD, *c_bO0 = cst + 2 * HD, *c_bO2 = cst + 2 * HD + D, *c_bO4 = cst + 2 * HD + 2 * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
   const int q0 = blockIdx.x * (16 * TW) + wave * 16;
   const bool qvalid = q0 + col < A.NQ;
@@ -761,63 +769,16 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
   float* act = A.act + (size_t)qi * ACT;
   const float* yrow = A.ybar + (size_t)qi * HD;
   const EnfLayout& L = A.L;
-  auto G = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
-  for (int i = tid; i < HD; i += TTH) { cst[i] = G(L.bB)[i]; cst[HD + i] = G(L.bF1)[i]; }
-  for (int i = tid; i < D; i += TTH) { cst[2 * HD + i] = G(L.bO0)[i]; cst[2 * HD + D + i] = G(L.bO2)[i]; }
-  for (int i = tid; i < 32; i += TTH) cst[2 * HD + 2 * D + i] = G(L.bO4)[i];
   Pipe P;
-  P.rs = make_blob_rsrc(A.blob, (unsigned)L.total);
-  P.rs2 = P.rs;
-  tan_first_stage<PTB::STAGE>(P, ring, (unsigned)L.atb, wave, lane);
+  tail_tan_open<D, H, BF16>(P, smem, A.blob, L, tid);
 
   // ---- forward chain with tangents; the pre-activations this lane stores are re-read by this lane only
   f32x4 g0[2];
   {
-    f32x4 a[NTH], da[NTH];
-    Frags<BF16, KBH> FH, dFH;
-    tan_load_rows<NTH>(a, yrow, quad);
-    tan_load_rows<NTH>(da, A.ydot + (size_t)qi * HD, quad);
-    make_frags<BF16, KBH>(FH, a);
-    make_frags<BF16, KBH>(dFH, da);
-#pragma unroll
-    for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bB, t, quad);
-    panel_gemm2<KBH, NTH, BF16, PTB::STAGE>(a, da, FH, dFH, P, ring, (unsigned)L.atb, (unsigned)L.atf1, true, lane);
-    tan_store_rows<NTH>(a, act, quad);
-    gelu_tangent<NTH>(a, da);
-    float mu, rstd;
-    ln_stats<NTH>(a, mu, rstd, A.inv_hd);
-    if (quad == 0) { act[ACT - 2] = mu; act[ACT - 1] = rstd; }
-    ln_apply<NTH>(a, mu, rstd);
-    ln_tangent<NTH>(da, a, rstd, A.inv_hd);
-    make_frags<BF16, KBH>(FH, a);
-    make_frags<BF16, KBH>(dFH, da);
-#pragma unroll
-    for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bF1, t, quad);
-    panel_gemm2<KBH, NTH, BF16, PO0::STAGE>(a, da, FH, dFH, P, ring, (unsigned)L.atf1, (unsigned)L.ato0, true, lane);
-    tan_store_rows<NTH>(a, act + HD, quad);
-    gelu_tangent<NTH>(a, da);
-    make_frags<BF16, KBH>(FH, a);
-    make_frags<BF16, KBH>(dFH, da);
-    f32x4 c[NT], dc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO0, t, quad);
-    panel_gemm2<KBH, NT, BF16, PO2::STAGE>(c, dc, FH, dFH, P, ring, (unsigned)L.ato0, (unsigned)L.ato2, true, lane);
-    tan_store_rows<NT>(c, act + 2 * HD, quad);
-    gelu_tangent<NT>(c, dc);
-    Frags<BF16, KB> FD, dFD;
-    make_frags<BF16, KB>(FD, c);
-    make_frags<BF16, KB>(dFD, dc);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO2, t, quad);
-    panel_gemm2<KB, NT, BF16, PO4::STAGE>(c, dc, FD, dFD, P, ring, (unsigned)L.ato2, (unsigned)L.ato4, true, lane);
-    tan_store_rows<NT>(c, act + 2 * HD + D, quad);
-    gelu_tangent<NT>(c, dc);
-    make_frags<BF16, KB>(FD, c);
-    make_frags<BF16, KB>(dFD, dc);
     f32x4 o4[2], do4[2];
-    o4[0] = rowvec(c_bO4, 0, quad);
-    o4[1] = rowvec(c_bO4, 1, quad);
-    panel_gemm2<KB, 2, BF16, PG4::STAGE>(o4, do4, FD, dFD, P, ring, (unsigned)L.ato4, (unsigned)L.gto4, true, lane);
+    tail_forward_tan<D, H, BF16, true, T::ST_G4>(o4, do4, yrow, A.ydot + (size_t)qi * HD, act, L,
+                                                 reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, ring,
+                                                 (unsigned)L.gto4, lane, quad, A.inv_hd);
     // ---- d out = (w > 0 ? w tan : 0) gs: a weight of 0 is a select, as in the fused loss
     const float wq = (A.weight && !A.cw) ? A.weight[qi] : 1.f;
 #pragma unroll
@@ -835,26 +796,26 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
   Frags<BF16, 1> F1;
   make_frags<BF16, 1>(F1, g0);
   f32x4 c[NT];
-  tan_zero_tiles<NT>(c);
-  panel_gemm1<1, NT, BF16, PO2::STAGE>(c, F1, P, ring, (unsigned)L.gto4, (unsigned)L.gto2, lane);                 // d g4
+  zero_tiles<NT>(c);
+  panel_gemm2<1, NT, BF16, T::ST_O2>(c, F1, P, ring, (unsigned)L.gto4, (unsigned)L.gto2, lane);                   // d g4
   gelu_back<NT>(c, act + 2 * HD + D, quad);                                                                       // d a_O2
   Frags<BF16, KB> FD;
   make_frags<BF16, KB>(FD, c);
-  tan_zero_tiles<NT>(c);
-  panel_gemm1<KB, NT, BF16, PG0::STAGE>(c, FD, P, ring, (unsigned)L.gto2, (unsigned)L.gto0, lane);                // d g3
+  zero_tiles<NT>(c);
+  panel_gemm2<KB, NT, BF16, T::ST_G0>(c, FD, P, ring, (unsigned)L.gto2, (unsigned)L.gto0, lane);                  // d g3
   gelu_back<NT>(c, act + 2 * HD, quad);                                                                           // d a_O0
   make_frags<BF16, KB>(FD, c);
   f32x4 a[NTH];
-  tan_zero_tiles<NTH>(a);
-  panel_gemm1<KB, NTH, BF16, PTB::STAGE>(a, FD, P, ring, (unsigned)L.gto0, (unsigned)L.gtf1, lane);               // d g2
+  zero_tiles<NTH>(a);
+  panel_gemm2<KB, NTH, BF16, T::ST_TB>(a, FD, P, ring, (unsigned)L.gto0, (unsigned)L.gtf1, lane);                 // d g2
   gelu_back<NTH>(a, act + HD, quad);                                                                              // d a_F1
   Frags<BF16, KBH> FH;
   make_frags<BF16, KBH>(FH, a);
-  tan_zero_tiles<NTH>(a);
-  panel_gemm1<KBH, NTH, BF16, PTB::STAGE>(a, FH, P, ring, (unsigned)L.gtf1, (unsigned)L.gtb, lane);               // d n
+  zero_tiles<NTH>(a);
+  panel_gemm2<KBH, NTH, BF16, T::ST_TB>(a, FH, P, ring, (unsigned)L.gtf1, (unsigned)L.gtb, lane);                 // d n
   {     // LayerNorm backward + gelu backward on a_B
     f32x4 pre[NTH];
-    tan_load_rows<NTH>(pre, act, quad);
+    load_rows<NTH>(pre, act, quad);
     const float mu = act[ACT - 2], rstd = act[ACT - 1];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -874,10 +835,10 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
       }
   }
   make_frags<BF16, KBH>(FH, a);
-  tan_zero_tiles<NTH>(a);
-  panel_gemm1<KBH, NTH, BF16, 1024>(a, FH, P, ring, (unsigned)L.gtb, NO_STAGE, lane);                             // d ybar
+  zero_tiles<NTH>(a);
+  panel_gemm2<KBH, NTH, BF16, 1024>(a, FH, P, ring, (unsigned)L.gtb, NO_STAGE, lane);                             // d ybar
   f32x4 y[NTH];
-  tan_load_rows<NTH>(y, yrow, quad);
+  load_rows<NTH>(y, yrow, quad);
 #pragma unroll
   for (int h = 0; h < H; ++h) {
     float s = 0.f;
@@ -888,28 +849,17 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
     s = xquad_sum(s);
     if (quad == 0 && qvalid) A.delta[(size_t)qi * H + h] = s;
   }
-  if (qvalid) tan_store_rows<NTH>(a, A.dybar + (size_t)qi * HD, quad);
+  if (qvalid) store_rows<NTH>(a, A.dybar + (size_t)qi * HD, quad);
 }
 
-// ---------------------------------------------------------------- launchers
-template <int D, int H, bool BF16>
-int launch_pair_gn_tail(const PairTanArgs& PA, const GnTailArgs& GA, hipStream_t st) {
-  auto pk = enf_pair_tangent_kernel<D, H, BF16>;
-  auto tk = enf_gn_tail_kernel<D, H, BF16>;
-  static EnfAttrBits pair_done{0}, tail_done{0};        // one per instantiation, one bit per device
-  constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
-  if (!enf_lds_attr(reinterpret_cast<const void*>(pk), pair_lds, pair_done)) return ENF_ELAUNCH;
-  if (!enf_lds_attr(reinterpret_cast<const void*>(tk), tail_lds, tail_done)) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(pk, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), pair_lds, st, PA);
-  if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(tk, dim3((GA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, GA);
-  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
+// ---------------------------------------------------------------- launch: the pair kernel, then the entry point's tail
+template <int D, int H, bool BF16> auto tail_kernel(const TailTanArgs&) { return enf_tail_tangent_kernel<D, H, BF16>; }
+template <int D, int H, bool BF16> auto tail_kernel(const GnTailArgs&) { return enf_gn_tail_kernel<D, H, BF16>; }
 
-template <int D, int H, bool BF16>
-int launch_pair_tail_tangent(const PairTanArgs& PA, const TailTanArgs& TA, hipStream_t st) {
+template <int D, int H, bool BF16, class TailArgsT>
+int launch_pair_tail(const PairTanArgs& PA, const TailArgsT& TA, hipStream_t st) {
   auto pk = enf_pair_tangent_kernel<D, H, BF16>;
-  auto tk = enf_tail_tangent_kernel<D, H, BF16>;
+  auto tk = tail_kernel<D, H, BF16>(TA);
   static EnfAttrBits pair_done{0}, tail_done{0};        // one per instantiation, one bit per device
   constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
   if (!enf_lds_attr(reinterpret_cast<const void*>(pk), pair_lds, pair_done)) return ENF_ELAUNCH;
@@ -919,68 +869,11 @@ int launch_pair_tail_tangent(const PairTanArgs& PA, const TailTanArgs& TA, hipSt
   hipLaunchKernelGGL(tk, dim3((TA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, TA);
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }
-
-// what the call serves beyond enf_check_desc: the rff embedding, the seven invariants without a per-latent phase, relu masks off
-bool tangent_supported(const EnfDesc* d) {
-  if (d->embedding != ENF_EMB_RFF || d->mask_mode != ENF_MASK_OFF) return false;
-  return d->invariant_id != ENF_INV_BALL && d->invariant_id != ENF_INV_BALL_LAT && d->invariant_id != ENF_INV_PONITA_FULL;
-}
-
-// the workspace: the plain workspace's regions as they are (latent table, an, kv, ybar are used in place), then the table's tangent
-// and d ybar
-struct TangentWorkspace { EnfWorkspace W; size_t ltd, ydot, total; };
-TangentWorkspace tangent_workspace(const EnfDims& m) {
-  TangentWorkspace T;
-  T.W = enf_workspace(m);
-  T.ltd = T.W.total;
-  T.ydot = T.ltd + enf_align(enf_lt_bytes(m));
-  T.total = T.ydot + enf_align(sizeof(float) * (size_t)m.B * m.N * m.HD);
-  return T;
-}
-
-}  // namespace
-
-extern "C" size_t enf_field_tangent_workspace_bytes(const EnfDesc* d) {
-  if (enf_check_desc(d) != ENF_OK || !tangent_supported(d)) return 0;
-  return tangent_workspace(enf_dims(d)).total;
-}
-
-extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                                 const float* dp, const float* da, const float* dsigma, const void* blob, float* out, float* tan,
-                                 void* workspace, void* stream) {
-  int rc = enf_check_desc(d);
-  if (rc) return rc;
-  if (!tangent_supported(d)) return ENF_EUNSUPPORTED;
-  if (!x || !p || !a || !blob || !tan || !workspace || !(dp || da || dsigma) || (d->use_window && !sigma)) return ENF_EINVAL;
-  const EnfDims m = enf_dims(d);
-  const EnfLayout L = enf_layout(m);
-  const TangentWorkspace T = tangent_workspace(m);
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const char* pk = (const char*)blob;
-  if ((rc = enf_launch_prologue(m, L, pk, p, a, sigma, F(T.W.lt), F(T.W.an), F(T.W.kv), st))) return rc;
-  {
-    PrologueTanArgs A;
-    A.p = p; A.sigma = d->use_window ? sigma : nullptr; A.dp = dp; A.da = da; A.dsigma = dsigma; A.blob = pk; A.L = L;
-    A.an = F(T.W.an); A.ltd = F(T.ltd);
-    A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
-    const size_t smem = sizeof(float) * PZT * (m.C + m.D + m.HD);
-    hipLaunchKernelGGL(enf_prologue_tangent_kernel, dim3((A.BZ + PZT - 1) / PZT), dim3(256), smem, st, A);
-    if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
-  }
-  PairTanArgs PA;
-  PA.x = x; PA.x_bstride = x_bstride; PA.lt = F(T.W.lt); PA.ltd = F(T.ltd); PA.blob = pk; PA.L = L;
-  PA.ybar = F(T.W.ybar); PA.ydot = F(T.ydot); PA.lse = nullptr; PA.inv_d = 1.0f / (float)m.Dt;
-  PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
-  const int zs = enf_latent_splits(m.Z);                 // as many latent splits as there are latents to split, up to one per wave
-  PA.qg = TW / (zs < TW ? zs : TW);
-  TailTanArgs TA;
-  TA.ybar = PA.ybar; TA.ydot = PA.ydot; TA.blob = pk; TA.L = L; TA.out = out; TA.tan = tan;
-  TA.NQ = m.B * m.N; TA.O = m.O; TA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-#define ENF_TAN_CASE(DD, HH)                                                                                                 \
-  if (m.D == DD && m.H == HH)                                                                                                \
-    return m.bf16 ? launch_pair_tail_tangent<DD, HH, true>(PA, TA, st) : launch_pair_tail_tangent<DD, HH, false>(PA, TA, st);
+// the instantiations: both entry points dispatch here
+template <class TailArgsT>
+int launch_pair_tail(const EnfDims& m, const PairTanArgs& PA, const TailArgsT& TA, hipStream_t st) {
+#define ENF_TAN_CASE(DD, HH) \
+  if (m.D == DD && m.H == HH) return m.bf16 ? launch_pair_tail<DD, HH, true>(PA, TA, st) : launch_pair_tail<DD, HH, false>(PA, TA, st);
   ENF_TAN_CASE(128, 2)
   ENF_TAN_CASE(64, 2)
   ENF_TAN_CASE(128, 1)
@@ -990,93 +883,134 @@ extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bst
   return ENF_EUNSUPPORTED;
 }
 
-// ---------------------------------------------------------------- the Gauss-Newton product (include/enf_hip.h, "Gauss-Newton product")
-namespace {
-// the workspace: the plain workspace's regions at their usual offsets, with ENF_BWD_DETERMINISTIC the deterministic regions behind them
-// (enf_det_workspace: K3's partial rows), then the table's tangent and d ybar's tangent -- a fit step or an evaluation with the same
-// deterministic bit runs on the same buffer
-struct GnWorkspace { EnfWorkspace W; EnfDetWorkspace X; size_t ltd, ydot, total; };
-GnWorkspace gn_workspace(const EnfDims& m, bool det) {
-  GnWorkspace T;
-  T.W = enf_workspace(m);
-  T.X = enf_det_workspace(m, T.W);
-  T.ltd = det ? T.X.total : T.W.total;
+// ---------------------------------------------------------------- the host sequence of both entry points
+// what the calls serve beyond enf_check_desc: the rff embedding, the seven invariants without a per-latent phase, relu masks off
+bool tangent_supported(const EnfDesc* d) {
+  if (d->embedding != ENF_EMB_RFF || d->mask_mode != ENF_MASK_OFF) return false;
+  return d->invariant_id != ENF_INV_BALL && d->invariant_id != ENF_INV_BALL_LAT && d->invariant_id != ENF_INV_PONITA_FULL;
+}
+
+// The workspace: the plain workspace's regions at their usual offsets (latent table, an, kv, ybar, ... are used in place), with `det`
+// (ENF_BWD_DETERMINISTIC) the deterministic regions behind them (enf_det_workspace: K3's partial rows), then the table's tangent and
+// ybar's tangent -- a fit step or an evaluation with the same deterministic bit runs on the same buffer.  enf_field_tangent's layout is
+// the one without the deterministic regions.
+struct TanWorkspace { size_t ltd, ydot, total; };
+TanWorkspace tan_workspace(const EnfDims& m, bool det) {
+  const EnfWorkspace W = enf_workspace(m);
+  TanWorkspace T;
+  T.ltd = det ? enf_det_workspace(m, W).total : W.total;
   T.ydot = T.ltd + enf_align(enf_lt_bytes(m));
   T.total = T.ydot + enf_align(sizeof(float) * (size_t)m.B * m.N * m.HD);
   return T;
 }
 constexpr unsigned GN_FLAGS = ENF_BWD_DETERMINISTIC | ENF_GN_REUSE_POINT;
+
+// enf_call's context (enf_launch.h) with the regions above and the point's pose rows and window sizes
+struct TanCall : EnfCall {
+  TanWorkspace T;
+  const float* p; const float* sigma;      // sigma: nullptr without a window
+};
+// Refusals in their order of precedence: the descriptor's (enf_check_desc), ENF_EUNSUPPORTED, then enf_call's -- ENF_EINVAL for a NULL
+// pointer (`pointers_ok`: the entry point's own set, p apart) or a window without `sigma` -- then ENF_EWORKSPACE.
+int tan_call(TanCall& c, const EnfDesc* d, bool pointers_ok, const float* p, const float* sigma, const void* packed, void* workspace,
+             size_t workspace_bytes, bool det, void* stream) {
+  int rc = enf_check_desc(d);
+  if (rc) return rc;
+  if (!tangent_supported(d)) return ENF_EUNSUPPORTED;
+  if ((rc = enf_call(c, d, pointers_ok && p, sigma, packed, workspace, ~(size_t)0, stream))) return rc;
+  c.T = tan_workspace(c.m, det);
+  if (workspace_bytes < c.T.total) return ENF_EWORKSPACE;
+  c.p = p;
+  c.sigma = d->use_window ? sigma : nullptr;
+  return ENF_OK;
+}
+// the table's tangent along (dp, da, dsigma), behind enf_launch_prologue at the same point
+int tan_launch_prologue(const TanCall& c, const float* dp, const float* da, const float* dsigma) {
+  const EnfDims& m = c.m;
+  PrologueTanArgs A;
+  A.p = c.p; A.sigma = c.sigma; A.dp = dp; A.da = da; A.dsigma = dsigma; A.blob = c.blob; A.L = c.L;
+  A.an = c.F(c.W.an); A.ltd = c.F(c.T.ltd);
+  A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
+  const size_t smem = sizeof(float) * PZT * (m.C + m.D + m.HD);
+  hipLaunchKernelGGL(enf_prologue_tangent_kernel, dim3((A.BZ + PZT - 1) / PZT), dim3(256), smem, c.st, A);
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+// lse: where the pair kernel leaves the log-sum-exp for a backward pair kernel, or nullptr
+PairTanArgs tan_pair_args(const TanCall& c, const float* x, int64_t x_bstride, float* lse) {
+  const EnfDims& m = c.m;
+  PairTanArgs PA;
+  PA.x = x; PA.x_bstride = x_bstride; PA.lt = c.F(c.W.lt); PA.ltd = c.F(c.T.ltd); PA.blob = c.blob; PA.L = c.L;
+  PA.ybar = c.F(c.W.ybar); PA.ydot = c.F(c.T.ydot); PA.lse = lse; PA.inv_d = 1.0f / (float)m.Dt;
+  PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
+  const int zs = enf_latent_splits(m.Z);                 // as many latent splits as there are latents to split, up to one per wave
+  PA.qg = TW / (zs < TW ? zs : TW);
+  return PA;
+}
+
 }  // namespace
 
+extern "C" size_t enf_field_tangent_workspace_bytes(const EnfDesc* d) {
+  if (enf_check_desc(d) != ENF_OK || !tangent_supported(d)) return 0;
+  return tan_workspace(enf_dims(d), false).total;
+}
+
+extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                                 const float* dp, const float* da, const float* dsigma, const void* blob, float* out, float* tan,
+                                 void* workspace, void* stream) {
+  TanCall c;       // (the call takes no workspace size)
+  int rc = tan_call(c, d, x && a && tan && (dp || da || dsigma), p, sigma, blob, workspace, ~(size_t)0, false, stream);
+  if (rc) return rc;
+  const EnfDims& m = c.m;
+  if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(c.W.lt), c.F(c.W.an), c.F(c.W.kv), c.st))) return rc;
+  if ((rc = tan_launch_prologue(c, dp, da, dsigma))) return rc;
+  const PairTanArgs PA = tan_pair_args(c, x, x_bstride, nullptr);
+  TailTanArgs TA;
+  TA.ybar = PA.ybar; TA.ydot = PA.ydot; TA.blob = c.blob; TA.L = c.L; TA.out = out; TA.tan = tan;
+  TA.NQ = m.B * m.N; TA.O = m.O; TA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
+  return launch_pair_tail(m, PA, TA, c.st);
+}
+
+// ---------------------------------------------------------------- the Gauss-Newton product (include/enf_hip.h, "Gauss-Newton product")
 extern "C" size_t enf_gn_workspace_bytes(const EnfDesc* d, unsigned flags) {
   if (enf_check_desc(d) != ENF_OK || !tangent_supported(d) || (flags & ~GN_FLAGS)) return 0;
-  return gn_workspace(enf_dims(d), (flags & ENF_BWD_DETERMINISTIC) != 0).total;
+  return tan_workspace(enf_dims(d), (flags & ENF_BWD_DETERMINISTIC) != 0).total;
 }
 
 extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                               const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
                               const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
                               size_t workspace_bytes, unsigned flags, void* stream) {
-  int rc = enf_check_desc(d);
-  if (rc) return rc;
-  if (!tangent_supported(d)) return ENF_EUNSUPPORTED;
-  if (!x || !p || !a || !packed || !gp || !ga || !gsigma || !workspace || !(vp || va || vsigma) || (weight && cweight) ||
-      (flags & ~GN_FLAGS) || (d->use_window && !sigma))
-    return ENF_EINVAL;
-  const EnfDims m = enf_dims(d);
-  const EnfLayout L = enf_layout(m);
   const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0, reuse = (flags & ENF_GN_REUSE_POINT) != 0;
-  const GnWorkspace T = gn_workspace(m, det);
-  if (workspace_bytes < T.total) return ENF_EWORKSPACE;
-  const EnfWorkspace& W = T.W;
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const char* pk = (const char*)packed;
+  TanCall c;
+  int rc = tan_call(c, d, x && a && gp && ga && gsigma && (vp || va || vsigma) && !(weight && cweight) && !(flags & ~GN_FLAGS), p, sigma,
+                    packed, workspace, workspace_bytes, det, stream);
+  if (rc) return rc;
+  const EnfDims& m = c.m;
+  const EnfLayout& L = c.L;
+  const EnfWorkspace& W = c.W;
+  hipStream_t st = c.st;
+  const char* pk = c.blob;
   const bool zb = enf_use_zfold_bwd(m);
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   // the point: latent table, what the prologue backward reads, and the z-fold backward's per-latent matrices -- unless the caller
   // vouches that a fit step or an earlier product at this point left them
   if (!reuse) {
-    if ((rc = enf_launch_prologue(m, L, pk, p, a, sigma, F(W.lt), F(W.an), F(W.kv), st))) return rc;
-    if (zb && (rc = enf_launch_wz(m, L, pk, F(W.lt), nullptr, F(W.wzb), nullptr, ws + W.wzt, st))) return rc;
+    if ((rc = enf_launch_prologue(m, L, pk, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
+    if (zb && (rc = enf_launch_wz(m, L, pk, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
   }
-  {
-    PrologueTanArgs A;
-    A.p = p; A.sigma = d->use_window ? sigma : nullptr; A.dp = vp; A.da = va; A.dsigma = vsigma; A.blob = pk; A.L = L;
-    A.an = F(W.an); A.ltd = F(T.ltd);
-    A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
-    const size_t smem = sizeof(float) * PZT * (m.C + m.D + m.HD);
-    hipLaunchKernelGGL(enf_prologue_tangent_kernel, dim3((A.BZ + PZT - 1) / PZT), dim3(256), smem, st, A);
-    if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
-  }
-  PairTanArgs PA;
-  PA.x = x; PA.x_bstride = x_bstride; PA.lt = F(W.lt); PA.ltd = F(T.ltd); PA.blob = pk; PA.L = L;
-  PA.ybar = F(W.ybar); PA.ydot = F(T.ydot); PA.lse = F(W.lse); PA.inv_d = 1.0f / (float)m.Dt;
-  PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
-  const int zs = enf_latent_splits(m.Z);
-  PA.qg = TW / (zs < TW ? zs : TW);
+  if ((rc = tan_launch_prologue(c, vp, va, vsigma))) return rc;
+  const PairTanArgs PA = tan_pair_args(c, x, x_bstride, c.F(W.lse));
   GnTailArgs GA;
   GA.ybar = PA.ybar; GA.ydot = PA.ydot; GA.blob = pk; GA.L = L; GA.weight = cweight ? cweight : weight; GA.cw = cweight != nullptr;
-  GA.dybar = F(W.dybar); GA.delta = F(W.delta); GA.act = F(W.tail_act);
+  GA.dybar = c.F(W.dybar); GA.delta = c.F(W.delta); GA.act = c.F(W.tail_act);
   GA.NQ = m.B * m.N; GA.O = m.O; GA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
   GA.gs = 2.0f * grad_scale / ((float)m.B * (float)m.N * (float)m.O);
-  rc = ENF_EUNSUPPORTED;
-#define ENF_GN_CASE(DD, HH)                                                                                                  \
-  if (m.D == DD && m.H == HH)                                                                                                \
-    rc = m.bf16 ? launch_pair_gn_tail<DD, HH, true>(PA, GA, st) : launch_pair_gn_tail<DD, HH, false>(PA, GA, st);
-  ENF_GN_CASE(128, 2)
-  ENF_GN_CASE(64, 2)
-  ENF_GN_CASE(128, 1)
-  ENF_GN_CASE(64, 1)
-  ENF_GN_CASE(64, 4)
-#undef ENF_GN_CASE
-  if (rc) return rc;
+  if ((rc = launch_pair_tail(m, PA, GA, st))) return rc;
   // the backward pair kernel without a store, in the variant the descriptor resolves to; deterministic: through the partial rows and
   // the fixed-order reduction, which overwrites the gradient table
-  if (!det && hipMemsetAsync(F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
-  if ((rc = enf_launch_pair_bwd(m, L, pk, x, x_bstride, F(W.lt), F(W.lse), F(W.dybar), F(W.delta), F(W.dlt), nullptr,
-                                zb ? ws + W.wzt : nullptr, zb ? F(W.wzb) : nullptr, nullptr, st, det ? F(T.X.part) : nullptr)))
+  if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
+  if ((rc = enf_launch_pair_bwd(m, L, pk, x, x_bstride, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), c.F(W.dlt), nullptr,
+                                zb ? c.ws + W.wzt : nullptr, zb ? c.F(W.wzb) : nullptr, nullptr, st, det ? c.F(c.X.part) : nullptr)))
     return rc;
-  return enf_launch_prologue_bwd(m, L, pk, p, sigma, F(W.an), F(W.kv), F(W.dlt), gp, ga, gsigma, st);
+  return enf_launch_prologue_bwd(m, L, pk, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), gp, ga, gsigma, st);
 }

@@ -7,7 +7,9 @@ cd "$(dirname "$0")/.."
 NAME=$1; FLAGS=$2; ONLY=$3
 mkdir -p variants build_variants/$NAME
 SRC=enf-pde_amd/csrc
-ALL="enf_api enf_pack enf_prologue enf_loss enf_table_adam enf_wz enf_pair_fwd enf_pair_bwd enf_pair_bwd_shared enf_xtd enf_tail enf_train enf_debug enf_ode enf_ode_basis enf_ode_block"
+# the Makefile's sources (the whole C-ABI) plus enf_debug
+ALL="$(sed -n 's/^SRCS *= *//p' $SRC/Makefile) enf_debug"
+[ "$ALL" != " enf_debug" ] || { echo "no SRCS line in $SRC/Makefile" >&2; exit 1; }
 OBJS=""
 for f in $ALL; do
   if [ -z "$ONLY" ] || [[ " $ONLY " == *" $f "* ]] || [ ! -f $SRC/$f.o ]; then

@@ -118,7 +118,57 @@ def errors(lib):
           fn(ctypes.byref(zf), *args(fn, null=(7,))), fn(ctypes.byref(zf), *args(fn, ws_bytes=lib.enf_pair_scratch_bytes(ctypes.byref(zf)) - 1)))
 
 
+def tangent(lib):
+    """enf_field_tangent and enf_gn_product: their size queries (every flag word, and one with an unknown bit) and the calls they refuse
+    before a launch.  enf_field_tangent takes no workspace size: every call here has a reason to be refused."""
+    flag_words = (0, _lib.ENF_GN_REUSE_POINT, _lib.ENF_BWD_DETERMINISTIC, _lib.ENF_BWD_DETERMINISTIC | _lib.ENF_GN_REUSE_POINT, 1 << 30)
+    for name, B, N, Z, C, O, dx, inv in SHAPES:
+        for D, H in WIDTHS:
+            for prec in (0, 1):
+                for emb in (0, 1):
+                    d = _lib.make_desc(B, N, Z, H, D, C, O, dx, _lib.INVARIANT_IDS[inv], 1, prec, embedding=emb)
+                    r = ctypes.byref(d)
+                    print("tangent", name, f"D{D} H{H} prec{prec} emb{emb}", lib.enf_field_tangent_workspace_bytes(r),
+                          *[lib.enf_gn_workspace_bytes(r, f) for f in flag_words])
+    valid = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, 0, 1, 1)
+    nowin = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, 0, 0, 1)
+    bad_dim = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 3, 0, 1, 1)
+    ffn = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, 0, 1, 1, embedding=1)
+    ball = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, _lib.INVARIANT_IDS["ball"], 1, 1)
+    P = 4096
+    # (x, x_bstride, p, a, sigma, dp, da, dsigma, blob, out, tan, workspace, stream)
+    ft = lib.enf_field_tangent
+    full = [P, 0, P, P, P, P, P, P, P, P, P, P, None]
+    row = []
+    for desc in (bad_dim, ffn, ball):               # descriptor / unsupported before a NULL pointer
+        row.append(ft(ctypes.byref(desc), *[None if i == 0 else v for i, v in enumerate(full)]))
+    for i in (0, 2, 3, 8, 10, 11):                  # each required pointer NULL in turn
+        row.append((i, ft(ctypes.byref(valid), *[None if j == i else v for j, v in enumerate(full)])))
+    row.append(ft(ctypes.byref(valid), *[None if j in (5, 6, 7) else v for j, v in enumerate(full)]))       # no direction
+    row.append(ft(ctypes.byref(valid), *[None if j == 4 else v for j, v in enumerate(full)]))               # window without sigma
+    print(ft.__name__, *row)
+    # (x, x_bstride, p, a, sigma, vp, va, vsigma, packed, weight, cweight, grad_scale, gp, ga, gsigma, workspace, bytes, flags, stream)
+    gn = lib.enf_gn_product
+    full = [P, 0, P, P, P, P, P, P, P, None, None, 1.0, P, P, P, P, 0, 0, None]
+    row = []
+    for desc in (bad_dim, ffn, ball):
+        row.append(gn(ctypes.byref(desc), *[None if i == 0 else v for i, v in enumerate(full)]))
+    for i in (0, 2, 3, 8, 12, 13, 14, 15):          # each required pointer NULL in turn, short workspace
+        row.append((i, gn(ctypes.byref(valid), *[None if j == i else v for j, v in enumerate(full)])))
+    row.append(gn(ctypes.byref(valid), *[None if j in (5, 6, 7) else v for j, v in enumerate(full)]))       # no direction
+    row.append(gn(ctypes.byref(valid), *[P if j in (9, 10) else v for j, v in enumerate(full)]))            # both kinds of weights
+    row.append(gn(ctypes.byref(valid), *[1 << 30 if j == 17 else v for j, v in enumerate(full)]))           # an unknown flag
+    row.append(gn(ctypes.byref(valid), *[None if j == 4 else v for j, v in enumerate(full)]))               # window without sigma
+    row.append(gn(ctypes.byref(nowin), *[None if j == 4 else v for j, v in enumerate(full)]))               # no window: short workspace
+    for f in flag_words[:4]:                        # every pointer given: a workspace one byte short
+        a = list(full)
+        a[16], a[17] = lib.enf_gn_workspace_bytes(ctypes.byref(valid), f) - 1, f
+        row.append(gn(ctypes.byref(valid), *a))
+    print(gn.__name__, *row)
+
+
 if __name__ == "__main__":
     lib = _lib.load()
     sizes(lib)
     errors(lib)
+    tangent(lib)

@@ -128,6 +128,10 @@ def test_gn_product_is_symmetric_and_positive(cuda, inv, precision):
     ("128x2", "rel_pos_periodic", 128, 2, 2, 130, 9, "bf16"),
     ("128x1", "rel_pos_periodic", 128, 1, 2, 40, 5, "f32"),
     ("64x4", "rel_pos_periodic", 64, 4, 2, 40, 5, "f32"),
+    ("64x1", "rel_pos_periodic", 64, 1, 2, 20, 7, "f32"),          # with the rows above and the default 64x2: every (D, H) pair of the
+    ("64x1", "rel_pos_periodic", 64, 1, 2, 20, 7, "bf16"),         # dispatch in both precisions
+    ("128x1", "rel_pos_periodic", 128, 1, 2, 20, 7, "bf16"),
+    ("64x4", "rel_pos_periodic", 64, 4, 2, 20, 7, "bf16"),
     ("16x2 padded", "polar_periodic", 16, 2, 2, 40, 5, "f32"),
     ("32x3 padded", "rel_pos", 32, 3, 2, 40, 5, "f32"),
     ("one latent", "rel_pos_periodic", 64, 2, 2, 20, 1, "f32"),

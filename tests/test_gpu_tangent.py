@@ -80,6 +80,10 @@ def test_tangent_is_dual_to_the_latent_backward(cuda, inv):
     ("128x2", "rel_pos_periodic", 128, 2, 2, 130, 9, "bf16"),
     ("128x1", "rel_pos_periodic", 128, 1, 2, 40, 5, "f32"),
     ("64x4", "rel_pos_periodic", 64, 4, 2, 40, 5, "f32"),
+    ("64x1", "rel_pos_periodic", 64, 1, 2, 20, 7, "f32"),          # with the rows above and the default 64x2: every (D, H) pair of the
+    ("64x1", "rel_pos_periodic", 64, 1, 2, 20, 7, "bf16"),         # dispatch in both precisions
+    ("128x1", "rel_pos_periodic", 128, 1, 2, 20, 7, "bf16"),
+    ("64x4", "rel_pos_periodic", 64, 4, 2, 20, 7, "bf16"),
     ("16x2 padded", "polar_periodic", 16, 2, 2, 40, 5, "f32"),     # zero-padded to 64 wide: d_true
     ("32x3 padded", "rel_pos", 32, 3, 2, 40, 5, "f32")])           # 3 -> 4 heads: h_true
 def test_tangent_other_instantiations(cuda, name, inv, D, H, B, N, Z, precision):
