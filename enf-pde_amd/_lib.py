@@ -26,7 +26,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
-           "enf_field_tangent_workspace_bytes", "enf_field_tangent",
+           "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
            "enf_gn_workspace_bytes", "enf_gn_product", "enf_cg_update",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
@@ -241,6 +241,8 @@ def _bind(path, test_hooks):
     lib.enf_field_tangent_workspace_bytes.restype = sz
     lib.enf_field_tangent_workspace_bytes.argtypes = [dp]
     lib.enf_field_tangent.argtypes = [dp, vp, i64] + [vp] * 11
+    # directional derivatives: enf_field_tangent with (xdot, xdot_bstride) behind (x, x_bstride); xdot may be NULL like the other tangents
+    lib.enf_field_tangent_x.argtypes = [dp, vp, i64, vp, i64] + [vp] * 11
     # Gauss-Newton product (include/enf_hip.h): p, a, sigma | vp, va, vsigma (each may be NULL) | packed, weight, cweight | grad_scale |
     # gp, ga, gsigma | workspace, bytes, flags, stream
     lib.enf_gn_workspace_bytes.restype = sz

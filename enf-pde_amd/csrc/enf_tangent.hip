@@ -1,9 +1,13 @@
-// enf_tangent.hip -- forward-mode ("tangent") decode along a latent direction (include/enf_hip.h: enf_field_tangent).
+// enf_tangent.hip -- forward-mode ("tangent") decode along a latent direction (include/enf_hip.h: enf_field_tangent) and, with
+// enf_field_tangent_x, along a direction in the query coordinates as well.
 //
-//   tan[b,n,o] = sum_z  d out[b,n,o] / d (p, a, sigma)[b,z,:]  .  (dp, da, dsigma)[b,z,:]
+//   tan[b,n,o] = sum_z  d out[b,n,o] / d (p, a, sigma)[b,z,:]  .  (dp, da, dsigma)[b,z,:]  +  sum_i d out[b,n,o] / d x[b,n,i]  xdot[b,n,i]
 //
 // the Jacobian-vector product of the decoder with respect to its latents: with (dp, da, dsigma) = dz/dt it is the time derivative of
-// the decoded field.  Three kernels carry a tangent beside every primal activation of the forward chain:
+// the decoded field, and with xdot = a velocity field beside it the material derivative.  The query direction enters in front of the
+// first GEMM stage only (pair_invariant_tan: a few terms per pair in (dinv, dwin)); the pair kernel that takes it is an instantiation
+// of its own (XD), so the one without it is the code it was.  Three kernels carry a tangent beside every primal activation of the
+// forward chain:
 //   enf_prologue_tangent_kernel   per latent row, fp32 on the vector ALU: the tangent of the latent table (`ltd`, the table's layout)
 //   enf_pair_tangent_kernel       the latent-split layout of K2 (enf_pair_fwd.hip): a wave owns 16 queries and a share of the latents;
 //                                 every weight stage in the LDS ring is multiplied twice (primal fragments, tangent fragments with a
@@ -180,10 +184,21 @@ template <int NT> DEV void ln_tangent(f32x4 (&dg)[NT], const f32x4 (&y)[NT], flo
 // Tangent of (invariant, window) along the latent's pose row and window coefficient, both in the latent table's embedded form
 // (tp: plain -> dp; ponita -> (dpx, dpy, -sin th dth, cos th dth); sphere -> (dphi, dth, cos th dth, -sin th dth)).  The formulas are
 // pair_invariant's (enf_device.h), differentiated; `inv` / `win` are its results for the same pair.
-template <bool FAST>
+// XD: also along the query's own tangent tq (zero beyond dx), in the coordinates as given (angles on the sphere, no metric factors).
+// Wherever the pair depends on x - p (or p - x) alone, that is the pose tangent tp - tq in the position components: the translation
+// x += e, p += e then cancels exactly.  What depends on x itself gets its own term: abs_pos' invariant, and theta_x on the sphere
+// (through q.sx, q.cx in `dot`, and as latitude_periodic's inv[0]).
+template <bool FAST, bool XD>
 DEV void pair_invariant_tan(int inv_id, int dx, const QueryPt& q, const f32x4& pz, float wcoef, int use_window, const float (&inv)[4],
-                            float win, const f32x4& tp, float twc, float (&dinv)[4], float& dwin) {
+                            float win, const f32x4& tpz, float twc, const float (&tq)[3], float (&dinv)[4], float& dwin) {
   const float PI = 3.14159265358979323846f;
+  f32x4 tp = tpz;
+  if constexpr (XD) {
+    const bool sphere = inv_id == ENF_INV_LATITUDE_PERIODIC || inv_id == ENF_INV_POLAR_PERIODIC;
+    tp[0] -= tq[0];                                        // phi on the sphere
+    if (!sphere) tp[1] -= tq[1];
+    if (!sphere && inv_id != ENF_INV_PONITA) tp[2] -= tq[2];   // (ponita: rows 2, 3 are the orientation's)
+  }
   dinv[0] = dinv[1] = dinv[2] = dinv[3] = 0.f;
   dwin = 0.f;
   switch (inv_id) {
@@ -198,9 +213,12 @@ DEV void pair_invariant_tan(int inv_id, int dx, const QueryPt& q, const f32x4& p
       const float cd = cos_rev<FAST>(dphi), sd = sin_rev<FAST>(dphi);
       const float dcd = sd * tp[0], dsd = -cd * tp[0];                  // d/d phi_p of cos / sin (phi_x - phi_p)
       const float dot = q.sx * pz[2] * cd + q.cx * pz[3];
-      const float ddot = q.sx * (tp[2] * cd + pz[2] * dcd) + q.cx * tp[3];
-      if (inv_id == ENF_INV_LATITUDE_PERIODIC) { dinv[1] = tp[1]; dinv[2] = dcd; dinv[3] = dsd; }
-      else dinv[0] = ddot;
+      float ddot = q.sx * (tp[2] * cd + pz[2] * dcd) + q.cx * tp[3];
+      if constexpr (XD) ddot = fmaf(q.cx * pz[2] * cd - q.sx * pz[3], tq[1], ddot);      // d dot / d theta_x
+      if (inv_id == ENF_INV_LATITUDE_PERIODIC) {
+        dinv[1] = tp[1]; dinv[2] = dcd; dinv[3] = dsd;
+        if constexpr (XD) dinv[0] = tq[1];
+      } else dinv[0] = ddot;
       if (use_window) {                         // win = exp(-ang^2 wc), ang = acos(clip(dot))
         const float dc = fminf(fmaxf(dot, -1.f + 1e-6f), 1.f - 1e-6f);
         const float ang = acosf(dc);
@@ -221,6 +239,7 @@ DEV void pair_invariant_tan(int inv_id, int dx, const QueryPt& q, const f32x4& p
       const float d2 = r0 * r0 + r1 * r1 + r2 * r2, rt = r0 * t0 + r1 * t1 + r2 * t2;
       if (inv_id == ENF_INV_REL_POS) { dinv[0] = -t0; dinv[1] = -t1; dinv[2] = -t2; }
       else if (inv_id == ENF_INV_NORM_REL_POS) dinv[0] = d2 > 0.f ? -rt * rsqrtf(d2) : 0.f;
+      else if constexpr (XD) { dinv[0] = tq[0]; dinv[1] = tq[1]; dinv[2] = tq[2]; }       // abs_pos: inv = x
       if (use_window) dwin = -twc * d2 + 2.f * wcoef * rt;
     } break;
   }
@@ -355,6 +374,7 @@ struct PairTanArgs {
   float* lse;                             // (B, N, H) in K2's convention (m* + log L) for the backward pair kernel, or nullptr
   float inv_d;                            // 1 / (true num_hidden)
   int B, N, Z, dx, inv, use_window, qg;   // qg: query groups per workgroup (1, 2, 4); ZS = TW / qg latent splits
+  const float* xdot; long long xdot_bstride;   // (B, N, dx) query tangent, read by the XD instantiations only (nullptr: the others run)
 };
 
 // LDS map: ring (2 slots) | constants | per-wave latent vectors u, v0, du, dv0 | softmax exchange (m, l, c, s)
@@ -375,7 +395,7 @@ template <int D, int H> struct TanSmem {
     _Pragma("unroll") for (int t_ = 0; t_ < NT; ++t_) ACC[t_] = rowvec(PTR, t_, quad);   \
   } while (0)
 
-template <int D, int H, bool BF16>
+template <int D, int H, bool BF16, bool XD>
 __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A) {
   using Cfg = PairCfg<D, BF16>;
   using SM = TanSmem<D, H>;
@@ -407,6 +427,13 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A)
   const int n0 = (blockIdx.x * QG + qgi) * 16;
   const int n = min(n0 + col, A.N - 1);                  // tail queries: clamped on load, guarded on store
   const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * A.dx, A.dx, A.inv);
+  float tq[3] = {0.f, 0.f, 0.f};                         // the query's tangent: x's row, clamped as x is
+  if constexpr (XD) {
+    const float* xd = A.xdot + (size_t)b * A.xdot_bstride + (size_t)n * A.dx;
+    tq[0] = xd[0];
+    if (A.dx > 1) tq[1] = xd[1];
+    if (A.dx > 2) tq[2] = xd[2];
+  }
   tan_first_stage<ST_DD>(P, ring, pQ1, wave, lane);      // (its barrier also publishes the constants)
 
   // softmax state against a per-column reference logit (the first one seen), as K2: Y = sum e rstd g, C = sum e rstd mu, L = sum e,
@@ -444,7 +471,7 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A)
 
     float inv[4], win, dinv[4], dwin;
     pair_invariant<BF16>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win);
-    pair_invariant_tan<BF16>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win, tpz, twc, dinv, dwin);
+    pair_invariant_tan<BF16, XD>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win, tpz, twc, tq, dinv, dwin);
 
     float logit[H], dlogit[H];
     Frags<BF16, KB> F, dF;
@@ -858,11 +885,11 @@ template <int D, int H, bool BF16> auto tail_kernel(const GnTailArgs&) { return 
 
 template <int D, int H, bool BF16, class TailArgsT>
 int launch_pair_tail(const PairTanArgs& PA, const TailArgsT& TA, hipStream_t st) {
-  auto pk = enf_pair_tangent_kernel<D, H, BF16>;
+  auto pk = PA.xdot ? enf_pair_tangent_kernel<D, H, BF16, true> : enf_pair_tangent_kernel<D, H, BF16, false>;
   auto tk = tail_kernel<D, H, BF16>(TA);
-  static EnfAttrBits pair_done{0}, tail_done{0};        // one per instantiation, one bit per device
+  static EnfAttrBits pair_done{0}, pair_x_done{0}, tail_done{0};        // one per instantiation, one bit per device
   constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
-  if (!enf_lds_attr(reinterpret_cast<const void*>(pk), pair_lds, pair_done)) return ENF_ELAUNCH;
+  if (!enf_lds_attr(reinterpret_cast<const void*>(pk), pair_lds, PA.xdot ? pair_x_done : pair_done)) return ENF_ELAUNCH;
   if (!enf_lds_attr(reinterpret_cast<const void*>(tk), tail_lds, tail_done)) return ENF_ELAUNCH;
   hipLaunchKernelGGL(pk, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), pair_lds, st, PA);
   if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
@@ -935,8 +962,9 @@ int tan_launch_prologue(const TanCall& c, const float* dp, const float* da, cons
   hipLaunchKernelGGL(enf_prologue_tangent_kernel, dim3((A.BZ + PZT - 1) / PZT), dim3(256), smem, c.st, A);
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }
-// lse: where the pair kernel leaves the log-sum-exp for a backward pair kernel, or nullptr
-PairTanArgs tan_pair_args(const TanCall& c, const float* x, int64_t x_bstride, float* lse) {
+// lse: where the pair kernel leaves the log-sum-exp for a backward pair kernel, or nullptr; xdot: the query tangent, or nullptr
+PairTanArgs tan_pair_args(const TanCall& c, const float* x, int64_t x_bstride, float* lse, const float* xdot = nullptr,
+                          int64_t xdot_bstride = 0) {
   const EnfDims& m = c.m;
   PairTanArgs PA;
   PA.x = x; PA.x_bstride = x_bstride; PA.lt = c.F(c.W.lt); PA.ltd = c.F(c.T.ltd); PA.blob = c.blob; PA.L = c.L;
@@ -944,6 +972,7 @@ PairTanArgs tan_pair_args(const TanCall& c, const float* x, int64_t x_bstride, f
   PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
   const int zs = enf_latent_splits(m.Z);                 // as many latent splits as there are latents to split, up to one per wave
   PA.qg = TW / (zs < TW ? zs : TW);
+  PA.xdot = xdot; PA.xdot_bstride = xdot_bstride;
   return PA;
 }
 
@@ -954,20 +983,28 @@ extern "C" size_t enf_field_tangent_workspace_bytes(const EnfDesc* d) {
   return tan_workspace(enf_dims(d), false).total;
 }
 
-extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                                 const float* dp, const float* da, const float* dsigma, const void* blob, float* out, float* tan,
-                                 void* workspace, void* stream) {
+// With xdot alone the prologue tangent still runs, on three NULL tangents: it then writes zeros to every element of `ltd` the pair
+// kernel reads (u, v0, the pose row, wcoef, c of every row) -- the workspace is not promised to hold anything.
+extern "C" int enf_field_tangent_x(const EnfDesc* d, const float* x, int64_t x_bstride, const float* xdot, int64_t xdot_bstride,
+                                   const float* p, const float* a, const float* sigma, const float* dp, const float* da,
+                                   const float* dsigma, const void* blob, float* out, float* tan, void* workspace, void* stream) {
   TanCall c;       // (the call takes no workspace size)
-  int rc = tan_call(c, d, x && a && tan && (dp || da || dsigma), p, sigma, blob, workspace, ~(size_t)0, false, stream);
+  int rc = tan_call(c, d, x && a && tan && (xdot || dp || da || dsigma), p, sigma, blob, workspace, ~(size_t)0, false, stream);
   if (rc) return rc;
   const EnfDims& m = c.m;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(c.W.lt), c.F(c.W.an), c.F(c.W.kv), c.st))) return rc;
   if ((rc = tan_launch_prologue(c, dp, da, dsigma))) return rc;
-  const PairTanArgs PA = tan_pair_args(c, x, x_bstride, nullptr);
+  const PairTanArgs PA = tan_pair_args(c, x, x_bstride, nullptr, xdot, xdot_bstride);
   TailTanArgs TA;
   TA.ybar = PA.ybar; TA.ydot = PA.ydot; TA.blob = c.blob; TA.L = c.L; TA.out = out; TA.tan = tan;
   TA.NQ = m.B * m.N; TA.O = m.O; TA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
   return launch_pair_tail(m, PA, TA, c.st);
+}
+
+extern "C" int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                                 const float* dp, const float* da, const float* dsigma, const void* blob, float* out, float* tan,
+                                 void* workspace, void* stream) {
+  return enf_field_tangent_x(d, x, x_bstride, nullptr, 0, p, a, sigma, dp, da, dsigma, blob, out, tan, workspace, stream);
 }
 
 // ---------------------------------------------------------------- the Gauss-Newton product (include/enf_hip.h, "Gauss-Newton product")

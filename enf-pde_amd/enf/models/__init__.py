@@ -568,9 +568,11 @@ class EquivariantCrossAttentionNeF:
         return dx
 
     # ------------------------------------------------------------------ tendency fields
-    def _tangent_args(self, what, x, p, a, gaussian_window_size, tangents):
+    def _tangent_args(self, what, x, p, a, gaussian_window_size, tangents, xdot=None):
         """The refusals and argument checks of the forward-mode calls (``tangent``, ``gn_product``), then _field_grad_args' tuple.
-        ``tangents``: ((name, tensor or None) for p, a, window), shapes of p / a / (B, Z, 1)."""
+        ``tangents``: ((name, tensor or None) for p, a, window), shapes of p / a / (B, Z, 1).  ``xdot`` (``tangent`` only): a query
+        direction or None; it counts as a tangent and is checked against x (shape, float32, the latents' device) before anything
+        touches the device; its layout is handled as x's (_x_arg)."""
         if self.num_layers > 0:
             raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
         if self.embedding_type != "rff":
@@ -578,8 +580,13 @@ class EquivariantCrossAttentionNeF:
         name = self.cross_attn_invariant.name
         if name in ("ball", "ball_lat", "ponita_full"):
             raise NotImplementedError(f"{what} does not serve the '{name}' invariant (no tangent of the per-latent phase / rotation)")
-        if all(t is None for _, t in tangents):
-            raise ValueError(f"{what} needs at least one of " + ", ".join(n for n, _ in tangents))
+        if xdot is None and all(t is None for _, t in tangents):
+            raise ValueError(f"{what} needs at least one of " + ", ".join(n for n, _ in tangents) + (", xdot" if what == "tangent" else ""))
+        if xdot is not None:
+            if x.dim() != 3 or tuple(xdot.shape) != tuple(x.shape):
+                raise AssertionError(f"xdot has shape {tuple(xdot.shape)}, expected x's {tuple(x.shape)}")
+            if xdot.device != p.device or xdot.dtype != torch.float32:
+                raise ValueError(f"xdot must be a float32 tensor on {p.device}")
         xb, xstride, p_, a_, s_ = self._field_grad_args(what, x, p, a, gaussian_window_size)
         B, Z, dev = p_.shape[0], p_.shape[1], p_.device
         for (label, t), shape in zip(tangents, (tuple(p_.shape), tuple(a_.shape), (B, Z, 1))):
@@ -640,23 +647,35 @@ class EquivariantCrossAttentionNeF:
         return gp, ga, (gs if s_ is not None else None)
 
     @torch.no_grad()
-    def tangent(self, params, x, p, a, gaussian_window_size, dp=None, da=None, dwindow=None, return_out=True):
+    def tangent(self, params, x, p, a, gaussian_window_size, dp=None, da=None, dwindow=None, return_out=True, xdot=None):
         """The decode in forward mode along a latent direction, in one native call (include/enf_hip.h: enf_field_tangent):
         tan[b, n, o] = sum_z d out[b, n, o] / d (p, a, window)[b, z, :] . (dp, da, dwindow)[b, z, :], returned as (out (B, N, O) or
         None, tan (B, N, O)).  With (dp, da, dwindow) = the latent ODE's right-hand side this is d u / d t of the decoded field.
         ``dp`` / ``da`` / ``dwindow`` have the shapes of p / a / the window (B, Z, 1) and must be float32 and contiguous on the
-        latents' device; each may be None (= zero), not all three.  ``dwindow`` of a model without a window contributes exactly zero.
+        latents' device; each may be None (= zero).  ``dwindow`` of a model without a window contributes exactly zero.
+        ``xdot``: None, or a direction in the query coordinates, float32 (B, N, dx) on the latents' device; a stride-0 batch
+        expansion (one direction field for all signals) is passed as such, as for ``x``; the same pass then adds sum_i d out / d x[b, n, i] xdot[b, n, i]
+        (include/enf_hip.h: enf_field_tangent_x) -- alone a directional derivative of the field, with the latent direction the
+        material derivative.  In the coordinates as given, as ``jacobian``: angle rates on the sphere, no metric factors.  With
+        ``xdot`` the three latent tangents may all be None; all four None is a ValueError.  Without it the call is
+        enf_field_tangent's, bit for bit.
         No autograd graph is built and none of the inputs gets a gradient.  Every element is written once without atomics: equal
         inputs give equal bits.  ``return_out`` False skips the store of the decode."""
-        xb, xstride, p_, a_, s_ = self._tangent_args("tangent", x, p, a, gaussian_window_size, (("dp", dp), ("da", da), ("dwindow", dwindow)))
+        xb, xstride, p_, a_, s_ = self._tangent_args("tangent", x, p, a, gaussian_window_size, (("dp", dp), ("da", da), ("dwindow", dwindow)),
+                                                     xdot=xdot)
         B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
         lib = _lib.load()
         packed = self.pack(params)
         desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lambda d, flags: lib.enf_field_tangent_workspace_bytes(d))
         out = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32) if return_out else None
         tan = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32)
-        _lib.launch(dev, lib.enf_field_tangent, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(dp), _ptr(da),
-                    _ptr(dwindow), _ptr(packed), _ptr(out), _ptr(tan), _ptr(ws), st)
+        if xdot is None:
+            _lib.launch(dev, lib.enf_field_tangent, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(dp), _ptr(da),
+                        _ptr(dwindow), _ptr(packed), _ptr(out), _ptr(tan), _ptr(ws), st)
+        else:
+            xd, xdstride = self._x_arg(xdot)
+            _lib.launch(dev, lib.enf_field_tangent_x, ctypes.byref(desc), _ptr(xb), xstride, _ptr(xd), xdstride, _ptr(p_), _ptr(a_), _ptr(s_),
+                        _ptr(dp), _ptr(da), _ptr(dwindow), _ptr(packed), _ptr(out), _ptr(tan), _ptr(ws), st)
         self._ws_touch(ws)
         return out, tan
 

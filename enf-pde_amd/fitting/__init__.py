@@ -6,6 +6,7 @@
   decode(...)          trainers/pde_trainer.py:389-405         full-grid decode (chunking optional)
   decode_jacobian, divergence, curl_2d, gradient_norm  (no counterpart)  the decode's Jacobian w.r.t. the coordinates and operators on it
   decode_tangent, decode_tendency  (no counterpart)             the decode in forward mode along a latent direction; d u / d t under the latent ODE
+  decode_directional, decode_material_derivative  (no counterpart)   the same pass along a query direction: c . grad u, and Du/Dt = u_t + c . grad u
   cg_solve, lm_fit_latents  (no counterpart)                   batched CG on the native Gauss-Newton product; Levenberg-Marquardt latent fits
   shard_signals / allreduce_mean_   SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
@@ -16,7 +17,7 @@
 """
 from .model import get_model_pde
 from .inner_loop import inner_loop, decode, make_masks, make_signal_masks, default_meta_sgd_lrs
-from .derivatives import decode_jacobian, decode_tangent, decode_tendency, divergence, curl_2d, gradient_norm
+from .derivatives import decode_jacobian, decode_tangent, decode_tendency, decode_directional, decode_material_derivative, divergence, curl_2d, gradient_norm
 from .gauss_newton import cg_solve, lm_fit_latents
 from .parallel import shard_range, allreduce_mean_, init_distributed
 from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState, draw_point_masks
@@ -25,5 +26,5 @@ from .ode_models import PonitaODEGen, MLPODE
 
 __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_masks", "default_meta_sgd_lrs", "shard_range",
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
-           "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency",
+           "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
            "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents"]

@@ -5,6 +5,8 @@
   decode_tangent(...)    (out, tan) on the full grid: the decode in forward mode along a latent direction
                          (EquivariantCrossAttentionNeF.tangent, include/enf_hip.h: enf_field_tangent)
   decode_tendency(...)   (u, du/dt) on the full grid for latents that follow dz/dt = ode_model(z)
+  decode_directional(...)          (u, D_c u = c . grad u) on the full grid along a direction field c in the query coordinates
+  decode_material_derivative(...)  (u, Du/Dt = u_t + c . grad u): the latent ODE's tendency and the advection term in ONE tangent pass
   divergence / curl_2d / gradient_norm   operators on a Jacobian whose components are CARTESIAN
 
 The Jacobian is w.r.t. the coordinates as the model takes them.  For the planar invariants these are Cartesian and the operators
@@ -13,7 +15,8 @@ the metric factors, which are not applied here.
 """
 import torch
 
-__all__ = ["decode_jacobian", "decode_tangent", "decode_tendency", "divergence", "curl_2d", "gradient_norm"]
+__all__ = ["decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative", "divergence",
+           "curl_2d", "gradient_norm"]
 
 
 def decode_jacobian(nef, nef_params, coords, p, a, window, chunk=None):
@@ -51,6 +54,46 @@ def decode_tendency(nef, nef_params, ode_model, ode_params, coords, p, a, window
     if dw is not None:
         dw = dw.reshape(p.shape[0], p.shape[1], 1)
     return decode_tangent(nef, nef_params, coords, p, a, window, dp, da, dw, chunk=chunk)
+
+
+def _tangent_x(nef, nef_params, coords, p, a, window, dp, da, dwindow, direction, chunk):
+    """decode_tangent with a query direction beside the latent one: the chunks slice ``direction`` with the grid."""
+    B = p.shape[0]
+    x = coords[None].expand(B, -1, -1) if coords.dim() == 2 else coords
+    xd = direction[None].expand(B, -1, -1) if direction.dim() == 2 else direction
+    if tuple(xd.shape) != tuple(x.shape):
+        raise ValueError(f"the direction has shape {tuple(direction.shape)}, expected (N, dx) or (B, N, dx) of the grid {tuple(x.shape)}")
+    if chunk is None:
+        return nef.tangent(nef_params, x, p, a, window, dp=dp, da=da, dwindow=dwindow, xdot=xd)
+    parts = [nef.tangent(nef_params, x[:, i:i + chunk], p, a, window, dp=dp, da=da, dwindow=dwindow, xdot=xd[:, i:i + chunk])
+             for i in range(0, x.shape[1], chunk)]
+    return torch.cat([o for o, _ in parts], dim=1), torch.cat([t for _, t in parts], dim=1)
+
+
+def decode_directional(nef, nef_params, coords, p, a, window, direction, chunk=None):
+    """(u (B, N, O), D u (B, N, O)) on the full grid: D u[b, n, o] = sum_i d u[b, n, o] / d coords[n, i] direction[n, i], the derivative
+    of the decoded field along ``direction`` -- an advection term c . grad u, the derivative along a streamline, a normal derivative on
+    a boundary -- in one forward-mode pass (EquivariantCrossAttentionNeF.tangent with ``xdot``), no Jacobian formed.
+    ``direction`` is (N, dx), one direction field for the batch, or (B, N, dx), float32, in COORDINATE RATES: the Jacobian's convention,
+    coordinates as the model takes them.  On the sphere these are rates of the angles; a physical velocity is divided by its metric
+    factors by the caller.  ``coords`` and ``chunk`` as in decode_jacobian: the chunks slice the direction with the grid, and every
+    query's result is the unchunked call's, bit for bit."""
+    return _tangent_x(nef, nef_params, coords, p, a, window, None, None, None, direction, chunk)
+
+
+def decode_material_derivative(nef, nef_params, ode_model, ode_params, coords, p, a, window, velocity, chunk=None):
+    """(u (B, N, O), Du/Dt (B, N, O)) on the full grid, Du/Dt = du/dt + velocity . grad u, for latents that follow the latent ODE:
+    dz/dt = ode_model.apply(ode_params, (p, a, window)) is evaluated ONCE, without autograd, as in decode_tendency, and ONE tangent pass
+    carries it together with the query direction ``velocity`` (forward mode is linear in its direction).
+    ``velocity`` is (N, dx) or (B, N, dx), float32, in COORDINATE RATES as ``direction`` of decode_directional: on the sphere a physical
+    velocity is divided by its metric factors by the caller.  ``None`` entries of the ODE's output mean zero.  ``chunk`` as in
+    decode_directional."""
+    with torch.no_grad():
+        dz = ode_model.apply(ode_params, (p, a, window))
+    dp, da, dw = (None if v is None else v.detach().float().contiguous() for v in dz)
+    if dw is not None:
+        dw = dw.reshape(p.shape[0], p.shape[1], 1)
+    return _tangent_x(nef, nef_params, coords, p, a, window, dp, da, dw, velocity, chunk)
 
 
 def _check(jac, what):

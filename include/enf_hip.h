@@ -497,6 +497,27 @@ int enf_field_tangent(const EnfDesc* d, const float* x, int64_t x_bstride, const
                       const void* blob, float* out /* (B,N,O) or NULL */, float* tan /* (B,N,O), OVERWRITTEN */, void* workspace,
                       void* stream);
 
+/* Directional derivatives (enf_field_tangent_x): enf_field_tangent with a direction in the QUERY coordinates carried by the same pass,
+ *     tan[b,n,o] = sum_z  d out[b,n,o] / d (p, a, sigma)[b,z,:]  .  (dp, da, dsigma)[b,z,:]
+ *                + sum_i  d out[b,n,o] / d x[b,n,i]  xdot[b,n,i]
+ * Forward mode is linear in its direction, so one pass serves both halves of a first-order transport term: with (dp, da, dsigma) = dz/dt
+ * and xdot = c(x) it is the material derivative Du/Dt = u_t + c . grad u; with xdot alone an advection term, the derivative along a
+ * characteristic or a streamline, a normal derivative on a boundary; with xdot = e_i a column of enf_field_grad's Jacobian in forward
+ * mode.  xdot is (B, N, dx) fp32 with a batch stride of its own, xdot_bstride (in elements; 0 = one direction field shared by the
+ * signals, whatever x_bstride is); it is read at the rows x is read at and is never written.  The direction is in the coordinates AS
+ * GIVEN, the convention of enf_field_grad: on the sphere xdot is (d phi / dt, d theta / dt), rates of the angles with no metric
+ * factors -- a physical velocity (u, v) is divided by its metric factors by the caller.
+ * xdot, dp, da, dsigma: each may be NULL (= zero), not all four.  With xdot == NULL the call IS enf_field_tangent (the same kernels,
+ * the same bits); with xdot the pair kernel is an instantiation of its own that adds the query's terms to the tangent of (invariant,
+ * window) in front of the first GEMM stage -- no further stage, accumulator, LDS region or workspace.
+ * Everything else is enf_field_tangent's: the workspace (enf_field_tangent_workspace_bytes(d)), what is served, the order of the
+ * errors (the descriptor's; ENF_EUNSUPPORTED; ENF_EINVAL for a NULL x, p, a, blob, tan, workspace, sigma with a window, or all four
+ * tangents NULL), one store per element with no atomics, bit-reproducible run to run and independent of what the workspace held. */
+int enf_field_tangent_x(const EnfDesc* d, const float* x, int64_t x_bstride, const float* xdot /* (B,N,dx) or NULL */,
+                        int64_t xdot_bstride, const float* p, const float* a, const float* sigma, const float* dp, const float* da,
+                        const float* dsigma, const void* blob, float* out /* (B,N,O) or NULL */, float* tan /* (B,N,O), OVERWRITTEN */,
+                        void* workspace, void* stream);
+
 /* Gauss-Newton product (enf_gn_product): the matrix-vector product of a Gauss-Newton / Levenberg-Marquardt fit of the latents in one
  * call,
  *     gv = grad_scale * 2 / (B N O) * sum_{n,o} J[b,n,o,:]^T  w[b,n,o]  (J v)[b,n,o]

@@ -165,6 +165,19 @@ def tangent(lib):
         a[16], a[17] = lib.enf_gn_workspace_bytes(ctypes.byref(valid), f) - 1, f
         row.append(gn(ctypes.byref(valid), *a))
     print(gn.__name__, *row)
+    # (x, x_bstride, xdot, xdot_bstride, p, a, sigma, dp, da, dsigma, blob, out, tan, workspace, stream): enf_field_tangent's refusals, and
+    # xdot counts as a direction.  Like enf_field_tangent it takes no workspace size: every call here has a reason to be refused.
+    fx = lib.enf_field_tangent_x
+    full = [P, 0, P, 0, P, P, P, P, P, P, P, P, P, P, None]
+    row = []
+    for desc in (bad_dim, ffn, ball):               # descriptor / unsupported before a NULL pointer
+        row.append(fx(ctypes.byref(desc), *[None if i == 0 else v for i, v in enumerate(full)]))
+    for i in (0, 4, 5, 10, 12, 13):                 # each required pointer NULL in turn
+        row.append((i, fx(ctypes.byref(valid), *[None if j == i else v for j, v in enumerate(full)])))
+    row.append(fx(ctypes.byref(valid), *[None if j in (2, 7, 8, 9) else v for j, v in enumerate(full)]))    # no direction at all
+    row.append(fx(ctypes.byref(valid), *[None if j in (0, 7, 8, 9) else v for j, v in enumerate(full)]))    # xdot alone, x missing
+    row.append(fx(ctypes.byref(valid), *[None if j == 6 else v for j, v in enumerate(full)]))               # window without sigma
+    print(fx.__name__, *row)
 
 
 if __name__ == "__main__":
