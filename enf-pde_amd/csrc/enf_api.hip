@@ -43,9 +43,9 @@ extern "C" int enf_check_desc(const EnfDesc* d) {
   if (d->invariant_id == ENF_INV_PONITA_FULL && d->dx != 3) return ENF_EDIM;   // queries (pos_x, pos_y, theta)
   if (enf_inv_has_phase(d->invariant_id) && d->D != 64) return ENF_EUNSUPPORTED;   // (the 128-wide backward kernel has no LDS left)
   if (enf_inv_has_phase(d->invariant_id) && d->dx != 3) return ENF_EDIM;   // ball, ball_lat: (phi, theta, r) coordinates
-  if (!(d->D == 64 || d->D == 128)) return ENF_EUNSUPPORTED;
+  if (!enf_width_compiled(d->D)) return ENF_EUNSUPPORTED;
   if (d->d_true < 0 || d->d_true > d->D || (d->d_true & 1)) return ENF_EINVAL;
-  if (!(d->H == 1 || d->H == 2 || (d->H == 4 && d->D == 64))) return ENF_EUNSUPPORTED;   // 4 heads: 64-wide kernels only
+  if (!enf_shape_compiled(d->D, d->H)) return ENF_EUNSUPPORTED;   // enf_layout.h: ENF_SHAPES (4 heads: 64-wide kernels only)
   if (d->h_true < 0 || d->h_true > d->H) return ENF_EINVAL;
   if (d->O > 32) return ENF_EUNSUPPORTED;
   if (d->precision != ENF_PREC_F32 && d->precision != ENF_PREC_BF16) return ENF_EINVAL;
@@ -172,24 +172,25 @@ extern "C" int enf_forward_stages(const EnfDesc* d, const float* x, int64_t x_bs
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
   float* yb = ybar ? ybar : c.F(W.ybar);
-  const bool zf = enf_use_zfold(m);
   float* ls = lse ? lse : c.F(W.lse);
-  // ENF_STAGE_YBAR_HALF: the hand-off to the tail as bf16 (the launchers' flag 2), decided HERE, once, for the pair kernel that writes
+  // ENF_STAGE_YBAR_HALF: the hand-off to the tail as bf16 (the launchers' ..._YBAR_HALF flags), decided HERE, once, for the pair kernel that writes
   // the rows and the tail that reads them.  Not with relu masks: the masked pair kernels (training passes) store fp32 only
   const bool yhalf = (stages & ENF_STAGE_YBAR_HALF) && m.bf16 && !ybar && (stages & ENF_STAGE_PAIR) && (stages & ENF_STAGE_TAIL) &&
                      !(stages & ENF_STAGE_TAIL_SAVE) && enf_zfold_split(m) <= 1 && m.mask_mode == ENF_MASK_OFF;
   if ((rc = enf_side_join_pending(c.st, workspace))) return rc;
   if ((stages & ENF_STAGE_PROLOGUE) && (rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), c.st))) return rc;
   if ((stages & (ENF_STAGE_PAIR | ENF_STAGE_FOLD)) &&
-      (rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), yb, ls, zf ? c.ws + W.wz : nullptr, zf ? c.F(W.wzb) : nullptr,
-                                zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, (stages & ENF_STAGE_FOLD) != 0,
-                                ((stages & ENF_STAGE_PAIR) != 0 ? 1 : 0) | (yhalf ? 2 : 0), c.st, shared ? c.F(W.dybar) : nullptr)))
+      (rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), yb, ls, c.fold_fwd(),
+                                (stages & ENF_STAGE_FOLD ? ENF_PAIR_FOLD : 0u) | (stages & ENF_STAGE_PAIR ? ENF_PAIR_PAIR : 0u) |
+                                    (yhalf ? ENF_PAIR_YBAR_HALF : 0u),
+                                c.st, shared ? c.F(W.dybar) : nullptr)))
     return rc;
   // starts behind the pair kernel, beside the tail, the caller's loss and the tail backward
   if ((stages & ENF_STAGE_PREPARE_BWD) && enf_use_zfold_bwd(m) && (rc = side_prepare_bwd(side_stream(), c, true)) < 0) return rc;
   const bool tsave = (stages & ENF_STAGE_TAIL_SAVE) != 0;      // stash the tail's pre-activations for the backward that follows
   if ((stages & ENF_STAGE_TAIL) &&
-      (rc = enf_launch_tail(m, c.L, c.blob, yb, out, nullptr, nullptr, nullptr, tsave ? c.F(W.tail_act) : nullptr, 0, (tsave ? 1 : 0) | (yhalf ? 2 : 0), c.st)))
+      (rc = enf_launch_tail(m, c.L, c.blob, yb, out, nullptr, nullptr, nullptr, tsave ? c.F(W.tail_act) : nullptr,
+                            ENF_TAIL_FWD | (tsave ? ENF_TAIL_STASH : 0u) | (yhalf ? ENF_TAIL_YBAR_HALF : 0u), c.st)))
     return rc;
   return ENF_OK;
 }
@@ -212,9 +213,8 @@ extern "C" int enf_backward_latents(const EnfDesc* d, const float* x, int64_t x_
 // the backward pair kernel on the workspace's dybar / delta / dlt, in the z-fold form where the shape resolves to it;
 // det: through the workspace's partial rows and the fixed-order reduction (which overwrites dlt) instead of float atomics
 static int pair_bwd_on_workspace(const EnfCall& c, const float* x, int64_t x_bstride, const float* lse, bool det = false) {
-  const bool zb = enf_use_zfold_bwd(c.m);
   return enf_launch_pair_bwd(c.m, c.L, c.blob, x, x_bstride, c.F(c.W.lt), lse, c.F(c.W.dybar), c.F(c.W.delta), c.F(c.W.dlt), nullptr,
-                             zb ? c.ws + c.W.wzt : nullptr, zb ? c.F(c.W.wzb) : nullptr, nullptr, c.st, det ? c.F(c.X.part) : nullptr);
+                             c.fold_bwd(), nullptr, c.st, det ? c.F(c.X.part) : nullptr);
 }
 
 extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a,
@@ -255,7 +255,9 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
     if (!rc && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
   }
   const bool treuse = (flags & ENF_BWD_REUSE_TAIL) && (flags & ENF_BWD_REUSE_PROLOGUE);
-  if ((rc = enf_launch_tail(m, c.L, c.blob, ybar, nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), 1, treuse ? 1 : 0, st))) return rc;
+  if ((rc = enf_launch_tail(m, c.L, c.blob, ybar, nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act),
+                            ENF_TAIL_BWD | (treuse ? ENF_TAIL_STASH : 0u), st)))
+    return rc;
   // (deterministic mode: the reduction overwrites the gradient table, nothing to zero)
   if (!prepared && !det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;      // the per-latent matrices (and, if prepared, the zeroed table)
@@ -302,12 +304,11 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
-  const bool zf = enf_use_zfold(m), zb = enf_use_zfold_bwd(m);
+  const bool zb = enf_use_zfold_bwd(m);
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
   // (shared: the parts of the one forward borrow d ybar | delta, which this step's tail overwrites afterwards)
-  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
-                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st,
+  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), c.fold_fwd(), ENF_PAIR_FOLD | ENF_PAIR_PAIR, st,
                                 shared ? c.F(W.dybar) : nullptr)))
     return rc;
   // the shared-latent backward (enf_layout.h: enf_shared_backward_rule): tail, loss and backward pair kernel run ONCE, on signal 0
@@ -330,7 +331,7 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
     if ((rc = enf_launch_mse_shared(out1, target, weight, m.B, m.N, grad_scale, dout, loss, st))) return rc;
     if ((rc = enf_side_join_pending(st, workspace))) return rc;
     if ((rc = enf_launch_pair_bwd_shared(m, c.L, c.blob, x, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), dout, c.F(W.dlt),
-                                         c.ws + W.wzt, c.F(W.wzb), st)))
+                                         c.fold_bwd(), st)))
       return rc;
     return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
   }
@@ -384,11 +385,9 @@ extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
-  const bool zf = enf_use_zfold(m);
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
-  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
-                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
+  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), c.fold_fwd(), ENF_PAIR_FOLD | ENF_PAIR_PAIR, st)))
     return rc;
   float* e = err ? err : (loss_b ? c.F(W.dybar) : nullptr);
   if ((rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
@@ -428,29 +427,31 @@ static int field_grad_sequence(const EnfDesc* d, const float* x, int64_t x_bstri
   if (det && workspace_bytes < c.X.total + enf_det_dx_bytes(m)) return ENF_EWORKSPACE;
   float* part = det ? c.F(c.X.part) : nullptr;
   float* dxpart = det ? c.F(c.X.total) : nullptr;
-  const bool zf = enf_use_zfold(m), zb = enf_use_zfold_bwd(m);
+  const bool zb = enf_use_zfold_bwd(m);
   const size_t per = (size_t)m.B * m.N * m.dx;                    // one channel's query gradient
   const int passes = dout ? 1 : m.O;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
   if (zb && (rc = enf_launch_wz(m, c.L, c.blob, c.F(W.lt), nullptr, c.F(W.wzb), nullptr, c.ws + W.wzt, st))) return rc;
-  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), zf ? c.ws + W.wz : nullptr,
-                                zf ? c.F(W.wzb) : nullptr, zf ? c.ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? c.F(W.ysplit) : nullptr, 1, 1, st)))
+  if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), c.fold_fwd(), ENF_PAIR_FOLD | ENF_PAIR_PAIR, st)))
     return rc;
   // the forward tail with the stash; without `out` its B N O values land in the workspace's d ybar region (B N HD floats, O <= 32 <= HD),
   // which the first backward pass overwrites
-  if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), out ? out : c.F(W.dybar), nullptr, nullptr, nullptr, c.F(W.tail_act), 0, 1, st))) return rc;
+  if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), out ? out : c.F(W.dybar), nullptr, nullptr, nullptr, c.F(W.tail_act),
+                            ENF_TAIL_FWD | ENF_TAIL_STASH, st)))
+    return rc;
   // default mode: K3 adds to d lt (scratch of this call, never returned: zeroed once, the passes pile up in it) and to the query gradient
   // with float atomics; deterministic mode: the fixed-order reductions overwrite both
   if (!det && (hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess ||
                hipMemsetAsync(grad, 0, sizeof(float) * per * passes, st) != hipSuccess))
     return ENF_ELAUNCH;
   for (int o = 0; o < passes; ++o) {
-    if (dout) rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), 1, 1, st);
+    if (dout) rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), nullptr, dout, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act),
+                                    ENF_TAIL_BWD | ENF_TAIL_STASH, st);
     else rc = enf_launch_tail_seed(m, c.L, c.blob, c.F(W.ybar), o, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st);
     if (rc) return rc;
     if ((rc = enf_launch_pair_bwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), c.F(W.dlt), nullptr,
-                                  zb ? c.ws + W.wzt : nullptr, zb ? c.F(W.wzb) : nullptr, grad + (size_t)o * per, st, part, dxpart)))
+                                  c.fold_bwd(), grad + (size_t)o * per, st, part, dxpart)))
       return rc;
   }
   return ENF_OK;
@@ -561,9 +562,9 @@ extern "C" int enf_pair_forward(const EnfDesc* d, const float* x, int64_t x_bstr
   const bool zf = S.total != 0;
   if (zf && (!scratch || scratch_bytes < S.total)) return ENF_EWORKSPACE;
   char* sc = (char*)scratch;
-  return enf_launch_pair_fwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, ybar, lse, zf ? sc + S.wz : nullptr,
-                             zf ? reinterpret_cast<float*>(sc + S.wzb) : nullptr, zf ? sc + S.wzu : nullptr,
-                             zf && enf_zfold_split(m) > 1 ? reinterpret_cast<float*>(sc + S.ysplit) : nullptr, 1, 1, (hipStream_t)stream);
+  EnfFoldFwd zs{};
+  if (zf) zs = {sc + S.wz, reinterpret_cast<float*>(sc + S.wzb), sc + S.wzu, enf_zfold_split(m) > 1 ? reinterpret_cast<float*>(sc + S.ysplit) : nullptr};
+  return enf_launch_pair_fwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, ybar, lse, zs, ENF_PAIR_FOLD | ENF_PAIR_PAIR, (hipStream_t)stream);
 }
 
 extern "C" size_t enf_relu_mask_bytes(const EnfDesc* d) {
@@ -609,11 +610,11 @@ extern "C" int enf_pair_backward_ex2(const EnfDesc* d, const float* x, int64_t x
   if (det) {
     const size_t pb = enf_det_part_bytes(m, false);
     if (scratch_bytes < pb + (dx ? enf_det_dx_bytes(m) : 0)) return ENF_EWORKSPACE;
-    return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, nullptr, nullptr, dx, st,
+    return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, EnfFoldBwd{}, dx, st,
                                (float*)scratch, dx ? reinterpret_cast<float*>((char*)scratch + pb) : nullptr);
   }
   if (hipMemsetAsync(dlt, 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
-  return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, nullptr, nullptr, dx, st);
+  return enf_launch_pair_bwd(m, enf_layout(m), (const char*)packed, x, x_bstride, lt, lse, dybar, delta, dlt, store, EnfFoldBwd{}, dx, st);
 }
 
 // ---- weight gradients of the per-pair chain: K3 (STORE) -> K4, chunked over signals (enf_xtd.hip)

@@ -7,15 +7,16 @@
 #include <atomic>
 #include "enf_layout.h"
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) holds per DEVICE: `done` keeps one bit per device ordinal of the calling
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) holds per DEVICE and per kernel: every kernel (the template argument: one
+// instantiation of this function, so one `done` each, with no index to compute) keeps one bit per device ordinal of the calling
 // thread's current device (ordinals beyond 63 set the attribute on every launch).  Safe from concurrent host threads:
 // setting the attribute twice is harmless, the bit is set only after it succeeded.
-typedef std::atomic<unsigned long long> EnfAttrBits;
-inline bool enf_lds_attr(const void* kern, int bytes, EnfAttrBits& done) {
+template <auto Kern> inline bool enf_lds_attr(int bytes) {
+  static std::atomic<unsigned long long> done{0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return false;
   if (dev >= 0 && dev < 64 && ((done.load(std::memory_order_acquire) >> dev) & 1ull)) return true;
-  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
   if (dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_release);
   return true;
 }
@@ -24,7 +25,6 @@ inline bool enf_lds_attr(const void* kern, int bytes, EnfAttrBits& done) {
 // scratch and a fixed-order pass adds them; no result depends on the order in which workgroups finish.
 // K3's query split (grid.y): one workgroup per CU is resident (LDS), so the query tiles are split until all 256 CUs have one.
 // `zfold` = the launch runs the z-fold form (one workgroup per latent; otherwise one wave per latent, 8 per workgroup).
-inline bool enf_pair_bwd_zfold_fits(const EnfDims& m) { return (size_t)m.H * 2 * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu; }
 inline int enf_pair_bwd_nsplit(const EnfDims& m, bool zfold) {
   const long long wgs = zfold ? (long long)m.B * m.Z : ((long long)m.B * m.Z + 7) / 8;
   const int ntiles = (m.N + 15) / 16;
@@ -59,6 +59,12 @@ inline EnfDetWorkspace enf_det_workspace(const EnfDims& m, const EnfWorkspace& W
   return X;
 }
 
+// ---- the scratch of the z-fold pair kernels as their launchers take it (regions of EnfWorkspace, or enf_pair_forward's own)
+// forward: all NULL for the latent-split variant; ysplit: the partial sums of ENF_VARIANT_ZFOLD_ZSPLIT, or NULL
+struct EnfFoldFwd { char* wz; float* wzb; char* wzu; float* ysplit; };
+// backward: the [forward | backward] panel pairs and the bias vectors; NULL: the latent-split form
+struct EnfFoldBwd { const char* wzt; const float* wzb; };
+
 // ---- what the entry points that run on a workspace (enf_forward_stages, enf_backward_latents_ex, enf_fit_step,
 // enf_backward_all) derive from their arguments
 struct EnfCall {
@@ -70,6 +76,15 @@ struct EnfCall {
   char* ws;             // the workspace (also the key of its pending side-stream work)
   const char* blob;     // the packed weights
   float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  // the workspace's scratch of the z-fold pair kernels, where the shape resolves to them (all NULL otherwise)
+  EnfFoldFwd fold_fwd() const {
+    const bool zf = enf_use_zfold(m);
+    return {zf ? ws + W.wz : nullptr, zf ? F(W.wzb) : nullptr, zf ? ws + W.wzu : nullptr, enf_zfold_split(m) > 1 ? F(W.ysplit) : nullptr};
+  }
+  EnfFoldBwd fold_bwd() const {
+    const bool zb = enf_use_zfold_bwd(m);
+    return {zb ? ws + W.wzt : nullptr, zb ? F(W.wzb) : nullptr};
+  }
 };
 // Errors in their order of precedence: the descriptor's (enf_check_desc), ENF_EINVAL for a NULL pointer (`pointers_ok` is the
 // entry point's own set; `packed` and `workspace` are everybody's) or for a window without `sigma`, ENF_EWORKSPACE.
@@ -110,32 +125,32 @@ int enf_launch_prologue_bwd_wg(const EnfDims& m, const EnfLayout& L, const char*
 int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const float* lt, char* wz, float* wzb, char* wzu,
                   char* wzt, hipStream_t st);
 
-// ---- K2, the forward pair kernel (enf_pair_fwd.hip).  wz / wzb / wzu: scratch of the z-fold variant (EnfWorkspace), all NULL
-// for the latent-split variant; ysplit: the partial sums of ENF_VARIANT_ZFOLD_ZSPLIT, or NULL.
-//   run_fold   nonzero: the z-fold variant first builds its per-latent matrices (enf_launch_wz)
-//   run_pair   bit set: 1 = run the pair stage (without it the call is the fold alone), 2 = hand ybar to the tail as bf16 (the caller
-//              passes the same decision to the tail's opt & 2; with relu masks on a call that runs the masked kernels: ENF_EINVAL)
+// ---- K2, the forward pair kernel (enf_pair_fwd.hip).  zs: the scratch of the z-fold variant.  flags:
+//   ENF_PAIR_FOLD       the z-fold variant first builds its per-latent matrices (enf_launch_wz)
+//   ENF_PAIR_PAIR       run the pair stage (without it the call is the fold alone)
+//   ENF_PAIR_YBAR_HALF  hand ybar to the tail as bf16 (the caller passes the same decision to the tail's ENF_TAIL_YBAR_HALF; with relu
+//                       masks on a call that runs the masked kernels: ENF_EINVAL)
 //   spart      != NULL: the caller vouches that all B signals hold the same latent rows and query points (x_bstride == 0) and lends
 //              B N (HD + H) floats: where the call runs the latent-split kernel without relu masks and without the bf16 hand-off, and
 //              B > 1, it computes signal 0 alone, its latents in enf_shared_fwd_parts(m) parts (enf_layout.h), and a merge kernel
 //              writes every signal's rows of ybar / lse; elsewhere the argument is ignored
+enum EnfPairFwdFlags : unsigned { ENF_PAIR_FOLD = 1u, ENF_PAIR_PAIR = 2u, ENF_PAIR_YBAR_HALF = 4u };
 int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride, const float* lt,
-                        float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit, int run_fold, int run_pair,
-                        hipStream_t st, float* spart = nullptr);
+                        float* ybar, float* lse, const EnfFoldFwd& zs, unsigned flags, hipStream_t st, float* spart = nullptr);
 
 // ---- K3, the backward pair kernel (enf_pair_bwd.hip): ADDS to `dlt`.  store != NULL: the activation-store form (the K4 operands
-// of ENF_NUM_STORE(H) buffers); otherwise wzt / wzb != NULL selects the z-fold form.  dxq: d x per query (added to), or NULL.
+// of ENF_NUM_STORE(H) buffers); otherwise zs.wzt / zs.wzb != NULL selects the z-fold form.  dxq: d x per query (added to), or NULL.
 // part != NULL: deterministic mode -- the kernel stores its partial rows in `part` (enf_det_part_bytes) and, with dxq, its
 // per-latent query-gradient shares in `dxpart` (enf_det_dx_bytes); two reduction kernels then OVERWRITE `dlt` (splits in
 // order) and `dxq` (latents in order): no float atomic runs, `dlt` need not be zeroed.
 int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride, const float* lt,
-                        const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store, const char* wzt,
-                        const float* wzb, float* dxq, hipStream_t st, float* part = nullptr, float* dxpart = nullptr);
+                        const float* lse, const float* dybar, const float* delta, float* dlt, void* const* store, const EnfFoldBwd& zs,
+                        float* dxq, hipStream_t st, float* part = nullptr, float* dxpart = nullptr);
 
 // the shared-latent backward (enf_layout.h: enf_shared_backward_rule): signal 0's pairs once, on the unit-seeded dybar / delta, contracted
 // with dout (B, N) into all B Z rows of `dlt` (ADDS); ENF_EUNSUPPORTED where there is no such instantiation
 int enf_launch_pair_bwd_shared(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, const float* lt, const float* lse,
-                               const float* dybar, const float* delta, const float* dout, float* dlt, const char* wzt, const float* wzb,
+                               const float* dybar, const float* delta, const float* dout, float* dlt, const EnfFoldBwd& zs,
                                hipStream_t st);
 
 // ---- K4, X^T delta over the activation store (enf_xtd.hip)
@@ -164,21 +179,22 @@ inline int enf_wgrad_chunk(const EnfDims& m, size_t avail, Bytes bytes) {
 }
 
 // ---- the per-query tail (enf_tail.hip)
-//   bwd   0: forward (ybar -> out); nonzero: backward (dout -> dybar, delta)
-//   opt   bit set: 1 = forward: stash the pre-activations in `act`; backward: `act` holds them, skip the recompute
-//                  2 = forward only: ybar is bf16 (the pair kernel's run_pair & 2)
+//   ENF_TAIL_BWD        backward (dout -> dybar, delta); without it forward (ybar -> out)
+//   ENF_TAIL_STASH      forward: stash the pre-activations in `act`; backward: `act` holds them, skip the recompute
+//   ENF_TAIL_YBAR_HALF  forward only: ybar is bf16 (the pair kernel's ENF_PAIR_YBAR_HALF)
 // _wg: tdel != NULL (backward only) is the weight-gradient form -- it also leaves every layer's input (in `act`, in place of
 // the pre-activations) and delta (in `tdel`) for the X^T delta products of enf_train.hip
+enum EnfTailFlags : unsigned { ENF_TAIL_FWD = 0u, ENF_TAIL_BWD = 1u, ENF_TAIL_STASH = 2u, ENF_TAIL_YBAR_HALF = 4u };
 int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, const float* dout,
-                    float* dybar, float* delta, float* act, int bwd, int opt, hipStream_t st);
+                    float* dybar, float* delta, float* act, unsigned flags, hipStream_t st);
 int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, const float* dout,
-                       float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st);
+                       float* dybar, float* delta, float* act, float* tdel, unsigned flags, hipStream_t st);
 // the seeded tail backward (enf_field_grad): d out = the unit vector of output channel `seed` (0 <= seed < O), formed in registers --
-// no d out in memory; `act` holds the pre-activations a forward with opt & 1 stashed; writes d ybar and delta
+// no d out in memory; `act` holds the pre-activations a forward with ENF_TAIL_STASH stashed; writes d ybar and delta
 int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
                          float* act, hipStream_t st);
 // forward chain with the stash (and `out`, if given) and the seeded backward in ONE launch (the shared-latent fit step): the results of
-// enf_launch_tail(.., opt = 1) followed by enf_launch_tail_seed, bit for bit
+// enf_launch_tail(.., ENF_TAIL_STASH) followed by enf_launch_tail_seed, bit for bit
 int enf_launch_tail_fwd_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
                              float* delta, float* act, hipStream_t st);
 // the inner step's tail as one kernel: forward chain -> mean squared error against `target` (added to *loss) and its gradient ->

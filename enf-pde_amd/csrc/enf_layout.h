@@ -17,6 +17,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include <stdint.h>
+#include <limits.h>
 #include "../../include/enf_hip.h"
 
 #ifdef __HIPCC__
@@ -99,6 +100,57 @@ inline EnfDims enf_dims(const EnfDesc* d) {
   m.mask_B = d->mask_signals > 0 ? d->mask_signals : d->B;
   m.mask_b0 = 0;
   return m;
+}
+
+// ---- THE compiled (num_hidden D, heads H) set: every shape-templated kernel exists for these pairs, in bf16 and fp32, and for no
+// other.  enf_check_desc, the launchers (enf_for_shape) and the shared-backward rule all read this list.
+#define ENF_SHAPES(X) X(128, 2) X(64, 2) X(128, 1) X(64, 1) X(64, 4)
+// the subset with a SHARED instantiation of enf_pair_bwd_kernel (enf_pair_bwd_shared.hip)
+#define ENF_SHARED_BWD_SHAPES(X) X(128, 2) X(64, 2) X(128, 1)
+template <int D_, int H_, bool BF16_> struct EnfShape {
+  static constexpr int D = D_, H = H_;
+  static constexpr bool BF16 = BF16_;
+};
+#define ENF_SHAPE_IS(DD, HH) || (D == DD && H == HH)
+#define ENF_WIDTH_IS(DD, HH) || D == DD
+constexpr bool enf_shape_compiled(int D, int H) { return false ENF_SHAPES(ENF_SHAPE_IS); }
+constexpr bool enf_width_compiled(int D) { return false ENF_SHAPES(ENF_WIDTH_IS); }          // some H has this D
+constexpr bool enf_shape_shared_bwd(int D, int H) { return false ENF_SHARED_BWD_SHAPES(ENF_SHAPE_IS); }
+#undef ENF_SHAPE_IS
+#undef ENF_WIDTH_IS
+#define ENF_SHAPE_OK(DD, HH) static_assert(DD % 32 == 0 && HH <= 4, "panels are 32 wide; the latent table has room for 4 heads' c");
+ENF_SHAPES(ENF_SHAPE_OK)
+#undef ENF_SHAPE_OK
+#define ENF_SHAPE_OK(DD, HH) static_assert(enf_shape_compiled(DD, HH), "the shared backward's shapes are a subset of ENF_SHAPES");
+ENF_SHARED_BWD_SHAPES(ENF_SHAPE_OK)
+#undef ENF_SHAPE_OK
+// f(EnfShape<D, H, BF16>{}) for m's shape and precision (f: a generic callable returning an error code); ENF_EUNSUPPORTED outside the set
+template <class F> inline int enf_for_shape(const EnfDims& m, F&& f) {
+#define ENF_SHAPE_CALL(DD, HH) \
+  if (m.D == DD && m.H == HH) return m.bf16 ? f(EnfShape<DD, HH, true>{}) : f(EnfShape<DD, HH, false>{});
+  ENF_SHAPES(ENF_SHAPE_CALL)
+#undef ENF_SHAPE_CALL
+  return ENF_EUNSUPPORTED;
+}
+
+// ---- THE rule for "the pair kernels carry the invariant as a compile-time constant" (the shipped configs' bf16 kernels, dx = 2):
+// (128, 2) with rel_pos_periodic / latitude_periodic / polar_periodic, (64, 2) with ponita.  enf_spec_inv: the id to compile in, or -1.
+// Each launcher adds its own conditions (forward: no relu masks; backward: the z-fold form and one STORE kernel; shared: two of the four).
+#define ENF_SPEC_INVS(X) X(ENF_INV_REL_POS_PERIODIC) X(ENF_INV_LATITUDE_PERIODIC) X(ENF_INV_POLAR_PERIODIC) X(ENF_INV_PONITA)
+constexpr bool enf_spec_rule(int D, int H, bool bf16, int inv) {
+  if (!bf16 || H != 2) return false;
+  return D == 128 ? inv == ENF_INV_REL_POS_PERIODIC || inv == ENF_INV_LATITUDE_PERIODIC || inv == ENF_INV_POLAR_PERIODIC
+                  : D == 64 && inv == ENF_INV_PONITA;
+}
+inline int enf_spec_inv(const EnfDims& m) { return m.dx == 2 && enf_spec_rule(m.D, m.H, m.bf16 != 0, m.inv) ? m.inv : -1; }
+template <int INV_> struct EnfInv { static constexpr int INV = INV_; };
+// f(EnfInv<spec>{}) where shape S has that specialisation, else f(EnfInv<-1>{}): no kernel outside the rule is named
+template <class S, class F> inline int enf_for_spec(int spec, F&& f) {
+#define ENF_SPEC_CALL(ID) \
+  if constexpr (enf_spec_rule(S::D, S::H, S::BF16, ID)) { if (spec == ID) return f(EnfInv<ID>{}); }
+  ENF_SPEC_INVS(ENF_SPEC_CALL)
+#undef ENF_SPEC_CALL
+  return f(EnfInv<-1>{});
 }
 
 // bytes of a packed panel with R output rows (multiple of 16) and K inputs (multiple of 32)
@@ -232,7 +284,7 @@ inline EnfStreamK enf_streamk(long long tiles, int Z, int len_min) {
 inline EnfStreamK enf_zfold_streamk(const EnfDims& m) {
   const EnfStreamK none{0, 0, 1};
   const long long tiles = (long long)((m.N + 127) / 128) * m.B;
-  if (tiles * m.Z >= 0x7fffffffLL) return none;
+  if (tiles * m.Z >= INT_MAX) return none;
   if (m.var_fwd == ENF_VARIANT_ZFOLD_ZSPLIT) return m.Z >= 2 ? enf_streamk(tiles, m.Z, (m.Z + 2) / 3) : none;   // forced: <= 4 parts
   if (m.var_fwd != ENF_VARIANT_AUTO) return none;
   if (tiles >= 192 || m.Z < ENF_SK_MIN_Z) return none;
@@ -246,10 +298,11 @@ inline EnfStreamK enf_zfold_streamk(const EnfDims& m) {
 }
 // 0 = the latent-split kernel; 1 = the z-fold kernel, one workgroup per 128-query tile walking all latents; s >= 2 = the z-fold kernel over
 // equal runs of latent steps, a tile's latents in up to s parts
+// one signal's folded matrices sit behind a buffer resource with 32-bit offsets: beyond 2 GB per signal (Z >= 32768
+// at D = 128, H = 2) only the latent-split variant can run
+inline bool enf_pair_fwd_zfold_fits(const EnfDims& m) { return (size_t)m.Z * m.H * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu; }
 inline int enf_zfold_split(const EnfDims& m) {
-  // one signal's folded matrices sit behind a buffer resource with 32-bit offsets: beyond 2 GB per signal (Z >= 32768
-  // at D = 128, H = 2) only the latent-split variant can run
-  if ((long long)m.Z * m.H * (long long)m.D * m.D * (m.bf16 ? 2 : 4) >= 0x7fffffffLL) return 0;
+  if (!enf_pair_fwd_zfold_fits(m)) return 0;
   const EnfStreamK k = enf_zfold_streamk(m);
   if (k.parts > 1) return k.parts;
   if (m.var_fwd == ENF_VARIANT_ZFOLD_ZSPLIT) return 1;
@@ -294,6 +347,8 @@ inline bool enf_use_zfold_bwd(const EnfDims& m) {
   if (m.var_bwd != ENF_VARIANT_AUTO) return m.var_bwd == ENF_VARIANT_ZFOLD;
   return (long long)m.B * m.Z >= 192;
 }
+// its buffer resource spans one latent's [forward | backward] panel pairs of all heads
+inline bool enf_pair_bwd_zfold_fits(const EnfDims& m) { return (size_t)m.H * 2 * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu; }
 
 // The shared-latent backward (ENF_FIT_SHARED_LATENTS, first inner step): with equal latents and points every activation the z-fold
 // backward recomputes, and the tail's Jacobian, are the same for all B signals, and the map d out -> d(latent table) is linear in
@@ -304,14 +359,14 @@ inline bool enf_use_zfold_bwd(const EnfDims& m) {
 // 1 where a fit step with these flags takes that path.  per_value / err: the call carries per-channel weights / wants the per-point
 // errors (both keep the ordinary sequence).
 inline bool enf_pair_bwd_shared_exists(const EnfDims& m) {      // the SHARED instantiations of enf_pair_bwd_kernel (launch_shared)
-  return !m.ffn && !enf_inv_has_phase(m.inv) && ((m.D == 128 && (m.H == 2 || m.H == 1)) || (m.D == 64 && m.H == 2));
+  return !m.ffn && !enf_inv_has_phase(m.inv) && enf_shape_shared_bwd(m.D, m.H);
 }
 inline int enf_shared_backward_rule(const EnfDims& m, unsigned flags, bool per_value, bool err) {
   if (!(flags & ENF_FIT_SHARED_LATENTS) || (flags & ENF_FIT_DETERMINISTIC)) return 0;
   // the shared forward runs: more than one signal, the latent-split forward, relu masks off
   if (m.B < 2 || enf_use_zfold(m) || m.mask_mode != ENF_MASK_OFF || enf_shared_fwd_parts(m) < 1) return 0;
   if (m.O != 1 || per_value || err) return 0;
-  if (!enf_use_zfold_bwd(m) || (size_t)m.H * 2 * enf_panel_bytes(m.D, m.D, m.bf16) >= 0x7fffffffu) return 0;
+  if (!enf_use_zfold_bwd(m) || !enf_pair_bwd_zfold_fits(m)) return 0;
   return enf_pair_bwd_shared_exists(m) ? 1 : 0;
 }
 

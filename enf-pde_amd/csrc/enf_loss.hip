@@ -363,7 +363,7 @@ extern "C" int enf_fit_inputs_b(int ncomp, const EnfFitComponent* comps, int32_t
     A.comp[k] = comps[k];
     total += (int64_t)B * Z * comps[k].width;
   }
-  if ((total + 255) / 256 > (int64_t)0x7fffffff) return ENF_EDIM;
+  if ((total + 255) / 256 > (int64_t)INT_MAX) return ENF_EDIM;
   A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = N; A.Ns = Ns; A.S1 = S1; A.dx = dx; A.O = O;
   A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = weight; A.ws = ws;
   hipLaunchKernelGGL(enf_fit_inputs_b_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
@@ -423,7 +423,7 @@ extern "C" int enf_fit_inputs_cw(int ncomp, const EnfFitComponent* comps, int32_
     A.comp[k] = comps[k];
     total += (int64_t)B * Z * comps[k].width;
   }
-  if ((total + 255) / 256 > (int64_t)0x7fffffff) return ENF_EDIM;
+  if ((total + 255) / 256 > (int64_t)INT_MAX) return ENF_EDIM;
   A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = N; A.Ns = Ns; A.S1 = S1; A.dx = dx; A.O = O;
   A.coords = coords; A.img = img; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = cweight; A.ws = ws;
   hipLaunchKernelGGL(enf_fit_inputs_cw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A,

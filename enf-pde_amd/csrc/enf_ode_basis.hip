@@ -659,8 +659,7 @@ extern "C" int enf_ode_basis_forward(int64_t P, int I, int degree, int H1, int J
 
 template <int I, int H1T, int JT> static int ob_launch_bwd(ObArgs A, int nwg, hipStream_t st) {
   using C = ObBwd<I, H1T, JT>;
-  static EnfAttrBits attr{0};
-  if (!enf_lds_attr((const void*)enf_ode_basis_bwd_kernel<I, H1T, JT>, C::LDS_BYTES, attr)) return ENF_ELAUNCH;
+  if (!enf_lds_attr<enf_ode_basis_bwd_kernel<I, H1T, JT>>(C::LDS_BYTES)) return ENF_ELAUNCH;
   hipLaunchKernelGGL((enf_ode_basis_bwd_kernel<I, H1T, JT>), dim3(nwg), dim3(64 * OB_NW), C::LDS_BYTES, st, A);
   return ENF_OK;
 }

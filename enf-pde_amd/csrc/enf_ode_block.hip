@@ -305,9 +305,8 @@ extern "C" int enf_ode_block_forward(int64_t R, int H, int M, const float* x, co
 }
 
 template <int HT, int MT> static int bk_launch_bwd(const BkArgs& A, dim3 grid, hipStream_t st) {
-  static EnfAttrBits attr{0};
   constexpr int LDS = BkCfg<HT, MT>::LDS_BWD;
-  if (!enf_lds_attr((const void*)enf_ode_block_bwd_kernel<HT, MT>, LDS, attr)) return ENF_ELAUNCH;
+  if (!enf_lds_attr<enf_ode_block_bwd_kernel<HT, MT>>(LDS)) return ENF_ELAUNCH;
   hipLaunchKernelGGL((enf_ode_block_bwd_kernel<HT, MT>), grid, dim3(256), LDS, st, A);
   return ENF_OK;
 }

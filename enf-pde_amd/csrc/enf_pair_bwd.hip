@@ -1272,9 +1272,8 @@ __global__ __launch_bounds__(256) void enf_dxq_reduce_kernel(const float* __rest
 template <int D, int H, bool BF16, bool STORE, bool ZF, int INV = -1, bool FFN = false>
 static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
   using SM = PairBwdSmem<D, H, BF16, FFN>;
-  auto kern = enf_pair_bwd_kernel<D, H, BF16, STORE, ZF, INV, FFN>;
-  static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
-  if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
+  constexpr auto kern = enf_pair_bwd_kernel<D, H, BF16, STORE, ZF, INV, FFN>;
+  if (!enf_lds_attr<kern>(SM::TOTAL)) return ENF_ELAUNCH;
   dim3 grid(ZF ? A.B * A.Z : (A.B * A.Z + NWAVES - 1) / NWAVES, A.nsplit);
   if (ZF && A.xcd_remap) grid = dim3(A.B * A.Z * A.nsplit, 1);
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), SM::TOTAL, st, A);
@@ -1285,16 +1284,16 @@ static int launch_pair_bwd(const PairBwdArgs& A, hipStream_t st) {
 
 static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
                            const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
-                           void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st, float* part,
+                           void* const* store, const EnfFoldBwd& zs, float* dxq, hipStream_t st, float* part,
                            float* dxpart, int* nsplit);
 
 int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
                         const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
-                        void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st, float* part,
+                        void* const* store, const EnfFoldBwd& zs, float* dxq, hipStream_t st, float* part,
                         float* dxpart) {
   if (part && dxq && !dxpart) return ENF_EINVAL;
   int ns = 1;
-  if (int rc = pair_bwd_kernel(m, L, blob, x, x_bstride, lt, lse, dybar, delta, dlt, store, wzt, wzb, dxq, st, part,
+  if (int rc = pair_bwd_kernel(m, L, blob, x, x_bstride, lt, lse, dybar, delta, dlt, store, zs, dxq, st, part,
                                part ? dxpart : nullptr, &ns))
     return rc;
   if (!part) return 0;
@@ -1311,14 +1310,14 @@ int enf_launch_pair_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, 
 
 static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
                            const float* lt, const float* lse, const float* dybar, const float* delta, float* dlt,
-                           void* const* store, const char* wzt, const float* wzb, float* dxq, hipStream_t st, float* part,
+                           void* const* store, const EnfFoldBwd& zs, float* dxq, hipStream_t st, float* part,
                            float* dxpart, int* nsplit) {
   PairBwdArgs A;
   A.dxq = dxq; A.part = part; A.dxpart = dxpart;
   A.dout = nullptr; A.SB = 0;
   A.masks = store && m.mask_mode == ENF_MASK_READ ? m.masks : nullptr; A.mask_B = m.mask_B; A.mask_b0 = m.mask_b0;
-  const bool zf = !store && wzt && wzb && enf_pair_bwd_zfold_fits(m);
-  A.wzt = wzt; A.wzb = wzb; A.inv_d = 1.0f / (float)m.Dt;
+  const bool zf = !store && zs.wzt && zs.wzb && enf_pair_bwd_zfold_fits(m);
+  A.wzt = zs.wzt; A.wzb = zs.wzb; A.inv_d = 1.0f / (float)m.Dt;
   A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.lse = lse; A.dybar = dybar; A.delta = delta;
   A.dlt = dlt; A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
   // one workgroup per CU is resident (LDS): split the query tiles over grid.y until all 256 CUs have one
@@ -1329,47 +1328,28 @@ static int pair_bwd_kernel(const EnfDims& m, const EnfLayout& L, const char* blo
   A.xcd_remap = zf && ns > 1 && wgs % 8 == 0;
   if (store)
     for (int i = 0; i < ENF_NUM_STORE(m.H); ++i) A.store[i] = store[i];
-  if (m.ffn) {                 // the ffn embedding: every shape of the rff set, run-time invariant; no relu, so no masks
-    A.masks = nullptr;
-#define ENF_FFN_CASE(DD, HH)                                                                                                       \
-    if (m.D == DD && m.H == HH) {                                                                                                 \
-      if (store) return m.bf16 ? launch_pair_bwd<DD, HH, true, true, false, -1, true>(A, st) : launch_pair_bwd<DD, HH, false, true, false, -1, true>(A, st); \
-      if (zf) return m.bf16 ? launch_pair_bwd<DD, HH, true, false, true, -1, true>(A, st) : launch_pair_bwd<DD, HH, false, false, true, -1, true>(A, st); \
-      return m.bf16 ? launch_pair_bwd<DD, HH, true, false, false, -1, true>(A, st) : launch_pair_bwd<DD, HH, false, false, false, -1, true>(A, st);      \
+  if (m.ffn) A.masks = nullptr;      // the ffn embedding: every shape, run-time invariant; no relu, so no masks
+  // the invariant as a compile-time constant (enf_layout.h: enf_spec_inv; configs 2, 4, 5: rel_pos_periodic; config 3:
+  // latitude_periodic and the SO(3) polar_periodic; config 1: ponita at num_hidden 64): the z-fold kernels, and the training path's
+  // kernel (activation store) of the headline configs, rel_pos_periodic
+  const int spec = !m.ffn && (zf || (store && m.inv == ENF_INV_REL_POS_PERIODIC)) ? enf_spec_inv(m) : -1;
+  return enf_for_shape(m, [&](auto s) {
+    using S = decltype(s);
+    if (m.ffn) {
+      if (store) return launch_pair_bwd<S::D, S::H, S::BF16, true, false, -1, true>(A, st);
+      return zf ? launch_pair_bwd<S::D, S::H, S::BF16, false, true, -1, true>(A, st) : launch_pair_bwd<S::D, S::H, S::BF16, false, false, -1, true>(A, st);
     }
-    ENF_FFN_CASE(128, 2)
-    ENF_FFN_CASE(64, 2)
-    ENF_FFN_CASE(128, 1)
-    ENF_FFN_CASE(64, 1)
-    ENF_FFN_CASE(64, 4)
-#undef ENF_FFN_CASE
-    return ENF_EUNSUPPORTED;
-  }
-#define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH) {                                                            \
-    if (store) return m.bf16 ? launch_pair_bwd<DD, HH, true, true, false>(A, st) : launch_pair_bwd<DD, HH, false, true, false>(A, st); \
-    if (zf) return m.bf16 ? launch_pair_bwd<DD, HH, true, false, true>(A, st) : launch_pair_bwd<DD, HH, false, false, true>(A, st);    \
-    return m.bf16 ? launch_pair_bwd<DD, HH, true, false, false>(A, st) : launch_pair_bwd<DD, HH, false, false, false>(A, st);         \
-  }
-  // the z-fold bf16 kernels of the shipped configs with the invariant as a compile-time constant (configs 2, 4, 5:
-  // rel_pos_periodic; config 3: latitude_periodic and the SO(3) polar_periodic; config 1: ponita at num_hidden 64)
-  if (zf && m.bf16 && m.dx == 2) {
-    if (m.D == 128 && m.H == 2) {
-      if (m.inv == ENF_INV_REL_POS_PERIODIC) return launch_pair_bwd<128, 2, true, false, true, ENF_INV_REL_POS_PERIODIC>(A, st);
-      if (m.inv == ENF_INV_LATITUDE_PERIODIC) return launch_pair_bwd<128, 2, true, false, true, ENF_INV_LATITUDE_PERIODIC>(A, st);
-      if (m.inv == ENF_INV_POLAR_PERIODIC) return launch_pair_bwd<128, 2, true, false, true, ENF_INV_POLAR_PERIODIC>(A, st);
-    }
-    if (m.D == 64 && m.H == 2 && m.inv == ENF_INV_PONITA) return launch_pair_bwd<64, 2, true, false, true, ENF_INV_PONITA>(A, st);
-  }
-  // the training path's kernel (activation store) of the headline configs likewise
-  if (store && m.bf16 && m.dx == 2 && m.D == 128 && m.H == 2 && m.inv == ENF_INV_REL_POS_PERIODIC)
-    return launch_pair_bwd<128, 2, true, true, false, ENF_INV_REL_POS_PERIODIC>(A, st);
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-  ENF_CASE(64, 1)
-  ENF_CASE(64, 4)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
+    return enf_for_spec<S>(spec, [&](auto i) {
+      if constexpr (i.INV < 0) {
+        if (store) return launch_pair_bwd<S::D, S::H, S::BF16, true, false>(A, st);
+        return zf ? launch_pair_bwd<S::D, S::H, S::BF16, false, true>(A, st) : launch_pair_bwd<S::D, S::H, S::BF16, false, false>(A, st);
+      } else {
+        if constexpr (i.INV == ENF_INV_REL_POS_PERIODIC) {
+          if (store) return launch_pair_bwd<S::D, S::H, S::BF16, true, false, i.INV>(A, st);
+        }
+        return launch_pair_bwd<S::D, S::H, S::BF16, false, true, i.INV>(A, st);      // (`spec` >= 0 without `store`: zf)
+      }
+    });
+  });
 }
 #endif  // ENF_PAIR_BWD_KERNEL_ONLY

@@ -68,14 +68,6 @@ extern "C" int enf_debug_read_stamps(unsigned long long* dst) {
 // relu-mask modes live in their own instantiation (MASKS): as wave-uniform runtime branches in the one kernel they cost
 // the default path 1.3 % (measured)
 #define K2_MASK_MODE (MASKS && !FFN ? A.mask_mode : 0)
-#ifndef ENF_ZFOLD_WAVES
-#define ENF_ZFOLD_WAVES 8
-#endif
-
-// waves per workgroup: the z-fold variant runs TWO independent 4-wave workgroups per CU (one wave of each
-// per SIMD) so that the SIMD-mates never meet at a barrier: while one computes its MFMA stage the other
-// keeps the vector ALU busy (8-wave lockstep measured 2 V + M per stage, M = the younger wave's MFMAs).
-template <bool ZFOLD> struct PairWaves { static constexpr int NW = ZFOLD && ENF_ZFOLD_WAVES == 4 ? 4 : NWAVES; };
 
 // The shared D x D weight panels of a latent step, in the order the step multiplies by them.  (The gamma/beta panels are one per
 // head and twice the size, the z-fold's W_zh are per latent: both always stream.)
@@ -139,12 +131,12 @@ template <int D, int H, bool BF16, int NW, bool FFN = false, bool ZFOLD = false,
 // a latent step starts at the AF panel (the relu-layer panels aq1 / av1 and the relu masks do not exist)
 // RES: keep the resident set of PairSmem in LDS for the workgroup's lifetime and stream only the other panels through the ring
 template <int D, int H, bool BF16, bool ZFOLD, bool MASKS, int INV = -1, bool FFN = false, bool RES = true>
-__global__ __launch_bounds__(64 * PairWaves<ZFOLD>::NW, 2) void enf_pair_fwd_kernel(PairFwdArgs A) {
+__global__ __launch_bounds__(NTHREADS, 2) void enf_pair_fwd_kernel(PairFwdArgs A) {
   const int inv_id = INV >= 0 ? INV : A.inv;
   const int dx_ = INV >= 0 ? 2 : A.dx;
   using Cfg = PairCfg<D, BF16>;
-  constexpr int NW = PairWaves<ZFOLD>::NW, NTH = 64 * NW;
-  using SM = PairSmem<D, H, BF16, NW, FFN, ZFOLD, RES && NW == NWAVES>;
+  constexpr int NW = NWAVES, NTH = NTHREADS;
+  using SM = PairSmem<D, H, BF16, NW, FFN, ZFOLD, RES>;
   constexpr int KB = Cfg::KB, NT = Cfg::NT;
   constexpr int ST_DD = Cfg::DD::STAGE, ST_GB = Cfg::GB::STAGE, PANEL_GB = Cfg::GB::BYTES, PANEL_DD = Cfg::DD::BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -609,16 +601,14 @@ static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
     if (g_test_streamed) return launch_pair_fwd<D, H, BF16, ZFOLD, MASKS, INV, FFN, false>(A, st);
   }
 #endif
-  constexpr int NW = PairWaves<ZFOLD>::NW;
-  using SM = PairSmem<D, H, BF16, NW, FFN, ZFOLD, RES && NW == NWAVES>;
-  auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV, FFN, RES>;
-  static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
-  if (!enf_lds_attr(reinterpret_cast<const void*>(kern), SM::TOTAL, attr_done)) return ENF_ELAUNCH;
+  using SM = PairSmem<D, H, BF16, NWAVES, FFN, ZFOLD, RES>;
+  constexpr auto kern = enf_pair_fwd_kernel<D, H, BF16, ZFOLD, MASKS, INV, FFN, RES>;
+  if (!enf_lds_attr<kern>(SM::TOTAL)) return ENF_ELAUNCH;
   dim3 grid((A.N + 16 * A.qg - 1) / (16 * A.qg), A.B);
   if (ZFOLD && A.zsplit > 1) grid = dim3((unsigned)(((long long)grid.x * A.B * A.Z + A.sk_len - 1) / A.sk_len));
   const bool shared = !ZFOLD && A.spart != nullptr;
   if (shared) grid.y = (unsigned)A.parts;
-  hipLaunchKernelGGL(kern, grid, dim3(64 * NW), SM::TOTAL, st, A);
+  hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), SM::TOTAL, st, A);
   if (shared) {
     const long long tot = (long long)A.N * (H * D / 4);
     hipLaunchKernelGGL(enf_shared_merge_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)(A.bcast < 4 ? A.bcast : 4)), dim3(256), 0, st,
@@ -634,72 +624,46 @@ static int launch_pair_fwd(const PairFwdArgs& A, hipStream_t st) {
 
 // relu masks: per call (EnfDims.masks / mask_mode / mask_B, from the descriptor)
 int enf_launch_pair_fwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* x, long long x_bstride,
-                        const float* lt, float* ybar, float* lse, char* wz, float* wzb, char* wzu, float* ysplit,
-                        int run_fold, int run_pair, hipStream_t st, float* spart) {
+                        const float* lt, float* ybar, float* lse, const EnfFoldFwd& zs, unsigned flags, hipStream_t st, float* spart) {
+  const bool run_pair = flags & ENF_PAIR_PAIR, yhalf = flags & ENF_PAIR_YBAR_HALF;
   PairFwdArgs A;
-  A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.ybar = ybar; A.lse = lse; A.wz = wz; A.wzb = wzb; A.wzu = wzu; A.inv_d = 1.0f / (float)m.Dt;
+  A.x = x; A.x_bstride = x_bstride; A.lt = lt; A.blob = blob; A.L = L; A.ybar = ybar; A.lse = lse; A.wz = zs.wz; A.wzb = zs.wzb; A.wzu = zs.wzu; A.inv_d = 1.0f / (float)m.Dt;
   A.B = m.B; A.N = m.N; A.Z = m.Z; A.dx = m.dx; A.inv = m.inv; A.use_window = m.use_window;
-  A.masks = m.masks; A.mask_mode = (run_pair & 1) && !m.ffn ? m.mask_mode : 0; A.mask_B = m.mask_B;   // (ffn: no relu, no masks)
+  A.masks = m.masks; A.mask_mode = run_pair && !m.ffn ? m.mask_mode : 0; A.mask_B = m.mask_B;   // (ffn: no relu, no masks)
   // the bf16 hand-off is the caller's decision, made once for this launcher and the tail's (enf_api.hip: yhalf).  The masked
   // instantiations store fp32 rows only: a caller that asks for both has decided wrongly -- refused, not answered with fp32 rows
   // that its tail would read as bf16
-  if ((run_pair & 2) && A.mask_mode) return ENF_EINVAL;
+  if (yhalf && A.mask_mode) return ENF_EINVAL;
   // as many latent splits as there are latents to split (up to 8); the rest of the 8 waves take more queries
   static_assert(NWAVES == 8, "enf_latent_splits (enf_layout.h) splits 8 waves");
   A.qg = NWAVES / enf_latent_splits(m.Z);
-  const bool zfold = wz && wzb && wzu && (size_t)m.Z * m.H * enf_panel_bytes(m.D, m.D, m.bf16) < 0x7fffffffu;
+  const bool zfold = zs.wz && zs.wzb && zs.wzu && enf_pair_fwd_zfold_fits(m);
   const EnfStreamK sk = enf_zfold_streamk(m);
-  A.zsplit = zfold && ysplit && sk.parts > 1 ? sk.parts : 1;
+  A.zsplit = zfold && zs.ysplit && sk.parts > 1 ? sk.parts : 1;
   A.sk_len = A.zsplit > 1 ? sk.len : 0;
-  A.ysplit = ysplit;
-  A.ybar_half = (run_pair & 2) && A.zsplit == 1 && m.bf16;
+  A.ysplit = zs.ysplit;
+  A.ybar_half = yhalf && A.zsplit == 1 && m.bf16;
   A.xcd_remap = zfold && m.B % 8 == 0 && A.zsplit == 1;
   // the shared-latent forward is a permission: it runs on the latent-split kernel, without relu masks, with ybar in fp32
-  const int sparts = spart && !zfold && !A.mask_mode && (run_pair & 3) == 1 ? enf_shared_fwd_parts(m) : 0;
+  const int sparts = spart && !zfold && !A.mask_mode && run_pair && !yhalf ? enf_shared_fwd_parts(m) : 0;
   A.spart = sparts ? spart : nullptr; A.parts = sparts ? sparts : 1; A.bcast = sparts ? m.B : 1;
   if (zfold) {
-    A.qg = PairWaves<true>::NW;
-    if (run_fold) {
-      int rc = enf_launch_wz(m, L, blob, lt, wz, wzb, wzu, nullptr, st);
+    A.qg = NWAVES;
+    if (flags & ENF_PAIR_FOLD) {
+      int rc = enf_launch_wz(m, L, blob, lt, zs.wz, zs.wzb, zs.wzu, nullptr, st);
       if (rc) return rc;
     }
   }
-  if (!(run_pair & 1)) return 0;
-  if (m.ffn) {                 // the ffn embedding: every shape of the rff set, run-time invariant
-#define ENF_FFN_CASE(DD, HH)                                                                                                      \
-    if (m.D == DD && m.H == HH) {                                                                                                \
-      if (zfold) return m.bf16 ? launch_pair_fwd<DD, HH, true, true, false, -1, true>(A, st) : launch_pair_fwd<DD, HH, false, true, false, -1, true>(A, st); \
-      return m.bf16 ? launch_pair_fwd<DD, HH, true, false, false, -1, true>(A, st) : launch_pair_fwd<DD, HH, false, false, false, -1, true>(A, st);         \
-    }
-    ENF_FFN_CASE(128, 2)
-    ENF_FFN_CASE(64, 2)
-    ENF_FFN_CASE(128, 1)
-    ENF_FFN_CASE(64, 1)
-    ENF_FFN_CASE(64, 4)
-#undef ENF_FFN_CASE
-    return ENF_EUNSUPPORTED;
-  }
-#define ENF_CASE(DD, HH)                                                                                      \
-  if (m.D == DD && m.H == HH) {                                                                               \
-    if (zfold) return m.bf16 ? launch_pair_fwd<DD, HH, true, true>(A, st) : launch_pair_fwd<DD, HH, false, true>(A, st); \
-    return m.bf16 ? launch_pair_fwd<DD, HH, true, false>(A, st) : launch_pair_fwd<DD, HH, false, false>(A, st);         \
-  }
-  if (m.bf16 && m.dx == 2 && !A.mask_mode) {       // the shipped configs' bf16 kernels with the invariant fixed at compile time
-    if (m.D == 128 && m.H == 2) {
-#define ENF_SPEC(INVID)                                                                                                  \
-      if (m.inv == INVID) return zfold ? launch_pair_fwd<128, 2, true, true, false, INVID>(A, st)                          \
-                                       : launch_pair_fwd<128, 2, true, false, false, INVID>(A, st);
-      ENF_SPEC(ENF_INV_REL_POS_PERIODIC) ENF_SPEC(ENF_INV_LATITUDE_PERIODIC) ENF_SPEC(ENF_INV_POLAR_PERIODIC)
-#undef ENF_SPEC
-    }
-    if (m.D == 64 && m.H == 2 && m.inv == ENF_INV_PONITA)
-      return zfold ? launch_pair_fwd<64, 2, true, true, false, ENF_INV_PONITA>(A, st) : launch_pair_fwd<64, 2, true, false, false, ENF_INV_PONITA>(A, st);
-  }
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-  ENF_CASE(64, 1)
-  ENF_CASE(64, 4)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
+  if (!run_pair) return 0;
+  // the ffn embedding: every shape, run-time invariant; rff: the shipped configs' bf16 kernels with the invariant fixed at compile
+  // time (enf_layout.h: enf_spec_inv), here without relu masks only
+  const int spec = m.ffn || A.mask_mode ? -1 : enf_spec_inv(m);
+  return enf_for_shape(m, [&](auto s) {
+    using S = decltype(s);
+    if (m.ffn)
+      return zfold ? launch_pair_fwd<S::D, S::H, S::BF16, true, false, -1, true>(A, st) : launch_pair_fwd<S::D, S::H, S::BF16, false, false, -1, true>(A, st);
+    return enf_for_spec<S>(spec, [&](auto i) {
+      return zfold ? launch_pair_fwd<S::D, S::H, S::BF16, true, false, i.INV>(A, st) : launch_pair_fwd<S::D, S::H, S::BF16, false, false, i.INV>(A, st);
+    });
+  });
 }

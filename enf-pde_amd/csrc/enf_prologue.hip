@@ -1,8 +1,8 @@
-// enf_prologue.hip -- K1, the latent prologue: the forward kernel and its backward, on the vector ALU and on the matrix pipe.
+// enf_prologue.hip -- K1, the latent prologue: the forward kernel on the vector ALU, its backward on the matrix pipe.
 //
 // The per-latent part of the decoder (NEF:220, NEF:56, ECA:93-94 and the logit fold of enf_pack.hip):
 //   s = a Ws + bs -> LayerNorm -> an;  k = an Wk + bk;  v0 = an Wv + bv;  u_h = MU_h k_h;  c_h = cvec_h . k_h
-// is a chain of small dense products over the B Z latent rows.  The first form (enf_prologue_kernel, enf_prologue_bwd_kernel: 4 latents
+// is a chain of small dense products over the B Z latent rows.  The first form (enf_prologue_kernel: 4 latents
 // per workgroup, one output feature per thread, weights streamed from L2 per workgroup) is bound by the latency of that stream -- every
 // workgroup reads all 392 KB of prologue weights for 4 latents: 100 MB of L2 traffic per call, 20 us forward / 35 us backward for
 // 0.2 GFLOP, three times per inner step.  In the second (enf_prologue_bwd_mfma_kernel, fp32 `v_mfma_f32_16x16x4_f32`) a workgroup takes
@@ -10,8 +10,8 @@
 // element is read once per 16 latents as an A-operand dword (coalesced: the output index on the lanes), activations sit in LDS as
 // [feature][latent] (the B operand is one conflict-free ds_read_b32), accumulator tiles go back to LDS as the next layer's input.  Same
 // arithmetic (fp32 throughout), same buffers (`an`, `kv`, latent table, `pg`).
-// The forward runs in the first form (20.0 us against 21.0 on the matrix pipe), the backward in the second where D % 32 == 0 (25.5 us
-// against 32.0).
+// The forward runs in the first form (20.0 us against 21.0 on the matrix pipe), the backward in the second (25.5 us against 32.0 in
+// the first form, which is no longer in the tree: every compiled width is a multiple of 32, so nothing could reach it).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <type_traits>
@@ -208,167 +208,6 @@ int enf_launch_prologue(const EnfDims& m, const EnfLayout& L, const char* blob, 
   const size_t smem = sizeof(float) * (ZT * m.C + ZT * m.D + ZT * m.HD);
   hipLaunchKernelGGL(enf_prologue_kernel, dim3((A.BZ + ZT - 1) / ZT), dim3(256), smem, st, A);
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
-
-// ---------------------------------------------------------------- K1 backward
-// dlt (B*Z rows: du | dv0 | dc | dpose | dwcoef) -> dp, da, dsigma.  Same scheme as the forward: gradient rows
-// staged in LDS as [feature][latent], the reduction index off the lanes (mu as stored is [h][i][d], i.e. the
-// output d of the transposed product is contiguous; a_to_k / a_to_v use their transposed copies wkT / wvT).
-struct PrologueBwdArgs {
-  const float* p; const float* sigma; const char* blob; EnfLayout L;
-  const float* an; const float* kv; const float* dlt;
-  float* dp; float* da; float* dsigma;
-  int BZ, H, D, C, dp_dim, inv;
-  int Dt;
-  float* pg;     // weight-gradient backward (or NULL): per latent row [d k (HD) | d an (D) | d s (D) | an (D) | d an * xn (D) | d c_h k_h (HD)],
-                 // the operands of the prologue's X^T delta products and column sums (enf_train.hip); an = the LayerNorm's affine output
-};
-
-__global__ __launch_bounds__(256) void enf_prologue_bwd_kernel(PrologueBwdArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int D = A.D, H = A.H, HD = H * D, C = A.C;
-  float* s_du = sm;                    // [HD][ZT]  d u
-  float* s_dk = s_du + ZT * HD;        // [2HD][ZT] d k | d v0
-  float* s_dan = s_dk + ZT * 2 * HD;   // [D][ZT]
-  float* s_dc = s_dan + ZT * D;        // [H][ZT]
-  float* s_part = s_dc + ZT * H;       // [256][ZT] partial sums of the d(an) stage
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row0 = blockIdx.x * ZT;
-  const int stride = enf_lt_stride(H, D);
-  auto W = [&](size_t off) { return reinterpret_cast<const float*>(A.blob + off); };
-  for (int t = tid; t < ZT * HD; t += 256) {
-    const int zz = t / HD, j = t % HD, r = row0 + zz;
-    const float* g = A.dlt + (size_t)(r < A.BZ ? r : 0) * stride;
-    s_du[j * ZT + zz] = r < A.BZ ? g[enf_lt_off_u(H, D) + j] : 0.f;
-    s_dk[(HD + j) * ZT + zz] = r < A.BZ ? g[enf_lt_off_v0(H, D) + j] : 0.f;
-  }
-  if (tid < ZT * H) {
-    const int zz = tid / H, h = tid % H, r = row0 + zz;
-    s_dc[h * ZT + zz] = r < A.BZ ? A.dlt[(size_t)r * stride + enf_lt_off_c(H, D) + h] : 0.f;
-  }
-  __syncthreads();
-  // dk[h*D+d] = sum_i MU_h[i][d] du_h[i] + cvec_h[d] dc_h
-  for (int j = tid; j < HD; j += 256) {
-    const int h = j / D, dd = j % D;
-    const float cv = W(A.L.cvec)[h * D + dd];
-    const float* mu = W(A.L.mu) + (size_t)h * D * D + dd;
-    float acc[ZT];
-#pragma unroll
-    for (int zz = 0; zz < ZT; ++zz) acc[zz] = cv * s_dc[h * ZT + zz];
-#pragma unroll PRO_UNROLL
-    for (int i = 0; i < D; ++i) {
-      const float w = mu[(size_t)i * D];
-      const float* gp = s_du + (h * D + i) * ZT;
-#pragma unroll
-      for (int q = 0; q < ZT / 4; ++q) {
-        const pf4 x = *reinterpret_cast<const pf4*>(gp + 4 * q);
-#pragma unroll
-        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(x[zz], w, acc[4 * q + zz]);
-      }
-    }
-#pragma unroll
-    for (int zz = 0; zz < ZT; ++zz) {
-      s_dk[j * ZT + zz] = acc[zz];
-      if (A.pg && row0 + zz < A.BZ) {
-        float* pr = A.pg + (size_t)(row0 + zz) * (2 * HD + 4 * D);
-        pr[j] = acc[zz];
-        pr[HD + 4 * D + j] = s_dc[h * ZT + zz] * A.kv[(size_t)(row0 + zz) * 2 * HD + j];
-      }
-    }
-  }
-  __syncthreads();
-  // d(an_affine)[d] = sum_j Wk[d][j] dk[j] + Wv[d][j] dv0[j]  (wkT/wvT: [j][d]); then through scale: dxn = dy * g.
-  // D outputs only: the 256 / D thread groups each take a slice of j and the partial sums meet in LDS
-  {
-    const int nsplit = 256 / D, d = tid % D, part = tid / D, jper = HD / nsplit;
-    float acc[ZT];
-#pragma unroll
-    for (int zz = 0; zz < ZT; ++zz) acc[zz] = 0.f;
-    const float* wkt = W(A.L.wkt) + d;
-    const float* wvt = W(A.L.wvt) + d;
-#pragma unroll PRO_UNROLL
-    for (int j = part * jper; j < (part + 1) * jper; ++j) {
-      const float wk = wkt[(size_t)j * D], wv = wvt[(size_t)j * D];
-#pragma unroll
-      for (int q = 0; q < ZT / 4; ++q) {
-        const pf4 kq = *reinterpret_cast<const pf4*>(s_dk + j * ZT + 4 * q), vq = *reinterpret_cast<const pf4*>(s_dk + (HD + j) * ZT + 4 * q);
-#pragma unroll
-        for (int zz = 0; zz < 4; ++zz) acc[4 * q + zz] = fmaf(wk, kq[zz], fmaf(wv, vq[zz], acc[4 * q + zz]));
-      }
-    }
-#pragma unroll
-    for (int zz = 0; zz < ZT; ++zz) s_part[tid * ZT + zz] = acc[zz];
-    __syncthreads();
-    if (tid < D) {
-      const float g = W(A.L.lna_g)[tid];
-#pragma unroll
-      for (int zz = 0; zz < ZT; ++zz) {
-        float v = 0.f;
-        for (int q = 0; q < nsplit; ++q) v += s_part[(q * D + tid) * ZT + zz];
-        s_dan[tid * ZT + zz] = v * g;
-        if (A.pg && row0 + zz < A.BZ) {
-          float* pr = A.pg + (size_t)(row0 + zz) * (2 * HD + 4 * D) + HD;
-          const float xn = A.an[(size_t)(row0 + zz) * (2 * D + 2) + D + tid];
-          pr[tid] = v;
-          pr[2 * D + tid] = xn * g + W(A.L.lna_b)[tid];
-          pr[3 * D + tid] = v * xn;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // LayerNorm backward: ds = rstd * (dxn - mean(dxn) - xn * mean(dxn * xn)); one wave per row
-  for (int zz = wave; zz < ZT; zz += 4) {
-    const int r = row0 + zz;
-    const int rr = r < A.BZ ? r : A.BZ - 1;
-    const float* anr = A.an + (size_t)rr * (2 * D + 2);
-    float v1 = 0.f, v2 = 0.f;
-    for (int d = lane; d < D; d += 64) { const float g = s_dan[d * ZT + zz]; v1 += g; v2 += g * anr[D + d]; }
-    const float m1 = wave_sum(v1) / A.Dt, m2 = wave_sum(v2) / A.Dt;
-    const float rstd = anr[2 * D + 1];
-    for (int d = lane; d < D; d += 64) {
-      const float ds = rstd * (s_dan[d * ZT + zz] - m1 - anr[D + d] * m2);
-      s_dan[d * ZT + zz] = ds;
-      if (A.pg && r < A.BZ) A.pg[(size_t)r * (2 * HD + 4 * D) + HD + D + d] = ds;
-    }
-  }
-  __syncthreads();
-  // da[c] = sum_d Ws[c][d] ds[d]
-  for (int t = tid; t < ZT * C; t += 256) {
-    const int zz = t / C, c = t % C, r = row0 + zz;
-    float sacc = 0.f;
-#pragma unroll PRO_UNROLL
-    for (int d = 0; d < D; ++d) sacc = fmaf(W(A.L.stem_w)[(size_t)c * D + d], s_dan[d * ZT + zz], sacc);
-    if (r < A.BZ) A.da[(size_t)r * C + c] = sacc;
-  }
-  if (tid < ZT) {
-    const int r = row0 + tid;
-    if (r < A.BZ) {
-      const float* g = A.dlt + (size_t)r * stride + enf_lt_off_pose(H, D);
-      const float* pp = A.p + (size_t)r * A.dp_dim;
-      float* o = A.dp + (size_t)r * A.dp_dim;
-      const bool sph = A.inv == ENF_INV_LATITUDE_PERIODIC || A.inv == ENF_INV_POLAR_PERIODIC || enf_inv_has_phase(A.inv);
-      if (A.inv == ENF_INV_PONITA || A.inv == ENF_INV_PONITA_FULL) { o[0] = g[0]; o[1] = g[1]; o[2] = -sinf(pp[2]) * g[2] + cosf(pp[2]) * g[3]; }
-      else if (sph) { o[0] = g[0]; o[1] = g[1] + cosf(pp[1]) * g[2] - sinf(pp[1]) * g[3]; }
-      else { for (int i = 0; i < A.dp_dim && i < 3; ++i) o[i] = g[i]; }
-      if (enf_inv_has_phase(A.inv)) {
-        const float* e = A.dlt + (size_t)r * stride + enf_lt_off_ext(H, D);     // d R (9) | d(latent-only invariants) (2)
-        if (A.inv == ENF_INV_BALL) {
-          const float ca = cosf(pp[0]), sa = sinf(pp[0]), cb = cosf(pp[1]), sb = sinf(pp[1]), cg = cosf(pp[2]), sg2 = sinf(pp[2]);
-          // chain rule through R(alpha, beta, gamma)
-          o[0] += e[0] * (-sa * cb) + e[1] * (-sa * sb * sg2 - ca * cg) + e[2] * (-sa * sb * cg + ca * sg2) +
-                  e[3] * (ca * cb) + e[4] * (ca * sb * sg2 - sa * cg) + e[5] * (ca * sb * cg + sa * sg2);
-          o[1] += e[0] * (-ca * sb) + e[1] * (ca * cb * sg2) + e[2] * (ca * cb * cg) + e[3] * (-sa * sb) + e[4] * (sa * cb * sg2) +
-                  e[5] * (sa * cb * cg) + e[6] * (-cb) + e[7] * (-sb * sg2) + e[8] * (-sb * cg);
-          o[2] = e[1] * (ca * sb * cg + sa * sg2) + e[2] * (-ca * sb * sg2 + sa * cg) + e[4] * (sa * sb * cg - ca * sg2) +
-                 e[5] * (-sa * sb * sg2 - ca * cg) + e[7] * (cb * cg) + e[8] * (-cb * sg2);
-          o[3] = e[9];
-        } else { o[1] += e[9]; o[2] = 0.f; o[3] = e[10]; }
-      }
-      const float sg = A.sigma ? A.sigma[r] : 1.f;
-      const float dwc = A.dlt[(size_t)r * stride + enf_lt_off_wcoef(H, D)];
-      A.dsigma[r] = (sph ? -1.f : -2.f) / (sg * sg * sg) * dwc;
-    }
-  }
 }
 
 // ---------------------------------------------------------------- K1 backward on the matrix pipe, 16 latents per workgroup
@@ -592,35 +431,21 @@ __global__ __launch_bounds__(64 * PW) void enf_prologue_bwd_mfma_kernel(ProBwdAr
 }
 }  // namespace
 
-static int enf_launch_prologue_bwd_mfma(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p, const float* sigma,
-                                        const float* an, const float* kv, const float* dlt, float* dp, float* da, float* dsigma,
-                                        float* pg, hipStream_t st) {
-  ProBwdArgs A;
-  A.p = p; A.sigma = sigma; A.blob = blob; A.L = L; A.an = an; A.kv = kv; A.dlt = dlt;
-  A.dp = dp; A.da = da; A.dsigma = dsigma; A.pg = pg;
-  A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
-  const size_t smem = sizeof(float) * LT * (3 * m.HD + m.D + m.H);
-  static EnfAttrBits attr{0};
-  if (!enf_lds_attr(reinterpret_cast<const void*>(enf_prologue_bwd_mfma_kernel), 160 * 1024, attr)) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(enf_prologue_bwd_mfma_kernel, dim3((A.BZ + LT - 1) / LT), dim3(64 * PW), smem, st, A);
-  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
-
 int enf_launch_prologue_bwd(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p,
                             const float* sigma, const float* an, const float* kv, const float* dlt, float* dp,
                             float* da, float* dsigma, hipStream_t st) {
   return enf_launch_prologue_bwd_wg(m, L, blob, p, sigma, an, kv, dlt, dp, da, dsigma, nullptr, st);
 }
+// (the kernel's tiles need D % 32 == 0: every compiled width is, enf_layout.h's static_assert over ENF_SHAPES)
 int enf_launch_prologue_bwd_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* p,
                                const float* sigma, const float* an, const float* kv, const float* dlt, float* dp,
                                float* da, float* dsigma, float* pg, hipStream_t st) {
-  if (m.D % 32 == 0) return enf_launch_prologue_bwd_mfma(m, L, blob, p, sigma, an, kv, dlt, dp, da, dsigma, pg, st);
-  PrologueBwdArgs A;
-  A.pg = pg;
+  ProBwdArgs A;
   A.p = p; A.sigma = sigma; A.blob = blob; A.L = L; A.an = an; A.kv = kv; A.dlt = dlt;
-  A.dp = dp; A.da = da; A.dsigma = dsigma;
+  A.dp = dp; A.da = da; A.dsigma = dsigma; A.pg = pg;
   A.BZ = m.B * m.Z; A.H = m.H; A.D = m.D; A.C = m.C; A.dp_dim = m.dp; A.inv = m.inv; A.Dt = m.Dt;
-  const size_t smem = sizeof(float) * (ZT * 3 * m.HD + ZT * m.D + ZT * m.H + ZT * 256);
-  hipLaunchKernelGGL(enf_prologue_bwd_kernel, dim3((A.BZ + ZT - 1) / ZT), dim3(256), smem, st, A);
+  const size_t smem = sizeof(float) * LT * (3 * m.HD + m.D + m.H);
+  if (!enf_lds_attr<enf_prologue_bwd_mfma_kernel>(160 * 1024)) return ENF_ELAUNCH;
+  hipLaunchKernelGGL(enf_prologue_bwd_mfma_kernel, dim3((A.BZ + LT - 1) / LT), dim3(64 * PW), smem, st, A);
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }

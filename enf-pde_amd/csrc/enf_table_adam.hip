@@ -113,7 +113,7 @@ extern "C" int enf_table_adam_update(int nseg, const EnfAdamSegment* segs, int64
     A.vec[k] = v4 ? 4 : 1;
     A.units[k] = n / A.vec[k];
     A.total += A.units[k];
-    if (n > (int64_t)0x7fffffff) A.wide = 1;
+    if (n > (int64_t)INT_MAX) A.wide = 1;
   }
   A.idx = idx; A.nseg = nseg; A.Z = Z; A.nidx = nidx;
   A.lr = lr; A.b1 = b1; A.b2 = b2; A.omb1 = 1.f - b1; A.omb2 = 1.f - b2; A.eps = eps; A.c1 = c1; A.c2 = c2;

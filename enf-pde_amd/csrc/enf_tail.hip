@@ -565,201 +565,148 @@ constexpr bool TAIL_LOSS_AW_ALL = true;       // the fused loss in every AW (tes
 constexpr bool TAIL_LOSS_AW_ALL = false;
 #endif
 
-template <int D, int H, bool BF16>
-static int launch_tail(const TailArgs& A, bool bwd, bool opt, hipStream_t st, bool cw = false, bool eval = false, bool seeded = false) {
-  const bool wg = bwd && A.tdel != nullptr;
-  const bool fused_loss = bwd && A.target != nullptr;
-  using T = TailCfg<D, H, BF16>;
-  // fewer active waves: the forward forms and the seeded backward forms.  Deterministic mode keeps eight (the partial-sum slots
-  // enf_launch_loss_sum reads are those of the 8-wave grid); so do the d out and weight-gradient backward.
+// ---- the launch forms: which kernel template, with which template arguments
+enum TailForm {
+  TF_FWD, TF_FWD_STASH, TF_EVAL, TF_EVAL_CW,                    // enf_tail_fwd_kernel
+  TF_BWD, TF_BWD_STASH, TF_WG, TF_WG_STASH,                     // enf_tail_bwd_kernel on d out: recompute / from the stash
+  TF_LOSS, TF_LOSS_CW, TF_SEED_STASH, TF_FWD_SEED,              // fused loss; seeded from the stash / behind its own forward chain
+  TF_COUNT
+};
+// bwd: enf_tail_bwd_kernel; chain: SAVE of the forward kernel (stash the pre-activations), RECOMP of the backward kernel (run the forward
+// chain first); eval: EVAL; wg / loss / cw / seed: the backward kernel's flags
+struct TailFormCfg { bool bwd, chain; int eval; bool wg, loss, cw, seed; };
+constexpr TailFormCfg tail_form_cfg(TailForm f) {
+  switch (f) {
+    case TF_FWD: return {false, false, 0, false, false, false, false};
+    case TF_FWD_STASH: return {false, true, 0, false, false, false, false};
+    case TF_EVAL: return {false, false, 1, false, false, false, false};
+    case TF_EVAL_CW: return {false, false, 2, false, false, false, false};
+    case TF_BWD: return {true, true, 0, false, false, false, false};
+    case TF_BWD_STASH: return {true, false, 0, false, false, false, false};
+    case TF_WG: return {true, true, 0, true, false, false, false};
+    case TF_WG_STASH: return {true, false, 0, true, false, false, false};
+    case TF_LOSS: return {true, true, 0, false, true, false, false};
+    case TF_LOSS_CW: return {true, true, 0, false, true, true, false};
+    case TF_SEED_STASH: return {true, false, 0, false, false, false, true};
+    default: return {true, true, 0, false, false, false, true};      // TF_FWD_SEED
+  }
+}
+// the forms the launcher's own rule runs on fewer active waves: the forward forms and the seeded backward forms (the d out and the
+// weight-gradient backward never, the fused loss in the test library only)
+constexpr bool tail_form_small(TailForm f) { return !tail_form_cfg(f).bwd || tail_form_cfg(f).seed; }
+constexpr bool tail_form_has_aw(TailForm f) { return tail_form_small(f) || (TAIL_LOSS_AW_ALL && tail_form_cfg(f).loss); }
+
+// THE place that names the kernels
+template <int D, int H, bool BF16, TailForm F, bool LA2, int AW> constexpr auto tail_kernel() {
+  constexpr TailFormCfg c = tail_form_cfg(F);
+  if constexpr (c.bwd) return enf_tail_bwd_kernel<D, H, BF16, LA2, c.chain, c.wg, c.loss, c.cw, c.seed, AW>;
+  else return enf_tail_fwd_kernel<D, H, BF16, LA2, c.chain, c.eval, AW>;
+}
+template <int D, int H, bool BF16, TailForm F, bool LA2, int AW>
+static int launch_tail_kernel(const TailArgs& A, dim3 grid, hipStream_t st) {
+  constexpr auto kern = tail_kernel<D, H, BF16, F, LA2, AW>();
+  constexpr int smem = LA2 ? TailCfg<D, H, BF16>::SMEM3 : TailCfg<D, H, BF16>::SMEM;
+  if (!enf_lds_attr<kern>(smem)) return ENF_ELAUNCH;
+  hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, st, A);
+  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
+}
+
+template <int D, int H, bool BF16, TailForm F>
+static int launch_tail_form(const TailArgs& A, hipStream_t st) {
+  constexpr TailFormCfg c = tail_form_cfg(F);
+  // fewer active waves: deterministic mode keeps eight (the partial-sum slots enf_launch_loss_sum reads are those of the 8-wave grid)
   int aw = NWAVES;
-  if ((!bwd || seeded) && !A.loss_part) aw = tail_active_waves(A.NQ);
+  if (tail_form_small(F) && !A.loss_part) aw = tail_active_waves(A.NQ);
 #ifdef ENF_TEST_HOOKS
-  if (g_test_tail_aw && !wg && !A.loss_part && (!bwd || seeded || fused_loss)) aw = g_test_tail_aw;
+  if (g_test_tail_aw && tail_form_has_aw(F) && !A.loss_part) aw = g_test_tail_aw;
 #endif
-  dim3 grid((A.NQ + 16 * aw - 1) / (16 * aw));
+  const dim3 grid((A.NQ + 16 * aw - 1) / (16 * aw));
   // few workgroups (at most one per CU): the deeper weight pipeline (LA2) instead of a second workgroup per CU
   const bool la2 = grid.x <= 256 || aw < NWAVES;
-  const int awi = aw == NWAVES ? 0 : aw == 4 ? 1 : aw == 2 ? 2 : 3;
-  // opt: forward -> stash the pre-activations (SAVE); backward -> they are stashed, skip the recompute
-  // [fwd / bwd / bwd + WG / fused loss / fused loss + CW / evaluation / evaluation + CW / seeded bwd][la2][opt][aw] (this function is
-  // one instantiation per D, H, BF16), one bit per device
-  static EnfAttrBits attr_done[8][2][2][4];
-  auto go = [&](void (*kern_ptr)(TailArgs)) -> int {
-    const int smem = la2 ? T::SMEM3 : T::SMEM;
-    const int which = seeded ? 7 : eval ? (cw ? 6 : 5) : fused_loss ? (cw ? 4 : 3) : (wg ? 2 : bwd);
-    if (!enf_lds_attr(reinterpret_cast<const void*>(kern_ptr), smem, attr_done[which][la2][opt][awi])) return ENF_ELAUNCH;
-    hipLaunchKernelGGL(kern_ptr, grid, dim3(NTHREADS), smem, st, A);
-    return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-  };
-  // the instantiations with fewer active waves (3-slot ring only): K(AW) names the kernel
-#define ENF_TAIL_AW(K)                 \
-  if (aw == 4) return go(K(4));        \
-  if (aw == 2) return go(K(2));        \
-  if (aw == 1) return go(K(1));
-#define ENF_K_SEED_STASH(AW_) enf_tail_bwd_kernel<D, H, BF16, true, false, false, false, false, true, AW_>
-#define ENF_K_SEED_FWD(AW_) enf_tail_bwd_kernel<D, H, BF16, true, true, false, false, false, true, AW_>
-#define ENF_K_LOSS(AW_) enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, false, false, AW_>
-#define ENF_K_LOSS_CW(AW_) enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, true, false, AW_>
-#define ENF_K_EVAL(AW_) enf_tail_fwd_kernel<D, H, BF16, true, false, 1, AW_>
-#define ENF_K_EVAL_CW(AW_) enf_tail_fwd_kernel<D, H, BF16, true, false, 2, AW_>
-#define ENF_K_FWD(AW_) enf_tail_fwd_kernel<D, H, BF16, true, false, 0, AW_>
-#define ENF_K_FWD_SAVE(AW_) enf_tail_fwd_kernel<D, H, BF16, true, true, 0, AW_>
-  if (seeded) {    // the seeded backward, d out = e_seed: from the stash (opt), or behind its own forward chain, which also stores `out`
-    if (!bwd || wg || fused_loss || eval || A.seed < 0 || A.seed >= A.O) return ENF_EINVAL;
-    if (opt) {
-      ENF_TAIL_AW(ENF_K_SEED_STASH)
-      return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, false, false, false, false, true>)
-                 : go(enf_tail_bwd_kernel<D, H, BF16, false, false, false, false, false, true>);
-    }
-    ENF_TAIL_AW(ENF_K_SEED_FWD)
-    return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, false, false, true>)
-               : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, false, false, true>);
+  if (c.seed && (A.seed < 0 || A.seed >= A.O)) return ENF_EINVAL;
+  if ((c.eval || c.loss) && !A.target) return ENF_EINVAL;
+  if ((c.eval == 2 || c.cw) && !A.weight) return ENF_EINVAL;
+  // (run-time la2, aw) -> template arguments; the instantiations with fewer active waves run the 3-slot ring only
+  if constexpr (tail_form_has_aw(F)) {
+    if (aw == 4) return launch_tail_kernel<D, H, BF16, F, true, 4>(A, grid, st);
+    if (aw == 2) return launch_tail_kernel<D, H, BF16, F, true, 2>(A, grid, st);
+    if (aw == 1) return launch_tail_kernel<D, H, BF16, F, true, 1>(A, grid, st);
   }
-  if (eval) {      // the evaluation tail: a forward instantiation whose epilogue forms err / the loss (same LA2 choice as the forward)
-    if (bwd || opt || !A.target || (cw && !A.weight)) return ENF_EINVAL;
-    if (cw) {
-      ENF_TAIL_AW(ENF_K_EVAL_CW)
-      return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 2>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 2>);
-    }
-    ENF_TAIL_AW(ENF_K_EVAL)
-    return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false, 1>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false, 1>);
-  }
-  if (fused_loss) {
-    if (wg || opt) return ENF_EINVAL;
-    if (cw) {
-      if (!A.weight) return ENF_EINVAL;
-      if constexpr (TAIL_LOSS_AW_ALL) { ENF_TAIL_AW(ENF_K_LOSS_CW) }
-      return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, true, true>)
-                 : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, true, true>);
-    }
-    if constexpr (TAIL_LOSS_AW_ALL) { ENF_TAIL_AW(ENF_K_LOSS) }
-    return la2 ? go(enf_tail_bwd_kernel<D, H, BF16, true, true, false, true>) : go(enf_tail_bwd_kernel<D, H, BF16, false, true, false, true>);
-  }
-  if (wg) {
-    if (la2) return opt ? go(enf_tail_bwd_kernel<D, H, BF16, true, false, true>) : go(enf_tail_bwd_kernel<D, H, BF16, true, true, true>);
-    return opt ? go(enf_tail_bwd_kernel<D, H, BF16, false, false, true>) : go(enf_tail_bwd_kernel<D, H, BF16, false, true, true>);
-  }
-  if (bwd) {
-    if (la2) return opt ? go(enf_tail_bwd_kernel<D, H, BF16, true, false>) : go(enf_tail_bwd_kernel<D, H, BF16, true, true>);
-    return opt ? go(enf_tail_bwd_kernel<D, H, BF16, false, false>) : go(enf_tail_bwd_kernel<D, H, BF16, false, true>);
-  }
-  if (opt) {
-    ENF_TAIL_AW(ENF_K_FWD_SAVE)
-    return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, true>) : go(enf_tail_fwd_kernel<D, H, BF16, false, true>);
-  }
-  ENF_TAIL_AW(ENF_K_FWD)
-  return la2 ? go(enf_tail_fwd_kernel<D, H, BF16, true, false>) : go(enf_tail_fwd_kernel<D, H, BF16, false, false>);
-#undef ENF_TAIL_AW
-#undef ENF_K_SEED_STASH
-#undef ENF_K_SEED_FWD
-#undef ENF_K_LOSS
-#undef ENF_K_LOSS_CW
-#undef ENF_K_EVAL
-#undef ENF_K_EVAL_CW
-#undef ENF_K_FWD
-#undef ENF_K_FWD_SAVE
+  return la2 ? launch_tail_kernel<D, H, BF16, F, true, NWAVES>(A, grid, st) : launch_tail_kernel<D, H, BF16, F, false, NWAVES>(A, grid, st);
+}
+
+// run-time form and shape -> launch_tail_form
+template <class S, int F = 0> static int launch_tail_shape(const TailArgs& A, TailForm form, hipStream_t st) {
+  if (form == F) return launch_tail_form<S::D, S::H, S::BF16, (TailForm)F>(A, st);
+  if constexpr (F + 1 < TF_COUNT) return launch_tail_shape<S, F + 1>(A, form, st);
+  else return ENF_EINVAL;
+}
+static int launch_tail(const EnfDims& m, const TailArgs& A, TailForm form, hipStream_t st) {
+  if (m.OB != 1) return ENF_EUNSUPPORTED;
+  return enf_for_shape(m, [&](auto s) { return launch_tail_shape<decltype(s)>(A, form, st); });
+}
+// what every form's arguments share; the entry points below set what differs
+static TailArgs tail_args(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar) {
+  TailArgs A{};
+  A.ybar = ybar; A.blob = blob; A.L = L;
+  A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
+  return A;
 }
 
 int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
-                    const float* dout, float* dybar, float* delta, float* act, int bwd, int opt, hipStream_t st) {
-  return enf_launch_tail_wg(m, L, blob, ybar, out, dout, dybar, delta, act, nullptr, bwd, opt, st);
+                    const float* dout, float* dybar, float* delta, float* act, unsigned flags, hipStream_t st) {
+  return enf_launch_tail_wg(m, L, blob, ybar, out, dout, dybar, delta, act, nullptr, flags, st);
 }
 int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
-                       const float* dout, float* dybar, float* delta, float* act, float* tdel, int bwd, int opt, hipStream_t st) {
-  if (m.OB != 1) return ENF_EUNSUPPORTED;
-  TailArgs A;
-  A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr; A.err = nullptr;
-  A.tdel = tdel;
-  A.ybar_half = (!bwd && (opt & 2) && m.bf16) ? 1 : 0;
-  opt &= 1;
-  A.ybar = ybar; A.blob = blob; A.L = L; A.out = out; A.dout = dout; A.dybar = dybar; A.delta = delta; A.act = act;
-  A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-#define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH) return m.bf16 ? launch_tail<DD, HH, true>(A, bwd != 0, opt != 0, st) : launch_tail<DD, HH, false>(A, bwd != 0, opt != 0, st);
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-  ENF_CASE(64, 1)
-  ENF_CASE(64, 4)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
-}
-
-static int tail_seed_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
-                            float* delta, float* act, bool stashed, hipStream_t st) {
-  if (m.OB != 1) return ENF_EUNSUPPORTED;
-  TailArgs A;
-  A.target = nullptr; A.weight = nullptr; A.loss = nullptr; A.gscale = 0.f; A.inv_n = 0.f; A.loss_part = nullptr; A.err = nullptr;
-  A.tdel = nullptr; A.out = out; A.dout = nullptr;
-  A.seed = seed;
-  A.ybar = ybar; A.blob = blob; A.L = L; A.dybar = dybar; A.delta = delta; A.act = act;
-  A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-#define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH)                                                              \
-    return m.bf16 ? launch_tail<DD, HH, true>(A, true, stashed, st, false, false, true) : launch_tail<DD, HH, false>(A, true, stashed, st, false, false, true);
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-  ENF_CASE(64, 1)
-  ENF_CASE(64, 4)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
+                       const float* dout, float* dybar, float* delta, float* act, float* tdel, unsigned flags, hipStream_t st) {
+  const bool bwd = flags & ENF_TAIL_BWD, stash = flags & ENF_TAIL_STASH;
+  TailArgs A = tail_args(m, L, blob, ybar);
+  A.out = out; A.dout = dout; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = tdel;
+  A.ybar_half = (!bwd && (flags & ENF_TAIL_YBAR_HALF) && m.bf16) ? 1 : 0;
+  const TailForm form = !bwd ? (stash ? TF_FWD_STASH : TF_FWD) : tdel ? (stash ? TF_WG_STASH : TF_WG) : (stash ? TF_BWD_STASH : TF_BWD);
+  return launch_tail(m, A, form, st);
 }
 
 int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
                          float* act, hipStream_t st) {
-  return tail_seed_kernel(m, L, blob, ybar, nullptr, seed, dybar, delta, act, true, st);
+  TailArgs A = tail_args(m, L, blob, ybar);
+  A.seed = seed; A.dybar = dybar; A.delta = delta; A.act = act;
+  return launch_tail(m, A, TF_SEED_STASH, st);
 }
 // Forward chain (stash in `act`, `out` (B N, O) stored if given) and the seeded backward in one launch: what enf_launch_tail with the
 // stash followed by enf_launch_tail_seed compute, bit for bit.
 int enf_launch_tail_fwd_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
                              float* delta, float* act, hipStream_t st) {
-  return tail_seed_kernel(m, L, blob, ybar, out, seed, dybar, delta, act, false, st);
+  TailArgs A = tail_args(m, L, blob, ybar);
+  A.out = out; A.seed = seed; A.dybar = dybar; A.delta = delta; A.act = act;
+  return launch_tail(m, A, TF_FWD_SEED, st);
 }
 
 int enf_tail_loss_parts(const EnfDims& m) {
   return (int)(((long long)m.B * m.N + 16 * NWAVES - 1) / (16 * NWAVES)) * NWAVES;
 }
 
-static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
-                            bool per_value, float* err, bool eval);
+// the fused loss and the evaluation tail: target, weights, the loss and its deterministic partials, the per-point errors
+static int tail_loss_kernel(const EnfDims& m, TailArgs& A, TailForm form, const float* target, const float* weight, float gscale, float* loss,
+                            float* loss_part, float* err, hipStream_t st) {
+  A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
+  A.loss_part = loss_part; A.err = err;
+  if (int rc = launch_tail(m, A, form, st)) return rc;
+  return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
+}
 
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
                          bool per_value, float* err) {
-  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, gscale, loss, dybar, delta, act, st, loss_part, per_value, err, false)) return rc;
-  return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
+  TailArgs A = tail_args(m, L, blob, ybar);
+  A.dybar = dybar; A.delta = delta; A.act = act;
+  return tail_loss_kernel(m, A, per_value ? TF_LOSS_CW : TF_LOSS, target, weight, gscale, loss, loss_part, err, st);
 }
 
 int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part) {
-  if (!loss) loss_part = nullptr;
-  if (int rc = tail_loss_kernel(m, L, blob, ybar, target, weight, 0.f, loss, nullptr, nullptr, nullptr, st, loss_part, per_value, err, true)) return rc;
-  return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
-}
-
-static int tail_loss_kernel(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
-                            const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
-                            bool per_value, float* err, bool eval) {
-  if (m.OB != 1) return ENF_EUNSUPPORTED;
-  TailArgs A;
-  A.loss_part = loss_part; A.err = err;
-  A.ybar = ybar; A.blob = blob; A.L = L; A.out = nullptr; A.dout = nullptr; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = nullptr;
-  A.ybar_half = 0;
-  A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
-  A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-#define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH)                                                              \
-    return m.bf16 ? launch_tail<DD, HH, true>(A, !eval, false, st, per_value, eval) : launch_tail<DD, HH, false>(A, !eval, false, st, per_value, eval);
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-  ENF_CASE(64, 1)
-  ENF_CASE(64, 4)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
+  TailArgs A = tail_args(m, L, blob, ybar);
+  return tail_loss_kernel(m, A, per_value ? TF_EVAL_CW : TF_EVAL, target, weight, 0.f, loss, loss ? loss_part : nullptr, err, st);
 }
 
 #ifdef ENF_TEST_HOOKS
@@ -778,8 +725,8 @@ extern "C" int enf_test_tail(const EnfDesc* d, const void* packed, int form, int
   const char* blob = (const char*)packed;
   hipStream_t st = (hipStream_t)stream;
   switch (form) {
-    case 0: return enf_launch_tail(m, L, blob, ybar, out, nullptr, nullptr, nullptr, nullptr, 0, 0, st);
-    case 1: return enf_launch_tail(m, L, blob, ybar, out, nullptr, nullptr, nullptr, act, 0, 1, st);
+    case 0: return enf_launch_tail(m, L, blob, ybar, out, nullptr, nullptr, nullptr, nullptr, ENF_TAIL_FWD, st);
+    case 1: return enf_launch_tail(m, L, blob, ybar, out, nullptr, nullptr, nullptr, act, ENF_TAIL_FWD | ENF_TAIL_STASH, st);
     case 2: return enf_launch_tail_eval(m, L, blob, ybar, target, weight, per_value != 0, loss, err, st, loss_part);
     case 3: return enf_launch_tail_seed(m, L, blob, ybar, seed, dybar, delta, act, st);
     case 4: return enf_launch_tail_fwd_seed(m, L, blob, ybar, out, seed, dybar, delta, act, st);

@@ -880,34 +880,25 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
 }
 
 // ---------------------------------------------------------------- launch: the pair kernel, then the entry point's tail
-template <int D, int H, bool BF16> auto tail_kernel(const TailTanArgs&) { return enf_tail_tangent_kernel<D, H, BF16>; }
-template <int D, int H, bool BF16> auto tail_kernel(const GnTailArgs&) { return enf_gn_tail_kernel<D, H, BF16>; }
+template <int D, int H, bool BF16> constexpr auto tail_kernel(const TailTanArgs*) { return enf_tail_tangent_kernel<D, H, BF16>; }
+template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgs*) { return enf_gn_tail_kernel<D, H, BF16>; }
 
-template <int D, int H, bool BF16, class TailArgsT>
-int launch_pair_tail(const PairTanArgs& PA, const TailArgsT& TA, hipStream_t st) {
-  auto pk = PA.xdot ? enf_pair_tangent_kernel<D, H, BF16, true> : enf_pair_tangent_kernel<D, H, BF16, false>;
-  auto tk = tail_kernel<D, H, BF16>(TA);
-  static EnfAttrBits pair_done{0}, pair_x_done{0}, tail_done{0};        // one per instantiation, one bit per device
-  constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
-  if (!enf_lds_attr(reinterpret_cast<const void*>(pk), pair_lds, PA.xdot ? pair_x_done : pair_done)) return ENF_ELAUNCH;
-  if (!enf_lds_attr(reinterpret_cast<const void*>(tk), tail_lds, tail_done)) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(pk, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), pair_lds, st, PA);
-  if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(tk, dim3((TA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, TA);
-  return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
-}
 // the instantiations: both entry points dispatch here
 template <class TailArgsT>
 int launch_pair_tail(const EnfDims& m, const PairTanArgs& PA, const TailArgsT& TA, hipStream_t st) {
-#define ENF_TAN_CASE(DD, HH) \
-  if (m.D == DD && m.H == HH) return m.bf16 ? launch_pair_tail<DD, HH, true>(PA, TA, st) : launch_pair_tail<DD, HH, false>(PA, TA, st);
-  ENF_TAN_CASE(128, 2)
-  ENF_TAN_CASE(64, 2)
-  ENF_TAN_CASE(128, 1)
-  ENF_TAN_CASE(64, 1)
-  ENF_TAN_CASE(64, 4)
-#undef ENF_TAN_CASE
-  return ENF_EUNSUPPORTED;
+  return enf_for_shape(m, [&](auto s) {
+    constexpr int D = s.D, H = s.H;
+    constexpr bool BF16 = s.BF16;
+    constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
+    constexpr auto pk0 = enf_pair_tangent_kernel<D, H, BF16, false>, pkx = enf_pair_tangent_kernel<D, H, BF16, true>;
+    constexpr auto tk = tail_kernel<D, H, BF16>((const TailArgsT*)nullptr);
+    if (!(PA.xdot ? enf_lds_attr<pkx>(pair_lds) : enf_lds_attr<pk0>(pair_lds))) return (int)ENF_ELAUNCH;
+    if (!enf_lds_attr<tk>(tail_lds)) return (int)ENF_ELAUNCH;
+    hipLaunchKernelGGL(PA.xdot ? pkx : pk0, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), pair_lds, st, PA);
+    if (hipGetLastError() != hipSuccess) return (int)ENF_ELAUNCH;
+    hipLaunchKernelGGL(tk, dim3((TA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, TA);
+    return hipGetLastError() == hipSuccess ? 0 : (int)ENF_ELAUNCH;
+  });
 }
 
 // ---------------------------------------------------------------- the host sequence of both entry points
@@ -1047,7 +1038,7 @@ extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstrid
   // the fixed-order reduction, which overwrites the gradient table
   if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
   if ((rc = enf_launch_pair_bwd(m, L, pk, x, x_bstride, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), c.F(W.dlt), nullptr,
-                                zb ? c.ws + W.wzt : nullptr, zb ? c.F(W.wzb) : nullptr, nullptr, st, det ? c.F(c.X.part) : nullptr)))
+                                c.fold_bwd(), nullptr, st, det ? c.F(c.X.part) : nullptr)))
     return rc;
   return enf_launch_prologue_bwd(m, L, pk, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), gp, ga, gsigma, st);
 }

@@ -287,7 +287,9 @@ extern "C" int enf_backward_all(const EnfDesc* d, const float* x, int64_t x_bstr
   if (!(flags & ENF_BWD_REUSE_PROLOGUE) && (rc = enf_launch_prologue(m, L, blob, p, a, sigma, F(W.lt), F(W.an), F(W.kv), st))) return rc;
   const bool treuse = (flags & ENF_BWD_REUSE_TAIL) && (flags & ENF_BWD_REUSE_PROLOGUE);
   float* tdel = G(S.tdel);
-  if ((rc = enf_launch_tail_wg(m, L, blob, ybar, nullptr, dout, F(W.dybar), F(W.delta), F(W.tail_act), tdel, 1, treuse ? 1 : 0, st))) return rc;
+  if ((rc = enf_launch_tail_wg(m, L, blob, ybar, nullptr, dout, F(W.dybar), F(W.delta), F(W.tail_act), tdel,
+                               ENF_TAIL_BWD | (treuse ? ENF_TAIL_STASH : 0u), st)))
+    return rc;
 
   // ---- 2. the per-pair chain: K3 with the activation store, K4, chunked over signals (enf_xtd.hip)
   float* dpair[ENF_NUM_PAIR_TENSORS];

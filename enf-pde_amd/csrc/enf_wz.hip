@@ -198,9 +198,8 @@ __global__ __launch_bounds__(64 * WZ_WAVES) void enf_wz_kernel(WzArgs A) {
 template <int D, int H, bool BF16>
 static int launch_wz(const WzArgs& A, hipStream_t st) {
   constexpr int PB = D * D * (BF16 ? 2 : 4);
-  auto kern = enf_wz_kernel<D, H, BF16>;
-  static EnfAttrBits attr_done{0};          // one per instantiation, one bit per device
-  if (!enf_lds_attr(reinterpret_cast<const void*>(kern), PB, attr_done)) return ENF_ELAUNCH;
+  constexpr auto kern = enf_wz_kernel<D, H, BF16>;
+  if (!enf_lds_attr<kern>(PB)) return ENF_ELAUNCH;
   // waves = COMBOS (head, block) roles x a number of latent lanes; each wave sweeps BZ / lanes latents
   constexpr int COMBOS = H * (D / 32);
   // the backward's call (both orientations) runs on the side stream beside the tail kernels and is off the critical
@@ -223,13 +222,5 @@ int enf_launch_wz(const EnfDims& m, const EnfLayout& L, const char* blob, const 
   A.lt = lt; A.blob = blob; A.L = L; A.wzb = wzb; A.wzu = wzu; A.BZ = m.B * m.Z;
   if (wzt) { A.wz = wzt; A.wzt = wzt + PB; A.pstride = 2 * PB; }
   else { A.wz = wz; A.wzt = nullptr; A.pstride = PB; }
-#define ENF_CASE(DD, HH)                                                                   \
-  if (m.D == DD && m.H == HH) return m.bf16 ? launch_wz<DD, HH, true>(A, st) : launch_wz<DD, HH, false>(A, st);
-  ENF_CASE(128, 2)
-  ENF_CASE(64, 2)
-  ENF_CASE(128, 1)
-  ENF_CASE(64, 1)
-  ENF_CASE(64, 4)
-#undef ENF_CASE
-  return ENF_EUNSUPPORTED;
+  return enf_for_shape(m, [&](auto s) { return launch_wz<s.D, s.H, s.BF16>(A, st); });
 }

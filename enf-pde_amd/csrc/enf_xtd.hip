@@ -349,7 +349,7 @@ int enf_launch_wgrad_chunks(const EnfDims& m, const EnfLayout& L, const char* bl
     mc.B = nb; mc.mask_b0 = b0;
     const size_t qo = (size_t)b0 * m.N;
     int rc = enf_launch_pair_bwd(mc, L, blob, x + (size_t)b0 * x_bstride, x_bstride, lt + (size_t)b0 * m.Z * stride, lse + qo * m.H,
-                                 dybar + qo * m.HD, delta + qo * m.H, dlt + (size_t)b0 * m.Z * stride, store, nullptr, nullptr,
+                                 dybar + qo * m.HD, delta + qo * m.H, dlt + (size_t)b0 * m.Z * stride, store, EnfFoldBwd{},
                                  dx ? dx + qo * m.dx : nullptr, st, detpart, dxpart);
     if (rc) return rc;
     if ((rc = enf_launch_xtd(mc, store, (long long)nb * m.Z * m.N, dpair, part, b0 > 0, st))) return rc;

@@ -81,6 +81,24 @@ def test_every_stage_and_flag_bit_of_the_header_is_named_in_the_binding():
     assert _lib.ENF_STAGES_FORWARD == sum(stages[f"ENF_STAGE_{k}"] for k in ("PROLOGUE", "PAIR", "TAIL", "FOLD"))
 
 
+def test_the_compiled_shape_table(lib):
+    """The (num_hidden, heads) set the kernels are compiled for (csrc/enf_layout.h: ENF_SHAPES) as the descriptor check and the
+    shared-backward rule answer it: ENF_OK exactly for the five pairs, ENF_EUNSUPPORTED (-3) for every other pair of the grid; the
+    shared backward (ENF_SHARED_BWD_SHAPES) on three of them.  The shared-backward descriptor is the one of
+    tests/test_shared_backward_host.py (6 signals, the latent-split forward and the z-fold backward forced)."""
+    from enf_pde_amd import _lib
+    table = {(128, 2), (64, 2), (128, 1), (64, 1), (64, 4)}
+    shared = {(128, 2), (128, 1), (64, 2)}
+    variants = (_lib.VARIANT["latent_split"], _lib.VARIANT["z_fold"])
+    for D in (32, 64, 96, 128, 256):
+        for H in (1, 2, 3, 4, 8):
+            for prec in (0, 1):
+                d = _lib.make_desc(6, 48, 24, H, D, 16, 1, 2, 0, 1, prec, variants=variants)
+                assert lib.enf_check_desc(ctypes.byref(d)) == (0 if (D, H) in table else -3), (D, H, prec)
+                applies = lib.enf_shared_backward_applies(ctypes.byref(d), _lib.ENF_FIT_SHARED_LATENTS)
+                assert applies == (1 if (D, H) in shared else 0 if (D, H) in table else -3), (D, H, prec)
+
+
 def test_check_desc_and_error_mapping(lib):
     from enf_pde_amd import _lib
     ok = _lib.make_desc(2, 100, 64, 2, 128, 16, 1, 2, 0, 1, 1)

@@ -44,8 +44,8 @@ int main() {
       const EnfDims m = enf_dims(&d);
       const EnfLayout L = enf_layout(m);
       // no scratch of the z-fold: the launcher resolves to the latent-split kernel; both return before any launch
-      const int both = enf_launch_pair_fwd(m, L, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 3, nullptr);
-      const int fold = enf_launch_pair_fwd(m, L, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 2, nullptr);
+      const int both = enf_launch_pair_fwd(m, L, nullptr, nullptr, 0, nullptr, nullptr, nullptr, EnfFoldFwd{}, ENF_PAIR_PAIR | ENF_PAIR_YBAR_HALF, nullptr);
+      const int fold = enf_launch_pair_fwd(m, L, nullptr, nullptr, 0, nullptr, nullptr, nullptr, EnfFoldFwd{}, ENF_PAIR_YBAR_HALF, nullptr);
       printf("variant %d mask_mode %d: run_pair 3 -> %d, run_pair 2 -> %d\n", variant, mode, both, fold);
       bad += both != ENF_EINVAL || fold != 0;
     }
@@ -55,8 +55,9 @@ int main() {
 
 
 def test_pair_launcher_refuses_the_hand_off_on_a_masked_call(tmp_path):
-    """enf_launch_pair_fwd(run_pair = 1 | 2) with relu masks on: ENF_EINVAL, before anything is launched (so this runs without a GPU);
-    the hand-off bit on the fold alone (run_pair = 2: no pair stage, no masked kernel) is not an error.  A small program of its own,
+    """enf_launch_pair_fwd(ENF_PAIR_PAIR | ENF_PAIR_YBAR_HALF, "run_pair 3" below) with relu masks on: ENF_EINVAL, before anything is
+    launched (so this runs without a GPU); the hand-off bit on the fold alone (ENF_PAIR_YBAR_HALF, "run_pair 2": no pair stage, no masked
+    kernel) is not an error.  A small program of its own,
     linked against the built library."""
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc) and os.path.exists(_lib.LIB_PATH), "build the library first"
