@@ -7,6 +7,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ENF_HIP_LIB") or os.path.join(_HERE, "libenf_hip.so")   # ENF_HIP_LIB: A/B builds (scripts/build_variant.sh)
 TEST_LIB_PATH = os.environ.get("ENF_HIP_TEST_LIB") or os.path.join(_HERE, "libenf_hip_test.so")    # same ABI + test hooks (csrc/Makefile); tests only
+F32R_LIB_PATH = os.environ.get("ENF_HIP_F32R_LIB") or os.path.join(_HERE, "libenf_hip_f32r.so")    # same ABI, -DENF_F32_ROUNDED=1 (csrc/Makefile); tests only
 
 ENF_NUM_TENSORS = 46
 PREC = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -105,6 +106,11 @@ class EnfError(RuntimeError):
 
 _lib = None
 _test_lib = None
+_f32r_lib = None
+# the test-only entry points of the two test libraries
+_DEBUG_HOOKS = ("enf_debug_gemm", "enf_debug_pack")
+_TEST_HOOKS = _DEBUG_HOOKS + ("enf_test_read_wave_sums", "enf_test_pair_fwd_streamed", "enf_test_tail_active_waves", "enf_test_tail_parts",
+                              "enf_test_tail")
 
 
 def load():
@@ -112,7 +118,7 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    _lib = _bind(LIB_PATH, test_hooks=False)
+    _lib = _bind(LIB_PATH, hooks=())
     return _lib
 
 
@@ -120,8 +126,18 @@ def load_test():
     """The test library (libenf_hip_test.so): the whole product ABI plus the test-only entry points.  Tests only."""
     global _test_lib
     if _test_lib is None:
-        _test_lib = _bind(TEST_LIB_PATH, test_hooks=True)
+        _test_lib = _bind(TEST_LIB_PATH, hooks=_TEST_HOOKS)
     return _test_lib
+
+
+def load_f32r():
+    """The bf16-faithful fp32 reference (libenf_hip_f32r.so): the product ABI built with -DENF_F32_ROUNDED=1, in which
+    precision="f32" rounds to bf16 every value that precision="bf16" holds as bf16 and keeps fp32 layouts, MFMAs and sums
+    (csrc/enf_layout.h), plus the layout self-test entry points.  Tests only: ``with _lib.using(_lib.load_f32r()): ...``."""
+    global _f32r_lib
+    if _f32r_lib is None:
+        _f32r_lib = _bind(F32R_LIB_PATH, hooks=_DEBUG_HOOKS)
+    return _f32r_lib
 
 
 class using:
@@ -140,7 +156,7 @@ class using:
         _lib = self.prev
 
 
-def _bind(path, test_hooks):
+def _bind(path, hooks):
     if not os.path.exists(path):
         raise EnfError(f"{path} not found: build it with `make -C enf-pde_amd/csrc` "
                        "(or python -c 'import __graft_entry__ as g; g.build()'). There is no fallback path.")
@@ -257,16 +273,16 @@ def _bind(path, test_hooks):
     lib.enf_backward_weights_scratch_bytes_ex.restype = sz
     lib.enf_backward_weights_scratch_bytes_ex.argtypes = [dp, ci, cu]
     lib.enf_backward_weights_ex.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, sz, cu, vp]
-    if test_hooks:
-        for name in ("enf_debug_gemm", "enf_debug_pack", "enf_test_read_wave_sums", "enf_test_pair_fwd_streamed",
-                     "enf_test_tail_active_waves", "enf_test_tail_parts", "enf_test_tail"):
-            getattr(lib, name).restype = ci
+    for name in hooks:
+        getattr(lib, name).restype = ci
+    if "enf_debug_gemm" in hooks:
+        lib.enf_debug_gemm.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+        lib.enf_debug_pack.argtypes = [vp, vp, ci, ci, ci, vp]
+    if "enf_test_tail" in hooks:
         lib.enf_test_tail_active_waves.argtypes = [ci]      # 1, 2, 4, 8: the tail launches run with that many active waves; 0: the launcher's rule; returns the previous setting
         lib.enf_test_tail_parts.argtypes = [dp]
         lib.enf_test_tail.argtypes = [dp, vp, ci, ci, vp, vp, vp, ci] + [vp] * 8      # one tail launch on the caller's buffers (csrc/enf_tail.hip)
         lib.enf_test_pair_fwd_streamed.argtypes = [ci]      # 1: the forward pair kernels run with an empty resident set; returns the previous setting
-        lib.enf_debug_gemm.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-        lib.enf_debug_pack.argtypes = [vp, vp, ci, ci, ci, vp]
         lib.enf_test_read_wave_sums.argtypes = [vp]
     if lib.enf_abi_version() != 2:
         raise EnfError(f"{path}: ABI version mismatch")

@@ -45,6 +45,13 @@ typedef __bf16 bf16x2_cvt __attribute__((ext_vector_type(2)));
 DEV unsigned bf16_pack2(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_cvt{a, b}, bf16x2_cvt));
 }
+// the same conversion with the result widened again: what a value is once a bf16 fragment holds it (ENF_F32_ROUNDED, enf_layout.h)
+DEV float bf16_round(float x) { return __builtin_bit_cast(float, bf16_pack2(x, x) & 0xffff0000u); }
+DEV f32x4 bf16_round4(const f32x4& x) {
+  const unsigned lo = bf16_pack2(x[0], x[1]), hi = bf16_pack2(x[2], x[3]);
+  return f32x4{__builtin_bit_cast(float, lo << 16), __builtin_bit_cast(float, lo & 0xffff0000u),
+               __builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
+}
 template <bool BF16, int KB>
 DEV void make_frags(Frags<BF16, KB>& F, const f32x4 (&X)[2 * KB]) {
 #pragma unroll
@@ -53,6 +60,9 @@ DEV void make_frags(Frags<BF16, KB>& F, const f32x4 (&X)[2 * KB]) {
       const u32x4 w = {bf16_pack2(X[2 * blk][0], X[2 * blk][1]), bf16_pack2(X[2 * blk][2], X[2 * blk][3]),
                        bf16_pack2(X[2 * blk + 1][0], X[2 * blk + 1][1]), bf16_pack2(X[2 * blk + 1][2], X[2 * blk + 1][3])};
       F.f[blk] = __builtin_bit_cast(bf16x8, w);
+    } else if constexpr (enf_bf16_valued(BF16)) {      // fp32 layout, bf16 values
+      F.f[2 * blk] = bf16_round4(X[2 * blk]);
+      F.f[2 * blk + 1] = bf16_round4(X[2 * blk + 1]);
     } else {
       F.f[2 * blk] = X[2 * blk];
       F.f[2 * blk + 1] = X[2 * blk + 1];

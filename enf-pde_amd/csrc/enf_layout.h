@@ -26,6 +26,17 @@
 #define ENF_HD
 #endif
 
+// ENF_F32_ROUNDED = 1 builds the bf16-faithful fp32 reference (libenf_hip_f32r.so, tests only; csrc/Makefile): the fp32 instantiations
+// round to bf16 (nearest even, the bf16 path's own conversions) every value the bf16 instantiations hold as bf16, and take the bf16
+// mode's arithmetic choices (hardware sin / cos); layouts, MFMA instructions, accumulators, biases, softmax and LayerNorm stay fp32.
+// A product of two bf16 values is exact in fp32, so the two precisions then differ in the order of fp32 sums only.
+// enf_bf16_valued(BF16) stands beside a template's BF16 wherever the question is "are the operands bf16-VALUED" and not "are they
+// STORED as bf16"; with the macro unset it is BF16 ("Rounding sites").
+#ifndef ENF_F32_ROUNDED
+#define ENF_F32_ROUNDED 0
+#endif
+constexpr bool enf_bf16_valued(bool bf16) { return bf16 || ENF_F32_ROUNDED; }
+
 struct EnfDims {
   int B, N, Z, H, D, C, O, dx, dp, I, inv, use_window, bf16;
   int Ht;      // the model's true num_heads (== H unless padded with zero heads)

@@ -112,7 +112,7 @@ __global__ void pack_panel_kernel(void* dst, const float* W, int ldw, int R, int
   float v = 0.f;
   if (r < Rvalid && k < Kvalid) v = scale * (trans ? W[(size_t)r * ldw + k] : W[(size_t)k * ldw + r]);
   if (bf16) reinterpret_cast<__bf16*>(dst)[e] = (__bf16)v;
-  else reinterpret_cast<float*>(dst)[e] = v;
+  else reinterpret_cast<float*>(dst)[e] = enf_bf16_valued(false) ? (float)(__bf16)v : v;      // (fp32 layout, bf16 values: ENF_F32_ROUNDED)
 }
 
 // gamma half of one head out of the [g g b b]-interleaved D x 2HD matrix: dst[i][j] = Wgamma_h[i][j]

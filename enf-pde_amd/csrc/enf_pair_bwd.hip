@@ -491,7 +491,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
     const size_t qrow = (size_t)b * A.N + n;
     const QueryPt q = load_query(A.x + (size_t)b * A.x_bstride + (size_t)n * dx_, dx_, inv_id);
     float inv[4], win;
-    pair_invariant<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, ext);
+    pair_invariant<enf_bf16_valued(BF16)>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, ext);
     const size_t srow = (size_t)bzc * A.N + n;        // row of the materialised activations (STORE)
     const bool swrite = STORE && nvalid && active;
     // SHARED: the A operand of the contraction, dout[signal 16 group + col][n0 + 4 quad + i], read again where it is used (L2 hits)
@@ -821,6 +821,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
             FG.f[2 * m][j] = (__bf16)dg[j >> 2][j & 3];
             FG.f[2 * m + 1][j] = (__bf16)v[2 * m + (j >> 2)][j & 3];
           }
+        } else if constexpr (enf_bf16_valued(BF16)) {      // fp32 layout, bf16 values
+          FG.f[4 * m] = bf16_round4(dg[0]); FG.f[4 * m + 1] = bf16_round4(dg[1]);
+          FG.f[4 * m + 2] = bf16_round4(v[2 * m]); FG.f[4 * m + 3] = bf16_round4(v[2 * m + 1]);
         } else {
           FG.f[4 * m] = dg[0]; FG.f[4 * m + 1] = dg[1];
           FG.f[4 * m + 2] = v[2 * m]; FG.f[4 * m + 3] = v[2 * m + 1];
@@ -1064,7 +1067,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
         float dwin = 0.f, tp[4] = {0.f, 0.f, 0.f, 0.f}, tw = 0.f;
 #pragma unroll
         for (int h = 0; h < H; ++h) { sc[h] = dlogit[h]; dwin += dlogit[h]; }
-        pair_invariant_bwd<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, tp, tw, nullptr, nullptr);
+        pair_invariant_bwd<enf_bf16_valued(BF16)>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, tp, tw, nullptr, nullptr);
         sc[H] = tp[0]; sc[H + 1] = tp[1]; sc[H + 2] = tp[2]; sc[H + 3] = tp[3]; sc[H + 4] = tw;
       }
       float ad[4];
@@ -1094,13 +1097,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_bwd_kernel(PairBwdArgs A
       float* dxp = A.dxq ? dxv : nullptr;
       if (has_ph) {
         float dR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        pair_invariant_bwd<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, dpose, dwc, dR, dxp, ext);
+        pair_invariant_bwd<enf_bf16_valued(BF16)>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, dpose, dwc, dR, dxp, ext);
         if (inv_id == ENF_INV_BALL) {
 #pragma unroll
           for (int k = 0; k < 9; ++k) eacc[k * 16] += dR[k];
         }
       } else
-      pair_invariant_bwd<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, dpose, dwc, nullptr, dxp);
+      pair_invariant_bwd<enf_bf16_valued(BF16)>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, dinv, dwin, dpose, dwc, nullptr, dxp);
       if (A.dxq && nvalid && active) {          // every latent's wave adds its share to the query's gradient
         if (A.dxpart) {                         // deterministic mode: the share goes to (b, z, n, :), summed over z afterwards
           float* o = A.dxpart + ((size_t)bzc * A.N + n) * dx_;

@@ -58,7 +58,7 @@ DEV void rff_embed(f32x4 (&E)[D / 16], const float (&inv)[4], const float* cfrag
     if (phase) t = *reinterpret_cast<const f32x4*>(phase + 16 * tt + 4 * quad);
     t = __builtin_amdgcn_mfma_f32_16x16x4f32(cfrag[tt * 64 + lane], bq, t, 0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { E[tt][i] = sin_rev<BF16>(t[i]); E[TT + tt][i] = cos_rev<BF16>(t[i]); }
+    for (int i = 0; i < 4; ++i) { E[tt][i] = sin_rev<enf_bf16_valued(BF16)>(t[i]); E[TT + tt][i] = cos_rev<enf_bf16_valued(BF16)>(t[i]); }
   }
 }
 

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_fwd_kernel(PairFwdArgs A
 
     float inv[4], win;
     const bool has_ph = INV < 0 && D == 64 && enf_inv_has_phase(inv_id);   // ball / ball_lat (64-wide only): rotation matrix and RFF phases of the latent
-    pair_invariant<BF16>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, ltrow + enf_lt_off_ext(H, D));
+    pair_invariant<enf_bf16_valued(BF16)>(inv_id, dx_, q, pz, wcoef, A.use_window, inv, win, ltrow + enf_lt_off_ext(H, D));
 
     float logit[H];
     Frags<BF16, KB> F;
@@ -318,9 +318,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_pair_fwd_kernel(PairFwdArgs A
         float s = 0.f;           // (as a packed-pair sum -- tiles_dot, enf_device.h -- this loop measured 0.6 % SLOWER on the fit-shape forward)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          const f32x4 u = rowvec(zv + h * D, t, quad);
+          if constexpr (ZFOLD && enf_bf16_valued(BF16)) {     // fp32 layout, the matrix-pipe branch's bf16 values: rounded h1 and u
+            const f32x4 u = bf16_round4(rowvec(zv + h * D, t, quad)), a = bf16_round4(acc[t]);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) s = fmaf(mread ? acc[t][i] : relu_f(acc[t][i]), u[i], s);
+            for (int i = 0; i < 4; ++i) s = fmaf(mread ? a[i] : relu_f(a[i]), u[i], s);
+          } else {
+            const f32x4 u = rowvec(zv + h * D, t, quad);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s = fmaf(mread ? acc[t][i] : relu_f(acc[t][i]), u[i], s);
+          }
         }
         logit[h] = xquad_sum(s) + ltrow[enf_lt_off_c(H, D) + h] + win;
       }

@@ -143,7 +143,7 @@ DEV void rff_embed2(f32x4 (&E)[D / 16], f32x4 (&dE)[D / 16], const float (&inv)[
     const f32x4 dt = __builtin_amdgcn_mfma_f32_16x16x4f32(cf, dbq, z4, 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float s = sin_rev<BF16>(t[i]), c = cos_rev<BF16>(t[i]);
+      const float s = sin_rev<enf_bf16_valued(BF16)>(t[i]), c = cos_rev<enf_bf16_valued(BF16)>(t[i]);
       E[tt][i] = s; E[TT + tt][i] = c;
       dE[tt][i] = TWO_PI * c * dt[i];
       dE[TT + tt][i] = -TWO_PI * s * dt[i];
@@ -470,8 +470,8 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
     float inv[4], win, dinv[4], dwin;
-    pair_invariant<BF16>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win);
-    pair_invariant_tan<BF16, XD>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win, tpz, twc, tq, dinv, dwin);
+    pair_invariant<enf_bf16_valued(BF16)>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win);
+    pair_invariant_tan<enf_bf16_valued(BF16), XD>(A.inv, A.dx, q, pz, wcoef, A.use_window, inv, win, tpz, twc, tq, dinv, dwin);
 
     float logit[H], dlogit[H];
     Frags<BF16, KB> F, dF;

@@ -148,7 +148,8 @@ __global__ __launch_bounds__(64 * WZ_WAVES) void enf_wz_kernel(WzArgs A) {
         } else {
 #pragma unroll
           for (int a = 0; a < 2; ++a)
-            *reinterpret_cast<f32x4*>(panel + (((kt * 2 * KB + 2 * blk + a) * 64 + lane) << 4)) = af[a][kt];
+            *reinterpret_cast<f32x4*>(panel + (((kt * 2 * KB + 2 * blk + a) * 64 + lane) << 4)) =
+                enf_bf16_valued(BF16) ? bf16_round4(af[a][kt]) : af[a][kt];
         }
       }
     }
@@ -175,7 +176,8 @@ __global__ __launch_bounds__(64 * WZ_WAVES) void enf_wz_kernel(WzArgs A) {
         } else {
 #pragma unroll
           for (int kt = 0; kt < NT; ++kt)
-            *reinterpret_cast<f32x4*>(panel_t + (((it * 2 * KB + kt) * 64 + lane) << 4)) = acc[kt];
+            *reinterpret_cast<f32x4*>(panel_t + (((it * 2 * KB + kt) * 64 + lane) << 4)) =
+                enf_bf16_valued(BF16) ? bf16_round4(acc[kt]) : acc[kt];
         }
       }
     }
