@@ -25,7 +25,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_backward_weights_scratch_bytes_ex",
            "enf_fit_step_w", "enf_mse_value_grad_w", "enf_fit_inputs_w", "enf_fit_inputs_b",
            "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
-           "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum",
+           "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum", "enf_fit_step_g", "enf_eval_loss_g",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
            "enf_gn_workspace_bytes", "enf_gn_product", "enf_cg_update",
@@ -248,6 +248,8 @@ def _bind(path, hooks):
     lib.enf_fit_step_e.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, cu, vp]
     lib.enf_eval_loss.argtypes = [dp, vp, i64] + [vp] * 11 + [sz, cu, vp]
     lib.enf_signal_sum.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, vp, vp]
+    lib.enf_fit_step_g.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_float] + [vp] * 7 + [sz, cu, vp]
+    lib.enf_eval_loss_g.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_int32] + [vp] * 6 + [sz, cu, vp]
     # derivative fields (include/enf_hip.h, "Derivative fields"): out (B, N, O) | NULL, jac (O, B, N, dx); dout (B, N, O), dx (B, N, dx)
     lib.enf_field_grad_workspace_bytes.restype = sz
     lib.enf_field_grad_workspace_bytes.argtypes = [dp, cu]

@@ -290,10 +290,12 @@ extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstri
 // or with `per_value` one per output value (B, N, O), which is then required.
 // err != NULL (enf_fit_step_e): the fused tail also stores the per-point errors (B, N), and with loss_b the per-signal sums follow at the
 // end of the sequence on the same stream; args_ok: the entry point's own argument checks (ENF_EINVAL, behind the descriptor's errors).
+// grp != NULL (enf_fit_step_g): the loss against grouped observations -- `target` is (B, N / G, O), the weights and errors are grp's (per
+// observation; weight, per_value and err stay unset), loss_b sums grp->err_g over a signal's N / G observations.
 static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, bool per_value, unsigned flags,
-                             void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true) {
+                             void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true, const EnfGroupObs* grp = nullptr) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
   // ENF_FIT_SHARED_LATENTS (include/enf_hip.h): a permission for the forward pair kernel; with one signal it says nothing
@@ -335,14 +337,18 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
       return rc;
     return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
   }
-  if ((rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
-                                 det ? c.F(c.X.loss) : nullptr, per_value, err)))
-    return rc;
+  if (grp) rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, *grp, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
+                                      det ? c.F(c.X.loss) : nullptr);
+  else rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
+                                 det ? c.F(c.X.loss) : nullptr, per_value, err);
+  if (rc) return rc;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse), det))) return rc;
   if ((rc = enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st))) return rc;
   // (behind the gradients: nothing of the step waits for the per-signal sums)
-  return err && loss_b ? enf_launch_signal_sum(err, m.B, m.N, 1.0f / ((float)m.N * (float)m.O), loss_b, st) : ENF_OK;
+  if (grp) err = grp->err_g;
+  const int rows = grp ? m.N / grp->G : m.N;      // the values a signal's loss is the mean of: its points, or its observations
+  return err && loss_b ? enf_launch_signal_sum(err, m.B, rows, 1.0f / ((float)rows * (float)m.O), loss_b, st) : ENF_OK;
 }
 
 extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
@@ -374,12 +380,16 @@ extern "C" int enf_fit_step_e(const EnfDesc* d, const float* x, int64_t x_bstrid
 
 // Evaluation without a decode: prologue, forward pair kernel (whatever variant the descriptor resolves to), the evaluation tail, the
 // per-signal sums.  loss_b without err: the per-point errors go through the workspace's (unused) d ybar region, B N HD floats.
-extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                             const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
-                             float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+// grp != NULL (enf_eval_loss_g): against grouped observations -- target (B, N / G, O), weights and errors per observation from grp
+// (weight, cweight and err unset); args_ok: the entry point's own argument checks.
+static int eval_loss_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
+                              float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream,
+                              const EnfGroupObs* grp = nullptr, bool args_ok = true) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
-  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && !(weight && cweight) && (loss || err || loss_b),
+  if (grp) err = grp->err_g;
+  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && !(weight && cweight) && (loss || err || loss_b) && args_ok,
                     sigma, packed, workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
@@ -390,10 +400,44 @@ extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride
   if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), c.fold_fwd(), ENF_PAIR_FOLD | ENF_PAIR_PAIR, st)))
     return rc;
   float* e = err ? err : (loss_b ? c.F(W.dybar) : nullptr);
-  if ((rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
-                                 det ? c.F(c.X.loss) : nullptr)))
-    return rc;
-  return loss_b ? enf_launch_signal_sum(e, m.B, m.N, 1.0f / ((float)m.N * (float)m.O), loss_b, st) : ENF_OK;
+  if (grp) {
+    const EnfGroupObs g{grp->G, grp->qweight, grp->oweight, e};
+    rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, g, 0.f, loss, nullptr, nullptr, nullptr, st, det ? c.F(c.X.loss) : nullptr);
+  } else
+    rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
+                              det ? c.F(c.X.loss) : nullptr);
+  if (rc) return rc;
+  const int rows = grp ? m.N / grp->G : m.N;
+  return loss_b ? enf_launch_signal_sum(e, m.B, rows, 1.0f / ((float)rows * (float)m.O), loss_b, st) : ENF_OK;
+}
+
+extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                             const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
+                             float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, weight, cweight, loss, err, loss_b, workspace, workspace_bytes, flags,
+                            stream);
+}
+
+// ---- grouped observations (include/enf_hip.h, "Grouped observations"): the two sequences above with the tail's grouped forms.
+// ENF_EINVAL, behind the descriptor's errors and before any launch: G outside {1, 2, 4, 8, 16}, N % G != 0, ENF_FIT_SHARED_LATENTS (the
+// shared backward's loss is another kernel), loss_b without err_g in the fit step (no region of its workspace is free for the errors).
+static bool group_args_ok(const EnfDesc* d, int32_t G) { return enf_group_size_ok(G) && d && d->N % G == 0; }
+
+extern "C" int enf_fit_step_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, const float* target, int32_t G, const float* qweight, const float* oweight, float grad_scale,
+                              float* loss, float* dp, float* da, float* dsigma, float* err_g, float* loss_b, void* workspace,
+                              size_t workspace_bytes, unsigned flags, void* stream) {
+  const EnfGroupObs g{G, qweight, oweight, err_g};
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
+                           false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && !(flags & ENF_FIT_SHARED_LATENTS) && !(loss_b && !err_g), &g);
+}
+
+extern "C" int enf_eval_loss_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, int32_t G, const float* qweight, const float* oweight, float* loss,
+                               float* err_g, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  const EnfGroupObs g{G, qweight, oweight, err_g};
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, nullptr, loss_b, workspace, workspace_bytes, flags,
+                            stream, &g, group_args_ok(d, G));
 }
 
 // ---- derivative fields: the Jacobian of a decode w.r.t. the query coordinates (include/enf_hip.h, "Derivative fields")

@@ -211,6 +211,14 @@ int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob,
 // *loss (through loss_part in deterministic mode) instead of storing `out`; weight / per_value as above.  ybar is fp32.
 int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part = nullptr);
+// grouped observations (include/enf_hip.h, "Grouped observations"): observation m of a signal is the q-weighted sum of the decode at
+// queries m G .. m G + G - 1.  qweight (B, N) or NULL (1 / G); oweight (B, N / G) or NULL (1); err_g (B, N / G) or NULL.
+struct EnfGroupObs { int G; const float* qweight; const float* oweight; float* err_g; };
+inline bool enf_group_size_ok(int G) { return G == 1 || G == 2 || G == 4 || G == 8 || G == 16; }
+// the fused-loss tail (dybar != NULL: arguments as enf_launch_tail_loss) or the evaluation tail (dybar, delta, act NULL: as
+// enf_launch_tail_eval) against target (B, N / G, O); ENF_EINVAL for a G outside the set or N % G != 0
+int enf_launch_tail_group(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target, const EnfGroupObs& g,
+                          float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part = nullptr);
 // the shared-latent backward's loss (enf_loss.hip): ONE row out1 (N values, O = 1) against all B signals' targets and weights (B, N;
 // weight may be NULL): *loss += the mean squared error, dout (B, N) = its gradient times gscale -- enf_mse_kernel's arithmetic
 int enf_launch_mse_shared(const float* out1, const float* target, const float* weight, int B, int N, float gscale, float* dout,

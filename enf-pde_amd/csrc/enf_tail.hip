@@ -39,6 +39,17 @@ struct TailArgs {
   int NQ, O;             // NQ = B*N queries
   float inv_hd;          // 1 / (H * true num_hidden)
 };
+// Grouped observations (the kernels' GRP flag / EVAL == 3; include/enf_hip.h, "Grouped observations"): observation m owns the G
+// consecutive queries m G .. m G + G - 1; `target` is then (NQ / G, O) and inv_n = 1 / (B M O).  The fields are appended at the END, in a
+// struct of their own that only the grouped instantiations take as their argument: the scalar loads a kernel's prologue is compiled to
+// depend on the size of its argument block, so the other kernels keep TailArgs as it was, and with it their instructions.
+struct TailArgsG : TailArgs {
+  const float* qweight;  // nullptr (every factor is 1 / G), or one quadrature factor per query (NQ floats, finite)
+  const float* oweight;  // nullptr (1), or one loss weight per observation (NQ / G floats, >= 0); the zero-weight rule of `weight`
+  float* err_g;          // nullptr, or the weighted squared error of every observation (NQ / G floats, OVERWRITTEN)
+  int G;                 // 1, 2, 4, 8 or 16
+};
+template <bool GROUPED> using TailArgsFor = std::conditional_t<GROUPED, TailArgsG, TailArgs>;
 
 // load_rows (enf_tail_common.h) from bf16 rows (two values per word, low half first)
 template <int NT> DEV void load_rows_half(f32x4 (&X)[NT], const unsigned short* row, int quad) {
@@ -267,6 +278,47 @@ DEV float tail_sq_err(const f32x4 (&o4)[2], f32x4 (&g0)[2], const TailArgs& A, i
   }
   return se;
 }
+// The fused loss against GROUPED observations (include/enf_hip.h, "Grouped observations"): obs[m] = sum_{k < G} q[m G + k] out[m G + k]
+// is compared with target[m].  The 16 queries of the tile sit in the 16 `col` lanes of each quad and a group is G consecutive, G-aligned
+// cols (the tile starts at a multiple of 16 and G divides 16 and N), so the group sum is an xor tree over col bits: shuffles by 1, 2, ..
+// G / 2 under wave-uniform tests of G, which never mix two quads.  Each step adds the same two values in both lanes, so every lane of a
+// group ends with the same bits.  (Contraction is off in here: a fused q * out + partner would round differently in the two lanes.)
+// A group is wholly valid or wholly beyond NQ; lanes beyond NQ contribute zeros.  The squared error is counted once per observation, by
+// the lane with col % G == 0; g0 = d out = q w (obs - target) gs in every lane.  w == 0 is a select, as in tail_sq_err.
+// Returns this lane's share of sum_o w (obs - target)^2.
+DEV float tail_sq_err_g(const f32x4 (&o4)[2], f32x4 (&g0)[2], const TailArgsG& A, int qi, bool qvalid, int col, int quad, float gs) {
+#pragma clang fp contract(off)
+  const int G = A.G;
+  const float q = A.qweight ? A.qweight[qi] : 1.0f / (float)G;
+  f32x4 s[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[t][i] = qvalid ? q * o4[t][i] : 0.f;
+#define ENF_GROUP_STEP(K_)                                             \
+  if (G > K_) {                                                        \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t)                      \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) s[t][i] += __shfl_xor(s[t][i], K_, 64); \
+  }
+  ENF_GROUP_STEP(1) ENF_GROUP_STEP(2) ENF_GROUP_STEP(4) ENF_GROUP_STEP(8)
+#undef ENF_GROUP_STEP
+  const int m = qi >> __builtin_ctz(G);
+  const float w = A.oweight ? A.oweight[m] : 1.f;
+  const bool live = qvalid && w > 0.f;
+  const bool head = (col & (G - 1)) == 0;
+  float se = 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int o = 16 * t + 4 * quad + i;
+      const float dd = (o < A.O && live) ? s[t][i] - A.target[(size_t)m * A.O + o] : 0.f;
+      const float wd = w * dd;
+      se = head ? fmaf(wd, dd, se) : se;
+      g0[t][i] = (q * wd) * gs;
+    }
+  return se;
+}
 // The wave's reduction of `se` in the order it always had (xor 32, 16, 8, 4, 2, 1).  After the first two steps the four quads are
 // folded: lanes 0..15 hold one weighted squared error per query, and with `err` they store it (one 64-byte store per wave; rows beyond
 // NQ -- clamped duplicate lanes -- do not).  No atomic and nothing that depends on which signals a wave straddles.  `want_sum` false:
@@ -286,7 +338,7 @@ DEV void tail_loss_add(float se, const TailArgs& A, int qtile) {      // qtile: 
   else atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
 }
 
-// EVAL (1: unweighted or per-point weights, 2: per-channel weights; never with SAVE): the evaluation tail -- the epilogue forms err and,
+// EVAL (1: unweighted or per-point weights, 2: per-channel weights, 3: grouped observations; never with SAVE): the evaluation tail -- the epilogue forms err and,
 // with A.loss, the scalar loss from the output accumulators instead of storing `out` (enf_eval_loss): no backward chain, no stash, no
 // `out` in HBM.
 //
@@ -298,7 +350,7 @@ DEV void tail_loss_add(float se, const TailArgs& A, int qtile) {      // qtile: 
 // 12-bit offsets and La2Cnt are those of eight waves) and run nothing else.  The waves with queries run the code below unchanged, so
 // their arithmetic does not depend on AW: the results are bit-equal.
 template <int D, int H, bool BF16, bool LA2, bool SAVE, int EVAL = 0, int AW = NWAVES>
-__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
+__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgsFor<EVAL == 3> A) {
   static_assert(!(SAVE && EVAL != 0), "the evaluation tail has no backward to stash for");
   static_assert(AW == NWAVES || (LA2 && (AW == 4 || AW == 2 || AW == 1)), "fewer active waves: small grids, the 3-slot ring");
   using T = TailCfg<D, H, BF16>;
@@ -326,7 +378,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
                          : A.ybar + (size_t)qi * T::HD;
   tail_forward<D, H, BF16, SAVE, LA2, NoPan, NoPan>(o4, yrow, SAVE ? A.act + (size_t)qi * T::ACT : nullptr, A.L,
                                                     cst, P, ring, NO_STAGE, NO_STAGE, lane, quad, A.inv_hd, true, yh);
-  if constexpr (EVAL != 0) {
+  if constexpr (EVAL == 3) {      // grouped observations: err_g per observation, stored by the group's first lane
+    const bool qvalid = q0 + col < A.NQ;
+    f32x4 g0[2];       // (dead code, as below)
+    float se = tail_sq_err_g(o4, g0, A, qi, qvalid, col, quad, 0.f);
+    se = tail_err_reduce(se, A.err_g, qi >> __builtin_ctz(A.G), qvalid && (col & (A.G - 1)) == 0, quad, A.loss != nullptr);
+    if (A.loss && lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
+  } else if constexpr (EVAL != 0) {
     const bool qvalid = q0 + col < A.NQ;
     f32x4 g0[2];       // (d out is not wanted: dead code)
     float se = tail_sq_err<EVAL == 2>(o4, g0, A, qi, qvalid, quad, 0.f);
@@ -354,11 +412,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgs A) {
 // SEED with RECOMP: the shared-latent fit step's tail in one kernel -- the unit seed does not depend on the loss, so the forward chain
 // (stash as ever, `out` stored where A.out is given) and the seeded backward chain need no launch between them.
 // AW: as in enf_tail_fwd_kernel.
+// GRP (with LOSS, never with CW): the loss against grouped observations (tail_sq_err_g) -- means over G consecutive queries, formed by
+// cross-lane adds in front of the squared error.  An instantiation of its own, one for every G; the other fused-loss kernels keep their code.
 template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false, bool SEED = false,
-          int AW = NWAVES>
-__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
+          int AW = NWAVES, bool GRP = false>
+__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgsFor<GRP> A) {
   static_assert(!LOSS || RECOMP, "the fused loss needs the forward chain's outputs");
   static_assert(!CW || LOSS, "per-channel weights belong to the fused loss");
+  static_assert(!GRP || (LOSS && !CW), "grouped observations are a form of the fused loss; their weights are per observation");
   static_assert(!SEED || (!WG && !LOSS), "the seeded backward writes d ybar and delta (and, with the forward chain, out) only");
   static_assert(AW == NWAVES || (LA2 && !WG && (AW == 4 || AW == 2 || AW == 1)), "fewer active waves: small grids, the 3-slot ring");
   using T = TailCfg<D, H, BF16>;
@@ -413,7 +474,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgs A) {
 
   // ---- backward chain
   f32x4 g0[2];
-  if constexpr (LOSS) {
+  if constexpr (LOSS && GRP) {
+    float se = tail_sq_err_g(o4, g0, A, qi, qvalid, col, quad, 2.0f * A.inv_n * A.gscale);
+    se = tail_err_reduce(se, A.err_g, qi >> __builtin_ctz(A.G), qvalid && (col & (A.G - 1)) == 0, quad);
+    if (lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
+  } else if constexpr (LOSS) {
     float se = tail_sq_err<CW>(o4, g0, A, qi, qvalid, quad, 2.0f * A.inv_n * A.gscale);
     se = tail_err_reduce(se, A.err, q0 + col, qvalid, quad);
     if (lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
@@ -570,25 +635,28 @@ enum TailForm {
   TF_FWD, TF_FWD_STASH, TF_EVAL, TF_EVAL_CW,                    // enf_tail_fwd_kernel
   TF_BWD, TF_BWD_STASH, TF_WG, TF_WG_STASH,                     // enf_tail_bwd_kernel on d out: recompute / from the stash
   TF_LOSS, TF_LOSS_CW, TF_SEED_STASH, TF_FWD_SEED,              // fused loss; seeded from the stash / behind its own forward chain
+  TF_LOSS_G, TF_EVAL_G,                                         // grouped observations: the fused loss and the evaluation tail
   TF_COUNT
 };
 // bwd: enf_tail_bwd_kernel; chain: SAVE of the forward kernel (stash the pre-activations), RECOMP of the backward kernel (run the forward
-// chain first); eval: EVAL; wg / loss / cw / seed: the backward kernel's flags
-struct TailFormCfg { bool bwd, chain; int eval; bool wg, loss, cw, seed; };
+// chain first); eval: EVAL; wg / loss / cw / seed / grp: the backward kernel's flags
+struct TailFormCfg { bool bwd, chain; int eval; bool wg, loss, cw, seed, grp; };
 constexpr TailFormCfg tail_form_cfg(TailForm f) {
   switch (f) {
-    case TF_FWD: return {false, false, 0, false, false, false, false};
-    case TF_FWD_STASH: return {false, true, 0, false, false, false, false};
-    case TF_EVAL: return {false, false, 1, false, false, false, false};
-    case TF_EVAL_CW: return {false, false, 2, false, false, false, false};
-    case TF_BWD: return {true, true, 0, false, false, false, false};
-    case TF_BWD_STASH: return {true, false, 0, false, false, false, false};
-    case TF_WG: return {true, true, 0, true, false, false, false};
-    case TF_WG_STASH: return {true, false, 0, true, false, false, false};
-    case TF_LOSS: return {true, true, 0, false, true, false, false};
-    case TF_LOSS_CW: return {true, true, 0, false, true, true, false};
-    case TF_SEED_STASH: return {true, false, 0, false, false, false, true};
-    default: return {true, true, 0, false, false, false, true};      // TF_FWD_SEED
+    case TF_FWD: return {false, false, 0, false, false, false, false, false};
+    case TF_FWD_STASH: return {false, true, 0, false, false, false, false, false};
+    case TF_EVAL: return {false, false, 1, false, false, false, false, false};
+    case TF_EVAL_CW: return {false, false, 2, false, false, false, false, false};
+    case TF_BWD: return {true, true, 0, false, false, false, false, false};
+    case TF_BWD_STASH: return {true, false, 0, false, false, false, false, false};
+    case TF_WG: return {true, true, 0, true, false, false, false, false};
+    case TF_WG_STASH: return {true, false, 0, true, false, false, false, false};
+    case TF_LOSS: return {true, true, 0, false, true, false, false, false};
+    case TF_LOSS_CW: return {true, true, 0, false, true, true, false, false};
+    case TF_SEED_STASH: return {true, false, 0, false, false, false, true, false};
+    case TF_LOSS_G: return {true, true, 0, false, true, false, false, true};
+    case TF_EVAL_G: return {false, false, 3, false, false, false, false, false};
+    default: return {true, true, 0, false, false, false, true, false};      // TF_FWD_SEED
   }
 }
 // the forms the launcher's own rule runs on fewer active waves: the forward forms and the seeded backward forms (the d out and the
@@ -599,20 +667,22 @@ constexpr bool tail_form_has_aw(TailForm f) { return tail_form_small(f) || (TAIL
 // THE place that names the kernels
 template <int D, int H, bool BF16, TailForm F, bool LA2, int AW> constexpr auto tail_kernel() {
   constexpr TailFormCfg c = tail_form_cfg(F);
-  if constexpr (c.bwd) return enf_tail_bwd_kernel<D, H, BF16, LA2, c.chain, c.wg, c.loss, c.cw, c.seed, AW>;
+  if constexpr (c.bwd) return enf_tail_bwd_kernel<D, H, BF16, LA2, c.chain, c.wg, c.loss, c.cw, c.seed, AW, c.grp>;
   else return enf_tail_fwd_kernel<D, H, BF16, LA2, c.chain, c.eval, AW>;
 }
 template <int D, int H, bool BF16, TailForm F, bool LA2, int AW>
-static int launch_tail_kernel(const TailArgs& A, dim3 grid, hipStream_t st) {
+static int launch_tail_kernel(const TailArgsG& A, dim3 grid, hipStream_t st) {
   constexpr auto kern = tail_kernel<D, H, BF16, F, LA2, AW>();
+  // (the kernel's own argument block: the grouped forms take the whole struct, the others its TailArgs part)
+  using Args = TailArgsFor<tail_form_cfg(F).grp || tail_form_cfg(F).eval == 3>;
   constexpr int smem = LA2 ? TailCfg<D, H, BF16>::SMEM3 : TailCfg<D, H, BF16>::SMEM;
   if (!enf_lds_attr<kern>(smem)) return ENF_ELAUNCH;
-  hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, st, A);
+  hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, st, static_cast<const Args&>(A));
   return hipGetLastError() == hipSuccess ? 0 : ENF_ELAUNCH;
 }
 
 template <int D, int H, bool BF16, TailForm F>
-static int launch_tail_form(const TailArgs& A, hipStream_t st) {
+static int launch_tail_form(const TailArgsG& A, hipStream_t st) {
   constexpr TailFormCfg c = tail_form_cfg(F);
   // fewer active waves: deterministic mode keeps eight (the partial-sum slots enf_launch_loss_sum reads are those of the 8-wave grid)
   int aw = NWAVES;
@@ -626,6 +696,7 @@ static int launch_tail_form(const TailArgs& A, hipStream_t st) {
   if (c.seed && (A.seed < 0 || A.seed >= A.O)) return ENF_EINVAL;
   if ((c.eval || c.loss) && !A.target) return ENF_EINVAL;
   if ((c.eval == 2 || c.cw) && !A.weight) return ENF_EINVAL;
+  if ((c.eval == 3 || c.grp) && (A.G < 1 || A.G > 16 || (A.G & (A.G - 1)) || A.NQ % A.G)) return ENF_EINVAL;
   // (run-time la2, aw) -> template arguments; the instantiations with fewer active waves run the 3-slot ring only
   if constexpr (tail_form_has_aw(F)) {
     if (aw == 4) return launch_tail_kernel<D, H, BF16, F, true, 4>(A, grid, st);
@@ -636,18 +707,18 @@ static int launch_tail_form(const TailArgs& A, hipStream_t st) {
 }
 
 // run-time form and shape -> launch_tail_form
-template <class S, int F = 0> static int launch_tail_shape(const TailArgs& A, TailForm form, hipStream_t st) {
+template <class S, int F = 0> static int launch_tail_shape(const TailArgsG& A, TailForm form, hipStream_t st) {
   if (form == F) return launch_tail_form<S::D, S::H, S::BF16, (TailForm)F>(A, st);
   if constexpr (F + 1 < TF_COUNT) return launch_tail_shape<S, F + 1>(A, form, st);
   else return ENF_EINVAL;
 }
-static int launch_tail(const EnfDims& m, const TailArgs& A, TailForm form, hipStream_t st) {
+static int launch_tail(const EnfDims& m, const TailArgsG& A, TailForm form, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   return enf_for_shape(m, [&](auto s) { return launch_tail_shape<decltype(s)>(A, form, st); });
 }
 // what every form's arguments share; the entry points below set what differs
-static TailArgs tail_args(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar) {
-  TailArgs A{};
+static TailArgsG tail_args(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar) {
+  TailArgsG A{};
   A.ybar = ybar; A.blob = blob; A.L = L;
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
   return A;
@@ -660,7 +731,7 @@ int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, cons
 int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
                        const float* dout, float* dybar, float* delta, float* act, float* tdel, unsigned flags, hipStream_t st) {
   const bool bwd = flags & ENF_TAIL_BWD, stash = flags & ENF_TAIL_STASH;
-  TailArgs A = tail_args(m, L, blob, ybar);
+  TailArgsG A = tail_args(m, L, blob, ybar);
   A.out = out; A.dout = dout; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = tdel;
   A.ybar_half = (!bwd && (flags & ENF_TAIL_YBAR_HALF) && m.bf16) ? 1 : 0;
   const TailForm form = !bwd ? (stash ? TF_FWD_STASH : TF_FWD) : tdel ? (stash ? TF_WG_STASH : TF_WG) : (stash ? TF_BWD_STASH : TF_BWD);
@@ -669,7 +740,7 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
 
 int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
                          float* act, hipStream_t st) {
-  TailArgs A = tail_args(m, L, blob, ybar);
+  TailArgsG A = tail_args(m, L, blob, ybar);
   A.seed = seed; A.dybar = dybar; A.delta = delta; A.act = act;
   return launch_tail(m, A, TF_SEED_STASH, st);
 }
@@ -677,7 +748,7 @@ int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob,
 // stash followed by enf_launch_tail_seed compute, bit for bit.
 int enf_launch_tail_fwd_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
                              float* delta, float* act, hipStream_t st) {
-  TailArgs A = tail_args(m, L, blob, ybar);
+  TailArgsG A = tail_args(m, L, blob, ybar);
   A.out = out; A.seed = seed; A.dybar = dybar; A.delta = delta; A.act = act;
   return launch_tail(m, A, TF_FWD_SEED, st);
 }
@@ -687,9 +758,10 @@ int enf_tail_loss_parts(const EnfDims& m) {
 }
 
 // the fused loss and the evaluation tail: target, weights, the loss and its deterministic partials, the per-point errors
-static int tail_loss_kernel(const EnfDims& m, TailArgs& A, TailForm form, const float* target, const float* weight, float gscale, float* loss,
-                            float* loss_part, float* err, hipStream_t st) {
-  A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)m.N * (float)m.O);
+static int tail_loss_kernel(const EnfDims& m, TailArgsG& A, TailForm form, const float* target, const float* weight, float gscale, float* loss,
+                            float* loss_part, float* err, hipStream_t st, int G = 1) {
+  // (G: the grouped forms' group size -- the mean is over the B M O observed values, M = N / G)
+  A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)(m.N / G) * (float)m.O);
   A.loss_part = loss_part; A.err = err;
   if (int rc = launch_tail(m, A, form, st)) return rc;
   return loss_part ? enf_launch_loss_sum(loss_part, enf_tail_loss_parts(m), loss, st) : 0;
@@ -698,15 +770,25 @@ static int tail_loss_kernel(const EnfDims& m, TailArgs& A, TailForm form, const 
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
                          bool per_value, float* err) {
-  TailArgs A = tail_args(m, L, blob, ybar);
+  TailArgsG A = tail_args(m, L, blob, ybar);
   A.dybar = dybar; A.delta = delta; A.act = act;
   return tail_loss_kernel(m, A, per_value ? TF_LOSS_CW : TF_LOSS, target, weight, gscale, loss, loss_part, err, st);
 }
 
 int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part) {
-  TailArgs A = tail_args(m, L, blob, ybar);
+  TailArgsG A = tail_args(m, L, blob, ybar);
   return tail_loss_kernel(m, A, per_value ? TF_EVAL_CW : TF_EVAL, target, weight, 0.f, loss, loss ? loss_part : nullptr, err, st);
+}
+
+// Grouped observations: the fused loss (dybar != NULL) or the evaluation tail (dybar == NULL) against target (B, N / G, O).
+int enf_launch_tail_group(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target, const EnfGroupObs& g,
+                          float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
+  if (!enf_group_size_ok(g.G) || m.N % g.G) return ENF_EINVAL;
+  TailArgsG A = tail_args(m, L, blob, ybar);
+  A.dybar = dybar; A.delta = delta; A.act = act;
+  A.G = g.G; A.qweight = g.qweight; A.oweight = g.oweight; A.err_g = g.err_g;
+  return tail_loss_kernel(m, A, dybar ? TF_LOSS_G : TF_EVAL_G, target, nullptr, gscale, loss, loss ? loss_part : nullptr, nullptr, st, g.G);
 }
 
 #ifdef ENF_TEST_HOOKS

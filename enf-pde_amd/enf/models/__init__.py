@@ -848,3 +848,96 @@ class EquivariantCrossAttentionNeF:
         _lib.launch(e.device, _lib.load().enf_signal_sum, _ptr(e), B, N, 1.0 / (float(N) * float(self.num_out)), _ptr(loss_b),
                     _lib.stream(e.device))
         return loss_b
+
+    # ------------------------------------------------------------------ grouped observations (cell averages)
+    GROUP_SIZES = (1, 2, 4, 8, 16)
+
+    def _cell_args(self, what, x, p, a, target, group, qweight, obs_weight):
+        """The shapes of a grouped call, checked before anything touches the device: x (B, N, dx) with N = M * group, target
+        (B, M, O), qweight (B, N) or None, obs_weight (B, M) or None.  Returns (B, Z, N, M)."""
+        if self.num_layers > 0:
+            raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
+        if int(group) not in self.GROUP_SIZES:
+            raise ValueError(f"group must be one of {self.GROUP_SIZES}, got {group}")
+        if x.dim() != 3 or p.dim() != 3 or a.dim() != 3:
+            raise ValueError("x, p and a must be (batch, ., .)")
+        B, Z, N = p.shape[0], p.shape[1], x.shape[1]
+        if x.shape[0] != B or a.shape[0] != B or a.shape[1] != Z:
+            raise ValueError(f"x {tuple(x.shape)}, p {tuple(p.shape)} and a {tuple(a.shape)} disagree on the batch or the latents")
+        if N % int(group):
+            raise ValueError(f"x holds {N} query points per signal, not a multiple of group = {group}")
+        M = N // int(group)
+        if tuple(target.shape) != (B, M, self.num_out):
+            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, self.num_out)}")
+        if qweight is not None and tuple(qweight.shape) != (B, N):
+            raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
+        if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
+            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
+        if not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda):
+            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
+        return B, Z, N, M
+
+    @torch.no_grad()
+    def mse_value_and_cell_grads(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None,
+                                 grad_scale=1.0, loss_out=None, return_errors=False):
+        """The fit step against GROUPED observations (include/enf_hip.h, "Grouped observations": enf_fit_step_g): observation m of a
+        signal is obs[m] = sum_k qweight[m group + k] out[m group + k] over the ``group`` consecutive query rows it owns -- a quadrature
+        rule over a cell (fitting/cells.py: cell_quadrature) -- and
+            loss = sum_{b,m} obs_weight[b,m] sum_o (obs - target)^2 / (B M O),        target (B, M, O), M = N / group.
+        ``group``: 1, 2, 4, 8 or 16.  ``qweight``: (B, N) finite factors, or None for 1 / group (the plain mean); ``obs_weight``: (B, M),
+        finite and >= 0, or None for 1 -- an observation of weight 0 does not exist, its target may be NaN.  Nothing is normalised.
+        The group sum, the loss and d out are formed in the fused tail's registers: no ``out`` in memory, no autograd graph.
+        ``loss_out``: an already ZEROED float32 (1,) tensor the loss is added to.  ``return_errors``: also err_g (B, M) =
+        obs_weight sum_o (obs - target)^2 and loss_b (B,) = err_g.sum(1) / (M O).
+        Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err_g, loss_b)."""
+        B, Z, N, M = self._cell_args("mse_value_and_cell_grads", x, p, a, target, group, qweight, obs_weight)
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        lib = _lib.load()
+        packed = self.pack(params)
+        p_, a_, s_ = self._latent_args(p, a, sigma)
+        dev = p_.device
+        xb, xstride = self._x_arg(x.float())
+        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
+        tgt = target.float().contiguous()
+        q_ = qweight.float().contiguous() if qweight is not None else None
+        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
+        loss = loss_out if loss_out is not None else torch.zeros(1, device=dev, dtype=torch.float32)
+        dp, da = torch.empty_like(p_), torch.empty_like(a_)
+        dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
+        err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
+        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
+        _lib.launch(dev, lib.enf_fit_step_g, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    int(group), _ptr(q_), _ptr(w_), float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(err), _ptr(loss_b),
+                    _ptr(ws), ws.numel(), self._det_flag(), st)
+        self._ws_touch(ws)
+        res = (loss, dp, da, dsig if sigma is not None else None)
+        return res + (err, loss_b) if return_errors else res
+
+    @torch.no_grad()
+    def eval_cell_loss(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None, loss_out=None,
+                       per_signal=True):
+        """Evaluation against grouped observations without a decode (include/enf_hip.h: enf_eval_loss_g): err_g (B, M) and loss_b (B,)
+        as mse_value_and_cell_grads(return_errors=True) gives them at the same point -- the same bits, in every mode.  ``loss_out``: an
+        already ZEROED float32 (1,) tensor; the scalar loss is added to it.  ``per_signal`` False skips loss_b.
+        Returns (loss_b or None, err_g)."""
+        B, Z, N, M = self._cell_args("eval_cell_loss", x, p, a, target, group, qweight, obs_weight)
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        lib = _lib.load()
+        packed = self.pack(params)
+        p_, a_, s_ = self._latent_args(p, a, sigma)
+        dev = p_.device
+        xb, xstride = self._x_arg(x.float())
+        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
+        tgt = target.float().contiguous()
+        q_ = qweight.float().contiguous() if qweight is not None else None
+        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
+        err = torch.empty((B, M), device=dev, dtype=torch.float32)
+        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
+        _lib.launch(dev, lib.enf_eval_loss_g, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    int(group), _ptr(q_), _ptr(w_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
+        self._ws_touch(ws)
+        return loss_b, err

@@ -8,7 +8,8 @@
   decode_tangent, decode_tendency  (no counterpart)             the decode in forward mode along a latent direction; d u / d t under the latent ODE
   decode_directional, decode_material_derivative  (no counterpart)   the same pass along a query direction: c . grad u, and Du/Dt = u_t + c . grad u
   cg_solve, lm_fit_latents  (no counterpart)                   batched CG on the native Gauss-Newton product; Levenberg-Marquardt latent fits
-  shard_signals / allreduce_mean_   SURVEY.md 8e               meta-batch data parallelism over RCCL
+  cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
+  shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
   ode_models           ode_models/ponita_ode_g.py, mlp_ode.py  PonitaODEGen (fused SepGconv HIP kernels), MLPODE
   solve_latent_ode     trainers/trainer_utils/solvers.py:69-162 Euler / RK4 over the latent tuple
@@ -19,6 +20,7 @@ from .model import get_model_pde
 from .inner_loop import inner_loop, decode, make_masks, make_signal_masks, default_meta_sgd_lrs
 from .derivatives import decode_jacobian, decode_tangent, decode_tendency, decode_directional, decode_material_derivative, divergence, curl_2d, gradient_norm
 from .gauss_newton import cg_solve, lm_fit_latents
+from .cells import cell_quadrature, decode_cell_averages, fit_cell_averages, draw_cell_samples
 from .parallel import shard_range, allreduce_mean_, init_distributed
 from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState, draw_point_masks
 from .trainers.trainer_utils import solve_latent_ode
@@ -27,4 +29,5 @@ from .ode_models import PonitaODEGen, MLPODE
 __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_masks", "default_meta_sgd_lrs", "shard_range",
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
-           "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents"]
+           "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
+           "draw_cell_samples"]

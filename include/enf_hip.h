@@ -436,6 +436,41 @@ int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const flo
  * atomics, no scratch, any N >= 1, 64-bit offsets.  The kernel enf_fit_step_e and enf_eval_loss run.  NULL or B, N < 1: ENF_EINVAL. */
 int enf_signal_sum(const float* err, int32_t B, int32_t N, float scale, float* loss_b, void* stream);
 
+/* Grouped observations (enf_fit_step_g, enf_eval_loss_g): data that are cell averages, not point values -- the cell means of a
+ * finite-volume solver, the box means of a reanalysis, a footprint's weighted mean.  An observation is a fixed linear functional of the
+ * decode, a quadrature rule over a few query points per cell, and the fused tail forms it in registers in front of the squared error.
+ *     G is the group size, one of {1, 2, 4, 8, 16};  N = M * G queries per signal;  observation m of signal b owns the CONSECUTIVE
+ *     query rows m G .. m G + G - 1 of x (B, N, dx; x_bstride as everywhere, 0 = one set of cells for all signals).
+ *     obs[b,m,o] = sum_{k<G} q[b, mG+k] * out[b, mG+k, o]         q = qweight (B, N), or NULL = 1/G exactly
+ *     loss       = 1/(B M O) * sum_{b,m} w[b,m] * sum_o (obs[b,m,o] - target[b,m,o])^2
+ *     d out[b, mG+k, o] = 2 * q[b,mG+k] * w[b,m] * (obs - target)[b,m,o] / (B M O) * grad_scale
+ *     err_g[b,m] = w[b,m] * sum_o (obs - target)^2                 loss_b[b] = sum_m err_g[b,m] / (M O)
+ * target is (B, M, O); w = oweight (B, M), or NULL for 1.  The zero-weight rule of "Weighted loss" holds per OBSERVATION: w[b,m] == 0
+ * is a select, so that observation's target may be NaN or Inf, and its share of the loss and of every d out of its group is exactly
+ * 0.0f.  q is a plain factor: it must be finite (any sign; q == 0 is a product, not a select) and the kernel multiplies with it.
+ * Nothing is normalised by the library: a caller who wants cell MEANS passes factors that sum to 1 per group (NULL does).
+ * The group sum is a fixed xor tree over the 16 query lanes of a wave's tile -- a group never straddles a tile, a signal or the rows
+ * beyond B N, because tiles start at multiples of 16, G divides 16 and G divides N -- so obs, err_g and d out are the same bits in
+ * every mode, as err is ("Per-signal and per-point errors"); ENF_FIT_DETERMINISTIC concerns `loss` and the gradients, as there.
+ * The host sequences, workspace sizes and served descriptors are those of enf_fit_step_w / enf_eval_loss (every width, head count,
+ * embedding, invariant, precision, pair-kernel variant and relu-mask mode); the tail runs an instantiation of its own, one for every G.
+ * flags: 0 or ENF_FIT_DETERMINISTIC.  ENF_FIT_SHARED_LATENTS is ENF_EINVAL: the shared backward's loss is another kernel, which has no
+ * grouped form (out of scope).  ENF_EINVAL, behind the descriptor's errors and before anything is launched, also for: G outside the
+ * set; N % G != 0; target == NULL; enf_fit_step_g with loss_b but without err_g (the fit step's workspace has no free region for the
+ * errors; enf_eval_loss_g allows it, through the region enf_eval_loss uses); enf_eval_loss_g with loss, err_g and loss_b all NULL.
+ * G == 1 is legal: with q == 1 (or NULL) it is the per-point loss, and the result agrees with enf_fit_step_w(weight = w) to rounding --
+ * not bit for bit, it is another instantiation.  (With q != 1 the residual is q out - target, not out - target.)
+ * `loss` is accumulated (the caller zeroes it), err_g and loss_b are OVERWRITTEN; nothing past [0, B M) and [0, B) is written. */
+int enf_fit_step_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                   const void* packed, const float* target /* (B,M,O) */, int32_t G, const float* qweight /* (B,N) or NULL */,
+                   const float* oweight /* (B,M) or NULL */, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                   float* err_g /* (B,M) or NULL */, float* loss_b /* (B) or NULL, needs err_g */, void* workspace, size_t workspace_bytes,
+                   unsigned flags, void* stream);
+int enf_eval_loss_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                    const void* packed, const float* target /* (B,M,O) */, int32_t G, const float* qweight /* (B,N) or NULL */,
+                    const float* oweight /* (B,M) or NULL */, float* loss /* scalar, accumulated, or NULL */, float* err_g /* (B,M) or NULL */,
+                    float* loss_b /* (B) or NULL */, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
 /* Derivative fields (enf_field_grad, enf_query_vjp): the Jacobian of a decode with respect to its query coordinates -- grad u, the
  * vorticity or divergence of a velocity field, a PDE residual on a decoded frame -- in one call, without the weight-gradient machinery.
  *     jac[o,b,n,i] = d out[b,n,o] / d x[b,n,i]        (O, B, N, dx) fp32, channel-major, required, OVERWRITTEN

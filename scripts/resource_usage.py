@@ -35,8 +35,10 @@ def parse(paths):
     out = {}
     for n, d in zip(names, dem):
         d = re.sub(r"^void ", "", d)
-        d = re.sub(r"\((TailArgs|PairBwdArgs)\)$", "", d)
+        d = re.sub(r"\((TailArgs|PairBwdArgs|std::conditional<[^<>]*, TailArgsG, TailArgs>::type)\)$", "", d)
         if d.startswith("enf_tail_"):
+            if d.startswith("enf_tail_bwd_kernel"):
+                d = re.sub(r", false>$", ">", d)      # the backward tail's trailing GRP = false is the default: the name it had before
             d = re.sub(r", 8>$", ">", d)      # the tail's trailing AW = 8 is the default: the name it had before AW existed
         out[d] = tuple(rows[n].get(k, "?") for k in KEYS)
     return out
