@@ -15,7 +15,7 @@ from oracle import enf_ref_np as R
 from oracle import enf_ref_torch as T
 from tests.helpers import make_cfg, make_inputs
 
-B, Z, O = 3, 7, 2
+B, Z = 3, 7
 _CASES = {}
 
 
@@ -55,10 +55,10 @@ def cell_loss(cfg, prm, x, p, a, s, target, G, q=None, w=None, grad_scale=1.0, g
               g=g, out_max=float(out.detach().abs().max()))
 
 
-def case(inv, G, N, D=64, H=2, seed=71):
-    """One problem and its reference: B = 3 signals, Z = 7 latents, O = 2 channels, N = M G points per signal; random q > 0, random
+def case(inv, G, N, D=64, H=2, seed=71, O=2):
+    """One problem and its reference: B = 3 signals, Z = 7 latents, O channels, N = M G points per signal; random q > 0, random
     targets (residuals are O(1)), w with about a third exact zeros.  `target` is clean; `poisoned(kind)` puts NaN / Inf under w == 0."""
-    key = (inv, G, N, D, H, seed)
+    key = (inv, G, N, D, H, seed, O)
     if key not in _CASES:
         cfg = make_cfg(inv, D=D, H=H, C=12, O=O, freq=(0.3, 0.6))
         prm = R.init_params(seed, cfg, jitter=0.1)
@@ -72,7 +72,7 @@ def case(inv, G, N, D=64, H=2, seed=71):
         w[1, 0] = 0.0
         gs = float(B)
         ref = cell_loss(cfg, prm, x, p, a, s, y, G, q, w, gs)
-        _CASES[key] = NS(cfg=cfg, prm=prm, x=x, p=p, a=a, s=s, q=q, y=y, w=w, G=G, N=N, M=M, gs=gs, ref=ref)
+        _CASES[key] = NS(cfg=cfg, prm=prm, x=x, p=p, a=a, s=s, q=q, y=y, w=w, G=G, N=N, M=M, O=O, gs=gs, ref=ref)
     return _CASES[key]
 
 

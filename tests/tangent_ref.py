@@ -29,12 +29,12 @@ def make_tangents(p, a, s, seed):
     return 0.3 * rng.standard_normal(p.shape), rng.standard_normal(a.shape), 0.1 * rng.standard_normal(s.shape)
 
 
-def case(inv, D=64, H=2, C=8, O=2, B=3, N=50, Z=7, seed=1, use_window=True):
+def case(inv, D=64, H=2, C=8, O=2, B=3, N=50, Z=7, seed=1, use_window=True, freq=(0.05, 0.1)):
     """(cfg, prm, (x, p, a, s), (dp, da, ds), out_ref, tan_ref); the defaults are the shape the reference was validated at: N = 50
     leaves a partial 16-query tile, Z = 7 leaves a wave without a latent."""
-    key = (inv, D, H, C, O, B, N, Z, seed, use_window)
+    key = (inv, D, H, C, O, B, N, Z, seed, use_window, tuple(freq))
     if key not in _CASES:
-        cfg = make_cfg(inv, D=D, H=H, C=C, O=O, use_window=use_window)
+        cfg = make_cfg(inv, D=D, H=H, C=C, O=O, use_window=use_window, freq=freq)
         prm = R.init_params(0, cfg, jitter=0.1)
         xpas = make_inputs(cfg, B, N, Z, seed)
         tang = make_tangents(*xpas[1:], seed + 100)

@@ -40,13 +40,13 @@ def make_xdot(x, seed):
     return np.random.default_rng(seed).standard_normal(x.shape)
 
 
-def case(inv, D=64, H=2, C=8, O=2, B=3, N=50, Z=7, seed=1, num_in=2, use_window=True):
+def case(inv, D=64, H=2, C=8, O=2, B=3, N=50, Z=7, seed=1, num_in=2, use_window=True, freq=(0.05, 0.1)):
     """(cfg, prm, (x, p, a, s), xdot, (dp, da, ds), out_ref, tan_x_ref, tan_all_ref): tan_x_ref along xdot alone, tan_all_ref along all
     four tangents.  The defaults are tests/tangent_ref.py's shape (a partial 16-query tile, a wave without a latent) with its inputs and
     latent tangents."""
-    key = (inv, D, H, C, O, B, N, Z, seed, num_in, use_window)
+    key = (inv, D, H, C, O, B, N, Z, seed, num_in, use_window, tuple(freq))
     if key not in _CASES:
-        cfg = make_cfg(inv, D=D, H=H, C=C, O=O, num_in=num_in, use_window=use_window)
+        cfg = make_cfg(inv, D=D, H=H, C=C, O=O, num_in=num_in, use_window=use_window, freq=freq)
         prm = R.init_params(0, cfg, jitter=0.1)
         xpas = make_inputs(cfg, B, N, Z, seed)
         tang = make_tangents(*xpas[1:], seed + 100)

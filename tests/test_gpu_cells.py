@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import enf_ref_np as R
-from tests.cells_ref import B, O, Z, case, f32, fit_loop, poisoned, rel
+from tests.cells_ref import B, Z, case, f32, fit_loop, poisoned, rel
 from tests.helpers import build_nef, make_cfg
 from tests.test_gpu_forward import TOL as TAU
 from enf_pde_amd import _lib
@@ -83,11 +83,11 @@ def _same_bits(u, v, names=("loss", "dp", "da", "ds", "err", "loss_b")):
     return [n for n in names if not torch.equal(getattr(u, n), getattr(v, n))]
 
 
-@pytest.mark.parametrize("D,H,precision,inv,gn", CASES)
-def test_fit_step_and_evaluation_match_the_reference(cuda, D, H, precision, inv, gn):
-    """loss, d(p, a, sigma), err_g and loss_b against tests/cells_ref.py in fp64, NaN / Inf targets under every zero weight; the
-    evaluation call gives the fit step's err_g and loss_b, bit for bit; loss_b.mean() is the loss; nothing behind the outputs."""
-    c = case(inv, *gn, D=D, H=H)
+def check_fit_step_and_evaluation(cuda, c, precision, what):
+    """One case of tests/cells_ref.py (any num_out: c.O) through enf_fit_step_g and enf_eval_loss_g: loss, d(p, a, sigma), err_g and
+    loss_b against the fp64 reference, NaN / Inf targets under every zero weight; the evaluation call gives the fit step's err_g and
+    loss_b, bit for bit; loss_b.mean() is the loss; nothing behind the outputs.  (tests/test_gpu_wide_out.py runs it at num_out 5, 32.)"""
+    O = c.O
     nef, params = _model(cuda, c, precision)
     tol_l, tol_g = TOL[precision]
     fit = _run(cuda, nef, params, c, "fit")
@@ -102,7 +102,7 @@ def test_fit_step_and_evaluation_match_the_reference(cuda, D, H, precision, inv,
     lbound = ebound.sum(1) / (c.M * O)
     d_err, d_lb = np.abs(fit.err.double().cpu().numpy() - c.ref.err_g), np.abs(fit.loss_b.double().cpu().numpy() - c.ref.loss_b)
     e_err, e_lb = float((d_err / np.maximum(ebound, 1e-300))[ebound > 0].max()), float((d_lb / np.maximum(lbound, 1e-300)).max())
-    print(f"cells {D}x{H} {precision} {inv} G={gn[0]} N={gn[1]}: loss {e_loss:.2e} dp {e_g[0]:.2e} da {e_g[1]:.2e} dsigma {e_g[2]:.2e} "
+    print(f"cells {what} {precision}: loss {e_loss:.2e} dp {e_g[0]:.2e} da {e_g[1]:.2e} dsigma {e_g[2]:.2e} "
           f"err_g / bound {e_err:.2e} loss_b / bound {e_lb:.2e} eval loss {abs(float(ev.loss) - c.ref.loss) / c.ref.loss:.2e}")
     assert e_loss <= tol_l and abs(float(ev.loss) - c.ref.loss) <= tol_l * c.ref.loss
     assert all(e <= tol_g for e in e_g), e_g
@@ -116,6 +116,13 @@ def test_fit_step_and_evaluation_match_the_reference(cuda, D, H, precision, inv,
     assert torch.equal(ev.err, fit.err) and torch.equal(ev.loss_b, fit.loss_b)
 
 
+@pytest.mark.parametrize("D,H,precision,inv,gn", CASES)
+def test_fit_step_and_evaluation_match_the_reference(cuda, D, H, precision, inv, gn):
+    """loss, d(p, a, sigma), err_g and loss_b against tests/cells_ref.py in fp64, NaN / Inf targets under every zero weight; the
+    evaluation call gives the fit step's err_g and loss_b, bit for bit; loss_b.mean() is the loss; nothing behind the outputs."""
+    check_fit_step_and_evaluation(cuda, case(inv, *gn, D=D, H=H), precision, f"{D}x{H} {inv} G={gn[0]} N={gn[1]}")
+
+
 @pytest.mark.parametrize("inv", INVS)
 @pytest.mark.parametrize("gn", PAIRS)
 def test_fit_step_matches_the_composed_route(cuda, inv, gn):
@@ -124,7 +131,7 @@ def test_fit_step_matches_the_composed_route(cuda, inv, gn):
     nef, params = _model(cuda, c, "f32")
     t = _t(cuda)
     fit = _run(cuda, nef, params, c, "fit", target=t(c.y))
-    G, M = c.G, c.M
+    G, M, O = c.G, c.M, c.O
     leaves = [t(v).requires_grad_(True) for v in (c.p, c.a, c.s)]
     out = nef.apply(params, t(c.x), *leaves)
     with torch.no_grad():

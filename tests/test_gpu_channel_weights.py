@@ -202,7 +202,7 @@ def _lat0(rng, t, Zl):
     return {"p_pos": t(rng.standard_normal((1, Zl, 2))), "a": t(rng.standard_normal((1, Zl, 6)))}
 
 
-@pytest.mark.parametrize("O", [1, 3, 5])
+@pytest.mark.parametrize("O", [1, 3, 5, 17])
 @pytest.mark.parametrize("per_signal", [False, True])
 def test_gather_parity(cuda, per_signal, O):
     rng = np.random.default_rng(11)

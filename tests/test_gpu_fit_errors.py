@@ -96,9 +96,10 @@ def _t(cuda):
     return lambda v: torch.tensor(np.asarray(v), dtype=torch.float32, device=cuda)
 
 
-def _run(cuda, nef, params, c, form, kind, flags=0, target=None, shared_x=False, want=("loss", "err", "loss_b")):
-    """One raw C-ABI call: kind "fit" = enf_fit_step_e, "eval" = enf_eval_loss, "w" = enf_fit_step_w / _cw (the existing calls).
-    err and loss_b sit in NaN-filled buffers with GUARD floats behind them."""
+def _run(cuda, nef, params, c, form, kind, flags=0, target=None, shared_x=False, want=("loss", "err", "loss_b"), poison=255):
+    """One raw C-ABI call on a workspace filled with `poison`: kind "fit" = enf_fit_step_e, "eval" = enf_eval_loss, "w" =
+    enf_fit_step_w / _cw (the existing calls).  err and loss_b sit in NaN-filled buffers with GUARD floats behind them.  The latent
+    count is the case's own (c.p): tests/test_gpu_wide_out.py runs its Z = 7 cases through here."""
     lib = _lib.load()
     t = _t(cuda)
     B, N, O = c.shape
@@ -106,9 +107,9 @@ def _run(cuda, nef, params, c, form, kind, flags=0, target=None, shared_x=False,
     y = _targets(c, form, cuda) if target is None else target
     w = t(c.w) if form == "point" else None
     cw = t(c.cw) if form == "channel" else None
-    desc = nef._desc(B, N, Z)
+    desc = nef._desc(B, N, c.p.shape[1])
     nbytes = int(lib.enf_workspace_bytes_ex(ctypes.byref(desc), flags))
-    ws = torch.full((nbytes,), 255, device=cuda, dtype=torch.uint8)
+    ws = torch.full((nbytes,), poison, device=cuda, dtype=torch.uint8)
     packed = nef.pack(params)
     ptr = lambda v: ctypes.c_void_p(v.data_ptr()) if v is not None else None
     st = ctypes.c_void_p(torch.cuda.current_stream(cuda).cuda_stream)

@@ -51,7 +51,8 @@ def test_update_rejects_bad_segments(cuda):
     assert lib.enf_meta_sgd_update(1, seg, 1.0, None) == -1
 
 
-@pytest.mark.parametrize("B,Z,N,Ns,S,dx,O,ori", [(16, 64, 4096, 512, 3, 2, 1, False), (3, 7, 100, 37, 2, 3, 3, True), (1, 1, 5, 5, 0, 2, 1, False)])
+@pytest.mark.parametrize("B,Z,N,Ns,S,dx,O,ori", [(16, 64, 4096, 512, 3, 2, 1, False), (3, 7, 100, 37, 2, 3, 3, True), (1, 1, 5, 5, 0, 2, 1, False),
+                                                 (3, 7, 100, 37, 2, 2, 17, False)])     # num_out 17: the O-strided gather
 def test_fit_inputs_in_one_launch_equal_the_framework_ops(cuda, B, Z, N, Ns, S, dx, O, ori):
     """enf_fit_inputs (inner_loop's setup: the signals' copies of the latent initialisation, the gathered coordinates / targets of all
     S + 1 point sets, zeroed loss accumulators; pde_trainer.py:157-159, 193-197) against the torch operations it replaces: bit for bit."""

@@ -30,7 +30,7 @@ def _lat0(rng, t, Z):
 
 
 # ---- 1. the gather
-@pytest.mark.parametrize("Ns,dx,O", [(16, 2, 2), (16, 3, 1), (1, 2, 2)])
+@pytest.mark.parametrize("Ns,dx,O", [(16, 2, 2), (16, 3, 1), (1, 2, 2), (16, 2, 17)])
 @pytest.mark.parametrize("weighted", [True, False])
 def test_gather_parity(cuda, Ns, dx, O, weighted):
     rng = np.random.default_rng(11)
