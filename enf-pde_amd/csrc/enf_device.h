@@ -604,6 +604,29 @@ template <int NT> DEV void ln_apply(f32x4 (&X)[NT], float mu, float rstd) {
   }
 }
 
+// ------------------------------------------------------------------ ordered partial sums
+// The fixed-order sum of per-workgroup partials, 32 elements x 8 groups per 256-thread block: thread (group = tid >> 5, element =
+// tid & 31) runs add(s, w) -- `s += partial w of my element` -- for w = group, group + 8, ... < nwg on s = 0, the eight group sums meet
+// in LDS and group 0 returns their total, added in group order (the other groups return 0).  The order depends on nwg alone, never on
+// which workgroup finished first: bitwise reproducible.  A thread without an element passes live = false; every thread calls.
+DEV float sum8x32_meet(float s) {
+  __shared__ float red[8][32];
+  const int el = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  red[grp][el] = s;
+  __syncthreads();
+  if (grp != 0) return 0.f;
+  float t = red[0][el];
+#pragma unroll
+  for (int k = 1; k < 8; ++k) t += red[k][el];
+  return t;
+}
+template <class Add> DEV float sum8x32(int nwg, bool live, Add add) {
+  float s = 0.f;
+  if (live)
+    for (int w = threadIdx.x >> 5; w < nwg; w += 8) add(s, w);
+  return sum8x32_meet(s);
+}
+
 // ------------------------------------------------------------------ invariants + window
 // xq: query coordinate (dx <= 3) of this lane's column; pz: latent pose row from the latent
 // table: periodic/rel/abs/norm -> (p0,p1,p2,-); ponita -> (px,py,cos t,sin t);

@@ -50,6 +50,8 @@ inline size_t enf_det_dx_bytes(const EnfDims& m) { return enf_align(sizeof(float
 int enf_tail_loss_parts(const EnfDims& m);
 // *loss += part[0] + ... + part[n - 1], one workgroup, fixed order (enf_loss.hip)
 int enf_launch_loss_sum(const float* part, int n, float* loss, hipStream_t st);
+// out[e] (+)= part[0][e] + ... + part[nwg - 1][e], e < n: the fixed-order sum of per-workgroup partials (enf_ode.hip)
+void enf_launch_sum_partials(const float* part, int nwg, int n, float* out, int accumulate, hipStream_t st);
 struct EnfDetWorkspace { size_t part, loss, total; };      // byte offsets in the workspace, behind EnfWorkspace::total
 inline EnfDetWorkspace enf_det_workspace(const EnfDims& m, const EnfWorkspace& W) {
   EnfDetWorkspace X;

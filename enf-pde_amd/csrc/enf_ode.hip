@@ -15,6 +15,7 @@
 // wave: 22.5 us per call at B=16, Z=64, J=64, C=128 = 0.31 of the fp32-MFMA peak.)
 #include <hip/hip_runtime.h>
 #include "enf_launch.h"
+#include "enf_device.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define OB_MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
@@ -157,14 +158,13 @@ extern "C" int enf_ode_conv_forward(int B, int Z, int J, int C, const float* a, 
   while (cg > 1 && (long)B * Z * (CT / cg) < 2048) cg /= 2;
   const dim3 grid(CT / cg, (Z + 3) / 4, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-  bool hit = false;                                          // a shape no instantiation covers is an error, not a no-op
-#define ODE_FWD(JM_, CG_) if (JM == JM_ && cg == CG_) { hit = true; hipLaunchKernelGGL((enf_ode_conv_fwd_kernel<JM_, CG_>), grid, block, 0, st, A); }
+#define ODE_FWD(JM_, CG_) if (JM == JM_ && cg == CG_) hipLaunchKernelGGL((enf_ode_conv_fwd_kernel<JM_, CG_>), grid, block, 0, st, A); else
   ODE_FWD(1, 1) ODE_FWD(1, 2) ODE_FWD(1, 4) ODE_FWD(1, 8)
   ODE_FWD(2, 1) ODE_FWD(2, 2) ODE_FWD(2, 4) ODE_FWD(2, 8)
   ODE_FWD(4, 1) ODE_FWD(4, 2) ODE_FWD(4, 4) ODE_FWD(4, 8)
   ODE_FWD(8, 1) ODE_FWD(8, 2) ODE_FWD(8, 4)
+  return ENF_EUNSUPPORTED;                                   // a shape no instantiation covers is an error, not a no-op
 #undef ODE_FWD
-  if (!hit) return ENF_EUNSUPPORTED;
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
@@ -180,15 +180,14 @@ extern "C" int enf_ode_conv_backward_basis(int B, int Z, int J, int C, const flo
   while (jg > 1 && (long)B * Z * (JT / jg) < 2048) jg /= 2;
   const dim3 grid(JT / jg, (Z + 3) / 4, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-  bool hit = false;
-#define ODE_DKB(CM_, JG_) if (CM == CM_ && jg == JG_) { hit = true; hipLaunchKernelGGL((enf_ode_conv_dkb_kernel<CM_, JG_>), grid, block, 0, st, A); }
+#define ODE_DKB(CM_, JG_) if (CM == CM_ && jg == JG_) hipLaunchKernelGGL((enf_ode_conv_dkb_kernel<CM_, JG_>), grid, block, 0, st, A); else
   ODE_DKB(1, 1) ODE_DKB(1, 2) ODE_DKB(1, 4) ODE_DKB(1, 8)
   ODE_DKB(2, 1) ODE_DKB(2, 2) ODE_DKB(2, 4) ODE_DKB(2, 8)
   ODE_DKB(4, 1) ODE_DKB(4, 2) ODE_DKB(4, 4) ODE_DKB(4, 8)
   ODE_DKB(8, 1) ODE_DKB(8, 2) ODE_DKB(8, 4)
   ODE_DKB(16, 1) ODE_DKB(16, 2)
+  return ENF_EUNSUPPORTED;
 #undef ODE_DKB
-  if (!hit) return ENF_EUNSUPPORTED;
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
@@ -198,7 +197,7 @@ extern "C" int enf_ode_conv_backward_basis(int B, int Z, int J, int C, const flo
 // senders s0 + 4 q + 0..3 of a 16-sender tile.  A workgroup walks a contiguous share of the (b, r) rows; wave w owns the
 // channel tiles w, w + 4 for every basis tile, accumulates them in registers over the whole share and writes one partial
 // (J, C) per workgroup -- followed by its share of d bias[c] = sum_{b,r} g[b,r,c], which costs the kernel one add per row --;
-// enf_ode_sum_partials_kernel adds the partials in a fixed order.  C = 256: 4 channel tiles per wave would be 128 accumulators
+// enf_sum_partials_kernel adds the partials in a fixed order.  C = 256: 4 channel tiles per wave would be 128 accumulators
 // (512 registers) at J = 128, so the grid's y index splits the channels into groups of 4 CK tiles (two halves of 128); a group
 // writes its own columns of its row share's partial, d bias included, and the number of partials stays what it is.
 struct OdeConvDwArgs { const float* a; const float* kb; const float* g; float* part; int B, Z, J, C, rows_per_wg; };
@@ -265,21 +264,15 @@ __global__ __launch_bounds__(256) void enf_ode_conv_dw_kernel(OdeConvDwArgs A) {
   }
 }
 
-// out[e] = sum over w of part[w][e], e < n: 32 elements x 8 groups per block, each group a fixed stride-8 share, then the 8
-// group sums in order (bitwise reproducible).
-__global__ __launch_bounds__(256) void enf_ode_sum_partials_kernel(const float* part, int nwg, int n, float* out) {
-  __shared__ float red[8][32];
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), grp = threadIdx.x >> 5;
-  float s = 0.f;
-  if (e < n)
-    for (int w = grp; w < nwg; w += 8) s += part[(size_t)w * n + e];
-  red[grp][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (grp == 0 && e < n) {
-    float t = 0.f;
-    for (int g = 0; g < 8; ++g) t += red[g][threadIdx.x & 31];
-    out[e] = t;
-  }
+// out[e] (+)= sum over w of part[w][e], e < n, in the fixed order of sum8x32 (enf_device.h): the partial sum of this file's d W and
+// of enf_ode_block.hip's parameter gradients (accumulate: a later chunk adds to what `out` holds).
+__global__ __launch_bounds__(256) void enf_sum_partials_kernel(const float* part, int nwg, int n, float* out, int accumulate) {
+  const int e = blockIdx.x * 32 + (threadIdx.x & 31);
+  const float t = sum8x32(nwg, e < n, [&](float& s, int w) { s += part[(size_t)w * n + e]; });
+  if (threadIdx.x < 32 && e < n) out[e] = accumulate ? out[e] + t : t;
+}
+void enf_launch_sum_partials(const float* part, int nwg, int n, float* out, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(enf_sum_partials_kernel, dim3((n + 31) / 32), dim3(256), 0, st, part, nwg, n, out, accumulate);
 }
 
 static int ode_dw_wgs(int B, int Z) { return B * Z < 256 ? B * Z : 256; }
@@ -299,12 +292,12 @@ extern "C" int enf_ode_conv_backward_weight(int B, int Z, int J, int C, const fl
   OdeConvDwArgs A{a, kb, g, (float*)scratch, B, Z, J, C, rpw};
   const int JT = J / 16, CK = C > 64 ? 2 : 1, groups = C > 128 ? C / 128 : 1;
   hipStream_t st = (hipStream_t)stream;
-  bool hit = false;
-#define ODE_DW(JT_, CK_) if (JT == JT_ && CK == CK_) { hit = true; hipLaunchKernelGGL((enf_ode_conv_dw_kernel<JT_, CK_>), dim3(nwg, groups), dim3(256), 0, st, A); }
+  const dim3 grid(nwg, groups), block(256);
+#define ODE_DW(JT_, CK_) if (JT == JT_ && CK == CK_) hipLaunchKernelGGL((enf_ode_conv_dw_kernel<JT_, CK_>), grid, block, 0, st, A); else
   ODE_DW(1, 1) ODE_DW(2, 1) ODE_DW(4, 1) ODE_DW(8, 1) ODE_DW(1, 2) ODE_DW(2, 2) ODE_DW(4, 2) ODE_DW(8, 2)
+  return ENF_EUNSUPPORTED;
 #undef ODE_DW
-  if (!hit) return ENF_EUNSUPPORTED;
-  hipLaunchKernelGGL(enf_ode_sum_partials_kernel, dim3((J * C + C + 31) / 32), dim3(256), 0, st, (const float*)scratch, nwg, J * C + C, dW);
+  enf_launch_sum_partials((const float*)scratch, nwg, J * C + C, dW, 0, st);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 

@@ -19,6 +19,7 @@
 // I <= 4 (smaller I: zero-padded components meet zero weight rows), degree 3, hidden / basis widths multiples of 16.
 #include <hip/hip_runtime.h>
 #include "enf_launch.h"
+#include "enf_device.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define OB_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0)
@@ -557,22 +558,15 @@ __global__ __launch_bounds__(64 * OB_NW) void enf_ode_basis_bwd_kernel(ObArgs A)
 // Sums the workgroup partials in a fixed order and un-packs: d W1 (F, H1), d b1 (H1), d W3 (H1, J), d b3 (J).
 struct ObReduceArgs { const float* part; int nwg, I, H1, J, FP, PART; float* dW1; float* db1; float* dW3; float* db3; };
 __global__ __launch_bounds__(256) void enf_ode_basis_reduce_kernel(ObReduceArgs A) {
-  __shared__ float red[8][32];
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), grp = threadIdx.x >> 5;
+  const int e = blockIdx.x * 32 + (threadIdx.x & 31);
   const int n1 = A.H1 * A.FP, n3 = A.J * A.H1, n = n1 + n3 + A.J;
-  float s = 0.f;
-  if (e < n1 + n3) {
-    for (int w = grp; w < A.nwg; w += 8) s += A.part[(size_t)w * A.PART + e];
-  } else if (e < n) {                                           // d b3: one row per wave of a workgroup
-    const int j = e - n1 - n3;
-    for (int w = grp; w < A.nwg; w += 8)
-      for (int v = 0; v < OB_NW; ++v) s += A.part[(size_t)w * A.PART + n1 + n3 + v * A.J + j];
-  }
-  red[grp][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (grp == 0 && e < n) {
-    float t = 0.f;
-    for (int g = 0; g < 8; ++g) t += red[g][threadIdx.x & 31];
+  const float t = sum8x32(A.nwg, e < n, [&](float& s, int w) {
+    const float* p = A.part + (size_t)w * A.PART + e;
+    if (e < n1 + n3) s += *p;
+    else                                                          // d b3: one row per wave of a workgroup
+      for (int v = 0; v < OB_NW; ++v) s += p[v * A.J];
+  });
+  if (threadIdx.x < 32 && e < n) {
     if (e < n1) {
       const int h = e / A.FP, row = ob_orig_row(A.I, e % A.FP);
       if (row >= 0) A.dW1[(size_t)row * A.H1 + h] = t;
@@ -617,15 +611,8 @@ static void ob_pack(int I, int H1, int J, const float* W1, const float* W3, floa
   hipLaunchKernelGGL(enf_ode_basis_pack_kernel, dim3((FP * H1 + J * H1 + 255) / 256), dim3(256), 0, st, K);
 }
 
-#ifndef OB_PT_OVERRIDE
-#define OB_PT_OVERRIDE 0   // experiment: pair tiles per wave of the forward kernel (measured at 128 / 64 / I = 4: 1 -> 125 us, 2 -> 84 us, 4 -> 80 us at one wave per SIMD)
-#endif
 #define OB_SHAPES(X, I_) X(I_, 2, 2) X(I_, 4, 2) X(I_, 4, 4) X(I_, 8, 4) X(I_, 8, 8) X(I_, 2, 4) X(I_, 4, 8) X(I_, 2, 8) X(I_, 8, 2)
-#ifdef OB_ONLY_BENCH_SHAPE   // build-time aid: one instantiation
-#define OB_ALL(X) X(4, 8, 4)
-#else
 #define OB_ALL(X) OB_SHAPES(X, 1) OB_SHAPES(X, 2) OB_SHAPES(X, 3) OB_SHAPES(X, 4)
-#endif
 
 extern "C" int enf_ode_basis_forward(int64_t P, int I, int degree, int H1, int J, const float* inv, const float* W1,
                                      const float* b1, const float* W3, const float* b3, float* kb, void* scratch,
@@ -643,15 +630,14 @@ extern "C" int enf_ode_basis_forward(int64_t P, int I, int degree, int H1, int J
   bool done = false;
 #define OB_FWD(I_, H_, J_)                                                                                              \
   if (!done && I == I_ && H1T == H_ && JT == J_) {                                                                      \
-    constexpr int PT = OB_PT_OVERRIDE > 0 ? OB_PT_OVERRIDE : (H_ <= 8 ? 2 : 1);                                         \
+    /* pair tiles per wave; measured at H1 = 128, J = 64, I = 4: 1 -> 125 us, 2 -> 84 us, 4 -> 80 us at one wave per SIMD */ \
+    constexpr int PT = H_ <= 8 ? 2 : 1;                                                                                 \
     hipLaunchKernelGGL((enf_ode_basis_fwd_kernel<I_, H_, J_, PT>), dim3((unsigned)((P + 64 * PT - 1) / (64 * PT))),      \
                        dim3(256), 0, st, A);                                                                            \
     done = true;                                                                                                        \
   }
   OB_ALL(OB_FWD)
-#ifndef OB_ONLY_BENCH_SHAPE
   OB_FWD(4, 16, 8) OB_FWD(4, 16, 4) OB_FWD(3, 16, 8) OB_FWD(3, 16, 4)
-#endif
 #undef OB_FWD
   if (!done) return ENF_EUNSUPPORTED;
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;

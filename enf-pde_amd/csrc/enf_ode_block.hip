@@ -10,7 +10,7 @@
 //   backward: LayerNorm again, d h = g W2^T, d pre = d h gelu'(pre), d xn = d pre W1^T, LayerNorm backward -> d x; the weight
 //             gradients contract over the 16 rows of the tile (h^T g, xn^T d pre: operands read from the LDS tiles with the rows
 //             along K), bias / scale gradients are column sums of the same tiles; one partial per workgroup, summed in a
-//             fixed order (enf_ode_sum_partials-style reduction below; bitwise reproducible).
+//             fixed order (enf_launch_sum_partials; bitwise reproducible).
 // The sum over the MFMA's K index is order-free: lane quad q takes 4 CONSECUTIVE k of a 16-wide super-step, so operands that
 // are contiguous along K are one 16-byte load.
 #include <hip/hip_runtime.h>
@@ -259,22 +259,6 @@ __global__ __launch_bounds__(256) void enf_ode_block_bwd_kernel(BkArgs A) {
   }
 }
 
-// out[e] = sum over w of part[w][e]: 32 elements x 8 groups per block, fixed order
-__global__ __launch_bounds__(256) void enf_ode_block_sum_kernel(const float* part, int nwg, int n, float* out, int accumulate) {
-  __shared__ float red[8][32];
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), grp = threadIdx.x >> 5;
-  float s = 0.f;
-  if (e < n)
-    for (int w = grp; w < nwg; w += 8) s += part[(size_t)w * n + e];
-  red[grp][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (grp == 0 && e < n) {
-    float t = 0.f;
-    for (int g = 0; g < 8; ++g) t += red[g][threadIdx.x & 31];
-    out[e] = accumulate ? out[e] + t : t;
-  }
-}
-
 // --------------------------------------------------------------------------------------------------------------- host
 constexpr int BK_CHUNK_WGS = 256;       // rows per backward chunk = 16 x this
 
@@ -333,7 +317,7 @@ extern "C" int enf_ode_block_backward(int64_t R, int H, int M, const float* x, c
     else rc = bk_launch_bwd<8, 16>(A, dim3(nwg), st);
     if (rc) return rc;
     // (stream order: the next chunk's partials overwrite the scratch only after this sum has read it)
-    hipLaunchKernelGGL(enf_ode_block_sum_kernel, dim3((n + 31) / 32), dim3(256), 0, st, (const float*)scratch, nwg, n, dparams, r0 > 0 ? 1 : 0);
+    enf_launch_sum_partials((const float*)scratch, nwg, n, dparams, r0 > 0 ? 1 : 0, st);
   }
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }

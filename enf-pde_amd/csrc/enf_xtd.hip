@@ -227,10 +227,10 @@ template <bool BF16> DEV int xtd_stored_col(int t) {
 }
 
 // 32 output elements x 8 slice groups per workgroup: a thread sums its group's slices (sl = group, group + 8, ...) of every
-// source in order, the eight group sums are added in order through LDS -- a fixed summation tree, 8x the loads in flight
+// source in order (source after source: not sum8x32's one walk), the eight group sums are added in order through LDS
+// (sum8x32_meet, enf_device.h) -- a fixed summation tree, 8x the loads in flight
 template <int D, bool BF16>
 __global__ __launch_bounds__(256) void enf_xtd_reduce_kernel(XtdReduceArgs A) {
-  __shared__ float red[8][32];
   const int d = blockIdx.y, el = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int e = blockIdx.x * 32 + el;                     // element of the (D + 1) x D block; row D = the bias
   const bool live = e < (D + 1) * D;
@@ -242,12 +242,8 @@ __global__ __launch_bounds__(256) void enf_xtd_reduce_kernel(XtdReduceArgs A) {
       const float* p = A.part + ((size_t)A.src[d][k]) * (size_t)(D + 1) * D + (size_t)sr * D + sc;
       for (int sl = grp; sl < A.KS; sl += 8) s += p[(size_t)sl * A.NP * (D + 1) * D];
     }
-  red[grp][el] = s;
-  __syncthreads();
+  const float t = sum8x32_meet(s);
   if (grp == 0 && live) {
-    float t = red[0][el];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) t += red[k][el];
     float* dst = r < D ? A.w[d] + (size_t)r * A.ld[d] + c : A.b[d] + c;
     *dst = A.accumulate ? *dst + t : t;
   }

@@ -53,7 +53,8 @@ def main():
         drop = args[i + 1]
         del args[i:i + 2]
     old, new = kernels(args[0]), kernels(args[1])
-    strip = lambda d: re.sub(r"\(.*\)$", "", d)          # the template arguments identify a kernel; its parameter list may be spelt anew
+    # the template arguments identify a kernel; its parameter list may be spelt anew (a kernel of an unnamed namespace keeps its name)
+    strip = lambda d: re.sub(r"\(.*\)$", "", d.replace("(anonymous namespace)::", ""))
     dold = {strip(d): b for d, b in zip(demangle(list(old)), old.values())}
     dnew = {}
     for d, b in zip(demangle(list(new)), new.values()):
