@@ -28,6 +28,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum", "enf_fit_step_g", "enf_eval_loss_g",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
+           "enf_field_second_workspace_bytes", "enf_field_second_x",
            "enf_gn_workspace_bytes", "enf_gn_product", "enf_cg_update",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
@@ -261,6 +262,11 @@ def _bind(path, hooks):
     lib.enf_field_tangent.argtypes = [dp, vp, i64] + [vp] * 11
     # directional derivatives: enf_field_tangent with (xdot, xdot_bstride) behind (x, x_bstride); xdot may be NULL like the other tangents
     lib.enf_field_tangent_x.argtypes = [dp, vp, i64, vp, i64] + [vp] * 11
+    # second directional derivatives: x, x_bstride, xdot (required), xdot_bstride | p, a, sigma | blob | out | NULL, tan | NULL, tan2 |
+    # workspace, stream
+    lib.enf_field_second_workspace_bytes.restype = sz
+    lib.enf_field_second_workspace_bytes.argtypes = [dp]
+    lib.enf_field_second_x.argtypes = [dp, vp, i64, vp, i64] + [vp] * 9
     # Gauss-Newton product (include/enf_hip.h): p, a, sigma | vp, va, vsigma (each may be NULL) | packed, weight, cweight | grad_scale |
     # gp, ga, gsigma | workspace, bytes, flags, stream
     lib.enf_gn_workspace_bytes.restype = sz

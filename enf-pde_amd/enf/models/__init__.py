@@ -679,6 +679,34 @@ class EquivariantCrossAttentionNeF:
         self._ws_touch(ws)
         return out, tan
 
+    @torch.no_grad()
+    def second_derivative(self, params, x, p, a, gaussian_window_size, xdot, return_out=True, return_first=True):
+        """The decode in forward mode to second order along a direction in the query coordinates, in one native call
+        (include/enf_hip.h: enf_field_second_x): (out (B, N, O) or None, tan (B, N, O) or None, tan2 (B, N, O)) with
+        tan[b, n, o] = sum_i d out / d x[b, n, i] xdot[b, n, i] (``tangent``'s value along ``xdot`` alone) and
+        tan2[b, n, o] = sum_ij xdot[b, n, i] xdot[b, n, j] d^2 out / d x[b, n, i] d x[b, n, j].  With xdot = e_i tan2 is a diagonal entry of
+        the Hessian; fitting.decode_laplacian / decode_hessian build the operators from such passes.
+        ``xdot``: float32 (B, N, dx) on the latents' device, required, checked and passed as ``tangent`` does (a stride-0 batch expansion
+        is passed as such).  In the coordinates as given, as ``jacobian``: angles on the sphere, no metric factors.  Second derivatives as
+        autograd means them: almost everywhere, the relu kinks contribute nothing.
+        No autograd graph is built and none of the inputs gets a gradient.  Every element is written once without atomics: equal
+        inputs give equal bits.  ``return_out`` / ``return_first`` False skip the stores of the decode / the first derivative."""
+        if xdot is None:
+            raise ValueError("second_derivative needs xdot")
+        xb, xstride, p_, a_, s_ = self._tangent_args("second_derivative", x, p, a, gaussian_window_size,
+                                                     (("dp", None), ("da", None), ("dwindow", None)), xdot=xdot)
+        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
+        lib = _lib.load()
+        packed = self.pack(params)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lambda d, flags: lib.enf_field_second_workspace_bytes(d))
+        new = lambda: torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32)
+        out, tan, tan2 = (new() if return_out else None), (new() if return_first else None), new()
+        xd, xdstride = self._x_arg(xdot)
+        _lib.launch(dev, lib.enf_field_second_x, ctypes.byref(desc), _ptr(xb), xstride, _ptr(xd), xdstride, _ptr(p_), _ptr(a_), _ptr(s_),
+                    _ptr(packed), _ptr(out), _ptr(tan), _ptr(tan2), _ptr(ws), st)
+        self._ws_touch(ws)
+        return out, tan, tan2
+
     # ------------------------------------------------------------------ relu masks (second-order terms by differences)
     def relu_mask_buffer(self, B, N, Z, device):
         """Device buffer for the relu masks of a (B, N, Z) problem (enf_relu_mask_bytes)."""

@@ -7,6 +7,7 @@
   decode_jacobian, divergence, curl_2d, gradient_norm  (no counterpart)  the decode's Jacobian w.r.t. the coordinates and operators on it
   decode_tangent, decode_tendency  (no counterpart)             the decode in forward mode along a latent direction; d u / d t under the latent ODE
   decode_directional, decode_material_derivative  (no counterpart)   the same pass along a query direction: c . grad u, and Du/Dt = u_t + c . grad u
+  decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual  (no counterpart)   second derivatives in forward mode: c^T H c, the Laplacian, the Hessian, u_t - nu Lap u
   cg_solve, lm_fit_latents  (no counterpart)                   batched CG on the native Gauss-Newton product; Levenberg-Marquardt latent fits
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
   shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
@@ -19,6 +20,7 @@
 from .model import get_model_pde
 from .inner_loop import inner_loop, decode, make_masks, make_signal_masks, default_meta_sgd_lrs
 from .derivatives import decode_jacobian, decode_tangent, decode_tendency, decode_directional, decode_material_derivative, divergence, curl_2d, gradient_norm
+from .derivatives import decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual
 from .gauss_newton import cg_solve, lm_fit_latents
 from .cells import cell_quadrature, decode_cell_averages, fit_cell_averages, draw_cell_samples
 from .parallel import shard_range, allreduce_mean_, init_distributed
@@ -30,4 +32,4 @@ __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_m
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
            "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
-           "draw_cell_samples"]
+           "draw_cell_samples", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual"]

@@ -7,6 +7,11 @@
   decode_tendency(...)   (u, du/dt) on the full grid for latents that follow dz/dt = ode_model(z)
   decode_directional(...)          (u, D_c u = c . grad u) on the full grid along a direction field c in the query coordinates
   decode_material_derivative(...)  (u, Du/Dt = u_t + c . grad u): the latent ODE's tendency and the advection term in ONE tangent pass
+  decode_second_directional(...)   (u, c . grad u, c^T H c): the second directional derivative in one second-order forward-mode pass
+                                   (EquivariantCrossAttentionNeF.second_derivative, include/enf_hip.h: enf_field_second_x)
+  decode_laplacian(...)            (u, grad u, lap u) from dx such passes along the unit vectors (Cartesian coordinates only)
+  decode_hessian(...)              (u, grad u, hess u) from dx (dx + 1) / 2 passes, by polarisation
+  decode_diffusion_residual(...)   (u, u_t - nu lap u) for latents that follow the latent ODE
   divergence / curl_2d / gradient_norm   operators on a Jacobian whose components are CARTESIAN
 
 The Jacobian is w.r.t. the coordinates as the model takes them.  For the planar invariants these are Cartesian and the operators
@@ -16,7 +21,7 @@ the metric factors, which are not applied here.
 import torch
 
 __all__ = ["decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative", "divergence",
-           "curl_2d", "gradient_norm"]
+           "curl_2d", "gradient_norm", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual"]
 
 
 def decode_jacobian(nef, nef_params, coords, p, a, window, chunk=None):
@@ -94,6 +99,93 @@ def decode_material_derivative(nef, nef_params, ode_model, ode_params, coords, p
     if dw is not None:
         dw = dw.reshape(p.shape[0], p.shape[1], 1)
     return _tangent_x(nef, nef_params, coords, p, a, window, dp, da, dw, velocity, chunk)
+
+
+def _second_x(nef, nef_params, coords, p, a, window, direction, chunk, return_out=True):
+    """(out or None, tan, tan2) of nef.second_derivative on the full grid; the chunks slice ``direction`` with the grid."""
+    B = p.shape[0]
+    x = coords[None].expand(B, -1, -1) if coords.dim() == 2 else coords
+    xd = direction[None].expand(B, -1, -1) if direction.dim() == 2 else direction
+    if tuple(xd.shape) != tuple(x.shape):
+        raise ValueError(f"the direction has shape {tuple(direction.shape)}, expected (N, dx) or (B, N, dx) of the grid {tuple(x.shape)}")
+    if chunk is None:
+        return nef.second_derivative(nef_params, x, p, a, window, xd, return_out=return_out)
+    parts = [nef.second_derivative(nef_params, x[:, i:i + chunk], p, a, window, xd[:, i:i + chunk], return_out=return_out)
+             for i in range(0, x.shape[1], chunk)]
+    return tuple(None if parts[0][k] is None else torch.cat([q[k] for q in parts], dim=1) for k in range(3))
+
+
+def decode_second_directional(nef, nef_params, coords, p, a, window, direction, chunk=None):
+    """(u (B, N, O), c . grad u (B, N, O), c^T H c (B, N, O)) on the full grid along a direction field c = ``direction`` in the query
+    coordinates: the decode, its first and its second directional derivative, c^T H c = sum_ij c_i c_j d^2 u / d x_i d x_j, in one
+    second-order forward-mode pass (EquivariantCrossAttentionNeF.second_derivative) -- a curvature along a streamline, a second normal
+    derivative on a boundary.  ``direction``, ``coords`` and ``chunk`` as in decode_directional: coordinate rates, coordinates as the
+    model takes them; every query's result is the unchunked call's, bit for bit.  Second derivatives as autograd means them: almost
+    everywhere, the relu kinks contribute nothing."""
+    return _second_x(nef, nef_params, coords, p, a, window, direction, chunk)
+
+
+def _unit_passes(nef, nef_params, coords, p, a, window, chunk, pairs):
+    """u, the first and second derivatives along the unit vectors e_i (lists of dx tensors), and with ``pairs`` the second derivatives
+    along e_i + e_j, i < j (a dict): dx (+ dx (dx - 1) / 2) second-order passes, the decode stored by the first one only."""
+    N, dx = coords.shape[-2], coords.shape[-1]
+
+    def along(*axes):
+        e = torch.zeros((N, dx), device=coords.device, dtype=torch.float32)
+        e[:, list(axes)] = 1.0
+        return e
+    u, first, second, mixed = None, [], [], {}
+    for i in range(dx):
+        o, t, t2 = _second_x(nef, nef_params, coords, p, a, window, along(i), chunk, return_out=i == 0)
+        u = o if i == 0 else u
+        first.append(t)
+        second.append(t2)
+    if pairs:
+        for i in range(dx):
+            for j in range(i + 1, dx):
+                mixed[(i, j)] = _second_x(nef, nef_params, coords, p, a, window, along(i, j), chunk, return_out=False)[2]
+    return u, first, second, mixed
+
+
+def decode_laplacian(nef, nef_params, coords, p, a, window, chunk=None):
+    """(u (B, N, O), grad (B, N, O, dx), lap (B, N, O)) on the full grid: the decode, its gradient and its Laplacian
+    lap = sum_i d^2 u / d x_i^2, from dx second-order forward-mode passes along the unit vectors (each returns a column of the gradient
+    for free).  CARTESIAN coordinates only: for latitude_periodic / polar_periodic the coordinates are angles, a sum of second angle
+    derivatives is not a physical operator and the call raises ValueError (metric-aware operators are not provided; decode_hessian
+    gives the second derivatives in the coordinates as given).  ``coords`` and ``chunk`` as in decode_jacobian."""
+    name = getattr(getattr(nef, "cross_attn_invariant", None), "name", None)
+    if name in ("latitude_periodic", "polar_periodic"):
+        raise ValueError(f"decode_laplacian: the coordinates of '{name}' are angles; a sum of second angle derivatives is not the "
+                         "Laplacian on the sphere (metric-aware operators are out of scope: see decode_hessian)")
+    u, first, second, _ = _unit_passes(nef, nef_params, coords, p, a, window, chunk, pairs=False)
+    lap = second[0]
+    for t2 in second[1:]:
+        lap = lap + t2
+    return u, torch.stack(first, dim=-1), lap
+
+
+def decode_hessian(nef, nef_params, coords, p, a, window, chunk=None):
+    """(u (B, N, O), grad (B, N, O, dx), hess (B, N, O, dx, dx)) on the full grid: hess[..., i, j] = d^2 u / d x_i d x_j in the
+    coordinates as the model takes them (angles on the sphere, no metric factors), from dx second-order passes along the unit vectors
+    and one per pair i < j along e_i + e_j, by polarisation: H_ij = (D2(e_i + e_j) - D2 e_i - D2 e_j) / 2.  Both triangles hold the
+    same values: the result is symmetric bit for bit.  ``coords`` and ``chunk`` as in decode_jacobian."""
+    u, first, second, mixed = _unit_passes(nef, nef_params, coords, p, a, window, chunk, pairs=True)
+    dx = len(first)
+    rows = [[None] * dx for _ in range(dx)]
+    for i in range(dx):
+        rows[i][i] = second[i]
+        for j in range(i + 1, dx):
+            rows[i][j] = rows[j][i] = (mixed[(i, j)] - second[i] - second[j]) * 0.5
+    return u, torch.stack(first, dim=-1), torch.stack([torch.stack(r, dim=-1) for r in rows], dim=-2)
+
+
+def decode_diffusion_residual(nef, nef_params, ode_model, ode_params, coords, p, a, window, diffusivity, chunk=None):
+    """(u (B, N, O), u_t - nu lap u (B, N, O)) on the full grid: the residual of the diffusion equation u_t = nu lap u for latents that
+    follow the latent ODE -- u_t from decode_tendency (one first-order pass), lap u from decode_laplacian (dx second-order passes).
+    ``diffusivity`` nu: a number, or a tensor that broadcasts against (B, N, O).  Cartesian coordinates, as decode_laplacian."""
+    u, lap = decode_laplacian(nef, nef_params, coords, p, a, window, chunk=chunk)[::2]
+    ut = decode_tendency(nef, nef_params, ode_model, ode_params, coords, p, a, window, chunk=chunk)[1]
+    return u, ut - diffusivity * lap
 
 
 def _check(jac, what):

@@ -553,6 +553,35 @@ int enf_field_tangent_x(const EnfDesc* d, const float* x, int64_t x_bstride, con
                         const float* dsigma, const void* blob, float* out /* (B,N,O) or NULL */, float* tan /* (B,N,O), OVERWRITTEN */,
                         void* workspace, void* stream);
 
+/* Second directional derivatives (enf_field_second_x): the decode in forward mode to SECOND order along a direction in the query
+ * coordinates,
+ *     tan2[b,n,o] = sum_ij  xdot[b,n,i] xdot[b,n,j]  d^2 out[b,n,o] / d x[b,n,i] d x[b,n,j]        (B, N, O) fp32, required, OVERWRITTEN
+ *     tan[b,n,o]  = sum_i   d out[b,n,o] / d x[b,n,i]  xdot[b,n,i]                                 (B, N, O) fp32 or NULL
+ * tan is enf_field_tangent_x's value along xdot alone; `out` (B, N, O) is the decode itself, or NULL.  With xdot = e_i tan2 is a
+ * diagonal entry of the Hessian (dx passes sum to the Laplacian), with e_i + e_j an off-diagonal one by polarisation
+ * (H_ij = (D2(e_i + e_j) - D2 e_i - D2 e_j) / 2): the diffusion term of a PDE residual next to enf_field_tangent's u_t.  "Second
+ * derivative" as autograd means it: almost everywhere, the relu kinks contribute nothing.  xdot is (B, N, dx) fp32, required, with a batch
+ * stride of its own (xdot_bstride, in elements; 0 = one direction field for all signals), read at the rows x is read at and never
+ * written.  Coordinates AS GIVEN, the convention of enf_field_grad: angles on the sphere, no metric factors -- a sum of second angle
+ * derivatives is not the Laplace-Beltrami operator.  The direction is in the query coordinates only: the latents have no tangent here.
+ * Sequence: latent prologue (no prologue tangent, no tangent table); the second-order pair kernel (the tangent pair kernel's latent-split
+ * layout, heads over grid.z; every weight stage multiplies the primal, the first-order and the second-order fragments; softmax sums
+ * U = sum e (d2y + 2 dl dy + (d2l + dl^2) y), R = sum e (d2l + dl^2) beside Y, C, L, T, S); the second-order tail.  In bf16 mode the
+ * first- and second-order fragments are rounded to bf16 exactly where the primal ones are.
+ * Every element of tan2, tan and out is written once, by one lane, with no atomics and a fixed order of operations: bit-reproducible
+ * run to run and independent of what the workspace held.  Caller-owned buffers, the caller's stream, no allocation, no host
+ * synchronisation, no settings.  `workspace`: enf_field_second_workspace_bytes(d) bytes -- enf_field_tangent_workspace_bytes' regions at
+ * their offsets followed by d2 ybar, so one buffer of this size also serves the plain and the tangent calls on the same descriptor;
+ * contents need not be kept.  The size query returns 0 for a bad or unserved descriptor.
+ * Served: what enf_field_tangent_x serves.  Errors in this order: the descriptor's; ENF_EUNSUPPORTED for ENF_EMB_FFN, ball, ball_lat,
+ * ponita_full and mask_mode != ENF_MASK_OFF; ENF_EINVAL for a NULL x, xdot, p, a, blob, tan2, workspace, or sigma with a window.
+ * (DESIGN.md 7 has accuracy and times.) */
+size_t enf_field_second_workspace_bytes(const EnfDesc* d);
+int enf_field_second_x(const EnfDesc* d, const float* x, int64_t x_bstride, const float* xdot /* (B,N,dx), required */,
+                       int64_t xdot_bstride, const float* p, const float* a, const float* sigma, const void* blob,
+                       float* out /* (B,N,O) or NULL */, float* tan /* (B,N,O) or NULL */, float* tan2 /* (B,N,O), OVERWRITTEN */,
+                       void* workspace, void* stream);
+
 /* Gauss-Newton product (enf_gn_product): the matrix-vector product of a Gauss-Newton / Levenberg-Marquardt fit of the latents in one
  * call,
  *     gv = grad_scale * 2 / (B N O) * sum_{n,o} J[b,n,o,:]^T  w[b,n,o]  (J v)[b,n,o]

@@ -180,8 +180,35 @@ def tangent(lib):
     print(fx.__name__, *row)
 
 
+def second(lib):
+    """enf_field_second_x: its size query beside the tangent's over the same grid, and the calls it refuses before a launch (it takes no
+    workspace size: every call here has a reason to be refused)."""
+    for name, B, N, Z, C, O, dx, inv in SHAPES:
+        for D, H in WIDTHS:
+            for prec in (0, 1):
+                for emb in (0, 1):
+                    d = _lib.make_desc(B, N, Z, H, D, C, O, dx, _lib.INVARIANT_IDS[inv], 1, prec, embedding=emb)
+                    print("second", name, f"D{D} H{H} prec{prec} emb{emb}", lib.enf_field_second_workspace_bytes(ctypes.byref(d)))
+    valid = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, 0, 1, 1)
+    bad_dim = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 3, 0, 1, 1)
+    ffn = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, 0, 1, 1, embedding=1)
+    ball = _lib.make_desc(2, 100, 25, 2, 64, 8, 2, 2, _lib.INVARIANT_IDS["ball"], 1, 1)
+    P = 4096
+    # (x, x_bstride, xdot, xdot_bstride, p, a, sigma, blob, out, tan, tan2, workspace, stream)
+    f2 = lib.enf_field_second_x
+    full = [P, 0, P, 0, P, P, P, P, P, P, P, P, None]
+    row = []
+    for desc in (bad_dim, ffn, ball):               # descriptor / unsupported before a NULL pointer
+        row.append(f2(ctypes.byref(desc), *[None if i == 0 else v for i, v in enumerate(full)]))
+    for i in (0, 2, 4, 5, 7, 10, 11):               # each required pointer NULL in turn
+        row.append((i, f2(ctypes.byref(valid), *[None if j == i else v for j, v in enumerate(full)])))
+    row.append(f2(ctypes.byref(valid), *[None if j == 6 else v for j, v in enumerate(full)]))               # window without sigma
+    print(f2.__name__, *row)
+
+
 if __name__ == "__main__":
     lib = _lib.load()
     sizes(lib)
     errors(lib)
     tangent(lib)
+    second(lib)
