@@ -26,6 +26,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_w", "enf_mse_value_grad_w", "enf_fit_inputs_w", "enf_fit_inputs_b",
            "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum", "enf_fit_step_g", "enf_eval_loss_g",
+           "enf_fit_step_gs", "enf_mse_value_grad_g", "enf_fit_inputs_g",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
            "enf_field_second_workspace_bytes", "enf_field_second_x",
@@ -251,6 +252,12 @@ def _bind(path, hooks):
     lib.enf_signal_sum.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, vp, vp]
     lib.enf_fit_step_g.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_float] + [vp] * 7 + [sz, cu, vp]
     lib.enf_eval_loss_g.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, ctypes.c_int32] + [vp] * 6 + [sz, cu, vp]
+    # grouped observations in the trainers: the fit step that may carry ENF_FIT_SHARED_LATENTS (enf_fit_step_g's arguments); the unfused
+    # loss out, target | B, N, O, G | qweight, oweight | grad_scale | dout, loss, err_g, scratch | bytes, flags, stream; the gather of
+    # sampled cells: B, Z, M, Ms, S1, G, dx, O | xq, q, obs, masks, xs, qs, ys, losses, oweight, ws | per_signal_masks, stream
+    lib.enf_fit_step_gs.argtypes = list(lib.enf_fit_step_g.argtypes)
+    lib.enf_mse_value_grad_g.argtypes = [vp, vp] + [ctypes.c_int32] * 4 + [vp, vp, ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
+    lib.enf_fit_inputs_g.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 8 + [vp] * 10 + [ctypes.c_int32, vp]
     # derivative fields (include/enf_hip.h, "Derivative fields"): out (B, N, O) | NULL, jac (O, B, N, dx); dout (B, N, O), dx (B, N, dx)
     lib.enf_field_grad_workspace_bytes.restype = sz
     lib.enf_field_grad_workspace_bytes.argtypes = [dp, cu]

@@ -314,7 +314,7 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
                                 shared ? c.F(W.dybar) : nullptr)))
     return rc;
   // the shared-latent backward (enf_layout.h: enf_shared_backward_rule): tail, loss and backward pair kernel run ONCE, on signal 0
-  const bool sbwd = enf_shared_backward_rule(m, flags, per_value, err != nullptr) == 1;
+  const bool sbwd = enf_shared_backward_rule(m, flags, per_value, err != nullptr || (grp && grp->err_g)) == 1;
   EnfDims m1 = m;
   if (sbwd) m1.B = 1;
   // what the backward pair kernel needs from the latent table alone runs on the side stream beside the tail
@@ -330,7 +330,10 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
     float* dout = c.F(W.dybar) + (size_t)m.N * m.HD;
     float* out1 = dout + (size_t)m.B * m.N;
     if ((rc = enf_launch_tail_fwd_seed(m1, c.L, c.blob, c.F(W.ybar), out1, 0, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
-    if ((rc = enf_launch_mse_shared(out1, target, weight, m.B, m.N, grad_scale, dout, loss, st))) return rc;
+    // (grouped: the one row's group sums with signal 0's factors against all B signals' observations and observation weights)
+    if (grp) rc = enf_launch_mse_group_shared(out1, target, grp->qweight, grp->oweight, m.B, m.N, grp->G, grad_scale, dout, loss, st);
+    else rc = enf_launch_mse_shared(out1, target, weight, m.B, m.N, grad_scale, dout, loss, st);
+    if (rc) return rc;
     if ((rc = enf_side_join_pending(st, workspace))) return rc;
     if ((rc = enf_launch_pair_bwd_shared(m, c.L, c.blob, x, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), dout, c.F(W.dlt),
                                          c.fold_bwd(), st)))
@@ -430,6 +433,18 @@ extern "C" int enf_fit_step_g(const EnfDesc* d, const float* x, int64_t x_bstrid
   const EnfGroupObs g{G, qweight, oweight, err_g};
   return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
                            false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && !(flags & ENF_FIT_SHARED_LATENTS) && !(loss_b && !err_g), &g);
+}
+
+// enf_fit_step_g that may carry ENF_FIT_SHARED_LATENTS (the first inner step of a fit on cells): the flag clear, the call above; set,
+// the one shared forward and -- where enf_shared_backward_rule holds and err_g is NULL -- the one shared backward, its d out (B, N) from
+// the grouped SHARED loss kernel; elsewhere the ordinary grouped tail behind the shared forward.
+extern "C" int enf_fit_step_gs(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, int32_t G, const float* qweight, const float* oweight, float grad_scale,
+                               float* loss, float* dp, float* da, float* dsigma, float* err_g, float* loss_b, void* workspace,
+                               size_t workspace_bytes, unsigned flags, void* stream) {
+  const EnfGroupObs g{G, qweight, oweight, err_g};
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
+                           false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && !(loss_b && !err_g), &g);
 }
 
 extern "C" int enf_eval_loss_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,

@@ -225,5 +225,9 @@ int enf_launch_tail_group(const EnfDims& m, const EnfLayout& L, const char* blob
 // weight may be NULL): *loss += the mean squared error, dout (B, N) = its gradient times gscale -- enf_mse_kernel's arithmetic
 int enf_launch_mse_shared(const float* out1, const float* target, const float* weight, int B, int N, float gscale, float* dout,
                           float* loss, hipStream_t st);
+// its grouped form (enf_fit_step_gs): the one row against all B signals' observations target (B, N / G) and weights oweight (B, N / G) or
+// NULL, with signal 0's factors q0 (N) or NULL (1 / G); dout (B, N) -- enf_mse_group_kernel's arithmetic
+int enf_launch_mse_group_shared(const float* out1, const float* target, const float* q0, const float* oweight, int B, int N, int G,
+                                float gscale, float* dout, float* loss, hipStream_t st);
 // loss_b[b] = scale * (err[b, 0] + ... + err[b, N - 1]): one workgroup per signal, fixed order, no atomics (enf_loss.hip)
 int enf_launch_signal_sum(const float* err, int B, int N, float scale, float* loss_b, hipStream_t st);

@@ -143,6 +143,95 @@ extern "C" int enf_mse_value_grad(const float* out, const float* target, size_t 
   return enf_mse_value_grad_ex(out, target, n, grad_scale, dout, loss, nullptr, 0, 0u, stream);
 }
 
+// The grouped form of enf_mse_kernel (include/enf_hip.h, "Grouped observations": enf_mse_value_grad_g): the loss of a decode `out`
+// (B, N, O) that exists in memory against observations (B, M, O), M = N / G.  One thread owns one (group, channel) i = (b M + m) O + o:
+// it forms obs = sum_k q out over the group's G consecutive rows, dd = obs - target under the select on w, its share w dd^2 of the loss,
+// and stores the G values d out = (q (w dd)) gs, gs = 2 inv_n gscale -- the operations of the fused tail's tail_sq_err_g in its order.
+// The group sum is the tail's xor tree written over registers: products first, then pairs at distance 1, 2, 4, 8 (rows beyond G are
+// zeros, and x + 0 is x).  Contraction is off, so the sum's bits do not depend on what the compiler fuses.
+// err_g (B, M): the thread of channel 0 adds its group's O shares in channel order with the products the other channels' threads form
+// (it recomputes their sums): one plain store per observation, no atomics.
+// SHARED (the shared-latent backward, enf_layout.h: enf_shared_backward_rule; O == 1): `out` is the ONE row of N values every signal
+// decodes to and q (N, or NULL) are signal 0's factors; target, w and d out stay per signal.
+__device__ __forceinline__ float mse_group_sum(const float* __restrict__ out, const float* __restrict__ q, size_t orow, size_t qrow, int O,
+                                               int o, int G) {
+#pragma clang fp contract(off)
+  float v[16];
+  const float qd = 1.0f / (float)G;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) v[k] = k < G ? (q ? q[qrow + k] : qd) * out[(orow + k) * (size_t)O + o] : 0.f;
+#pragma unroll
+  for (int d = 1; d < 16; d <<= 1)
+#pragma unroll
+    for (int k = 0; k < 16; k += 2 * d) v[k] += v[k + d];
+  return v[0];
+}
+
+template <bool SHARED>
+__global__ __launch_bounds__(256) void enf_mse_group_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                            const float* __restrict__ qweight, const float* __restrict__ oweight, size_t n,
+                                                            int M, int O, int G, float inv_n, float gscale, float* __restrict__ dout,
+                                                            float* __restrict__ err_g, float* loss, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  const float gs = 2.0f * inv_n * gscale;
+  float s = 0.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t bm = i / (size_t)O;                     // the observation, b M + m
+    const int o = (int)(i - bm * (size_t)O);
+    const size_t row = bm * (size_t)G;                   // its first query row, b N + m G
+    const size_t orow = SHARED ? row % ((size_t)M * G) : row;     // the row of `out` (and of q) it reads
+    const float w = oweight ? oweight[bm] : 1.f;
+    const bool live = w > 0.f;
+    const float dd = live ? mse_group_sum(out, qweight, orow, orow, O, o, G) - target[i] : 0.f;
+    const float wd = w * dd;
+    s = fmaf(wd, dd, s);
+    if (dout) {
+      const float qd = 1.0f / (float)G;
+      for (int k = 0; k < G; ++k) dout[(row + k) * (size_t)O + o] = ((qweight ? qweight[orow + k] : qd) * wd) * gs;
+    }
+    if (err_g && o == 0) {
+      float e = fmaf(wd, dd, 0.f);
+      for (int c = 1; c < O; ++c) {
+        const float dc = live ? mse_group_sum(out, qweight, orow, orow, O, c, G) - target[i + c] : 0.f;
+        e = fmaf(w * dc, dc, e);
+      }
+      err_g[bm] = e;
+    }
+  }
+  mse_block_sum(s, inv_n, loss, part);
+}
+
+// Every grouped MSE launch: n = B M O threads' worth of (group, channel) pairs on the grid of mse_launch, the deterministic sum behind it.
+static int mse_group_launch(bool shared, const float* out, const float* target, const float* qweight, const float* oweight, int B, int N,
+                            int O, int G, float grad_scale, float* dout, float* err_g, float* loss, void* scratch, size_t scratch_bytes,
+                            unsigned flags, hipStream_t st) {
+  if (!out || !target || !loss || B < 1 || N < 1 || O < 1 || !enf_group_size_ok(G) || N % G || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
+  const int M = N / G;
+  const size_t n = (size_t)B * (size_t)M * (size_t)O;
+  const bool det = (flags & ENF_MSE_DETERMINISTIC) != 0;
+  if (det && !scratch) return ENF_EINVAL;
+  if (det && scratch_bytes < enf_mse_scratch_bytes(n, flags)) return ENF_EWORKSPACE;
+  const size_t blocks = mse_blocks(n);
+  float* part = det ? (float*)scratch : nullptr;
+  const float inv_n = 1.0f / ((float)B * (float)M * (float)O);      // the fused tail's (enf_tail.hip: tail_loss_kernel)
+  hipLaunchKernelGGL(shared ? enf_mse_group_kernel<true> : enf_mse_group_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, out, target,
+                     qweight, oweight, n, M, O, G, inv_n, grad_scale, dout, err_g, loss, part);
+  if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
+  return det ? enf_launch_loss_sum(part, (int)blocks, loss, st) : ENF_OK;
+}
+
+int enf_launch_mse_group_shared(const float* out1, const float* target, const float* q0, const float* oweight, int B, int N, int G,
+                                float gscale, float* dout, float* loss, hipStream_t st) {
+  return mse_group_launch(true, out1, target, q0, oweight, B, N, 1, G, gscale, dout, nullptr, loss, nullptr, 0, 0u, st);
+}
+
+extern "C" int enf_mse_value_grad_g(const float* out, const float* target, int32_t B, int32_t N, int32_t O, int32_t G, const float* qweight,
+                                    const float* oweight, float grad_scale, float* dout, float* loss, float* err_g, void* scratch,
+                                    size_t scratch_bytes, unsigned flags, void* stream) {
+  return mse_group_launch(false, out, target, qweight, oweight, B, N, O, G, grad_scale, dout, err_g, loss, scratch, scratch_bytes, flags,
+                          (hipStream_t)stream);
+}
+
 struct SgdArgs { EnfSgdSegment seg[ENF_SGD_MAX_SEGMENTS]; int nseg; float scale; };
 
 __global__ __launch_bounds__(256) void enf_meta_sgd_kernel(SgdArgs A) {
@@ -270,6 +359,65 @@ __global__ __launch_bounds__(256) void enf_fit_inputs_rows_kernel(FitInArgs A, u
     return;
   }
   fit_broadcast_then(A, i - nrow, [&](int64_t j) { if (j < A.S1) A.losses[j] = 0.f; });
+}
+
+// Sampled CELLS (enf_fit_inputs_g; include/enf_hip.h, "Grouped observations"): A.N = M cells, A.Ns = Ms sampled ones, A.coords = the
+// cells' quadrature points (M G, dx), A.img = the observations (B, M, O), A.weight = the observation weights (B, M) or NULL.  One thread
+// per (s, b, i) OBSERVATION of the outputs, as in enf_fit_inputs_rows_kernel: it reads its cell index once, copies the O targets and the
+// weight, and -- with per-signal masks every thread, with shared masks the threads of signal 0 -- the cell's G rows of points and
+// factors: row i G + k of the set is row m G + k of cell m.  An index outside [0, M) is never used as an offset: its rows are cell 0's
+// (finite: q is a factor, not a select), its targets zeros and its weight 0.  A.ws NULL (shared masks without weights): not written.
+// All offsets are 64-bit.
+__global__ __launch_bounds__(256) void enf_fit_inputs_cells_kernel(FitInArgs A, int G, const float* __restrict__ q, float* __restrict__ qs,
+                                                                   bool per_signal) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nrow = (int64_t)A.S1 * A.B * A.Ns;
+  if (i < nrow) {
+    const int64_t c = i % A.Ns, r = i / A.Ns, b = r % A.B, s = r / A.B;
+    const int64_t m = A.masks[per_signal ? (b * A.Ns + c) * A.S1 + s : c * A.S1 + s];
+    const bool ok = m >= 0 && m < (int64_t)A.N;
+    if (per_signal || b == 0) {
+      const int64_t src = (ok ? m : (int64_t)0) * G, dst = (per_signal ? i : s * A.Ns + c) * G;
+      const int nx = G * A.dx;
+      for (int k = 0; k < nx; ++k) A.xs[dst * A.dx + k] = A.coords[src * A.dx + k];
+      if (q)
+        for (int k = 0; k < G; ++k) qs[dst + k] = q[src + k];
+    }
+    float* __restrict__ y = A.ys + i * A.O;
+    if (ok) {
+      const float* __restrict__ im = A.img + (b * A.N + m) * A.O;
+      for (int o = 0; o < A.O; ++o) y[o] = im[o];
+    } else {
+      for (int o = 0; o < A.O; ++o) y[o] = 0.f;
+    }
+    if (A.ws) A.ws[i] = ok ? (A.weight ? A.weight[b * A.N + m] : 1.0f) : 0.f;
+    return;
+  }
+  fit_broadcast_then(A, i - nrow, [&](int64_t j) { if (j < A.S1) A.losses[j] = 0.f; });
+}
+
+extern "C" int enf_fit_inputs_g(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1, int32_t G,
+                                int32_t dx, int32_t O, const float* xq, const float* q, const float* obs, const int64_t* masks, float* xs,
+                                float* qs, float* ys, float* losses, const float* oweight, float* ws, int32_t per_signal_masks, void* stream) {
+  const bool per_signal = per_signal_masks != 0;
+  if (ncomp < 1 || ncomp > ENF_SGD_MAX_SEGMENTS || !comps || !xq || !obs || !masks || !xs || !ys || !losses) return ENF_EINVAL;
+  if (B < 1 || Z < 1 || M < 1 || Ms < 1 || S1 < 1 || dx < 1 || O < 1 || !enf_group_size_ok(G)) return ENF_EINVAL;
+  if ((q == nullptr) != (qs == nullptr)) return ENF_EINVAL;
+  // ws is what says that an index outside [0, M) does not exist: required with per-signal masks (1 / 0 without oweight)
+  if (per_signal ? ws == nullptr : (oweight == nullptr) != (ws == nullptr)) return ENF_EINVAL;
+  FitInArgs A{};
+  int64_t total = (int64_t)S1 * B * Ms + S1;
+  for (int k = 0; k < ncomp; ++k) {
+    if (!comps[k].src || !comps[k].dst || comps[k].width < 1) return ENF_EINVAL;
+    A.comp[k] = comps[k];
+    total += (int64_t)B * Z * comps[k].width;
+  }
+  if ((total + 255) / 256 > (int64_t)INT_MAX) return ENF_EDIM;
+  A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = M; A.Ns = Ms; A.S1 = S1; A.dx = dx; A.O = O;
+  A.coords = xq; A.img = obs; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = oweight; A.ws = ws;
+  hipLaunchKernelGGL(enf_fit_inputs_cells_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A, (int)G, q, qs,
+                     per_signal);
+  return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
 // Every enf_fit_inputs* call: validation (`args_ok` is the entry point's own condition on weight / ws), FitInArgs, grid and launch.

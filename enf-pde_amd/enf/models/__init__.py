@@ -907,7 +907,7 @@ class EquivariantCrossAttentionNeF:
 
     @torch.no_grad()
     def mse_value_and_cell_grads(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None,
-                                 grad_scale=1.0, loss_out=None, return_errors=False):
+                                 grad_scale=1.0, loss_out=None, return_errors=False, shared_latents=False):
         """The fit step against GROUPED observations (include/enf_hip.h, "Grouped observations": enf_fit_step_g): observation m of a
         signal is obs[m] = sum_k qweight[m group + k] out[m group + k] over the ``group`` consecutive query rows it owns -- a quadrature
         rule over a cell (fitting/cells.py: cell_quadrature) -- and
@@ -917,6 +917,10 @@ class EquivariantCrossAttentionNeF:
         The group sum, the loss and d out are formed in the fused tail's registers: no ``out`` in memory, no autograd graph.
         ``loss_out``: an already ZEROED float32 (1,) tensor the loss is added to.  ``return_errors``: also err_g (B, M) =
         obs_weight sum_o (obs - target)^2 and loss_b (B,) = err_g.sum(1) / (M O).
+        ``shared_latents``: the caller's statement that every signal holds the same latents, that ``x`` is one set of cells expanded
+        over the signals with stride 0 and that the rows of ``qweight`` are equal -- the first inner step of a fit on shared cells.  The
+        call then goes to enf_fit_step_gs with ENF_FIT_SHARED_LATENTS: one forward for all signals and, where the library's rule holds,
+        one backward.  Without it the call is enf_fit_step_g, as before.
         Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err_g, loss_b)."""
         B, Z, N, M = self._cell_args("mse_value_and_cell_grads", x, p, a, target, group, qweight, obs_weight)
         sigma = gaussian_window_size if self.use_gaussian_window else None
@@ -936,9 +940,10 @@ class EquivariantCrossAttentionNeF:
         dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
         err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
         loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
-        _lib.launch(dev, lib.enf_fit_step_g, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+        fn, flags = (lib.enf_fit_step_gs, self._det_flag() | _lib.ENF_FIT_SHARED_LATENTS) if shared_latents else (lib.enf_fit_step_g, self._det_flag())
+        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
                     int(group), _ptr(q_), _ptr(w_), float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(err), _ptr(loss_b),
-                    _ptr(ws), ws.numel(), self._det_flag(), st)
+                    _ptr(ws), ws.numel(), flags, st)
         self._ws_touch(ws)
         res = (loss, dp, da, dsig if sigma is not None else None)
         return res + (err, loss_b) if return_errors else res
@@ -969,3 +974,57 @@ class EquivariantCrossAttentionNeF:
                     int(group), _ptr(q_), _ptr(w_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
         self._ws_touch(ws)
         return loss_b, err
+
+    def cell_mse(self, out, target, group, qweight=None, obs_weight=None):
+        """The grouped loss of a decode that exists in memory (include/enf_hip.h: enf_mse_value_grad_g), for the weight-gradient path:
+            loss = sum_{b,m} obs_weight[b,m] sum_o (obs - target)^2 / (B M O),    obs[b,m] = sum_k qweight[b, m group + k] out[b, m group + k]
+        with out (B, N, O), target (B, M, O), M = N / group; ``qweight`` (B, N) or None for 1 / group, ``obs_weight`` (B, M) or None for 1
+        (an observation of weight 0 does not exist, its target may be NaN).  A torch.autograd.Function: loss and d out come from ONE
+        kernel, the backward multiplies d out by the incoming scalar.  Differentiable once, and only with respect to ``out``.
+        Returns the loss, a 0-d tensor."""
+        if int(group) not in self.GROUP_SIZES:
+            raise ValueError(f"group must be one of {self.GROUP_SIZES}, got {group}")
+        if out.dim() != 3 or out.shape[1] % int(group):
+            raise ValueError(f"out must be (B, M * group, O), got {tuple(out.shape)} with group = {group}")
+        B, N, O = out.shape
+        M = N // int(group)
+        if tuple(target.shape) != (B, M, O):
+            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, O)}")
+        if qweight is not None and tuple(qweight.shape) != (B, N):
+            raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
+        if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
+            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
+        if not (out.is_cuda and target.is_cuda):
+            raise _lib.EnfError("EquivariantCrossAttentionNeF.cell_mse needs CUDA/HIP tensors: there is no CPU path")
+        return _CellMseFunction.apply(out, target, int(group), qweight, obs_weight, self._det_flag())
+
+
+class _CellMseFunction(torch.autograd.Function):
+    """nef.cell_mse: enf_mse_value_grad_g once in the forward (loss and d out at grad_scale 1); the backward scales the stored d out."""
+
+    @staticmethod
+    def forward(ctx, out, target, group, qweight, obs_weight, det):
+        lib = _lib.load()
+        dev = out.device
+        o_ = out.detach().float().contiguous()
+        B, N, O = o_.shape
+        t_ = target.detach().float().contiguous()
+        q_ = qweight.detach().float().contiguous() if qweight is not None else None
+        w_ = obs_weight.detach().float().contiguous() if obs_weight is not None else None
+        need = ctx.needs_input_grad[0]
+        dout = torch.empty_like(o_) if need else None
+        loss = torch.zeros(1, device=dev, dtype=torch.float32)
+        nscr = int(lib.enf_mse_scratch_bytes(B * (N // group) * O, det))
+        scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr else None
+        _lib.launch(dev, lib.enf_mse_value_grad_g, _ptr(o_), _ptr(t_), B, N, O, group, _ptr(q_), _ptr(w_), 1.0, _ptr(dout), _ptr(loss), None,
+                    _ptr(scr), nscr, det, _lib.stream(dev))
+        if need:
+            ctx.save_for_backward(dout)
+        ctx.out_dtype = out.dtype
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (dout,) = ctx.saved_tensors
+        return (dout * g).to(ctx.out_dtype), None, None, None, None, None

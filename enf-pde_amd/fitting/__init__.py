@@ -10,6 +10,7 @@
   decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual  (no counterpart)   second derivatives in forward mode: c^T H c, the Laplacian, the Hessian, u_t - nu Lap u
   cg_solve, lm_fit_latents  (no counterpart)                   batched CG on the native Gauss-Newton product; Levenberg-Marquardt latent fits
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
+  inner_loop_cells, gather_cell_samples, cell_mse_torch  (no counterpart)   the inner loop on sampled cells (the trainers' cells=) and the torch-op mirrors of its kernels
   shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
   ode_models           ode_models/ponita_ode_g.py, mlp_ode.py  PonitaODEGen (fused SepGconv HIP kernels), MLPODE
@@ -23,6 +24,7 @@ from .derivatives import decode_jacobian, decode_tangent, decode_tendency, decod
 from .derivatives import decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual
 from .gauss_newton import cg_solve, lm_fit_latents
 from .cells import cell_quadrature, decode_cell_averages, fit_cell_averages, draw_cell_samples
+from .cells import inner_loop_cells, gather_cell_samples, cell_mse_torch
 from .parallel import shard_range, allreduce_mean_, init_distributed
 from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState, draw_point_masks
 from .trainers.trainer_utils import solve_latent_ode
@@ -32,4 +34,4 @@ __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_m
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
            "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
-           "draw_cell_samples", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual"]
+           "draw_cell_samples", "inner_loop_cells", "gather_cell_samples", "cell_mse_torch", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual"]

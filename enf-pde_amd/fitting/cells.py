@@ -6,11 +6,14 @@ footprint's weighted mean.  Such an observation is a fixed linear functional of 
 a quadrature rule over G points of cell m.  ``cell_quadrature`` builds the points and factors, ``decode_cell_averages`` applies the
 functional to a decode in torch ops, and ``fit_cell_averages`` runs the inner loop's update rule on the fused grouped step
 (nef.mse_value_and_cell_grads: the group sums are formed in the tail's registers, no decode exists in memory).
-Nothing here is wired into ``inner_loop`` or the trainers."""
+``inner_loop_cells`` is inner_loop on sampled cells -- one gather launch (enf_fit_inputs_g), the shared-latent hint at step 0 -- and what
+the trainers run with ``cells=``; ``gather_cell_samples`` and ``cell_mse_torch`` are the torch-op mirrors of the gather kernel and of the
+unfused grouped loss (nef.cell_mse)."""
 import numpy as np
 import torch
 
-from .inner_loop import _pose, meta_sgd_update
+from .. import _lib
+from .inner_loop import FUSED_FIT_INPUTS, _pose, _shared_kw, meta_sgd_update, normalize_sampled_weights
 
 GROUP_SIZES = (1, 2, 4, 8, 16)
 
@@ -183,4 +186,159 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
         lat = meta_sgd_update(lat, grads, lrs, B)
     if per_signal_loss:
         return losses[S], lat, torch.stack(rows_b)
+    return losses[S], lat
+
+
+def gather_cell_samples(x, q, group, obs, masks, obs_weight=None):
+    """What enf_fit_inputs_g gathers, in torch ops: x (M G, dx) quadrature points, q (M G,) factors or None, obs (B, M, O), masks long
+    cell indices (Ms, S1) shared by the signals or (B, Ms, S1) per signal, obs_weight (B, M) or None
+    -> xs (S1, Ms G, dx) | (S1, B, Ms G, dx), qs alike without the last axis (None without q), ys (S1, B, Ms, O), ws (S1, B, Ms).
+    Row i G + k of a sampled set is row m G + k of cell m.  An index outside [0, M) gives cell 0's points and factors, zero targets and
+    weight 0; ws is None on shared masks without ``obs_weight`` and 1 / 0 on per-signal masks without it."""
+    G = int(group)
+    B, M, O = obs.shape
+    S1 = masks.shape[-1]
+    per_signal = masks.dim() == 3
+    idx = masks.permute(2, 0, 1) if per_signal else masks.t()                        # (S1, B, Ms) | (S1, Ms)
+    ok = (idx >= 0) & (idx < M)
+    ic = torch.where(ok, idx, torch.zeros_like(idx))
+    rows = (ic[..., None] * G + torch.arange(G, device=ic.device)).reshape(*ic.shape[:-1], -1)
+    xs = x[rows].contiguous()
+    qs = q[rows].contiguous() if q is not None else None
+    icb, okb = (ic, ok) if per_signal else (ic[:, None].expand(-1, B, -1), ok[:, None].expand(-1, B, -1))
+    ys = torch.gather(obs[None].expand(S1, -1, -1, -1), 2, icb[..., None].expand(-1, -1, -1, O)).float()
+    ys = torch.where(okb[..., None], ys, torch.zeros_like(ys)).contiguous()
+    if obs_weight is None and not per_signal:
+        return xs, qs, ys, None
+    w = torch.gather(obs_weight[None].expand(S1, -1, -1), 2, icb).float() if obs_weight is not None else \
+        torch.ones(icb.shape, device=obs.device, dtype=torch.float32)
+    return xs, qs, ys, torch.where(okb, w, torch.zeros_like(w)).contiguous()
+
+
+def cell_mse_torch(out, target, group, qweight=None, obs_weight=None):
+    """The grouped loss in torch ops, differentiable by autograd -- the mirror of nef.cell_mse (enf_mse_value_grad_g):
+    sum_{b,m} w[b,m] sum_o (obs - target)^2 / (B M O) with obs = sum_k q out over each group; w == 0 is a select, so that
+    observation's target may be NaN and its share of the loss and of d out is zero."""
+    G = int(group)
+    B, N, O = out.shape
+    M = N // G
+    q = torch.full((B, N), 1.0 / G, device=out.device, dtype=out.dtype) if qweight is None else qweight.to(out.dtype)
+    w = torch.ones((B, M), device=out.device, dtype=out.dtype) if obs_weight is None else obs_weight.to(out.dtype)
+    obs = (q[..., None] * out).reshape(B, M, G, O).sum(2)
+    live = (w > 0)[..., None]
+    dd = torch.where(live, obs - torch.where(live, target.to(out.dtype), torch.zeros_like(obs)), torch.zeros_like(obs))
+    return (w[..., None] * dd * dd).sum() / (B * M * O)
+
+
+def _cell_inputs(latents0, x, q, group, obs, masks, obs_weight):
+    """enf_fit_inputs_g (include/enf_hip.h): (lat, xs_all, qs_all, ys_all, losses, ws_all) of inner_loop_cells in one launch, or None
+    where the arguments are not what the kernel takes (fp32, contiguous, on one GPU, long masks, at most four latent components of
+    leading dimension 1)."""
+    ts = list(latents0.values()) + [x, obs] + [t for t in (q, obs_weight) if t is not None]
+    if not (obs.is_cuda and masks.is_cuda and masks.dtype == torch.int64 and masks.dim() in (2, 3) and masks.is_contiguous() and x.dim() == 2
+            and obs.dim() == 3 and 1 <= len(latents0) <= _lib.ENF_SGD_MAX_SEGMENTS and masks.shape[0] > 0
+            and all(t.dtype == torch.float32 and t.is_contiguous() and t.device == obs.device for t in ts)
+            and all(v.dim() == 3 and v.shape[0] == 1 for v in latents0.values())
+            and len({v.shape[1] for v in latents0.values()}) == 1):
+        return None
+    G = int(group)
+    B, M, O = obs.shape
+    Ms, S1 = masks.shape[-2:]
+    per_signal = masks.dim() == 3
+    if per_signal and masks.shape[0] != B:
+        return None
+    Z = next(iter(latents0.values())).shape[1]
+    dev, dx = obs.device, x.shape[1]
+    lead = (S1, B, Ms * G) if per_signal else (S1, Ms * G)
+    lat = {k: torch.empty((B, Z, v.shape[2]), device=dev, dtype=torch.float32) for k, v in latents0.items()}
+    xs = torch.empty(lead + (dx,), device=dev, dtype=torch.float32)
+    qs = torch.empty(lead, device=dev, dtype=torch.float32) if q is not None else None
+    ys = torch.empty((S1, B, Ms, O), device=dev, dtype=torch.float32)
+    ws = torch.empty((S1, B, Ms), device=dev, dtype=torch.float32) if obs_weight is not None or per_signal else None
+    losses = torch.empty(S1, device=dev, dtype=torch.float32)
+    comps = (_lib.EnfFitComponent * _lib.ENF_SGD_MAX_SEGMENTS)()
+    keep = []
+    for i, (k, v) in enumerate(latents0.items()):
+        src = v.detach()
+        keep.append(src)
+        comps[i] = _lib.EnfFitComponent(src.data_ptr(), lat[k].data_ptr(), v.shape[2], 0)
+    _lib.launch(dev, _lib.load().enf_fit_inputs_g, len(latents0), comps, B, Z, M, Ms, S1, G, dx, O, _lib.ptr(x), _lib.ptr(q), _lib.ptr(obs),
+                _lib.ptr(masks), _lib.ptr(xs), _lib.ptr(qs), _lib.ptr(ys), _lib.ptr(losses), _lib.ptr(obs_weight), _lib.ptr(ws),
+                1 if per_signal else 0, _lib.stream(dev))
+    return lat, xs, qs, ys, losses, ws
+
+
+def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks, obs_weights=None, optimize_gaussian_window=False,
+                     noise_pos=0.0, generator=None, normalize_weights=False, per_signal_loss=False):
+    """inner_loop on cell averages: fit per-signal latents with S steps of meta-SGD, every step against a sampled set of cells.
+
+    x, q     : the quadrature points (M G, dx) and factors (M G,) of the M cells (cell_quadrature), shared by the signals; q None is
+               the plain mean, 1 / group
+    targets  : (B, M, O) observed cell averages;  obs_weights: None or (B, M), finite and >= 0, taken as they are
+    masks    : long CELL indices, (Ms, S + 1) shared by the signals or (B, Ms, S + 1) per signal; with per-signal masks an index outside
+               [0, M) -- a sampler's padding -- has weight 0 and does not exist
+    The sampled points, factors, targets and weights of all steps, the signals' copies of the latent initialisation and the zeroed loss
+    accumulators come from ONE launch (enf_fit_inputs_g), or from gather_cell_samples where the tensors are not what the kernel takes.
+    Each step is one nef.mse_value_and_cell_grads -- step 0 with the shared-latent hint under the conditions of inner_loop (shared masks,
+    no pose noise, not deterministic, a decoder that knows the keyword) -- and the final loss is nef.eval_cell_loss, without a decode.
+    normalize_weights, noise_pos, optimize_gaussian_window, per_signal_loss and the return values are inner_loop's."""
+    G = int(group)
+    if G not in GROUP_SIZES:
+        raise ValueError(f"group must be one of {GROUP_SIZES}, got {group}")
+    B, M, O = targets.shape
+    if x.dim() != 2 or x.shape[0] != M * G:
+        raise ValueError(f"x must be (M * group, dx) = ({M * G}, dx), got {tuple(x.shape)}")
+    if q is not None and tuple(q.shape) != (M * G,):
+        raise ValueError(f"q has shape {tuple(q.shape)}, expected {(M * G,)}")
+    if obs_weights is not None and tuple(obs_weights.shape) != (B, M):
+        raise ValueError(f"obs_weights have shape {tuple(obs_weights.shape)}, expected {(B, M)}")
+    per_signal = masks.dim() == 3
+    if masks.dim() not in (2, 3) or (per_signal and masks.shape[0] != B):
+        raise ValueError(f"masks have shape {tuple(masks.shape)}, expected (Ms, S + 1) or ({B}, Ms, S + 1)")
+    S = masks.shape[-1] - 1
+    dev = targets.device
+    w_full = obs_weights.to(device=dev, dtype=torch.float32).contiguous() if obs_weights is not None else None
+    fused = _cell_inputs(latents0, x, q, G, targets, masks, w_full) if FUSED_FIT_INPUTS else None
+    if fused is not None:
+        lat, xs_all, qs_all, ys_all, losses, ws_all = fused
+    else:
+        lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
+        losses = torch.zeros(S + 1, device=dev, dtype=torch.float32)
+        xs_all, qs_all, ys_all, ws_all = gather_cell_samples(x.to(dev), None if q is None else q.to(dev), G, targets, masks.to(dev), w_full)
+    if normalize_weights:
+        if ws_all is None:
+            raise ValueError("normalize_weights needs sampled weights: pass obs_weights= or per-signal masks")
+        ws_all = normalize_sampled_weights(ws_all)
+    if noise_pos:
+        lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator, device="cpu").to(lat["p_pos"].device) * noise_pos
+    n_ori = nef.cross_attn_invariant.num_z_ori_dims
+    n_pos = lat["p_pos"].shape[-1]
+
+    def sampled(s):     # step s's cells -- every signal's own, or a stride-0 batch --, factors and weights
+        xs, qs = xs_all[s], None if qs_all is None else qs_all[s]
+        if not per_signal:
+            xs, qs = _batched(xs, qs, B)
+        return xs, qs, None if ws_all is None else ws_all[s]
+
+    rows = []
+    for s in range(S):
+        xs, qs, ws = sampled(s)
+        res = nef.mse_value_and_cell_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[s], G, qweight=qs,
+                                           obs_weight=ws, loss_out=losses[s:s + 1], **({"return_errors": True} if per_signal_loss else {}),
+                                           **_shared_kw(nef, s, per_signal, noise_pos, step="mse_value_and_cell_grads"))
+        _, dp, da, dsig = res[:4]
+        if per_signal_loss:
+            rows.append(res[5])
+        grads = {"p_pos": dp[..., :n_pos], "a": da}
+        if n_ori > 0:
+            grads["p_ori"] = dp[..., n_pos:]
+        if optimize_gaussian_window and dsig is not None:
+            grads["gaussian_window"] = dsig
+        lat = meta_sgd_update(lat, grads, lrs, B)
+    xs, qs, ws = sampled(S)
+    lb, _ = nef.eval_cell_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], G, qweight=qs, obs_weight=ws,
+                               loss_out=losses[S:], per_signal=per_signal_loss)
+    if per_signal_loss:
+        rows.append(lb)
+        return losses[S], lat, torch.stack(rows)
     return losses[S], lat

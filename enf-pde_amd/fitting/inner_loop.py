@@ -209,8 +209,9 @@ def _takes_shared_hint(fn):
     return any(q.name == "shared_latents" for q in params)
 
 
-def _shared_kw(nef, s, per_signal, noise_pos):
-    """The keyword of step ``s``'s mse_value_and_latent_grads: at step 0 every signal still holds the one latent initialisation, and with
+def _shared_kw(nef, s, per_signal, noise_pos, step="mse_value_and_latent_grads"):
+    """The keyword of step ``s``'s mse_value_and_latent_grads (or of ``step``, the grouped step of inner_loop_cells): at step 0 every
+    signal still holds the one latent initialisation, and with
     shared masks the same points (a stride-0 batch) -- unless the poses were jittered per signal -- so the step may run its forward pair
     kernel once for all signals (include/enf_hip.h: ENF_FIT_SHARED_LATENTS).  A decoder whose step does not know the hint is not given it,
     and neither is one in deterministic mode: the one forward adds a query's partial sums in another fp32 order, and that mode keeps a
@@ -220,7 +221,7 @@ def _shared_kw(nef, s, per_signal, noise_pos):
     det = getattr(nef, "is_deterministic", None)
     if det is not None and det():
         return {}
-    fn = nef.mse_value_and_latent_grads
+    fn = getattr(nef, step)
     return {"shared_latents": True} if _takes_shared_hint(getattr(fn, "__func__", fn)) else {}
 
 

@@ -31,6 +31,7 @@ from ..optim import Adam, AdamW, clip_by_global_norm, global_norm, scatter_rows,
 from ..parallel import allreduce_mean_
 from ..inner_loop import decode, make_signal_masks, gather_signal_points
 from ..weights import LossWeights, cut_frames, nef_kw, weighted_mse
+from ..cells import GROUP_SIZES, _batched, gather_cell_samples
 from .latent_ode import LatentODEMixin, _leaves, _unflatten
 from .pde_trainer import _tree_from_tensors
 
@@ -125,13 +126,58 @@ class NonMetaPDETrainer(LatentODEMixin):
             img, coords, lw = img[:, sub], coords[sub], lw and lw.points(sub)
         return img, coords, lw, xs
 
-    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None):
+    def _fit_cells(self, state, obs, mask, weights, normalize, cells):
+        """_fit_points on cell averages: ``cells`` = (x (M G, dx), q (M G,) or None, group), ``obs`` (B, M, O) cell means, ``mask``
+        and ``weights`` (M,) / (B, M) per observation.  Returns (targets (B, m, O), xs (B, m G, dx), qs (B, m G) or None, ws (B, m) or
+        None, group): at most max(1, max_num_sampled_points // group) cells, one subset for the batch (a stride-0 xs) or, with
+        ``sample_observed`` and weights, every signal's own observed cells with the weights rescaled for that draw.  The one place
+        where a step on cells draws from ``state.rng``."""
+        x, q, G = cells[0], cells[1], int(cells[2])
+        if G not in GROUP_SIZES:
+            raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
+        img = obs.reshape(obs.shape[0], -1, obs.shape[-1])
+        B, M, O = img.shape
+        if x.dim() != 2 or x.shape[0] != M * G:
+            raise ValueError(f"cells hold {tuple(x.shape)} quadrature points, the batch {M} cells of {G}")
+        lw = LossWeights.build(weights, None, B, M, O, normalize=normalize, device=img.device)
+        pick = None
+        if mask is not None:
+            pick = torch.as_tensor(mask, device=img.device)
+            pick = pick.nonzero().reshape(-1) if pick.dtype == torch.bool else pick.long()
+        n = max(1, self.config.training.max_num_sampled_points // G)
+        if self.sample_observed and lw is not None:
+            if pick is not None:
+                keep = torch.zeros(M, dtype=torch.bool, device=img.device)
+                keep[pick] = True
+                lw = lw.keep(keep[None].expand(B, -1))
+            m = make_signal_masks(lw.support(), min(n, M), 0, generator=state.rng, device=img.device)
+            xs, qs, ys, ws = gather_cell_samples(x, q, G, img, m, lw.drawn_on(m).w)
+            return ys[0].to(img.dtype), xs[0], None if qs is None else qs[0], ws[0], G
+        if pick is None and n < M:
+            pick = torch.arange(M, device=img.device)
+        if pick is not None and n < pick.numel():
+            pick = pick[torch.randperm(pick.numel(), generator=state.rng)[:n].to(pick.device)]
+        if pick is not None:
+            rows = (pick[:, None] * G + torch.arange(G, device=pick.device)).reshape(-1)
+            img, x, q, lw = img[:, pick], x[rows], None if q is None else q[rows], lw and lw.points(pick)
+        xs, qs = _batched(x, q, B)
+        return img, xs, qs, None if lw is None else lw.w, G
+
+    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None, cells=None):
         """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
         before ``mask`` and the point sampling unless ``normalize`` is False.
         ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (mean 1 over each signal's N * O values unless
-        ``normalize`` is False), for fields whose variables are observed separately; not together with ``weights``."""
-        img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
+        ``normalize`` is False), for fields whose variables are observed separately; not together with ``weights``.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``initial_state`` holds (B, M, O) cell means, ``mask`` and
+        ``weights`` are per observation (_fit_cells), and the loss is the grouped one (nef.cell_mse) of the decode at the sampled
+        cells' quadrature points.  ``channel_weights`` with ``cells`` is a ValueError."""
+        if cells is not None:
+            if channel_weights is not None:
+                raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
+            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells)
+        else:
+            img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
@@ -140,15 +186,18 @@ class NonMetaPDETrainer(LatentODEMixin):
         if xs is None:
             xs = coords[None].expand(img.shape[0], -1, -1)
         out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
-        loss = ((out - img) ** 2).mean() if lw is None else weighted_mse(out, img, lw.w)
+        if cells is not None:
+            loss = self.nef.cell_mse(out, img, G, qs, ws)
+        else:
+            loss = ((out - img) ** 2).mean() if lw is None else weighted_mse(out, img, lw.w)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)
         gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
         ga = [torch.zeros_like(leaves[k]) if gi is None else gi for k, gi in zip(names, g[len(w):])]
         return loss.detach(), gw, dict(zip(names, ga))
 
-    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True, channel_weights=None):
+    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True, channel_weights=None, cells=None):
         initial_state, traj_idx = batch
-        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize, channel_weights)
+        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize, channel_weights, cells)
         names = list(ga.keys())
         flat = gw + [ga[k] for k in names] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=initial_state.shape[0])
@@ -164,17 +213,18 @@ class NonMetaPDETrainer(LatentODEMixin):
         return loss, NonMetaTrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state,
                                        ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None):
-        """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137); ``weights`` / ``channel_weights`` as in
-        loss_and_grads"""
-        return self._step(state, batch, mask, True, weights, normalize, channel_weights)
+    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, cells=None):
+        """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137); ``weights`` / ``channel_weights`` /
+        ``cells`` as in loss_and_grads"""
+        return self._step(state, batch, mask, True, weights, normalize, channel_weights, cells)
 
-    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None):
+    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, cells=None):
         """Only the latents move (:139-171)."""
-        return self._step(state, batch, mask, False, weights, normalize, channel_weights)
+        return self._step(state, batch, mask, False, weights, normalize, channel_weights, cells)
 
     @torch.no_grad()
-    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, per_signal_loss=False):
+    def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, per_signal_loss=False,
+                         cells=None):
         """nef_train_step_autodec_only (:139-171) on the native latent-only path: same arguments, same (loss, new_state), same draw
         from ``state.rng`` (_fit_points), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
         are read under no_grad, ONE nef.mse_value_and_latent_grads (enf_fit_step_w: forward, fused weighted loss, backward to the
@@ -187,9 +237,16 @@ class NonMetaPDETrainer(LatentODEMixin):
         ``channel_weights`` (N, O) / (B, N, O): the one fit call is enf_fit_step_cw; still one fit call and one table update.
         ``per_signal_loss``: the one fit call is enf_fit_step_e and a third value is returned, loss_b (B,): every signal's own loss
         (this rank's signals; loss_b.mean() is the loss before the all-reduce, up to rounding).  Same draw from ``state.rng``, same
-        new state."""
+        new state.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): the batch holds (B, M, O) cell means (loss_and_grads) and the one
+        fit call is the grouped step, enf_fit_step_g (nef.mse_value_and_cell_grads); the table update is the same."""
         initial_state, traj_idx = batch
-        img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
+        if cells is not None:
+            if channel_weights is not None:
+                raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
+            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells)
+        else:
+            img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         tables = [P[k].detach() for k in names]
@@ -197,7 +254,11 @@ class NonMetaPDETrainer(LatentODEMixin):
         if xs is None:
             xs = coords[None].expand(img.shape[0], -1, -1)
         more = {"return_errors": True} if per_signal_loss else {}
-        loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, **nef_kw(lw), **more)
+        if cells is not None:
+            loss, dp, da, dwin, *errs = self.nef.mse_value_and_cell_grads(state.params["nef"], xs, p, a, window, img, G, qweight=qs,
+                                                                          obs_weight=ws, **more)
+        else:
+            loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, **nef_kw(lw), **more)
         loss = loss.reshape(())
         n_pos = P["p_pos"].shape[-1]
         by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dwin}

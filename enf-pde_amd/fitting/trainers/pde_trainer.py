@@ -45,6 +45,7 @@ import torch
 
 from ... import _lib
 from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
+from ..cells import GROUP_SIZES, _batched, gather_cell_samples
 from .latent_ode import LatentODEMixin, draw_point_masks, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
@@ -78,8 +79,28 @@ def _sampled(coords, img, masks, s, weights, copies=1):
     return (xs[0] if copies == 1 else xs[0].repeat(copies, 1, 1)), ys[0].to(img.dtype), ws[0]
 
 
-def _loss(nef, params, coords, img, masks, s, lat, weights=None):
+def _sampled_cells(cells, img, masks, s, weights, copies=1):
+    """The cells of step ``s`` (``cells`` = (x (M G, dx), q (M G,) or None, group); masks hold CELL indices): (xs (copies * B, Ms G, dx),
+    qs (B, Ms G) or None, ys (B, Ms, O), ws (B, Ms) or None) -- gather_cell_samples on column s, shared masks as a stride-0 batch;
+    per-signal masks give every signal its own cells and always weights (0 where the sampler padded with -1)."""
+    x, q, G = cells
+    B = img.shape[0]
+    xs, qs, ys, ws = gather_cell_samples(x, q, G, img, masks[..., s:s + 1], weights)
+    xs, qs = xs[0], None if qs is None else qs[0]
+    if masks.dim() == 2:
+        xs, qs = _batched(xs, qs, B)
+        xs = xs if copies == 1 else xs[:1].expand(copies * B, -1, -1)
+    elif copies > 1:
+        xs = xs.repeat(copies, 1, 1)
+    return xs, qs, ys[0].to(img.dtype), None if ws is None else ws[0]
+
+
+def _loss(nef, params, coords, img, masks, s, lat, weights=None, cells=None):
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
+    if cells is not None:         # the grouped loss of the decode at the sampled cells' quadrature points (nef.cell_mse: one kernel)
+        xs, qs, ys, ws = _sampled_cells(cells, img, masks, s, weights)
+        out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
+        return nef.cell_mse(out, ys, cells[2], qs, ws)
     xs, ys, ws = _sampled(coords, img, masks, s, weights)               # pde_trainer.py:193-197
     out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
     if ws is None:
@@ -93,18 +114,30 @@ def _latent_grads(nef, params, coords, img, masks, s, lat, keys, weights=None):
     return {k: (torch.zeros_like(lat[k]) if gk is None else gk) for k, gk in zip(keys, g)}
 
 
-def _full_grads(nef, weights, coords, img, masks, s, lat, keys, point_weights=None):
+def _cell_latent_grads(nef, params, cells, img, masks, s, lat, keys, weights=None):
+    """_latent_grads against sampled cells: ONE grouped fit step (nef.mse_value_and_cell_grads: no decode, no autograd graph), whose
+    forward pair kernel records the relu masks when the caller has set them to "write"."""
+    n_ori = nef.cross_attn_invariant.num_z_ori_dims
+    xs, qs, ys, ws = _sampled_cells(cells, img, masks, s, weights)
+    _, dp, da, dsig = nef.mse_value_and_cell_grads(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys, cells[2], qweight=qs,
+                                                   obs_weight=ws)
+    n_pos = lat["p_pos"].shape[-1]
+    by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dsig}
+    return {k: (torch.zeros_like(lat[k]) if by_name[k] is None else by_name[k].reshape(lat[k].shape)) for k in keys}
+
+
+def _full_grads(nef, weights, coords, img, masks, s, lat, keys, point_weights=None, cells=None):
     """(loss, grads w.r.t. the 46 weight tensors, grads w.r.t. the latents) on the training path."""
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
-    loss = _loss(nef, _tree_from_tensors(w, nef), coords, img, masks, s, leaves, point_weights)
+    loss = _loss(nef, _tree_from_tensors(w, nef), coords, img, masks, s, leaves, point_weights, cells)
     g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
     gl = {k: (torch.zeros_like(lat[k]) if gi is None else gi) for k, gi in zip(keys, g[len(w):])}
     return loss.detach(), gw, gl
 
 
-def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf=None, point_weights=None):
+def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf=None, point_weights=None, cells=None):
     """grads(plus) - grads(minus) of the step-s loss, w.r.t. the weights and the latents, in ONE training-path pass: the two
     latent sets run as one batch of 2B signals whose second half enters the loss with a minus sign (the outer step is
     bound by its many small kernels, so one pass of twice the batch costs about half of two passes)."""
@@ -112,10 +145,15 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: torch.cat([plus[k], minus[k]], 0).detach().requires_grad_(True) for k in plus}
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    xs, ys, pw = _sampled(coords, img, masks, s, point_weights, copies=2)     # (per-signal masks: signal b + B at the points of b)
+    if cells is not None:
+        xs, qs, ys, pw = _sampled_cells(cells, img, masks, s, point_weights, copies=2)
+    else:
+        xs, ys, pw = _sampled(coords, img, masks, s, point_weights, copies=2)     # (per-signal masks: signal b + B at the points of b)
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
         out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
-        if pw is None:
+        if cells is not None:
+            loss = nef.cell_mse(out[:B], ys, cells[2], qs, pw) - nef.cell_mse(out[B:], ys, cells[2], qs, pw)
+        elif pw is None:
             loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
         else:
             loss = weighted_mse(out[:B], ys, pw) - weighted_mse(out[B:], ys, pw)
@@ -127,7 +165,7 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
 
 def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
                    second_order="fd", fd_step=None, noise_pos=0.0, generator=None, terminal=None, freeze_relu=True,
-                   weights=None, normalize=True, channel_weights=None):
+                   weights=None, normalize=True, channel_weights=None, cells=None):
     """Value and gradient of the last-inner-step loss w.r.t. (nef weights, meta-init latents, inner lrs).
 
     Returns (loss, grads) with grads = {'nef': [46 tensors in ENF_W_* order], 'autodecoder': {key: (1,Z,.)},
@@ -143,7 +181,20 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     ``channel_weights``: None, or (N, O) / (B, N, O) loss weights per value (fitting/weights.py: prepare_channel_weights), mean 1
     over each signal's N * O values unless ``normalize`` is False; not together with ``weights``.  Every pass that takes the
     per-point weights -- the inner steps, the terminal loss and both perturbed passes of the finite differences -- takes these.
+    ``cells``: None, or (x (M G, dx), q (M G,) or None, group): train on CELL AVERAGES (fitting/cells.py; include/enf_hip.h, "Grouped
+    observations").  ``img`` is then (B, M, O) cell means, ``masks`` index cells, ``weights`` are per observation, (M,) / (B, M), and
+    ``coords`` is not used.  The forward sweep runs the grouped fit step (nef.mse_value_and_cell_grads, which records the relu masks);
+    the default terminal loss and both halves of the finite differences decode the cells' quadrature points and take the grouped loss
+    nef.cell_mse.  ``channel_weights`` with ``cells`` is a ValueError.
     """
+    if cells is not None:
+        if channel_weights is not None:
+            raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
+        if int(cells[2]) not in GROUP_SIZES:
+            raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
+        if cells[0].dim() != 2 or cells[0].shape[0] != img.shape[1] * int(cells[2]):
+            raise ValueError(f"cells hold {tuple(cells[0].shape)} quadrature points, img {img.shape[1]} cells of {int(cells[2])}")
+        cells = (cells[0], cells[1], int(cells[2]))
     pw = loss_tensor(LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device))
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
@@ -166,16 +217,20 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     freeze = second_order == "fd" and freeze_relu and hasattr(nef, "relu_masks")
     for s in range(S):
         # (the forward of this pass also records the relu masks at phi_s for the adjoint sweep's frozen-mask differences)
-        relu_bufs.append(nef.relu_mask_buffer(B, masks.shape[-2], lat["a"].shape[1], coords.device) if freeze else None)
+        rows = masks.shape[-2] * (cells[2] if cells is not None else 1)      # query rows of a step
+        relu_bufs.append(nef.relu_mask_buffer(B, rows, lat["a"].shape[1], img.device) if freeze else None)
         with (nef.relu_masks(relu_bufs[s], "write", B) if freeze else contextlib.nullcontext()):
-            g = _latent_grads(nef, frozen, coords, img, masks, s, lat, keys, pw)
+            if cells is not None:
+                g = _cell_latent_grads(nef, frozen, cells, img, masks, s, lat, keys, pw)
+            else:
+                g = _latent_grads(nef, frozen, coords, img, masks, s, lat, keys, pw)
         g = {k: (torch.zeros_like(lat[k]) if (k not in g or masked(k)) else g[k] * B) for k in lat}    # pde_trainer.py:207
         phis.append(lat)
         gs.append(g)
         lat = {k: (lat[k] - lrs[k] * g[k]).detach() for k in lat}                                       # pde_trainer.py:215-219
     # ---- last step: value, d/d theta, lambda_S
     if terminal is None:
-        loss, g_theta, lam = _full_grads(nef, weights, coords, img, masks, S, lat, keys, pw)
+        loss, g_theta, lam = _full_grads(nef, weights, coords, img, masks, S, lat, keys, pw, cells)
     else:
         loss, g_theta, lam = terminal(weights, lat, keys)
     lam = {k: lam.get(k, torch.zeros_like(lat[k])) for k in lat}
@@ -198,7 +253,7 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
         # with the relu masks AT phi_s both perturbed passes differentiate the same piecewise-linear branch, so their
         # difference is the almost-everywhere second derivative (what jax.grad of the inner steps computes) instead of
         # also counting the units that flip between phi_s - eps w and phi_s + eps w
-        gw_d, gl_d = _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_bufs[s], pw)
+        gw_d, gl_d = _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_bufs[s], pw, cells)
         c = B / (2.0 * eps)                                                     # a 0-dim device tensor
         g_theta = list(torch._foreach_sub(g_theta, torch._foreach_mul(gw_d, c)))
         lam = {k: lam[k] - c * gl_d[k] if k in gl_d else lam[k] for k in lam}
@@ -294,18 +349,22 @@ class MetaSGDPDETrainer(LatentODEMixin):
         keys = [k for k in LATENT_KEYS if k in P and not (k == "p_ori" and self.outer_autodecoder.num_ori_dims == 0)]
         return {k: P[k] for k in keys}
 
-    def _draw_masks(self, state, num_coords, lw=None):
+    def _draw_masks(self, state, num_coords, lw=None, group=1):
         """The index sets of one fit and the weights to fit on them with: make_masks and ``lw`` as it is, or with ``sample_observed``
-        and weights make_signal_masks on their support and the weights rescaled for that draw (LossWeights.drawn_on)."""
+        and weights make_signal_masks on their support and the weights rescaled for that draw (LossWeights.drawn_on).  ``group`` > 1:
+        the indices are cells of that many quadrature rows each, max(1, max_num_sampled_points // group) of them."""
         cfg = self.config
-        n = cfg.training.max_num_sampled_points
+        n = cfg.training.max_num_sampled_points if group == 1 else max(1, cfg.training.max_num_sampled_points // int(group))
         if self.sample_observed and lw is not None:
             masks = make_signal_masks(lw.support(), n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
             return masks, lw.drawn_on(masks)
         return make_masks(num_coords, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device), lw
 
-    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None):
+    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None, cells=None):
         """One outer step on ``batch`` = (B, N, O) initial states (trajectory[:, 0], pde_trainer.py:485-487).
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``batch`` holds (B, M, O) cell means and the step trains on them
+        (meta_gradients); masks drawn here sample max(1, max_num_sampled_points // group) cells, ``weights`` are per observation, and
+        the ``sample_observed`` draw works on them.  ``channel_weights`` with ``cells`` is a ValueError.
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (meta_gradients).
         ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (meta_gradients); with ``sample_observed`` the masks are
         drawn from the points that carry at least one observed value (point_support).
@@ -313,14 +372,19 @@ class MetaSGDPDETrainer(LatentODEMixin):
         the outer gradients are averaged with one flat all-reduce before the (identical) optimiser updates."""
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
+        if cells is not None and channel_weights is not None:
+            raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
         # (point weights that this step does not draw from go on as they came: meta_gradients prepares them)
         lw, kw = None, {"weights": weights, "normalize": normalize}
         if channel_weights is not None or (masks is None and self.sample_observed):
             lw = LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device)
         if masks is None:
-            masks, lw = self._draw_masks(state, self.coords.shape[0], lw)
+            masks, lw = self._draw_masks(state, img.shape[1] if cells is not None else self.coords.shape[0], lw,
+                                         group=int(cells[2]) if cells is not None else 1)
         if lw is not None:
             kw = dict(loop_kw(lw), normalize=False)
+        if cells is not None:
+            kw["cells"] = cells
         lat0 = self._latents0(state)
         lrs = state.params["meta_sgd_lrs"]
         loss, grads = meta_gradients(self.nef, state.params["nef"], lat0, lrs, self.coords, img, masks,

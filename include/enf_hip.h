@@ -454,8 +454,8 @@ int enf_signal_sum(const float* err, int32_t B, int32_t N, float scale, float* l
  * every mode, as err is ("Per-signal and per-point errors"); ENF_FIT_DETERMINISTIC concerns `loss` and the gradients, as there.
  * The host sequences, workspace sizes and served descriptors are those of enf_fit_step_w / enf_eval_loss (every width, head count,
  * embedding, invariant, precision, pair-kernel variant and relu-mask mode); the tail runs an instantiation of its own, one for every G.
- * flags: 0 or ENF_FIT_DETERMINISTIC.  ENF_FIT_SHARED_LATENTS is ENF_EINVAL: the shared backward's loss is another kernel, which has no
- * grouped form (out of scope).  ENF_EINVAL, behind the descriptor's errors and before anything is launched, also for: G outside the
+ * flags: 0 or ENF_FIT_DETERMINISTIC.  ENF_FIT_SHARED_LATENTS is ENF_EINVAL in these two calls: enf_fit_step_gs below is the fit step
+ * that takes it.  ENF_EINVAL, behind the descriptor's errors and before anything is launched, also for: G outside the
  * set; N % G != 0; target == NULL; enf_fit_step_g with loss_b but without err_g (the fit step's workspace has no free region for the
  * errors; enf_eval_loss_g allows it, through the region enf_eval_loss uses); enf_eval_loss_g with loss, err_g and loss_b all NULL.
  * G == 1 is legal: with q == 1 (or NULL) it is the per-point loss, and the result agrees with enf_fit_step_w(weight = w) to rounding --
@@ -470,6 +470,37 @@ int enf_eval_loss_g(const EnfDesc* d, const float* x, int64_t x_bstride, const f
                     const void* packed, const float* target /* (B,M,O) */, int32_t G, const float* qweight /* (B,N) or NULL */,
                     const float* oweight /* (B,M) or NULL */, float* loss /* scalar, accumulated, or NULL */, float* err_g /* (B,M) or NULL */,
                     float* loss_b /* (B) or NULL */, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
+/* The first inner step on shared latents against grouped observations: enf_fit_step_g's arguments, and `flags` may also carry
+ * ENF_FIT_SHARED_LATENTS -- the caller's statement that the latents, the cells (x_bstride == 0) and the rows of qweight are equal for all
+ * signals, as at step 0 of a fit on shared cells.  With the flag clear the call runs enf_fit_step_g's sequence: its bits.  With the flag
+ * set the one shared forward runs wherever enf_shared_forward_parts says it does, and the one shared backward where
+ * enf_shared_backward_applies(d, flags) holds and err_g == NULL (O == 1, the z-fold backward, an invariant without phases, a (D, H) of
+ * the rule's set, not deterministic): ONE tail pass, unit-seeded tail backward and backward pair pass on signal 0, contracted with d out
+ * (B, N) -- which the grouped SHARED form of the loss kernel forms from signal 0's row of outputs, signal 0's factors qweight[0, :] and
+ * all B signals' targets and observation weights.  Elsewhere the ordinary grouped tail runs behind the shared forward.  The results agree
+ * with the unflagged call to rounding, not bit for bit.  Workspace sizes are unchanged; the borrowed regions are those documented for
+ * the shared backward (d out and the row of outputs behind signal 0's rows of d ybar).  B == 1 with the flag: the flag says nothing, the
+ * call is enf_fit_step_g.  B > 1 with the flag and x_bstride != 0: ENF_EINVAL.  Every other refusal is enf_fit_step_g's, in its order. */
+int enf_fit_step_gs(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                    const void* packed, const float* target /* (B,M,O) */, int32_t G, const float* qweight /* (B,N) or NULL */,
+                    const float* oweight /* (B,M) or NULL */, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                    float* err_g /* (B,M) or NULL */, float* loss_b /* (B) or NULL, needs err_g */, void* workspace, size_t workspace_bytes,
+                    unsigned flags, void* stream);
+
+/* The unfused grouped loss, for a caller that holds a decode out (B, N, O) in memory (the weight-gradient path): the definitions above,
+ *     *loss += the grouped loss;   dout (B, N, O) or NULL = d out;   err_g (B, M) or NULL, OVERWRITTEN.
+ * One thread owns one (group, channel): it forms obs as the tail does (products, then pairs at distance 1, 2, .. G / 2), the residual
+ * under the select on w -- a NaN or Inf target under w == 0 is allowed and leaves exact zeros --, its share of the loss and the G values of
+ * d out; err_g is stored by the thread of channel 0, which adds the O shares in channel order.  d out and err_g involve no atomics: the
+ * same bits run to run, in every mode.  The scalar loss is added with one atomic per workgroup, or with flags = ENF_MSE_DETERMINISTIC
+ * through `scratch` (enf_mse_scratch_bytes(B M O, flags) bytes) in a fixed order, as enf_mse_value_grad_w.  qweight NULL = 1 / G exactly,
+ * oweight NULL = 1.  ENF_EINVAL: out, target or loss NULL; B, N, O < 1; G outside the set; N % G != 0; an unknown flag bit; deterministic
+ * without scratch.  Then ENF_EWORKSPACE. */
+int enf_mse_value_grad_g(const float* out /* (B,N,O) */, const float* target /* (B,M,O) */, int32_t B, int32_t N, int32_t O, int32_t G,
+                         const float* qweight /* (B,N) or NULL */, const float* oweight /* (B,M) or NULL */, float grad_scale,
+                         float* dout /* (B,N,O) or NULL */, float* loss, float* err_g /* (B,M) or NULL */, void* scratch,
+                         size_t scratch_bytes, unsigned flags, void* stream);
 
 /* Derivative fields (enf_field_grad, enf_query_vjp): the Jacobian of a decode with respect to its query coordinates -- grad u, the
  * vorticity or divergence of a velocity field, a PDE residual on a decoded frame -- in one call, without the weight-gradient machinery.
@@ -747,6 +778,24 @@ int enf_fit_inputs_cw(int ncomp, const EnfFitComponent* comps, int32_t B, int32_
                       const float* coords, const float* img, const int64_t* masks, float* xs, float* ys, float* losses,
                       const float* cweight /* (B,N,O), required */, float* ws /* (S1,B,Ns,O), required */, int32_t per_signal_masks,
                       void* stream);
+
+/* The inner loop's setup on sampled CELLS in one launch, the counterpart of enf_fit_inputs_w / _b / _cw for cell indices: the latent
+ * broadcast and the zeroed loss accumulators of enf_fit_inputs, and the gather of S1 = S + 1 sets of Ms cells out of M.
+ *     xq (M G, dx) the cells' quadrature points, q (M G) their factors or NULL, obs (B, M, O), oweight (B, M) or NULL
+ *     per_signal_masks == 0: masks (Ms, S1),    xs (S1, Ms G, dx),    qs (S1, Ms G)
+ *     per_signal_masks != 0: masks (B, Ms, S1), xs (S1, B, Ms G, dx), qs (S1, B, Ms G)
+ *     ys (S1, B, Ms, O), ws (S1, B, Ms), losses (S1)
+ * Row i G + k of a sampled set is row m G + k of cell m = masks[..]; ys[s,b,i,:] = obs[b,m,:]; ws[s,b,i] = oweight[b,m].
+ * The index contract of enf_fit_inputs_b: an index outside [0, M) is never dereferenced; its xs / qs rows are cell 0's (finite: q is a
+ * factor, not a select), its ys row zeros and its ws 0.0f.  ws is therefore required with per-signal masks (without oweight it is 1 for
+ * an index in range and 0 outside); with shared masks ws and oweight are given together or both NULL.  q and qs likewise.  64-bit row
+ * offsets.  ENF_EINVAL before any launch: a NULL required pointer, a size < 1, G outside {1, 2, 4, 8, 16}, q / qs or oweight / ws not
+ * given as stated, ncomp outside [1, ENF_SGD_MAX_SEGMENTS] or a bad component. */
+int enf_fit_inputs_g(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1, int32_t G,
+                     int32_t dx, int32_t O, const float* xq /* (M*G, dx) */, const float* q /* (M*G) or NULL */,
+                     const float* obs /* (B, M, O) */, const int64_t* masks, float* xs, float* qs /* NULL iff q NULL */,
+                     float* ys /* (S1, B, Ms, O) */, float* losses, const float* oweight /* (B, M) or NULL */,
+                     float* ws /* (S1, B, Ms) */, int32_t per_signal_masks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
