@@ -17,7 +17,9 @@
 // The same file holds the Gauss-Newton product (enf_gn_product, at the end): prologue tangent and pair kernel as above -- the pair
 // kernel then also stores lse for the backward pair kernel -- and
 //   enf_gn_tail_kernel            the tail's chain with tangents, d out = w tan formed in registers, the tail's backward chain
-// followed by the backward pair kernel and the prologue backward of the other files.
+// followed by the backward pair kernel and the prologue backward of the other files.  enf_gn_product_g is the same product for grouped
+// observations (cell averages): the same host sequence (gn_product_sequence) with the GRP instantiation of the tail, which forms the
+// group sum of the tangent over the wave's query lanes in front of d out.
 // There is one copy of each thing the two entry points have in common: the doubled tail chain (tail_forward_tan, which stashes the
 // pre-activations for the Gauss-Newton tail only), the panel product (panel_gemm2, whose one-operand form serves the backward chain),
 // the launcher and its (D, H) dispatch (launch_pair_tail), and the host sequence (tan_call: refusals, dimensions, workspace;
@@ -519,11 +521,23 @@ struct GnTailArgs {
   float* dybar; float* delta; float* act;      // (NQ, HD), (NQ, H), (NQ, TailCfg::ACT)
   int NQ, O, cw;
   float inv_hd;          // 1 / (true heads * true num_hidden)
-  float gs;              // 2 grad_scale / (B N O)
+  float gs;              // 2 grad_scale / (B N O); grouped: 2 grad_scale / (B M O), M = N / G
+};
+// The grouped form's arguments (include/enf_hip.h, "Grouped observations"), appended behind the block every other instantiation takes:
+// a longer shared block would move their scalar loads ("Grouped observations").
+struct GnTailArgsG : GnTailArgs {
+  int G;                 // 1, 2, 4, 8 or 16; NQ % G == 0
+  const float* qweight;  // nullptr (every factor is 1 / G), or one quadrature factor per query (NQ floats, finite)
+  const float* oweight;  // nullptr (1), or one weight per observation (NQ / G floats, >= 0); the zero-weight select of `weight`
 };
 
-template <int D, int H, bool BF16>
-__global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
+// GRP (enf_gn_product_g): the seed is that of a loss on grouped observations.  The wave's 16 rows sit in do4 in the hot tail's lane
+// layout (tile start a multiple of 16, lane = (col, quad)), so the tangent of the group sums is tail_sq_err_g's xor tree (enf_tail.hip)
+// on do4, in place -- do4 is dead behind the seed -- and d out = q w obs_tan gs in that function's order of operations, contraction off:
+// every lane of a group holds the same bits.  As stated there, a group never straddles a tile, a signal or the clamped rows beyond NQ:
+// tiles start at multiples of 16, G divides 16 and G divides N.  One instantiation serves every G; `weight` and `cw` are not read.
+template <int D, int H, bool BF16, bool GRP = false>
+__global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(std::conditional_t<GRP, GnTailArgsG, GnTailArgs> A) {
   using T = TailCfg<D, H, BF16>;
   constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD, ACT = T::ACT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -545,17 +559,44 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
     tail_forward_tan<D, H, BF16, true, T::ST_G4>(o4, do4, yrow, A.ydot + (size_t)qi * HD, act, L,
                                                  reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, ring,
                                                  (unsigned)L.gto4, lane, quad, A.inv_hd);
-    // ---- d out = (w > 0 ? w tan : 0) gs: a weight of 0 is a select, as in the fused loss
-    const float wq = (A.weight && !A.cw) ? A.weight[qi] : 1.f;
+    if constexpr (GRP) {
+      // ---- d out = (w > 0 ? q (w obs_tan) : 0) gs,  obs_tan = sum_k q tan over the group: a weight of 0 is a select per observation
+#pragma clang fp contract(off)
+      const int G = A.G;
+      const float q = A.qweight ? A.qweight[qi] : 1.0f / (float)G;
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = 16 * t + 4 * quad + i;
-        const bool in = o < A.O && qvalid;
-        const float w = (in && A.cw) ? A.weight[(size_t)qi * A.O + o] : wq;
-        g0[t][i] = (in && w > 0.f) ? w * do4[t][i] * A.gs : 0.f;
-      }
+        for (int i = 0; i < 4; ++i) do4[t][i] = qvalid ? q * do4[t][i] : 0.f;
+#define ENF_GROUP_STEP(K_)                                             \
+  if (G > K_) {                                                        \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t)                      \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) do4[t][i] += __shfl_xor(do4[t][i], K_, 64); \
+  }
+      ENF_GROUP_STEP(1) ENF_GROUP_STEP(2) ENF_GROUP_STEP(4) ENF_GROUP_STEP(8)
+#undef ENF_GROUP_STEP
+      const float w = A.oweight ? A.oweight[qi >> __builtin_ctz(G)] : 1.f;
+      const bool live = qvalid && w > 0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int o = 16 * t + 4 * quad + i;
+          g0[t][i] = (o < A.O && live) ? (q * (w * do4[t][i])) * A.gs : 0.f;
+        }
+    } else {
+      // ---- d out = (w > 0 ? w tan : 0) gs: a weight of 0 is a select, as in the fused loss
+      const float wq = (A.weight && !A.cw) ? A.weight[qi] : 1.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int o = 16 * t + 4 * quad + i;
+          const bool in = o < A.O && qvalid;
+          const float w = (in && A.cw) ? A.weight[(size_t)qi * A.O + o] : wq;
+          g0[t][i] = (in && w > 0.f) ? w * do4[t][i] * A.gs : 0.f;
+        }
+    }
   }
 
   // ---- backward chain (enf_tail_bwd_kernel's) on the stash
@@ -621,6 +662,7 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(GnTailArgs A) {
 // ---------------------------------------------------------------- launch: the pair kernel, then the entry point's tail
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const TailTanArgs*) { return enf_tail_tangent_kernel<D, H, BF16>; }
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgs*) { return enf_gn_tail_kernel<D, H, BF16>; }
+template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgsG*) { return enf_gn_tail_kernel<D, H, BF16, true>; }
 
 // the instantiations: both entry points dispatch here
 template <class TailArgsT>
@@ -705,14 +747,19 @@ extern "C" size_t enf_gn_workspace_bytes(const EnfDesc* d, unsigned flags) {
   return tan_workspace(enf_dims(d), (flags & ENF_BWD_DETERMINISTIC) != 0).total;
 }
 
-extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                              const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
-                              const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
-                              size_t workspace_bytes, unsigned flags, void* stream) {
+// The one copy of the product's host sequence.  grp == NULL: enf_gn_product (weight (B, N) or cweight (B, N, O)).  grp != NULL
+// (enf_gn_product_g): the seed of a loss on grouped observations -- the grouped instantiation of the tail, grp's factors and
+// observation weights, 1 / (B M O) in the scale; `args_ok` then carries the entry point's own checks (ENF_EINVAL, behind
+// ENF_EUNSUPPORTED and before ENF_EWORKSPACE).
+namespace {
+int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                        const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
+                        const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
+                        size_t workspace_bytes, unsigned flags, void* stream, const EnfGroupObs* grp = nullptr, bool args_ok = true) {
   const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0, reuse = (flags & ENF_GN_REUSE_POINT) != 0;
   TanCall c;
-  int rc = tan_call(c, d, x && a && gp && ga && gsigma && (vp || va || vsigma) && !(weight && cweight) && !(flags & ~GN_FLAGS), p, sigma,
-                    packed, workspace, workspace_bytes, det, stream);
+  int rc = tan_call(c, d, x && a && gp && ga && gsigma && (vp || va || vsigma) && !(weight && cweight) && !(flags & ~GN_FLAGS) && args_ok,
+                    p, sigma, packed, workspace, workspace_bytes, det, stream);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfLayout& L = c.L;
@@ -729,12 +776,17 @@ extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstrid
   }
   if ((rc = tan_launch_prologue(c, vp, va, vsigma))) return rc;
   const PairTanArgs PA = tan_pair_args(c, x, x_bstride, c.F(W.lse));
-  GnTailArgs GA;
+  GnTailArgsG GA;
   GA.ybar = PA.ybar; GA.ydot = PA.ydot; GA.blob = pk; GA.L = L; GA.weight = cweight ? cweight : weight; GA.cw = cweight != nullptr;
   GA.dybar = c.F(W.dybar); GA.delta = c.F(W.delta); GA.act = c.F(W.tail_act);
   GA.NQ = m.B * m.N; GA.O = m.O; GA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-  GA.gs = 2.0f * grad_scale / ((float)m.B * (float)m.N * (float)m.O);
-  if ((rc = launch_pair_tail(m, PA, GA, st))) return rc;
+  const int rows = grp ? m.N / grp->G : m.N;      // the values a signal's loss is the mean of: its points, or its observations
+  GA.gs = 2.0f * grad_scale / ((float)m.B * (float)rows * (float)m.O);
+  if (grp) {
+    GA.G = grp->G; GA.qweight = grp->qweight; GA.oweight = grp->oweight;
+    rc = launch_pair_tail(m, PA, GA, st);
+  } else rc = launch_pair_tail(m, PA, static_cast<const GnTailArgs&>(GA), st);
+  if (rc) return rc;
   // the backward pair kernel without a store, in the variant the descriptor resolves to; deterministic: through the partial rows and
   // the fixed-order reduction, which overwrites the gradient table
   if (!det && hipMemsetAsync(c.F(W.dlt), 0, enf_lt_bytes(m), st) != hipSuccess) return ENF_ELAUNCH;
@@ -742,4 +794,24 @@ extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstrid
                                 c.fold_bwd(), nullptr, st, det ? c.F(c.X.part) : nullptr)))
     return rc;
   return enf_launch_prologue_bwd(m, L, pk, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), gp, ga, gsigma, st);
+}
+}  // namespace
+
+extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
+                              const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
+                              size_t workspace_bytes, unsigned flags, void* stream) {
+  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, weight, cweight, grad_scale, gp, ga, gsigma, workspace,
+                             workspace_bytes, flags, stream);
+}
+
+// The product for grouped observations (include/enf_hip.h, "Gauss-Newton product on grouped observations"): ENF_EINVAL also for G
+// outside {1, 2, 4, 8, 16} or N % G != 0, as in enf_fit_step_g.
+extern "C" int enf_gn_product_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                                const float* vp, const float* va, const float* vsigma, const void* packed, int32_t G,
+                                const float* qweight, const float* oweight, float grad_scale, float* gp, float* ga, float* gsigma,
+                                void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  const EnfGroupObs g{G, qweight, oweight, nullptr};
+  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, nullptr, nullptr, grad_scale, gp, ga, gsigma, workspace,
+                             workspace_bytes, flags, stream, &g, enf_group_size_ok(G) && d && d->N % G == 0);
 }

@@ -568,11 +568,9 @@ class EquivariantCrossAttentionNeF:
         return dx
 
     # ------------------------------------------------------------------ tendency fields
-    def _tangent_args(self, what, x, p, a, gaussian_window_size, tangents, xdot=None):
-        """The refusals and argument checks of the forward-mode calls (``tangent``, ``gn_product``), then _field_grad_args' tuple.
-        ``tangents``: ((name, tensor or None) for p, a, window), shapes of p / a / (B, Z, 1).  ``xdot`` (``tangent`` only): a query
-        direction or None; it counts as a tangent and is checked against x (shape, float32, the latents' device) before anything
-        touches the device; its layout is handled as x's (_x_arg)."""
+    def _tangent_refusals(self, what, tangents, xdot=None):
+        """What the forward-mode calls do not serve, and a call without any direction: the checks that look at no tensor's shape or
+        device (``gn_cell_product`` runs them in front of its shape checks)."""
         if self.num_layers > 0:
             raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
         if self.embedding_type != "rff":
@@ -582,6 +580,13 @@ class EquivariantCrossAttentionNeF:
             raise NotImplementedError(f"{what} does not serve the '{name}' invariant (no tangent of the per-latent phase / rotation)")
         if xdot is None and all(t is None for _, t in tangents):
             raise ValueError(f"{what} needs at least one of " + ", ".join(n for n, _ in tangents) + (", xdot" if what == "tangent" else ""))
+
+    def _tangent_args(self, what, x, p, a, gaussian_window_size, tangents, xdot=None):
+        """The refusals and argument checks of the forward-mode calls (``tangent``, ``gn_product``), then _field_grad_args' tuple.
+        ``tangents``: ((name, tensor or None) for p, a, window), shapes of p / a / (B, Z, 1).  ``xdot`` (``tangent`` only): a query
+        direction or None; it counts as a tangent and is checked against x (shape, float32, the latents' device) before anything
+        touches the device; its layout is handled as x's (_x_arg)."""
+        self._tangent_refusals(what, tangents, xdot)
         if xdot is not None:
             if x.dim() != 3 or tuple(xdot.shape) != tuple(x.shape):
                 raise AssertionError(f"xdot has shape {tuple(xdot.shape)}, expected x's {tuple(x.shape)}")
@@ -882,7 +887,8 @@ class EquivariantCrossAttentionNeF:
 
     def _cell_args(self, what, x, p, a, target, group, qweight, obs_weight):
         """The shapes of a grouped call, checked before anything touches the device: x (B, N, dx) with N = M * group, target
-        (B, M, O), qweight (B, N) or None, obs_weight (B, M) or None.  Returns (B, Z, N, M)."""
+        (B, M, O) -- None for a call that takes none (``gn_cell_product``) --, qweight (B, N) or None, obs_weight (B, M) or None.
+        Returns (B, Z, N, M)."""
         if self.num_layers > 0:
             raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
         if int(group) not in self.GROUP_SIZES:
@@ -895,13 +901,13 @@ class EquivariantCrossAttentionNeF:
         if N % int(group):
             raise ValueError(f"x holds {N} query points per signal, not a multiple of group = {group}")
         M = N // int(group)
-        if tuple(target.shape) != (B, M, self.num_out):
+        if target is not None and tuple(target.shape) != (B, M, self.num_out):
             raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, self.num_out)}")
         if qweight is not None and tuple(qweight.shape) != (B, N):
             raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
         if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
             raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
-        if not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda):
+        if not (x.is_cuda and p.is_cuda and a.is_cuda and (target is None or target.is_cuda)):
             raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
         return B, Z, N, M
 
@@ -974,6 +980,39 @@ class EquivariantCrossAttentionNeF:
                     int(group), _ptr(q_), _ptr(w_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
         self._ws_touch(ws)
         return loss_b, err
+
+    @torch.no_grad()
+    def gn_cell_product(self, params, x, p, a, gaussian_window_size, group, qweight=None, obs_weight=None, vp=None, va=None,
+                        vwindow=None, grad_scale=1.0, reuse=None):
+        """The Gauss-Newton matrix of a latent fit on GROUPED observations applied to a direction, in one native call
+        (include/enf_hip.h: enf_gn_product_g):
+            (gp, ga, gwindow or None) = grad_scale * 2 / (B M O) * sum_m Jg^T w Jg (vp, va, vwindow),    Jg = sum_k qweight J
+        with J = d out / d (p, a, window), the sum over the ``group`` consecutive rows of observation m, and w = ``obs_weight`` -- the
+        observation model of ``mse_value_and_cell_grads``, whose ``grad_scale`` makes this the Gauss-Newton Hessian of that step's loss
+        in the units of its gradient.  ``group``, ``qweight`` (B, N) or None for 1 / group, ``obs_weight`` (B, M) or None for 1 as
+        there: an observation of weight 0 does not exist.  ``vp`` / ``va`` / ``vwindow`` and ``reuse`` as in ``gn_product``; the tag
+        may also come from right behind ``mse_value_and_cell_grads`` (not ``shared_latents``) or an earlier ``gn_cell_product`` at the
+        same point.  The group sum of the tangent and d out are formed in the tail's registers.  Size the buffer first: ``gn_reserve``."""
+        tangents = (("vp", vp), ("va", va), ("vwindow", vwindow))
+        self._tangent_refusals("gn_cell_product", tangents)
+        B, Z, N, M = self._cell_args("gn_cell_product", x, p, a, None, group, qweight, obs_weight)
+        xb, xstride, p_, a_, s_ = self._tangent_args("gn_cell_product", x, p, a, gaussian_window_size, tangents)
+        dev = p_.device
+        lib = _lib.load()
+        packed = self.pack(params)
+        q_ = qweight.float().contiguous() if qweight is not None else None
+        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_gn_workspace_bytes)
+        flags = self._det_flag()
+        if reuse is not None and reuse == self._ws_tag(ws) and reuse[1] is not None:
+            flags |= _lib.ENF_GN_REUSE_POINT
+        gp, ga = torch.empty_like(p_), torch.empty_like(a_)
+        gs = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
+        _lib.launch(dev, lib.enf_gn_product_g, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(vp), _ptr(va),
+                    _ptr(vwindow), _ptr(packed), int(group), _ptr(q_), _ptr(w_), float(grad_scale), _ptr(gp), _ptr(ga), _ptr(gs),
+                    _ptr(ws), ws.numel(), flags, st)
+        self._ws_touch(ws)
+        return gp, ga, (gs if s_ is not None else None)
 
     def cell_mse(self, out, target, group, qweight=None, obs_weight=None):
         """The grouped loss of a decode that exists in memory (include/enf_hip.h: enf_mse_value_grad_g), for the weight-gradient path:

@@ -9,6 +9,7 @@
   decode_directional, decode_material_derivative  (no counterpart)   the same pass along a query direction: c . grad u, and Du/Dt = u_t + c . grad u
   decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual  (no counterpart)   second derivatives in forward mode: c^T H c, the Laplacian, the Hessian, u_t - nu Lap u
   cg_solve, lm_fit_latents  (no counterpart)                   batched CG on the native Gauss-Newton product; Levenberg-Marquardt latent fits
+  lm_fit_cell_averages  (no counterpart)                       the Levenberg-Marquardt fit against cell averages, on the grouped Gauss-Newton product
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
   inner_loop_cells, gather_cell_samples, cell_mse_torch  (no counterpart)   the inner loop on sampled cells (the trainers' cells=) and the torch-op mirrors of its kernels
   shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
@@ -22,7 +23,7 @@ from .model import get_model_pde
 from .inner_loop import inner_loop, decode, make_masks, make_signal_masks, default_meta_sgd_lrs
 from .derivatives import decode_jacobian, decode_tangent, decode_tendency, decode_directional, decode_material_derivative, divergence, curl_2d, gradient_norm
 from .derivatives import decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual
-from .gauss_newton import cg_solve, lm_fit_latents
+from .gauss_newton import cg_solve, lm_fit_latents, lm_fit_cell_averages
 from .cells import cell_quadrature, decode_cell_averages, fit_cell_averages, draw_cell_samples
 from .cells import inner_loop_cells, gather_cell_samples, cell_mse_torch
 from .parallel import shard_range, allreduce_mean_, init_distributed
@@ -33,5 +34,5 @@ from .ode_models import PonitaODEGen, MLPODE
 __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_masks", "default_meta_sgd_lrs", "shard_range",
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
-           "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
+           "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "lm_fit_cell_averages", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
            "draw_cell_samples", "inner_loop_cells", "gather_cell_samples", "cell_mse_torch", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual"]

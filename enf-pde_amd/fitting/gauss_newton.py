@@ -5,6 +5,8 @@ Levenberg-Marquardt loop on top of it.
                                       one launch per iteration beside the product, per-signal alpha / beta, frozen signals
   lm_fit_latents(nef, ...)            per signal: gradient and loss from one fit step, a damped Gauss-Newton step by cg_solve on
                                       EquivariantCrossAttentionNeF.gn_product, accept where the signal's loss fell
+  lm_fit_cell_averages(nef, ...)      the same loop against cell averages (grouped observations): the grouped fit step, the grouped
+                                      product EquivariantCrossAttentionNeF.gn_cell_product, the grouped evaluation
 
 The loss is a sum over signals and the latents of different signals do not interact, so the Gauss-Newton matrix is block diagonal:
 every quantity below (damping, step length, acceptance) is per signal, and nothing in a loop iteration reads a value back to the host.
@@ -12,8 +14,9 @@ every quantity below (damping, step length, acceptance) is per signal, and nothi
 import torch
 
 from .. import _lib
+from .cells import _batched
 
-__all__ = ["cg_solve", "lm_fit_latents"]
+__all__ = ["cg_solve", "lm_fit_latents", "lm_fit_cell_averages"]
 
 
 def _cg_update(segs, B, Z, lam, rho, q=None):
@@ -62,6 +65,58 @@ def cg_solve(matvec, rhs, lam, iters):
 _COMPONENTS = ("p", "a", "window")
 
 
+def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate):
+    """The one copy of the Levenberg-Marquardt loop.  The front ends bind their observation model into three callables on the
+    current latents ``cur`` = {"p", "a", "window"}:
+      step(cur)             -> ((dp, da, dwindow or None), loss_b (B,)): the fit step at gradient scale B with its per-signal losses
+      product(cur, v, tag)  -> (gp, ga, gwindow or None): the Gauss-Newton product at the same scale along v = {component: tensor},
+                               ``tag`` the workspace tag behind the last call at this point
+      evaluate(cur)         -> loss_b (B,) at a trial point
+    Returns what lm_fit_latents documents."""
+    comps = tuple(components)
+    if not comps or any(c not in _COMPONENTS for c in comps) or len(set(comps)) != len(comps):
+        raise ValueError(f"components must be a non-empty subset of {_COMPONENTS}, got {components}")
+    if "window" in comps and window is None:
+        raise ValueError("components names the window, but the model has none")
+    comps = tuple(c for c in _COMPONENTS if c in comps)
+    B, Z = p.shape[0], p.shape[1]
+    dev = p.device
+    cur = {"p": p.detach().float().contiguous(), "a": a.detach().float().contiguous(),
+           "window": None if window is None else window.detach().float().reshape(B, Z, 1).contiguous()}
+    lam = torch.full((B,), float(damping), device=dev, dtype=torch.float32)
+    loss_b = torch.empty((int(steps) + 1, B), device=dev, dtype=torch.float32)
+    accepted = torch.zeros((int(steps), B), device=dev, dtype=torch.bool)
+    nef.gn_reserve(B, N, Z, dev)            # the fit step below must already run on the buffer the products reuse
+    last = None
+    for k in range(int(steps)):
+        g, lb = step(cur)
+        grads = dict(zip(_COMPONENTS, g))
+        loss_b[k] = lb
+        tag = [nef.workspace_tag(dev)]
+
+        def matvec(d, tag=tag):
+            out = product(cur, dict(zip(comps, d)), tag[0])
+            tag[0] = nef.workspace_tag(dev)
+            g = dict(zip(_COMPONENTS, out))
+            return tuple(g[c] for c in comps)
+
+        delta = cg_solve(matvec, tuple(-grads[c] for c in comps), lam, cg_iters)
+        trial = dict(cur)
+        for c, dlt in zip(comps, delta):
+            trial[c] = cur[c] + dlt
+        lb_t = evaluate(trial)
+        acc = lb_t < lb                      # (a NaN trial loss is a rejection)
+        for c in comps:
+            cur[c] = torch.where(acc[:, None, None], trial[c], cur[c])
+        lam = torch.where(acc, lam * down, lam * up)
+        accepted[k] = acc
+        last = torch.where(acc, lb_t, lb)
+    if last is None:
+        last = evaluate(cur)
+    loss_b[int(steps)] = last
+    return (cur["p"], cur["a"], cur["window"]), loss_b, lam, accepted
+
+
 @torch.no_grad()
 def lm_fit_latents(nef, params, x, target, p, a, window, steps, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0, components=("p", "a"),
                    weight=None, channel_weight=None):
@@ -75,50 +130,51 @@ def lm_fit_latents(nef, params, x, target, p, a, window, steps, cg_iters=8, damp
     ``weight`` / ``channel_weight``: the loss weights of the fit step.
     Returns ((p, a, window), loss_b (steps + 1, B), damping (B,), accepted (steps, B) bool), all on the device; loss_b[k] is the loss
     before step k, loss_b[steps] the final one."""
-    comps = tuple(components)
-    if not comps or any(c not in _COMPONENTS for c in comps) or len(set(comps)) != len(comps):
-        raise ValueError(f"components must be a non-empty subset of {_COMPONENTS}, got {components}")
-    if "window" in comps and window is None:
-        raise ValueError("components names the window, but the model has none")
-    comps = tuple(c for c in _COMPONENTS if c in comps)
-    B, Z, N = p.shape[0], p.shape[1], x.shape[1]
-    dev = p.device
-    cur = {"p": p.detach().float().contiguous(), "a": a.detach().float().contiguous(),
-           "window": None if window is None else window.detach().float().reshape(B, Z, 1).contiguous()}
-    lam = torch.full((B,), float(damping), device=dev, dtype=torch.float32)
-    loss_b = torch.empty((int(steps) + 1, B), device=dev, dtype=torch.float32)
-    accepted = torch.zeros((int(steps), B), device=dev, dtype=torch.bool)
+    B = p.shape[0]
     wkw = dict(weight=weight, channel_weight=channel_weight)
-    nef.gn_reserve(B, N, Z, dev)            # the fit step below must already run on the buffer the products reuse
-    last = None
-    for k in range(int(steps)):
+
+    def step(cur):
         res = nef.mse_value_and_latent_grads(params, x, cur["p"], cur["a"], cur["window"], target, grad_scale=float(B), return_errors=True,
                                              **wkw)
-        grads = dict(zip(_COMPONENTS, res[1:4]))
-        lb = res[5]
-        loss_b[k] = lb
-        tag = [nef.workspace_tag(dev)]
+        return res[1:4], res[5]
 
-        def matvec(d, tag=tag):
-            v = dict(zip(comps, d))
-            out = nef.gn_product(params, x, cur["p"], cur["a"], cur["window"], vp=v.get("p"), va=v.get("a"), vwindow=v.get("window"),
-                                 grad_scale=float(B), reuse=tag[0], **wkw)
-            tag[0] = nef.workspace_tag(dev)
-            g = dict(zip(_COMPONENTS, out))
-            return tuple(g[c] for c in comps)
+    def product(cur, v, tag):
+        return nef.gn_product(params, x, cur["p"], cur["a"], cur["window"], vp=v.get("p"), va=v.get("a"), vwindow=v.get("window"),
+                              grad_scale=float(B), reuse=tag, **wkw)
 
-        delta = cg_solve(matvec, tuple(-grads[c] for c in comps), lam, cg_iters)
-        trial = dict(cur)
-        for c, dlt in zip(comps, delta):
-            trial[c] = cur[c] + dlt
-        lb_t, _ = nef.eval_loss(params, x, trial["p"], trial["a"], trial["window"], target, **wkw)
-        acc = lb_t < lb                      # (a NaN trial loss is a rejection)
-        for c in comps:
-            cur[c] = torch.where(acc[:, None, None], trial[c], cur[c])
-        lam = torch.where(acc, lam * down, lam * up)
-        accepted[k] = acc
-        last = torch.where(acc, lb_t, lb)
-    if last is None:
-        last = nef.eval_loss(params, x, cur["p"], cur["a"], cur["window"], target, **wkw)[0]
-    loss_b[int(steps)] = last
-    return (cur["p"], cur["a"], cur["window"]), loss_b, lam, accepted
+    def evaluate(cur):
+        return nef.eval_loss(params, x, cur["p"], cur["a"], cur["window"], target, **wkw)[0]
+
+    return _lm_loop(nef, x.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate)
+
+
+@torch.no_grad()
+def lm_fit_cell_averages(nef, params, x, q, group, target, p, a, window, steps, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0,
+                         components=("p", "a"), obs_weight=None):
+    """Levenberg-Marquardt fit of the latents of B signals to CELL AVERAGES (fitting/cells.py; include/enf_hip.h, "Grouped
+    observations"): ``target`` (B, M, O) are observations obs[m] = sum_k q[m group + k] out[m group + k] over the ``group`` consecutive
+    quadrature points of cell m.  ``x``: the points, (N, dx) shared by the signals or (B, N, dx), a stride-0 batch included; ``q``: the
+    factors (N,), (B, N), or None for 1 / group (cell_quadrature gives both); ``obs_weight``: None or (B, M), an observation of weight 0
+    does not exist.  An observation is linear in the decode, so the Gauss-Newton matrix is exact up to the residual's curvature.
+    lm_fit_latents' loop on the grouped calls.  Per step: one ``nef.mse_value_and_cell_grads(return_errors=True, grad_scale=B)``;
+    ``cg_iters`` products ``nef.gn_cell_product`` at that point (the latent prologue reused) inside ``cg_solve``; one
+    ``nef.eval_cell_loss`` at the trial point; per-signal acceptance and damping by torch.where, no host synchronisation in the loop.
+    The other arguments and the return values are lm_fit_latents'."""
+    B = p.shape[0]
+    xb, qb = _batched(x, q, B)
+    G = int(group)
+    okw = dict(qweight=qb, obs_weight=obs_weight)
+
+    def step(cur):
+        res = nef.mse_value_and_cell_grads(params, xb, cur["p"], cur["a"], cur["window"], target, G, grad_scale=float(B),
+                                           return_errors=True, **okw)
+        return res[1:4], res[5]
+
+    def product(cur, v, tag):
+        return nef.gn_cell_product(params, xb, cur["p"], cur["a"], cur["window"], G, vp=v.get("p"), va=v.get("a"),
+                                   vwindow=v.get("window"), grad_scale=float(B), reuse=tag, **okw)
+
+    def evaluate(cur):
+        return nef.eval_cell_loss(params, xb, cur["p"], cur["a"], cur["window"], target, G, **okw)[0]
+
+    return _lm_loop(nef, xb.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate)

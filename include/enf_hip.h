@@ -628,8 +628,10 @@ int enf_field_second_x(const EnfDesc* d, const float* x, int64_t x_bstride, cons
  * forward chain runs once; the backward pair kernel without a store; the prologue backward.
  * flags: ENF_BWD_DETERMINISTIC -- the backward pair kernel's fixed-order route: no float atomic runs, same inputs give the same bits,
  * independent of what the workspace held (the rest of the sequence is deterministic by construction).  ENF_GN_REUSE_POINT -- the
- * caller's statement that the last call on this workspace was enf_fit_step_w / _cw / _e / _ex WITHOUT ENF_FIT_SHARED_LATENTS, or an
- * earlier enf_gn_product, on the same (d, x, p, a, sigma, packed) and the same deterministic bit: the prologue and the z-fold matrices
+ * caller's statement that the last call on this workspace was enf_fit_step_w / _cw / _e / _ex / _g WITHOUT ENF_FIT_SHARED_LATENTS
+ * (enf_fit_step_gs with the flag clear is enf_fit_step_g), or an earlier enf_gn_product or enf_gn_product_g, on the same
+ * (d, x, p, a, sigma, packed) and the same deterministic bit -- the grouped step runs the per-point step's sequence around another
+ * tail, so it leaves the latent table, `an`, `kv` and the z-fold backward's matrices as that step does: the prologue and the z-fold matrices
  * are not recomputed (a CG solve calls the product many times at one point, right behind the fit step that gave the gradient).  Any
  * other bit: ENF_EINVAL.
  * `workspace`: ONE buffer of enf_gn_workspace_bytes(d, flags) bytes.  It begins with the plain workspace's regions at their usual
@@ -646,6 +648,27 @@ int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstride, const fl
                    const void* packed, const float* weight /* (B,N) or NULL */, const float* cweight /* (B,N,O) or NULL */,
                    float grad_scale, float* gp, float* ga, float* gsigma /* shapes of p / a / sigma, required, OVERWRITTEN */,
                    void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+/* Gauss-Newton product on grouped observations (enf_gn_product_g): the product above for a fit on cell averages, in the notation of
+ * "Grouped observations" (G, M = N / G, q = qweight (B, N) or NULL = 1/G exactly, w = oweight (B, M) or NULL = 1),
+ *     gv = grad_scale * 2 / (B M O) * sum_{m,o} Jg[b,m,o,:]^T  w[b,m]  (Jg v)[b,m,o]
+ *     Jg[b,m,o,:] = sum_{k<G} q[b, mG+k] * J[b, mG+k, o, :]                the Jacobian of the group sums obs[b,m,o]
+ * w is under the zero-weight select: an observation of weight 0 does not exist, and its G rows get d out == 0.0f exactly, whatever
+ * their x and q hold (finite).  q is a plain finite factor; nothing is normalised.  With enf_fit_step_g's grad_scale gv is the
+ * Gauss-Newton Hessian of that step's loss applied to v, in the units of its gradient -- an observation is linear in the decode, so the
+ * matrix is exact up to the residual's curvature.
+ * The sequence is enf_gn_product's with the grouped form of the GN tail: behind the tangent chain a wave forms obs_tan = sum_k q tan by
+ * the fixed xor tree of the fused grouped loss over its 16 query lanes (a group never straddles a tile, a signal or the rows beyond
+ * B N, see there) and d out = q * (w * obs_tan) * 2 grad_scale / (B M O) in every lane of the group, in registers: neither tan,
+ * obs_tan nor d out reaches memory.  One instantiation serves every G.  G == 1 with q == 1 (or NULL) is the per-point product with
+ * weight = w, to rounding -- not bit for bit, it is another instantiation.
+ * Workspace and size query: enf_gn_workspace_bytes, unchanged.  flags: ENF_BWD_DETERMINISTIC, ENF_GN_REUSE_POINT, as above.
+ * Errors in this order: the descriptor's; ENF_EUNSUPPORTED as enf_gn_product gives it; ENF_EINVAL for what enf_gn_product refuses
+ * and for G outside {1, 2, 4, 8, 16} or N % G != 0; then ENF_EWORKSPACE. */
+int enf_gn_product_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                     const float* vp, const float* va, const float* vsigma, const void* packed,
+                     int32_t G, const float* qweight /* (B,N) or NULL = 1/G */, const float* oweight /* (B,M) or NULL = 1 */,
+                     float grad_scale, float* gp, float* ga, float* gsigma,
+                     void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
 /* One conjugate-gradient step for B independent systems in one launch: the Gauss-Newton matrix of a fit is block diagonal over the
  * signals, so a solve is B separate CG iterations with per-signal alpha, beta and damping.  The vectors are split over up to three
  * segments (the latent components), each (B, Z, width) fp32 contiguous.
