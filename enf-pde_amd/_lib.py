@@ -27,6 +27,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_cw", "enf_mse_value_grad_cw", "enf_fit_inputs_cw",
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum", "enf_fit_step_g", "enf_eval_loss_g",
            "enf_fit_step_gs", "enf_mse_value_grad_g", "enf_fit_inputs_g",
+           "enf_fit_step_gc", "enf_eval_loss_gc", "enf_mse_value_grad_gc", "enf_fit_inputs_gc",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
            "enf_field_second_workspace_bytes", "enf_field_second_x",
@@ -258,6 +259,12 @@ def _bind(path, hooks):
     lib.enf_fit_step_gs.argtypes = list(lib.enf_fit_step_g.argtypes)
     lib.enf_mse_value_grad_g.argtypes = [vp, vp] + [ctypes.c_int32] * 4 + [vp, vp, ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
     lib.enf_fit_inputs_g.argtypes = [ctypes.c_int, ctypes.POINTER(EnfFitComponent)] + [ctypes.c_int32] * 8 + [vp] * 10 + [ctypes.c_int32, vp]
+    # per-value weights on grouped observations: the _g calls' arguments with cweight_g (B, M, O), required, in place of oweight; the
+    # gather's ws is (S1, B, Ms, O)
+    lib.enf_fit_step_gc.argtypes = list(lib.enf_fit_step_g.argtypes)
+    lib.enf_eval_loss_gc.argtypes = list(lib.enf_eval_loss_g.argtypes)
+    lib.enf_mse_value_grad_gc.argtypes = list(lib.enf_mse_value_grad_g.argtypes)
+    lib.enf_fit_inputs_gc.argtypes = list(lib.enf_fit_inputs_g.argtypes)
     # derivative fields (include/enf_hip.h, "Derivative fields"): out (B, N, O) | NULL, jac (O, B, N, dx); dout (B, N, O), dx (B, N, dx)
     lib.enf_field_grad_workspace_bytes.restype = sz
     lib.enf_field_grad_workspace_bytes.argtypes = [dp, cu]

@@ -404,7 +404,7 @@ static int eval_loss_sequence(const EnfDesc* d, const float* x, int64_t x_bstrid
     return rc;
   float* e = err ? err : (loss_b ? c.F(W.dybar) : nullptr);
   if (grp) {
-    const EnfGroupObs g{grp->G, grp->qweight, grp->oweight, e};
+    const EnfGroupObs g{grp->G, grp->qweight, grp->oweight, e, grp->cweight};
     rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, g, 0.f, loss, nullptr, nullptr, nullptr, st, det ? c.F(c.X.loss) : nullptr);
   } else
     rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
@@ -453,6 +453,30 @@ extern "C" int enf_eval_loss_g(const EnfDesc* d, const float* x, int64_t x_bstri
   const EnfGroupObs g{G, qweight, oweight, err_g};
   return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, nullptr, loss_b, workspace, workspace_bytes, flags,
                             stream, &g, group_args_ok(d, G));
+}
+
+// ---- per-value weights on grouped observations: the same two sequences, the group descriptor carrying cweight_g (B, M, O) in place of
+// oweight -- the tail's per-value grouped forms.  The refusals are the _g calls'; cweight_g is required; ENF_FIT_SHARED_LATENTS is
+// ENF_EUNSUPPORTED (the flag is taken out of what the sequence sees, so the descriptor's errors come first).
+extern "C" int enf_fit_step_gc(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, int32_t G, const float* qweight, const float* cweight_g, float grad_scale,
+                               float* loss, float* dp, float* da, float* dsigma, float* err_g, float* loss_b, void* workspace,
+                               size_t workspace_bytes, unsigned flags, void* stream) {
+  if (flags & ENF_FIT_SHARED_LATENTS) {
+    if (int rc = enf_check_desc(d)) return rc;
+    return ENF_EUNSUPPORTED;
+  }
+  const EnfGroupObs g{G, qweight, nullptr, err_g, cweight_g};
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
+                           false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && cweight_g && !(loss_b && !err_g), &g);
+}
+
+extern "C" int enf_eval_loss_gc(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                                const void* packed, const float* target, int32_t G, const float* qweight, const float* cweight_g, float* loss,
+                                float* err_g, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  const EnfGroupObs g{G, qweight, nullptr, err_g, cweight_g};
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, nullptr, loss_b, workspace, workspace_bytes, flags,
+                            stream, &g, group_args_ok(d, G) && cweight_g);
 }
 
 // ---- derivative fields: the Jacobian of a decode w.r.t. the query coordinates (include/enf_hip.h, "Derivative fields")

@@ -215,7 +215,8 @@ int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob,
                          const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part = nullptr);
 // grouped observations (include/enf_hip.h, "Grouped observations"): observation m of a signal is the q-weighted sum of the decode at
 // queries m G .. m G + G - 1.  qweight (B, N) or NULL (1 / G); oweight (B, N / G) or NULL (1); err_g (B, N / G) or NULL.
-struct EnfGroupObs { int G; const float* qweight; const float* oweight; float* err_g; };
+// cweight (B, N / G, O) or NULL: one weight per observed VALUE in place of oweight (the _gc calls) -- the tail's per-value grouped forms.
+struct EnfGroupObs { int G; const float* qweight; const float* oweight; float* err_g; const float* cweight = nullptr; };
 inline bool enf_group_size_ok(int G) { return G == 1 || G == 2 || G == 4 || G == 8 || G == 16; }
 // the fused-loss tail (dybar != NULL: arguments as enf_launch_tail_loss) or the evaluation tail (dybar, delta, act NULL: as
 // enf_launch_tail_eval) against target (B, N / G, O); ENF_EINVAL for a G outside the set or N % G != 0

@@ -153,6 +153,8 @@ extern "C" int enf_mse_value_grad(const float* out, const float* target, size_t 
 // (it recomputes their sums): one plain store per observation, no atomics.
 // SHARED (the shared-latent backward, enf_layout.h: enf_shared_backward_rule; O == 1): `out` is the ONE row of N values every signal
 // decodes to and q (N, or NULL) are signal 0's factors; target, w and d out stay per signal.
+// cweight (enf_mse_value_grad_gc; never with SHARED): one weight per observed value (B, M, O) in place of oweight -- the thread reads
+// cweight[i], its own (group, channel), and the err_g thread every channel's own weight; the arithmetic is the same.
 __device__ __forceinline__ float mse_group_sum(const float* __restrict__ out, const float* __restrict__ q, size_t orow, size_t qrow, int O,
                                                int o, int G) {
 #pragma clang fp contract(off)
@@ -169,8 +171,8 @@ __device__ __forceinline__ float mse_group_sum(const float* __restrict__ out, co
 
 template <bool SHARED>
 __global__ __launch_bounds__(256) void enf_mse_group_kernel(const float* __restrict__ out, const float* __restrict__ target,
-                                                            const float* __restrict__ qweight, const float* __restrict__ oweight, size_t n,
-                                                            int M, int O, int G, float inv_n, float gscale, float* __restrict__ dout,
+                                                            const float* __restrict__ qweight, const float* __restrict__ oweight,
+                                                            const float* __restrict__ cweight, size_t n, int M, int O, int G, float inv_n, float gscale, float* __restrict__ dout,
                                                             float* __restrict__ err_g, float* loss, float* __restrict__ part) {
 #pragma clang fp contract(off)
   const float gs = 2.0f * inv_n * gscale;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void enf_mse_group_kernel(const float* __restr
     const int o = (int)(i - bm * (size_t)O);
     const size_t row = bm * (size_t)G;                   // its first query row, b N + m G
     const size_t orow = SHARED ? row % ((size_t)M * G) : row;     // the row of `out` (and of q) it reads
-    const float w = oweight ? oweight[bm] : 1.f;
+    const float w = cweight ? cweight[i] : (oweight ? oweight[bm] : 1.f);
     const bool live = w > 0.f;
     const float dd = live ? mse_group_sum(out, qweight, orow, orow, O, o, G) - target[i] : 0.f;
     const float wd = w * dd;
@@ -192,8 +194,9 @@ __global__ __launch_bounds__(256) void enf_mse_group_kernel(const float* __restr
     if (err_g && o == 0) {
       float e = fmaf(wd, dd, 0.f);
       for (int c = 1; c < O; ++c) {
-        const float dc = live ? mse_group_sum(out, qweight, orow, orow, O, c, G) - target[i + c] : 0.f;
-        e = fmaf(w * dc, dc, e);
+        const float wc = cweight ? cweight[i + c] : w;
+        const float dc = wc > 0.f ? mse_group_sum(out, qweight, orow, orow, O, c, G) - target[i + c] : 0.f;
+        e = fmaf(wc * dc, dc, e);
       }
       err_g[bm] = e;
     }
@@ -204,8 +207,8 @@ __global__ __launch_bounds__(256) void enf_mse_group_kernel(const float* __restr
 // Every grouped MSE launch: n = B M O threads' worth of (group, channel) pairs on the grid of mse_launch, the deterministic sum behind it.
 static int mse_group_launch(bool shared, const float* out, const float* target, const float* qweight, const float* oweight, int B, int N,
                             int O, int G, float grad_scale, float* dout, float* err_g, float* loss, void* scratch, size_t scratch_bytes,
-                            unsigned flags, hipStream_t st) {
-  if (!out || !target || !loss || B < 1 || N < 1 || O < 1 || !enf_group_size_ok(G) || N % G || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
+                            unsigned flags, hipStream_t st, const float* cweight = nullptr, bool args_ok = true) {
+  if (!args_ok || !out || !target || !loss || B < 1 || N < 1 || O < 1 || !enf_group_size_ok(G) || N % G || (flags & ~ENF_MSE_DETERMINISTIC)) return ENF_EINVAL;
   const int M = N / G;
   const size_t n = (size_t)B * (size_t)M * (size_t)O;
   const bool det = (flags & ENF_MSE_DETERMINISTIC) != 0;
@@ -215,7 +218,7 @@ static int mse_group_launch(bool shared, const float* out, const float* target, 
   float* part = det ? (float*)scratch : nullptr;
   const float inv_n = 1.0f / ((float)B * (float)M * (float)O);      // the fused tail's (enf_tail.hip: tail_loss_kernel)
   hipLaunchKernelGGL(shared ? enf_mse_group_kernel<true> : enf_mse_group_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, out, target,
-                     qweight, oweight, n, M, O, G, inv_n, grad_scale, dout, err_g, loss, part);
+                     qweight, oweight, cweight, n, M, O, G, inv_n, grad_scale, dout, err_g, loss, part);
   if (hipGetLastError() != hipSuccess) return ENF_ELAUNCH;
   return det ? enf_launch_loss_sum(part, (int)blocks, loss, st) : ENF_OK;
 }
@@ -230,6 +233,13 @@ extern "C" int enf_mse_value_grad_g(const float* out, const float* target, int32
                                     size_t scratch_bytes, unsigned flags, void* stream) {
   return mse_group_launch(false, out, target, qweight, oweight, B, N, O, G, grad_scale, dout, err_g, loss, scratch, scratch_bytes, flags,
                           (hipStream_t)stream);
+}
+
+extern "C" int enf_mse_value_grad_gc(const float* out, const float* target, int32_t B, int32_t N, int32_t O, int32_t G, const float* qweight,
+                                     const float* cweight_g, float grad_scale, float* dout, float* loss, float* err_g, void* scratch,
+                                     size_t scratch_bytes, unsigned flags, void* stream) {
+  return mse_group_launch(false, out, target, qweight, nullptr, B, N, O, G, grad_scale, dout, err_g, loss, scratch, scratch_bytes, flags,
+                          (hipStream_t)stream, cweight_g, cweight_g != nullptr);
 }
 
 struct SgdArgs { EnfSgdSegment seg[ENF_SGD_MAX_SEGMENTS]; int nseg; float scale; };
@@ -367,9 +377,10 @@ __global__ __launch_bounds__(256) void enf_fit_inputs_rows_kernel(FitInArgs A, u
 // weight, and -- with per-signal masks every thread, with shared masks the threads of signal 0 -- the cell's G rows of points and
 // factors: row i G + k of the set is row m G + k of cell m.  An index outside [0, M) is never used as an offset: its rows are cell 0's
 // (finite: q is a factor, not a select), its targets zeros and its weight 0.  A.ws NULL (shared masks without weights): not written.
-// All offsets are 64-bit.
+// per_value (enf_fit_inputs_gc): A.weight holds one weight per observed value, (B, M, O) -> A.ws (S1, B, Ms, O), as
+// enf_fit_inputs_rows_kernel gathers them for points; an index outside [0, M) gives O zeros.  All offsets are 64-bit.
 __global__ __launch_bounds__(256) void enf_fit_inputs_cells_kernel(FitInArgs A, int G, const float* __restrict__ q, float* __restrict__ qs,
-                                                                   bool per_signal) {
+                                                                   bool per_signal, bool per_value) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nrow = (int64_t)A.S1 * A.B * A.Ns;
   if (i < nrow) {
@@ -390,21 +401,26 @@ __global__ __launch_bounds__(256) void enf_fit_inputs_cells_kernel(FitInArgs A, 
     } else {
       for (int o = 0; o < A.O; ++o) y[o] = 0.f;
     }
-    if (A.ws) A.ws[i] = ok ? (A.weight ? A.weight[b * A.N + m] : 1.0f) : 0.f;
+    if (per_value) {
+      float* __restrict__ w = A.ws + i * A.O;
+      for (int o = 0; o < A.O; ++o) w[o] = ok ? A.weight[(b * A.N + m) * A.O + o] : 0.f;
+    } else if (A.ws) A.ws[i] = ok ? (A.weight ? A.weight[b * A.N + m] : 1.0f) : 0.f;
     return;
   }
   fit_broadcast_then(A, i - nrow, [&](int64_t j) { if (j < A.S1) A.losses[j] = 0.f; });
 }
 
-extern "C" int enf_fit_inputs_g(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1, int32_t G,
-                                int32_t dx, int32_t O, const float* xq, const float* q, const float* obs, const int64_t* masks, float* xs,
-                                float* qs, float* ys, float* losses, const float* oweight, float* ws, int32_t per_signal_masks, void* stream) {
+// Both gathers of cells: validation, FitInArgs, grid and launch.  per_value: `oweight` is cweight_g (B, M, O) and ws (S1, B, Ms, O).
+static int fit_inputs_cells_launch(bool per_value, int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1,
+                                   int32_t G, int32_t dx, int32_t O, const float* xq, const float* q, const float* obs, const int64_t* masks,
+                                   float* xs, float* qs, float* ys, float* losses, const float* oweight, float* ws, int32_t per_signal_masks,
+                                   void* stream) {
   const bool per_signal = per_signal_masks != 0;
   if (ncomp < 1 || ncomp > ENF_SGD_MAX_SEGMENTS || !comps || !xq || !obs || !masks || !xs || !ys || !losses) return ENF_EINVAL;
   if (B < 1 || Z < 1 || M < 1 || Ms < 1 || S1 < 1 || dx < 1 || O < 1 || !enf_group_size_ok(G)) return ENF_EINVAL;
   if ((q == nullptr) != (qs == nullptr)) return ENF_EINVAL;
   // ws is what says that an index outside [0, M) does not exist: required with per-signal masks (1 / 0 without oweight)
-  if (per_signal ? ws == nullptr : (oweight == nullptr) != (ws == nullptr)) return ENF_EINVAL;
+  if (per_value ? !(oweight && ws) : (per_signal ? ws == nullptr : (oweight == nullptr) != (ws == nullptr))) return ENF_EINVAL;
   FitInArgs A{};
   int64_t total = (int64_t)S1 * B * Ms + S1;
   for (int k = 0; k < ncomp; ++k) {
@@ -416,8 +432,22 @@ extern "C" int enf_fit_inputs_g(int ncomp, const EnfFitComponent* comps, int32_t
   A.ncomp = ncomp; A.B = B; A.Z = Z; A.N = M; A.Ns = Ms; A.S1 = S1; A.dx = dx; A.O = O;
   A.coords = xq; A.img = obs; A.masks = masks; A.xs = xs; A.ys = ys; A.losses = losses; A.weight = oweight; A.ws = ws;
   hipLaunchKernelGGL(enf_fit_inputs_cells_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A, (int)G, q, qs,
-                     per_signal);
+                     per_signal, per_value);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
+}
+
+extern "C" int enf_fit_inputs_g(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1, int32_t G,
+                                int32_t dx, int32_t O, const float* xq, const float* q, const float* obs, const int64_t* masks, float* xs,
+                                float* qs, float* ys, float* losses, const float* oweight, float* ws, int32_t per_signal_masks, void* stream) {
+  return fit_inputs_cells_launch(false, ncomp, comps, B, Z, M, Ms, S1, G, dx, O, xq, q, obs, masks, xs, qs, ys, losses, oweight, ws,
+                                 per_signal_masks, stream);
+}
+extern "C" int enf_fit_inputs_gc(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1, int32_t G,
+                                 int32_t dx, int32_t O, const float* xq, const float* q, const float* obs, const int64_t* masks, float* xs,
+                                 float* qs, float* ys, float* losses, const float* cweight_g, float* ws, int32_t per_signal_masks,
+                                 void* stream) {
+  return fit_inputs_cells_launch(true, ncomp, comps, B, Z, M, Ms, S1, G, dx, O, xq, q, obs, masks, xs, qs, ys, losses, cweight_g, ws,
+                                 per_signal_masks, stream);
 }
 
 // Every enf_fit_inputs* call: validation (`args_ok` is the entry point's own condition on weight / ws), FitInArgs, grid and launch.

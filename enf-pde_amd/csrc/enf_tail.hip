@@ -49,7 +49,14 @@ struct TailArgsG : TailArgs {
   float* err_g;          // nullptr, or the weighted squared error of every observation (NQ / G floats, OVERWRITTEN)
   int G;                 // 1, 2, 4, 8 or 16
 };
-template <bool GROUPED> using TailArgsFor = std::conditional_t<GROUPED, TailArgsG, TailArgs>;
+// Per-value weights on grouped observations (GRP with CW / EVAL == 4; include/enf_hip.h, "Grouped observations": the _gc calls): one
+// weight per observed VALUE in place of `oweight`.  Appended in a struct of its own again, for the reason above: only the per-value
+// grouped instantiations take it, so TailArgs and TailArgsG keep their layout and the kernels on them their instructions.
+struct TailArgsGC : TailArgsG {
+  const float* cweight;  // (NQ / G, O) floats, >= 0, never nullptr; the zero-weight rule per value
+};
+// GROUPED 0: TailArgs; 1: TailArgsG; 2: TailArgsGC
+template <int GROUPED> using TailArgsFor = std::conditional_t<GROUPED == 2, TailArgsGC, std::conditional_t<GROUPED == 1, TailArgsG, TailArgs>>;
 
 // load_rows (enf_tail_common.h) from bf16 rows (two values per word, low half first)
 template <int NT> DEV void load_rows_half(f32x4 (&X)[NT], const unsigned short* row, int quad) {
@@ -286,7 +293,11 @@ DEV float tail_sq_err(const f32x4 (&o4)[2], f32x4 (&g0)[2], const TailArgs& A, i
 // A group is wholly valid or wholly beyond NQ; lanes beyond NQ contribute zeros.  The squared error is counted once per observation, by
 // the lane with col % G == 0; g0 = d out = q w (obs - target) gs in every lane.  w == 0 is a select, as in tail_sq_err.
 // Returns this lane's share of sum_o w (obs - target)^2.
-DEV float tail_sq_err_g(const f32x4 (&o4)[2], f32x4 (&g0)[2], const TailArgsG& A, int qi, bool qvalid, int col, int quad, float gs) {
+// CW (A is then a TailArgsGC): one weight per observed value.  After the tree every lane of a group holds obs for its eight channels, so
+// the lane reads cweight[m][o] where the per-observation form reads oweight[m] and applies the select per value, as tail_sq_err<CW> does;
+// the arithmetic per value and its order are those of the per-observation form.
+template <bool CW, class Args>
+DEV float tail_sq_err_g(const f32x4 (&o4)[2], f32x4 (&g0)[2], const Args& A, int qi, bool qvalid, int col, int quad, float gs) {
 #pragma clang fp contract(off)
   const int G = A.G;
   const float q = A.qweight ? A.qweight[qi] : 1.0f / (float)G;
@@ -303,20 +314,35 @@ DEV float tail_sq_err_g(const f32x4 (&o4)[2], f32x4 (&g0)[2], const TailArgsG& A
   ENF_GROUP_STEP(1) ENF_GROUP_STEP(2) ENF_GROUP_STEP(4) ENF_GROUP_STEP(8)
 #undef ENF_GROUP_STEP
   const int m = qi >> __builtin_ctz(G);
-  const float w = A.oweight ? A.oweight[m] : 1.f;
-  const bool live = qvalid && w > 0.f;
   const bool head = (col & (G - 1)) == 0;
   float se = 0.f;
+  if constexpr (CW) {
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int o = 16 * t + 4 * quad + i;
-      const float dd = (o < A.O && live) ? s[t][i] - A.target[(size_t)m * A.O + o] : 0.f;
-      const float wd = w * dd;
-      se = head ? fmaf(wd, dd, se) : se;
-      g0[t][i] = (q * wd) * gs;
-    }
+      for (int i = 0; i < 4; ++i) {
+        const int o = 16 * t + 4 * quad + i;
+        const bool in = o < A.O && qvalid;
+        const float w = in ? A.cweight[(size_t)m * A.O + o] : 0.f;
+        const float dd = (in && w > 0.f) ? s[t][i] - A.target[(size_t)m * A.O + o] : 0.f;
+        const float wd = w * dd;
+        se = head ? fmaf(wd, dd, se) : se;
+        g0[t][i] = (q * wd) * gs;
+      }
+  } else {
+    const float w = A.oweight ? A.oweight[m] : 1.f;
+    const bool live = qvalid && w > 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int o = 16 * t + 4 * quad + i;
+        const float dd = (o < A.O && live) ? s[t][i] - A.target[(size_t)m * A.O + o] : 0.f;
+        const float wd = w * dd;
+        se = head ? fmaf(wd, dd, se) : se;
+        g0[t][i] = (q * wd) * gs;
+      }
+  }
   return se;
 }
 // The wave's reduction of `se` in the order it always had (xor 32, 16, 8, 4, 2, 1).  After the first two steps the four quads are
@@ -338,7 +364,7 @@ DEV void tail_loss_add(float se, const TailArgs& A, int qtile) {      // qtile: 
   else atomicAdd(A.loss, se * A.inv_n);          // (one per wave, nobody waits for it; the caller zeroed *loss)
 }
 
-// EVAL (1: unweighted or per-point weights, 2: per-channel weights, 3: grouped observations; never with SAVE): the evaluation tail -- the epilogue forms err and,
+// EVAL (1: unweighted or per-point weights, 2: per-channel weights, 3: grouped observations, 4: grouped with per-value weights; never with SAVE): the evaluation tail -- the epilogue forms err and,
 // with A.loss, the scalar loss from the output accumulators instead of storing `out` (enf_eval_loss): no backward chain, no stash, no
 // `out` in HBM.
 //
@@ -350,7 +376,7 @@ DEV void tail_loss_add(float se, const TailArgs& A, int qtile) {      // qtile: 
 // 12-bit offsets and La2Cnt are those of eight waves) and run nothing else.  The waves with queries run the code below unchanged, so
 // their arithmetic does not depend on AW: the results are bit-equal.
 template <int D, int H, bool BF16, bool LA2, bool SAVE, int EVAL = 0, int AW = NWAVES>
-__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgsFor<EVAL == 3> A) {
+__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgsFor<EVAL == 4 ? 2 : (EVAL == 3 ? 1 : 0)> A) {
   static_assert(!(SAVE && EVAL != 0), "the evaluation tail has no backward to stash for");
   static_assert(AW == NWAVES || (LA2 && (AW == 4 || AW == 2 || AW == 1)), "fewer active waves: small grids, the 3-slot ring");
   using T = TailCfg<D, H, BF16>;
@@ -378,10 +404,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgsFor<E
                          : A.ybar + (size_t)qi * T::HD;
   tail_forward<D, H, BF16, SAVE, LA2, NoPan, NoPan>(o4, yrow, SAVE ? A.act + (size_t)qi * T::ACT : nullptr, A.L,
                                                     cst, P, ring, NO_STAGE, NO_STAGE, lane, quad, A.inv_hd, true, yh);
-  if constexpr (EVAL == 3) {      // grouped observations: err_g per observation, stored by the group's first lane
+  if constexpr (EVAL >= 3) {      // grouped observations: err_g per observation, stored by the group's first lane
     const bool qvalid = q0 + col < A.NQ;
     f32x4 g0[2];       // (dead code, as below)
-    float se = tail_sq_err_g(o4, g0, A, qi, qvalid, col, quad, 0.f);
+    float se = tail_sq_err_g<EVAL == 4>(o4, g0, A, qi, qvalid, col, quad, 0.f);
     se = tail_err_reduce(se, A.err_g, qi >> __builtin_ctz(A.G), qvalid && (col & (A.G - 1)) == 0, quad, A.loss != nullptr);
     if (A.loss && lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
   } else if constexpr (EVAL != 0) {
@@ -412,14 +438,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_fwd_kernel(TailArgsFor<E
 // SEED with RECOMP: the shared-latent fit step's tail in one kernel -- the unit seed does not depend on the loss, so the forward chain
 // (stash as ever, `out` stored where A.out is given) and the seeded backward chain need no launch between them.
 // AW: as in enf_tail_fwd_kernel.
-// GRP (with LOSS, never with CW): the loss against grouped observations (tail_sq_err_g) -- means over G consecutive queries, formed by
+// GRP (with LOSS): the loss against grouped observations (tail_sq_err_g) -- means over G consecutive queries, formed by
 // cross-lane adds in front of the squared error.  An instantiation of its own, one for every G; the other fused-loss kernels keep their code.
+// GRP with CW: one weight per observed value (TailArgsGC), an instantiation of its own again.
 template <int D, int H, bool BF16, bool LA2, bool RECOMP, bool WG = false, bool LOSS = false, bool CW = false, bool SEED = false,
           int AW = NWAVES, bool GRP = false>
-__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgsFor<GRP> A) {
+__global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgsFor<GRP ? (CW ? 2 : 1) : 0> A) {
   static_assert(!LOSS || RECOMP, "the fused loss needs the forward chain's outputs");
   static_assert(!CW || LOSS, "per-channel weights belong to the fused loss");
-  static_assert(!GRP || (LOSS && !CW), "grouped observations are a form of the fused loss; their weights are per observation");
+  static_assert(!GRP || LOSS, "grouped observations are a form of the fused loss (CW: their weights are per value, else per observation)");
   static_assert(!SEED || (!WG && !LOSS), "the seeded backward writes d ybar and delta (and, with the forward chain, out) only");
   static_assert(AW == NWAVES || (LA2 && !WG && (AW == 4 || AW == 2 || AW == 1)), "fewer active waves: small grids, the 3-slot ring");
   using T = TailCfg<D, H, BF16>;
@@ -475,7 +502,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void enf_tail_bwd_kernel(TailArgsFor<G
   // ---- backward chain
   f32x4 g0[2];
   if constexpr (LOSS && GRP) {
-    float se = tail_sq_err_g(o4, g0, A, qi, qvalid, col, quad, 2.0f * A.inv_n * A.gscale);
+    float se = tail_sq_err_g<CW>(o4, g0, A, qi, qvalid, col, quad, 2.0f * A.inv_n * A.gscale);
     se = tail_err_reduce(se, A.err_g, qi >> __builtin_ctz(A.G), qvalid && (col & (A.G - 1)) == 0, quad);
     if (lane == 0) tail_loss_add(se, A, blockIdx.x * AW + wave);
   } else if constexpr (LOSS) {
@@ -636,6 +663,7 @@ enum TailForm {
   TF_BWD, TF_BWD_STASH, TF_WG, TF_WG_STASH,                     // enf_tail_bwd_kernel on d out: recompute / from the stash
   TF_LOSS, TF_LOSS_CW, TF_SEED_STASH, TF_FWD_SEED,              // fused loss; seeded from the stash / behind its own forward chain
   TF_LOSS_G, TF_EVAL_G,                                         // grouped observations: the fused loss and the evaluation tail
+  TF_LOSS_GC, TF_EVAL_GC,                                       // the same with one weight per observed value
   TF_COUNT
 };
 // bwd: enf_tail_bwd_kernel; chain: SAVE of the forward kernel (stash the pre-activations), RECOMP of the backward kernel (run the forward
@@ -656,6 +684,8 @@ constexpr TailFormCfg tail_form_cfg(TailForm f) {
     case TF_SEED_STASH: return {true, false, 0, false, false, false, true, false};
     case TF_LOSS_G: return {true, true, 0, false, true, false, false, true};
     case TF_EVAL_G: return {false, false, 3, false, false, false, false, false};
+    case TF_LOSS_GC: return {true, true, 0, false, true, true, false, true};
+    case TF_EVAL_GC: return {false, false, 4, false, false, false, false, false};
     default: return {true, true, 0, false, false, false, true, false};      // TF_FWD_SEED
   }
 }
@@ -671,10 +701,12 @@ template <int D, int H, bool BF16, TailForm F, bool LA2, int AW> constexpr auto 
   else return enf_tail_fwd_kernel<D, H, BF16, LA2, c.chain, c.eval, AW>;
 }
 template <int D, int H, bool BF16, TailForm F, bool LA2, int AW>
-static int launch_tail_kernel(const TailArgsG& A, dim3 grid, hipStream_t st) {
+static int launch_tail_kernel(const TailArgsGC& A, dim3 grid, hipStream_t st) {
   constexpr auto kern = tail_kernel<D, H, BF16, F, LA2, AW>();
-  // (the kernel's own argument block: the grouped forms take the whole struct, the others its TailArgs part)
-  using Args = TailArgsFor<tail_form_cfg(F).grp || tail_form_cfg(F).eval == 3>;
+  // (the kernel's own argument block: the per-value grouped forms take the whole struct, the grouped forms its TailArgsG part, the others
+  // its TailArgs part)
+  constexpr TailFormCfg c = tail_form_cfg(F);
+  using Args = TailArgsFor<(c.grp && c.cw) || c.eval == 4 ? 2 : (c.grp || c.eval == 3 ? 1 : 0)>;
   constexpr int smem = LA2 ? TailCfg<D, H, BF16>::SMEM3 : TailCfg<D, H, BF16>::SMEM;
   if (!enf_lds_attr<kern>(smem)) return ENF_ELAUNCH;
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, st, static_cast<const Args&>(A));
@@ -682,7 +714,7 @@ static int launch_tail_kernel(const TailArgsG& A, dim3 grid, hipStream_t st) {
 }
 
 template <int D, int H, bool BF16, TailForm F>
-static int launch_tail_form(const TailArgsG& A, hipStream_t st) {
+static int launch_tail_form(const TailArgsGC& A, hipStream_t st) {
   constexpr TailFormCfg c = tail_form_cfg(F);
   // fewer active waves: deterministic mode keeps eight (the partial-sum slots enf_launch_loss_sum reads are those of the 8-wave grid)
   int aw = NWAVES;
@@ -695,8 +727,9 @@ static int launch_tail_form(const TailArgsG& A, hipStream_t st) {
   const bool la2 = grid.x <= 256 || aw < NWAVES;
   if (c.seed && (A.seed < 0 || A.seed >= A.O)) return ENF_EINVAL;
   if ((c.eval || c.loss) && !A.target) return ENF_EINVAL;
-  if ((c.eval == 2 || c.cw) && !A.weight) return ENF_EINVAL;
-  if ((c.eval == 3 || c.grp) && (A.G < 1 || A.G > 16 || (A.G & (A.G - 1)) || A.NQ % A.G)) return ENF_EINVAL;
+  if ((c.eval == 2 || (c.cw && !c.grp)) && !A.weight) return ENF_EINVAL;
+  if ((c.eval == 4 || (c.cw && c.grp)) && !A.cweight) return ENF_EINVAL;
+  if ((c.eval >= 3 || c.grp) && (A.G < 1 || A.G > 16 || (A.G & (A.G - 1)) || A.NQ % A.G)) return ENF_EINVAL;
   // (run-time la2, aw) -> template arguments; the instantiations with fewer active waves run the 3-slot ring only
   if constexpr (tail_form_has_aw(F)) {
     if (aw == 4) return launch_tail_kernel<D, H, BF16, F, true, 4>(A, grid, st);
@@ -707,18 +740,18 @@ static int launch_tail_form(const TailArgsG& A, hipStream_t st) {
 }
 
 // run-time form and shape -> launch_tail_form
-template <class S, int F = 0> static int launch_tail_shape(const TailArgsG& A, TailForm form, hipStream_t st) {
+template <class S, int F = 0> static int launch_tail_shape(const TailArgsGC& A, TailForm form, hipStream_t st) {
   if (form == F) return launch_tail_form<S::D, S::H, S::BF16, (TailForm)F>(A, st);
   if constexpr (F + 1 < TF_COUNT) return launch_tail_shape<S, F + 1>(A, form, st);
   else return ENF_EINVAL;
 }
-static int launch_tail(const EnfDims& m, const TailArgsG& A, TailForm form, hipStream_t st) {
+static int launch_tail(const EnfDims& m, const TailArgsGC& A, TailForm form, hipStream_t st) {
   if (m.OB != 1) return ENF_EUNSUPPORTED;
   return enf_for_shape(m, [&](auto s) { return launch_tail_shape<decltype(s)>(A, form, st); });
 }
 // what every form's arguments share; the entry points below set what differs
-static TailArgsG tail_args(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar) {
-  TailArgsG A{};
+static TailArgsGC tail_args(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar) {
+  TailArgsGC A{};
   A.ybar = ybar; A.blob = blob; A.L = L;
   A.NQ = m.B * m.N; A.O = m.O; A.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
   return A;
@@ -731,7 +764,7 @@ int enf_launch_tail(const EnfDims& m, const EnfLayout& L, const char* blob, cons
 int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out,
                        const float* dout, float* dybar, float* delta, float* act, float* tdel, unsigned flags, hipStream_t st) {
   const bool bwd = flags & ENF_TAIL_BWD, stash = flags & ENF_TAIL_STASH;
-  TailArgsG A = tail_args(m, L, blob, ybar);
+  TailArgsGC A = tail_args(m, L, blob, ybar);
   A.out = out; A.dout = dout; A.dybar = dybar; A.delta = delta; A.act = act; A.tdel = tdel;
   A.ybar_half = (!bwd && (flags & ENF_TAIL_YBAR_HALF) && m.bf16) ? 1 : 0;
   const TailForm form = !bwd ? (stash ? TF_FWD_STASH : TF_FWD) : tdel ? (stash ? TF_WG_STASH : TF_WG) : (stash ? TF_BWD_STASH : TF_BWD);
@@ -740,7 +773,7 @@ int enf_launch_tail_wg(const EnfDims& m, const EnfLayout& L, const char* blob, c
 
 int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, int seed, float* dybar, float* delta,
                          float* act, hipStream_t st) {
-  TailArgsG A = tail_args(m, L, blob, ybar);
+  TailArgsGC A = tail_args(m, L, blob, ybar);
   A.seed = seed; A.dybar = dybar; A.delta = delta; A.act = act;
   return launch_tail(m, A, TF_SEED_STASH, st);
 }
@@ -748,7 +781,7 @@ int enf_launch_tail_seed(const EnfDims& m, const EnfLayout& L, const char* blob,
 // stash followed by enf_launch_tail_seed compute, bit for bit.
 int enf_launch_tail_fwd_seed(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, float* out, int seed, float* dybar,
                              float* delta, float* act, hipStream_t st) {
-  TailArgsG A = tail_args(m, L, blob, ybar);
+  TailArgsGC A = tail_args(m, L, blob, ybar);
   A.out = out; A.seed = seed; A.dybar = dybar; A.delta = delta; A.act = act;
   return launch_tail(m, A, TF_FWD_SEED, st);
 }
@@ -758,7 +791,7 @@ int enf_tail_loss_parts(const EnfDims& m) {
 }
 
 // the fused loss and the evaluation tail: target, weights, the loss and its deterministic partials, the per-point errors
-static int tail_loss_kernel(const EnfDims& m, TailArgsG& A, TailForm form, const float* target, const float* weight, float gscale, float* loss,
+static int tail_loss_kernel(const EnfDims& m, TailArgsGC& A, TailForm form, const float* target, const float* weight, float gscale, float* loss,
                             float* loss_part, float* err, hipStream_t st, int G = 1) {
   // (G: the grouped forms' group size -- the mean is over the B M O observed values, M = N / G)
   A.target = target; A.weight = weight; A.loss = loss; A.gscale = gscale; A.inv_n = 1.0f / ((float)m.B * (float)(m.N / G) * (float)m.O);
@@ -770,14 +803,14 @@ static int tail_loss_kernel(const EnfDims& m, TailArgsG& A, TailForm form, const
 int enf_launch_tail_loss(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part,
                          bool per_value, float* err) {
-  TailArgsG A = tail_args(m, L, blob, ybar);
+  TailArgsGC A = tail_args(m, L, blob, ybar);
   A.dybar = dybar; A.delta = delta; A.act = act;
   return tail_loss_kernel(m, A, per_value ? TF_LOSS_CW : TF_LOSS, target, weight, gscale, loss, loss_part, err, st);
 }
 
 int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target,
                          const float* weight, bool per_value, float* loss, float* err, hipStream_t st, float* loss_part) {
-  TailArgsG A = tail_args(m, L, blob, ybar);
+  TailArgsGC A = tail_args(m, L, blob, ybar);
   return tail_loss_kernel(m, A, per_value ? TF_EVAL_CW : TF_EVAL, target, weight, 0.f, loss, loss ? loss_part : nullptr, err, st);
 }
 
@@ -785,10 +818,12 @@ int enf_launch_tail_eval(const EnfDims& m, const EnfLayout& L, const char* blob,
 int enf_launch_tail_group(const EnfDims& m, const EnfLayout& L, const char* blob, const float* ybar, const float* target, const EnfGroupObs& g,
                           float gscale, float* loss, float* dybar, float* delta, float* act, hipStream_t st, float* loss_part) {
   if (!enf_group_size_ok(g.G) || m.N % g.G) return ENF_EINVAL;
-  TailArgsG A = tail_args(m, L, blob, ybar);
+  TailArgsGC A = tail_args(m, L, blob, ybar);
   A.dybar = dybar; A.delta = delta; A.act = act;
-  A.G = g.G; A.qweight = g.qweight; A.oweight = g.oweight; A.err_g = g.err_g;
-  return tail_loss_kernel(m, A, dybar ? TF_LOSS_G : TF_EVAL_G, target, nullptr, gscale, loss, loss ? loss_part : nullptr, nullptr, st, g.G);
+  A.G = g.G; A.qweight = g.qweight; A.oweight = g.oweight; A.err_g = g.err_g; A.cweight = g.cweight;
+  // (per-value weights: the forms of their own; without them the calls run the instantiations they always ran)
+  const TailForm form = g.cweight ? (dybar ? TF_LOSS_GC : TF_EVAL_GC) : (dybar ? TF_LOSS_G : TF_EVAL_G);
+  return tail_loss_kernel(m, A, form, target, nullptr, gscale, loss, loss ? loss_part : nullptr, nullptr, st, g.G);
 }
 
 #ifdef ENF_TEST_HOOKS

@@ -885,10 +885,13 @@ class EquivariantCrossAttentionNeF:
     # ------------------------------------------------------------------ grouped observations (cell averages)
     GROUP_SIZES = (1, 2, 4, 8, 16)
 
-    def _cell_args(self, what, x, p, a, target, group, qweight, obs_weight):
+    def _cell_args(self, what, x, p, a, target, group, qweight, obs_weight, obs_channel_weight=None):
         """The shapes of a grouped call, checked before anything touches the device: x (B, N, dx) with N = M * group, target
-        (B, M, O) -- None for a call that takes none (``gn_cell_product``) --, qweight (B, N) or None, obs_weight (B, M) or None.
+        (B, M, O) -- None for a call that takes none (``gn_cell_product``) --, qweight (B, N) or None, obs_weight (B, M) or None,
+        obs_channel_weight (B, M, O) or None (never together with obs_weight).
         Returns (B, Z, N, M)."""
+        if obs_weight is not None and obs_channel_weight is not None:
+            raise ValueError(f"{what}: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
         if self.num_layers > 0:
             raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
         if int(group) not in self.GROUP_SIZES:
@@ -907,13 +910,15 @@ class EquivariantCrossAttentionNeF:
             raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
         if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
             raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
+        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, M, self.num_out):
+            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, M, self.num_out)}")
         if not (x.is_cuda and p.is_cuda and a.is_cuda and (target is None or target.is_cuda)):
             raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
         return B, Z, N, M
 
     @torch.no_grad()
     def mse_value_and_cell_grads(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None,
-                                 grad_scale=1.0, loss_out=None, return_errors=False, shared_latents=False):
+                                 grad_scale=1.0, loss_out=None, return_errors=False, shared_latents=False, obs_channel_weight=None):
         """The fit step against GROUPED observations (include/enf_hip.h, "Grouped observations": enf_fit_step_g): observation m of a
         signal is obs[m] = sum_k qweight[m group + k] out[m group + k] over the ``group`` consecutive query rows it owns -- a quadrature
         rule over a cell (fitting/cells.py: cell_quadrature) -- and
@@ -927,8 +932,13 @@ class EquivariantCrossAttentionNeF:
         over the signals with stride 0 and that the rows of ``qweight`` are equal -- the first inner step of a fit on shared cells.  The
         call then goes to enf_fit_step_gs with ENF_FIT_SHARED_LATENTS: one forward for all signals and, where the library's rule holds,
         one backward.  Without it the call is enf_fit_step_g, as before.
+        ``obs_channel_weight``: (B, M, O), finite and >= 0, one weight per observed VALUE in place of ``obs_weight`` (both: ValueError)
+        -- loss = sum_{b,m,o} cw (obs - target)^2 / (B M O), err_g = sum_o cw (obs - target)^2, the zero-weight rule per value
+        (enf_fit_step_gc).  With ``shared_latents`` it is NotImplementedError.
         Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err_g, loss_b)."""
-        B, Z, N, M = self._cell_args("mse_value_and_cell_grads", x, p, a, target, group, qweight, obs_weight)
+        if shared_latents and obs_channel_weight is not None:
+            raise NotImplementedError("mse_value_and_cell_grads: shared_latents with obs_channel_weight is not built; run the step unshared")
+        B, Z, N, M = self._cell_args("mse_value_and_cell_grads", x, p, a, target, group, qweight, obs_weight, obs_channel_weight)
         sigma = gaussian_window_size if self.use_gaussian_window else None
         if self.use_gaussian_window and sigma is None:
             raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
@@ -947,6 +957,8 @@ class EquivariantCrossAttentionNeF:
         err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
         loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
         fn, flags = (lib.enf_fit_step_gs, self._det_flag() | _lib.ENF_FIT_SHARED_LATENTS) if shared_latents else (lib.enf_fit_step_g, self._det_flag())
+        if obs_channel_weight is not None:
+            fn, w_ = lib.enf_fit_step_gc, obs_channel_weight.float().contiguous()
         _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
                     int(group), _ptr(q_), _ptr(w_), float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(err), _ptr(loss_b),
                     _ptr(ws), ws.numel(), flags, st)
@@ -956,12 +968,13 @@ class EquivariantCrossAttentionNeF:
 
     @torch.no_grad()
     def eval_cell_loss(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None, loss_out=None,
-                       per_signal=True):
+                       per_signal=True, obs_channel_weight=None):
         """Evaluation against grouped observations without a decode (include/enf_hip.h: enf_eval_loss_g): err_g (B, M) and loss_b (B,)
         as mse_value_and_cell_grads(return_errors=True) gives them at the same point -- the same bits, in every mode.  ``loss_out``: an
         already ZEROED float32 (1,) tensor; the scalar loss is added to it.  ``per_signal`` False skips loss_b.
+        ``obs_channel_weight``: (B, M, O) in place of ``obs_weight``, as in mse_value_and_cell_grads (enf_eval_loss_gc).
         Returns (loss_b or None, err_g)."""
-        B, Z, N, M = self._cell_args("eval_cell_loss", x, p, a, target, group, qweight, obs_weight)
+        B, Z, N, M = self._cell_args("eval_cell_loss", x, p, a, target, group, qweight, obs_weight, obs_channel_weight)
         sigma = gaussian_window_size if self.use_gaussian_window else None
         if self.use_gaussian_window and sigma is None:
             raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
@@ -976,7 +989,10 @@ class EquivariantCrossAttentionNeF:
         w_ = obs_weight.float().contiguous() if obs_weight is not None else None
         err = torch.empty((B, M), device=dev, dtype=torch.float32)
         loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
-        _lib.launch(dev, lib.enf_eval_loss_g, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+        fn = lib.enf_eval_loss_g
+        if obs_channel_weight is not None:
+            fn, w_ = lib.enf_eval_loss_gc, obs_channel_weight.float().contiguous()
+        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
                     int(group), _ptr(q_), _ptr(w_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
         self._ws_touch(ws)
         return loss_b, err
@@ -1014,13 +1030,29 @@ class EquivariantCrossAttentionNeF:
         self._ws_touch(ws)
         return gp, ga, (gs if s_ is not None else None)
 
-    def cell_mse(self, out, target, group, qweight=None, obs_weight=None):
+    def cell_fit_loss(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None, obs_channel_weight=None):
+        """The grouped loss of the decode of latents as a function of the LATENTS, without a decode in memory and with the decoder's
+        weights frozen: a torch.autograd.Function around mse_value_and_cell_grads.  The forward makes one enf_fit_step_g / _gc call
+        (loss and d loss / d (p, a, window) at grad_scale 1); the backward multiplies the stored gradients by the incoming scalar.
+        Differentiable once, with respect to ``p``, ``a`` and ``gaussian_window_size`` only -- ``params`` get no gradient (take
+        apply + cell_mse where they need one).  Arguments as mse_value_and_cell_grads.  Returns the loss, a 0-d tensor."""
+        self._cell_args("cell_fit_loss", x, p, a, target, group, qweight, obs_weight, obs_channel_weight)
+        if self.use_gaussian_window and gaussian_window_size is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        win = gaussian_window_size if self.use_gaussian_window else None
+        return _CellFitLossFunction.apply(self, params, x, p, a, win, target, int(group), qweight, obs_weight, obs_channel_weight)
+
+    def cell_mse(self, out, target, group, qweight=None, obs_weight=None, obs_channel_weight=None):
         """The grouped loss of a decode that exists in memory (include/enf_hip.h: enf_mse_value_grad_g), for the weight-gradient path:
             loss = sum_{b,m} obs_weight[b,m] sum_o (obs - target)^2 / (B M O),    obs[b,m] = sum_k qweight[b, m group + k] out[b, m group + k]
         with out (B, N, O), target (B, M, O), M = N / group; ``qweight`` (B, N) or None for 1 / group, ``obs_weight`` (B, M) or None for 1
         (an observation of weight 0 does not exist, its target may be NaN).  A torch.autograd.Function: loss and d out come from ONE
         kernel, the backward multiplies d out by the incoming scalar.  Differentiable once, and only with respect to ``out``.
+        ``obs_channel_weight``: (B, M, O) in place of ``obs_weight`` (both: ValueError), one weight per observed value
+        (enf_mse_value_grad_gc): loss = sum_{b,m,o} cw (obs - target)^2 / (B M O).
         Returns the loss, a 0-d tensor."""
+        if obs_weight is not None and obs_channel_weight is not None:
+            raise ValueError("cell_mse: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
         if int(group) not in self.GROUP_SIZES:
             raise ValueError(f"group must be one of {self.GROUP_SIZES}, got {group}")
         if out.dim() != 3 or out.shape[1] % int(group):
@@ -1033,16 +1065,19 @@ class EquivariantCrossAttentionNeF:
             raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
         if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
             raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
+        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, M, O):
+            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, M, O)}")
         if not (out.is_cuda and target.is_cuda):
             raise _lib.EnfError("EquivariantCrossAttentionNeF.cell_mse needs CUDA/HIP tensors: there is no CPU path")
-        return _CellMseFunction.apply(out, target, int(group), qweight, obs_weight, self._det_flag())
+        return _CellMseFunction.apply(out, target, int(group), qweight, obs_weight, self._det_flag(), obs_channel_weight)
 
 
 class _CellMseFunction(torch.autograd.Function):
-    """nef.cell_mse: enf_mse_value_grad_g once in the forward (loss and d out at grad_scale 1); the backward scales the stored d out."""
+    """nef.cell_mse: enf_mse_value_grad_g (with obs_channel_weight: _gc) once in the forward (loss and d out at grad_scale 1); the
+    backward scales the stored d out."""
 
     @staticmethod
-    def forward(ctx, out, target, group, qweight, obs_weight, det):
+    def forward(ctx, out, target, group, qweight, obs_weight, det, obs_channel_weight=None):
         lib = _lib.load()
         dev = out.device
         o_ = out.detach().float().contiguous()
@@ -1055,7 +1090,10 @@ class _CellMseFunction(torch.autograd.Function):
         loss = torch.zeros(1, device=dev, dtype=torch.float32)
         nscr = int(lib.enf_mse_scratch_bytes(B * (N // group) * O, det))
         scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr else None
-        _lib.launch(dev, lib.enf_mse_value_grad_g, _ptr(o_), _ptr(t_), B, N, O, group, _ptr(q_), _ptr(w_), 1.0, _ptr(dout), _ptr(loss), None,
+        fn = lib.enf_mse_value_grad_g
+        if obs_channel_weight is not None:
+            fn, w_ = lib.enf_mse_value_grad_gc, obs_channel_weight.detach().float().contiguous()
+        _lib.launch(dev, fn, _ptr(o_), _ptr(t_), B, N, O, group, _ptr(q_), _ptr(w_), 1.0, _ptr(dout), _ptr(loss), None,
                     _ptr(scr), nscr, det, _lib.stream(dev))
         if need:
             ctx.save_for_backward(dout)
@@ -1066,4 +1104,29 @@ class _CellMseFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         (dout,) = ctx.saved_tensors
-        return (dout * g).to(ctx.out_dtype), None, None, None, None, None
+        return (dout * g).to(ctx.out_dtype), None, None, None, None, None, None
+
+
+class _CellFitLossFunction(torch.autograd.Function):
+    """nef.cell_fit_loss: one mse_value_and_cell_grads in the forward; the backward scales its dp, da, dwindow."""
+
+    @staticmethod
+    def forward(ctx, nef, params, x, p, a, window, target, group, qweight, obs_weight, obs_channel_weight):
+        det = lambda t: t.detach() if t is not None else None
+        loss, dp, da, dsig = nef.mse_value_and_cell_grads(params, x.detach(), p.detach(), a.detach(), det(window), target.detach(), group,
+                                                          qweight=det(qweight), obs_weight=det(obs_weight),
+                                                          obs_channel_weight=det(obs_channel_weight))
+        ctx.save_for_backward(dp, da, dsig if dsig is not None else dp.new_zeros(()))
+        ctx.has_window = dsig is not None
+        ctx.shapes = (p.shape, a.shape, None if window is None else window.shape)
+        ctx.dtypes = (p.dtype, a.dtype, None if window is None else window.dtype)
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        dp, da, dsig = ctx.saved_tensors
+        gp = (dp * g).reshape(ctx.shapes[0]).to(ctx.dtypes[0]) if ctx.needs_input_grad[3] else None
+        ga = (da * g).reshape(ctx.shapes[1]).to(ctx.dtypes[1]) if ctx.needs_input_grad[4] else None
+        gw = (dsig * g).reshape(ctx.shapes[2]).to(ctx.dtypes[2]) if ctx.has_window and ctx.needs_input_grad[5] else None
+        return None, None, None, gp, ga, gw, None, None, None, None, None

@@ -18,6 +18,23 @@ from .inner_loop import FUSED_FIT_INPUTS, _pose, _shared_kw, meta_sgd_update, no
 GROUP_SIZES = (1, 2, 4, 8, 16)
 
 
+def check_cells(cells, num_cells):
+    """What every step takes as ``cells=``: (x (M G, dx), q (M G,) or None, group) with group a size the fused tail serves and
+    M = ``num_cells``, the cells the data hold.  Returns (x, q, int(group)); ValueError otherwise."""
+    if int(cells[2]) not in GROUP_SIZES:
+        raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
+    if cells[0].dim() != 2 or cells[0].shape[0] != num_cells * int(cells[2]):
+        raise ValueError(f"cells hold {tuple(cells[0].shape)} quadrature points, img {num_cells} cells of {int(cells[2])}")
+    if cells[1] is not None and tuple(cells[1].shape) != (cells[0].shape[0],):
+        raise ValueError(f"cells hold {cells[0].shape[0]} quadrature points and factors of shape {tuple(cells[1].shape)}")
+    return cells[0], cells[1], int(cells[2])
+
+
+def cell_weight_kw(ws, channel):
+    """The keyword nef.mse_value_and_cell_grads, nef.eval_cell_loss, nef.cell_mse and nef.cell_fit_loss take sampled weights by."""
+    return {} if ws is None else {"obs_channel_weight" if channel else "obs_weight": ws}
+
+
 def _rule_1d(k, rule):
     """Nodes in (-1, 1) and weights that sum to 1 of a k-point rule on the reference interval."""
     if k < 1:
@@ -118,8 +135,18 @@ def draw_cell_samples(num_cells, sample, steps, generator=None):
     return torch.stack([torch.randperm(int(num_cells), generator=generator, device=dev)[:int(sample)] for _ in range(int(steps) + 1)])
 
 
+def _one_weight_kind(what, obs_weight, obs_channel_weight, shape):
+    """Both weight kinds at once is a ValueError; the per-value weights are (B, M, O)."""
+    if obs_channel_weight is None:
+        return
+    if obs_weight is not None:
+        raise ValueError(f"{what}: pass one weight per observation or obs_channel_weight (one per value), not both")
+    if tuple(obs_channel_weight.shape) != tuple(shape):
+        raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {tuple(shape)}")
+
+
 def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, obs_weight=None, sample=None, generator=None,
-                      optimize_gaussian_window=False, per_signal_loss=False):
+                      optimize_gaussian_window=False, per_signal_loss=False, obs_channel_weight=None):
     """Fit per-signal latents to cell averages with `steps` steps of the inner loop's meta-SGD rule (inner_loop: meta_sgd_update on the
     gradient of the batch-mean loss times B, so that the signals are independent).
 
@@ -127,7 +154,8 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
     x, q     : the quadrature points (N, dx) and factors (N,) of the M = N / group cells (cell_quadrature), shared by the signals;
                q None is the plain mean, 1 / group
     targets  : (B, M, O) observed cell averages;  obs_weight: None or (B, M), finite and >= 0 -- an observation of weight 0 does not
-               exist and its target may be NaN
+               exist and its target may be NaN;  obs_channel_weight: None or (B, M, O), one weight per observed value in its place (both:
+               ValueError), the zero-weight rule per value
     sample   : None (every step sees all M observations), an int (every step and the final loss draw a fresh set of that many
                observations, draw_cell_samples with ``generator``), or the index tensor (steps + 1, M_s) itself.  The points,
                factors, targets and weights of all steps are gathered once, in torch ops.
@@ -146,6 +174,11 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
         raise ValueError(f"q has shape {tuple(q.shape)}, expected {(M * G,)}")
     if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
         raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
+    _one_weight_kind("fit_cell_averages", obs_weight, obs_channel_weight, (B, M, O))
+    per_value = obs_channel_weight is not None
+    wkey = "obs_channel_weight" if per_value else "obs_weight"
+    if per_value:
+        obs_weight = obs_channel_weight
     dev = targets.device
     tg = targets.float()
     if sample is None:
@@ -171,10 +204,10 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
         xb, qb = _batched(xs.to(dev), None if qs is None else qs.to(dev), B)
         args = (params, xb, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys, G)
         if s == S:
-            lb, _ = nef.eval_cell_loss(*args, qweight=qb, obs_weight=ws, loss_out=losses[S:], per_signal=per_signal_loss)
+            lb, _ = nef.eval_cell_loss(*args, qweight=qb, loss_out=losses[S:], per_signal=per_signal_loss, **{wkey: ws})
             rows_b.append(lb)
             break
-        res = nef.mse_value_and_cell_grads(*args, qweight=qb, obs_weight=ws, loss_out=losses[s:s + 1], return_errors=per_signal_loss)
+        res = nef.mse_value_and_cell_grads(*args, qweight=qb, loss_out=losses[s:s + 1], return_errors=per_signal_loss, **{wkey: ws})
         _, dp, da, dsig = res[:4]
         if per_signal_loss:
             rows_b.append(res[5])
@@ -189,14 +222,16 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
     return losses[S], lat
 
 
-def gather_cell_samples(x, q, group, obs, masks, obs_weight=None):
+def gather_cell_samples(x, q, group, obs, masks, obs_weight=None, obs_channel_weight=None):
     """What enf_fit_inputs_g gathers, in torch ops: x (M G, dx) quadrature points, q (M G,) factors or None, obs (B, M, O), masks long
     cell indices (Ms, S1) shared by the signals or (B, Ms, S1) per signal, obs_weight (B, M) or None
     -> xs (S1, Ms G, dx) | (S1, B, Ms G, dx), qs alike without the last axis (None without q), ys (S1, B, Ms, O), ws (S1, B, Ms).
     Row i G + k of a sampled set is row m G + k of cell m.  An index outside [0, M) gives cell 0's points and factors, zero targets and
-    weight 0; ws is None on shared masks without ``obs_weight`` and 1 / 0 on per-signal masks without it."""
+    weight 0; ws is None on shared masks without ``obs_weight`` and 1 / 0 on per-signal masks without it.
+    ``obs_channel_weight`` (B, M, O) in place of ``obs_weight`` (enf_fit_inputs_gc): ws is (S1, B, Ms, O), O zeros for an index outside."""
     G = int(group)
     B, M, O = obs.shape
+    _one_weight_kind("gather_cell_samples", obs_weight, obs_channel_weight, (B, M, O))
     S1 = masks.shape[-1]
     per_signal = masks.dim() == 3
     idx = masks.permute(2, 0, 1) if per_signal else masks.t()                        # (S1, B, Ms) | (S1, Ms)
@@ -208,6 +243,9 @@ def gather_cell_samples(x, q, group, obs, masks, obs_weight=None):
     icb, okb = (ic, ok) if per_signal else (ic[:, None].expand(-1, B, -1), ok[:, None].expand(-1, B, -1))
     ys = torch.gather(obs[None].expand(S1, -1, -1, -1), 2, icb[..., None].expand(-1, -1, -1, O)).float()
     ys = torch.where(okb[..., None], ys, torch.zeros_like(ys)).contiguous()
+    if obs_channel_weight is not None:
+        w = torch.gather(obs_channel_weight[None].expand(S1, -1, -1, -1), 2, icb[..., None].expand(-1, -1, -1, O)).float()
+        return xs, qs, ys, torch.where(okb[..., None], w, torch.zeros_like(w)).contiguous()
     if obs_weight is None and not per_signal:
         return xs, qs, ys, None
     w = torch.gather(obs_weight[None].expand(S1, -1, -1), 2, icb).float() if obs_weight is not None else \
@@ -215,25 +253,28 @@ def gather_cell_samples(x, q, group, obs, masks, obs_weight=None):
     return xs, qs, ys, torch.where(okb, w, torch.zeros_like(w)).contiguous()
 
 
-def cell_mse_torch(out, target, group, qweight=None, obs_weight=None):
+def cell_mse_torch(out, target, group, qweight=None, obs_weight=None, obs_channel_weight=None):
     """The grouped loss in torch ops, differentiable by autograd -- the mirror of nef.cell_mse (enf_mse_value_grad_g):
     sum_{b,m} w[b,m] sum_o (obs - target)^2 / (B M O) with obs = sum_k q out over each group; w == 0 is a select, so that
-    observation's target may be NaN and its share of the loss and of d out is zero."""
+    observation's target may be NaN and its share of the loss and of d out is zero.
+    ``obs_channel_weight`` (B, M, O) in place of ``obs_weight`` (both: ValueError): one weight, and one select, per observed value."""
     G = int(group)
     B, N, O = out.shape
     M = N // G
+    _one_weight_kind("cell_mse_torch", obs_weight, obs_channel_weight, (B, M, O))
     q = torch.full((B, N), 1.0 / G, device=out.device, dtype=out.dtype) if qweight is None else qweight.to(out.dtype)
     w = torch.ones((B, M), device=out.device, dtype=out.dtype) if obs_weight is None else obs_weight.to(out.dtype)
     obs = (q[..., None] * out).reshape(B, M, G, O).sum(2)
-    live = (w > 0)[..., None]
+    w = w[..., None] if obs_channel_weight is None else obs_channel_weight.to(out.dtype)
+    live = (w > 0).expand(B, M, O)
     dd = torch.where(live, obs - torch.where(live, target.to(out.dtype), torch.zeros_like(obs)), torch.zeros_like(obs))
-    return (w[..., None] * dd * dd).sum() / (B * M * O)
+    return (w * dd * dd).sum() / (B * M * O)
 
 
-def _cell_inputs(latents0, x, q, group, obs, masks, obs_weight):
+def _cell_inputs(latents0, x, q, group, obs, masks, obs_weight, per_value=False):
     """enf_fit_inputs_g (include/enf_hip.h): (lat, xs_all, qs_all, ys_all, losses, ws_all) of inner_loop_cells in one launch, or None
     where the arguments are not what the kernel takes (fp32, contiguous, on one GPU, long masks, at most four latent components of
-    leading dimension 1)."""
+    leading dimension 1).  ``per_value``: obs_weight is (B, M, O) and the launch is enf_fit_inputs_gc, ws_all (S1, B, Ms, O)."""
     ts = list(latents0.values()) + [x, obs] + [t for t in (q, obs_weight) if t is not None]
     if not (obs.is_cuda and masks.is_cuda and masks.dtype == torch.int64 and masks.dim() in (2, 3) and masks.is_contiguous() and x.dim() == 2
             and obs.dim() == 3 and 1 <= len(latents0) <= _lib.ENF_SGD_MAX_SEGMENTS and masks.shape[0] > 0
@@ -254,7 +295,7 @@ def _cell_inputs(latents0, x, q, group, obs, masks, obs_weight):
     xs = torch.empty(lead + (dx,), device=dev, dtype=torch.float32)
     qs = torch.empty(lead, device=dev, dtype=torch.float32) if q is not None else None
     ys = torch.empty((S1, B, Ms, O), device=dev, dtype=torch.float32)
-    ws = torch.empty((S1, B, Ms), device=dev, dtype=torch.float32) if obs_weight is not None or per_signal else None
+    ws = torch.empty((S1, B, Ms) + ((O,) if per_value else ()), device=dev, dtype=torch.float32) if obs_weight is not None or per_signal else None
     losses = torch.empty(S1, device=dev, dtype=torch.float32)
     comps = (_lib.EnfFitComponent * _lib.ENF_SGD_MAX_SEGMENTS)()
     keep = []
@@ -262,14 +303,15 @@ def _cell_inputs(latents0, x, q, group, obs, masks, obs_weight):
         src = v.detach()
         keep.append(src)
         comps[i] = _lib.EnfFitComponent(src.data_ptr(), lat[k].data_ptr(), v.shape[2], 0)
-    _lib.launch(dev, _lib.load().enf_fit_inputs_g, len(latents0), comps, B, Z, M, Ms, S1, G, dx, O, _lib.ptr(x), _lib.ptr(q), _lib.ptr(obs),
+    fn = _lib.load().enf_fit_inputs_gc if per_value else _lib.load().enf_fit_inputs_g
+    _lib.launch(dev, fn, len(latents0), comps, B, Z, M, Ms, S1, G, dx, O, _lib.ptr(x), _lib.ptr(q), _lib.ptr(obs),
                 _lib.ptr(masks), _lib.ptr(xs), _lib.ptr(qs), _lib.ptr(ys), _lib.ptr(losses), _lib.ptr(obs_weight), _lib.ptr(ws),
                 1 if per_signal else 0, _lib.stream(dev))
     return lat, xs, qs, ys, losses, ws
 
 
 def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks, obs_weights=None, optimize_gaussian_window=False,
-                     noise_pos=0.0, generator=None, normalize_weights=False, per_signal_loss=False):
+                     noise_pos=0.0, generator=None, normalize_weights=False, per_signal_loss=False, obs_channel_weight=None):
     """inner_loop on cell averages: fit per-signal latents with S steps of meta-SGD, every step against a sampled set of cells.
 
     x, q     : the quadrature points (M G, dx) and factors (M G,) of the M cells (cell_quadrature), shared by the signals; q None is
@@ -281,6 +323,8 @@ def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks
     accumulators come from ONE launch (enf_fit_inputs_g), or from gather_cell_samples where the tensors are not what the kernel takes.
     Each step is one nef.mse_value_and_cell_grads -- step 0 with the shared-latent hint under the conditions of inner_loop (shared masks,
     no pose noise, not deterministic, a decoder that knows the keyword) -- and the final loss is nef.eval_cell_loss, without a decode.
+    obs_channel_weight : None or (B, M, O), one weight per observed value in place of obs_weights (both: ValueError); the gather is
+               enf_fit_inputs_gc, every step enf_fit_step_gc and runs unshared (no shared-latent hint at step 0)
     normalize_weights, noise_pos, optimize_gaussian_window, per_signal_loss and the return values are inner_loop's."""
     G = int(group)
     if G not in GROUP_SIZES:
@@ -292,23 +336,29 @@ def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks
         raise ValueError(f"q has shape {tuple(q.shape)}, expected {(M * G,)}")
     if obs_weights is not None and tuple(obs_weights.shape) != (B, M):
         raise ValueError(f"obs_weights have shape {tuple(obs_weights.shape)}, expected {(B, M)}")
+    _one_weight_kind("inner_loop_cells", obs_weights, obs_channel_weight, (B, M, O))
+    per_value = obs_channel_weight is not None
+    wkey = "obs_channel_weight" if per_value else "obs_weight"
+    if per_value:
+        obs_weights = obs_channel_weight
     per_signal = masks.dim() == 3
     if masks.dim() not in (2, 3) or (per_signal and masks.shape[0] != B):
         raise ValueError(f"masks have shape {tuple(masks.shape)}, expected (Ms, S + 1) or ({B}, Ms, S + 1)")
     S = masks.shape[-1] - 1
     dev = targets.device
     w_full = obs_weights.to(device=dev, dtype=torch.float32).contiguous() if obs_weights is not None else None
-    fused = _cell_inputs(latents0, x, q, G, targets, masks, w_full) if FUSED_FIT_INPUTS else None
+    fused = _cell_inputs(latents0, x, q, G, targets, masks, w_full, per_value) if FUSED_FIT_INPUTS else None
     if fused is not None:
         lat, xs_all, qs_all, ys_all, losses, ws_all = fused
     else:
         lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
         losses = torch.zeros(S + 1, device=dev, dtype=torch.float32)
-        xs_all, qs_all, ys_all, ws_all = gather_cell_samples(x.to(dev), None if q is None else q.to(dev), G, targets, masks.to(dev), w_full)
+        xs_all, qs_all, ys_all, ws_all = gather_cell_samples(x.to(dev), None if q is None else q.to(dev), G, targets, masks.to(dev),
+                                                             **{wkey: w_full})
     if normalize_weights:
         if ws_all is None:
             raise ValueError("normalize_weights needs sampled weights: pass obs_weights= or per-signal masks")
-        ws_all = normalize_sampled_weights(ws_all)
+        ws_all = normalize_sampled_weights(ws_all, channel=per_value)
     if noise_pos:
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator, device="cpu").to(lat["p_pos"].device) * noise_pos
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
@@ -324,8 +374,9 @@ def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks
     for s in range(S):
         xs, qs, ws = sampled(s)
         res = nef.mse_value_and_cell_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[s], G, qweight=qs,
-                                           obs_weight=ws, loss_out=losses[s:s + 1], **({"return_errors": True} if per_signal_loss else {}),
-                                           **_shared_kw(nef, s, per_signal, noise_pos, step="mse_value_and_cell_grads"))
+                                           loss_out=losses[s:s + 1], **({"return_errors": True} if per_signal_loss else {}),
+                                           **({"obs_channel_weight": ws} if per_value else
+                                              dict(obs_weight=ws, **_shared_kw(nef, s, per_signal, noise_pos, step="mse_value_and_cell_grads"))))
         _, dp, da, dsig = res[:4]
         if per_signal_loss:
             rows.append(res[5])
@@ -336,8 +387,8 @@ def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks
             grads["gaussian_window"] = dsig
         lat = meta_sgd_update(lat, grads, lrs, B)
     xs, qs, ws = sampled(S)
-    lb, _ = nef.eval_cell_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], G, qweight=qs, obs_weight=ws,
-                               loss_out=losses[S:], per_signal=per_signal_loss)
+    lb, _ = nef.eval_cell_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], G, qweight=qs,
+                               loss_out=losses[S:], per_signal=per_signal_loss, **{wkey: ws})
     if per_signal_loss:
         rows.append(lb)
         return losses[S], lat, torch.stack(rows)

@@ -31,9 +31,9 @@ from ..optim import Adam, AdamW, clip_by_global_norm, global_norm, scatter_rows,
 from ..parallel import allreduce_mean_
 from ..inner_loop import decode, make_signal_masks, gather_signal_points
 from ..weights import LossWeights, cut_frames, nef_kw, weighted_mse
-from ..cells import GROUP_SIZES, _batched, gather_cell_samples
-from .latent_ode import LatentODEMixin, _leaves, _unflatten
-from .pde_trainer import _tree_from_tensors
+from ..cells import GROUP_SIZES, _batched, cell_weight_kw, gather_cell_samples
+from .latent_ode import LatentODEMixin, cell_loss_weights, _leaves, _unflatten
+from .pde_trainer import _NO_CHANNEL_WEIGHTS_ON_CELLS, _cell_kw, _tree_from_tensors
 
 TRAIN_FRAMES, VAL_FRAMES = 10, 20            # fixed in the reference (:206,241,252), not read from the dataset config
 
@@ -126,12 +126,13 @@ class NonMetaPDETrainer(LatentODEMixin):
             img, coords, lw = img[:, sub], coords[sub], lw and lw.points(sub)
         return img, coords, lw, xs
 
-    def _fit_cells(self, state, obs, mask, weights, normalize, cells):
+    def _fit_cells(self, state, obs, mask, weights, normalize, cells, cell_channel_weights=None):
         """_fit_points on cell averages: ``cells`` = (x (M G, dx), q (M G,) or None, group), ``obs`` (B, M, O) cell means, ``mask``
         and ``weights`` (M,) / (B, M) per observation.  Returns (targets (B, m, O), xs (B, m G, dx), qs (B, m G) or None, ws (B, m) or
         None, group): at most max(1, max_num_sampled_points // group) cells, one subset for the batch (a stride-0 xs) or, with
         ``sample_observed`` and weights, every signal's own observed cells with the weights rescaled for that draw.  The one place
-        where a step on cells draws from ``state.rng``."""
+        where a step on cells draws from ``state.rng``.  ``cell_channel_weights`` (M, O) / (B, M, O) in place of ``weights``: one
+        weight per observed value, ws (B, m, O); a cell is observed where any of its values is."""
         x, q, G = cells[0], cells[1], int(cells[2])
         if G not in GROUP_SIZES:
             raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
@@ -139,7 +140,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         B, M, O = img.shape
         if x.dim() != 2 or x.shape[0] != M * G:
             raise ValueError(f"cells hold {tuple(x.shape)} quadrature points, the batch {M} cells of {G}")
-        lw = LossWeights.build(weights, None, B, M, O, normalize=normalize, device=img.device)
+        lw = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=img.device)
         pick = None
         if mask is not None:
             pick = torch.as_tensor(mask, device=img.device)
@@ -151,7 +152,7 @@ class NonMetaPDETrainer(LatentODEMixin):
                 keep[pick] = True
                 lw = lw.keep(keep[None].expand(B, -1))
             m = make_signal_masks(lw.support(), min(n, M), 0, generator=state.rng, device=img.device)
-            xs, qs, ys, ws = gather_cell_samples(x, q, G, img, m, lw.drawn_on(m).w)
+            xs, qs, ys, ws = gather_cell_samples(x, q, G, img, m, **cell_weight_kw(lw.drawn_on(m).w, lw.channel))
             return ys[0].to(img.dtype), xs[0], None if qs is None else qs[0], ws[0], G
         if pick is None and n < M:
             pick = torch.arange(M, device=img.device)
@@ -163,7 +164,8 @@ class NonMetaPDETrainer(LatentODEMixin):
         xs, qs = _batched(x, q, B)
         return img, xs, qs, None if lw is None else lw.w, G
 
-    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None, cells=None):
+    def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None, cells=None,
+                       cell_channel_weights=None):
         """(recon_loss, grads['nef'] as 46 tensors, grads['autodecoder'] as dense tensors like the latent table).
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (fitting/weights.py), normalised to mean 1 per signal
         before ``mask`` and the point sampling unless ``normalize`` is False.
@@ -171,11 +173,14 @@ class NonMetaPDETrainer(LatentODEMixin):
         ``normalize`` is False), for fields whose variables are observed separately; not together with ``weights``.
         ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``initial_state`` holds (B, M, O) cell means, ``mask`` and
         ``weights`` are per observation (_fit_cells), and the loss is the grouped one (nef.cell_mse) of the decode at the sampled
-        cells' quadrature points.  ``channel_weights`` with ``cells`` is a ValueError."""
+        cells' quadrature points.  ``channel_weights`` with ``cells`` is a ValueError; ``cell_channel_weights`` (M, O) / (B, M, O) are
+        the weights per observed value of the cells (not together with ``weights``)."""
         if cells is not None:
             if channel_weights is not None:
-                raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
-            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells)
+                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
+            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells, cell_channel_weights)
+        elif cell_channel_weights is not None:
+            raise ValueError("cell_channel_weights= goes with cells=")
         else:
             img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
@@ -187,7 +192,7 @@ class NonMetaPDETrainer(LatentODEMixin):
             xs = coords[None].expand(img.shape[0], -1, -1)
         out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
         if cells is not None:
-            loss = self.nef.cell_mse(out, img, G, qs, ws)
+            loss = self.nef.cell_mse(out, img, G, qs, **_cell_kw(ws))
         else:
             loss = ((out - img) ** 2).mean() if lw is None else weighted_mse(out, img, lw.w)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)
@@ -195,9 +200,9 @@ class NonMetaPDETrainer(LatentODEMixin):
         ga = [torch.zeros_like(leaves[k]) if gi is None else gi for k, gi in zip(names, g[len(w):])]
         return loss.detach(), gw, dict(zip(names, ga))
 
-    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True, channel_weights=None, cells=None):
+    def _step(self, state, batch, mask, update_nef, weights=None, normalize=True, channel_weights=None, cells=None, cell_channel_weights=None):
         initial_state, traj_idx = batch
-        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize, channel_weights, cells)
+        loss, gw, ga = self.loss_and_grads(state, initial_state, traj_idx, mask, weights, normalize, channel_weights, cells, cell_channel_weights)
         names = list(ga.keys())
         flat = gw + [ga[k] for k in names] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=initial_state.shape[0])
@@ -213,18 +218,20 @@ class NonMetaPDETrainer(LatentODEMixin):
         return loss, NonMetaTrainState(params=params, nef_opt_state=nef_opt_state, autodecoder_opt_state=ad_state,
                                        ode_opt_state=state.ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, cells=None):
+    def nef_train_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, cells=None,
+                       cell_channel_weights=None):
         """batch = (initial states (B, ..., O), trajectory indices (B,) long)   (:101-137); ``weights`` / ``channel_weights`` /
-        ``cells`` as in loss_and_grads"""
-        return self._step(state, batch, mask, True, weights, normalize, channel_weights, cells)
+        ``cells`` / ``cell_channel_weights`` as in loss_and_grads"""
+        return self._step(state, batch, mask, True, weights, normalize, channel_weights, cells, cell_channel_weights)
 
-    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, cells=None):
+    def nef_train_step_autodec_only(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, cells=None,
+                                    cell_channel_weights=None):
         """Only the latents move (:139-171)."""
-        return self._step(state, batch, mask, False, weights, normalize, channel_weights, cells)
+        return self._step(state, batch, mask, False, weights, normalize, channel_weights, cells, cell_channel_weights)
 
     @torch.no_grad()
     def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, per_signal_loss=False,
-                         cells=None):
+                         cells=None, cell_channel_weights=None):
         """nef_train_step_autodec_only (:139-171) on the native latent-only path: same arguments, same (loss, new_state), same draw
         from ``state.rng`` (_fit_points), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
         are read under no_grad, ONE nef.mse_value_and_latent_grads (enf_fit_step_w: forward, fused weighted loss, backward to the
@@ -239,12 +246,15 @@ class NonMetaPDETrainer(LatentODEMixin):
         (this rank's signals; loss_b.mean() is the loss before the all-reduce, up to rounding).  Same draw from ``state.rng``, same
         new state.
         ``cells``: None, or (x (M G, dx), q (M G,) or None, group): the batch holds (B, M, O) cell means (loss_and_grads) and the one
-        fit call is the grouped step, enf_fit_step_g (nef.mse_value_and_cell_grads); the table update is the same."""
+        fit call is the grouped step, enf_fit_step_g (nef.mse_value_and_cell_grads); the table update is the same.
+        ``cell_channel_weights`` (M, O) / (B, M, O), with ``cells``: weights per observed value, the one fit call is enf_fit_step_gc."""
         initial_state, traj_idx = batch
         if cells is not None:
             if channel_weights is not None:
-                raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
-            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells)
+                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
+            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells, cell_channel_weights)
+        elif cell_channel_weights is not None:
+            raise ValueError("cell_channel_weights= goes with cells=")
         else:
             img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
         P = state.params["autodecoder"]["params"]
@@ -256,7 +266,7 @@ class NonMetaPDETrainer(LatentODEMixin):
         more = {"return_errors": True} if per_signal_loss else {}
         if cells is not None:
             loss, dp, da, dwin, *errs = self.nef.mse_value_and_cell_grads(state.params["nef"], xs, p, a, window, img, G, qweight=qs,
-                                                                          obs_weight=ws, **more)
+                                                                          **_cell_kw(ws), **more)
         else:
             loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, **nef_kw(lw), **more)
         loss = loss.reshape(())
@@ -283,18 +293,23 @@ class NonMetaPDETrainer(LatentODEMixin):
             raise ValueError(f"NonMetaPDETrainer.{what} needs a latent ODE: build the trainer with ode_model=... "
                              "(the second value of get_model_pde(cfg))")
 
-    def ode_loss(self, params, trajectory, traj_idx, point_masks=None, generator=None, graph=False, weights=None, normalize=True):
+    def ode_loss(self, params, trajectory, traj_idx, point_masks=None, generator=None, graph=False, weights=None, normalize=True,
+                 cells=None, cell_channel_weights=None, fused=False):
         """:244-307.  The first 10 frames of ``trajectory`` (B, T, *grid, O) against the roll-out of the table rows ``traj_idx``
         (B,) long, decoded at ``point_masks`` (frames, n_s) long -- one permutation of the grid per frame, shared by the signals of
-        the batch; drawn from ``generator`` when None and max_num_sampled_points is smaller than the grid."""
+        the batch; drawn from ``generator`` when None and max_num_sampled_points is smaller than the grid.
+        ``cells`` / ``cell_channel_weights`` / ``fused``: the trajectory holds cell means (LatentODEMixin.rollout_loss)."""
         self._need_ode("ode_loss")
         trajectory = trajectory[:, :TRAIN_FRAMES]                                # :252
         weights = cut_frames(weights, slice(TRAIN_FRAMES))                       # (B, T, N): the frames the loss sees
+        more = {}
+        if cells is not None or cell_channel_weights is not None or fused:
+            more = {"cells": cells, "cell_channel_weights": cut_frames(cell_channel_weights, slice(TRAIN_FRAMES), channel=True), "fused": fused}
         z0 = self.autodecoder.apply(params["autodecoder"], traj_idx)             # :255
         return self.rollout_loss(params["nef"], params["ode_params"], z0, trajectory, point_masks, generator, graph=graph,
-                                 weights=weights, normalize=normalize)
+                                 weights=weights, normalize=normalize, **more)
 
-    def ode_train_step(self, state, batch, point_masks=None, weights=None, normalize=True):
+    def ode_train_step(self, state, batch, point_masks=None, weights=None, normalize=True, cells=None, cell_channel_weights=None):
         """:173-199: one clip_by_global_norm(1) + AdamW step on the ODE parameters only.  ``batch`` = (trajectory (B, T, *grid, O),
         trajectory indices (B,) long) or the reference's (trajectory, _, traj_idx): the trajectory is ``batch[0]`` and the indices
         are ``batch[-1]``, whatever lies between is ignored.  nef weights, the latent table and their optimiser states are handed
@@ -307,14 +322,20 @@ class NonMetaPDETrainer(LatentODEMixin):
         is on the all-reduced values), so it reaches neither the parameters nor the AdamW moments.  The known way there is a
         table still at its initial value: with features exactly 1 the ODE model sees a - 1 = 0, every LayerNorm(eps 1e-6) in it
         normalises a constant vector with gain 1000, and the Jacobian of da/dt w.r.t. a (~1e5 for three layers) compounds over
-        the nine steps of the roll-out beyond the fp32 range."""
+        the nine steps of the roll-out beyond the fp32 range.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): the trajectory holds (B, T, M, O) cell means, ``point_masks`` index
+        cells, ``weights`` are per observation and ``cell_channel_weights`` (M, O) / (B, M, O) / (B, T, M, O) per observed value (not
+        both).  The nef weights are frozen, so the loss does not decode: nef.cell_fit_loss, one grouped fit step over the B T
+        signal-frames (rollout_loss(cells=, fused=True))."""
         self._need_ode("ode_train_step")
         trajectory, traj_idx = batch[0], batch[-1]
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         P = state.params["autodecoder"]["params"]
         params = {"nef": state.params["nef"], "autodecoder": {"params": {k: v.detach() for k, v in P.items()}},
                   "ode_params": _unflatten(state.params["ode_params"], leaves)}
-        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph, weights=weights, normalize=normalize)
+        more = {} if cells is None and cell_channel_weights is None else \
+            {"cells": cells, "cell_channel_weights": cell_channel_weights, "fused": cells is not None}
+        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph, weights=weights, normalize=normalize, **more)
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
         grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
         flat = grads + [loss.detach().reshape(1)]
@@ -331,18 +352,35 @@ class NonMetaPDETrainer(LatentODEMixin):
                                               step=state.step + 1, rng=state.rng)
 
     @torch.no_grad()
-    def val_step(self, state, batch, autodecoder=None, weights=None, normalize=True, channel_weights=None):
+    def val_step(self, state, batch, autodecoder=None, weights=None, normalize=True, channel_weights=None, cells=None,
+                 cell_channel_weights=None, return_frames=False, chunk=None):
         """:201-241: ``batch`` = (trajectory, traj_idx) or (trajectory, _, traj_idx), read as ``batch[0]`` and ``batch[-1]`` like
         ode_train_step's.  The first 20 frames against the roll-out of the rows ``traj_idx`` of ``state.params['autodecoder']``, read
         through ``autodecoder`` (a shell for validation signals; default: the trainer's own), decoded on the full grid in chunks of
         max_num_sampled_points.  Returns (mse over frames 0..9, mse over frames 10..19); a trajectory of at most 10 frames gives
         zero for the second.  Roll-outs of more than 4 frames replay one captured hipGraph per derivative evaluation.
         ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value; the two errors are then weighted per value
-        (a NaN under a zero weight does not count); not together with ``weights``."""
+        (a NaN under a zero weight does not count); not together with ``weights``.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): the trajectory holds (B, T, M, O) cell means; all M cells of all
+        B T signal-frames of the roll-out are evaluated with nef.eval_cell_loss in chunks of ``chunk`` cells (default
+        max_num_sampled_points // group) -- no decode.  Returns the two means of loss_b over the horizons, with ``return_frames``
+        followed by loss_b (B, T).  ``weights`` per observation or ``cell_channel_weights`` per observed value; ``channel_weights``
+        with ``cells`` is a ValueError."""
         self._need_ode("val_step")
         trajectory, traj_idx = batch[0], batch[-1]
         trajectory = trajectory[:, :VAL_FRAMES]                                  # :206
         B, T = trajectory.shape[:2]
+        if cells is not None:
+            if channel_weights is not None:
+                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
+            traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
+            cells = self._cells_of("val_step", cells, traj.shape[2])
+            fw = cell_loss_weights(weights, cell_channel_weights, B, traj.shape[2], traj.shape[3], T=T, normalize=normalize,
+                                   device=traj.device, frames=slice(T))
+            z0 = (autodecoder or self.autodecoder).apply(state.params["autodecoder"], traj_idx)
+            return self._val_cells(state.params["nef"], state.params["ode_params"], z0, traj, TRAIN_FRAMES, cells, fw, return_frames, chunk)
+        if cell_channel_weights is not None or return_frames:
+            raise ValueError("cell_channel_weights= and return_frames= go with cells=")
         # (N,) / (B, N) / (B, T, N) weights on the full grid, or per channel: the pair is then the two weighted errors
         fw = LossWeights.build(weights, channel_weights, B, self.coords.shape[0], trajectory.shape[-1], T=T, normalize=normalize,
                                device=self.coords.device, frames=slice(T))

@@ -45,14 +45,16 @@ import torch
 
 from ... import _lib
 from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
-from ..cells import GROUP_SIZES, _batched, gather_cell_samples
-from .latent_ode import LatentODEMixin, draw_point_masks, _leaves, _unflatten
+from ..cells import _batched, cell_weight_kw, check_cells, gather_cell_samples, inner_loop_cells
+from .latent_ode import LatentODEMixin, cell_loss_weights, draw_point_masks, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
 from ..weights import LossWeights, cut_frames, loop_kw, nef_kw, loss_tensor, weighted_mse
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
+_NO_CHANNEL_WEIGHTS_ON_CELLS = ("cells= takes per-observation weights= (M,) / (B, M) or cell_channel_weights= (M, O) / (B, M, O); "
+                                "channel_weights are not served on cells")
 
 
 def _tree_from_tensors(tensors, nef=None):
@@ -82,10 +84,11 @@ def _sampled(coords, img, masks, s, weights, copies=1):
 def _sampled_cells(cells, img, masks, s, weights, copies=1):
     """The cells of step ``s`` (``cells`` = (x (M G, dx), q (M G,) or None, group); masks hold CELL indices): (xs (copies * B, Ms G, dx),
     qs (B, Ms G) or None, ys (B, Ms, O), ws (B, Ms) or None) -- gather_cell_samples on column s, shared masks as a stride-0 batch;
-    per-signal masks give every signal its own cells and always weights (0 where the sampler padded with -1)."""
+    per-signal masks give every signal its own cells and always weights (0 where the sampler padded with -1).  Per-value ``weights``
+    (B, M, O) come back as (B, Ms, O): on cells the two kinds differ by rank (_cell_kw)."""
     x, q, G = cells
     B = img.shape[0]
-    xs, qs, ys, ws = gather_cell_samples(x, q, G, img, masks[..., s:s + 1], weights)
+    xs, qs, ys, ws = gather_cell_samples(x, q, G, img, masks[..., s:s + 1], **cell_weight_kw(weights, weights is not None and weights.dim() == 3))
     xs, qs = xs[0], None if qs is None else qs[0]
     if masks.dim() == 2:
         xs, qs = _batched(xs, qs, B)
@@ -95,12 +98,27 @@ def _sampled_cells(cells, img, masks, s, weights, copies=1):
     return xs, qs, ys[0].to(img.dtype), None if ws is None else ws[0]
 
 
+def _cell_kw(ws):
+    """The keyword of a grouped call for sampled weights (B, Ms) per observation or (B, Ms, O) per value."""
+    return cell_weight_kw(ws, ws is not None and ws.dim() == 3)
+
+
+def _cell_loop_kw(lw):
+    """The keyword meta_gradients(cells=) and the trainer steps on cells take a LossWeights (or None) by."""
+    return {} if lw is None else {"cell_channel_weights" if lw.channel else "weights": lw.w}
+
+
+def _cell_fit_kw(lw):
+    """The keyword inner_loop_cells takes it by."""
+    return {} if lw is None else {"obs_channel_weight" if lw.channel else "obs_weights": lw.w}
+
+
 def _loss(nef, params, coords, img, masks, s, lat, weights=None, cells=None):
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
     if cells is not None:         # the grouped loss of the decode at the sampled cells' quadrature points (nef.cell_mse: one kernel)
         xs, qs, ys, ws = _sampled_cells(cells, img, masks, s, weights)
         out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
-        return nef.cell_mse(out, ys, cells[2], qs, ws)
+        return nef.cell_mse(out, ys, cells[2], qs, **_cell_kw(ws))
     xs, ys, ws = _sampled(coords, img, masks, s, weights)               # pde_trainer.py:193-197
     out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
     if ws is None:
@@ -120,7 +138,7 @@ def _cell_latent_grads(nef, params, cells, img, masks, s, lat, keys, weights=Non
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
     xs, qs, ys, ws = _sampled_cells(cells, img, masks, s, weights)
     _, dp, da, dsig = nef.mse_value_and_cell_grads(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys, cells[2], qweight=qs,
-                                                   obs_weight=ws)
+                                                   **_cell_kw(ws))
     n_pos = lat["p_pos"].shape[-1]
     by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dsig}
     return {k: (torch.zeros_like(lat[k]) if by_name[k] is None else by_name[k].reshape(lat[k].shape)) for k in keys}
@@ -152,7 +170,7 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
         out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
         if cells is not None:
-            loss = nef.cell_mse(out[:B], ys, cells[2], qs, pw) - nef.cell_mse(out[B:], ys, cells[2], qs, pw)
+            loss = nef.cell_mse(out[:B], ys, cells[2], qs, **_cell_kw(pw)) - nef.cell_mse(out[B:], ys, cells[2], qs, **_cell_kw(pw))
         elif pw is None:
             loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
         else:
@@ -165,7 +183,7 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
 
 def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
                    second_order="fd", fd_step=None, noise_pos=0.0, generator=None, terminal=None, freeze_relu=True,
-                   weights=None, normalize=True, channel_weights=None, cells=None):
+                   weights=None, normalize=True, channel_weights=None, cells=None, cell_channel_weights=None):
     """Value and gradient of the last-inner-step loss w.r.t. (nef weights, meta-init latents, inner lrs).
 
     Returns (loss, grads) with grads = {'nef': [46 tensors in ENF_W_* order], 'autodecoder': {key: (1,Z,.)},
@@ -186,16 +204,19 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     ``coords`` is not used.  The forward sweep runs the grouped fit step (nef.mse_value_and_cell_grads, which records the relu masks);
     the default terminal loss and both halves of the finite differences decode the cells' quadrature points and take the grouped loss
     nef.cell_mse.  ``channel_weights`` with ``cells`` is a ValueError.
+    ``cell_channel_weights``: None, or (M, O) / (B, M, O) weights per observed VALUE of the cells (with ``cells`` only, not together with
+    ``weights``), mean 1 over each signal's M * O values unless ``normalize`` is False: every grouped pass takes them in place of the
+    per-observation weights (enf_fit_step_gc, enf_mse_value_grad_gc).
     """
     if cells is not None:
         if channel_weights is not None:
-            raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
-        if int(cells[2]) not in GROUP_SIZES:
-            raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
-        if cells[0].dim() != 2 or cells[0].shape[0] != img.shape[1] * int(cells[2]):
-            raise ValueError(f"cells hold {tuple(cells[0].shape)} quadrature points, img {img.shape[1]} cells of {int(cells[2])}")
-        cells = (cells[0], cells[1], int(cells[2]))
-    pw = loss_tensor(LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device))
+            raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
+        cells = check_cells(cells, img.shape[1])
+        pw = loss_tensor(cell_loss_weights(weights, cell_channel_weights, *img.shape, normalize=normalize, device=img.device))
+    else:
+        if cell_channel_weights is not None:
+            raise ValueError("cell_channel_weights= goes with cells=")
+        pw = loss_tensor(LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device))
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
     if fd_step is None:      # truncation (~step^2) against the rounding of the first-order gradients (~1 / step): bf16 kernels
@@ -360,11 +381,13 @@ class MetaSGDPDETrainer(LatentODEMixin):
             return masks, lw.drawn_on(masks)
         return make_masks(num_coords, n, cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device), lw
 
-    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None, cells=None):
+    def nef_train_step(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None, cells=None,
+                       cell_channel_weights=None):
         """One outer step on ``batch`` = (B, N, O) initial states (trajectory[:, 0], pde_trainer.py:485-487).
         ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``batch`` holds (B, M, O) cell means and the step trains on them
         (meta_gradients); masks drawn here sample max(1, max_num_sampled_points // group) cells, ``weights`` are per observation, and
         the ``sample_observed`` draw works on them.  ``channel_weights`` with ``cells`` is a ValueError.
+        ``cell_channel_weights``: None, or (M, O) / (B, M, O) weights per observed value of the cells (meta_gradients), not with ``weights``.
         ``weights``: None, or (N,) / (B, N) loss weights on the full grid (meta_gradients).
         ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (meta_gradients); with ``sample_observed`` the masks are
         drawn from the points that carry at least one observed value (point_support).
@@ -373,16 +396,20 @@ class MetaSGDPDETrainer(LatentODEMixin):
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
         if cells is not None and channel_weights is not None:
-            raise ValueError("cells= takes per-observation weights= (M,) / (B, M); channel_weights are not served on cells")
+            raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
         # (point weights that this step does not draw from go on as they came: meta_gradients prepares them)
+        if cell_channel_weights is not None and cells is None:
+            raise ValueError("cell_channel_weights= goes with cells=")
         lw, kw = None, {"weights": weights, "normalize": normalize}
-        if channel_weights is not None or (masks is None and self.sample_observed):
+        if cell_channel_weights is not None:
+            lw = cell_loss_weights(weights, cell_channel_weights, *img.shape, normalize=normalize, device=img.device)
+        elif channel_weights is not None or (masks is None and self.sample_observed):
             lw = LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device)
         if masks is None:
             masks, lw = self._draw_masks(state, img.shape[1] if cells is not None else self.coords.shape[0], lw,
                                          group=int(cells[2]) if cells is not None else 1)
         if lw is not None:
-            kw = dict(loop_kw(lw), normalize=False)
+            kw = dict(_cell_loop_kw(lw) if cells is not None else loop_kw(lw), normalize=False)
         if cells is not None:
             kw["cells"] = cells
         lat0 = self._latents0(state)
@@ -418,7 +445,8 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return loss, new_state
 
     @torch.no_grad()
-    def fit_errors(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None, chunk=None):
+    def fit_errors(self, state, batch, masks=None, weights=None, normalize=True, channel_weights=None, chunk=None, cells=None,
+                   cell_channel_weights=None):
         """Which signal did not fit, and where: fit the latents of ``batch`` = (B, N, O) initial states as nef_train_step's inner loop
         does (same arguments, same draw of the masks from ``state.rng``), then evaluate the fit on the FULL grid without decoding it
         (nef.eval_loss, include/enf_hip.h: enf_eval_loss).  Returns (loss_b (B,), err (B, N)):
@@ -426,10 +454,29 @@ class MetaSGDPDETrainer(LatentODEMixin):
         with w the prepared ``weights`` / ``channel_weights`` on the full grid (mean 1 per signal unless ``normalize`` is False; not the
         rescaled weights a fit on per-signal masks uses), or 1; a point of weight 0 has err 0 and its target may be NaN.
         ``chunk``: points per evaluation call, as val_step's decode takes it (None: the whole grid in one call).  Every chunk's errors
-        are written into the one (B, N) tensor and loss_b is summed from it once, in a fixed order."""
+        are written into the one (B, N) tensor and loss_b is summed from it once, in a fixed order.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``batch`` holds (B, M, O) cell means; the fit is inner_loop_cells on
+        sampled cells and the evaluation nef.eval_cell_loss on ALL M cells (``chunk`` counts cells).  Returns (loss_b (B,), err_g (B, M)):
+            err_g[b, m] = w[b, m] sum_o (obs - batch)^2, or sum_o cw[b, m, o] (obs - batch)^2       loss_b[b] = err_g[b].sum() / (M O)
+        with ``weights`` (M,) / (B, M) per observation or ``cell_channel_weights`` (M, O) / (B, M, O) per observed value."""
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
         B, N, O = img.shape
+        if cells is not None:
+            if channel_weights is not None:
+                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
+            cells = self._cells_of("fit_errors", cells, N)
+            lw = cell_loss_weights(weights, cell_channel_weights, B, N, O, normalize=normalize, device=img.device)
+            if not img.is_cuda:
+                raise _lib.EnfError("MetaSGDPDETrainer.fit_errors needs CUDA/HIP tensors: there is no CPU path")
+            lat = self._fitted_cells(state, img, masks, lw, cells)
+            sol = (_pose(lat, self.nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"))
+            fw = lw and LossWeights(lw.w[:, None], lw.channel)
+            err, loss_b = self._cell_frame_errors(state.params["nef"], tuple(None if v is None else v[:, None] for v in sol),
+                                                  img[:, None], cells, fw, chunk)
+            return loss_b.reshape(B), err
+        if cell_channel_weights is not None:
+            raise ValueError("cell_channel_weights= goes with cells=")
         if not (img.is_cuda and self.coords.is_cuda):
             raise _lib.EnfError("MetaSGDPDETrainer.fit_errors needs CUDA/HIP tensors: there is no CPU path")
         lw = fit_lw = LossWeights.build(weights, channel_weights, B, N, O, normalize=normalize, device=img.device)
@@ -517,23 +564,62 @@ class MetaSGDPDETrainer(LatentODEMixin):
                             noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, **loop_kw(weights))
         return {k: v.detach() for k, v in lat.items()}
 
+    def _fitted_cells(self, state, img, masks, lw, cells, noise=True):
+        """_fitted on cell means ``img`` (B, M, O): masks of max(1, max_num_sampled_points // group) cells (drawn here when None,
+        _draw_masks), then inner_loop_cells with the weights ``lw`` (a LossWeights over (B, M[, O]) or None).  ``noise`` False: without
+        the training steps' pose noise, as val_step fits."""
+        cfg = self.config
+        x, q, G = cells
+        if masks is None:
+            masks, lw = self._draw_masks(state, img.shape[1], lw, group=G)
+        with torch.enable_grad():
+            _, lat = inner_loop_cells(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], x, q, G, img, masks,
+                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
+                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0) if noise else 0.0, generator=state.rng,
+                                      **_cell_fit_kw(lw))
+        return {k: v.detach() for k, v in lat.items()}
+
+    def _cell_trajectory(self, what, trajectory, cells, channel_weights):
+        """``trajectory`` (B, T, ..., O) as (B, T, M, O) cell means and ``cells`` checked against M."""
+        if channel_weights is not None:
+            raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
+        traj = trajectory.reshape(trajectory.shape[0], trajectory.shape[1], -1, trajectory.shape[-1])
+        return traj, self._cells_of(what, cells, traj.shape[2])
+
     def _frame0(self, trajectory, weights, channel_weights, normalize):
         """The LossWeights of the fit on frame 0 of ``trajectory`` (B, T, *grid, O), or None."""
         return LossWeights.build(weights, channel_weights, trajectory.shape[0], self.coords.shape[0], trajectory.shape[-1],
                                  normalize=normalize, device=self.coords.device, frames=0)
 
-    def ode_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True):
+    def ode_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True, cells=None,
+                       cell_channel_weights=None):
         """pde_trainer.py:290-318: one Adam step on the ODE parameters only.  The fitted latents do not depend on them, so
         the inner loop runs without a graph; the gradient flows decoder -> (HIP latent backward) -> solver -> ODE model.
-        ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid: frame 0's weigh the fit, all the roll-out loss."""
+        ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on the full grid: frame 0's weigh the fit, all the roll-out loss.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``trajectory`` holds (B, T, M, O) cell means; ``masks`` and
+        ``point_masks`` index cells, ``weights`` are per observation ((M,) / (B, M) / (B, T, M)) and ``cell_channel_weights`` (M, O) /
+        (B, M, O) / (B, T, M, O) per observed value (not both).  Frame 0 is fitted with inner_loop_cells, and the roll-out loss does
+        not decode: the nef weights are frozen, so it is nef.cell_fit_loss -- one grouped fit step over the B T signal-frames
+        (rollout_loss(cells=, fused=True))."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]                  # pde_trainer.py:421-422
         weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
-        lat = self._fitted(state, trajectory, masks, self._frame0(trajectory, weights, None, normalize))
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
-        loss = self.ode_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
-                             normalize=normalize)
+        if cells is not None:
+            trajectory, cells = self._cell_trajectory("ode_train_step", trajectory, cells, None)
+            cell_channel_weights = cut_frames(cell_channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
+            B, _, M, O = trajectory.shape
+            lw0 = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=trajectory.device, frames=0)
+            lat = self._fitted_cells(state, trajectory[:, 0], masks, lw0, cells)
+            loss = self.rollout_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
+                                     normalize=normalize, cells=cells, cell_channel_weights=cell_channel_weights, fused=True)
+        else:
+            if cell_channel_weights is not None:
+                raise ValueError("cell_channel_weights= goes with cells=")
+            lat = self._fitted(state, trajectory, masks, self._frame0(trajectory, weights, None, normalize))
+            loss = self.ode_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
+                                 normalize=normalize)
         grads = list(torch.autograd.grad(loss, leaves, allow_unused=True))
         grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
         flat = grads + [loss.detach().reshape(1)]
@@ -544,32 +630,52 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                        autodecoder_opt_state=state.autodecoder_opt_state, meta_sgd_opt_state=state.meta_sgd_opt_state,
                                        ode_opt_state=ode_opt_state, step=state.step + 1, rng=state.rng)
 
-    def dual_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True, channel_weights=None):
+    def dual_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True, channel_weights=None,
+                        cells=None, cell_channel_weights=None):
         """pde_trainer.py:320-358: the roll-out loss trains the nef weights (clip + AdamW), the inner learning rates (Adam,
         clipped) and the ODE parameters (Adam); the latent initialisation is left alone.  The nef / learning-rate
         gradients include the path through the inner loop (the same adjoint recursion as nef_train_step, started from
         d loss / d fitted latents of the roll-out).  ``weights`` as in ode_train_step.
         ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value: frame 0's weigh the fit, all the roll-out
-        loss; not together with ``weights``."""
+        loss; not together with ``weights``.
+        ``cells`` / ``cell_channel_weights``: as in ode_train_step.  The fit's meta-gradient is meta_gradients(cells=), and the
+        terminal roll-out loss is taken through nef.apply + nef.cell_mse (rollout_loss(cells=)): it needs the weight gradients."""
         cfg = self.config
         trajectory = trajectory[:, :cfg.dataset.traj_len_train]
-        lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
-        weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
-        channel_weights = cut_frames(channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
-        coords, img, masks, lw0 = self._fit_initial_latents(state, trajectory[:, 0], masks, weights=lw0)
+        more = {}
+        if cells is not None:
+            trajectory, cells = self._cell_trajectory("dual_train_step", trajectory, cells, channel_weights)
+            B, _, M, O = trajectory.shape
+            lw0 = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=trajectory.device, frames=0)
+            weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
+            cell_channel_weights = cut_frames(cell_channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
+            coords, img, G = None, trajectory[:, 0], cells[2]
+            if masks is None:
+                masks, lw0 = self._draw_masks(state, M, lw0, group=G)
+            num, n_s = M, max(1, cfg.training.max_num_sampled_points // G)
+            more = {"cells": cells, "cell_channel_weights": cell_channel_weights}
+        else:
+            if cell_channel_weights is not None:
+                raise ValueError("cell_channel_weights= goes with cells=")
+            lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
+            weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
+            channel_weights = cut_frames(channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
+            coords, img, masks, lw0 = self._fit_initial_latents(state, trajectory[:, 0], masks, weights=lw0)
+            num, n_s = self.coords.shape[0], cfg.training.max_num_sampled_points
+            more = {"channel_weights": channel_weights}
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
-        if point_masks is None and cfg.training.max_num_sampled_points < self.coords.shape[0]:
-            point_masks = draw_point_masks(self.coords.shape[0], cfg.training.max_num_sampled_points, trajectory.shape[1],
-                                           state.rng, self.coords.device)
+        if point_masks is None and n_s < num:
+            point_masks = draw_point_masks(num, n_s, trajectory.shape[1], state.rng, trajectory.device if cells is not None else self.coords.device)
         side = {}
         point_weights = weights             # (`weights` below are the network's)
 
         def terminal(weights, lat, keys):
             w = [t.detach().requires_grad_(True) for t in weights]
             lv = {k: lat[k].detach().requires_grad_(True) for k in lat}
-            loss = self.ode_loss(_tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph,
-                                 weights=point_weights, normalize=normalize, channel_weights=channel_weights)
+            loss = (self.rollout_loss if cells is not None else self.ode_loss)(
+                _tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph, weights=point_weights,
+                normalize=normalize, **more)
             g = torch.autograd.grad(loss, w + [lv[k] for k in keys] + leaves, allow_unused=True)
             z = lambda t, gi: torch.zeros_like(t) if gi is None else gi
             side["ode"] = [z(t, gi) for t, gi in zip(leaves, g[len(w) + len(keys):])]
@@ -581,7 +687,7 @@ class MetaSGDPDETrainer(LatentODEMixin):
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal,
-                                     normalize=False, **loop_kw(lw0))
+                                     normalize=False, **(dict(_cell_loop_kw(lw0), cells=cells) if cells is not None else loop_kw(lw0)))
         lr_keys = list(lrs.keys())
         flat = grads["nef"] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + side["ode"] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])
@@ -631,9 +737,20 @@ class MetaSGDPDETrainer(LatentODEMixin):
             total, n = total + float(loss), n + 1
         return total / max(n, 1), state
 
+    def _val_step_cells(self, state, trajectory, T_in, masks, weights, normalize, channel_weights, cells, cell_channel_weights,
+                        return_frames, chunk):
+        trajectory, cells = self._cell_trajectory("val_step", trajectory, cells, channel_weights)
+        B, T, M, O = trajectory.shape
+        lw0 = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=trajectory.device, frames=0)
+        fw = cell_loss_weights(weights, cell_channel_weights, B, M, O, T=T, normalize=normalize, device=trajectory.device, frames=slice(T))
+        if not trajectory.is_cuda:
+            raise _lib.EnfError("MetaSGDPDETrainer.val_step(cells=) needs CUDA/HIP tensors: there is no CPU path")
+        lat = self._fitted_cells(state, trajectory[:, 0], masks, lw0, cells, noise=False)
+        return self._val_cells(state.params["nef"], state.params["ode_params"], lat, trajectory, T_in, cells, fw, return_frames, chunk)
+
     @torch.no_grad()
     def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True, drop_rate=None,
-                 channel_weights=None):
+                 channel_weights=None, cells=None, cell_channel_weights=None, return_frames=False, chunk=None):
         """pde_trainer.py:360-409: fit the first frame, roll out over train + out-of-horizon frames, decode the full grid;
         returns (mse over the training horizon, mse beyond it).  ``weights``: None, or (N,) / (B, N) / (B, T, N) loss weights on
         the full grid (fitting/weights.py; mean 1 per signal-frame unless ``normalize`` is False): frame 0's weigh the fit, and
@@ -645,11 +762,25 @@ class MetaSGDPDETrainer(LatentODEMixin):
         two errors are still taken over all valid points of the full grid.
         ``channel_weights``: None, or (N, O) / (B, N, O) / (B, T, N, O) weights per value, used like ``weights`` (not together with
         them): frame 0's weigh the fit, a point is observed where any of its channels is, and the two errors are weighted per
-        value -- a field with NaN in one variable validates on its other variables there."""
+        value -- a field with NaN in one variable validates on its other variables there.
+        ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``trajectory`` holds (B, T, M, O) cell means.  Frame 0 is fitted on
+        sampled cells (inner_loop_cells; ``masks`` index cells), the latents are rolled out, and ALL M cells of all B T signal-frames
+        are evaluated with nef.eval_cell_loss in chunks of ``chunk`` cells (default max_num_sampled_points // group; the bits do not
+        depend on it): no decode and no (B, T, N, O) tensor.  Returns (mean of loss_b over the training horizon, mean beyond it), and
+        with ``return_frames`` a third value, loss_b (B, T), every signal-frame's own error of the roll-out.  ``weights`` per
+        observation or ``cell_channel_weights`` per observed value, with or without a frame axis; ``drop_rate``, ``initial_state_dp``
+        and ``channel_weights`` with ``cells`` are a ValueError."""
         cfg = self.config
         T_in = cfg.dataset.traj_len_train
         trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
         B, T = trajectory.shape[:2]
+        if cells is not None:
+            if drop_rate is not None or initial_state_dp > 0:
+                raise ValueError("drop_rate and initial_state_dp are not served on cells")
+            return self._val_step_cells(state, trajectory, T_in, masks, weights, normalize, channel_weights, cells, cell_channel_weights,
+                                        return_frames, chunk)
+        if cell_channel_weights is not None or return_frames:
+            raise ValueError("cell_channel_weights= and return_frames= go with cells=")
         N, O = self.coords.shape[0], trajectory.shape[-1]
         lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
         if drop_rate is not None:

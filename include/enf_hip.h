@@ -502,6 +502,38 @@ int enf_mse_value_grad_g(const float* out /* (B,N,O) */, const float* target /* 
                          float* dout /* (B,N,O) or NULL */, float* loss, float* err_g /* (B,M) or NULL */, void* scratch,
                          size_t scratch_bytes, unsigned flags, void* stream);
 
+/* Per-value weights on grouped observations (enf_fit_step_gc, enf_eval_loss_gc, enf_mse_value_grad_gc, enf_fit_inputs_gc): a cell that
+ * lacks one variable counts with its others -- a masked sea-surface value under a valid wind, one NaN variable in a box.  With
+ * cw = cweight_g (B, M, O), finite and >= 0, REQUIRED, in place of oweight:
+ *     loss      = 1/(B M O) * sum_{b,m,o} cw[b,m,o] * (obs[b,m,o] - target[b,m,o])^2
+ *     d out[b, mG+k, o] = 2 * q[b,mG+k] * cw[b,m,o] * (obs - target)[b,m,o] / (B M O) * grad_scale
+ *     err_g[b,m] = sum_o cw[b,m,o] * (obs - target)^2              loss_b[b] = sum_m err_g[b,m] / (M O)
+ * The zero-weight rule holds per VALUE: a value of weight 0 does not exist, its target may be NaN or Inf, and its share of the loss and
+ * of every d out of its group is exactly 0.0f.  Nothing is normalised.
+ * After the xor tree every lane of a group holds obs for its eight channels; the lane reads cw[m][o] where the per-observation form
+ * reads oweight[m] and applies the select per value.  The arithmetic per value and its order are the per-observation form's, so with
+ * cw[b,m,:] = w[b,m] the results are those of the _g call with oweight = w, bit for bit (under ENF_FIT_DETERMINISTIC for the loss and
+ * the gradients).  The tail runs instantiations of their own on an argument block of their own: every other call keeps its kernels.
+ * Each call takes its _g counterpart's arguments, refusals and workspace sizes; cweight_g == NULL is ENF_EINVAL.
+ * ENF_FIT_SHARED_LATENTS on enf_fit_step_gc: ENF_EUNSUPPORTED (behind the descriptor's errors) -- the shared first step with per-value
+ * weights is not built. */
+int enf_fit_step_gc(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                    const void* packed, const float* target /* (B,M,O) */, int32_t G, const float* qweight /* (B,N) or NULL */,
+                    const float* cweight_g /* (B,M,O), required */, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                    float* err_g /* (B,M) or NULL */, float* loss_b /* (B) or NULL, needs err_g */, void* workspace, size_t workspace_bytes,
+                    unsigned flags, void* stream);
+int enf_eval_loss_gc(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                     const void* packed, const float* target /* (B,M,O) */, int32_t G, const float* qweight /* (B,N) or NULL */,
+                     const float* cweight_g /* (B,M,O), required */, float* loss /* scalar, accumulated, or NULL */,
+                     float* err_g /* (B,M) or NULL */, float* loss_b /* (B) or NULL */, void* workspace, size_t workspace_bytes,
+                     unsigned flags, void* stream);
+/* enf_mse_value_grad_g with per-value weights: the same kernel, whose thread of (group, channel o) reads cw[b,m,o]; err_g adds the O
+ * shares in channel order, each under its own weight. */
+int enf_mse_value_grad_gc(const float* out /* (B,N,O) */, const float* target /* (B,M,O) */, int32_t B, int32_t N, int32_t O, int32_t G,
+                          const float* qweight /* (B,N) or NULL */, const float* cweight_g /* (B,M,O), required */, float grad_scale,
+                          float* dout /* (B,N,O) or NULL */, float* loss, float* err_g /* (B,M) or NULL */, void* scratch,
+                          size_t scratch_bytes, unsigned flags, void* stream);
+
 /* Derivative fields (enf_field_grad, enf_query_vjp): the Jacobian of a decode with respect to its query coordinates -- grad u, the
  * vorticity or divergence of a velocity field, a PDE residual on a decoded frame -- in one call, without the weight-gradient machinery.
  *     jac[o,b,n,i] = d out[b,n,o] / d x[b,n,i]        (O, B, N, dx) fp32, channel-major, required, OVERWRITTEN
@@ -819,6 +851,14 @@ int enf_fit_inputs_g(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t
                      const float* obs /* (B, M, O) */, const int64_t* masks, float* xs, float* qs /* NULL iff q NULL */,
                      float* ys /* (S1, B, Ms, O) */, float* losses, const float* oweight /* (B, M) or NULL */,
                      float* ws /* (S1, B, Ms) */, int32_t per_signal_masks, void* stream);
+/* enf_fit_inputs_g for per-value weights (include "Grouped observations", the _gc calls), in the same single launch by the same kernel:
+ *       ws[s, b, i, o] = cweight_g[b, masks[..], o]      (S1, B, Ms, O)      cweight_g (B, M, O)
+ * cweight_g and ws are both required (NULL is ENF_EINVAL), with either mask layout; an index outside [0, M) gives O zeros. */
+int enf_fit_inputs_gc(int ncomp, const EnfFitComponent* comps, int32_t B, int32_t Z, int32_t M, int32_t Ms, int32_t S1, int32_t G,
+                      int32_t dx, int32_t O, const float* xq /* (M*G, dx) */, const float* q /* (M*G) or NULL */,
+                      const float* obs /* (B, M, O) */, const int64_t* masks, float* xs, float* qs /* NULL iff q NULL */,
+                      float* ys /* (S1, B, Ms, O) */, float* losses, const float* cweight_g /* (B, M, O), required */,
+                      float* ws /* (S1, B, Ms, O), required */, int32_t per_signal_masks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
