@@ -12,6 +12,7 @@
   lm_fit_cell_averages  (no counterpart)                       the Levenberg-Marquardt fit against cell averages, on the grouped Gauss-Newton product
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
   inner_loop_cells, gather_cell_samples, cell_mse_torch  (no counterpart)   the inner loop on sampled cells (the trainers' cells=) and the torch-op mirrors of its kernels
+  observations: Points, Cells, observed  (no counterpart)      what a fit observes -- point values or cell averages -- and the one parser of weights= / channel_weights= / cells= / cell_channel_weights=
   shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
   ode_models           ode_models/ponita_ode_g.py, mlp_ode.py  PonitaODEGen (fused SepGconv HIP kernels), MLPODE

@@ -6,14 +6,15 @@ footprint's weighted mean.  Such an observation is a fixed linear functional of 
 a quadrature rule over G points of cell m.  ``cell_quadrature`` builds the points and factors, ``decode_cell_averages`` applies the
 functional to a decode in torch ops, and ``fit_cell_averages`` runs the inner loop's update rule on the fused grouped step
 (nef.mse_value_and_cell_grads: the group sums are formed in the tail's registers, no decode exists in memory).
-``inner_loop_cells`` is inner_loop on sampled cells -- one gather launch (enf_fit_inputs_g), the shared-latent hint at step 0 -- and what
-the trainers run with ``cells=``; ``gather_cell_samples`` and ``cell_mse_torch`` are the torch-op mirrors of the gather kernel and of the
-unfused grouped loss (nef.cell_mse)."""
+``inner_loop_cells`` is inner_loop on sampled cells -- the same loop (inner_loop.py: _fit_loop) given a ``Cells`` value
+(fitting/observations.py): one gather launch (enf_fit_inputs_g), the shared-latent hint at step 0 -- and what the trainers run with
+``cells=``; ``fit_cell_averages`` keeps its own sampling and takes the step body from that loop (_sgd_step).  ``gather_cell_samples`` and
+``cell_mse_torch`` are the torch-op mirrors of the gather kernel and of the unfused grouped loss (nef.cell_mse)."""
 import numpy as np
 import torch
 
 from .. import _lib
-from .inner_loop import FUSED_FIT_INPUTS, _pose, _shared_kw, meta_sgd_update, normalize_sampled_weights
+from .inner_loop import _fit_loop, _pose, _sgd_step, _shared_kw      # (_shared_kw: re-exported)
 
 GROUP_SIZES = (1, 2, 4, 8, 16)
 
@@ -175,8 +176,8 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
     if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
         raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
     _one_weight_kind("fit_cell_averages", obs_weight, obs_channel_weight, (B, M, O))
-    per_value = obs_channel_weight is not None
-    wkey = "obs_channel_weight" if per_value else "obs_weight"
+    from .observations import Cells                  # (observations imports this module)
+    obs, per_value = Cells(x, q, G, M), obs_channel_weight is not None
     if per_value:
         obs_weight = obs_channel_weight
     dev = targets.device
@@ -194,31 +195,19 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
         ys_all = tg[:, idx].transpose(0, 1).contiguous()                                    # (S + 1, B, M_s, O)
         ws_all = obs_weight.to(dev)[:, idx].transpose(0, 1).contiguous() if obs_weight is not None else None
         pick = lambda s: (xs_all[s], None if qs_all is None else qs_all[s], ys_all[s], None if ws_all is None else ws_all[s])
-    n_ori = nef.cross_attn_invariant.num_z_ori_dims
     lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
     losses = torch.zeros(S + 1, device=dev, dtype=torch.float32)
-    n_pos = lat["p_pos"].shape[-1]
-    rows_b = []
-    for s in range(S + 1):
+    rows_b = [] if per_signal_loss else None
+    for s in range(S + 1):                                               # S steps, then the loss on the last set
         xs, qs, ys, ws = pick(s)
         xb, qb = _batched(xs.to(dev), None if qs is None else qs.to(dev), B)
-        args = (params, xb, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys, G)
-        if s == S:
-            lb, _ = nef.eval_cell_loss(*args, qweight=qb, loss_out=losses[S:], per_signal=per_signal_loss, **{wkey: ws})
-            rows_b.append(lb)
-            break
-        res = nef.mse_value_and_cell_grads(*args, qweight=qb, loss_out=losses[s:s + 1], return_errors=per_signal_loss, **{wkey: ws})
-        _, dp, da, dsig = res[:4]
-        if per_signal_loss:
-            rows_b.append(res[5])
-        grads = {"p_pos": dp[..., :n_pos], "a": da}
-        if n_ori > 0:
-            grads["p_ori"] = dp[..., n_pos:]
-        if optimize_gaussian_window and dsig is not None:
-            grads["gaussian_window"] = dsig
-        lat = meta_sgd_update(lat, grads, lrs, B)
+        if s < S:
+            lat = _sgd_step(nef, params, obs, lat, lrs, xb, qb, ys, ws, per_value, optimize_gaussian_window, rows_b,
+                            loss_out=losses[s:s + 1], return_errors=per_signal_loss)
+    lb = obs.final_loss(nef, params, xb, qb, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"), ys, ws,
+                        per_value, losses[S:], per_signal_loss)
     if per_signal_loss:
-        return losses[S], lat, torch.stack(rows_b)
+        return losses[S], lat, torch.stack(rows_b + [lb])
     return losses[S], lat
 
 
@@ -337,59 +326,11 @@ def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks
     if obs_weights is not None and tuple(obs_weights.shape) != (B, M):
         raise ValueError(f"obs_weights have shape {tuple(obs_weights.shape)}, expected {(B, M)}")
     _one_weight_kind("inner_loop_cells", obs_weights, obs_channel_weight, (B, M, O))
-    per_value = obs_channel_weight is not None
-    wkey = "obs_channel_weight" if per_value else "obs_weight"
-    if per_value:
-        obs_weights = obs_channel_weight
-    per_signal = masks.dim() == 3
-    if masks.dim() not in (2, 3) or (per_signal and masks.shape[0] != B):
+    from .observations import Cells                  # (observations imports this module)
+    if masks.dim() not in (2, 3) or (masks.dim() == 3 and masks.shape[0] != B):
         raise ValueError(f"masks have shape {tuple(masks.shape)}, expected (Ms, S + 1) or ({B}, Ms, S + 1)")
-    S = masks.shape[-1] - 1
-    dev = targets.device
-    w_full = obs_weights.to(device=dev, dtype=torch.float32).contiguous() if obs_weights is not None else None
-    fused = _cell_inputs(latents0, x, q, G, targets, masks, w_full, per_value) if FUSED_FIT_INPUTS else None
-    if fused is not None:
-        lat, xs_all, qs_all, ys_all, losses, ws_all = fused
-    else:
-        lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
-        losses = torch.zeros(S + 1, device=dev, dtype=torch.float32)
-        xs_all, qs_all, ys_all, ws_all = gather_cell_samples(x.to(dev), None if q is None else q.to(dev), G, targets, masks.to(dev),
-                                                             **{wkey: w_full})
-    if normalize_weights:
-        if ws_all is None:
-            raise ValueError("normalize_weights needs sampled weights: pass obs_weights= or per-signal masks")
-        ws_all = normalize_sampled_weights(ws_all, channel=per_value)
-    if noise_pos:
-        lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator, device="cpu").to(lat["p_pos"].device) * noise_pos
-    n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    n_pos = lat["p_pos"].shape[-1]
-
-    def sampled(s):     # step s's cells -- every signal's own, or a stride-0 batch --, factors and weights
-        xs, qs = xs_all[s], None if qs_all is None else qs_all[s]
-        if not per_signal:
-            xs, qs = _batched(xs, qs, B)
-        return xs, qs, None if ws_all is None else ws_all[s]
-
-    rows = []
-    for s in range(S):
-        xs, qs, ws = sampled(s)
-        res = nef.mse_value_and_cell_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[s], G, qweight=qs,
-                                           loss_out=losses[s:s + 1], **({"return_errors": True} if per_signal_loss else {}),
-                                           **({"obs_channel_weight": ws} if per_value else
-                                              dict(obs_weight=ws, **_shared_kw(nef, s, per_signal, noise_pos, step="mse_value_and_cell_grads"))))
-        _, dp, da, dsig = res[:4]
-        if per_signal_loss:
-            rows.append(res[5])
-        grads = {"p_pos": dp[..., :n_pos], "a": da}
-        if n_ori > 0:
-            grads["p_ori"] = dp[..., n_pos:]
-        if optimize_gaussian_window and dsig is not None:
-            grads["gaussian_window"] = dsig
-        lat = meta_sgd_update(lat, grads, lrs, B)
-    xs, qs, ws = sampled(S)
-    lb, _ = nef.eval_cell_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], G, qweight=qs,
-                               loss_out=losses[S:], per_signal=per_signal_loss, **{wkey: ws})
-    if per_signal_loss:
-        rows.append(lb)
-        return losses[S], lat, torch.stack(rows)
-    return losses[S], lat
+    per_value = obs_channel_weight is not None
+    w = obs_channel_weight if per_value else obs_weights
+    w = w.to(device=targets.device, dtype=torch.float32).contiguous() if w is not None else None
+    return _fit_loop(nef, nef_params, Cells(x, q, G, M), latents0, lrs, targets, masks, w, per_value, optimize_gaussian_window, noise_pos,
+                     generator, normalize_weights, per_signal_loss)

@@ -1,4 +1,8 @@
-"""MAML inner loop and decode on the HIP path (trainers/pde_trainer.py:122-235, 389-405)."""
+"""MAML inner loop and decode on the HIP path (trainers/pde_trainer.py:122-235, 389-405).
+
+``inner_loop`` (point values) and fitting/cells.py: ``inner_loop_cells`` (cell averages) are one loop, ``_fit_loop``: what differs between
+the two kinds of observation -- the gather, the decoder's calls, the form of the last loss, when step 0 may share its forward -- it asks
+of the observation value it is given (fitting/observations.py)."""
 import functools
 import inspect
 
@@ -257,64 +261,62 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
                Every weight form and both mask layouts.
     Returns (loss on the last mask, fitted latents dict with leading dim B), with ``per_signal_loss`` followed by loss_b.
     """
+    from .observations import Points                 # (observations imports this module)
     B = img.shape[0]
-    per_signal = masks.dim() == 3
-    if per_signal and masks.shape[0] != B:
+    if masks.dim() == 3 and masks.shape[0] != B:
         raise ValueError(f"per-signal masks have shape {tuple(masks.shape)}, expected ({B}, N_s, S + 1)")
-    S = masks.shape[-1] - 1
+    return _fit_loop(nef, nef_params, Points(coords), latents0, lrs, img, masks, _full_grid_weights(img, weights, channel_weights),
+                     channel_weights is not None, optimize_gaussian_window, noise_pos, generator, normalize_weights, per_signal_loss)
+
+
+def split_latent_grads(dp, da, dsig, n_pos, ori=True):
+    """A fit step's (dp, da, dsig) by the latents' names: the pose gradient split into ``p_pos`` and, with ``ori``, ``p_ori`` (column
+    slices of dp), ``a``, and ``gaussian_window`` where dsig is not None."""
+    grads = {"p_pos": dp[..., :n_pos], "a": da}
+    if ori:
+        grads["p_ori"] = dp[..., n_pos:]
+    if dsig is not None:
+        grads["gaussian_window"] = dsig
+    return grads
+
+
+def _sgd_step(nef, nef_params, obs, lat, lrs, xs, qs, ys, ws, channel, optimize_gaussian_window, rows, **kw):
+    """One inner step: obs.fit_step at ``lat``, then the meta-SGD update with the gradient of the batch-mean loss times B
+    (pde_trainer.py:206), scaled by the learned rates (:215-219); sigma only moves when asked to (:209-212).  ``rows``: None, or the
+    list that takes the step's loss_b."""
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    channel = channel_weights is not None
-    full = _full_grid_weights(img, weights, channel_weights)
-    lat, xs_all, ys_all, losses, ws_all = _gather_inputs(latents0, coords, img, masks, full, channel)
+    res = obs.fit_step(nef, nef_params, xs, qs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys, ws, channel, True, **kw)
+    if rows is not None:
+        rows.append(res[5])
+    grads = split_latent_grads(res[1], res[2], res[3] if optimize_gaussian_window else None, lat["p_pos"].shape[-1], n_ori > 0)
+    return meta_sgd_update(lat, grads, lrs, ys.shape[0])
+
+
+def _fit_loop(nef, nef_params, obs, latents0, lrs, data, masks, w, channel, optimize_gaussian_window, noise_pos, generator,
+              normalize_weights, per_signal_loss):
+    """The loop behind inner_loop and inner_loop_cells (fitting/observations.py: ``obs`` says which): gather once, jitter once, S steps,
+    the loss on the last mask.  ``w``: the full weights next to ``data``, float32 and contiguous, or None; ``channel``: they are per value."""
+    B, S, per_signal = data.shape[0], masks.shape[-1] - 1, masks.dim() == 3
+    lat, xs_all, qs_all, ys_all, losses, ws_all = obs.gather(latents0, data, masks, w, channel)
     if normalize_weights:
         if ws_all is None:
-            raise ValueError("normalize_weights needs sampled weights: pass weights= or per-signal masks")
+            raise ValueError("normalize_weights needs sampled weights: pass weights or per-signal masks")
         ws_all = normalize_sampled_weights(ws_all, channel=channel)
     if noise_pos:                                                                             # pde_trainer.py:162-167
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
-    n_pos = lat["p_pos"].shape[-1]
-    weight_kw = "channel_weight" if channel else "weight"      # the keyword that takes ws_all[s]: enf_fit_step_cw, or enf_fit_step_w
-
-    def sampled(s):     # step s's points -- every signal's own, or a stride-0 batch -- and weights
-        return xs_all[s] if per_signal else xs_all[s][None].expand(B, -1, -1), None if ws_all is None else ws_all[s]
-
-    rows = []                                                           # loss_b, with per_signal_loss
+    rows = [] if per_signal_loss else None                              # loss_b, with per_signal_loss
+    more = {"return_errors": True} if per_signal_loss else {}
     for s in range(S):                                                  # pde_trainer.py:191
-        xs, ws = sampled(s)
-        res = nef.mse_value_and_latent_grads(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[s],
-                                             loss_out=losses[s:s + 1], **{weight_kw: ws},
-                                             **({"return_errors": True} if per_signal_loss else {}),
-                                             **_shared_kw(nef, s, per_signal, noise_pos))
-        _, dp, da, dsig = res[:4]
-        if per_signal_loss:
-            rows.append(res[5])
-        # the gradient of the batch-mean loss times B (pde_trainer.py:206), scaled by the learned rates (:215-219);
-        # sigma only moves when asked to (:209-212)
-        grads = {"p_pos": dp[..., :n_pos], "a": da}
-        if n_ori > 0:
-            grads["p_ori"] = dp[..., n_pos:]
-        if optimize_gaussian_window and dsig is not None:
-            grads["gaussian_window"] = dsig
-        lat = meta_sgd_update(lat, grads, lrs, B)
-    xs, ws = sampled(S)
+        xs, qs, ws = obs.step_inputs(xs_all, qs_all, ws_all, s, B, per_signal)
+        lat = _sgd_step(nef, nef_params, obs, lat, lrs, xs, qs, ys_all[s], ws, channel, optimize_gaussian_window, rows,
+                        loss_out=losses[s:s + 1], **more, **(_shared_kw(nef, s, per_signal, noise_pos, step=obs.STEP) if obs.hints(channel) else {}))
+    xs, qs, ws = obs.step_inputs(xs_all, qs_all, ws_all, S, B, per_signal)
+    lb = obs.final_loss(nef, nef_params, xs, qs, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"),
+                        ys_all[S], ws, channel, losses[S:], per_signal_loss)
     if per_signal_loss:
-        lb, _ = nef.eval_loss(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys_all[S], loss_out=losses[S:],
-                              **{weight_kw: ws})
         rows.append(lb)
         return losses[S], lat, torch.stack(rows)
-    with torch.no_grad():                                               # pde_trainer.py:225-235
-        out = nef.apply(nef_params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window")).float().contiguous()
-        if out.shape != ys_all[S].shape:
-            raise AssertionError(f"targets have shape {tuple(ys_all[S].shape)}, expected {tuple(out.shape)}")
-        lib, n, loss = _lib.load(), out.numel(), losses[S:].data_ptr()
-        if ws is None:
-            fn, args = lib.enf_mse_value_grad, (n, 1.0, None, loss)
-        elif channel:
-            fn, args = lib.enf_mse_value_grad_cw, (ws.data_ptr(), n, 1.0, None, loss, None, 0, 0)
-        else:
-            fn, args = lib.enf_mse_value_grad_w, (ws.data_ptr(), n, out.shape[-1], 1.0, None, loss, None, 0, 0)
-        _lib.launch(out.device, fn, out.data_ptr(), ys_all[S].data_ptr(), *args, _lib.stream(out.device))
     return losses[S], lat
 
 

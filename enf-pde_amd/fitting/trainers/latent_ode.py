@@ -2,6 +2,9 @@
 at (a random subset of) the grid points and compare with the trajectory (pde_trainer.py:429-481 from the fitted latents on;
 nonmaml_pde_trainer.py:257-307 from the table's latents on -- the same lines).  The MAML trainer gets its frame-0 latents
 from the inner loop, the auto-decoder trainer from its latent table; from there on there is one copy, here.
+Whether the trajectory holds point values or cell means is asked of the observation value (fitting/observations.py: ``observed`` parses
+the step's four keywords): ``rollout_loss`` has one body for both, ``_errors`` is the one decode-free evaluation in chunks, and
+``sample_frames`` / ``sample_cell_frames`` are the two kinds' frame samplers by their old names.
 
 ``LatentODEMixin`` expects ``self.config`` (node.dt, node.method, training.max_num_sampled_points), ``self.nef``,
 ``self.ode_model``, ``self.coords`` and ``self.graph_ode_training``.
@@ -9,8 +12,8 @@ from the inner loop, the auto-decoder trainer from its latent table; from there 
 import torch
 
 from ..inner_loop import _pose
-from ..cells import cell_weight_kw, check_cells
-from ..weights import LossWeights, loss_tensor, weighted_mse
+from ..observations import Cells, Points, cell_loss_weights, observed      # (cell_loss_weights: re-exported)
+from ..weights import loss_tensor, weighted_mse
 from .trainer_utils.solvers import solve_latent_ode
 
 
@@ -40,62 +43,19 @@ def draw_point_masks(num_points, num_sampled, num_frames, generator=None, device
 def sample_frames(coords, traj, point_masks=None, weights=None):
     """Queries and targets of the B T signal-frames: ``coords`` (N, dx), ``traj`` (B, T, N, O), ``point_masks`` (T, n_s) long or
     None for the full grid.  Returns xs (B T, n, dx) and ys (B T, n, O), signal-major like the flattened roll-out; with
-    ``weights`` (B, T, N) also their gather ws (B T, n); per-channel weights (B, T, N, O) give ws (B T, n, O)."""
-    B, T, N, O = traj.shape
-    if point_masks is None:
-        xs, ys = coords[None].expand(B * T, -1, -1), traj.reshape(B * T, N, O)
-        return (xs, ys) if weights is None else (xs, ys, weights.reshape(B * T, N, *weights.shape[3:]))
-    n_s = point_masks.shape[1]
-    xs = coords[point_masks][None].expand(B, -1, -1, -1).reshape(B * T, n_s, -1)
-    ys = torch.gather(traj, 2, point_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n_s, O)
-    if weights is None:
-        return xs, ys
-    if weights.dim() == 4:
-        return xs, ys, torch.gather(weights, 2, point_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n_s, O)
-    return xs, ys, torch.gather(weights, 2, point_masks[None].expand(B, -1, -1)).reshape(B * T, n_s)
+    ``weights`` (B, T, N) also their gather ws (B T, n); per-channel weights (B, T, N, O) give ws (B T, n, O).
+    (fitting/observations.py: Points.sample_frames)"""
+    xs, _, ys, ws = Points(coords).sample_frames(traj, point_masks, weights)
+    return (xs, ys) if weights is None else (xs, ys, ws)
 
 
 def sample_cell_frames(cells, traj, cell_masks=None, weights=None):
     """sample_frames on cell averages: ``cells`` = (x (M G, dx), q (M G,) or None, group), ``traj`` (B, T, M, O) cell means,
-    ``cell_masks`` (T, m_s) long CELL indices or None for all M.  Returns xs (B T, m G, dx), qs (B T, m G) or None, ys (B T, m, O) and
-    ws -- None, (B T, m) from ``weights`` (B, T, M), or (B T, m, O) from per-value weights (B, T, M, O); row i G + k of a frame's set is
-    row c G + k of its cell c, signal-major like the flattened roll-out."""
-    x, q, G = cells
-    B, T, M, O = traj.shape
-    if cell_masks is None:
-        xs = x[None].expand(B * T, -1, -1)
-        qs = None if q is None else q[None].expand(B * T, -1)
-        return xs, qs, traj.reshape(B * T, M, O), None if weights is None else weights.reshape(B * T, M, *weights.shape[3:])
-    m_s = cell_masks.shape[1]
-    rows = (cell_masks[..., None] * G + torch.arange(G, device=cell_masks.device)).reshape(T, m_s * G)
-    xs = x[rows][None].expand(B, -1, -1, -1).reshape(B * T, m_s * G, -1)
-    qs = None if q is None else q[rows][None].expand(B, -1, -1).reshape(B * T, m_s * G)
-    ys = torch.gather(traj, 2, cell_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, m_s, O)
-    if weights is None:
-        ws = None
-    elif weights.dim() == 4:
-        ws = torch.gather(weights, 2, cell_masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, m_s, O)
-    else:
-        ws = torch.gather(weights, 2, cell_masks[None].expand(B, -1, -1)).reshape(B * T, m_s)
-    return xs, qs, ys, ws
-
-
-def cell_loss_weights(weights, cell_channel_weights, B, M, O, **kw):
-    """LossWeights.build for data on cells: ``weights`` per observation, ``cell_channel_weights`` per observed value; both at once is
-    a ValueError that names them."""
-    if weights is not None and cell_channel_weights is not None:
-        raise ValueError("pass weights= (one per observation) or cell_channel_weights= (one per observed value), not both")
-    return LossWeights.build(weights, cell_channel_weights, B, M, O, **kw)
+    ``cell_masks`` (T, m_s) long CELL indices or None for all M.  Returns (xs, qs, ys, ws) of Cells.sample_frames."""
+    return Cells(*cells, traj.shape[2]).sample_frames(traj, cell_masks, weights)
 
 
 class LatentODEMixin:
-    def _cells_of(self, what, cells, num_cells):
-        """``cells`` checked as meta_gradients checks them (fitting/cells.py: check_cells), and the decoder as the grouped fit step
-        does: the grouped calls are built for num_layers = 0."""
-        if getattr(self.nef, "num_layers", 0) > 0:
-            raise NotImplementedError(f"{what} with cells= is built for num_layers = 0 (the fused decoder)")
-        return check_cells(cells, num_cells)
-
     def rollout(self, ode_params, lat, num_frames, graph=False):
         """Latents of ``num_frames`` frames from those of frame 0: (B, T, Z, .) each (pde_trainer.py:432-441).  ``lat``: the
         latent dict of the inner loop, or the (p, a, window) tuple of an auto-decoder.
@@ -164,88 +124,57 @@ class LatentODEMixin:
         (not together with ``weights``); ``channel_weights`` with ``cells`` is a ValueError.
         ``fused`` (cells only): the loss does not decode -- nef.cell_fit_loss, ONE grouped fit step over the B T signal-frames whose
         latent gradients the backward scales; the nef weights get no gradient (ode_train_step: they are frozen there)."""
-        if cells is not None:
-            if channel_weights is not None:
-                raise ValueError("cells= takes per-observation weights= or cell_channel_weights=; channel_weights are not served on cells")
-            return self._rollout_loss_cells(nef_params, ode_params, lat, trajectory, point_masks, generator, graph, weights, normalize,
-                                            cells, cell_channel_weights, fused)
-        if cell_channel_weights is not None or fused:
-            raise ValueError("cell_channel_weights= and fused= go with cells=")
+        if fused and cells is None:
+            raise ValueError("fused= goes with cells=")
         B, T = trajectory.shape[:2]
-        N, n_s = self.coords.shape[0], self.config.training.max_num_sampled_points
-        fw = LossWeights.build(weights, channel_weights, B, N, trajectory.shape[-1], T=T, normalize=normalize, device=trajectory.device)
-        sol = self.rollout(ode_params, lat, T, graph=graph)
-        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
-        if n_s < N:                                                               # pde_trainer.py:446-471
-            if point_masks is None:
-                point_masks = draw_point_masks(N, n_s, T, generator, self.coords.device)
-        else:
+        obs, fw = observed(self.coords, weights, channel_weights, cells, cell_channel_weights, B, traj.shape[2], traj.shape[3], T=T,
+                           normalize=normalize, device=traj.device, nef=self.nef)
+        n_s = obs.num_sampled(self.config.training.max_num_sampled_points)
+        if n_s >= obs.num:                                                        # pde_trainer.py:446-471
             point_masks = None
-        xs, ys, *ws = sample_frames(self.coords, traj, point_masks, loss_tensor(fw))
-        recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
-        return weighted_mse(recon, ys, ws[0]) if ws else ((recon - ys) ** 2).mean()
-
-    def _rollout_loss_cells(self, nef_params, ode_params, lat, trajectory, cell_masks, generator, graph, weights, normalize, cells,
-                            cell_channel_weights, fused):
-        B, T = trajectory.shape[:2]
-        traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
-        M, O = traj.shape[2:]
-        cells = self._cells_of("rollout_loss", cells, M)
-        G = cells[2]
-        fw = cell_loss_weights(weights, cell_channel_weights, B, M, O, T=T, normalize=normalize, device=traj.device)
-        m_s = max(1, self.config.training.max_num_sampled_points // G)
-        if m_s < M:
-            if cell_masks is None:
-                cell_masks = draw_point_masks(M, m_s, T, generator, traj.device)
-        else:
-            cell_masks = None
+        elif point_masks is None:
+            point_masks = draw_point_masks(obs.num, n_s, T, generator, traj.device)
         sol = self.rollout(ode_params, lat, T, graph=graph)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
-        xs, qs, ys, ws = sample_cell_frames(cells, traj, cell_masks, loss_tensor(fw))
-        wkw = cell_weight_kw(ws, fw is not None and fw.channel)
+        xs, qs, ys, ws = obs.sample_frames(traj, point_masks, loss_tensor(fw))
         if fused:
-            return self.nef.cell_fit_loss(nef_params, xs, p_fl, a_fl, w_fl, ys, G, qweight=qs, **wkw)
-        recon = self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl)
-        return self.nef.cell_mse(recon, ys, G, qs, **wkw)
+            return obs.fused_loss(self.nef, nef_params, xs, qs, p_fl, a_fl, w_fl, ys, ws)
+        return obs.loss_of_decode(self.nef, self.nef.apply(nef_params, xs, p_fl, a_fl, w_fl), ys, qs, ws, weighted_mse)
 
     @torch.no_grad()
-    def _cell_frame_errors(self, nef_params, sol, trajectory, cells, fw=None, chunk=None):
-        """err_g (B T, M) and loss_b (B, T) of rolled-out latents ``sol`` (each (B, T, Z, .)) against ALL M cells of every frame of
-        ``trajectory`` (B, T, M, O), without a decode: nef.eval_cell_loss in chunks of ``chunk`` cells (None: one call), every chunk's
-        errors written into the one tensor and loss_b summed from it once, in a fixed order -- the same bits for every chunking."""
-        B, T, M, O = trajectory.shape
-        x, q, G = cells
-        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
-        tgt = trajectory.reshape(B * T, M, O)
-        w = None if fw is None else fw.w.reshape(B * T, M, *fw.w.shape[3:])
-        err = torch.empty((B * T, M), device=tgt.device, dtype=torch.float32)
-        step = M if chunk is None else max(1, int(chunk))
-        for i in range(0, M, step):
-            part = slice(i, min(i + step, M))
-            rows = slice(part.start * G, part.stop * G)
-            xs = x[rows][None].expand(B * T, -1, -1)
-            qs = None if q is None else q[rows][None].expand(B * T, -1)
-            _, e = self.nef.eval_cell_loss(nef_params, xs, p_fl, a_fl, w_fl, tgt[:, part], G, qweight=qs, per_signal=False,
-                                           **cell_weight_kw(None if w is None else w[:, part], fw is not None and fw.channel))
+    def _errors(self, nef_params, obs, p, a, window, targets, lw=None, chunk=None):
+        """err (n, num) of ``n`` signals with latents (p, a, window) against ALL ``num`` observations ``targets`` (n, num, O), without a
+        decode: obs.eval (nef.eval_loss / nef.eval_cell_loss) in chunks of ``chunk`` observations (None: one call), every chunk's errors
+        written into the one tensor, so that nef.signal_losses sums them once, in a fixed order -- the same bits for every chunking.
+        ``lw``: a LossWeights or None, its tensor read as (n, num[, O])."""
+        n, num = targets.shape[:2]
+        w = None if lw is None else lw.w.reshape(n, num, *lw.w.shape[lw.w.dim() - lw.channel:])
+        err = torch.empty((n, num), device=targets.device, dtype=torch.float32)
+        step = num if chunk is None else max(1, int(chunk))
+        for i in range(0, num, step):
+            part = slice(i, min(i + step, num))
+            _, e = obs.eval(self.nef, nef_params, part, n, p, a, window, targets[:, part], None if w is None else w[:, part],
+                            lw is not None and lw.channel)
             err[:, part] = e
-        return err, self.nef.signal_losses(err).reshape(B, T)
+        return err
 
     @torch.no_grad()
-    def _val_cells(self, nef_params, ode_params, lat, trajectory, num_in, cells, fw=None, return_frames=False, chunk=None):
+    def _val_cells(self, nef_params, ode_params, lat, trajectory, num_in, obs, fw=None, return_frames=False, chunk=None):
         """The validation roll-out on cell means ``trajectory`` (B, T, M, O) from frame-0 latents ``lat``: roll out, evaluate all M cells
-        of all B T signal-frames without a decode (_cell_frame_errors; ``chunk`` cells per call, default max_num_sampled_points //
-        group) and return (mean of loss_b over the first ``num_in`` frames, mean beyond them -- zero where there are none), with
-        ``return_frames`` followed by loss_b (B, T)."""
-        B, T = trajectory.shape[:2]
+        of all B T signal-frames without a decode (_errors; ``chunk`` cells per call, default max_num_sampled_points // group) and
+        return (mean of loss_b over the first ``num_in`` frames, mean beyond them -- zero where there are none), with ``return_frames``
+        followed by loss_b (B, T)."""
+        B, T, M, O = trajectory.shape
         if isinstance(lat, dict):
             lat = {k: v.detach() for k, v in lat.items()}
         else:
             lat = tuple(None if v is None else v.detach() for v in lat)
         sol = self.rollout(ode_params, lat, T, graph=T > 4)
+        p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         if chunk is None:
-            chunk = max(1, self.config.training.max_num_sampled_points // cells[2])
-        _, loss_b = self._cell_frame_errors(nef_params, sol, trajectory, cells, fw, chunk)
+            chunk = obs.num_sampled(self.config.training.max_num_sampled_points)
+        loss_b = self.nef.signal_losses(self._errors(nef_params, obs, p_fl, a_fl, w_fl, trajectory.reshape(B * T, M, O), fw, chunk)).reshape(B, T)
         e_in = loss_b[:, :num_in].mean()
         e_out = loss_b[:, num_in:].mean() if T > num_in else loss_b.new_zeros(())
         return (e_in, e_out, loss_b) if return_frames else (e_in, e_out)

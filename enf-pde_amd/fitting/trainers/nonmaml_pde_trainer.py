@@ -29,11 +29,11 @@ import torch
 
 from ..optim import Adam, AdamW, clip_by_global_norm, global_norm, scatter_rows, table_adam_update
 from ..parallel import allreduce_mean_
-from ..inner_loop import decode, make_signal_masks, gather_signal_points
-from ..weights import LossWeights, cut_frames, nef_kw, weighted_mse
-from ..cells import GROUP_SIZES, _batched, cell_weight_kw, gather_cell_samples
-from .latent_ode import LatentODEMixin, cell_loss_weights, _leaves, _unflatten
-from .pde_trainer import _NO_CHANNEL_WEIGHTS_ON_CELLS, _cell_kw, _tree_from_tensors
+from ..inner_loop import decode, split_latent_grads
+from ..weights import cut_frames, loss_tensor, weighted_mse
+from ..observations import observed
+from .latent_ode import LatentODEMixin, _leaves, _unflatten
+from .pde_trainer import _tree_from_tensors
 
 TRAIN_FRAMES, VAL_FRAMES = 10, 20            # fixed in the reference (:206,241,252), not read from the dataset config
 
@@ -105,64 +105,14 @@ class NonMetaPDETrainer(LatentODEMixin):
         state, epoch, _ = load_train_state(path, self.init_train_state(**init_kwargs))
         return state, epoch
 
-    def _fit_points(self, state, initial_state, mask, weights, normalize, channel_weights=None):
-        """What a nef step fits on (:311-335): (targets (B, n, O), coordinates (n, dx), the LossWeights of these points or None,
-        per-signal coordinates (B, n, dx) or None).  The one place where a nef step draws from ``state.rng``: loss_and_grads and
-        fit_latents_step both call it, so the two consume the generator alike.  With ``channel_weights`` (N, O) / (B, N, O) a
-        point counts as observed where any of its channels is."""
+    def _fit(self, state, initial_state, mask, weights, normalize, channel_weights, cells, cell_channel_weights):
+        """What a nef step fits: (obs, targets (B, n, O), xs (B, n G, dx), qs (B, n G) or None, ws (B, n[, O]) or None, whether ws is per
+        value) -- the four keywords parsed (fitting/observations.py: observed) and the subset drawn by obs.subset, the one place where a
+        nef step draws from ``state.rng``: loss_and_grads and fit_latents_step both call it, so the two consume the generator alike."""
         img = initial_state.reshape(initial_state.shape[0], -1, initial_state.shape[-1])
-        coords = self.coords
-        lw = LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device)
-        if mask is not None:                                                              # :321-323
-            img, coords, lw = img[:, mask], coords[mask], lw and lw.points(mask)
-        npts, xs = self.config.training.max_num_sampled_points, None
-        if self.sample_observed and lw is not None:      # every signal's own min(npts, N) observed points; -1 padding has weight 0
-            m = make_signal_masks(lw.support(), min(npts, coords.shape[0]), 0, generator=state.rng, device=coords.device)
-            # (the factor n_b / N of a draw from the observed points: the loss keeps the scale of the shared subset's)
-            xs, img, ws = (t[0] for t in gather_signal_points(coords, img, m, lw.drawn_on(m).w))
-            lw = LossWeights(ws, lw.channel)
-        elif npts < coords.shape[0]:                                                      # :326-335
-            sub = torch.randperm(coords.shape[0], generator=state.rng)[:npts].to(coords.device)
-            img, coords, lw = img[:, sub], coords[sub], lw and lw.points(sub)
-        return img, coords, lw, xs
-
-    def _fit_cells(self, state, obs, mask, weights, normalize, cells, cell_channel_weights=None):
-        """_fit_points on cell averages: ``cells`` = (x (M G, dx), q (M G,) or None, group), ``obs`` (B, M, O) cell means, ``mask``
-        and ``weights`` (M,) / (B, M) per observation.  Returns (targets (B, m, O), xs (B, m G, dx), qs (B, m G) or None, ws (B, m) or
-        None, group): at most max(1, max_num_sampled_points // group) cells, one subset for the batch (a stride-0 xs) or, with
-        ``sample_observed`` and weights, every signal's own observed cells with the weights rescaled for that draw.  The one place
-        where a step on cells draws from ``state.rng``.  ``cell_channel_weights`` (M, O) / (B, M, O) in place of ``weights``: one
-        weight per observed value, ws (B, m, O); a cell is observed where any of its values is."""
-        x, q, G = cells[0], cells[1], int(cells[2])
-        if G not in GROUP_SIZES:
-            raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
-        img = obs.reshape(obs.shape[0], -1, obs.shape[-1])
-        B, M, O = img.shape
-        if x.dim() != 2 or x.shape[0] != M * G:
-            raise ValueError(f"cells hold {tuple(x.shape)} quadrature points, the batch {M} cells of {G}")
-        lw = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=img.device)
-        pick = None
-        if mask is not None:
-            pick = torch.as_tensor(mask, device=img.device)
-            pick = pick.nonzero().reshape(-1) if pick.dtype == torch.bool else pick.long()
-        n = max(1, self.config.training.max_num_sampled_points // G)
-        if self.sample_observed and lw is not None:
-            if pick is not None:
-                keep = torch.zeros(M, dtype=torch.bool, device=img.device)
-                keep[pick] = True
-                lw = lw.keep(keep[None].expand(B, -1))
-            m = make_signal_masks(lw.support(), min(n, M), 0, generator=state.rng, device=img.device)
-            xs, qs, ys, ws = gather_cell_samples(x, q, G, img, m, **cell_weight_kw(lw.drawn_on(m).w, lw.channel))
-            return ys[0].to(img.dtype), xs[0], None if qs is None else qs[0], ws[0], G
-        if pick is None and n < M:
-            pick = torch.arange(M, device=img.device)
-        if pick is not None and n < pick.numel():
-            pick = pick[torch.randperm(pick.numel(), generator=state.rng)[:n].to(pick.device)]
-        if pick is not None:
-            rows = (pick[:, None] * G + torch.arange(G, device=pick.device)).reshape(-1)
-            img, x, q, lw = img[:, pick], x[rows], None if q is None else q[rows], lw and lw.points(pick)
-        xs, qs = _batched(x, q, B)
-        return img, xs, qs, None if lw is None else lw.w, G
+        obs, lw = observed(self.coords, weights, channel_weights, cells, cell_channel_weights, *img.shape, normalize=normalize, device=img.device)
+        img, xs, qs, lw = obs.subset(img, mask, lw, self.config.training.max_num_sampled_points, state.rng, self.sample_observed)
+        return obs, img, xs, qs, loss_tensor(lw), lw is not None and lw.channel
 
     def loss_and_grads(self, state, initial_state, traj_idx, mask=None, weights=None, normalize=True, channel_weights=None, cells=None,
                        cell_channel_weights=None):
@@ -172,29 +122,16 @@ class NonMetaPDETrainer(LatentODEMixin):
         ``channel_weights``: None, or (N, O) / (B, N, O) weights per value (mean 1 over each signal's N * O values unless
         ``normalize`` is False), for fields whose variables are observed separately; not together with ``weights``.
         ``cells``: None, or (x (M G, dx), q (M G,) or None, group): ``initial_state`` holds (B, M, O) cell means, ``mask`` and
-        ``weights`` are per observation (_fit_cells), and the loss is the grouped one (nef.cell_mse) of the decode at the sampled
+        ``weights`` are per observation (Cells.subset), and the loss is the grouped one (nef.cell_mse) of the decode at the sampled
         cells' quadrature points.  ``channel_weights`` with ``cells`` is a ValueError; ``cell_channel_weights`` (M, O) / (B, M, O) are
         the weights per observed value of the cells (not together with ``weights``)."""
-        if cells is not None:
-            if channel_weights is not None:
-                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells, cell_channel_weights)
-        elif cell_channel_weights is not None:
-            raise ValueError("cell_channel_weights= goes with cells=")
-        else:
-            img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
+        obs, img, xs, qs, ws, channel = self._fit(state, initial_state, mask, weights, normalize, channel_weights, cells, cell_channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         leaves = {k: P[k].detach().requires_grad_(True) for k in names}
         w = [t.detach().requires_grad_(True) for t in self.nef.param_tensors(state.params["nef"])]
         p, a, window = self.autodecoder.apply({"params": leaves}, traj_idx)               # :338
-        if xs is None:
-            xs = coords[None].expand(img.shape[0], -1, -1)
-        out = self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window)                     # :341
-        if cells is not None:
-            loss = self.nef.cell_mse(out, img, G, qs, **_cell_kw(ws))
-        else:
-            loss = ((out - img) ** 2).mean() if lw is None else weighted_mse(out, img, lw.w)
+        loss = obs.loss_of_decode(self.nef, self.nef.apply(_tree_from_tensors(w, self.nef), xs, p, a, window), img, qs, ws, weighted_mse)      # :341
         g = torch.autograd.grad(loss, w + [leaves[k] for k in names], allow_unused=True)
         gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
         ga = [torch.zeros_like(leaves[k]) if gi is None else gi for k, gi in zip(names, g[len(w):])]
@@ -233,7 +170,7 @@ class NonMetaPDETrainer(LatentODEMixin):
     def fit_latents_step(self, state, batch, mask=None, weights=None, normalize=True, channel_weights=None, per_signal_loss=False,
                          cells=None, cell_channel_weights=None):
         """nef_train_step_autodec_only (:139-171) on the native latent-only path: same arguments, same (loss, new_state), same draw
-        from ``state.rng`` (_fit_points), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
+        from ``state.rng`` (_fit), but nothing that only the weights need is computed.  The rows ``traj_idx`` of the table
         are read under no_grad, ONE nef.mse_value_and_latent_grads (enf_fit_step_w: forward, fused weighted loss, backward to the
         latents; neither ``out`` nor an autograd graph nor a weight gradient exists) returns the loss and the gradient w.r.t.
         those rows, and ONE enf_table_adam_update (optim.table_adam_update) applies optax adam to the whole table from them: rows
@@ -249,29 +186,15 @@ class NonMetaPDETrainer(LatentODEMixin):
         fit call is the grouped step, enf_fit_step_g (nef.mse_value_and_cell_grads); the table update is the same.
         ``cell_channel_weights`` (M, O) / (B, M, O), with ``cells``: weights per observed value, the one fit call is enf_fit_step_gc."""
         initial_state, traj_idx = batch
-        if cells is not None:
-            if channel_weights is not None:
-                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-            img, xs, qs, ws, G = self._fit_cells(state, initial_state, mask, weights, normalize, cells, cell_channel_weights)
-        elif cell_channel_weights is not None:
-            raise ValueError("cell_channel_weights= goes with cells=")
-        else:
-            img, coords, lw, xs = self._fit_points(state, initial_state, mask, weights, normalize, channel_weights)
+        obs, img, xs, qs, ws, channel = self._fit(state, initial_state, mask, weights, normalize, channel_weights, cells, cell_channel_weights)
         P = state.params["autodecoder"]["params"]
         names = list(P.keys())
         tables = [P[k].detach() for k in names]
         p, a, window = self.autodecoder.apply({"params": dict(zip(names, tables))}, traj_idx)
-        if xs is None:
-            xs = coords[None].expand(img.shape[0], -1, -1)
-        more = {"return_errors": True} if per_signal_loss else {}
-        if cells is not None:
-            loss, dp, da, dwin, *errs = self.nef.mse_value_and_cell_grads(state.params["nef"], xs, p, a, window, img, G, qweight=qs,
-                                                                          **_cell_kw(ws), **more)
-        else:
-            loss, dp, da, dwin, *errs = self.nef.mse_value_and_latent_grads(state.params["nef"], xs, p, a, window, img, **nef_kw(lw), **more)
+        loss, dp, da, dwin, *errs = obs.fit_step(self.nef, state.params["nef"], xs, qs, p, a, window, img, ws, channel,
+                                                 **({"return_errors": True} if per_signal_loss else {}))
         loss = loss.reshape(())
-        n_pos = P["p_pos"].shape[-1]
-        by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dwin}
+        by_name = split_latent_grads(dp, da, dwin, P["p_pos"].shape[-1])
         grads = [by_name.get(k) for k in names]
         grads = [torch.zeros((dp.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) if g is None else g
                  for g, t in zip(grads, tables)]                                             # e.g. a decoder without a window
@@ -302,12 +225,10 @@ class NonMetaPDETrainer(LatentODEMixin):
         self._need_ode("ode_loss")
         trajectory = trajectory[:, :TRAIN_FRAMES]                                # :252
         weights = cut_frames(weights, slice(TRAIN_FRAMES))                       # (B, T, N): the frames the loss sees
-        more = {}
-        if cells is not None or cell_channel_weights is not None or fused:
-            more = {"cells": cells, "cell_channel_weights": cut_frames(cell_channel_weights, slice(TRAIN_FRAMES), channel=True), "fused": fused}
+        cell_channel_weights = cut_frames(cell_channel_weights, slice(TRAIN_FRAMES), channel=True)
         z0 = self.autodecoder.apply(params["autodecoder"], traj_idx)             # :255
         return self.rollout_loss(params["nef"], params["ode_params"], z0, trajectory, point_masks, generator, graph=graph,
-                                 weights=weights, normalize=normalize, **more)
+                                 weights=weights, normalize=normalize, cells=cells, cell_channel_weights=cell_channel_weights, fused=fused)
 
     def ode_train_step(self, state, batch, point_masks=None, weights=None, normalize=True, cells=None, cell_channel_weights=None):
         """:173-199: one clip_by_global_norm(1) + AdamW step on the ODE parameters only.  ``batch`` = (trajectory (B, T, *grid, O),
@@ -333,9 +254,8 @@ class NonMetaPDETrainer(LatentODEMixin):
         P = state.params["autodecoder"]["params"]
         params = {"nef": state.params["nef"], "autodecoder": {"params": {k: v.detach() for k, v in P.items()}},
                   "ode_params": _unflatten(state.params["ode_params"], leaves)}
-        more = {} if cells is None and cell_channel_weights is None else \
-            {"cells": cells, "cell_channel_weights": cell_channel_weights, "fused": cells is not None}
-        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph, weights=weights, normalize=normalize, **more)
+        loss = self.ode_loss(params, trajectory, traj_idx, point_masks, state.rng, graph=graph, weights=weights, normalize=normalize,
+                             cells=cells, cell_channel_weights=cell_channel_weights, fused=cells is not None)
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
         grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
         flat = grads + [loss.detach().reshape(1)]
@@ -370,21 +290,15 @@ class NonMetaPDETrainer(LatentODEMixin):
         trajectory, traj_idx = batch[0], batch[-1]
         trajectory = trajectory[:, :VAL_FRAMES]                                  # :206
         B, T = trajectory.shape[:2]
-        if cells is not None:
-            if channel_weights is not None:
-                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-            traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
-            cells = self._cells_of("val_step", cells, traj.shape[2])
-            fw = cell_loss_weights(weights, cell_channel_weights, B, traj.shape[2], traj.shape[3], T=T, normalize=normalize,
-                                   device=traj.device, frames=slice(T))
-            z0 = (autodecoder or self.autodecoder).apply(state.params["autodecoder"], traj_idx)
-            return self._val_cells(state.params["nef"], state.params["ode_params"], z0, traj, TRAIN_FRAMES, cells, fw, return_frames, chunk)
-        if cell_channel_weights is not None or return_frames:
-            raise ValueError("cell_channel_weights= and return_frames= go with cells=")
-        # (N,) / (B, N) / (B, T, N) weights on the full grid, or per channel: the pair is then the two weighted errors
-        fw = LossWeights.build(weights, channel_weights, B, self.coords.shape[0], trajectory.shape[-1], T=T, normalize=normalize,
-                               device=self.coords.device, frames=slice(T))
+        if return_frames and cells is None:
+            raise ValueError("return_frames= goes with cells=")
+        traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
+        # weights with or without a frame axis, per point / observation or per value: the pair is then the two weighted errors
+        obs, fw = observed(self.coords, weights, channel_weights, cells, cell_channel_weights, B, traj.shape[2], traj.shape[3], T=T,
+                           normalize=normalize, device=traj.device, frames=slice(T), nef=self.nef)
         z0 = (autodecoder or self.autodecoder).apply(state.params["autodecoder"], traj_idx)     # :209-210
+        if cells is not None:      # no decode: all cells of all signal-frames evaluated by nef.eval_cell_loss
+            return self._val_cells(state.params["nef"], state.params["ode_params"], z0, traj, TRAIN_FRAMES, obs, fw, return_frames, chunk)
         sol = self.rollout(state.params["ode_params"], tuple(None if v is None else v.detach() for v in z0), T, graph=T > 4)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl,

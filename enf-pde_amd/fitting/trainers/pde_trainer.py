@@ -44,17 +44,16 @@ from types import SimpleNamespace
 import torch
 
 from ... import _lib
-from ..inner_loop import _pose, make_masks, make_signal_masks, gather_signal_points, inner_loop, decode
-from ..cells import _batched, cell_weight_kw, check_cells, gather_cell_samples, inner_loop_cells
-from .latent_ode import LatentODEMixin, cell_loss_weights, draw_point_masks, _leaves, _unflatten
+from ..inner_loop import _pose, make_masks, make_signal_masks, inner_loop, decode
+from ..cells import inner_loop_cells
+from ..observations import Cells, Points, observed
+from .latent_ode import LatentODEMixin, draw_point_masks, _leaves, _unflatten
 from ..optim import Adam, AdamW, clip_by_global_norm
 from ..parallel import allreduce_mean_
-from ..weights import LossWeights, cut_frames, loop_kw, nef_kw, loss_tensor, weighted_mse
+from ..weights import LossWeights, cut_frames, loss_tensor, weighted_mse
 from ...enf.models import TENSOR_PATHS, BLOCK_PATHS, tensor_paths, _get, _set
 
 LATENT_KEYS = ("p_pos", "p_ori", "a", "gaussian_window")
-_NO_CHANNEL_WEIGHTS_ON_CELLS = ("cells= takes per-observation weights= (M,) / (B, M) or cell_channel_weights= (M, O) / (B, M, O); "
-                                "channel_weights are not served on cells")
 
 
 def _tree_from_tensors(tensors, nef=None):
@@ -68,94 +67,18 @@ def _tree_from_tensors(tensors, nef=None):
     return {"params": out}
 
 
-def _sampled(coords, img, masks, s, weights, copies=1):
-    """The points of step ``s``: (xs (copies * B, N_s, dx), ys (B, N_s, O), weights (B, N_s) or None).  Shared masks (N_s, S+1) give
-    the reference's gather (pde_trainer.py:193-197) with a stride-0 batch; per-signal masks (B, N_s, S+1) give every signal its own
-    points and always weights (0 where the sampler padded with -1; fitting/inner_loop.py: gather_signal_points).  Per-channel
-    ``weights`` (B, N, O) come back as (B, N_s, O); weighted_mse tells the two apart by their rank."""
-    B = img.shape[0]
-    if masks.dim() == 2:
-        m = masks[:, s]
-        return coords[m][None].expand(copies * B, -1, -1), img[:, m], (None if weights is None else weights[:, m])
-    xs, ys, ws = gather_signal_points(coords, img, masks[:, :, s:s + 1], weights)
-    return (xs[0] if copies == 1 else xs[0].repeat(copies, 1, 1)), ys[0].to(img.dtype), ws[0]
-
-
-def _sampled_cells(cells, img, masks, s, weights, copies=1):
-    """The cells of step ``s`` (``cells`` = (x (M G, dx), q (M G,) or None, group); masks hold CELL indices): (xs (copies * B, Ms G, dx),
-    qs (B, Ms G) or None, ys (B, Ms, O), ws (B, Ms) or None) -- gather_cell_samples on column s, shared masks as a stride-0 batch;
-    per-signal masks give every signal its own cells and always weights (0 where the sampler padded with -1).  Per-value ``weights``
-    (B, M, O) come back as (B, Ms, O): on cells the two kinds differ by rank (_cell_kw)."""
-    x, q, G = cells
-    B = img.shape[0]
-    xs, qs, ys, ws = gather_cell_samples(x, q, G, img, masks[..., s:s + 1], **cell_weight_kw(weights, weights is not None and weights.dim() == 3))
-    xs, qs = xs[0], None if qs is None else qs[0]
-    if masks.dim() == 2:
-        xs, qs = _batched(xs, qs, B)
-        xs = xs if copies == 1 else xs[:1].expand(copies * B, -1, -1)
-    elif copies > 1:
-        xs = xs.repeat(copies, 1, 1)
-    return xs, qs, ys[0].to(img.dtype), None if ws is None else ws[0]
-
-
-def _cell_kw(ws):
-    """The keyword of a grouped call for sampled weights (B, Ms) per observation or (B, Ms, O) per value."""
-    return cell_weight_kw(ws, ws is not None and ws.dim() == 3)
-
-
-def _cell_loop_kw(lw):
-    """The keyword meta_gradients(cells=) and the trainer steps on cells take a LossWeights (or None) by."""
-    return {} if lw is None else {"cell_channel_weights" if lw.channel else "weights": lw.w}
-
-
-def _cell_fit_kw(lw):
-    """The keyword inner_loop_cells takes it by."""
-    return {} if lw is None else {"obs_channel_weight" if lw.channel else "obs_weights": lw.w}
-
-
-def _loss(nef, params, coords, img, masks, s, lat, weights=None, cells=None):
-    n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    if cells is not None:         # the grouped loss of the decode at the sampled cells' quadrature points (nef.cell_mse: one kernel)
-        xs, qs, ys, ws = _sampled_cells(cells, img, masks, s, weights)
-        out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
-        return nef.cell_mse(out, ys, cells[2], qs, **_cell_kw(ws))
-    xs, ys, ws = _sampled(coords, img, masks, s, weights)               # pde_trainer.py:193-197
-    out = nef.apply(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"))
-    if ws is None:
-        return ((out - ys) ** 2).mean()                                 # pde_trainer.py:185
-    return weighted_mse(out, ys, ws)                                    # (fitting/weights.py: the per-point weighted form)
-
-
-def _latent_grads(nef, params, coords, img, masks, s, lat, keys, weights=None):
-    leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
-    g = torch.autograd.grad(_loss(nef, params, coords, img, masks, s, leaves, weights), [leaves[k] for k in keys], allow_unused=True)
-    return {k: (torch.zeros_like(lat[k]) if gk is None else gk) for k, gk in zip(keys, g)}
-
-
-def _cell_latent_grads(nef, params, cells, img, masks, s, lat, keys, weights=None):
-    """_latent_grads against sampled cells: ONE grouped fit step (nef.mse_value_and_cell_grads: no decode, no autograd graph), whose
-    forward pair kernel records the relu masks when the caller has set them to "write"."""
-    n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    xs, qs, ys, ws = _sampled_cells(cells, img, masks, s, weights)
-    _, dp, da, dsig = nef.mse_value_and_cell_grads(params, xs, _pose(lat, n_ori), lat["a"], lat.get("gaussian_window"), ys, cells[2], qweight=qs,
-                                                   **_cell_kw(ws))
-    n_pos = lat["p_pos"].shape[-1]
-    by_name = {"p_pos": dp[..., :n_pos], "p_ori": dp[..., n_pos:], "a": da, "gaussian_window": dsig}
-    return {k: (torch.zeros_like(lat[k]) if by_name[k] is None else by_name[k].reshape(lat[k].shape)) for k in keys}
-
-
-def _full_grads(nef, weights, coords, img, masks, s, lat, keys, point_weights=None, cells=None):
+def _full_grads(nef, weights, obs, img, masks, s, lat, keys, point_weights=None):
     """(loss, grads w.r.t. the 46 weight tensors, grads w.r.t. the latents) on the training path."""
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
-    loss = _loss(nef, _tree_from_tensors(w, nef), coords, img, masks, s, leaves, point_weights, cells)
+    loss = obs.decode_loss(nef, _tree_from_tensors(w, nef), img, masks, s, leaves, point_weights, weighted_mse)
     g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
     gl = {k: (torch.zeros_like(lat[k]) if gi is None else gi) for k, gi in zip(keys, g[len(w):])}
     return loss.detach(), gw, gl
 
 
-def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf=None, point_weights=None, cells=None):
+def _diff_grads(nef, weights, obs, img, masks, s, plus, minus, keys, relu_buf=None, point_weights=None):
     """grads(plus) - grads(minus) of the step-s loss, w.r.t. the weights and the latents, in ONE training-path pass: the two
     latent sets run as one batch of 2B signals whose second half enters the loss with a minus sign (the outer step is
     bound by its many small kernels, so one pass of twice the batch costs about half of two passes)."""
@@ -163,18 +86,10 @@ def _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_buf
     w = [t.detach().requires_grad_(True) for t in weights]
     leaves = {k: torch.cat([plus[k], minus[k]], 0).detach().requires_grad_(True) for k in plus}
     n_ori = nef.cross_attn_invariant.num_z_ori_dims
-    if cells is not None:
-        xs, qs, ys, pw = _sampled_cells(cells, img, masks, s, point_weights, copies=2)
-    else:
-        xs, ys, pw = _sampled(coords, img, masks, s, point_weights, copies=2)     # (per-signal masks: signal b + B at the points of b)
+    xs, qs, ys, pw = obs.sampled(img, masks, s, point_weights, copies=2)      # (per-signal masks: signal b + B at the points of b)
     with (nef.relu_masks(relu_buf, "read", B) if relu_buf is not None else contextlib.nullcontext()):
         out = nef.apply(_tree_from_tensors(w, nef), xs, _pose(leaves, n_ori), leaves["a"], leaves.get("gaussian_window"))
-        if cells is not None:
-            loss = nef.cell_mse(out[:B], ys, cells[2], qs, **_cell_kw(pw)) - nef.cell_mse(out[B:], ys, cells[2], qs, **_cell_kw(pw))
-        elif pw is None:
-            loss = ((out[:B] - ys) ** 2).mean() - ((out[B:] - ys) ** 2).mean()
-        else:
-            loss = weighted_mse(out[:B], ys, pw) - weighted_mse(out[B:], ys, pw)
+        loss = obs.loss_of_decode(nef, out[:B], ys, qs, pw, weighted_mse) - obs.loss_of_decode(nef, out[B:], ys, qs, pw, weighted_mse)
         g = torch.autograd.grad(loss, w + [leaves[k] for k in keys], allow_unused=True)
     gw = [torch.zeros_like(t) if gi is None else gi for t, gi in zip(w, g[:len(w)])]
     gl = {k: (torch.zeros_like(plus[k]) if gi is None else gi[:B] + gi[B:]) for k, gi in zip(keys, g[len(w):])}
@@ -208,15 +123,8 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     ``weights``), mean 1 over each signal's M * O values unless ``normalize`` is False: every grouped pass takes them in place of the
     per-observation weights (enf_fit_step_gc, enf_mse_value_grad_gc).
     """
-    if cells is not None:
-        if channel_weights is not None:
-            raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-        cells = check_cells(cells, img.shape[1])
-        pw = loss_tensor(cell_loss_weights(weights, cell_channel_weights, *img.shape, normalize=normalize, device=img.device))
-    else:
-        if cell_channel_weights is not None:
-            raise ValueError("cell_channel_weights= goes with cells=")
-        pw = loss_tensor(LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device))
+    obs, pw = observed(coords, weights, channel_weights, cells, cell_channel_weights, *img.shape, normalize=normalize, device=img.device)
+    pw = loss_tensor(pw)
     if second_order not in ("fd", "none"):
         raise ValueError("second_order must be 'fd' or 'none'")
     if fd_step is None:      # truncation (~step^2) against the rounding of the first-order gradients (~1 / step): bf16 kernels
@@ -238,20 +146,16 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
     freeze = second_order == "fd" and freeze_relu and hasattr(nef, "relu_masks")
     for s in range(S):
         # (the forward of this pass also records the relu masks at phi_s for the adjoint sweep's frozen-mask differences)
-        rows = masks.shape[-2] * (cells[2] if cells is not None else 1)      # query rows of a step
-        relu_bufs.append(nef.relu_mask_buffer(B, rows, lat["a"].shape[1], img.device) if freeze else None)
+        relu_bufs.append(nef.relu_mask_buffer(B, masks.shape[-2] * obs.rows, lat["a"].shape[1], img.device) if freeze else None)
         with (nef.relu_masks(relu_bufs[s], "write", B) if freeze else contextlib.nullcontext()):
-            if cells is not None:
-                g = _cell_latent_grads(nef, frozen, cells, img, masks, s, lat, keys, pw)
-            else:
-                g = _latent_grads(nef, frozen, coords, img, masks, s, lat, keys, pw)
+            g = obs.latent_grads(nef, frozen, img, masks, s, lat, keys, pw, weighted_mse)
         g = {k: (torch.zeros_like(lat[k]) if (k not in g or masked(k)) else g[k] * B) for k in lat}    # pde_trainer.py:207
         phis.append(lat)
         gs.append(g)
         lat = {k: (lat[k] - lrs[k] * g[k]).detach() for k in lat}                                       # pde_trainer.py:215-219
     # ---- last step: value, d/d theta, lambda_S
     if terminal is None:
-        loss, g_theta, lam = _full_grads(nef, weights, coords, img, masks, S, lat, keys, pw, cells)
+        loss, g_theta, lam = _full_grads(nef, weights, obs, img, masks, S, lat, keys, pw)
     else:
         loss, g_theta, lam = terminal(weights, lat, keys)
     lam = {k: lam.get(k, torch.zeros_like(lat[k])) for k in lat}
@@ -274,7 +178,7 @@ def meta_gradients(nef, nef_params, latents0, lrs, coords, img, masks, optimize_
         # with the relu masks AT phi_s both perturbed passes differentiate the same piecewise-linear branch, so their
         # difference is the almost-everywhere second derivative (what jax.grad of the inner steps computes) instead of
         # also counting the units that flip between phi_s - eps w and phi_s + eps w
-        gw_d, gl_d = _diff_grads(nef, weights, coords, img, masks, s, plus, minus, keys, relu_bufs[s], pw, cells)
+        gw_d, gl_d = _diff_grads(nef, weights, obs, img, masks, s, plus, minus, keys, relu_bufs[s], pw)
         c = B / (2.0 * eps)                                                     # a 0-dim device tensor
         g_theta = list(torch._foreach_sub(g_theta, torch._foreach_mul(gw_d, c)))
         lam = {k: lam[k] - c * gl_d[k] if k in gl_d else lam[k] for k in lam}
@@ -395,29 +299,16 @@ class MetaSGDPDETrainer(LatentODEMixin):
         the outer gradients are averaged with one flat all-reduce before the (identical) optimiser updates."""
         cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
-        if cells is not None and channel_weights is not None:
-            raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-        # (point weights that this step does not draw from go on as they came: meta_gradients prepares them)
-        if cell_channel_weights is not None and cells is None:
-            raise ValueError("cell_channel_weights= goes with cells=")
-        lw, kw = None, {"weights": weights, "normalize": normalize}
-        if cell_channel_weights is not None:
-            lw = cell_loss_weights(weights, cell_channel_weights, *img.shape, normalize=normalize, device=img.device)
-        elif channel_weights is not None or (masks is None and self.sample_observed):
-            lw = LossWeights.build(weights, channel_weights, *img.shape, normalize=normalize, device=img.device)
+        obs, lw = observed(self.coords, weights, channel_weights, cells, cell_channel_weights, *img.shape, normalize=normalize, device=img.device)
         if masks is None:
-            masks, lw = self._draw_masks(state, img.shape[1] if cells is not None else self.coords.shape[0], lw,
-                                         group=int(cells[2]) if cells is not None else 1)
-        if lw is not None:
-            kw = dict(_cell_loop_kw(lw) if cells is not None else loop_kw(lw), normalize=False)
-        if cells is not None:
-            kw["cells"] = cells
+            masks, lw = self._draw_masks(state, obs.num, lw, group=obs.rows)
         lat0 = self._latents0(state)
         lrs = state.params["meta_sgd_lrs"]
         loss, grads = meta_gradients(self.nef, state.params["nef"], lat0, lrs, self.coords, img, masks,
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
-                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, **kw)
+                                     noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, normalize=False,
+                                     **obs.step_kw(lw))           # (the weights are prepared: meta_gradients takes them as they are)
         lat_keys, lr_keys = list(lat0.keys()), list(lrs.keys())
         flat = grads["nef"] + [grads["autodecoder"][k] for k in lat_keys] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])                               # SURVEY.md 8e: one exchange per outer step
@@ -459,44 +350,16 @@ class MetaSGDPDETrainer(LatentODEMixin):
         sampled cells and the evaluation nef.eval_cell_loss on ALL M cells (``chunk`` counts cells).  Returns (loss_b (B,), err_g (B, M)):
             err_g[b, m] = w[b, m] sum_o (obs - batch)^2, or sum_o cw[b, m, o] (obs - batch)^2       loss_b[b] = err_g[b].sum() / (M O)
         with ``weights`` (M,) / (B, M) per observation or ``cell_channel_weights`` (M, O) / (B, M, O) per observed value."""
-        cfg = self.config
         img = batch.reshape(batch.shape[0], -1, batch.shape[-1])
         B, N, O = img.shape
-        if cells is not None:
-            if channel_weights is not None:
-                raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-            cells = self._cells_of("fit_errors", cells, N)
-            lw = cell_loss_weights(weights, cell_channel_weights, B, N, O, normalize=normalize, device=img.device)
-            if not img.is_cuda:
-                raise _lib.EnfError("MetaSGDPDETrainer.fit_errors needs CUDA/HIP tensors: there is no CPU path")
-            lat = self._fitted_cells(state, img, masks, lw, cells)
-            sol = (_pose(lat, self.nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"))
-            fw = lw and LossWeights(lw.w[:, None], lw.channel)
-            err, loss_b = self._cell_frame_errors(state.params["nef"], tuple(None if v is None else v[:, None] for v in sol),
-                                                  img[:, None], cells, fw, chunk)
-            return loss_b.reshape(B), err
-        if cell_channel_weights is not None:
-            raise ValueError("cell_channel_weights= goes with cells=")
-        if not (img.is_cuda and self.coords.is_cuda):
+        obs, lw = observed(self.coords, weights, channel_weights, cells, cell_channel_weights, B, N, O, normalize=normalize, device=img.device,
+                           nef=self.nef)
+        if not (img.is_cuda and obs.x.is_cuda):
             raise _lib.EnfError("MetaSGDPDETrainer.fit_errors needs CUDA/HIP tensors: there is no CPU path")
-        lw = fit_lw = LossWeights.build(weights, channel_weights, B, N, O, normalize=normalize, device=img.device)
-        if masks is None:
-            masks, fit_lw = self._draw_masks(state, N, lw)
-        with torch.enable_grad():
-            # (per_signal_loss: the loop's own final loss comes from enf_eval_loss too -- nothing is decoded anywhere)
-            _, lat, _ = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], self.coords, img, masks,
-                                   optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
-                                   noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, per_signal_loss=True,
-                                   **loop_kw(fit_lw))
-        pose = _pose(lat, self.nef.cross_attn_invariant.num_z_ori_dims)
-        err = torch.empty((B, N), device=img.device, dtype=torch.float32)
-        step = N if chunk is None else max(1, int(chunk))
-        for i in range(0, N, step):
-            part = slice(i, min(i + step, N))
-            _, e = self.nef.eval_loss(state.params["nef"], self.coords[part][None].expand(B, -1, -1), pose, lat["a"],
-                                      lat.get("gaussian_window"), img[:, part], per_signal=False,
-                                      **nef_kw(lw and lw.points(part)))
-            err[:, part] = e
+        # (decode_free: the loop's own final loss comes from enf_eval_loss too -- nothing is decoded anywhere)
+        lat = self._fit_latents(state, obs, img, masks, lw, decode_free=True)
+        err = self._errors(state.params["nef"], obs, _pose(lat, self.nef.cross_attn_invariant.num_z_ori_dims), lat["a"],
+                           lat.get("gaussian_window"), img, lw, chunk)
         return self.nef.signal_losses(err), err
 
     def meta_gradient_report(self, state, batch, masks=None):
@@ -556,40 +419,36 @@ class MetaSGDPDETrainer(LatentODEMixin):
         return self.rollout_loss(nef_params, ode_params, lat, trajectory, point_masks, generator, graph=graph, weights=weights,
                                  normalize=normalize, channel_weights=channel_weights)
 
-    def _fitted(self, state, trajectory, masks, weights=None):
-        coords, img, masks, weights = self._fit_initial_latents(state, trajectory[:, 0], masks, weights=weights)
+    def _fit_latents(self, state, obs, img, masks, lw, noise=True, decode_free=False):
+        """The latents of ``img`` (B, num, O) -- grid values or cell means, as ``obs`` says -- after the inner loop (inner_loop on Points,
+        inner_loop_cells on Cells; obs.loop_args), detached: on ``masks``, or on masks of obs.num_sampled(max_num_sampled_points)
+        observations drawn here (_draw_masks), with the weights ``lw`` (a LossWeights over (B, num[, O]) or None).  ``noise`` False:
+        without the training steps' pose noise, as val_step fits.  ``decode_free``: the loop's last loss is not to decode either."""
         cfg = self.config
-        _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
-                            optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
-                            noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, **loop_kw(weights))
-        return {k: v.detach() for k, v in lat.items()}
+        if masks is None:
+            masks, lw = self._draw_masks(state, obs.num, lw, group=obs.rows)
+        args, kw = obs.loop_args(img, masks, lw, decode_free)
+        with torch.enable_grad():
+            res = (inner_loop if isinstance(obs, Points) else inner_loop_cells)(
+                self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], *args,
+                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
+                noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0) if noise else 0.0, generator=state.rng, **kw)
+        return {k: v.detach() for k, v in res[1].items()}
+
+    def _fitted(self, state, trajectory, masks, weights=None):
+        """_fit_latents on frame 0 of a trajectory of grid values."""
+        return self._fit_latents(state, Points(self.coords), trajectory[:, 0].reshape(trajectory.shape[0], -1, trajectory.shape[-1]), masks, weights)
 
     def _fitted_cells(self, state, img, masks, lw, cells, noise=True):
-        """_fitted on cell means ``img`` (B, M, O): masks of max(1, max_num_sampled_points // group) cells (drawn here when None,
-        _draw_masks), then inner_loop_cells with the weights ``lw`` (a LossWeights over (B, M[, O]) or None).  ``noise`` False: without
-        the training steps' pose noise, as val_step fits."""
-        cfg = self.config
-        x, q, G = cells
-        if masks is None:
-            masks, lw = self._draw_masks(state, img.shape[1], lw, group=G)
-        with torch.enable_grad():
-            _, lat = inner_loop_cells(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], x, q, G, img, masks,
-                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
-                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0) if noise else 0.0, generator=state.rng,
-                                      **_cell_fit_kw(lw))
-        return {k: v.detach() for k, v in lat.items()}
+        """_fit_latents on cell means ``img`` (B, M, O) of ``cells`` = (x, q, group)."""
+        return self._fit_latents(state, Cells(*cells, img.shape[1]), img, masks, lw, noise)
 
-    def _cell_trajectory(self, what, trajectory, cells, channel_weights):
-        """``trajectory`` (B, T, ..., O) as (B, T, M, O) cell means and ``cells`` checked against M."""
-        if channel_weights is not None:
-            raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
-        traj = trajectory.reshape(trajectory.shape[0], trajectory.shape[1], -1, trajectory.shape[-1])
-        return traj, self._cells_of(what, cells, traj.shape[2])
-
-    def _frame0(self, trajectory, weights, channel_weights, normalize):
-        """The LossWeights of the fit on frame 0 of ``trajectory`` (B, T, *grid, O), or None."""
-        return LossWeights.build(weights, channel_weights, trajectory.shape[0], self.coords.shape[0], trajectory.shape[-1],
-                                 normalize=normalize, device=self.coords.device, frames=0)
+    def _frames(self, trajectory, weights, channel_weights, cell_channel_weights, num_frames):
+        """The first ``num_frames`` frames of ``trajectory`` as (B, T, num, O), and of the three weights where they have a frame axis."""
+        part = slice(num_frames)
+        traj = trajectory[:, part]
+        return (traj.reshape(traj.shape[0], traj.shape[1], -1, traj.shape[-1]), cut_frames(weights, part),
+                cut_frames(channel_weights, part, channel=True), cut_frames(cell_channel_weights, part, channel=True))
 
     def ode_train_step(self, state, trajectory, masks=None, point_masks=None, weights=None, normalize=True, cells=None,
                        cell_channel_weights=None):
@@ -601,29 +460,20 @@ class MetaSGDPDETrainer(LatentODEMixin):
         (B, M, O) / (B, T, M, O) per observed value (not both).  Frame 0 is fitted with inner_loop_cells, and the roll-out loss does
         not decode: the nef weights are frozen, so it is nef.cell_fit_loss -- one grouped fit step over the B T signal-frames
         (rollout_loss(cells=, fused=True))."""
-        cfg = self.config
-        trajectory = trajectory[:, :cfg.dataset.traj_len_train]                  # pde_trainer.py:421-422
-        weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
+        traj, weights, _, cell_channel_weights = self._frames(trajectory, weights, None, cell_channel_weights,
+                                                              self.config.dataset.traj_len_train)                  # pde_trainer.py:421-422
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
-        if cells is not None:
-            trajectory, cells = self._cell_trajectory("ode_train_step", trajectory, cells, None)
-            cell_channel_weights = cut_frames(cell_channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
-            B, _, M, O = trajectory.shape
-            lw0 = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=trajectory.device, frames=0)
-            lat = self._fitted_cells(state, trajectory[:, 0], masks, lw0, cells)
-            loss = self.rollout_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
-                                     normalize=normalize, cells=cells, cell_channel_weights=cell_channel_weights, fused=True)
-        else:
-            if cell_channel_weights is not None:
-                raise ValueError("cell_channel_weights= goes with cells=")
-            lat = self._fitted(state, trajectory, masks, self._frame0(trajectory, weights, None, normalize))
-            loss = self.ode_loss(state.params["nef"], ode_params, lat, trajectory, point_masks, state.rng, graph=graph, weights=weights,
-                                 normalize=normalize)
+        B, _, num, O = traj.shape
+        obs, lw0 = observed(self.coords, weights, None, cells, cell_channel_weights, B, num, O, normalize=normalize, device=traj.device, frames=0,
+                            nef=self.nef)
+        lat = self._fit_latents(state, obs, traj[:, 0], masks, lw0)
+        loss = self.rollout_loss(state.params["nef"], ode_params, lat, traj, point_masks, state.rng, graph=graph, weights=weights,
+                                 normalize=normalize, cells=cells, cell_channel_weights=cell_channel_weights, fused=cells is not None)
         grads = list(torch.autograd.grad(loss, leaves, allow_unused=True))
         grads = [torch.zeros_like(t) if g is None else g for t, g in zip(leaves, grads)]
         flat = grads + [loss.detach().reshape(1)]
-        allreduce_mean_(flat, weight=trajectory.shape[0])
+        allreduce_mean_(flat, weight=B)
         new_leaves, ode_opt_state = self.ode_opt.update(grads, state.ode_opt_state, [t.detach() for t in leaves])
         params = dict(state.params, ode_params=_unflatten(state.params["ode_params"], new_leaves))
         return flat[-1][0], TrainState(params=params, nef_opt_state=state.nef_opt_state,
@@ -641,41 +491,27 @@ class MetaSGDPDETrainer(LatentODEMixin):
         ``cells`` / ``cell_channel_weights``: as in ode_train_step.  The fit's meta-gradient is meta_gradients(cells=), and the
         terminal roll-out loss is taken through nef.apply + nef.cell_mse (rollout_loss(cells=)): it needs the weight gradients."""
         cfg = self.config
-        trajectory = trajectory[:, :cfg.dataset.traj_len_train]
-        more = {}
-        if cells is not None:
-            trajectory, cells = self._cell_trajectory("dual_train_step", trajectory, cells, channel_weights)
-            B, _, M, O = trajectory.shape
-            lw0 = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=trajectory.device, frames=0)
-            weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
-            cell_channel_weights = cut_frames(cell_channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
-            coords, img, G = None, trajectory[:, 0], cells[2]
-            if masks is None:
-                masks, lw0 = self._draw_masks(state, M, lw0, group=G)
-            num, n_s = M, max(1, cfg.training.max_num_sampled_points // G)
-            more = {"cells": cells, "cell_channel_weights": cell_channel_weights}
-        else:
-            if cell_channel_weights is not None:
-                raise ValueError("cell_channel_weights= goes with cells=")
-            lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
-            weights = cut_frames(weights, slice(cfg.dataset.traj_len_train))
-            channel_weights = cut_frames(channel_weights, slice(cfg.dataset.traj_len_train), channel=True)
-            coords, img, masks, lw0 = self._fit_initial_latents(state, trajectory[:, 0], masks, weights=lw0)
-            num, n_s = self.coords.shape[0], cfg.training.max_num_sampled_points
-            more = {"channel_weights": channel_weights}
+        traj, weights, channel_weights, cell_channel_weights = self._frames(trajectory, weights, channel_weights, cell_channel_weights,
+                                                                            cfg.dataset.traj_len_train)
+        B, T, num, O = traj.shape
+        obs, lw0 = observed(self.coords, weights, channel_weights, cells, cell_channel_weights, B, num, O, normalize=normalize, device=traj.device,
+                            frames=0, nef=self.nef)
+        img = traj[:, 0]
+        if masks is None:
+            masks, lw0 = self._draw_masks(state, obs.num, lw0, group=obs.rows)
         leaves, graph = self._ode_train_leaves(state.params["ode_params"])
         ode_params = _unflatten(state.params["ode_params"], leaves)
-        if point_masks is None and n_s < num:
-            point_masks = draw_point_masks(num, n_s, trajectory.shape[1], state.rng, trajectory.device if cells is not None else self.coords.device)
+        n_s = obs.num_sampled(cfg.training.max_num_sampled_points)
+        if point_masks is None and n_s < obs.num:
+            point_masks = draw_point_masks(obs.num, n_s, T, state.rng, traj.device)
         side = {}
         point_weights = weights             # (`weights` below are the network's)
 
         def terminal(weights, lat, keys):
             w = [t.detach().requires_grad_(True) for t in weights]
             lv = {k: lat[k].detach().requires_grad_(True) for k in lat}
-            loss = (self.rollout_loss if cells is not None else self.ode_loss)(
-                _tree_from_tensors(w, self.nef), ode_params, lv, trajectory, point_masks, graph=graph, weights=point_weights,
-                normalize=normalize, **more)
+            loss = self.rollout_loss(_tree_from_tensors(w, self.nef), ode_params, lv, traj, point_masks, graph=graph, weights=point_weights,
+                                     normalize=normalize, channel_weights=channel_weights, cells=cells, cell_channel_weights=cell_channel_weights)
             g = torch.autograd.grad(loss, w + [lv[k] for k in keys] + leaves, allow_unused=True)
             z = lambda t, gi: torch.zeros_like(t) if gi is None else gi
             side["ode"] = [z(t, gi) for t, gi in zip(leaves, g[len(w) + len(keys):])]
@@ -683,11 +519,11 @@ class MetaSGDPDETrainer(LatentODEMixin):
                 {k: z(lat[k], gi) for k, gi in zip(keys, g[len(w):len(w) + len(keys)])}
 
         lrs = state.params["meta_sgd_lrs"]
-        loss, grads = meta_gradients(self.nef, state.params["nef"], self._latents0(state), lrs, coords, img, masks,
+        loss, grads = meta_gradients(self.nef, state.params["nef"], self._latents0(state), lrs, self.coords, img, masks,
                                      optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False),
                                      second_order=self.second_order, fd_step=self.fd_step,
                                      noise_pos=getattr(cfg.meta, "noise_pos_inner_loop", 0.0), generator=state.rng, terminal=terminal,
-                                     normalize=False, **(dict(_cell_loop_kw(lw0), cells=cells) if cells is not None else loop_kw(lw0)))
+                                     normalize=False, **obs.step_kw(lw0))
         lr_keys = list(lrs.keys())
         flat = grads["nef"] + [grads["meta_sgd_lrs"][k] for k in lr_keys] + side["ode"] + [loss.reshape(1)]
         allreduce_mean_(flat, weight=img.shape[0])
@@ -737,17 +573,6 @@ class MetaSGDPDETrainer(LatentODEMixin):
             total, n = total + float(loss), n + 1
         return total / max(n, 1), state
 
-    def _val_step_cells(self, state, trajectory, T_in, masks, weights, normalize, channel_weights, cells, cell_channel_weights,
-                        return_frames, chunk):
-        trajectory, cells = self._cell_trajectory("val_step", trajectory, cells, channel_weights)
-        B, T, M, O = trajectory.shape
-        lw0 = cell_loss_weights(weights, cell_channel_weights, B, M, O, normalize=normalize, device=trajectory.device, frames=0)
-        fw = cell_loss_weights(weights, cell_channel_weights, B, M, O, T=T, normalize=normalize, device=trajectory.device, frames=slice(T))
-        if not trajectory.is_cuda:
-            raise _lib.EnfError("MetaSGDPDETrainer.val_step(cells=) needs CUDA/HIP tensors: there is no CPU path")
-        lat = self._fitted_cells(state, trajectory[:, 0], masks, lw0, cells, noise=False)
-        return self._val_cells(state.params["nef"], state.params["ode_params"], lat, trajectory, T_in, cells, fw, return_frames, chunk)
-
     @torch.no_grad()
     def val_step(self, state, trajectory, initial_state_dp=0.0, masks=None, weights=None, normalize=True, drop_rate=None,
                  channel_weights=None, cells=None, cell_channel_weights=None, return_frames=False, chunk=None):
@@ -774,15 +599,17 @@ class MetaSGDPDETrainer(LatentODEMixin):
         T_in = cfg.dataset.traj_len_train
         trajectory = trajectory[:, :T_in + cfg.dataset.traj_len_out_horizon]
         B, T = trajectory.shape[:2]
-        if cells is not None:
-            if drop_rate is not None or initial_state_dp > 0:
-                raise ValueError("drop_rate and initial_state_dp are not served on cells")
-            return self._val_step_cells(state, trajectory, T_in, masks, weights, normalize, channel_weights, cells, cell_channel_weights,
-                                        return_frames, chunk)
-        if cell_channel_weights is not None or return_frames:
-            raise ValueError("cell_channel_weights= and return_frames= go with cells=")
-        N, O = self.coords.shape[0], trajectory.shape[-1]
-        lw0 = self._frame0(trajectory, weights, channel_weights, normalize)
+        if cells is not None and (drop_rate is not None or initial_state_dp > 0):
+            raise ValueError("drop_rate and initial_state_dp are not served on cells")
+        if return_frames and cells is None:
+            raise ValueError("return_frames= goes with cells=")
+        traj = trajectory.reshape(B, T, -1, trajectory.shape[-1])
+        N, O = traj.shape[2:]
+        parse = lambda **kw: observed(self.coords, weights, channel_weights, cells, cell_channel_weights, B, N, O, normalize=normalize,
+                                      device=traj.device, nef=self.nef, **kw)
+        obs, lw0 = parse(frames=0)
+        fw = parse(T=T, frames=slice(T))[1]
+        img = traj[:, 0]
         if drop_rate is not None:
             if not 0.0 <= drop_rate < 1.0:
                 raise ValueError(f"drop_rate must lie in [0, 1), got {drop_rate}")
@@ -791,21 +618,20 @@ class MetaSGDPDETrainer(LatentODEMixin):
             kept = torch.rand((B, N), generator=state.rng) >= drop_rate
             if lw0 is not None:
                 kept &= (lw0.support() > 0).cpu()
-            coords, img = self.coords, trajectory[:, 0].reshape(B, -1, O)
             masks = make_signal_masks(kept, max(1, min(cfg.training.max_num_sampled_points, int((1.0 - drop_rate) * N))),
-                                      cfg.meta.num_inner_steps, generator=state.rng, device=coords.device)
+                                      cfg.meta.num_inner_steps, generator=state.rng, device=self.coords.device)
             # what the signal kept is its observed set: weights of mean 1 over the grid again (as normalize asks), then the
             # factor of a draw from the observed points -- the fit's loss keeps the scale of a fit without drop-out
-            kept = kept.to(coords.device)
+            kept = kept.to(self.coords.device)
             lw0 = LossWeights(kept.float()) if lw0 is None else lw0.keep(kept)
             lw0 = (lw0.renormalized() if normalize else lw0).observed_draw(masks.shape[1])
-        else:
-            coords, img, masks, lw0 = self._fit_initial_latents(state, trajectory[:, 0], masks, initial_state_dp, lw0)
-        with torch.enable_grad():
-            _, lat = inner_loop(self.nef, state.params["nef"], self._latents0(state), state.params["meta_sgd_lrs"], coords, img, masks,
-                                optimize_gaussian_window=getattr(cfg.nef, "optimize_gaussian_window", False), **loop_kw(lw0))
-        sol = self.rollout(state.params["ode_params"], {k: v.detach() for k, v in lat.items()}, T, graph=T > 4)
+        elif initial_state_dp > 0:
+            coords, img, masks, lw0 = self._fit_initial_latents(state, img, masks, initial_state_dp, lw0)
+            obs = Points(coords)
+        lat = self._fit_latents(state, obs, img, masks, lw0, noise=False)
+        if cells is not None:      # no decode: all cells of all signal-frames evaluated by nef.eval_cell_loss
+            return self._val_cells(state.params["nef"], state.params["ode_params"], lat, traj, T_in, obs, fw, return_frames, chunk)
+        sol = self.rollout(state.params["ode_params"], lat, T, graph=T > 4)
         p_fl, a_fl, w_fl = (None if v is None else v.reshape(B * T, *v.shape[2:]) for v in sol)
         recon = decode(self.nef, state.params["nef"], self.coords, p_fl, a_fl, w_fl).reshape(trajectory.shape)
-        fw = LossWeights.build(weights, channel_weights, B, N, O, T=T, normalize=normalize, device=recon.device, frames=slice(T))
         return self._horizon_errors(recon, trajectory, T_in, fw)

@@ -76,13 +76,13 @@ T.rff_net = rff_masked
 _orig_diff = PT._diff_grads
 
 
-def diff_frozen(nef, weights, coords, img, masks, s, plus, minus, keys):
+def diff_frozen(nef, weights, obs, img, masks, s, plus, minus, keys, *rest):
     base = {k: 0.5 * (plus[k] + minus[k]) for k in plus}              # phi_s
     STATE.update(mode="write", masks=[], i=0)
     with torch.no_grad():
-        PT._loss(nef, PT._tree_from_tensors([w.detach() for w in weights]), coords, img, masks, s, base)
+        obs.decode_loss(nef, PT._tree_from_tensors([w.detach() for w in weights]), img, masks, s, base, None, PT.weighted_mse)
     STATE.update(mode="read", i=0)
-    out = _orig_diff(nef, weights, coords, img, masks, s, plus, minus, keys)
+    out = _orig_diff(nef, weights, obs, img, masks, s, plus, minus, keys)
     STATE.update(mode=None)
     return out
 

@@ -3,6 +3,7 @@ enf_fit_step_gs): the torch-op mirrors of the two new kernels against fp64 state
 against tests/cells_ref.py: fit_loop, the refusals of the three C calls (every call here fails its checks, so nothing is launched), and
 the yardstick of the grouped meta-gradient (tests/cells_train_ref.py) against central differences of its own loss."""
 import copy
+import importlib
 import ctypes
 import os
 import re
@@ -120,7 +121,7 @@ def test_inner_loop_cells_reproduces_the_reference_loop(monkeypatch):
     c = case("rel_pos_periodic", 4, 16)
     S, M = 2, c.M
     lr_p, lr_a = 0.7, np.linspace(1.0, 3.0, c.a.shape[-1])
-    monkeypatch.setattr(CELLS, "meta_sgd_update", lambda lat, g, lrs, scale: {k: (lat[k] - lrs[k] * (scale * g[k]) if k in g else lat[k]) for k in lat})
+    monkeypatch.setattr(importlib.import_module("enf_pde_amd.fitting.inner_loop"), "meta_sgd_update", lambda lat, g, lrs, scale: {k: (lat[k] - lrs[k] * (scale * g[k]) if k in g else lat[k]) for k in lat})
     t = torch.tensor
     lat0 = {"p_pos": t(c.p[:1]), "a": t(c.a[:1]), "gaussian_window": t(c.s[:1])}
     lrs = {"p_pos": t([lr_p], dtype=torch.float64), "a": t(lr_a), "gaussian_window": t([0.0], dtype=torch.float64)}
