@@ -28,6 +28,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_fit_step_e", "enf_eval_loss", "enf_signal_sum", "enf_fit_step_g", "enf_eval_loss_g",
            "enf_fit_step_gs", "enf_mse_value_grad_g", "enf_fit_inputs_g",
            "enf_fit_step_gc", "enf_eval_loss_gc", "enf_mse_value_grad_gc", "enf_fit_inputs_gc",
+           "enf_obs_apply", "enf_mse_a_scratch_bytes", "enf_mse_value_grad_a", "enf_obs_workspace_bytes", "enf_fit_step_a", "enf_eval_loss_a",
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
            "enf_field_second_workspace_bytes", "enf_field_second_x",
@@ -97,6 +98,12 @@ class EnfCgSegment(ctypes.Structure):
     """One latent component of a batched conjugate-gradient step (include/enf_hip.h: enf_cg_update)."""
     _fields_ = [("x", ctypes.c_void_p), ("r", ctypes.c_void_p), ("d", ctypes.c_void_p), ("q", ctypes.c_void_p),
                 ("width", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class EnfSparseObs(ctypes.Structure):
+    """A sparse linear observation operator, CSR and CSC on the device (include/enf_hip.h, "Sparse linear observations")."""
+    _fields_ = [("M", ctypes.c_int32), ("nnz", ctypes.c_int64), ("row_ptr", ctypes.c_void_p), ("col", ctypes.c_void_p),
+                ("val", ctypes.c_void_p), ("col_ptr", ctypes.c_void_p), ("trow", ctypes.c_void_p), ("tval", ctypes.c_void_p)]
 
 
 class EnfFitComponent(ctypes.Structure):
@@ -265,6 +272,18 @@ def _bind(path, hooks):
     lib.enf_eval_loss_gc.argtypes = list(lib.enf_eval_loss_g.argtypes)
     lib.enf_mse_value_grad_gc.argtypes = list(lib.enf_mse_value_grad_g.argtypes)
     lib.enf_fit_inputs_gc.argtypes = list(lib.enf_fit_inputs_g.argtypes)
+    # sparse linear observations (include/enf_hip.h): out, B, N, O, op, obs, stream | out, target, B, N, O, op, oweight, cweight,
+    # grad_scale, dout, loss, err_a, scratch, bytes, flags, stream | the fit step and the evaluation: enf_fit_step_g's / enf_eval_loss_g's
+    # arguments with (op, oweight, cweight) in place of (G, qweight, oweight)
+    op = ctypes.POINTER(EnfSparseObs)
+    lib.enf_obs_apply.argtypes = [vp] + [ctypes.c_int32] * 3 + [op, vp, vp]
+    lib.enf_mse_a_scratch_bytes.restype = sz
+    lib.enf_mse_a_scratch_bytes.argtypes = [ctypes.c_int32] * 3 + [ci, cu]
+    lib.enf_mse_value_grad_a.argtypes = [vp, vp] + [ctypes.c_int32] * 3 + [op, vp, vp, ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
+    lib.enf_obs_workspace_bytes.restype = sz
+    lib.enf_obs_workspace_bytes.argtypes = [dp, ctypes.c_int32, cu]
+    lib.enf_fit_step_a.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, op, vp, vp, ctypes.c_float] + [vp] * 7 + [sz, cu, vp]
+    lib.enf_eval_loss_a.argtypes = [dp, vp, i64, vp, vp, vp, vp, vp, op] + [vp] * 6 + [sz, cu, vp]
     # derivative fields (include/enf_hip.h, "Derivative fields"): out (B, N, O) | NULL, jac (O, B, N, dx); dout (B, N, O), dx (B, N, dx)
     lib.enf_field_grad_workspace_bytes.restype = sz
     lib.enf_field_grad_workspace_bytes.argtypes = [dp, cu]

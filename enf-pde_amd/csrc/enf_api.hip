@@ -292,10 +292,15 @@ extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstri
 // end of the sequence on the same stream; args_ok: the entry point's own argument checks (ENF_EINVAL, behind the descriptor's errors).
 // grp != NULL (enf_fit_step_g): the loss against grouped observations -- `target` is (B, N / G, O), the weights and errors are grp's (per
 // observation; weight, per_value and err stay unset), loss_b sums grp->err_g over a signal's N / G observations.
+// ao != NULL (enf_fit_step_a): the loss against a sparse linear operator (include/enf_hip.h, "Sparse linear observations") -- `target` is
+// (B, M, O), the weights are ao's and the errors go through `err`; the tail runs forward with its stash and backward on it, the two products of enf_obs.hip
+// between them, on the regions of enf_obs_workspace behind the workspace (weight, per_value, err and grp stay unset).
+struct ObsStep { const EnfSparseObs* op; const float* oweight; const float* cweight; };
 static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                              float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, bool per_value, unsigned flags,
-                             void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true, const EnfGroupObs* grp = nullptr) {
+                             void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true, const EnfGroupObs* grp = nullptr,
+                             const ObsStep* ao = nullptr) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
   // ENF_FIT_SHARED_LATENTS (include/enf_hip.h): a permission for the forward pair kernel; with one signal it says nothing
@@ -307,6 +312,8 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
   const bool zb = enf_use_zfold_bwd(m);
+  const EnfObsWorkspace Y = enf_obs_workspace(m, det ? c.X.total : W.total, ao ? ao->op->M : 1);
+  if (ao && workspace_bytes < Y.total) return ENF_EWORKSPACE;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
   // (shared: the parts of the one forward borrow d ybar | delta, which this step's tail overwrites afterwards)
@@ -340,7 +347,19 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
       return rc;
     return enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st);
   }
-  if (grp) rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, *grp, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
+  if (ao) {
+    // out -> [kernel 1] obs, r, err_a, loss -> [kernel 2] d out; loss_b without err_a: the errors go through the workspace's own region
+    if (loss_b && !err) err = c.F(Y.err);
+    const float gs = 2.0f * (1.0f / ((float)m.B * (float)ao->op->M * (float)m.O)) * grad_scale;
+    if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), c.F(Y.out), nullptr, nullptr, nullptr, c.F(W.tail_act), ENF_TAIL_FWD | ENF_TAIL_STASH, st)))
+      return rc;
+    if ((rc = enf_launch_obs_loss(*ao->op, m.N, m.B, m.O, c.F(Y.out), target, ao->oweight, ao->cweight, c.F(Y.r), err, loss,
+                                  det ? c.F(Y.loss) : nullptr, st)))
+      return rc;
+    if ((rc = enf_launch_obs_transpose(*ao->op, m.N, m.B, m.O, c.F(Y.r), gs, c.F(Y.dout), st))) return rc;
+    rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), nullptr, c.F(Y.dout), c.F(W.dybar), c.F(W.delta), c.F(W.tail_act),
+                         ENF_TAIL_BWD | ENF_TAIL_STASH, st);
+  } else if (grp) rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, *grp, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
                                       det ? c.F(c.X.loss) : nullptr);
   else rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
                                  det ? c.F(c.X.loss) : nullptr, per_value, err);
@@ -350,7 +369,7 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
   if ((rc = enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st))) return rc;
   // (behind the gradients: nothing of the step waits for the per-signal sums)
   if (grp) err = grp->err_g;
-  const int rows = grp ? m.N / grp->G : m.N;      // the values a signal's loss is the mean of: its points, or its observations
+  const int rows = ao ? ao->op->M : (grp ? m.N / grp->G : m.N);      // the values a signal's loss is the mean of: its points, or its observations
   return err && loss_b ? enf_launch_signal_sum(err, m.B, rows, 1.0f / ((float)rows * (float)m.O), loss_b, st) : ENF_OK;
 }
 
@@ -388,7 +407,7 @@ extern "C" int enf_fit_step_e(const EnfDesc* d, const float* x, int64_t x_bstrid
 static int eval_loss_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                               const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
                               float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream,
-                              const EnfGroupObs* grp = nullptr, bool args_ok = true) {
+                              const EnfGroupObs* grp = nullptr, bool args_ok = true, const ObsStep* ao = nullptr) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
   if (grp) err = grp->err_g;
@@ -398,19 +417,26 @@ static int eval_loss_sequence(const EnfDesc* d, const float* x, int64_t x_bstrid
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
+  const EnfObsWorkspace Y = enf_obs_workspace(m, det ? c.X.total : W.total, ao ? ao->op->M : 1);
+  if (ao && workspace_bytes < Y.total) return ENF_EWORKSPACE;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
   if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), c.fold_fwd(), ENF_PAIR_FOLD | ENF_PAIR_PAIR, st)))
     return rc;
   float* e = err ? err : (loss_b ? c.F(W.dybar) : nullptr);
-  if (grp) {
+  if (ao) {      // (enf_eval_loss_a: the plain forward tail into the workspace, then the forward product with the loss)
+    if (!err && loss_b) e = c.F(Y.err);
+    if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), c.F(Y.out), nullptr, nullptr, nullptr, nullptr, ENF_TAIL_FWD, st))) return rc;
+    rc = enf_launch_obs_loss(*ao->op, m.N, m.B, m.O, c.F(Y.out), target, ao->oweight, ao->cweight, nullptr, e, loss,
+                             det ? c.F(Y.loss) : nullptr, st);
+  } else if (grp) {
     const EnfGroupObs g{grp->G, grp->qweight, grp->oweight, e, grp->cweight};
     rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, g, 0.f, loss, nullptr, nullptr, nullptr, st, det ? c.F(c.X.loss) : nullptr);
   } else
     rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
                               det ? c.F(c.X.loss) : nullptr);
   if (rc) return rc;
-  const int rows = grp ? m.N / grp->G : m.N;
+  const int rows = ao ? ao->op->M : (grp ? m.N / grp->G : m.N);
   return loss_b ? enf_launch_signal_sum(e, m.B, rows, 1.0f / ((float)rows * (float)m.O), loss_b, st) : ENF_OK;
 }
 
@@ -477,6 +503,34 @@ extern "C" int enf_eval_loss_gc(const EnfDesc* d, const float* x, int64_t x_bstr
   const EnfGroupObs g{G, qweight, nullptr, err_g, cweight_g};
   return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, nullptr, loss_b, workspace, workspace_bytes, flags,
                             stream, &g, group_args_ok(d, G) && cweight_g);
+}
+
+// ---- sparse linear observations (include/enf_hip.h, "Sparse linear observations"): the two sequences above with the tail run unfused
+// and the two products of enf_obs.hip in the loss's place.  ENF_EINVAL, behind the descriptor's errors and before any launch: an operator
+// that enf_obs_op_ok refuses (NULL, M < 1, nnz < 0, a missing array), both weight kinds, ENF_FIT_SHARED_LATENTS.
+extern "C" size_t enf_obs_workspace_bytes(const EnfDesc* d, int32_t M, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || M < 1 || (flags & ~ENF_FIT_DETERMINISTIC)) return 0;
+  const EnfDims m = enf_dims(d);
+  const EnfWorkspace W = enf_workspace(m);
+  return enf_obs_workspace(m, (flags & ENF_FIT_DETERMINISTIC) ? enf_det_workspace(m, W).total : W.total, M).total;
+}
+
+extern "C" int enf_fit_step_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                              const void* packed, const float* target, const EnfSparseObs* op, const float* oweight, const float* cweight,
+                              float grad_scale, float* loss, float* dp, float* da, float* dsigma, float* err_a, float* loss_b, void* workspace,
+                              size_t workspace_bytes, unsigned flags, void* stream) {
+  const ObsStep s{op, oweight, cweight};
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
+                           false, flags, stream, err_a, loss_b, enf_obs_op_ok(op, true) && !(oweight && cweight) && !(flags & ENF_FIT_SHARED_LATENTS),
+                           nullptr, &s);
+}
+
+extern "C" int enf_eval_loss_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, const EnfSparseObs* op, const float* oweight, const float* cweight,
+                               float* loss, float* err_a, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  const ObsStep s{op, oweight, cweight};
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, err_a, loss_b, workspace, workspace_bytes, flags,
+                            stream, nullptr, enf_obs_op_ok(op, false) && !(oweight && cweight), &s);
 }
 
 // ---- derivative fields: the Jacobian of a decode w.r.t. the query coordinates (include/enf_hip.h, "Derivative fields")

@@ -232,3 +232,28 @@ int enf_launch_mse_group_shared(const float* out1, const float* target, const fl
                                 float gscale, float* dout, float* loss, hipStream_t st);
 // loss_b[b] = scale * (err[b, 0] + ... + err[b, N - 1]): one workgroup per signal, fixed order, no atomics (enf_loss.hip)
 int enf_launch_signal_sum(const float* err, int B, int N, float scale, float* loss_b, hipStream_t st);
+
+// ---- sparse linear observations (include/enf_hip.h, "Sparse linear observations"; enf_obs.hip)
+enum { ENF_OBS_TREE_MIN = 65,        // rows of at least this many entries are summed by their whole wave (lane-strided partials, xor tree)
+       ENF_OBS_MAX_BLOCKS = 1024 };  // the grid's cap = the loss partials of a deterministic call
+// what every entry point checks of an operator (M >= 1, 0 <= nnz < 2^31, the CSR's pointers; transposed: the CSC's too)
+bool enf_obs_op_ok(const EnfSparseObs* op, bool transposed);
+// kernel 1, the forward product with the loss on out (B, N, O): r = w (obs - target) (B, M, O) and err_a (B, M), each NULL or stored;
+// loss NULL or *loss += the loss -- with part != NULL (ENF_OBS_MAX_BLOCKS floats) through it and enf_launch_loss_sum
+int enf_launch_obs_loss(const EnfSparseObs& op, int N, int B, int O, const float* out, const float* target, const float* oweight,
+                        const float* cweight, float* r, float* err_a, float* loss, float* part, hipStream_t st);
+// kernel 2, the transposed product: dout (B, N, O) = gs * A^T r, every element written
+int enf_launch_obs_transpose(const EnfSparseObs& op, int N, int B, int O, const float* r, float gs, float* dout, hipStream_t st);
+// the regions enf_fit_step_a / enf_eval_loss_a carve behind the plain or deterministic workspace (`base` = its total), byte offsets
+struct EnfObsWorkspace { size_t out, dout, r, err, loss, total; };
+inline EnfObsWorkspace enf_obs_workspace(const EnfDims& m, size_t base, int M) {
+  EnfObsWorkspace Y;
+  const size_t bno = enf_align(sizeof(float) * (size_t)m.B * m.N * m.O), bm = (size_t)m.B * (size_t)M;
+  Y.out = base;
+  Y.dout = Y.out + bno;
+  Y.r = Y.dout + bno;
+  Y.err = Y.r + enf_align(sizeof(float) * bm * m.O);
+  Y.loss = Y.err + enf_align(sizeof(float) * bm);
+  Y.total = Y.loss + enf_align(sizeof(float) * ENF_OBS_MAX_BLOCKS);
+  return Y;
+}

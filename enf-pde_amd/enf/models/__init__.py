@@ -1071,6 +1071,153 @@ class EquivariantCrossAttentionNeF:
             raise _lib.EnfError("EquivariantCrossAttentionNeF.cell_mse needs CUDA/HIP tensors: there is no CPU path")
         return _CellMseFunction.apply(out, target, int(group), qweight, obs_weight, self._det_flag(), obs_channel_weight)
 
+    # ------------------------------------------------------------------ sparse linear observations (any linear operator, CSR)
+    def _operator_args(self, what, x, p, a, target, op, obs_weight, obs_channel_weight):
+        """The shapes of a call against an operator (fitting/operators.py: SparseObservations), checked before anything touches the
+        device: x (B, N, dx) with N = op.N, target (B, M, O) with M = op.M, obs_weight (B, M) or None, obs_channel_weight (B, M, O) or
+        None (never both).  Returns (B, Z, N, M)."""
+        if obs_weight is not None and obs_channel_weight is not None:
+            raise ValueError(f"{what}: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
+        if self.num_layers > 0:
+            raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
+        if x.dim() != 3 or p.dim() != 3 or a.dim() != 3:
+            raise ValueError("x, p and a must be (batch, ., .)")
+        B, Z, N, M = p.shape[0], p.shape[1], x.shape[1], op.M
+        if x.shape[0] != B or a.shape[0] != B or a.shape[1] != Z:
+            raise ValueError(f"x {tuple(x.shape)}, p {tuple(p.shape)} and a {tuple(a.shape)} disagree on the batch or the latents")
+        if N != op.N:
+            raise ValueError(f"x holds {N} query points per signal, the operator has {op.N} columns")
+        if tuple(target.shape) != (B, M, self.num_out):
+            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, self.num_out)}")
+        if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
+            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
+        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, M, self.num_out):
+            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, M, self.num_out)}")
+        if not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda and op.val.is_cuda):
+            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
+        return B, Z, N, M
+
+    @torch.no_grad()
+    def mse_value_and_operator_grads(self, params, x, p, a, gaussian_window_size, target, op, obs_weight=None, obs_channel_weight=None,
+                                     grad_scale=1.0, loss_out=None, return_errors=False, deterministic=None):
+        """The fit step against observations obs = A out of a sparse linear operator ``op`` (fitting/operators.py: SparseObservations;
+        include/enf_hip.h, "Sparse linear observations": enf_fit_step_a), shared by the signals:
+            loss = sum_{b,m,o} w (obs - target)^2 / (B M O),        target (B, M, O), M = op.M, x (B, N, dx), N = op.N.
+        ``obs_weight`` (B, M) or ``obs_channel_weight`` (B, M, O), finite and >= 0, or neither for 1 -- a weight of 0 is a select, the
+        target under it may be NaN.  The decode exists only in the call's workspace; the pair and tail kernels are the point fit's.
+        ``loss_out``: an already ZEROED float32 (1,) tensor the loss is added to.  ``return_errors``: also err_a (B, M) and loss_b (B,).
+        ``deterministic``: None for the model's mode, or True / False for this call.
+        Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err_a, loss_b)."""
+        B, Z, N, M = self._operator_args("mse_value_and_operator_grads", x, p, a, target, op, obs_weight, obs_channel_weight)
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        lib = _lib.load()
+        packed = self.pack(params)
+        p_, a_, s_ = self._latent_args(p, a, sigma)
+        dev = p_.device
+        xb, xstride = self._x_arg(x.float())
+        flags = self._det_flag() if deterministic is None else (_lib.ENF_FIT_DETERMINISTIC if deterministic else 0)
+        desc = self._desc(B, N, Z, masks=self._masks)
+        ws = self._workspace(desc, dev, lambda d, _f: lib.enf_obs_workspace_bytes(d, M, _lib.ENF_FIT_DETERMINISTIC))
+        tgt = target.float().contiguous()
+        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
+        c_ = obs_channel_weight.float().contiguous() if obs_channel_weight is not None else None
+        loss = loss_out if loss_out is not None else torch.zeros(1, device=dev, dtype=torch.float32)
+        dp, da = torch.empty_like(p_), torch.empty_like(a_)
+        dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
+        err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
+        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
+        s = op.struct()
+        _lib.launch(dev, lib.enf_fit_step_a, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    ctypes.byref(s), _ptr(w_), _ptr(c_), float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(err), _ptr(loss_b),
+                    _ptr(ws), ws.numel(), flags, _lib.stream(dev))
+        self._ws_touch(ws)
+        res = (loss, dp, da, dsig if sigma is not None else None)
+        return res + (err, loss_b) if return_errors else res
+
+    @torch.no_grad()
+    def eval_operator_loss(self, params, x, p, a, gaussian_window_size, target, op, obs_weight=None, obs_channel_weight=None,
+                           loss_out=None, per_signal=True, deterministic=None):
+        """Evaluation against an operator's observations without returning a decode (include/enf_hip.h: enf_eval_loss_a): err_a (B, M)
+        and loss_b (B,) as mse_value_and_operator_grads(return_errors=True) gives them at the same point -- the same bits, in every mode.
+        ``loss_out``: an already ZEROED float32 (1,) tensor; the scalar loss is added to it.  ``per_signal`` False skips loss_b.
+        Returns (loss_b or None, err_a)."""
+        B, Z, N, M = self._operator_args("eval_operator_loss", x, p, a, target, op, obs_weight, obs_channel_weight)
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        lib = _lib.load()
+        packed = self.pack(params)
+        p_, a_, s_ = self._latent_args(p, a, sigma)
+        dev = p_.device
+        xb, xstride = self._x_arg(x.float())
+        flags = self._det_flag() if deterministic is None else (_lib.ENF_FIT_DETERMINISTIC if deterministic else 0)
+        desc = self._desc(B, N, Z, masks=self._masks)
+        ws = self._workspace(desc, dev, lambda d, _f: lib.enf_obs_workspace_bytes(d, M, _lib.ENF_FIT_DETERMINISTIC))
+        tgt = target.float().contiguous()
+        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
+        c_ = obs_channel_weight.float().contiguous() if obs_channel_weight is not None else None
+        err = torch.empty((B, M), device=dev, dtype=torch.float32)
+        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
+        s = op.struct(transposed=False)
+        _lib.launch(dev, lib.enf_eval_loss_a, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
+                    ctypes.byref(s), _ptr(w_), _ptr(c_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), flags, _lib.stream(dev))
+        self._ws_touch(ws)
+        return loss_b, err
+
+    def operator_mse(self, out, target, op, obs_weight=None, obs_channel_weight=None):
+        """The loss of a decode that exists in memory against an operator's observations (include/enf_hip.h: enf_mse_value_grad_a), for
+        the weight-gradient path: loss = sum_{b,m,o} w (A out - target)^2 / (B M O) with out (B, N, O), target (B, M, O).  A
+        torch.autograd.Function as cell_mse: loss and d out come from the two kernels of csrc/enf_obs.hip, the backward multiplies d out
+        by the incoming scalar; differentiable once, with respect to ``out`` only.  Returns the loss, a 0-d tensor."""
+        if obs_weight is not None and obs_channel_weight is not None:
+            raise ValueError("operator_mse: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
+        if out.dim() != 3 or out.shape[1] != op.N:
+            raise ValueError(f"out must be (B, {op.N}, O) for this operator, got {tuple(out.shape)}")
+        B, N, O = out.shape
+        if tuple(target.shape) != (B, op.M, O):
+            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, op.M, O)}")
+        if obs_weight is not None and tuple(obs_weight.shape) != (B, op.M):
+            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, op.M)}")
+        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, op.M, O):
+            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, op.M, O)}")
+        if not (out.is_cuda and target.is_cuda and op.val.is_cuda):
+            raise _lib.EnfError("EquivariantCrossAttentionNeF.operator_mse needs CUDA/HIP tensors: there is no CPU path")
+        return _OperatorMseFunction.apply(out, target, op, obs_weight, obs_channel_weight, self._det_flag())
+
+
+class _OperatorMseFunction(torch.autograd.Function):
+    """nef.operator_mse: enf_mse_value_grad_a once in the forward (loss and d out at grad_scale 1); the backward scales the stored d out."""
+
+    @staticmethod
+    def forward(ctx, out, target, op, obs_weight, obs_channel_weight, det):
+        lib = _lib.load()
+        dev = out.device
+        o_ = out.detach().float().contiguous()
+        B, N, O = o_.shape
+        t_ = target.detach().float().contiguous()
+        w_ = obs_weight.detach().float().contiguous() if obs_weight is not None else None
+        c_ = obs_channel_weight.detach().float().contiguous() if obs_channel_weight is not None else None
+        need = ctx.needs_input_grad[0]
+        dout = torch.empty_like(o_) if need else None
+        loss = torch.zeros(1, device=dev, dtype=torch.float32)
+        nscr = int(lib.enf_mse_a_scratch_bytes(B, op.M, O, 1 if need else 0, det))
+        scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr else None
+        s = op.struct(transposed=need)
+        _lib.launch(dev, lib.enf_mse_value_grad_a, _ptr(o_), _ptr(t_), B, N, O, ctypes.byref(s), _ptr(w_), _ptr(c_), 1.0, _ptr(dout),
+                    _ptr(loss), None, _ptr(scr), nscr, det, _lib.stream(dev))
+        if need:
+            ctx.save_for_backward(dout)
+        ctx.out_dtype = out.dtype
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (dout,) = ctx.saved_tensors
+        return (dout * g).to(ctx.out_dtype), None, None, None, None, None
+
 
 class _CellMseFunction(torch.autograd.Function):
     """nef.cell_mse: enf_mse_value_grad_g (with obs_channel_weight: _gc) once in the forward (loss and d out at grad_scale 1); the

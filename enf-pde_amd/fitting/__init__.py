@@ -12,6 +12,7 @@
   lm_fit_cell_averages  (no counterpart)                       the Levenberg-Marquardt fit against cell averages, on the grouped Gauss-Newton product
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
   inner_loop_cells, gather_cell_samples, cell_mse_torch  (no counterpart)   the inner loop on sampled cells (the trainers' cells=) and the torch-op mirrors of its kernels
+  SparseObservations, cell_operator, line_integrals, decode_observations, fit_linear_observations  (no counterpart)   fits against any sparse linear observation operator (CSR): 9- / 27-point and closed cell rules, ragged or overlapping rows, line integrals
   observations: Points, Cells, observed  (no counterpart)      what a fit observes -- point values or cell averages -- and the one parser of weights= / channel_weights= / cells= / cell_channel_weights=
   shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
@@ -27,6 +28,7 @@ from .derivatives import decode_second_directional, decode_laplacian, decode_hes
 from .gauss_newton import cg_solve, lm_fit_latents, lm_fit_cell_averages
 from .cells import cell_quadrature, decode_cell_averages, fit_cell_averages, draw_cell_samples
 from .cells import inner_loop_cells, gather_cell_samples, cell_mse_torch
+from .operators import SparseObservations, cell_operator, line_integrals, decode_observations, fit_linear_observations
 from .parallel import shard_range, allreduce_mean_, init_distributed
 from .trainers import MetaSGDPDETrainer, TrainState, meta_gradients, NonMetaPDETrainer, NonMetaTrainState, draw_point_masks
 from .trainers.trainer_utils import solve_latent_ode
@@ -36,4 +38,5 @@ __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_m
            "allreduce_mean_", "init_distributed", "MetaSGDPDETrainer", "TrainState", "meta_gradients", "NonMetaPDETrainer", "NonMetaTrainState",
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
            "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "lm_fit_cell_averages", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
-           "draw_cell_samples", "inner_loop_cells", "gather_cell_samples", "cell_mse_torch", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual"]
+           "draw_cell_samples", "inner_loop_cells", "gather_cell_samples", "cell_mse_torch", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual",
+           "SparseObservations", "cell_operator", "line_integrals", "decode_observations", "fit_linear_observations"]

@@ -8,6 +8,8 @@ above the decoder has one body per step instead of one per kind.  The keyword a 
   - the loop's final loss without ``per_signal_loss`` is a decode plus the loss kernel on points, always nef.eval_cell_loss on cells;
   - the shared-latent hint of step 0 is given for every weight form on points, on cells only without per-value weights;
   - the forward sweep of meta_gradients differentiates nef.apply with autograd on points and runs the grouped fit step on cells.
+``LinearObservations(x, op)`` -- any sparse linear operator on the decode (fitting/operators.py) -- answers the step and the final loss
+for fit_linear_observations only; ``observed`` and the trainers refuse it.
 ``observed`` is the one parser of a public step's four keywords (weights, channel_weights, cells, cell_channel_weights): it refuses
 what is not served and returns the observation value with the prepared LossWeights.
 """
@@ -285,6 +287,30 @@ class Cells(_Observed):
         return xs, qs, *_gather_frames(traj, cell_masks, weights)
 
 
+class LinearObservations(_Observed):
+    """Linear functionals of the field given by a sparse operator (fitting/operators.py: SparseObservations) on the query points ``x``
+    (N, dx): observation m owns the entries of row m, of any number, shared or not.  It answers what fit_linear_observations asks -- the
+    step and the final loss -- and nothing else yet: ``observed`` and the trainers' steps refuse it, there is no sampling of rows."""
+    STEP, WEIGHT_KW = "mse_value_and_operator_grads", ("obs_weight", "obs_channel_weight")
+    REFUSAL = ("a linear observation operator is served by fitting.fit_linear_observations only: the trainers' steps, inner_loop sampling and "
+               "the Gauss-Newton fits do not take it yet")
+
+    def __init__(self, x, op):
+        if x.dim() != 2 or x.shape[0] != op.N:
+            raise ValueError(f"x must be (N, dx) = ({op.N}, dx) for this operator, got {tuple(x.shape)}")
+        self.x, self.op, self.num = x, op, op.M
+
+    def hints(self, channel):
+        return False
+
+    def fit_step(self, nef, params, xs, qs, p, a, window, ys, ws, channel, always=False, **kw):
+        return nef.mse_value_and_operator_grads(params, xs, p, a, window, ys, self.op, **kw, **self._weight_kw(ws, channel, always))
+
+    def final_loss(self, nef, params, xs, qs, p, a, window, ys, ws, channel, loss_out, per_signal_loss):
+        return nef.eval_operator_loss(params, xs, p, a, window, ys, self.op, loss_out=loss_out, per_signal=per_signal_loss,
+                                      **self._weight_kw(ws, channel, True))[0]
+
+
 def cell_loss_weights(weights, cell_channel_weights, B, M, O, **kw):
     """LossWeights.build for data on cells: ``weights`` per observation, ``cell_channel_weights`` per observed value; both at once is
     a ValueError that names them."""
@@ -305,6 +331,9 @@ def observed(coords, weights, channel_weights, cells, cell_channel_weights, B, n
             raise ValueError("cell_channel_weights= goes with cells=")
         lw = LossWeights.build(weights, channel_weights, B, num, O, T=T, normalize=normalize, device=device, frames=frames)
         return Points(coords), lw
+    from .operators import SparseObservations        # (operators imports this module)
+    if isinstance(cells, LinearObservations) or any(isinstance(c, SparseObservations) for c in (cells if isinstance(cells, (tuple, list)) else ())):
+        raise NotImplementedError(LinearObservations.REFUSAL)
     if channel_weights is not None:
         raise ValueError(_NO_CHANNEL_WEIGHTS_ON_CELLS)
     if getattr(nef, "num_layers", 0) > 0:

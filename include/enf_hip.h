@@ -860,6 +860,75 @@ int enf_fit_inputs_gc(int ncomp, const EnfFitComponent* comps, int32_t B, int32_
                       float* ys /* (S1, B, Ms, O) */, float* losses, const float* cweight_g /* (B, M, O), required */,
                       float* ws /* (S1, B, Ms, O), required */, int32_t per_signal_masks, void* stream);
 
+/* Sparse linear observations (enf_obs_apply, enf_mse_value_grad_a, enf_fit_step_a, enf_eval_loss_a): an observation is ANY fixed linear
+ * functional of the decode -- a 9- or 27-point cell rule, a triangle of an unstructured mesh, a footprint whose size changes with
+ * latitude, a closed rule that shares nodes with its neighbour, an increment u(x_i) - u(x_j), a line integral along a ray, a conserved
+ * total.  One operator A (M x N) is shared by the B signals of a call, given as CSR for the forward product and as CSC (the same
+ * entries sorted by column, stably) for the transposed one; with the notation of "Grouped observations":
+ *     obs[b,m,o]    = sum_{e in [row_ptr[m], row_ptr[m+1])}  val[e] * out[b, col[e], o]
+ *     loss          = 1/(B M O) * sum_{b,m,o} w * (obs - target)^2
+ *     d out[b,n,o]  = grad_scale * 2/(B M O) * sum_{e in [col_ptr[n], col_ptr[n+1])}  tval[e] * (w * (obs - target))[b, trow[e], o]
+ *     err_a[b,m]    = sum_o w * (obs - target)^2                    loss_b[b] = sum_m err_a[b,m] / (M O)
+ * target is (B, M, O).  w is oweight (B, M), or cweight (B, M, O), or 1; both at once is ENF_EINVAL.  The zero-weight rule holds per
+ * observation (oweight) or per value (cweight) exactly as for groups: w == 0 is a select, the target under it may be NaN or Inf, and
+ * its share of the loss and of every d out is exactly 0.0f.  val is a plain finite factor of any sign; nothing is normalised.  An
+ * empty row is legal: its obs is 0 and it counts in M.  A query row that no observation references gets d out == 0.0f exactly.
+ * Indices are int32 (nnz <= 2^31 - 1); offsets into the (B, ., O) tensors are 64-bit.  The library cannot check that the CSC is the
+ * transpose of the CSR (fitting/operators.py builds it; a host test checks it): a mismatch gives a wrong gradient, never an address --
+ * a col or trow outside its range is SKIPPED before it becomes an offset, and row and column ranges are clamped to [0, nnz].
+ * Nothing of the decoder's kernels changes: these calls run two memory-bound kernels (csrc/enf_obs.hip) between the existing launches.
+ * Summation order, a function of a row's length alone (so obs, r = w (obs - target), err_a and d out are the same bits in every mode
+ * and under every launch geometry; no atomics):
+ *     forward, length <= 64:  the row's entries in entry order, one fma each
+ *     forward, length >= 65:  64 partial sums, partial l over entries l, l + 64, l + 128, ... in order (fma), then the fixed xor tree
+ *                             over the partials at distance 32, 16, 8, 4, 2, 1
+ *     transposed, any length: the column's entries in the CSC's entry order, one fma each, then the factor grad_scale 2/(B M O)
+ * err_a adds its O shares in channel order.  The scalar loss is added with one float atomic per workgroup, or in deterministic mode
+ * through scratch and the fixed-order sum of "Deterministic mode". */
+typedef struct EnfSparseObs {
+  int32_t M;                /* observations (rows of A) */
+  int64_t nnz;              /* entries */
+  const int32_t* row_ptr;   /* (M + 1) */
+  const int32_t* col;       /* (nnz) query rows, any order within a row, repeats allowed */
+  const float* val;         /* (nnz) */
+  const int32_t* col_ptr;   /* (N + 1): the CSC; the three may be NULL where no d out is formed */
+  const int32_t* trow;      /* (nnz) observations */
+  const float* tval;        /* (nnz) */
+} EnfSparseObs;
+/* obs (B, M, O) = A out, out (B, N, O): the forward product alone.  ENF_EINVAL: a NULL, B, N, O or M < 1, nnz < 0. */
+int enf_obs_apply(const float* out, int32_t B, int32_t N, int32_t O, const EnfSparseObs* op, float* obs, void* stream);
+/* The unfused loss for a caller that holds a decode, enf_mse_value_grad_g's counterpart: *loss += the loss; dout (B, N, O) or NULL
+ * (then the CSC may be NULL); err_a (B, M) or NULL, OVERWRITTEN.  scratch: enf_mse_a_scratch_bytes(B, M, O, dout != NULL, flags) bytes
+ * -- r (B, M, O) where d out is wanted, the loss partials with flags = ENF_MSE_DETERMINISTIC; its contents need not be kept.
+ * ENF_EINVAL: out, target, loss or a needed part of op NULL; B, N, O, M < 1; nnz < 0; both weights; an unknown flag bit; scratch NULL
+ * where bytes are needed.  Then ENF_EWORKSPACE. */
+size_t enf_mse_a_scratch_bytes(int32_t B, int32_t M, int32_t O, int want_dout, unsigned flags);
+int enf_mse_value_grad_a(const float* out /* (B,N,O) */, const float* target /* (B,M,O) */, int32_t B, int32_t N, int32_t O,
+                         const EnfSparseObs* op, const float* oweight /* (B,M) or NULL */, const float* cweight /* (B,M,O) or NULL */,
+                         float grad_scale, float* dout /* (B,N,O) or NULL */, float* loss, float* err_a /* (B,M) or NULL */,
+                         void* scratch, size_t scratch_bytes, unsigned flags, void* stream);
+/* The fit step and the evaluation against an operator.  enf_fit_step_a: prologue, forward pair kernel, the forward tail with its
+ * stash (out into the workspace), the forward product with the loss, the transposed product, the tail backward on the stash, the
+ * backward pair kernel, the prologue backward, and with loss_b the per-signal sums -- the pair and tail kernels of enf_fit_step_w,
+ * for every descriptor it serves.  enf_eval_loss_a: prologue, forward pair kernel, plain forward tail, the forward product with the
+ * loss, the per-signal sums.  `workspace`: ONE buffer of enf_obs_workspace_bytes(d, M, flags) bytes; it begins with the plain (or,
+ * with ENF_FIT_DETERMINISTIC, the deterministic) workspace's regions at their usual offsets, followed by out and d out (B, N, O), r
+ * (B, M, O), the errors (B, M) of a call that wants loss_b without err_a -- so that combination is allowed here -- and the loss
+ * partials.  flags: 0 or ENF_FIT_DETERMINISTIC; ENF_FIT_SHARED_LATENTS is ENF_EINVAL.  ENF_EINVAL, behind the descriptor's errors and
+ * before any launch: a NULL that is required, M < 1, nnz < 0, both weight kinds; enf_eval_loss_a with loss, err_a and loss_b all NULL.
+ * `loss` is accumulated (the caller zeroes it); err_a and loss_b are OVERWRITTEN. */
+size_t enf_obs_workspace_bytes(const EnfDesc* d, int32_t M, unsigned flags);
+int enf_fit_step_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                   const void* packed, const float* target /* (B,M,O) */, const EnfSparseObs* op, const float* oweight /* (B,M) or NULL */,
+                   const float* cweight /* (B,M,O) or NULL */, float grad_scale, float* loss, float* dp, float* da, float* dsigma,
+                   float* err_a /* (B,M) or NULL */, float* loss_b /* (B) or NULL */, void* workspace, size_t workspace_bytes,
+                   unsigned flags, void* stream);
+int enf_eval_loss_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                    const void* packed, const float* target /* (B,M,O) */, const EnfSparseObs* op, const float* oweight /* (B,M) or NULL */,
+                    const float* cweight /* (B,M,O) or NULL */, float* loss /* scalar, accumulated, or NULL */,
+                    float* err_a /* (B,M) or NULL */, float* loss_b /* (B) or NULL */, void* workspace, size_t workspace_bytes,
+                    unsigned flags, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
  * SepGconv.__call__ (:63-83), over the fully connected latent set of every signal:
