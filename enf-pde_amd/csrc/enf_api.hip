@@ -270,49 +270,35 @@ extern "C" int enf_backward_latents_ex(const EnfDesc* d, const float* x, int64_t
 // mean squared error against `target` and its gradient, backward to the latents.  Same kernels as enf_forward_stages +
 // enf_mse_value_grad + enf_backward_latents_ex with every REUSE flag, except that the tail runs ONCE (forward chain, loss and
 // backward chain in one kernel, enf_tail.hip: LOSS) and neither `out` nor `d out` exists.
-extern "C" int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                            const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
-                            float* dsigma, void* workspace, size_t workspace_bytes, void* stream) {
-  return enf_fit_step_ex(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, 0u,
-                         stream);
-}
-
-// flags = ENF_FIT_DETERMINISTIC: the same kernels; the tail's loss partials and K3's gradient rows go through the workspace's
-// partial buffers and are added in a fixed order (no float atomic, no zero-fill of the gradient table)
-extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                               const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
-                               float* dsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
-  return enf_fit_step_w(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes,
-                        nullptr, flags, stream);
-}
-
-// The one copy of the fit-step sequence.  weight != NULL: one loss weight per signal and query (include/enf_hip.h, "Weighted loss"),
-// or with `per_value` one per output value (B, N, O), which is then required.
-// err != NULL (enf_fit_step_e): the fused tail also stores the per-point errors (B, N), and with loss_b the per-signal sums follow at the
-// end of the sequence on the same stream; args_ok: the entry point's own argument checks (ENF_EINVAL, behind the descriptor's errors).
-// grp != NULL (enf_fit_step_g): the loss against grouped observations -- `target` is (B, N / G, O), the weights and errors are grp's (per
-// observation; weight, per_value and err stay unset), loss_b sums grp->err_g over a signal's N / G observations.
-// ao != NULL (enf_fit_step_a): the loss against a sparse linear operator (include/enf_hip.h, "Sparse linear observations") -- `target` is
-// (B, M, O), the weights are ao's and the errors go through `err`; the tail runs forward with its stash and backward on it, the two products of enf_obs.hip
-// between them, on the regions of enf_obs_workspace behind the workspace (weight, per_value, err and grp stay unset).
-struct ObsStep { const EnfSparseObs* op; const float* oweight; const float* cweight; };
+// The one copy of the fit-step sequence, against the loss `ls` describes (enf_launch.h: EnfLossSpec; `target` is (B, rows, O)).
+// With ls.err the tail also stores the per-observation errors, and with ls.loss_b the per-signal sums follow at the end of the sequence
+// on the same stream.  ENF_FIT_DETERMINISTIC: the same kernels; the loss partials and K3's gradient rows go through the workspace's
+// partial buffers and are added in a fixed order (no float atomic, no zero-fill of the gradient table).
+// An operator: the tail runs forward with its stash and backward on it, the two products of enf_obs.hip between them, on the regions of
+// enf_obs_workspace behind the workspace.
 static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                              const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
-                             float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, bool per_value, unsigned flags,
-                             void* stream, float* err = nullptr, float* loss_b = nullptr, bool args_ok = true, const EnfGroupObs* grp = nullptr,
-                             const ObsStep* ao = nullptr) {
+                             float* dsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const EnfLossSpec& ls) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
   // ENF_FIT_SHARED_LATENTS (include/enf_hip.h): a permission for the forward pair kernel; with one signal it says nothing
   const bool shared = (flags & ENF_FIT_SHARED_LATENTS) && d && d->B > 1;
+  const int refusal = ls.check(d, flags, ENF_LOSS_FIT);
+  if (refusal == ENF_EUNSUPPORTED) {
+    const int drc = enf_check_desc(d);
+    return drc ? drc : refusal;
+  }
   int rc = enf_call(c, d, !(flags & ~(ENF_FIT_DETERMINISTIC | ENF_FIT_SHARED_LATENTS)) && !(shared && x_bstride != 0) && x && p && a && target &&
-                    loss && dp && da && dsigma && (!per_value || weight) && args_ok, sigma, packed, workspace, workspace_bytes, stream, det);
+                    loss && dp && da && dsigma && refusal == ENF_OK, sigma, packed, workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
   const bool zb = enf_use_zfold_bwd(m);
-  const EnfObsWorkspace Y = enf_obs_workspace(m, det ? c.X.total : W.total, ao ? ao->op->M : 1);
+  const bool grp = ls.kind == ENF_LOSS_GROUPS, ao = ls.kind == ENF_LOSS_OPERATOR;
+  const int rows = ls.rows(m);
+  float* err = ls.err;
+  const EnfObsWorkspace Y = enf_obs_workspace(m, det ? c.X.total : W.total, ao ? rows : 1);
   if (ao && workspace_bytes < Y.total) return ENF_EWORKSPACE;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
@@ -321,7 +307,7 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
                                 shared ? c.F(W.dybar) : nullptr)))
     return rc;
   // the shared-latent backward (enf_layout.h: enf_shared_backward_rule): tail, loss and backward pair kernel run ONCE, on signal 0
-  const bool sbwd = enf_shared_backward_rule(m, flags, per_value, err != nullptr || (grp && grp->err_g)) == 1;
+  const bool sbwd = enf_shared_backward_rule(m, flags, ls.cweight != nullptr, err != nullptr) == 1;
   EnfDims m1 = m;
   if (sbwd) m1.B = 1;
   // what the backward pair kernel needs from the latent table alone runs on the side stream beside the tail
@@ -338,8 +324,8 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
     float* out1 = dout + (size_t)m.B * m.N;
     if ((rc = enf_launch_tail_fwd_seed(m1, c.L, c.blob, c.F(W.ybar), out1, 0, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st))) return rc;
     // (grouped: the one row's group sums with signal 0's factors against all B signals' observations and observation weights)
-    if (grp) rc = enf_launch_mse_group_shared(out1, target, grp->qweight, grp->oweight, m.B, m.N, grp->G, grad_scale, dout, loss, st);
-    else rc = enf_launch_mse_shared(out1, target, weight, m.B, m.N, grad_scale, dout, loss, st);
+    if (grp) rc = enf_launch_mse_group_shared(out1, target, ls.qweight, ls.weight, m.B, m.N, ls.G, grad_scale, dout, loss, st);
+    else rc = enf_launch_mse_shared(out1, target, ls.weight, m.B, m.N, grad_scale, dout, loss, st);
     if (rc) return rc;
     if ((rc = enf_side_join_pending(st, workspace))) return rc;
     if ((rc = enf_launch_pair_bwd_shared(m, c.L, c.blob, x, c.F(W.lt), c.F(W.lse), c.F(W.dybar), c.F(W.delta), dout, c.F(W.dlt),
@@ -349,45 +335,59 @@ static int fit_step_sequence(const EnfDesc* d, const float* x, int64_t x_bstride
   }
   if (ao) {
     // out -> [kernel 1] obs, r, err_a, loss -> [kernel 2] d out; loss_b without err_a: the errors go through the workspace's own region
-    if (loss_b && !err) err = c.F(Y.err);
-    const float gs = 2.0f * (1.0f / ((float)m.B * (float)ao->op->M * (float)m.O)) * grad_scale;
+    if (ls.loss_b && !err) err = c.F(Y.err);
+    const float gs = 2.0f * (1.0f / ((float)m.B * (float)rows * (float)m.O)) * grad_scale;
     if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), c.F(Y.out), nullptr, nullptr, nullptr, c.F(W.tail_act), ENF_TAIL_FWD | ENF_TAIL_STASH, st)))
       return rc;
-    if ((rc = enf_launch_obs_loss(*ao->op, m.N, m.B, m.O, c.F(Y.out), target, ao->oweight, ao->cweight, c.F(Y.r), err, loss,
+    if ((rc = enf_launch_obs_loss(*ls.op, m.N, m.B, m.O, c.F(Y.out), target, ls.weight, ls.cweight, c.F(Y.r), err, loss,
                                   det ? c.F(Y.loss) : nullptr, st)))
       return rc;
-    if ((rc = enf_launch_obs_transpose(*ao->op, m.N, m.B, m.O, c.F(Y.r), gs, c.F(Y.dout), st))) return rc;
+    if ((rc = enf_launch_obs_transpose(*ls.op, m.N, m.B, m.O, c.F(Y.r), gs, c.F(Y.dout), st))) return rc;
     rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), nullptr, c.F(Y.dout), c.F(W.dybar), c.F(W.delta), c.F(W.tail_act),
                          ENF_TAIL_BWD | ENF_TAIL_STASH, st);
-  } else if (grp) rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, *grp, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
-                                      det ? c.F(c.X.loss) : nullptr);
-  else rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, weight, grad_scale, loss, c.F(W.dybar), c.F(W.delta), c.F(W.tail_act), st,
-                                 det ? c.F(c.X.loss) : nullptr, per_value, err);
+  } else if (grp) rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, ls.group(err), grad_scale, loss, c.F(W.dybar), c.F(W.delta),
+                                             c.F(W.tail_act), st, det ? c.F(c.X.loss) : nullptr);
+  else rc = enf_launch_tail_loss(m, c.L, c.blob, c.F(W.ybar), target, ls.cweight ? ls.cweight : ls.weight, grad_scale, loss, c.F(W.dybar),
+                                 c.F(W.delta), c.F(W.tail_act), st, det ? c.F(c.X.loss) : nullptr, ls.cweight != nullptr, err);
   if (rc) return rc;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = pair_bwd_on_workspace(c, x, x_bstride, c.F(W.lse), det))) return rc;
   if ((rc = enf_launch_prologue_bwd(m, c.L, c.blob, p, sigma, c.F(W.an), c.F(W.kv), c.F(W.dlt), dp, da, dsigma, st))) return rc;
   // (behind the gradients: nothing of the step waits for the per-signal sums)
-  if (grp) err = grp->err_g;
-  const int rows = ao ? ao->op->M : (grp ? m.N / grp->G : m.N);      // the values a signal's loss is the mean of: its points, or its observations
-  return err && loss_b ? enf_launch_signal_sum(err, m.B, rows, 1.0f / ((float)rows * (float)m.O), loss_b, st) : ENF_OK;
+  return err && ls.loss_b ? enf_launch_signal_sum(err, m.B, rows, 1.0f / ((float)rows * (float)m.O), ls.loss_b, st) : ENF_OK;
 }
 
+extern "C" int enf_fit_step(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                            const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                            float* dsigma, void* workspace, size_t workspace_bytes, void* stream) {
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, 0u, stream,
+                           EnfLossSpec{});
+}
+
+extern "C" int enf_fit_step_ex(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                               const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
+                               float* dsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream,
+                           EnfLossSpec{});
+}
+
+// one loss weight per signal and query, weight (B, N) or NULL (include/enf_hip.h, "Weighted loss")
 extern "C" int enf_fit_step_w(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                               const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                               float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, unsigned flags,
                               void* stream) {
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, weight,
-                           false, flags, stream);
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream,
+                           EnfLossSpec{ENF_LOSS_POINTS, weight});
 }
 
-// per-channel loss weights, cweight (B, N, O), required (include/enf_hip.h, "Weighted loss")
+// per-channel loss weights, cweight (B, N, O), required
 extern "C" int enf_fit_step_cw(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                                float* dsigma, void* workspace, size_t workspace_bytes, const float* cweight, unsigned flags,
                                void* stream) {
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, cweight,
-                           true, flags, stream);
+  EnfLossSpec ls{ENF_LOSS_POINTS, nullptr, cweight};
+  ls.need_cweight = true;
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream, ls);
 }
 
 // enf_fit_step_w / _cw plus the per-point errors and, with loss_b, the per-signal losses (include/enf_hip.h, "Per-signal and per-point
@@ -396,69 +396,62 @@ extern "C" int enf_fit_step_e(const EnfDesc* d, const float* x, int64_t x_bstrid
                               const void* packed, const float* target, float grad_scale, float* loss, float* dp, float* da,
                               float* dsigma, void* workspace, size_t workspace_bytes, const float* weight, const float* cweight,
                               float* err, float* loss_b, unsigned flags, void* stream) {
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes,
-                           cweight ? cweight : weight, cweight != nullptr, flags, stream, err, loss_b, err && !(weight && cweight));
+  EnfLossSpec ls{ENF_LOSS_POINTS, weight, cweight, err, loss_b};
+  ls.need_err = true;
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream, ls);
 }
 
-// Evaluation without a decode: prologue, forward pair kernel (whatever variant the descriptor resolves to), the evaluation tail, the
-// per-signal sums.  loss_b without err: the per-point errors go through the workspace's (unused) d ybar region, B N HD floats.
-// grp != NULL (enf_eval_loss_g): against grouped observations -- target (B, N / G, O), weights and errors per observation from grp
-// (weight, cweight and err unset); args_ok: the entry point's own argument checks.
+// Evaluation without a decode, against the loss `ls` describes: prologue, forward pair kernel (whatever variant the descriptor resolves
+// to), the evaluation tail -- for an operator the plain forward tail into the workspace, then the forward product with the loss --, the
+// per-signal sums.  loss_b without err: the errors go through the workspace's (unused) d ybar region, B N HD floats, or the
+// operator's own region.
 static int eval_loss_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                              const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
-                              float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream,
-                              const EnfGroupObs* grp = nullptr, bool args_ok = true, const ObsStep* ao = nullptr) {
+                              const void* packed, const float* target, float* loss, void* workspace, size_t workspace_bytes,
+                              unsigned flags, void* stream, const EnfLossSpec& ls) {
   EnfCall c;
   const bool det = (flags & ENF_FIT_DETERMINISTIC) != 0;
-  if (grp) err = grp->err_g;
-  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && !(weight && cweight) && (loss || err || loss_b) && args_ok,
-                    sigma, packed, workspace, workspace_bytes, stream, det);
+  int rc = enf_call(c, d, !(flags & ~ENF_FIT_DETERMINISTIC) && x && p && a && target && (loss || ls.err || ls.loss_b) &&
+                    ls.check(d, flags, ENF_LOSS_EVAL) == ENF_OK, sigma, packed, workspace, workspace_bytes, stream, det);
   if (rc) return rc;
   const EnfDims& m = c.m;
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
-  const EnfObsWorkspace Y = enf_obs_workspace(m, det ? c.X.total : W.total, ao ? ao->op->M : 1);
+  const bool ao = ls.kind == ENF_LOSS_OPERATOR;
+  const int rows = ls.rows(m);
+  const EnfObsWorkspace Y = enf_obs_workspace(m, det ? c.X.total : W.total, ao ? rows : 1);
   if (ao && workspace_bytes < Y.total) return ENF_EWORKSPACE;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   if ((rc = enf_launch_prologue(m, c.L, c.blob, p, a, sigma, c.F(W.lt), c.F(W.an), c.F(W.kv), st))) return rc;
   if ((rc = enf_launch_pair_fwd(m, c.L, c.blob, x, x_bstride, c.F(W.lt), c.F(W.ybar), c.F(W.lse), c.fold_fwd(), ENF_PAIR_FOLD | ENF_PAIR_PAIR, st)))
     return rc;
-  float* e = err ? err : (loss_b ? c.F(W.dybar) : nullptr);
-  if (ao) {      // (enf_eval_loss_a: the plain forward tail into the workspace, then the forward product with the loss)
-    if (!err && loss_b) e = c.F(Y.err);
+  float* e = ls.err ? ls.err : (ls.loss_b ? c.F(ao ? Y.err : W.dybar) : nullptr);
+  if (ao) {
     if ((rc = enf_launch_tail(m, c.L, c.blob, c.F(W.ybar), c.F(Y.out), nullptr, nullptr, nullptr, nullptr, ENF_TAIL_FWD, st))) return rc;
-    rc = enf_launch_obs_loss(*ao->op, m.N, m.B, m.O, c.F(Y.out), target, ao->oweight, ao->cweight, nullptr, e, loss,
-                             det ? c.F(Y.loss) : nullptr, st);
-  } else if (grp) {
-    const EnfGroupObs g{grp->G, grp->qweight, grp->oweight, e, grp->cweight};
-    rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, g, 0.f, loss, nullptr, nullptr, nullptr, st, det ? c.F(c.X.loss) : nullptr);
-  } else
-    rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, cweight ? cweight : weight, cweight != nullptr, loss, e, st,
+    rc = enf_launch_obs_loss(*ls.op, m.N, m.B, m.O, c.F(Y.out), target, ls.weight, ls.cweight, nullptr, e, loss, det ? c.F(Y.loss) : nullptr, st);
+  } else if (ls.kind == ENF_LOSS_GROUPS)
+    rc = enf_launch_tail_group(m, c.L, c.blob, c.F(W.ybar), target, ls.group(e), 0.f, loss, nullptr, nullptr, nullptr, st, det ? c.F(c.X.loss) : nullptr);
+  else
+    rc = enf_launch_tail_eval(m, c.L, c.blob, c.F(W.ybar), target, ls.cweight ? ls.cweight : ls.weight, ls.cweight != nullptr, loss, e, st,
                               det ? c.F(c.X.loss) : nullptr);
   if (rc) return rc;
-  const int rows = ao ? ao->op->M : (grp ? m.N / grp->G : m.N);
-  return loss_b ? enf_launch_signal_sum(e, m.B, rows, 1.0f / ((float)rows * (float)m.O), loss_b, st) : ENF_OK;
+  return ls.loss_b ? enf_launch_signal_sum(e, m.B, rows, 1.0f / ((float)rows * (float)m.O), ls.loss_b, st) : ENF_OK;
 }
 
 extern "C" int enf_eval_loss(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                              const void* packed, const float* target, const float* weight, const float* cweight, float* loss,
                              float* err, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
-  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, weight, cweight, loss, err, loss_b, workspace, workspace_bytes, flags,
-                            stream);
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, loss, workspace, workspace_bytes, flags, stream,
+                            EnfLossSpec{ENF_LOSS_POINTS, weight, cweight, err, loss_b});
 }
 
-// ---- grouped observations (include/enf_hip.h, "Grouped observations"): the two sequences above with the tail's grouped forms.
-// ENF_EINVAL, behind the descriptor's errors and before any launch: G outside {1, 2, 4, 8, 16}, N % G != 0, ENF_FIT_SHARED_LATENTS (the
-// shared backward's loss is another kernel), loss_b without err_g in the fit step (no region of its workspace is free for the errors).
-static bool group_args_ok(const EnfDesc* d, int32_t G) { return enf_group_size_ok(G) && d && d->N % G == 0; }
-
+// ---- grouped observations (include/enf_hip.h, "Grouped observations"): the two sequences with the tail's grouped forms; target
+// (B, N / G, O), weights and errors per observation.
 extern "C" int enf_fit_step_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                               const void* packed, const float* target, int32_t G, const float* qweight, const float* oweight, float grad_scale,
                               float* loss, float* dp, float* da, float* dsigma, float* err_g, float* loss_b, void* workspace,
                               size_t workspace_bytes, unsigned flags, void* stream) {
-  const EnfGroupObs g{G, qweight, oweight, err_g};
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
-                           false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && !(flags & ENF_FIT_SHARED_LATENTS) && !(loss_b && !err_g), &g);
+  const EnfLossSpec ls{ENF_LOSS_GROUPS, oweight, nullptr, err_g, loss_b, G, qweight};
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream, ls);
 }
 
 // enf_fit_step_g that may carry ENF_FIT_SHARED_LATENTS (the first inner step of a fit on cells): the flag clear, the call above; set,
@@ -468,46 +461,38 @@ extern "C" int enf_fit_step_gs(const EnfDesc* d, const float* x, int64_t x_bstri
                                const void* packed, const float* target, int32_t G, const float* qweight, const float* oweight, float grad_scale,
                                float* loss, float* dp, float* da, float* dsigma, float* err_g, float* loss_b, void* workspace,
                                size_t workspace_bytes, unsigned flags, void* stream) {
-  const EnfGroupObs g{G, qweight, oweight, err_g};
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
-                           false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && !(loss_b && !err_g), &g);
+  EnfLossSpec ls{ENF_LOSS_GROUPS, oweight, nullptr, err_g, loss_b, G, qweight};
+  ls.shared_entry = true;
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream, ls);
 }
 
 extern "C" int enf_eval_loss_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                const void* packed, const float* target, int32_t G, const float* qweight, const float* oweight, float* loss,
                                float* err_g, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
-  const EnfGroupObs g{G, qweight, oweight, err_g};
-  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, nullptr, loss_b, workspace, workspace_bytes, flags,
-                            stream, &g, group_args_ok(d, G));
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, loss, workspace, workspace_bytes, flags, stream,
+                            EnfLossSpec{ENF_LOSS_GROUPS, oweight, nullptr, err_g, loss_b, G, qweight});
 }
 
-// ---- per-value weights on grouped observations: the same two sequences, the group descriptor carrying cweight_g (B, M, O) in place of
-// oweight -- the tail's per-value grouped forms.  The refusals are the _g calls'; cweight_g is required; ENF_FIT_SHARED_LATENTS is
-// ENF_EUNSUPPORTED (the flag is taken out of what the sequence sees, so the descriptor's errors come first).
+// per-value weights on grouped observations: cweight_g (B, M, O), required, in place of oweight -- the tail's per-value grouped forms
 extern "C" int enf_fit_step_gc(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                const void* packed, const float* target, int32_t G, const float* qweight, const float* cweight_g, float grad_scale,
                                float* loss, float* dp, float* da, float* dsigma, float* err_g, float* loss_b, void* workspace,
                                size_t workspace_bytes, unsigned flags, void* stream) {
-  if (flags & ENF_FIT_SHARED_LATENTS) {
-    if (int rc = enf_check_desc(d)) return rc;
-    return ENF_EUNSUPPORTED;
-  }
-  const EnfGroupObs g{G, qweight, nullptr, err_g, cweight_g};
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
-                           false, flags, stream, nullptr, loss_b, group_args_ok(d, G) && cweight_g && !(loss_b && !err_g), &g);
+  EnfLossSpec ls{ENF_LOSS_GROUPS, nullptr, cweight_g, err_g, loss_b, G, qweight};
+  ls.need_cweight = true;
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream, ls);
 }
 
 extern "C" int enf_eval_loss_gc(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                 const void* packed, const float* target, int32_t G, const float* qweight, const float* cweight_g, float* loss,
                                 float* err_g, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
-  const EnfGroupObs g{G, qweight, nullptr, err_g, cweight_g};
-  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, nullptr, loss_b, workspace, workspace_bytes, flags,
-                            stream, &g, group_args_ok(d, G) && cweight_g);
+  EnfLossSpec ls{ENF_LOSS_GROUPS, nullptr, cweight_g, err_g, loss_b, G, qweight};
+  ls.need_cweight = true;
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, loss, workspace, workspace_bytes, flags, stream, ls);
 }
 
-// ---- sparse linear observations (include/enf_hip.h, "Sparse linear observations"): the two sequences above with the tail run unfused
-// and the two products of enf_obs.hip in the loss's place.  ENF_EINVAL, behind the descriptor's errors and before any launch: an operator
-// that enf_obs_op_ok refuses (NULL, M < 1, nnz < 0, a missing array), both weight kinds, ENF_FIT_SHARED_LATENTS.
+// ---- sparse linear observations (include/enf_hip.h, "Sparse linear observations"): the two sequences with the tail run unfused and
+// the two products of enf_obs.hip in the loss's place; target (B, M, O), weights and errors per observation.
 extern "C" size_t enf_obs_workspace_bytes(const EnfDesc* d, int32_t M, unsigned flags) {
   if (enf_check_desc(d) != ENF_OK || M < 1 || (flags & ~ENF_FIT_DETERMINISTIC)) return 0;
   const EnfDims m = enf_dims(d);
@@ -519,18 +504,15 @@ extern "C" int enf_fit_step_a(const EnfDesc* d, const float* x, int64_t x_bstrid
                               const void* packed, const float* target, const EnfSparseObs* op, const float* oweight, const float* cweight,
                               float grad_scale, float* loss, float* dp, float* da, float* dsigma, float* err_a, float* loss_b, void* workspace,
                               size_t workspace_bytes, unsigned flags, void* stream) {
-  const ObsStep s{op, oweight, cweight};
-  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, nullptr,
-                           false, flags, stream, err_a, loss_b, enf_obs_op_ok(op, true) && !(oweight && cweight) && !(flags & ENF_FIT_SHARED_LATENTS),
-                           nullptr, &s);
+  const EnfLossSpec ls{ENF_LOSS_OPERATOR, oweight, cweight, err_a, loss_b, 1, nullptr, op};
+  return fit_step_sequence(d, x, x_bstride, p, a, sigma, packed, target, grad_scale, loss, dp, da, dsigma, workspace, workspace_bytes, flags, stream, ls);
 }
 
 extern "C" int enf_eval_loss_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                const void* packed, const float* target, const EnfSparseObs* op, const float* oweight, const float* cweight,
                                float* loss, float* err_a, float* loss_b, void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
-  const ObsStep s{op, oweight, cweight};
-  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, nullptr, nullptr, loss, err_a, loss_b, workspace, workspace_bytes, flags,
-                            stream, nullptr, enf_obs_op_ok(op, false) && !(oweight && cweight), &s);
+  return eval_loss_sequence(d, x, x_bstride, p, a, sigma, packed, target, loss, workspace, workspace_bytes, flags, stream,
+                            EnfLossSpec{ENF_LOSS_OPERATOR, oweight, cweight, err_a, loss_b, 1, nullptr, op});
 }
 
 // ---- derivative fields: the Jacobian of a decode w.r.t. the query coordinates (include/enf_hip.h, "Derivative fields")

@@ -257,3 +257,44 @@ inline EnfObsWorkspace enf_obs_workspace(const EnfDims& m, size_t base, int M) {
   Y.total = Y.loss + enf_align(sizeof(float) * ENF_OBS_MAX_BLOCKS);
   return Y;
 }
+
+// ---- what the loss of a host sequence is: fit_step_sequence and eval_loss_sequence (enf_api.hip), gn_product_sequence
+// (enf_tangent.hip).  An entry point fills one and calls its sequence; which forms exist and what each refuses is check()'s.
+enum EnfLossKind { ENF_LOSS_POINTS,      // every query is an observation (include/enf_hip.h, "Weighted loss")
+                   ENF_LOSS_GROUPS,      // observation m is the q-weighted sum of G consecutive queries ("Grouped observations")
+                   ENF_LOSS_OPERATOR };  // obs = A out of a CSR operator, the tail unfused ("Sparse linear observations")
+enum EnfLossCall { ENF_LOSS_FIT, ENF_LOSS_EVAL, ENF_LOSS_GN };
+struct EnfLossSpec {
+  EnfLossKind kind = ENF_LOSS_POINTS;
+  const float* weight = nullptr;      // one weight per observation, (B, rows), or NULL (1)
+  const float* cweight = nullptr;     // one per observed VALUE in its place, (B, rows, O); never both
+  float* err = nullptr;               // the per-observation errors (B, rows), or NULL
+  float* loss_b = nullptr;            // the per-signal losses (B), or NULL
+  int G = 1;                          // groups: the group size and the factors (B, N) or NULL (1 / G)
+  const float* qweight = nullptr;
+  const EnfSparseObs* op = nullptr;   // operator
+  // what differs between the entry points of one kind
+  bool need_cweight = false;          // the per-value calls (_cw, _gc): cweight is required
+  bool need_err = false;              // enf_fit_step_e: err is required
+  bool shared_entry = false;          // groups: the call that may carry ENF_FIT_SHARED_LATENTS (enf_fit_step_gs)
+  // the values a signal's loss is the mean of: its points, or its observations
+  int rows(const EnfDims& m) const { return kind == ENF_LOSS_OPERATOR ? op->M : kind == ENF_LOSS_GROUPS ? m.N / G : m.N; }
+  // the grouped tail's argument, the errors going to `e`
+  EnfGroupObs group(float* e) const { return {G, qweight, weight, e, cweight}; }
+  // ENF_OK, or what the call answers BEHIND the descriptor's errors and before any launch: ENF_EINVAL, or ENF_EUNSUPPORTED for the
+  // per-value grouped fit with ENF_FIT_SHARED_LATENTS (the shared loss kernel has no per-value form), which the sequence answers
+  // ahead of its own ENF_EINVAL.  The flag is the fit's alone: on points a permission, on groups _gs's (the shared backward's loss
+  // is another kernel), on an operator refused.
+  int check(const EnfDesc* d, unsigned flags, EnfLossCall call) const {
+    const bool shared = call == ENF_LOSS_FIT && (flags & ENF_FIT_SHARED_LATENTS);
+    if (shared && kind == ENF_LOSS_GROUPS && need_cweight) return ENF_EUNSUPPORTED;
+    if (shared && (kind == ENF_LOSS_OPERATOR || (kind == ENF_LOSS_GROUPS && !shared_entry))) return ENF_EINVAL;
+    if ((weight && cweight) || (need_cweight && !cweight) || (need_err && !err)) return ENF_EINVAL;
+    if (kind == ENF_LOSS_GROUPS && !(enf_group_size_ok(G) && d && d->N % G == 0)) return ENF_EINVAL;
+    // (the grouped fit has no region of its workspace free for the errors)
+    if (kind == ENF_LOSS_GROUPS && call == ENF_LOSS_FIT && loss_b && !err) return ENF_EINVAL;
+    // an operator that enf_obs_op_ok refuses (the fit reads the CSC too); there is no product against one
+    if (kind == ENF_LOSS_OPERATOR && (call == ENF_LOSS_GN || !enf_obs_op_ok(op, call == ENF_LOSS_FIT))) return ENF_EINVAL;
+    return ENF_OK;
+  }
+};

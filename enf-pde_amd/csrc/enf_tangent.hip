@@ -747,18 +747,16 @@ extern "C" size_t enf_gn_workspace_bytes(const EnfDesc* d, unsigned flags) {
   return tan_workspace(enf_dims(d), (flags & ENF_BWD_DETERMINISTIC) != 0).total;
 }
 
-// The one copy of the product's host sequence.  grp == NULL: enf_gn_product (weight (B, N) or cweight (B, N, O)).  grp != NULL
-// (enf_gn_product_g): the seed of a loss on grouped observations -- the grouped instantiation of the tail, grp's factors and
-// observation weights, 1 / (B M O) in the scale; `args_ok` then carries the entry point's own checks (ENF_EINVAL, behind
-// ENF_EUNSUPPORTED and before ENF_EWORKSPACE).
+// The one copy of the product's host sequence, seeded by the loss `ls` describes (enf_launch.h: EnfLossSpec): on points the weights
+// (B, N) or (B, N, O); on grouped observations the grouped instantiation of the tail with the factors and observation weights,
+// 1 / (B M O) in the scale.  What ls.check refuses is ENF_EINVAL, behind ENF_EUNSUPPORTED and before ENF_EWORKSPACE.
 namespace {
 int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
-                        const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
-                        const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
-                        size_t workspace_bytes, unsigned flags, void* stream, const EnfGroupObs* grp = nullptr, bool args_ok = true) {
+                        const float* vp, const float* va, const float* vsigma, const void* packed, float grad_scale, float* gp, float* ga,
+                        float* gsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const EnfLossSpec& ls) {
   const bool det = (flags & ENF_BWD_DETERMINISTIC) != 0, reuse = (flags & ENF_GN_REUSE_POINT) != 0;
   TanCall c;
-  int rc = tan_call(c, d, x && a && gp && ga && gsigma && (vp || va || vsigma) && !(weight && cweight) && !(flags & ~GN_FLAGS) && args_ok,
+  int rc = tan_call(c, d, x && a && gp && ga && gsigma && (vp || va || vsigma) && !(flags & ~GN_FLAGS) && ls.check(d, flags, ENF_LOSS_GN) == ENF_OK,
                     p, sigma, packed, workspace, workspace_bytes, det, stream);
   if (rc) return rc;
   const EnfDims& m = c.m;
@@ -766,7 +764,7 @@ int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, con
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
   const char* pk = c.blob;
-  const bool zb = enf_use_zfold_bwd(m);
+  const bool zb = enf_use_zfold_bwd(m), grp = ls.kind == ENF_LOSS_GROUPS;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   // the point: latent table, what the prologue backward reads, and the z-fold backward's per-latent matrices -- unless the caller
   // vouches that a fit step or an earlier product at this point left them
@@ -777,13 +775,13 @@ int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, con
   if ((rc = tan_launch_prologue(c, vp, va, vsigma))) return rc;
   const PairTanArgs PA = tan_pair_args(c, x, x_bstride, c.F(W.lse));
   GnTailArgsG GA;
-  GA.ybar = PA.ybar; GA.ydot = PA.ydot; GA.blob = pk; GA.L = L; GA.weight = cweight ? cweight : weight; GA.cw = cweight != nullptr;
+  GA.ybar = PA.ybar; GA.ydot = PA.ydot; GA.blob = pk; GA.L = L;
+  GA.weight = grp ? nullptr : (ls.cweight ? ls.cweight : ls.weight); GA.cw = !grp && ls.cweight != nullptr;
   GA.dybar = c.F(W.dybar); GA.delta = c.F(W.delta); GA.act = c.F(W.tail_act);
   GA.NQ = m.B * m.N; GA.O = m.O; GA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-  const int rows = grp ? m.N / grp->G : m.N;      // the values a signal's loss is the mean of: its points, or its observations
-  GA.gs = 2.0f * grad_scale / ((float)m.B * (float)rows * (float)m.O);
+  GA.gs = 2.0f * grad_scale / ((float)m.B * (float)ls.rows(m) * (float)m.O);
   if (grp) {
-    GA.G = grp->G; GA.qweight = grp->qweight; GA.oweight = grp->oweight;
+    GA.G = ls.G; GA.qweight = ls.qweight; GA.oweight = ls.weight;
     rc = launch_pair_tail(m, PA, GA, st);
   } else rc = launch_pair_tail(m, PA, static_cast<const GnTailArgs&>(GA), st);
   if (rc) return rc;
@@ -801,17 +799,15 @@ extern "C" int enf_gn_product(const EnfDesc* d, const float* x, int64_t x_bstrid
                               const float* vp, const float* va, const float* vsigma, const void* packed, const float* weight,
                               const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma, void* workspace,
                               size_t workspace_bytes, unsigned flags, void* stream) {
-  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, weight, cweight, grad_scale, gp, ga, gsigma, workspace,
-                             workspace_bytes, flags, stream);
+  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, grad_scale, gp, ga, gsigma, workspace, workspace_bytes, flags,
+                             stream, EnfLossSpec{ENF_LOSS_POINTS, weight, cweight});
 }
 
-// The product for grouped observations (include/enf_hip.h, "Gauss-Newton product on grouped observations"): ENF_EINVAL also for G
-// outside {1, 2, 4, 8, 16} or N % G != 0, as in enf_fit_step_g.
+// The product for grouped observations (include/enf_hip.h, "Gauss-Newton product on grouped observations")
 extern "C" int enf_gn_product_g(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                                 const float* vp, const float* va, const float* vsigma, const void* packed, int32_t G,
                                 const float* qweight, const float* oweight, float grad_scale, float* gp, float* ga, float* gsigma,
                                 void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
-  const EnfGroupObs g{G, qweight, oweight, nullptr};
-  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, nullptr, nullptr, grad_scale, gp, ga, gsigma, workspace,
-                             workspace_bytes, flags, stream, &g, enf_group_size_ok(G) && d && d->N % G == 0);
+  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, grad_scale, gp, ga, gsigma, workspace, workspace_bytes, flags,
+                             stream, EnfLossSpec{ENF_LOSS_GROUPS, oweight, nullptr, nullptr, nullptr, G, qweight});
 }

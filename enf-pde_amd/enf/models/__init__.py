@@ -16,6 +16,7 @@ from .. import steerable_attention  # noqa: F401  (package layout parity)
 from ..steerable_attention.invariant import BaseInvariant
 from ... import _lib
 from . import _pad
+from ._obs_calls import Cells as _Cells, Operator as _Operator, Points as _Points, f32 as _f32
 
 __all__ = ["EquivariantCrossAttentionNeF", "TENSOR_PATHS", "FFN_TENSOR_PATHS", "tensor_paths"]
 
@@ -84,6 +85,7 @@ def _set(tree, path, value):
 
 
 _ptr = _lib.ptr
+_POINTS = _Points()      # (the kind of the calls on points holds nothing of a call)
 
 
 FUSED_FIT_STEP = __import__("os").environ.get("ENF_FIT_STEP") != "0"      # mse_value_and_latent_grads through enf_fit_step (one call)
@@ -292,18 +294,6 @@ class EquivariantCrossAttentionNeF:
         p_ = p.float().contiguous()
         s_ = sigma.float().reshape(p_.shape[0], p_.shape[1], 1).contiguous() if sigma is not None else None
         return p_, a.float().contiguous(), s_
-
-    def _weight_args(self, weight, channel_weight, B, N):
-        """The loss weights of a (B, N) problem, checked and as the library takes them: (weight (B, N) or None, channel_weight
-        (B, N, O) or None), float32 and contiguous; at most one of them."""
-        if weight is not None and channel_weight is not None:
-            raise ValueError("pass weight= (B, N) or channel_weight= (B, N, O), not both")
-        if channel_weight is not None and tuple(channel_weight.shape) != (B, N, self.num_out):
-            raise ValueError(f"channel_weight has shape {tuple(channel_weight.shape)}, expected {(B, N, self.num_out)}")
-        if weight is not None and tuple(weight.shape) != (B, N):
-            raise ValueError(f"weight has shape {tuple(weight.shape)}, expected {(B, N)}")
-        return (weight.float().contiguous() if weight is not None else None,
-                channel_weight.float().contiguous() if channel_weight is not None else None)
 
     def _ws_touch(self, ws):
         """Mark a use of workspace `ws`; returns the tag identifying this use."""
@@ -633,21 +623,28 @@ class EquivariantCrossAttentionNeF:
         ``reuse``: the ``workspace_tag`` taken right after the ``mse_value_and_latent_grads`` (not ``shared_latents``) or the
         ``gn_product`` that last ran at the SAME (x, p, a, window, params) on this stream -- the latent prologue is then not recomputed.
         A tag that is no longer the workspace's current one silently recomputes.  Size the buffer first: ``gn_reserve``."""
-        xb, xstride, p_, a_, s_ = self._tangent_args("gn_product", x, p, a, gaussian_window_size,
-                                                     (("vp", vp), ("va", va), ("vwindow", vwindow)))
-        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
-        w_, cw_ = self._weight_args(weight, channel_weight, B, N)
+        latents = self._tangent_args("gn_product", x, p, a, gaussian_window_size, (("vp", vp), ("va", va), ("vwindow", vwindow)))
+        if weight is not None and channel_weight is not None:
+            raise _POINTS.both("gn_product")
+        _POINTS.shapes(p.shape[0], x.shape[1], x.shape[1], self.num_out, None, weight, channel_weight)
+        return self._gn_call(_POINTS, params, x.shape[1], latents, (vp, va, vwindow), weight, channel_weight, grad_scale, reuse)
+
+    def _gn_call(self, kind, params, N, latents, v, weight, cweight, grad_scale, reuse):
+        """The native call of ``gn_product`` / ``gn_cell_product`` behind their checks.  ``latents``: _tangent_args' tuple."""
+        xb, xstride, p_, a_, s_ = latents
+        B, Z, dev = p_.shape[0], p_.shape[1], p_.device
         lib = _lib.load()
         packed = self.pack(params)
+        w_, cw_ = _f32(weight), _f32(cweight)
         desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_gn_workspace_bytes)
         flags = self._det_flag()
         if reuse is not None and reuse == self._ws_tag(ws) and reuse[1] is not None:
             flags |= _lib.ENF_GN_REUSE_POINT
         gp, ga = torch.empty_like(p_), torch.empty_like(a_)
         gs = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
-        _lib.launch(dev, lib.enf_gn_product, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(vp), _ptr(va),
-                    _ptr(vwindow), _ptr(packed), _ptr(w_), _ptr(cw_), float(grad_scale), _ptr(gp), _ptr(ga), _ptr(gs), _ptr(ws),
-                    ws.numel(), flags, st)
+        fn, mid = kind.gn(lib, w_, cw_)
+        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(v[0]), _ptr(v[1]), _ptr(v[2]),
+                    _ptr(packed), *mid, float(grad_scale), _ptr(gp), _ptr(ga), _ptr(gs), _ptr(ws), ws.numel(), flags, st)
         self._ws_touch(ws)
         return gp, ga, (gs if s_ is not None else None)
 
@@ -760,10 +757,13 @@ class EquivariantCrossAttentionNeF:
             raise _lib.EnfError("mse_value_and_latent_grads(return_errors=True) needs CUDA/HIP tensors: there is no CPU path")
         if return_errors and (self.num_layers > 0 or not FUSED_FIT_STEP):
             raise NotImplementedError("return_errors needs the one-call inner step (enf_fit_step_e): num_layers = 0 and ENF_FIT_STEP on")
-        weight, channel_weight = self._weight_args(weight, channel_weight, p.shape[0], x.shape[1])
-        lib = _lib.load()
-        sigma = gaussian_window_size if self.use_gaussian_window else None
+        B, N = p.shape[0], x.shape[1]
+        if weight is not None and channel_weight is not None:
+            raise _POINTS.both("mse_value_and_latent_grads")
+        _POINTS.shapes(B, N, N, self.num_out, None, weight, channel_weight)
         if self.num_layers > 0:           # no fused sequence for the layered model: autograd through apply()
+            weight, channel_weight = _f32(weight), _f32(channel_weight)
+            sigma = gaussian_window_size if self.use_gaussian_window else None
             with torch.enable_grad():
                 leaves = [t.detach().float().requires_grad_(True) for t in (p, a)] + \
                          ([sigma.detach().float().requires_grad_(True)] if sigma is not None else [])
@@ -782,19 +782,35 @@ class EquivariantCrossAttentionNeF:
             if loss_out is not None:
                 loss_out.add_(loss.detach().reshape(1))
             return loss.detach().reshape(1), g[0], g[1], (g[2] if sigma is not None else None)
+        _POINTS.shapes(B, N, N, self.num_out, target, None, None)
+        return self._fit_step(_POINTS, N, params, x, p, a, gaussian_window_size, target, weight, channel_weight, grad_scale, loss_out,
+                              return_errors, shared_latents)
+
+    def _fit_step(self, kind, M, params, x, p, a, gaussian_window_size, target, weight, cweight, grad_scale, loss_out, return_errors,
+                  shared_latents=False, deterministic=None):
+        """The one body of the fit steps (``mse_value_and_latent_grads`` / ``_cell_grads`` / ``_operator_grads``) behind their checks:
+        the arguments as the library takes them, descriptor and workspace, the output buffers, the kind's native call (_obs_calls.py).
+        Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err (B, M), loss_b (B,))."""
+        sigma = gaussian_window_size if self.use_gaussian_window else None
+        if self.use_gaussian_window and sigma is None:
+            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        lib = _lib.load()
         packed = self.pack(params)
         p_, a_, s_ = self._latent_args(p, a, sigma)
         B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
         xb, xstride = self._x_arg(x.float())
-        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
+        flags = self._det_flag() if deterministic is None else (_lib.ENF_FIT_DETERMINISTIC if deterministic else 0)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks, size_query=kind.size_query)
         tgt = target.float().contiguous()
-        if tuple(tgt.shape) != (B, N, self.num_out):
-            raise AssertionError(f"target has shape {tuple(tgt.shape)}, expected {(B, N, self.num_out)}")
+        w_ = weight.float().contiguous() if weight is not None else None
+        cw_ = cweight.float().contiguous() if cweight is not None else None
         loss = loss_out if loss_out is not None else torch.zeros(1, device=dev, dtype=torch.float32)
         dp, da = torch.empty_like(p_), torch.empty_like(a_)
         dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
-        det = self._det_flag()
-        if not FUSED_FIT_STEP:       # the same step as three library calls (cross-check in the tests, A/B in scripts/)
+        err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
+        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
+        res = (loss, dp, da, dsig if sigma is not None else None)
+        if kind is _POINTS and not FUSED_FIT_STEP:       # the same step as three library calls (cross-check in the tests, A/B in scripts/)
             HD = self._Hp * self._Dp
             out = torch.empty((B, N, self.num_out), device=dev, dtype=torch.float32)
             ybar = torch.empty((B, N, HD), device=dev, dtype=torch.float32)
@@ -803,35 +819,27 @@ class EquivariantCrossAttentionNeF:
                         _ptr(out), _ptr(ybar), _ptr(lse), _ptr(ws), ws.numel(),
                         _lib.ENF_STAGES_FORWARD | _lib.ENF_STAGE_TAIL_SAVE | _lib.ENF_STAGE_PREPARE_BWD, st)
             dout = torch.empty_like(out)
-            nmse = int(lib.enf_mse_scratch_bytes(out.numel(), det))
+            nmse = int(lib.enf_mse_scratch_bytes(out.numel(), flags))
             mse_scr = torch.empty(nmse, device=dev, dtype=torch.uint8) if nmse else None
-            if channel_weight is not None:
-                _lib.launch(dev, lib.enf_mse_value_grad_cw, _ptr(out), _ptr(tgt), _ptr(channel_weight), out.numel(), float(grad_scale),
-                            _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
+            if cw_ is not None:
+                _lib.launch(dev, lib.enf_mse_value_grad_cw, _ptr(out), _ptr(tgt), _ptr(cw_), out.numel(), float(grad_scale),
+                            _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, flags, st)
             else:
-                _lib.launch(dev, lib.enf_mse_value_grad_w, _ptr(out), _ptr(tgt), _ptr(weight), out.numel(), self.num_out, float(grad_scale),
-                            _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, det, st)
+                _lib.launch(dev, lib.enf_mse_value_grad_w, _ptr(out), _ptr(tgt), _ptr(w_), out.numel(), self.num_out, float(grad_scale),
+                            _ptr(dout), _ptr(loss), _ptr(mse_scr), nmse, flags, st)
             _lib.launch(dev, lib.enf_backward_latents_ex, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_),
                         _ptr(packed), _ptr(ybar), _ptr(lse), _ptr(dout), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(),
-                        _lib.ENF_BWD_REUSE_PROLOGUE | _lib.ENF_BWD_REUSE_TAIL | _lib.ENF_BWD_REUSE_PREPARED | det, st)
+                        _lib.ENF_BWD_REUSE_PROLOGUE | _lib.ENF_BWD_REUSE_TAIL | _lib.ENF_BWD_REUSE_PREPARED | flags, st)
             self._ws_touch(ws)
-            return loss, dp, da, (dsig if sigma is not None else None)
-        # ONE library call per inner step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail as a single kernel with
-        # the loss and its gradient formed in registers, pair backward, prologue backward
+            return res
+        # ONE library call per step (include/enf_hip.h: enf_fit_step): prologue, pair forward, the tail with the loss and its gradient
+        # (on points and cells a single kernel that forms them in registers), pair backward, prologue backward
         if shared_latents:
-            det |= _lib.ENF_FIT_SHARED_LATENTS
-        if return_errors:                   # the same sequence and instantiations; the tail also stores its per-query errors
-            err = torch.empty((B, N), device=dev, dtype=torch.float32)
-            loss_b = torch.empty((B,), device=dev, dtype=torch.float32)
-            fn, extra = lib.enf_fit_step_e, (_ptr(weight), _ptr(channel_weight), _ptr(err), _ptr(loss_b))
-        elif channel_weight is not None:    # the same sequence, the tail's per-channel instantiation
-            fn, extra = lib.enf_fit_step_cw, (_ptr(channel_weight),)
-        else:
-            fn, extra = lib.enf_fit_step_w, (_ptr(weight),)
-        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt), float(grad_scale),
-                    _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(ws), ws.numel(), *extra, det, st)
+            flags |= _lib.ENF_FIT_SHARED_LATENTS
+        fn, rest = kind.fit(lib, w_, cw_, shared_latents, (float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig)), (err, loss_b),
+                            (_ptr(ws), ws.numel()))
+        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt), *rest, flags, st)
         self._ws_touch(ws)
-        res = (loss, dp, da, dsig if sigma is not None else None)
         return res + (err, loss_b) if return_errors else res
 
     @torch.no_grad()
@@ -848,24 +856,32 @@ class EquivariantCrossAttentionNeF:
             raise _lib.EnfError("EquivariantCrossAttentionNeF.eval_loss needs CUDA/HIP tensors: there is no CPU path")
         if self.num_layers > 0:
             raise NotImplementedError("eval_loss is built for num_layers = 0 (the fused decoder)")
-        B, Z, N = p.shape[0], p.shape[1], x.shape[1]
-        w_, cw_ = self._weight_args(weight, channel_weight, B, N)
-        tgt = target.float().contiguous()
-        if tuple(tgt.shape) != (B, N, self.num_out):
-            raise AssertionError(f"target has shape {tuple(tgt.shape)}, expected {(B, N, self.num_out)}")
-        lib = _lib.load()
+        if weight is not None and channel_weight is not None:
+            raise _POINTS.both("eval_loss")
+        _POINTS.shapes(p.shape[0], x.shape[1], x.shape[1], self.num_out, target, weight, channel_weight)
+        return self._eval(_POINTS, x.shape[1], params, x, p, a, gaussian_window_size, target, weight, channel_weight, loss_out, per_signal)
+
+    def _eval(self, kind, M, params, x, p, a, gaussian_window_size, target, weight, cweight, loss_out, per_signal, deterministic=None):
+        """The one body of the evaluations (``eval_loss`` / ``eval_cell_loss`` / ``eval_operator_loss``) behind their checks, as
+        _fit_step.  Returns (loss_b (B,) or None, err (B, M))."""
         sigma = gaussian_window_size if self.use_gaussian_window else None
         if self.use_gaussian_window and sigma is None:
             raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
+        lib = _lib.load()
         packed = self.pack(params)
         p_, a_, s_ = self._latent_args(p, a, sigma)
-        dev = p_.device
+        B, Z, N, dev = p_.shape[0], p_.shape[1], x.shape[1], p_.device
         xb, xstride = self._x_arg(x.float())
-        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
-        err = torch.empty((B, N), device=dev, dtype=torch.float32)
+        flags = self._det_flag() if deterministic is None else (_lib.ENF_FIT_DETERMINISTIC if deterministic else 0)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks, size_query=kind.size_query)
+        tgt = target.float().contiguous()
+        w_ = weight.float().contiguous() if weight is not None else None
+        cw_ = cweight.float().contiguous() if cweight is not None else None
+        err = torch.empty((B, M), device=dev, dtype=torch.float32)
         loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
-        _lib.launch(dev, lib.enf_eval_loss, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    _ptr(w_), _ptr(cw_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
+        fn, mid = kind.evaluate(lib, w_, cw_)
+        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt), *mid,
+                    _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), flags, st)
         self._ws_touch(ws)
         return loss_b, err
 
@@ -882,39 +898,40 @@ class EquivariantCrossAttentionNeF:
                     _lib.stream(e.device))
         return loss_b
 
-    # ------------------------------------------------------------------ grouped observations (cell averages)
-    GROUP_SIZES = (1, 2, 4, 8, 16)
+    # ------------------------------------------------------------------ observations that are not points: cells, sparse operators
+    GROUP_SIZES = _Cells.GROUP_SIZES
 
-    def _cell_args(self, what, x, p, a, target, group, qweight, obs_weight, obs_channel_weight=None):
-        """The shapes of a grouped call, checked before anything touches the device: x (B, N, dx) with N = M * group, target
-        (B, M, O) -- None for a call that takes none (``gn_cell_product``) --, qweight (B, N) or None, obs_weight (B, M) or None,
-        obs_channel_weight (B, M, O) or None (never together with obs_weight).
-        Returns (B, Z, N, M)."""
-        if obs_weight is not None and obs_channel_weight is not None:
-            raise ValueError(f"{what}: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
+    def _obs_args(self, what, kind, x, p, a, target, weight, cweight):
+        """The one shape and refusal checker of the calls against cells and operators (_obs_calls.py: the kind), run before anything
+        touches the device: never both weight forms, the fused decoder, the kind's own parameters, x (B, N, dx) against p and a, N
+        against the kind, then target (B, M, O) -- None for a call that takes none (``gn_cell_product``) --, qweight (B, N), the
+        weights (B, M) / (B, M, O), and the devices."""
+        if weight is not None and cweight is not None:
+            raise kind.both(what)
         if self.num_layers > 0:
             raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
-        if int(group) not in self.GROUP_SIZES:
-            raise ValueError(f"group must be one of {self.GROUP_SIZES}, got {group}")
         if x.dim() != 3 or p.dim() != 3 or a.dim() != 3:
             raise ValueError("x, p and a must be (batch, ., .)")
         B, Z, N = p.shape[0], p.shape[1], x.shape[1]
         if x.shape[0] != B or a.shape[0] != B or a.shape[1] != Z:
             raise ValueError(f"x {tuple(x.shape)}, p {tuple(p.shape)} and a {tuple(a.shape)} disagree on the batch or the latents")
-        if N % int(group):
-            raise ValueError(f"x holds {N} query points per signal, not a multiple of group = {group}")
-        M = N // int(group)
-        if target is not None and tuple(target.shape) != (B, M, self.num_out):
-            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, self.num_out)}")
-        if qweight is not None and tuple(qweight.shape) != (B, N):
-            raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
-        if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
-            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
-        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, M, self.num_out):
-            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, M, self.num_out)}")
-        if not (x.is_cuda and p.is_cuda and a.is_cuda and (target is None or target.is_cuda)):
+        M = kind.rows(N)
+        kind.shapes(B, N, M, self.num_out, target, weight, cweight)
+        if not (x.is_cuda and p.is_cuda and a.is_cuda and (target is None or target.is_cuda) and (kind.op is None or kind.op.val.is_cuda)):
             raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
-        return B, Z, N, M
+        return M
+
+    def _decode_loss(self, what, kind, out, target, weight, cweight):
+        """``cell_mse`` / ``operator_mse``: the same checks on a decode out (B, N, O) in place of x, p and a, then the one Function."""
+        if weight is not None and cweight is not None:
+            raise kind.both(what)
+        if out.dim() != 3:
+            raise ValueError(f"out must be (B, N, O), got {tuple(out.shape)}")
+        B, N, O = out.shape
+        kind.shapes(B, N, kind.rows(N), O, target, weight, cweight)
+        if not (out.is_cuda and target.is_cuda and (kind.op is None or kind.op.val.is_cuda)):
+            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
+        return _ObsMseFunction.apply(out, target, kind, weight, cweight, self._det_flag())
 
     @torch.no_grad()
     def mse_value_and_cell_grads(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None,
@@ -938,33 +955,10 @@ class EquivariantCrossAttentionNeF:
         Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err_g, loss_b)."""
         if shared_latents and obs_channel_weight is not None:
             raise NotImplementedError("mse_value_and_cell_grads: shared_latents with obs_channel_weight is not built; run the step unshared")
-        B, Z, N, M = self._cell_args("mse_value_and_cell_grads", x, p, a, target, group, qweight, obs_weight, obs_channel_weight)
-        sigma = gaussian_window_size if self.use_gaussian_window else None
-        if self.use_gaussian_window and sigma is None:
-            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
-        lib = _lib.load()
-        packed = self.pack(params)
-        p_, a_, s_ = self._latent_args(p, a, sigma)
-        dev = p_.device
-        xb, xstride = self._x_arg(x.float())
-        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
-        tgt = target.float().contiguous()
-        q_ = qweight.float().contiguous() if qweight is not None else None
-        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
-        loss = loss_out if loss_out is not None else torch.zeros(1, device=dev, dtype=torch.float32)
-        dp, da = torch.empty_like(p_), torch.empty_like(a_)
-        dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
-        err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
-        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
-        fn, flags = (lib.enf_fit_step_gs, self._det_flag() | _lib.ENF_FIT_SHARED_LATENTS) if shared_latents else (lib.enf_fit_step_g, self._det_flag())
-        if obs_channel_weight is not None:
-            fn, w_ = lib.enf_fit_step_gc, obs_channel_weight.float().contiguous()
-        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    int(group), _ptr(q_), _ptr(w_), float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(err), _ptr(loss_b),
-                    _ptr(ws), ws.numel(), flags, st)
-        self._ws_touch(ws)
-        res = (loss, dp, da, dsig if sigma is not None else None)
-        return res + (err, loss_b) if return_errors else res
+        kind = _Cells(group, qweight)
+        M = self._obs_args("mse_value_and_cell_grads", kind, x, p, a, target, obs_weight, obs_channel_weight)
+        return self._fit_step(kind, M, params, x, p, a, gaussian_window_size, target, obs_weight, obs_channel_weight, grad_scale, loss_out,
+                              return_errors, shared_latents)
 
     @torch.no_grad()
     def eval_cell_loss(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None, loss_out=None,
@@ -974,28 +968,9 @@ class EquivariantCrossAttentionNeF:
         already ZEROED float32 (1,) tensor; the scalar loss is added to it.  ``per_signal`` False skips loss_b.
         ``obs_channel_weight``: (B, M, O) in place of ``obs_weight``, as in mse_value_and_cell_grads (enf_eval_loss_gc).
         Returns (loss_b or None, err_g)."""
-        B, Z, N, M = self._cell_args("eval_cell_loss", x, p, a, target, group, qweight, obs_weight, obs_channel_weight)
-        sigma = gaussian_window_size if self.use_gaussian_window else None
-        if self.use_gaussian_window and sigma is None:
-            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
-        lib = _lib.load()
-        packed = self.pack(params)
-        p_, a_, s_ = self._latent_args(p, a, sigma)
-        dev = p_.device
-        xb, xstride = self._x_arg(x.float())
-        desc, ws, st = self._call_ctx(B, N, Z, dev, masks=self._masks)
-        tgt = target.float().contiguous()
-        q_ = qweight.float().contiguous() if qweight is not None else None
-        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
-        err = torch.empty((B, M), device=dev, dtype=torch.float32)
-        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
-        fn = lib.enf_eval_loss_g
-        if obs_channel_weight is not None:
-            fn, w_ = lib.enf_eval_loss_gc, obs_channel_weight.float().contiguous()
-        _lib.launch(dev, fn, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    int(group), _ptr(q_), _ptr(w_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), self._det_flag(), st)
-        self._ws_touch(ws)
-        return loss_b, err
+        kind = _Cells(group, qweight)
+        M = self._obs_args("eval_cell_loss", kind, x, p, a, target, obs_weight, obs_channel_weight)
+        return self._eval(kind, M, params, x, p, a, gaussian_window_size, target, obs_weight, obs_channel_weight, loss_out, per_signal)
 
     @torch.no_grad()
     def gn_cell_product(self, params, x, p, a, gaussian_window_size, group, qweight=None, obs_weight=None, vp=None, va=None,
@@ -1011,24 +986,10 @@ class EquivariantCrossAttentionNeF:
         same point.  The group sum of the tangent and d out are formed in the tail's registers.  Size the buffer first: ``gn_reserve``."""
         tangents = (("vp", vp), ("va", va), ("vwindow", vwindow))
         self._tangent_refusals("gn_cell_product", tangents)
-        B, Z, N, M = self._cell_args("gn_cell_product", x, p, a, None, group, qweight, obs_weight)
-        xb, xstride, p_, a_, s_ = self._tangent_args("gn_cell_product", x, p, a, gaussian_window_size, tangents)
-        dev = p_.device
-        lib = _lib.load()
-        packed = self.pack(params)
-        q_ = qweight.float().contiguous() if qweight is not None else None
-        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
-        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_gn_workspace_bytes)
-        flags = self._det_flag()
-        if reuse is not None and reuse == self._ws_tag(ws) and reuse[1] is not None:
-            flags |= _lib.ENF_GN_REUSE_POINT
-        gp, ga = torch.empty_like(p_), torch.empty_like(a_)
-        gs = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
-        _lib.launch(dev, lib.enf_gn_product_g, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(vp), _ptr(va),
-                    _ptr(vwindow), _ptr(packed), int(group), _ptr(q_), _ptr(w_), float(grad_scale), _ptr(gp), _ptr(ga), _ptr(gs),
-                    _ptr(ws), ws.numel(), flags, st)
-        self._ws_touch(ws)
-        return gp, ga, (gs if s_ is not None else None)
+        kind = _Cells(group, qweight)
+        self._obs_args("gn_cell_product", kind, x, p, a, None, obs_weight, None)
+        latents = self._tangent_args("gn_cell_product", x, p, a, gaussian_window_size, tangents)
+        return self._gn_call(kind, params, x.shape[1], latents, (vp, va, vwindow), obs_weight, None, grad_scale, reuse)
 
     def cell_fit_loss(self, params, x, p, a, gaussian_window_size, target, group, qweight=None, obs_weight=None, obs_channel_weight=None):
         """The grouped loss of the decode of latents as a function of the LATENTS, without a decode in memory and with the decoder's
@@ -1036,7 +997,7 @@ class EquivariantCrossAttentionNeF:
         (loss and d loss / d (p, a, window) at grad_scale 1); the backward multiplies the stored gradients by the incoming scalar.
         Differentiable once, with respect to ``p``, ``a`` and ``gaussian_window_size`` only -- ``params`` get no gradient (take
         apply + cell_mse where they need one).  Arguments as mse_value_and_cell_grads.  Returns the loss, a 0-d tensor."""
-        self._cell_args("cell_fit_loss", x, p, a, target, group, qweight, obs_weight, obs_channel_weight)
+        self._obs_args("cell_fit_loss", _Cells(group, qweight), x, p, a, target, obs_weight, obs_channel_weight)
         if self.use_gaussian_window and gaussian_window_size is None:
             raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
         win = gaussian_window_size if self.use_gaussian_window else None
@@ -1051,51 +1012,7 @@ class EquivariantCrossAttentionNeF:
         ``obs_channel_weight``: (B, M, O) in place of ``obs_weight`` (both: ValueError), one weight per observed value
         (enf_mse_value_grad_gc): loss = sum_{b,m,o} cw (obs - target)^2 / (B M O).
         Returns the loss, a 0-d tensor."""
-        if obs_weight is not None and obs_channel_weight is not None:
-            raise ValueError("cell_mse: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
-        if int(group) not in self.GROUP_SIZES:
-            raise ValueError(f"group must be one of {self.GROUP_SIZES}, got {group}")
-        if out.dim() != 3 or out.shape[1] % int(group):
-            raise ValueError(f"out must be (B, M * group, O), got {tuple(out.shape)} with group = {group}")
-        B, N, O = out.shape
-        M = N // int(group)
-        if tuple(target.shape) != (B, M, O):
-            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, O)}")
-        if qweight is not None and tuple(qweight.shape) != (B, N):
-            raise ValueError(f"qweight has shape {tuple(qweight.shape)}, expected {(B, N)}")
-        if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
-            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
-        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, M, O):
-            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, M, O)}")
-        if not (out.is_cuda and target.is_cuda):
-            raise _lib.EnfError("EquivariantCrossAttentionNeF.cell_mse needs CUDA/HIP tensors: there is no CPU path")
-        return _CellMseFunction.apply(out, target, int(group), qweight, obs_weight, self._det_flag(), obs_channel_weight)
-
-    # ------------------------------------------------------------------ sparse linear observations (any linear operator, CSR)
-    def _operator_args(self, what, x, p, a, target, op, obs_weight, obs_channel_weight):
-        """The shapes of a call against an operator (fitting/operators.py: SparseObservations), checked before anything touches the
-        device: x (B, N, dx) with N = op.N, target (B, M, O) with M = op.M, obs_weight (B, M) or None, obs_channel_weight (B, M, O) or
-        None (never both).  Returns (B, Z, N, M)."""
-        if obs_weight is not None and obs_channel_weight is not None:
-            raise ValueError(f"{what}: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
-        if self.num_layers > 0:
-            raise NotImplementedError(f"{what} is built for num_layers = 0 (the fused decoder)")
-        if x.dim() != 3 or p.dim() != 3 or a.dim() != 3:
-            raise ValueError("x, p and a must be (batch, ., .)")
-        B, Z, N, M = p.shape[0], p.shape[1], x.shape[1], op.M
-        if x.shape[0] != B or a.shape[0] != B or a.shape[1] != Z:
-            raise ValueError(f"x {tuple(x.shape)}, p {tuple(p.shape)} and a {tuple(a.shape)} disagree on the batch or the latents")
-        if N != op.N:
-            raise ValueError(f"x holds {N} query points per signal, the operator has {op.N} columns")
-        if tuple(target.shape) != (B, M, self.num_out):
-            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, M, self.num_out)}")
-        if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
-            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
-        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, M, self.num_out):
-            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, M, self.num_out)}")
-        if not (x.is_cuda and p.is_cuda and a.is_cuda and target.is_cuda and op.val.is_cuda):
-            raise _lib.EnfError(f"EquivariantCrossAttentionNeF.{what} needs CUDA/HIP tensors: there is no CPU path")
-        return B, Z, N, M
+        return self._decode_loss("cell_mse", _Cells(group, qweight), out, target, obs_weight, obs_channel_weight)
 
     @torch.no_grad()
     def mse_value_and_operator_grads(self, params, x, p, a, gaussian_window_size, target, op, obs_weight=None, obs_channel_weight=None,
@@ -1108,33 +1025,10 @@ class EquivariantCrossAttentionNeF:
         ``loss_out``: an already ZEROED float32 (1,) tensor the loss is added to.  ``return_errors``: also err_a (B, M) and loss_b (B,).
         ``deterministic``: None for the model's mode, or True / False for this call.
         Returns (loss (1,), dp, da, dwindow or None), with ``return_errors`` followed by (err_a, loss_b)."""
-        B, Z, N, M = self._operator_args("mse_value_and_operator_grads", x, p, a, target, op, obs_weight, obs_channel_weight)
-        sigma = gaussian_window_size if self.use_gaussian_window else None
-        if self.use_gaussian_window and sigma is None:
-            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
-        lib = _lib.load()
-        packed = self.pack(params)
-        p_, a_, s_ = self._latent_args(p, a, sigma)
-        dev = p_.device
-        xb, xstride = self._x_arg(x.float())
-        flags = self._det_flag() if deterministic is None else (_lib.ENF_FIT_DETERMINISTIC if deterministic else 0)
-        desc = self._desc(B, N, Z, masks=self._masks)
-        ws = self._workspace(desc, dev, lambda d, _f: lib.enf_obs_workspace_bytes(d, M, _lib.ENF_FIT_DETERMINISTIC))
-        tgt = target.float().contiguous()
-        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
-        c_ = obs_channel_weight.float().contiguous() if obs_channel_weight is not None else None
-        loss = loss_out if loss_out is not None else torch.zeros(1, device=dev, dtype=torch.float32)
-        dp, da = torch.empty_like(p_), torch.empty_like(a_)
-        dsig = torch.empty((B, Z, 1), device=dev, dtype=torch.float32)
-        err = torch.empty((B, M), device=dev, dtype=torch.float32) if return_errors else None
-        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if return_errors else None
-        s = op.struct()
-        _lib.launch(dev, lib.enf_fit_step_a, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    ctypes.byref(s), _ptr(w_), _ptr(c_), float(grad_scale), _ptr(loss), _ptr(dp), _ptr(da), _ptr(dsig), _ptr(err), _ptr(loss_b),
-                    _ptr(ws), ws.numel(), flags, _lib.stream(dev))
-        self._ws_touch(ws)
-        res = (loss, dp, da, dsig if sigma is not None else None)
-        return res + (err, loss_b) if return_errors else res
+        kind = _Operator(op)
+        M = self._obs_args("mse_value_and_operator_grads", kind, x, p, a, target, obs_weight, obs_channel_weight)
+        return self._fit_step(kind, M, params, x, p, a, gaussian_window_size, target, obs_weight, obs_channel_weight, grad_scale, loss_out,
+                              return_errors, deterministic=deterministic)
 
     @torch.no_grad()
     def eval_operator_loss(self, params, x, p, a, gaussian_window_size, target, op, obs_weight=None, obs_channel_weight=None,
@@ -1143,70 +1037,35 @@ class EquivariantCrossAttentionNeF:
         and loss_b (B,) as mse_value_and_operator_grads(return_errors=True) gives them at the same point -- the same bits, in every mode.
         ``loss_out``: an already ZEROED float32 (1,) tensor; the scalar loss is added to it.  ``per_signal`` False skips loss_b.
         Returns (loss_b or None, err_a)."""
-        B, Z, N, M = self._operator_args("eval_operator_loss", x, p, a, target, op, obs_weight, obs_channel_weight)
-        sigma = gaussian_window_size if self.use_gaussian_window else None
-        if self.use_gaussian_window and sigma is None:
-            raise AssertionError("gaussian_window_size is required when use_gaussian_window=True")
-        lib = _lib.load()
-        packed = self.pack(params)
-        p_, a_, s_ = self._latent_args(p, a, sigma)
-        dev = p_.device
-        xb, xstride = self._x_arg(x.float())
-        flags = self._det_flag() if deterministic is None else (_lib.ENF_FIT_DETERMINISTIC if deterministic else 0)
-        desc = self._desc(B, N, Z, masks=self._masks)
-        ws = self._workspace(desc, dev, lambda d, _f: lib.enf_obs_workspace_bytes(d, M, _lib.ENF_FIT_DETERMINISTIC))
-        tgt = target.float().contiguous()
-        w_ = obs_weight.float().contiguous() if obs_weight is not None else None
-        c_ = obs_channel_weight.float().contiguous() if obs_channel_weight is not None else None
-        err = torch.empty((B, M), device=dev, dtype=torch.float32)
-        loss_b = torch.empty((B,), device=dev, dtype=torch.float32) if per_signal else None
-        s = op.struct(transposed=False)
-        _lib.launch(dev, lib.enf_eval_loss_a, ctypes.byref(desc), _ptr(xb), xstride, _ptr(p_), _ptr(a_), _ptr(s_), _ptr(packed), _ptr(tgt),
-                    ctypes.byref(s), _ptr(w_), _ptr(c_), _ptr(loss_out), _ptr(err), _ptr(loss_b), _ptr(ws), ws.numel(), flags, _lib.stream(dev))
-        self._ws_touch(ws)
-        return loss_b, err
+        kind = _Operator(op)
+        M = self._obs_args("eval_operator_loss", kind, x, p, a, target, obs_weight, obs_channel_weight)
+        return self._eval(kind, M, params, x, p, a, gaussian_window_size, target, obs_weight, obs_channel_weight, loss_out, per_signal,
+                          deterministic)
 
     def operator_mse(self, out, target, op, obs_weight=None, obs_channel_weight=None):
         """The loss of a decode that exists in memory against an operator's observations (include/enf_hip.h: enf_mse_value_grad_a), for
         the weight-gradient path: loss = sum_{b,m,o} w (A out - target)^2 / (B M O) with out (B, N, O), target (B, M, O).  A
         torch.autograd.Function as cell_mse: loss and d out come from the two kernels of csrc/enf_obs.hip, the backward multiplies d out
         by the incoming scalar; differentiable once, with respect to ``out`` only.  Returns the loss, a 0-d tensor."""
-        if obs_weight is not None and obs_channel_weight is not None:
-            raise ValueError("operator_mse: pass obs_weight (one weight per observation) or obs_channel_weight (one per value), not both")
-        if out.dim() != 3 or out.shape[1] != op.N:
-            raise ValueError(f"out must be (B, {op.N}, O) for this operator, got {tuple(out.shape)}")
-        B, N, O = out.shape
-        if tuple(target.shape) != (B, op.M, O):
-            raise ValueError(f"target has shape {tuple(target.shape)}, expected {(B, op.M, O)}")
-        if obs_weight is not None and tuple(obs_weight.shape) != (B, op.M):
-            raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, op.M)}")
-        if obs_channel_weight is not None and tuple(obs_channel_weight.shape) != (B, op.M, O):
-            raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {(B, op.M, O)}")
-        if not (out.is_cuda and target.is_cuda and op.val.is_cuda):
-            raise _lib.EnfError("EquivariantCrossAttentionNeF.operator_mse needs CUDA/HIP tensors: there is no CPU path")
-        return _OperatorMseFunction.apply(out, target, op, obs_weight, obs_channel_weight, self._det_flag())
+        return self._decode_loss("operator_mse", _Operator(op), out, target, obs_weight, obs_channel_weight)
 
 
-class _OperatorMseFunction(torch.autograd.Function):
-    """nef.operator_mse: enf_mse_value_grad_a once in the forward (loss and d out at grad_scale 1); the backward scales the stored d out."""
+class _ObsMseFunction(torch.autograd.Function):
+    """nef.cell_mse / nef.operator_mse: the kind's enf_mse_value_grad_* call once in the forward (loss and d out at grad_scale 1); the
+    backward scales the stored d out."""
 
     @staticmethod
-    def forward(ctx, out, target, op, obs_weight, obs_channel_weight, det):
+    def forward(ctx, out, target, kind, weight, cweight, det):
         lib = _lib.load()
         dev = out.device
-        o_ = out.detach().float().contiguous()
+        o_, t_, w_, c_ = _f32(out), _f32(target), _f32(weight), _f32(cweight)
         B, N, O = o_.shape
-        t_ = target.detach().float().contiguous()
-        w_ = obs_weight.detach().float().contiguous() if obs_weight is not None else None
-        c_ = obs_channel_weight.detach().float().contiguous() if obs_channel_weight is not None else None
         need = ctx.needs_input_grad[0]
         dout = torch.empty_like(o_) if need else None
         loss = torch.zeros(1, device=dev, dtype=torch.float32)
-        nscr = int(lib.enf_mse_a_scratch_bytes(B, op.M, O, 1 if need else 0, det))
+        fn, nscr, mid = kind.mse(lib, B, N, O, w_, c_, need, det)
         scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr else None
-        s = op.struct(transposed=need)
-        _lib.launch(dev, lib.enf_mse_value_grad_a, _ptr(o_), _ptr(t_), B, N, O, ctypes.byref(s), _ptr(w_), _ptr(c_), 1.0, _ptr(dout),
-                    _ptr(loss), None, _ptr(scr), nscr, det, _lib.stream(dev))
+        _lib.launch(dev, fn, _ptr(o_), _ptr(t_), B, N, O, *mid, 1.0, _ptr(dout), _ptr(loss), None, _ptr(scr), nscr, det, _lib.stream(dev))
         if need:
             ctx.save_for_backward(dout)
         ctx.out_dtype = out.dtype
@@ -1217,41 +1076,6 @@ class _OperatorMseFunction(torch.autograd.Function):
     def backward(ctx, g):
         (dout,) = ctx.saved_tensors
         return (dout * g).to(ctx.out_dtype), None, None, None, None, None
-
-
-class _CellMseFunction(torch.autograd.Function):
-    """nef.cell_mse: enf_mse_value_grad_g (with obs_channel_weight: _gc) once in the forward (loss and d out at grad_scale 1); the
-    backward scales the stored d out."""
-
-    @staticmethod
-    def forward(ctx, out, target, group, qweight, obs_weight, det, obs_channel_weight=None):
-        lib = _lib.load()
-        dev = out.device
-        o_ = out.detach().float().contiguous()
-        B, N, O = o_.shape
-        t_ = target.detach().float().contiguous()
-        q_ = qweight.detach().float().contiguous() if qweight is not None else None
-        w_ = obs_weight.detach().float().contiguous() if obs_weight is not None else None
-        need = ctx.needs_input_grad[0]
-        dout = torch.empty_like(o_) if need else None
-        loss = torch.zeros(1, device=dev, dtype=torch.float32)
-        nscr = int(lib.enf_mse_scratch_bytes(B * (N // group) * O, det))
-        scr = torch.empty(nscr, device=dev, dtype=torch.uint8) if nscr else None
-        fn = lib.enf_mse_value_grad_g
-        if obs_channel_weight is not None:
-            fn, w_ = lib.enf_mse_value_grad_gc, obs_channel_weight.detach().float().contiguous()
-        _lib.launch(dev, fn, _ptr(o_), _ptr(t_), B, N, O, group, _ptr(q_), _ptr(w_), 1.0, _ptr(dout), _ptr(loss), None,
-                    _ptr(scr), nscr, det, _lib.stream(dev))
-        if need:
-            ctx.save_for_backward(dout)
-        ctx.out_dtype = out.dtype
-        return loss.reshape(())
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        (dout,) = ctx.saved_tensors
-        return (dout * g).to(ctx.out_dtype), None, None, None, None, None, None
 
 
 class _CellFitLossFunction(torch.autograd.Function):
