@@ -32,7 +32,7 @@ EXPORTS = ["enf_abi_version", "enf_strerror", "enf_invariant_dim", "enf_invarian
            "enf_field_grad_workspace_bytes", "enf_field_grad", "enf_query_vjp",
            "enf_field_tangent_workspace_bytes", "enf_field_tangent", "enf_field_tangent_x",
            "enf_field_second_workspace_bytes", "enf_field_second_x",
-           "enf_gn_workspace_bytes", "enf_gn_product", "enf_gn_product_g", "enf_cg_update",
+           "enf_gn_workspace_bytes", "enf_gn_product", "enf_gn_product_g", "enf_gn_a_workspace_bytes", "enf_gn_product_a", "enf_cg_update",
            "enf_ode_conv_forward", "enf_ode_conv_backward_basis", "enf_ode_conv_backward_weight", "enf_ode_conv_backward_weight_scratch_bytes", "enf_ode_poly_num_features", "enf_ode_poly_forward",
            "enf_ode_poly_backward", "enf_ode_vec_readout_forward", "enf_ode_vec_readout_backward", "enf_ode_block_supported", "enf_ode_block_scratch_bytes", "enf_ode_block_forward", "enf_ode_block_backward",
            "enf_ode_basis_supported", "enf_ode_basis_scratch_bytes", "enf_ode_basis_forward",
@@ -307,6 +307,10 @@ def _bind(path, hooks):
     lib.enf_gn_product.argtypes = [dp, vp, i64] + [vp] * 9 + [ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
     # the product on grouped observations: (G, qweight, oweight) in place of (weight, cweight)
     lib.enf_gn_product_g.argtypes = [dp, vp, i64] + [vp] * 7 + [ctypes.c_int32, vp, vp, ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
+    # the product on sparse observations: (op, oweight, cweight) in their place; its size query takes M
+    lib.enf_gn_a_workspace_bytes.restype = sz
+    lib.enf_gn_a_workspace_bytes.argtypes = [dp, ctypes.c_int32, cu]
+    lib.enf_gn_product_a.argtypes = [dp, vp, i64] + [vp] * 7 + [op, vp, vp, ctypes.c_float] + [vp] * 4 + [sz, cu, vp]
     lib.enf_cg_update.argtypes = [ci, ctypes.POINTER(EnfCgSegment), ctypes.c_int32, ctypes.c_int32, vp, vp, vp]
     lib.enf_pair_backward_scratch_bytes.restype = sz
     lib.enf_pair_backward_scratch_bytes.argtypes = [dp, cu]

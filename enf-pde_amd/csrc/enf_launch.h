@@ -242,6 +242,10 @@ bool enf_obs_op_ok(const EnfSparseObs* op, bool transposed);
 // loss NULL or *loss += the loss -- with part != NULL (ENF_OBS_MAX_BLOCKS floats) through it and enf_launch_loss_sum
 int enf_launch_obs_loss(const EnfSparseObs& op, int N, int B, int O, const float* out, const float* target, const float* oweight,
                         const float* cweight, float* r, float* err_a, float* loss, float* part, hipStream_t st);
+// kernel 1 with weights and no target (enf_gn_product_a): r (B, M, O) = (w > 0 ? w (A x) : 0) of x (B, N, O), every element written;
+// oweight (B, M), cweight (B, M, O), or neither (1); no loss, no atomic
+int enf_launch_obs_weigh(const EnfSparseObs& op, int N, int B, int O, const float* x, const float* oweight, const float* cweight, float* r,
+                         hipStream_t st);
 // kernel 2, the transposed product: dout (B, N, O) = gs * A^T r, every element written
 int enf_launch_obs_transpose(const EnfSparseObs& op, int N, int B, int O, const float* r, float gs, float* dout, hipStream_t st);
 // the regions enf_fit_step_a / enf_eval_loss_a carve behind the plain or deterministic workspace (`base` = its total), byte offsets
@@ -293,8 +297,8 @@ struct EnfLossSpec {
     if (kind == ENF_LOSS_GROUPS && !(enf_group_size_ok(G) && d && d->N % G == 0)) return ENF_EINVAL;
     // (the grouped fit has no region of its workspace free for the errors)
     if (kind == ENF_LOSS_GROUPS && call == ENF_LOSS_FIT && loss_b && !err) return ENF_EINVAL;
-    // an operator that enf_obs_op_ok refuses (the fit reads the CSC too); there is no product against one
-    if (kind == ENF_LOSS_OPERATOR && (call == ENF_LOSS_GN || !enf_obs_op_ok(op, call == ENF_LOSS_FIT))) return ENF_EINVAL;
+    // an operator that enf_obs_op_ok refuses (the fit and the product read the CSC too)
+    if (kind == ENF_LOSS_OPERATOR && !enf_obs_op_ok(op, call != ENF_LOSS_EVAL)) return ENF_EINVAL;
     return ENF_OK;
   }
 };

@@ -1,6 +1,7 @@
 // enf_obs.hip -- sparse linear observations (include/enf_hip.h, "Sparse linear observations"): the two products of an operator
 // A (M x N), shared by the B signals of a call, with a decode that exists in memory.
 //   forward     obs[b,m,o] = sum_{e in row m} val[e] out[b, col[e], o]       with the loss: r = w (obs - target), err_a, loss
+//                                                                            or with weights alone: r = w obs (enf_gn_product_a)
 //   transposed  d out[b,n,o] = gs * sum_{e in column n} tval[e] r[b, trow[e], o]
 // Both are ONE kernel body, enf_obs_kernel: y[b,i,:] = scale * sum_e v[e] x[b, idx[e], :] over the entries [ptr[i], ptr[i + 1]), the
 // forward launches with the loss epilogue behind the sum.  Memory-bound work on a few hundred kilobytes; no atomics but the scalar
@@ -68,8 +69,11 @@ __device__ __forceinline__ void obs_accumulate(const ObsArgs& A, const float* __
   }
 }
 
-template <int CH, bool VEC, bool LOSS>
+// WEIGH (the Gauss-Newton product's forward, enf_launch_obs_weigh): weights without a target -- r = (w > 0 ? w y : 0) stored in the
+// sum's pass; no loss, no atomic, no LDS.  An instantiation of its own: the other two keep their code.
+template <int CH, bool VEC, bool LOSS, bool WEIGH = false>
 __global__ __launch_bounds__(256) void enf_obs_kernel(ObsArgs A) {
+  static_assert(!(LOSS && WEIGH), "the weighted product has no target");
   const int lane = threadIdx.x & 63;
   const long long items = (long long)A.B * A.rows;
   const long long waves = (items + A.rpw - 1) / A.rpw;
@@ -128,6 +132,17 @@ __global__ __launch_bounds__(256) void enf_obs_kernel(ObsArgs A) {
           }
         }
         if (A.r) obs_store<CH, VEC>(A.r + at, rr, kc);
+      } else if constexpr (WEIGH) {
+        ObsVec<CH> wv4{};
+        if (A.cweight) wv4 = obs_load<CH, VEC>(A.cweight + at, kc);
+        const float w1 = A.oweight ? A.oweight[i] : 1.f;
+        ObsVec<CH> rr;
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+          const float w = A.cweight ? wv4.v[k] : w1;
+          rr.v[k] = (k < kc && w > 0.f) ? w * s.v[k] : 0.f;               // weight 0: a select, the sum under it is not used
+        }
+        obs_store<CH, VEC>(A.r + at, rr, kc);
       } else {
 #pragma unroll
         for (int k = 0; k < CH; ++k) s.v[k] *= A.scale;
@@ -167,10 +182,10 @@ static bool obs_vec4(const ObsArgs& A) {
   return A.O % 4 == 0 && al(A.x) && al(A.y) && al(A.r) && al(A.target) && al(A.cweight);
 }
 // one channel per pass at O == 1, four otherwise (scalar accesses, the last pass short), the 16-byte form where obs_vec4 holds
-template <bool LOSS> static int obs_launch(const ObsArgs& A, unsigned blocks, hipStream_t st) {
-  if (obs_vec4(A)) hipLaunchKernelGGL((enf_obs_kernel<4, true, LOSS>), dim3(blocks), dim3(256), 0, st, A);
-  else if (A.O > 1) hipLaunchKernelGGL((enf_obs_kernel<4, false, LOSS>), dim3(blocks), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL((enf_obs_kernel<1, false, LOSS>), dim3(blocks), dim3(256), 0, st, A);
+template <bool LOSS, bool WEIGH = false> static int obs_launch(const ObsArgs& A, unsigned blocks, hipStream_t st) {
+  if (obs_vec4(A)) hipLaunchKernelGGL((enf_obs_kernel<4, true, LOSS, WEIGH>), dim3(blocks), dim3(256), 0, st, A);
+  else if (A.O > 1) hipLaunchKernelGGL((enf_obs_kernel<4, false, LOSS, WEIGH>), dim3(blocks), dim3(256), 0, st, A);
+  else hipLaunchKernelGGL((enf_obs_kernel<1, false, LOSS, WEIGH>), dim3(blocks), dim3(256), 0, st, A);
   return hipGetLastError() == hipSuccess ? ENF_OK : ENF_ELAUNCH;
 }
 
@@ -197,6 +212,18 @@ int enf_launch_obs_loss(const EnfSparseObs& op, int N, int B, int O, const float
   const unsigned blocks = obs_blocks((long long)B * op.M, A.rpw);
   if (int rc = obs_launch<true>(A, blocks, st)) return rc;
   return loss && part ? enf_launch_loss_sum(part, (int)blocks, loss, st) : ENF_OK;
+}
+
+// the forward product with weights and no target (the Gauss-Newton product): r (B, M, O) = (w > 0 ? w (A x) : 0), w = oweight (B, M),
+// cweight (B, M, O) or 1; kernel 1's work split and order of sums
+int enf_launch_obs_weigh(const EnfSparseObs& op, int N, int B, int O, const float* x, const float* oweight, const float* cweight, float* r,
+                         hipStream_t st) {
+  ObsArgs A{};
+  A.ptr = op.row_ptr; A.idx = op.col; A.v = op.val; A.nnz = op.nnz; A.rows = op.M; A.ncols = N; A.B = B; A.O = O;
+  A.tree = 1; A.rpw = obs_rows_per_wave(op.nnz, op.M, true);
+  A.x = x; A.scale = 1.f;
+  A.oweight = oweight; A.cweight = cweight; A.r = r;
+  return obs_launch<false, true>(A, obs_blocks((long long)B * op.M, A.rpw), st);
 }
 
 // the transposed product (kernel 2): d out (B, N, O) = gs * A^T r, every element written, a column in the CSC's entry order

@@ -19,7 +19,9 @@
 //   enf_gn_tail_kernel            the tail's chain with tangents, d out = w tan formed in registers, the tail's backward chain
 // followed by the backward pair kernel and the prologue backward of the other files.  enf_gn_product_g is the same product for grouped
 // observations (cell averages): the same host sequence (gn_product_sequence) with the GRP instantiation of the tail, which forms the
-// group sum of the tangent over the wave's query lanes in front of d out.
+// group sum of the tangent over the wave's query lanes in front of d out.  enf_gn_product_a is the product for a sparse observation
+// operator: the same host sequence with the tail cut open -- the stash form of enf_tail_tangent_kernel, the two products of enf_obs.hip
+// on tan in memory, enf_tail.hip's backward on the stash.
 // There is one copy of each thing the two entry points have in common: the doubled tail chain (tail_forward_tan, which stashes the
 // pre-activations for the Gauss-Newton tail only), the panel product (panel_gemm2, whose one-operand form serves the backward chain),
 // the launcher and its (D, H) dispatch (launch_pair_tail), and the host sequence (tan_call: refusals, dimensions, workspace;
@@ -468,9 +470,15 @@ struct TailTanArgs {
   int NQ, O;
   float inv_hd;          // 1 / (true heads * true num_hidden)
 };
+// The stash form's argument (enf_gn_product_a), appended behind the block the plain form takes, as GnTailArgsG below.
+struct TailTanArgsS : TailTanArgs {
+  float* act;            // (NQ, TailCfg::ACT): the pre-activations and the LayerNorm's mu, rstd, as enf_tail_fwd_kernel<.., SAVE> leaves them
+};
 
-template <int D, int H, bool BF16>
-__global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(TailTanArgs A) {
+// SAVE (enf_gn_product_a): tail_forward_tan's stash in `act` for enf_tail_bwd_kernel's stash form (enf_tail.hip), which runs behind
+// the two operator products on `tan`; stores tan and no out.  Clamped (duplicate) queries stash the same values, as in the other tails.
+template <int D, int H, bool BF16, bool SAVE = false>
+__global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(std::conditional_t<SAVE, TailTanArgsS, TailTanArgs> A) {
   constexpr int HD = H * D;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
@@ -479,9 +487,11 @@ __global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(TailTanArgs A)
   Pipe P;
   tail_tan_open<D, H, BF16>(P, smem, A.blob, A.L, tid);
   f32x4 o4[2], do4[2];
-  tail_forward_tan<D, H, BF16, false, 1024>(o4, do4, A.ybar + (size_t)qi * HD, A.ydot + (size_t)qi * HD, nullptr, A.L,
-                                            reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, smem, NO_STAGE, lane,
-                                            quad, A.inv_hd);
+  float* act = nullptr;
+  if constexpr (SAVE) act = A.act + (size_t)qi * TailCfg<D, H, BF16>::ACT;
+  tail_forward_tan<D, H, BF16, SAVE, 1024>(o4, do4, A.ybar + (size_t)qi * HD, A.ydot + (size_t)qi * HD, act, A.L,
+                                           reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, smem, NO_STAGE, lane,
+                                           quad, A.inv_hd);
   if (q0 + col < A.NQ) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -489,7 +499,9 @@ __global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(TailTanArgs A)
       for (int i = 0; i < 4; ++i) {
         const int o = 16 * t + 4 * quad + i;
         if (o < A.O) {
-          if (A.out) A.out[(size_t)(q0 + col) * A.O + o] = o4[t][i];
+          if constexpr (!SAVE) {
+            if (A.out) A.out[(size_t)(q0 + col) * A.O + o] = o4[t][i];
+          }
           A.tan[(size_t)(q0 + col) * A.O + o] = do4[t][i];
         }
       }
@@ -661,6 +673,7 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(std::conditional_t<
 
 // ---------------------------------------------------------------- launch: the pair kernel, then the entry point's tail
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const TailTanArgs*) { return enf_tail_tangent_kernel<D, H, BF16>; }
+template <int D, int H, bool BF16> constexpr auto tail_kernel(const TailTanArgsS*) { return enf_tail_tangent_kernel<D, H, BF16, true>; }
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgs*) { return enf_gn_tail_kernel<D, H, BF16>; }
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgsG*) { return enf_gn_tail_kernel<D, H, BF16, true>; }
 
@@ -750,7 +763,26 @@ extern "C" size_t enf_gn_workspace_bytes(const EnfDesc* d, unsigned flags) {
 // The one copy of the product's host sequence, seeded by the loss `ls` describes (enf_launch.h: EnfLossSpec): on points the weights
 // (B, N) or (B, N, O); on grouped observations the grouped instantiation of the tail with the factors and observation weights,
 // 1 / (B M O) in the scale.  What ls.check refuses is ENF_EINVAL, behind ENF_EUNSUPPORTED and before ENF_EWORKSPACE.
+// An operator couples rows across tiles and waves, so its tail is cut open as the fit step's: the tangent tail's stash form leaves tan
+// and the stash, the two products of enf_obs.hip form d out = gs A^T (w A tan) in memory, and the tail's own backward (enf_tail.hip,
+// the stash form) runs on it.  Both tails store TailCfg's layout per query through store_rows, so the one reads the other's stash.
 namespace {
+// enf_gn_product_a's regions behind tan_workspace(..).total: tan (B, N, O) | r (B, M, O) | d out (B, N, O).  The total is never below
+// the deterministic enf_obs_workspace, so one buffer serves the fit step, the products and the evaluation of an LM step.
+struct GnObsWorkspace { size_t tan, r, dout, total; };
+GnObsWorkspace gn_obs_workspace(const EnfDims& m, bool det, int M) {
+  GnObsWorkspace Y;
+  const size_t bno = enf_align(sizeof(float) * (size_t)m.B * m.N * m.O);
+  Y.tan = tan_workspace(m, det).total;
+  Y.r = Y.tan + bno;
+  Y.dout = Y.r + enf_align(sizeof(float) * (size_t)m.B * (size_t)M * m.O);
+  Y.total = Y.dout + bno;
+  const EnfWorkspace W = enf_workspace(m);
+  const size_t fit = enf_obs_workspace(m, enf_det_workspace(m, W).total, M).total;
+  if (Y.total < fit) Y.total = fit;
+  return Y;
+}
+
 int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
                         const float* vp, const float* va, const float* vsigma, const void* packed, float grad_scale, float* gp, float* ga,
                         float* gsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const EnfLossSpec& ls) {
@@ -764,7 +796,9 @@ int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, con
   const EnfWorkspace& W = c.W;
   hipStream_t st = c.st;
   const char* pk = c.blob;
-  const bool zb = enf_use_zfold_bwd(m), grp = ls.kind == ENF_LOSS_GROUPS;
+  const bool zb = enf_use_zfold_bwd(m), grp = ls.kind == ENF_LOSS_GROUPS, ao = ls.kind == ENF_LOSS_OPERATOR;
+  const GnObsWorkspace Y = gn_obs_workspace(m, det, ao ? ls.op->M : 1);
+  if (ao && workspace_bytes < Y.total) return ENF_EWORKSPACE;
   if ((rc = enf_side_join_pending(st, workspace))) return rc;
   // the point: latent table, what the prologue backward reads, and the z-fold backward's per-latent matrices -- unless the caller
   // vouches that a fit step or an earlier product at this point left them
@@ -780,7 +814,16 @@ int gn_product_sequence(const EnfDesc* d, const float* x, int64_t x_bstride, con
   GA.dybar = c.F(W.dybar); GA.delta = c.F(W.delta); GA.act = c.F(W.tail_act);
   GA.NQ = m.B * m.N; GA.O = m.O; GA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
   GA.gs = 2.0f * grad_scale / ((float)m.B * (float)ls.rows(m) * (float)m.O);
-  if (grp) {
+  if (ao) {
+    // tan and the stash -> [kernel 1] r = w (A tan) -> [kernel 2] d out = gs A^T r -> the tail's backward on the stash
+    TailTanArgsS TA;
+    TA.ybar = PA.ybar; TA.ydot = PA.ydot; TA.blob = pk; TA.L = L; TA.out = nullptr; TA.tan = c.F(Y.tan);
+    TA.NQ = GA.NQ; TA.O = m.O; TA.inv_hd = GA.inv_hd; TA.act = GA.act;
+    if ((rc = launch_pair_tail(m, PA, TA, st))) return rc;
+    if ((rc = enf_launch_obs_weigh(*ls.op, m.N, m.B, m.O, c.F(Y.tan), ls.weight, ls.cweight, c.F(Y.r), st))) return rc;
+    if ((rc = enf_launch_obs_transpose(*ls.op, m.N, m.B, m.O, c.F(Y.r), GA.gs, c.F(Y.dout), st))) return rc;
+    rc = enf_launch_tail(m, L, pk, PA.ybar, nullptr, c.F(Y.dout), GA.dybar, GA.delta, GA.act, ENF_TAIL_BWD | ENF_TAIL_STASH, st);
+  } else if (grp) {
     GA.G = ls.G; GA.qweight = ls.qweight; GA.oweight = ls.weight;
     rc = launch_pair_tail(m, PA, GA, st);
   } else rc = launch_pair_tail(m, PA, static_cast<const GnTailArgs&>(GA), st);
@@ -810,4 +853,18 @@ extern "C" int enf_gn_product_g(const EnfDesc* d, const float* x, int64_t x_bstr
                                 void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
   return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, grad_scale, gp, ga, gsigma, workspace, workspace_bytes, flags,
                              stream, EnfLossSpec{ENF_LOSS_GROUPS, oweight, nullptr, nullptr, nullptr, G, qweight});
+}
+
+// The product for sparse linear observations (include/enf_hip.h, "Gauss-Newton product on sparse observations")
+extern "C" size_t enf_gn_a_workspace_bytes(const EnfDesc* d, int32_t M, unsigned flags) {
+  if (enf_check_desc(d) != ENF_OK || !tangent_supported(d) || M < 1 || (flags & ~GN_FLAGS)) return 0;
+  return gn_obs_workspace(enf_dims(d), (flags & ENF_BWD_DETERMINISTIC) != 0, M).total;
+}
+
+extern "C" int enf_gn_product_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                                const float* vp, const float* va, const float* vsigma, const void* packed, const EnfSparseObs* op,
+                                const float* oweight, const float* cweight, float grad_scale, float* gp, float* ga, float* gsigma,
+                                void* workspace, size_t workspace_bytes, unsigned flags, void* stream) {
+  return gn_product_sequence(d, x, x_bstride, p, a, sigma, vp, va, vsigma, packed, grad_scale, gp, ga, gsigma, workspace, workspace_bytes, flags,
+                             stream, EnfLossSpec{ENF_LOSS_OPERATOR, oweight, cweight, nullptr, nullptr, 1, nullptr, op});
 }

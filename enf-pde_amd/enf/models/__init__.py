@@ -596,12 +596,14 @@ class EquivariantCrossAttentionNeF:
         return xb, xstride, p_, a_, s_
 
     # ------------------------------------------------------------------ Gauss-Newton product
-    def gn_reserve(self, B, N, Z, device):
+    def gn_reserve(self, B, N, Z, device, op=None):
         """Size this stream's cached workspace for ``gn_product`` on a (B, N, Z) problem.  The cache grows by REPLACING a buffer, so a
         fit step whose workspace a following ``gn_product(reuse=...)`` is to reuse must already run on the larger buffer: call this
-        first.  Returns the workspace's current tag (``workspace_tag``)."""
+        first.  ``op``: a SparseObservations -- the buffer of ``gn_operator_product`` (enf_gn_a_workspace_bytes), which also holds
+        ``mse_value_and_operator_grads`` and ``eval_operator_loss`` against that operator.  Returns the workspace's current tag
+        (``workspace_tag``)."""
         lib = _lib.load()
-        self._call_ctx(B, N, Z, torch.device(device), size_query=lib.enf_gn_workspace_bytes)
+        self._call_ctx(B, N, Z, torch.device(device), size_query=lib.enf_gn_workspace_bytes if op is None else _Operator(op).gn_size_query)
         return self.workspace_tag(device)
 
     def workspace_tag(self, device):
@@ -630,13 +632,13 @@ class EquivariantCrossAttentionNeF:
         return self._gn_call(_POINTS, params, x.shape[1], latents, (vp, va, vwindow), weight, channel_weight, grad_scale, reuse)
 
     def _gn_call(self, kind, params, N, latents, v, weight, cweight, grad_scale, reuse):
-        """The native call of ``gn_product`` / ``gn_cell_product`` behind their checks.  ``latents``: _tangent_args' tuple."""
+        """The native call of ``gn_product`` / ``gn_cell_product`` / ``gn_operator_product`` behind their checks.  ``latents``: _tangent_args' tuple."""
         xb, xstride, p_, a_, s_ = latents
         B, Z, dev = p_.shape[0], p_.shape[1], p_.device
         lib = _lib.load()
         packed = self.pack(params)
         w_, cw_ = _f32(weight), _f32(cweight)
-        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=lib.enf_gn_workspace_bytes)
+        desc, ws, st = self._call_ctx(B, N, Z, dev, size_query=kind.gn_size_query or lib.enf_gn_workspace_bytes)
         flags = self._det_flag()
         if reuse is not None and reuse == self._ws_tag(ws) and reuse[1] is not None:
             flags |= _lib.ENF_GN_REUSE_POINT
@@ -1041,6 +1043,25 @@ class EquivariantCrossAttentionNeF:
         M = self._obs_args("eval_operator_loss", kind, x, p, a, target, obs_weight, obs_channel_weight)
         return self._eval(kind, M, params, x, p, a, gaussian_window_size, target, obs_weight, obs_channel_weight, loss_out, per_signal,
                           deterministic)
+
+    @torch.no_grad()
+    def gn_operator_product(self, params, x, p, a, gaussian_window_size, op, obs_weight=None, obs_channel_weight=None, vp=None, va=None,
+                            vwindow=None, grad_scale=1.0, reuse=None):
+        """The Gauss-Newton matrix of a latent fit against a sparse operator's observations applied to a direction, in one native call
+        (include/enf_hip.h: enf_gn_product_a):
+            (gp, ga, gwindow or None) = grad_scale * 2 / (B M O) * J^T A^T W A J (vp, va, vwindow),    J = d out / d (p, a, window)
+        with A = ``op`` and W = ``obs_weight`` (B, M), ``obs_channel_weight`` (B, M, O) or 1 -- the observation model of
+        ``mse_value_and_operator_grads``, whose ``grad_scale`` makes this the Gauss-Newton Hessian of that step's loss in the units of
+        its gradient; what has weight 0 does not exist.  ``vp`` / ``va`` / ``vwindow`` and ``reuse`` as in ``gn_product``; the tag may
+        also come from right behind ``mse_value_and_operator_grads`` or an earlier ``gn_operator_product`` at the same point.  The
+        tangent of the decode, the weighted observations' tangent and d out exist only in the call's workspace.  Size the buffer
+        first: ``gn_reserve(..., op=op)``."""
+        tangents = (("vp", vp), ("va", va), ("vwindow", vwindow))
+        self._tangent_refusals("gn_operator_product", tangents)
+        kind = _Operator(op)
+        self._obs_args("gn_operator_product", kind, x, p, a, None, obs_weight, obs_channel_weight)
+        latents = self._tangent_args("gn_operator_product", x, p, a, gaussian_window_size, tangents)
+        return self._gn_call(kind, params, x.shape[1], latents, (vp, va, vwindow), obs_weight, obs_channel_weight, grad_scale, reuse)
 
     def operator_mse(self, out, target, op, obs_weight=None, obs_channel_weight=None):
         """The loss of a decode that exists in memory against an operator's observations (include/enf_hip.h: enf_mse_value_grad_a), for

@@ -22,6 +22,7 @@ class _Kind:
     wname, cwname, target_error = "obs_weight", "obs_channel_weight", ValueError      # the weights' keywords; a wrong target's error
     qweight = op = None         # cells: the factors (B, N); operator: the SparseObservations
     size_query = None           # a (desc, flags) workspace query of the kind's own, or the model's plain / deterministic workspace
+    gn_size_query = None        # the same for the Gauss-Newton product, or enf_gn_workspace_bytes
 
     def both(self, what):
         return ValueError(f"{what}: pass {self.wname} (one weight per observation) or {self.cwname} (one per value), not both")
@@ -113,6 +114,12 @@ class Operator(_Kind):
 
     def evaluate(self, lib, w, cw):
         return lib.enf_eval_loss_a, self.mid(w, cw, False)
+
+    def gn_size_query(self, desc, flags):    # the product's buffer also holds the fit step's and the evaluation's regions
+        return _lib.load().enf_gn_a_workspace_bytes(desc, self.op.M, flags)
+
+    def gn(self, lib, w, cw):
+        return lib.enf_gn_product_a, self.mid(w, cw, True)
 
     def mse(self, lib, B, N, O, w, cw, need, det):
         return lib.enf_mse_value_grad_a, int(lib.enf_mse_a_scratch_bytes(B, self.op.M, O, 1 if need else 0, det)), self.mid(w, cw, need)

@@ -10,6 +10,7 @@
   decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual  (no counterpart)   second derivatives in forward mode: c^T H c, the Laplacian, the Hessian, u_t - nu Lap u
   cg_solve, lm_fit_latents  (no counterpart)                   batched CG on the native Gauss-Newton product; Levenberg-Marquardt latent fits
   lm_fit_cell_averages  (no counterpart)                       the Levenberg-Marquardt fit against cell averages, on the grouped Gauss-Newton product
+  lm_fit_linear_observations  (no counterpart)                 the Levenberg-Marquardt fit against a sparse linear observation operator, on its Gauss-Newton product
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
   inner_loop_cells, gather_cell_samples, cell_mse_torch  (no counterpart)   the inner loop on sampled cells (the trainers' cells=) and the torch-op mirrors of its kernels
   SparseObservations, cell_operator, line_integrals, decode_observations, fit_linear_observations  (no counterpart)   fits against any sparse linear observation operator (CSR): 9- / 27-point and closed cell rules, ragged or overlapping rows, line integrals
@@ -25,7 +26,7 @@ from .model import get_model_pde
 from .inner_loop import inner_loop, decode, make_masks, make_signal_masks, default_meta_sgd_lrs
 from .derivatives import decode_jacobian, decode_tangent, decode_tendency, decode_directional, decode_material_derivative, divergence, curl_2d, gradient_norm
 from .derivatives import decode_second_directional, decode_laplacian, decode_hessian, decode_diffusion_residual
-from .gauss_newton import cg_solve, lm_fit_latents, lm_fit_cell_averages
+from .gauss_newton import cg_solve, lm_fit_latents, lm_fit_cell_averages, lm_fit_linear_observations
 from .cells import cell_quadrature, decode_cell_averages, fit_cell_averages, draw_cell_samples
 from .cells import inner_loop_cells, gather_cell_samples, cell_mse_torch
 from .operators import SparseObservations, cell_operator, line_integrals, decode_observations, fit_linear_observations
@@ -39,4 +40,4 @@ __all__ = ["get_model_pde", "inner_loop", "decode", "make_masks", "make_signal_m
            "solve_latent_ode", "PonitaODEGen", "MLPODE", "draw_point_masks", "decode_jacobian", "decode_tangent", "decode_tendency", "decode_directional", "decode_material_derivative",
            "divergence", "curl_2d", "gradient_norm", "cg_solve", "lm_fit_latents", "lm_fit_cell_averages", "cell_quadrature", "decode_cell_averages", "fit_cell_averages",
            "draw_cell_samples", "inner_loop_cells", "gather_cell_samples", "cell_mse_torch", "decode_second_directional", "decode_laplacian", "decode_hessian", "decode_diffusion_residual",
-           "SparseObservations", "cell_operator", "line_integrals", "decode_observations", "fit_linear_observations"]
+           "SparseObservations", "cell_operator", "line_integrals", "decode_observations", "fit_linear_observations", "lm_fit_linear_observations"]

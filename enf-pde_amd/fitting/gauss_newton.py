@@ -7,6 +7,8 @@ Levenberg-Marquardt loop on top of it.
                                       EquivariantCrossAttentionNeF.gn_product, accept where the signal's loss fell
   lm_fit_cell_averages(nef, ...)      the same loop against cell averages (grouped observations): the grouped fit step, the grouped
                                       product EquivariantCrossAttentionNeF.gn_cell_product, the grouped evaluation
+  lm_fit_linear_observations(nef, ...)  the same loop against a sparse linear observation operator (fitting/operators.py): the operator
+                                      fit step, the product EquivariantCrossAttentionNeF.gn_operator_product, the operator evaluation
 
 The loss is a sum over signals and the latents of different signals do not interact, so the Gauss-Newton matrix is block diagonal:
 every quantity below (damping, step length, acceptance) is per signal, and nothing in a loop iteration reads a value back to the host.
@@ -16,7 +18,7 @@ import torch
 from .. import _lib
 from .cells import _batched
 
-__all__ = ["cg_solve", "lm_fit_latents", "lm_fit_cell_averages"]
+__all__ = ["cg_solve", "lm_fit_latents", "lm_fit_cell_averages", "lm_fit_linear_observations"]
 
 
 def _cg_update(segs, B, Z, lam, rho, q=None):
@@ -65,13 +67,14 @@ def cg_solve(matvec, rhs, lam, iters):
 _COMPONENTS = ("p", "a", "window")
 
 
-def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate):
+def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate, op=None):
     """The one copy of the Levenberg-Marquardt loop.  The front ends bind their observation model into three callables on the
     current latents ``cur`` = {"p", "a", "window"}:
       step(cur)             -> ((dp, da, dwindow or None), loss_b (B,)): the fit step at gradient scale B with its per-signal losses
       product(cur, v, tag)  -> (gp, ga, gwindow or None): the Gauss-Newton product at the same scale along v = {component: tensor},
                                ``tag`` the workspace tag behind the last call at this point
       evaluate(cur)         -> loss_b (B,) at a trial point
+    ``op``: the operator of a fit against one -- the buffer is then reserved for its product (gn_reserve(..., op=op)).
     Returns what lm_fit_latents documents."""
     comps = tuple(components)
     if not comps or any(c not in _COMPONENTS for c in comps) or len(set(comps)) != len(comps):
@@ -86,7 +89,7 @@ def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, component
     lam = torch.full((B,), float(damping), device=dev, dtype=torch.float32)
     loss_b = torch.empty((int(steps) + 1, B), device=dev, dtype=torch.float32)
     accepted = torch.zeros((int(steps), B), device=dev, dtype=torch.bool)
-    nef.gn_reserve(B, N, Z, dev)            # the fit step below must already run on the buffer the products reuse
+    nef.gn_reserve(B, N, Z, dev, **({} if op is None else {"op": op}))      # the fit step below must already run on the buffer the products reuse
     last = None
     for k in range(int(steps)):
         g, lb = step(cur)
@@ -178,3 +181,43 @@ def lm_fit_cell_averages(nef, params, x, q, group, target, p, a, window, steps, 
         return nef.eval_cell_loss(params, xb, cur["p"], cur["a"], cur["window"], target, G, **okw)[0]
 
     return _lm_loop(nef, xb.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate)
+
+
+@torch.no_grad()
+def lm_fit_linear_observations(nef, params, x, op, target, p, a, window, steps, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0,
+                               components=("p", "a"), obs_weight=None, obs_channel_weight=None):
+    """Levenberg-Marquardt fit of the latents of B signals to LINEAR OBSERVATIONS obs = A out of a sparse operator ``op``
+    (fitting/operators.py: SparseObservations; include/enf_hip.h, "Sparse linear observations"), shared by the signals: ``target``
+    (B, M, O), M = op.M.  ``x``: the operator's query points, (N, dx) shared by the signals or (B, N, dx), a stride-0 batch included,
+    N = op.N; ``obs_weight``: None or (B, M), ``obs_channel_weight``: None or (B, M, O), one weight per observed value (both:
+    ValueError) -- what has weight 0 does not exist.  An observation is linear in the decode, so the Gauss-Newton matrix is exact up
+    to the residual's curvature.
+    lm_fit_latents' loop on the operator calls.  Per step: one ``nef.mse_value_and_operator_grads(return_errors=True, grad_scale=B)``;
+    ``cg_iters`` products ``nef.gn_operator_product`` at that point (the latent prologue reused) inside ``cg_solve``; one
+    ``nef.eval_operator_loss`` at the trial point; per-signal acceptance and damping by torch.where, no host synchronisation in the loop.
+    The other arguments and the return values are lm_fit_latents'."""
+    B = p.shape[0]
+    if x.dim() not in (2, 3):
+        raise ValueError(f"x must be (N, dx) or (B, N, dx), got {tuple(x.shape)}")
+    xb = x[None].expand(B, -1, -1) if x.dim() == 2 else x
+    if xb.shape[0] != B:
+        raise ValueError(f"x holds {xb.shape[0]} signals, the latents {B}")
+    if xb.shape[1] != op.N:
+        raise ValueError(f"x holds {xb.shape[1]} query points, the operator has {op.N} columns")
+    if target.dim() != 3 or target.shape[0] != B or target.shape[1] != op.M:
+        raise ValueError(f"target has shape {tuple(target.shape)}, expected ({B}, {op.M}, O)")
+    okw = dict(obs_weight=obs_weight, obs_channel_weight=obs_channel_weight)
+
+    def step(cur):
+        res = nef.mse_value_and_operator_grads(params, xb, cur["p"], cur["a"], cur["window"], target, op, grad_scale=float(B),
+                                               return_errors=True, **okw)
+        return res[1:4], res[5]
+
+    def product(cur, v, tag):
+        return nef.gn_operator_product(params, xb, cur["p"], cur["a"], cur["window"], op, vp=v.get("p"), va=v.get("a"),
+                                       vwindow=v.get("window"), grad_scale=float(B), reuse=tag, **okw)
+
+    def evaluate(cur):
+        return nef.eval_operator_loss(params, xb, cur["p"], cur["a"], cur["window"], target, op, **okw)[0]
+
+    return _lm_loop(nef, xb.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate, op=op)

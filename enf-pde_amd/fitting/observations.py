@@ -290,10 +290,11 @@ class Cells(_Observed):
 class LinearObservations(_Observed):
     """Linear functionals of the field given by a sparse operator (fitting/operators.py: SparseObservations) on the query points ``x``
     (N, dx): observation m owns the entries of row m, of any number, shared or not.  It answers what fit_linear_observations asks -- the
-    step and the final loss -- and nothing else yet: ``observed`` and the trainers' steps refuse it, there is no sampling of rows."""
+    step and the final loss -- and nothing else yet: ``observed`` and the trainers' steps refuse it, there is no sampling of rows.  (The
+    Levenberg-Marquardt fit, gauss_newton.lm_fit_linear_observations, takes x and the operator themselves.)"""
     STEP, WEIGHT_KW = "mse_value_and_operator_grads", ("obs_weight", "obs_channel_weight")
-    REFUSAL = ("a linear observation operator is served by fitting.fit_linear_observations only: the trainers' steps, inner_loop sampling and "
-               "the Gauss-Newton fits do not take it yet")
+    REFUSAL = ("a linear observation operator is served by fitting.fit_linear_observations and fitting.lm_fit_linear_observations only: "
+               "the trainers' steps and inner_loop sampling do not take it yet")
 
     def __init__(self, x, op):
         if x.dim() != 2 or x.shape[0] != op.N:

@@ -928,6 +928,31 @@ int enf_eval_loss_a(const EnfDesc* d, const float* x, int64_t x_bstride, const f
                     const float* cweight /* (B,M,O) or NULL */, float* loss /* scalar, accumulated, or NULL */,
                     float* err_a /* (B,M) or NULL */, float* loss_b /* (B) or NULL */, void* workspace, size_t workspace_bytes,
                     unsigned flags, void* stream);
+/* Gauss-Newton product on sparse observations (enf_gn_product_a): enf_gn_product for a fit against an operator, in the notation above,
+ *     gv = grad_scale * 2 / (B M O) * J^T A^T W A J v,        J = d out / d (p, a, sigma),  v = (vp, va, vsigma),  gv = (gp, ga, gsigma)
+ * W = oweight (B, M), cweight (B, M, O) or 1 under the zero-weight select, per observation or per value: what has weight 0 does not
+ * exist.  The scale and sign are those of enf_fit_step_a's gradient, so with that step's grad_scale gv is the Gauss-Newton Hessian of
+ * its loss applied to v -- exact up to the residual's curvature, an observation being linear in the decode.
+ * An operator couples rows across tiles and waves, so the Gauss-Newton tail is cut open as the fit step's is.  Sequence: latent
+ * prologue (skipped under ENF_GN_REUSE_POINT, with the z-fold backward's matrices); the prologue tangent; the tangent pair kernel, which
+ * leaves lse; the tangent tail in its stash form -- tan (B, N, O) and the tail's activation stash, no out; the forward product with the
+ * weights in the same pass, r = (w > 0 ? w (A tan) : 0) (B, M, O); the transposed product d out = grad_scale 2/(B M O) A^T r, every
+ * element written (a query row in no observation gets 0.0f); the tail's backward on the stash (the kernel of enf_fit_step_a); the
+ * backward pair kernel; the prologue backward.  The two products keep "Sparse linear observations"' summation order and safety rules
+ * and are functions of their inputs in every mode; ENF_BWD_DETERMINISTIC selects the backward pair kernel's fixed-order route as in
+ * enf_gn_product.  ENF_GN_REUSE_POINT: as there, the last call on this workspace being enf_fit_step_a (same deterministic bit) or an
+ * earlier enf_gn_product_a at the same (d, x, p, a, sigma, packed).
+ * `workspace`: ONE buffer of enf_gn_a_workspace_bytes(d, M, flags) bytes -- enf_gn_workspace_bytes' regions followed by tan, r and
+ * d out, and never less than enf_obs_workspace_bytes(d, M, ENF_FIT_DETERMINISTIC): the fit step, the products and the evaluation of a
+ * Levenberg-Marquardt step run on one buffer.  The size query returns 0 for a bad or unserved descriptor, M < 1 or an unknown flag bit.
+ * Served: what enf_gn_product serves.  Errors in this order: the descriptor's; ENF_EUNSUPPORTED as enf_gn_product gives it; ENF_EINVAL
+ * for what enf_gn_product refuses, a NULL op, M < 1, nnz < 0, a missing CSR or CSC array (the product reads both), both weight kinds;
+ * then ENF_EWORKSPACE. */
+size_t enf_gn_a_workspace_bytes(const EnfDesc* d, int32_t M, unsigned flags);
+int enf_gn_product_a(const EnfDesc* d, const float* x, int64_t x_bstride, const float* p, const float* a, const float* sigma,
+                     const float* vp, const float* va, const float* vsigma, const void* packed, const EnfSparseObs* op,
+                     const float* oweight /* (B,M) or NULL */, const float* cweight /* (B,M,O) or NULL */, float grad_scale,
+                     float* gp, float* ga, float* gsigma, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Latent ODE (experiments/fitting/ode_models/ponita_ode_g.py): the separable group convolution of a ConvBlock,
