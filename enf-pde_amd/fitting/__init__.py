@@ -14,7 +14,9 @@
   cell_quadrature, decode_cell_averages, fit_cell_averages  (no counterpart)   fits against cell averages: quadrature groups in the fused tail
   inner_loop_cells, gather_cell_samples, cell_mse_torch  (no counterpart)   the inner loop on sampled cells (the trainers' cells=) and the torch-op mirrors of its kernels
   SparseObservations, cell_operator, line_integrals, decode_observations, fit_linear_observations  (no counterpart)   fits against any sparse linear observation operator (CSR): 9- / 27-point and closed cell rules, ragged or overlapping rows, line integrals
-  observations: Points, Cells, observed  (no counterpart)      what a fit observes -- point values or cell averages -- and the one parser of weights= / channel_weights= / cells= / cell_channel_weights=
+  Points (inner_loop), Cells (cells), LinearObservations (operators)  (no counterpart)   what a fit observes: one value per kind, beside its helpers; every meta-SGD fit runs inner_loop._fit_body on one, every Levenberg-Marquardt fit gauss_newton._lm_loop
+  observations: observed  (no counterpart)                     the one parser of weights= / channel_weights= / cells= / cell_channel_weights=
+  (imports go one way: weights <- inner_loop <- cells <- operators <- observations <- gauss_newton, trainers)
   shard_signals / allreduce_mean_  SURVEY.md 8e               meta-batch data parallelism over RCCL
   MetaSGDPDETrainer    trainers/pde_trainer.py:60-67,237-500   outer steps: nef (meta-gradient), ode, dual; val_step
   ode_models           ode_models/ponita_ode_g.py, mlp_ode.py  PonitaODEGen (fused SepGconv HIP kernels), MLPODE

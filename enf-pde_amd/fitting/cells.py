@@ -6,34 +6,35 @@ footprint's weighted mean.  Such an observation is a fixed linear functional of 
 a quadrature rule over G points of cell m.  ``cell_quadrature`` builds the points and factors, ``decode_cell_averages`` applies the
 functional to a decode in torch ops, and ``fit_cell_averages`` runs the inner loop's update rule on the fused grouped step
 (nef.mse_value_and_cell_grads: the group sums are formed in the tail's registers, no decode exists in memory).
-``inner_loop_cells`` is inner_loop on sampled cells -- the same loop (inner_loop.py: _fit_loop) given a ``Cells`` value
-(fitting/observations.py): one gather launch (enf_fit_inputs_g), the shared-latent hint at step 0 -- and what the trainers run with
-``cells=``; ``fit_cell_averages`` keeps its own sampling and takes the step body from that loop (_sgd_step).  ``gather_cell_samples`` and
-``cell_mse_torch`` are the torch-op mirrors of the gather kernel and of the unfused grouped loss (nef.cell_mse)."""
+``Cells`` is the observation value of this kind (inner_loop.py: _Observed).  ``inner_loop_cells`` is inner_loop on sampled cells -- the
+same loop (inner_loop.py: _fit_loop) given a ``Cells`` value: one gather launch (enf_fit_inputs_g), the shared-latent hint at step 0 --
+and what the trainers run with ``cells=``; ``fit_cell_averages`` chooses its inputs itself (all cells, or samples it gathers in torch
+ops) and runs the same body on them (inner_loop.py: _fit_given).  ``check_cells`` and ``check_obs_weights`` are the one copy of the
+argument checks.  ``gather_cell_samples`` and ``cell_mse_torch`` are the torch-op mirrors of the gather kernel and of the unfused
+grouped loss (nef.cell_mse)."""
 import numpy as np
 import torch
 
 from .. import _lib
-from .inner_loop import _fit_loop, _pose, _sgd_step, _shared_kw      # (_shared_kw: re-exported)
+from .inner_loop import _Observed, _batched, _fit_given, _fit_loop, _fresh, _gather_frames, _pose, make_signal_masks, split_latent_grads
+from .inner_loop import _shared_kw      # noqa: F401  (tests/test_gpu_cells_train.py asks this module for the hint of the grouped step)
+from .weights import LossWeights
 
 GROUP_SIZES = (1, 2, 4, 8, 16)
 
 
-def check_cells(cells, num_cells):
-    """What every step takes as ``cells=``: (x (M G, dx), q (M G,) or None, group) with group a size the fused tail serves and
-    M = ``num_cells``, the cells the data hold.  Returns (x, q, int(group)); ValueError otherwise."""
-    if int(cells[2]) not in GROUP_SIZES:
+def check_cells(cells, num_cells, x_wrong=None, q_wrong=None):
+    """The one check of cells shared by the signals: (x (M G, dx), q (M G,) or None, group) with group a size the fused tail serves and
+    M = ``num_cells``, the cells the data hold.  Returns (x, q, int(group)); ValueError otherwise, group first, then x, then q.
+    ``x_wrong(x)`` / ``q_wrong(q)``: the words of a caller that names its arguments otherwise than ``cells=`` does."""
+    x, q, G = cells[0], cells[1], int(cells[2])
+    if G not in GROUP_SIZES:
         raise ValueError(f"group must be one of {GROUP_SIZES}, got {cells[2]}")
-    if cells[0].dim() != 2 or cells[0].shape[0] != num_cells * int(cells[2]):
-        raise ValueError(f"cells hold {tuple(cells[0].shape)} quadrature points, img {num_cells} cells of {int(cells[2])}")
-    if cells[1] is not None and tuple(cells[1].shape) != (cells[0].shape[0],):
-        raise ValueError(f"cells hold {cells[0].shape[0]} quadrature points and factors of shape {tuple(cells[1].shape)}")
-    return cells[0], cells[1], int(cells[2])
-
-
-def cell_weight_kw(ws, channel):
-    """The keyword nef.mse_value_and_cell_grads, nef.eval_cell_loss, nef.cell_mse and nef.cell_fit_loss take sampled weights by."""
-    return {} if ws is None else {"obs_channel_weight" if channel else "obs_weight": ws}
+    if x.dim() != 2 or x.shape[0] != num_cells * G:
+        raise ValueError(x_wrong(x) if x_wrong else f"cells hold {tuple(x.shape)} quadrature points, img {num_cells} cells of {G}")
+    if q is not None and tuple(q.shape) != (x.shape[0],):
+        raise ValueError(q_wrong(q) if q_wrong else f"cells hold {x.shape[0]} quadrature points and factors of shape {tuple(q.shape)}")
+    return x, q, G
 
 
 def _rule_1d(k, rule):
@@ -106,13 +107,6 @@ def cell_quadrature(cells, k, rule="gauss", kind="cartesian", dtype=torch.float3
     return (torch.tensor(x.reshape(M * G, dx), dtype=dtype, device=device), torch.tensor(q.reshape(M * G), dtype=dtype, device=device))
 
 
-def _batched(x, q, B):
-    """x (N, dx) or (B, N, dx) -> a batch (stride 0 where shared); q None, (N,) or (B, N) -> None or (B, N)."""
-    xb = x[None].expand(B, -1, -1) if x.dim() == 2 else x
-    qb = None if q is None else (q[None].expand(B, -1) if q.dim() == 1 else q)
-    return xb, qb
-
-
 @torch.no_grad()
 def decode_cell_averages(nef, params, x, q, group, p, a, window):
     """obs (B, M, O) = sum_k q[m G + k] out[b, m G + k] of a decode at the quadrature points: the decode (nef.apply) and the group sum
@@ -146,6 +140,16 @@ def _one_weight_kind(what, obs_weight, obs_channel_weight, shape):
         raise ValueError(f"obs_channel_weight has shape {tuple(obs_channel_weight.shape)}, expected {tuple(shape)}")
 
 
+def check_obs_weights(what, obs_weight, obs_channel_weight, shape, named="obs_weight has"):
+    """The one check of a fit's weights on observations of any kind, ``shape`` = (B, M, O): per observation (B, M), or per value
+    (B, M, O), not both.  Returns (the weights to fit with or None, whether they are per value).  ``named``: the caller's own argument."""
+    if obs_weight is not None and tuple(obs_weight.shape) != tuple(shape[:2]):
+        raise ValueError(f"{named} shape {tuple(obs_weight.shape)}, expected {tuple(shape[:2])}")
+    _one_weight_kind(what, obs_weight, obs_channel_weight, shape)
+    per_value = obs_channel_weight is not None
+    return (obs_channel_weight if per_value else obs_weight), per_value
+
+
 def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, obs_weight=None, sample=None, generator=None,
                       optimize_gaussian_window=False, per_signal_loss=False, obs_channel_weight=None):
     """Fit per-signal latents to cell averages with `steps` steps of the inner loop's meta-SGD rule (inner_loop: meta_sgd_update on the
@@ -164,26 +168,16 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
     Returns (loss on the last set, fitted latents dict with leading dimension B), with ``per_signal_loss`` followed by loss_b
     (steps + 1, B) -- what inner_loop returns."""
     G, S = int(group), int(steps)
-    if G not in GROUP_SIZES:
-        raise ValueError(f"group must be one of {GROUP_SIZES}, got {group}")
-    if x.dim() != 2 or x.shape[0] % G:
-        raise ValueError(f"x must be (M * group, dx), got {tuple(x.shape)} with group = {G}")
     B, M, O = targets.shape
-    if x.shape[0] != M * G:
-        raise ValueError(f"x holds {x.shape[0] // G} cells, targets {M}")
-    if q is not None and tuple(q.shape) != (M * G,):
-        raise ValueError(f"q has shape {tuple(q.shape)}, expected {(M * G,)}")
-    if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
-        raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
-    _one_weight_kind("fit_cell_averages", obs_weight, obs_channel_weight, (B, M, O))
-    from .observations import Cells                  # (observations imports this module)
-    obs, per_value = Cells(x, q, G, M), obs_channel_weight is not None
-    if per_value:
-        obs_weight = obs_channel_weight
+    check_cells((x, q, group), M, q_wrong=lambda q: f"q has shape {tuple(q.shape)}, expected {(M * G,)}",
+                x_wrong=lambda x: (f"x must be (M * group, dx), got {tuple(x.shape)} with group = {G}" if x.dim() != 2 or x.shape[0] % G else
+                                   f"x holds {x.shape[0] // G} cells, targets {M}"))
+    w, per_value = check_obs_weights("fit_cell_averages", obs_weight, obs_channel_weight, (B, M, O))
     dev = targets.device
     tg = targets.float()
-    if sample is None:
-        pick = lambda s: (x, q, tg, obs_weight)
+    if sample is None:                                                   # the caller's tensors themselves, a stride-0 batch: no gather
+        given = (*_batched(x.to(dev), None if q is None else q.to(dev), B), tg, w)
+        inputs = lambda s: given
     else:
         idx = sample if torch.is_tensor(sample) else draw_cell_samples(M, sample, S, generator)
         if idx.dim() != 2 or idx.shape[0] != S + 1:
@@ -193,22 +187,9 @@ def fit_cell_averages(nef, params, latents0, lrs, x, q, group, targets, steps, o
         xs_all = x.to(dev)[rows]                                                            # (S + 1, M_s G, dx)
         qs_all = q.to(dev)[rows] if q is not None else None
         ys_all = tg[:, idx].transpose(0, 1).contiguous()                                    # (S + 1, B, M_s, O)
-        ws_all = obs_weight.to(dev)[:, idx].transpose(0, 1).contiguous() if obs_weight is not None else None
-        pick = lambda s: (xs_all[s], None if qs_all is None else qs_all[s], ys_all[s], None if ws_all is None else ws_all[s])
-    lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
-    losses = torch.zeros(S + 1, device=dev, dtype=torch.float32)
-    rows_b = [] if per_signal_loss else None
-    for s in range(S + 1):                                               # S steps, then the loss on the last set
-        xs, qs, ys, ws = pick(s)
-        xb, qb = _batched(xs.to(dev), None if qs is None else qs.to(dev), B)
-        if s < S:
-            lat = _sgd_step(nef, params, obs, lat, lrs, xb, qb, ys, ws, per_value, optimize_gaussian_window, rows_b,
-                            loss_out=losses[s:s + 1], return_errors=per_signal_loss)
-    lb = obs.final_loss(nef, params, xb, qb, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"), ys, ws,
-                        per_value, losses[S:], per_signal_loss)
-    if per_signal_loss:
-        return losses[S], lat, torch.stack(rows_b + [lb])
-    return losses[S], lat
+        ws_all = w.to(dev)[:, idx].transpose(0, 1).contiguous() if w is not None else None
+        inputs = lambda s: (*_batched(xs_all[s], None if qs_all is None else qs_all[s], B), ys_all[s], None if ws_all is None else ws_all[s])
+    return _fit_given(nef, params, Cells.given(rows=G), latents0, lrs, inputs, B, S, dev, per_value, optimize_gaussian_window, per_signal_loss)
 
 
 def gather_cell_samples(x, q, group, obs, masks, obs_weight=None, obs_channel_weight=None):
@@ -299,6 +280,137 @@ def _cell_inputs(latents0, x, q, group, obs, masks, obs_weight, per_value=False)
     return lat, xs, qs, ys, losses, ws
 
 
+class Cells(_Observed):
+    """Averages of the field over ``num`` cells: quadrature points ``x`` (num * group, dx) and factors ``q`` (num * group,) or None for
+    the plain mean, ``rows`` = group query rows per observation.  The constructor is where ``cells=`` is validated (check_cells).
+    Where it differs from points: the loop's final loss is always nef.eval_cell_loss, never a decode; the shared-latent hint of step 0
+    is given only without per-value weights; meta_gradients' forward sweep runs the grouped fit step instead of autograd."""
+    WEIGHT_KW = ("obs_weight", "obs_channel_weight")
+    STEP, EVAL, PRODUCT = "mse_value_and_cell_grads", "eval_cell_loss", "gn_cell_product"
+
+    def __init__(self, x, q, group, num):
+        self.x, self.q, self.rows = check_cells((x, q, group), num)
+        self.num = num
+
+    def _call(self, nef, name, params, xs, qs, p, a, window, *ys, **kw):
+        return getattr(nef, name)(params, xs, p, a, window, *ys, self.rows, qweight=qs, **kw)
+
+    def num_sampled(self, max_points):
+        return max(1, max_points // self.rows)
+
+    def hints(self, channel):
+        return not channel
+
+    def step_kw(self, lw):
+        return {"cells": (self.x, self.q, self.rows), **({} if lw is None else {"cell_channel_weights" if lw.channel else "weights": lw.w})}
+
+    def loop_args(self, img, masks, lw, decode_free=False):
+        """What inner_loop_cells takes after the learning rates, and by keyword (its last loss never decodes)."""
+        return (self.x, self.q, self.rows, img, masks), {} if lw is None else {"obs_channel_weight" if lw.channel else "obs_weights": lw.w}
+
+    def gather(self, latents0, img, masks, w, channel, fused_launch):
+        """One launch (enf_fit_inputs_g / _gc), or gather_cell_samples where the tensors are not what the kernel takes or without
+        ``fused_launch``, the loop's reading of inner_loop.FUSED_FIT_INPUTS: one switch for points and cells."""
+        fused = _cell_inputs(latents0, self.x, self.q, self.rows, img, masks, w, channel) if fused_launch else None
+        if fused is not None:
+            return fused
+        dev = img.device
+        lat, losses = _fresh(latents0, img.shape[0], masks.shape[-1], dev)
+        xs_all, qs_all, ys_all, ws_all = gather_cell_samples(self.x.to(dev), None if self.q is None else self.q.to(dev), self.rows, img,
+                                                             masks.to(dev), **self._weight_kw(w, channel, True))
+        return lat, xs_all, qs_all, ys_all, losses, ws_all
+
+    def step_inputs(self, xs_all, qs_all, ws_all, s, B, per_signal):
+        xs, qs = xs_all[s], None if qs_all is None else qs_all[s]
+        if not per_signal:
+            xs, qs = _batched(xs, qs, B)
+        return xs, qs, None if ws_all is None else ws_all[s]
+
+    def sampled(self, img, masks, s, weights, copies=1):
+        """The cells of step ``s`` (masks hold CELL indices): (xs (copies * B, Ms G, dx), qs (B, Ms G) or None, ys (B, Ms, O), ws (B, Ms)
+        or None) -- gather_cell_samples on column s, shared masks as a stride-0 batch; per-signal masks give every signal its own cells
+        and always weights (0 where the sampler padded with -1).  Per-value ``weights`` (B, M, O) come back as (B, Ms, O)."""
+        B = img.shape[0]
+        xs, qs, ys, ws = gather_cell_samples(self.x, self.q, self.rows, img, masks[..., s:s + 1],
+                                             **self._weight_kw(weights, weights is not None and weights.dim() == 3))
+        xs, qs = xs[0], None if qs is None else qs[0]
+        if masks.dim() == 2:
+            xs, qs = _batched(xs, qs, B)
+            xs = xs if copies == 1 else xs[:1].expand(copies * B, -1, -1)
+        elif copies > 1:
+            xs = xs.repeat(copies, 1, 1)
+        return xs, qs, ys[0].to(img.dtype), None if ws is None else ws[0]
+
+    def eval(self, nef, params, part, n, p, a, window, ys, ws, channel):
+        """(loss_b or None, err_g (n, |part|)) of ``n`` signals on the cells ``part``, without a decode (nef.eval_cell_loss)."""
+        rows = slice(part.start * self.rows, part.stop * self.rows)
+        xs, qs = _batched(self.x[rows], None if self.q is None else self.q[rows], n)
+        return nef.eval_cell_loss(params, xs, p, a, window, ys, self.rows, qweight=qs, per_signal=False, **self._weight_kw(ws, channel))
+
+    def loss_of_decode(self, nef, out, ys, qs, ws, mse=None):
+        """The grouped loss of a decode at the cells' quadrature rows (nef.cell_mse: one kernel).  Sampled weights (B, Ms) are per
+        observation, (B, Ms, O) per value: on cells the two kinds differ by rank."""
+        return nef.cell_mse(out, ys, self.rows, qs, **self._weight_kw(ws, ws is not None and ws.dim() == 3))
+
+    def fused_loss(self, nef, params, xs, qs, p, a, window, ys, ws):
+        """The same loss without a decode (nef.cell_fit_loss: one grouped fit step whose latent gradients the backward scales)."""
+        return nef.cell_fit_loss(params, xs, p, a, window, ys, self.rows, qweight=qs, **self._weight_kw(ws, ws is not None and ws.dim() == 3))
+
+    def latent_grads(self, nef, params, img, masks, s, lat, keys, weights, mse=None):
+        """d loss_s / d lat[keys] of meta_gradients' forward sweep: ONE grouped fit step (no decode, no autograd graph), whose forward
+        pair kernel records the relu masks when the caller has set them to "write"."""
+        xs, qs, ys, ws = self.sampled(img, masks, s, weights)
+        _, dp, da, dsig = self.fit_step(nef, params, xs, qs, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"],
+                                        lat.get("gaussian_window"), ys, ws, ws is not None and ws.dim() == 3)
+        g = split_latent_grads(dp, da, dsig, lat["p_pos"].shape[-1])
+        return {k: (torch.zeros_like(lat[k]) if g.get(k) is None else g[k].reshape(lat[k].shape)) for k in keys}
+
+    def subset(self, img, mask, lw, max_points, rng, per_signal):
+        """Points.subset on cell means ``img`` (B, M, O), ``mask`` and ``lw`` per observation: (targets (B, m, O), xs (B, m G, dx), qs
+        (B, m G) or None, the LossWeights of these cells or None) -- at most num_sampled(max_points) cells, one subset for the batch (a
+        stride-0 xs) or, with ``per_signal`` and weights, every signal's own observed cells with the weights rescaled for that draw.
+        With weights per observed value a cell is observed where any of its values is."""
+        x, q, G = self.x, self.q, self.rows
+        B, M, O = img.shape
+        pick = None
+        if mask is not None:
+            pick = torch.as_tensor(mask, device=img.device)
+            pick = pick.nonzero().reshape(-1) if pick.dtype == torch.bool else pick.long()
+        n = self.num_sampled(max_points)
+        if per_signal and lw is not None:
+            if pick is not None:
+                keep = torch.zeros(M, dtype=torch.bool, device=img.device)
+                keep[pick] = True
+                lw = lw.keep(keep[None].expand(B, -1))
+            m = make_signal_masks(lw.support(), min(n, M), 0, generator=rng, device=img.device)
+            xs, qs, ys, ws = gather_cell_samples(x, q, G, img, m, **self._weight_kw(lw.drawn_on(m).w, lw.channel))
+            return ys[0].to(img.dtype), xs[0], None if qs is None else qs[0], LossWeights(ws[0], lw.channel)
+        if pick is None and n < M:
+            pick = torch.arange(M, device=img.device)
+        if pick is not None and n < pick.numel():
+            pick = pick[torch.randperm(pick.numel(), generator=rng)[:n].to(pick.device)]
+        if pick is not None:
+            rows = (pick[:, None] * G + torch.arange(G, device=pick.device)).reshape(-1)
+            img, x, q, lw = img[:, pick], x[rows], None if q is None else q[rows], lw and lw.points(pick)
+        return img, *_batched(x, q, B), lw
+
+    def sample_frames(self, traj, cell_masks=None, weights=None):
+        """sample_frames on cell averages: ``traj`` (B, T, M, O) cell means, ``cell_masks`` (T, m_s) long CELL indices or None for all M.
+        Returns xs (B T, m G, dx), qs (B T, m G) or None, ys (B T, m, O) and ws -- None, (B T, m) from ``weights`` (B, T, M), or
+        (B T, m, O) from per-value weights (B, T, M, O); row i G + k of a frame's set is row c G + k of its cell c, signal-major like
+        the flattened roll-out."""
+        x, q, G = self.x, self.q, self.rows
+        B, T, M, O = traj.shape
+        if cell_masks is None:
+            xs, qs = _batched(x, q, B * T)
+            return xs, qs, traj.reshape(B * T, M, O), None if weights is None else weights.reshape(B * T, M, *weights.shape[3:])
+        m_s = cell_masks.shape[1]
+        rows = (cell_masks[..., None] * G + torch.arange(G, device=cell_masks.device)).reshape(T, m_s * G)
+        xs = x[rows][None].expand(B, -1, -1, -1).reshape(B * T, m_s * G, -1)
+        qs = None if q is None else q[rows][None].expand(B, -1, -1).reshape(B * T, m_s * G)
+        return xs, qs, *_gather_frames(traj, cell_masks, weights)
+
+
 def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks, obs_weights=None, optimize_gaussian_window=False,
                      noise_pos=0.0, generator=None, normalize_weights=False, per_signal_loss=False, obs_channel_weight=None):
     """inner_loop on cell averages: fit per-signal latents with S steps of meta-SGD, every step against a sampled set of cells.
@@ -316,21 +428,12 @@ def inner_loop_cells(nef, nef_params, latents0, lrs, x, q, group, targets, masks
                enf_fit_inputs_gc, every step enf_fit_step_gc and runs unshared (no shared-latent hint at step 0)
     normalize_weights, noise_pos, optimize_gaussian_window, per_signal_loss and the return values are inner_loop's."""
     G = int(group)
-    if G not in GROUP_SIZES:
-        raise ValueError(f"group must be one of {GROUP_SIZES}, got {group}")
     B, M, O = targets.shape
-    if x.dim() != 2 or x.shape[0] != M * G:
-        raise ValueError(f"x must be (M * group, dx) = ({M * G}, dx), got {tuple(x.shape)}")
-    if q is not None and tuple(q.shape) != (M * G,):
-        raise ValueError(f"q has shape {tuple(q.shape)}, expected {(M * G,)}")
-    if obs_weights is not None and tuple(obs_weights.shape) != (B, M):
-        raise ValueError(f"obs_weights have shape {tuple(obs_weights.shape)}, expected {(B, M)}")
-    _one_weight_kind("inner_loop_cells", obs_weights, obs_channel_weight, (B, M, O))
-    from .observations import Cells                  # (observations imports this module)
+    check_cells((x, q, group), M, x_wrong=lambda x: f"x must be (M * group, dx) = ({M * G}, dx), got {tuple(x.shape)}",
+                q_wrong=lambda q: f"q has shape {tuple(q.shape)}, expected {(M * G,)}")
+    w, per_value = check_obs_weights("inner_loop_cells", obs_weights, obs_channel_weight, (B, M, O), named="obs_weights have")
     if masks.dim() not in (2, 3) or (masks.dim() == 3 and masks.shape[0] != B):
         raise ValueError(f"masks have shape {tuple(masks.shape)}, expected (Ms, S + 1) or ({B}, Ms, S + 1)")
-    per_value = obs_channel_weight is not None
-    w = obs_channel_weight if per_value else obs_weights
     w = w.to(device=targets.device, dtype=torch.float32).contiguous() if w is not None else None
-    return _fit_loop(nef, nef_params, Cells(x, q, G, M), latents0, lrs, targets, masks, w, per_value, optimize_gaussian_window, noise_pos,
-                     generator, normalize_weights, per_signal_loss)
+    return _fit_loop(nef, nef_params, Cells.given(x=x, q=q, rows=G, num=M), latents0, lrs, targets, masks, w, per_value,
+                     optimize_gaussian_window, noise_pos, generator, normalize_weights, per_signal_loss)

@@ -12,11 +12,15 @@ Levenberg-Marquardt loop on top of it.
 
 The loss is a sum over signals and the latents of different signals do not interact, so the Gauss-Newton matrix is block diagonal:
 every quantity below (damping, step length, acceptance) is per signal, and nothing in a loop iteration reads a value back to the host.
+The three fits are one loop, ``_lm_loop``, on the calls half of an observation kind (inner_loop.py: _Observed); the public functions
+only check and batch their arguments and name the kind.
 """
 import torch
 
 from .. import _lib
-from .cells import _batched
+from .inner_loop import Points, _batched
+from .cells import Cells
+from .operators import LinearObservations, check_operator
 
 __all__ = ["cg_solve", "lm_fit_latents", "lm_fit_cell_averages", "lm_fit_linear_observations"]
 
@@ -67,14 +71,14 @@ def cg_solve(matvec, rhs, lam, iters):
 _COMPONENTS = ("p", "a", "window")
 
 
-def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate, op=None):
-    """The one copy of the Levenberg-Marquardt loop.  The front ends bind their observation model into three callables on the
-    current latents ``cur`` = {"p", "a", "window"}:
-      step(cur)             -> ((dp, da, dwindow or None), loss_b (B,)): the fit step at gradient scale B with its per-signal losses
-      product(cur, v, tag)  -> (gp, ga, gwindow or None): the Gauss-Newton product at the same scale along v = {component: tensor},
-                               ``tag`` the workspace tag behind the last call at this point
-      evaluate(cur)         -> loss_b (B,) at a trial point
-    ``op``: the operator of a fit against one -- the buffer is then reserved for its product (gn_reserve(..., op=op)).
+def _lm_loop(nef, params, obs, xs, qs, target, wkw, p, a, window, steps, cg_iters, damping, down, up, components):
+    """The one copy of the Levenberg-Marquardt loop, on any kind of observation ``obs`` (inner_loop.py: _Observed; its calls half is
+    all the loop needs): the batched query rows ``xs`` (B, N, dx) with the kind's factors ``qs`` or None, ``target`` and the weight
+    keywords ``wkw`` (obs.weights_kw) go to three calls at the current latents ``cur`` = {"p", "a", "window"}:
+      obs.fit_step    at gradient scale B with return_errors: the gradient and the per-signal losses
+      obs.gn_product  at the same scale along v = {component: tensor}, with ``reuse`` the workspace tag behind the last call there
+      obs.loss_b      the per-signal losses at a trial point
+    The buffer is reserved first, with what the kind's product needs beside the sizes (obs.reserve_kw: the operator).
     Returns what lm_fit_latents documents."""
     comps = tuple(components)
     if not comps or any(c not in _COMPONENTS for c in comps) or len(set(comps)) != len(comps):
@@ -86,19 +90,21 @@ def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, component
     dev = p.device
     cur = {"p": p.detach().float().contiguous(), "a": a.detach().float().contiguous(),
            "window": None if window is None else window.detach().float().reshape(B, Z, 1).contiguous()}
+    at = lambda lat: (nef, params, xs, qs, lat["p"], lat["a"], lat["window"])
     lam = torch.full((B,), float(damping), device=dev, dtype=torch.float32)
     loss_b = torch.empty((int(steps) + 1, B), device=dev, dtype=torch.float32)
     accepted = torch.zeros((int(steps), B), device=dev, dtype=torch.bool)
-    nef.gn_reserve(B, N, Z, dev, **({} if op is None else {"op": op}))      # the fit step below must already run on the buffer the products reuse
+    nef.gn_reserve(B, xs.shape[1], Z, dev, **obs.reserve_kw())      # the fit step below must already run on the buffer the products reuse
     last = None
     for k in range(int(steps)):
-        g, lb = step(cur)
-        grads = dict(zip(_COMPONENTS, g))
+        res = obs.fit_step(*at(cur), target, None, False, grad_scale=float(B), return_errors=True, **wkw)
+        grads, lb = dict(zip(_COMPONENTS, res[1:4])), res[5]
         loss_b[k] = lb
         tag = [nef.workspace_tag(dev)]
 
         def matvec(d, tag=tag):
-            out = product(cur, dict(zip(comps, d)), tag[0])
+            v = dict(zip(comps, d))
+            out = obs.gn_product(*at(cur), vp=v.get("p"), va=v.get("a"), vwindow=v.get("window"), grad_scale=float(B), reuse=tag[0], **wkw)
             tag[0] = nef.workspace_tag(dev)
             g = dict(zip(_COMPONENTS, out))
             return tuple(g[c] for c in comps)
@@ -107,7 +113,7 @@ def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, component
         trial = dict(cur)
         for c, dlt in zip(comps, delta):
             trial[c] = cur[c] + dlt
-        lb_t = evaluate(trial)
+        lb_t = obs.loss_b(*at(trial), target, **wkw)
         acc = lb_t < lb                      # (a NaN trial loss is a rejection)
         for c in comps:
             cur[c] = torch.where(acc[:, None, None], trial[c], cur[c])
@@ -115,7 +121,7 @@ def _lm_loop(nef, N, p, a, window, steps, cg_iters, damping, down, up, component
         accepted[k] = acc
         last = torch.where(acc, lb_t, lb)
     if last is None:
-        last = evaluate(cur)
+        last = obs.loss_b(*at(cur), target, **wkw)
     loss_b[int(steps)] = last
     return (cur["p"], cur["a"], cur["window"]), loss_b, lam, accepted
 
@@ -133,22 +139,9 @@ def lm_fit_latents(nef, params, x, target, p, a, window, steps, cg_iters=8, damp
     ``weight`` / ``channel_weight``: the loss weights of the fit step.
     Returns ((p, a, window), loss_b (steps + 1, B), damping (B,), accepted (steps, B) bool), all on the device; loss_b[k] is the loss
     before step k, loss_b[steps] the final one."""
-    B = p.shape[0]
-    wkw = dict(weight=weight, channel_weight=channel_weight)
-
-    def step(cur):
-        res = nef.mse_value_and_latent_grads(params, x, cur["p"], cur["a"], cur["window"], target, grad_scale=float(B), return_errors=True,
-                                             **wkw)
-        return res[1:4], res[5]
-
-    def product(cur, v, tag):
-        return nef.gn_product(params, x, cur["p"], cur["a"], cur["window"], vp=v.get("p"), va=v.get("a"), vwindow=v.get("window"),
-                              grad_scale=float(B), reuse=tag, **wkw)
-
-    def evaluate(cur):
-        return nef.eval_loss(params, x, cur["p"], cur["a"], cur["window"], target, **wkw)[0]
-
-    return _lm_loop(nef, x.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate)
+    obs = Points.given()
+    return _lm_loop(nef, params, obs, x, None, target, obs.weights_kw(weight, channel_weight), p, a, window, steps, cg_iters, damping, down,
+                    up, components)
 
 
 @torch.no_grad()
@@ -163,24 +156,9 @@ def lm_fit_cell_averages(nef, params, x, q, group, target, p, a, window, steps, 
     ``cg_iters`` products ``nef.gn_cell_product`` at that point (the latent prologue reused) inside ``cg_solve``; one
     ``nef.eval_cell_loss`` at the trial point; per-signal acceptance and damping by torch.where, no host synchronisation in the loop.
     The other arguments and the return values are lm_fit_latents'."""
-    B = p.shape[0]
-    xb, qb = _batched(x, q, B)
-    G = int(group)
-    okw = dict(qweight=qb, obs_weight=obs_weight)
-
-    def step(cur):
-        res = nef.mse_value_and_cell_grads(params, xb, cur["p"], cur["a"], cur["window"], target, G, grad_scale=float(B),
-                                           return_errors=True, **okw)
-        return res[1:4], res[5]
-
-    def product(cur, v, tag):
-        return nef.gn_cell_product(params, xb, cur["p"], cur["a"], cur["window"], G, vp=v.get("p"), va=v.get("a"),
-                                   vwindow=v.get("window"), grad_scale=float(B), reuse=tag, **okw)
-
-    def evaluate(cur):
-        return nef.eval_cell_loss(params, xb, cur["p"], cur["a"], cur["window"], target, G, **okw)[0]
-
-    return _lm_loop(nef, xb.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate)
+    obs = Cells.given(rows=int(group))
+    xb, qb = _batched(x, q, p.shape[0])
+    return _lm_loop(nef, params, obs, xb, qb, target, obs.weights_kw(obs_weight), p, a, window, steps, cg_iters, damping, down, up, components)
 
 
 @torch.no_grad()
@@ -197,27 +175,7 @@ def lm_fit_linear_observations(nef, params, x, op, target, p, a, window, steps, 
     ``nef.eval_operator_loss`` at the trial point; per-signal acceptance and damping by torch.where, no host synchronisation in the loop.
     The other arguments and the return values are lm_fit_latents'."""
     B = p.shape[0]
-    if x.dim() not in (2, 3):
-        raise ValueError(f"x must be (N, dx) or (B, N, dx), got {tuple(x.shape)}")
-    xb = x[None].expand(B, -1, -1) if x.dim() == 2 else x
-    if xb.shape[0] != B:
-        raise ValueError(f"x holds {xb.shape[0]} signals, the latents {B}")
-    if xb.shape[1] != op.N:
-        raise ValueError(f"x holds {xb.shape[1]} query points, the operator has {op.N} columns")
-    if target.dim() != 3 or target.shape[0] != B or target.shape[1] != op.M:
-        raise ValueError(f"target has shape {tuple(target.shape)}, expected ({B}, {op.M}, O)")
-    okw = dict(obs_weight=obs_weight, obs_channel_weight=obs_channel_weight)
-
-    def step(cur):
-        res = nef.mse_value_and_operator_grads(params, xb, cur["p"], cur["a"], cur["window"], target, op, grad_scale=float(B),
-                                               return_errors=True, **okw)
-        return res[1:4], res[5]
-
-    def product(cur, v, tag):
-        return nef.gn_operator_product(params, xb, cur["p"], cur["a"], cur["window"], op, vp=v.get("p"), va=v.get("a"),
-                                       vwindow=v.get("window"), grad_scale=float(B), reuse=tag, **okw)
-
-    def evaluate(cur):
-        return nef.eval_operator_loss(params, xb, cur["p"], cur["a"], cur["window"], target, op, **okw)[0]
-
-    return _lm_loop(nef, xb.shape[1], p, a, window, steps, cg_iters, damping, down, up, components, step, product, evaluate, op=op)
+    check_operator(x, op, B, target, "target has shape {shape}, expected ({B}, {M}, O)")
+    obs = LinearObservations.given(op=op)
+    return _lm_loop(nef, params, obs, _batched(x, None, B)[0], None, target, obs.weights_kw(obs_weight, obs_channel_weight), p, a, window,
+                    steps, cg_iters, damping, down, up, components)

@@ -1,15 +1,22 @@
 """MAML inner loop and decode on the HIP path (trainers/pde_trainer.py:122-235, 389-405).
 
-``inner_loop`` (point values) and fitting/cells.py: ``inner_loop_cells`` (cell averages) are one loop, ``_fit_loop``: what differs between
-the two kinds of observation -- the gather, the decoder's calls, the form of the last loss, when step 0 may share its forward -- it asks
-of the observation value it is given (fitting/observations.py)."""
+Every meta-SGD fit of the package ends in ONE body, ``_fit_body``: S times ``_sgd_step``, the loss on the last set, the return values.
+``inner_loop`` (point values) and fitting/cells.py: ``inner_loop_cells`` (cell averages) reach it through ``_fit_loop``, which gathers the
+sampled inputs of all steps once and jitters the poses; fitting/cells.py: ``fit_cell_averages`` and fitting/operators.py:
+``fit_linear_observations`` through ``_fit_given``, on inputs they choose themselves.  What differs between the kinds of observation --
+the gather, the decoder's calls, the form of the last loss, when step 0 may share its forward -- the body asks of the observation
+value it is given: ``_Observed`` is what the kinds share, ``Points`` the kind of this module (``Cells``: fitting/cells.py,
+``LinearObservations``: fitting/operators.py).  The loop and the body look up ``meta_sgd_update``, ``_shared_kw`` and
+``FUSED_FIT_INPUTS`` in this module when they run -- the switch is handed to the kind's gather -- so that one patch of any of them
+reaches every fit, on points and on cells.  This module imports no other module of the fitting layer but weights.py; cells.py,
+operators.py, observations.py (the parser ``observed``), gauss_newton.py and the trainers import it, in that order."""
 import functools
 import inspect
 
 import torch
 
 from .. import _lib
-from .weights import gather_point_weights
+from .weights import LossWeights, gather_point_weights, loop_kw
 
 
 def default_meta_sgd_lrs(latent_dim, lr_p=1.0, lr_a=5.0, lr_window=0.0, with_ori=False, device="cuda"):
@@ -152,17 +159,30 @@ def _full_grid_weights(img, weights, channel_weights):
     return weights.to(device=img.device, dtype=torch.float32).contiguous()
 
 
-def _gather_inputs(latents0, coords, img, masks, weights, channel):
+def _fresh(latents0, B, S1, dev):
+    """What every fit starts from: the signals' own copies of the latent initialisation (pde_trainer.py:157-159; fresh tensors) and one
+    zeroed loss accumulator per step and for the last loss."""
+    return {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}, torch.zeros(S1, device=dev, dtype=torch.float32)
+
+
+def _batched(x, q, B):
+    """The one place that broadcasts shared query rows to a batch: x (N, dx) or (B, N, dx) -> a batch (stride 0 where shared);
+    q None, (N,) or (B, N) -> None or (B, N)."""
+    xb = x[None].expand(B, -1, -1) if x.dim() == 2 else x
+    qb = None if q is None else (q[None].expand(B, -1) if q.dim() == 1 else q)
+    return xb, qb
+
+
+def _gather_inputs(latents0, coords, img, masks, weights, channel, fused_launch):
     """What inner_loop prepares before its first step, for every weight form and both mask layouts: the signals' copies of the latent
     initialisation (pde_trainer.py:157-159), the coordinates and targets of all S+1 steps gathered once (:193-197), one zeroed loss
     accumulator per step and the gathered weights -- (lat, xs_all, ys_all, losses, ws_all), ws_all None without weights on shared
-    masks.  ONE launch (_fit_inputs) instead of eight framework kernels, or the same in torch ops."""
-    fused = _fit_inputs(latents0, coords, img, masks, weights, channel=channel) if FUSED_FIT_INPUTS else None
+    masks.  ONE launch (_fit_inputs) instead of eight framework kernels, or -- where the launch declines, or without ``fused_launch``, the
+    loop's reading of FUSED_FIT_INPUTS -- the same in torch ops."""
+    fused = _fit_inputs(latents0, coords, img, masks, weights, channel=channel) if fused_launch else None
     if fused is not None:
         return fused if len(fused) == 5 else (*fused, None)
-    B = img.shape[0]
-    lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}       # (a fresh tensor)
-    losses = torch.zeros(masks.shape[-1], device=img.device, dtype=torch.float32)        # zeroed in one fill
+    lat, losses = _fresh(latents0, img.shape[0], masks.shape[-1], img.device)
     if masks.dim() == 3:                                                 # (S+1, B, N_s, .): enf_fit_inputs_b / _cw in torch ops
         xs_all, ys_all, ws_all = gather_signal_points(coords, img, masks, weights)
         return lat, xs_all, ys_all, losses, ws_all
@@ -229,6 +249,172 @@ def _shared_kw(nef, s, per_signal, noise_pos, step="mse_value_and_latent_grads")
     return {"shared_latents": True} if _takes_shared_hint(getattr(fn, "__func__", fn)) else {}
 
 
+class _Observed:
+    """What the kinds of observation share.  A kind has two halves.  The CALLS half says which calls of the decoder are the kind's fit
+    step, evaluation and Gauss-Newton product (STEP / EVAL / PRODUCT), what they take beside the query rows (``_call``: nothing, the
+    group size and the factors, the operator) and which keywords carry sampled weights (WEIGHT_KW, chosen here and nowhere else); it
+    needs no grid.  The constructor adds the other half, the shared grid the loops sample from, and validates it.  ``Kind.given(...)``
+    builds a kind from parts that its caller has checked in its own words: both halves, or the calls half alone for a caller that
+    brings batched inputs of its own (gauss_newton._lm_loop, fit_cell_averages, fit_linear_observations)."""
+
+    @classmethod
+    def given(cls, **owns):
+        obs = object.__new__(cls)
+        obs.__dict__.update(owns)
+        return obs
+
+    def _weight_kw(self, ws, channel, always=False):
+        return {self.WEIGHT_KW[bool(channel)]: ws} if ws is not None or always else {}
+
+    def weights_kw(self, *ws):
+        """A front end's own weight arguments, in the order of WEIGHT_KW (per observation, then per value), by the decoder's keywords."""
+        return dict(zip(self.WEIGHT_KW, ws))
+
+    def reserve_kw(self):
+        """What nef.gn_reserve takes beside the sizes."""
+        return {}
+
+    def fit_step(self, nef, params, xs, qs, p, a, window, ys, ws, channel, always=False, **kw):
+        return self._call(nef, self.STEP, params, xs, qs, p, a, window, ys, **kw, **self._weight_kw(ws, channel, always))
+
+    def gn_product(self, nef, params, xs, qs, p, a, window, **kw):
+        return self._call(nef, self.PRODUCT, params, xs, qs, p, a, window, **kw)
+
+    def loss_b(self, nef, params, xs, qs, p, a, window, ys, **kw):
+        """Every signal's loss from the kind's evaluation, without a decode."""
+        return self._call(nef, self.EVAL, params, xs, qs, p, a, window, ys, **kw)[0]
+
+    def final_loss(self, nef, params, xs, qs, p, a, window, ys, ws, channel, loss_out, per_signal_loss):
+        """The loop's loss on the last set, added to ``loss_out``; returns loss_b with ``per_signal_loss``."""
+        return self.loss_b(nef, params, xs, qs, p, a, window, ys, loss_out=loss_out, per_signal=per_signal_loss,
+                           **self._weight_kw(ws, channel, True))
+
+    def decode_loss(self, nef, params, img, masks, s, lat, weights, mse):
+        xs, qs, ys, ws = self.sampled(img, masks, s, weights)                      # pde_trainer.py:193-197
+        out = nef.apply(params, xs, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"))
+        return self.loss_of_decode(nef, out, ys, qs, ws, mse)
+
+
+class Points(_Observed):
+    """Values of the field at the N grid points ``coords`` (N, dx): one query row per observation."""
+    rows, WEIGHT_KW = 1, ("weight", "channel_weight")
+    STEP, EVAL, PRODUCT = "mse_value_and_latent_grads", "eval_loss", "gn_product"
+
+    def __init__(self, coords):
+        self.x, self.num = coords, coords.shape[0]
+
+    def _call(self, nef, name, params, xs, qs, p, a, window, *ys, **kw):
+        return getattr(nef, name)(params, xs, p, a, window, *ys, **kw)
+
+    def num_sampled(self, max_points):
+        return max_points
+
+    def hints(self, channel):
+        return True
+
+    def step_kw(self, lw):
+        """The keywords a public step takes this observation and its prepared weights by."""
+        return loop_kw(lw)
+
+    def loop_args(self, img, masks, lw, decode_free=False):
+        """What inner_loop takes after the learning rates, and by keyword, to fit these points with the prepared weights ``lw``;
+        ``decode_free``: its last loss is to come from enf_eval_loss."""
+        return (self.x, img, masks), dict(loop_kw(lw), **({"per_signal_loss": True} if decode_free else {}))
+
+    def gather(self, latents0, img, masks, w, channel, fused_launch):
+        lat, xs_all, ys_all, losses, ws_all = _gather_inputs(latents0, self.x, img, masks, w, channel, fused_launch)
+        return lat, xs_all, None, ys_all, losses, ws_all
+
+    def step_inputs(self, xs_all, qs_all, ws_all, s, B, per_signal):
+        return xs_all[s] if per_signal else _batched(xs_all[s], None, B)[0], None, None if ws_all is None else ws_all[s]
+
+    def sampled(self, img, masks, s, weights, copies=1):
+        """The points of step ``s``: (xs (copies * B, N_s, dx), None, ys (B, N_s, O), weights (B, N_s) or None).  Shared masks (N_s, S+1)
+        give the reference's gather (pde_trainer.py:193-197) with a stride-0 batch; per-signal masks (B, N_s, S+1) give every signal its
+        own points and always weights (0 where the sampler padded with -1; gather_signal_points).  Per-channel ``weights`` (B, N, O) come
+        back as (B, N_s, O); weighted_mse tells the two apart by their rank."""
+        if masks.dim() == 2:
+            m = masks[:, s]
+            return _batched(self.x[m], None, copies * img.shape[0])[0], None, img[:, m], (None if weights is None else weights[:, m])
+        xs, ys, ws = gather_signal_points(self.x, img, masks[:, :, s:s + 1], weights)
+        return (xs[0] if copies == 1 else xs[0].repeat(copies, 1, 1)), None, ys[0].to(img.dtype), ws[0]
+
+    def eval(self, nef, params, part, n, p, a, window, ys, ws, channel):
+        """(loss_b or None, err (n, |part|)) of ``n`` signals on the slice ``part`` of the grid, without a decode (nef.eval_loss)."""
+        return nef.eval_loss(params, _batched(self.x[part], None, n)[0], p, a, window, ys, per_signal=False, **self._weight_kw(ws, channel))
+
+    def loss_of_decode(self, nef, out, ys, qs, ws, mse):
+        """``mse``: the calling module's weighted_mse (fitting/weights.py), formed only where there are weights."""
+        return ((out - ys) ** 2).mean() if ws is None else mse(out, ys, ws)         # pde_trainer.py:185
+
+    def final_loss(self, nef, params, xs, qs, p, a, window, ys, ws, channel, loss_out, per_signal_loss):
+        """The loop's loss on the last mask, added to ``loss_out``: enf_eval_loss with ``per_signal_loss`` (returns loss_b), else the
+        reference's decode (pde_trainer.py:225-235) and the loss kernel of the weight form (returns None)."""
+        if per_signal_loss:
+            return self.loss_b(nef, params, xs, qs, p, a, window, ys, loss_out=loss_out, **self._weight_kw(ws, channel, True))
+        with torch.no_grad():
+            out = nef.apply(params, xs, p, a, window).float().contiguous()
+            if out.shape != ys.shape:
+                raise AssertionError(f"targets have shape {tuple(ys.shape)}, expected {tuple(out.shape)}")
+            lib, n, loss = _lib.load(), out.numel(), loss_out.data_ptr()
+            if ws is None:
+                fn, args = lib.enf_mse_value_grad, (n, 1.0, None, loss)
+            elif channel:
+                fn, args = lib.enf_mse_value_grad_cw, (ws.data_ptr(), n, 1.0, None, loss, None, 0, 0)
+            else:
+                fn, args = lib.enf_mse_value_grad_w, (ws.data_ptr(), n, out.shape[-1], 1.0, None, loss, None, 0, 0)
+            _lib.launch(out.device, fn, out.data_ptr(), ys.data_ptr(), *args, _lib.stream(out.device))
+
+    def latent_grads(self, nef, params, img, masks, s, lat, keys, weights, mse):
+        """d loss_s / d lat[keys] of meta_gradients' forward sweep: autograd through nef.apply."""
+        leaves = {k: lat[k].detach().requires_grad_(True) for k in lat}
+        g = torch.autograd.grad(self.decode_loss(nef, params, img, masks, s, leaves, weights, mse), [leaves[k] for k in keys], allow_unused=True)
+        return {k: (torch.zeros_like(lat[k]) if gk is None else gk) for k, gk in zip(keys, g)}
+
+    def subset(self, img, mask, lw, max_points, rng, per_signal):
+        """What a step of the auto-decoder trainer fits on (nonmaml_pde_trainer.py:311-335): (targets (B, n, O), xs (B, n, dx), None,
+        the LossWeights of these points or None) -- ``mask`` first (:321-323), then at most ``max_points`` points, one subset for the
+        batch drawn from ``rng`` (a stride-0 xs, :326-335), or with ``per_signal`` and weights every signal's own observed points (the
+        sampler's -1 padding has weight 0) with the weights rescaled for that draw.  With channel weights a point counts as observed
+        where any of its channels is."""
+        coords = self.x
+        if mask is not None:
+            img, coords, lw = img[:, mask], coords[mask], lw and lw.points(mask)
+        if per_signal and lw is not None:
+            m = make_signal_masks(lw.support(), min(max_points, coords.shape[0]), 0, generator=rng, device=coords.device)
+            # (the factor n_b / N of a draw from the observed points: the loss keeps the scale of the shared subset's)
+            xs, img, ws = (t[0] for t in gather_signal_points(coords, img, m, lw.drawn_on(m).w))
+            return img, xs, None, LossWeights(ws, lw.channel)
+        if max_points < coords.shape[0]:
+            sub = torch.randperm(coords.shape[0], generator=rng)[:max_points].to(coords.device)
+            img, coords, lw = img[:, sub], coords[sub], lw and lw.points(sub)
+        return img, _batched(coords, None, img.shape[0])[0], None, lw
+
+    def sample_frames(self, traj, point_masks=None, weights=None):
+        """Queries and targets of the B T signal-frames: ``traj`` (B, T, N, O), ``point_masks`` (T, n_s) long or None for the full grid.
+        Returns xs (B T, n, dx), None, ys (B T, n, O), signal-major like the flattened roll-out, and the gather of ``weights`` (B, T, N)
+        -> ws (B T, n), per-channel (B, T, N, O) -> (B T, n, O), or None."""
+        B, T, N, O = traj.shape
+        if point_masks is None:
+            return (_batched(self.x, None, B * T)[0], None, traj.reshape(B * T, N, O),
+                    None if weights is None else weights.reshape(B * T, N, *weights.shape[3:]))
+        n_s = point_masks.shape[1]
+        xs = self.x[point_masks][None].expand(B, -1, -1, -1).reshape(B * T, n_s, -1)
+        return xs, None, *_gather_frames(traj, point_masks, weights)
+
+
+def _gather_frames(traj, masks, weights):
+    """ys (B T, n, O) and ws -- None, (B T, n) or (B T, n, O) -- of ``traj`` (B, T, num, O) at the per-frame index sets ``masks`` (T, n)."""
+    B, T, _, O = traj.shape
+    n = masks.shape[1]
+    ys = torch.gather(traj, 2, masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n, O)
+    if weights is None:
+        return ys, None
+    if weights.dim() == 4:
+        return ys, torch.gather(weights, 2, masks[None, :, :, None].expand(B, -1, -1, O)).reshape(B * T, n, O)
+    return ys, torch.gather(weights, 2, masks[None].expand(B, -1, -1)).reshape(B * T, n)
+
+
 def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaussian_window=False,
                noise_pos=0.0, generator=None, weights=None, normalize_weights=False, channel_weights=None, per_signal_loss=False):
     """Fit per-signal latents with S steps of meta-SGD (pde_trainer.py:156-235).
@@ -261,7 +447,6 @@ def inner_loop(nef, nef_params, latents0, lrs, coords, img, masks, optimize_gaus
                Every weight form and both mask layouts.
     Returns (loss on the last mask, fitted latents dict with leading dim B), with ``per_signal_loss`` followed by loss_b.
     """
-    from .observations import Points                 # (observations imports this module)
     B = img.shape[0]
     if masks.dim() == 3 and masks.shape[0] != B:
         raise ValueError(f"per-signal masks have shape {tuple(masks.shape)}, expected ({B}, N_s, S + 1)")
@@ -294,10 +479,11 @@ def _sgd_step(nef, nef_params, obs, lat, lrs, xs, qs, ys, ws, channel, optimize_
 
 def _fit_loop(nef, nef_params, obs, latents0, lrs, data, masks, w, channel, optimize_gaussian_window, noise_pos, generator,
               normalize_weights, per_signal_loss):
-    """The loop behind inner_loop and inner_loop_cells (fitting/observations.py: ``obs`` says which): gather once, jitter once, S steps,
-    the loss on the last mask.  ``w``: the full weights next to ``data``, float32 and contiguous, or None; ``channel``: they are per value."""
+    """The loop behind inner_loop and inner_loop_cells (``obs`` says which): gather once, jitter once, then the body on step s's share
+    of the gather, with the shared-latent hint where step 0 may take it.  ``w``: the full weights next to ``data``, float32 and
+    contiguous, or None; ``channel``: they are per value."""
     B, S, per_signal = data.shape[0], masks.shape[-1] - 1, masks.dim() == 3
-    lat, xs_all, qs_all, ys_all, losses, ws_all = obs.gather(latents0, data, masks, w, channel)
+    lat, xs_all, qs_all, ys_all, losses, ws_all = obs.gather(latents0, data, masks, w, channel, FUSED_FIT_INPUTS)
     if normalize_weights:
         if ws_all is None:
             raise ValueError("normalize_weights needs sampled weights: pass weights or per-signal masks")
@@ -305,15 +491,36 @@ def _fit_loop(nef, nef_params, obs, latents0, lrs, data, masks, w, channel, opti
     if noise_pos:                                                                             # pde_trainer.py:162-167
         lat["p_pos"] = lat["p_pos"] + torch.randn(lat["p_pos"].shape, generator=generator,
                                                   device="cpu").to(lat["p_pos"].device) * noise_pos
-    rows = [] if per_signal_loss else None                              # loss_b, with per_signal_loss
     more = {"return_errors": True} if per_signal_loss else {}
-    for s in range(S):                                                  # pde_trainer.py:191
+
+    def inputs(s):
         xs, qs, ws = obs.step_inputs(xs_all, qs_all, ws_all, s, B, per_signal)
-        lat = _sgd_step(nef, nef_params, obs, lat, lrs, xs, qs, ys_all[s], ws, channel, optimize_gaussian_window, rows,
-                        loss_out=losses[s:s + 1], **more, **(_shared_kw(nef, s, per_signal, noise_pos, step=obs.STEP) if obs.hints(channel) else {}))
-    xs, qs, ws = obs.step_inputs(xs_all, qs_all, ws_all, S, B, per_signal)
+        return xs, qs, ys_all[s], ws
+    return _fit_body(nef, nef_params, obs, lat, lrs, inputs, S, losses, channel, optimize_gaussian_window, per_signal_loss,
+                     lambda s: {**more, **(_shared_kw(nef, s, per_signal, noise_pos, step=obs.STEP) if obs.hints(channel) else {})})
+
+
+def _fit_given(nef, nef_params, obs, latents0, lrs, inputs, B, S, dev, channel, optimize_gaussian_window, per_signal_loss):
+    """The fit of fit_cell_averages and fit_linear_observations: the body on inputs the caller chose -- ``inputs(s)`` -> step s's (xs, qs,
+    ys, ws), already a batch -- from the latent initialisation, never with the shared-latent hint."""
+    lat, losses = _fresh(latents0, B, S + 1, dev)
+    return _fit_body(nef, nef_params, obs, lat, lrs, inputs, S, losses, channel, optimize_gaussian_window, per_signal_loss,
+                     lambda s: {"return_errors": per_signal_loss})
+
+
+def _fit_body(nef, nef_params, obs, lat, lrs, inputs, S, losses, channel, optimize_gaussian_window, per_signal_loss, step_kw):
+    """What every meta-SGD fit runs, whatever it observes and however it chose its inputs: S steps from the signals' latents ``lat``,
+    step s on ``inputs(s)`` = (xs, qs, ys, ws) with the keywords ``step_kw(s)`` and its loss in ``losses[s]``; then the loss on
+    ``inputs(S)`` at the fitted latents in ``losses[S]``.  Returns (that loss, the latents), with ``per_signal_loss`` followed by
+    loss_b (S + 1, B)."""
+    rows = [] if per_signal_loss else None                              # loss_b, with per_signal_loss
+    for s in range(S):                                                  # pde_trainer.py:191
+        xs, qs, ys, ws = inputs(s)
+        lat = _sgd_step(nef, nef_params, obs, lat, lrs, xs, qs, ys, ws, channel, optimize_gaussian_window, rows, loss_out=losses[s:s + 1],
+                        **step_kw(s))
+    xs, qs, ys, ws = inputs(S)
     lb = obs.final_loss(nef, nef_params, xs, qs, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"),
-                        ys_all[S], ws, channel, losses[S:], per_signal_loss)
+                        ys, ws, channel, losses[S:], per_signal_loss)
     if per_signal_loss:
         rows.append(lb)
         return losses[S], lat, torch.stack(rows)
@@ -324,8 +531,7 @@ def _fit_loop(nef, nef_params, obs, latents0, lrs, data, masks, w, channel, opti
 def decode(nef, nef_params, coords, p, a, window, chunk=None):
     """Reconstruct (B, N, O) on the full grid (pde_trainer.py:393-402).  The fused kernel tiles over
     queries itself, so ``chunk`` is optional (the reference chunks by max_num_sampled_points)."""
-    B = p.shape[0]
-    x = coords[None].expand(B, -1, -1) if coords.dim() == 2 else coords
+    x = _batched(coords, None, p.shape[0])[0]
     if chunk is None:
         return nef.apply(nef_params, x, p, a, window)
     outs = [nef.apply(nef_params, x[:, i:i + chunk], p, a, window) for i in range(0, x.shape[1], chunk)]

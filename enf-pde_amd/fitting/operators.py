@@ -6,15 +6,16 @@ here rows may have any length (0 .. N), share query points and refer to them in 
 that share nodes between neighbouring cells, triangles, footprints of changing size, increments, line integrals, conserved totals.
 
 ``SparseObservations`` holds the CSR (forward product) and the CSC (transposed product) of one operator, validated on the host when it
-is built.  ``cell_operator`` and ``line_integrals`` build (x, op) pairs; ``decode_observations`` and ``fit_linear_observations`` run a
+is built; ``LinearObservations`` is the observation value of this kind (inner_loop.py: _Observed) and ``check_operator`` the one copy
+of the argument checks.  ``cell_operator`` and ``line_integrals`` build (x, op) pairs; ``decode_observations`` and ``fit_linear_observations`` run a
 decoder against them (nef.mse_value_and_operator_grads: the pair and tail kernels of the point fit with the two products of
 csrc/enf_obs.hip between the tail's forward and backward)."""
 import numpy as np
 import torch
 
 from .. import _lib
-from .cells import _edges, _rule_1d, _one_weight_kind
-from .inner_loop import _pose, _sgd_step
+from .cells import _edges, _rule_1d, check_obs_weights
+from .inner_loop import _Observed, _batched, _fit_given
 
 CLOSED_RULES = ("trapezoid", "simpson")
 
@@ -224,14 +225,55 @@ def line_integrals(starts, ends, k, rule="gauss", dtype=torch.float32, device=No
     return torch.tensor(x.reshape(R * k, -1), dtype=dtype, device=device), op
 
 
+def check_operator(x, op, B=None, target=None, target_wrong=None, shared=False):
+    """The one check of query points and targets against an operator; ValueError otherwise, x first.
+    ``shared``: ``x`` is the grid the signals share and must be (N, dx) with N = op.N; else it is that or a batch (B, N, dx).
+    ``target``: must be (B, op.M, O); ``target_wrong``: the caller's words for it, a format of {shape}, {got}, {B} and {M}."""
+    if shared:
+        if x.dim() != 2 or x.shape[0] != op.N:
+            raise ValueError(f"x must be (N, dx) = ({op.N}, dx) for this operator, got {tuple(x.shape)}")
+    else:
+        if x.dim() not in (2, 3):
+            raise ValueError(f"x must be (N, dx) or (B, N, dx), got {tuple(x.shape)}")
+        if x.dim() == 3 and x.shape[0] != B:
+            raise ValueError(f"x holds {x.shape[0]} signals, the latents {B}")
+        if x.shape[-2] != op.N:
+            raise ValueError(f"x holds {x.shape[-2]} query points, the operator has {op.N} columns")
+    if target is not None and (target.dim() != 3 or target.shape[0] != B or target.shape[1] != op.M):
+        raise ValueError(target_wrong.format(shape=tuple(target.shape), got=target.shape[1] if target.dim() > 1 else "no", B=B, M=op.M))
+
+
+class LinearObservations(_Observed):
+    """Linear functionals of the field given by a sparse operator (SparseObservations) on the query points ``x`` (N, dx): observation m
+    owns the entries of row m, of any number, shared or not.  It answers what the fits on an operator ask -- the step, the evaluation,
+    the Gauss-Newton product and its buffer (fit_linear_observations, gauss_newton.lm_fit_linear_observations) -- and nothing of what
+    sampling needs: there is no gather of rows, and ``observed`` and the trainers' steps refuse it."""
+    WEIGHT_KW = ("obs_weight", "obs_channel_weight")
+    STEP, EVAL, PRODUCT = "mse_value_and_operator_grads", "eval_operator_loss", "gn_operator_product"
+    REFUSAL = ("a linear observation operator is served by fitting.fit_linear_observations and fitting.lm_fit_linear_observations only: "
+               "the trainers' steps and inner_loop sampling do not take it yet")
+
+    def __init__(self, x, op):
+        check_operator(x, op, shared=True)
+        self.x, self.op, self.num = x, op, op.M
+
+    def _call(self, nef, name, params, xs, qs, p, a, window, *ys, **kw):
+        return getattr(nef, name)(params, xs, p, a, window, *ys, self.op, **kw)
+
+    def hints(self, channel):
+        return False
+
+    def reserve_kw(self):
+        return {"op": self.op}
+
+
 @torch.no_grad()
 def decode_observations(nef, params, x, op, p, a, window):
     """obs (B, M, O) = A out of a decode at the operator's query points: nef.apply followed by the forward product (enf_obs_apply).
     x (N, dx) or (B, N, dx)."""
     B = p.shape[0]
-    xb = x[None].expand(B, -1, -1) if x.dim() == 2 else x
-    if xb.shape[1] != op.N:
-        raise ValueError(f"x holds {xb.shape[1]} query points, the operator has {op.N} columns")
+    check_operator(x, op, B)
+    xb, _ = _batched(x, None, B)
     out = nef.apply(params, xb, p, a, window).float().contiguous()
     obs = torch.empty((B, op.M, out.shape[2]), device=out.device, dtype=torch.float32)
     s = op.struct(transposed=False)
@@ -251,27 +293,10 @@ def fit_linear_observations(nef, params, latents0, lrs, x, op, targets, steps, o
                     target may be NaN;  obs_channel_weight: None or (B, M, O), one weight per observed value (both: ValueError)
     Returns (loss at the fitted latents, latents dict with leading dimension B), with ``per_signal_loss`` followed by loss_b
     (steps + 1, B)."""
-    from .observations import LinearObservations          # (observations imports this module)
-    obs = LinearObservations(x, op)
-    B, M, O = targets.shape
-    if M != op.M:
-        raise ValueError(f"targets hold {M} observations, the operator {op.M}")
-    if obs_weight is not None and tuple(obs_weight.shape) != (B, M):
-        raise ValueError(f"obs_weight has shape {tuple(obs_weight.shape)}, expected {(B, M)}")
-    _one_weight_kind("fit_linear_observations", obs_weight, obs_channel_weight, (B, M, O))
-    per_value = obs_channel_weight is not None
-    ws = obs_channel_weight if per_value else obs_weight
-    dev, S = targets.device, int(steps)
-    ys = targets.float()
-    xb = x.to(dev)[None].expand(B, -1, -1)
-    lat = {k: v.detach().repeat_interleave(B, dim=0) for k, v in latents0.items()}
-    losses = torch.zeros(S + 1, device=dev, dtype=torch.float32)
-    rows_b = [] if per_signal_loss else None
-    for s in range(S):
-        lat = _sgd_step(nef, params, obs, lat, lrs, xb, None, ys, ws, per_value, optimize_gaussian_window, rows_b,
-                        loss_out=losses[s:s + 1], return_errors=per_signal_loss)
-    lb = obs.final_loss(nef, params, xb, None, _pose(lat, nef.cross_attn_invariant.num_z_ori_dims), lat["a"], lat.get("gaussian_window"), ys,
-                        ws, per_value, losses[S:], per_signal_loss)
-    if per_signal_loss:
-        return losses[S], lat, torch.stack(rows_b + [lb])
-    return losses[S], lat
+    B = targets.shape[0]
+    check_operator(x, op, B, targets, "targets hold {got} observations, the operator {M}", shared=True)
+    w, per_value = check_obs_weights("fit_linear_observations", obs_weight, obs_channel_weight, targets.shape)
+    dev = targets.device
+    given = (_batched(x.to(dev), None, B)[0], None, targets.float(), w)         # the caller's tensors themselves, a stride-0 batch
+    return _fit_given(nef, params, LinearObservations.given(op=op), latents0, lrs, lambda s: given, B, int(steps), dev, per_value,
+                      optimize_gaussian_window, per_signal_loss)

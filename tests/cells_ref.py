@@ -13,6 +13,7 @@ import torch
 
 from oracle import enf_ref_np as R
 from oracle import enf_ref_torch as T
+from tests.gn_ref import sgd_rule
 from tests.helpers import make_cfg, make_inputs
 
 B, Z = 3, 7
@@ -91,10 +92,9 @@ def fit_loop(cfg, prm, x, q, G, targets, w, lat0, lrs, steps):
     Bn = targets.shape[0]
     p, a, s = (np.repeat(np.asarray(u, dtype=np.float64), Bn, 0) for u in lat0)
     xb, qb = np.repeat(x[None], Bn, 0), np.repeat(q[None], Bn, 0)
-    losses = []
-    for _ in range(steps):
-        r = cell_loss(cfg, prm, xb, p, a, s, targets, G, qb, w, float(Bn))
-        losses.append(r.loss)
-        p, a = p - lrs[0] * r.g[0], a - lrs[1] * r.g[1]
-    losses.append(cell_loss(cfg, prm, xb, p, a, s, targets, G, qb, w, grads=False).loss)
-    return np.array(losses), (p, a, s)
+
+    def loss(cur, grads):
+        r = cell_loss(cfg, prm, xb, *cur, targets, G, qb, w, float(Bn), grads=grads)
+        return r.loss, r.g
+    losses, lat = sgd_rule(loss, p, a, s, steps, lrs[0], lrs[1])           # (tests/gn_ref.py: the one copy of the rule)
+    return np.array(losses), tuple(lat)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from oracle import enf_ref_torch as T
-from tests import cells_ref, tangent_ref
+from tests import cells_ref, gn_ref, tangent_ref
 from tests.cells_ref import cell_loss, f32, rel  # noqa: F401
 
 _CASES, _FIT = {}, {}
@@ -92,57 +92,22 @@ def fit_case(inv, G=4, N=80, seed=21, scale_p=0.05, scale_a=0.5):
     return _FIT[key]
 
 
+def _loss(cfg, prm, x, q, G, target, w, B):
+    """cells_ref.cell_loss at gradient scale B as tests/gn_ref.lm_loop and sgd_rule take a loss: (loss_b, g)"""
+    def loss(cur, grads):
+        r = cell_loss(cfg, prm, x, *cur, target, G, q, w, float(B), grads=grads)
+        return r.loss_b, r.g
+    return loss
+
+
 def oracle_lm_cells(cfg, prm, x, q, G, target, p, a, s, steps, w=None, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0, which=(0, 1)):
-    """lm_fit_cell_averages on the oracle (tests/gn_ref.oracle_lm on the grouped loss and product): loss_b (steps + 1, B) and the
+    """lm_fit_cell_averages on the oracle (tests/gn_ref.lm_loop on the grouped loss and product): loss_b (steps + 1, B) and the
     acceptance masks (steps, B).  `which`: the moving components (0 = p, 1 = a, 2 = sigma)."""
     B = p.shape[0]
-    cur = [p.copy(), a.copy(), s.copy()]
-    lam = np.full(B, damping)
-    hist, accs = [], []
-    bdot = lambda u, v: sum((ui * vi).reshape(B, -1).sum(1) for ui, vi in zip(u, v))
-    for _ in range(steps):
-        r0 = cell_loss(cfg, prm, x, *cur, target, G, q, w, float(B))
-        lb, g = r0.loss_b, r0.g
-        hist.append(lb)
-        r = [-g[c] for c in which]
-        xs = [np.zeros_like(v) for v in r]
-        d = [v.copy() for v in r]
-        rho = bdot(r, r)
-        for _ in range(cg_iters):
-            v = [None, None, None]
-            for c, dc in zip(which, d):
-                v[c] = dc
-            gv = oracle_gn_cells(cfg, prm, x, *cur, v, G, q, w, float(B))[0]
-            qd = [gv[c] + lam.reshape(B, 1, 1) * dc for c, dc in zip(which, d)]
-            kappa = bdot(d, qd)
-            live = (rho > 0) & np.isfinite(rho) & (kappa > 0) & np.isfinite(kappa)
-            alpha = np.where(live, rho / np.where(live, kappa, 1.0), 0.0).reshape(B, 1, 1)
-            xs = [xi + alpha * di for xi, di in zip(xs, d)]
-            r = [ri - alpha * qi for ri, qi in zip(r, qd)]
-            rho2 = np.where(live, bdot(r, r), rho)
-            beta = np.where(live, rho2 / np.where(live, rho, 1.0), 0.0).reshape(B, 1, 1)
-            lv = live.reshape(B, 1, 1)
-            d = [np.where(lv, ri + beta * di, di) for ri, di in zip(r, d)]
-            rho = rho2
-        trial = [v.copy() for v in cur]
-        for c, dx in zip(which, xs):
-            trial[c] = cur[c] + dx
-        lb_t = cell_loss(cfg, prm, x, *trial, target, G, q, w, grads=False).loss_b
-        acc = lb_t < lb
-        for c in which:
-            cur[c] = np.where(acc.reshape(B, 1, 1), trial[c], cur[c])
-        lam = np.where(acc, lam * down, lam * up)
-        accs.append(acc)
-        last = np.where(acc, lb_t, lb)
-    hist.append(last)
-    return np.stack(hist), np.stack(accs)
+    return gn_ref.lm_loop(_loss(cfg, prm, x, q, G, target, w, B), lambda cur, v: oracle_gn_cells(cfg, prm, x, *cur, v, G, q, w, float(B))[0],
+                          p, a, s, steps, cg_iters, damping, down, up, which)
 
 
 def oracle_sgd_cells(cfg, prm, x, q, G, target, p, a, s, steps, w=None, lr_p=1.0, lr_a=5.0):
     """`steps` of the inner loop's SGD rule on (p, a) with gradient scale B against the grouped loss: the final per-signal losses"""
-    cur = [p.copy(), a.copy(), s.copy()]
-    for _ in range(steps):
-        g = cell_loss(cfg, prm, x, *cur, target, G, q, w, float(p.shape[0])).g
-        cur[0] = cur[0] - lr_p * g[0]
-        cur[1] = cur[1] - lr_a * g[1]
-    return cell_loss(cfg, prm, x, *cur, target, G, q, w, grads=False).loss_b
+    return gn_ref.sgd_rule(_loss(cfg, prm, x, q, G, target, w, p.shape[0]), p, a, s, steps, lr_p, lr_a)[0][-1]

@@ -71,16 +71,19 @@ def fit_case(inv, seed=21):
     return _FIT[(inv, seed)]
 
 
-def oracle_lm(cfg, prm, x, target, p, a, s, steps, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0, which=(0, 1)):
-    """lm_fit_latents on the oracle: returns loss_b (steps + 1, B) and the acceptance masks (steps, B).  `which`: the moving components
-    (0 = p, 1 = a, 2 = sigma)."""
+def lm_loop(loss, product, p, a, s, steps, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0, which=(0, 1)):
+    """The Levenberg-Marquardt loop of fitting/gauss_newton.py in fp64, dense per-signal CG, on ANY loss, written once.  Two callables on
+    the current latents ``cur`` = [p, a, s] say which:
+      loss(cur, grads)  -> (loss_b (B,), (gp, ga, gs) at gradient scale B -- or anything without ``grads``)
+      product(cur, v)   -> (gp, ga, gs), the Gauss-Newton product at gradient scale B along v = [vp, va, vs], a None entry is zero
+    Returns loss_b (steps + 1, B) and the acceptance masks (steps, B).  `which`: the moving components (0 = p, 1 = a, 2 = sigma)."""
     B = p.shape[0]
     cur = [p.copy(), a.copy(), s.copy()]
     lam = np.full(B, damping)
     hist, accs = [], []
     bdot = lambda u, v: sum((ui * vi).reshape(B, -1).sum(1) for ui, vi in zip(u, v))
     for _ in range(steps):
-        lb, g = oracle_loss_grad(cfg, prm, x, *cur, target, grad_scale=float(B))
+        lb, g = loss(cur, True)
         hist.append(lb)
         r = [-g[c] for c in which]
         xs = [np.zeros_like(v) for v in r]
@@ -90,7 +93,7 @@ def oracle_lm(cfg, prm, x, target, p, a, s, steps, cg_iters=8, damping=1e-2, dow
             v = [None, None, None]
             for c, dc in zip(which, d):
                 v[c] = dc
-            gv, _ = oracle_gn(cfg, prm, x, *cur, v, None, grad_scale=float(B))
+            gv = product(cur, v)
             q = [gv[c] + lam.reshape(B, 1, 1) * dc for c, dc in zip(which, d)]
             kappa = bdot(d, q)
             live = (rho > 0) & np.isfinite(rho) & (kappa > 0) & np.isfinite(kappa)
@@ -105,7 +108,7 @@ def oracle_lm(cfg, prm, x, target, p, a, s, steps, cg_iters=8, damping=1e-2, dow
         trial = [v.copy() for v in cur]
         for c, dx in zip(which, xs):
             trial[c] = cur[c] + dx
-        lb_t, _ = oracle_loss_grad(cfg, prm, x, *trial, target)
+        lb_t = loss(trial, False)[0]
         acc = lb_t < lb
         for c in which:
             cur[c] = np.where(acc.reshape(B, 1, 1), trial[c], cur[c])
@@ -116,14 +119,31 @@ def oracle_lm(cfg, prm, x, target, p, a, s, steps, cg_iters=8, damping=1e-2, dow
     return np.stack(hist), np.stack(accs)
 
 
+def sgd_rule(loss, p, a, s, steps, lr_p, lr_a):
+    """The inner loop's SGD rule on (p, a) in fp64, written once: ``loss(cur, grads)`` -> (a value, (gp, ga, gs) at gradient scale B) as
+    for lm_loop.  Returns (the values before every step and after the last one (steps + 1), the latents [p, a, s])."""
+    cur = [p, a, s]
+    vals = []
+    for _ in range(steps):
+        val, g = loss(cur, True)
+        vals.append(val)
+        cur = [cur[0] - lr_p * g[0], cur[1] - lr_a * g[1], s]
+    vals.append(loss(cur, False)[0])
+    return vals, cur
+
+
+def oracle_lm(cfg, prm, x, target, p, a, s, steps, cg_iters=8, damping=1e-2, down=1.0 / 3.0, up=4.0, which=(0, 1)):
+    """lm_fit_latents on the oracle (lm_loop on oracle_loss_grad and oracle_gn): loss_b (steps + 1, B) and the acceptance masks
+    (steps, B).  `which`: the moving components (0 = p, 1 = a, 2 = sigma)."""
+    B = float(p.shape[0])
+    return lm_loop(lambda cur, grads: oracle_loss_grad(cfg, prm, x, *cur, target, grad_scale=B),
+                   lambda cur, v: oracle_gn(cfg, prm, x, *cur, v, None, grad_scale=B)[0], p, a, s, steps, cg_iters, damping, down, up, which)
+
+
 def oracle_sgd(cfg, prm, x, target, p, a, s, steps, lr_p=1.0, lr_a=5.0):
     """`steps` of the inner loop's SGD rule on (p, a) with gradient scale B: the final per-signal losses"""
-    cur = [p.copy(), a.copy(), s.copy()]
-    for _ in range(steps):
-        _, g = oracle_loss_grad(cfg, prm, x, *cur, target, grad_scale=float(p.shape[0]))
-        cur[0] = cur[0] - lr_p * g[0]
-        cur[1] = cur[1] - lr_a * g[1]
-    return oracle_loss_grad(cfg, prm, x, *cur, target)[0]
+    loss = lambda cur, grads: oracle_loss_grad(cfg, prm, x, *cur, target, grad_scale=float(p.shape[0]))
+    return sgd_rule(loss, p, a, s, steps, lr_p, lr_a)[0][-1]
 
 
 _GN = {}

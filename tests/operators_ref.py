@@ -16,6 +16,7 @@ import torch
 from oracle import enf_ref_np as R
 from oracle import enf_ref_torch as T
 from tests.cells_ref import B, Z, f32, rel      # noqa: F401  (re-exported: one batch shape and one error measure for both yardsticks)
+from tests.gn_ref import sgd_rule
 from tests.helpers import make_cfg, make_inputs
 
 _CASES = {}
@@ -126,10 +127,9 @@ def fit_loop(cfg, prm, x, A, targets, w, lat0, lrs, steps):
     Bn = targets.shape[0]
     p, a, s = (np.repeat(np.asarray(u, dtype=np.float64), Bn, 0) for u in lat0)
     xb = np.repeat(x[None], Bn, 0)
-    losses = []
-    for _ in range(steps):
-        r = operator_loss(cfg, prm, xb, p, a, s, A, targets, w, float(Bn))
-        losses.append(r.loss)
-        p, a = p - lrs[0] * r.g[0], a - lrs[1] * r.g[1]
-    losses.append(operator_loss(cfg, prm, xb, p, a, s, A, targets, w, grads=False).loss)
-    return np.array(losses), (p, a, s)
+
+    def loss(cur, grads):
+        r = operator_loss(cfg, prm, xb, *cur, A, targets, w, float(Bn), grads=grads)
+        return r.loss, r.g
+    losses, lat = sgd_rule(loss, p, a, s, steps, lrs[0], lrs[1])           # (tests/gn_ref.py: the one copy of the rule)
+    return np.array(losses), tuple(lat)

@@ -208,8 +208,7 @@ def _run_cells(monkeypatch, pr, **kw):
     def update(lat, grads, lrs, scale):
         updates.append((sorted(grads), scale))
         return {k: v + 1.0 for k, v in lat.items()}
-    monkeypatch.setattr(IL, "meta_sgd_update", update)
-    monkeypatch.setattr(CELLS, "meta_sgd_update", update, raising=False)      # (where the loop on cells looks the update up)
+    monkeypatch.setattr(IL, "meta_sgd_update", update)            # (the loop on cells is inner_loop's: it looks the update up there)
     nef = _RecCells()
     return nef, CELLS.inner_loop_cells(nef, None, pr.lat0, None, pr.x, pr.q, G, pr.obs, pr.masks, **pr.kw, **kw), updates
 
