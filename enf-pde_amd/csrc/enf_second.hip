@@ -14,7 +14,11 @@
 //                            query RFFNet for its logit, the value RFFNet and its folded Dense).  The softmax sums Y, C, L, T, S get
 //                            U = sum e (d2y + 2 dl dy + (d2l + dl^2) y) and R = sum e (d2l + dl^2) beside them, and
 //                            d2 ybar = U / L - 2 (S / L) d ybar - (R / L) ybar
-//   enf_tail_second_kernel   tail_forward_tan's chain with the third stream; stores out (optional), tan (optional) and tan2
+//   enf_tail_tangent_kernel  <.., ORDER = 2> (enf_tangent_common.h): the tangent tail's chain and kernel with the third stream; stores
+//                            out (optional), tan (optional) and tan2
+// The pair kernel calls the second-order forms of the panel product and of the activation rules directly.  gb_panel3 and rff_embed3
+// are its own; panel_gemm3, gelu_second and ln_second sit in enf_tangent_common.h beside their first-order forms, where the tail chain
+// picks one by its order.
 // Every output element is written once, by one lane, in a fixed order of operations: no atomics, bit-reproducible run to run.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,30 +29,6 @@
 #include "enf_tangent_common.h"
 
 namespace {
-
-// The three-operand form of panel_gemm2: acc += panel . F (the caller initialised acc), dacc = panel . dF, d2acc = panel . d2F (zero
-// start, no bias), all from the SAME staged panel before its slot is released.
-template <int KBIN, int MTOUT, bool BF16, int NEXT_BYTES>
-DEV void panel_gemm3(f32x4 (&acc)[MTOUT], f32x4 (&dacc)[MTOUT], f32x4 (&d2acc)[MTOUT], const Frags<BF16, KBIN>& F,
-                     const Frags<BF16, KBIN>& dF, const Frags<BF16, KBIN>& d2F, Pipe& P, char* ring, unsigned panel, unsigned next,
-                     bool active, int lane) {
-  using C = PanelCfg<KBIN, MTOUT, BF16>;
-#pragma unroll
-  for (int sp = 0; sp < C::SPP; ++sp) {
-    if (sp + 1 < C::SPP) tan_issue<C::STAGE>(P, panel + (sp + 1) * C::STAGE, ring + (P.cur ^ 1) * STAGE_MAX, lane);
-    else if (next != NO_STAGE) tan_issue<NEXT_BYTES>(P, next, ring + (P.cur ^ 1) * STAGE_MAX, lane);
-    const char* slot = ring + P.cur * STAGE_MAX;
-    if (active) {
-      gemm_stage<BF16, KBIN, C::MTS, INIT_ACC>(&acc[sp * C::MTS], F, slot, lane);
-      gemm_stage<BF16, KBIN, C::MTS, INIT_ZERO>(&dacc[sp * C::MTS], dF, slot, lane);
-      gemm_stage<BF16, KBIN, C::MTS, INIT_ZERO>(&d2acc[sp * C::MTS], d2F, slot, lane);
-    } else {
-#pragma unroll
-      for (int mt = 0; mt < C::MTS; ++mt) dacc[sp * C::MTS + mt] = d2acc[sp * C::MTS + mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    stage_close(P);
-  }
-}
 
 // gb_panel2 without a tangent of v0 and with the second-order stream: v = v0 (1 + gamma) + beta, dv = v0 dgamma + dbeta,
 // d2v = v0 d2gamma + d2beta
@@ -119,71 +99,6 @@ DEV void rff_embed3(f32x4 (&E)[D / 16], f32x4 (&dE)[D / 16], f32x4 (&d2E)[D / 16
       d2E[TT + tt][i] = fmaf(-TWO_PI * s, d2t[i], -w2 * c);
     }
   }
-}
-
-// gelu_fg2 with the second derivative from the same sigmoid: with s = sigmoid(w), w = 2k(x + c x^3), w' = 2k(1 + 3c x^2), w'' = 12 k c x
-//   g' = s + x s(1-s) w',   g'' = 2 s(1-s) w' + x s(1-s) ((1-2s) w'^2 + w'')
-DEV void gelu_fgh2(f32x2 x, f32x2& g, f32x2& dg, f32x2& hg) {
-  const float c = 0.7978845608028654f;
-  const float c2 = -2.0f * c * 1.4426950408889634f;
-  const f32x2 x2 = x * x;
-  const f32x2 u = x * (x2 * (c2 * 0.044715f) + c2);
-  f32x2 e;
-  e[0] = __builtin_amdgcn_exp2f(u[0]);
-  e[1] = __builtin_amdgcn_exp2f(u[1]);
-  e = e + 1.0f;
-  f32x2 s;
-  s[0] = __builtin_amdgcn_rcpf(e[0]);
-  s[1] = __builtin_amdgcn_rcpf(e[1]);
-  g = x * s;
-  const f32x2 gs = g - g * s, wp = x2 * (6.0f * c * 0.044715f) + 2.0f * c;
-  dg = gs * wp + s;
-  const f32x2 ss = s - s * s;
-  hg = ss * wp * 2.0f + gs * ((1.0f - 2.0f * s) * wp * wp + x * (12.0f * c * 0.044715f));
-}
-// X <- gelu(X), dX <- gelu'(X) dX, d2X <- gelu'(X) d2X + gelu''(X) dX^2
-template <int NT> DEV void gelu_second(f32x4 (&X)[NT], f32x4 (&dX)[NT], f32x4 (&d2X)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    f32x2 g0, d0, h0, g1, d1, h1;
-    gelu_fgh2(lo2(X[t]), g0, d0, h0);
-    gelu_fgh2(hi2(X[t]), g1, d1, h1);
-    const f32x4 g = {g0[0], g0[1], g1[0], g1[1]}, d = {d0[0], d0[1], d1[0], d1[1]}, h = {h0[0], h0[1], h1[0], h1[1]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      d2X[t][i] = fmaf(d[i], d2X[t][i], h[i] * dX[t][i] * dX[t][i]);
-      dX[t][i] *= d[i];
-    }
-    X[t] = g;
-  }
-}
-
-// LayerNorm without affine, y = (g - mu) rstd already applied; dg, d2g the raw streams on entry, dy, d2y on exit.  With
-// m1 = mean(y dg) and means over the true width (exact with the eps):
-//   dy = rstd (dg - mean dg - y m1)                                    (ln_tangent's expression)
-//   d2y = rstd (d2g - mean d2g - y mean(y d2g)) - 2 rstd m1 dy - rstd y mean(dy dg)
-// Every sum carries a raw stream as a factor, which is zero in zero-padded features: padding adds nothing.
-template <int NT> DEV void ln_second(f32x4 (&dg)[NT], f32x4 (&d2g)[NT], const f32x4 (&y)[NT], float rstd, float inv_n) {
-  float s, d, s2, dd2;
-  tiles_sum_dot<NT>(dg, [&](int t) { return y[t]; }, s, d);
-  tiles_sum_dot<NT>(d2g, [&](int t) { return y[t]; }, s2, dd2);
-  const float m1 = xquad_sum(d) * inv_n;
-  const float c0 = -(xquad_sum(s) * inv_n) * rstd, c1 = -m1 * rstd;
-  float q = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float dy = fmaf(y[t][i], c1, fmaf(dg[t][i], rstd, c0));
-      q = fmaf(dy, dg[t][i], q);
-      dg[t][i] = dy;
-    }
-  const float mq = xquad_sum(q) * inv_n;
-  const float e0 = -(xquad_sum(s2) * inv_n) * rstd, e1 = -(xquad_sum(dd2) * inv_n + mq) * rstd, f = -2.f * rstd * m1;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d2g[t][i] = fmaf(f, dg[t][i], fmaf(y[t][i], e1, fmaf(d2g[t][i], rstd, e0)));
 }
 
 // (invariant, window) differentiated twice along the query's own tangent tq (zero beyond dx); the latent has no tangent.  `inv`, `win`
@@ -502,114 +417,14 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_second_kernel(PairSecArgs A) 
   }
 }
 
-// ---------------------------------------------------------------- the tail
-struct TailSecArgs {
-  const float* ybar; const float* ydot; const float* y2; const char* blob; EnfLayout L;
-  float* out;            // (B N, O) or nullptr
-  float* tan;            // (B N, O) or nullptr
-  float* tan2;           // (B N, O)
-  int NQ, O;
-  float inv_hd;          // 1 / (true heads * true num_hidden)
-};
-
-// tail_forward_tan's chain (without the stash) with the second-order stream: o4 / do4 / d2o4 = the (padded) 32 network outputs and
-// their two derivatives.  Precondition: the first stage of L.atb is resident in ring[P.cur] and visible.
-template <int D, int H, bool BF16>
-DEV void tail_forward_sec(f32x4 (&o4)[2], f32x4 (&do4)[2], f32x4 (&d2o4)[2], const float* yrow, const float* ydrow, const float* y2row,
-                          const EnfLayout& L, const float* cst, Pipe& P, char* ring, int lane, int quad, float inv_hd) {
-  using T = TailCfg<D, H, BF16>;
-  constexpr int KB = T::KB, KBH = T::KBH, NT = T::NT, NTH = T::NTH, HD = T::HD;
-  const float* c_bB = cst, *c_bF1 = cst + HD, *c_bO0 = cst + 2 * HD, *c_bO2 = cst + 2 * HD + D, *c_bO4 = cst + 2 * HD + 2 * D;
-  f32x4 c[NT], dc[NT], d2c[NT];
-  {
-    f32x4 a[NTH], da[NTH], d2a[NTH];
-    Frags<BF16, KBH> FH, dFH, d2FH;
-    load_rows<NTH>(a, yrow, quad);
-    make_frags<BF16, KBH>(FH, a);
-    load_rows<NTH>(da, ydrow, quad);
-    make_frags<BF16, KBH>(dFH, da);
-    load_rows<NTH>(d2a, y2row, quad);
-    make_frags<BF16, KBH>(d2FH, d2a);
-#pragma unroll
-    for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bB, t, quad);
-    panel_gemm3<KBH, NTH, BF16, T::ST_TB>(a, da, d2a, FH, dFH, d2FH, P, ring, (unsigned)L.atb, (unsigned)L.atf1, true, lane);
-    gelu_second<NTH>(a, da, d2a);
-    float mu, rstd;
-    ln_stats<NTH>(a, mu, rstd, inv_hd);
-    ln_apply<NTH>(a, mu, rstd);
-    ln_second<NTH>(da, d2a, a, rstd, inv_hd);
-    make_frags<BF16, KBH>(FH, a);
-    make_frags<BF16, KBH>(dFH, da);
-    make_frags<BF16, KBH>(d2FH, d2a);
-#pragma unroll
-    for (int t = 0; t < NTH; ++t) a[t] = rowvec(c_bF1, t, quad);
-    panel_gemm3<KBH, NTH, BF16, T::ST_O0>(a, da, d2a, FH, dFH, d2FH, P, ring, (unsigned)L.atf1, (unsigned)L.ato0, true, lane);
-    gelu_second<NTH>(a, da, d2a);
-    make_frags<BF16, KBH>(FH, a);
-    make_frags<BF16, KBH>(dFH, da);
-    make_frags<BF16, KBH>(d2FH, d2a);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO0, t, quad);
-    panel_gemm3<KBH, NT, BF16, T::ST_O2>(c, dc, d2c, FH, dFH, d2FH, P, ring, (unsigned)L.ato0, (unsigned)L.ato2, true, lane);
-  }
-  gelu_second<NT>(c, dc, d2c);
-  Frags<BF16, KB> FD, dFD, d2FD;
-  make_frags<BF16, KB>(FD, c);
-  make_frags<BF16, KB>(dFD, dc);
-  make_frags<BF16, KB>(d2FD, d2c);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) c[t] = rowvec(c_bO2, t, quad);
-  panel_gemm3<KB, NT, BF16, T::ST_O4>(c, dc, d2c, FD, dFD, d2FD, P, ring, (unsigned)L.ato2, (unsigned)L.ato4, true, lane);
-  gelu_second<NT>(c, dc, d2c);
-  make_frags<BF16, KB>(FD, c);
-  make_frags<BF16, KB>(dFD, dc);
-  make_frags<BF16, KB>(d2FD, d2c);
-  o4[0] = rowvec(c_bO4, 0, quad);
-  o4[1] = rowvec(c_bO4, 1, quad);
-  panel_gemm3<KB, 2, BF16, 1024>(o4, do4, d2o4, FD, dFD, d2FD, P, ring, (unsigned)L.ato4, NO_STAGE, true, lane);
-}
-
-template <int D, int H, bool BF16>
-__global__ __launch_bounds__(TTH, 1) void enf_tail_second_kernel(TailSecArgs A) {
-  constexpr int HD = H * D;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
-  const int q0 = blockIdx.x * (16 * TW) + wave * 16;
-  const int qi = min(q0 + col, A.NQ - 1);          // tail queries: clamped on load, guarded on store
-  Pipe P;
-  tail_tan_open<D, H, BF16>(P, smem, A.blob, A.L, tid);
-  f32x4 o4[2], do4[2], d2o4[2];
-  tail_forward_sec<D, H, BF16>(o4, do4, d2o4, A.ybar + (size_t)qi * HD, A.ydot + (size_t)qi * HD, A.y2 + (size_t)qi * HD, A.L,
-                               reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, smem, lane, quad, A.inv_hd);
-  if (q0 + col < A.NQ) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = 16 * t + 4 * quad + i;
-        if (o < A.O) {
-          if (A.out) A.out[(size_t)(q0 + col) * A.O + o] = o4[t][i];
-          if (A.tan) A.tan[(size_t)(q0 + col) * A.O + o] = do4[t][i];
-          A.tan2[(size_t)(q0 + col) * A.O + o] = d2o4[t][i];
-        }
-      }
-  }
-}
-
-// ---------------------------------------------------------------- launch and workspace
-int launch_pair_tail_second(const EnfDims& m, const PairSecArgs& PA, const TailSecArgs& TA, hipStream_t st) {
-  return enf_for_shape(m, [&](auto s) {
-    constexpr int D = s.D, H = s.H;
-    constexpr bool BF16 = s.BF16;
-    constexpr int pair_lds = SecSmem<D>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
-    constexpr auto pk = enf_pair_second_kernel<D, H, BF16>;
-    constexpr auto tk = enf_tail_second_kernel<D, H, BF16>;
-    if (!enf_lds_attr<pk>(pair_lds) || !enf_lds_attr<tk>(tail_lds)) return (int)ENF_ELAUNCH;
-    hipLaunchKernelGGL(pk, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B, H), dim3(TTH), pair_lds, st, PA);
-    if (hipGetLastError() != hipSuccess) return (int)ENF_ELAUNCH;
-    hipLaunchKernelGGL(tk, dim3((TA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, TA);
-    return hipGetLastError() == hipSuccess ? 0 : (int)ENF_ELAUNCH;
-  });
+// ---------------------------------------------------------------- launch (launch_pair_tail, enf_tangent_common.h) and workspace
+// one head per grid.z; the tail is the order-2 instantiation of enf_tail_tangent_kernel
+template <class S> bool pair_launch(S, const PairSecArgs& PA, hipStream_t st) {
+  constexpr int lds = SecSmem<S::D>::TOTAL;
+  constexpr auto pk = enf_pair_second_kernel<S::D, S::H, S::BF16>;
+  if (!enf_lds_attr<pk>(lds)) return false;
+  hipLaunchKernelGGL(pk, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B, S::H), dim3(TTH), lds, st, PA);
+  return hipGetLastError() == hipSuccess;
 }
 
 // enf_field_tangent_workspace_bytes' regions at their offsets, then d2 ybar: one buffer serves the plain and the tangent calls too
@@ -644,8 +459,8 @@ extern "C" int enf_field_second_x(const EnfDesc* d, const float* x, int64_t x_bs
   PA.B = m.B; PA.N = m.N; PA.Z = m.Z; PA.dx = m.dx; PA.inv = m.inv; PA.use_window = m.use_window;
   const int zs = enf_latent_splits(m.Z);                 // as many latent splits as there are latents to split, up to one per wave
   PA.qg = TW / (zs < TW ? zs : TW);
-  TailSecArgs TA;
+  TailTanArgs2 TA;
   TA.ybar = PA.ybar; TA.ydot = PA.ydot; TA.y2 = PA.y2; TA.blob = c.blob; TA.L = c.L; TA.out = out; TA.tan = tan; TA.tan2 = tan2;
   TA.NQ = m.B * m.N; TA.O = m.O; TA.inv_hd = 1.0f / (float)(m.Ht * m.Dt);
-  return launch_pair_tail_second(m, PA, TA, c.st);
+  return launch_pair_tail(m, PA, TA, c.st);
 }

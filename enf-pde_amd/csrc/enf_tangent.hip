@@ -14,6 +14,7 @@
 //                                 zero start and no bias); the softmax sums Y, C, L get T = sum e (dy + dl y) and S = sum e dl beside
 //                                 them and  ybar = (Y - C) / L,  d ybar = T / L - (S / L) ybar
 //   enf_tail_tangent_kernel       tail_forward's chain (enf_tail.hip) with the same doubling; writes out (optional) and tan
+//                                 (enf_tangent_common.h: the order-1 instantiations of the kernel enf_second.hip runs at order 2)
 // The same file holds the Gauss-Newton product (enf_gn_product, at the end): prologue tangent and pair kernel as above -- the pair
 // kernel then also stores lse for the backward pair kernel -- and
 //   enf_gn_tail_kernel            the tail's chain with tangents, d out = w tan formed in registers, the tail's backward chain
@@ -22,11 +23,13 @@
 // group sum of the tangent over the wave's query lanes in front of d out.  enf_gn_product_a is the product for a sparse observation
 // operator: the same host sequence with the tail cut open -- the stash form of enf_tail_tangent_kernel, the two products of enf_obs.hip
 // on tan in memory, enf_tail.hip's backward on the stash.
-// There is one copy of each thing the two entry points have in common: the doubled tail chain (tail_forward_tan, which stashes the
-// pre-activations for the Gauss-Newton tail only), the panel product (panel_gemm2, whose one-operand form serves the backward chain),
-// the launcher and its (D, H) dispatch (launch_pair_tail), and the host sequence (tan_call: refusals, dimensions, workspace;
-// tan_launch_prologue; tan_pair_args).  The row moves, the chain's shapes and the constants' load are enf_tail.hip's
-// (enf_tail_common.h).  Not shared: the Gauss-Newton tail's backward chain, a copy of enf_tail_bwd_kernel's (see there).
+// There is one copy of each thing the entry points have in common, here and in enf_second.hip: the tail chain with its derivative
+// streams (tail_forward<.., ORDER, SAVE, ..> of enf_tangent_common.h, which stashes the pre-activations for the Gauss-Newton tails
+// only), the panel product (panel_gemm2, whose one-operand form serves the backward chain), the launcher and its (D, H) dispatch
+// (launch_pair_tail, which takes this file's pair kernel through pair_launch and its Gauss-Newton tails through tail_kernel), and the
+// host sequence (tan_call: refusals, dimensions, workspace; tan_launch_prologue; tan_pair_args).  The row moves, the chain's
+// shapes and the constants' load are enf_tail.hip's (enf_tail_common.h).  Not shared: the Gauss-Newton tail's backward chain, a copy
+// of enf_tail_bwd_kernel's (see there).
 // Register room: at D = 128, H = 2 the accumulators Y and T alone are 128 registers, so these kernels run ONE wave per SIMD
 // (workgroups of 4 waves, a 512-register budget) instead of K2's two.  Every output element is written once, by one lane, in a fixed
 // order of operations: no atomics, the call is bit-reproducible run to run.
@@ -462,56 +465,13 @@ __global__ __launch_bounds__(TTH, 1) void enf_pair_tangent_kernel(PairTanArgs A)
   }
 }
 
-// ---------------------------------------------------------------- (c) the tails
-struct TailTanArgs {
-  const float* ybar; const float* ydot; const char* blob; EnfLayout L;
-  float* out;            // (B N, O) or nullptr
-  float* tan;            // (B N, O)
-  int NQ, O;
-  float inv_hd;          // 1 / (true heads * true num_hidden)
-};
-// The stash form's argument (enf_gn_product_a), appended behind the block the plain form takes, as GnTailArgsG below.
-struct TailTanArgsS : TailTanArgs {
-  float* act;            // (NQ, TailCfg::ACT): the pre-activations and the LayerNorm's mu, rstd, as enf_tail_fwd_kernel<.., SAVE> leaves them
-};
-
-// SAVE (enf_gn_product_a): tail_forward_tan's stash in `act` for enf_tail_bwd_kernel's stash form (enf_tail.hip), which runs behind
-// the two operator products on `tan`; stores tan and no out.  Clamped (duplicate) queries stash the same values, as in the other tails.
-template <int D, int H, bool BF16, bool SAVE = false>
-__global__ __launch_bounds__(TTH, 1) void enf_tail_tangent_kernel(std::conditional_t<SAVE, TailTanArgsS, TailTanArgs> A) {
-  constexpr int HD = H * D;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
-  const int q0 = blockIdx.x * (16 * TW) + wave * 16;
-  const int qi = min(q0 + col, A.NQ - 1);
-  Pipe P;
-  tail_tan_open<D, H, BF16>(P, smem, A.blob, A.L, tid);
-  f32x4 o4[2], do4[2];
-  float* act = nullptr;
-  if constexpr (SAVE) act = A.act + (size_t)qi * TailCfg<D, H, BF16>::ACT;
-  tail_forward_tan<D, H, BF16, SAVE, 1024>(o4, do4, A.ybar + (size_t)qi * HD, A.ydot + (size_t)qi * HD, act, A.L,
-                                           reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, smem, NO_STAGE, lane,
-                                           quad, A.inv_hd);
-  if (q0 + col < A.NQ) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = 16 * t + 4 * quad + i;
-        if (o < A.O) {
-          if constexpr (!SAVE) {
-            if (A.out) A.out[(size_t)(q0 + col) * A.O + o] = o4[t][i];
-          }
-          A.tan[(size_t)(q0 + col) * A.O + o] = do4[t][i];
-        }
-      }
-  }
-}
+// ---------------------------------------------------------------- (c) the tail: enf_tail_tangent_kernel (enf_tangent_common.h)
 
 // ---------------------------------------------------------------- (d) the Gauss-Newton tail (include/enf_hip.h, "Gauss-Newton product")
-// The chain above with the stash, then d out = (w > 0 ? w tan : 0) gs formed in registers where tail_sq_err forms its gradient, then a
-// backward chain on the stash: d ybar and delta for the backward pair kernel.  Neither tan nor d out reaches memory and the forward
-// chain runs once.  One wave per SIMD, the 2-slot ring with four waves issuing, as every kernel of this file.
+// tail_forward's chain (enf_tangent_common.h) at order 1 with the stash, then d out = (w > 0 ? w tan : 0) gs formed in registers where
+// tail_sq_err forms its gradient, then a backward chain on the stash: d ybar and delta for the backward pair kernel.  Neither tan nor
+// d out reaches memory and the forward chain runs once.  One wave per SIMD, the 2-slot ring with four waves issuing, as every kernel
+// of this file.
 // The backward chain MIRRORS enf_tail_bwd_kernel's (enf_tail.hip), line for line, and is kept as a second copy on purpose: that kernel
 // runs another ring (three slots or two, eight waves issuing), and a chain shared between the two would either make the hot tail branch
 // on its caller or -- tried -- change the code generation of all 220 of its backward instantiations.  A change of the
@@ -567,10 +527,11 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(std::conditional_t<
   // ---- forward chain with tangents; the pre-activations this lane stores are re-read by this lane only
   f32x4 g0[2];
   {
-    f32x4 o4[2], do4[2];
-    tail_forward_tan<D, H, BF16, true, T::ST_G4>(o4, do4, yrow, A.ydot + (size_t)qi * HD, act, L,
-                                                 reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P, ring,
-                                                 (unsigned)L.gto4, lane, quad, A.inv_hd);
+    f32x4 o4[2][2];
+    const float* const rows[2] = {yrow, A.ydot + (size_t)qi * HD};
+    tail_forward<D, H, BF16, 1, true, T::ST_G4>(o4, rows, act, L, reinterpret_cast<const float*>(smem + TailTanSmem<D, H>::CONSTS), P,
+                                                ring, (unsigned)L.gto4, lane, quad, A.inv_hd);
+    f32x4 (&do4)[2] = o4[1];
     if constexpr (GRP) {
       // ---- d out = (w > 0 ? q (w obs_tan) : 0) gs,  obs_tan = sum_k q tan over the group: a weight of 0 is a select per observation
 #pragma clang fp contract(off)
@@ -671,28 +632,17 @@ __global__ __launch_bounds__(TTH, 1) void enf_gn_tail_kernel(std::conditional_t<
   if (qvalid) store_rows<NTH>(a, A.dybar + (size_t)qi * HD, quad);
 }
 
-// ---------------------------------------------------------------- launch: the pair kernel, then the entry point's tail
-template <int D, int H, bool BF16> constexpr auto tail_kernel(const TailTanArgs*) { return enf_tail_tangent_kernel<D, H, BF16>; }
-template <int D, int H, bool BF16> constexpr auto tail_kernel(const TailTanArgsS*) { return enf_tail_tangent_kernel<D, H, BF16, true>; }
+// ---------------------------------------------------------------- launch (launch_pair_tail, enf_tangent_common.h): this file's parts
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgs*) { return enf_gn_tail_kernel<D, H, BF16>; }
 template <int D, int H, bool BF16> constexpr auto tail_kernel(const GnTailArgsG*) { return enf_gn_tail_kernel<D, H, BF16, true>; }
 
-// the instantiations: both entry points dispatch here
-template <class TailArgsT>
-int launch_pair_tail(const EnfDims& m, const PairTanArgs& PA, const TailArgsT& TA, hipStream_t st) {
-  return enf_for_shape(m, [&](auto s) {
-    constexpr int D = s.D, H = s.H;
-    constexpr bool BF16 = s.BF16;
-    constexpr int pair_lds = TanSmem<D, H>::TOTAL, tail_lds = TailTanSmem<D, H>::TOTAL;
-    constexpr auto pk0 = enf_pair_tangent_kernel<D, H, BF16, false>, pkx = enf_pair_tangent_kernel<D, H, BF16, true>;
-    constexpr auto tk = tail_kernel<D, H, BF16>((const TailArgsT*)nullptr);
-    if (!(PA.xdot ? enf_lds_attr<pkx>(pair_lds) : enf_lds_attr<pk0>(pair_lds))) return (int)ENF_ELAUNCH;
-    if (!enf_lds_attr<tk>(tail_lds)) return (int)ENF_ELAUNCH;
-    hipLaunchKernelGGL(PA.xdot ? pkx : pk0, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), pair_lds, st, PA);
-    if (hipGetLastError() != hipSuccess) return (int)ENF_ELAUNCH;
-    hipLaunchKernelGGL(tk, dim3((TA.NQ + 16 * TW - 1) / (16 * TW)), dim3(TTH), tail_lds, st, TA);
-    return hipGetLastError() == hipSuccess ? 0 : (int)ENF_ELAUNCH;
-  });
+// the pair kernel with or without the query tangent
+template <class S> bool pair_launch(S, const PairTanArgs& PA, hipStream_t st) {
+  constexpr int lds = TanSmem<S::D, S::H>::TOTAL;
+  constexpr auto pk0 = enf_pair_tangent_kernel<S::D, S::H, S::BF16, false>, pkx = enf_pair_tangent_kernel<S::D, S::H, S::BF16, true>;
+  if (!(PA.xdot ? enf_lds_attr<pkx>(lds) : enf_lds_attr<pk0>(lds))) return false;
+  hipLaunchKernelGGL(PA.xdot ? pkx : pk0, dim3((PA.N + 16 * PA.qg - 1) / (16 * PA.qg), PA.B), dim3(TTH), lds, st, PA);
+  return hipGetLastError() == hipSuccess;
 }
 
 // ---------------------------------------------------------------- the host sequence of both entry points

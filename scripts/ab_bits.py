@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
-"""Bit-for-bit A/B of the small loss / gather / partial-sum kernels between two builds of the library.
+"""Bit-for-bit A/B of two builds of the library on a fixed, seeded list of calls.
 
-  python scripts/ab_bits.py OLD/libenf_hip.so NEW/libenf_hip.so
+  python scripts/ab_bits.py [--calls small|forward_mode] OLD/libenf_hip.so NEW/libenf_hip.so
+
+  small (the default)   the small loss / gather / partial-sum kernels
+  forward_mode          the forward-mode kernels of enf_tangent.hip and enf_second.hip: enf_field_tangent, enf_field_tangent_x,
+                        enf_field_second_x and the three Gauss-Newton products (profiles/README.md, forward_mode_jet_ab.txt)
 
 For each library one fresh child process (ENF_HIP_LIB set, enf_pde_amd/_lib.py) runs the fixed, seeded list of calls below and writes
 every output's raw bytes; this process compares them and prints one line per call.  Exit status 1 if any output differs.
@@ -176,18 +180,110 @@ def child(out_path):
     np.savez(out_path, **res)
 
 
+def child_forward_mode(out_path):
+    """Every compiled (D, H) in both precisions at B = 2, N = 50 (a partly filled query group, a clamped tail) and 70 (a second
+    workgroup), Z = 1, 2, 7 (4, 2, 1 query groups; at Z = 7 one wave is inactive in the last iteration), O = 2; at (64, 2) also O = 32,
+    the seven served invariants, rel_pos at dx = 1 and 3, the window off, x / xdot expanded with stride 0 and the far-logit case of
+    tests/test_gpu_second.py (the softmax's rescale branch).  The products run deterministic (their backward pair kernel adds with
+    float atomics otherwise) on weights with exact zeros.  No atomics anywhere: every output is compared."""
+    import numpy as np
+    import torch
+    from enf_pde_amd.fitting.operators import SparseObservations
+    from oracle import enf_ref_np as R
+    from tests.helpers import make_cfg, make_inputs, build_nef
+
+    dev = torch.device("cuda:0")
+    res = {}
+
+    def tt(v):
+        return torch.tensor(v, dtype=torch.float32, device=dev)
+
+    def put(name, *ts):
+        torch.cuda.synchronize()
+        for i, t in enumerate(t for t in ts if t is not None):
+            res[f"{name} [{i}]"] = t.detach().cpu().contiguous().view(torch.uint8).numpy().copy()
+
+    def run(tag, cfg, B, N, Z, inputs=None, expand=False, products=True):
+        O = cfg["num_out"]
+        prm = R.init_params(3, cfg, jitter=0.1)
+        x, p, a, s = inputs or make_inputs(cfg, B, N, Z, 4)
+        rng = np.random.default_rng(11)
+        xd, dp, da, ds = (rng.standard_normal(v.shape) for v in (x, p, a, s))
+        w, cw, ow = np.abs(rng.standard_normal((B, N))), np.abs(rng.standard_normal((B, N, O))), np.abs(rng.standard_normal((B, N // 2)))
+        w[:, ::4], cw[:, ::3], ow[:, ::5] = 0.0, 0.0, 0.0          # exact zeros
+        qw = np.abs(rng.standard_normal((B, N))) + 0.1
+        G = 4 if N % 4 == 0 else 2                                 # G divides N: 2 at N = 50 and 70, 4 at N = 52 and 72
+        rows = np.repeat(np.arange(N // 2), 3)                     # an operator of M = N / 2 rows, three entries each, across tiles
+        op = SparseObservations.from_coo(rows, (rows * 2 + np.tile([0, 1, 17], N // 2)) % N, rng.standard_normal(rows.size), N // 2, N,
+                                         device=dev)
+        for prec in ("bf16", "f32"):
+            nef = build_nef(cfg, prec)
+            nef.deterministic = True
+            P = nef.load_params(prm, device=dev)
+            tx, txd = tt(x), tt(xd)
+            if expand:
+                tx, txd = tt(x[0])[None].expand(B, -1, -1), tt(xd[0])[None].expand(B, -1, -1)
+            lat = (tt(p), tt(a), tt(s))
+            v = dict(dp=tt(dp), da=tt(da), dwindow=tt(ds))
+            name = f"{tag} B={B} N={N} Z={Z} O={O} {prec}"
+            put(f"tangent {name}", *nef.tangent(P, tx, *lat, **v))
+            put(f"tangent, no out {name}", *nef.tangent(P, tx, *lat, return_out=False, **v))
+            put(f"tangent_x {name}", *nef.tangent(P, tx, *lat, xdot=txd, **v))
+            put(f"tangent_x, xdot alone {name}", *nef.tangent(P, tx, *lat, xdot=txd))
+            put(f"second_x {name}", *nef.second_derivative(P, tx, *lat, txd))
+            put(f"second_x, no out, no tan {name}", *nef.second_derivative(P, tx, *lat, txd, return_out=False, return_first=False))
+            if not products:
+                continue
+            gv = dict(vp=v["dp"], va=v["da"], vwindow=v["dwindow"], grad_scale=3.0)
+            nef.gn_reserve(B, N, Z, dev, op=op)
+            put(f"gn_product, weight {name}", *nef.gn_product(P, tx, *lat, weight=tt(w), **gv))
+            put(f"gn_product, channel weight {name}", *nef.gn_product(P, tx, *lat, channel_weight=tt(cw), **gv))
+            put(f"gn_product_g G={G} {name}", *nef.gn_cell_product(P, tx, *lat, G, qweight=tt(qw),
+                                                                  obs_weight=tt(np.abs(rng.standard_normal((B, N // G))) * (np.arange(N // G) % 3 > 0)), **gv))
+            put(f"gn_product_a {name}", *nef.gn_operator_product(P, tx, *lat, op, obs_weight=tt(ow), **gv))
+
+    for D, H in ((64, 1), (64, 2), (64, 4), (128, 1), (128, 2)):
+        for N in (50, 70):
+            for Z in (1, 2, 7):
+                run(f"rel_pos_periodic D={D} H={H}", make_cfg("rel_pos_periodic", D=D, H=H, C=8, O=2), 2, N, Z)
+    run("rel_pos_periodic D=64 H=2, both output tiles", make_cfg("rel_pos_periodic", D=64, H=2, C=8, O=32), 2, 50, 7)
+    for N in (52, 72):                                             # enf_gn_product_g at G = 4, which has to divide N
+        run("rel_pos_periodic D=64 H=2, G = 4", make_cfg("rel_pos_periodic", D=64, H=2, C=8, O=2), 2, N, 7)
+    for inv in ("latitude_periodic", "polar_periodic", "ponita", "abs_pos", "rel_pos", "norm_rel_pos"):
+        run(f"{inv} D=64 H=2", make_cfg(inv, D=64, H=2, C=8, O=2), 2, 50, 7)
+    for dx in (1, 3):
+        run(f"rel_pos dx={dx} D=64 H=2", make_cfg("rel_pos", D=64, H=2, C=8, O=2, num_in=dx), 2, 50, 7)
+    run("rel_pos_periodic D=64 H=2, no window", make_cfg("rel_pos_periodic", D=64, H=2, C=8, O=2, use_window=False), 2, 50, 7)
+    run("rel_pos_periodic D=64 H=2, x and xdot stride 0", make_cfg("rel_pos_periodic", D=64, H=2, C=8, O=2), 2, 50, 7, expand=True)
+    cfg = make_cfg("rel_pos", D=64, H=2, C=8, O=2)                  # tests/test_gpu_second.py, _far_first_case
+    x, p, a, s = make_inputs(cfg, 3, 50, 7, 1)
+    p[:, :4] = 3.0 + 0.2 * p[:, :4]
+    s[:] = 0.3
+    run("rel_pos D=64 H=2, far latents first", cfg, 3, 50, 7, inputs=(x, p, a, s))
+    np.savez(out_path, **res)
+
+
+CALLS = {"small": child, "forward_mode": child_forward_mode}
+
+
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--child":
-        return child(sys.argv[2])
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    calls = "small"
+    if len(args) >= 2 and args[0] == "--calls":
+        calls, args = args[1], args[2:]
+    if calls not in CALLS:
+        sys.exit(__doc__)
+    if len(args) == 2 and args[0] == "--child":
+        return CALLS[calls](args[1])
+    if len(args) != 2:
         sys.exit(__doc__)
     import numpy as np
     got = []
     with tempfile.TemporaryDirectory() as tmp:
-        for i, path in enumerate(sys.argv[1:3]):
+        for i, path in enumerate(args):
             out = os.path.join(tmp, f"{i}.npz")
             env = dict(os.environ, ENF_HIP_LIB=os.path.abspath(path))
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", out], check=True, env=env, timeout=900)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--calls", calls, "--child", out], check=True, env=env, timeout=900)
             with np.load(out) as z:
                 got.append({k: z[k] for k in z.files})
     old, new = got
